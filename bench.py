@@ -10,9 +10,16 @@ One step = one synthetic ORBIT-shaped task through SingleStepFewShotRecogniser.p
 the support/query frames already resident in HBM (5-way, 5 shots x 8 frames = 200 support frames, 200 query
 frames). Metric (BASELINE.json): query frames/sec per task = M / (t_personalise + t_predict); `value` is the
 whole-job rate over all ranks (tasks are independent units: rank r runs its own tasks, no data-path collective;
-"scaling": "weak"). Rank 0 prints ONE JSON line carrying `roofline` (dominant kernel = the fp32-MFMA
-implicit-GEMM convolution, per-launch HIP events on its stream) and `cpu_baseline` (the PyTorch-CPU oracle of
-the same path timed on this box's host cores, N=1 only, bounded sample).
+"scaling": "weak"). Rank 0 prints ONE JSON line.
+
+A plain run sets up, settles, warms up, times the K steps and prints the line (`value`, `ms_per_step`, frame accuracy,
+host-side diagnostics of the timed steps). `--full` adds every other measurement and check, each in runs of its own after the
+timed steps: the parity gates against the transformers fixture and the CPU oracle, `roofline` (dominant kernel = the
+fp32-MFMA implicit-GEMM convolution, per-launch HIP events on its stream) with every kernel family's floor, `head_roofline`,
+the metric's variants, the LITE block, `cpu_baseline` (the PyTorch-CPU oracle of the same path timed on the host's cores,
+N=1 only, bounded sample), the full-size gates and, with N > 1, the per-rank report and the communication self-checks.
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/logits.npy (float32; LITE: the logits of the
+step's tasks, and DIR/train_loss.npy, float64, the step's summed loss); the inputs depend only on the arguments.
 
 `--mode lite_train` (resnet18 workloads) times the LITE meta-training step instead: one step = one task through
 Learner.train_task_with_lite (per query batch: personalise_with_lite -> predict_a_batch -> scaled CE -> backward)
@@ -768,9 +775,15 @@ def main():
                     help="lite_train: tasks accumulated per rank and optimizer step (reference --tasks_per_batch = this x "
                          "--gpus; BASELINE config 5 = 8 x 8 GPUs = 64 tasks/step). One bench step = one optimizer step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, every other measurement and check (roofline, "
+                                                        "CPU baseline, parity gates, LITE block, variants, multi-GPU checks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy")
     ap.add_argument("--distinct-tasks", type=int, default=4, help="tasks resident in HBM, cycled through")
     ap.add_argument("--batch-size", type=int, default=256, help="clips per extractor call (reference --batch_size)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     backend = os.environ.get("ORBIT_BENCH_BACKEND", "nccl")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -810,8 +823,8 @@ def main():
     fe_name, adapt, size = WORKLOADS[args.workload]
     train = args.mode == "lite_train"
     model = build_model(args.workload, device, args.batch_size, train=train)
-    gate = parity_gate(model, fe_name, device)  # every rank, before anything is timed (on the synthetic checkpoint the
-    #                                             transformers fixture was recorded for)
+    # every rank, before anything is timed (on the synthetic checkpoint the transformers fixture was recorded for)
+    gate = parity_gate(model, fe_name, device) if args.full else None
     ckpt = trained_checkpoint(args.workload)
     template = "blobs" if ckpt else "noise"
     if ckpt:  # the accuracy half of the metric needs weights that carry class signal: the meta-trained checkpoint
@@ -878,6 +891,7 @@ def main():
         loop.label_wait = PendingLabelSet.wait_seconds - waited0  # ... of which blocked on a task's label-set count
         barrier()
         elapsed = time.perf_counter() - t0
+        loop.last = outs[-per_step:]  # what the last step returned (its per_step tasks)
         # frame accuracy (utils/eval_metrics.py:27-36) outside the timed region: five tiny torch launches per step, and
         # their first call in a fresh process loads code objects (that alone cost 2 ms/step in a first run)
         correct = torch.zeros(2, device=device)
@@ -919,12 +933,14 @@ def main():
         run_step.step_losses = []
     elapsed, correct, issued = loop(args.steps)  # the timed region behind `value`
     label_wait = getattr(loop, "label_wait", 0.0)
+    # (copied to the host before any --full leg runs the model again)
+    last_logits = torch.cat(loop.last).float().cpu() if args.dump_outputs else None
     train_losses = None
     if train:  # the loss of every optimizer step of the timed region, summed over the ranks (each task's loss already carries
         #        1 / tasks_per_batch, single-step-learner.py:231): N ranks x T tasks must reproduce 1 rank x N T tasks
         train_losses = torch.stack(run_step.step_losses[:args.steps]).double() if run_step.step_losses else torch.zeros(0)
     value_memoised = None
-    if not train:  # round 4's form: label sets of the resident tasks resolved and memoised before the clock
+    if not train and args.full:  # round 4's form: label sets of the resident tasks resolved and memoised before the clock
         fresh_labels = False
         for t in tasks:
             model.classifier.unique_labels(t["context_labels"], device)
@@ -952,11 +968,11 @@ def main():
         return ms[len(ms) // 2]
 
     timed_mode = getattr(model, "overlap_query", False)  # "auto" (default) | False | 2
-    if timed_mode == 2:
+    if timed_mode == 2 and args.full:
         model.overlap_query = True  # per-task latency: the joined form (both passes of ONE task, head on the caller's stream)
-    median_task_ms = per_task_events(args.steps)
+    median_task_ms = per_task_events(args.steps) if args.full else None
     value_overlap_off = value_overlap_joined = None
-    if bool(timed_mode):
+    if bool(timed_mode) and args.full:
         model.overlap_query = False
         loop(2)
         off_elapsed, _, _ = loop(args.steps)
@@ -967,21 +983,24 @@ def main():
             j_elapsed, _, _ = loop(args.steps)
             value_overlap_joined = NUM_QUERY * args.steps * per_step * world / j_elapsed
         model.overlap_query = timed_mode
-    # roofline leg: the SAME K steps again with one HIP-event pair recorded per conv_igemm launch on its stream
-    # (kept out of the timed region above: recording ~80 events per task costs host time and serialises the queue)
-    overlap, lite_overlap = getattr(model, "overlap_query", False), getattr(model, "lite_overlap", False)
-    lite_query_overlap = getattr(model, "lite_query_overlap", False)
-    model.overlap_query = False  # per-launch durations are only meaningful when the kernels run one at a time
-    model.lite_overlap = model.lite_query_overlap = False  # (LITE: the H-subset and query passes otherwise run beside the cache pass)
-    lib.orbit_prof_set_roofs(6.3e12, PEAK_FP32_MFMA_TFLOPS * 1e12, 64.0 * 1024.0 / 11.06e-9)
-    lib.orbit_prof_enable(1)
-    elapsed_prof, _, _ = loop(args.steps)
-    lib.orbit_prof_enable(0)
-    model.overlap_query, model.lite_overlap, model.lite_query_overlap = overlap, lite_overlap, lite_query_overlap
-    prof_rows = collect_prof(lib)  # (every rank: the records are per process)
+    prof_rows = elapsed_prof = None
+    if args.full:
+        # roofline leg: the SAME K steps again with one HIP-event pair recorded per conv_igemm launch on its stream
+        # (kept out of the timed region above: recording ~80 events per task costs host time and serialises the queue)
+        overlap, lite_overlap = getattr(model, "overlap_query", False), getattr(model, "lite_overlap", False)
+        lite_query_overlap = getattr(model, "lite_query_overlap", False)
+        model.overlap_query = False  # per-launch durations are only meaningful when the kernels run one at a time
+        model.lite_overlap = model.lite_query_overlap = False  # (LITE: the H-subset and query passes otherwise run beside the cache pass)
+        lib.orbit_prof_set_roofs(6.3e12, PEAK_FP32_MFMA_TFLOPS * 1e12, 64.0 * 1024.0 / 11.06e-9)
+        lib.orbit_prof_enable(1)
+        elapsed_prof, _, _ = loop(args.steps)
+        lib.orbit_prof_enable(0)
+        model.overlap_query, model.lite_overlap, model.lite_query_overlap = overlap, lite_overlap, lite_query_overlap
+        prof_rows = collect_prof(lib)  # (every rank: the records are per process)
     per_rank = None
     if dist is not None:
-        per_rank = per_rank_report(rank, world, dist, device, elapsed, issued, args.steps, run_step if train else None)
+        if args.full:
+            per_rank = per_rank_report(rank, world, dist, device, elapsed, issued, args.steps, run_step if train else None)
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
@@ -991,14 +1010,14 @@ def main():
             dist.all_reduce(train_losses)
         torch.cuda.synchronize()
 
-    rccl_ranks = rccl_check(lib, rank, world, backend, dist, device)  # every rank: it is a collective
+    rccl_ranks = rccl_check(lib, rank, world, backend, dist, device) if args.full else None  # every rank: it is a collective
 
     # The P2P / IPC self-check is the LAST collective of the run and runs under a watchdog: it exercises code no multi-GPU node
     # has executed yet (hipIpcOpenMemHandle across devices, peer writes over xGMI) and must not be able to cost the run its line -
     # every timed number and every other exchange is complete by now; if the check does not return within 90 s (or raises) the
     # line says so and the process ends with a hard exit instead of waiting for a communicator that may never drain.
     comm_check, comm_hung = None, False
-    if dist is not None:
+    if dist is not None and args.full:
         import threading
         box = {}
 
@@ -1020,25 +1039,23 @@ def main():
             os._exit(0)  # (a stuck self-check thread holds the communicator: no orderly teardown)
         if dist is not None:
             dist.destroy_process_group()
-    variants, other, total_bytes, n_main, conv_ms, conv_fl = conv_rows_summary(prof_rows)
     if rank != 0:
         leave()
         return
 
-    ms, fl = ctypes.c_double(conv_ms), ctypes.c_double(conv_fl)
-    achieved = fl.value / (ms.value * 1e-3) / 1e12 if ms.value > 0 else 0.0
-    # HBM traffic per launch of the dominant kernel: PMC counters cannot be read from inside this process; the value is
-    # the one tools/collect_profiles.sh measured with rocprofv3 on this same command (committed under profiles/)
-    traffic, traffic_source = pmc_traffic(args.workload + (":lite_train" if train else ""))
-    fam = family_table(prof_rows, args.steps * per_step, 1e3 * elapsed / args.steps / per_step)
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), last_logits.numpy())
+        if train_losses is not None and train_losses.numel():
+            np.save(os.path.join(args.dump_outputs, "train_loss.npy"), train_losses[-1:].cpu().numpy().astype(np.float64))
     macs = model.feature_extractor.macs_per_frame(size, size)
     out = {
         "metric": baseline_metric(),
         "value": NUM_QUERY * args.steps * per_step * world / elapsed,
         "unit": "query frames/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "rccl_ranks": rccl_ranks, "ranks_share_gpus": bool(world > torch.cuda.device_count()),
-        "per_rank": per_rank,
+        "ranks_share_gpus": bool(world > torch.cuda.device_count()),
         "ms_per_step": 1e3 * elapsed / args.steps,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
@@ -1063,19 +1080,14 @@ def main():
         "lite_subset_beside_cache_pass": bool(getattr(model, "lite_overlap", False)) if train else None,
         "lite_query_pass_beside_cache_pass": bool(getattr(model, "lite_query_overlap", False)) if train else None,
         "train_loss_per_step": [float(x) for x in train_losses.cpu()] if train_losses is not None else None,
-        "median_task_ms": median_task_ms,
         "labels": "every timed task carries a label tensor new to the head: its label set is resolved inside the timed region "
                   "(orbit_label_set on a side stream, class count waited for at the head kernel)" if not train else
                   "every task's labels are uploaded from the host as a new tensor before the clock (unpack_task); their label set "
                   "comes from the host copy",
-        # this rank's rate with the label sets of the resident tasks resolved and memoised before the clock (round 4's `value`)
-        "value_memoised_labels": value_memoised,
-        "value_overlap_off": value_overlap_off,
         # the library's default mode. Round 6: the recogniser's default IS the timed mode (overlap_query = "auto": the query pass
         # runs on the second stream when the clips are on the host or carry a readiness mark, which bench's resident clips do) -
         # one number; with ORBIT_BENCH_OVERLAP=2 (pipelined opt-in) the default mode is not what was timed and is not reported
         "value_default_mode": (NUM_QUERY * args.steps * per_step * world / elapsed) if timed_mode in ("auto", False) else None,
-        "value_overlap_joined": value_overlap_joined,
         "overlap_mode": {False: "off", "auto": "library default (auto): query pass on a second stream from the clips' readiness "
                          "event, joined before the head", True: "query pass on a second stream, joined before the head", 2:
                          "pipelined: query pass and head on a second stream, not joined (tasks overlap out of phase)"}[
@@ -1090,158 +1102,175 @@ def main():
         "settling_steps_before_warmup": settling,
         "overlap_query_stream": bool(getattr(model, "overlap_query", False)),
         "extractor_gflop_per_task": 2 * macs * (WAY * SHOTS * FRAMES_PER_SHOT + NUM_QUERY) / 1e9,
-        "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / PEAK_FP32_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
-                     "algorithmic_bytes_per_launch": total_bytes / max(n_main, 1),
-                     "kernel": "the dense-convolution MFMA kernels: orbit::conv_igemm_kernel (all instantiations, incl. the reduce "
-                               "pass of split-K launches) and orbit::pw_rgemm_kernel (pointwise register GEMM)" + (
-                         " + orbit::conv_wgrad_kernel" if train else ""),
-                     "launches": n_main, "avg_launch_us": 1e3 * ms.value / max(n_main, 1),
-                     "algorithmic_hbm_gbs": total_bytes / (ms.value * 1e-3) / 1e9 if ms.value > 0 else None,
-                     # share of the instrumented repeat's own wall time (overlap off there, so the kernels run one at a
-                     # time and the share cannot exceed 1; round 3 divided by the overlapped loop's time)
-                     "kernel_time_share": ms.value / (1e3 * elapsed_prof),
-                     # the whole path against the same roof: every extractor FLOP of the task / the timed step / peak
-                     "whole_task_frac": (2 * macs * (WAY * SHOTS * FRAMES_PER_SHOT + NUM_QUERY) * per_step * world * args.steps
-                                         / elapsed / 1e12 / PEAK_FP32_MFMA_TFLOPS) if not train else None,
-                     "measured": "per-launch HIP events on the launch stream over a repeat of the %d timed steps with the "
-                                 "support/query overlap switched off, so every kernel runs alone (instrumented repeat took "
-                                 "%.1f ms/step)" % (args.steps, 1e3 * elapsed_prof / args.steps),
-                     "variants": variants,  # (the kernels outside this family: `families` below)
-                     # round 6: every kernel family of the task against its own floor
-                     "families": fam["families"], "task_kernel_ms_serial": fam["task_kernel_ms_serial"],
-                     "task_floor_ms": fam["task_floor_ms"], "whole_task_frac_of_floor": fam["whole_task_frac_of_floor"],
-                     "task_floor_simd_ms": fam["task_floor_simd_ms"],
-                     "whole_task_frac_of_floor_simd": fam["whole_task_frac_of_floor_simd"],
-                     "floor_definition": fam["floor_definition"]},
-        # N > 1: which carrier each exchange uses and whether the peer-to-peer inbox path works on this node (one-time check)
-        "multi_gpu": None if dist is None else {
-            "data_path_collective": ("one all-reduce(SUM) of the flat gradient bucket per optimizer step through %s" % (
-                "the direct reduce-scatter + all-gather over P2P inboxes (ORBIT_BENCH_P2P_GRADIENTS=1)"
-                if getattr(getattr(run_step, "bucket", None), "p2p", None) is not None else
-                "torch.distributed all_reduce (backend %s%s)" % (backend, " = RCCL ring over xGMI" if backend == "nccl" else "")))
-            if train else "none (task-parallel inference: independent tasks per rank; frame-accuracy counts all-reduced after "
-                          "the clock)",
-            "c_abi_rccl_allreduce_over_ranks": rccl_ranks, "comm_selfcheck": comm_check},
     }
-    out["head_roofline"] = head_roofline(device)
-    if not train and world == 1:
-        out["variants_of_the_metric"] = metric_variants(model, tasks, device, min(args.steps, 20))
-    bf3 = None
-    if not train and world == 1 and os.environ.get("ORBIT_BENCH_BF3", "0") == "1":  # (frozen opt-in path: off unless asked for)
-        # OPT-IN alternative, never `value`: the 14x14 / 7x7 pointwise convs with both operands split three
-        # ways into bf16 and six products per fp32 product on the bf16 matrix cores (csrc/conv_bf3.hip, option conv_bf3). The
-        # same timed loop, then the serial leg with per-launch events; its logit error against the pinned oracle is added
-        # below from the cpu_baseline task.
-        bf3_prev = lib.orbit_get_option(b"conv_bf3")  # (0 unless ORBIT_CONV_BF3 was set for an A/B run)
-        lib.orbit_set_option(b"conv_bf3", 3)
-        try:
-            loop(3)
-            el3, _, _ = loop(args.steps)
-            ov = getattr(model, "overlap_query", False)
-            model.overlap_query = False
-            loop(2)
-            off3, _, _ = loop(args.steps)
-            lib.orbit_prof_enable(1)
-            loop(args.steps)
-            lib.orbit_prof_enable(0)
-            model.overlap_query = ov
-            ms3, fl3, n3 = ctypes.c_double(), ctypes.c_double(), ctypes.c_long()
-            lib.orbit_prof_collect(ctypes.byref(ms3), ctypes.byref(fl3), ctypes.byref(n3))
-            split_ms = split_fl = conv_ms3 = conv_fl3 = 0.0
-            for i in range(lib.orbit_prof_num_variants()):
-                nm = ctypes.create_string_buffer(48)
-                vms, vfl = ctypes.c_double(), ctypes.c_double()
-                lib.orbit_prof_variant(i, nm, None, ctypes.byref(vms), ctypes.byref(vfl), None)
-                if nm.value.decode().startswith("conv"):  # as `roofline`: the dense conv kernels, not the fused fronts
-                    conv_ms3 += vms.value
-                    conv_fl3 += vfl.value
-                if nm.value.decode().startswith("conv_bf3<"):
-                    split_ms += vms.value
-                    split_fl += vfl.value
-            ms3.value, fl3.value = conv_ms3, conv_fl3
-            bf3 = {"option": "conv_bf3 = 3 (default 0): dense convs + the expand stage of the row-streaming fused fronts", "ms_per_step": 1e3 * el3 / args.steps,
-                   "query_frames_per_s": NUM_QUERY * args.steps * per_step / el3,
-                   "query_frames_per_s_overlap_off": NUM_QUERY * args.steps * per_step / off3,
-                   "conv_tflops_all_dense_conv_launches": fl3.value / ms3.value / 1e9 if ms3.value else None,
-                   "conv_frac_of_fp32_mfma_peak": fl3.value / ms3.value / 1e9 / PEAK_FP32_MFMA_TFLOPS if ms3.value else None,
-                   "split_kernel_share_of_conv_flops": split_fl / fl3.value if fl3.value else None,
-                   "split_kernel_tflops": split_fl / split_ms / 1e9 if split_ms else None,
-                   "note": "fp32 operands split x = x0 + x1 + x2 (bf16, round to nearest, 24 significand bits), products "
-                           "x0w0 + x0w1 + x1w0 + x1w1 + x0w2 + x2w0 on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; the fraction "
-                           "is quoted against the fp32-MFMA peak the default path is priced on (FLOPs of the fp32 problem)"}
-        except Exception as e:  # the experimental leg must never cost the default path its line
-            bf3 = None
-            out["opt_in_conv_bf3_error"] = repr(e)[:300]
-        finally:
-            lib.orbit_prof_enable(0)
-            lib.orbit_set_option(b"conv_bf3", bf3_prev)
-    out["opt_in_conv_bf3"] = bf3
-    out["lite_train"] = None
-    if not train and world == 1 and not HEADS.get(args.workload) and os.environ.get("ORBIT_BENCH_LITE_BLOCK", "1") != "0":
-        try:
-            out["lite_train"] = lite_train_block(args, device, lib, tasks, ckpt)
-        except Exception as e:  # the extra leg must never cost the headline its line
-            out["lite_train"] = {"error": repr(e)[:300]}
-        finally:
-            lib.orbit_prof_enable(0)
-    if not args.no_cpu_baseline and world == 1:
-        sd_before = {k: v.clone() for k, v in model.state_dict().items()} if train else None
-        base, task, want = cpu_baseline(args.workload, model, train=train, way=way, template=template)
-        if train:  # the same LITE step on the same weights and permutation
-            import numpy as np
-            model.load_state_dict(sd_before)
-            np.random.seed(1991)
-        got = run_step(model, {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in task.items()}).cpu()
-        base["max_abs_dlogit_vs_gpu"] = float((got - want).abs().max().item())
-        base["argmax_identical"] = bool(torch.equal(got.argmax(1), want.argmax(1)))
-        # the accuracy half of the metric on this task, both sides (utils/eval_metrics.py:27-36)
-        base["frame_accuracy_gpu"] = float((got.argmax(1) == task["target_labels"]).float().mean())
-        base["frame_accuracy_oracle"] = float((want.argmax(1) == task["target_labels"]).float().mean())
-        out["cpu_baseline"] = base
-        if bf3 is not None:  # the opt-in path's logits on the same task against the same oracle logits
+    if args.full:
+        variants, other, total_bytes, n_main, conv_ms, conv_fl = conv_rows_summary(prof_rows)
+        ms, fl = ctypes.c_double(conv_ms), ctypes.c_double(conv_fl)
+        achieved = fl.value / (ms.value * 1e-3) / 1e12 if ms.value > 0 else 0.0
+        # HBM traffic per launch of the dominant kernel: PMC counters cannot be read from inside this process; the value is
+        # the one tools/collect_profiles.sh measured with rocprofv3 on this same command (committed under profiles/)
+        traffic, traffic_source = pmc_traffic(args.workload + (":lite_train" if train else ""))
+        fam = family_table(prof_rows, args.steps * per_step, 1e3 * elapsed / args.steps / per_step)
+        out.update({
+            "rccl_ranks": rccl_ranks,
+            "per_rank": per_rank,
+            "median_task_ms": median_task_ms,
+            # this rank's rate with the label sets of the resident tasks resolved and memoised before the clock (round 4's `value`)
+            "value_memoised_labels": value_memoised,
+            "value_overlap_off": value_overlap_off,
+            "value_overlap_joined": value_overlap_joined,
+            "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                         "frac": achieved / PEAK_FP32_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
+                         "algorithmic_bytes_per_launch": total_bytes / max(n_main, 1),
+                         "kernel": "the dense-convolution MFMA kernels: orbit::conv_igemm_kernel (all instantiations, incl. the reduce "
+                                   "pass of split-K launches) and orbit::pw_rgemm_kernel (pointwise register GEMM)" + (
+                             " + orbit::conv_wgrad_kernel" if train else ""),
+                         "launches": n_main, "avg_launch_us": 1e3 * ms.value / max(n_main, 1),
+                         "algorithmic_hbm_gbs": total_bytes / (ms.value * 1e-3) / 1e9 if ms.value > 0 else None,
+                         # share of the instrumented repeat's own wall time (overlap off there, so the kernels run one at a
+                         # time and the share cannot exceed 1; round 3 divided by the overlapped loop's time)
+                         "kernel_time_share": ms.value / (1e3 * elapsed_prof),
+                         # the whole path against the same roof: every extractor FLOP of the task / the timed step / peak
+                         "whole_task_frac": (2 * macs * (WAY * SHOTS * FRAMES_PER_SHOT + NUM_QUERY) * per_step * world * args.steps
+                                             / elapsed / 1e12 / PEAK_FP32_MFMA_TFLOPS) if not train else None,
+                         "measured": "per-launch HIP events on the launch stream over a repeat of the %d timed steps with the "
+                                     "support/query overlap switched off, so every kernel runs alone (instrumented repeat took "
+                                     "%.1f ms/step)" % (args.steps, 1e3 * elapsed_prof / args.steps),
+                         "variants": variants,  # (the kernels outside this family: `families` below)
+                         # round 6: every kernel family of the task against its own floor
+                         "families": fam["families"], "task_kernel_ms_serial": fam["task_kernel_ms_serial"],
+                         "task_floor_ms": fam["task_floor_ms"], "whole_task_frac_of_floor": fam["whole_task_frac_of_floor"],
+                         "task_floor_simd_ms": fam["task_floor_simd_ms"],
+                         "whole_task_frac_of_floor_simd": fam["whole_task_frac_of_floor_simd"],
+                         "floor_definition": fam["floor_definition"]},
+            # N > 1: which carrier each exchange uses and whether the peer-to-peer inbox path works on this node (one-time check)
+            "multi_gpu": None if dist is None else {
+                "data_path_collective": ("one all-reduce(SUM) of the flat gradient bucket per optimizer step through %s" % (
+                    "the direct reduce-scatter + all-gather over P2P inboxes (ORBIT_BENCH_P2P_GRADIENTS=1)"
+                    if getattr(getattr(run_step, "bucket", None), "p2p", None) is not None else
+                    "torch.distributed all_reduce (backend %s%s)" % (backend, " = RCCL ring over xGMI" if backend == "nccl" else "")))
+                if train else "none (task-parallel inference: independent tasks per rank; frame-accuracy counts all-reduced after "
+                              "the clock)",
+                "c_abi_rccl_allreduce_over_ranks": rccl_ranks, "comm_selfcheck": comm_check},
+        })
+        out["head_roofline"] = head_roofline(device)
+        if not train and world == 1:
+            out["variants_of_the_metric"] = metric_variants(model, tasks, device, min(args.steps, 20))
+        bf3 = None
+        if not train and world == 1 and os.environ.get("ORBIT_BENCH_BF3", "0") == "1":  # (frozen opt-in path: off unless asked for)
+            # OPT-IN alternative, never `value`: the 14x14 / 7x7 pointwise convs with both operands split three
+            # ways into bf16 and six products per fp32 product on the bf16 matrix cores (csrc/conv_bf3.hip, option conv_bf3). The
+            # same timed loop, then the serial leg with per-launch events; its logit error against the pinned oracle is added
+            # below from the cpu_baseline task.
+            bf3_prev = lib.orbit_get_option(b"conv_bf3")  # (0 unless ORBIT_CONV_BF3 was set for an A/B run)
             lib.orbit_set_option(b"conv_bf3", 3)
             try:
-                got3 = run_step(model, {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in task.items()}).cpu()
+                loop(3)
+                el3, _, _ = loop(args.steps)
+                ov = getattr(model, "overlap_query", False)
+                model.overlap_query = False
+                loop(2)
+                off3, _, _ = loop(args.steps)
+                lib.orbit_prof_enable(1)
+                loop(args.steps)
+                lib.orbit_prof_enable(0)
+                model.overlap_query = ov
+                ms3, fl3, n3 = ctypes.c_double(), ctypes.c_double(), ctypes.c_long()
+                lib.orbit_prof_collect(ctypes.byref(ms3), ctypes.byref(fl3), ctypes.byref(n3))
+                split_ms = split_fl = conv_ms3 = conv_fl3 = 0.0
+                for i in range(lib.orbit_prof_num_variants()):
+                    nm = ctypes.create_string_buffer(48)
+                    vms, vfl = ctypes.c_double(), ctypes.c_double()
+                    lib.orbit_prof_variant(i, nm, None, ctypes.byref(vms), ctypes.byref(vfl), None)
+                    if nm.value.decode().startswith("conv"):  # as `roofline`: the dense conv kernels, not the fused fronts
+                        conv_ms3 += vms.value
+                        conv_fl3 += vfl.value
+                    if nm.value.decode().startswith("conv_bf3<"):
+                        split_ms += vms.value
+                        split_fl += vfl.value
+                ms3.value, fl3.value = conv_ms3, conv_fl3
+                bf3 = {"option": "conv_bf3 = 3 (default 0): dense convs + the expand stage of the row-streaming fused fronts", "ms_per_step": 1e3 * el3 / args.steps,
+                       "query_frames_per_s": NUM_QUERY * args.steps * per_step / el3,
+                       "query_frames_per_s_overlap_off": NUM_QUERY * args.steps * per_step / off3,
+                       "conv_tflops_all_dense_conv_launches": fl3.value / ms3.value / 1e9 if ms3.value else None,
+                       "conv_frac_of_fp32_mfma_peak": fl3.value / ms3.value / 1e9 / PEAK_FP32_MFMA_TFLOPS if ms3.value else None,
+                       "split_kernel_share_of_conv_flops": split_fl / fl3.value if fl3.value else None,
+                       "split_kernel_tflops": split_fl / split_ms / 1e9 if split_ms else None,
+                       "note": "fp32 operands split x = x0 + x1 + x2 (bf16, round to nearest, 24 significand bits), products "
+                               "x0w0 + x0w1 + x1w0 + x1w1 + x0w2 + x2w0 on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; the fraction "
+                               "is quoted against the fp32-MFMA peak the default path is priced on (FLOPs of the fp32 problem)"}
+            except Exception as e:  # the experimental leg must never cost the default path its line
+                bf3 = None
+                out["opt_in_conv_bf3_error"] = repr(e)[:300]
             finally:
+                lib.orbit_prof_enable(0)
                 lib.orbit_set_option(b"conv_bf3", bf3_prev)
-            # the same task twice more under the stream overlap: the path must be repeatable bit for bit (an earlier form of the
-            # kernel was not - an LDS return overwrote operands of queued bf16 MFMAs when another stream's kernels were on the chip)
-            lib.orbit_set_option(b"conv_bf3", 3)
+        out["opt_in_conv_bf3"] = bf3
+        out["lite_train"] = None
+        if not train and world == 1 and not HEADS.get(args.workload) and os.environ.get("ORBIT_BENCH_LITE_BLOCK", "1") != "0":
             try:
-                dev_task = {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in task.items()}
-                bf3["bitwise_repeatable_under_overlap"] = all(bool(torch.equal(run_step(model, dev_task).cpu(), got3)) for _ in range(3))
+                out["lite_train"] = lite_train_block(args, device, lib, tasks, ckpt)
+            except Exception as e:  # the extra leg must never cost the headline its line
+                out["lite_train"] = {"error": repr(e)[:300]}
             finally:
-                lib.orbit_set_option(b"conv_bf3", bf3_prev)
-            bf3["max_abs_dlogit_vs_oracle"] = float((got3 - want).abs().max().item())
-            bf3["argmax_identical_to_oracle"] = bool(torch.equal(got3.argmax(1), want.argmax(1)))
-            bf3["max_abs_dlogit_vs_default_path"] = float((got3 - got).abs().max().item())
-            bf3["default_path_max_abs_dlogit_vs_oracle"] = base["max_abs_dlogit_vs_gpu"]
-        # parity gate (no timing is reported for a path that does not reproduce the reference's logits)
-        if not (base["max_abs_dlogit_vs_gpu"] <= 1e-3 and base["argmax_identical"]):
-            print("PARITY GATE FAILED, no timing reported: " + json.dumps(base), file=sys.stderr)
-            raise SystemExit(3)
-        # the BASELINE configs this command does not time get one full-size HIP-vs-oracle task each in the
-        # default run's record - config 4 (CNAPs FiLM adaptation + resnet18 @224) and config 5's task shape (10-way
-        # efficientnet_b0 @224) - under the same gate. (ORBIT_BENCH_FULL_GATES=0 skips them: A/B runs.)
-        gates = []
-        if (not train and args.workload == "efficientnet_b0_224" and way == WAY
-                and os.environ.get("ORBIT_BENCH_FULL_GATES", "1") != "0"):
-            gates.append(dict(full_size_gate("efficientnet_b0_224", 10, device, base["cores"], template, model=model),
-                              config="BASELINE configs[4] task shape: ProtoNet + efficientnet_b0, 224x224, 10-way"))
-            gates.append(dict(full_size_gate("cnaps_resnet18_224", WAY, device, base["cores"], "noise"),
-                              config="BASELINE configs[3]: CNAPs (set encoder + FiLM generator) + resnet18, 224x224, 5-way"))
-            gates.append({"workload": args.workload, "way": way, "config": "BASELINE configs[2] (this run's cpu_baseline task)",
-                          "max_abs_dlogit_vs_oracle": base["max_abs_dlogit_vs_gpu"], "argmax_identical": base["argmax_identical"]})
-            for g in gates:
-                if not (g["max_abs_dlogit_vs_oracle"] <= 1e-3 and g["argmax_identical"]):
-                    print("PARITY GATE FAILED (full-size task of %s), no timing reported: %s" % (g["config"], json.dumps(g)),
-                          file=sys.stderr)
-                    raise SystemExit(3)
-        out["full_size_parity"] = gates or None
-    else:
-        out["cpu_baseline"] = None
-    out["parity_gate"] = gate
+                lib.orbit_prof_enable(0)
+        if not args.no_cpu_baseline and world == 1:
+            sd_before = {k: v.clone() for k, v in model.state_dict().items()} if train else None
+            base, task, want = cpu_baseline(args.workload, model, train=train, way=way, template=template)
+            if train:  # the same LITE step on the same weights and permutation
+                import numpy as np
+                model.load_state_dict(sd_before)
+                np.random.seed(1991)
+            got = run_step(model, {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in task.items()}).cpu()
+            base["max_abs_dlogit_vs_gpu"] = float((got - want).abs().max().item())
+            base["argmax_identical"] = bool(torch.equal(got.argmax(1), want.argmax(1)))
+            # the accuracy half of the metric on this task, both sides (utils/eval_metrics.py:27-36)
+            base["frame_accuracy_gpu"] = float((got.argmax(1) == task["target_labels"]).float().mean())
+            base["frame_accuracy_oracle"] = float((want.argmax(1) == task["target_labels"]).float().mean())
+            out["cpu_baseline"] = base
+            if bf3 is not None:  # the opt-in path's logits on the same task against the same oracle logits
+                lib.orbit_set_option(b"conv_bf3", 3)
+                try:
+                    got3 = run_step(model, {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in task.items()}).cpu()
+                finally:
+                    lib.orbit_set_option(b"conv_bf3", bf3_prev)
+                # the same task twice more under the stream overlap: the path must be repeatable bit for bit (an earlier form of the
+                # kernel was not - an LDS return overwrote operands of queued bf16 MFMAs when another stream's kernels were on the chip)
+                lib.orbit_set_option(b"conv_bf3", 3)
+                try:
+                    dev_task = {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in task.items()}
+                    bf3["bitwise_repeatable_under_overlap"] = all(bool(torch.equal(run_step(model, dev_task).cpu(), got3)) for _ in range(3))
+                finally:
+                    lib.orbit_set_option(b"conv_bf3", bf3_prev)
+                bf3["max_abs_dlogit_vs_oracle"] = float((got3 - want).abs().max().item())
+                bf3["argmax_identical_to_oracle"] = bool(torch.equal(got3.argmax(1), want.argmax(1)))
+                bf3["max_abs_dlogit_vs_default_path"] = float((got3 - got).abs().max().item())
+                bf3["default_path_max_abs_dlogit_vs_oracle"] = base["max_abs_dlogit_vs_gpu"]
+            # parity gate (no timing is reported for a path that does not reproduce the reference's logits)
+            if not (base["max_abs_dlogit_vs_gpu"] <= 1e-3 and base["argmax_identical"]):
+                print("PARITY GATE FAILED, no timing reported: " + json.dumps(base), file=sys.stderr)
+                raise SystemExit(3)
+            # the BASELINE configs this command does not time get one full-size HIP-vs-oracle task each in the
+            # default run's record - config 4 (CNAPs FiLM adaptation + resnet18 @224) and config 5's task shape (10-way
+            # efficientnet_b0 @224) - under the same gate. (ORBIT_BENCH_FULL_GATES=0 skips them: A/B runs.)
+            gates = []
+            if (not train and args.workload == "efficientnet_b0_224" and way == WAY
+                    and os.environ.get("ORBIT_BENCH_FULL_GATES", "1") != "0"):
+                gates.append(dict(full_size_gate("efficientnet_b0_224", 10, device, base["cores"], template, model=model),
+                                  config="BASELINE configs[4] task shape: ProtoNet + efficientnet_b0, 224x224, 10-way"))
+                gates.append(dict(full_size_gate("cnaps_resnet18_224", WAY, device, base["cores"], "noise"),
+                                  config="BASELINE configs[3]: CNAPs (set encoder + FiLM generator) + resnet18, 224x224, 5-way"))
+                gates.append({"workload": args.workload, "way": way, "config": "BASELINE configs[2] (this run's cpu_baseline task)",
+                              "max_abs_dlogit_vs_oracle": base["max_abs_dlogit_vs_gpu"], "argmax_identical": base["argmax_identical"]})
+                for g in gates:
+                    if not (g["max_abs_dlogit_vs_oracle"] <= 1e-3 and g["argmax_identical"]):
+                        print("PARITY GATE FAILED (full-size task of %s), no timing reported: %s" % (g["config"], json.dumps(g)),
+                              file=sys.stderr)
+                        raise SystemExit(3)
+            out["full_size_parity"] = gates or None
+        else:
+            out["cpu_baseline"] = None
+        out["parity_gate"] = gate
     print(json.dumps(out))
     leave()
 

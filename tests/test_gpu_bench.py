@@ -1,10 +1,12 @@
-"""bench.py's output contract on a real GPU: ONE JSON line with BASELINE.json's metric on the headline workload, the
-`roofline` block of the dominant kernel and the `cpu_baseline` block of the oracle, behind the parity gates."""
+"""bench.py's output contract on a real GPU: ONE JSON line with BASELINE.json's metric on the headline workload; with
+`--full` also the `roofline` block of the dominant kernel and the `cpu_baseline` block of the oracle, behind the parity
+gates."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +29,7 @@ def _run(args, timeout=900):
 
 
 def test_bench_line_contract():
-    d = _run(["--steps", "3", "--warmup", "1"])
+    d = _run(["--full", "--steps", "3", "--warmup", "1"])
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert d["metric"] == base["metric"] and d["unit"] == "query frames/s"
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
@@ -82,7 +84,7 @@ def test_bench_launches_its_own_ranks():
     env = dict(os.environ, ORBIT_BENCH_BACKEND="gloo", **FAST)
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1
@@ -103,11 +105,36 @@ def test_bench_launches_its_own_ranks():
         assert out.returncode != 0 and not [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
 
 
-def test_bench_other_modes_run():
+def test_bench_other_modes_run(tmp_path):
     d = _run(["--workload", "resnet18_84", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
     assert "resnet18" in d["config"]["workload"] and d["value"] > 0 and "cpu_baseline" not in d or d["cpu_baseline"] is None
-    t = _run(["--mode", "lite_train", "--workload", "resnet18_84", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    t = _run(["--mode", "lite_train", "--workload", "resnet18_84", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+              "--dump-outputs", str(tmp_path)])
     assert "LITE" in t["config"]["workload"] and t["ms_per_step"] > 0
+    # the last optimizer step's logits (one task, 200 query frames, 5-way) and its summed loss, as the line reports it
+    logits, loss = np.load(str(tmp_path / "logits.npy")), np.load(str(tmp_path / "train_loss.npy"))
+    assert logits.dtype == np.float32 and logits.shape == (200, 5) and np.isfinite(logits).all()
+    assert loss.dtype == np.float64 and loss.shape == (1,) and abs(loss[0] - t["train_loss_per_step"][-1]) <= 1e-12 * abs(loss[0])
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times the K steps and prints the headline line without the extra legs; --dump-outputs holds
+    the logits of the last timed step. Two runs whose last step is the same resident task (task (K - 1) % 4) dump the same
+    logits whatever K and W were: the inputs depend only on the arguments, and a task's logits only on the task."""
+    a = _run(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")])
+    b = _run(["--steps", "7", "--warmup", "0", "--dump-outputs", str(tmp_path / "b")])
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    for d, steps, warmup in ((a, 3, 1), (b, 7, 0)):
+        assert d["metric"] == base["metric"] and d["unit"] == "query frames/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and d["steps"] == steps and d["warmup"] == warmup and d["n_gpus"] == 1
+        assert abs(d["value"] - 200.0 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert 0.0 <= d["frame_accuracy"] <= 1.0
+        for key in ("roofline", "cpu_baseline", "lite_train", "head_roofline", "variants_of_the_metric", "parity_gate",
+                    "full_size_parity", "value_memoised_labels", "median_task_ms"):
+            assert key not in d, key
+    la, lb = np.load(str(tmp_path / "a" / "logits.npy")), np.load(str(tmp_path / "b" / "logits.npy"))
+    assert la.dtype == np.float32 and la.shape == (200, 5) and np.isfinite(la).all()
+    assert np.abs(la - lb).max() <= 1e-5, np.abs(la - lb).max()
 
 
 def test_bench_config5_command_contract():
@@ -137,7 +164,7 @@ def test_bench_training_form_two_ranks_reproduces_one_rank():
     optimizer step agrees - the second step's only if the first step's all-reduced gradients moved the parameters alike. The
     line also carries the per-rank report a SCALE record needs (bucket bytes, all-reduce time by carrier)."""
     common = ["--mode", "lite_train", "--workload", "resnet18_84", "--steps", "3", "--warmup", "0", "--no-cpu-baseline",
-              "--distinct-tasks", "6"]  # (tasks 0 .. 5 in windows of two on either run)
+              "--distinct-tasks", "6", "--full"]  # (tasks 0 .. 5 in windows of two on either run)
     env = dict(os.environ, ORBIT_BENCH_BACKEND="gloo", ORBIT_DIST_BACKEND="gloo", OMP_NUM_THREADS="8", **FAST)
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
     outs = []

@@ -1,7 +1,7 @@
 # whole-task A/B of runtime options (GPU box): bash tools/ab_opts.sh <outdir> "ENV=V ENV2=V2" "..." ...   (two rounds, interleaved)
 O=$1; shift; mkdir -p $O
 i=0; for cfg in "$@"; do i=$((i+1)); echo "$cfg" > $O/cfg_$i.txt; done
-for rep in 1 2; do i=0; for cfg in "$@"; do i=$((i+1)); env $cfg python bench.py --no-cpu-baseline --steps 40 --warmup 10 > $O/b_${i}_$rep.json 2>$O/b_${i}_$rep.err; done; done
+for rep in 1 2; do i=0; for cfg in "$@"; do i=$((i+1)); env $cfg python bench.py --full --no-cpu-baseline --steps 40 --warmup 10 > $O/b_${i}_$rep.json 2>$O/b_${i}_$rep.err; done; done
 python - "$O" "$#" <<'PY'
 import json, sys
 o, n = sys.argv[1], int(sys.argv[2])

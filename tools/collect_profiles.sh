@@ -17,19 +17,19 @@ export ORBIT_BENCH_OVERLAP=0 ORBIT_LITE_OVERLAP=0  # (LITE: the H-subset pass se
 export ORBIT_BENCH_LITE_BLOCK=0
 for W in efficientnet_b0_224 resnet18_84 ${EXTRA_WORKLOADS:-}; do
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$W -- \
-      python $R/bench.py --workload $W --steps 10 --warmup 3 --no-cpu-baseline > $O/${TAG}_bench_$W.json 2> $O/${TAG}_bench_$W.err
+      python $R/bench.py --full --workload $W --steps 10 --warmup 3 --no-cpu-baseline > $O/${TAG}_bench_$W.json 2> $O/${TAG}_bench_$W.err
   cp $(ls $O/stats_$W/*/*kernel_stats.csv | head -1) $O/${TAG}_kernel_stats_$W.csv
 done
 # the LITE meta-training step (forward + backward + optimizer) of the headline extractor
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_lite -- \
-    python $R/bench.py --mode lite_train --steps 10 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_lite_train_profiled.json 2> $O/${TAG}_bench_lite.err
+    python $R/bench.py --full --mode lite_train --steps 10 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_lite_train_profiled.json 2> $O/${TAG}_bench_lite.err
 cp $(ls $O/stats_lite/*/*kernel_stats.csv | head -1) $O/${TAG}_kernel_stats_lite_train_efficientnet_b0_224.csv
 traffic() {  # traffic <name> <workload tag> <kernel substrings, |-separated> <bench.py args...>
   local NAME=$1 WL=$2 KERN=$3; shift 3
   for C in FETCH_SIZE WRITE_SIZE; do
     # (counter collection serialises every dispatch: no settling chunks, eager launches, two steps - a LITE step is ~900 launches)
     ORBIT_BENCH_SETTLE=0 ORBIT_TRAIN_GRAPH=0 ORBIT_GRAPH=0 timeout 600 rocprofv3 --pmc $C --output-format csv -d $O/pmc_${NAME}_$C -- \
-        python $R/bench.py "$@" --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $O/${TAG}_pmc_${NAME}_$C.err
+        python $R/bench.py --full "$@" --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2> $O/${TAG}_pmc_${NAME}_$C.err
     F=$(ls $O/pmc_${NAME}_$C/*/*counter_collection.csv | head -1)
     python - "$F" "$C" > $O/${TAG}_pmc_${NAME}_${C}_summary.txt <<'PY'
 import csv, sys, collections

@@ -6,12 +6,12 @@ cd $R
 python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1; tail -2 $O/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 for w in efficientnet_b0_224 resnet18_84 resnet18_224 cnaps_resnet18_224; do
-  python bench.py --workload $w > $O/full_$w.json 2> $O/full_$w.err
-  python bench.py --mode lite_train --workload $w > $O/lite_$w.json 2> $O/lite_$w.err
+  python bench.py --full --workload $w > $O/full_$w.json 2> $O/full_$w.err
+  python bench.py --full --mode lite_train --workload $w > $O/lite_$w.json 2> $O/lite_$w.err
 done
-for w in cnaps_versa_resnet18_224 simple_cnaps_resnet18_224; do python bench.py --workload $w --no-cpu-baseline > $O/full_$w.json 2> $O/full_$w.err; done
-python bench.py --workload efficientnet_b0_224 --way 10 --no-cpu-baseline > $O/full_efficientnet_b0_224_10way.json 2> $O/full_10way.err
-python bench.py --mode lite_train --workload efficientnet_b0_224 --way 10 --tasks-per-rank 8 --steps 10 --warmup 3 --no-cpu-baseline > $O/lite_config5_10way_8tasks.json 2> $O/lite_config5.err
+for w in cnaps_versa_resnet18_224 simple_cnaps_resnet18_224; do python bench.py --full --workload $w --no-cpu-baseline > $O/full_$w.json 2> $O/full_$w.err; done
+python bench.py --full --workload efficientnet_b0_224 --way 10 --no-cpu-baseline > $O/full_efficientnet_b0_224_10way.json 2> $O/full_10way.err
+python bench.py --full --mode lite_train --workload efficientnet_b0_224 --way 10 --tasks-per-rank 8 --steps 10 --warmup 3 --no-cpu-baseline > $O/lite_config5_10way_8tasks.json 2> $O/lite_config5.err
 python - "$O" <<'PY'
 import json, glob, os, sys
 for f in sorted(glob.glob(sys.argv[1] + '/*.json')):

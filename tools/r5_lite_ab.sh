@@ -3,7 +3,7 @@ O=${1:-gpurun_out/r5d}; shift; mkdir -p $O
 for rep in 1 2; do
   for cfg in "$@"; do
     tag=$(echo "$cfg" | tr ' =' '__')
-    env $cfg timeout 300 python bench.py --mode lite_train --no-cpu-baseline --steps 30 --warmup 10 > $O/lite_${tag}_$rep.json 2> $O/lite_${tag}_$rep.err
+    env $cfg timeout 300 python bench.py --full --mode lite_train --no-cpu-baseline --steps 30 --warmup 10 > $O/lite_${tag}_$rep.json 2> $O/lite_${tag}_$rep.err
   done
 done
 R=${GRAFT_REPO_ROOT:-$(pwd)}
