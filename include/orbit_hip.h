@@ -100,6 +100,9 @@ int orbit_device_count(void);
  *                   more than 256 channels (EfficientNet-B0's 1152 -> 320 at 7x7; a rule on the layer, not on the batch, so a
  *                   frame's bits do not depend on the batch it arrives in); 0 = never; 2 = every conv it supports. Read at plan
  *                   creation (which filters get a fragment-ordered copy) and at launch
+ *                   The same switch (!= 0) lets the streaming gated projection (csrc/pw_stream.hip) serve EfficientNet's narrow
+ *                   projections (32 -> 16, 96 / 144 -> 24, 144 -> 40; H * W % 16 == 0) with the squeeze-excite gate computed in its prologue,
+ *                   instead of a se_gate2 launch + the LDS-tiled conv; 0 = that pair
  *   "conv_bf3"      0 (default) = every product is an fp32 x fp32 MFMA. OPT-IN bits: 1 = dense convs with Cin % 16 == 0,
  *                   Cin >= 64, Cout >= 40 split both operands three ways into bf16 and sum six of the nine bf16 x bf16 products on
  *                   v_mfma_f32_32x32x16_bf16 (csrc/conv_bf3.hip); 2 = the expand GEMM of the row-streaming fused fronts does the
@@ -234,6 +237,15 @@ int orbit_op_conv2d(const float* x, int x_nchw, const float* w, float* y,
                     int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                     int pad_top, int pad_left, int Ho, int Wo, int act, int pool2,
                     orbit_stream_t stream);
+/* Gated 1x1 projection with its squeeze-excite gate (no activation):
+ *   gate = sigmoid(W2 silu(W1 (sum over chunks of partial[b][chunk]) / (H*W) + b1) + b2),
+ *   y = conv1x1(x * gate) * scale + shift (+ residual).
+ * partial [B][chunks][Cin]; w1 [R][Cin]; w2t = W2 transposed [R][Cin]; gate_out [B][Cin] or NULL. Option conv_rgemm != 0 and
+ * orbit_pw_stream_supported(): one kernel that computes the gate in its prologue; otherwise se_gate2 + the conv kernel. */
+int orbit_op_pw_stream(const float* x, const float* w, const float* scale, const float* shift, const float* residual,
+                       const float* partial, int chunks, const float* w1, const float* b1, const float* w2t, const float* b2,
+                       int R, float* y, float* gate_out, int B, int H, int W, int Cin, int Cout, orbit_stream_t stream);
+int orbit_pw_stream_supported(int Cin, int Cout, int H, int W);
 /* depthwise KxK conv, NHWC, w torch [C][1][K][K]; y = act(dw(x)*scale+shift) */
 int orbit_op_dwconv2d(const float* x, const float* w, float* y, const float* scale, const float* shift,
                       int B, int H, int W, int C, int K, int stride, int pad_top, int pad_left,

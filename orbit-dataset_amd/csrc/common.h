@@ -120,6 +120,24 @@ bool conv_bf3_supported(const ConvDesc& d);
 int launch_conv_bf3(const ConvDesc& d, hipStream_t s);
 bool pw_rgemm_preferred(const ConvDesc& d);  // where it measured faster than the LDS-tiled kernel (conv_rgemm = 1)
 int launch_pw_rgemm(const ConvDesc& d, hipStream_t s);
+// narrow gated pointwise projections with the squeeze-excite gate computed in the prologue (csrc/pw_stream.hip; option
+// pw_stream): y = scale * conv1x1(x * gate(partial)) + shift (+ residual), no activation
+struct PwStreamDesc {
+    const float* x;
+    const float* w_packed;  // conv_pack_weights layout
+    float* y;
+    const float* scale;
+    const float* shift;
+    const float* residual = nullptr;
+    const float* partial;   // squeeze-excite pooling partials [B][chunks][Cin]
+    int chunks, se_hw;
+    const float *w1, *b1, *w2t, *b2;  // gate MLP: W1 [R][Cin], b1 [R], W2 transposed [R][Cin], b2 [Cin]
+    int R;
+    float* gate_out = nullptr;  // [B][Cin] (tests) or nullptr
+    int B, H, W, Cin, Cout;
+};
+bool pw_stream_supported(int Cin, int Cout, int H, int W);  // a function of the layer only
+int launch_pw_stream(const PwStreamDesc& d, hipStream_t s);
 bool conv_prof_enabled();
 // per-launch HIP-event records of orbit_prof_* (no-ops returning -1 while profiling is off)
 int prof_start(const char* name, double flops, double bytes, hipStream_t s, double silu = 0.0);  // silu: SiLU evaluations of the launch

@@ -566,6 +566,16 @@ int orbit_extractor_forward(orbit_extractor_t* fe, const float* frames, int B, c
     return ORBIT_OK;
 }
 
+// the squeeze-excite op at index i is computed by its consumer, the gated projection right after it (csrc/pw_stream.hip):
+// a function of the layer (and of option conv_rgemm, != 0: the register-GEMM family), never of the batch
+static bool se_in_projection(const orbit_extractor_t* fe, size_t i) {
+    if (!get_option("conv_rgemm") || i + 1 >= fe->ops.size() || fe->ops[i].kind != OP_SE) return false;
+    const Op& c = fe->ops[i + 1];
+    return c.kind == OP_CONV && c.use_gate && c.Cin == fe->ops[i].Cin && c.KH == 1 && c.KW == 1 && c.stride == 1 &&
+           c.pad_t == 0 && c.pad_l == 0 && !c.x_nchw && !c.pool2 && c.act == ORBIT_ACT_NONE && c.bn >= 0 &&
+           c.Ho == c.H && c.Wo == c.W && pw_stream_supported(c.Cin, c.Cout, c.H, c.W);
+}
+
 static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const float* film_gamma, const float* film_beta,
                     float* feats, void* workspace, hipStream_t s) {
     const WsLayout L = ws_layout(fe, B);
@@ -599,6 +609,19 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                     rc = launch_stem_direct(buf(o.in), fe->d_pool + fe->params[o.weight].off, scale + fe->bns[o.bn].fold_off,
                                             shift + fe->bns[o.bn].fold_off, buf(o.out), B, o.H, o.W, o.pad_t, o.pad_l, o.Ho,
                                             o.Wo, s);
+                    break;
+                }
+                if (oi > 0 && se_in_projection(fe, oi - 1)) {
+                    const Op& se = fe->ops[oi - 1];
+                    PwStreamDesc d;
+                    d.x = buf(o.in), d.w_packed = fe->d_packed + o.packed_off, d.y = buf(o.out);
+                    d.scale = scale + fe->bns[o.bn].fold_off, d.shift = shift + fe->bns[o.bn].fold_off;
+                    d.residual = o.res >= 0 ? buf(o.res) : nullptr;
+                    d.partial = buf(101), d.chunks = se.se_chunks, d.se_hw = se.se_hw;
+                    d.w1 = fe->d_pool + fe->params[se.se_w1].off, d.b1 = fe->d_pool + fe->params[se.se_b1].off;
+                    d.w2t = fe->d_packed + se.packed_off, d.b2 = fe->d_pool + fe->params[se.se_b2].off, d.R = se.R;
+                    d.B = B, d.H = o.H, d.W = o.W, d.Cin = o.Cin, d.Cout = o.Cout;
+                    rc = launch_pw_stream(d, s);
                     break;
                 }
                 ConvDesc d;
@@ -642,6 +665,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                 rc = launch_avgpool(buf(o.in), buf(o.out), B, o.H * o.W, o.Cin, s);
                 break;
             case OP_SE:
+                if (se_in_projection(fe, oi)) break;  // the projection computes the gate in its prologue
                 rc = launch_se_gate2(buf(101), o.se_chunks, o.se_hw, fe->d_pool + fe->params[o.se_w1].off,
                                      fe->d_pool + fe->params[o.se_b1].off, fe->d_packed + o.packed_off,
                                      fe->d_pool + fe->params[o.se_b2].off, buf(102), B, o.Cin, o.R, s);

@@ -42,7 +42,7 @@ static Option g_options[] = {
     {"conv_tile", "ORBIT_CONV_TILE", 0, false},      // 0 heuristic; 3 = 64x64, 4 = 128x32, 6 = 32x32 with K split over the waves
     {"conv_bk", "ORBIT_CONV_BK", 0, false},          // 0 = widest K-tile that divides Cin; 8 / 16 / 32 caps it
     {"conv_splitk", "ORBIT_CONV_SPLITK", 1, false},  // split-K over blocks for short, long-K layers
-    {"conv_rgemm", "ORBIT_CONV_RGEMM", 1, false},    // pointwise register GEMM: 0 never, 1 where measured faster, 2 wherever supported
+    {"conv_rgemm", "ORBIT_CONV_RGEMM", 1, false},    // pointwise register GEMMs (pw_rgemm, pw_stream): 0 never, 1 where measured faster, 2 wherever supported
     {"conv_bf3", "ORBIT_CONV_BF3", 0, false},        // OPT-IN bf16 x 3 split (bit 1 dense convs, bit 2 fused-front expands); never in `value`
     // depthwise kernel families: 1 = where measured faster (default), 0 = never, 2 = wherever it fits
     {"dw_window", "ORBIT_DW_WINDOW", 1, false},
