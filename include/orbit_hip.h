@@ -18,6 +18,9 @@
  *   orbit_set_mean                       model/set_encoders.py:61-75 (SetEncoder.aggregate 'mean')
  *   orbit_filmgen_*                      model/feature_adapters.py:36-78 (FilmParameterGenerator),
  *                                        model/mlps.py:52-63 (DenseBlock)
+ *   orbit_vit_*                          model/feature_extractors.py:49-63 (vit_s_32, vit_b_32, vit_b_32_clip: timm
+ *                                        0.6.12 VisionTransformer, num_classes=0), inference only; FiLM on the
+ *                                        LayerNorms model/film.py:57-66
  *   orbit_op_*                           single operators (conv/pool/depthwise/SE) exposed for parity tests
  *
  * Conventions
@@ -41,6 +44,7 @@ extern "C" {
 
 typedef struct orbit_extractor orbit_extractor_t;
 typedef struct orbit_filmgen orbit_filmgen_t;
+typedef struct orbit_vit orbit_vit_t;
 typedef void* orbit_stream_t; /* hipStream_t */
 
 #define ORBIT_OK 0
@@ -208,6 +212,41 @@ double orbit_extractor_macs_per_frame(const orbit_extractor_t* fe);
 int orbit_extractor_forward(orbit_extractor_t* fe, const float* frames, int B,
                             const float* film_gamma, const float* film_beta,
                             float* feats, void* workspace, size_t workspace_bytes, orbit_stream_t stream);
+
+/* ---- vision-transformer feature extractors (csrc/vit.hip) --------------------------------------- */
+/* Reference model/feature_extractors.py:49-63 builds timm 0.6.12 `vit_small_patch32_224_in21k` ("vit_s_32"),
+ * `vit_base_patch32_224_in21k` ("vit_b_32") and `vit_base_patch32_224_clip_laion2b` ("vit_b_32_clip") with num_classes=0;
+ * the feature is LN_final(tokens)[:, 0] (timm forward_head, global_pool='token'). Same semantics as the orbit_extractor_*
+ * family (orbit_extractor_create rejects these names). H = W = 224 only (reference utils/args.py: --frame_size 224 for
+ * these backbones; the position table is fixed). Creation and enumeration do not touch the device. Inference only: the
+ * reference's LITE / fine-tuning backward through a ViT is not provided. */
+int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out);
+void orbit_vit_destroy(orbit_vit_t* v);
+/* timm state_dict keys in timm's order: cls_token, pos_embed, patch_embed.proj.{weight,bias (not CLIP)}, norm_pre.* (CLIP),
+ * blocks.{i}.{norm1, attn.qkv, attn.proj, norm2, mlp.fc1, mlp.fc2}.{weight,bias}, norm.{weight,bias} */
+int orbit_vit_num_params(const orbit_vit_t* v);
+const char* orbit_vit_param_name(const orbit_vit_t* v, int i);
+size_t orbit_vit_param_numel(const orbit_vit_t* v, int i);
+/* as orbit_extractor_load / _load_async / _load_all_async (torch layouts, fp32) */
+int orbit_vit_load(orbit_vit_t* v, const char* key, const float* data, size_t numel);
+int orbit_vit_load_async(orbit_vit_t* v, const char* key, const float* device_data, size_t numel, orbit_stream_t stream);
+int orbit_vit_load_all_async(orbit_vit_t* v, const float* const* device_ptrs, int n, orbit_stream_t stream);
+/* checks that every parameter was loaded (the kernels read the torch layouts: nothing is repacked); forward fails before it */
+int orbit_vit_finalize(orbit_vit_t* v, orbit_stream_t stream);
+int orbit_vit_output_size(const orbit_vit_t* v);
+/* FiLM slots (reference model/film.py:57-66: every LayerNorm named norm / norm1 / norm2, not norm_pre): 25 in module order
+ * blocks.0.norm1, blocks.0.norm2, ..., blocks.11.norm2, norm; D channels each; film_size = 25 D */
+int orbit_vit_film_slots(const orbit_vit_t* v);
+int orbit_vit_film_slot_channels(const orbit_vit_t* v, int slot);
+const char* orbit_vit_film_slot_name(const orbit_vit_t* v, int slot);
+int orbit_vit_film_size(const orbit_vit_t* v);
+size_t orbit_vit_workspace_bytes(const orbit_vit_t* v, int B);
+/* patch embedding + the four linear layers + QK^T and PV, per frame */
+double orbit_vit_macs_per_frame(const orbit_vit_t* v);
+/* frames [B][3][224][224] NCHW fp32 -> feats [B][D] (model/few_shot_recognisers.py:99-153 with a ViT extractor).
+ * film_gamma / film_beta: NULL, or the LayerNorm weight / bias of every FiLM slot concatenated in slot order. */
+int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
+                      float* feats, void* workspace, size_t workspace_bytes, orbit_stream_t stream);
 
 /* ---- FiLM parameter generator ------------------------------------------------------------------ */
 /* n_gen generators (sorted FiLM-name order). Generator i: Linear(z_dim,hid) -> LayerNorm(hid) -> ReLU ->

@@ -46,6 +46,23 @@ _SIGNATURES = {
     "orbit_extractor_workspace_bytes": (c_size_t, [P, c_int]),
     "orbit_extractor_macs_per_frame": (c_double, [P]),
     "orbit_extractor_forward": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P]),
+    "orbit_vit_create": (c_int, [c_char_p, c_int, c_int, POINTER(c_void_p)]),
+    "orbit_vit_destroy": (None, [P]),
+    "orbit_vit_num_params": (c_int, [P]),
+    "orbit_vit_param_name": (c_char_p, [P, c_int]),
+    "orbit_vit_param_numel": (c_size_t, [P, c_int]),
+    "orbit_vit_load": (c_int, [P, c_char_p, P, c_size_t]),
+    "orbit_vit_load_async": (c_int, [P, c_char_p, P, c_size_t, P]),
+    "orbit_vit_load_all_async": (c_int, [P, P, c_int, P]),
+    "orbit_vit_finalize": (c_int, [P, P]),
+    "orbit_vit_output_size": (c_int, [P]),
+    "orbit_vit_film_slots": (c_int, [P]),
+    "orbit_vit_film_slot_channels": (c_int, [P, c_int]),
+    "orbit_vit_film_slot_name": (c_char_p, [P, c_int]),
+    "orbit_vit_film_size": (c_int, [P]),
+    "orbit_vit_workspace_bytes": (c_size_t, [P, c_int]),
+    "orbit_vit_macs_per_frame": (c_double, [P]),
+    "orbit_vit_forward": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P]),
     "orbit_filmgen_create": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                      POINTER(c_void_p)]),
     "orbit_filmgen_destroy": (None, [P]),

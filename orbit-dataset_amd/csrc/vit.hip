@@ -1,0 +1,555 @@
+// Vision-transformer feature extractors (timm 0.6.12 `vit_small_patch32_224_in21k`, `vit_base_patch32_224_in21k`,
+// `vit_base_patch32_224_clip_laion2b`, built with num_classes=0: reference model/feature_extractors.py:49-63), inference only.
+//
+// One forward, fp32 throughout (reference: timm VisionTransformer.forward_features + forward_head with global_pool='token'):
+//   tokens[b][0]   = cls_token + pos_embed[0]
+//   tokens[b][1+p] = patch_embed(frames)[b][p] + pos_embed[1+p]          32x32 stride-32 conv, p = 0..48 (224x224 frames)
+//   (CLIP) tokens  = LayerNorm_pre(tokens)
+//   12 x { x += proj(attn(LN1(x)));  x += fc2(GELU_erf(fc1(LN2(x)))) }
+//   feature        = LN_final(x)[:, 0]
+// Kernels:
+//   vit_gemm_kernel      y = x W^T + b (+ erf-GELU | + residual) on v_mfma_f32_32x32x2_f32, 128- or 64-row tiles x 128
+//                        columns x 32-deep K steps, operands staged K-major in LDS. The patch embedding is the same kernel
+//                        with an implicit-GEMM A loader (rows gathered from the NCHW frames, k = c*1024 + kh*32 + kw, the
+//                        OIHW order of the filter) and an epilogue that adds pos_embed and writes token rows 1..49.
+//                        Every output element is the same k-ordered fma chain whatever the tile height or M: a frame's
+//                        features do not depend on the batch it is in (bit for bit).
+//   vit_layernorm_kernel one wave per token row, two-pass (mean, centred variance) in registers; gamma / beta from the
+//                        parameter pool or from the per-task FiLM vectors (reference model/film.py:57-66).
+//   vit_attention_kernel one workgroup per (frame, head): Q, K, V (50 x 64) in LDS, S = QK^T / 8, row softmax, O = PV.
+#include <cmath>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "common.h"
+
+using namespace orbit;
+
+namespace {
+
+constexpr int VIT_PATCH = 32;
+constexpr int VIT_SIZE = 224;
+constexpr int VIT_GRID = VIT_SIZE / VIT_PATCH;    // 7
+constexpr int VIT_P = VIT_GRID * VIT_GRID;        // 49 patches
+constexpr int VIT_N = VIT_P + 1;                  // 50 tokens
+constexpr int VIT_KPATCH = 3 * VIT_PATCH * VIT_PATCH;  // 3072
+constexpr int VIT_HD = 64;                        // head dim
+constexpr int VIT_DEPTH = 12;
+constexpr int VIT_MAX_B = 8192;
+
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+// ---- token GEMM ------------------------------------------------------------------------------------------------------
+constexpr int G_BN = 128, G_BK = 32, G_THREADS = 256;
+enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_PATCH = 3 };
+
+struct GemmArgs {
+    const float* x;         // [M][K] token rows, or the NCHW frames (EPI_PATCH)
+    const float* w;         // [N][K] (torch Linear / OIHW conv layout)
+    const float* bias;      // [N] or nullptr
+    const float* residual;  // [M][N] (EPI_RESIDUAL; may alias y)
+    const float* pos;       // pos_embed [50][N] (EPI_PATCH)
+    float* y;
+    int M, N, K;
+};
+
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
+
+// address of the 4 consecutive k of A row m (clamped into [0, M)) starting at k
+template <int EPI>
+__device__ __forceinline__ const float* a_row_ptr(const GemmArgs& a, int m, int k) {
+    if (EPI == EPI_PATCH) {
+        const int b = m / VIT_P, p = m - b * VIT_P;
+        const int ph = p / VIT_GRID, pw = p - ph * VIT_GRID;
+        const int c = k >> 10, kh = (k >> 5) & 31, kw = k & 31;
+        return a.x + (((size_t)b * 3 + c) * VIT_SIZE + ph * VIT_PATCH + kh) * VIT_SIZE + pw * VIT_PATCH + kw;
+    }
+    return a.x + (size_t)m * a.K + k;
+}
+
+template <int BM, int EPI>
+__global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
+    constexpr int TI = BM / 64;          // 32-row MFMA tiles per wave (waves are 2 x 2 over the block tile)
+    constexpr int AR = BM / 32;          // float4 loads of A per thread per K step
+    constexpr int BR = G_BN / 32;        // ... of B
+    constexpr int LDA = BM + 4, LDB = G_BN + 4;
+    __shared__ float As[G_BK * LDA];
+    __shared__ float Bs[G_BK * LDB];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int n0 = blockIdx.x * G_BN, m0 = blockIdx.y * BM;
+    const int lc = tid & 7, lr = tid >> 3;  // loader: k chunk (4 floats) and row
+
+    const float* ap[AR];
+#pragma unroll
+    for (int i = 0; i < AR; ++i) {
+        int m = m0 + lr + 32 * i;
+        m = m < a.M ? m : a.M - 1;  // rows past the tail re-read the last row; their outputs are never stored
+        ap[i] = a_row_ptr<EPI>(a, m, 4 * lc);
+    }
+    const float* bp[BR];
+#pragma unroll
+    for (int i = 0; i < BR; ++i) bp[i] = a.w + (size_t)(n0 + lr + 32 * i) * a.K + 4 * lc;
+
+    floatx16 acc[TI][2];
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    float4 ra[AR], rb[BR];
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+            // patch rows: k0 advances (c, kh) - one frame row of 32 pixels per K step
+            const float* p = EPI == EPI_PATCH ? ap[i] + ((k0 >> 10) * VIT_SIZE + ((k0 >> 5) & 31)) * VIT_SIZE
+                                              : ap[i] + k0;
+            ra[i] = *reinterpret_cast<const float4*>(p);
+        }
+#pragma unroll
+        for (int i = 0; i < BR; ++i) rb[i] = *reinterpret_cast<const float4*>(bp[i] + k0);
+    };
+
+    const int nk = a.K / G_BK;
+    load(0);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+            const int r = lr + 32 * i;
+            As[(4 * lc + 0) * LDA + r] = ra[i].x;
+            As[(4 * lc + 1) * LDA + r] = ra[i].y;
+            As[(4 * lc + 2) * LDA + r] = ra[i].z;
+            As[(4 * lc + 3) * LDA + r] = ra[i].w;
+        }
+#pragma unroll
+        for (int i = 0; i < BR; ++i) {
+            const int r = lr + 32 * i;
+            Bs[(4 * lc + 0) * LDB + r] = rb[i].x;
+            Bs[(4 * lc + 1) * LDB + r] = rb[i].y;
+            Bs[(4 * lc + 2) * LDB + r] = rb[i].z;
+            Bs[(4 * lc + 3) * LDB + r] = rb[i].w;
+        }
+        __syncthreads();
+        if (kt + 1 < nk) load((kt + 1) * G_BK);  // next K step in flight during the MFMAs
+        const int kh = lane >> 5, col = lane & 31;
+#pragma unroll
+        for (int kk = 0; kk < G_BK / 2; ++kk) {
+            float af[TI], bf[2];
+#pragma unroll
+            for (int i = 0; i < TI; ++i) af[i] = As[(2 * kk + kh) * LDA + wm * (BM / 2) + 32 * i + col];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bf[j] = Bs[(2 * kk + kh) * LDB + wn * 64 + 32 * j + col];
+#pragma unroll
+            for (int i = 0; i < TI; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
+        }
+    }
+
+    // epilogue: C[row][col], col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = n0 + wn * 64 + 32 * j + (lane & 31);
+            const float bv = a.bias ? a.bias[col] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = m0 + wm * (BM / 2) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (row >= a.M) continue;
+                float v = acc[i][j][r] + bv;
+                if (EPI == EPI_PATCH) {
+                    const int b = row / VIT_P, p = row - b * VIT_P;
+                    v += a.pos[(size_t)(1 + p) * a.N + col];
+                    a.y[((size_t)b * VIT_N + 1 + p) * a.N + col] = v;
+                    continue;
+                }
+                if (EPI == EPI_GELU) v = gelu_erf(v);
+                if (EPI == EPI_RESIDUAL) v += a.residual[(size_t)row * a.N + col];
+                a.y[(size_t)row * a.N + col] = v;
+            }
+        }
+}
+
+template <int EPI>
+int launch_gemm(const GemmArgs& a, const char* what, hipStream_t s) {
+    if (a.N % G_BN || a.K % G_BK || a.M <= 0) return set_err(ORBIT_ERR_ARG, "vit gemm: unsupported shape M=%d N=%d K=%d", a.M, a.N, a.K);
+    // tile height: 128 rows unless that leaves fewer than two tiles per CU (the D x D and 4D x D layers at ~10k rows)
+    const int n_tiles = a.N / G_BN;
+    const bool tall = (long)cdiv(a.M, 128) * n_tiles >= 512;
+    const double flops = 2.0 * a.M * a.N * a.K;
+    const double bytes = 4.0 * ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N * (EPI == EPI_RESIDUAL ? 2 : 1));
+    char name[48];
+    snprintf(name, sizeof(name), "vit_%s<%d>", what, tall ? 128 : 64);
+    const int pi = prof_start(name, flops, bytes, s);
+    if (tall)
+        vit_gemm_kernel<128, EPI><<<dim3(n_tiles, cdiv(a.M, 128)), G_THREADS, 0, s>>>(a);
+    else
+        vit_gemm_kernel<64, EPI><<<dim3(n_tiles, cdiv(a.M, 64)), G_THREADS, 0, s>>>(a);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
+// ---- class token row -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void vit_cls_kernel(const float* __restrict__ cls, const float* __restrict__ pos,
+                                                      float* __restrict__ tokens, int B, int D) {
+    const size_t n = (size_t)B * D;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const int b = (int)(i / D), d = (int)(i - (size_t)b * D);
+        tokens[(size_t)b * VIT_N * D + d] = cls[d] + pos[d];
+    }
+}
+
+// ---- LayerNorm -------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int NPL>  // D / 64 values per lane
+__global__ __launch_bounds__(256) void vit_layernorm_kernel(const float* x, size_t x_stride, float* y, size_t y_stride,
+                                                            int rows, const float* __restrict__ g,
+                                                            const float* __restrict__ b, float eps) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    constexpr int D = NPL * 64;
+    const float* xr = x + (size_t)row * x_stride;
+    float v[NPL];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) v[i] = xr[lane + 64 * i], s += v[i];
+    const float mean = wave_sum(s) * (1.f / D);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) v[i] -= mean, q += v[i] * v[i];
+    const float rstd = 1.f / sqrtf(wave_sum(q) * (1.f / D) + eps);
+    float* yr = y + (size_t)row * y_stride;  // (may alias x: every lane has read its values)
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) yr[lane + 64 * i] = v[i] * rstd * g[lane + 64 * i] + b[lane + 64 * i];
+}
+
+int launch_layernorm(const float* x, size_t xs, float* y, size_t ys, int rows, int D, const float* g, const float* b,
+                     float eps, hipStream_t s) {
+    const int pi = prof_start("vit_layernorm", 8.0 * rows * D, 4.0 * 2 * rows * D, s);
+    const dim3 grid(cdiv(rows, 4));
+    if (D == 384)
+        vit_layernorm_kernel<6><<<grid, 256, 0, s>>>(x, xs, y, ys, rows, g, b, eps);
+    else if (D == 768)
+        vit_layernorm_kernel<12><<<grid, 256, 0, s>>>(x, xs, y, ys, rows, g, b, eps);
+    else
+        return set_err(ORBIT_ERR_ARG, "vit layernorm: unsupported width %d", D);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
+// ---- attention -------------------------------------------------------------------------------------------------------
+// qkv [B*50][3D] (timm: qkv.reshape(B, N, 3, heads, 64)) -> out [B*50][D], columns h*64..h*64+63
+__global__ __launch_bounds__(256) void vit_attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int D,
+                                                            int heads) {
+    constexpr int LDK = VIT_HD + 1, LDS_ = 52;
+    __shared__ float q[VIT_N * VIT_HD], k[VIT_N * LDK], v[VIT_N * VIT_HD], sc[VIT_N * LDS_];
+    const int bh = blockIdx.x, b = bh / heads, h = bh - b * heads;
+    const int tid = threadIdx.x;
+    const float* base = qkv + (size_t)b * VIT_N * 3 * D + h * VIT_HD;
+    for (int i = tid; i < VIT_N * VIT_HD; i += 256) {
+        const int t = i >> 6, d = i & 63;
+        const float* r = base + (size_t)t * 3 * D + d;
+        q[i] = r[0];
+        k[t * LDK + d] = r[D];
+        v[i] = r[2 * D];
+    }
+    __syncthreads();
+    for (int i = tid; i < VIT_N * VIT_N; i += 256) {
+        const int r = i / VIT_N, c = i - r * VIT_N;
+        float acc = 0.f;
+#pragma unroll 16
+        for (int d = 0; d < VIT_HD; ++d) acc = fmaf(q[r * VIT_HD + d], k[c * LDK + d], acc);
+        sc[r * LDS_ + c] = acc * 0.125f;  // head_dim ** -0.5
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int r = wave; r < VIT_N; r += 4) {
+        const float val = lane < VIT_N ? sc[r * LDS_ + lane] : -INFINITY;
+        float m = val;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        const float e = lane < VIT_N ? expf(val - m) : 0.f;
+        const float sum = wave_sum(e);
+        if (lane < VIT_N) sc[r * LDS_ + lane] = e / sum;
+    }
+    __syncthreads();
+    for (int i = tid; i < VIT_N * VIT_HD; i += 256) {
+        const int r = i >> 6, d = i & 63;
+        float acc = 0.f;
+#pragma unroll 10
+        for (int c = 0; c < VIT_N; ++c) acc = fmaf(sc[r * LDS_ + c], v[c * VIT_HD + d], acc);
+        out[((size_t)b * VIT_N + r) * D + h * VIT_HD + d] = acc;
+    }
+}
+
+}  // namespace
+
+// ---- plan ------------------------------------------------------------------------------------------------------------
+struct orbit_vit {
+    struct Param {
+        std::string key;
+        size_t numel, off;
+        bool loaded = false;
+    };
+    std::string name;
+    int D = 0, heads = 0, mlp = 0;
+    float eps = 1e-6f;
+    bool clip = false;  // pre_norm: no patch-embedding bias, norm_pre after the position add
+    std::vector<Param> params;
+    std::unordered_map<std::string, int> index;
+    std::vector<std::string> film_names;  // FiLM slots (LayerNorm module names), D channels each
+    size_t pool_floats = 0;
+    float* d_pool = nullptr;
+    const float** d_src = nullptr;
+    size_t* d_meta = nullptr;
+    std::vector<const float*> h_src;
+    bool finalized = false;
+    double macs = 0;
+
+    int add(const std::string& key, size_t numel) {
+        index[key] = (int)params.size();
+        params.push_back({key, numel, pool_floats});
+        pool_floats += (numel + 63) / 64 * 64;  // 256-byte aligned tensors (float4 loads)
+        return (int)params.size() - 1;
+    }
+    const float* p(const std::string& key) const { return d_pool + params[index.at(key)].off; }
+    int ensure_device() {
+        if (!d_pool) ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_pool), pool_floats * sizeof(float)));
+        return ORBIT_OK;
+    }
+};
+
+namespace {
+
+struct VitWs {
+    size_t x, h, big, total;
+};
+VitWs vit_ws(const orbit_vit* v, int B) {
+    const size_t M = (size_t)B * VIT_N;
+    VitWs L;
+    L.x = 0;
+    L.h = align_up(M * v->D * sizeof(float), 256);
+    L.big = L.h + align_up(M * v->D * sizeof(float), 256);
+    L.total = L.big + align_up(M * v->mlp * sizeof(float), 256);
+    return L;
+}
+
+__global__ __launch_bounds__(256) void vit_gather_params_kernel(const float* const* __restrict__ src,
+                                                                const size_t* __restrict__ meta, float* __restrict__ pool) {
+    const float* s_ = src[blockIdx.y];
+    float* d = pool + meta[2 * blockIdx.y];
+    const size_t n = meta[2 * blockIdx.y + 1];
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) d[i] = s_[i];
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out) {
+    ORBIT_REQUIRE(name && out, "vit_create: null pointer");
+    std::string n(name);
+    int D, heads;
+    bool clip = false;
+    if (n == "vit_s_32") D = 384, heads = 6;
+    else if (n == "vit_b_32") D = 768, heads = 12;
+    else if (n == "vit_b_32_clip") D = 768, heads = 12, clip = true;
+    else return set_err(ORBIT_ERR_ARG, "Invalid feature_extractor_name: %s (transformer extractors: vit_s_32, vit_b_32, "
+                        "vit_b_32_clip)", name);
+    ORBIT_REQUIRE(H == VIT_SIZE && W == VIT_SIZE, "vit_create: %s runs on %dx%d frames only (fixed position table), got %dx%d",
+                  name, VIT_SIZE, VIT_SIZE, H, W);
+    orbit_vit* v = new orbit_vit();
+    v->name = n, v->D = D, v->heads = heads, v->mlp = 4 * D, v->clip = clip, v->eps = clip ? 1e-5f : 1e-6f;
+    // timm 0.6.12 VisionTransformer state_dict order
+    v->add("cls_token", D);
+    v->add("pos_embed", (size_t)VIT_N * D);
+    v->add("patch_embed.proj.weight", (size_t)D * VIT_KPATCH);
+    if (!clip) v->add("patch_embed.proj.bias", D);
+    if (clip) v->add("norm_pre.weight", D), v->add("norm_pre.bias", D);
+    for (int i = 0; i < VIT_DEPTH; ++i) {
+        const std::string b = "blocks." + std::to_string(i);
+        v->add(b + ".norm1.weight", D), v->add(b + ".norm1.bias", D);
+        v->add(b + ".attn.qkv.weight", (size_t)3 * D * D), v->add(b + ".attn.qkv.bias", 3 * D);
+        v->add(b + ".attn.proj.weight", (size_t)D * D), v->add(b + ".attn.proj.bias", D);
+        v->add(b + ".norm2.weight", D), v->add(b + ".norm2.bias", D);
+        v->add(b + ".mlp.fc1.weight", (size_t)4 * D * D), v->add(b + ".mlp.fc1.bias", 4 * D);
+        v->add(b + ".mlp.fc2.weight", (size_t)4 * D * D), v->add(b + ".mlp.fc2.bias", D);
+        v->film_names.push_back(b + ".norm1");
+        v->film_names.push_back(b + ".norm2");
+    }
+    v->add("norm.weight", D), v->add("norm.bias", D);
+    v->film_names.push_back("norm");
+    const double Dd = D;
+    v->macs = (double)VIT_P * VIT_KPATCH * Dd + VIT_DEPTH * (VIT_N * 12.0 * Dd * Dd + 2.0 * VIT_N * VIT_N * Dd);
+    *out = v;
+    return ORBIT_OK;
+}
+
+void orbit_vit_destroy(orbit_vit_t* v) {
+    if (!v) return;
+    (void)hipFree(v->d_pool);
+    (void)hipFree(v->d_src);
+    (void)hipFree(v->d_meta);
+    delete v;
+}
+
+int orbit_vit_num_params(const orbit_vit_t* v) { return v ? (int)v->params.size() : 0; }
+const char* orbit_vit_param_name(const orbit_vit_t* v, int i) {
+    return (v && i >= 0 && i < (int)v->params.size()) ? v->params[i].key.c_str() : nullptr;
+}
+size_t orbit_vit_param_numel(const orbit_vit_t* v, int i) {
+    return (v && i >= 0 && i < (int)v->params.size()) ? v->params[i].numel : 0;
+}
+
+int orbit_vit_load(orbit_vit_t* v, const char* key, const float* data, size_t numel) {
+    ORBIT_REQUIRE(v && key && data, "vit_load: null pointer");
+    auto it = v->index.find(key);
+    ORBIT_REQUIRE(it != v->index.end(), "vit_load: unexpected key '%s' for %s", key, v->name.c_str());
+    auto& p = v->params[it->second];
+    ORBIT_REQUIRE(p.numel == numel, "vit_load: '%s' has %zu elements, expected %zu", key, numel, p.numel);
+    if (int rc = v->ensure_device()) return rc;
+    ORBIT_HIP_CHECK(hipMemcpy(v->d_pool + p.off, data, numel * sizeof(float), hipMemcpyDefault));
+    p.loaded = true;
+    v->finalized = false;
+    return ORBIT_OK;
+}
+
+int orbit_vit_load_async(orbit_vit_t* v, const char* key, const float* device_data, size_t numel, orbit_stream_t stream) {
+    ORBIT_REQUIRE(v && key && device_data, "vit_load_async: null pointer");
+    auto it = v->index.find(key);
+    ORBIT_REQUIRE(it != v->index.end(), "vit_load_async: unexpected key '%s' for %s", key, v->name.c_str());
+    auto& p = v->params[it->second];
+    ORBIT_REQUIRE(p.numel == numel, "vit_load_async: '%s' has %zu elements, expected %zu", key, numel, p.numel);
+    if (int rc = v->ensure_device()) return rc;
+    ORBIT_HIP_CHECK(hipMemcpyAsync(v->d_pool + p.off, device_data, numel * sizeof(float), hipMemcpyDeviceToDevice,
+                                   (hipStream_t)stream));
+    p.loaded = true;
+    v->finalized = false;
+    return ORBIT_OK;
+}
+
+int orbit_vit_load_all_async(orbit_vit_t* v, const float* const* device_ptrs, int n, orbit_stream_t stream) {
+    ORBIT_REQUIRE(v && device_ptrs, "vit_load_all_async: null pointer");
+    ORBIT_REQUIRE(n == (int)v->params.size(), "vit_load_all_async: %d pointers for %zu parameters", n, v->params.size());
+    if (int rc = v->ensure_device()) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (!v->d_src) {
+        ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&v->d_src), n * sizeof(float*)));
+        ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&v->d_meta), 2 * n * sizeof(size_t)));
+        std::vector<size_t> meta(2 * n);
+        for (int i = 0; i < n; ++i) meta[2 * i] = v->params[i].off, meta[2 * i + 1] = v->params[i].numel;
+        ORBIT_HIP_CHECK(hipMemcpy(v->d_meta, meta.data(), meta.size() * sizeof(size_t), hipMemcpyHostToDevice));
+    }
+    bool same = (int)v->h_src.size() == n;
+    for (int i = 0; same && i < n; ++i) same = v->h_src[i] == device_ptrs[i];
+    if (!same) {
+        for (int i = 0; i < n; ++i) ORBIT_REQUIRE(device_ptrs[i], "vit_load_all_async: null tensor %d", i);
+        v->h_src.assign(device_ptrs, device_ptrs + n);
+        ORBIT_HIP_CHECK(hipStreamSynchronize(s));  // the table may still be read by an earlier gather on this stream
+        ORBIT_HIP_CHECK(hipMemcpy(v->d_src, v->h_src.data(), n * sizeof(float*), hipMemcpyHostToDevice));
+    }
+    vit_gather_params_kernel<<<dim3(32, n), 256, 0, s>>>(v->d_src, v->d_meta, v->d_pool);
+    ORBIT_LAUNCH_CHECK();
+    for (auto& p : v->params) p.loaded = true;
+    v->finalized = false;
+    return ORBIT_OK;
+}
+
+int orbit_vit_finalize(orbit_vit_t* v, orbit_stream_t stream) {
+    (void)stream;  // the kernels read the torch layouts as loaded: nothing to repack
+    ORBIT_REQUIRE(v, "vit_finalize: null pointer");
+    for (const auto& p : v->params) ORBIT_REQUIRE(p.loaded, "vit_finalize: parameter '%s' was never loaded", p.key.c_str());
+    v->finalized = true;
+    return ORBIT_OK;
+}
+
+int orbit_vit_output_size(const orbit_vit_t* v) { return v ? v->D : 0; }
+int orbit_vit_film_slots(const orbit_vit_t* v) { return v ? (int)v->film_names.size() : 0; }
+int orbit_vit_film_slot_channels(const orbit_vit_t* v, int slot) {
+    return (v && slot >= 0 && slot < (int)v->film_names.size()) ? v->D : 0;
+}
+const char* orbit_vit_film_slot_name(const orbit_vit_t* v, int slot) {
+    return (v && slot >= 0 && slot < (int)v->film_names.size()) ? v->film_names[slot].c_str() : nullptr;
+}
+int orbit_vit_film_size(const orbit_vit_t* v) { return v ? (int)v->film_names.size() * v->D : 0; }
+size_t orbit_vit_workspace_bytes(const orbit_vit_t* v, int B) {
+    if (!v || B <= 0 || B > VIT_MAX_B) return 0;
+    return vit_ws(v, B).total;
+}
+double orbit_vit_macs_per_frame(const orbit_vit_t* v) { return v ? v->macs : 0.0; }
+
+int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
+                      float* feats, void* workspace, size_t workspace_bytes, orbit_stream_t stream) {
+    ORBIT_REQUIRE(v && frames && feats && workspace, "vit_forward: null pointer");
+    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "vit_forward: batch of %d frames (1..%d)", B, VIT_MAX_B);
+    if (!v->finalized) return set_err(ORBIT_ERR_STATE, "vit_forward: call orbit_vit_finalize first");
+    ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr),
+                  "vit_forward: film_gamma and film_beta must be given together");
+    const VitWs L = vit_ws(v, B);
+    ORBIT_REQUIRE(workspace_bytes >= L.total, "vit_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, L.total);
+    ORBIT_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)frames & 15) == 0,
+                  "vit_forward: workspace must be 256-byte and frames 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int D = v->D, M = B * VIT_N;
+    char* ws = static_cast<char*>(workspace);
+    float* x = reinterpret_cast<float*>(ws + L.x);
+    float* h = reinterpret_cast<float*>(ws + L.h);
+    float* big = reinterpret_cast<float*>(ws + L.big);
+    auto ln_params = [&](const std::string& mod, int slot, const float** g, const float** b) {
+        if (film_gamma && slot >= 0) *g = film_gamma + (size_t)slot * D, *b = film_beta + (size_t)slot * D;
+        else *g = v->p(mod + ".weight"), *b = v->p(mod + ".bias");
+    };
+    int rc;
+    {   // tokens: patch embedding (+ bias) + pos_embed into rows 1..49, cls_token + pos_embed[0] into row 0
+        GemmArgs a{frames, v->p("patch_embed.proj.weight"), v->clip ? nullptr : v->p("patch_embed.proj.bias"), nullptr,
+                   v->p("pos_embed"), x, B * VIT_P, D, VIT_KPATCH};
+        if ((rc = launch_gemm<EPI_PATCH>(a, "patch_embed", s))) return rc;
+        const int pi = prof_start("vit_cls_token", 0.0, 4.0 * B * D, s);
+        vit_cls_kernel<<<cdiv(B * D, 256) < 1024 ? cdiv(B * D, 256) : 1024, 256, 0, s>>>(v->p("cls_token"), v->p("pos_embed"),
+                                                                                         x, B, D);
+        prof_stop(pi, s);
+        ORBIT_LAUNCH_CHECK();
+        if (v->clip && (rc = launch_layernorm(x, D, x, D, M, D, v->p("norm_pre.weight"), v->p("norm_pre.bias"), v->eps, s)))
+            return rc;
+    }
+    for (int i = 0; i < VIT_DEPTH; ++i) {
+        const std::string b = "blocks." + std::to_string(i);
+        const float *g, *be;
+        ln_params(b + ".norm1", 2 * i, &g, &be);
+        if ((rc = launch_layernorm(x, D, h, D, M, D, g, be, v->eps, s))) return rc;
+        GemmArgs qkv{h, v->p(b + ".attn.qkv.weight"), v->p(b + ".attn.qkv.bias"), nullptr, nullptr, big, M, 3 * D, D};
+        if ((rc = launch_gemm<EPI_BIAS>(qkv, "qkv", s))) return rc;
+        const int pi = prof_start("vit_attention", 4.0 * B * v->heads * VIT_N * VIT_N * VIT_HD,
+                                  4.0 * 4 * (double)M * D, s);
+        vit_attention_kernel<<<B * v->heads, 256, 0, s>>>(big, h, D, v->heads);
+        prof_stop(pi, s);
+        ORBIT_LAUNCH_CHECK();
+        GemmArgs proj{h, v->p(b + ".attn.proj.weight"), v->p(b + ".attn.proj.bias"), x, nullptr, x, M, D, D};
+        if ((rc = launch_gemm<EPI_RESIDUAL>(proj, "proj", s))) return rc;
+        ln_params(b + ".norm2", 2 * i + 1, &g, &be);
+        if ((rc = launch_layernorm(x, D, h, D, M, D, g, be, v->eps, s))) return rc;
+        GemmArgs fc1{h, v->p(b + ".mlp.fc1.weight"), v->p(b + ".mlp.fc1.bias"), nullptr, nullptr, big, M, 4 * D, D};
+        if ((rc = launch_gemm<EPI_GELU>(fc1, "fc1", s))) return rc;
+        GemmArgs fc2{big, v->p(b + ".mlp.fc2.weight"), v->p(b + ".mlp.fc2.bias"), x, nullptr, x, M, D, 4 * D};
+        if ((rc = launch_gemm<EPI_RESIDUAL>(fc2, "fc2", s))) return rc;
+    }
+    const float *g, *be;
+    ln_params("norm", 2 * VIT_DEPTH, &g, &be);
+    // final LayerNorm on the class token of every frame, straight into the caller's feature rows
+    return launch_layernorm(x, (size_t)VIT_N * D, feats, D, B, D, g, be, v->eps, s);
+}
+
+}  // extern "C"

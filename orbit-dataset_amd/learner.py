@@ -41,7 +41,7 @@ from .optim import apply_lr_scale, cross_entropy, init_optimizer  # noqa: F401  
 def build_parser():
     p = argparse.ArgumentParser(description="single-step learner on the MI355X-native recogniser (synthetic tasks)")
     # flags shared with the reference (utils/args.py)
-    p.add_argument("--feature_extractor", default="efficientnet_b0", choices=["efficientnet_b0", "resnet18"])
+    p.add_argument("--feature_extractor", default="efficientnet_b0", choices=["efficientnet_b0", "resnet18", "vit_s_32", "vit_b_32", "vit_b_32_clip"])
     p.add_argument("--learn_extractor", action="store_true")
     p.add_argument("--adapt_features", action="store_true")
     p.add_argument("--classifier", default="proto", choices=["proto", "proto_cosine", "versa", "mahalanobis", "linear"])
@@ -116,12 +116,25 @@ def build_parser():
     return p
 
 
+VIT_EXTRACTORS = {"vit_s_32": "imagenet_inception", "vit_b_32": "imagenet_inception", "vit_b_32_clip": "openai_clip"}
+
+
 def verify_args(args):
-    """reference utils/args.py:203-217"""
+    """reference utils/args.py:203-217. For the transformer extractors also the frame normalisation the reference sets
+    for them (utils/args.py:185-190; the other extractors keep --frame_norm_method) and the inference-only scope."""
     if "train" in args.mode and not args.learn_extractor and not args.adapt_features:
         sys.exit("error: at least one of --learn_extractor and --adapt_features must be used when training")
     if args.frame_size % 1 or args.frame_size < 32:
         sys.exit("error: --frame_size must be >= 32")
+    fe = args.feature_extractor
+    if fe in VIT_EXTRACTORS:
+        args.frame_norm_method = VIT_EXTRACTORS[fe]
+        if args.frame_size != 224:
+            sys.exit("error: --feature_extractor %s needs --frame_size 224 (got %d)" % (fe, args.frame_size))
+        multistep = getattr(args, "personalize_num_grad_steps", None) is not None
+        if "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
+            sys.exit("error: --feature_extractor %s is inference-only here (no backward through a ViT): use --mode test "
+                     "without --learn_extractor / --with_lite%s" % (fe, " / --adapt_features" if multistep else ""))
 
 
 def frame_accuracy(logits, label):

@@ -5,7 +5,8 @@ same signature and return value `(extractor, film_parameter_names)`, `extractor.
 parameters when `learn_extractor=False`, FiLM tagging when `with_film=True`. The reference builds timm
 networks; here the network lives in liborbit_hip.so and this module is only its parameter container
 (state_dict-compatible key names: torchvision layout for resnet18, timm `tf_efficientnet_b0` layout for
-efficientnet_b0) plus the call into `orbit_extractor_forward`. `resnet18` and arbitrary frame sizes are
+efficientnet_b0, timm VisionTransformer layout for vit_s_32 / vit_b_32 / vit_b_32_clip) plus the call into
+`orbit_extractor_forward` (`orbit_vit_forward` for the transformers, csrc/vit.hip). `resnet18` and arbitrary frame sizes are
 additions BASELINE.json's configs require (the snapshot's args.py:27,77 no longer list them).
 
 There is no pretrained-weight download (no network): `pretrained=True` is accepted for signature parity and
@@ -45,12 +46,16 @@ def _ensure_child(module, name, cls=ParamNode):
 class _Plan:
     """One native plan (frame size specific) and the parameter stamp it was last synchronised with."""
 
-    def __init__(self, name, H, W, trainable=False):
+    def __init__(self, name, H, W, trainable=False, api="extractor"):
         lib = _lib.load()
         h = ctypes.c_void_p()
-        # the fused MBConv front kernels have no backward form: a plan that will record a tape is built without them
-        _lib.check(lib.orbit_extractor_create_ex(name.encode(), H, W, 1 if trainable else 0, ctypes.byref(h)),
-                   "orbit_extractor_create_ex")
+        if api == "extractor":
+            # the fused MBConv front kernels have no backward form: a plan that will record a tape is built without them
+            _lib.check(lib.orbit_extractor_create_ex(name.encode(), H, W, 1 if trainable else 0, ctypes.byref(h)),
+                       "orbit_extractor_create_ex")
+        else:
+            _lib.check(getattr(lib, "orbit_%s_create" % api)(name.encode(), H, W, ctypes.byref(h)), "orbit_%s_create" % api)
+        self.api = api
         self.handle = h
         self.stamp = None
         self.generation = 0  # bumped by every parameter upload: a tape recorded under generation g can only be replayed under g
@@ -58,7 +63,7 @@ class _Plan:
 
     def destroy(self):
         if self.handle:
-            _lib.load().orbit_extractor_destroy(self.handle)
+            getattr(_lib.load(), "orbit_%s_destroy" % self.api)(self.handle)
             self.handle = None
 
 
@@ -77,6 +82,10 @@ class HipNetwork(nn.Module):
     records a tape and `backward()` runs the native gradient kernels (model/autograd.py).
     """
 
+    # native entry-point family (orbit_<api>_*) and the frame size of the throw-away plan that enumerates the parameters
+    _api = "extractor"
+    _probe_size = 64
+
     def __init__(self, native_name):
         super().__init__()
         self.native_name = native_name
@@ -86,28 +95,32 @@ class HipNetwork(nn.Module):
         self._persist_key = None
         self._persist = {}       # (key, kind) -> tensor
         self._persist_busy = {}  # key -> True while a tape recorded into the buffers awaits its backward
-        lib = _lib.load()
+        fn = self._fn
         # a throw-away plan at a nominal size enumerates the state_dict keys and FiLM slots
-        probe = _Plan(native_name, 64, 64)
+        probe = _Plan(native_name, self._probe_size, self._probe_size, api=self._api)
         try:
             h = probe.handle
-            self.output_size = lib.orbit_extractor_output_size(h)
+            self.output_size = fn("output_size")(h)
             self._keys = []
-            for i in range(lib.orbit_extractor_num_params(h)):
-                key = lib.orbit_extractor_param_name(h, i).decode()
-                numel = lib.orbit_extractor_param_numel(h, i)
+            for i in range(fn("num_params")(h)):
+                key = fn("param_name")(h, i).decode()
+                numel = fn("param_numel")(h, i)
                 self._keys.append((key, numel))
             self._film_slot_names = []
             self._film_slot_channels = []
-            for s in range(lib.orbit_extractor_film_slots(h)):
-                self._film_slot_names.append(lib.orbit_extractor_film_slot_name(h, s).decode())
-                self._film_slot_channels.append(lib.orbit_extractor_film_slot_channels(h, s))
-            self.film_size = lib.orbit_extractor_film_size(h)
+            for s in range(fn("film_slots")(h)):
+                self._film_slot_names.append(fn("film_slot_name")(h, s).decode())
+                self._film_slot_channels.append(fn("film_slot_channels")(h, s))
+            self.film_size = fn("film_size")(h)
         finally:
             probe.destroy()
         self._leaves = []  # (module, attr, key)
         for key, numel in self._keys:
             self._register_leaf(key, numel)
+
+    def _fn(self, name):
+        """The native entry point orbit_<api>_<name> of this network's family."""
+        return getattr(_lib.load(), "orbit_%s_%s" % (self._api, name))
 
     # ---- parameter tree -------------------------------------------------------------------------
     def _register_leaf(self, key, numel):
@@ -145,10 +158,9 @@ class HipNetwork(nn.Module):
         statistics gets its own (unfused) plan. Both enumerate the same parameters in the same order."""
         plan = self._plans.get((H, W, trainable))
         if plan is None:
-            plan = _Plan(self.native_name, H, W, trainable)
-            lib = _lib.load()
-            names = [lib.orbit_extractor_param_name(plan.handle, i).decode()
-                     for i in range(lib.orbit_extractor_num_params(plan.handle))]
+            plan = _Plan(self.native_name, H, W, trainable, api=self._api)
+            names = [self._fn("param_name")(plan.handle, i).decode()
+                     for i in range(self._fn("num_params")(plan.handle))]
             if names != [k for k, _ in self._keys]:
                 raise _lib.OrbitHipError("native plan enumerates different parameters than the module tree")
             self._plans[(H, W, trainable)] = plan
@@ -209,7 +221,7 @@ class HipNetwork(nn.Module):
 
     def sync(self, plan=None):
         """(Re)upload parameters into the native plan(s) if they changed since the last upload."""
-        lib = _lib.load()
+        fn = self._fn
         stamp = self._stamp()
         plans = [plan] if plan is not None else list(self._plans.values())
         for pl in plans:
@@ -225,19 +237,18 @@ class HipNetwork(nn.Module):
                 # every tensor already lives on the device: ONE gather kernel (the pointer table is cached inside the plan)
                 # instead of one stream-ordered copy per tensor - after every optimizer step this was ~360 ctypes calls
                 ptrs = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-                _lib.check(lib.orbit_extractor_load_all_async(pl.handle, ptrs, len(tensors), _lib.stream_handle()),
-                           "orbit_extractor_load_all_async")
+                _lib.check(fn("load_all_async")(pl.handle, ptrs, len(tensors), _lib.stream_handle()),
+                           "orbit_%s_load_all_async" % self._api)
             else:
                 for (node, attr, key, own), t in zip(self._leaves, tensors):
                     t = t.contiguous().float()
                     if t.is_cuda:  # stream-ordered copy: no host sync while parameters follow optimizer steps
-                        _lib.check(lib.orbit_extractor_load_async(pl.handle, key.encode(), ctypes.c_void_p(t.data_ptr()),
-                                                                  t.numel(), _lib.stream_handle()),
-                                   "orbit_extractor_load_async(%s)" % key)
+                        _lib.check(fn("load_async")(pl.handle, key.encode(), ctypes.c_void_p(t.data_ptr()), t.numel(),
+                                                    _lib.stream_handle()), "orbit_%s_load_async(%s)" % (self._api, key))
                     else:
-                        _lib.check(lib.orbit_extractor_load(pl.handle, key.encode(), ctypes.c_void_p(t.data_ptr()),
-                                                            t.numel()), "orbit_extractor_load(%s)" % key)
-            _lib.check(lib.orbit_extractor_finalize(pl.handle, _lib.stream_handle()), "orbit_extractor_finalize")
+                        _lib.check(fn("load")(pl.handle, key.encode(), ctypes.c_void_p(t.data_ptr()), t.numel()),
+                                   "orbit_%s_load(%s)" % (self._api, key))
+            _lib.check(fn("finalize")(pl.handle, _lib.stream_handle()), "orbit_%s_finalize" % self._api)
             pl.stamp = stamp
             pl.generation += 1
 
@@ -247,7 +258,7 @@ class HipNetwork(nn.Module):
         key = (B, _lib.stream_handle().value or 0)
         ws = plan.workspaces.get(key)
         if ws is None or ws.device != device:
-            nbytes = _lib.load().orbit_extractor_workspace_bytes(plan.handle, B)
+            nbytes = self._fn("workspace_bytes")(plan.handle, B)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
             # keep the most recent batch size per stream
             plan.workspaces = {k: v for k, v in plan.workspaces.items() if k[1] != key[1]}
@@ -267,7 +278,7 @@ class HipNetwork(nn.Module):
         return rep, eag
 
     def macs_per_frame(self, H, W):
-        return _lib.load().orbit_extractor_macs_per_frame(self._plan(H, W).handle)
+        return self._fn("macs_per_frame")(self._plan(H, W).handle)
 
     # ---- FiLM ---------------------------------------------------------------------------------------
     def film_slot_modules(self):
@@ -498,6 +509,94 @@ class EfficientNetB0(HipNetwork):
         return (cout, numel // cout, 1, 1)
 
 
+_VIT_OUTPUT = {"vit_s_32": 384, "vit_b_32": 768, "vit_b_32_clip": 768}
+VIT_FRAME_SIZE = 224
+
+
+class VisionTransformer(HipNetwork):
+    """timm 0.6.12 ViT-S/32, ViT-B/32 or ViT-B/32-CLIP with num_classes=0 (reference model/feature_extractors.py:49-63) on the
+    native transformer runtime (csrc/vit.hip, orbit_vit_*): same parameter tree, state_dict keys and shapes as the timm
+    module, FiLM on the LayerNorms named norm / norm1 / norm2 (reference model/film.py:57-66).
+
+    Inference only: a forward that would need a gradient (LITE meta-training, --learn_extractor, FiLM gradients) raises
+    NotImplementedError before anything is launched. There is no BatchNorm or dropout, so train() and eval() compute the same
+    features. Frames must be 224 x 224 (the position table is fixed)."""
+
+    _api = "vit"
+    _probe_size = VIT_FRAME_SIZE
+
+    def __init__(self, name):
+        super().__init__(name)
+
+    def _leaf_shape(self, key, numel):
+        # (cls_token is the first key: its size is the embedding width D)
+        if key == "cls_token":
+            self.__dict__["_leaf_D"] = numel
+            return (1, 1, numel)
+        D = self.__dict__["_leaf_D"]
+        if key == "pos_embed":
+            return (1, numel // D, D)
+        if key == "patch_embed.proj.weight":
+            return (D, 3, 32, 32)
+        if key.endswith(".weight") and (".attn." in key or ".mlp." in key):
+            return {"qkv": (3 * D, D), "proj": (D, D), "fc1": (4 * D, D), "fc2": (D, 4 * D)}[key.split(".")[-2]]
+        return (numel,)
+
+    def _plan(self, H, W, trainable=False):
+        if (H, W) != (VIT_FRAME_SIZE, VIT_FRAME_SIZE):
+            raise ValueError("%s runs on %dx%d frames only (got %dx%d)" % (self.native_name, VIT_FRAME_SIZE, VIT_FRAME_SIZE,
+                                                                          H, W))
+        return super()._plan(H, W, False)  # one plan: there is no training runtime
+
+    def in_sync(self, H, W, trainable=True):
+        plan = self._plans.get((H, W, False))
+        return plan is not None and plan.stamp == self._stamp()
+
+    def prepare(self, H, W, trainable=True):
+        self.sync(self._plan(H, W))
+
+    def train_graph_stats(self):
+        return 0, 0  # no training entry points
+
+    def wants_grad(self, film=None):
+        if super().wants_grad(film):
+            raise NotImplementedError(
+                "%s is an inference-only extractor: no native backward (LITE meta-training, --learn_extractor, FiLM "
+                "gradients); run it under torch.no_grad() with frozen parameters" % self.native_name)
+        return False
+
+    def forward(self, x, film=None, out=None, check_sync=True):
+        _lib.require_gpu()
+        if x.dim() == 5:
+            x = x.flatten(end_dim=1)
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("expected frames of shape [B,3,H,W], got %s" % (tuple(x.shape),))
+        if not x.is_cuda:
+            raise _lib.OrbitHipError("frames must be on the HIP device (got %s); no CPU fallback" % x.device)
+        x = x.contiguous().float()
+        B, _, H, W = x.shape
+        if film is None:
+            film = self._gather_swapped_film()
+        if film is not None:
+            if film[0].numel() != self.film_size or film[1].numel() != self.film_size:
+                raise ValueError("film vectors must have %d elements" % self.film_size)
+            film = (film[0].contiguous().float(), film[1].contiguous().float())
+        self.wants_grad(film)  # raises before any launch
+        plan = self._plan(H, W)
+        if check_sync or plan.stamp is None:
+            self.sync(plan)
+        feats = out if out is not None else torch.empty(B, self.output_size, device=x.device, dtype=torch.float32)
+        if B == 0:
+            return feats
+        ws = self._workspace(plan, B, x.device)
+        gamma, beta = film if film is not None else (None, None)
+        _lib.check(_lib.load().orbit_vit_forward(
+            plan.handle, _lib.dptr(x, torch.float32), B, _lib.dptr(gamma), _lib.dptr(beta),
+            _lib.dptr(feats, torch.float32), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_handle()),
+            "orbit_vit_forward")
+        return feats
+
+
 def create_feature_extractor(feature_extractor_name: str, pretrained: bool = True, with_film: bool = False,
                              learn_extractor: bool = True):
     """Same contract as the reference factory (model/feature_extractors.py:37-79)."""
@@ -507,9 +606,11 @@ def create_feature_extractor(feature_extractor_name: str, pretrained: bool = Tru
         feature_extractor = ResNet18()
     elif feature_extractor_name == "efficientnet_b0":
         feature_extractor = EfficientNetB0()
+    elif feature_extractor_name in _VIT_OUTPUT:
+        feature_extractor = VisionTransformer(feature_extractor_name)
     else:
         raise ValueError(f"Invalid feature_extractor_name: {feature_extractor_name}")
-    assert feature_extractor.output_size == _EXTRACTOR_OUTPUT[feature_extractor_name]
+    assert feature_extractor.output_size == {**_EXTRACTOR_OUTPUT, **_VIT_OUTPUT}[feature_extractor_name]
 
     if not learn_extractor:
         freeze_extractor(feature_extractor)

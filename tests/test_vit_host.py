@@ -1,0 +1,149 @@
+"""CPU-side checks of the transformer extractors (vit_s_32, vit_b_32, vit_b_32_clip): the orbit_vit_* plan enumerates timm's
+state_dict and the reference's FiLM slots without touching the device, the Python module mirrors timm's parameter tree, the
+learner applies the reference's per-backbone settings and refuses what is out of scope, and the CPU pin (tests/vit_pin.py)
+equals Hugging Face's independent ViTModel / CLIPVisionModel."""
+import ctypes
+
+import pytest
+import torch
+
+import orbit_dataset_amd  # noqa: F401
+from orbit_dataset_amd import _lib
+
+import vit_pin
+
+NAMES = ("vit_s_32", "vit_b_32", "vit_b_32_clip")
+TOTALS = {"vit_s_32": 22493952, "vit_b_32": 87455232, "vit_b_32_clip": 87456000}
+MACS = {"vit_s_32": 1.1425e9, "vit_b_32": 4.4084e9, "vit_b_32_clip": 4.4084e9}
+
+
+def _create(lib, name, H=224, W=224):
+    h = ctypes.c_void_p()
+    rc = lib.orbit_vit_create(name.encode(), H, W, ctypes.byref(h))
+    return rc, h
+
+
+def _timm_shapes(name):
+    return {k: tuple(v.shape) for k, v in vit_pin.TimmViT(name).state_dict().items()}
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_plan_enumerates_timm_state_dict(lib, name):
+    rc, h = _create(lib, name)
+    assert rc == 0, _lib.last_error()
+    try:
+        keys = [lib.orbit_vit_param_name(h, i).decode() for i in range(lib.orbit_vit_num_params(h))]
+        numels = [lib.orbit_vit_param_numel(h, i) for i in range(lib.orbit_vit_num_params(h))]
+        shapes = _timm_shapes(name)
+        assert keys == list(shapes)  # timm's state_dict order
+        for k, n in zip(keys, numels):
+            assert n == torch.Size(shapes[k]).numel(), k
+        assert sum(numels) == TOTALS[name]
+        assert ("patch_embed.proj.bias" in keys) == (name != "vit_b_32_clip")
+        assert ("norm_pre.weight" in keys) == (name == "vit_b_32_clip")
+        D = lib.orbit_vit_output_size(h)
+        assert D == vit_pin.VIT[name][0]
+        n = lib.orbit_vit_film_slots(h)
+        slots = [lib.orbit_vit_film_slot_name(h, i).decode() for i in range(n)]
+        want = [s for i in range(12) for s in ("blocks.%d.norm1" % i, "blocks.%d.norm2" % i)] + ["norm"]
+        assert n == 25 and slots == want == vit_pin.TimmViT(name).film_slot_names()
+        assert all(lib.orbit_vit_film_slot_channels(h, i) == D for i in range(n))
+        assert lib.orbit_vit_film_size(h) == 25 * D
+        macs = lib.orbit_vit_macs_per_frame(h)
+        assert abs(macs - MACS[name]) / MACS[name] < 2e-3, macs
+        assert lib.orbit_vit_workspace_bytes(h, 200) >= 200 * 50 * 6 * D * 4
+    finally:
+        lib.orbit_vit_destroy(h)
+
+
+def test_create_rejects_sizes_and_names_and_extractor_create_keeps_rejecting(lib):
+    for size in (64, 84, 128, 256):
+        rc, _ = _create(lib, "vit_b_32", size, size)
+        assert rc != 0 and "224" in _lib.last_error()
+    rc, _ = _create(lib, "vit_l_16")
+    assert rc != 0 and "Invalid feature_extractor_name" in _lib.last_error()
+    rc, _ = _create(lib, "resnet18")
+    assert rc != 0
+    h = ctypes.c_void_p()
+    assert lib.orbit_extractor_create(b"vit_b_32", 224, 224, ctypes.byref(h)) != 0
+    assert "Invalid feature_extractor_name" in _lib.last_error()
+
+
+def test_forward_before_load_and_finalize_fails(lib):
+    rc, h = _create(lib, "vit_s_32")
+    assert rc == 0
+    try:
+        bad = (ctypes.c_float * 4)()
+        assert lib.orbit_vit_finalize(h, None) != 0 and "never loaded" in _lib.last_error()
+        assert lib.orbit_vit_forward(h, bad, 1, None, None, bad, bad, 1 << 30, None) != 0
+        assert "finalize" in _lib.last_error()
+        assert lib.orbit_vit_load(h, b"no.such.key", bad, 4) != 0 and "unexpected key" in _lib.last_error()
+        assert lib.orbit_vit_load(h, b"cls_token", bad, 4) != 0 and "expected 384" in _lib.last_error()
+    finally:
+        lib.orbit_vit_destroy(h)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_module_mirrors_timm_and_loads_timm_state_dict(lib, name):
+    from orbit_dataset_amd.model.feature_extractors import create_feature_extractor
+    fe, film_names = create_feature_extractor(name, pretrained=True, with_film=True, learn_extractor=False)
+    D = vit_pin.VIT[name][0]
+    assert fe.output_size == D and fe.film_size == 25 * D
+    assert {k: tuple(v.shape) for k, v in fe.state_dict().items()} == _timm_shapes(name)
+    assert len(film_names) == 50 and film_names[:2] == ["blocks.0.norm1.weight", "blocks.0.norm1.bias"]
+    assert film_names[-2:] == ["norm.weight", "norm.bias"]
+    assert [n for n, _ in fe.film_slot_modules()] == vit_pin.TimmViT(name).film_slot_names()
+    pin = vit_pin.TimmViT(name)
+    with torch.no_grad():
+        for p in pin.parameters():
+            p.normal_()
+    fe.load_state_dict(pin.state_dict(), strict=True)
+    assert all(torch.equal(a, b) for a, b in zip(fe.state_dict().values(), pin.state_dict().values()))
+    assert not fe.wants_grad(None)  # frozen
+    fe2, _ = create_feature_extractor(name, with_film=False, learn_extractor=True)
+    with pytest.raises(NotImplementedError, match=name):
+        fe2.wants_grad(None)
+    with torch.no_grad():
+        assert not fe2.wants_grad(None)
+
+
+def test_learner_flags(lib):
+    from orbit_dataset_amd.learner import build_multistep_parser, build_parser, verify_args
+    p = build_parser()
+    for name, norm in (("vit_s_32", "imagenet_inception"), ("vit_b_32", "imagenet_inception"),
+                       ("vit_b_32_clip", "openai_clip")):
+        a = p.parse_args(["--mode", "test", "--feature_extractor", name, "--adapt_features", "--classifier", "versa"])
+        verify_args(a)
+        assert a.frame_norm_method == norm
+    a = p.parse_args(["--feature_extractor", "efficientnet_b0", "--frame_norm_method", "openai_clip"])
+    verify_args(a)
+    assert a.frame_norm_method == "openai_clip"  # existing names keep today's behaviour
+    for bad in (["--frame_size", "84"], ["--mode", "train", "--adapt_features"], ["--mode", "train_test", "--learn_extractor"],
+                ["--learn_extractor"], ["--with_lite"]):
+        with pytest.raises(SystemExit):
+            verify_args(p.parse_args(["--feature_extractor", "vit_b_32"] + bad))
+    m = build_multistep_parser()
+    verify_args(m.parse_args(["--feature_extractor", "vit_s_32"]))
+    with pytest.raises(SystemExit):
+        verify_args(m.parse_args(["--feature_extractor", "vit_s_32", "--adapt_features"]))
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_cpu_pin_equals_hugging_face(name):
+    from orbit_dataset_amd import synthetic
+    from torch.func import functional_call
+    pin = vit_pin.TimmViT(name).eval()
+    synthetic.init_parameters_(pin)
+    hf = vit_pin.load_hf(name, vit_pin.hf_model(name), pin.state_dict())
+    x = torch.randn(2, 3, 224, 224, generator=torch.Generator().manual_seed(1))
+    film = {}
+    for slot in pin.film_slot_names():
+        film[slot + ".weight"] = 1 + 0.1 * torch.randn(pin.output_size)
+        film[slot + ".bias"] = 0.1 * torch.randn(pin.output_size)
+    with torch.no_grad():
+        assert (pin(x) - vit_pin.hf_features(name, hf, x)).abs().max().item() <= 1e-5
+        a = functional_call(pin, film, (x,))
+        out = functional_call(hf, vit_pin.film_swap_hf(name, film), (), {"pixel_values": x})
+        b = out.pooler_output if vit_pin.VIT[name][3] else out.last_hidden_state[:, 0]
+        assert (a - b).abs().max().item() <= 1e-5
+        assert (a - pin(x)).abs().max().item() > 0.1  # FiLM reaches the features

@@ -1,0 +1,143 @@
+"""Throughput of the transformer extractors (csrc/vit.hip) on config-3-shaped tasks: one JSON line.
+
+For each of vit_s_32 / vit_b_32 / vit_b_32_clip: a 5-way task with 200 support and 200 query frames at 224 x 224, run
+personalise() + predict() in test mode with ProtoNets (`proto`) and with CNAPs (`versa` + FiLM adaptation); the median ms per
+task after warm-up, query frames/s, per-family kernel time of one proto task from the library's per-launch event records
+(token GEMM, attention, LayerNorm, patch embedding), the token GEMMs' TF/s as a fraction of the 155 TF fp32 MFMA peak, and
+torch.nn.functional.linear (fp32, the vendor BLAS) on the same four shapes at M = 10 000 token rows as a reference point.
+
+    python tools/vit_bench.py [--steps 10] [--warmup 3] [--models vit_s_32,vit_b_32,vit_b_32_clip]
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+import orbit_dataset_amd  # noqa: E402,F401
+from orbit_dataset_amd import _lib, synthetic  # noqa: E402
+from orbit_dataset_amd.model.few_shot_recognisers import SingleStepFewShotRecogniser  # noqa: E402
+
+PEAK_TF = 155.0  # fp32 MFMA, measured (v_mfma_f32_32x32x2_f32)
+
+
+def _time(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms)
+
+
+def _model(name, adapt, classifier):
+    m = SingleStepFewShotRecogniser(name, adapt, classifier, 1, 200, False, 16, 1.0)
+    synthetic.init_parameters_(m)
+    m._set_device("cuda:0")
+    m._send_to_device()
+    m.set_test_mode(True)
+    return m
+
+
+def _task_fn(model, task):
+    def run():
+        with torch.no_grad():
+            model.personalise(task["context_clips"], task["context_labels"])
+            model.predict(task["target_clips"])
+            model._reset()
+    return run
+
+
+def _families(run):
+    """per-family kernel ms and flops of one call of `run` from orbit_prof_* records"""
+    lib = _lib.load()
+    torch.cuda.synchronize()
+    lib.orbit_prof_enable(1)
+    run()
+    torch.cuda.synchronize()
+    t, f, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_long()
+    lib.orbit_prof_collect(ctypes.byref(t), ctypes.byref(f), ctypes.byref(n))
+    fam = {}
+    for i in range(lib.orbit_prof_num_variants()):
+        name = ctypes.create_string_buffer(48)
+        launches, ms, flops, nbytes = ctypes.c_long(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        lib.orbit_prof_variant(i, name, ctypes.byref(launches), ctypes.byref(ms), ctypes.byref(flops), ctypes.byref(nbytes))
+        v = name.value.decode()
+        if not v.startswith("vit_"):
+            key = "other"
+        elif v.startswith(("vit_qkv", "vit_proj", "vit_fc1", "vit_fc2")):
+            key = "gemm"
+        elif v.startswith(("vit_patch_embed", "vit_cls_token")):
+            key = "patch"
+        else:
+            key = v[4:]
+        d = fam.setdefault(key, {"ms": 0.0, "flops": 0.0, "launches": 0})
+        d["ms"] += ms.value
+        d["flops"] += flops.value
+        d["launches"] += launches.value
+    lib.orbit_prof_enable(0)
+    return fam
+
+
+def _torch_linear(D, steps, warmup, M=10000):
+    torch.backends.cuda.matmul.allow_tf32 = False
+    out = {}
+    for tag, K, N in (("qkv", D, 3 * D), ("proj", D, D), ("fc1", D, 4 * D), ("fc2", 4 * D, D)):
+        x = torch.randn(M, K, device="cuda:0")
+        w = torch.randn(N, K, device="cuda:0") / K ** 0.5
+        b = torch.randn(N, device="cuda:0")
+        ms = _time(lambda: torch.nn.functional.linear(x, w, b), steps, warmup)
+        out[tag] = {"ms": round(ms, 4), "tflops": round(2.0 * M * N * K / ms / 1e9, 2)}
+    return out
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--steps", type=int, default=10)
+    p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--models", default="vit_s_32,vit_b_32,vit_b_32_clip")
+    a = p.parse_args(argv)
+    _lib.require_gpu()
+    torch.cuda.set_device(0)
+    result = {"metric": "vit_task_ms", "task": "5-way, 200 support + 200 query frames, 224x224", "peak_tflops": PEAK_TF,
+              "models": {}}
+    for name in a.models.split(","):
+        task = synthetic.make_task_on_device(0, 5, 5, 8, 200, 224, 1, "cuda:0")
+        r = {}
+        proto = _model(name, False, "proto")
+        run = _task_fn(proto, task)
+        r["proto_ms"] = round(_time(run, a.steps, a.warmup), 3)
+        r["query_frames_per_s"] = round(200.0 / (r["proto_ms"] / 2) * 1e3, 1)  # (support and query passes are the same size)
+        fam = _families(run)
+        r["kernel_ms"] = {k: round(v["ms"], 3) for k, v in sorted(fam.items())}
+        g = fam.get("gemm", {"ms": 0.0, "flops": 0.0})
+        tf = g["flops"] / g["ms"] / 1e9 if g["ms"] else 0.0
+        r["gemm_tflops"] = round(tf, 2)
+        r["gemm_fraction_of_peak"] = round(tf / PEAK_TF, 3)
+        macs = proto.feature_extractor.macs_per_frame(224, 224)
+        r["task_tflop"] = round(2 * macs * 400 / 1e12, 3)
+        r["task_floor_ms"] = round(2 * macs * 400 / (PEAK_TF * 1e12) * 1e3, 2)
+        del proto
+        cnaps = _model(name, True, "versa")
+        r["cnaps_ms"] = round(_time(_task_fn(cnaps, task), a.steps, a.warmup), 3)
+        del cnaps
+        r["torch_linear_m10000"] = _torch_linear(384 if name == "vit_s_32" else 768, a.steps, a.warmup)
+        result["models"][name] = r
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
