@@ -115,6 +115,10 @@ static bool fused_front_sweeps(const orbit_extractor* fe, size_t i, int bn_train
     if (d.act != ORBIT_ACT_SILU || d.Cin != o.Cout || !mbconv_rows_supported(o.H, o.W, o.Cin, o.Cout, d.KH, d.stride)) return false;
     if (fe->bns[o.bn].conv_bias >= 0) return false;
     if (opt == 1 && o.H < 56) return false;  // (the 28x28 blocks: statistics sweep + front measured no faster than the pair)
+    // the front's statistics rows (one per frame and strip-band tile) are sized for B * 16 tiles (max_bn_partial_floats below):
+    // wider maps (Wo = 113 / 120 for 452 / 480 pixel frames: 25 tiles) take the unfused pair before any statistics are touched
+    const int tiles = mbconv_rows_tiles(o.H, o.W, o.Cin, o.Cout, d.KH, d.stride);
+    if (tiles <= 0 || tiles > 16) return false;
     for (size_t j = i + 2; j < fe->ops.size(); ++j) {  // no later reader of the expanded tensor before its buffer is rewritten
         const Op& q = fe->ops[j];
         if (q.in == o.out || q.res == o.out) return false;

@@ -589,7 +589,9 @@ int launch_bn_stats_from_partials(float* partial, int nblk, int M, int C, float 
         const int GS = cdiv(nblk, BN_COMPACT_TO), nout = cdiv(nblk, GS), cols4 = 2 * C / 4;
         float* out = partial + (size_t)nblk * 2 * C;
         const size_t items = (size_t)nout * cols4;
+        const int rec = prof_start("bn_partial_compact", 2.0 * nblk * C, 4.0 * (nblk + nout) * 2.0 * C, s);
         bn_partial_compact_kernel<<<(unsigned)((items + 255) / 256), 256, 0, s>>>(partial, nblk, cols4, GS, nout, out);
+        prof_stop(rec, s);
         ORBIT_LAUNCH_CHECK();
         src = out, nblk = nout;
     }
@@ -717,7 +719,9 @@ int launch_bn_backward_reduced(const float* g, const float* y, const float* mean
         const int GS = cdiv(nblk, BN_COMPACT_TO), nout = cdiv(nblk, GS), cols4 = 2 * C / 4;
         float* out = partial + (size_t)nblk * 2 * C;
         const size_t items = (size_t)nout * cols4;
+        const int rec = prof_start("bn_partial_compact", 2.0 * nblk * C, 4.0 * (nblk + nout) * 2.0 * C, s);
         bn_partial_compact_kernel<<<(unsigned)((items + 255) / 256), 256, 0, s>>>(partial, nblk, cols4, GS, nout, out);
+        prof_stop(rec, s);
         ORBIT_LAUNCH_CHECK();
         src = out, nblk = nout;
     }
@@ -787,7 +791,9 @@ int launch_bn_backward_reduced_gated(const float* dxg, const float* gate, const 
         const int GS = cdiv(nblk, BN_COMPACT_TO), nout = cdiv(nblk, GS), cols4 = 2 * C / 4;
         float* out = partial + (size_t)nblk * 2 * C;
         const size_t items = (size_t)nout * cols4;
+        const int rec = prof_start("bn_partial_compact", 2.0 * nblk * C, 4.0 * (nblk + nout) * 2.0 * C, s);
         bn_partial_compact_kernel<<<(unsigned)((items + 255) / 256), 256, 0, s>>>(partial, nblk, cols4, GS, nout, out);
+        prof_stop(rec, s);
         ORBIT_LAUNCH_CHECK();
         src = out, nblk = nout;
     }

@@ -424,10 +424,119 @@ def test_backward_is_deterministic(device):
     assert torch.equal(grads[0], grads[1])
 
 
-@pytest.mark.parametrize("size,B,bn_train", [(64, 4, True), (96, 3, False)])
-def test_efficientnet_backward_matches_autograd(device, bn_train, size, B):
+def _prof_rows(lib):
+    """{profiling row: launches} since orbit_prof_enable(1)."""
+    import ctypes
+    lib.orbit_prof_collect(None, None, None)
+    buf, n = ctypes.create_string_buffer(48), ctypes.c_long(0)
+    rows = {}
+    for i in range(lib.orbit_prof_num_variants()):
+        lib.orbit_prof_variant(i, buf, ctypes.byref(n), None, None, None)
+        rows[buf.value.decode()] = rows.get(buf.value.decode(), 0) + n.value
+    return rows
+
+
+_EFFNET_ORACLE = {}  # (size, B) -> fp64 train-mode results of the module's oracle, computed once per module
+
+
+def _efficientnet_oracle(ref, size, B, backward, device):
+    """The fp64 oracle's train-mode (batch-statistics BatchNorm) forward, and with `backward` its parameter gradients, for
+    the inputs test_efficientnet_backward_matches_autograd draws at (size, B, seed 0): {"out", "running", "grads"}. Run on the
+    GPU: torch's fp64 convolutions there are its own kernels, not MIOpen (pinned to the CPU oracle by
+    test_fp64_oracle_on_the_gpu_matches_the_cpu_oracle). Cached per (size, B)."""
+    hit = _EFFNET_ORACLE.get((size, B))
+    if hit is not None and (hit["grads"] is not None or not backward):
+        return hit
+    x, dfeat = _effnet_inputs(size, B)
+    m = ref.double().to(device).train()
+    m.zero_grad()
+    with torch.set_grad_enabled(backward):
+        out = m(x.double().to(device))
+        if backward:
+            out.backward(dfeat.double().to(device))
+    hit = {"out": out.detach().cpu(),
+           "running": {k: v.detach().cpu().clone() for k, v in m.state_dict().items() if "running" in k},
+           "grads": {n: p.grad.detach().cpu().clone() for n, p in m.named_parameters()} if backward else None}
+    del m, out
+    torch.cuda.empty_cache()
+    _EFFNET_ORACLE[(size, B)] = hit
+    return hit
+
+
+def _effnet_inputs(size, B, seed=0):
+    x = torch.randn(B, 3, size, size, generator=torch.Generator().manual_seed(7 * size + seed))
+    dfeat = torch.randn(B, 1280, generator=torch.Generator().manual_seed(seed))
+    return x, dfeat
+
+
+def _gradient_errors(got, want):
+    """{name: error} of every parameter gradient against the fp64 oracle's. Some gradients vanish in exact arithmetic (a
+    bias in front of a 1x1 conv + batch-statistics BatchNorm): those (reference magnitude < 1e-5 of the largest gradient in
+    the net) must come out as rounding noise of that scale; every other tensor is measured against its own largest
+    magnitude."""
+    top = max(float(g.abs().max()) for g in want.values())
+    errs = {}
+    for name, g in got.items():
+        diff = float((g.double().cpu() - want[name]).abs().max())
+        mag = float(want[name].abs().max())
+        errs[name] = diff / mag if mag > 1e-5 * top else 2e-4 * diff / (1e-5 * top)
+    return errs
+
+
+def test_fp64_oracle_on_the_gpu_matches_the_cpu_oracle(device):
+    """The large cases below run the fp64 oracle module on the GPU (on the CPU, 200 frames at 224 forward + backward take
+    minutes and tens of GB: 8 frames take 17 s and 2.5 GB on 8 threads). Same module, same inputs, B = 2 at 64 px: features
+    and every running statistic within 1e-10 of the CPU's, every gradient within 1e-10 of its own largest entry - or, for
+    the gradients that vanish in exact arithmetic (see _gradient_errors), of 1e-5 of the largest gradient in the net."""
+    ref, _ = _oracle_and_native("efficientnet_b0", device)
+    rsd = {k: v.clone() for k, v in ref.state_dict().items()}
+    x, dfeat = _effnet_inputs(64, 2)
+    res = {}
+    for dev in ("cpu", device):
+        ref.load_state_dict(rsd)
+        m = ref.double().to(dev).train()
+        m.zero_grad()
+        out = m(x.double().to(dev))
+        out.backward(dfeat.double().to(dev))
+        res[str(dev)] = (out.detach().cpu().clone(), {n: p.grad.cpu().clone() for n, p in m.named_parameters()},
+                         {k: v.cpu().clone() for k, v in m.state_dict().items() if "running" in k})
+        ref = m.cpu()
+    (o_c, g_c, r_c), (o_g, g_g, r_g) = res["cpu"], res[str(device)]
+    assert rel(o_g, o_c) < 1e-10
+    top = max(float(g.abs().max()) for g in g_c.values())
+    assert max(float((g_g[n] - g_c[n]).abs().max()) / max(float(g_c[n].abs().max()), 1e-5 * top) for n in g_c) < 1e-10
+    assert max(rel(r_g[k], r_c[k]) for k in r_c) < 1e-10
+
+
+# (size, B, bn_train, profiling rows the native forward + backward must launch). The LITE step at 224 px (bench.py --mode
+# lite_train) runs the taped pair on the 16-frame H subset and on up to 200 query frames:
+# * h_subset: the H-subset shape; the dense filter gradients' split geometry at B = 16. Its conv epilogues emit one statistics
+#   partial per 128 rows at most (1 568 on a 112-px layer), below the 2 048 above which the BatchNorm finalizes compact them:
+#   bn_partial_compact does NOT run here (measured) - thin112 / thin56 / odd reach it;
+# * thin112 / thin56: >= 2^18 rows - the thin pointwise filter-gradient kernel on the 112-px layers (B >= 21; 2 launches), on
+#   the 56-px layers as well (B >= 84; 6 launches; 200 = the benchmarked query batch, dense filter gradients at their split cap);
+# * odd: 231 px - 116 / 58 / 29 / 15 / 8-pixel maps, multiples of no tile, strip or row-block width;
+# * big: 480 px - the taped pair on 240-px maps, wider than the 448 px the two-sweep fused front's tiling serves (the taped
+#   forward never takes the fused front; its widest depthwise launch is block 1.0's stride-2 3x3).
+EFFNET_BACKWARD_CASES = [
+    pytest.param(64, 4, True, (), id="64-4-True"),
+    pytest.param(96, 3, False, (), id="96-3-False"),
+    pytest.param(224, 16, True, ("conv_wgrad<nhwc>",), id="h_subset"),
+    pytest.param(224, 24, True, ("conv_wgrad_thin", "bn_partial_compact"), id="thin112"),
+    pytest.param(224, 200, True, ("conv_wgrad_thin", "bn_partial_compact"), id="thin56"),
+    pytest.param(231, 24, True, ("conv_wgrad_thin", "bn_partial_compact"), id="odd"),
+    pytest.param(480, 2, True, ("dwconv<3x3/2>,train",), id="big"),
+]
+
+
+@pytest.mark.parametrize("size,B,bn_train,rows", EFFNET_BACKWARD_CASES)
+def test_efficientnet_backward_matches_autograd(device, lib, bn_train, size, B, rows):
     """Depthwise / squeeze-excite / SiLU backward through the whole tf_efficientnet_b0 plan. No ReLU here, so there
-    are no mask flips: every seed has to be close to fp32-exact (the fast exp/rcp of SiLU and sigmoid costs a little)."""
+    are no mask flips: every seed has to be close to fp32-exact (the fast exp/rcp of SiLU and sigmoid costs a little).
+    The cases with profiling rows run the oracle on the GPU (see _efficientnet_oracle) and must show those rows' launchers
+    launched during the native forward + backward (EFFNET_BACKWARD_CASES). The dense filter gradients' split counts and the
+    depthwise chunk / block counts follow from B * H * W and have no row of their own: that they take their large-batch
+    values is not checked here."""
     ref, nat = _oracle_and_native("efficientnet_b0", device)
     ref = ref.double()
     sd, rsd = {k: v.clone() for k, v in nat.state_dict().items()}, {k: v.clone() for k, v in ref.state_dict().items()}
@@ -436,31 +545,36 @@ def test_efficientnet_backward_matches_autograd(device, bn_train, size, B):
         nat.load_state_dict(sd), ref.load_state_dict(rsd)
         nat.zero_grad(), ref.zero_grad()
         ref.train(bn_train), nat.train(bn_train)
-        x = torch.randn(B, 3, size, size, generator=torch.Generator().manual_seed(7 * size + seed))
-        dfeat = torch.randn(B, 1280, generator=torch.Generator().manual_seed(seed))
-        out_ref = ref(x.double())
-        out_ref.backward(dfeat.double())
-        out = nat(x.to(device))
-        assert rel(out.detach(), out_ref.detach()) < 5e-5
-        out.backward(dfeat.to(device))
-        ref_grads = dict(ref.named_parameters())
-        # some gradients vanish in exact arithmetic (a bias in front of a 1x1 conv + batch-statistics BatchNorm): those
-        # (reference magnitude < 1e-5 of the largest gradient in the net) must come out as rounding noise of that scale;
-        # every other tensor is measured against its own largest magnitude
-        top = max(float(g.grad.abs().max()) for g in ref_grads.values())
-        errs = {}
-        for name, p in nat.named_parameters():
-            want = ref_grads[name].grad
-            diff = float((p.grad.double().cpu() - want).abs().max())
-            mag = float(want.abs().max())
-            errs[name] = diff / mag if mag > 1e-5 * top else 2e-4 * diff / (1e-5 * top)
+        x, dfeat = _effnet_inputs(size, B, seed)
+        if not rows:
+            out_ref = ref(x.double())
+            out_ref.backward(dfeat.double())
+            want = {"out": out_ref.detach(), "grads": {n: p.grad for n, p in ref.named_parameters()},
+                    "running": ref.state_dict()}
+        else:
+            want = _efficientnet_oracle(ref, size, B, backward=True, device=device)
+            lib.orbit_prof_enable(1)
+        try:
+            out = nat(x.to(device))
+            assert rel(out.detach(), want["out"]) < 5e-5
+            out.backward(dfeat.to(device))
+            if rows:
+                torch.cuda.synchronize()
+                launches = {r: n for r, n in _prof_rows(lib).items() if r in rows}
+                assert all(launches.get(r, 0) > 0 for r in rows), ("did not run", rows, launches)
+        finally:
+            lib.orbit_prof_enable(0)
+        errs = _gradient_errors({n: p.grad for n, p in nat.named_parameters()}, want["grads"])
         if bn_train:
-            ref_sd = ref.state_dict()
             for name, buf in nat.state_dict().items():
                 if "running" in name:
-                    assert rel(buf, ref_sd[name]) < 2e-5, name
+                    assert rel(buf, want["running"][name]) < 2e-5, name
         worst = max(errs, key=errs.get)
         assert errs[worst] < 2e-4, (worst, errs[worst])
+        if rows:
+            stat = max(rel(b, want["running"][k]) for k, b in nat.state_dict().items() if "running" in k)
+            print("\n[effnet-backward %d x %d] launches %s, features %.3g, gradient %.3g (%s), running statistics %.3g"
+                  % (B, size, launches, rel(out.detach(), want["out"]), errs[worst], worst, stat))
         return errs[worst]
 
     run(0)
@@ -576,15 +690,16 @@ def test_no_backward_forward_is_bit_identical_to_the_taped_forward(device, B, si
         lib.orbit_set_option(b"train_fused_fronts", fronts)
 
 
-@pytest.mark.parametrize("B,size", [(5, 224), (4, 160), (3, 97)])
+@pytest.mark.parametrize("B,size", [(5, 224), (4, 160), (3, 97), (2, 480)])
 def test_no_backward_forward_on_two_sweep_fused_fronts(device, B, size):
     """Round 6 (option train_fused_fronts): on a no-grad batch-statistics forward the expansion conv + depthwise conv of an
     MBConv block run as a STATISTICS SWEEP of the expansion conv (nothing stored) + the row-streaming fused front in its RAW form.
     Against the unfused pair: the first BatchNorm of every fused block sees the SAME statistics bit for bit (same conv kernel,
     same tiles - checked on its running statistics), everything downstream agrees to summation order of the second BatchNorm's
     statistics (features and running statistics to 1e-5 relative). 224: the exact-tiling instantiations; 160 / 97: the guarded
-    ones. Option 2 = every shape the fused front serves (the default, 1, takes the 112x112 / 56x56 blocks); 3 = as 2 with the conv's
-    own statistics sweep instead of the Gram-matrix statistics."""
+    ones; 480: maps wider than the front's tiling serves (block 1.0: 25 strip-band tiles), where the unfused pair must be
+    taken. Option 2 = every shape the fused front serves (the default, 1, takes the 112x112 / 56x56 blocks); 3 = as 2 with the
+    conv's own statistics sweep instead of the Gram-matrix statistics."""
     from orbit_dataset_amd import _lib
     from orbit_dataset_amd.model.feature_extractors import create_feature_extractor
     lib = _lib.load()
@@ -628,6 +743,41 @@ def test_no_backward_forward_on_two_sweep_fused_fronts(device, B, size):
     # another order), i.e. the fused path ran
     assert not torch.equal(outs[2][1]["blocks.1.0.bn2.running_var"], sd_base["blocks.1.0.bn2.running_var"]) or \
         not torch.equal(outs[2][0], base)
+
+
+@pytest.mark.parametrize("B,size", [(200, 224), (2, 480)])
+def test_no_backward_forward_matches_autograd(device, lib, B, size):
+    """The LITE cache pass (ORBIT_TRAIN_NO_BACKWARD: train-mode forward under torch.no_grad()) against the fp64 oracle's
+    train-mode forward, for every train_fused_fronts value: features at 5e-5, every running statistic at 2e-5. 200 x 224:
+    the benchmarked context set - the Gram-matrix statistics of block 1.0 sum 2.5 M pixels (option 1 must run bn_gram and the
+    raw fused front); 2 x 480: maps wider than the fused front's tiling serves."""
+    ref, nat = _oracle_and_native("efficientnet_b0", device)
+    want = _efficientnet_oracle(ref, size, B, backward=False, device=device)
+    sd0 = {k: v.clone() for k, v in nat.state_dict().items()}
+    x = _effnet_inputs(size, B)[0].to(device)
+    prev = lib.orbit_get_option(b"train_fused_fronts")
+    try:
+        for opt in (0, 1, 2, 3):
+            lib.orbit_set_option(b"train_fused_fronts", opt)
+            nat.load_state_dict(sd0)
+            nat.train()
+            lib.orbit_prof_enable(1)
+            with torch.no_grad():
+                feats = nat(x)
+            torch.cuda.synchronize()
+            rows = {r: n for r, n in _prof_rows(lib).items() if r in ("bn_gram", "mbconv_rows,raw")}
+            lib.orbit_prof_enable(0)
+            if opt == 1 and size == 224:
+                assert rows.get("bn_gram", 0) > 0 and rows.get("mbconv_rows,raw", 0) > 0, rows
+            stats = {k: rel(v, want["running"][k]) for k, v in nat.state_dict().items() if "running" in k}
+            worst = max(stats, key=stats.get)
+            print("\n[no-backward %d x %d, option %d] %s, features %.3g, running statistics %.3g (%s)"
+                  % (B, size, opt, rows, rel(feats, want["out"]), stats[worst], worst))
+            assert rel(feats, want["out"]) < 5e-5, opt
+            assert stats[worst] < 2e-5, (opt, worst, stats[worst])
+    finally:
+        lib.orbit_prof_enable(0)
+        lib.orbit_set_option(b"train_fused_fronts", prev)
 
 
 @pytest.mark.parametrize("Cin,C,P", [(16, 96, 50_000), (24, 144, 31_337), (24, 144, 9_999), (16, 96, 257)])
