@@ -310,6 +310,22 @@ int orbit_op_avgpool(const float* x, float* y, int B, int HW, int C, orbit_strea
 int orbit_op_se_gate(const float* pooled, const float* w1, const float* b1, const float* w2,
                      const float* b2, float* gate, int B, int C, int R, orbit_stream_t stream);
 
+/* The transformer extractors' kernels one by one (csrc/vit.hip), token rows row-major fp32.
+ * y [M][N] = x [M][K] . w [N][K]^T + bias (NULL = 0); epilogue 0: nothing more, 1: erf-GELU, 2: + residual [M][N] (may alias y;
+ * NULL unless epilogue 2). N % 128 == 0, K % 32 == 0, x and w 16-byte aligned. tile_rows: 0 = the forward's rule (128-row
+ * tiles when they make at least 512 workgroups, else 64-row), 64 or 128 = that tile height. */
+int orbit_op_vit_linear(const float* x, const float* w, const float* bias, const float* residual, float* y, int M, int N,
+                        int K, int epilogue, int tile_rows, orbit_stream_t stream);
+/* frames NCHW [B][3][224][224], w OIHW [D][3][32][32], pos_embed [50][D], cls_token [D] -> tokens [B][50][D]: row 0 =
+ * cls_token + pos_embed[0], row 1+p = patch p (row-major 7x7) . w + bias + pos_embed[1+p]. D is 384 or 768. */
+int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,
+                             const float* cls_token, float* tokens, int B, int D, int tile_rows, orbit_stream_t stream);
+/* LayerNorm over the D (384 or 768) values of each row; row r at x + r * x_stride / y + r * y_stride floats; y may alias x. */
+int orbit_op_vit_layernorm(const float* x, size_t x_stride, float* y, size_t y_stride, int rows, int D, const float* gamma,
+                           const float* beta, float eps, orbit_stream_t stream);
+/* qkv [B][50][3][heads][64] -> out [B][50][heads][64] = softmax(q k^T / 8) v per (frame, head); D = 64 heads, 384 or 768. */
+int orbit_op_vit_attention(const float* qkv, float* out, int B, int D, int heads, orbit_stream_t stream);
+
 /* fused MBConv front half (EfficientNet InvertedResidual, Cin <= 40): y = silu(bn2(dw_KxK(silu(bn1(x . w1^T))))) with the
  * expanded tensor kept in LDS. x NHWC [B][H][W][Cin]; w1 torch [mid][Cin][1][1]; wdw torch [mid][1][K][K];
  * scale/shift = folded BatchNorms [mid]; y NHWC [B][Ho][Wo][mid]; pool_partial [B][tiles][mid] or NULL: partial sums

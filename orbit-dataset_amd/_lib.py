@@ -78,6 +78,10 @@ _SIGNATURES = {
     "orbit_op_maxpool2d": (c_int, [P, P] + [c_int] * 9 + [P]),
     "orbit_op_avgpool": (c_int, [P, P, c_int, c_int, c_int, P]),
     "orbit_op_se_gate": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P]),
+    "orbit_op_vit_linear": (c_int, [P] * 5 + [c_int] * 5 + [P]),
+    "orbit_op_vit_patch_embed": (c_int, [P] * 6 + [c_int] * 3 + [P]),
+    "orbit_op_vit_layernorm": (c_int, [P, c_size_t, P, c_size_t, c_int, c_int, P, P, c_float, P]),
+    "orbit_op_vit_attention": (c_int, [P, P, c_int, c_int, c_int, P]),
     "orbit_op_mbconv_front": (c_int, [P] * 9 + [c_int] * 11 + [P]),
     "orbit_op_mbconv_front_partials": (c_int, [c_int] * 6),
     "orbit_op_stem_dw_front_partials": (c_int, [c_int] * 3),

@@ -176,12 +176,15 @@ __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
         }
 }
 
+// tile_rows: 0 = the rule below, 64 / 128 = that instantiation (the single-operator entry points; the forward passes 0)
 template <int EPI>
-int launch_gemm(const GemmArgs& a, const char* what, hipStream_t s) {
+int launch_gemm(const GemmArgs& a, const char* what, hipStream_t s, int tile_rows = 0) {
     if (a.N % G_BN || a.K % G_BK || a.M <= 0) return set_err(ORBIT_ERR_ARG, "vit gemm: unsupported shape M=%d N=%d K=%d", a.M, a.N, a.K);
+    if (tile_rows != 0 && tile_rows != 64 && tile_rows != 128)
+        return set_err(ORBIT_ERR_ARG, "vit gemm: tile_rows must be 0, 64 or 128, got %d", tile_rows);
     // tile height: 128 rows unless that leaves fewer than two tiles per CU (the D x D and 4D x D layers at ~10k rows)
     const int n_tiles = a.N / G_BN;
-    const bool tall = (long)cdiv(a.M, 128) * n_tiles >= 512;
+    const bool tall = tile_rows ? tile_rows == 128 : (long)cdiv(a.M, 128) * n_tiles >= 512;
     const double flops = 2.0 * a.M * a.N * a.K;
     const double bytes = 4.0 * ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N * (EPI == EPI_RESIDUAL ? 2 : 1));
     char name[48];
@@ -225,7 +228,10 @@ __global__ __launch_bounds__(256) void vit_layernorm_kernel(const float* x, size
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NPL; ++i) v[i] = xr[lane + 64 * i], s += v[i];
-    const float mean = wave_sum(s) * (1.f / D);
+    // a division, not * (1.f / D): the compiler contracts that product into the subtraction below (fma(-sum, 1/D, v)), which
+    // subtracts the UNROUNDED sum * fl(1/D) - for a constant row c that leaves v = -c * 2^-25 instead of 0, and at variance 0 the
+    // 1/sqrt(eps) = 1000 behind it turns that into 1e-4 * gamma (tests/test_gpu_vit_ops.py, constant rows must give beta)
+    const float mean = wave_sum(s) / D;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NPL; ++i) v[i] -= mean, q += v[i] * v[i];
@@ -550,6 +556,74 @@ int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* f
     ln_params("norm", 2 * VIT_DEPTH, &g, &be);
     // final LayerNorm on the class token of every frame, straight into the caller's feature rows
     return launch_layernorm(x, (size_t)VIT_N * D, feats, D, B, D, g, be, v->eps, s);
+}
+
+// ---- single operators (parity tests) ---------------------------------------------------------------------------------
+int orbit_op_vit_linear(const float* x, const float* w, const float* bias, const float* residual, float* y, int M, int N,
+                        int K, int epilogue, int tile_rows, orbit_stream_t stream) {
+    ORBIT_REQUIRE(x && w && y, "op_vit_linear: null pointer");
+    ORBIT_REQUIRE(M > 0 && M <= VIT_MAX_B * VIT_N && N > 0 && K > 0, "op_vit_linear: bad shape M=%d N=%d K=%d", M, N, K);
+    ORBIT_REQUIRE(N % G_BN == 0 && K % G_BK == 0, "op_vit_linear: N must be a multiple of %d and K of %d, got N=%d K=%d", G_BN,
+                  G_BK, N, K);
+    ORBIT_REQUIRE(epilogue == EPI_BIAS || epilogue == EPI_GELU || epilogue == EPI_RESIDUAL,
+                  "op_vit_linear: epilogue must be 0 (bias), 1 (erf-GELU) or 2 (residual), got %d", epilogue);
+    ORBIT_REQUIRE((epilogue == EPI_RESIDUAL) == (residual != nullptr), "op_vit_linear: residual goes with epilogue 2 only");
+    ORBIT_REQUIRE(tile_rows == 0 || tile_rows == 64 || tile_rows == 128, "op_vit_linear: tile_rows must be 0, 64 or 128, got %d",
+                  tile_rows);
+    ORBIT_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "op_vit_linear: x and w must be 16-byte aligned");
+    ORBIT_REQUIRE(((uintptr_t)y & 3) == 0 && ((uintptr_t)bias & 3) == 0 && ((uintptr_t)residual & 3) == 0,
+                  "op_vit_linear: y, bias and residual must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const GemmArgs a{x, w, bias, residual, nullptr, y, M, N, K};
+    if (epilogue == EPI_GELU) return launch_gemm<EPI_GELU>(a, "op_linear_gelu", s, tile_rows);
+    if (epilogue == EPI_RESIDUAL) return launch_gemm<EPI_RESIDUAL>(a, "op_linear_residual", s, tile_rows);
+    return launch_gemm<EPI_BIAS>(a, "op_linear", s, tile_rows);
+}
+
+int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,
+                             const float* cls_token, float* tokens, int B, int D, int tile_rows, orbit_stream_t stream) {
+    ORBIT_REQUIRE(frames && w && pos_embed && cls_token && tokens, "op_vit_patch_embed: null pointer");
+    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "op_vit_patch_embed: batch of %d frames (1..%d)", B, VIT_MAX_B);
+    ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_patch_embed: unsupported width %d (384 or 768)", D);
+    ORBIT_REQUIRE(tile_rows == 0 || tile_rows == 64 || tile_rows == 128,
+                  "op_vit_patch_embed: tile_rows must be 0, 64 or 128, got %d", tile_rows);
+    ORBIT_REQUIRE(((uintptr_t)frames & 15) == 0 && ((uintptr_t)w & 15) == 0,
+                  "op_vit_patch_embed: frames and w must be 16-byte aligned");
+    ORBIT_REQUIRE(((uintptr_t)tokens & 3) == 0 && ((uintptr_t)bias_or_null & 3) == 0 && ((uintptr_t)pos_embed & 3) == 0 &&
+                      ((uintptr_t)cls_token & 3) == 0,
+                  "op_vit_patch_embed: tokens, bias, pos_embed and cls_token must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const GemmArgs a{frames, w, bias_or_null, nullptr, pos_embed, tokens, B * VIT_P, D, VIT_KPATCH};
+    if (int rc = launch_gemm<EPI_PATCH>(a, "op_patch_embed", s, tile_rows)) return rc;
+    vit_cls_kernel<<<cdiv(B * D, 256) < 1024 ? cdiv(B * D, 256) : 1024, 256, 0, s>>>(cls_token, pos_embed, tokens, B, D);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
+int orbit_op_vit_layernorm(const float* x, size_t x_stride, float* y, size_t y_stride, int rows, int D, const float* gamma,
+                           const float* beta, float eps, orbit_stream_t stream) {
+    ORBIT_REQUIRE(x && y && gamma && beta, "op_vit_layernorm: null pointer");
+    ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_layernorm: unsupported width %d (384 or 768)", D);
+    ORBIT_REQUIRE(rows > 0 && rows <= VIT_MAX_B * VIT_N, "op_vit_layernorm: %d rows (1..%d)", rows, VIT_MAX_B * VIT_N);
+    ORBIT_REQUIRE(x_stride >= (size_t)D && y_stride >= (size_t)D, "op_vit_layernorm: row strides must be at least D");
+    ORBIT_REQUIRE(eps >= 0.f, "op_vit_layernorm: negative eps");
+    ORBIT_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 3) == 0,
+                  "op_vit_layernorm: pointers must be 4-byte aligned");
+    return launch_layernorm(x, x_stride, y, y_stride, rows, D, gamma, beta, eps, (hipStream_t)stream);
+}
+
+int orbit_op_vit_attention(const float* qkv, float* out, int B, int D, int heads, orbit_stream_t stream) {
+    ORBIT_REQUIRE(qkv && out, "op_vit_attention: null pointer");
+    ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_attention: unsupported width %d (384 or 768)", D);
+    ORBIT_REQUIRE(heads * VIT_HD == D, "op_vit_attention: %d heads of %d do not make D=%d", heads, VIT_HD, D);
+    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "op_vit_attention: batch of %d frames (1..%d)", B, VIT_MAX_B);
+    ORBIT_REQUIRE((((uintptr_t)qkv | (uintptr_t)out) & 3) == 0, "op_vit_attention: pointers must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int pi = prof_start("vit_attention", 4.0 * B * heads * VIT_N * VIT_N * VIT_HD, 4.0 * 4 * (double)B * VIT_N * D, s);
+    vit_attention_kernel<<<B * heads, 256, 0, s>>>(qkv, out, D, heads);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
 }
 
 }  // extern "C"

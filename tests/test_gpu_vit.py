@@ -1,6 +1,9 @@
 """GPU parity of the transformer extractors (csrc/vit.hip): features against the Hugging Face fixture G15 and the live CPU pin
-(tests/vit_pin.py), batch-size independence, the FiLM fast path, and the recogniser end to end against OracleRecogniser with
-the pin injected as its extractor (logits within 1e-3, identical argmax: the project's parity gate)."""
+(tests/vit_pin.py), batch-size independence - also across the GEMM tile-height switch, at the 256 / 448 frames where every
+128-row instantiation runs - the FiLM fast path, parameters stressed towards a trained ViT (peaked attention, outlier channels,
+LayerNorm variance near eps) against the pin in float64, and the recogniser end to end against OracleRecogniser with the pin
+injected as its extractor (logits within 1e-3, identical argmax: the project's parity gate). The kernels one by one:
+tests/test_gpu_vit_ops.py."""
 import importlib.util
 import os
 
@@ -13,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 import orbit_dataset_amd  # noqa: E402,F401
 import vit_pin  # noqa: E402
+from test_gpu_vit_ops import _prof_rows  # noqa: E402
 from oracle import blocks  # noqa: E402
 from oracle.recogniser import OracleRecogniser  # noqa: E402
 from orbit_dataset_amd import synthetic  # noqa: E402
@@ -108,6 +112,92 @@ def test_features_match_cpu_pin_and_do_not_depend_on_the_batch(device, name, siz
             assert torch.equal(fe(frames[:3].cuda()).cpu(), big[:3])
         finally:
             fe.eval()
+
+
+GEMMS = ("patch_embed", "qkv", "proj", "fc1", "fc2")
+
+
+@pytest.mark.parametrize("name,B", [("vit_b_32", 256), ("vit_s_32", 448), ("vit_b_32_clip", 256)])
+def test_features_across_the_tile_height_switch(device, lib, name, B):
+    """At 256 (ViT-B) / 448 (ViT-S) frames every token GEMM and the patch embedding take the 128-row tile; the same frames in
+    chunks of 67 take the 64-row tile (but ViT-B's fc1). The profiling rows say which ran, and every chunk's features are
+    BITWISE the matching rows of the big run: the 67-frame path is pinned to the CPU reference above, and equality carries
+    that to the tall kernels (3 frames of the big run are also compared with the pin directly)."""
+    fe, pin = _pair(name)
+    frames = torch.randn(B, 3, 224, 224, device=device, generator=torch.Generator(device=device).manual_seed(5))
+    with torch.no_grad():
+        lib.orbit_prof_enable(1)
+        try:
+            big = fe(frames)
+            torch.cuda.synchronize()
+            rows = {r: n for r, n in _prof_rows(lib).items() if r.endswith(">")}
+            assert rows == dict([("vit_patch_embed<128>", 1)] + [("vit_%s<128>" % g, 12) for g in GEMMS[1:]]), rows
+            lib.orbit_prof_enable(1)
+            chunks = [(i, fe(frames[i:i + 67])) for i in range(0, B, 67)]
+            torch.cuda.synchronize()
+            rows = {r: n for r, n in _prof_rows(lib).items() if r.endswith(">")}
+        finally:
+            lib.orbit_prof_enable(0)
+        n = len(chunks)
+        want_rows = {"vit_patch_embed<64>": n}
+        for g in GEMMS[1:]:
+            want_rows["vit_%s<%d>" % (g, 128 if g == "fc1" and name != "vit_s_32" else 64)] = 12 * n
+        assert rows == want_rows, rows
+        for i, got in chunks:
+            assert torch.equal(got, big[i:i + 67]), "frames %d.. differ between a 67-frame batch and the %d-frame batch" % (i, B)
+        err = (big[:3].cpu() - pin(frames[:3].cpu())).abs().max().item()
+        assert err <= FEAT_TOL, err
+
+
+QK_FACTOR, POS_BUMP, POS_CHANNELS, SMALL = 1.75, 8.0, (3, 77, 190, 301), 1e-3
+
+
+def _stressed(name, sd, case):
+    """Parameters edited after init_parameters_. The factors were chosen on the CPU so that 4 x the fp32 pin's own error (the
+    gate below) stays within FEAT_TOL on all three models. Case 'peaked': attention logits reach +-15 (mean top probability
+    0.47) and four residual channels sit at 8 in a stream of std 1 .. 1.6; the fp32 pin is 0.7e-5 / 1.3e-5 / 1.1e-5 (ViT-S /
+    ViT-B / CLIP) from the float64 pin (at a q/k factor of 2 it is 3.2e-5 on ViT-B, at 2.5 above 1e-4: peaked attention
+    amplifies rounding, so the factor stops here). Case 'near_eps': token variance ~1e-6 at the first LayerNorms; the fp32 pin is
+    0.33e-5 / 0.38e-5 / 0.38e-5 off, and the in21k / CLIP eps exchanged move the features by 1.4 .. 2.1 (5e-4 unstressed)."""
+    sd = {k: v.clone() for k, v in sd.items()}
+    D = vit_pin.VIT[name][0]
+    if case == "peaked":
+        for k in sd:
+            if k.endswith("attn.qkv.weight") or k.endswith("attn.qkv.bias"):
+                sd[k][:2 * D] *= QK_FACTOR  # the q and k rows
+        sd["pos_embed"][..., list(POS_CHANNELS)] += POS_BUMP
+    else:
+        for k in ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias"):
+            if k in sd:
+                sd[k] *= SMALL
+    return sd
+
+
+@pytest.mark.parametrize("case", ["peaked", "near_eps"])
+@pytest.mark.parametrize("name", NAMES)
+def test_stressed_parameters_match_the_float64_pin(device, name, case):
+    """Gate: 4 x the fp32 CPU pin's own error against the float64 pin on the same inputs (the reasoning of
+    tests/test_gpu_vit_ops.py), never looser than FEAT_TOL."""
+    fe, pin = _pair(name)
+    base = {k: v.clone() for k, v in pin.state_dict().items()}
+    sd = _stressed(name, base, case)
+    frames = torch.randn(3, 3, 224, 224, generator=torch.Generator().manual_seed(11))
+    ref = vit_pin.TimmViT(name).eval()
+    ref.load_state_dict(sd)
+    with torch.no_grad():
+        fp32 = ref(frames)
+        want = ref.double()(frames.double())
+        e32 = (fp32.double() - want).abs().max().item()
+        tol = min(4 * e32, FEAT_TOL)
+        try:
+            fe.load_state_dict(sd, strict=True)
+            got = fe(frames.cuda()).cpu()
+        finally:
+            fe.load_state_dict(base, strict=True)
+    err = (got.double() - want).abs().max().item()
+    print("\n[vit-stress] %s %s: err %.3g, fp32 pin %.3g, err / e32 %.2f" % (name, case, err, e32, err / e32))
+    assert torch.isfinite(got).all()
+    assert err <= tol, "%s %s: max |dfeature| = %.3g > %.3g (fp32 pin: %.3g)" % (name, case, err, tol, e32)
 
 
 def _recogniser_pair(name, adapt, classifier, batch_size=8):

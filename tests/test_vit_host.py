@@ -147,3 +147,58 @@ def test_cpu_pin_equals_hugging_face(name):
         b = out.pooler_output if vit_pin.VIT[name][3] else out.last_hidden_state[:, 0]
         assert (a - b).abs().max().item() <= 1e-5
         assert (a - pin(x)).abs().max().item() > 0.1  # FiLM reaches the features
+
+
+def test_operator_entry_points_refuse_bad_arguments_before_any_launch(lib):
+    """orbit_op_vit_*: every shape, tile height, width and alignment the kernels cannot take is an argument error (-1) with
+    its reason, returned before anything is launched (the pointers here are host addresses: a launch would fault)."""
+    buf = (ctypes.c_float * 64)()
+    base = ctypes.addressof(buf)
+    base += -base % 16
+    p, odd, odd4 = ctypes.c_void_p(base), ctypes.c_void_p(base + 4), ctypes.c_void_p(base + 2)
+
+    def refused(rc, word):
+        assert rc == -1, rc
+        assert word in _lib.last_error(), _lib.last_error()
+
+    lin = lib.orbit_op_vit_linear
+    refused(lin(p, p, p, None, p, 50, 384 + 64, 384, 0, 0, None), "multiple")    # N % 128
+    refused(lin(p, p, p, None, p, 50, 384, 384 + 16, 0, 0, None), "multiple")    # K % 32
+    refused(lin(p, p, p, None, p, 0, 384, 384, 0, 0, None), "shape")
+    refused(lin(p, p, p, None, p, 50, 0, 384, 0, 0, None), "shape")
+    for tile in (1, 32, 96, 256, -64):
+        refused(lin(p, p, p, None, p, 50, 384, 384, 0, tile, None), "tile_rows")
+    for epi in (-1, 3):                                                          # 3 is the patch epilogue: not a linear layer
+        refused(lin(p, p, p, None, p, 50, 384, 384, epi, 0, None), "epilogue")
+    refused(lin(p, p, p, None, p, 50, 384, 384, 2, 0, None), "residual")         # residual epilogue without a residual
+    refused(lin(p, p, p, p, p, 50, 384, 384, 1, 0, None), "residual")            # and a residual without it
+    refused(lin(odd, p, p, None, p, 50, 384, 384, 0, 0, None), "aligned")
+    refused(lin(p, odd, p, None, p, 50, 384, 384, 0, 0, None), "aligned")
+    refused(lin(p, p, p, None, odd4, 50, 384, 384, 0, 0, None), "aligned")
+    refused(lin(None, p, p, None, p, 50, 384, 384, 0, 0, None), "null")
+
+    pe = lib.orbit_op_vit_patch_embed
+    for D in (0, 128, 512, 1024):
+        refused(pe(p, p, None, p, p, p, 1, D, 0, None), "width")
+    refused(pe(p, p, None, p, p, p, 1, 384, 32, None), "tile_rows")
+    refused(pe(p, p, None, p, p, p, 0, 384, 0, None), "batch")
+    refused(pe(odd, p, None, p, p, p, 1, 384, 0, None), "aligned")
+    refused(pe(p, odd, None, p, p, p, 1, 384, 0, None), "aligned")
+    refused(pe(p, p, None, None, p, p, 1, 384, 0, None), "null")
+
+    ln = lib.orbit_op_vit_layernorm
+    for D in (64, 383, 512, 1536):
+        refused(ln(p, D, p, D, 4, D, p, p, 1e-6, None), "width")
+    refused(ln(p, 384, p, 384, 0, 384, p, p, 1e-6, None), "rows")
+    refused(ln(p, 383, p, 384, 4, 384, p, p, 1e-6, None), "stride")
+    refused(ln(p, 384, p, 100, 4, 384, p, p, 1e-6, None), "stride")
+    refused(ln(p, 384, odd4, 384, 4, 384, p, p, 1e-6, None), "aligned")
+    refused(ln(p, 384, p, 384, 4, 384, None, p, 1e-6, None), "null")
+
+    at = lib.orbit_op_vit_attention
+    refused(at(p, p, 1, 512, 8, None), "width")
+    refused(at(p, p, 1, 384, 12, None), "heads")
+    refused(at(p, p, 1, 768, 6, None), "heads")
+    refused(at(p, p, 0, 384, 6, None), "batch")
+    refused(at(odd4, p, 1, 384, 6, None), "aligned")
+    refused(at(p, None, 1, 384, 6, None), "null")
