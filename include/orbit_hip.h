@@ -77,7 +77,7 @@ int orbit_device_count(void);
  *   "graph"         HIP-graph replay of extractor forwards: 0 = never, 1 = always, 2 = adaptive (default: only while an
  *                   eager kernel launch costs > ~12 us of host time on this host); read per forward
  *   "train_graph"   1 (default) = the training entry points (orbit_extractor_train_forward / _backward) replay captured HIP
- *                   graphs from the third sight of a call on (same pointers, same sizes); 0 = eager launches
+ *                   graphs from the second sight of a call on (same pointers, same sizes; the first runs eagerly); 0 = eager launches
  *   "mbconv_rows"   1 (default) = EfficientNet blocks 1.0 .. 3.0 (112x112 .. 28x28 maps) run the row-streaming fused front
  *                   (csrc/mbconv_rows.hip: expand 1x1 + BN + SiLU + depthwise + BN + SiLU + SE partials, expanded rows in an
  *                   LDS ring); 0 = conv + depthwise kernel pair everywhere. Read when a plan is created

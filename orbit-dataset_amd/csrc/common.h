@@ -12,7 +12,7 @@ namespace orbit {
 // thread-local error message returned by orbit_last_error()
 char* err_buf();
 int set_err(int code, const char* fmt, ...);
-// runtime options (orbit_set_option / ORBIT_* environment; the table is in csrc/head.hip)
+// runtime options (orbit_set_option / ORBIT_* environment; the table is in csrc/runtime.hip)
 int get_option(const char* name);
 int option_epoch();  // changes whenever orbit_set_option changed a value (key of captured launch sequences)
 
@@ -139,7 +139,7 @@ struct PwStreamDesc {
 bool pw_stream_supported(int Cin, int Cout, int H, int W);  // a function of the layer only
 int launch_pw_stream(const PwStreamDesc& d, hipStream_t s);
 bool conv_prof_enabled();
-// per-launch HIP-event records of orbit_prof_* (no-ops returning -1 while profiling is off)
+// per-launch HIP-event records of orbit_prof_* (csrc/runtime.hip; no-ops returning -1 while profiling is off)
 int prof_start(const char* name, double flops, double bytes, hipStream_t s, double silu = 0.0);  // silu: SiLU evaluations of the launch
 void prof_stop(int idx, hipStream_t s);  // per-launch event profiling is on (graphs are bypassed while it is)
 

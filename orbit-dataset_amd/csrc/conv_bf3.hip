@@ -24,6 +24,7 @@
 
 #include "bf3.h"
 #include "common.h"
+#include "device_util.h"
 
 namespace orbit {
 
@@ -45,19 +46,6 @@ struct Bf3Params {
     int H, W, KH, KW, stride, pad_t, pad_l, Ho, Wo, KT;
     FastDiv fd_wo;
 };
-
-__device__ __forceinline__ float bf3_act(float v, int act) {
-    if (act == ORBIT_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == ORBIT_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-    return v;
-}
-
-__device__ __forceinline__ int bf3_xcd_remap(int bid, int nblk) {  // as conv_igemm.hip: contiguous tile runs per XCD
-    const int q = nblk >> 3, r = nblk & 7;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return start + slot;
-}
 
 template <int BM, int BN, int WGM, int WGN, int BK, bool GATE, int PF, bool ODD, bool PW>
 __global__ __launch_bounds__(256) void conv_bf3_kernel(const Bf3Params p) {
@@ -81,7 +69,7 @@ __global__ __launch_bounds__(256) void conv_bf3_kernel(const Bf3Params p) {
     const int l31 = lane & 31, lh = lane >> 5;
     const int wm = (wave / WGN) * WM, wn = (wave % WGN) * WN;
     const int ntiles = p.m_tiles * p.n_tiles;
-    const int tile = bf3_xcd_remap(blockIdx.x, ntiles);
+    const int tile = xcd_remap(blockIdx.x, ntiles);
     const int m0 = (tile / p.n_tiles) * BM, n0 = (tile % p.n_tiles) * BN;
 
     auto sw = [](int r) { return BK == 32 ? ((r >> 2) & 3) : ((r >> 3) & 1); };
@@ -332,7 +320,7 @@ __global__ __launch_bounds__(256) void conv_bf3_kernel(const Bf3Params p) {
             const int r = tid / TPO + it * RPO;
             if (m0 + r < p.M) {
                 f32x4 o = v[it] + res[it];
-                o[0] = bf3_act(o[0], p.act), o[1] = bf3_act(o[1], p.act), o[2] = bf3_act(o[2], p.act), o[3] = bf3_act(o[3], p.act);
+                o[0] = apply_act(o[0], p.act), o[1] = apply_act(o[1], p.act), o[2] = apply_act(o[2], p.act), o[3] = apply_act(o[3], p.act);
                 *reinterpret_cast<f32x4*>(p.y + (size_t)(m0 + r) * p.Cout + n) = o;
             }
         }

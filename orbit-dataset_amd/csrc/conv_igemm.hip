@@ -28,9 +28,8 @@
 // fp32 in, fp32 accumulate: bit-equivalent to an fmaf chain, which is what the 1e-3 logit parity
 // target needs (no TF32-class path exists on gfx950).
 #include <algorithm>
-#include <cstdlib>
-#include <vector>
 #include "common.h"
+#include "device_util.h"
 
 namespace orbit {
 
@@ -66,21 +65,6 @@ struct ConvParams {
     float* y_raw;              // dual write (training tape under running-statistics BatchNorm): the RAW conv output goes
                                // here, y receives act(raw * scale + shift + residual); null = single output
 };
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == ORBIT_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == ORBIT_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));  // v_exp_f32 + v_rcp_f32, ~1 ulp each
-    return v;
-}
-
-// XCD-aware remap: hardware places block i on XCD i % 8; give each XCD a contiguous run of logical
-// tiles so that the n-tiles sharing an A row-panel hit the same L2 (bijective for any grid size).
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-    const int q = nblk >> 3, r = nblk & 7;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return start + slot;
-}
 
 template <bool POOL2>
 __device__ __forceinline__ void decode_row(const ConvParams& p, int m, int& b, int& ho, int& wo) {
@@ -621,64 +605,6 @@ int conv_pack_weights(const float* w_oihw, float* w_packed, int Cin, int Cout, i
     return ORBIT_OK;
 }
 
-// ---- optional per-launch profiling (bench.py roofline): HIP events recorded on the launch stream ------
-struct ProfRec {
-    hipEvent_t start, stop;
-    int variant;
-    double flops, bytes, silu;
-};
-struct ProfVariant {
-    char name[48];
-    long launches;
-    double ms, flops, bytes;
-    double floor_ms;  // sum over the launches of max(bytes / HBM rate, FLOP / matrix rate): the launch-by-launch roofline floor
-    double silu;      // SiLU evaluations (two transcendentals each: the VALU work the matrix roof does not see)
-    double floor_simd_ms;  // ... of max(bytes / HBM rate, FLOP / matrix rate + SiLU / SiLU rate): on gfx950 a SIMD issues EITHER
-                           // an MFMA OR VALU instructions (profiles/r03_coexec_probe.txt), so matrix and SiLU time add up
-};
-// orbit_prof_set_roofs. SiLU: 11.06 ns of one SIMD per 64 evaluations at 8 waves per SIMD (v_exp_f32 + v_rcp_f32 + 3 packed
-// multiply-adds, profiles/r03_valu_probe.txt) x 1024 SIMDs
-static double g_roof_bytes_per_s = 6.3e12, g_roof_flop_per_s = 157.3e12, g_roof_silu_per_s = 64.0 * 1024.0 / 11.06e-9;
-static bool g_prof_on = false;
-bool conv_prof_enabled() { return g_prof_on; }
-static std::vector<ProfRec> g_prof_recs;
-static std::vector<hipEvent_t> g_prof_pool;
-static std::vector<ProfVariant> g_prof_variants;
-
-static hipEvent_t prof_event() {
-    if (!g_prof_pool.empty()) {
-        hipEvent_t e = g_prof_pool.back();
-        g_prof_pool.pop_back();
-        return e;
-    }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
-    return e;
-}
-static int prof_variant(const char* name) {
-    for (size_t i = 0; i < g_prof_variants.size(); ++i)
-        if (strcmp(g_prof_variants[i].name, name) == 0) return (int)i;
-    ProfVariant v;
-    memset(&v, 0, sizeof(v));
-    snprintf(v.name, sizeof(v.name), "%s", name);
-    g_prof_variants.push_back(v);
-    return (int)g_prof_variants.size() - 1;
-}
-
-// shared with the other MFMA kernels (conv_wgrad.hip): returns a record index or -1 when profiling is off
-int prof_start(const char* name, double flops, double bytes, hipStream_t s, double silu) {
-    if (!g_prof_on) return -1;
-    ProfRec r;
-    r.start = prof_event(), r.stop = prof_event(), r.variant = prof_variant(name);
-    r.flops = flops, r.bytes = bytes, r.silu = silu;
-    (void)hipEventRecord(r.start, s);
-    g_prof_recs.push_back(r);
-    return (int)g_prof_recs.size() - 1;
-}
-void prof_stop(int idx, hipStream_t s) {
-    if (idx >= 0 && idx < (int)g_prof_recs.size()) (void)hipEventRecord(g_prof_recs[idx].stop, s);
-}
-
 template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL>
 static int launch_cfg2(ConvParams& p, hipStream_t s) {
     p.m_tiles = cdiv(p.M, BM);
@@ -694,27 +620,22 @@ static int launch_cfg2(ConvParams& p, hipStream_t s) {
         attr_set = true;
     }
     const int grid = p.m_tiles * p.n_tiles * (p.ksplit > 1 ? p.ksplit : 1);
-    if (g_prof_on) {
+    int rec = -1;
+    if (conv_prof_enabled()) {  // per-launch event record (csrc/runtime.hip), one variant per instantiation
         char name[48];
         snprintf(name, sizeof(name), "conv_igemm<%d,%d,%d,%s%s%s%s%s>", BM, BN, BK, MODE ? "nchw" : "nhwc",
                  POOL2 ? ",pool2" : "", GATE ? ",gate" : "", PW ? ",pw" : "",
                  p.ksplit > 1 ? ",splitk" : WGK == 2 ? ",k2" : WGK == 4 ? ",k4" : (!p.y ? ",stats" : ""));
-        ProfRec r;
-        r.start = prof_event(), r.stop = prof_event(), r.variant = prof_variant(name);
         const double pix = POOL2 ? (double)p.B * p.HoP * p.WoP * 4 : (double)p.B * p.Ho * p.Wo;
-        r.flops = 2.0 * pix * p.Cout * p.KH * p.KW * p.Cin * p.prof_flop_scale;  // algorithmic (unpadded) FLOPs
+        const double flops = 2.0 * pix * p.Cout * p.KH * p.KW * p.Cin * p.prof_flop_scale;  // algorithmic (unpadded) FLOPs
         // algorithmic HBM bytes: input once, output once (pooled if fused), residual once, weights once
-        r.bytes = 4.0 * ((double)p.B * p.H * p.W * p.Cin +
-                         (POOL2 ? pix / 4 : pix) * p.Cout * ((p.residual ? 1.0 : 0.0) + (p.y || p.ksplit > 1 ? 1.0 : 0.0)) +
-                         (double)p.Cout * p.KH * p.KW * p.Cin);
-        r.silu = p.act == ORBIT_ACT_SILU && p.ksplit <= 1 ? pix * p.Cout : 0.0;
-        (void)hipEventRecord(r.start, s);
-        kern<<<grid, 256, lds, s>>>(p);
-        (void)hipEventRecord(r.stop, s);
-        g_prof_recs.push_back(r);
-    } else {
-        kern<<<grid, 256, lds, s>>>(p);
+        const double bytes = 4.0 * ((double)p.B * p.H * p.W * p.Cin +
+                                    (POOL2 ? pix / 4 : pix) * p.Cout * ((p.residual ? 1.0 : 0.0) + (p.y || p.ksplit > 1 ? 1.0 : 0.0)) +
+                                    (double)p.Cout * p.KH * p.KW * p.Cin);
+        rec = prof_start(name, flops, bytes, s, p.act == ORBIT_ACT_SILU && p.ksplit <= 1 ? pix * p.Cout : 0.0);
     }
+    kern<<<grid, 256, lds, s>>>(p);
+    prof_stop(rec, s);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
 }
@@ -871,68 +792,6 @@ int launch_conv(const ConvDesc& d, hipStream_t s) {
 using namespace orbit;
 
 extern "C" {
-
-// Profiling of the dominant kernel (all conv_igemm instantiations). enable(1) starts recording one HIP event
-// pair per launch on the launch stream; collect() waits for them, folds them into per-variant totals and
-// returns the grand totals; variant(i) reads one row. Not thread-safe: one profiled stream at a time.
-int orbit_prof_enable(int on) {
-    g_prof_on = on != 0;
-    if (on) {
-        for (ProfRec& r : g_prof_recs) g_prof_pool.push_back(r.start), g_prof_pool.push_back(r.stop);
-        g_prof_recs.clear();
-        g_prof_variants.clear();
-    }
-    return ORBIT_OK;
-}
-
-int orbit_prof_collect(double* total_ms, double* total_flops, long* launches) {
-    double ms = 0, fl = 0;
-    for (ProfRec& r : g_prof_recs) {
-        ORBIT_HIP_CHECK(hipEventSynchronize(r.stop));
-        float t = 0.f;
-        ORBIT_HIP_CHECK(hipEventElapsedTime(&t, r.start, r.stop));
-        ProfVariant& v = g_prof_variants[r.variant];
-        v.launches += 1, v.ms += t, v.flops += r.flops, v.bytes += r.bytes, v.silu += r.silu;
-        const double fb = r.bytes / g_roof_bytes_per_s, ff = r.flops / g_roof_flop_per_s;
-        v.floor_ms += 1e3 * (fb > ff ? fb : ff);
-        const double fs = ff + r.silu / g_roof_silu_per_s;
-        v.floor_simd_ms += 1e3 * (fb > fs ? fb : fs);
-        ms += t, fl += r.flops;
-        g_prof_pool.push_back(r.start), g_prof_pool.push_back(r.stop);
-    }
-    if (total_ms) *total_ms = ms;
-    if (total_flops) *total_flops = fl;
-    if (launches) *launches = (long)g_prof_recs.size();
-    g_prof_recs.clear();
-    return ORBIT_OK;
-}
-
-int orbit_prof_num_variants(void) { return (int)g_prof_variants.size(); }
-
-int orbit_prof_set_roofs(double hbm_bytes_per_s, double matrix_flop_per_s, double silu_evals_per_s) {
-    ORBIT_REQUIRE(hbm_bytes_per_s > 0 && matrix_flop_per_s > 0 && silu_evals_per_s > 0, "prof_set_roofs: rates must be positive");
-    g_roof_bytes_per_s = hbm_bytes_per_s, g_roof_flop_per_s = matrix_flop_per_s, g_roof_silu_per_s = silu_evals_per_s;
-    return ORBIT_OK;
-}
-
-int orbit_prof_variant_floor(int i, double* floor_ms, double* floor_simd_ms, double* silu_evals) {
-    ORBIT_REQUIRE(i >= 0 && i < (int)g_prof_variants.size(), "prof_variant_floor: index out of range");
-    if (floor_ms) *floor_ms = g_prof_variants[i].floor_ms;
-    if (floor_simd_ms) *floor_simd_ms = g_prof_variants[i].floor_simd_ms;
-    if (silu_evals) *silu_evals = g_prof_variants[i].silu;
-    return ORBIT_OK;
-}
-
-int orbit_prof_variant(int i, char* name48, long* launches, double* ms, double* flops, double* bytes) {
-    ORBIT_REQUIRE(i >= 0 && i < (int)g_prof_variants.size(), "prof_variant: index out of range");
-    const ProfVariant& v = g_prof_variants[i];
-    if (name48) memcpy(name48, v.name, sizeof(v.name));
-    if (launches) *launches = v.launches;
-    if (ms) *ms = v.ms;
-    if (flops) *flops = v.flops;
-    if (bytes) *bytes = v.bytes;
-    return ORBIT_OK;
-}
 
 /* Training form (single-operator entry for the parity tests): y = conv(x * gate) without epilogue, plus the per-channel sums
  * and sums of squares of y that the epilogue emits per row block, reduced to stats [2][Cout]; *stat_blocks receives the

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "common.h"
+#include "graph_cache.h"
 
 namespace orbit {
 
@@ -177,129 +178,42 @@ struct orbit_extractor {
     std::vector<BNDev> bn_dev;  // host copy of the fold descriptors
     bool finalized = false;
 
-    // HIP-graph cache: one instantiated graph per distinct (pointers, batch, stream) tuple of forward(). A forward is
-    // 25-90 dependent launches; replaying them as one graph launch takes the host out of the loop (on a slow or busy
-    // host the eager launch sequence, not the GPU, bounded small workloads).
+    // HIP-graph caches (graph_cache.h). Forward: one instantiated graph per distinct (pointers, batch) tuple of forward(). A
+    // forward is 25-90 dependent launches; replaying them as one graph launch takes the host out of the loop (on a slow or
+    // busy host the eager launch sequence, not the GPU, bounded small workloads). Cleared by orbit_extractor_finalize.
     struct GraphKey {
-        const void *frames, *gamma, *beta, *feats, *ws, *stream;
+        const void *frames, *gamma, *beta, *feats, *ws;
         int B;
-        int epoch;  // option_epoch() at capture: runtime options choose kernels
-        bool operator==(const GraphKey& o) const {
-            return frames == o.frames && gamma == o.gamma && beta == o.beta && feats == o.feats && ws == o.ws &&
-                   stream == o.stream && B == o.B && epoch == o.epoch;
-        }
     };
-    struct GraphEntry {
-        GraphKey key;
-        hipGraphExec_t exec = nullptr;  // nullptr: seen once (ran eagerly), capture on the next sight
-        unsigned long stamp = 0;
-    };
-    std::vector<GraphEntry> graphs;
-    unsigned long graph_clock = 0;
+    GraphCache<GraphKey> graphs{32};
     double eager_us_per_launch = 0.0;  // running average of the HOST cost of one eager kernel launch (option graph=2)
     int eager_samples = 0;
-    hipStream_t cap_stream = nullptr;  // private non-default stream used only to CAPTURE (the legacy default stream,
-                                       // torch's default, cannot be captured); graphs are launched on the caller's
-    void clear_graphs() {
-        for (GraphEntry& g : graphs)
-            if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        graphs.clear();
-    }
+    hipStream_t cap_stream = nullptr;  // private stream both caches CAPTURE on; graphs are launched on the caller's
 
-    // Graph cache of the TRAINING entry points (orbit_extractor_train_forward / orbit_extractor_backward): one LITE step
-    // of efficientnet_b0 is ~4 000 dependent launches, and the host, not the GPU, bounded it (39 of 41 ms enqueuing).
-    // Keyed by every pointer and scalar that a launch of the sequence bakes in; the plan's own buffers (parameter pool,
-    // packed filters, dgrad filters) are allocated once and never move, so these graphs survive parameter updates (the
-    // kernels read the CURRENT contents) and are only dropped with the plan. Callers whose allocator hands back the same
-    // addresses step after step (torch's caching allocator in a steady-state training loop) replay; others stay eager.
+    // Training entry points (orbit_extractor_train_forward / orbit_extractor_backward): one LITE step of efficientnet_b0 is
+    // ~4 000 dependent launches, and the host, not the GPU, bounded it. Keyed by every pointer and scalar that a launch of
+    // the sequence bakes in; the plan's own buffers (parameter pool, packed filters, dgrad filters) are allocated once and
+    // never move, so these graphs survive parameter updates (the kernels read the CURRENT contents) and are only dropped
+    // with the plan. Callers whose allocator hands back the same addresses step after step (torch's caching allocator in a
+    // steady-state training loop) replay; others stay eager.
     struct TrainGraphKey {
         const void* p[10];
-        long v[5];  // v[4] = option_epoch() (set by run_train_graphed)
-        bool operator==(const TrainGraphKey& o) const { return memcmp(this, &o, sizeof(*this)) == 0; }
+        long v[4];
     };
-    struct TrainGraphEntry {
-        TrainGraphKey key;
-        hipGraphExec_t exec = nullptr;  // nullptr: seen once (ran eagerly); captured on the next sight
-        bool dead = false;              // capture failed for this key: stay eager
-        unsigned long stamp = 0;
-    };
-    std::vector<TrainGraphEntry> train_graphs;
+    GraphCache<TrainGraphKey> train_graphs{64};
     long train_graph_replays = 0, train_graph_eager = 0;
-    void clear_train_graphs() {
-        for (TrainGraphEntry& g : train_graphs)
-            if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        train_graphs.clear();
-    }
+    // option train_graph: 0 = never, 1 (default) = replay from the second sight of a key on
     template <class F>
-    int run_train_graphed(TrainGraphKey key, hipStream_t s, F&& run) {
-        // 0 (default) = never, 1 = replay from the third sight of a key on. Opt-in: measured on MI355X the LITE step of
-        // efficientnet_b0 is bound by the GPU side of its ~1 260 short kernels (42 ms of kernel time per step), so replay
-        // only frees the host (36 -> 26 ms of enqueue time per step) without shortening the step (41.3 vs 41.4 ms)
-        const int opt = get_option("train_graph");
-        if (opt == 0 || conv_prof_enabled()) {
+    int run_train_graphed(const TrainGraphKey& key, hipStream_t s, F&& run) {
+        bool replayed = false;
+        const int rc = (get_option("train_graph") == 0 || conv_prof_enabled())
+                           ? run(s)
+                           : train_graphs.run(key, s, &cap_stream, run, &replayed);
+        if (replayed)
+            ++train_graph_replays;
+        else
             ++train_graph_eager;
-            return run(s);
-        }
-        key.v[4] = option_epoch();
-        TrainGraphEntry* hit = nullptr;
-        for (auto& g : train_graphs)
-            if (g.key == key) hit = &g;
-        if (hit == nullptr) {
-            if (train_graphs.size() >= 64) {  // evict the least recently used entry
-                size_t lru = 0;
-                for (size_t i = 1; i < train_graphs.size(); ++i)
-                    if (train_graphs[i].stamp < train_graphs[lru].stamp) lru = i;
-                if (train_graphs[lru].exec) (void)hipGraphExecDestroy(train_graphs[lru].exec);
-                train_graphs.erase(train_graphs.begin() + lru);
-            }
-            TrainGraphEntry e;
-            e.key = key, e.stamp = ++graph_clock;
-            train_graphs.push_back(e);
-            ++train_graph_eager;
-            return run(s);  // first sight: eager (also performs one-time kernel attribute set-up)
-        }
-        hit->stamp = ++graph_clock;
-        if (hit->dead) {
-            ++train_graph_eager;
-            return run(s);
-        }
-        if (hit->exec == nullptr) {
-            hipGraph_t graph = nullptr;
-            if (cap_stream == nullptr && hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking) != hipSuccess) {
-                (void)hipGetLastError();
-                hit->dead = true;
-                return run(s);
-            }
-            if (hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-                (void)hipGetLastError();
-                hit->dead = true;
-                return run(s);
-            }
-            const int rc = run(cap_stream);
-            const hipError_t ce = hipStreamEndCapture(cap_stream, &graph);
-            hipGraphExec_t exec = nullptr;
-            if (rc == ORBIT_OK && ce == hipSuccess && graph != nullptr &&
-                hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess && exec != nullptr) {
-                hit->exec = exec;
-            } else {
-                (void)hipGetLastError();
-                hit->dead = true;
-            }
-            if (graph) (void)hipGraphDestroy(graph);
-            if (rc != ORBIT_OK) return rc;
-            if (hit->dead) {
-                ++train_graph_eager;
-                return run(s);
-            }
-        }
-        if (hipGraphLaunch(hit->exec, s) != hipSuccess) {
-            (void)hipGetLastError();
-            hit->dead = true;
-            ++train_graph_eager;
-            return run(s);
-        }
-        ++train_graph_replays;
-        return ORBIT_OK;
+        return rc;
     }
 
     // device buffers are created on first use so that a plan can be built and inspected (state_dict keys,

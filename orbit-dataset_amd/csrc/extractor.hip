@@ -321,8 +321,8 @@ int orbit_extractor_create_ex(const char* name, int H, int W, int flags, orbit_e
 void orbit_extractor_destroy(orbit_extractor_t* fe) {
     if (!fe) return;
     extractor_train_release(fe);
-    fe->clear_graphs();
-    fe->clear_train_graphs();
+    fe->graphs.clear();
+    fe->train_graphs.clear();
     if (fe->cap_stream) (void)hipStreamDestroy(fe->cap_stream);
     (void)hipFree(fe->d_pool);
     (void)hipFree(fe->d_src);
@@ -459,7 +459,7 @@ int orbit_extractor_finalize(orbit_extractor_t* fe, orbit_stream_t stream) {
     bn_fold_all_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->d_pool, nullptr, nullptr, fe->d_fold,
                                             fe->d_fold + fe->fold_floats);
     ORBIT_LAUNCH_CHECK();
-    fe->clear_graphs();
+    fe->graphs.clear();
     fe->finalized = true;
     return ORBIT_OK;
 }
@@ -515,55 +515,14 @@ int orbit_extractor_forward(orbit_extractor_t* fe, const float* frames, int B, c
         return rc;
     }
 
-    // graph path: 1st sight of a pointer tuple runs eagerly (also performs one-time kernel attribute setup), the 2nd
-    // captures + instantiates, later ones replay
-    const orbit_extractor::GraphKey key{frames, film_gamma, film_beta, feats, workspace, nullptr, B, option_epoch()};
-    orbit_extractor::GraphEntry* hit = nullptr;
-    for (auto& g : fe->graphs)
-        if (g.key == key) hit = &g;
-    if (hit == nullptr) {
-        if (fe->graphs.size() >= 32) {  // evict the least recently used entry
-            size_t lru = 0;
-            for (size_t i = 1; i < fe->graphs.size(); ++i)
-                if (fe->graphs[i].stamp < fe->graphs[lru].stamp) lru = i;
-            if (fe->graphs[lru].exec) (void)hipGraphExecDestroy(fe->graphs[lru].exec);
-            fe->graphs.erase(fe->graphs.begin() + lru);
-        }
-        orbit_extractor::GraphEntry e;
-        e.key = key, e.stamp = ++fe->graph_clock;
-        fe->graphs.push_back(e);
-        return run_plan(fe, frames, B, film_gamma, film_beta, feats, workspace, s);
-    }
-    hit->stamp = ++fe->graph_clock;
-    if (hit->exec == nullptr) {
-        hipGraph_t graph = nullptr;
-        if (fe->cap_stream == nullptr)
-            ORBIT_HIP_CHECK(hipStreamCreateWithFlags(&fe->cap_stream, hipStreamNonBlocking));
-        if (hipStreamBeginCapture(fe->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            return run_plan(fe, frames, B, film_gamma, film_beta, feats, workspace, s);  // capture unavailable: stay eager
-        }
-        const int rc = run_plan(fe, frames, B, film_gamma, film_beta, feats, workspace, fe->cap_stream);
-        const hipError_t ce = hipStreamEndCapture(fe->cap_stream, &graph);
-        if (rc != ORBIT_OK) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc;
-        }
-        if (ce != hipSuccess || graph == nullptr) {
-            (void)hipGetLastError();
-            return run_plan(fe, frames, B, film_gamma, film_beta, feats, workspace, s);  // capture unavailable: stay eager
-        }
-        hipGraphExec_t exec = nullptr;
-        const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess || exec == nullptr) {
-            (void)hipGetLastError();
-            return run_plan(fe, frames, B, film_gamma, film_beta, feats, workspace, s);
-        }
-        hit->exec = exec;
-    }
-    ORBIT_HIP_CHECK(hipGraphLaunch(hit->exec, s));
-    return ORBIT_OK;
+    // graph path: 1st sight of a pointer tuple runs eagerly, the 2nd captures + instantiates, later ones replay
+    orbit_extractor::GraphKey key;
+    memset(&key, 0, sizeof(key));
+    key.frames = frames, key.gamma = film_gamma, key.beta = film_beta, key.feats = feats, key.ws = workspace, key.B = B;
+    bool replayed = false;
+    return fe->graphs.run(
+        key, s, &fe->cap_stream,
+        [&](hipStream_t rs) { return run_plan(fe, frames, B, film_gamma, film_beta, feats, workspace, rs); }, &replayed);
 }
 
 // the squeeze-excite op at index i is computed by its consumer, the gated projection right after it (csrc/pw_stream.hip):

@@ -8,86 +8,10 @@
 //
 // All three kernels are HBM-bound (AI ~ 2.4 FLOP/B): rows are streamed once with 16-byte loads, the
 // class matrix W (C*D*4 B ~ 25 KB) stays in L1/L2, reductions are wave64 DPP/shuffle reductions.
-#include <cstdlib>
 #include "common.h"
+#include "device_util.h"
 
 namespace orbit {
-
-static thread_local char g_err[512] = "";
-char* err_buf() { return g_err; }
-int set_err(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// ---- library options (tuning switches): name -> int; initial value from the environment ORBIT_<NAME upper-cased>
-struct Option {
-    const char* name;
-    const char* env;
-    int value;
-    bool init;
-};
-static Option g_options[] = {
-    // network runtime
-    {"graph", "ORBIT_GRAPH", 2, false},              // forward launch sequences as HIP graphs: 0 never, 1 always, 2 adaptive
-    {"train_graph", "ORBIT_TRAIN_GRAPH", 1, false},  // the same for the training entry points: 0 never, 1 from the third sight of a call
-    {"mbconv_rows", "ORBIT_MBCONV_ROWS", 1, false},  // row-streaming fused MBConv fronts at plan creation (0 = conv + depthwise pair)
-    {"stem_rows", "ORBIT_STEM_ROWS", 1, false},      // the same for stem + first depthwise
-    {"train_dw_xf", "ORBIT_TRAIN_DW_XF", 1, false},  // no-backward training forwards: BatchNorm + SiLU applied on the depthwise load
-    {"train_fused_fronts", "ORBIT_TRAIN_FUSED_FRONTS", 1, false},  // ... and MBConv fronts as statistics sweep + row-streaming kernel
-    // dense convolutions
-    {"conv_tile", "ORBIT_CONV_TILE", 0, false},      // 0 heuristic; 3 = 64x64, 4 = 128x32, 6 = 32x32 with K split over the waves
-    {"conv_bk", "ORBIT_CONV_BK", 0, false},          // 0 = widest K-tile that divides Cin; 8 / 16 / 32 caps it
-    {"conv_splitk", "ORBIT_CONV_SPLITK", 1, false},  // split-K over blocks for short, long-K layers
-    {"conv_rgemm", "ORBIT_CONV_RGEMM", 1, false},    // pointwise register GEMMs (pw_rgemm, pw_stream): 0 never, 1 where measured faster, 2 wherever supported
-    {"conv_bf3", "ORBIT_CONV_BF3", 0, false},        // OPT-IN bf16 x 3 split (bit 1 dense convs, bit 2 fused-front expands); never in `value`
-    // depthwise kernel families: 1 = where measured faster (default), 0 = never, 2 = wherever it fits
-    {"dw_window", "ORBIT_DW_WINDOW", 1, false},
-    {"dw_lds", "ORBIT_DW_LDS", 1, false},
-    {"dw_pipe", "ORBIT_DW_PIPE", 1, false},
-    // head
-    {"head_stream", "ORBIT_HEAD_STREAM", 1, false}};  // streaming distance kernel (T = 1, D = 512 / 1280); 0 = general LDS form
-static Option* find_option(const char* name) {
-    for (Option& o : g_options)
-        if (strcmp(o.name, name) == 0) {
-            if (!o.init) {
-                const char* e = getenv(o.env);
-                if (e) o.value = atoi(e);
-                o.init = true;
-            }
-            return &o;
-        }
-    return nullptr;
-}
-int get_option(const char* name) {
-    Option* o = find_option(name);
-    return o ? o->value : 0;
-}
-// bumped by every orbit_set_option that changes a value: captured launch sequences (csrc/extractor.hip, extractor.h) carry the
-// epoch they were recorded under in their key, so a graph never replays kernels chosen under other option values
-static int g_option_epoch = 0;
-int option_epoch() { return g_option_epoch; }
-
-// wave64 sum on the VALU with DPP lane permutes (quad swaps, half-row / row mirrors, then row broadcasts), result
-// broadcast from lane 63. __shfl_xor lowers to ds_bpermute_b32, an LDS-pipe round trip per step: with 20 reductions per
-// wave in the distance kernel those 120 dependent round trips, not HBM, set the kernel time.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false);
-    return v + __int_as_float(moved);
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    v = dpp_add<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-    v = dpp_add<0x141, 0xf>(v);  // row_half_mirror
-    v = dpp_add<0x140, 0xf>(v);  // row_mirror: every lane of a 16-lane row holds the row sum
-    v = dpp_add<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
-    v = dpp_add<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3: lane 63 holds the wave sum
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
 
 // ---- configure: segmented sum by class --------------------------------------------------------
 // grid (ceil(D/256), C, n_tasks), block 256: thread = one feature column d of one class.
@@ -208,7 +132,7 @@ __global__ __launch_bounds__(256) void proto_finalize_kernel(const float* __rest
         sq += mu * mu;
     }
     if (cosine) return;
-    sq = wave_sum(sq);
+    sq = wave_sum_dpp(sq);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
     __syncthreads();
     if (threadIdx.x == 0) b[(size_t)task * C + c] = -(red[0] + red[1] + red[2] + red[3]);
@@ -300,16 +224,16 @@ __global__ __launch_bounds__(256) void proto_predict_kernel(
         }
         if (c0 == 0 && cosine) {
 #pragma unroll
-            for (int r = 0; r < R; ++r) qn2[r] = wave_sum(qq[r]);
+            for (int r = 0; r < R; ++r) qn2[r] = wave_sum_dpp(qq[r]);
         }
 #pragma unroll
         for (int j = 0; j < CT; ++j) {
             if (c0 + j >= C) break;
-            const float wn = cosine ? sqrtf(wave_sum(wn2[j])) : 0.f;
+            const float wn = cosine ? sqrtf(wave_sum_dpp(wn2[j])) : 0.f;
             const float bj = cosine ? 0.f : bias[(size_t)task * C + c0 + j];
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                float v = wave_sum(dot[r][j]);
+                float v = wave_sum_dpp(dot[r][j]);
                 if (cosine)
                     v = logit_scale * (v / (fmaxf(sqrtf(qn2[r]), 1e-8f) * fmaxf(wn, 1e-8f)));
                 else
@@ -349,7 +273,7 @@ __global__ __launch_bounds__(256) void proto_predict_lds_kernel(
                 const float4 w = *reinterpret_cast<const float4*>(Ws + (size_t)c * D + d);
                 s += w.x * w.x + w.y * w.y + w.z * w.z + w.w * w.w;
             }
-            s = wave_sum(s);
+            s = wave_sum_dpp(s);
             if (lane == 0) wn[c] = sqrtf(s);
         }
         __syncthreads();
@@ -400,7 +324,7 @@ __global__ __launch_bounds__(256) void proto_predict_lds_kernel(
         }
         if (c0 == 0 && cosine) {
 #pragma unroll
-            for (int r = 0; r < R; ++r) qn2[r] = wave_sum(qq[r]);
+            for (int r = 0; r < R; ++r) qn2[r] = wave_sum_dpp(qq[r]);
         }
 #pragma unroll
         for (int j = 0; j < CT; ++j) {
@@ -409,7 +333,7 @@ __global__ __launch_bounds__(256) void proto_predict_lds_kernel(
             const float wnj = cosine ? wn[c0 + j] : 0.f;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                float v = wave_sum(dot[r][j]);
+                float v = wave_sum_dpp(dot[r][j]);
                 if (cosine)
                     v = logit_scale * (v / (fmaxf(sqrtf(qn2[r]), 1e-8f) * fmaxf(wnj, 1e-8f)));
                 else
@@ -435,15 +359,8 @@ __global__ __launch_bounds__(256) void proto_predict_lds_kernel(
 // Block -> (task, row block): the hardware deals consecutive block ids round-robin over the 8 XCDs, each with its own L2. A
 // task's weights (C x D floats, 25.6 KB) are staged by every one of its row blocks; dealt round-robin, a task's 13 blocks sat
 // on 8 different XCDs and its weights were fetched from memory 8 times (PMC: 79.3 MB of traffic per 64-task launch against
-// 67.4 MB of algorithmic bytes, 1.18x). The bijective remap below gives every XCD a contiguous run of logical blocks, so the
-// blocks of one task share one L2 and the weights cross the fabric once.
-__device__ __forceinline__ int head_xcd_remap(int bid, int nblk) {
-    const int q = nblk >> 3, r = nblk & 7;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return start + slot;
-}
-
+// 67.4 MB of algorithmic bytes, 1.18x). xcd_remap (csrc/device_util.h) gives every XCD a contiguous run of logical blocks, so
+// the blocks of one task share one L2 and the weights cross the fabric once.
 // (Forcing 8 waves per SIMD - launch_bounds(512, 8): 64 VGPRs, four blocks per CU = 1 024 slots for the 832 blocks of the
 // 64-task launch - spills 16 dwords per lane and measured 38.6 us against 19.5 us: the 79-register form stays.)
 // LEAN: Euclidean distance, no argmax output - the per-row cosine norms and the running best class leave the register file
@@ -453,7 +370,7 @@ __global__ __launch_bounds__(NW * 64) void proto_predict_stream_kernel(
     const float* __restrict__ Q, const float* __restrict__ W, const float* __restrict__ bias, int M, int D, int C,
     float logit_scale, int cosine, float* __restrict__ logits, int32_t* __restrict__ argmax, int blocks_per_task) {
     extern __shared__ __attribute__((aligned(16))) float Ws[];  // [C][D] weights, then [C] norms
-    const int logical = head_xcd_remap(blockIdx.x, gridDim.x);
+    const int logical = xcd_remap(blockIdx.x, gridDim.x);
     const int task = logical / blocks_per_task, bx = logical - task * blocks_per_task;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int m0 = (bx * NW + wave) * R;
@@ -478,7 +395,7 @@ __global__ __launch_bounds__(NW * 64) void proto_predict_stream_kernel(
                 const float4 w = *reinterpret_cast<const float4*>(Ws + (size_t)c * D + d);
                 s += w.x * w.x + w.y * w.y + w.z * w.z + w.w * w.w;
             }
-            s = wave_sum(s);
+            s = wave_sum_dpp(s);
             if (lane == 0) wn[c] = sqrtf(s);
         }
         __syncthreads();
@@ -495,7 +412,7 @@ __global__ __launch_bounds__(NW * 64) void proto_predict_stream_kernel(
 #pragma unroll
             for (int i = 0; i < NI; ++i)
                 qq += x[r][i].x * x[r][i].x + x[r][i].y * x[r][i].y + x[r][i].z * x[r][i].z + x[r][i].w * x[r][i].w;
-            qn2[r] = wave_sum(qq);
+            qn2[r] = wave_sum_dpp(qq);
         }
     }
     // one class at a time (rolled): only NI weight quads are live beside the R x NI query quads. Unrolled over the classes
@@ -518,7 +435,7 @@ __global__ __launch_bounds__(NW * 64) void proto_predict_stream_kernel(
         const float wnj = (!LEAN && cosine) ? wn[c] : 0.f;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            float v = wave_sum(acc[r]);
+            float v = wave_sum_dpp(acc[r]);
             if (!LEAN && cosine)
                 v = logit_scale * (v / (fmaxf(sqrtf(qn2[r]), 1e-8f) * fmaxf(wnj, 1e-8f)));
             else
@@ -581,50 +498,6 @@ __global__ __launch_bounds__(64) void set_mean_kernel(const float* __restrict__ 
 using namespace orbit;
 
 extern "C" {
-
-int orbit_version(void) { return 100; }
-
-/* Once per device the library is used on: keep freed stream-ordered allocations in the device's default memory pool. The
- * few entry points that take scratch with hipMallocAsync / hipFreeAsync (single-operator test entries, the FiLM generator's
- * backward) otherwise hit a pool whose release threshold is 0: every synchronisation trims it, the next call allocates for
- * real, and the real free that follows synchronises the device under the host's feet. */
-int orbit_runtime_init(void) {
-    int dev = 0;
-    ORBIT_HIP_CHECK(hipGetDevice(&dev));
-    static bool done[64] = {false};
-    if (dev < 0 || dev >= 64 || done[dev]) return ORBIT_OK;
-    hipMemPool_t pool = nullptr;
-    ORBIT_HIP_CHECK(hipDeviceGetDefaultMemPool(&pool, dev));
-    uint64_t keep = UINT64_MAX;
-    ORBIT_HIP_CHECK(hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep));
-    done[dev] = true;
-    return ORBIT_OK;
-}
-
-int orbit_set_option(const char* name, int value) {
-    ORBIT_REQUIRE(name, "set_option: null name");
-    Option* o = find_option(name);
-    ORBIT_REQUIRE(o != nullptr, "set_option: unknown option '%s'", name);
-    if (o->value != value) ++g_option_epoch;
-    o->value = value;
-    return ORBIT_OK;
-}
-int orbit_get_option(const char* name) {
-    if (!name) return -1;
-    return find_option(name) ? get_option(name) : -1;
-}
-const char* orbit_last_error(void) { return err_buf(); }
-
-int orbit_device_count(void) {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) {
-        set_err(ORBIT_ERR_HIP, "hipGetDeviceCount: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        return 0;
-    }
-    return n;
-}
 
 int orbit_proto_configure(const float* feats, const int64_t* labels, const int64_t* class_ids,
                           int n_tasks, int N, int T, int D, int C, float* sums, float* counts,

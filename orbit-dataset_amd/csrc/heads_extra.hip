@@ -7,14 +7,9 @@
 // covariance blending, batched in-place blocked Gauss-Jordan inversion of the SPD matrices (cov + I), and the
 // Mahalanobis quadratic form (difference -> MFMA GEMM through the 1x1 path of conv_igemm -> row dot).
 #include "common.h"
+#include "device_util.h"
 
 namespace orbit {
-
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ---- y[r][o] = act(x[r] . W[o] + b[o]) (+ residual[r][o]); R <= 16 rows, one wave per output unit -------------------
 constexpr int DENSE_MAX_ROWS = 16;
@@ -38,7 +33,7 @@ __global__ __launch_bounds__(256) void dense_rows_kernel(const float* __restrict
 #pragma unroll
     for (int r = 0; r < DENSE_MAX_ROWS; ++r) {
         if (r >= R) break;
-        float v = wave_sum64(acc[r]) + (b ? b[o] : 0.f);
+        float v = wave_sum_xor(acc[r]) + (b ? b[o] : 0.f);
         if (act == ORBIT_ACT_ELU) v = v > 0.f ? v : expm1f(v);
         else if (act == ORBIT_ACT_RELU) v = fmaxf(v, 0.f);
         if (residual) v += residual[(size_t)r * out + o];
@@ -295,7 +290,7 @@ __global__ __launch_bounds__(256) void maha_rowdot_kernel(const float* __restric
     if (m >= M) return;
     float s = 0.f;
     for (int d = lane; d < D; d += 64) s = fmaf(first[(size_t)m * D + d], diff[(size_t)m * D + d], s);
-    s = wave_sum64(s);
+    s = wave_sum_xor(s);
     if (lane == 0) logits[(size_t)m * C + c] = -scale * s;
 }
 

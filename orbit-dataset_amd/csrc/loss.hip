@@ -11,19 +11,9 @@
 //             `grad` is read on the device (it is the upstream autograd value - no synchronisation).
 // Accurate expf / logf (not the fast hardware approximations): the loss is compared with torch at 1e-6.
 #include "common.h"
+#include "device_util.h"
 
 namespace orbit {
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_add(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, const long* __restrict__ labels,
                                                       int N, int C, float* __restrict__ row_loss,
@@ -34,10 +24,10 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     const float* z = logits + (size_t)row * C;
     float m = -INFINITY;
     for (int c = lane; c < C; c += 64) m = fmaxf(m, z[c]);
-    m = wave_max(m);
+    m = wave_max_xor(m);
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += expf(z[c] - m);
-    s = wave_add(s);
+    s = wave_sum_xor(s);
     const long lab = labels[row];
     // a label outside [0, C) has no defined loss: NaN, so that it cannot pass unnoticed (torch asserts on the device)
     const float picked = (lab >= 0 && lab < C) ? z[lab] - m : NAN;

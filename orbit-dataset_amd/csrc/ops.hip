@@ -8,18 +8,13 @@
 //   BatchNorm (eval) + FiLM      model/few_shot_recognisers.py:114-117,176-183 — never a kernel of its own:
 //                                folded here to a per-channel (scale, shift) consumed by conv epilogues.
 #include "common.h"
+#include "device_util.h"
 #include "se_gate.h"
 #include <algorithm>
 
 namespace orbit {
 
 using v4f = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ float act_fn(float v, int act) {
-    if (act == ORBIT_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == ORBIT_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));  // v_exp_f32 + v_rcp_f32, ~1 ulp each
-    return v;
-}
 
 // Input transform of the depthwise kernels (XF): the kernel reads the RAW output y of the producing convolution and applies
 // that layer's BatchNorm + activation, act(y * in_scale[c] + in_shift[c]), as it loads - the activated tensor is never
@@ -158,10 +153,10 @@ __global__ __launch_bounds__(256) void dwconv_se_kernel(const float* __restrict_
                     const int wo = wq * 4 + j;
                     if (wo < Wo) {
                         float4 o;
-                        o.x = act_fn(acc[j].x * sc.x + sh.x, act);
-                        o.y = act_fn(acc[j].y * sc.y + sh.y, act);
-                        o.z = act_fn(acc[j].z * sc.z + sh.z, act);
-                        o.w = act_fn(acc[j].w * sc.w + sh.w, act);
+                        o.x = apply_act(acc[j].x * sc.x + sh.x, act);
+                        o.y = apply_act(acc[j].y * sc.y + sh.y, act);
+                        o.z = apply_act(acc[j].z * sc.z + sh.z, act);
+                        o.w = apply_act(acc[j].w * sc.w + sh.w, act);
                         *reinterpret_cast<float4*>(yb + ((size_t)ho * Wo + wo) * C) = o;
                         psum.x += o.x, psum.y += o.y, psum.z += o.z, psum.w += o.w;
                         if (STATS) psq.x += o.x * o.x, psq.y += o.y * o.y, psq.z += o.z * o.z, psq.w += o.w * o.w;
@@ -287,7 +282,7 @@ __global__ __launch_bounds__(256) void dwconv_pipe_kernel(const float* __restric
                     const int wo = wq * 4 + j;
                     if (wo < Wo) {
                         v4f o = acc[j] * sc + sh;
-                        o[0] = act_fn(o[0], act), o[1] = act_fn(o[1], act), o[2] = act_fn(o[2], act), o[3] = act_fn(o[3], act);
+                        o[0] = apply_act(o[0], act), o[1] = apply_act(o[1], act), o[2] = apply_act(o[2], act), o[3] = apply_act(o[3], act);
                         *reinterpret_cast<v4f*>(yb + ((size_t)ho * Wo + wo) * C) = o;
                         psum += o;
                         if (STATS) psq += o * o;
@@ -441,8 +436,8 @@ __global__ __launch_bounds__(256) void dwconv_win_kernel(const float* __restrict
                                     *reinterpret_cast<v4f*>(yb + ((size_t)ho * Wo + wo) * C) = dw_bnb(acc[j], yv[j], bv, bnb.act, psum, psq);
                                 } else {
                                     v4f o = acc[j] * sc + sh;
-                                    o[0] = act_fn(o[0], act), o[1] = act_fn(o[1], act), o[2] = act_fn(o[2], act),
-                                    o[3] = act_fn(o[3], act);
+                                    o[0] = apply_act(o[0], act), o[1] = apply_act(o[1], act), o[2] = apply_act(o[2], act),
+                                    o[3] = apply_act(o[3], act);
                                     *reinterpret_cast<v4f*>(yb + ((size_t)ho * Wo + wo) * C) = o;
                                     psum += o;
                                     if (STATS) psq += o * o;
@@ -624,7 +619,7 @@ __global__ __launch_bounds__(256) void dwconv_lds_kernel(const float* __restrict
                         *reinterpret_cast<v4f*>(yb + ((size_t)ho * Wo + wo) * C) = dw_bnb(acc[j], yv[j], bv, bnb.act, psum, psq);
                     } else {
                         v4f o = acc[j] * sc + sh;
-                        o[0] = act_fn(o[0], act), o[1] = act_fn(o[1], act), o[2] = act_fn(o[2], act), o[3] = act_fn(o[3], act);
+                        o[0] = apply_act(o[0], act), o[1] = apply_act(o[1], act), o[2] = apply_act(o[2], act), o[3] = apply_act(o[3], act);
                         *reinterpret_cast<v4f*>(yb + ((size_t)ho * Wo + wo) * C) = o;
                         psum += o;
                         if (STATS) psq += o * o;
@@ -736,8 +731,7 @@ __global__ __launch_bounds__(256) void se_gate_kernel(const float* __restrict__ 
     for (int r = wave; r < R; r += 4) {
         float s = 0.f;
         for (int c = lane; c < C; c += 64) s = fmaf(w1[(size_t)r * C + c], sp[c], s);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        s = wave_sum_xor(s);
         if (lane == 0) {
             s += b1[r];
             hid[r] = s / (1.0f + expf(-s));  // SiLU

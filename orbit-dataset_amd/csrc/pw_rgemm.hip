@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <cmath>
 #include "common.h"
+#include "device_util.h"
 
 namespace orbit {
 
@@ -53,19 +54,6 @@ struct PwrParams {
     FastDiv fd_ng; // block -> (pixel group, column group)
 };
 
-__device__ __forceinline__ int pwr_xcd_remap(int bid, int nblk) {  // as conv_igemm.hip: contiguous logical runs per XCD
-    const int q = nblk >> 3, r = nblk & 7;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return start + slot;
-}
-
-__device__ __forceinline__ float pwr_act(float v, int act) {
-    if (act == ORBIT_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == ORBIT_ACT_SILU) return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));  // the library's SiLU (conv_igemm.hip)
-    return v;
-}
-
 // ODD: every K slice of the launch holds an odd number of chunks (the launcher cuts the slices so that all have one parity)
 template <int T, bool GATE, bool ODD>
 __global__ __launch_bounds__(256) void pw_rgemm_kernel(const PwrParams p) {
@@ -73,7 +61,7 @@ __global__ __launch_bounds__(256) void pw_rgemm_kernel(const PwrParams p) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 15, q = lane >> 4;
-    const int bid = pwr_xcd_remap(blockIdx.x, gridDim.x);
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int mg = (int)fdiv((unsigned)bid, p.fd_ng), ng = bid - mg * p.n_groups;  // column groups of a pixel group are neighbours
     const int wm = p.wk == 1 ? wave : p.wk == 2 ? (wave >> 1) : 0;
     const int ks = p.wk == 1 ? 0 : p.wk == 2 ? (wave & 1) : wave;
@@ -190,7 +178,7 @@ __global__ __launch_bounds__(256) void pw_rgemm_kernel(const PwrParams p) {
             if (m >= p.M) continue;
             f32x4 v = acc[r][t] * sc + sh;
             if (p.residual) v += *reinterpret_cast<const f32x4*>(p.residual + (size_t)m * p.Cout + n);
-            v[0] = pwr_act(v[0], p.act), v[1] = pwr_act(v[1], p.act), v[2] = pwr_act(v[2], p.act), v[3] = pwr_act(v[3], p.act);
+            v[0] = apply_act(v[0], p.act), v[1] = apply_act(v[1], p.act), v[2] = apply_act(v[2], p.act), v[3] = apply_act(v[3], p.act);
             *reinterpret_cast<f32x4*>(p.y + (size_t)m * p.Cout + n) = v;
         }
     }

@@ -2,6 +2,7 @@
 // projection kernel in pw_stream.hip, which must produce the same bits).
 #pragma once
 #include "common.h"
+#include "device_util.h"
 
 namespace orbit {
 
@@ -12,20 +13,6 @@ using v4f = __attribute__((ext_vector_type(4))) float;
 // One block per frame; the block pulls both weight matrices (up to 2 x 221 KB at C = 1152) through one CU's L1, so the
 // kernel is a chain of L2 latencies: everything is float4 and every phase keeps 16-20 independent loads per lane in
 // flight (layer 1: one wave per hidden unit, four units at a time; layer 2: eight hidden units per step).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float se_dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float se_wave_sum(float v) {  // lane 63 holds the sum; returned wave-uniform
-    v = se_dpp_add<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v = se_dpp_add<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-    v = se_dpp_add<0x141, 0xf>(v);  // row_half_mirror
-    v = se_dpp_add<0x140, 0xf>(v);  // row_mirror
-    v = se_dpp_add<0x142, 0xa>(v);  // row_bcast:15
-    v = se_dpp_add<0x143, 0xc>(v);  // row_bcast:31
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
 // NT threads cooperate; U = hidden units a wave works on at a time. `partial`, `gate`, `pooled_out` point at THIS frame's
 // rows; sm2 needs ((C + R + 3) & ~3) + 4 * NT floats.
 template <int NT, int U>
@@ -98,7 +85,7 @@ __device__ __forceinline__ void se_gate_frame(const float* __restrict__ partial,
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int r = r0 + (NT / 64) * u;
-            const float sum = se_wave_sum(acc[u]);
+            const float sum = wave_sum_dpp(acc[u]);
             if (r < R && lane == 0) {
                 const float t = sum + b1[r];
                 hid[r] = t / (1.0f + expf(-t));

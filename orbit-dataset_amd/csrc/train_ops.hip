@@ -9,6 +9,7 @@
 // All tensors are NHWC fp32 viewed as [M][C] matrices (M = B*H*W); every kernel is HBM-bound: one pass, float4 per
 // thread, fixed reduction order (no atomics) so that gradients are run-to-run deterministic.
 #include "common.h"
+#include "device_util.h"
 
 namespace orbit {
 
@@ -153,20 +154,6 @@ __global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const float* __r
 // 112x112). Sums: fp32 per thread over <= ~64 pixels, fp32 over a block's 256 threads in a fixed order, double over the
 // blocks and through the quadratic form; the variance is E[y^2] - mean^2 in double, as in bn_stats_finalize_kernel.
 // partial[blk][CIN * CIN + CIN]: G row-major, then the column sums. Grid (nblk, CIN / RS): a block owns RS rows of G.
-// wave64 sum on the VALU with DPP lane permutes (as csrc/head.hip wave_sum: no LDS round trips), returned wave-uniform
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float gram_dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float gram_wave_sum(float v) {
-    v = gram_dpp_add<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-    v = gram_dpp_add<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-    v = gram_dpp_add<0x141, 0xf>(v);  // row_half_mirror
-    v = gram_dpp_add<0x140, 0xf>(v);  // row_mirror
-    v = gram_dpp_add<0x142, 0xa>(v);  // row_bcast:15
-    v = gram_dpp_add<0x143, 0xc>(v);  // row_bcast:31: lane 63 holds the wave sum
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
 
 template <int CIN, int RS>
 __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restrict__ x, int P, int pixels_per_block,
@@ -217,10 +204,10 @@ __global__ __launch_bounds__(256) void gram_partial_kernel(const float* __restri
     for (int i = 0; i < RS; ++i) {
 #pragma unroll
         for (int j = 0; j < CIN; ++j) {
-            const float t = gram_wave_sum(acc[i][j]);
+            const float t = wave_sum_dpp(acc[i][j]);
             if (lane == 0) red[wave][i * CIN + j] = t;
         }
-        const float t = gram_wave_sum(rs[i]);
+        const float t = wave_sum_dpp(rs[i]);
         if (lane == 0) red[wave][RS * CIN + i] = t;
     }
     __syncthreads();
@@ -857,12 +844,6 @@ int launch_add_inplace(float* dst, const float* src, size_t n, hipStream_t s) {
 }
 
 // ---- prototype head backward: d(features) of logits = s*(q.W^T + b) or s*cos(q, w_c); q = mean of T frame rows -----
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // one wave per query row; C <= 64 (dlogits of the row live in lane registers)
 __global__ __launch_bounds__(256) void proto_predict_bwd_kernel(const float* __restrict__ dlogits,
                                                                 const float* __restrict__ Q,
@@ -895,7 +876,7 @@ __global__ __launch_bounds__(256) void proto_predict_bwd_kernel(const float* __r
         x *= invT;
         qq += x * x;
     }
-    const float nq = sqrtf(wave_sum_f(qq)), nqc = fmaxf(nq, 1e-8f);
+    const float nq = sqrtf(wave_sum_xor(qq)), nqc = fmaxf(nq, 1e-8f);
     float a_c = 0.f, b_sum = 0.f;  // lane c keeps dl_c / (nq' nw'_c); b_sum = sum_c dl_c dot_c / (nq'^2 nw'_c nq)
     for (int c = 0; c < C; ++c) {
         float dot = 0.f, ww = 0.f;
@@ -906,8 +887,8 @@ __global__ __launch_bounds__(256) void proto_predict_bwd_kernel(const float* __r
             const float w = Wt[(size_t)c * D + d];
             dot += x * w, ww += w * w;
         }
-        dot = wave_sum_f(dot);
-        const float nwc = fmaxf(sqrtf(wave_sum_f(ww)), 1e-8f);
+        dot = wave_sum_xor(dot);
+        const float nwc = fmaxf(sqrtf(wave_sum_xor(ww)), 1e-8f);
         const float dl = __shfl(my_dl, c, 64);
         if (lane == c) a_c = dl / (nqc * nwc);
         if (nq > 1e-8f) b_sum += dl * dot / (nqc * nqc * nwc * nq);

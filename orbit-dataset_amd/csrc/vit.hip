@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "common.h"
+#include "device_util.h"
 
 using namespace orbit;
 
@@ -210,12 +211,6 @@ __global__ __launch_bounds__(256) void vit_cls_kernel(const float* __restrict__ 
 }
 
 // ---- LayerNorm -------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <int NPL>  // D / 64 values per lane
 __global__ __launch_bounds__(256) void vit_layernorm_kernel(const float* x, size_t x_stride, float* y, size_t y_stride,
                                                             int rows, const float* __restrict__ g,
@@ -231,11 +226,11 @@ __global__ __launch_bounds__(256) void vit_layernorm_kernel(const float* x, size
     // a division, not * (1.f / D): the compiler contracts that product into the subtraction below (fma(-sum, 1/D, v)), which
     // subtracts the UNROUNDED sum * fl(1/D) - for a constant row c that leaves v = -c * 2^-25 instead of 0, and at variance 0 the
     // 1/sqrt(eps) = 1000 behind it turns that into 1e-4 * gamma (tests/test_gpu_vit_ops.py, constant rows must give beta)
-    const float mean = wave_sum(s) / D;
+    const float mean = wave_sum_xor(s) / D;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NPL; ++i) v[i] -= mean, q += v[i] * v[i];
-    const float rstd = 1.f / sqrtf(wave_sum(q) * (1.f / D) + eps);
+    const float rstd = 1.f / sqrtf(wave_sum_xor(q) * (1.f / D) + eps);
     float* yr = y + (size_t)row * y_stride;  // (may alias x: every lane has read its values)
 #pragma unroll
     for (int i = 0; i < NPL; ++i) yr[lane + 64 * i] = v[i] * rstd * g[lane + 64 * i] + b[lane + 64 * i];
@@ -284,11 +279,9 @@ __global__ __launch_bounds__(256) void vit_attention_kernel(const float* __restr
     const int wave = tid >> 6, lane = tid & 63;
     for (int r = wave; r < VIT_N; r += 4) {
         const float val = lane < VIT_N ? sc[r * LDS_ + lane] : -INFINITY;
-        float m = val;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        const float m = wave_max_xor(val);
         const float e = lane < VIT_N ? expf(val - m) : 0.f;
-        const float sum = wave_sum(e);
+        const float sum = wave_sum_xor(e);
         if (lane < VIT_N) sc[r * LDS_ + lane] = e / sum;
     }
     __syncthreads();
