@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 #include "../../include/orbit_hip.h"
 
 namespace orbit {
@@ -164,6 +165,20 @@ struct DwBnBwd {
     float* wgrad_partial = nullptr;
     int* wgrad_rows = nullptr;
 };
+// The depthwise kernels are instantiated for K in {3, 5} and stride in {1, 2}: f(integral_constant K, integral_constant stride)
+// turns the two runtime ints into template arguments, once for every launcher of the family (callers validate K and stride)
+template <class F>
+static inline void dw_dispatch_ks(int K, int stride, F&& f) {
+    using std::integral_constant;
+    if (K == 3 && stride == 1) f(integral_constant<int, 3>{}, integral_constant<int, 1>{});
+    else if (K == 3) f(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+    else if (stride == 1) f(integral_constant<int, 5>{}, integral_constant<int, 1>{});
+    else f(integral_constant<int, 5>{}, integral_constant<int, 2>{});
+}
+// forward kernel forms of launch_dwconv_se (csrc/ops.hip): plain streaming, software-pipelined streaming, register window, LDS
+// input patch. dw_form_rule is the one place that chooses between them (options dw_lds / dw_window / dw_pipe + measured rules)
+enum DwForm { DW_STREAM, DW_PIPE, DW_WINDOW, DW_LDS };
+DwForm dw_form_rule(int K, int stride, int Ho, bool train_form, bool lds_fits = true);
 // depthwise + fused SE pooling partials [B][chunks][C] (pool_partial may be nullptr); chunks = dwconv_se_chunks(Ho)
 int dwconv_se_chunks(int Ho);
 int launch_dwconv_se(const float* x, const float* w_khwc, float* y, const float* scale, const float* shift,

@@ -374,13 +374,10 @@ static void wgrad_geometry(int M, int Cout, int NC, int& co_tiles, int& n_tiles,
     co_tiles = cdiv(Cout, 64), n_tiles = cdiv(NC, 64);
     const int tiles = co_tiles * n_tiles;
     const int total_steps = cdiv(M, WG_BKM);
-    static const int target = [] {  // (ORBIT_WGRAD_BLOCKS: tuning experiments only)
-        const char* e = getenv("ORBIT_WGRAD_BLOCKS");
-        // 1536 (round 6; 2048 before): a quarter less partial-tile traffic (the split reductions move ~1 GB per LITE step),
-        // same-box A/B 24.54 / 24.53 -> 24.41 / 24.23 ms per step (profiles/r06_lite_ab_fused_fronts.txt)
-        return e && atoi(e) > 0 ? atoi(e) : 1536;
-    }();
-    splits = cdiv(target, tiles);
+    // 1536 (2048 before; 1024 measured no better): a quarter less partial-tile traffic (the split reductions move ~1 GB per LITE
+    // step), same-box A/B 24.54 / 24.53 -> 24.41 / 24.23 ms per step (profiles/r06_lite_ab_fused_fronts.txt)
+    constexpr int WGRAD_TARGET_BLOCKS = 1536;
+    splits = cdiv(WGRAD_TARGET_BLOCKS, tiles);
     const int max_splits = total_steps >= 8 ? total_steps / 8 : 1;
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;

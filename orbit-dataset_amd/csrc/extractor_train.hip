@@ -962,9 +962,7 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
                 // that BatchNorm's apply pass from d(x * gate) (slot kt stays the depthwise op's gradient slot)
                 SeBnFuse fuse;
                 const SeBnFuse* fuse_ptr = nullptr;
-                static const char* write_g_env = getenv("ORBIT_SE_BWD_WRITE_G");  // tuning experiments only
-                const bool sums_only = fe->ops[src].kind == OP_DWCONV && !(write_g_env && atoi(write_g_env) != 0) &&
-                                       (unsigned long long)B * o.H * o.W * (o.Cin / 4) < (1ull << 32);
+                const bool sums_only = fe->ops[src].kind == OP_DWCONV && (unsigned long long)B * o.H * o.W * (o.Cin / 4) < (1ull << 32);
                 int k = kt;
                 if (!sums_only) {
                     k = alloc();

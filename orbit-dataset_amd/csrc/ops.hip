@@ -753,25 +753,78 @@ static int grid_for(size_t total) {
 // channel quads per block: the largest divisor of C/4 that is <= 64 (keeps every thread on a fixed channel quad)
 static int dw_cb4(int C) {
     const int c4 = C / 4;
-    static const char* env = getenv("ORBIT_DW_CB4");  // tuning experiments only
-    const int cap = env ? atoi(env) : 64;
-    for (int d = c4 < cap ? c4 : cap; d >= 1; --d)
+    for (int d = c4 < 64 ? c4 : 64; d >= 1; --d)
         if (c4 % d == 0) return d;
     return 1;
 }
-int dwconv_se_rows_per_chunk(int Ho) {
-    static const char* env = getenv("ORBIT_DW_RPC");  // tuning experiments only: rows per chunk for maps of <= 28 rows
-    if (env && Ho <= 28 && atoi(env) > 0) return atoi(env) < Ho ? atoi(env) : Ho;
-    return Ho >= 56 ? 8 : (Ho >= 14 ? 7 : Ho);
-}
+static int dwconv_se_rows_per_chunk(int Ho) { return Ho >= 56 ? 8 : (Ho >= 14 ? 7 : Ho); }
 int dwconv_se_chunks(int Ho) { return cdiv(Ho, dwconv_se_rows_per_chunk(Ho)); }
 
+// The kernel form the options and the measured rules prefer for a (K, stride) layer with Ho output rows, before any fit check
+// (dw_lds / dw_window / dw_pipe: 1 = auto, 0 = never, 2 = always; read here and nowhere else). train_form: the statistics
+// epilogue, with the input transform applied per load. lds_fits = false: what dw_plan falls back to when the patch does not fit.
+DwForm dw_form_rule(int K, int stride, int Ho, bool train_form, bool lds_fits) {
+    // LDS patch, measured (tools/dw_bench.py, 200 frames): 5x5 stride 1 -39..-41 % time (28x240, 14x480, 14x672), -15 % at
+    // 7x1152; 3x3 stride 1 on <= 14 rows -10..-20 %; stride 2 and the large 3x3 maps are faster through the streaming kernels.
+    // Train form (tools/dw_train_bench.py): the small stride-2 map (14 -> 7 rows, 5x5) 158 -> 84 us through the LDS patch (the
+    // transform once per element instead of once per tap)
+    const int lds_opt = get_option("dw_lds");
+    if (lds_fits && (lds_opt == 2 || (lds_opt == 1 && ((stride == 1 && (K == 5 || Ho <= 14)) || (train_form && stride == 2 && Ho < 14)))))
+        return DW_LDS;
+    // register window, measured in-process against the plain streaming kernel (tools/dw_bench.py): +30..45 % on 3x3 / stride 1
+    // with >= 14 rows (112x32, 56x144, 14x480), slower on 5x5 (K x NCOL window -> 256 VGPRs, 1 wave/SIMD) and on stride 2
+    const int win_opt = get_option("dw_window");
+    if (win_opt == 2 || (win_opt == 1 && K == 3 && stride == 1 && Ho >= 14)) return DW_WINDOW;
+    // software-pipelined streaming: measured +5..9 % on the large stride-2 layers (112x96 3x3, 56x144 5x5), slower on the small
+    // maps (two tap rows of registers -> 2 waves per SIMD); train form: also the 28 -> 14 row layer, 102 -> 60 us
+    const int pipe_opt = get_option("dw_pipe");
+    if (pipe_opt == 2 || (pipe_opt == 1 && stride == 2 && Ho >= (train_form ? 14 : 28))) return DW_PIPE;
+    return DW_STREAM;
+}
+
 // whether launch_dwconv_se runs a (K, stride) layer with Ho output rows through the register-window kernel (the form that can
-// carry the filter gradient, DwBnBwd::wgrad_partial); conservative: false where the LDS form is tried first
-bool dwconv_se_window_form(int K, int stride, int Ho) {
-    const int lds_opt = get_option("dw_lds"), win_opt = get_option("dw_window");
-    if (lds_opt == 2 || (lds_opt == 1 && stride == 1 && (K == 5 || Ho <= 14))) return false;
-    return win_opt == 2 || (win_opt == 1 && K == 3 && stride == 1 && Ho >= 14);
+// carry the filter gradient, DwBnBwd::wgrad_partial). A function of the rule alone, so conservative: false wherever the LDS rule
+// claims the shape, even if its patch would not fit and the launch falls back to the window
+bool dwconv_se_window_form(int K, int stride, int Ho) { return dw_form_rule(K, stride, Ho, false) == DW_WINDOW; }
+
+// the form launch_dwconv_se launches and its geometry
+struct DwPlan {
+    DwForm form;
+    int cb4, rpc;  // channel quads per block (streaming forms), output rows per chunk
+    dim3 grid;     // (channel slices, row chunks, frames) of the chosen form
+    size_t lds;    // its dynamic LDS bytes
+    int cs4, G, IWA;  // LDS form: channel quads per block, 4-column output groups, patch width
+    bool deep;        // LDS form: 12 staging loads in flight instead of 8
+};
+static DwPlan dw_plan(int B, int C, int K, int stride, int Ho, int Wo, bool train_form) {
+    DwPlan p{};
+    p.cb4 = dw_cb4(C), p.rpc = dwconv_se_rows_per_chunk(Ho);
+    p.form = dw_form_rule(K, stride, Ho, train_form);
+    if (p.form == DW_LDS) {
+        const int c4 = C / 4;
+        p.G = cdiv(Wo, 4);
+        // channel quads per block (a pixel's slice stays >= 64 contiguous bytes): the widest slice (longest contiguous run per
+        // pixel) whose (256 / cs4) / G row lanes cover the chunk's rows in at most two passes; else the narrowest that fits
+        for (int cand : {16, 8, 4}) {
+            if (c4 % cand != 0 || p.G > 256 / cand) continue;
+            p.cs4 = cand;
+            if (2 * ((256 / cand) / p.G) >= p.rpc) break;
+        }
+        p.IWA = (4 * p.G - 1) * stride + K;
+        const int IHmax = (p.rpc - 1) * stride + K;
+        p.lds = ((size_t)IHmax * p.IWA * (p.cs4 * 4 + 4)) * sizeof(float) + (size_t)(K * K * p.cs4 + 256) * sizeof(float4);
+        if (p.cs4 != 0 && p.lds <= 64 * 1024) {
+            p.grid = dim3(c4 / p.cs4, cdiv(Ho, p.rpc), B);
+            // staging batch per thread: 8 loads in flight, 12 where a thread owns more than 8 patch pixels (7x7 maps with
+            // 16-quad slices: one HBM round trip instead of two, +6 %; elsewhere 12 is neutral or slightly worse)
+            p.deep = IHmax * p.IWA > 8 * (256 / p.cs4);
+            return p;
+        }
+        p.form = dw_form_rule(K, stride, Ho, train_form, false);
+    }
+    p.grid = dim3(C / 4 / p.cb4, cdiv(Ho, p.rpc), B);
+    p.lds = (size_t)(K * K * p.cb4 + (256 / p.cb4) * p.cb4) * sizeof(float4);
+    return p;
 }
 
 static int launch_dwconv_se_impl(const float* x, const float* w_khwc, float* y, const float* scale, const float* shift,
@@ -817,154 +870,81 @@ static int launch_dwconv_se_impl(const float* x, const float* w_khwc, float* y, 
     ORBIT_REQUIRE(C % 4 == 0, "dwconv_se: C %% 4 != 0 (C=%d)", C);
     ORBIT_REQUIRE((K == 3 || K == 5) && (stride == 1 || stride == 2), "dwconv_se: K=%d stride=%d not instantiated", K,
                   stride);
-    const int cb4 = dw_cb4(C), rpc = dwconv_se_rows_per_chunk(Ho);
-    // LDS-patch kernel (dw_lds: 1 = auto: the 5x5 layers, 0 = never, 2 = whenever it fits): channel quads per block sized
-    // so that a pixel's slice is >= 64 contiguous bytes and enough (column group, row) positions remain per block
-    const int lds_opt = get_option("dw_lds");
-    // measured (tools/dw_bench.py, 200 frames): 5x5 stride 1 -39..-41 % time (28x240, 14x480, 14x672), -15 % at 7x1152;
-    // 3x3 stride 1 on <= 14 rows -10..-20 %; stride 2 and the large 3x3 maps are faster through the streaming kernels
-    // train form (statistics epilogue, the input transform applied per load) at 200 frames, tools/dw_train_bench.py: the small
-    // stride-2 map (14 -> 7 rows, 5x5) 158 -> 84 us through the LDS patch (the transform once per element instead of once per tap)
-    const bool train_form = stats != 0;
-    if (lds_opt == 2 || (lds_opt == 1 && ((stride == 1 && (K == 5 || Ho <= 14)) || (train_form && stride == 2 && Ho < 14)))) {
-        const int c4 = C / 4;
-        const int G = cdiv(Wo, 4);
-        // channel quads per block: the widest slice (longest contiguous run per pixel) whose (256 / cs4) / G row lanes
-        // cover the chunk's rows in at most two passes; else the narrowest that fits
-        int cs4 = 0;
-        for (int cand : {16, 8, 4}) {
-            if (c4 % cand != 0 || G > 256 / cand) continue;
-            cs4 = cand;
-            if (2 * ((256 / cand) / G) >= rpc) break;
+    const DwPlan p = dw_plan(B, C, K, stride, Ho, Wo, stats != 0);
+    const dim3 grid = p.grid;
+    const size_t lds = p.lds;
+    const int cb4 = p.cb4, rpc = p.rpc, cs4 = p.cs4, G = p.G, IWA = p.IWA;
+    const DwInXf no_xf{nullptr, nullptr, 0};
+    dw_dispatch_ks(K, stride, [&](auto kc, auto sc) {
+        constexpr int KK = decltype(kc)::value, SS = decltype(sc)::value;
+        switch (p.form) {
+        case DW_LDS:
+            if (bnb) {
+                if constexpr (SS == 1)
+                    dwconv_lds_kernel<KK, SS, 8, true, false, true><<<grid, 256, lds, s>>>(
+                        x, w_khwc, y, nullptr, nullptr, bnb->partial, H, W, C, pad_t, pad_l, Ho, Wo, act, cs4, rpc, G, IWA, no_xf, *bnb);
+                *bnb->nblk = (int)(grid.y * grid.z);
+            } else if (use_xf)
+                dwconv_lds_kernel<KK, SS, 8, true, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t,
+                                                                               pad_l, Ho, Wo, act, cs4, rpc, G, IWA, xf);
+            else if (stats)
+                dwconv_lds_kernel<KK, SS, 8, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, pad_l,
+                                                                         Ho, Wo, act, cs4, rpc, G, IWA);
+            else if (p.deep)
+                dwconv_lds_kernel<KK, SS, 12><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, pad_l, Ho,
+                                                                    Wo, act, cs4, rpc, G, IWA);
+            else
+                dwconv_lds_kernel<KK, SS, 8><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, pad_l, Ho,
+                                                                   Wo, act, cs4, rpc, G, IWA);
+            break;
+        case DW_WINDOW: {
+            constexpr int NO = KK == 3 ? 4 : (SS == 1 ? 2 : 1);  // outputs per thread: what the K x NCOL window leaves registers for
+            if (bnb && bnb->wgrad_partial) {
+                const size_t lds_wg = (size_t)(K * K * cb4 + 8 * 256) * sizeof(float4);
+                if constexpr (SS == 1)
+                    dwconv_win_kernel<KK, SS, NO, true, false, true, true><<<grid, 256, lds_wg, s>>>(
+                        x, w_khwc, y, nullptr, nullptr, bnb->partial, H, W, C, pad_t, pad_l, Ho, Wo, act, cb4, rpc, no_xf, *bnb);
+                *bnb->nblk = *bnb->wgrad_rows = (int)(grid.y * grid.z);
+            } else if (bnb) {
+                if constexpr (SS == 1)
+                    dwconv_win_kernel<KK, SS, NO, true, false, true><<<grid, 256, lds, s>>>(
+                        x, w_khwc, y, nullptr, nullptr, bnb->partial, H, W, C, pad_t, pad_l, Ho, Wo, act, cb4, rpc, no_xf, *bnb);
+                *bnb->nblk = (int)(grid.y * grid.z);
+            } else if (use_xf)
+                dwconv_win_kernel<KK, SS, NO, true, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t,
+                                                                                 pad_l, Ho, Wo, act, cb4, rpc, xf);
+            else if (stats)
+                dwconv_win_kernel<KK, SS, NO, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, pad_l,
+                                                                           Ho, Wo, act, cb4, rpc);
+            else
+                dwconv_win_kernel<KK, SS, NO><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, pad_l, Ho,
+                                                                     Wo, act, cb4, rpc);
+            break;
         }
-        static const char* cs_env = getenv("ORBIT_DW_CS4");  // tuning experiments only
-        if (cs_env && atoi(cs_env) > 0 && c4 % atoi(cs_env) == 0 && G <= 256 / atoi(cs_env)) cs4 = atoi(cs_env);
-        if (cs4 != 0) {
-            const int IWA = (4 * G - 1) * stride + K;
-            const int IHmax = (rpc - 1) * stride + K;
-            const size_t ldsb = ((size_t)IHmax * IWA * (cs4 * 4 + 4)) * sizeof(float) +
-                                (size_t)(K * K * cs4 + 256) * sizeof(float4);
-            if (ldsb <= 64 * 1024) {
-                dim3 gl(c4 / cs4, cdiv(Ho, rpc), B);
-                // staging batch per thread: 8 loads in flight, 12 where a thread owns more than 8 patch pixels (7x7 maps with
-                // 16-quad slices: one HBM round trip instead of two, +6 %; elsewhere 12 is neutral or slightly worse)
-                const bool deep = IHmax * IWA > 8 * (256 / cs4);
-#define ORBIT_DWL(KK, SS)                                                                                              \
-    do {                                                                                                               \
-        if (bnb) {                                                                                                     \
-            if constexpr (SS == 1)                                                                                     \
-                dwconv_lds_kernel<KK, SS, 8, true, false, true><<<gl, 256, ldsb, s>>>(x, w_khwc, y, nullptr, nullptr, bnb->partial, H, \
-                                                                                      W, C, pad_t, pad_l, Ho, Wo, act, cs4, rpc, G,  \
-                                                                                      IWA, DwInXf{nullptr, nullptr, 0}, *bnb); \
-            *bnb->nblk = (int)(gl.y * gl.z);                                                                           \
-        } else if (use_xf)                                                                                             \
-            dwconv_lds_kernel<KK, SS, 8, true, true><<<gl, 256, ldsb, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, \
-                                                                           C, pad_t, pad_l, Ho, Wo, act, cs4, rpc, G,  \
-                                                                           IWA, xf);                                   \
-        else if (stats)                                                                                                \
-            dwconv_lds_kernel<KK, SS, 8, true><<<gl, 256, ldsb, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C,  \
-                                                                     pad_t, pad_l, Ho, Wo, act, cs4, rpc, G, IWA);     \
-        else if (deep)                                                                                                 \
-            dwconv_lds_kernel<KK, SS, 12><<<gl, 256, ldsb, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, \
-                                                                  pad_l, Ho, Wo, act, cs4, rpc, G, IWA); \
-        else                                                                                                           \
-            dwconv_lds_kernel<KK, SS, 8><<<gl, 256, ldsb, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t,  \
-                                                                 pad_l, Ho, Wo, act, cs4, rpc, G, IWA); \
-    } while (0)
-                if (K == 3 && stride == 1) ORBIT_DWL(3, 1);
-                else if (K == 3) ORBIT_DWL(3, 2);
-                else if (stride == 1) ORBIT_DWL(5, 1);
-                else ORBIT_DWL(5, 2);
-#undef ORBIT_DWL
-                ORBIT_LAUNCH_CHECK();
-                return ORBIT_OK;
-            }
+        case DW_PIPE:
+            if (use_xf)
+                dwconv_pipe_kernel<KK, SS, true, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t,
+                                                                              pad_l, Ho, Wo, act, cb4, rpc, xf);
+            else if (stats)
+                dwconv_pipe_kernel<KK, SS, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, pad_l, Ho,
+                                                                        Wo, act, cb4, rpc);
+            else
+                dwconv_pipe_kernel<KK, SS><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, pad_l, Ho, Wo,
+                                                                  act, cb4, rpc);
+            break;
+        case DW_STREAM:
+            if (use_xf)
+                dwconv_se_kernel<KK, SS, true, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, pad_l,
+                                                                            Ho, Wo, act, cb4, rpc, xf);
+            else if (stats)
+                dwconv_se_kernel<KK, SS, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, pad_l, Ho,
+                                                                      Wo, act, cb4, rpc);
+            else
+                dwconv_se_kernel<KK, SS><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, pad_l, Ho, Wo, act,
+                                                                cb4, rpc);
+            break;
         }
-    }
-    dim3 grid(C / 4 / cb4, cdiv(Ho, rpc), B);
-    const size_t lds = (size_t)(K * K * cb4 + (256 / cb4) * cb4) * sizeof(float4);
-    // register-window kernel: measured in-process on MI355X against the plain streaming kernel (tools/dw_bench.py):
-    // +30..45 % on 3x3 / stride 1 with >= 14 rows (112x32, 56x144, 14x480), slower on 5x5 (K x NCOL window -> 256
-    // VGPRs, 1 wave/SIMD) and on stride 2. dw_window: 1 = auto (default), 0 = never, 2 = always.
-    const int win_opt = get_option("dw_window");
-    if (win_opt == 2 || (win_opt == 1 && K == 3 && stride == 1 && Ho >= 14)) {
-        const size_t lds_wg = (size_t)(K * K * cb4 + 8 * 256) * sizeof(float4);
-#define ORBIT_DWW(KK, SS, NO)                                                                                          \
-    do {                                                                                                               \
-        if (bnb && bnb->wgrad_partial) {                                                                               \
-            if constexpr (SS == 1)                                                                                     \
-                dwconv_win_kernel<KK, SS, NO, true, false, true, true><<<grid, 256, lds_wg, s>>>(                      \
-                    x, w_khwc, y, nullptr, nullptr, bnb->partial, H, W, C, pad_t, pad_l, Ho, Wo, act, cb4, rpc,           \
-                    DwInXf{nullptr, nullptr, 0}, *bnb);                                                                \
-            *bnb->nblk = *bnb->wgrad_rows = (int)(grid.y * grid.z);                                                    \
-        } else if (bnb) {                                                                                              \
-            if constexpr (SS == 1)                                                                                     \
-                dwconv_win_kernel<KK, SS, NO, true, false, true><<<grid, 256, lds, s>>>(x, w_khwc, y, nullptr, nullptr,   \
-                                                                                        bnb->partial, H, W, C, pad_t, pad_l, Ho, Wo, \
-                                                                                        act, cb4, rpc, DwInXf{nullptr, nullptr, 0}, \
-                                                                                        *bnb);                         \
-            *bnb->nblk = (int)(grid.y * grid.z);                                                                       \
-        } else if (use_xf)                                                                                             \
-            dwconv_win_kernel<KK, SS, NO, true, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, \
-                                                                             W, C, pad_t, pad_l, Ho, Wo, act, cb4, rpc, \
-                                                                             xf);                                      \
-        else if (stats)                                                                                                \
-            dwconv_win_kernel<KK, SS, NO, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, \
-                                                                       pad_t, pad_l, Ho, Wo, act, cb4, rpc);           \
-        else                                                                                                           \
-            dwconv_win_kernel<KK, SS, NO><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t, \
-                                                                 pad_l, Ho, Wo, act, cb4, rpc);                        \
-    } while (0)
-        if (K == 3 && stride == 1) ORBIT_DWW(3, 1, 4);
-        else if (K == 3) ORBIT_DWW(3, 2, 4);
-        else if (stride == 1) ORBIT_DWW(5, 1, 2);
-        else ORBIT_DWW(5, 2, 1);
-#undef ORBIT_DWW
-        ORBIT_LAUNCH_CHECK();
-        return ORBIT_OK;
-    }
-    // software-pipelined streaming kernel (dw_pipe: 1 = auto, 0 = never, 2 = always): measured +5..9 % on the large
-    // stride-2 layers (112x96 3x3, 56x144 5x5), slower on the small maps (two tap rows of registers -> 2 waves per SIMD)
-    const int pipe_opt = get_option("dw_pipe");
-    // (train form: also the 28 -> 14 row layer, 102 -> 60 us)
-    if (pipe_opt == 2 || (pipe_opt == 1 && stride == 2 && Ho >= (train_form ? 14 : 28))) {
-#define ORBIT_DWP(KK, SS)                                                                                              \
-    do {                                                                                                               \
-        if (use_xf)                                                                                                    \
-            dwconv_pipe_kernel<KK, SS, true, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, \
-                                                                          C, pad_t, pad_l, Ho, Wo, act, cb4, rpc, xf); \
-        else if (stats)                                                                                                \
-            dwconv_pipe_kernel<KK, SS, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C,    \
-                                                                    pad_t, pad_l, Ho, Wo, act, cb4, rpc);              \
-        else                                                                                                           \
-            dwconv_pipe_kernel<KK, SS><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t,   \
-                                                              pad_l, Ho, Wo, act, cb4, rpc);                           \
-    } while (0)
-        if (K == 3 && stride == 1) ORBIT_DWP(3, 1);
-        else if (K == 3) ORBIT_DWP(3, 2);
-        else if (stride == 1) ORBIT_DWP(5, 1);
-        else ORBIT_DWP(5, 2);
-#undef ORBIT_DWP
-        ORBIT_LAUNCH_CHECK();
-        return ORBIT_OK;
-    }
-#define ORBIT_DW(KK, SS)                                                                                               \
-    do {                                                                                                               \
-        if (use_xf)                                                                                                    \
-            dwconv_se_kernel<KK, SS, true, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, \
-                                                                        pad_t, pad_l, Ho, Wo, act, cb4, rpc, xf);      \
-        else if (stats)                                                                                                \
-            dwconv_se_kernel<KK, SS, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C,      \
-                                                                  pad_t, pad_l, Ho, Wo, act, cb4, rpc);                \
-        else                                                                                                           \
-            dwconv_se_kernel<KK, SS><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t,   \
-                                                              pad_l, Ho, Wo, act, cb4, rpc); \
-    } while (0)
-    if (K == 3 && stride == 1) ORBIT_DW(3, 1);
-    else if (K == 3) ORBIT_DW(3, 2);
-    else if (stride == 1) ORBIT_DW(5, 1);
-    else ORBIT_DW(5, 2);
-#undef ORBIT_DW
+    });
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
 }

@@ -648,7 +648,7 @@ struct DwWgLdsParams {
     int H, W, C, pad_t, pad_l, Ho, Wo, cs4, rpc, G, IWA, chunks, tiles_total, tpb;
 };
 
-template <int K, int S, bool XF>
+template <int K, int S, bool XF>  // (only XF = true is instantiated: launch_dwconv_wgrad takes this form for the transform alone)
 __global__ __launch_bounds__(256) void dwconv_wgrad_lds_kernel(const DwWgLdsParams p) {
     constexpr int NCOL = 3 * S + K, U = 8;
     extern __shared__ __attribute__((aligned(16))) float smw[];
@@ -1003,25 +1003,29 @@ int launch_dwconv_dgrad(const float* dy, const float* w_khwc, float* dx, int B, 
         if (fuse_wg) gx = std::min(gx, dgrad_s2_fused_blocks(B, H, W, C, K)), *bnb->wgrad_rows = gx;
         if (bnb) *bnb->nblk = gx;
         const size_t lds = (size_t)(K * K * G + (fuse_wg ? 8 * 256 : bnb ? 512 : 0)) * sizeof(f32x4);
-#define ORBIT_DG2(KK, PT_, PL_)                                                                                       \
-    do {                                                                                                              \
-        if (fuse_wg)                                                                                                  \
-            dwconv_dgrad_s2_kernel<KK, PT_, PL_, true, true><<<dim3(gx, yg), 256, lds, s>>>(dy, w_khwc, dx, B, H, W, C / 4,   \
-                                                                                            pad_t, pad_l, Ho, Wo, G, R, *bnb); \
-        else if (bnb)                                                                                                 \
-            dwconv_dgrad_s2_kernel<KK, PT_, PL_, true><<<dim3(gx, yg), 256, lds, s>>>(dy, w_khwc, dx, B, H, W, C / 4, pad_t,  \
-                                                                                      pad_l, Ho, Wo, G, R, *bnb);     \
-        else                                                                                                          \
-            dwconv_dgrad_s2_kernel<KK, PT_, PL_><<<dim3(gx, yg), 256, lds, s>>>(dy, w_khwc, dx, B, H, W, C / 4, pad_t, pad_l, \
-                                                                                Ho, Wo, G, R);                        \
-    } while (0)
-        const int pt = pad_t & 1, pl = pad_l & 1;
-        if (K == 3) {
-            if (!pt && !pl) ORBIT_DG2(3, 0, 0); else if (!pt) ORBIT_DG2(3, 0, 1); else if (!pl) ORBIT_DG2(3, 1, 0); else ORBIT_DG2(3, 1, 1);
-        } else {
-            if (!pt && !pl) ORBIT_DG2(5, 0, 0); else if (!pt) ORBIT_DG2(5, 0, 1); else if (!pl) ORBIT_DG2(5, 1, 0); else ORBIT_DG2(5, 1, 1);
-        }
-#undef ORBIT_DG2
+        dw_dispatch_ks(K, 2, [&](auto kc, auto) {
+            constexpr int KK = decltype(kc)::value;
+            // the padding parities are template arguments too (they fix which taps meet which pixel of a 2x2 block)
+            auto launch = [&](auto ptc, auto plc) {
+                constexpr int PT = decltype(ptc)::value, PL = decltype(plc)::value;
+                if (fuse_wg)
+                    dwconv_dgrad_s2_kernel<KK, PT, PL, true, true><<<dim3(gx, yg), 256, lds, s>>>(dy, w_khwc, dx, B, H, W, C / 4, pad_t,
+                                                                                                  pad_l, Ho, Wo, G, R, *bnb);
+                else if (bnb)
+                    dwconv_dgrad_s2_kernel<KK, PT, PL, true><<<dim3(gx, yg), 256, lds, s>>>(dy, w_khwc, dx, B, H, W, C / 4, pad_t, pad_l,
+                                                                                            Ho, Wo, G, R, *bnb);
+                else
+                    dwconv_dgrad_s2_kernel<KK, PT, PL><<<dim3(gx, yg), 256, lds, s>>>(dy, w_khwc, dx, B, H, W, C / 4, pad_t, pad_l, Ho, Wo,
+                                                                                      G, R);
+            };
+            const std::integral_constant<int, 0> even;
+            const std::integral_constant<int, 1> odd;
+            const bool pt = pad_t & 1, pl = pad_l & 1;
+            if (!pt && !pl) launch(even, even);
+            else if (!pt) launch(even, odd);
+            else if (!pl) launch(odd, even);
+            else launch(odd, odd);
+        });
         ORBIT_LAUNCH_CHECK();
         return ORBIT_OK;
     }
@@ -1045,27 +1049,19 @@ int launch_dwconv_wgrad(const float* x, const float* dy, float* dw, float* scrat
     ORBIT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "dwconv_wgrad: the input transform needs scale and shift");
     ORBIT_REQUIRE(stride == 1 || stride == 2, "dwconv_wgrad: stride %d", stride);
     const DwWgLdsGeom lg = dw_wgrad_lds_geom(B, H, W, C, K, stride, Ho, Wo);
-    // Without the input transform the global-load form below stays the default: measured on the whole LITE step (one box,
-    // profiles/r05_lite_ab_taped_xf.txt) 31.40 ms against 31.55 ms with the LDS form everywhere - its gain is the transform
-    // (30.31 ms). ORBIT_DW_WGRAD_LDS=1 forces the LDS form (parity tests, A/B runs).
-    static const char* lds_env = getenv("ORBIT_DW_WGRAD_LDS");
+    // The LDS form is taken exactly when the input transform is asked for; without it the global-load form below serves: measured
+    // on the whole LITE step (one box, profiles/r05_lite_ab_taped_xf.txt) 31.40 ms against 31.55 ms with the LDS form everywhere -
+    // its gain is the transform (30.31 ms)
     ORBIT_REQUIRE(!in_scale || lg.ok, "dwconv_wgrad: the input transform needs the LDS form, which does not fit this layer");
-    if (lg.ok && (in_scale || (lds_env && atoi(lds_env) == 1))) {
+    if (in_scale) {
         DwWgLdsParams q;
         q.x = x, q.dy = dy, q.partial = scratch, q.in_scale = in_scale, q.in_shift = in_shift, q.in_act = in_act;
         q.H = H, q.W = W, q.C = C, q.pad_t = pad_t, q.pad_l = pad_l, q.Ho = Ho, q.Wo = Wo;
         q.cs4 = lg.cs4, q.rpc = lg.rpc, q.G = lg.G, q.IWA = lg.IWA, q.chunks = lg.chunks, q.tiles_total = B * lg.chunks, q.tpb = lg.tpb;
         const dim3 grid(C / 4 / lg.cs4, lg.groups);
-#define ORBIT_DWWL(KK, SS)                                                                          \
-    do {                                                                                            \
-        if (in_scale) dwconv_wgrad_lds_kernel<KK, SS, true><<<grid, 256, lg.lds, s>>>(q);           \
-        else dwconv_wgrad_lds_kernel<KK, SS, false><<<grid, 256, lg.lds, s>>>(q);                   \
-    } while (0)
-        if (K == 3 && stride == 1) ORBIT_DWWL(3, 1);
-        else if (K == 3) ORBIT_DWWL(3, 2);
-        else if (stride == 1) ORBIT_DWWL(5, 1);
-        else ORBIT_DWWL(5, 2);
-#undef ORBIT_DWWL
+        dw_dispatch_ks(K, stride, [&](auto kc, auto sc) {
+            dwconv_wgrad_lds_kernel<decltype(kc)::value, decltype(sc)::value, true><<<grid, 256, lg.lds, s>>>(q);
+        });
         ORBIT_LAUNCH_CHECK();
         dwconv_wgrad_reduce_kernel<<<cdiv(K * K * C, 16), 256, 0, s>>>(scratch, lg.groups, K * K, C, dw);
         ORBIT_LAUNCH_CHECK();
@@ -1082,14 +1078,10 @@ int launch_dwconv_wgrad(const float* x, const float* dy, float* dw, float* scrat
     const int rows = cdiv(total_rows, chunks);
     chunks = cdiv(total_rows, rows);
     dim3 grid(chunks, yg);
-#define ORBIT_DWW(KK, SS, NBB)                                                                                          \
-    dwconv_wgrad_partial_kernel<KK, SS, NBB><<<grid, 256, 0, s>>>(x, dy, scratch, B, H, W, C / 4, pad_t, pad_l, Ho, Wo, \
-                                                                  rows, G, R)
-    if (K == 3 && stride == 1) ORBIT_DWW(3, 1, 4);
-    else if (K == 3) ORBIT_DWW(3, 2, 4);
-    else if (stride == 1) ORBIT_DWW(5, 1, 4);
-    else ORBIT_DWW(5, 2, 2);
-#undef ORBIT_DWW
+    dw_dispatch_ks(K, stride, [&](auto kc, auto sc) {
+        constexpr int KK = decltype(kc)::value, SS = decltype(sc)::value, NB = KK == 5 && SS == 2 ? 2 : 4;
+        dwconv_wgrad_partial_kernel<KK, SS, NB><<<grid, 256, 0, s>>>(x, dy, scratch, B, H, W, C / 4, pad_t, pad_l, Ho, Wo, rows, G, R);
+    });
     ORBIT_LAUNCH_CHECK();
     dwconv_wgrad_reduce_kernel<<<cdiv(K * K * C, 16), 256, 0, s>>>(scratch, chunks, K * K, C, dw);
     ORBIT_LAUNCH_CHECK();
