@@ -144,19 +144,54 @@ bool conv_prof_enabled();
 int prof_start(const char* name, double flops, double bytes, hipStream_t s, double silu = 0.0);  // silu: SiLU evaluations of the launch
 void prof_stop(int idx, hipStream_t s);  // per-launch event profiling is on (graphs are bypassed while it is)
 
+// ---- BatchNorm state as values --------------------------------------------------------------------------------------
+// One layer's slice of the four fold arrays (batch or running mean, 1 / sqrt(var + eps), folded scale / shift), already offset
+// to the layer: BnFold is what a train-mode finalize writes, BnFoldC what every later pass reads.
+struct BnFoldC {
+    const float* mean = nullptr;
+    const float* invstd = nullptr;
+    const float* scale = nullptr;
+    const float* shift = nullptr;
+};
+struct BnFold {
+    float* mean = nullptr;
+    float* invstd = nullptr;
+    float* scale = nullptr;  // scale / shift nullable: statistics only
+    float* shift = nullptr;
+    operator BnFoldC() const { return {mean, invstd, scale, shift}; }
+};
+// the affine and running-statistics inputs of a train-mode finalize (gamma / beta nullable = 1 / 0; conv_bias nullable; running
+// statistics nullable = no update)
+struct BnAffine {
+    const float* gamma = nullptr;
+    const float* beta = nullptr;
+    const float* conv_bias = nullptr;
+    float* running_mean = nullptr;
+    float* running_var = nullptr;
+    float eps = 0.f, momentum = 0.f;
+};
+// ... and of a backward: the gamma the forward used and where its gradients go (each nullable = not wanted)
+struct BnGrads {
+    const float* gamma = nullptr;
+    float* dgamma = nullptr;
+    float* dbeta = nullptr;
+    float* dbias = nullptr;  // gradient of the preceding convolution's bias
+};
+// a taped BatchNorm + activation layer as a fused backward reads it: raw input y of the BatchNorm, its fold view, the
+// activation, and the [rows][2][C] buffer that receives the channel sums of g and g * xhat
+struct BnTaped {
+    const float* y = nullptr;
+    BnFoldC bn;
+    int act = 0;
+    float* partial = nullptr;
+};
+
 // The depthwise DATA gradient fused with the first pass of the preceding BatchNorm's backward (the LITE step): the tensor a
 // depthwise dgrad produces is d(act(BatchNorm(y))) of the expansion conv before it; with this the kernel reads y at its output
 // pixels, writes g = dx * act'(y * scale + shift) instead of dx and emits the per-block channel sums of g and of g * xhat
 // (xhat = (y - mean) * invstd) to partial[block][2][C] - the layout bn_bwd_finalize reads - so that BatchNorm's backward needs
 // no reduction pass over (dx, y) of its own (launch_bn_backward_reduced finishes it).
-struct DwBnBwd {
-    const float* y = nullptr;  // raw output of the producing conv, laid out like the dgrad's output
-    const float* mean = nullptr;
-    const float* invstd = nullptr;
-    const float* scale = nullptr;
-    const float* shift = nullptr;
-    int act = 0;
-    float* partial = nullptr;
+struct DwBnBwd : BnTaped {  // (y: raw output of the producing conv, laid out like the dgrad's output)
     int* nblk = nullptr;  // out: partial rows written, 0 when the chosen kernel has no fused form (then dx was written plain)
     // optional: the layer's FILTER gradient in the same pass. The layer's input is act(y * scale + shift) - the tensor the kernel
     // rebuilds at its output pixels anyway - and every (output pixel, tap) pair meets the dy element the data gradient multiplies
@@ -231,23 +266,19 @@ int launch_se_gate(const float* pooled, const float* w1, const float* b1, const 
 // ---- training-side launchers (train_ops.hip, conv_wgrad.hip) ------------------------------------------------------
 int bn_reduce_blocks(int M, int C);  // rows of the [blocks][2][C] partial buffer the BatchNorm reductions need
 // batch statistics of y[M][C] -> mean, invstd, folded scale/shift (gamma/beta nullable = 1/0), running-stat update
-int launch_bn_stats(const float* y, int M, int C, float eps, float momentum, const float* gamma, const float* beta,
-                    const float* conv_bias, float* mean, float* invstd, float* scale, float* shift, float* running_mean,
-                    float* running_var, float* partial, hipStream_t s);
+int launch_bn_stats(const float* y, int M, int C, const BnAffine& a, const BnFold& out, float* partial, hipStream_t s);
 // the same from [nblk][2][C] partials a producing kernel wrote (ConvDesc::stats, launch_dwconv_se(..., stats)); `partial` is
 // bn_partial_floats(nblk, C) floats (room for the compaction stage of very long partial lists)
 size_t bn_partial_floats(size_t nblk, int C);
 int launch_sum_partials(const float* partial, int nblk, int C, float* stats /* [2][C] */, hipStream_t s);
 // batch statistics of a POINTWISE conv's output y = W x from the Gram matrix of its input x [P][Cin] (Cin = 16 or 24;
 // W [C][Cin] as torch stores a 1x1 filter): no pass over y, no y at all. scratch: bn_gram_scratch_floats(P, Cin) floats
+constexpr int BN_GRAM_MAX_CIN = 24;
 bool bn_gram_supported(int Cin);
 size_t bn_gram_scratch_floats(int P, int Cin);
-int launch_bn_stats_from_gram(const float* x, int P, int Cin, const float* w, int C, float eps, float momentum,
-                              const float* gamma, const float* beta, float* mean, float* invstd, float* scale, float* shift,
-                              float* running_mean, float* running_var, float* scratch, hipStream_t s);
-int launch_bn_stats_from_partials(float* partial, int nblk, int M, int C, float eps, float momentum, const float* gamma,
-                                  const float* beta, const float* conv_bias, float* mean, float* invstd, float* scale,
-                                  float* shift, float* running_mean, float* running_var, hipStream_t s);
+int launch_bn_stats_from_gram(const float* x, int P, int Cin, const float* w, int C, const BnAffine& a, const BnFold& out,
+                              float* scratch, hipStream_t s);  // (a pointwise conv with a bias is not served: a.conv_bias == nullptr)
+int launch_bn_stats_from_partials(float* partial, int nblk, int M, int C, const BnAffine& a, const BnFold& out, hipStream_t s);
 int launch_scale_shift_act(const float* y, const float* scale, const float* shift, const float* residual, int act,
                            size_t M, int C, float* out, hipStream_t s);
 // a = act(y * scale + shift) for [B][HW][C] plus the squeeze-excite pooling partials pool[B][se_pool_chunks][C] of a
@@ -255,11 +286,10 @@ int se_pool_chunks(int B, int HW, int C);
 int launch_scale_shift_act_pool(const float* y, const float* scale, const float* shift, int act, int B, int HW, int C,
                                 float* out, float* pool, hipStream_t s);
 // coef: 3*C floats of scratch; dy nullable (reductions only); dres nullable (gradient of the residual input)
-// scale/shift: folded BatchNorm of the forward (needed to rebuild the SiLU pre-activation), else nullable
-int launch_bn_backward(const float* dout, const float* out, const float* y, const float* mean, const float* invstd,
-                       const float* gamma, const float* scale, const float* shift, int train, int act, int M, int C,
-                       float* dy, float* dres, int dres_accumulate, float* dgamma, float* dbeta, float* dbias,
-                       float* partial, float* coef, hipStream_t s);
+// bn.scale / bn.shift: folded BatchNorm of the forward (needed to rebuild the SiLU pre-activation), else nullable
+int launch_bn_backward(const float* dout, const float* out, const float* y, const BnFoldC& bn, const BnGrads& p, int train,
+                       int act, int M, int C, float* dy, float* dres, int dres_accumulate, float* partial, float* coef,
+                       hipStream_t s);
 int launch_maxpool_idx(const float* x, float* y, uint8_t* idx, int B, int H, int W, int C, int K, int stride, int pad,
                        int Ho, int Wo, hipStream_t s);
 int launch_maxpool_bwd(const float* dy, const uint8_t* idx, float* dx, int B, int H, int W, int C, int K, int stride,
@@ -267,21 +297,15 @@ int launch_maxpool_bwd(const float* dy, const uint8_t* idx, float* dx, int B, in
 int launch_avgpool_bwd(const float* dy, float* dx, int B, int HW, int C, hipStream_t s);
 int launch_upsample_zero(const float* src, float* dst, int B, int H, int W, int C, int stride, int Hs, int Ws,
                          hipStream_t s);
-int launch_add_inplace(float* dst, const float* src, size_t n, hipStream_t s);
 // MBConv pieces (train_mbconv.hip)
 int launch_colmean(const float* x, float* pooled, int B, int HW, int C, hipStream_t s);  // [B][HW][C] -> means [B][C]
-int launch_gate_mul(const float* x, const float* gate, float* xg, int B, int HW, int C, hipStream_t s);
 size_t se_bwd_scratch_floats(int B, int C, int R);
 // dxg: gradient of x*gate; writes dx (through the product, the gate MLP and the average pool) and, when dw1 != NULL, the
 // gradients of the four SE tensors (W1 [R][C], b1 [R], W2 [C][R], b2 [C])
 // bn (optional): x = act(BatchNorm(y)); then `dx` receives g = d x * act'(.) instead of d x and bn->partial the per-(frame,
 // chunk) sums of g and g * xhat ([B * se_pool_chunks(B, HW, C)][2][C]): launch_bn_backward_reduced finishes that BatchNorm's
 // backward without a reduction pass of its own
-struct SeBnFuse {
-    const float *y, *mean, *invstd, *scale, *shift;
-    int act;
-    float* partial;
-};
+using SeBnFuse = BnTaped;
 int launch_se_gate_backward(const float* dxg, const float* x, const float* pooled, const float* gate, const float* w1,
                             const float* b1, const float* w2, const float* b2, float* dx, float* dw1, float* db1,
                             float* dw2, float* db2, float* scratch, int B, int HW, int C, int R, hipStream_t s,
@@ -303,16 +327,14 @@ struct SeParamJobs {
 SeParamJob se_bwd_param_job(const float* scratch, const float* pooled, int B, int C, int R, float* dw1, float* db1, float* dw2,
                             float* db2);
 int launch_se_param_grad_batched(const SeParamJobs& jobs, int n, hipStream_t s);
-int launch_bn_backward_reduced_gated(const float* dxg, const float* gate, const float* dpooled, int HW, const float* y,
-                                     const float* mean, const float* invstd, const float* scale, const float* shift, int act,
-                                     const float* gamma, int train, int M, int C, float* dy, float* dgamma, float* dbeta,
-                                     float* partial, int nblk, float* coef, hipStream_t s);
+// t: the layer (y, fold view, act) and t.partial = the [nblk][2][C] sums the squeeze-excite backward left
+int launch_bn_backward_reduced_gated(const float* dxg, const float* gate, const float* dpooled, int HW, const BnTaped& t,
+                                     const BnGrads& p, int train, int M, int C, float* dy, int nblk, float* coef, hipStream_t s);
 // (w2t, optional: W2 transposed to [R][C] - the plan's packed copy; the MLP backward then reads W2 contiguously)
 // BatchNorm backward whose reduction pass already ran (g = dout * act'(.) in `g`, [nblk][2][C] sums of g and g * xhat in
 // `partial`): finalize + apply only. coef: 3*C floats
-int launch_bn_backward_reduced(const float* g, const float* y, const float* mean, const float* invstd, const float* gamma,
-                               int train, int M, int C, float* dy, float* dgamma, float* dbeta, float* partial, int nblk,
-                               float* coef, hipStream_t s);
+int launch_bn_backward_reduced(const float* g, const float* y, const BnFoldC& bn, const BnGrads& p, int train, int M, int C,
+                               float* dy, float* partial, int nblk, float* coef, hipStream_t s);
 // flip_scratch (K*K*C floats, optional): stride-1 layers then run as a FORWARD depthwise convolution of dy with the flipped
 // taps through the LDS-patch kernels of csrc/ops.hip instead of the per-pixel gather
 int launch_dwconv_dgrad(const float* dy, const float* w_khwc, float* dx, int B, int H, int W, int C, int K, int stride,

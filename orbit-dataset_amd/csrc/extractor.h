@@ -36,6 +36,8 @@ struct BNDev {         // device descriptor for the fold kernel
 };
 
 enum OpKind { OP_CONV, OP_DWCONV, OP_MAXPOOL, OP_AVGPOOL, OP_SE, OP_MBFRONT };
+// buffer ids of Op::in / out / res: -1 = the frames, 0..2 = the rotating activation buffers, and
+enum { BUF_FEATS = 100, BUF_POOLED = 101, BUF_GATE = 102 };  // the features, the squeeze-excite pooling partials, the gate
 
 // One weight re-layout of a plan (orbit_extractor_finalize / the dgrad filters of the training runtime). A LITE step repacks
 // every filter after the optimizer moved it: ~80 + 32 launches of ~4 us each per step as separate kernels; all jobs of a
@@ -101,7 +103,7 @@ static inline int run_pack_jobs(const std::vector<PackJob>& jobs, PackJob** d_jo
 
 struct Op {
     OpKind kind;
-    int in = -1, out = -1, res = -1;  // buffer ids: -1 frames, 0..2 activations, 100 feats, 101 pooled, 102 gate
+    int in = -1, out = -1, res = -1;  // buffer ids (BUF_* above)
     int H = 0, W = 0, Cin = 0, Cout = 0, KH = 1, KW = 1, stride = 1, pad_t = 0, pad_l = 0, Ho = 0, Wo = 0;
     int act = ORBIT_ACT_NONE, pool2 = 0, x_nchw = 0, use_gate = 0;
     int weight = -1, bias = -1, bn = -1;  // param / BN indices
@@ -141,12 +143,6 @@ static __global__ __launch_bounds__(256) void bn_fold_all_kernel(const BNDev* __
 
 }  // namespace orbit
 
-struct orbit_extractor;
-namespace orbit {
-void extractor_train_invalidate(const orbit_extractor* fe);  // parameters changed: training-side repacks are stale
-void extractor_train_release(const orbit_extractor* fe);     // plan is being destroyed
-}  // namespace orbit
-
 using namespace orbit;  // internal header: only included by the two runtime translation units
 
 struct orbit_extractor {
@@ -177,6 +173,13 @@ struct orbit_extractor {
     BNDev* d_bn = nullptr;
     std::vector<BNDev> bn_dev;  // host copy of the fold descriptors
     bool finalized = false;
+    // training side (csrc/extractor_train.hip), built at the first backward: the dgrad-packed filters, their re-layouts as one
+    // launch for all layers (PackJob kind 4) and whether they follow the current parameters (every load clears it)
+    float* d_dgrad = nullptr;
+    std::vector<size_t> dgrad_off;  // per op, SIZE_MAX: none
+    std::vector<PackJob> dgrad_jobs;
+    PackJob* d_dgrad_jobs = nullptr;
+    bool dgrad_packed = false;
 
     // HIP-graph caches (graph_cache.h). Forward: one instantiated graph per distinct (pointers, batch) tuple of forward(). A
     // forward is 25-90 dependent launches; replaying them as one graph launch takes the host out of the loop (on a slow or

@@ -69,7 +69,7 @@ static int build_resnet18(orbit_extractor* fe, int H, int W) {
         }
     }
     Op o;
-    o.kind = OP_AVGPOOL, o.in = cur, o.out = 100, o.H = h, o.W = w, o.Cin = 512, o.Cout = 512;
+    o.kind = OP_AVGPOOL, o.in = cur, o.out = BUF_FEATS, o.H = h, o.W = w, o.Cin = 512, o.Cout = 512;
     fe->ops.push_back(o);
     return ORBIT_OK;
 }
@@ -115,9 +115,9 @@ static int build_efficientnet_b0(orbit_extractor* fe, int H, int W, bool unfused
         fe->ops.push_back(o);
     };
     auto add_se = [&](const std::string& p, int buf, int C, int R, int hh, int ww, int chunks) {
-        (void)buf;  // the pooled sums come from the depthwise kernel's partials (buffer 101), not from a re-read
+        (void)buf;  // the pooled sums come from the depthwise kernel's partials (BUF_POOLED), not from a re-read
         Op s;
-        s.kind = OP_SE, s.in = 101, s.out = 102, s.Cin = C, s.R = R;
+        s.kind = OP_SE, s.in = BUF_POOLED, s.out = BUF_GATE, s.Cin = C, s.R = R;
         s.se_chunks = chunks, s.se_hw = hh * ww;
         s.packed_off = fe->packed_floats;  // W2 transposed to [R][C]
         fe->packed_floats += (size_t)(C * R + 3) / 4 * 4;
@@ -224,7 +224,7 @@ static int build_efficientnet_b0(orbit_extractor* fe, int H, int W, bool unfused
     bn = fe->add_bn("bn2", 1280, eps, true);  // root bn2 is FiLM-tagged
     fe->add_conv("conv_head.weight", bn, cur, t1, -1, h, w, cin, 1280, 1, 1, 0, 0, h, w, ORBIT_ACT_SILU, 0, 0, 0);
     Op o;
-    o.kind = OP_AVGPOOL, o.in = t1, o.out = 100, o.H = h, o.W = w, o.Cin = 1280, o.Cout = 1280;
+    o.kind = OP_AVGPOOL, o.in = t1, o.out = BUF_FEATS, o.H = h, o.W = w, o.Cin = 1280, o.Cout = 1280;
     fe->ops.push_back(o);
     return ORBIT_OK;
 }
@@ -246,7 +246,7 @@ static int build_set_encoder(orbit_extractor* fe, int H, int W) {
         cur = out, cin = 64, h /= 2, w /= 2;
     }
     Op o;
-    o.kind = OP_AVGPOOL, o.in = cur, o.out = 100, o.H = h, o.W = w, o.Cin = 64, o.Cout = 64;
+    o.kind = OP_AVGPOOL, o.in = cur, o.out = BUF_FEATS, o.H = h, o.W = w, o.Cin = 64, o.Cout = 64;
     fe->ops.push_back(o);
     return ORBIT_OK;
 }
@@ -320,7 +320,8 @@ int orbit_extractor_create_ex(const char* name, int H, int W, int flags, orbit_e
 
 void orbit_extractor_destroy(orbit_extractor_t* fe) {
     if (!fe) return;
-    extractor_train_release(fe);
+    (void)hipFree(fe->d_dgrad);
+    (void)hipFree(fe->d_dgrad_jobs);
     fe->graphs.clear();
     fe->train_graphs.clear();
     if (fe->cap_stream) (void)hipStreamDestroy(fe->cap_stream);
@@ -352,7 +353,7 @@ int orbit_extractor_load(orbit_extractor_t* fe, const char* key, const float* da
     ORBIT_HIP_CHECK(hipMemcpy(fe->d_pool + p.off, data, numel * sizeof(float), hipMemcpyDefault));
     p.loaded = true;
     fe->finalized = false;
-    extractor_train_invalidate(fe);
+    fe->dgrad_packed = false;
     return ORBIT_OK;
 }
 
@@ -368,7 +369,7 @@ int orbit_extractor_load_async(orbit_extractor_t* fe, const char* key, const flo
                                    (hipStream_t)stream));
     p.loaded = true;
     fe->finalized = false;
-    extractor_train_invalidate(fe);
+    fe->dgrad_packed = false;
     return ORBIT_OK;
 }
 
@@ -406,7 +407,7 @@ int orbit_extractor_load_all_async(orbit_extractor_t* fe, const float* const* de
     ORBIT_LAUNCH_CHECK();
     for (Param& p : fe->params) p.loaded = true;
     fe->finalized = false;
-    extractor_train_invalidate(fe);
+    fe->dgrad_packed = false;
     return ORBIT_OK;
 }
 
@@ -541,9 +542,9 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
     char* ws = static_cast<char*>(workspace);
     auto buf = [&](int id) -> float* {
         if (id == -1) return const_cast<float*>(frames);
-        if (id == 100) return feats;
-        if (id == 101) return reinterpret_cast<float*>(ws + L.pooled);
-        if (id == 102) return reinterpret_cast<float*>(ws + L.gate);
+        if (id == BUF_FEATS) return feats;
+        if (id == BUF_POOLED) return reinterpret_cast<float*>(ws + L.pooled);
+        if (id == BUF_GATE) return reinterpret_cast<float*>(ws + L.gate);
         return reinterpret_cast<float*>(ws + L.buf[id]);
     };
     const float* scale = fe->d_fold;
@@ -576,7 +577,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                     d.x = buf(o.in), d.w_packed = fe->d_packed + o.packed_off, d.y = buf(o.out);
                     d.scale = scale + fe->bns[o.bn].fold_off, d.shift = shift + fe->bns[o.bn].fold_off;
                     d.residual = o.res >= 0 ? buf(o.res) : nullptr;
-                    d.partial = buf(101), d.chunks = se.se_chunks, d.se_hw = se.se_hw;
+                    d.partial = buf(BUF_POOLED), d.chunks = se.se_chunks, d.se_hw = se.se_hw;
                     d.w1 = fe->d_pool + fe->params[se.se_w1].off, d.b1 = fe->d_pool + fe->params[se.se_b1].off;
                     d.w2t = fe->d_packed + se.packed_off, d.b2 = fe->d_pool + fe->params[se.se_b2].off, d.R = se.R;
                     d.B = B, d.H = o.H, d.W = o.W, d.Cin = o.Cin, d.Cout = o.Cout;
@@ -589,7 +590,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                 d.scale = o.bn >= 0 ? scale + fe->bns[o.bn].fold_off : nullptr;
                 d.shift = o.bn >= 0 ? shift + fe->bns[o.bn].fold_off : nullptr;
                 d.residual = o.res >= 0 ? buf(o.res) : nullptr;
-                d.gate = o.use_gate ? buf(102) : nullptr;
+                d.gate = o.use_gate ? buf(BUF_GATE) : nullptr;
                 d.B = B, d.H = o.H, d.W = o.W, d.Cin = o.Cin, d.Cout = o.Cout, d.KH = o.KH, d.KW = o.KW;
                 d.stride = o.stride, d.pad_t = o.pad_t, d.pad_l = o.pad_l, d.Ho = o.Ho, d.Wo = o.Wo;
                 d.act = o.act, d.pool2 = o.pool2, d.x_nchw = o.x_nchw;
@@ -600,7 +601,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
             case OP_DWCONV:
                 rc = launch_dwconv_se(buf(o.in), fe->d_packed + o.packed_off, buf(o.out),
                                       scale + fe->bns[o.bn].fold_off, shift + fe->bns[o.bn].fold_off,
-                                      o.pool_partial ? buf(101) : nullptr, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t,
+                                      o.pool_partial ? buf(BUF_POOLED) : nullptr, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t,
                                       o.pad_l, o.Ho, o.Wo, o.act, s);
                 break;
             case OP_MBFRONT:
@@ -608,12 +609,12 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                     rc = launch_stem_rows(buf(o.in), fe->d_packed + o.packed_off2, scale + fe->bns[o.bn].fold_off,
                                           shift + fe->bns[o.bn].fold_off, fe->d_packed + o.packed_off,
                                           scale + fe->bns[o.bn2].fold_off, shift + fe->bns[o.bn2].fold_off, buf(o.out),
-                                          buf(101), B, o.stem_h, o.stem_w, o.stem_pt, o.stem_pl, o.H, o.W, s, o.se_chunks);
+                                          buf(BUF_POOLED), B, o.stem_h, o.stem_w, o.stem_pt, o.stem_pl, o.H, o.W, s, o.se_chunks);
                 else
                     rc = launch_mbconv_rows(buf(o.in), fe->d_pool + fe->params[o.weight].off,
                                             scale + fe->bns[o.bn].fold_off, shift + fe->bns[o.bn].fold_off,
                                             fe->d_packed + o.packed_off, scale + fe->bns[o.bn2].fold_off,
-                                            shift + fe->bns[o.bn2].fold_off, buf(o.out), buf(101), B, o.H, o.W, o.Cin,
+                                            shift + fe->bns[o.bn2].fold_off, buf(o.out), buf(BUF_POOLED), B, o.H, o.W, o.Cin,
                                             o.Cout, o.KH, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s, o.se_chunks);
                 break;
             case OP_MAXPOOL:
@@ -625,9 +626,9 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                 break;
             case OP_SE:
                 if (se_in_projection(fe, oi)) break;  // the projection computes the gate in its prologue
-                rc = launch_se_gate2(buf(101), o.se_chunks, o.se_hw, fe->d_pool + fe->params[o.se_w1].off,
+                rc = launch_se_gate2(buf(BUF_POOLED), o.se_chunks, o.se_hw, fe->d_pool + fe->params[o.se_w1].off,
                                      fe->d_pool + fe->params[o.se_b1].off, fe->d_packed + o.packed_off,
-                                     fe->d_pool + fe->params[o.se_b2].off, buf(102), B, o.Cin, o.R, s);
+                                     fe->d_pool + fe->params[o.se_b2].off, buf(BUF_GATE), B, o.Cin, o.R, s);
                 break;
         }
         if (rc != ORBIT_OK) return rc;

@@ -49,9 +49,9 @@ __global__ __launch_bounds__(256) void bn_apply_deferred_kernel(const BNDev* __r
 }
 
 struct TapeLayout {
-    // byte offsets per op ((size_t)-1: none). conv / depthwise: y raw output, a activation, p/idx fused pool, xg gated
-    // input. squeeze-excite: p = pooled means [B][C], a = gate [B][C]. max-pool: p output, idx argmax.
-    std::vector<size_t> y, a, p, idx, xg;
+    // byte offsets per op ((size_t)-1: none). conv / depthwise: y raw output, a activation, p/idx fused pool.
+    // squeeze-excite: p = pooled means [B][C], a = gate [B][C]. max-pool: p output, idx argmax.
+    std::vector<size_t> y, a, p, idx;
     size_t mean = 0, invstd = 0, scale = 0, shift = 0, partial = 0, pool = 0, total = 0;
     size_t rstat = 0;  // [2][fold_floats]: batch mean / unbiased variance of an ORBIT_TRAIN_DEFER_RUNNING_STATS forward
 };
@@ -69,63 +69,27 @@ static bool plan_trainable(const orbit_extractor* fe) {
 
 static bool has_bn(const Op& o) { return o.kind == OP_CONV || o.kind == OP_DWCONV; }
 
-// A batch-statistics conv whose activated output is read by ONE consumer, the depthwise conv that follows (EfficientNet's
-// expansion convs and stem): that consumer applies the conv's BatchNorm + SiLU as it loads the RAW output (DwInXf in
-// csrc/ops.hip), so the activated 6x-expanded tensor is never written - on forwards that run no backward (round 3) and, since
-// round 5, on TAPED ones: the only other reader of the activation is the depthwise filter gradient, whose LDS form applies the
-// same transform as it stages its input patch (dwconv_wgrad_lds_kernel, csrc/train_mbconv.hip; each element passes once). A
-// first attempt with the transform inside the global-load filter-gradient kernel - every input loaded K times, SiLU per load -
-// lost more there (1.76 -> 3.98 ms) than the forward gained (profiles/r05_lite_ab_taped_xf.txt). The activation must not be
-// ReLU on a taped forward (its BatchNorm backward reads the mask from the activated tensor). Forward and backward evaluate
-// this on the same plan and batch; the option is read by both (do not flip train_dw_xf between a forward and its backward).
-static bool conv_feeds_dw_raw(const orbit_extractor* fe, size_t i, int bn_train, bool no_backward, int B) {
-    const Op& o = fe->ops[i];
-    if (o.kind != OP_CONV || !bn_train || !get_option("train_dw_xf") || o.pool2 || o.res >= 0 || o.Cout % 4 != 0) return false;
-    if (i + 1 >= fe->ops.size() || fe->ops[i + 1].kind != OP_DWCONV || fe->ops[i + 1].in != o.out) return false;
-    if (!no_backward) {
-        const Op& d = fe->ops[i + 1];
-        if (o.act != ORBIT_ACT_SILU && o.act != ORBIT_ACT_NONE) return false;
-        if (!dwconv_wgrad_xf_supported(B, d.H, d.W, d.Cin, d.KH, d.stride, d.Ho, d.Wo)) return false;
-    }
-    for (size_t j = i + 2; j < fe->ops.size(); ++j) {  // no later reader of the buffer before it is written again
+// no op from `first` on reads buffer `id` before it is written again
+static bool no_later_reader(const orbit_extractor* fe, size_t first, int id) {
+    for (size_t j = first; j < fe->ops.size(); ++j) {
         const Op& q = fe->ops[j];
-        if (q.in == o.out || q.res == o.out) return false;
-        if (q.out == o.out) break;
+        if (q.in == id || q.res == id) return false;
+        if (q.out == id) break;
     }
     return true;
 }
 
-// Round 6: on a NO-BACKWARD batch-statistics forward (the cache pass of the LITE step: 200 frames under torch.no_grad() while the
-// extractor is being learned, reference few_shot_recognisers.py:404-408) an MBConv block's expansion conv + depthwise conv run
-// as the row-streaming fused front of the inference plans in two sweeps: (1) the expansion conv as a STATISTICS SWEEP
-// (ConvDesc::stats_only: same kernel, same tiles, nothing stored) gives the first BatchNorm's batch statistics, (2) the fused
-// front (csrc/mbconv_rows.hip, RAW form) re-expands in its LDS ring with that scale / shift, stores the RAW depthwise outputs
-// and their column sums - the second BatchNorm then proceeds as on the unfused path. The 6x-expanded tensor (963 MB per 200
-// frames for block 1.0) is neither written nor read. Taped forwards keep the unfused pair: their backward reads that tensor.
-// `train_fused_fronts`: 1 (default) = where measured faster (the 112x112 / 56x56 blocks), 0 = never, 2 = every supported shape,
-// 3 = as 2 with the statistics sweep of the conv instead of the Gram-matrix statistics (parity tests: bit-identical first
-// BatchNorm).
-static bool fused_front_sweeps(const orbit_extractor* fe, size_t i, int bn_train, bool no_backward) {
-    const Op& o = fe->ops[i];
-    const int opt = get_option("train_fused_fronts");
-    if (!opt || o.kind != OP_CONV || !bn_train || !no_backward || o.x_nchw || o.pool2 || o.res >= 0 || o.use_gate) return false;
-    if (o.KH != 1 || o.KW != 1 || o.stride != 1 || o.act != ORBIT_ACT_SILU) return false;
-    if (i + 1 >= fe->ops.size() || fe->ops[i + 1].kind != OP_DWCONV || fe->ops[i + 1].in != o.out) return false;
-    const Op& d = fe->ops[i + 1];
-    if (d.act != ORBIT_ACT_SILU || d.Cin != o.Cout || !mbconv_rows_supported(o.H, o.W, o.Cin, o.Cout, d.KH, d.stride)) return false;
-    if (fe->bns[o.bn].conv_bias >= 0) return false;
-    if (opt == 1 && o.H < 56) return false;  // (the 28x28 blocks: statistics sweep + front measured no faster than the pair)
-    // the front's statistics rows (one per frame and strip-band tile) are sized for B * 16 tiles (max_bn_partial_floats below):
-    // wider maps (Wo = 113 / 120 for 452 / 480 pixel frames: 25 tiles) take the unfused pair before any statistics are touched
-    const int tiles = mbconv_rows_tiles(o.H, o.W, o.Cin, o.Cout, d.KH, d.stride);
-    if (tiles <= 0 || tiles > 16) return false;
-    for (size_t j = i + 2; j < fe->ops.size(); ++j) {  // no later reader of the expanded tensor before its buffer is rewritten
-        const Op& q = fe->ops[j];
-        if (q.in == o.out || q.res == o.out) return false;
-        if (q.out == o.out) break;
-    }
-    return true;
+// the depthwise op whose activated output squeeze-excite op i pools: the nearest one before it (-1: malformed plan)
+static int se_source(const orbit_extractor* fe, size_t i) {
+    for (int j = (int)i - 1; j >= 0; --j)
+        if (fe->ops[j].kind == OP_DWCONV) return j;
+    return -1;
 }
+
+// The two-sweep fused front (train_forms below) writes one statistics row per frame and strip-band tile. The partial buffer is
+// sized for this many tiles per frame; wider maps (Wo = 113 / 120 for 452 / 480 pixel frames: 25 tiles) take the unfused pair
+// before any statistics are touched.
+static const int FRONT_TILE_CAP = 16;
 
 static size_t max_bn_partial_floats(const orbit_extractor* fe, int B) {
     size_t m = 4;
@@ -145,8 +109,8 @@ static size_t max_bn_partial_floats(const orbit_extractor* fe, int B) {
                 m = std::max(m, bn_partial_floats((size_t)B * dwconv_se_chunks(o.Ho), o.Cout));
                 // (the two-sweep fused front writes one row per frame and strip-band tile instead; its first sweep's Gram
                 // partials of the block input live here too)
-                m = std::max(m, bn_partial_floats((size_t)B * 16, o.Cout));
-                m = std::max(m, bn_gram_scratch_floats(B * o.H * o.W, 24));
+                m = std::max(m, bn_partial_floats((size_t)B * FRONT_TILE_CAP, o.Cout));
+                m = std::max(m, bn_gram_scratch_floats(B * o.H * o.W, BN_GRAM_MAX_CIN));
             }
             // backward of a depthwise BatchNorm whose reduction rides on the squeeze-excite backward (+ 3*C coefficients)
             if (o.kind == OP_DWCONV)
@@ -158,14 +122,10 @@ static size_t max_bn_partial_floats(const orbit_extractor* fe, int B) {
 // squeeze-excite pooling partials of the pooled apply pass (launch_scale_shift_act_pool): [B][chunks][C]
 static size_t max_se_pool_floats(const orbit_extractor* fe, int B) {
     size_t m = 4;
-    int last_dw = -1;
     for (size_t i = 0; i < fe->ops.size(); ++i) {
         const Op& o = fe->ops[i];
-        if (o.kind == OP_DWCONV) last_dw = (int)i;
-        if (o.kind == OP_SE && last_dw >= 0) {
-            const Op& dw = fe->ops[last_dw];
-            m = std::max(m, (size_t)B * se_pool_chunks(B, dw.Ho * dw.Wo, o.Cin) * o.Cin);
-        }
+        const int dw = o.kind == OP_SE ? se_source(fe, i) : -1;
+        if (dw >= 0) m = std::max(m, (size_t)B * se_pool_chunks(B, fe->ops[dw].Ho * fe->ops[dw].Wo, o.Cin) * o.Cin);
     }
     return m;
 }
@@ -173,7 +133,7 @@ static size_t max_se_pool_floats(const orbit_extractor* fe, int B) {
 static TapeLayout tape_layout(const orbit_extractor* fe, int B) {
     TapeLayout L;
     const size_t n = fe->ops.size();
-    L.y.assign(n, NONE), L.a.assign(n, NONE), L.p.assign(n, NONE), L.idx.assign(n, NONE), L.xg.assign(n, NONE);
+    L.y.assign(n, NONE), L.a.assign(n, NONE), L.p.assign(n, NONE), L.idx.assign(n, NONE);
     size_t off = 0;
     auto take = [&](size_t bytes) {
         const size_t o = off;
@@ -190,7 +150,7 @@ static TapeLayout tape_layout(const orbit_extractor* fe, int B) {
                 L.p[i] = take(pe * 4), L.idx[i] = take(pe);
             }
             // (a gated projection reads x and the gate separately - forward through the GATE prologue of conv_igemm, filter
-            // gradient through conv_wgrad's - so the product x * gate is never materialised; L.xg stays unused)
+            // gradient through conv_wgrad's - so the product x * gate is never materialised and has no place on the tape)
         } else if (o.kind == OP_DWCONV) {
             const size_t e = (size_t)B * o.Ho * o.Wo * o.Cout;
             L.y[i] = take(e * 4), L.a[i] = take(e * 4);
@@ -221,10 +181,104 @@ static Producers producers(const orbit_extractor* fe) {
         const Op& o = fe->ops[i];
         P.in.push_back(o.in >= 0 && last.count(o.in) ? last[o.in] : -1);
         P.res.push_back(o.res >= 0 && last.count(o.res) ? last[o.res] : -1);
-        P.gate.push_back(o.kind == OP_CONV && o.use_gate && last.count(102) ? last[102] : -1);
+        P.gate.push_back(o.kind == OP_CONV && o.use_gate && last.count(BUF_GATE) ? last[BUF_GATE] : -1);
         last[o.out] = (int)i;
     }
     return P;
+}
+
+// ---- the training form of every op ----------------------------------------------------------------------------------------
+// Decided here, once per run, for the forward AND the backward (both call train_forms on the same plan, batch and BatchNorm mode;
+// the backward with no_backward = false). This is the only reader of the options train_dw_xf and train_fused_fronts: do not flip
+// them between a forward and its backward. The sizing functions above stay independent of options and flags (the tape is sized
+// without them): they take the maximum over the forms.
+enum ConvForm {
+    CONV_PLAIN,       // (batch statistics, then) the activation pass
+    CONV_DUAL,        // running-statistics BatchNorm: the conv's epilogue writes the raw output AND the activation
+    CONV_RAW_TO_DW,   // batch statistics only: the depthwise conv that follows applies BatchNorm + activation as it loads
+    CONV_SWEEP_GRAM,  // sweep 1 of a fused front: batch statistics from the Gram matrix of the conv's input, no conv
+    CONV_SWEEP_CONV   // sweep 1 of a fused front: the conv run for its statistics alone (ConvDesc::stats_only)
+};
+struct OpForm {
+    ConvForm conv = CONV_PLAIN;  // OP_CONV
+    int tiles = 0;               // ... the two sweeps: strip-band tiles per frame of the fused front (<= FRONT_TILE_CAP)
+    int raw_src = -1;            // OP_DWCONV: the conv whose RAW output it reads (CONV_RAW_TO_DW; the backward's raw_fed), or -1
+    int front = -1;              // ... the conv it runs with as the row-streaming fused front (sweep 2), or -1
+    bool pooled = false;         // ... its activation pass also leaves the squeeze-excite pooling partials in TapeLayout::pool
+    bool through_act = false;    // ... backward: its data gradient may go through the producing conv's activation (DwBnBwd)
+    int se_dw = -1;              // OP_SE: the depthwise op it pools
+};
+typedef std::vector<OpForm> TrainForms;
+
+static TrainForms train_forms(const orbit_extractor* fe, int B, int bn_train, bool no_backward) {
+    const int dw_xf = get_option("train_dw_xf"), fronts = get_option("train_fused_fronts");
+    const size_t n = fe->ops.size();
+    const Producers P = producers(fe);
+    TrainForms F(n);
+    // what raw-fed and through-act share: a batch-statistics conv, no fused pool, no residual, float4 channels, option on
+    auto xf_conv = [&](const Op& o) {
+        return o.kind == OP_CONV && bn_train && dw_xf && !o.pool2 && o.res < 0 && o.Cout % 4 == 0;
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const Op& o = fe->ops[i];
+        OpForm& f = F[i];
+        if (o.kind == OP_CONV) {
+            // the depthwise conv that follows and reads this output, and whether it is the ONLY reader
+            const Op* d = i + 1 < n && fe->ops[i + 1].kind == OP_DWCONV && fe->ops[i + 1].in == o.out ? &fe->ops[i + 1] : nullptr;
+            const bool sole = d && no_later_reader(fe, i + 2, o.out);
+            // Two-sweep fused front: on a NO-BACKWARD batch-statistics forward (the cache pass of the LITE step: 200 frames under
+            // torch.no_grad() while the extractor is being learned, reference few_shot_recognisers.py:404-408) an MBConv block's
+            // expansion conv + depthwise conv run as the row-streaming fused front of the inference plans in two sweeps: (1) the
+            // first BatchNorm's batch statistics - from the Gram matrix of the block's input where bn_gram_supported (csrc/
+            // train_ops.hip launch_bn_stats_from_gram), else from the expansion conv as a STATISTICS SWEEP (same kernel, same
+            // tiles, nothing stored), (2) the fused front (csrc/mbconv_rows.hip, RAW form) re-expands in its LDS ring with that
+            // scale / shift, stores the RAW depthwise outputs and their column sums - the second BatchNorm then proceeds as on the
+            // unfused path. The 6x-expanded tensor (963 MB per 200 frames for block 1.0) is neither written nor read. Taped
+            // forwards keep the unfused pair: their backward reads that tensor.
+            // `train_fused_fronts`: 1 (default) = where measured faster (the 112x112 / 56x56 blocks), 0 = never, 2 = every
+            // supported shape, 3 = as 2 with the statistics sweep of the conv instead of the Gram-matrix statistics (parity tests:
+            // bit-identical first BatchNorm).
+            bool front = fronts && bn_train && no_backward && sole && !o.x_nchw && !o.pool2 && o.res < 0 && !o.use_gate &&
+                         o.KH == 1 && o.KW == 1 && o.stride == 1 && o.act == ORBIT_ACT_SILU && d->act == ORBIT_ACT_SILU &&
+                         d->Cin == o.Cout && mbconv_rows_supported(o.H, o.W, o.Cin, o.Cout, d->KH, d->stride) &&
+                         fe->bns[o.bn].conv_bias < 0;
+            if (front && fronts == 1 && o.H < 56) front = false;  // (the 28x28 blocks: statistics sweep + front measured no faster than the pair)
+            const int tiles = front ? mbconv_rows_tiles(o.H, o.W, o.Cin, o.Cout, d->KH, d->stride) : 0;
+            if (tiles <= 0 || tiles > FRONT_TILE_CAP) front = false;
+            // Raw-to-depthwise: a batch-statistics conv whose activated output is read by ONE consumer, the depthwise conv that
+            // follows (EfficientNet's expansion convs and stem): that consumer applies the conv's BatchNorm + SiLU as it loads the
+            // RAW output (DwInXf in csrc/ops.hip), so the activated 6x-expanded tensor is never written - on forwards that run no
+            // backward and on TAPED ones: the only other reader of the activation is the depthwise filter gradient, whose LDS form
+            // applies the same transform as it stages its input patch (dwconv_wgrad_lds_kernel, csrc/train_mbconv.hip; each
+            // element passes once). A first attempt with the transform inside the global-load filter-gradient kernel - every
+            // input loaded K times, SiLU per load - lost more there (1.76 -> 3.98 ms) than the forward gained
+            // (profiles/r05_lite_ab_taped_xf.txt). The activation must not be ReLU on a taped forward (its BatchNorm backward
+            // reads the mask from the activated tensor).
+            const bool raw = xf_conv(o) && sole &&
+                             (no_backward || ((o.act == ORBIT_ACT_SILU || o.act == ORBIT_ACT_NONE) &&
+                                              dwconv_wgrad_xf_supported(B, d->H, d->W, d->Cin, d->KH, d->stride, d->Ho, d->Wo)));
+            // Dual write: running-statistics BatchNorm (frozen extractor: CNAPs meta-training, FiLM fine-tuning): scale / shift
+            // are known before the conv runs, so its epilogue writes BOTH the raw output (tape: xhat and the SiLU derivative need
+            // it) and the activation - no separate activation pass over the tensor
+            if (front) f.conv = bn_gram_supported(o.Cin) && fronts != 3 ? CONV_SWEEP_GRAM : CONV_SWEEP_CONV, f.tiles = tiles;
+            else if (!bn_train && !o.pool2) f.conv = CONV_DUAL;
+            else if (raw) f.conv = CONV_RAW_TO_DW;
+        } else if (o.kind == OP_DWCONV) {
+            const int prev = (int)i - 1;  // (a conv in one of the three forms below is followed by its depthwise reader)
+            if (prev >= 0 && F[prev].conv == CONV_RAW_TO_DW) f.raw_src = prev;
+            if (prev >= 0 && (F[prev].conv == CONV_SWEEP_GRAM || F[prev].conv == CONV_SWEEP_CONV)) f.front = prev;
+            // the activation pass also produces the squeeze-excite pooling partials when an SE op consumes this tensor
+            f.pooled = i + 1 < n && fe->ops[i + 1].kind == OP_SE;
+            // the producer is a convolution + BatchNorm + SiLU right before this layer. Not raw_fed: no filter-gradient fit test
+            // and no later-reader test here (the data gradient's epilogue needs neither), but no conv bias.
+            const int src = P.in[i];
+            f.through_act = src >= 0 && src == prev && xf_conv(fe->ops[src]) && fe->bns[fe->ops[src].bn].conv_bias < 0 &&
+                            (fe->ops[src].act == ORBIT_ACT_SILU || fe->ops[src].act == ORBIT_ACT_NONE);
+        } else if (o.kind == OP_SE) {
+            f.se_dw = se_source(fe, i);
+        }
+    }
+    return F;
 }
 
 struct BwdLayout {
@@ -268,73 +322,42 @@ static BwdLayout bwd_layout(const orbit_extractor* fe, int B) {
 
 using namespace orbit;
 
-// lazily built training-side device state of a plan
-struct orbit_train_state {
-    float* d_dgrad = nullptr;  // dgrad-packed filters
-    std::vector<PackJob> jobs;  // their re-layouts, one launch for all layers (PackJob kind 4)
-    PackJob* d_jobs = nullptr;
-    std::vector<size_t> dgrad_off;
-    size_t dgrad_floats = 0;
-    bool packed = false;
-};
-
-static std::map<const orbit_extractor*, orbit_train_state>& train_states() {
-    static std::map<const orbit_extractor*, orbit_train_state> m;
-    return m;
-}
-
-namespace orbit {
-void extractor_train_invalidate(const orbit_extractor* fe) {  // parameters changed: repack on next use
-    auto it = train_states().find(fe);
-    if (it != train_states().end()) it->second.packed = false;
-}
-void extractor_train_release(const orbit_extractor* fe) {
-    auto it = train_states().find(fe);
-    if (it == train_states().end()) return;
-    (void)hipFree(it->second.d_dgrad);
-    (void)hipFree(it->second.d_jobs);
-    train_states().erase(it);
-}
-}  // namespace orbit
-
-static int ensure_dgrad_filters(orbit_extractor* fe, orbit_train_state** out, hipStream_t s) {
-    orbit_train_state& st = train_states()[fe];
-    if (st.dgrad_off.empty()) {
-        st.dgrad_off.assign(fe->ops.size(), NONE);
+// the dgrad-packed filters follow the parameters: built at the first backward, repacked whenever a load cleared dgrad_packed
+static int ensure_dgrad_filters(orbit_extractor* fe, hipStream_t s) {
+    if (fe->dgrad_off.empty()) {
+        fe->dgrad_off.assign(fe->ops.size(), NONE);
         size_t off = 0;
         for (size_t i = 0; i < fe->ops.size(); ++i) {
             const Op& o = fe->ops[i];
             if (o.kind != OP_CONV || o.x_nchw) continue;
-            st.dgrad_off[i] = off;
+            fe->dgrad_off[i] = off;
             off += conv_dgrad_packed_floats(o.Cin, o.Cout, o.KH, o.KW);
         }
-        st.dgrad_floats = std::max<size_t>(off, 4);
-        ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&st.d_dgrad), st.dgrad_floats * sizeof(float)));
+        ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fe->d_dgrad), std::max<size_t>(off, 4) * sizeof(float)));
     }
-    if (!st.packed) {
-        if (st.jobs.empty()) {
+    if (!fe->dgrad_packed) {
+        if (fe->dgrad_jobs.empty()) {
             for (size_t i = 0; i < fe->ops.size(); ++i) {
                 const Op& o = fe->ops[i];
-                if (st.dgrad_off[i] == NONE) continue;
+                if (fe->dgrad_off[i] == NONE) continue;
                 const ConvPackGeom g = conv_pack_geom(o.Cout, o.Cin, o.KH, o.KW, 0);  // the dgrad conv: Cin' = Cout, Cout' = Cin
                 PackJob j;
-                j.src = fe->d_pool + fe->params[o.weight].off, j.dst = st.d_dgrad + st.dgrad_off[i], j.kind = 4;
+                j.src = fe->d_pool + fe->params[o.weight].off, j.dst = fe->d_dgrad + fe->dgrad_off[i], j.kind = 4;
                 j.Cin = o.Cin, j.Cout = o.Cout, j.KH = o.KH, j.KW = o.KW, j.cin_pad = g.cin_pad, j.KT = g.kt;
                 j.cout_pad = g.cout_pad, j.total = (unsigned)((size_t)g.cout_pad * g.kt);
-                st.jobs.push_back(j);
+                fe->dgrad_jobs.push_back(j);
             }
         }
-        if (int rc = run_pack_jobs(st.jobs, &st.d_jobs, s)) return rc;
-        st.packed = true;
+        if (int rc = run_pack_jobs(fe->dgrad_jobs, &fe->d_dgrad_jobs, s)) return rc;
+        fe->dgrad_packed = true;
     }
-    *out = &st;
     return ORBIT_OK;
 }
 
 static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, const float* film_gamma,
                              const float* film_beta, int bn_train, float momentum, float* feats, void* tape,
                              hipStream_t s, bool no_backward = false, bool defer_stats = false);
-static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const float* frames, int B, const float* film_gamma,
+static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const float* film_gamma,
                         const float* film_beta, int bn_train, const float* dfeats, const void* tape, float* param_grads,
                         int filter_grads, float* dfilm_gamma, float* dfilm_beta, void* workspace, hipStream_t s);
 
@@ -426,116 +449,96 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
     const TapeLayout L = tape_layout(fe, B);
     char* tp = static_cast<char*>(tape);
     auto fl = [&](size_t off) { return reinterpret_cast<float*>(tp + off); };
-    float *mean = fl(L.mean), *invstd = fl(L.invstd), *scale = fl(L.scale), *shift = fl(L.shift);
     // deferred running statistics: the finalize kernels run their update with momentum 1 (the statistics replace the slot's
     // content, which is never read) on a slot of the tape instead of on the plan's running statistics;
     // orbit_extractor_apply_deferred_bn_stats applies the real update later - so this forward may overlap, on another stream,
     // with a forward that updates them
     defer_stats = defer_stats && bn_train;
     if (defer_stats) momentum = 1.0f;
-    auto run_mean = [&](const BNDesc& bn) {
-        return defer_stats ? fl(L.rstat) + bn.fold_off : fe->d_pool + fe->params[bn.mean].off;
-    };
-    auto run_var = [&](const BNDesc& bn) {
-        return defer_stats ? fl(L.rstat) + fe->fold_floats + bn.fold_off : fe->d_pool + fe->params[bn.var].off;
-    };
     const bool film = film_gamma && fe->film_size > 0;
+    auto param = [&](int k) { return fe->d_pool + fe->params[k].off; };
+    // a layer's slice of the fold arrays on the tape, and the inputs of its train-mode finalize
+    auto fold = [&](const BNDesc& bn) {
+        return BnFold{fl(L.mean) + bn.fold_off, fl(L.invstd) + bn.fold_off, fl(L.scale) + bn.fold_off, fl(L.shift) + bn.fold_off};
+    };
+    auto affine = [&](const BNDesc& bn) {
+        const bool fm = film && bn.film_off >= 0;
+        BnAffine a;
+        a.gamma = fm ? film_gamma + bn.film_off : param(bn.gamma), a.beta = fm ? film_beta + bn.film_off : param(bn.beta);
+        a.conv_bias = bn.conv_bias >= 0 ? param(bn.conv_bias) : nullptr;
+        a.running_mean = defer_stats ? fl(L.rstat) + bn.fold_off : param(bn.mean);
+        a.running_var = defer_stats ? fl(L.rstat) + fe->fold_floats + bn.fold_off : param(bn.var);
+        a.eps = bn.eps, a.momentum = momentum;
+        return a;
+    };
     if (!bn_train) {
         dim3 grid((unsigned)fe->bns.size(), 2);
         bn_fold_all_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->d_pool, film ? film_gamma : nullptr,
-                                                film ? film_beta : nullptr, scale, shift);
+                                                film ? film_beta : nullptr, fl(L.scale), fl(L.shift));
         ORBIT_LAUNCH_CHECK();
-        bn_eval_stats_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->d_pool, mean, invstd);
+        bn_eval_stats_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->d_pool, fl(L.mean), fl(L.invstd));
         ORBIT_LAUNCH_CHECK();
     }
+    const TrainForms F = train_forms(fe, B, bn_train, no_backward);
     std::map<int, const float*> cur;  // buffer id -> tensor currently held
     cur[-1] = frames;
-    int last_dw = -1;
-    bool dw_pooled = false;  // the last depthwise op's activation pass left pooling partials in L.pool
-    bool dw_in_raw = false;  // the tensor the next depthwise op reads is a RAW conv output (see ORBIT_TRAIN_NO_BACKWARD)
-    int dw_in_bn = -1, dw_in_act = ORBIT_ACT_NONE;
-    int front_conv = -1;  // the expansion conv whose statistics sweep just ran: the next depthwise op is the fused front
     for (size_t i = 0; i < fe->ops.size(); ++i) {
         const Op& o = fe->ops[i];
+        const OpForm& f = F[i];
         int rc = ORBIT_OK;
         if (o.kind == OP_CONV) {
             const BNDesc& bn = fe->bns[o.bn];
+            const BnFold bf = fold(bn);
             const float* xin = cur[o.in];
-            const bool sweep = fused_front_sweeps(fe, i, bn_train, no_backward);
+            if (f.conv == CONV_SWEEP_GRAM) {
+                rc = launch_bn_stats_from_gram(xin, B * o.H * o.W, o.Cin, param(o.weight), o.Cout, affine(bn), bf, fl(L.partial), s);
+                if (rc != ORBIT_OK) return rc;
+                cur[o.out] = nullptr;  // the fused front below re-expands in LDS
+                continue;
+            }
             ConvDesc d;
             d.x = xin, d.w_packed = fe->d_packed + o.packed_off, d.y = fl(L.y[i]);
             d.scale = d.shift = d.residual = d.gate = nullptr;
             // squeeze-excite: the projection multiplies the gate into its A operand on the fly (as the inference plan does)
-            if (o.use_gate) d.gate = cur[102];
+            if (o.use_gate) d.gate = cur[BUF_GATE];
             int stat_blocks = 0;  // train-mode BatchNorm: column sums of the raw outputs come from the conv's epilogue
             if (bn_train) d.stats = fl(L.partial), d.stats_blocks = &stat_blocks;
             d.B = B, d.H = o.H, d.W = o.W, d.Cin = o.Cin, d.Cout = o.Cout, d.KH = o.KH, d.KW = o.KW;
             d.stride = o.stride, d.pad_t = o.pad_t, d.pad_l = o.pad_l, d.Ho = o.Ho, d.Wo = o.Wo;
             d.act = ORBIT_ACT_NONE, d.pool2 = 0, d.x_nchw = o.x_nchw;
-            // running-statistics BatchNorm (frozen extractor: CNAPs meta-training, FiLM fine-tuning): scale / shift are known
-            // before the conv runs, so its epilogue writes BOTH the raw output (tape: xhat and the SiLU derivative need it)
-            // and the activation - no separate activation pass over the tensor
-            const bool dual = !bn_train && !o.pool2;
-            if (dual) {
+            if (f.conv == CONV_DUAL) {
                 d.y_raw = fl(L.y[i]), d.y = fl(L.a[i]);
-                d.scale = scale + bn.fold_off, d.shift = shift + bn.fold_off;
+                d.scale = bf.scale, d.shift = bf.shift;
                 d.residual = o.res >= 0 ? cur[o.res] : nullptr;
                 d.act = o.act;
             }
-            if (sweep && bn_train && bn_gram_supported(o.Cin) && get_option("train_fused_fronts") != 3) {
-                // sweep 1 without the conv: the first BatchNorm's batch statistics from the Gram matrix of the block's input
-                // (csrc/train_ops.hip launch_bn_stats_from_gram; option value 3 keeps the statistics sweep of the conv itself)
-                const bool fm = film && bn.film_off >= 0;
-                rc = launch_bn_stats_from_gram(xin, B * o.H * o.W, o.Cin, fe->d_pool + fe->params[o.weight].off, o.Cout, bn.eps,
-                                               momentum, fm ? film_gamma + bn.film_off : fe->d_pool + fe->params[bn.gamma].off,
-                                               fm ? film_beta + bn.film_off : fe->d_pool + fe->params[bn.beta].off,
-                                               mean + bn.fold_off, invstd + bn.fold_off, scale + bn.fold_off, shift + bn.fold_off,
-                                               run_mean(bn), run_var(bn), fl(L.partial), s);
-                if (rc != ORBIT_OK) return rc;
-                front_conv = (int)i;
-                cur[o.out] = nullptr;
-                continue;
-            }
-            if (sweep) d.y = nullptr, d.stats_only = true;  // statistics only: the fused front below re-expands in LDS
+            if (f.conv == CONV_SWEEP_CONV) d.y = nullptr, d.stats_only = true;
             rc = launch_conv(d, s);
             if (rc != ORBIT_OK) return rc;
-            if (dual) {
+            if (f.conv == CONV_DUAL) {
                 cur[o.out] = fl(L.a[i]);
                 continue;
             }
-            if (sweep && stat_blocks <= 0)
+            if (f.conv == CONV_SWEEP_CONV && stat_blocks <= 0)
                 return set_err(ORBIT_ERR_STATE, "extractor_train_forward: the statistics sweep of op %zu emitted no partials", i);
             const int M = B * o.Ho * o.Wo;
             if (bn_train) {
-                const bool fm = film && bn.film_off >= 0;
-                const float* gam = fm ? film_gamma + bn.film_off : fe->d_pool + fe->params[bn.gamma].off;
-                const float* bet = fm ? film_beta + bn.film_off : fe->d_pool + fe->params[bn.beta].off;
-                const float* cb = bn.conv_bias >= 0 ? fe->d_pool + fe->params[bn.conv_bias].off : nullptr;
                 if (stat_blocks > 0)
-                    rc = launch_bn_stats_from_partials(fl(L.partial), stat_blocks, M, o.Cout, bn.eps, momentum, gam, bet, cb,
-                                                       mean + bn.fold_off, invstd + bn.fold_off, scale + bn.fold_off,
-                                                       shift + bn.fold_off, run_mean(bn), run_var(bn), s);
+                    rc = launch_bn_stats_from_partials(fl(L.partial), stat_blocks, M, o.Cout, affine(bn), bf, s);
                 else  // (fused pooling / split-K launches do not emit them: the statistics pass of its own)
-                    rc = launch_bn_stats(d.y, M, o.Cout, bn.eps, momentum, gam, bet, cb, mean + bn.fold_off,
-                                         invstd + bn.fold_off, scale + bn.fold_off, shift + bn.fold_off,
-                                         run_mean(bn), run_var(bn), fl(L.partial), s);
+                    rc = launch_bn_stats(d.y, M, o.Cout, affine(bn), bf, fl(L.partial), s);
                 if (rc != ORBIT_OK) return rc;
             }
-            if (sweep) {
-                front_conv = (int)i;
-                cur[o.out] = nullptr;
+            if (f.conv == CONV_SWEEP_CONV) {
+                cur[o.out] = nullptr;  // the fused front below re-expands in LDS
                 continue;
             }
-            // the only consumer is the depthwise conv that follows: it applies this BatchNorm + activation as it loads the raw
-            // output (conv_feeds_dw_raw above), so the activated 6x-expanded tensor is neither written nor read back
-            dw_in_raw = conv_feeds_dw_raw(fe, i, bn_train, no_backward, B);
-            if (dw_in_raw) {
-                cur[o.out] = d.y;
-                dw_in_bn = o.bn, dw_in_act = o.act;
+            if (f.conv == CONV_RAW_TO_DW) {
+                cur[o.out] = d.y;  // the activated tensor is neither written nor read back
                 continue;
             }
-            rc = launch_scale_shift_act(d.y, scale + bn.fold_off, shift + bn.fold_off,
-                                        o.res >= 0 ? cur[o.res] : nullptr, o.act, (size_t)M, o.Cout, fl(L.a[i]), s);
+            rc = launch_scale_shift_act(d.y, bf.scale, bf.shift, o.res >= 0 ? cur[o.res] : nullptr, o.act, (size_t)M, o.Cout,
+                                        fl(L.a[i]), s);
             if (rc != ORBIT_OK) return rc;
             if (o.pool2) {
                 rc = launch_maxpool_idx(fl(L.a[i]), fl(L.p[i]), reinterpret_cast<uint8_t*>(tp + L.idx[i]), B, o.Ho, o.Wo,
@@ -546,70 +549,56 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
             }
         } else if (o.kind == OP_DWCONV) {
             const BNDesc& bn = fe->bns[o.bn];
+            const BnFold bf = fold(bn);
             float* y = fl(L.y[i]);
             // train-mode BatchNorm: the depthwise kernel itself emits the column sums / sums of squares of its raw outputs
-            const float* in_sc = dw_in_raw ? scale + fe->bns[dw_in_bn].fold_off : nullptr;
-            const float* in_sh = dw_in_raw ? shift + fe->bns[dw_in_bn].fold_off : nullptr;
             int stat_rows = B * dwconv_se_chunks(o.Ho);
-            if (front_conv >= 0) {
+            if (f.front >= 0) {
                 // sweep 2 of the fused front: expand (first BatchNorm's batch statistics from the sweep above) + depthwise in
                 // one row-streaming kernel, RAW depthwise outputs + their column sums out
-                const Op& c = fe->ops[front_conv];
-                const BNDesc& bn1 = fe->bns[c.bn];
-                const int tiles = mbconv_rows_tiles(c.H, c.W, c.Cin, c.Cout, o.KH, o.stride);
-                if (tiles <= 0 || tiles > 16) return set_err(ORBIT_ERR_STATE, "extractor_train_forward: fused front tiling");
-                rc = launch_mbconv_rows(cur[c.in], fe->d_pool + fe->params[c.weight].off, scale + bn1.fold_off,
-                                        shift + bn1.fold_off, fe->d_packed + o.packed_off, nullptr, nullptr, y, fl(L.partial), B,
-                                        c.H, c.W, c.Cin, c.Cout, o.KH, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s, 0, true);
-                stat_rows = B * tiles;
-                front_conv = -1;
+                const Op& c = fe->ops[f.front];
+                const BnFold f1 = fold(fe->bns[c.bn]);
+                rc = launch_mbconv_rows(cur[c.in], param(c.weight), f1.scale, f1.shift, fe->d_packed + o.packed_off, nullptr, nullptr,
+                                        y, fl(L.partial), B, c.H, c.W, c.Cin, c.Cout, o.KH, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo,
+                                        s, 0, true);
+                stat_rows = B * F[f.front].tiles;
             } else {
+                BnFoldC in;  // the producing conv's BatchNorm + activation, applied to its RAW output as it is loaded
+                int in_act = ORBIT_ACT_NONE;
+                if (f.raw_src >= 0) in = fold(fe->bns[fe->ops[f.raw_src].bn]), in_act = fe->ops[f.raw_src].act;
                 rc = launch_dwconv_se(cur[o.in], fe->d_packed + o.packed_off, y, nullptr, nullptr,
                                       bn_train ? fl(L.partial) : nullptr, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t, o.pad_l,
-                                      o.Ho, o.Wo, ORBIT_ACT_NONE, s, bn_train ? 1 : 0, in_sc, in_sh, dw_in_act);
+                                      o.Ho, o.Wo, ORBIT_ACT_NONE, s, bn_train ? 1 : 0, in.scale, in.shift, in_act);
             }
-            dw_in_raw = false;
             if (rc != ORBIT_OK) return rc;
             const int M = B * o.Ho * o.Wo;
             if (bn_train) {
-                const bool fm = film && bn.film_off >= 0;
-                rc = launch_bn_stats_from_partials(fl(L.partial), stat_rows, M, o.Cout, bn.eps, momentum,
-                                                   fm ? film_gamma + bn.film_off : fe->d_pool + fe->params[bn.gamma].off,
-                                                   fm ? film_beta + bn.film_off : fe->d_pool + fe->params[bn.beta].off,
-                                                   nullptr, mean + bn.fold_off, invstd + bn.fold_off, scale + bn.fold_off,
-                                                   shift + bn.fold_off, run_mean(bn), run_var(bn), s);
+                rc = launch_bn_stats_from_partials(fl(L.partial), stat_rows, M, o.Cout, affine(bn), bf, s);
                 if (rc != ORBIT_OK) return rc;
             }
-            // the activation pass also produces the squeeze-excite pooling partials when an SE op consumes this tensor
-            dw_pooled = i + 1 < fe->ops.size() && fe->ops[i + 1].kind == OP_SE;
-            if (dw_pooled)
-                rc = launch_scale_shift_act_pool(y, scale + bn.fold_off, shift + bn.fold_off, o.act, B, o.Ho * o.Wo, o.Cout,
-                                                 fl(L.a[i]), fl(L.pool), s);
+            if (f.pooled)
+                rc = launch_scale_shift_act_pool(y, bf.scale, bf.shift, o.act, B, o.Ho * o.Wo, o.Cout, fl(L.a[i]), fl(L.pool), s);
             else
-                rc = launch_scale_shift_act(y, scale + bn.fold_off, shift + bn.fold_off, nullptr, o.act, (size_t)M, o.Cout,
-                                            fl(L.a[i]), s);
+                rc = launch_scale_shift_act(y, bf.scale, bf.shift, nullptr, o.act, (size_t)M, o.Cout, fl(L.a[i]), s);
             cur[o.out] = fl(L.a[i]);
-            last_dw = (int)i;
         } else if (o.kind == OP_SE) {
             // squeeze (mean over the depthwise output) + excite MLP -> gate [B][C]
-            if (last_dw < 0) return set_err(ORBIT_ERR_STATE, "extractor_train_forward: squeeze-excite without a producer");
-            const Op& dw = fe->ops[last_dw];
-            if (dw_pooled) {
+            if (f.se_dw < 0) return set_err(ORBIT_ERR_STATE, "extractor_train_forward: squeeze-excite without a producer");
+            const Op& dw = fe->ops[f.se_dw];
+            if (F[f.se_dw].pooled) {
                 // the inference gate kernel on the partial sums the activation pass left; the pooled means it forms go on the
                 // tape (the gate MLP's backward reads them)
-                rc = launch_se_gate2(fl(L.pool), se_pool_chunks(B, dw.Ho * dw.Wo, o.Cin), dw.Ho * dw.Wo,
-                                     fe->d_pool + fe->params[o.se_w1].off, fe->d_pool + fe->params[o.se_b1].off,
-                                     fe->d_packed + o.packed_off, fe->d_pool + fe->params[o.se_b2].off, fl(L.a[i]), B, o.Cin,
-                                     o.R, s, fl(L.p[i]));
+                rc = launch_se_gate2(fl(L.pool), se_pool_chunks(B, dw.Ho * dw.Wo, o.Cin), dw.Ho * dw.Wo, param(o.se_w1),
+                                     param(o.se_b1), fe->d_packed + o.packed_off, param(o.se_b2), fl(L.a[i]), B, o.Cin, o.R, s,
+                                     fl(L.p[i]));
             } else {
-                rc = launch_colmean(fl(L.a[last_dw]), fl(L.p[i]), B, dw.Ho * dw.Wo, o.Cin, s);
+                rc = launch_colmean(fl(L.a[f.se_dw]), fl(L.p[i]), B, dw.Ho * dw.Wo, o.Cin, s);
                 if (rc != ORBIT_OK) return rc;
                 // the inference gate kernel, fed with the means as a single "partial sum" over one element
-                rc = launch_se_gate2(fl(L.p[i]), 1, 1, fe->d_pool + fe->params[o.se_w1].off,
-                                     fe->d_pool + fe->params[o.se_b1].off, fe->d_packed + o.packed_off,
-                                     fe->d_pool + fe->params[o.se_b2].off, fl(L.a[i]), B, o.Cin, o.R, s);
+                rc = launch_se_gate2(fl(L.p[i]), 1, 1, param(o.se_w1), param(o.se_b1), fe->d_packed + o.packed_off,
+                                     param(o.se_b2), fl(L.a[i]), B, o.Cin, o.R, s);
             }
-            cur[102] = fl(L.a[i]);
+            cur[BUF_GATE] = fl(L.a[i]);
         } else if (o.kind == OP_MAXPOOL) {
             rc = launch_maxpool_idx(cur[o.in], fl(L.p[i]), reinterpret_cast<uint8_t*>(tp + L.idx[i]), B, o.H, o.W, o.Cin,
                                     o.pool_k, o.stride, o.pool_pad, o.Ho, o.Wo, s);
@@ -656,22 +645,21 @@ int orbit_extractor_backward(orbit_extractor_t* fe, const float* frames, int B, 
     ORBIT_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)tape & 255) == 0,
                   "extractor_backward: tape and workspace must be 256-byte aligned");
     // the dgrad-packed filters follow the parameters: repacked OUTSIDE any captured graph whenever they changed
-    orbit_train_state* st = nullptr;
-    if (int rc = ensure_dgrad_filters(fe, &st, (hipStream_t)stream)) return rc;
+    if (int rc = ensure_dgrad_filters(fe, (hipStream_t)stream)) return rc;
     orbit_extractor::TrainGraphKey key;
     memset(&key, 0, sizeof(key));
     key.p[0] = frames, key.p[1] = film_gamma, key.p[2] = film_beta, key.p[3] = dfeats, key.p[4] = tape;
     key.p[5] = param_grads, key.p[6] = dfilm_gamma, key.p[7] = dfilm_beta, key.p[8] = workspace;
     key.v[0] = 2 /* backward */, key.v[1] = B, key.v[2] = bn_train, key.v[3] = filter_grads;
     return fe->run_train_graphed(key, (hipStream_t)stream, [&](hipStream_t s) {
-        return backward_run(fe, st, frames, B, film_gamma, film_beta, bn_train, dfeats, tape, param_grads, filter_grads,
+        return backward_run(fe, frames, B, film_gamma, film_beta, bn_train, dfeats, tape, param_grads, filter_grads,
                             dfilm_gamma, dfilm_beta, workspace, s);
     });
 }
 
 }  // extern "C"
 
-static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const float* frames, int B, const float* film_gamma,
+static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const float* film_gamma,
                         const float* film_beta, int bn_train, const float* dfeats, const void* tape, float* param_grads,
                         int filter_grads, float* dfilm_gamma, float* dfilm_beta, void* workspace, hipStream_t s) {
     const bool film = film_gamma && film_beta && fe->film_size > 0;
@@ -694,9 +682,27 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
     size_t se_scratch_used = 0;
     SeParamJobs se_jobs;
     int n_se_jobs = 0;
-    const float *mean = tf(L.mean), *invstd = tf(L.invstd), *scale = tf(L.scale), *shift = tf(L.shift);
+    auto param = [&](int k) { return fe->d_pool + fe->params[k].off; };
+    // a layer's slice of the fold arrays on the tape; the gamma its forward used (FiLM's or the plan's) with the matching places
+    // of its gradients
+    auto fold = [&](const BNDesc& bn) {
+        return BnFoldC{tf(L.mean) + bn.fold_off, tf(L.invstd) + bn.fold_off, tf(L.scale) + bn.fold_off, tf(L.shift) + bn.fold_off};
+    };
+    auto grads = [&](const BNDesc& bn) {
+        const bool fm = film && bn.film_off >= 0;
+        BnGrads p;
+        p.gamma = fm ? film_gamma + bn.film_off : param(bn.gamma);
+        if (fm) {
+            if (dfilm_gamma) p.dgamma = dfilm_gamma + bn.film_off, p.dbeta = dfilm_beta + bn.film_off;
+        } else if (param_grads) {
+            p.dgamma = param_grads + fe->params[bn.gamma].off, p.dbeta = param_grads + fe->params[bn.beta].off;
+        }
+        if (wg && bn.conv_bias >= 0) p.dbias = param_grads + fe->params[bn.conv_bias].off;
+        return p;
+    };
 
     const Producers P = producers(fe);
+    const TrainForms F = train_forms(fe, B, bn_train, false);
     const int n = (int)fe->ops.size();
     // the earliest op whose backward yields something that was asked for
     int first_needed = n;
@@ -771,14 +777,6 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
             if (g < 0) continue;
             const BNDesc& bn = fe->bns[o.bn];
             const int M = B * o.Ho * o.Wo;
-            const bool fm = film && bn.film_off >= 0;
-            const float* gamma = fm ? film_gamma + bn.film_off : fe->d_pool + fe->params[bn.gamma].off;
-            float *dgam = nullptr, *dbet = nullptr;
-            if (fm) {
-                if (dfilm_gamma) dgam = dfilm_gamma + bn.film_off, dbet = dfilm_beta + bn.film_off;
-            } else if (param_grads) {
-                dgam = param_grads + fe->params[bn.gamma].off, dbet = param_grads + fe->params[bn.beta].off;
-            }
             const int src = P.in[i];
             const bool need_dx = src >= first_needed;
             const bool need_dy = need_dx || wg;
@@ -787,32 +785,27 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
                 kdy = alloc();
                 if (kdy < 0) return set_err(ORBIT_ERR_STATE, "extractor_backward: gradient slots exhausted");
             }
+            float* dy = need_dy ? slot_ptr(kdy) : nullptr;
             if (pre_reduced[i] > 0 && gated[i].gate) {
                 float* coef = partial + bn_partial_floats((size_t)pre_reduced[i], o.Cout);
-                rc = launch_bn_backward_reduced_gated(slot_ptr(g), gated[i].gate, gated[i].dpooled, gated[i].HW, tf(L.y[i]),
-                                                      mean + bn.fold_off, invstd + bn.fold_off, scale + bn.fold_off,
-                                                      shift + bn.fold_off, o.act, gamma, bn_train, M, o.Cout,
-                                                      need_dy ? slot_ptr(kdy) : nullptr, dgam, dbet, partial, pre_reduced[i],
-                                                      coef, s);
+                rc = launch_bn_backward_reduced_gated(slot_ptr(g), gated[i].gate, gated[i].dpooled, gated[i].HW,
+                                                      BnTaped{tf(L.y[i]), fold(bn), o.act, partial}, grads(bn), bn_train, M, o.Cout,
+                                                      dy, pre_reduced[i], coef, s);
             } else if (pre_reduced[i] > 0) {
                 float* coef = partial + bn_partial_floats((size_t)pre_reduced[i], o.Cout);
-                rc = launch_bn_backward_reduced(slot_ptr(g), tf(L.y[i]), mean + bn.fold_off, invstd + bn.fold_off, gamma,
-                                                bn_train, M, o.Cout, need_dy ? slot_ptr(kdy) : nullptr, dgam, dbet, partial,
+                rc = launch_bn_backward_reduced(slot_ptr(g), tf(L.y[i]), fold(bn), grads(bn), bn_train, M, o.Cout, dy, partial,
                                                 pre_reduced[i], coef, s);
             } else {
                 float* coef = partial + (size_t)bn_reduce_blocks(M, o.Cout) * 2 * o.Cout;
-                rc = launch_bn_backward(slot_ptr(g), tf(L.a[i]), tf(L.y[i]), mean + bn.fold_off, invstd + bn.fold_off, gamma,
-                                        scale + bn.fold_off, shift + bn.fold_off, bn_train, o.act, M, o.Cout,
-                                        need_dy ? slot_ptr(kdy) : nullptr, nullptr, 0, dgam, dbet, nullptr, partial, coef, s);
+                rc = launch_bn_backward(slot_ptr(g), tf(L.a[i]), tf(L.y[i]), fold(bn), grads(bn), bn_train, o.act, M, o.Cout, dy,
+                                        nullptr, 0, partial, coef, s);
             }
             if (rc != ORBIT_OK) return rc;
             release(g), grad_slot[i] = -1;
-            // the producer is a convolution + BatchNorm + SiLU whose only reader is this layer (see the data gradient below)
-            const Op& po = fe->ops[src >= 0 ? src : 0];
-            const bool through_act = need_dx && src == i - 1 && po.kind == OP_CONV && bn_train && !po.pool2 && po.res < 0 &&
-                                     po.Cout % 4 == 0 && fe->bns[po.bn].conv_bias < 0 &&
-                                     (po.act == ORBIT_ACT_SILU || po.act == ORBIT_ACT_NONE) && get_option("train_dw_xf");
-            const bool raw_fed = src >= 0 && conv_feeds_dw_raw(fe, (size_t)src, bn_train, false, B);
+            // the producer is a convolution + BatchNorm + SiLU right before this layer (see the data gradient below), and whether
+            // the forward fed this layer that conv's RAW output (train_forms decides both)
+            const bool through_act = need_dx && F[i].through_act;
+            const bool raw_fed = F[i].raw_src >= 0;
             // ... and on the stride-2 layers and the large 3x3 maps the filter gradient rides on that data-gradient kernel
             // (DwBnBwd::wgrad_partial)
             const bool wg_fused = wg && through_act && raw_fed &&
@@ -821,10 +814,10 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
                 if (raw_fed) {
                     // the forward never wrote this layer's input: the filter gradient rebuilds it from the producing conv's raw
                     // output as it stages its patch
-                    const BNDesc& sbn = fe->bns[fe->ops[src].bn];
+                    const BnFoldC in = fold(fe->bns[fe->ops[src].bn]);
                     return launch_dwconv_wgrad(tf(L.y[src]), slot_ptr(kdy), param_grads + fe->params[o.weight].off,
                                                wgrad_scratch, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s,
-                                               scale + sbn.fold_off, shift + sbn.fold_off, fe->ops[src].act);
+                                               in.scale, in.shift, fe->ops[src].act);
                 }
                 return launch_dwconv_wgrad(out_tensor(src), slot_ptr(kdy), param_grads + fe->params[o.weight].off,
                                            wgrad_scratch, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s);
@@ -845,11 +838,10 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
                 DwBnBwd bnb;
                 const DwBnBwd* bnb_ptr = nullptr;
                 if (through_act) {
-                    const BNDesc& sbn = fe->bns[po.bn];
+                    const Op& po = fe->ops[src];
                     if (wg_fused)
                         bnb.wgrad_partial = wgrad_scratch + dwconv_bwd_fused_partial_offset(o.Cin, o.KH), bnb.wgrad_rows = &wrows;
-                    bnb.y = tf(L.y[src]), bnb.mean = mean + sbn.fold_off, bnb.invstd = invstd + sbn.fold_off;
-                    bnb.scale = scale + sbn.fold_off, bnb.shift = shift + sbn.fold_off, bnb.act = po.act;
+                    bnb.y = tf(L.y[src]), bnb.bn = fold(fe->bns[po.bn]), bnb.act = po.act;
                     bnb.partial = partial, bnb.nblk = &nblk;
                     bnb_ptr = &bnb;
                 }
@@ -876,15 +868,7 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
                 release(g), g = k;
             }
             // BatchNorm (+ReLU, + residual fan-out)
-            const bool fm = film && bn.film_off >= 0;
-            const float* gamma = fm ? film_gamma + bn.film_off : fe->d_pool + fe->params[bn.gamma].off;
-            float *dgam = nullptr, *dbet = nullptr, *dbias = nullptr;
-            if (fm) {
-                if (dfilm_gamma) dgam = dfilm_gamma + bn.film_off, dbet = dfilm_beta + bn.film_off;
-            } else if (param_grads) {
-                dgam = param_grads + fe->params[bn.gamma].off, dbet = param_grads + fe->params[bn.beta].off;
-            }
-            if (wg && bn.conv_bias >= 0) dbias = param_grads + fe->params[bn.conv_bias].off;
+            const BnGrads bp = grads(bn);
             float* dres = nullptr;
             int dres_acc = 0;
             const int rsrc = o.res >= 0 ? P.res[i] : -1;
@@ -904,18 +888,17 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
                 kdy = alloc();
                 if (kdy < 0) return set_err(ORBIT_ERR_STATE, "extractor_backward: gradient slots exhausted");
             }
+            float* dy = need_dy ? slot_ptr(kdy) : nullptr;
             if (pre_reduced[i] > 0) {
-                ORBIT_REQUIRE(!dres && !dbias && !o.pool2, "extractor_backward: pre-reduced BatchNorm with a residual or bias");
+                ORBIT_REQUIRE(!dres && !bp.dbias && !o.pool2, "extractor_backward: pre-reduced BatchNorm with a residual or bias");
                 float* coef = partial + bn_partial_floats((size_t)pre_reduced[i], o.Cout);
-                rc = launch_bn_backward_reduced(slot_ptr(g), tf(L.y[i]), mean + bn.fold_off, invstd + bn.fold_off, gamma,
-                                                bn_train, M, o.Cout, need_dy ? slot_ptr(kdy) : nullptr, dgam, dbet, partial,
+                rc = launch_bn_backward_reduced(slot_ptr(g), tf(L.y[i]), fold(bn), bp, bn_train, M, o.Cout, dy, partial,
                                                 pre_reduced[i], coef, s);
             } else {
                 // partial holds [blocks][2][C] followed by the 3*C apply coefficients
                 float* coef = partial + (size_t)bn_reduce_blocks(M, o.Cout) * 2 * o.Cout;
-                rc = launch_bn_backward(slot_ptr(g), tf(L.a[i]), tf(L.y[i]), mean + bn.fold_off, invstd + bn.fold_off, gamma,
-                                        scale + bn.fold_off, shift + bn.fold_off, bn_train, o.act, M, o.Cout,
-                                        need_dy ? slot_ptr(kdy) : nullptr, dres, dres_acc, dgam, dbet, dbias, partial, coef, s);
+                rc = launch_bn_backward(slot_ptr(g), tf(L.a[i]), tf(L.y[i]), fold(bn), bp, bn_train, o.act, M, o.Cout, dy, dres,
+                                        dres_acc, partial, coef, s);
             }
             if (rc != ORBIT_OK) return rc;
             if (!need_dy && dres) {
@@ -944,7 +927,7 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
                 float* se_scratch = se_scratch_base + se_scratch_used;  // this block's own (see se_jobs)
                 se_scratch_used += align_up(se_bwd_scratch_floats(B, o.Cin, so.R), 64);
                 SLOT_OR_FAIL(kt);
-                rc = launch_conv_dgrad(slot_ptr(kdy), st->d_dgrad + st->dgrad_off[i], nullptr, slot_ptr(kt), up, B, o.H, o.W,
+                rc = launch_conv_dgrad(slot_ptr(kdy), fe->d_dgrad + fe->dgrad_off[i], nullptr, slot_ptr(kt), up, B, o.H, o.W,
                                        o.Cin, o.Cout, o.KH, o.KW, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s);
                 if (rc != ORBIT_OK) return rc;
                 float* pg = wg ? param_grads : nullptr;
@@ -970,19 +953,15 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
                 }
                 grad_slot[src] = k;
                 if (fe->ops[src].kind == OP_DWCONV) {
-                    const BNDesc& sbn = fe->bns[fe->ops[src].bn];
-                    fuse.y = tf(L.y[src]), fuse.mean = mean + sbn.fold_off, fuse.invstd = invstd + sbn.fold_off;
-                    fuse.scale = scale + sbn.fold_off, fuse.shift = shift + sbn.fold_off, fuse.act = fe->ops[src].act;
-                    fuse.partial = partial;
+                    fuse = BnTaped{tf(L.y[src]), fold(fe->bns[fe->ops[src].bn]), fe->ops[src].act, partial};
                     fuse_ptr = &fuse;
                     pre_reduced[src] = B * se_pool_chunks(B, o.H * o.W, o.Cin);
                     if (sums_only)
                         gated[src].gate = tf(L.a[se]), gated[src].dpooled = se_bwd_dpooled(se_scratch, B, o.Cin, so.R),
                         gated[src].HW = o.H * o.W;
                 }
-                rc = launch_se_gate_backward(slot_ptr(kt), out_tensor(src), tf(L.p[se]), tf(L.a[se]),
-                                             fe->d_pool + fe->params[so.se_w1].off, fe->d_pool + fe->params[so.se_b1].off,
-                                             fe->d_pool + fe->params[so.se_w2].off, fe->d_pool + fe->params[so.se_b2].off,
+                rc = launch_se_gate_backward(slot_ptr(kt), out_tensor(src), tf(L.p[se]), tf(L.a[se]), param(so.se_w1),
+                                             param(so.se_b1), param(so.se_w2), param(so.se_b2),
                                              sums_only ? nullptr : slot_ptr(k), pg ? pg + fe->params[so.se_w1].off : nullptr,
                                              pg ? pg + fe->params[so.se_b1].off : nullptr,
                                              pg ? pg + fe->params[so.se_w2].off : nullptr,
@@ -997,7 +976,7 @@ static int backward_run(orbit_extractor_t* fe, orbit_train_state* st, const floa
                 } else {
                     acc = slot_ptr(grad_slot[src]);
                 }
-                rc = launch_conv_dgrad(slot_ptr(kdy), st->d_dgrad + st->dgrad_off[i], acc, slot_ptr(grad_slot[src]), up, B,
+                rc = launch_conv_dgrad(slot_ptr(kdy), fe->d_dgrad + fe->dgrad_off[i], acc, slot_ptr(grad_slot[src]), up, B,
                                        o.H, o.W, o.Cin, o.Cout, o.KH, o.KW, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s);
             }
             release(kdy);

@@ -355,8 +355,8 @@ __global__ __launch_bounds__(256) void dwconv_win_kernel(const float* __restrict
     DwBnbVec bv;
     const float* byb = nullptr;
     if (BNB) {
-        bv.sc = *reinterpret_cast<const v4f*>(bnb.scale + c), bv.sh = *reinterpret_cast<const v4f*>(bnb.shift + c);
-        bv.mu = *reinterpret_cast<const v4f*>(bnb.mean + c), bv.is = *reinterpret_cast<const v4f*>(bnb.invstd + c);
+        bv.sc = *reinterpret_cast<const v4f*>(bnb.bn.scale + c), bv.sh = *reinterpret_cast<const v4f*>(bnb.bn.shift + c);
+        bv.mu = *reinterpret_cast<const v4f*>(bnb.bn.mean + c), bv.is = *reinterpret_cast<const v4f*>(bnb.bn.invstd + c);
         byb = bnb.y + (size_t)b * Ho * Wo * C + c;
     }
     v4f wacc[WG ? K * K : 1];
@@ -577,8 +577,8 @@ __global__ __launch_bounds__(256) void dwconv_lds_kernel(const float* __restrict
     DwBnbVec bv;
     const float* byb = nullptr;
     if (BNB) {
-        bv.sc = *reinterpret_cast<const v4f*>(bnb.scale + c), bv.sh = *reinterpret_cast<const v4f*>(bnb.shift + c);
-        bv.mu = *reinterpret_cast<const v4f*>(bnb.mean + c), bv.is = *reinterpret_cast<const v4f*>(bnb.invstd + c);
+        bv.sc = *reinterpret_cast<const v4f*>(bnb.bn.scale + c), bv.sh = *reinterpret_cast<const v4f*>(bnb.bn.shift + c);
+        bv.mu = *reinterpret_cast<const v4f*>(bnb.bn.mean + c), bv.is = *reinterpret_cast<const v4f*>(bnb.bn.invstd + c);
         byb = bnb.y + (size_t)b * Ho * Wo * C + c;
     }
     if (rl < RL) {
@@ -856,7 +856,7 @@ static int launch_dwconv_se_impl(const float* x, const float* w_khwc, float* y, 
                                  const DwBnBwd* bnb) {
     ORBIT_REQUIRE(x && w_khwc && y, "dwconv_se: null pointer");
     if (bnb) {
-        ORBIT_REQUIRE(bnb->y && bnb->mean && bnb->invstd && bnb->scale && bnb->shift && bnb->partial && bnb->nblk,
+        ORBIT_REQUIRE(bnb->y && bnb->bn.mean && bnb->bn.invstd && bnb->bn.scale && bnb->bn.shift && bnb->partial && bnb->nblk,
                       "dwconv_se: incomplete BatchNorm-backward epilogue");
         ORBIT_REQUIRE(!stats && !in_scale && !scale && !shift && !pool_partial && stride == 1 && act == ORBIT_ACT_NONE,
                       "dwconv_se: the BatchNorm-backward epilogue belongs to the plain stride-1 data-gradient use");

@@ -25,17 +25,6 @@ static int grid_for(size_t total) {
 }
 
 // ---- squeeze-excite gate -------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gate_mul_kernel(const float* __restrict__ x, const float* __restrict__ gate,
-                                                       float* __restrict__ xg, int HW, int C4, size_t total4) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
-        const unsigned iu = (unsigned)i;  // 32-bit index arithmetic (launcher: total < 2^32)
-        const int q = (int)(iu % (unsigned)C4);
-        const size_t b = iu / ((unsigned)HW * (unsigned)C4);
-        reinterpret_cast<f32x4*>(xg)[i] = reinterpret_cast<const f32x4*>(x)[i] *
-                                          reinterpret_cast<const f32x4*>(gate)[b * C4 + q];
-    }
-}
-
 // pooled[b][c] = mean_hw x[b][hw][c] (the squeeze of squeeze-excite over the LARGE depthwise outputs: HW up to 112*112);
 // block = (frame b, group of G channel quads), R row lanes, float4 loads, fixed-order LDS combine
 __global__ __launch_bounds__(256) void colmean_kernel(const float* __restrict__ x, float* __restrict__ pooled, int HW,
@@ -437,8 +426,8 @@ __global__ __launch_bounds__(256) void dwconv_dgrad_s2_kernel(const float* __res
 #pragma unroll
     for (int t = 0; t < (WG ? K * K : 1); ++t) wacc[t] = zero;
     if (BNB && live) {
-        bsc = reinterpret_cast<const f32x4*>(bnb.scale)[q], bsh = reinterpret_cast<const f32x4*>(bnb.shift)[q];
-        bmu = reinterpret_cast<const f32x4*>(bnb.mean)[q], bis = reinterpret_cast<const f32x4*>(bnb.invstd)[q];
+        bsc = reinterpret_cast<const f32x4*>(bnb.bn.scale)[q], bsh = reinterpret_cast<const f32x4*>(bnb.bn.shift)[q];
+        bmu = reinterpret_cast<const f32x4*>(bnb.bn.mean)[q], bis = reinterpret_cast<const f32x4*>(bnb.bn.invstd)[q];
     }
     for (unsigned i = blockIdx.x * R + rl; live && i < total; i += gridDim.x * R) {
         const unsigned bw = i / (unsigned)W2, b = bw / (unsigned)H2;
@@ -636,7 +625,7 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_partial_kernel(const float* 
 // csrc/ops.hip - and the taps read LDS; a block walks `tpb` tiles with its K*K accumulators in registers and reduces once at the
 // end. Because an element is touched once on its way in, the preceding BatchNorm + SiLU can be applied THERE (XF: `x` is the RAW
 // output of the expansion conv, act(x * in_scale[c] + in_shift[c]) is staged; the zero padding stays zero): the taped forward
-// of a batch-statistics step then never writes the activated 6x-expanded tensor (conv_feeds_dw_raw, csrc/extractor_train.hip).
+// of a batch-statistics step then never writes the activated 6x-expanded tensor (CONV_RAW_TO_DW in train_forms, csrc/extractor_train.hip).
 // partial[group][tap][c]; thread = (channel quad lc of the slice, 4-column group g, row lane rl); fixed summation order.
 struct DwWgLdsParams {
     const float* x;
@@ -852,15 +841,6 @@ int launch_colmean(const float* x, float* pooled, int B, int HW, int C, hipStrea
     return ORBIT_OK;
 }
 
-int launch_gate_mul(const float* x, const float* gate, float* xg, int B, int HW, int C, hipStream_t s) {
-    ORBIT_REQUIRE(C % 4 == 0, "gate_mul: C %% 4 != 0");
-    const size_t total4 = (size_t)B * HW * (C / 4);
-    ORBIT_REQUIRE((unsigned long long)(total4) < (1ull << 32), "tensor too large for the 32-bit index arithmetic of this kernel");
-    gate_mul_kernel<<<grid_for(total4), 256, 0, s>>>(x, gate, xg, HW, C / 4, total4);
-    ORBIT_LAUNCH_CHECK();
-    return ORBIT_OK;
-}
-
 // scratch: du [B*C] | dv [B*R] | h [B*R] | dgate [B*C] | dpooled [B*C]
 size_t se_bwd_scratch_floats(int B, int C, int R) { return (size_t)B * (3 * (size_t)C + 2 * (size_t)R) + 16; }
 
@@ -918,8 +898,8 @@ int launch_se_gate_backward(const float* dxg, const float* x, const float* poole
             const int Q = C / 4;
             Gc = Q < 256 ? Q : 256, Rc = 256 / Gc, ygc = cdiv(Q, Gc);  // the column layout of the BatchNorm kernels
         }
-        gate_bwd_apply_bn_kernel<<<dim3(chunks, ygc, B), 256, 0, s>>>(dxg, gate, dp, bn->y, bn->mean, bn->invstd, bn->scale,
-                                                                      bn->shift, bn->act, HW, C, cdiv(HW, chunks), Gc, Rc, dx,
+        gate_bwd_apply_bn_kernel<<<dim3(chunks, ygc, B), 256, 0, s>>>(dxg, gate, dp, bn->y, bn->bn.mean, bn->bn.invstd, bn->bn.scale,
+                                                                      bn->bn.shift, bn->act, HW, C, cdiv(HW, chunks), Gc, Rc, dx,
                                                                       bn->partial);
         ORBIT_LAUNCH_CHECK();
         return ORBIT_OK;
@@ -1125,7 +1105,7 @@ int orbit_op_dwconv2d_dgrad_bn(const float* dy, const float* w, const float* y_r
     const size_t npart = bn_partial_floats((size_t)dwconv_dgrad_bn_blocks(B, H, W, C, stride), C);
     ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (npack + nscr + npart) * sizeof(float), s));
     int nblk = 0, wrows = 0;
-    DwBnBwd bnb{y_raw, mean, invstd, scale, shift, act, tmp + npack + nscr, &nblk};
+    DwBnBwd bnb{{y_raw, {mean, invstd, scale, shift}, act, tmp + npack + nscr}, &nblk};
     if (dw) bnb.wgrad_partial = tmp + npack + dwconv_bwd_fused_partial_offset(C, K), bnb.wgrad_rows = &wrows;
     int rc = dwconv_pack_weights(w, tmp, C, K, s);
     if (rc == ORBIT_OK) rc = launch_dwconv_dgrad(dy, tmp, g, B, H, W, C, K, stride, pad_top, pad_left, Ho, Wo, s, tmp + npack, &bnb);

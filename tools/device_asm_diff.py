@@ -55,7 +55,8 @@ def functions(lines):
             if m and m.group(1) in out:
                 out[m.group(1)].append(line)
         if cur is not None:
-            cur.append(re.sub(r"\b(BB|LBB|Lfunc_begin|Lfunc_end)\d+", r"\1", line))
+            # (the padding before a label's `;` comment depends on how many digits <n> had: dropped with it)
+            cur.append(re.sub(r"\s+;", " ;", re.sub(r"\b(BB|LBB|Lfunc_begin|Lfunc_end)\d+", r"\1", line)))
             if "; -- End function" in line or ".end_amdhsa_kernel" in line:
                 cur = None
     return out
