@@ -218,8 +218,9 @@ int orbit_extractor_forward(orbit_extractor_t* fe, const float* frames, int B,
  * `vit_base_patch32_224_in21k` ("vit_b_32") and `vit_base_patch32_224_clip_laion2b` ("vit_b_32_clip") with num_classes=0;
  * the feature is LN_final(tokens)[:, 0] (timm forward_head, global_pool='token'). Same semantics as the orbit_extractor_*
  * family (orbit_extractor_create rejects these names). H = W = 224 only (reference utils/args.py: --frame_size 224 for
- * these backbones; the position table is fixed). Creation and enumeration do not touch the device. Inference only: the
- * reference's LITE / fine-tuning backward through a ViT is not provided. */
+ * these backbones; the position table is fixed). Creation and enumeration do not touch the device. Inference only by default:
+ * orbit_vit_train_forward / orbit_vit_backward below give the gradients of the FiLM vectors of the FROZEN network (the reference's
+ * --adapt_features recipes); weight gradients (--learn_extractor) are not provided. */
 int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out);
 void orbit_vit_destroy(orbit_vit_t* v);
 /* timm state_dict keys in timm's order: cls_token, pos_embed, patch_embed.proj.{weight,bias (not CLIP)}, norm_pre.* (CLIP),
@@ -247,6 +248,23 @@ double orbit_vit_macs_per_frame(const orbit_vit_t* v);
  * film_gamma / film_beta: NULL, or the LayerNorm weight / bias of every FiLM slot concatenated in slot order. */
 int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
                       float* feats, void* workspace, size_t workspace_bytes, orbit_stream_t stream);
+/* Gradients of the FiLM vectors (LayerNorm gamma / beta of the 25 slots) through the frozen network, fp32, deterministic.
+ * orbit_vit_train_forward = orbit_vit_forward (same kernels, same order, bitwise the same feats; workspace of
+ * orbit_vit_workspace_bytes) that also fills the caller-owned tape: per block the input stream, qkv, the post-attention stream
+ * and the fc1 pre-activation (9 * 50 B * D floats), then the stream entering the final norm (50 B * D floats); LayerNorm
+ * statistics are recomputed. orbit_vit_backward: dfeats [B][D] -> dgamma, dbeta [25 D] in slot order (overwritten), with the
+ * film vectors the forward was given (NULL = the plan's own LayerNorm parameters). The first backward after a parameter upload
+ * transposes the qkv / proj / fc1 / fc2 weights into a plan-owned buffer (144 D^2 floats) on `stream`; inference never
+ * allocates it. One stream per plan: a backward issued on another stream is not ordered behind those transposes (nor behind
+ * the parameter upload), so the caller orders the streams itself. Tape and workspaces 256-byte aligned; byte counts are 0 for B outside 1..8192. */
+size_t orbit_vit_tape_bytes(const orbit_vit_t* v, int B);
+size_t orbit_vit_backward_workspace_bytes(const orbit_vit_t* v, int B);
+int orbit_vit_train_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
+                            float* feats, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
+                            orbit_stream_t stream);
+int orbit_vit_backward(orbit_vit_t* v, int B, const float* film_gamma, const float* film_beta, const float* dfeats,
+                       const void* tape, size_t tape_bytes, float* dgamma, float* dbeta, void* workspace,
+                       size_t workspace_bytes, orbit_stream_t stream);
 
 /* ---- FiLM parameter generator ------------------------------------------------------------------ */
 /* n_gen generators (sorted FiLM-name order). Generator i: Linear(z_dim,hid) -> LayerNorm(hid) -> ReLU ->
@@ -325,6 +343,22 @@ int orbit_op_vit_layernorm(const float* x, size_t x_stride, float* y, size_t y_s
                            const float* beta, float eps, orbit_stream_t stream);
 /* qkv [B][50][3][heads][64] -> out [B][50][heads][64] = softmax(q k^T / 8) v per (frame, head); D = 64 heads, 384 or 768. */
 int orbit_op_vit_attention(const float* qkv, float* out, int B, int D, int heads, orbit_stream_t stream);
+/* The backward kernels of orbit_vit_backward one by one.
+ * dx [M][K] = dy [M][N] . w [N][K] (w in the torch Linear layout; wt_scratch [K][N] receives its transpose, which the GEMM of
+ * orbit_op_vit_linear then reads), optionally times GELU'(u) (u [M][K], the erf form: Phi(u) + u phi(u)) or plus residual [M][K]
+ * (may alias dx) - not both. K % 128 == 0, N % 32 == 0; dy, w and wt_scratch 16-byte aligned; tile_rows as above. */
+int orbit_op_vit_linear_dgrad(const float* dy, const float* w, float* wt_scratch, const float* u, const float* residual,
+                              float* dx, int M, int N, int K, int tile_rows, orbit_stream_t stream);
+/* LayerNorm backward over rows of D (384 or 768) values at x + r * x_stride, dy + r * dy_stride: dgamma / dbeta [D] summed over
+ * ALL rows (overwritten) and, unless dx is NULL, dx + r * dx_stride = the data gradient (+ dres + r * dx_stride when dres is
+ * given, contiguous rows only; it may alias dx). With dx_stride > D (the final norm: only token 0 of a frame's 50 carries a
+ * gradient) the rows * dx_stride floats at dx are zeroed before the rows are written. partial: scratch of at least ceil(rows / 64) * 2 * D floats. */
+int orbit_op_vit_layernorm_bwd(const float* x, size_t x_stride, const float* dy, size_t dy_stride, const float* gamma, float eps,
+                               const float* dres, float* dx, size_t dx_stride, int rows, int D, float* dgamma, float* dbeta,
+                               float* partial, size_t partial_floats, orbit_stream_t stream);
+/* qkv [B][50][3][heads][64], dout [B][50][heads][64] -> dqkv in qkv's layout (gradients of q, k and v). */
+int orbit_op_vit_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int D, int heads,
+                               orbit_stream_t stream);
 
 /* fused MBConv front half (EfficientNet InvertedResidual, Cin <= 40): y = silu(bn2(dw_KxK(silu(bn1(x . w1^T))))) with the
  * expanded tensor kept in LDS. x NHWC [B][H][W][Cin]; w1 torch [mid][Cin][1][1]; wdw torch [mid][1][K][K];

@@ -63,6 +63,10 @@ _SIGNATURES = {
     "orbit_vit_workspace_bytes": (c_size_t, [P, c_int]),
     "orbit_vit_macs_per_frame": (c_double, [P]),
     "orbit_vit_forward": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P]),
+    "orbit_vit_tape_bytes": (c_size_t, [P, c_int]),
+    "orbit_vit_backward_workspace_bytes": (c_size_t, [P, c_int]),
+    "orbit_vit_train_forward": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P, c_size_t, P]),
+    "orbit_vit_backward": (c_int, [P, c_int, P, P, P, P, c_size_t, P, P, P, c_size_t, P]),
     "orbit_filmgen_create": (c_int, [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                      POINTER(c_void_p)]),
     "orbit_filmgen_destroy": (None, [P]),
@@ -82,6 +86,10 @@ _SIGNATURES = {
     "orbit_op_vit_patch_embed": (c_int, [P] * 6 + [c_int] * 3 + [P]),
     "orbit_op_vit_layernorm": (c_int, [P, c_size_t, P, c_size_t, c_int, c_int, P, P, c_float, P]),
     "orbit_op_vit_attention": (c_int, [P, P, c_int, c_int, c_int, P]),
+    "orbit_op_vit_linear_dgrad": (c_int, [P] * 6 + [c_int] * 4 + [P]),
+    "orbit_op_vit_layernorm_bwd": (c_int, [P, c_size_t, P, c_size_t, P, c_float, P, P, c_size_t, c_int, c_int, P, P, P,
+                                           c_size_t, P]),
+    "orbit_op_vit_attention_bwd": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "orbit_op_mbconv_front": (c_int, [P] * 9 + [c_int] * 11 + [P]),
     "orbit_op_mbconv_front_partials": (c_int, [c_int] * 6),
     "orbit_op_stem_dw_front_partials": (c_int, [c_int] * 3),

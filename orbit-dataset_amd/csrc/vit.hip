@@ -1,5 +1,7 @@
 // Vision-transformer feature extractors (timm 0.6.12 `vit_small_patch32_224_in21k`, `vit_base_patch32_224_in21k`,
-// `vit_base_patch32_224_clip_laion2b`, built with num_classes=0: reference model/feature_extractors.py:49-63), inference only.
+// `vit_base_patch32_224_clip_laion2b`, built with num_classes=0: reference model/feature_extractors.py:49-63), inference only by
+// default; orbit_vit_train_forward / orbit_vit_backward give the gradients of the FiLM vectors (LayerNorm gamma / beta) of the
+// frozen network (second half of this file).
 //
 // One forward, fp32 throughout (reference: timm VisionTransformer.forward_features + forward_head with global_pool='token'):
 //   tokens[b][0]   = cls_token + pos_embed[0]
@@ -43,7 +45,8 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 // ---- token GEMM ------------------------------------------------------------------------------------------------------
 constexpr int G_BN = 128, G_BK = 32, G_THREADS = 256;
-enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_PATCH = 3 };
+// EPI_GELU_TAPE: EPI_GELU that also stores the pre-activation (aux); EPI_DGELU: times GELU'(u), u read through `residual`
+enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_PATCH = 3, EPI_GELU_TAPE = 4, EPI_DGELU = 5 };
 
 struct GemmArgs {
     const float* x;         // [M][K] token rows, or the NCHW frames (EPI_PATCH)
@@ -53,9 +56,14 @@ struct GemmArgs {
     const float* pos;       // pos_embed [50][N] (EPI_PATCH)
     float* y;
     int M, N, K;
+    float* aux = nullptr;   // [M][N] pre-activation out (EPI_GELU_TAPE)
 };
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
+// d/du of u Phi(u) = Phi(u) + u phi(u); Phi through erfc, which keeps its relative accuracy in the negative tail
+__device__ __forceinline__ float gelu_erf_grad(float u) {
+    return 0.5f * erfcf(-u * 0.70710678118654752f) + u * 0.39894228040143268f * expf(-0.5f * u * u);
+}
 
 // address of the 4 consecutive k of A row m (clamped into [0, M)) starting at k
 template <int EPI>
@@ -69,7 +77,10 @@ __device__ __forceinline__ const float* a_row_ptr(const GemmArgs& a, int m, int 
     return a.x + (size_t)m * a.K + k;
 }
 
-template <int BM, int EPI>
+// BLOCKED (the data-gradient GEMMs): the k-ordered chain is cut every 256 k into a second accumulator set, so the rounding error
+// grows with sqrt(256) + K / 256 instead of sqrt(K) - the accuracy of a cache-blocked CPU sgemm, which the gradient tests take
+// as their yardstick. The forward keeps the single chain (its bit-for-bit promises are pinned to it).
+template <int BM, int EPI, bool BLOCKED = false>
 __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
     constexpr int TI = BM / 64;          // 32-row MFMA tiles per wave (waves are 2 x 2 over the block tile)
     constexpr int AR = BM / 32;          // float4 loads of A per thread per K step
@@ -101,6 +112,15 @@ __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    floatx16 tot[BLOCKED ? TI : 1][2];
+    if (BLOCKED) {
+#pragma unroll
+        for (int i = 0; i < TI; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
+    }
 
     float4 ra[AR], rb[BR];
     auto load = [&](int k0) {
@@ -150,6 +170,14 @@ __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
         }
+        if (BLOCKED && ((kt & 7) == 7 || kt + 1 == nk)) {
+#pragma unroll
+            for (int i = 0; i < TI; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) tot[i][j][r] += acc[i][j][r], acc[i][j][r] = 0.f;
+        }
     }
 
     // epilogue: C[row][col], col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
@@ -163,14 +191,16 @@ __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
             for (int r = 0; r < 16; ++r) {
                 const int row = m0 + wm * (BM / 2) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (row >= a.M) continue;
-                float v = acc[i][j][r] + bv;
+                float v = (BLOCKED ? tot[i][j][r] : acc[i][j][r]) + bv;
                 if (EPI == EPI_PATCH) {
                     const int b = row / VIT_P, p = row - b * VIT_P;
                     v += a.pos[(size_t)(1 + p) * a.N + col];
                     a.y[((size_t)b * VIT_N + 1 + p) * a.N + col] = v;
                     continue;
                 }
-                if (EPI == EPI_GELU) v = gelu_erf(v);
+                if (EPI == EPI_GELU_TAPE) a.aux[(size_t)row * a.N + col] = v;
+                if (EPI == EPI_GELU || EPI == EPI_GELU_TAPE) v = gelu_erf(v);
+                if (EPI == EPI_DGELU) v *= gelu_erf_grad(a.residual[(size_t)row * a.N + col]);
                 if (EPI == EPI_RESIDUAL) v += a.residual[(size_t)row * a.N + col];
                 a.y[(size_t)row * a.N + col] = v;
             }
@@ -178,7 +208,7 @@ __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
 }
 
 // tile_rows: 0 = the rule below, 64 / 128 = that instantiation (the single-operator entry points; the forward passes 0)
-template <int EPI>
+template <int EPI, bool BLOCKED = false>
 int launch_gemm(const GemmArgs& a, const char* what, hipStream_t s, int tile_rows = 0) {
     if (a.N % G_BN || a.K % G_BK || a.M <= 0) return set_err(ORBIT_ERR_ARG, "vit gemm: unsupported shape M=%d N=%d K=%d", a.M, a.N, a.K);
     if (tile_rows != 0 && tile_rows != 64 && tile_rows != 128)
@@ -187,14 +217,14 @@ int launch_gemm(const GemmArgs& a, const char* what, hipStream_t s, int tile_row
     const int n_tiles = a.N / G_BN;
     const bool tall = tile_rows ? tile_rows == 128 : (long)cdiv(a.M, 128) * n_tiles >= 512;
     const double flops = 2.0 * a.M * a.N * a.K;
-    const double bytes = 4.0 * ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N * (EPI == EPI_RESIDUAL ? 2 : 1));
+    const double bytes = 4.0 * ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N * (EPI == EPI_RESIDUAL || EPI == EPI_GELU_TAPE || EPI == EPI_DGELU ? 2 : 1));
     char name[48];
     snprintf(name, sizeof(name), "vit_%s<%d>", what, tall ? 128 : 64);
     const int pi = prof_start(name, flops, bytes, s);
     if (tall)
-        vit_gemm_kernel<128, EPI><<<dim3(n_tiles, cdiv(a.M, 128)), G_THREADS, 0, s>>>(a);
+        vit_gemm_kernel<128, EPI, BLOCKED><<<dim3(n_tiles, cdiv(a.M, 128)), G_THREADS, 0, s>>>(a);
     else
-        vit_gemm_kernel<64, EPI><<<dim3(n_tiles, cdiv(a.M, 64)), G_THREADS, 0, s>>>(a);
+        vit_gemm_kernel<64, EPI, BLOCKED><<<dim3(n_tiles, cdiv(a.M, 64)), G_THREADS, 0, s>>>(a);
     prof_stop(pi, s);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
@@ -294,6 +324,203 @@ __global__ __launch_bounds__(256) void vit_attention_kernel(const float* __restr
     }
 }
 
+// ---- backward kernels (frozen network: data gradients and the per-slot LayerNorm dgamma / dbeta) -----------------------
+// in [R][C] -> out [C][R] with the library's transpose (csrc/ops.hip): the K-contiguous copy of a Linear weight that the
+// data-gradient GEMM reads. Runs once per parameter upload, not per step.
+int vit_transpose(const float* in, float* out, int R, int C, hipStream_t s) {
+    const int pi = prof_start("vit_transpose", 0.0, 8.0 * R * C, s);
+    const int rc = launch_transpose(in, out, R, C, s);
+    prof_stop(pi, s);
+    return rc;
+}
+
+// qkv [B*50][3D], dout [B*50][D] (gradient of the attention output) -> dqkv [B*50][3D] (the [B][50][3][heads][64] layout of
+// qkv). One workgroup per (frame, head) as the forward; S and P are recomputed by the forward's own code, then
+//   dV = P^T dO,  dP = dO V^T,  dS = P o (dP - rowsum(dP o P)) (in place over P),  dQ = dS K / 8,  dK = dS^T Q / 8.
+// LDS: Q, dO 50 x 64, K, V 50 x 65, P 50 x 52 floats = 62 016 bytes with alignment: two workgroups (8 waves) per CU of 160 KB - the same
+// two-per-SIMD occupancy the 256-thread forward reaches with its 46 KB; the kernel is LDS-latency bound either way.
+__global__ __launch_bounds__(256) void vit_attention_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
+                                                                float* __restrict__ dqkv, int D, int heads) {
+    constexpr int LDK = VIT_HD + 1, LDS_ = 52;
+    __shared__ float q[VIT_N * VIT_HD], k[VIT_N * LDK], v[VIT_N * LDK], go[VIT_N * VIT_HD], sc[VIT_N * LDS_];
+    const int bh = blockIdx.x, b = bh / heads, h = bh - b * heads;
+    const int tid = threadIdx.x;
+    const float* base = qkv + (size_t)b * VIT_N * 3 * D + h * VIT_HD;
+    float* dbase = dqkv + (size_t)b * VIT_N * 3 * D + h * VIT_HD;
+    for (int i = tid; i < VIT_N * VIT_HD; i += 256) {
+        const int t = i >> 6, d = i & 63;
+        const float* r = base + (size_t)t * 3 * D + d;
+        q[i] = r[0];
+        k[t * LDK + d] = r[D];
+        v[t * LDK + d] = r[2 * D];
+        go[i] = dout[((size_t)b * VIT_N + t) * D + h * VIT_HD + d];
+    }
+    __syncthreads();
+    for (int i = tid; i < VIT_N * VIT_N; i += 256) {
+        const int r = i / VIT_N, c = i - r * VIT_N;
+        float acc = 0.f;
+#pragma unroll 16
+        for (int d = 0; d < VIT_HD; ++d) acc = fmaf(q[r * VIT_HD + d], k[c * LDK + d], acc);
+        sc[r * LDS_ + c] = acc * 0.125f;
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int r = wave; r < VIT_N; r += 4) {
+        const float val = lane < VIT_N ? sc[r * LDS_ + lane] : -INFINITY;
+        const float m = wave_max_xor(val);
+        const float e = lane < VIT_N ? expf(val - m) : 0.f;
+        const float sum = wave_sum_xor(e);
+        if (lane < VIT_N) sc[r * LDS_ + lane] = e / sum;
+    }
+    __syncthreads();
+    for (int i = tid; i < VIT_N * VIT_HD; i += 256) {  // dV[c][d] = sum_r P[r][c] dO[r][d]
+        const int c = i >> 6, d = i & 63;
+        float acc = 0.f;
+#pragma unroll 10
+        for (int r = 0; r < VIT_N; ++r) acc = fmaf(sc[r * LDS_ + c], go[r * VIT_HD + d], acc);
+        dbase[(size_t)c * 3 * D + 2 * D + d] = acc;
+    }
+    __syncthreads();
+    for (int r = wave; r < VIT_N; r += 4) {  // row r of dS over row r of P; lane = key
+        float dp = 0.f;
+        if (lane < VIT_N) {
+#pragma unroll 16
+            for (int d = 0; d < VIT_HD; ++d) dp = fmaf(go[r * VIT_HD + d], v[lane * LDK + d], dp);
+        }
+        const float p = lane < VIT_N ? sc[r * LDS_ + lane] : 0.f;
+        const float t = wave_sum_xor(dp * p);
+        if (lane < VIT_N) sc[r * LDS_ + lane] = p * (dp - t);
+    }
+    __syncthreads();
+    for (int i = tid; i < VIT_N * VIT_HD; i += 256) {
+        const int r = i >> 6, d = i & 63;  // (r is the query row of dQ and the key row of dK)
+        float aq = 0.f, ak = 0.f;
+#pragma unroll 10
+        for (int c = 0; c < VIT_N; ++c) {
+            aq = fmaf(sc[r * LDS_ + c], k[c * LDK + d], aq);
+            ak = fmaf(sc[c * LDS_ + r], q[c * VIT_HD + d], ak);
+        }
+        dbase[(size_t)r * 3 * D + d] = aq * 0.125f;
+        dbase[(size_t)r * 3 * D + D + d] = ak * 0.125f;
+    }
+}
+
+int launch_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int D, int heads, hipStream_t s) {
+    const int pi = prof_start("vit_attention_bwd", 10.0 * B * heads * VIT_N * VIT_N * VIT_HD, 4.0 * 7 * (double)B * VIT_N * D, s);
+    vit_attention_bwd_kernel<<<B * heads, 256, 0, s>>>(qkv, dout, dqkv, D, heads);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
+// LayerNorm backward, one wave per row with the row in registers, 64 rows per block (16 per wave, interleaved). mean / rstd
+// are recomputed by the forward's own code (mean by division, see vit_layernorm_kernel).
+//   xhat = (x - mean) rstd,  g = dy o gamma,  dx = rstd (g - mean(g) - xhat mean(g o xhat))  [+ dres]
+// dx == nullptr: no data gradient (block 0's norm1). dres may alias dx. With dx_stride > D (the final norm: token 0 of every
+// frame carries a gradient, the other 49 tokens none) only the D floats of each row are written: the caller zeroes the stream.
+// Per-channel sums of dy and dy o xhat over the block's rows go to partial[block][2][D] (waves added in wave order);
+// vit_layernorm_bwd_finalize_kernel adds the blocks in block order.
+constexpr int LNB_ROWS = 64;
+template <int NPL>
+__global__ __launch_bounds__(256) void vit_layernorm_bwd_kernel(const float* x, size_t x_stride, const float* dy,
+                                                                size_t dy_stride, const float* __restrict__ g, float eps,
+                                                                const float* dres, float* dx, size_t dx_stride, int rows,
+                                                                float* __restrict__ partial) {
+    constexpr int D = NPL * 64;
+    __shared__ float red[3][2][D];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float gam[NPL], sb[NPL], sg[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) gam[i] = g[lane + 64 * i], sb[i] = 0.f, sg[i] = 0.f;
+    for (int j = 0; j < LNB_ROWS / 4; ++j) {
+        const int row = blockIdx.x * LNB_ROWS + 4 * j + wave;
+        if (row >= rows) break;  // (wave-uniform)
+        const float* xr = x + (size_t)row * x_stride;
+        const float* dyr = dy + (size_t)row * dy_stride;
+        float v[NPL], d[NPL];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) v[i] = xr[lane + 64 * i], d[i] = dyr[lane + 64 * i], s += v[i];
+        const float mean = wave_sum_xor(s) / D;
+        float qq = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) v[i] -= mean, qq += v[i] * v[i];
+        const float rstd = 1.f / sqrtf(wave_sum_xor(qq) * (1.f / D) + eps);
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+            v[i] *= rstd;  // xhat
+            sb[i] += d[i];
+            sg[i] += d[i] * v[i];
+            d[i] *= gam[i];  // g
+            s1 += d[i];
+            s2 += d[i] * v[i];
+        }
+        if (!dx) continue;
+        const float m1 = wave_sum_xor(s1) / D, m2 = wave_sum_xor(s2) / D;
+        float* dxr = dx + (size_t)row * dx_stride;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+            float o = rstd * (d[i] - m1 - v[i] * m2);
+            if (dres) o += dres[(size_t)row * dx_stride + lane + 64 * i];
+            dxr[lane + 64 * i] = o;
+        }
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) red[wave - 1][0][lane + 64 * i] = sb[i], red[wave - 1][1][lane + 64 * i] = sg[i];
+    }
+    __syncthreads();
+    if (wave == 0) {
+        float* pr = partial + (size_t)blockIdx.x * 2 * D;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+            const int c = lane + 64 * i;
+            pr[c] = ((sb[i] + red[0][0][c]) + red[1][0][c]) + red[2][0][c];
+            pr[D + c] = ((sg[i] + red[0][1][c]) + red[1][1][c]) + red[2][1][c];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void vit_layernorm_bwd_finalize_kernel(const float* __restrict__ partial, int nblocks, int D,
+                                                                         float* __restrict__ dbeta, float* __restrict__ dgamma) {
+    const int i = blockIdx.x * 256 + threadIdx.x;  // [2][D]: dbeta then dgamma
+    if (i >= 2 * D) return;
+    float acc = 0.f;
+    for (int b = 0; b < nblocks; ++b) acc += partial[(size_t)b * 2 * D + i];
+    if (i < D) dbeta[i] = acc;
+    else dgamma[i - D] = acc;
+}
+
+// zeroes of a gradient stream that the final norm's backward then writes token 0 of every frame into
+int zero_gradient_stream(float* dx, size_t floats, hipStream_t s) {
+    const int pi = prof_start("vit_grad_stream_zero", 0.0, 4.0 * floats, s);
+    const hipError_t e = hipMemsetAsync(dx, 0, floats * sizeof(float), s);
+    prof_stop(pi, s);
+    ORBIT_HIP_CHECK(e);
+    return ORBIT_OK;
+}
+
+size_t layernorm_bwd_partial_floats(int rows, int D) { return (size_t)cdiv(rows, LNB_ROWS) * 2 * D; }
+
+int launch_layernorm_bwd(const float* x, size_t xs, const float* dy, size_t dys, const float* g, float eps, const float* dres,
+                         float* dx, size_t dxs, int rows, int D, float* partial, float* dgamma, float* dbeta, hipStream_t s) {
+    if (D != 384 && D != 768) return set_err(ORBIT_ERR_ARG, "vit layernorm backward: unsupported width %d", D);
+    const int nblocks = cdiv(rows, LNB_ROWS);
+    int pi = prof_start("vit_layernorm_bwd", 16.0 * rows * D, 4.0 * (dx ? 3 : 2) * rows * D, s);
+    if (D == 384)
+        vit_layernorm_bwd_kernel<6><<<nblocks, 256, 0, s>>>(x, xs, dy, dys, g, eps, dres, dx, dxs, rows, partial);
+    else
+        vit_layernorm_bwd_kernel<12><<<nblocks, 256, 0, s>>>(x, xs, dy, dys, g, eps, dres, dx, dxs, rows, partial);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    pi = prof_start("vit_layernorm_bwd_finalize", 2.0 * nblocks * D, 8.0 * nblocks * D, s);
+    vit_layernorm_bwd_finalize_kernel<<<cdiv(2 * D, 256), 256, 0, s>>>(partial, nblocks, D, dbeta, dgamma);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
 }  // namespace
 
 // ---- plan ------------------------------------------------------------------------------------------------------------
@@ -317,6 +544,10 @@ struct orbit_vit {
     std::vector<const float*> h_src;
     bool finalized = false;
     double macs = 0;
+    // K-contiguous transposed copies of the qkv / proj / fc1 / fc2 weights (12 D^2 floats per block) for the data-gradient
+    // GEMMs: made by the first orbit_vit_backward after a parameter upload, never by inference
+    float* d_wt = nullptr;
+    bool wt_valid = false;
 
     int add(const std::string& key, size_t numel) {
         index[key] = (int)params.size();
@@ -343,6 +574,33 @@ VitWs vit_ws(const orbit_vit* v, int B) {
     L.h = align_up(M * v->D * sizeof(float), 256);
     L.big = L.h + align_up(M * v->D * sizeof(float), 256);
     L.total = L.big + align_up(M * v->mlp * sizeof(float), 256);
+    return L;
+}
+
+// tape of a taped forward: per block the input x [M][D], qkv [M][3D], the post-attention stream x_mid [M][D] and the fc1
+// pre-activation u [M][4D] (9 M D floats), then the stream entering the final norm [M][D]. LayerNorm statistics are recomputed.
+struct VitTape {
+    size_t x, qkv, mid, u, block, last, total;  // byte offsets inside a block, block stride, the final stream, size
+};
+VitTape vit_tape(const orbit_vit* v, int B) {
+    const size_t md = align_up((size_t)B * VIT_N * v->D * sizeof(float), 256);
+    VitTape T;
+    T.x = 0, T.qkv = md, T.mid = 4 * md, T.u = 5 * md, T.block = 9 * md;
+    T.last = VIT_DEPTH * T.block;
+    T.total = T.last + md;
+    return T;
+}
+struct VitBwdWs {
+    size_t dx, h, big, partial, total;
+};
+VitBwdWs vit_bwd_ws(const orbit_vit* v, int B) {
+    const size_t M = (size_t)B * VIT_N;
+    VitBwdWs L;
+    L.dx = 0;
+    L.h = align_up(M * v->D * sizeof(float), 256);
+    L.big = L.h + align_up(M * v->D * sizeof(float), 256);
+    L.partial = L.big + align_up(M * v->mlp * sizeof(float), 256);
+    L.total = L.partial + align_up(layernorm_bwd_partial_floats((int)M, v->D) * sizeof(float), 256);
     return L;
 }
 
@@ -402,6 +660,7 @@ void orbit_vit_destroy(orbit_vit_t* v) {
     (void)hipFree(v->d_pool);
     (void)hipFree(v->d_src);
     (void)hipFree(v->d_meta);
+    (void)hipFree(v->d_wt);
     delete v;
 }
 
@@ -422,7 +681,7 @@ int orbit_vit_load(orbit_vit_t* v, const char* key, const float* data, size_t nu
     if (int rc = v->ensure_device()) return rc;
     ORBIT_HIP_CHECK(hipMemcpy(v->d_pool + p.off, data, numel * sizeof(float), hipMemcpyDefault));
     p.loaded = true;
-    v->finalized = false;
+    v->finalized = false, v->wt_valid = false;
     return ORBIT_OK;
 }
 
@@ -436,7 +695,7 @@ int orbit_vit_load_async(orbit_vit_t* v, const char* key, const float* device_da
     ORBIT_HIP_CHECK(hipMemcpyAsync(v->d_pool + p.off, device_data, numel * sizeof(float), hipMemcpyDeviceToDevice,
                                    (hipStream_t)stream));
     p.loaded = true;
-    v->finalized = false;
+    v->finalized = false, v->wt_valid = false;
     return ORBIT_OK;
 }
 
@@ -463,7 +722,7 @@ int orbit_vit_load_all_async(orbit_vit_t* v, const float* const* device_ptrs, in
     vit_gather_params_kernel<<<dim3(32, n), 256, 0, s>>>(v->d_src, v->d_meta, v->d_pool);
     ORBIT_LAUNCH_CHECK();
     for (auto& p : v->params) p.loaded = true;
-    v->finalized = false;
+    v->finalized = false, v->wt_valid = false;
     return ORBIT_OK;
 }
 
@@ -490,21 +749,21 @@ size_t orbit_vit_workspace_bytes(const orbit_vit_t* v, int B) {
 }
 double orbit_vit_macs_per_frame(const orbit_vit_t* v) { return v ? v->macs : 0.0; }
 
-int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
-                      float* feats, void* workspace, size_t workspace_bytes, orbit_stream_t stream) {
-    ORBIT_REQUIRE(v && frames && feats && workspace, "vit_forward: null pointer");
-    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "vit_forward: batch of %d frames (1..%d)", B, VIT_MAX_B);
-    if (!v->finalized) return set_err(ORBIT_ERR_STATE, "vit_forward: call orbit_vit_finalize first");
-    ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr),
-                  "vit_forward: film_gamma and film_beta must be given together");
+}  // extern "C"
+
+namespace {
+
+// the forward. tape == nullptr: inference, the stream is updated in place inside the workspace. With a tape the same kernels in
+// the same order write what the backward reads straight into it (each residual GEMM reads one tape slot and writes the next),
+// and fc1 stores its pre-activation beside GELU(u) (EPI_GELU_TAPE): the features are bitwise those of the inference forward.
+int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta, float* feats,
+                     void* workspace, char* tape, hipStream_t s) {
     const VitWs L = vit_ws(v, B);
-    ORBIT_REQUIRE(workspace_bytes >= L.total, "vit_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, L.total);
-    ORBIT_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)frames & 15) == 0,
-                  "vit_forward: workspace must be 256-byte and frames 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
+    const VitTape T = vit_tape(v, B);
     const int D = v->D, M = B * VIT_N;
     char* ws = static_cast<char*>(workspace);
-    float* x = reinterpret_cast<float*>(ws + L.x);
+    auto slot = [&](int i, size_t off) { return reinterpret_cast<float*>(tape + (i < VIT_DEPTH ? i * T.block + off : T.last)); };
+    float* x = tape ? slot(0, T.x) : reinterpret_cast<float*>(ws + L.x);
     float* h = reinterpret_cast<float*>(ws + L.h);
     float* big = reinterpret_cast<float*>(ws + L.big);
     auto ln_params = [&](const std::string& mod, int slot, const float** g, const float** b) {
@@ -526,29 +785,167 @@ int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* f
     }
     for (int i = 0; i < VIT_DEPTH; ++i) {
         const std::string b = "blocks." + std::to_string(i);
+        float* qkvb = tape ? slot(i, T.qkv) : big;
+        float* xmid = tape ? slot(i, T.mid) : x;
+        float* xout = tape ? slot(i + 1, T.x) : x;
         const float *g, *be;
         ln_params(b + ".norm1", 2 * i, &g, &be);
         if ((rc = launch_layernorm(x, D, h, D, M, D, g, be, v->eps, s))) return rc;
-        GemmArgs qkv{h, v->p(b + ".attn.qkv.weight"), v->p(b + ".attn.qkv.bias"), nullptr, nullptr, big, M, 3 * D, D};
+        GemmArgs qkv{h, v->p(b + ".attn.qkv.weight"), v->p(b + ".attn.qkv.bias"), nullptr, nullptr, qkvb, M, 3 * D, D};
         if ((rc = launch_gemm<EPI_BIAS>(qkv, "qkv", s))) return rc;
         const int pi = prof_start("vit_attention", 4.0 * B * v->heads * VIT_N * VIT_N * VIT_HD,
                                   4.0 * 4 * (double)M * D, s);
-        vit_attention_kernel<<<B * v->heads, 256, 0, s>>>(big, h, D, v->heads);
+        vit_attention_kernel<<<B * v->heads, 256, 0, s>>>(qkvb, h, D, v->heads);
         prof_stop(pi, s);
         ORBIT_LAUNCH_CHECK();
-        GemmArgs proj{h, v->p(b + ".attn.proj.weight"), v->p(b + ".attn.proj.bias"), x, nullptr, x, M, D, D};
+        GemmArgs proj{h, v->p(b + ".attn.proj.weight"), v->p(b + ".attn.proj.bias"), x, nullptr, xmid, M, D, D};
         if ((rc = launch_gemm<EPI_RESIDUAL>(proj, "proj", s))) return rc;
         ln_params(b + ".norm2", 2 * i + 1, &g, &be);
-        if ((rc = launch_layernorm(x, D, h, D, M, D, g, be, v->eps, s))) return rc;
+        if ((rc = launch_layernorm(xmid, D, h, D, M, D, g, be, v->eps, s))) return rc;
         GemmArgs fc1{h, v->p(b + ".mlp.fc1.weight"), v->p(b + ".mlp.fc1.bias"), nullptr, nullptr, big, M, 4 * D, D};
-        if ((rc = launch_gemm<EPI_GELU>(fc1, "fc1", s))) return rc;
-        GemmArgs fc2{big, v->p(b + ".mlp.fc2.weight"), v->p(b + ".mlp.fc2.bias"), x, nullptr, x, M, D, 4 * D};
+        if (tape) {
+            fc1.aux = slot(i, T.u);
+            if ((rc = launch_gemm<EPI_GELU_TAPE>(fc1, "fc1", s))) return rc;
+        } else if ((rc = launch_gemm<EPI_GELU>(fc1, "fc1", s))) {
+            return rc;
+        }
+        GemmArgs fc2{big, v->p(b + ".mlp.fc2.weight"), v->p(b + ".mlp.fc2.bias"), xmid, nullptr, xout, M, D, 4 * D};
         if ((rc = launch_gemm<EPI_RESIDUAL>(fc2, "fc2", s))) return rc;
+        x = xout;
     }
     const float *g, *be;
     ln_params("norm", 2 * VIT_DEPTH, &g, &be);
     // final LayerNorm on the class token of every frame, straight into the caller's feature rows
     return launch_layernorm(x, (size_t)VIT_N * D, feats, D, B, D, g, be, v->eps, s);
+}
+
+// (re)build the transposed weights on `s` if a parameter upload invalidated them
+int vit_ensure_wt(orbit_vit_t* v, hipStream_t s) {
+    const size_t D = v->D, per_block = 12 * D * D;
+    if (!v->d_wt) ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&v->d_wt), VIT_DEPTH * per_block * sizeof(float)));
+    if (v->wt_valid) return ORBIT_OK;
+    int rc;
+    for (int i = 0; i < VIT_DEPTH; ++i) {
+        const std::string b = "blocks." + std::to_string(i);
+        float* wt = v->d_wt + i * per_block;  // qkv^T [D][3D], proj^T [D][D], fc1^T [D][4D], fc2^T [4D][D]
+        if ((rc = vit_transpose(v->p(b + ".attn.qkv.weight"), wt, 3 * v->D, v->D, s))) return rc;
+        if ((rc = vit_transpose(v->p(b + ".attn.proj.weight"), wt + 3 * D * D, v->D, v->D, s))) return rc;
+        if ((rc = vit_transpose(v->p(b + ".mlp.fc1.weight"), wt + 4 * D * D, 4 * v->D, v->D, s))) return rc;
+        if ((rc = vit_transpose(v->p(b + ".mlp.fc2.weight"), wt + 8 * D * D, v->D, 4 * v->D, s))) return rc;
+    }
+    v->wt_valid = true;
+    return ORBIT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
+                      float* feats, void* workspace, size_t workspace_bytes, orbit_stream_t stream) {
+    ORBIT_REQUIRE(v && frames && feats && workspace, "vit_forward: null pointer");
+    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "vit_forward: batch of %d frames (1..%d)", B, VIT_MAX_B);
+    if (!v->finalized) return set_err(ORBIT_ERR_STATE, "vit_forward: call orbit_vit_finalize first");
+    ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr),
+                  "vit_forward: film_gamma and film_beta must be given together");
+    const VitWs L = vit_ws(v, B);
+    ORBIT_REQUIRE(workspace_bytes >= L.total, "vit_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, L.total);
+    ORBIT_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)frames & 15) == 0,
+                  "vit_forward: workspace must be 256-byte and frames 16-byte aligned");
+    return vit_forward_impl(v, frames, B, film_gamma, film_beta, feats, workspace, nullptr, (hipStream_t)stream);
+}
+
+// ---- FiLM gradients of the frozen network ----------------------------------------------------------------------------
+size_t orbit_vit_tape_bytes(const orbit_vit_t* v, int B) {
+    if (!v || B <= 0 || B > VIT_MAX_B) return 0;
+    return vit_tape(v, B).total;
+}
+size_t orbit_vit_backward_workspace_bytes(const orbit_vit_t* v, int B) {
+    if (!v || B <= 0 || B > VIT_MAX_B) return 0;
+    return vit_bwd_ws(v, B).total;
+}
+
+int orbit_vit_train_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
+                            float* feats, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
+                            orbit_stream_t stream) {
+    ORBIT_REQUIRE(v && frames && feats && tape && workspace, "vit_train_forward: null pointer");
+    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "vit_train_forward: batch of %d frames (1..%d)", B, VIT_MAX_B);
+    if (!v->finalized) return set_err(ORBIT_ERR_STATE, "vit_train_forward: call orbit_vit_finalize first");
+    ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr),
+                  "vit_train_forward: film_gamma and film_beta must be given together");
+    const VitWs L = vit_ws(v, B);
+    const VitTape T = vit_tape(v, B);
+    ORBIT_REQUIRE(workspace_bytes >= L.total, "vit_train_forward: workspace too small (%zu < %zu bytes)", workspace_bytes,
+                  L.total);
+    ORBIT_REQUIRE(tape_bytes >= T.total, "vit_train_forward: tape too small (%zu < %zu bytes)", tape_bytes, T.total);
+    ORBIT_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)tape & 255) == 0 && ((uintptr_t)frames & 15) == 0,
+                  "vit_train_forward: workspace and tape must be 256-byte and frames 16-byte aligned");
+    return vit_forward_impl(v, frames, B, film_gamma, film_beta, feats, workspace, static_cast<char*>(tape), (hipStream_t)stream);
+}
+
+int orbit_vit_backward(orbit_vit_t* v, int B, const float* film_gamma, const float* film_beta, const float* dfeats,
+                       const void* tape, size_t tape_bytes, float* dgamma, float* dbeta, void* workspace,
+                       size_t workspace_bytes, orbit_stream_t stream) {
+    ORBIT_REQUIRE(v && dfeats && tape && dgamma && dbeta && workspace, "vit_backward: null pointer");
+    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "vit_backward: batch of %d frames (1..%d)", B, VIT_MAX_B);
+    if (!v->finalized) return set_err(ORBIT_ERR_STATE, "vit_backward: call orbit_vit_finalize first");
+    ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr),
+                  "vit_backward: film_gamma and film_beta must be given together");
+    const VitBwdWs L = vit_bwd_ws(v, B);
+    const VitTape T = vit_tape(v, B);
+    ORBIT_REQUIRE(workspace_bytes >= L.total, "vit_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, L.total);
+    ORBIT_REQUIRE(tape_bytes >= T.total, "vit_backward: tape too small (%zu < %zu bytes)", tape_bytes, T.total);
+    ORBIT_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)tape & 255) == 0,
+                  "vit_backward: workspace and tape must be 256-byte aligned");
+    ORBIT_REQUIRE((((uintptr_t)dfeats | (uintptr_t)dgamma | (uintptr_t)dbeta | (uintptr_t)film_gamma) & 3) == 0,
+                  "vit_backward: dfeats, dgamma, dbeta and film_gamma must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = vit_ensure_wt(v, s))) return rc;
+    const int D = v->D, M = B * VIT_N;
+    char* ws = static_cast<char*>(workspace);
+    const char* tp = static_cast<const char*>(tape);
+    float* dx = reinterpret_cast<float*>(ws + L.dx);
+    float* h = reinterpret_cast<float*>(ws + L.h);
+    float* big = reinterpret_cast<float*>(ws + L.big);
+    float* partial = reinterpret_cast<float*>(ws + L.partial);
+    auto slot = [&](int i, size_t off) { return reinterpret_cast<const float*>(tp + i * T.block + off); };
+    auto gamma_of = [&](const std::string& mod, int sl) {
+        return film_gamma ? film_gamma + (size_t)sl * D : v->p(mod + ".weight");
+    };
+    // final norm: token 0 of every frame from dfeats; the other 49 token rows of the gradient stream are exactly zero
+    const int last = 2 * VIT_DEPTH;
+    if ((rc = zero_gradient_stream(dx, (size_t)M * D, s))) return rc;
+    if ((rc = launch_layernorm_bwd(reinterpret_cast<const float*>(tp + T.last), (size_t)VIT_N * D, dfeats, D, gamma_of("norm", last),
+                                   v->eps, nullptr, dx, (size_t)VIT_N * D, B, D, partial, dgamma + (size_t)last * D,
+                                   dbeta + (size_t)last * D, s)))
+        return rc;
+    const size_t DD = (size_t)D * D;
+    for (int i = VIT_DEPTH - 1; i >= 0; --i) {
+        const std::string b = "blocks." + std::to_string(i);
+        const float* wt = v->d_wt + i * 12 * DD;  // qkv^T, proj^T, fc1^T, fc2^T (vit_ensure_wt)
+        // x_out = x_mid + fc2(GELU(u)):  du = (dx W2) o GELU'(u),  dh = du W1,  dx += LN2'(dh)
+        GemmArgs dfc2{dx, wt + 8 * DD, nullptr, slot(i, T.u), nullptr, big, M, 4 * D, D};
+        if ((rc = launch_gemm<EPI_DGELU, true>(dfc2, "dgrad_fc2", s))) return rc;
+        GemmArgs dfc1{big, wt + 4 * DD, nullptr, nullptr, nullptr, h, M, D, 4 * D};
+        if ((rc = launch_gemm<EPI_BIAS, true>(dfc1, "dgrad_fc1", s))) return rc;
+        int sl = 2 * i + 1;
+        if ((rc = launch_layernorm_bwd(slot(i, T.mid), D, h, D, gamma_of(b + ".norm2", sl), v->eps, dx, dx, D, M, D, partial,
+                                       dgamma + (size_t)sl * D, dbeta + (size_t)sl * D, s)))
+            return rc;
+        // x_mid = x + proj(attn(qkv)):  dO = dx Wp,  dqkv = attn'(dO),  dh = dqkv Wqkv,  dx += LN1'(dh)
+        GemmArgs dproj{dx, wt + 3 * DD, nullptr, nullptr, nullptr, h, M, D, D};
+        if ((rc = launch_gemm<EPI_BIAS, true>(dproj, "dgrad_proj", s))) return rc;
+        if ((rc = launch_attention_bwd(slot(i, T.qkv), h, big, B, D, v->heads, s))) return rc;
+        GemmArgs dqkv{big, wt, nullptr, nullptr, nullptr, h, M, D, 3 * D};
+        if ((rc = launch_gemm<EPI_BIAS, true>(dqkv, "dgrad_qkv", s))) return rc;
+        sl = 2 * i;
+        // (block 0: nothing upstream of its norm1 takes a gradient - the patch embedding and CLIP's norm_pre are frozen)
+        if ((rc = launch_layernorm_bwd(slot(i, T.x), D, h, D, gamma_of(b + ".norm1", sl), v->eps, dx, i > 0 ? dx : nullptr, D, M,
+                                       D, partial, dgamma + (size_t)sl * D, dbeta + (size_t)sl * D, s)))
+            return rc;
+    }
+    return ORBIT_OK;
 }
 
 // ---- single operators (parity tests) ---------------------------------------------------------------------------------
@@ -617,6 +1014,63 @@ int orbit_op_vit_attention(const float* qkv, float* out, int B, int D, int heads
     prof_stop(pi, s);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
+}
+
+int orbit_op_vit_linear_dgrad(const float* dy, const float* w, float* wt_scratch, const float* u, const float* residual,
+                              float* dx, int M, int N, int K, int tile_rows, orbit_stream_t stream) {
+    ORBIT_REQUIRE(dy && w && wt_scratch && dx, "op_vit_linear_dgrad: null pointer");
+    ORBIT_REQUIRE(M > 0 && M <= VIT_MAX_B * VIT_N && N > 0 && K > 0, "op_vit_linear_dgrad: bad shape M=%d N=%d K=%d", M, N, K);
+    ORBIT_REQUIRE(K % G_BN == 0 && N % G_BK == 0,
+                  "op_vit_linear_dgrad: K (the Linear's in_features) must be a multiple of %d and N of %d, got N=%d K=%d", G_BN,
+                  G_BK, N, K);
+    ORBIT_REQUIRE(!(u && residual), "op_vit_linear_dgrad: either u (times GELU') or residual (accumulate), not both");
+    ORBIT_REQUIRE(tile_rows == 0 || tile_rows == 64 || tile_rows == 128,
+                  "op_vit_linear_dgrad: tile_rows must be 0, 64 or 128, got %d", tile_rows);
+    ORBIT_REQUIRE(((uintptr_t)dy & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)wt_scratch & 15) == 0,
+                  "op_vit_linear_dgrad: dy, w and wt_scratch must be 16-byte aligned");
+    ORBIT_REQUIRE(((uintptr_t)dx & 3) == 0 && ((uintptr_t)u & 3) == 0 && ((uintptr_t)residual & 3) == 0,
+                  "op_vit_linear_dgrad: dx, u and residual must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = vit_transpose(w, wt_scratch, N, K, s)) return rc;
+    const GemmArgs a{dy, wt_scratch, nullptr, u ? u : residual, nullptr, dx, M, K, N};
+    if (u) return launch_gemm<EPI_DGELU, true>(a, "op_dgrad_gelu", s, tile_rows);
+    if (residual) return launch_gemm<EPI_RESIDUAL, true>(a, "op_dgrad_residual", s, tile_rows);
+    return launch_gemm<EPI_BIAS, true>(a, "op_dgrad", s, tile_rows);
+}
+
+int orbit_op_vit_layernorm_bwd(const float* x, size_t x_stride, const float* dy, size_t dy_stride, const float* gamma, float eps,
+                               const float* dres, float* dx, size_t dx_stride, int rows, int D, float* dgamma, float* dbeta,
+                               float* partial, size_t partial_floats, orbit_stream_t stream) {
+    ORBIT_REQUIRE(x && dy && gamma && dgamma && dbeta && partial, "op_vit_layernorm_bwd: null pointer");
+    ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_layernorm_bwd: unsupported width %d (384 or 768)", D);
+    ORBIT_REQUIRE(rows > 0 && rows <= VIT_MAX_B * VIT_N, "op_vit_layernorm_bwd: %d rows (1..%d)", rows, VIT_MAX_B * VIT_N);
+    ORBIT_REQUIRE(x_stride >= (size_t)D && dy_stride >= (size_t)D && (!dx || dx_stride >= (size_t)D),
+                  "op_vit_layernorm_bwd: row strides must be at least D");
+    ORBIT_REQUIRE(dx || !dres, "op_vit_layernorm_bwd: dres without dx");
+    ORBIT_REQUIRE(!dres || dx_stride == (size_t)D, "op_vit_layernorm_bwd: dres goes with contiguous rows (dx_stride == D) only");
+    ORBIT_REQUIRE(eps >= 0.f, "op_vit_layernorm_bwd: negative eps");
+    ORBIT_REQUIRE(partial_floats >= layernorm_bwd_partial_floats(rows, D),
+                  "op_vit_layernorm_bwd: partial buffer too small (%zu < %zu floats)", partial_floats,
+                  layernorm_bwd_partial_floats(rows, D));
+    ORBIT_REQUIRE((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)gamma | (uintptr_t)dres | (uintptr_t)dx | (uintptr_t)dgamma |
+                    (uintptr_t)dbeta | (uintptr_t)partial) & 3) == 0,
+                  "op_vit_layernorm_bwd: pointers must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    // the final-norm form: the rows x dx_stride stream is zeroed first, as orbit_vit_backward zeroes its gradient stream
+    if (dx && dx_stride > (size_t)D)
+        if (int rc = zero_gradient_stream(dx, (size_t)rows * dx_stride, s)) return rc;
+    return launch_layernorm_bwd(x, x_stride, dy, dy_stride, gamma, eps, dres, dx, dx_stride, rows, D, partial, dgamma, dbeta, s);
+}
+
+int orbit_op_vit_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int D, int heads,
+                               orbit_stream_t stream) {
+    ORBIT_REQUIRE(qkv && dout && dqkv, "op_vit_attention_bwd: null pointer");
+    ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_attention_bwd: unsupported width %d (384 or 768)", D);
+    ORBIT_REQUIRE(heads * VIT_HD == D, "op_vit_attention_bwd: %d heads of %d do not make D=%d", heads, VIT_HD, D);
+    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "op_vit_attention_bwd: batch of %d frames (1..%d)", B, VIT_MAX_B);
+    ORBIT_REQUIRE((((uintptr_t)qkv | (uintptr_t)dout | (uintptr_t)dqkv) & 3) == 0,
+                  "op_vit_attention_bwd: pointers must be 4-byte aligned");
+    return launch_attention_bwd(qkv, dout, dqkv, B, D, heads, (hipStream_t)stream);
 }
 
 }  // extern "C"

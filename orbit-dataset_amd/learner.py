@@ -51,6 +51,10 @@ def build_parser():
     p.add_argument("--batch_size", type=int, default=256)
     p.add_argument("--tasks_per_batch", type=int, default=16)
     p.add_argument("--with_lite", action="store_true")
+    p.add_argument("--vit_native_backward", action="store_true",
+                   help="vit_* extractors: opt in to the native FiLM gradients through the FROZEN transformer (--adapt_features "
+                        "training, with or without --with_lite; the multi-step finetuner's --adapt_features). --learn_extractor "
+                        "stays refused: weight gradients are not built")
     p.add_argument("--num_lite_samples", type=int, default=16)
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--seed", type=int, default=synthetic.DEFAULT_SEED)
@@ -121,7 +125,8 @@ VIT_EXTRACTORS = {"vit_s_32": "imagenet_inception", "vit_b_32": "imagenet_incept
 
 def verify_args(args):
     """reference utils/args.py:203-217. For the transformer extractors also the frame normalisation the reference sets
-    for them (utils/args.py:185-190; the other extractors keep --frame_norm_method) and the inference-only scope."""
+    for them (utils/args.py:185-190; the other extractors keep --frame_norm_method) and the inference-only scope, which
+    --vit_native_backward widens to everything but --learn_extractor."""
     if "train" in args.mode and not args.learn_extractor and not args.adapt_features:
         sys.exit("error: at least one of --learn_extractor and --adapt_features must be used when training")
     if args.frame_size % 1 or args.frame_size < 32:
@@ -132,7 +137,11 @@ def verify_args(args):
         if args.frame_size != 224:
             sys.exit("error: --feature_extractor %s needs --frame_size 224 (got %d)" % (fe, args.frame_size))
         multistep = getattr(args, "personalize_num_grad_steps", None) is not None
-        if "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
+        if getattr(args, "vit_native_backward", False):
+            if args.learn_extractor:
+                sys.exit("error: --vit_native_backward gives FiLM gradients through a frozen %s only: --learn_extractor "
+                         "(weight gradients through a ViT) is not built" % fe)
+        elif "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
             sys.exit("error: --feature_extractor %s is inference-only here (no backward through a ViT): use --mode test "
                      "without --learn_extractor / --with_lite%s" % (fe, " / --adapt_features" if multistep else ""))
 
@@ -181,8 +190,13 @@ class Learner:
         else:
             synthetic.init_parameters_(self.model, seed=a.seed,
                                        film_strength=0.02 if a.feature_extractor == "efficientnet_b0" else 0.1)
+        self._opt_in_vit_backward()
         self.model._set_device(self.device)
         self.model._send_to_device()
+
+    def _opt_in_vit_backward(self):
+        if getattr(self.args, "vit_native_backward", False) and self.args.feature_extractor in VIT_EXTRACTORS:
+            self.model.feature_extractor.native_backward = True
 
     def make_task(self, index):
         a = self.args
@@ -533,6 +547,7 @@ class MultiStepLearner(Learner):
         else:
             synthetic.init_parameters_(self.model, seed=a.seed,
                                        film_strength=0.02 if a.feature_extractor == "efficientnet_b0" else 0.1)
+        self._opt_in_vit_backward()
         self.model._set_device(self.device)
         self.model._send_to_device()
         self.base_state = {k: v.clone() for k, v in self.model.state_dict().items()}

@@ -6,6 +6,7 @@ C-ABI call; torch only routes the gradients between the nodes and into `param.gr
 `zero_grad` work unchanged, as in utils/optim.py:11-33).
 
   ExtractorFunction      orbit_extractor_train_forward / orbit_extractor_backward   (resnet18, efficientnet_b0, set encoder)
+  VitFunction            orbit_vit_train_forward / orbit_vit_backward                (vit_*: FiLM vectors of the frozen network)
   ProtoPredictFunction   orbit_proto_predict / orbit_proto_predict_backward          (gradient w.r.t. query features;
                          the prototypes are constants, classifier_heads.py:261-263 re-wraps them in nn.Parameter)
   MahalanobisPredictFunction  orbit_mahalanobis_predict / orbit_mahalanobis_predict_backward (w.r.t. query features)
@@ -105,6 +106,50 @@ class ExtractorFunction(torch.autograd.Function):
                     n *= d
                 out[n_fixed + j] = flat[off:off + n].view(shape)
         return tuple(out)
+
+
+class VitFunction(torch.autograd.Function):
+    """feats = vit(frames; gamma, beta) with a tape; gradients for the FiLM vectors only (the network is frozen). Runs on the
+    caller's stream."""
+
+    @staticmethod
+    def forward(ctx, net, plan, frames, gamma, beta):
+        lib = _lib.load()
+        B, dev = frames.shape[0], frames.device
+        gamma, beta = gamma.detach().contiguous().float(), beta.detach().contiguous().float()
+        tape = _empty_bytes(lib.orbit_vit_tape_bytes(plan.handle, B), dev)
+        ws = net._workspace(plan, B, dev)
+        feats = torch.empty(B, net.output_size, device=dev, dtype=torch.float32)
+        _lib.check(lib.orbit_vit_train_forward(
+            plan.handle, _lib.dptr(frames, torch.float32), B, _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(feats),
+            ctypes.c_void_p(tape.data_ptr()), tape.numel(), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+            _lib.stream_handle()), "orbit_vit_train_forward")
+        ctx.plan, ctx.tape, ctx.B, ctx.generation = plan, tape, B, plan.generation
+        ctx.save_for_backward(gamma, beta)
+        return feats
+
+    @staticmethod
+    def backward(ctx, dfeats):
+        lib = _lib.load()
+        gamma, beta = ctx.saved_tensors
+        plan = ctx.plan
+        if plan.generation != ctx.generation:  # (as ExtractorFunction: the backward reads the weights from the plan)
+            raise RuntimeError("the extractor's parameters were modified (re-uploaded into the native plan) between the "
+                               "forward that recorded this tape and its backward; run backward before changing them")
+        if ctx.tape is None:
+            raise RuntimeError("this ViT tape was already consumed by a backward")
+        if not (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]):
+            ctx.tape = None
+            return None, None, None, None, None
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+        ws = _empty_bytes(lib.orbit_vit_backward_workspace_bytes(plan.handle, ctx.B), gamma.device)
+        dfeats = dfeats.contiguous().float()
+        _lib.check(lib.orbit_vit_backward(
+            plan.handle, ctx.B, _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(dfeats), ctypes.c_void_p(ctx.tape.data_ptr()),
+            ctx.tape.numel(), _lib.dptr(dgamma), _lib.dptr(dbeta), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+            _lib.stream_handle()), "orbit_vit_backward")
+        ctx.tape = None
+        return (None, None, None, dgamma if ctx.needs_input_grad[3] else None, dbeta if ctx.needs_input_grad[4] else None)
 
 
 class ProtoPredictFunction(torch.autograd.Function):

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .autograd import ExtractorFunction
+from .autograd import ExtractorFunction, VitFunction
 
 _EXTRACTOR_OUTPUT = {"resnet18": 512, "efficientnet_b0": 1280}
 _BN_EPS = {"resnet18": 1e-5, "efficientnet_b0": 1e-3, "set_encoder": 1e-5}
@@ -518,12 +518,16 @@ class VisionTransformer(HipNetwork):
     native transformer runtime (csrc/vit.hip, orbit_vit_*): same parameter tree, state_dict keys and shapes as the timm
     module, FiLM on the LayerNorms named norm / norm1 / norm2 (reference model/film.py:57-66).
 
-    Inference only: a forward that would need a gradient (LITE meta-training, --learn_extractor, FiLM gradients) raises
-    NotImplementedError before anything is launched. There is no BatchNorm or dropout, so train() and eval() compute the same
-    features. Frames must be 224 x 224 (the position table is fixed)."""
+    Inference only by default: a forward that would need a gradient (LITE meta-training, --learn_extractor, FiLM gradients)
+    raises NotImplementedError before anything is launched. With `native_backward = True` set on the instance, the FiLM
+    vectors - or, without them, the FiLM-slot LayerNorm weights / biases - of an otherwise FROZEN network get their gradients
+    from orbit_vit_train_forward / orbit_vit_backward (autograd.VitFunction); any other parameter requiring a gradient is still
+    refused. There is no BatchNorm or dropout, so train() and eval() compute the same features. Frames must be 224 x 224 (the
+    position table is fixed)."""
 
     _api = "vit"
     _probe_size = VIT_FRAME_SIZE
+    native_backward = False  # opt-in (learner flag --vit_native_backward)
 
     def __init__(self, name):
         super().__init__(name)
@@ -559,11 +563,20 @@ class VisionTransformer(HipNetwork):
         return 0, 0  # no training entry points
 
     def wants_grad(self, film=None):
-        if super().wants_grad(film):
+        if not super().wants_grad(film):
+            return False
+        if not self.native_backward:
             raise NotImplementedError(
                 "%s is an inference-only extractor: no native backward (LITE meta-training, --learn_extractor, FiLM "
                 "gradients); run it under torch.no_grad() with frozen parameters" % self.native_name)
-        return False
+        film_keys = {n + leaf for n in self._film_slot_names for leaf in (".weight", ".bias")}
+        other = [key for _, _, key, own in self._leaves if own is not None and own.requires_grad and key not in film_keys]
+        if other:
+            raise NotImplementedError(
+                "%s: native_backward gives the gradients of the FiLM vectors / FiLM-slot LayerNorm parameters of a frozen "
+                "network only; %d other parameters require a gradient (first: %s) and weight gradients (--learn_extractor) "
+                "are not built" % (self.native_name, len(other), other[0]))
+        return True
 
     def forward(self, x, film=None, out=None, check_sync=True):
         _lib.require_gpu()
@@ -581,10 +594,18 @@ class VisionTransformer(HipNetwork):
             if film[0].numel() != self.film_size or film[1].numel() != self.film_size:
                 raise ValueError("film vectors must have %d elements" % self.film_size)
             film = (film[0].contiguous().float(), film[1].contiguous().float())
-        self.wants_grad(film)  # raises before any launch
+        use_tape = self.wants_grad(film) and B > 0  # raises before any launch
         plan = self._plan(H, W)
         if check_sync or plan.stamp is None:
             self.sync(plan)
+        if use_tape:
+            if out is not None:
+                raise ValueError("`out=` cannot be combined with autograd")
+            if film is None:  # the network's own LayerNorm parameters: autograd splits dgamma / dbeta into their 50 grads
+                slots = self.film_slot_modules()
+                film = (torch.cat([m._parameters["weight"].reshape(-1) for _, m in slots]),
+                        torch.cat([m._parameters["bias"].reshape(-1) for _, m in slots]))
+            return VitFunction.apply(self, plan, x, film[0], film[1])
         feats = out if out is not None else torch.empty(B, self.output_size, device=x.device, dtype=torch.float32)
         if B == 0:
             return feats
