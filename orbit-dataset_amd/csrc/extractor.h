@@ -8,14 +8,9 @@
 #include <vector>
 #include "common.h"
 #include "graph_cache.h"
+#include "param_pool.h"
 
 namespace orbit {
-
-struct Param {
-    std::string key;
-    size_t numel = 0, off = 0;  // offset (floats) into the parameter pool
-    bool loaded = false;
-};
 
 struct BNDesc {        // host side
     int gamma, beta, mean, var;  // param indices
@@ -148,23 +143,16 @@ using namespace orbit;  // internal header: only included by the two runtime tra
 struct orbit_extractor {
     std::string name;
     int H = 0, W = 0, out_size = 0;
-    std::vector<Param> params;
-    std::map<std::string, int> index;
+    ParamPool pool{4};  // the parameters by state_dict key (csrc/param_pool.h); float4-aligned tensors
     std::vector<BNDesc> bns;
     std::vector<Op> ops;
     std::vector<int> film_slots;  // BN indices in module-traversal order
     int film_size = 0;
-    size_t pool_floats = 0, packed_floats = 0, fold_floats = 0;
+    size_t packed_floats = 0, fold_floats = 0;
     size_t buf_elems[3] = {0, 0, 0};  // per-frame element counts of the rotating activation buffers
     int max_se_c = 0;
     size_t max_partial = 0;  // floats per frame of the SE pooling-partial buffer
     double macs = 0;
-    float* d_pool = nullptr;
-    // batched upload (orbit_extractor_load_all_async): device table of source pointers + its host shadow, and the static
-    // table of (pool offset, numel) per parameter
-    const float** d_src = nullptr;
-    std::vector<const float*> h_src;
-    size_t* d_dst_meta = nullptr;  // [n][2] = offset, numel
     float* d_packed = nullptr;
     std::vector<PackJob> pack_jobs;   // filter re-layouts of orbit_extractor_finalize (built at the first call)
     PackJob* d_pack_jobs = nullptr;
@@ -222,32 +210,25 @@ struct orbit_extractor {
     // device buffers are created on first use so that a plan can be built and inspected (state_dict keys,
     // FiLM slots, workspace size, MACs) on a host without a GPU
     int ensure_device() {
-        if (d_pool) return ORBIT_OK;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_pool), pool_floats * sizeof(float));
-        if (e == hipSuccess) e = hipMemset(d_pool, 0, pool_floats * sizeof(float));
-        if (e == hipSuccess)
-            e = hipMalloc(reinterpret_cast<void**>(&d_packed), std::max<size_t>(packed_floats, 4) * sizeof(float));
+        if (d_packed) return ORBIT_OK;
+        if (int rc = pool.ensure_device()) return rc;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_packed), std::max<size_t>(packed_floats, 4) * sizeof(float));
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_fold), 2 * fold_floats * sizeof(float));
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_bn), bn_dev.size() * sizeof(BNDev));
         if (e == hipSuccess)
             e = hipMemcpy(d_bn, bn_dev.data(), bn_dev.size() * sizeof(BNDev), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
-            (void)hipFree(d_pool), (void)hipFree(d_packed), (void)hipFree(d_fold), (void)hipFree(d_bn);
-            d_pool = d_packed = d_fold = nullptr, d_bn = nullptr;
+            pool.free_device();
+            (void)hipFree(d_packed), (void)hipFree(d_fold), (void)hipFree(d_bn);
+            d_packed = d_fold = nullptr, d_bn = nullptr;
             (void)hipGetLastError();
             return set_err(ORBIT_ERR_HIP, "extractor: device allocation failed: %s", hipGetErrorString(e));
         }
         return ORBIT_OK;
     }
 
-    int add_param(const std::string& key, size_t numel) {
-        Param p;
-        p.key = key, p.numel = numel, p.off = pool_floats;
-        pool_floats += (numel + 3) / 4 * 4;
-        params.push_back(p);
-        index[key] = (int)params.size() - 1;
-        return (int)params.size() - 1;
-    }
+    int add_param(const std::string& key, size_t numel) { return pool.add(key, numel); }
+    float* param(int k) const { return pool.ptr(k); }
     int add_bn(const std::string& prefix, int C, float eps, bool film, int conv_bias = -1) {
         BNDesc b;
         b.name = prefix;
@@ -280,7 +261,7 @@ struct orbit_extractor {
         o.H = H_, o.W = W_, o.Cin = Cin, o.Cout = Cout, o.KH = K, o.KW = K, o.stride = stride;
         o.pad_t = pad_t, o.pad_l = pad_l, o.Ho = Ho, o.Wo = Wo, o.act = act, o.pool2 = pool2;
         o.x_nchw = x_nchw, o.use_gate = use_gate, o.bn = bn, o.bias = bias;
-        o.weight = index.count(wkey) ? index[wkey] : add_param(wkey, (size_t)Cout * Cin * K * K);
+        o.weight = pool.find(wkey) >= 0 ? pool.find(wkey) : add_param(wkey, (size_t)Cout * Cin * K * K);
         o.packed_off = packed_floats;
         packed_floats += conv_packed_floats(Cin, Cout, K, K, x_nchw);
         // the fragment-ordered copy of a pointwise filter only where the register GEMM will be asked for it (csrc/pw_rgemm.hip:

@@ -136,8 +136,6 @@ static int build_efficientnet_b0(orbit_extractor* fe, int H, int W, bool unfused
         int ho, wo;
         const int t1 = (cur + 1) % 3, t2 = (cur + 2) % 3;
         // registration order: conv_dw, bn1, se, conv_pw, bn2
-        const size_t dw_slot = fe->params.size();
-        (void)dw_slot;
         // conv_dw param is registered inside add_dw, bn1 after it: keep state_dict order cosmetic only
         const int bn1 = fe->add_bn(p + ".bn1", 32, eps, false);
         int se_chunks0;
@@ -295,7 +293,7 @@ int orbit_extractor_create_ex(const char* name, int H, int W, int flags, orbit_e
     ORBIT_REQUIRE(name && out, "extractor_create: null pointer");
     ORBIT_REQUIRE(H >= 8 && W >= 8 && H <= 4096 && W <= 4096, "extractor_create: bad frame size %dx%d", H, W);
     orbit_extractor* fe = new orbit_extractor();
-    fe->name = name, fe->H = H, fe->W = W;
+    fe->name = name, fe->pool.owner = name, fe->H = H, fe->W = W;
     int rc;
     if (fe->name == "resnet18") rc = build_resnet18(fe, H, W);
     else if (fe->name == "efficientnet_b0") rc = build_efficientnet_b0(fe, H, W, (flags & ORBIT_PLAN_UNFUSED) != 0);
@@ -309,9 +307,9 @@ int orbit_extractor_create_ex(const char* name, int H, int W, int flags, orbit_e
     for (size_t i = 0; i < fe->bns.size(); ++i) {
         const BNDesc& b = fe->bns[i];
         BNDev& d = fe->bn_dev[i];
-        d.gamma = fe->params[b.gamma].off, d.beta = fe->params[b.beta].off;
-        d.mean = fe->params[b.mean].off, d.var = fe->params[b.var].off;
-        d.conv_bias = b.conv_bias >= 0 ? fe->params[b.conv_bias].off : (size_t)-1;
+        d.gamma = fe->pool.off(b.gamma), d.beta = fe->pool.off(b.beta);
+        d.mean = fe->pool.off(b.mean), d.var = fe->pool.off(b.var);
+        d.conv_bias = b.conv_bias >= 0 ? fe->pool.off(b.conv_bias) : (size_t)-1;
         d.fold_off = b.fold_off, d.C = b.C, d.film_off = b.film_off, d.eps = b.eps;
     }
     *out = fe;
@@ -325,9 +323,7 @@ void orbit_extractor_destroy(orbit_extractor_t* fe) {
     fe->graphs.clear();
     fe->train_graphs.clear();
     if (fe->cap_stream) (void)hipStreamDestroy(fe->cap_stream);
-    (void)hipFree(fe->d_pool);
-    (void)hipFree(fe->d_src);
-    (void)hipFree(fe->d_dst_meta);
+    fe->pool.free_device();
     (void)hipFree(fe->d_packed);
     (void)hipFree(fe->d_pack_jobs);
     (void)hipFree(fe->d_fold);
@@ -335,86 +331,37 @@ void orbit_extractor_destroy(orbit_extractor_t* fe) {
     delete fe;
 }
 
-int orbit_extractor_num_params(const orbit_extractor_t* fe) { return fe ? (int)fe->params.size() : 0; }
-const char* orbit_extractor_param_name(const orbit_extractor_t* fe, int i) {
-    return (fe && i >= 0 && i < (int)fe->params.size()) ? fe->params[i].key.c_str() : nullptr;
-}
-size_t orbit_extractor_param_numel(const orbit_extractor_t* fe, int i) {
-    return (fe && i >= 0 && i < (int)fe->params.size()) ? fe->params[i].numel : 0;
-}
+int orbit_extractor_num_params(const orbit_extractor_t* fe) { return fe ? fe->pool.size() : 0; }
+const char* orbit_extractor_param_name(const orbit_extractor_t* fe, int i) { return fe ? fe->pool.name(i) : nullptr; }
+size_t orbit_extractor_param_numel(const orbit_extractor_t* fe, int i) { return fe ? fe->pool.numel(i) : 0; }
 
+// every upload invalidates what finalize derived from the parameters and the dgrad filters of the training runtime
 int orbit_extractor_load(orbit_extractor_t* fe, const char* key, const float* data, size_t numel) {
     ORBIT_REQUIRE(fe && key && data, "extractor_load: null pointer");
-    auto it = fe->index.find(key);
-    ORBIT_REQUIRE(it != fe->index.end(), "extractor_load: unexpected key '%s' for %s", key, fe->name.c_str());
-    Param& p = fe->params[it->second];
-    ORBIT_REQUIRE(p.numel == numel, "extractor_load: '%s' has %zu elements, expected %zu", key, numel, p.numel);
-    if (int rc = fe->ensure_device()) return rc;
-    ORBIT_HIP_CHECK(hipMemcpy(fe->d_pool + p.off, data, numel * sizeof(float), hipMemcpyDefault));
-    p.loaded = true;
-    fe->finalized = false;
-    fe->dgrad_packed = false;
+    if (int rc = fe->pool.load("extractor_load", key, data, numel)) return rc;
+    fe->finalized = false, fe->dgrad_packed = false;
     return ORBIT_OK;
 }
 
 int orbit_extractor_load_async(orbit_extractor_t* fe, const char* key, const float* device_data, size_t numel,
                                orbit_stream_t stream) {
     ORBIT_REQUIRE(fe && key && device_data, "extractor_load_async: null pointer");
-    auto it = fe->index.find(key);
-    ORBIT_REQUIRE(it != fe->index.end(), "extractor_load_async: unexpected key '%s' for %s", key, fe->name.c_str());
-    Param& p = fe->params[it->second];
-    ORBIT_REQUIRE(p.numel == numel, "extractor_load_async: '%s' has %zu elements, expected %zu", key, numel, p.numel);
-    if (int rc = fe->ensure_device()) return rc;
-    ORBIT_HIP_CHECK(hipMemcpyAsync(fe->d_pool + p.off, device_data, numel * sizeof(float), hipMemcpyDeviceToDevice,
-                                   (hipStream_t)stream));
-    p.loaded = true;
-    fe->finalized = false;
-    fe->dgrad_packed = false;
+    if (int rc = fe->pool.load_async("extractor_load_async", key, device_data, numel, (hipStream_t)stream)) return rc;
+    fe->finalized = false, fe->dgrad_packed = false;
     return ORBIT_OK;
-}
-
-// one kernel copies every parameter tensor into the pool: grid (chunks, parameters)
-__global__ __launch_bounds__(256) void gather_params_kernel(const float* const* __restrict__ src,
-                                                            const size_t* __restrict__ meta, float* __restrict__ pool) {
-    const float* s_ = src[blockIdx.y];
-    float* d = pool + meta[2 * blockIdx.y];
-    const size_t n = meta[2 * blockIdx.y + 1];
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) d[i] = s_[i];
 }
 
 int orbit_extractor_load_all_async(orbit_extractor_t* fe, const float* const* device_ptrs, int n, orbit_stream_t stream) {
     ORBIT_REQUIRE(fe && device_ptrs, "extractor_load_all_async: null pointer");
-    ORBIT_REQUIRE(n == (int)fe->params.size(), "extractor_load_all_async: %d pointers for %zu parameters", n,
-                  fe->params.size());
-    if (int rc = fe->ensure_device()) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (!fe->d_src) {
-        ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fe->d_src), n * sizeof(float*)));
-        ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fe->d_dst_meta), 2 * n * sizeof(size_t)));
-        std::vector<size_t> meta(2 * n);
-        for (int i = 0; i < n; ++i) meta[2 * i] = fe->params[i].off, meta[2 * i + 1] = fe->params[i].numel;
-        ORBIT_HIP_CHECK(hipMemcpy(fe->d_dst_meta, meta.data(), meta.size() * sizeof(size_t), hipMemcpyHostToDevice));
-    }
-    bool same = (int)fe->h_src.size() == n;
-    for (int i = 0; same && i < n; ++i) same = fe->h_src[i] == device_ptrs[i];
-    if (!same) {  // the tensors moved (first call, load_state_dict with new storage): refresh the pointer table
-        for (int i = 0; i < n; ++i) ORBIT_REQUIRE(device_ptrs[i], "extractor_load_all_async: null tensor %d", i);
-        fe->h_src.assign(device_ptrs, device_ptrs + n);
-        ORBIT_HIP_CHECK(hipStreamSynchronize(s));  // the table may still be read by an earlier gather on this stream
-        ORBIT_HIP_CHECK(hipMemcpy(fe->d_src, fe->h_src.data(), n * sizeof(float*), hipMemcpyHostToDevice));
-    }
-    gather_params_kernel<<<dim3(32, n), 256, 0, s>>>(fe->d_src, fe->d_dst_meta, fe->d_pool);
-    ORBIT_LAUNCH_CHECK();
-    for (Param& p : fe->params) p.loaded = true;
-    fe->finalized = false;
-    fe->dgrad_packed = false;
+    if (int rc = fe->pool.load_all_async("extractor_load_all_async", device_ptrs, n, 32, (hipStream_t)stream)) return rc;
+    fe->finalized = false, fe->dgrad_packed = false;
     return ORBIT_OK;
 }
 
 int orbit_extractor_finalize(orbit_extractor_t* fe, orbit_stream_t stream) {
     ORBIT_REQUIRE(fe, "extractor_finalize: null pointer");
-    for (const Param& p : fe->params)
-        ORBIT_REQUIRE(p.loaded, "extractor_finalize: parameter '%s' was never loaded", p.key.c_str());
+    const char* missing = nullptr;
+    ORBIT_REQUIRE(fe->pool.all_loaded(&missing), "extractor_finalize: parameter '%s' was never loaded", missing);
     if (int rc = fe->ensure_device()) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (fe->pack_jobs_bk != get_option("conv_bk")) {  // (tuning sweeps change the K-tile width, i.e. the packed geometry)
@@ -434,19 +381,19 @@ int orbit_extractor_finalize(orbit_extractor_t* fe, orbit_stream_t stream) {
         for (const Op& o : fe->ops) {
             if (o.kind == OP_CONV) {
                 const ConvPackGeom g = conv_pack_geom(o.Cin, o.Cout, o.KH, o.KW, o.x_nchw);
-                job(o.x_nchw ? 1 : 0, fe->d_pool + fe->params[o.weight].off, fe->d_packed + o.packed_off, o.Cin, o.Cout, o.KH,
+                job(o.x_nchw ? 1 : 0, fe->param(o.weight), fe->d_packed + o.packed_off, o.Cin, o.Cout, o.KH,
                     o.KW, g.cin_pad, g.kt, g.cout_pad, (size_t)g.cout_pad * g.kt);
                 if (o.frag_off != SIZE_MAX)
-                    job(5, fe->d_pool + fe->params[o.weight].off, fe->d_packed + o.frag_off, o.Cin, o.Cout, 1, 1, 0, o.Cin / 16,
+                    job(5, fe->param(o.weight), fe->d_packed + o.frag_off, o.Cin, o.Cout, 1, 1, 0, o.Cin / 16,
                         0, conv_frag_floats(o.Cin, o.Cout, 1, 1, 0));
             } else if (o.kind == OP_DWCONV) {
-                job(2, fe->d_pool + fe->params[o.weight].off, fe->d_packed + o.packed_off, o.Cin, 0, o.KH, o.KH, 0, 0, 0,
+                job(2, fe->param(o.weight), fe->d_packed + o.packed_off, o.Cin, 0, o.KH, o.KH, 0, 0, 0,
                     (size_t)o.Cin * o.KH * o.KH);
             } else if (o.kind == OP_MBFRONT) {
-                job(2, fe->d_pool + fe->params[o.weight2].off, fe->d_packed + o.packed_off, o.Cout, 0, o.KH, o.KH, 0, 0, 0,
+                job(2, fe->param(o.weight2), fe->d_packed + o.packed_off, o.Cout, 0, o.KH, o.KH, 0, 0, 0,
                     (size_t)o.Cout * o.KH * o.KH);
             } else if (o.kind == OP_SE) {
-                job(3, fe->d_pool + fe->params[o.se_w2].off, fe->d_packed + o.packed_off, o.Cin, o.R, 0, 0, 0, 0, 0,
+                job(3, fe->param(o.se_w2), fe->d_packed + o.packed_off, o.Cin, o.R, 0, 0, 0, 0, 0,
                     (size_t)o.Cin * o.R);
             }
         }
@@ -454,10 +401,10 @@ int orbit_extractor_finalize(orbit_extractor_t* fe, orbit_stream_t stream) {
     if (int rc = run_pack_jobs(fe->pack_jobs, &fe->d_pack_jobs, s)) return rc;
     for (const Op& o : fe->ops)  // (the fused stem's [mid][32] filter layout has its own kernel; inference plans only)
         if (o.kind == OP_MBFRONT && o.stem)
-            if (int rc = stem_pack_weights(fe->d_pool + fe->params[o.weight].off, fe->d_packed + o.packed_off2, o.Cout, s))
+            if (int rc = stem_pack_weights(fe->param(o.weight), fe->d_packed + o.packed_off2, o.Cout, s))
                 return rc;
     dim3 grid((unsigned)fe->bns.size(), 2);
-    bn_fold_all_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->d_pool, nullptr, nullptr, fe->d_fold,
+    bn_fold_all_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->pool.d_pool, nullptr, nullptr, fe->d_fold,
                                             fe->d_fold + fe->fold_floats);
     ORBIT_LAUNCH_CHECK();
     fe->graphs.clear();
@@ -553,7 +500,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
         float* fs = reinterpret_cast<float*>(ws + L.fold);
         dim3 grid((unsigned)fe->bns.size(), 2);
         const int rec = prof_start("bn_fold_film", 0.0, 4.0 * 6.0 * fe->fold_floats, s);
-        bn_fold_all_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->d_pool, film_gamma, film_beta, fs, fs + fe->fold_floats);
+        bn_fold_all_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->pool.d_pool, film_gamma, film_beta, fs, fs + fe->fold_floats);
         prof_stop(rec, s);
         ORBIT_LAUNCH_CHECK();
         scale = fs, shift = fs + fe->fold_floats;
@@ -566,7 +513,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                 if (o.x_nchw && !o.pool2 && o.res < 0 && o.bn >= 0 &&
                     stem_direct_supported(o.Cin, o.Cout, o.KH, o.stride, o.W, o.act) && o.KH == o.KW) {
                     // EfficientNet stem: LDS-staged input rows + VALU (csrc/stem.hip) instead of the element-wise gather
-                    rc = launch_stem_direct(buf(o.in), fe->d_pool + fe->params[o.weight].off, scale + fe->bns[o.bn].fold_off,
+                    rc = launch_stem_direct(buf(o.in), fe->param(o.weight), scale + fe->bns[o.bn].fold_off,
                                             shift + fe->bns[o.bn].fold_off, buf(o.out), B, o.H, o.W, o.pad_t, o.pad_l, o.Ho,
                                             o.Wo, s);
                     break;
@@ -578,8 +525,8 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                     d.scale = scale + fe->bns[o.bn].fold_off, d.shift = shift + fe->bns[o.bn].fold_off;
                     d.residual = o.res >= 0 ? buf(o.res) : nullptr;
                     d.partial = buf(BUF_POOLED), d.chunks = se.se_chunks, d.se_hw = se.se_hw;
-                    d.w1 = fe->d_pool + fe->params[se.se_w1].off, d.b1 = fe->d_pool + fe->params[se.se_b1].off;
-                    d.w2t = fe->d_packed + se.packed_off, d.b2 = fe->d_pool + fe->params[se.se_b2].off, d.R = se.R;
+                    d.w1 = fe->param(se.se_w1), d.b1 = fe->param(se.se_b1);
+                    d.w2t = fe->d_packed + se.packed_off, d.b2 = fe->param(se.se_b2), d.R = se.R;
                     d.B = B, d.H = o.H, d.W = o.W, d.Cin = o.Cin, d.Cout = o.Cout;
                     rc = launch_pw_stream(d, s);
                     break;
@@ -611,7 +558,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                                           scale + fe->bns[o.bn2].fold_off, shift + fe->bns[o.bn2].fold_off, buf(o.out),
                                           buf(BUF_POOLED), B, o.stem_h, o.stem_w, o.stem_pt, o.stem_pl, o.H, o.W, s, o.se_chunks);
                 else
-                    rc = launch_mbconv_rows(buf(o.in), fe->d_pool + fe->params[o.weight].off,
+                    rc = launch_mbconv_rows(buf(o.in), fe->param(o.weight),
                                             scale + fe->bns[o.bn].fold_off, shift + fe->bns[o.bn].fold_off,
                                             fe->d_packed + o.packed_off, scale + fe->bns[o.bn2].fold_off,
                                             shift + fe->bns[o.bn2].fold_off, buf(o.out), buf(BUF_POOLED), B, o.H, o.W, o.Cin,
@@ -626,9 +573,9 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                 break;
             case OP_SE:
                 if (se_in_projection(fe, oi)) break;  // the projection computes the gate in its prologue
-                rc = launch_se_gate2(buf(BUF_POOLED), o.se_chunks, o.se_hw, fe->d_pool + fe->params[o.se_w1].off,
-                                     fe->d_pool + fe->params[o.se_b1].off, fe->d_packed + o.packed_off,
-                                     fe->d_pool + fe->params[o.se_b2].off, buf(BUF_GATE), B, o.Cin, o.R, s);
+                rc = launch_se_gate2(buf(BUF_POOLED), o.se_chunks, o.se_hw, fe->param(o.se_w1),
+                                     fe->param(o.se_b1), fe->d_packed + o.packed_off,
+                                     fe->param(o.se_b2), buf(BUF_GATE), B, o.Cin, o.R, s);
                 break;
         }
         if (rc != ORBIT_OK) return rc;

@@ -342,7 +342,7 @@ static int ensure_dgrad_filters(orbit_extractor* fe, hipStream_t s) {
                 if (fe->dgrad_off[i] == NONE) continue;
                 const ConvPackGeom g = conv_pack_geom(o.Cout, o.Cin, o.KH, o.KW, 0);  // the dgrad conv: Cin' = Cout, Cout' = Cin
                 PackJob j;
-                j.src = fe->d_pool + fe->params[o.weight].off, j.dst = fe->d_dgrad + fe->dgrad_off[i], j.kind = 4;
+                j.src = fe->param(o.weight), j.dst = fe->d_dgrad + fe->dgrad_off[i], j.kind = 4;
                 j.Cin = o.Cin, j.Cout = o.Cout, j.KH = o.KH, j.KW = o.KW, j.cin_pad = g.cin_pad, j.KT = g.kt;
                 j.cout_pad = g.cout_pad, j.total = (unsigned)((size_t)g.cout_pad * g.kt);
                 fe->dgrad_jobs.push_back(j);
@@ -375,16 +375,16 @@ size_t orbit_extractor_backward_workspace_bytes(const orbit_extractor_t* fe, int
     return bwd_layout(fe, B).total;
 }
 
-size_t orbit_extractor_grad_floats(const orbit_extractor_t* fe) { return fe ? fe->pool_floats : 0; }
+size_t orbit_extractor_grad_floats(const orbit_extractor_t* fe) { return fe ? fe->pool.pool_floats : 0; }
 size_t orbit_extractor_param_offset(const orbit_extractor_t* fe, int i) {
-    return (fe && i >= 0 && i < (int)fe->params.size()) ? fe->params[i].off : 0;
+    return (fe && i >= 0 && i < fe->pool.size()) ? fe->pool.off(i) : 0;
 }
 size_t orbit_extractor_bn_stat_floats(const orbit_extractor_t* fe) { return fe ? fe->fold_floats : 0; }
 
 int orbit_extractor_export_bn_stats(orbit_extractor_t* fe, float* dst, orbit_stream_t stream) {
     ORBIT_REQUIRE(fe && dst, "extractor_export_bn_stats: null pointer");
     if (!fe->finalized) return set_err(ORBIT_ERR_STATE, "extractor_export_bn_stats: plan is not finalized");
-    bn_export_kernel<<<dim3((unsigned)fe->bns.size(), 2), 256, 0, (hipStream_t)stream>>>(fe->d_bn, fe->d_pool, dst,
+    bn_export_kernel<<<dim3((unsigned)fe->bns.size(), 2), 256, 0, (hipStream_t)stream>>>(fe->d_bn, fe->pool.d_pool, dst,
                                                                                         fe->fold_floats);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
@@ -432,11 +432,11 @@ int orbit_extractor_apply_deferred_bn_stats(orbit_extractor_t* fe, const void* t
     const TapeLayout L = tape_layout(fe, B);
     ORBIT_REQUIRE(tape_bytes >= L.total, "extractor_apply_deferred_bn_stats: tape too small (%zu < %zu bytes)", tape_bytes, L.total);
     bn_apply_deferred_kernel<<<dim3((unsigned)fe->bns.size(), 2), 256, 0, (hipStream_t)stream>>>(
-        fe->d_bn, fe->d_pool, reinterpret_cast<const float*>(static_cast<const char*>(tape) + L.rstat), fe->fold_floats, momentum);
+        fe->d_bn, fe->pool.d_pool, reinterpret_cast<const float*>(static_cast<const char*>(tape) + L.rstat), fe->fold_floats, momentum);
     ORBIT_LAUNCH_CHECK();
     // the static fold follows the running statistics this call just changed (the deferred forward skipped its own re-fold)
     bn_fold_all_kernel<<<dim3((unsigned)fe->bns.size(), 2), 256, 0, (hipStream_t)stream>>>(
-        fe->d_bn, fe->d_pool, nullptr, nullptr, fe->d_fold, fe->d_fold + fe->fold_floats);
+        fe->d_bn, fe->pool.d_pool, nullptr, nullptr, fe->d_fold, fe->d_fold + fe->fold_floats);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
 }
@@ -456,7 +456,7 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
     defer_stats = defer_stats && bn_train;
     if (defer_stats) momentum = 1.0f;
     const bool film = film_gamma && fe->film_size > 0;
-    auto param = [&](int k) { return fe->d_pool + fe->params[k].off; };
+    auto param = [&](int k) { return fe->param(k); };
     // a layer's slice of the fold arrays on the tape, and the inputs of its train-mode finalize
     auto fold = [&](const BNDesc& bn) {
         return BnFold{fl(L.mean) + bn.fold_off, fl(L.invstd) + bn.fold_off, fl(L.scale) + bn.fold_off, fl(L.shift) + bn.fold_off};
@@ -473,10 +473,10 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
     };
     if (!bn_train) {
         dim3 grid((unsigned)fe->bns.size(), 2);
-        bn_fold_all_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->d_pool, film ? film_gamma : nullptr,
+        bn_fold_all_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->pool.d_pool, film ? film_gamma : nullptr,
                                                 film ? film_beta : nullptr, fl(L.scale), fl(L.shift));
         ORBIT_LAUNCH_CHECK();
-        bn_eval_stats_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->d_pool, fl(L.mean), fl(L.invstd));
+        bn_eval_stats_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->pool.d_pool, fl(L.mean), fl(L.invstd));
         ORBIT_LAUNCH_CHECK();
     }
     const TrainForms F = train_forms(fe, B, bn_train, no_backward);
@@ -614,7 +614,7 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
         // d_pool's statistics nor write the plan-owned d_fold here - orbit_extractor_apply_deferred_bn_stats re-folds after
         // the join)
         dim3 grid((unsigned)fe->bns.size(), 2);
-        bn_fold_all_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->d_pool, nullptr, nullptr, fe->d_fold,
+        bn_fold_all_kernel<<<grid, 256, 0, s>>>(fe->d_bn, fe->pool.d_pool, nullptr, nullptr, fe->d_fold,
                                                 fe->d_fold + fe->fold_floats);
         ORBIT_LAUNCH_CHECK();
     }
@@ -682,7 +682,7 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
     size_t se_scratch_used = 0;
     SeParamJobs se_jobs;
     int n_se_jobs = 0;
-    auto param = [&](int k) { return fe->d_pool + fe->params[k].off; };
+    auto param = [&](int k) { return fe->param(k); };
     // a layer's slice of the fold arrays on the tape; the gamma its forward used (FiLM's or the plan's) with the matching places
     // of its gradients
     auto fold = [&](const BNDesc& bn) {
@@ -695,9 +695,9 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
         if (fm) {
             if (dfilm_gamma) p.dgamma = dfilm_gamma + bn.film_off, p.dbeta = dfilm_beta + bn.film_off;
         } else if (param_grads) {
-            p.dgamma = param_grads + fe->params[bn.gamma].off, p.dbeta = param_grads + fe->params[bn.beta].off;
+            p.dgamma = param_grads + fe->pool.off(bn.gamma), p.dbeta = param_grads + fe->pool.off(bn.beta);
         }
-        if (wg && bn.conv_bias >= 0) p.dbias = param_grads + fe->params[bn.conv_bias].off;
+        if (wg && bn.conv_bias >= 0) p.dbias = param_grads + fe->pool.off(bn.conv_bias);
         return p;
     };
 
@@ -815,11 +815,11 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
                     // the forward never wrote this layer's input: the filter gradient rebuilds it from the producing conv's raw
                     // output as it stages its patch
                     const BnFoldC in = fold(fe->bns[fe->ops[src].bn]);
-                    return launch_dwconv_wgrad(tf(L.y[src]), slot_ptr(kdy), param_grads + fe->params[o.weight].off,
+                    return launch_dwconv_wgrad(tf(L.y[src]), slot_ptr(kdy), param_grads + fe->pool.off(o.weight),
                                                wgrad_scratch, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s,
                                                in.scale, in.shift, fe->ops[src].act);
                 }
-                return launch_dwconv_wgrad(out_tensor(src), slot_ptr(kdy), param_grads + fe->params[o.weight].off,
+                return launch_dwconv_wgrad(out_tensor(src), slot_ptr(kdy), param_grads + fe->pool.off(o.weight),
                                            wgrad_scratch, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s);
             };
             if (wg && !wg_fused) {
@@ -851,7 +851,7 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
                 if (bnb_ptr) pre_reduced[src] = nblk;  // 0: that kernel form has no such epilogue, the slot holds plain dx
                 if (wg_fused)
                     rc = wrows > 0 ? launch_dwconv_wgrad_reduce(bnb.wgrad_partial, wrows, o.KH, o.Cin,
-                                                                param_grads + fe->params[o.weight].off, s)
+                                                                param_grads + fe->pool.off(o.weight), s)
                                    : filter_gradient();
             }
             release(kdy);
@@ -913,7 +913,7 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
                 float* cw = cwgrad_base + cwgrad_used;
                 cwgrad_used += align_up(conv_wgrad_scratch_floats(B, o.Cin, o.Cout, o.KH, o.KW, o.Ho, o.Wo), 64);
                 WgradReduceJob* defer = n_wg_jobs < WGRAD_REDUCE_JOBS ? &wg_jobs.j[n_wg_jobs] : nullptr;
-                rc = launch_conv_wgrad(out_tensor(src), o.x_nchw, slot_ptr(kdy), param_grads + fe->params[o.weight].off, B,
+                rc = launch_conv_wgrad(out_tensor(src), o.x_nchw, slot_ptr(kdy), param_grads + fe->pool.off(o.weight), B,
                                        o.H, o.W, o.Cin, o.Cout, o.KH, o.KW, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, cw, s,
                                        o.use_gate ? tf(L.a[P.gate[i]]) : nullptr, defer);
                 if (rc != ORBIT_OK) return rc;
@@ -935,9 +935,9 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
                 // end of the reverse pass (nothing in it reads them)
                 const bool batch_params = pg != nullptr && n_se_jobs < SE_PARAM_JOBS && so.R <= 48;
                 if (batch_params) {
-                    se_jobs.j[n_se_jobs++] = se_bwd_param_job(se_scratch, tf(L.p[se]), B, o.Cin, so.R, pg + fe->params[so.se_w1].off,
-                                                              pg + fe->params[so.se_b1].off, pg + fe->params[so.se_w2].off,
-                                                              pg + fe->params[so.se_b2].off);
+                    se_jobs.j[n_se_jobs++] = se_bwd_param_job(se_scratch, tf(L.p[se]), B, o.Cin, so.R, pg + fe->pool.off(so.se_w1),
+                                                              pg + fe->pool.off(so.se_b1), pg + fe->pool.off(so.se_w2),
+                                                              pg + fe->pool.off(so.se_b2));
                     pg = nullptr;
                 }
                 // x = SiLU(BatchNorm(depthwise output)): the first (reduction) pass of that BatchNorm's backward is folded
@@ -962,10 +962,10 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
                 }
                 rc = launch_se_gate_backward(slot_ptr(kt), out_tensor(src), tf(L.p[se]), tf(L.a[se]), param(so.se_w1),
                                              param(so.se_b1), param(so.se_w2), param(so.se_b2),
-                                             sums_only ? nullptr : slot_ptr(k), pg ? pg + fe->params[so.se_w1].off : nullptr,
-                                             pg ? pg + fe->params[so.se_b1].off : nullptr,
-                                             pg ? pg + fe->params[so.se_w2].off : nullptr,
-                                             pg ? pg + fe->params[so.se_b2].off : nullptr, se_scratch, B, o.H * o.W, o.Cin,
+                                             sums_only ? nullptr : slot_ptr(k), pg ? pg + fe->pool.off(so.se_w1) : nullptr,
+                                             pg ? pg + fe->pool.off(so.se_b1) : nullptr,
+                                             pg ? pg + fe->pool.off(so.se_w2) : nullptr,
+                                             pg ? pg + fe->pool.off(so.se_b2) : nullptr, se_scratch, B, o.H * o.W, o.Cin,
                                              so.R, s, fuse_ptr, fe->d_packed + so.packed_off);
                 if (!sums_only) release(kt);
             } else if (need_dx) {

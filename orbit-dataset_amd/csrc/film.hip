@@ -6,9 +6,11 @@
 // all generators run in ONE grouped launch: block (gen, chunk) recomputes the 64-wide hidden vector
 // (4 K MACs) and produces up to 256 outputs, writing straight into the concatenated gamma'/beta'
 // vectors that the extractor's BatchNorm folding consumes.
+#include <cstring>
 #include <string>
 #include <vector>
 #include "common.h"
+#include "param_pool.h"
 
 namespace orbit {
 
@@ -198,23 +200,17 @@ using namespace orbit;
 struct orbit_filmgen {
     int n_gen = 0, z_dim = 0, hid = 0, max_out = 0;
     std::vector<GenDesc> gens;
-    size_t pool_floats = 0;
-    float* d_pool = nullptr;
+    ParamPool pool{4};  // tensor t of generator i is parameter 8 i + t, keyed "<i>.<name>"
     GenDesc* d_gens = nullptr;
-    // orbit_filmgen_load_all_async: device table of source pointers + (offset, numel) of each destination
-    const float** d_src = nullptr;
-    size_t* d_dst_meta = nullptr;
-    std::vector<const float*> h_src;
     float* d_dzp = nullptr;  // [n_gen][z_dim]: per-generator dz of orbit_filmgen_backward (calls are stream-ordered by the caller)
 };
 
-// one kernel copies every generator tensor into the pool: grid (chunks, tensors)
-__global__ __launch_bounds__(256) void filmgen_gather_kernel(const float* const* __restrict__ src,
-                                                             const size_t* __restrict__ meta, float* __restrict__ pool) {
-    const float* s_ = src[blockIdx.y];
-    float* d = pool + meta[2 * blockIdx.y];
-    const size_t n = meta[2 * blockIdx.y + 1];
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) d[i] = s_[i];
+// the tensors of one generator, in the order of GenDesc's offsets and of orbit_filmgen_load_all_async's pointer list
+static const char* const FILM_TENSORS[8] = {"w1", "b1", "ln_w", "ln_b", "w2", "b2", "reg", "init"};
+static int film_tensor(const char* name) {
+    for (int t = 0; t < 8; ++t)
+        if (strcmp(name, FILM_TENSORS[t]) == 0) return t;
+    return -1;
 }
 
 extern "C" {
@@ -226,30 +222,26 @@ int orbit_filmgen_create(int n_gen, int z_dim, int hidden, const int* out_size, 
                   "filmgen_create: bad sizes (n_gen=%d z=%d hid=%d)", n_gen, z_dim, hidden);
     orbit_filmgen* g = new orbit_filmgen();
     g->n_gen = n_gen, g->z_dim = z_dim, g->hid = hidden;
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        size_t o = off;
-        off += (n + 3) / 4 * 4;
-        return o;
-    };
+    g->pool.owner = "filmgen";
     for (int i = 0; i < n_gen; ++i) {
         GenDesc d;
         d.out = out_size[i], d.kind = kind[i], d.dst = dst_offset[i];
-        d.w1 = take((size_t)hidden * z_dim), d.b1 = take(hidden), d.ln_w = take(hidden), d.ln_b = take(hidden);
-        d.w2 = take((size_t)d.out * hidden), d.b2 = take(d.out), d.reg = take(d.out), d.init = take(d.out);
+        const size_t h = hidden, o = d.out;
+        const size_t numel[8] = {h * z_dim, h, h, h, o * h, o, o, o};
+        size_t* const off[8] = {&d.w1, &d.b1, &d.ln_w, &d.ln_b, &d.w2, &d.b2, &d.reg, &d.init};
+        for (int t = 0; t < 8; ++t) *off[t] = g->pool.off(g->pool.add(std::to_string(i) + "." + FILM_TENSORS[t], numel[t]));
         g->gens.push_back(d);
         if (d.out > g->max_out) g->max_out = d.out;
     }
-    g->pool_floats = off;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->d_pool), off * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(g->d_pool, 0, off * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&g->d_gens), sizeof(GenDesc) * n_gen);
-    if (e == hipSuccess) e = hipMemcpy(g->d_gens, g->gens.data(), sizeof(GenDesc) * n_gen, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(g->d_pool);
-        (void)hipFree(g->d_gens);
-        delete g;
-        return set_err(ORBIT_ERR_HIP, "filmgen_create: %s", hipGetErrorString(e));
+    int rc = g->pool.ensure_device();
+    if (rc == ORBIT_OK) {
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&g->d_gens), sizeof(GenDesc) * n_gen);
+        if (e == hipSuccess) e = hipMemcpy(g->d_gens, g->gens.data(), sizeof(GenDesc) * n_gen, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = set_err(ORBIT_ERR_HIP, "filmgen_create: %s", hipGetErrorString(e));
+    }
+    if (rc != ORBIT_OK) {
+        orbit_filmgen_destroy(g);
+        return rc;
     }
     *out = g;
     return ORBIT_OK;
@@ -257,10 +249,8 @@ int orbit_filmgen_create(int n_gen, int z_dim, int hidden, const int* out_size, 
 
 void orbit_filmgen_destroy(orbit_filmgen_t* g) {
     if (!g) return;
-    (void)hipFree(g->d_pool);
+    g->pool.free_device();
     (void)hipFree(g->d_gens);
-    (void)hipFree(g->d_src);
-    (void)hipFree(g->d_dst_meta);
     (void)hipFree(g->d_dzp);
     delete g;
 }
@@ -268,52 +258,18 @@ void orbit_filmgen_destroy(orbit_filmgen_t* g) {
 int orbit_filmgen_load(orbit_filmgen_t* g, int gen, const char* tensor, const float* data, size_t numel) {
     ORBIT_REQUIRE(g && tensor && data, "filmgen_load: null pointer");
     ORBIT_REQUIRE(gen >= 0 && gen < g->n_gen, "filmgen_load: generator %d out of range", gen);
-    const GenDesc& d = g->gens[gen];
-    const std::string t(tensor);
-    size_t off = 0, expect = 0;
-    if (t == "w1") off = d.w1, expect = (size_t)g->hid * g->z_dim;
-    else if (t == "b1") off = d.b1, expect = g->hid;
-    else if (t == "ln_w") off = d.ln_w, expect = g->hid;
-    else if (t == "ln_b") off = d.ln_b, expect = g->hid;
-    else if (t == "w2") off = d.w2, expect = (size_t)d.out * g->hid;
-    else if (t == "b2") off = d.b2, expect = d.out;
-    else if (t == "reg") off = d.reg, expect = d.out;
-    else if (t == "init") off = d.init, expect = d.out;
-    else return set_err(ORBIT_ERR_ARG, "filmgen_load: unknown tensor '%s'", tensor);
+    const int t = film_tensor(tensor);
+    ORBIT_REQUIRE(t >= 0, "filmgen_load: unknown tensor '%s'", tensor);
+    const size_t expect = g->pool.numel(8 * gen + t);
     ORBIT_REQUIRE(numel == expect, "filmgen_load: %s of generator %d has %zu elements, expected %zu", tensor,
                   gen, numel, expect);
-    ORBIT_HIP_CHECK(hipMemcpy(g->d_pool + off, data, numel * sizeof(float), hipMemcpyDefault));
-    return ORBIT_OK;
+    return g->pool.load("filmgen_load", g->pool.name(8 * gen + t), data, numel);
 }
 
 int orbit_filmgen_load_all_async(orbit_filmgen_t* g, const float* const* device_ptrs, int n, orbit_stream_t stream) {
     ORBIT_REQUIRE(g && device_ptrs, "filmgen_load_all_async: null pointer");
     ORBIT_REQUIRE(n == 8 * g->n_gen, "filmgen_load_all_async: %d pointers for %d generators x 8 tensors", n, g->n_gen);
-    hipStream_t s = (hipStream_t)stream;
-    if (!g->d_src) {
-        ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->d_src), n * sizeof(float*)));
-        ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->d_dst_meta), 2 * n * sizeof(size_t)));
-        std::vector<size_t> meta(2 * n);
-        for (int i = 0; i < g->n_gen; ++i) {
-            const GenDesc& d = g->gens[i];
-            const size_t off[8] = {d.w1, d.b1, d.ln_w, d.ln_b, d.w2, d.b2, d.reg, d.init};
-            const size_t num[8] = {(size_t)g->hid * g->z_dim, (size_t)g->hid, (size_t)g->hid, (size_t)g->hid,
-                                   (size_t)d.out * g->hid, (size_t)d.out, (size_t)d.out, (size_t)d.out};
-            for (int t = 0; t < 8; ++t) meta[2 * (8 * i + t)] = off[t], meta[2 * (8 * i + t) + 1] = num[t];
-        }
-        ORBIT_HIP_CHECK(hipMemcpy(g->d_dst_meta, meta.data(), meta.size() * sizeof(size_t), hipMemcpyHostToDevice));
-    }
-    bool same = (int)g->h_src.size() == n;
-    for (int i = 0; same && i < n; ++i) same = g->h_src[i] == device_ptrs[i];
-    if (!same) {  // the tensors moved: refresh the pointer table (an earlier gather on this stream may still read it)
-        for (int i = 0; i < n; ++i) ORBIT_REQUIRE(device_ptrs[i], "filmgen_load_all_async: null tensor %d", i);
-        g->h_src.assign(device_ptrs, device_ptrs + n);
-        ORBIT_HIP_CHECK(hipStreamSynchronize(s));
-        ORBIT_HIP_CHECK(hipMemcpy(g->d_src, g->h_src.data(), n * sizeof(float*), hipMemcpyHostToDevice));
-    }
-    filmgen_gather_kernel<<<dim3(4, n), 256, 0, s>>>(g->d_src, g->d_dst_meta, g->d_pool);
-    ORBIT_LAUNCH_CHECK();
-    return ORBIT_OK;
+    return g->pool.load_all_async("filmgen_load_all_async", device_ptrs, n, 4, (hipStream_t)stream);
 }
 
 int orbit_filmgen_forward(orbit_filmgen_t* g, const float* z, float* film_gamma, float* film_beta, float* l2,
@@ -321,29 +277,21 @@ int orbit_filmgen_forward(orbit_filmgen_t* g, const float* z, float* film_gamma,
     ORBIT_REQUIRE(g && z && film_gamma && film_beta, "filmgen_forward: null pointer");
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(g->n_gen, cdiv(g->max_out, 256));
-    filmgen_kernel<<<grid, 256, 0, s>>>(g->d_gens, g->d_pool, z, g->z_dim, g->hid, film_gamma, film_beta);
+    filmgen_kernel<<<grid, 256, 0, s>>>(g->d_gens, g->pool.d_pool, z, g->z_dim, g->hid, film_gamma, film_beta);
     ORBIT_LAUNCH_CHECK();
     if (l2) {
-        film_l2_kernel<<<1, 256, 0, s>>>(g->d_gens, g->n_gen, g->d_pool, l2);
+        film_l2_kernel<<<1, 256, 0, s>>>(g->d_gens, g->n_gen, g->pool.d_pool, l2);
         ORBIT_LAUNCH_CHECK();
     }
     return ORBIT_OK;
 }
 
-size_t orbit_filmgen_grad_floats(const orbit_filmgen_t* g) { return g ? g->pool_floats : 0; }
+size_t orbit_filmgen_grad_floats(const orbit_filmgen_t* g) { return g ? g->pool.pool_floats : 0; }
 
 size_t orbit_filmgen_param_offset(const orbit_filmgen_t* g, int gen, const char* tensor) {
     if (!g || !tensor || gen < 0 || gen >= g->n_gen) return (size_t)-1;
-    const GenDesc& d = g->gens[gen];
-    const std::string t(tensor);
-    if (t == "w1") return d.w1;
-    if (t == "b1") return d.b1;
-    if (t == "ln_w") return d.ln_w;
-    if (t == "ln_b") return d.ln_b;
-    if (t == "w2") return d.w2;
-    if (t == "b2") return d.b2;
-    if (t == "reg") return d.reg;
-    return (size_t)-1;
+    const int t = film_tensor(tensor);
+    return (t >= 0 && t < 7) ? g->pool.off(8 * gen + t) : (size_t)-1;  // (`init` is not a parameter: it has no gradient slot)
 }
 
 int orbit_filmgen_backward(orbit_filmgen_t* g, const float* z, const float* dfilm_gamma, const float* dfilm_beta,
@@ -354,7 +302,7 @@ int orbit_filmgen_backward(orbit_filmgen_t* g, const float* z, const float* dfil
     // the 31 ms CNAPs step were spent inside this call)
     if (g->d_dzp == nullptr) ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g->d_dzp), (size_t)g->n_gen * g->z_dim * sizeof(float)));
     float* dzp = g->d_dzp;
-    filmgen_bwd_kernel<<<g->n_gen, 256, (size_t)g->max_out * sizeof(float), s>>>(g->d_gens, g->d_pool, z, g->z_dim, g->hid,
+    filmgen_bwd_kernel<<<g->n_gen, 256, (size_t)g->max_out * sizeof(float), s>>>(g->d_gens, g->pool.d_pool, z, g->z_dim, g->hid,
                                                                                 dfilm_gamma, dfilm_beta, dl2, grads, dzp);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && dz) {

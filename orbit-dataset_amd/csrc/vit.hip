@@ -21,11 +21,11 @@
 //   vit_attention_kernel one workgroup per (frame, head): Q, K, V (50 x 64) in LDS, S = QK^T / 8, row softmax, O = PV.
 #include <cmath>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "common.h"
 #include "device_util.h"
+#include "param_pool.h"
 
 using namespace orbit;
 
@@ -208,11 +208,14 @@ __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
 }
 
 // tile_rows: 0 = the rule below, 64 / 128 = that instantiation (the single-operator entry points; the forward passes 0)
+int check_tile_rows(int tile_rows) {
+    ORBIT_REQUIRE(tile_rows == 0 || tile_rows == 64 || tile_rows == 128, "vit gemm: tile_rows must be 0, 64 or 128, got %d", tile_rows);
+    return ORBIT_OK;
+}
 template <int EPI, bool BLOCKED = false>
 int launch_gemm(const GemmArgs& a, const char* what, hipStream_t s, int tile_rows = 0) {
     if (a.N % G_BN || a.K % G_BK || a.M <= 0) return set_err(ORBIT_ERR_ARG, "vit gemm: unsupported shape M=%d N=%d K=%d", a.M, a.N, a.K);
-    if (tile_rows != 0 && tile_rows != 64 && tile_rows != 128)
-        return set_err(ORBIT_ERR_ARG, "vit gemm: tile_rows must be 0, 64 or 128, got %d", tile_rows);
+    if (int rc = check_tile_rows(tile_rows)) return rc;
     // tile height: 128 rows unless that leaves fewer than two tiles per CU (the D x D and 4D x D layers at ~10k rows)
     const int n_tiles = a.N / G_BN;
     const bool tall = tile_rows ? tile_rows == 128 : (long)cdiv(a.M, 128) * n_tiles >= 512;
@@ -238,6 +241,14 @@ __global__ __launch_bounds__(256) void vit_cls_kernel(const float* __restrict__ 
         const int b = (int)(i / D), d = (int)(i - (size_t)b * D);
         tokens[(size_t)b * VIT_N * D + d] = cls[d] + pos[d];
     }
+}
+
+int launch_cls_token(const float* cls, const float* pos, float* tokens, int B, int D, hipStream_t s) {
+    const int pi = prof_start("vit_cls_token", 0.0, 4.0 * B * D, s);
+    vit_cls_kernel<<<cdiv(B * D, 256) < 1024 ? cdiv(B * D, 256) : 1024, 256, 0, s>>>(cls, pos, tokens, B, D);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
 }
 
 // ---- LayerNorm -------------------------------------------------------------------------------------------------------
@@ -324,6 +335,14 @@ __global__ __launch_bounds__(256) void vit_attention_kernel(const float* __restr
     }
 }
 
+int launch_attention(const float* qkv, float* out, int B, int D, int heads, hipStream_t s) {
+    const int pi = prof_start("vit_attention", 4.0 * B * heads * VIT_N * VIT_N * VIT_HD, 4.0 * 4 * (double)B * VIT_N * D, s);
+    vit_attention_kernel<<<B * heads, 256, 0, s>>>(qkv, out, D, heads);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
 // ---- backward kernels (frozen network: data gradients and the per-slot LayerNorm dgamma / dbeta) -----------------------
 // in [R][C] -> out [C][R] with the library's transpose (csrc/ops.hip): the K-contiguous copy of a Linear weight that the
 // data-gradient GEMM reads. Runs once per parameter upload, not per step.
@@ -335,7 +354,7 @@ int vit_transpose(const float* in, float* out, int R, int C, hipStream_t s) {
 }
 
 // qkv [B*50][3D], dout [B*50][D] (gradient of the attention output) -> dqkv [B*50][3D] (the [B][50][3][heads][64] layout of
-// qkv). One workgroup per (frame, head) as the forward; S and P are recomputed by the forward's own code, then
+// qkv). One workgroup per (frame, head) as the forward; S and P are recomputed by a copy of the forward's code (keep the two in step), then
 //   dV = P^T dO,  dP = dO V^T,  dS = P o (dP - rowsum(dP o P)) (in place over P),  dQ = dS K / 8,  dK = dS^T Q / 8.
 // LDS: Q, dO 50 x 64, K, V 50 x 65, P 50 x 52 floats = 62 016 bytes with alignment: two workgroups (8 waves) per CU of 160 KB - the same
 // two-per-SIMD occupancy the 256-thread forward reaches with its 46 KB; the kernel is LDS-latency bound either way.
@@ -414,7 +433,7 @@ int launch_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B
 }
 
 // LayerNorm backward, one wave per row with the row in registers, 64 rows per block (16 per wave, interleaved). mean / rstd
-// are recomputed by the forward's own code (mean by division, see vit_layernorm_kernel).
+// are recomputed by a copy of the forward's code that must be kept in step with it (mean by division, see vit_layernorm_kernel).
 //   xhat = (x - mean) rstd,  g = dy o gamma,  dx = rstd (g - mean(g) - xhat mean(g o xhat))  [+ dres]
 // dx == nullptr: no data gradient (block 0's norm1). dres may alias dx. With dx_stride > D (the final norm: token 0 of every
 // frame carries a gradient, the other 49 tokens none) only the D floats of each row are written: the caller zeroes the stream.
@@ -524,56 +543,45 @@ int launch_layernorm_bwd(const float* x, size_t xs, const float* dy, size_t dys,
 }  // namespace
 
 // ---- plan ------------------------------------------------------------------------------------------------------------
+constexpr size_t VIT_ABSENT = SIZE_MAX;
+struct VitBlock {  // pool offsets (floats) of a block's twelve tensors, in state_dict order
+    size_t norm1_w, norm1_b, qkv_w, qkv_b, proj_w, proj_b, norm2_w, norm2_b, fc1_w, fc1_b, fc2_w, fc2_b;
+};
 struct orbit_vit {
-    struct Param {
-        std::string key;
-        size_t numel, off;
-        bool loaded = false;
-    };
     std::string name;
     int D = 0, heads = 0, mlp = 0;
     float eps = 1e-6f;
     bool clip = false;  // pre_norm: no patch-embedding bias, norm_pre after the position add
-    std::vector<Param> params;
-    std::unordered_map<std::string, int> index;
+    ParamPool pool{64};  // the parameters by state_dict key (csrc/param_pool.h); 256-byte aligned tensors (float4 loads)
+    // where the forward and the backward find each tensor: pool offsets, fixed by orbit_vit_create
+    size_t cls = 0, pos = 0, patch_w = 0, patch_b = VIT_ABSENT, pre_w = VIT_ABSENT, pre_b = VIT_ABSENT, norm_w = 0, norm_b = 0;
+    VitBlock blk[VIT_DEPTH];
     std::vector<std::string> film_names;  // FiLM slots (LayerNorm module names), D channels each
-    size_t pool_floats = 0;
-    float* d_pool = nullptr;
-    const float** d_src = nullptr;
-    size_t* d_meta = nullptr;
-    std::vector<const float*> h_src;
     bool finalized = false;
     double macs = 0;
-    // K-contiguous transposed copies of the qkv / proj / fc1 / fc2 weights (12 D^2 floats per block) for the data-gradient
-    // GEMMs: made by the first orbit_vit_backward after a parameter upload, never by inference
+    // K-contiguous transposed copies of the qkv / proj / fc1 / fc2 weights (vit_wt) for the data-gradient GEMMs: made by the
+    // first orbit_vit_backward after a parameter upload, never by inference
     float* d_wt = nullptr;
     bool wt_valid = false;
 
-    int add(const std::string& key, size_t numel) {
-        index[key] = (int)params.size();
-        params.push_back({key, numel, pool_floats});
-        pool_floats += (numel + 63) / 64 * 64;  // 256-byte aligned tensors (float4 loads)
-        return (int)params.size() - 1;
-    }
-    const float* p(const std::string& key) const { return d_pool + params[index.at(key)].off; }
-    int ensure_device() {
-        if (!d_pool) ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_pool), pool_floats * sizeof(float)));
-        return ORBIT_OK;
-    }
+    const float* p(size_t off) const { return off == VIT_ABSENT ? nullptr : pool.d_pool + off; }
 };
 
 namespace {
 
+// one buffer layout for both directions: the token stream (forward) or the gradient stream (backward) [M][D], a D-wide and a
+// 4D-wide scratch, and for the backward the LayerNorm partial sums behind them
 struct VitWs {
-    size_t x, h, big, total;
+    size_t x, h, big, partial, total;
 };
-VitWs vit_ws(const orbit_vit* v, int B) {
+VitWs vit_ws(const orbit_vit* v, int B, bool backward) {
     const size_t M = (size_t)B * VIT_N;
     VitWs L;
     L.x = 0;
     L.h = align_up(M * v->D * sizeof(float), 256);
     L.big = L.h + align_up(M * v->D * sizeof(float), 256);
-    L.total = L.big + align_up(M * v->mlp * sizeof(float), 256);
+    L.partial = L.big + align_up(M * v->mlp * sizeof(float), 256);
+    L.total = L.partial + (backward ? align_up(layernorm_bwd_partial_floats((int)M, v->D) * sizeof(float), 256) : 0);
     return L;
 }
 
@@ -590,26 +598,28 @@ VitTape vit_tape(const orbit_vit* v, int B) {
     T.total = T.last + md;
     return T;
 }
-struct VitBwdWs {
-    size_t dx, h, big, partial, total;
+
+// the transposed weights of one block inside d_wt: qkv^T [D][3D], proj^T [D][D], fc1^T [D][4D], fc2^T [4D][D] (float offsets)
+struct VitWt {
+    size_t qkv, proj, fc1, fc2, block;
 };
-VitBwdWs vit_bwd_ws(const orbit_vit* v, int B) {
-    const size_t M = (size_t)B * VIT_N;
-    VitBwdWs L;
-    L.dx = 0;
-    L.h = align_up(M * v->D * sizeof(float), 256);
-    L.big = L.h + align_up(M * v->D * sizeof(float), 256);
-    L.partial = L.big + align_up(M * v->mlp * sizeof(float), 256);
-    L.total = L.partial + align_up(layernorm_bwd_partial_floats((int)M, v->D) * sizeof(float), 256);
-    return L;
+VitWt vit_wt(const orbit_vit* v) {
+    const size_t DD = (size_t)v->D * v->D;
+    return {0, 3 * DD, 4 * DD, 8 * DD, 12 * DD};
 }
 
-__global__ __launch_bounds__(256) void vit_gather_params_kernel(const float* const* __restrict__ src,
-                                                                const size_t* __restrict__ meta, float* __restrict__ pool) {
-    const float* s_ = src[blockIdx.y];
-    float* d = pool + meta[2 * blockIdx.y];
-    const size_t n = meta[2 * blockIdx.y + 1];
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) d[i] = s_[i];
+// what the three whole-network entry points refuse alike (their own null pointers are checked before, with the same text)
+int vit_check_call(const char* who, const orbit_vit* v, int B, const float* film_gamma, const float* film_beta) {
+    ORBIT_REQUIRE(v, "%s: null pointer", who);
+    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "%s: batch of %d frames (1..%d)", who, B, VIT_MAX_B);
+    if (!v->finalized) return set_err(ORBIT_ERR_STATE, "%s: call orbit_vit_finalize first", who);
+    ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr), "%s: film_gamma and film_beta must be given together", who);
+    return ORBIT_OK;
+}
+int vit_check_buffer(const char* who, const char* what, const void* ptr, size_t bytes, size_t need) {
+    ORBIT_REQUIRE(bytes >= need, "%s: %s too small (%zu < %zu bytes)", who, what, bytes, need);
+    ORBIT_REQUIRE(((uintptr_t)ptr & 255) == 0, "%s: %s must be 256-byte aligned", who, what);
+    return ORBIT_OK;
 }
 
 }  // namespace
@@ -629,25 +639,27 @@ int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out) {
     ORBIT_REQUIRE(H == VIT_SIZE && W == VIT_SIZE, "vit_create: %s runs on %dx%d frames only (fixed position table), got %dx%d",
                   name, VIT_SIZE, VIT_SIZE, H, W);
     orbit_vit* v = new orbit_vit();
-    v->name = n, v->D = D, v->heads = heads, v->mlp = 4 * D, v->clip = clip, v->eps = clip ? 1e-5f : 1e-6f;
+    v->name = n, v->pool.owner = n, v->D = D, v->heads = heads, v->mlp = 4 * D, v->clip = clip, v->eps = clip ? 1e-5f : 1e-6f;
+    auto add = [&](const std::string& key, size_t numel) { return v->pool.off(v->pool.add(key, numel)); };
     // timm 0.6.12 VisionTransformer state_dict order
-    v->add("cls_token", D);
-    v->add("pos_embed", (size_t)VIT_N * D);
-    v->add("patch_embed.proj.weight", (size_t)D * VIT_KPATCH);
-    if (!clip) v->add("patch_embed.proj.bias", D);
-    if (clip) v->add("norm_pre.weight", D), v->add("norm_pre.bias", D);
+    v->cls = add("cls_token", D);
+    v->pos = add("pos_embed", (size_t)VIT_N * D);
+    v->patch_w = add("patch_embed.proj.weight", (size_t)D * VIT_KPATCH);
+    if (!clip) v->patch_b = add("patch_embed.proj.bias", D);
+    if (clip) v->pre_w = add("norm_pre.weight", D), v->pre_b = add("norm_pre.bias", D);
     for (int i = 0; i < VIT_DEPTH; ++i) {
         const std::string b = "blocks." + std::to_string(i);
-        v->add(b + ".norm1.weight", D), v->add(b + ".norm1.bias", D);
-        v->add(b + ".attn.qkv.weight", (size_t)3 * D * D), v->add(b + ".attn.qkv.bias", 3 * D);
-        v->add(b + ".attn.proj.weight", (size_t)D * D), v->add(b + ".attn.proj.bias", D);
-        v->add(b + ".norm2.weight", D), v->add(b + ".norm2.bias", D);
-        v->add(b + ".mlp.fc1.weight", (size_t)4 * D * D), v->add(b + ".mlp.fc1.bias", 4 * D);
-        v->add(b + ".mlp.fc2.weight", (size_t)4 * D * D), v->add(b + ".mlp.fc2.bias", D);
+        VitBlock& k = v->blk[i];
+        k.norm1_w = add(b + ".norm1.weight", D), k.norm1_b = add(b + ".norm1.bias", D);
+        k.qkv_w = add(b + ".attn.qkv.weight", (size_t)3 * D * D), k.qkv_b = add(b + ".attn.qkv.bias", 3 * D);
+        k.proj_w = add(b + ".attn.proj.weight", (size_t)D * D), k.proj_b = add(b + ".attn.proj.bias", D);
+        k.norm2_w = add(b + ".norm2.weight", D), k.norm2_b = add(b + ".norm2.bias", D);
+        k.fc1_w = add(b + ".mlp.fc1.weight", (size_t)4 * D * D), k.fc1_b = add(b + ".mlp.fc1.bias", 4 * D);
+        k.fc2_w = add(b + ".mlp.fc2.weight", (size_t)4 * D * D), k.fc2_b = add(b + ".mlp.fc2.bias", D);
         v->film_names.push_back(b + ".norm1");
         v->film_names.push_back(b + ".norm2");
     }
-    v->add("norm.weight", D), v->add("norm.bias", D);
+    v->norm_w = add("norm.weight", D), v->norm_b = add("norm.bias", D);
     v->film_names.push_back("norm");
     const double Dd = D;
     v->macs = (double)VIT_P * VIT_KPATCH * Dd + VIT_DEPTH * (VIT_N * 12.0 * Dd * Dd + 2.0 * VIT_N * VIT_N * Dd);
@@ -657,71 +669,33 @@ int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out) {
 
 void orbit_vit_destroy(orbit_vit_t* v) {
     if (!v) return;
-    (void)hipFree(v->d_pool);
-    (void)hipFree(v->d_src);
-    (void)hipFree(v->d_meta);
+    v->pool.free_device();
     (void)hipFree(v->d_wt);
     delete v;
 }
 
-int orbit_vit_num_params(const orbit_vit_t* v) { return v ? (int)v->params.size() : 0; }
-const char* orbit_vit_param_name(const orbit_vit_t* v, int i) {
-    return (v && i >= 0 && i < (int)v->params.size()) ? v->params[i].key.c_str() : nullptr;
-}
-size_t orbit_vit_param_numel(const orbit_vit_t* v, int i) {
-    return (v && i >= 0 && i < (int)v->params.size()) ? v->params[i].numel : 0;
-}
+int orbit_vit_num_params(const orbit_vit_t* v) { return v ? v->pool.size() : 0; }
+const char* orbit_vit_param_name(const orbit_vit_t* v, int i) { return v ? v->pool.name(i) : nullptr; }
+size_t orbit_vit_param_numel(const orbit_vit_t* v, int i) { return v ? v->pool.numel(i) : 0; }
 
+// every upload invalidates the finalized state and the transposed weights of the backward
 int orbit_vit_load(orbit_vit_t* v, const char* key, const float* data, size_t numel) {
     ORBIT_REQUIRE(v && key && data, "vit_load: null pointer");
-    auto it = v->index.find(key);
-    ORBIT_REQUIRE(it != v->index.end(), "vit_load: unexpected key '%s' for %s", key, v->name.c_str());
-    auto& p = v->params[it->second];
-    ORBIT_REQUIRE(p.numel == numel, "vit_load: '%s' has %zu elements, expected %zu", key, numel, p.numel);
-    if (int rc = v->ensure_device()) return rc;
-    ORBIT_HIP_CHECK(hipMemcpy(v->d_pool + p.off, data, numel * sizeof(float), hipMemcpyDefault));
-    p.loaded = true;
+    if (int rc = v->pool.load("vit_load", key, data, numel)) return rc;
     v->finalized = false, v->wt_valid = false;
     return ORBIT_OK;
 }
 
 int orbit_vit_load_async(orbit_vit_t* v, const char* key, const float* device_data, size_t numel, orbit_stream_t stream) {
     ORBIT_REQUIRE(v && key && device_data, "vit_load_async: null pointer");
-    auto it = v->index.find(key);
-    ORBIT_REQUIRE(it != v->index.end(), "vit_load_async: unexpected key '%s' for %s", key, v->name.c_str());
-    auto& p = v->params[it->second];
-    ORBIT_REQUIRE(p.numel == numel, "vit_load_async: '%s' has %zu elements, expected %zu", key, numel, p.numel);
-    if (int rc = v->ensure_device()) return rc;
-    ORBIT_HIP_CHECK(hipMemcpyAsync(v->d_pool + p.off, device_data, numel * sizeof(float), hipMemcpyDeviceToDevice,
-                                   (hipStream_t)stream));
-    p.loaded = true;
+    if (int rc = v->pool.load_async("vit_load_async", key, device_data, numel, (hipStream_t)stream)) return rc;
     v->finalized = false, v->wt_valid = false;
     return ORBIT_OK;
 }
 
 int orbit_vit_load_all_async(orbit_vit_t* v, const float* const* device_ptrs, int n, orbit_stream_t stream) {
     ORBIT_REQUIRE(v && device_ptrs, "vit_load_all_async: null pointer");
-    ORBIT_REQUIRE(n == (int)v->params.size(), "vit_load_all_async: %d pointers for %zu parameters", n, v->params.size());
-    if (int rc = v->ensure_device()) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (!v->d_src) {
-        ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&v->d_src), n * sizeof(float*)));
-        ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&v->d_meta), 2 * n * sizeof(size_t)));
-        std::vector<size_t> meta(2 * n);
-        for (int i = 0; i < n; ++i) meta[2 * i] = v->params[i].off, meta[2 * i + 1] = v->params[i].numel;
-        ORBIT_HIP_CHECK(hipMemcpy(v->d_meta, meta.data(), meta.size() * sizeof(size_t), hipMemcpyHostToDevice));
-    }
-    bool same = (int)v->h_src.size() == n;
-    for (int i = 0; same && i < n; ++i) same = v->h_src[i] == device_ptrs[i];
-    if (!same) {
-        for (int i = 0; i < n; ++i) ORBIT_REQUIRE(device_ptrs[i], "vit_load_all_async: null tensor %d", i);
-        v->h_src.assign(device_ptrs, device_ptrs + n);
-        ORBIT_HIP_CHECK(hipStreamSynchronize(s));  // the table may still be read by an earlier gather on this stream
-        ORBIT_HIP_CHECK(hipMemcpy(v->d_src, v->h_src.data(), n * sizeof(float*), hipMemcpyHostToDevice));
-    }
-    vit_gather_params_kernel<<<dim3(32, n), 256, 0, s>>>(v->d_src, v->d_meta, v->d_pool);
-    ORBIT_LAUNCH_CHECK();
-    for (auto& p : v->params) p.loaded = true;
+    if (int rc = v->pool.load_all_async("vit_load_all_async", device_ptrs, n, 32, (hipStream_t)stream)) return rc;
     v->finalized = false, v->wt_valid = false;
     return ORBIT_OK;
 }
@@ -729,7 +703,8 @@ int orbit_vit_load_all_async(orbit_vit_t* v, const float* const* device_ptrs, in
 int orbit_vit_finalize(orbit_vit_t* v, orbit_stream_t stream) {
     (void)stream;  // the kernels read the torch layouts as loaded: nothing to repack
     ORBIT_REQUIRE(v, "vit_finalize: null pointer");
-    for (const auto& p : v->params) ORBIT_REQUIRE(p.loaded, "vit_finalize: parameter '%s' was never loaded", p.key.c_str());
+    const char* missing = nullptr;
+    ORBIT_REQUIRE(v->pool.all_loaded(&missing), "vit_finalize: parameter '%s' was never loaded", missing);
     v->finalized = true;
     return ORBIT_OK;
 }
@@ -745,7 +720,7 @@ const char* orbit_vit_film_slot_name(const orbit_vit_t* v, int slot) {
 int orbit_vit_film_size(const orbit_vit_t* v) { return v ? (int)v->film_names.size() * v->D : 0; }
 size_t orbit_vit_workspace_bytes(const orbit_vit_t* v, int B) {
     if (!v || B <= 0 || B > VIT_MAX_B) return 0;
-    return vit_ws(v, B).total;
+    return vit_ws(v, B, false).total;
 }
 double orbit_vit_macs_per_frame(const orbit_vit_t* v) { return v ? v->macs : 0.0; }
 
@@ -758,7 +733,7 @@ namespace {
 // and fc1 stores its pre-activation beside GELU(u) (EPI_GELU_TAPE): the features are bitwise those of the inference forward.
 int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta, float* feats,
                      void* workspace, char* tape, hipStream_t s) {
-    const VitWs L = vit_ws(v, B);
+    const VitWs L = vit_ws(v, B, false);
     const VitTape T = vit_tape(v, B);
     const int D = v->D, M = B * VIT_N;
     char* ws = static_cast<char*>(workspace);
@@ -766,72 +741,64 @@ int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* fi
     float* x = tape ? slot(0, T.x) : reinterpret_cast<float*>(ws + L.x);
     float* h = reinterpret_cast<float*>(ws + L.h);
     float* big = reinterpret_cast<float*>(ws + L.big);
-    auto ln_params = [&](const std::string& mod, int slot, const float** g, const float** b) {
-        if (film_gamma && slot >= 0) *g = film_gamma + (size_t)slot * D, *b = film_beta + (size_t)slot * D;
-        else *g = v->p(mod + ".weight"), *b = v->p(mod + ".bias");
+    // LayerNorm of FiLM slot `slot`: the per-task vectors when given, else the module's own weight / bias
+    auto ln_params = [&](size_t w, size_t b, int slot, const float** g, const float** be) {
+        if (film_gamma) *g = film_gamma + (size_t)slot * D, *be = film_beta + (size_t)slot * D;
+        else *g = v->p(w), *be = v->p(b);
     };
     int rc;
     {   // tokens: patch embedding (+ bias) + pos_embed into rows 1..49, cls_token + pos_embed[0] into row 0
-        GemmArgs a{frames, v->p("patch_embed.proj.weight"), v->clip ? nullptr : v->p("patch_embed.proj.bias"), nullptr,
-                   v->p("pos_embed"), x, B * VIT_P, D, VIT_KPATCH};
+        GemmArgs a{frames, v->p(v->patch_w), v->p(v->patch_b), nullptr, v->p(v->pos), x, B * VIT_P, D, VIT_KPATCH};
         if ((rc = launch_gemm<EPI_PATCH>(a, "patch_embed", s))) return rc;
-        const int pi = prof_start("vit_cls_token", 0.0, 4.0 * B * D, s);
-        vit_cls_kernel<<<cdiv(B * D, 256) < 1024 ? cdiv(B * D, 256) : 1024, 256, 0, s>>>(v->p("cls_token"), v->p("pos_embed"),
-                                                                                         x, B, D);
-        prof_stop(pi, s);
-        ORBIT_LAUNCH_CHECK();
-        if (v->clip && (rc = launch_layernorm(x, D, x, D, M, D, v->p("norm_pre.weight"), v->p("norm_pre.bias"), v->eps, s)))
-            return rc;
+        if ((rc = launch_cls_token(v->p(v->cls), v->p(v->pos), x, B, D, s))) return rc;
+        if (v->clip && (rc = launch_layernorm(x, D, x, D, M, D, v->p(v->pre_w), v->p(v->pre_b), v->eps, s))) return rc;
     }
     for (int i = 0; i < VIT_DEPTH; ++i) {
-        const std::string b = "blocks." + std::to_string(i);
+        const VitBlock& k = v->blk[i];
         float* qkvb = tape ? slot(i, T.qkv) : big;
         float* xmid = tape ? slot(i, T.mid) : x;
         float* xout = tape ? slot(i + 1, T.x) : x;
         const float *g, *be;
-        ln_params(b + ".norm1", 2 * i, &g, &be);
+        ln_params(k.norm1_w, k.norm1_b, 2 * i, &g, &be);
         if ((rc = launch_layernorm(x, D, h, D, M, D, g, be, v->eps, s))) return rc;
-        GemmArgs qkv{h, v->p(b + ".attn.qkv.weight"), v->p(b + ".attn.qkv.bias"), nullptr, nullptr, qkvb, M, 3 * D, D};
+        GemmArgs qkv{h, v->p(k.qkv_w), v->p(k.qkv_b), nullptr, nullptr, qkvb, M, 3 * D, D};
         if ((rc = launch_gemm<EPI_BIAS>(qkv, "qkv", s))) return rc;
-        const int pi = prof_start("vit_attention", 4.0 * B * v->heads * VIT_N * VIT_N * VIT_HD,
-                                  4.0 * 4 * (double)M * D, s);
-        vit_attention_kernel<<<B * v->heads, 256, 0, s>>>(qkvb, h, D, v->heads);
-        prof_stop(pi, s);
-        ORBIT_LAUNCH_CHECK();
-        GemmArgs proj{h, v->p(b + ".attn.proj.weight"), v->p(b + ".attn.proj.bias"), x, nullptr, xmid, M, D, D};
+        if ((rc = launch_attention(qkvb, h, B, D, v->heads, s))) return rc;
+        GemmArgs proj{h, v->p(k.proj_w), v->p(k.proj_b), x, nullptr, xmid, M, D, D};
         if ((rc = launch_gemm<EPI_RESIDUAL>(proj, "proj", s))) return rc;
-        ln_params(b + ".norm2", 2 * i + 1, &g, &be);
+        ln_params(k.norm2_w, k.norm2_b, 2 * i + 1, &g, &be);
         if ((rc = launch_layernorm(xmid, D, h, D, M, D, g, be, v->eps, s))) return rc;
-        GemmArgs fc1{h, v->p(b + ".mlp.fc1.weight"), v->p(b + ".mlp.fc1.bias"), nullptr, nullptr, big, M, 4 * D, D};
+        GemmArgs fc1{h, v->p(k.fc1_w), v->p(k.fc1_b), nullptr, nullptr, big, M, 4 * D, D};
         if (tape) {
             fc1.aux = slot(i, T.u);
             if ((rc = launch_gemm<EPI_GELU_TAPE>(fc1, "fc1", s))) return rc;
         } else if ((rc = launch_gemm<EPI_GELU>(fc1, "fc1", s))) {
             return rc;
         }
-        GemmArgs fc2{big, v->p(b + ".mlp.fc2.weight"), v->p(b + ".mlp.fc2.bias"), xmid, nullptr, xout, M, D, 4 * D};
+        GemmArgs fc2{big, v->p(k.fc2_w), v->p(k.fc2_b), xmid, nullptr, xout, M, D, 4 * D};
         if ((rc = launch_gemm<EPI_RESIDUAL>(fc2, "fc2", s))) return rc;
         x = xout;
     }
     const float *g, *be;
-    ln_params("norm", 2 * VIT_DEPTH, &g, &be);
+    ln_params(v->norm_w, v->norm_b, 2 * VIT_DEPTH, &g, &be);
     // final LayerNorm on the class token of every frame, straight into the caller's feature rows
     return launch_layernorm(x, (size_t)VIT_N * D, feats, D, B, D, g, be, v->eps, s);
 }
 
 // (re)build the transposed weights on `s` if a parameter upload invalidated them
 int vit_ensure_wt(orbit_vit_t* v, hipStream_t s) {
-    const size_t D = v->D, per_block = 12 * D * D;
-    if (!v->d_wt) ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&v->d_wt), VIT_DEPTH * per_block * sizeof(float)));
+    const VitWt W = vit_wt(v);
+    const int D = v->D;
+    if (!v->d_wt) ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&v->d_wt), VIT_DEPTH * W.block * sizeof(float)));
     if (v->wt_valid) return ORBIT_OK;
     int rc;
     for (int i = 0; i < VIT_DEPTH; ++i) {
-        const std::string b = "blocks." + std::to_string(i);
-        float* wt = v->d_wt + i * per_block;  // qkv^T [D][3D], proj^T [D][D], fc1^T [D][4D], fc2^T [4D][D]
-        if ((rc = vit_transpose(v->p(b + ".attn.qkv.weight"), wt, 3 * v->D, v->D, s))) return rc;
-        if ((rc = vit_transpose(v->p(b + ".attn.proj.weight"), wt + 3 * D * D, v->D, v->D, s))) return rc;
-        if ((rc = vit_transpose(v->p(b + ".mlp.fc1.weight"), wt + 4 * D * D, 4 * v->D, v->D, s))) return rc;
-        if ((rc = vit_transpose(v->p(b + ".mlp.fc2.weight"), wt + 8 * D * D, v->D, 4 * v->D, s))) return rc;
+        const VitBlock& k = v->blk[i];
+        float* wt = v->d_wt + i * W.block;
+        if ((rc = vit_transpose(v->p(k.qkv_w), wt + W.qkv, 3 * D, D, s))) return rc;
+        if ((rc = vit_transpose(v->p(k.proj_w), wt + W.proj, D, D, s))) return rc;
+        if ((rc = vit_transpose(v->p(k.fc1_w), wt + W.fc1, 4 * D, D, s))) return rc;
+        if ((rc = vit_transpose(v->p(k.fc2_w), wt + W.fc2, D, 4 * D, s))) return rc;
     }
     v->wt_valid = true;
     return ORBIT_OK;
@@ -843,15 +810,11 @@ extern "C" {
 
 int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
                       float* feats, void* workspace, size_t workspace_bytes, orbit_stream_t stream) {
-    ORBIT_REQUIRE(v && frames && feats && workspace, "vit_forward: null pointer");
-    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "vit_forward: batch of %d frames (1..%d)", B, VIT_MAX_B);
-    if (!v->finalized) return set_err(ORBIT_ERR_STATE, "vit_forward: call orbit_vit_finalize first");
-    ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr),
-                  "vit_forward: film_gamma and film_beta must be given together");
-    const VitWs L = vit_ws(v, B);
-    ORBIT_REQUIRE(workspace_bytes >= L.total, "vit_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, L.total);
-    ORBIT_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)frames & 15) == 0,
-                  "vit_forward: workspace must be 256-byte and frames 16-byte aligned");
+    const char* who = "vit_forward";
+    ORBIT_REQUIRE(frames && feats && workspace, "%s: null pointer", who);
+    if (int rc = vit_check_call(who, v, B, film_gamma, film_beta)) return rc;
+    if (int rc = vit_check_buffer(who, "workspace", workspace, workspace_bytes, vit_ws(v, B, false).total)) return rc;
+    ORBIT_REQUIRE(((uintptr_t)frames & 15) == 0, "%s: frames must be 16-byte aligned", who);
     return vit_forward_impl(v, frames, B, film_gamma, film_beta, feats, workspace, nullptr, (hipStream_t)stream);
 }
 
@@ -862,86 +825,74 @@ size_t orbit_vit_tape_bytes(const orbit_vit_t* v, int B) {
 }
 size_t orbit_vit_backward_workspace_bytes(const orbit_vit_t* v, int B) {
     if (!v || B <= 0 || B > VIT_MAX_B) return 0;
-    return vit_bwd_ws(v, B).total;
+    return vit_ws(v, B, true).total;
 }
 
 int orbit_vit_train_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
                             float* feats, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
                             orbit_stream_t stream) {
-    ORBIT_REQUIRE(v && frames && feats && tape && workspace, "vit_train_forward: null pointer");
-    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "vit_train_forward: batch of %d frames (1..%d)", B, VIT_MAX_B);
-    if (!v->finalized) return set_err(ORBIT_ERR_STATE, "vit_train_forward: call orbit_vit_finalize first");
-    ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr),
-                  "vit_train_forward: film_gamma and film_beta must be given together");
-    const VitWs L = vit_ws(v, B);
-    const VitTape T = vit_tape(v, B);
-    ORBIT_REQUIRE(workspace_bytes >= L.total, "vit_train_forward: workspace too small (%zu < %zu bytes)", workspace_bytes,
-                  L.total);
-    ORBIT_REQUIRE(tape_bytes >= T.total, "vit_train_forward: tape too small (%zu < %zu bytes)", tape_bytes, T.total);
-    ORBIT_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)tape & 255) == 0 && ((uintptr_t)frames & 15) == 0,
-                  "vit_train_forward: workspace and tape must be 256-byte and frames 16-byte aligned");
+    const char* who = "vit_train_forward";
+    ORBIT_REQUIRE(frames && feats && tape && workspace, "%s: null pointer", who);
+    if (int rc = vit_check_call(who, v, B, film_gamma, film_beta)) return rc;
+    if (int rc = vit_check_buffer(who, "workspace", workspace, workspace_bytes, vit_ws(v, B, false).total)) return rc;
+    if (int rc = vit_check_buffer(who, "tape", tape, tape_bytes, vit_tape(v, B).total)) return rc;
+    ORBIT_REQUIRE(((uintptr_t)frames & 15) == 0, "%s: frames must be 16-byte aligned", who);
     return vit_forward_impl(v, frames, B, film_gamma, film_beta, feats, workspace, static_cast<char*>(tape), (hipStream_t)stream);
 }
 
 int orbit_vit_backward(orbit_vit_t* v, int B, const float* film_gamma, const float* film_beta, const float* dfeats,
                        const void* tape, size_t tape_bytes, float* dgamma, float* dbeta, void* workspace,
                        size_t workspace_bytes, orbit_stream_t stream) {
-    ORBIT_REQUIRE(v && dfeats && tape && dgamma && dbeta && workspace, "vit_backward: null pointer");
-    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "vit_backward: batch of %d frames (1..%d)", B, VIT_MAX_B);
-    if (!v->finalized) return set_err(ORBIT_ERR_STATE, "vit_backward: call orbit_vit_finalize first");
-    ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr),
-                  "vit_backward: film_gamma and film_beta must be given together");
-    const VitBwdWs L = vit_bwd_ws(v, B);
+    const char* who = "vit_backward";
+    ORBIT_REQUIRE(dfeats && tape && dgamma && dbeta && workspace, "%s: null pointer", who);
+    if (int rc = vit_check_call(who, v, B, film_gamma, film_beta)) return rc;
+    const VitWs L = vit_ws(v, B, true);
     const VitTape T = vit_tape(v, B);
-    ORBIT_REQUIRE(workspace_bytes >= L.total, "vit_backward: workspace too small (%zu < %zu bytes)", workspace_bytes, L.total);
-    ORBIT_REQUIRE(tape_bytes >= T.total, "vit_backward: tape too small (%zu < %zu bytes)", tape_bytes, T.total);
-    ORBIT_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)tape & 255) == 0,
-                  "vit_backward: workspace and tape must be 256-byte aligned");
+    if (int rc = vit_check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
+    if (int rc = vit_check_buffer(who, "tape", tape, tape_bytes, T.total)) return rc;
     ORBIT_REQUIRE((((uintptr_t)dfeats | (uintptr_t)dgamma | (uintptr_t)dbeta | (uintptr_t)film_gamma) & 3) == 0,
-                  "vit_backward: dfeats, dgamma, dbeta and film_gamma must be 4-byte aligned");
+                  "%s: dfeats, dgamma, dbeta and film_gamma must be 4-byte aligned", who);
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if ((rc = vit_ensure_wt(v, s))) return rc;
+    const VitWt W = vit_wt(v);
     const int D = v->D, M = B * VIT_N;
     char* ws = static_cast<char*>(workspace);
     const char* tp = static_cast<const char*>(tape);
-    float* dx = reinterpret_cast<float*>(ws + L.dx);
+    float* dx = reinterpret_cast<float*>(ws + L.x);
     float* h = reinterpret_cast<float*>(ws + L.h);
     float* big = reinterpret_cast<float*>(ws + L.big);
     float* partial = reinterpret_cast<float*>(ws + L.partial);
     auto slot = [&](int i, size_t off) { return reinterpret_cast<const float*>(tp + i * T.block + off); };
-    auto gamma_of = [&](const std::string& mod, int sl) {
-        return film_gamma ? film_gamma + (size_t)sl * D : v->p(mod + ".weight");
-    };
+    auto gamma_of = [&](size_t w, int sl) { return film_gamma ? film_gamma + (size_t)sl * D : v->p(w); };
     // final norm: token 0 of every frame from dfeats; the other 49 token rows of the gradient stream are exactly zero
     const int last = 2 * VIT_DEPTH;
     if ((rc = zero_gradient_stream(dx, (size_t)M * D, s))) return rc;
-    if ((rc = launch_layernorm_bwd(reinterpret_cast<const float*>(tp + T.last), (size_t)VIT_N * D, dfeats, D, gamma_of("norm", last),
+    if ((rc = launch_layernorm_bwd(reinterpret_cast<const float*>(tp + T.last), (size_t)VIT_N * D, dfeats, D, gamma_of(v->norm_w, last),
                                    v->eps, nullptr, dx, (size_t)VIT_N * D, B, D, partial, dgamma + (size_t)last * D,
                                    dbeta + (size_t)last * D, s)))
         return rc;
-    const size_t DD = (size_t)D * D;
     for (int i = VIT_DEPTH - 1; i >= 0; --i) {
-        const std::string b = "blocks." + std::to_string(i);
-        const float* wt = v->d_wt + i * 12 * DD;  // qkv^T, proj^T, fc1^T, fc2^T (vit_ensure_wt)
+        const VitBlock& k = v->blk[i];
+        const float* wt = v->d_wt + i * W.block;  // (vit_ensure_wt)
         // x_out = x_mid + fc2(GELU(u)):  du = (dx W2) o GELU'(u),  dh = du W1,  dx += LN2'(dh)
-        GemmArgs dfc2{dx, wt + 8 * DD, nullptr, slot(i, T.u), nullptr, big, M, 4 * D, D};
+        GemmArgs dfc2{dx, wt + W.fc2, nullptr, slot(i, T.u), nullptr, big, M, 4 * D, D};
         if ((rc = launch_gemm<EPI_DGELU, true>(dfc2, "dgrad_fc2", s))) return rc;
-        GemmArgs dfc1{big, wt + 4 * DD, nullptr, nullptr, nullptr, h, M, D, 4 * D};
+        GemmArgs dfc1{big, wt + W.fc1, nullptr, nullptr, nullptr, h, M, D, 4 * D};
         if ((rc = launch_gemm<EPI_BIAS, true>(dfc1, "dgrad_fc1", s))) return rc;
         int sl = 2 * i + 1;
-        if ((rc = launch_layernorm_bwd(slot(i, T.mid), D, h, D, gamma_of(b + ".norm2", sl), v->eps, dx, dx, D, M, D, partial,
+        if ((rc = launch_layernorm_bwd(slot(i, T.mid), D, h, D, gamma_of(k.norm2_w, sl), v->eps, dx, dx, D, M, D, partial,
                                        dgamma + (size_t)sl * D, dbeta + (size_t)sl * D, s)))
             return rc;
         // x_mid = x + proj(attn(qkv)):  dO = dx Wp,  dqkv = attn'(dO),  dh = dqkv Wqkv,  dx += LN1'(dh)
-        GemmArgs dproj{dx, wt + 3 * DD, nullptr, nullptr, nullptr, h, M, D, D};
+        GemmArgs dproj{dx, wt + W.proj, nullptr, nullptr, nullptr, h, M, D, D};
         if ((rc = launch_gemm<EPI_BIAS, true>(dproj, "dgrad_proj", s))) return rc;
         if ((rc = launch_attention_bwd(slot(i, T.qkv), h, big, B, D, v->heads, s))) return rc;
-        GemmArgs dqkv{big, wt, nullptr, nullptr, nullptr, h, M, D, 3 * D};
+        GemmArgs dqkv{big, wt + W.qkv, nullptr, nullptr, nullptr, h, M, D, 3 * D};
         if ((rc = launch_gemm<EPI_BIAS, true>(dqkv, "dgrad_qkv", s))) return rc;
         sl = 2 * i;
         // (block 0: nothing upstream of its norm1 takes a gradient - the patch embedding and CLIP's norm_pre are frozen)
-        if ((rc = launch_layernorm_bwd(slot(i, T.x), D, h, D, gamma_of(b + ".norm1", sl), v->eps, dx, i > 0 ? dx : nullptr, D, M,
+        if ((rc = launch_layernorm_bwd(slot(i, T.x), D, h, D, gamma_of(k.norm1_w, sl), v->eps, dx, i > 0 ? dx : nullptr, D, M,
                                        D, partial, dgamma + (size_t)sl * D, dbeta + (size_t)sl * D, s)))
             return rc;
     }
@@ -949,6 +900,7 @@ int orbit_vit_backward(orbit_vit_t* v, int B, const float* film_gamma, const flo
 }
 
 // ---- single operators (parity tests) ---------------------------------------------------------------------------------
+// (tile_rows is validated by launch_gemm, before it launches)
 int orbit_op_vit_linear(const float* x, const float* w, const float* bias, const float* residual, float* y, int M, int N,
                         int K, int epilogue, int tile_rows, orbit_stream_t stream) {
     ORBIT_REQUIRE(x && w && y, "op_vit_linear: null pointer");
@@ -958,8 +910,6 @@ int orbit_op_vit_linear(const float* x, const float* w, const float* bias, const
     ORBIT_REQUIRE(epilogue == EPI_BIAS || epilogue == EPI_GELU || epilogue == EPI_RESIDUAL,
                   "op_vit_linear: epilogue must be 0 (bias), 1 (erf-GELU) or 2 (residual), got %d", epilogue);
     ORBIT_REQUIRE((epilogue == EPI_RESIDUAL) == (residual != nullptr), "op_vit_linear: residual goes with epilogue 2 only");
-    ORBIT_REQUIRE(tile_rows == 0 || tile_rows == 64 || tile_rows == 128, "op_vit_linear: tile_rows must be 0, 64 or 128, got %d",
-                  tile_rows);
     ORBIT_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "op_vit_linear: x and w must be 16-byte aligned");
     ORBIT_REQUIRE(((uintptr_t)y & 3) == 0 && ((uintptr_t)bias & 3) == 0 && ((uintptr_t)residual & 3) == 0,
                   "op_vit_linear: y, bias and residual must be 4-byte aligned");
@@ -975,8 +925,6 @@ int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* b
     ORBIT_REQUIRE(frames && w && pos_embed && cls_token && tokens, "op_vit_patch_embed: null pointer");
     ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "op_vit_patch_embed: batch of %d frames (1..%d)", B, VIT_MAX_B);
     ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_patch_embed: unsupported width %d (384 or 768)", D);
-    ORBIT_REQUIRE(tile_rows == 0 || tile_rows == 64 || tile_rows == 128,
-                  "op_vit_patch_embed: tile_rows must be 0, 64 or 128, got %d", tile_rows);
     ORBIT_REQUIRE(((uintptr_t)frames & 15) == 0 && ((uintptr_t)w & 15) == 0,
                   "op_vit_patch_embed: frames and w must be 16-byte aligned");
     ORBIT_REQUIRE(((uintptr_t)tokens & 3) == 0 && ((uintptr_t)bias_or_null & 3) == 0 && ((uintptr_t)pos_embed & 3) == 0 &&
@@ -985,9 +933,7 @@ int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* b
     hipStream_t s = (hipStream_t)stream;
     const GemmArgs a{frames, w, bias_or_null, nullptr, pos_embed, tokens, B * VIT_P, D, VIT_KPATCH};
     if (int rc = launch_gemm<EPI_PATCH>(a, "op_patch_embed", s, tile_rows)) return rc;
-    vit_cls_kernel<<<cdiv(B * D, 256) < 1024 ? cdiv(B * D, 256) : 1024, 256, 0, s>>>(cls_token, pos_embed, tokens, B, D);
-    ORBIT_LAUNCH_CHECK();
-    return ORBIT_OK;
+    return launch_cls_token(cls_token, pos_embed, tokens, B, D, s);
 }
 
 int orbit_op_vit_layernorm(const float* x, size_t x_stride, float* y, size_t y_stride, int rows, int D, const float* gamma,
@@ -1008,12 +954,7 @@ int orbit_op_vit_attention(const float* qkv, float* out, int B, int D, int heads
     ORBIT_REQUIRE(heads * VIT_HD == D, "op_vit_attention: %d heads of %d do not make D=%d", heads, VIT_HD, D);
     ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "op_vit_attention: batch of %d frames (1..%d)", B, VIT_MAX_B);
     ORBIT_REQUIRE((((uintptr_t)qkv | (uintptr_t)out) & 3) == 0, "op_vit_attention: pointers must be 4-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const int pi = prof_start("vit_attention", 4.0 * B * heads * VIT_N * VIT_N * VIT_HD, 4.0 * 4 * (double)B * VIT_N * D, s);
-    vit_attention_kernel<<<B * heads, 256, 0, s>>>(qkv, out, D, heads);
-    prof_stop(pi, s);
-    ORBIT_LAUNCH_CHECK();
-    return ORBIT_OK;
+    return launch_attention(qkv, out, B, D, heads, (hipStream_t)stream);
 }
 
 int orbit_op_vit_linear_dgrad(const float* dy, const float* w, float* wt_scratch, const float* u, const float* residual,
@@ -1024,8 +965,7 @@ int orbit_op_vit_linear_dgrad(const float* dy, const float* w, float* wt_scratch
                   "op_vit_linear_dgrad: K (the Linear's in_features) must be a multiple of %d and N of %d, got N=%d K=%d", G_BN,
                   G_BK, N, K);
     ORBIT_REQUIRE(!(u && residual), "op_vit_linear_dgrad: either u (times GELU') or residual (accumulate), not both");
-    ORBIT_REQUIRE(tile_rows == 0 || tile_rows == 64 || tile_rows == 128,
-                  "op_vit_linear_dgrad: tile_rows must be 0, 64 or 128, got %d", tile_rows);
+    if (int rc = check_tile_rows(tile_rows)) return rc;  // (here too: the transpose below launches before launch_gemm)
     ORBIT_REQUIRE(((uintptr_t)dy & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)wt_scratch & 15) == 0,
                   "op_vit_linear_dgrad: dy, w and wt_scratch must be 16-byte aligned");
     ORBIT_REQUIRE(((uintptr_t)dx & 3) == 0 && ((uintptr_t)u & 3) == 0 && ((uintptr_t)residual & 3) == 0,
