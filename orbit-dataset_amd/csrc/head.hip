@@ -355,7 +355,10 @@ __global__ __launch_bounds__(256) void proto_predict_lds_kernel(
 // block stages the task's weights into LDS, so the two memory latencies overlap instead of adding, and the dot products run
 // from registers against LDS after the barrier. The 64-task launch (67 MB) is ~8 us of HBM time: what it can lose is
 // exactly such serialised latencies (round 1: W staging -> barrier -> first row load, 2.7 TB/s). Same per-lane accumulation
-// order as proto_predict_lds_kernel (d ascending), hence bit-identical logits.
+// order as proto_predict_lds_kernel (d ascending), but NOT the same bits: inside a quad, x.x w.x + x.y w.y + x.z w.z + x.w w.w
+// is contracted to one rounded product and three FMAs, and which product is the rounded one is the compiler's choice per
+// instantiation (scalar FMAs here, packed math in the LDS form). On an MI355X (5 tasks x 37 x 1280, 5-way) the two forms
+// differ in the last bits; each is held to its fp64 bound, and LEAN to the bits of non-LEAN (tests/test_gpu_head_forms.py).
 // Block -> (task, row block): the hardware deals consecutive block ids round-robin over the 8 XCDs, each with its own L2. A
 // task's weights (C x D floats, 25.6 KB) are staged by every one of its row blocks; dealt round-robin, a task's 13 blocks sat
 // on 8 different XCDs and its weights were fetched from memory 8 times (PMC: 79.3 MB of traffic per 64-task launch against
@@ -531,6 +534,7 @@ int orbit_proto_finalize(const float* sums, const float* counts, int n_tasks, in
     ORBIT_REQUIRE(sums && counts && W, "proto_finalize: null pointer");
     ORBIT_REQUIRE(cosine || b, "proto_finalize: euclidean head needs a bias buffer");
     ORBIT_REQUIRE(n_tasks > 0 && D > 0 && C > 0, "proto_finalize: bad sizes");
+    ORBIT_REQUIRE(n_tasks <= 65535, "proto_finalize: n_tasks too large");  // grid.y
     dim3 grid(C, n_tasks);
     const int rec = prof_start("head_finalize", 3.0 * n_tasks * C * D, (double)n_tasks * 4.0 * (2.0 * C * D + 2.0 * C),
                                (hipStream_t)stream);
@@ -561,9 +565,11 @@ static int proto_predict_impl(const float* Q, const float* W, const float* b, in
     ORBIT_REQUIRE(Q && W && logits, "proto_predict: null pointer");
     ORBIT_REQUIRE(cosine || b, "proto_predict: weight and/or bias not set - is the model personalised?");
     ORBIT_REQUIRE(n_tasks > 0 && M > 0 && T > 0 && D > 0 && C > 0, "proto_predict: bad sizes");
+    ORBIT_REQUIRE(n_tasks <= 65535, "proto_predict: n_tasks too large");  // grid.y of the LDS-staged and the generic form
     hipStream_t s = (hipStream_t)stream;
     // rows per wave: measured on MI355X (64 tasks x 200 x 1280): R = 1 with the row loop unrolled streams faster than
     // R = 4 (more waves in flight beats W reuse: W is L1/L2-resident anyway); the R > 1 forms stay for very wide heads
+    // (the 60 KB limit is below the 64 KB of dynamic LDS a launch gets without hipFuncSetAttribute: no opt-in at any C, D)
     const size_t lds = ((size_t)C * D + C) * sizeof(float);
     if ((D & 3) == 0 && lds <= 60 * 1024 && (long)M * n_tasks >= 64) {
         // head_stream (default 1; 0 = the general LDS form below, parity tests): rows requested before the weight staging, one

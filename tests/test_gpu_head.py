@@ -74,7 +74,8 @@ def test_head_edge_cases(device):
 
 
 def test_head_full_size_properties(device):
-    """At full size (M = 64 tasks x 200 queries, D = 1280) check properties instead of an oracle run:
+    """At full size (ONE task with M = 64 x 200 query rows, D = 1280; batched launches: test_gpu_head_forms.py) check
+    properties instead of an oracle run:
     (i) a query equal to prototype c scores highest on column c with logit mu.mu (euclidean: 2 mu.mu - mu.mu);
     (ii) logits are linear in logit_scale; (iii) permuting the support set leaves W, b unchanged up to fp32
     summation order."""

@@ -278,7 +278,7 @@ def test_avgpool_backward(device):
 # ---- head backward ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cosine", [0, 1])
 @pytest.mark.parametrize("M,T,D,C,scale", [(200, 1, 1280, 5, 1.0), (37, 1, 512, 10, 32.0), (12, 4, 512, 5, 1.0),
-                                           (9, 3, 130, 7, 2.0)])
+                                           (9, 3, 130, 7, 2.0), (37, 1, 512, 17, 1.0), (9, 3, 130, 64, 2.0)])
 def test_proto_predict_backward(device, cosine, M, T, D, C, scale):
     lib = _lib.load()
     g = torch.Generator().manual_seed(M + D + C)
@@ -298,6 +298,19 @@ def test_proto_predict_backward(device, cosine, M, T, D, C, scale):
                                                 _lib.dptr(df), _st()), "proto_predict_backward")
     torch.cuda.synchronize()
     assert rel_err(df.cpu(), feats.grad) < 2e-5
+
+
+def test_proto_predict_backward_refuses_65_classes(device):
+    """The row's dlogits live in the 64 lanes of its wave: C = 65 is an argument error, and nothing is written."""
+    lib = _lib.load()
+    M, D, C = 3, 64, 65
+    dl, f, w = torch.zeros(M, C, device=device), torch.zeros(M, D, device=device), torch.zeros(C, D, device=device)
+    df = torch.full((M, D), 7.0, device=device)
+    rc = lib.orbit_proto_predict_backward(_lib.dptr(dl), _lib.dptr(f), _lib.dptr(w), M, 1, D, C, 1.0, 0, _lib.dptr(df), _st())
+    assert rc == -1  # ORBIT_ERR_ARG
+    assert "proto_predict_backward" in _lib.last_error()
+    torch.cuda.synchronize()
+    assert bool((df == 7.0).all())
 
 
 # ---- MBConv pieces: depthwise convolution and squeeze-excite backward -----------------------------------------------
