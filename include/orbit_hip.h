@@ -220,7 +220,7 @@ int orbit_extractor_forward(orbit_extractor_t* fe, const float* frames, int B,
  * family (orbit_extractor_create rejects these names). H = W = 224 only (reference utils/args.py: --frame_size 224 for
  * these backbones; the position table is fixed). Creation and enumeration do not touch the device. Inference only by default:
  * orbit_vit_train_forward / orbit_vit_backward below give the gradients of the FiLM vectors of the FROZEN network (the reference's
- * --adapt_features recipes); weight gradients (--learn_extractor) are not provided. */
+ * --adapt_features recipes), orbit_vit_backward_params those of every parameter as well (--learn_extractor). */
 int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out);
 void orbit_vit_destroy(orbit_vit_t* v);
 /* timm state_dict keys in timm's order: cls_token, pos_embed, patch_embed.proj.{weight,bias (not CLIP)}, norm_pre.* (CLIP),
@@ -265,6 +265,23 @@ int orbit_vit_train_forward(orbit_vit_t* v, const float* frames, int B, const fl
 int orbit_vit_backward(orbit_vit_t* v, int B, const float* film_gamma, const float* film_beta, const float* dfeats,
                        const void* tape, size_t tape_bytes, float* dgamma, float* dbeta, void* workspace,
                        size_t workspace_bytes, orbit_stream_t stream);
+/* Gradients of every parameter (--learn_extractor), on the tape of orbit_vit_train_forward (unchanged). The flat gradient buffer
+ * follows the orbit_extractor_* convention: orbit_vit_grad_floats floats, parameter i (orbit_vit_param_name order) at
+ * orbit_vit_param_offset(i) in its torch layout, every tensor 256-byte aligned.
+ * orbit_vit_backward_params = orbit_vit_backward (same kernels, same order: dgamma / dbeta are bit for bit what it writes for the
+ * same tape and arguments) that also WRITES param_grads for every parameter except the 50 FiLM-slot LayerNorm weights / biases:
+ * their gradients are dgamma / dbeta, with or without film vectors (with film vectors the modules' own LayerNorm parameters
+ * take no part in the forward), and their slots in param_grads are left untouched. frames: the batch the tape was recorded on
+ * (16-byte aligned; the patch-embedding filter gradient reads it). Per block the X operands that are not on the tape are
+ * recomputed by the forward's kernels; the Linear filter gradients dW [N][K] = dY^T X split their reduction over the token
+ * rows into a number of partial tiles that depends on (rows, N, K) only, added in a fixed order: deterministic, no atomics.
+ * param_grads 256-byte aligned; workspace of orbit_vit_backward_params_workspace_bytes (0 for B outside 1..8192). */
+size_t orbit_vit_grad_floats(const orbit_vit_t* v);
+size_t orbit_vit_param_offset(const orbit_vit_t* v, int i);
+size_t orbit_vit_backward_params_workspace_bytes(const orbit_vit_t* v, int B);
+int orbit_vit_backward_params(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
+                              const float* dfeats, const void* tape, size_t tape_bytes, float* param_grads, float* dgamma,
+                              float* dbeta, void* workspace, size_t workspace_bytes, orbit_stream_t stream);
 
 /* ---- FiLM parameter generator ------------------------------------------------------------------ */
 /* n_gen generators (sorted FiLM-name order). Generator i: Linear(z_dim,hid) -> LayerNorm(hid) -> ReLU ->
@@ -359,6 +376,20 @@ int orbit_op_vit_layernorm_bwd(const float* x, size_t x_stride, const float* dy,
 /* qkv [B][50][3][heads][64], dout [B][50][heads][64] -> dqkv in qkv's layout (gradients of q, k and v). */
 int orbit_op_vit_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int D, int heads,
                                orbit_stream_t stream);
+/* The weight-gradient kernels of orbit_vit_backward_params one by one.
+ * dw [N][K] = dy [M][N]^T . x [M][K] (gelu_on_x = 1: . GELU_erf(x), the fc2 layer, whose tape holds the pre-activation) and,
+ * unless dbias is NULL, dbias [N] = the column sums of dy; both overwritten. N % 128 == 0, K % 32 == 0; every pointer 16-byte
+ * aligned. The reduction over M is split into partial tiles in `workspace` (at least
+ * orbit_op_vit_linear_wgrad_workspace_floats(M, N, K) floats - a function of the shape alone, 0 for a shape the entry point
+ * refuses; NULL allowed when it is 0) that a second launch adds in a fixed order. */
+size_t orbit_op_vit_linear_wgrad_workspace_floats(int M, int N, int K);
+int orbit_op_vit_linear_wgrad(const float* dy, const float* x, float* dw, float* dbias_or_null, int M, int N, int K, int gelu_on_x,
+                              float* workspace, size_t workspace_floats, orbit_stream_t stream);
+/* Backward of orbit_op_vit_patch_embed: frames NCHW [B][3][224][224], dtokens [B][50][D] -> dw OIHW [D][3][32][32], dbias [D]
+ * (NULL: the CLIP form has none) = the sum of token rows 1..49, dpos [50][D] = the sum over frames, dcls [D] = its row 0.
+ * workspace: orbit_op_vit_linear_wgrad_workspace_floats(49 B, D, 3072) floats. */
+int orbit_op_vit_patch_embed_bwd(const float* frames, const float* dtokens, float* dw, float* dbias_or_null, float* dpos,
+                                 float* dcls, int B, int D, float* workspace, size_t workspace_floats, orbit_stream_t stream);
 
 /* fused MBConv front half (EfficientNet InvertedResidual, Cin <= 40): y = silu(bn2(dw_KxK(silu(bn1(x . w1^T))))) with the
  * expanded tensor kept in LDS. x NHWC [B][H][W][Cin]; w1 torch [mid][Cin][1][1]; wdw torch [mid][1][K][K];

@@ -1,7 +1,7 @@
 // Vision-transformer feature extractors (timm 0.6.12 `vit_small_patch32_224_in21k`, `vit_base_patch32_224_in21k`,
 // `vit_base_patch32_224_clip_laion2b`, built with num_classes=0: reference model/feature_extractors.py:49-63), inference only by
 // default; orbit_vit_train_forward / orbit_vit_backward give the gradients of the FiLM vectors (LayerNorm gamma / beta) of the
-// frozen network (second half of this file).
+// frozen network, orbit_vit_backward_params those of every parameter as well (second half of this file).
 //
 // One forward, fp32 throughout (reference: timm VisionTransformer.forward_features + forward_head with global_pool='token'):
 //   tokens[b][0]   = cls_token + pos_embed[0]
@@ -19,6 +19,7 @@
 //   vit_layernorm_kernel one wave per token row, two-pass (mean, centred variance) in registers; gamma / beta from the
 //                        parameter pool or from the per-task FiLM vectors (reference model/film.py:57-66).
 //   vit_attention_kernel one workgroup per (frame, head): Q, K, V (50 x 64) in LDS, S = QK^T / 8, row softmax, O = PV.
+#include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
@@ -65,15 +66,18 @@ __device__ __forceinline__ float gelu_erf_grad(float u) {
     return 0.5f * erfcf(-u * 0.70710678118654752f) + u * 0.39894228040143268f * expf(-0.5f * u * u);
 }
 
+// implicit-GEMM row gather of the patch embedding: element k = c*1024 + kh*32 + kw of patch m % 49 of frame m / 49 (NCHW frames)
+__device__ __forceinline__ const float* patch_row_ptr(const float* frames, int m, int k) {
+    const int b = m / VIT_P, p = m - b * VIT_P;
+    const int ph = p / VIT_GRID, pw = p - ph * VIT_GRID;
+    const int c = k >> 10, kh = (k >> 5) & 31, kw = k & 31;
+    return frames + (((size_t)b * 3 + c) * VIT_SIZE + ph * VIT_PATCH + kh) * VIT_SIZE + pw * VIT_PATCH + kw;
+}
+
 // address of the 4 consecutive k of A row m (clamped into [0, M)) starting at k
 template <int EPI>
 __device__ __forceinline__ const float* a_row_ptr(const GemmArgs& a, int m, int k) {
-    if (EPI == EPI_PATCH) {
-        const int b = m / VIT_P, p = m - b * VIT_P;
-        const int ph = p / VIT_GRID, pw = p - ph * VIT_GRID;
-        const int c = k >> 10, kh = (k >> 5) & 31, kw = k & 31;
-        return a.x + (((size_t)b * 3 + c) * VIT_SIZE + ph * VIT_PATCH + kh) * VIT_SIZE + pw * VIT_PATCH + kw;
-    }
+    if (EPI == EPI_PATCH) return patch_row_ptr(a.x, m, k);
     return a.x + (size_t)m * a.K + k;
 }
 
@@ -540,6 +544,214 @@ int launch_layernorm_bwd(const float* x, size_t xs, const float* dy, size_t dys,
     return ORBIT_OK;
 }
 
+
+// ---- weight gradients (orbit_vit_backward_params) ----------------------------------------------------------------------
+// dW [N][K] = dY^T X, dY [M][N] and X [M][K] row-major: the reduction runs over the token rows, the slow dimension of both
+// operands, so a 32-row step of either is float4 loads along n / k that land in LDS already reduction-major ([m][n], [m][k]) -
+// the layout the MFMA fragment reads of vit_gemm_kernel want, without its transposing scatter. One block owns a 128 (n) x 128 (k)
+// tile of dW and one of `splits` contiguous ranges of 32-row steps (the output is small and M is long: 27 tiles for the ViT-S
+// qkv layer); it writes its partial tile to the workspace and vit_wgrad_reduce_kernel adds the partials in split order. The
+// split count is wgrad_splits(M, N, K), nothing else: results are bitwise reproducible. Inside a split the chain is cut every
+// 256 rows as in the BLOCKED data-gradient GEMMs. Rows past M are never loaded and enter the sums as exact zeros (they would be
+// summed here, not merely left unstored as in the forward). Columns past K (K a multiple of 32, not of 128) likewise.
+//   WX_GELU   X = GELU_erf(u), applied to the loaded registers (fc2: only the pre-activation is on the tape)
+//   WX_PATCH  X = the patches gathered from the NCHW frames (patch_row_ptr), dY row m = token 1 + m % 49 of frame m / 49
+// The bias gradient db [n] = sum_m dY [m][n] is folded into the blocks of k-tile 0, which sum the dY tile they hold in LDS (32
+// rows into a fresh sum per step, steps and 256-row chunks as the accumulators): dY is not read a second time.
+constexpr int W_BT = 128;
+enum { WX_PLAIN = 0, WX_GELU = 1, WX_PATCH = 2 };
+
+struct WgradArgs {
+    const float* dy;
+    const float* x;
+    float* dw;  // [N][K], or with splits > 1 the partial tiles [splits][N][K]
+    float* db;  // nullptr, [N], or with splits > 1 [splits][N]
+    int M, N, K, splits;
+};
+
+// doubles while the grid stays within 512 blocks (two 256-thread blocks per CU) and every split keeps at least four 32-row steps:
+// the split count changes at M = 225, 481, 993, 2017, 4065, ... and nowhere else
+int wgrad_splits(int M, int N, int K) {
+    const long tiles = (long)(N / W_BT) * cdiv(K, W_BT);
+    const int steps = cdiv(M, G_BK);
+    int s = 1;
+    while (2 * s * tiles <= 512 && 8 * s <= steps) s *= 2;
+    return s;
+}
+size_t wgrad_ws_floats(int M, int N, int K) {
+    const int s = wgrad_splits(M, N, K);
+    return s > 1 ? (size_t)s * ((size_t)N * K + N) : 0;
+}
+
+template <int XM>
+__global__ __launch_bounds__(G_THREADS, 2) void vit_wgrad_kernel(WgradArgs a) {
+    constexpr int LD = W_BT + 4;
+    __shared__ __attribute__((aligned(16))) float As[G_BK * LD];  // dY tile [m][n]
+    __shared__ __attribute__((aligned(16))) float Bs[G_BK * LD];  // X tile [m][k]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int k0 = blockIdx.x * W_BT, n0 = blockIdx.y * W_BT, sp = blockIdx.z;
+    const int steps = (a.M + G_BK - 1) / G_BK;
+    const int s_begin = (int)((long)sp * steps / a.splits), s_end = (int)((long)(sp + 1) * steps / a.splits);
+    const int lc = tid & 31, lr = tid >> 5;  // loader: float4 chunk along n / k, and row (lr + 8 i)
+    const bool k_in = k0 + 4 * lc < a.K;
+    const bool bias_block = a.db != nullptr && blockIdx.x == 0;
+
+    floatx16 acc[2][2], tot[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f, tot[i][j][r] = 0.f;
+    float bacc = 0.f, btot = 0.f;
+
+    float4 ra[4], rb[4];
+    auto load = [&](int st) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int m = st * G_BK + lr + 8 * i;
+            ra[i] = rb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (m >= a.M) continue;
+            const size_t dyrow = XM == WX_PATCH ? (size_t)(m / VIT_P) * VIT_N + 1 + m % VIT_P : (size_t)m;
+            ra[i] = *reinterpret_cast<const float4*>(a.dy + dyrow * a.N + n0 + 4 * lc);
+            if (!k_in) continue;
+            const float* xp = XM == WX_PATCH ? patch_row_ptr(a.x, m, k0 + 4 * lc) : a.x + (size_t)m * a.K + k0 + 4 * lc;
+            rb[i] = *reinterpret_cast<const float4*>(xp);
+            if (XM == WX_GELU) rb[i] = make_float4(gelu_erf(rb[i].x), gelu_erf(rb[i].y), gelu_erf(rb[i].z), gelu_erf(rb[i].w));
+        }
+    };
+
+    if (s_begin < s_end) load(s_begin);
+    for (int st = s_begin; st < s_end; ++st) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            *reinterpret_cast<float4*>(&As[(lr + 8 * i) * LD + 4 * lc]) = ra[i];
+            *reinterpret_cast<float4*>(&Bs[(lr + 8 * i) * LD + 4 * lc]) = rb[i];
+        }
+        __syncthreads();
+        if (st + 1 < s_end) load(st + 1);  // next step in flight during the MFMAs
+        const int kh = lane >> 5, col = lane & 31;
+#pragma unroll
+        for (int kk = 0; kk < G_BK / 2; ++kk) {
+            float af[2], bf[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) af[i] = As[(2 * kk + kh) * LD + wm * 64 + 32 * i + col];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bf[j] = Bs[(2 * kk + kh) * LD + wn * 64 + 32 * j + col];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
+        }
+        if (bias_block && tid < W_BT) {  // (waves 0 and 1: wave-uniform)
+            float s = 0.f;
+#pragma unroll
+            for (int r = 0; r < G_BK; ++r) s += As[r * LD + tid];
+            bacc += s;
+        }
+        if (((st - s_begin) & 7) == 7 || st + 1 == s_end) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) tot[i][j][r] += acc[i][j][r], acc[i][j][r] = 0.f;
+            btot += bacc, bacc = 0.f;
+        }
+    }
+
+    // dW[n][k]: C row = n, C col = k (the lanes of a store run along k)
+    float* out = a.dw + (a.splits > 1 ? (size_t)sp * a.N * a.K : 0);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = k0 + wn * 64 + 32 * j + (lane & 31);
+            if (col >= a.K) continue;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = n0 + wm * 64 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                out[(size_t)row * a.K + col] = tot[i][j][r];
+            }
+        }
+    if (bias_block && tid < W_BT) a.db[(a.splits > 1 ? (size_t)sp * a.N : 0) + n0 + tid] = btot;
+}
+
+// part: [splits][nk] then (db) [splits][n]; the splits are added in split order, four consecutive floats per thread
+__global__ __launch_bounds__(256) void vit_wgrad_reduce_kernel(const float* __restrict__ part, int splits, size_t nk, size_t n,
+                                                               float* __restrict__ dw, float* __restrict__ db) {
+    const size_t e = 4 * ((size_t)blockIdx.x * 256 + threadIdx.x);
+    if (e >= nk + (db ? n : 0)) return;
+    const bool w = e < nk;
+    const float* src = w ? part + e : part + splits * nk + (e - nk);
+    const size_t stride = w ? nk : n;
+    float4 acc = *reinterpret_cast<const float4*>(src);
+    for (int s = 1; s < splits; ++s) {
+        const float4 v = *reinterpret_cast<const float4*>(src + s * stride);
+        acc.x += v.x, acc.y += v.y, acc.z += v.z, acc.w += v.w;
+    }
+    *reinterpret_cast<float4*>(w ? dw + e : db + (e - nk)) = acc;
+}
+
+// ws: wgrad_ws_floats(M, N, K) floats, 16-byte aligned (unused when the rule gives one split)
+template <int XM>
+int launch_wgrad(const float* dy, const float* x, float* dw, float* db, int M, int N, int K, float* ws, const char* what,
+                 hipStream_t s) {
+    if (N % W_BT || K % G_BK || M <= 0) return set_err(ORBIT_ERR_ARG, "vit wgrad: unsupported shape M=%d N=%d K=%d", M, N, K);
+    const int splits = wgrad_splits(M, N, K);
+    const size_t nk = (size_t)N * K;
+    WgradArgs a{dy, x, dw, db, M, N, K, splits};
+    if (splits > 1) a.dw = ws, a.db = db ? ws + splits * nk : nullptr;
+    char name[48];
+    snprintf(name, sizeof(name), "vit_%s<%d>", what, splits);
+    int pi = prof_start(name, 2.0 * M * N * K + (db ? (double)M * N : 0.0),
+                        4.0 * ((double)M * N + (double)M * K + (double)splits * (nk + (db ? N : 0))), s);
+    vit_wgrad_kernel<XM><<<dim3(cdiv(K, W_BT), N / W_BT, splits), G_THREADS, 0, s>>>(a);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    if (splits == 1) return ORBIT_OK;
+    const size_t total = nk + (db ? N : 0);
+    pi = prof_start("vit_wgrad_reduce", (double)(splits - 1) * total, 4.0 * (splits + 1) * total, s);
+    vit_wgrad_reduce_kernel<<<(unsigned)((total / 4 + 255) / 256), 256, 0, s>>>(ws, splits, nk, N, dw, db);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
+// gradient stream dx0 [B][50][D] entering the token assembly -> dpos [50][D] = sum_b dx0[b] (frames in ascending order, a fresh
+// sum every 64 frames), dcls [D] = its row 0. (The patch bias gradient, the sum of rows 1..49, is the folded bias of the patch
+// weight-gradient GEMM, which holds exactly those rows in LDS.)
+__global__ __launch_bounds__(256) void vit_token_bwd_kernel(const float* __restrict__ dx0, int B, int D, float* __restrict__ dpos,
+                                                            float* __restrict__ dcls) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const size_t stride = (size_t)VIT_N * D;
+    if (i >= VIT_N * D) return;
+    float tot = 0.f;
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int b1 = b0 + 64 < B ? b0 + 64 : B;
+        float acc = 0.f;
+#pragma unroll 4
+        for (int b = b0; b < b1; ++b) acc += dx0[b * stride + i];
+        tot += acc;
+    }
+    dpos[i] = tot;
+    if (i < D) dcls[i] = tot;
+}
+
+// frames, dx0 -> d patch weight [D][3072], d patch bias [D] (or nullptr: CLIP), d pos_embed [50][D], d cls_token [D]
+int launch_patch_embed_bwd(const float* frames, const float* dx0, float* dw, float* db, float* dpos, float* dcls, int B, int D,
+                           float* ws, hipStream_t s) {
+    if (int rc = launch_wgrad<WX_PATCH>(dx0, frames, dw, db, B * VIT_P, D, VIT_KPATCH, ws, "wgrad_patch_embed", s)) return rc;
+    const int pi = prof_start("vit_token_bwd", (double)B * VIT_N * D, 4.0 * (B + 1) * VIT_N * D, s);
+    vit_token_bwd_kernel<<<cdiv(VIT_N * D, 256), 256, 0, s>>>(dx0, B, D, dpos, dcls);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
 }  // namespace
 
 // ---- plan ------------------------------------------------------------------------------------------------------------
@@ -582,6 +794,25 @@ VitWs vit_ws(const orbit_vit* v, int B, bool backward) {
     L.big = L.h + align_up(M * v->D * sizeof(float), 256);
     L.partial = L.big + align_up(M * v->mlp * sizeof(float), 256);
     L.total = L.partial + (backward ? align_up(layernorm_bwd_partial_floats((int)M, v->D) * sizeof(float), 256) : 0);
+    return L;
+}
+
+// orbit_vit_backward_params: the frozen backward's buffers, one more D-wide buffer (the recomputed X operand of a weight
+// gradient: h is busy holding dh) and the partial tiles of the largest split weight-gradient GEMM
+struct VitWsParams {
+    size_t x, h, h2, big, partial, wgrad, total;
+};
+VitWsParams vit_ws_params(const orbit_vit* v, int B) {
+    const int M = B * VIT_N, D = v->D;
+    const size_t md = align_up((size_t)M * D * sizeof(float), 256);
+    size_t wg = wgrad_ws_floats(B * VIT_P, D, VIT_KPATCH);
+    const int shapes[4][2] = {{D, 4 * D}, {4 * D, D}, {D, D}, {3 * D, D}};  // (N, K) of fc2, fc1, proj, qkv
+    for (const auto& nk : shapes) wg = std::max(wg, wgrad_ws_floats(M, nk[0], nk[1]));
+    VitWsParams L;
+    L.x = 0, L.h = md, L.h2 = 2 * md, L.big = 3 * md;
+    L.partial = L.big + align_up((size_t)M * v->mlp * sizeof(float), 256);
+    L.wgrad = L.partial + align_up(layernorm_bwd_partial_floats(M, D) * sizeof(float), 256);
+    L.total = L.wgrad + align_up(wg * sizeof(float), 256);
     return L;
 }
 
@@ -804,6 +1035,91 @@ int vit_ensure_wt(orbit_vit_t* v, hipStream_t s) {
     return ORBIT_OK;
 }
 
+// the buffers of a reverse pass inside the caller's workspace; h2 and wgrad only with parameter gradients
+struct VitBwdBuffers {
+    float *dx, *h, *h2, *big, *partial, *wgrad;
+};
+
+// The reverse pass. pg == nullptr: the FiLM gradients of the frozen network (orbit_vit_backward). With pg, the flat parameter
+// gradient buffer (pool offsets), the same kernels in the same order compute the same dgamma / dbeta, and between them every
+// Linear layer's weight / bias gradient is taken from its dY and its X operand - on the tape (fc2: GELU of the pre-activation,
+// on load) or recomputed into h2 by the forward's kernel (LN2(x_mid) for fc1, attention(qkv) for proj, LN1(x) for qkv); block
+// 0's norm1 then hands its data gradient on to (CLIP) norm_pre and the token assembly.
+int vit_backward_impl(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
+                      const float* dfeats, const char* tp, float* pg, float* dgamma, float* dbeta, const VitBwdBuffers& b,
+                      hipStream_t s) {
+    int rc;
+    if ((rc = vit_ensure_wt(v, s))) return rc;
+    const VitWt W = vit_wt(v);
+    const VitTape T = vit_tape(v, B);
+    const int D = v->D, M = B * VIT_N;
+    float *dx = b.dx, *h = b.h, *h2 = b.h2, *big = b.big, *partial = b.partial;
+    auto slot = [&](int i, size_t off) { return reinterpret_cast<const float*>(tp + i * T.block + off); };
+    auto gamma_of = [&](size_t w, int sl) { return film_gamma ? film_gamma + (size_t)sl * D : v->p(w); };
+    auto beta_of = [&](size_t w, int sl) { return film_beta ? film_beta + (size_t)sl * D : v->p(w); };
+    // final norm: token 0 of every frame from dfeats; the other 49 token rows of the gradient stream are exactly zero
+    const int last = 2 * VIT_DEPTH;
+    if ((rc = zero_gradient_stream(dx, (size_t)M * D, s))) return rc;
+    if ((rc = launch_layernorm_bwd(reinterpret_cast<const float*>(tp + T.last), (size_t)VIT_N * D, dfeats, D, gamma_of(v->norm_w, last),
+                                   v->eps, nullptr, dx, (size_t)VIT_N * D, B, D, partial, dgamma + (size_t)last * D,
+                                   dbeta + (size_t)last * D, s)))
+        return rc;
+    for (int i = VIT_DEPTH - 1; i >= 0; --i) {
+        const VitBlock& k = v->blk[i];
+        const float* wt = v->d_wt + i * W.block;  // (vit_ensure_wt)
+        // x_out = x_mid + fc2(GELU(u)):  du = (dx W2) o GELU'(u),  dh = du W1,  dx += LN2'(dh)
+        if (pg && (rc = launch_wgrad<WX_GELU>(dx, slot(i, T.u), pg + k.fc2_w, pg + k.fc2_b, M, D, 4 * D, b.wgrad, "wgrad_fc2", s)))
+            return rc;
+        GemmArgs dfc2{dx, wt + W.fc2, nullptr, slot(i, T.u), nullptr, big, M, 4 * D, D};
+        if ((rc = launch_gemm<EPI_DGELU, true>(dfc2, "dgrad_fc2", s))) return rc;
+        int sl = 2 * i + 1;
+        if (pg) {
+            if ((rc = launch_layernorm(slot(i, T.mid), D, h2, D, M, D, gamma_of(k.norm2_w, sl), beta_of(k.norm2_b, sl), v->eps, s)))
+                return rc;
+            if ((rc = launch_wgrad<WX_PLAIN>(big, h2, pg + k.fc1_w, pg + k.fc1_b, M, 4 * D, D, b.wgrad, "wgrad_fc1", s))) return rc;
+        }
+        GemmArgs dfc1{big, wt + W.fc1, nullptr, nullptr, nullptr, h, M, D, 4 * D};
+        if ((rc = launch_gemm<EPI_BIAS, true>(dfc1, "dgrad_fc1", s))) return rc;
+        if ((rc = launch_layernorm_bwd(slot(i, T.mid), D, h, D, gamma_of(k.norm2_w, sl), v->eps, dx, dx, D, M, D, partial,
+                                       dgamma + (size_t)sl * D, dbeta + (size_t)sl * D, s)))
+            return rc;
+        // x_mid = x + proj(attn(qkv)):  dO = dx Wp,  dqkv = attn'(dO),  dh = dqkv Wqkv,  dx += LN1'(dh)
+        if (pg) {
+            if ((rc = launch_attention(slot(i, T.qkv), h2, B, D, v->heads, s))) return rc;
+            if ((rc = launch_wgrad<WX_PLAIN>(dx, h2, pg + k.proj_w, pg + k.proj_b, M, D, D, b.wgrad, "wgrad_proj", s))) return rc;
+        }
+        GemmArgs dproj{dx, wt + W.proj, nullptr, nullptr, nullptr, h, M, D, D};
+        if ((rc = launch_gemm<EPI_BIAS, true>(dproj, "dgrad_proj", s))) return rc;
+        if ((rc = launch_attention_bwd(slot(i, T.qkv), h, big, B, D, v->heads, s))) return rc;
+        sl = 2 * i;
+        if (pg) {
+            if ((rc = launch_layernorm(slot(i, T.x), D, h2, D, M, D, gamma_of(k.norm1_w, sl), beta_of(k.norm1_b, sl), v->eps, s)))
+                return rc;
+            if ((rc = launch_wgrad<WX_PLAIN>(big, h2, pg + k.qkv_w, pg + k.qkv_b, M, 3 * D, D, b.wgrad, "wgrad_qkv", s))) return rc;
+        }
+        GemmArgs dqkv{big, wt + W.qkv, nullptr, nullptr, nullptr, h, M, D, 3 * D};
+        if ((rc = launch_gemm<EPI_BIAS, true>(dqkv, "dgrad_qkv", s))) return rc;
+        // (block 0 of the frozen network: nothing upstream of its norm1 takes a gradient)
+        if ((rc = launch_layernorm_bwd(slot(i, T.x), D, h, D, gamma_of(k.norm1_w, sl), v->eps, dx, i > 0 || pg ? dx : nullptr, D, M,
+                                       D, partial, dgamma + (size_t)sl * D, dbeta + (size_t)sl * D, s)))
+            return rc;
+    }
+    if (!pg) return ORBIT_OK;
+    const float* dx0 = dx;
+    if (v->clip) {
+        // norm_pre ran in place: its input tokens are rebuilt from the frames (patch GEMM + class-token row) into h2
+        GemmArgs a{frames, v->p(v->patch_w), v->p(v->patch_b), nullptr, v->p(v->pos), h2, B * VIT_P, D, VIT_KPATCH};
+        if ((rc = launch_gemm<EPI_PATCH>(a, "patch_embed", s))) return rc;
+        if ((rc = launch_cls_token(v->p(v->cls), v->p(v->pos), h2, B, D, s))) return rc;
+        if ((rc = launch_layernorm_bwd(h2, D, dx, D, v->p(v->pre_w), v->eps, nullptr, h, D, M, D, partial, pg + v->pre_w,
+                                       pg + v->pre_b, s)))
+            return rc;
+        dx0 = h;
+    }
+    return launch_patch_embed_bwd(frames, dx0, pg + v->patch_w, v->patch_b == VIT_ABSENT ? nullptr : pg + v->patch_b, pg + v->pos,
+                                  pg + v->cls, B, D, b.wgrad, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -847,56 +1163,44 @@ int orbit_vit_backward(orbit_vit_t* v, int B, const float* film_gamma, const flo
     ORBIT_REQUIRE(dfeats && tape && dgamma && dbeta && workspace, "%s: null pointer", who);
     if (int rc = vit_check_call(who, v, B, film_gamma, film_beta)) return rc;
     const VitWs L = vit_ws(v, B, true);
-    const VitTape T = vit_tape(v, B);
     if (int rc = vit_check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
-    if (int rc = vit_check_buffer(who, "tape", tape, tape_bytes, T.total)) return rc;
+    if (int rc = vit_check_buffer(who, "tape", tape, tape_bytes, vit_tape(v, B).total)) return rc;
     ORBIT_REQUIRE((((uintptr_t)dfeats | (uintptr_t)dgamma | (uintptr_t)dbeta | (uintptr_t)film_gamma) & 3) == 0,
                   "%s: dfeats, dgamma, dbeta and film_gamma must be 4-byte aligned", who);
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = vit_ensure_wt(v, s))) return rc;
-    const VitWt W = vit_wt(v);
-    const int D = v->D, M = B * VIT_N;
     char* ws = static_cast<char*>(workspace);
-    const char* tp = static_cast<const char*>(tape);
-    float* dx = reinterpret_cast<float*>(ws + L.x);
-    float* h = reinterpret_cast<float*>(ws + L.h);
-    float* big = reinterpret_cast<float*>(ws + L.big);
-    float* partial = reinterpret_cast<float*>(ws + L.partial);
-    auto slot = [&](int i, size_t off) { return reinterpret_cast<const float*>(tp + i * T.block + off); };
-    auto gamma_of = [&](size_t w, int sl) { return film_gamma ? film_gamma + (size_t)sl * D : v->p(w); };
-    // final norm: token 0 of every frame from dfeats; the other 49 token rows of the gradient stream are exactly zero
-    const int last = 2 * VIT_DEPTH;
-    if ((rc = zero_gradient_stream(dx, (size_t)M * D, s))) return rc;
-    if ((rc = launch_layernorm_bwd(reinterpret_cast<const float*>(tp + T.last), (size_t)VIT_N * D, dfeats, D, gamma_of(v->norm_w, last),
-                                   v->eps, nullptr, dx, (size_t)VIT_N * D, B, D, partial, dgamma + (size_t)last * D,
-                                   dbeta + (size_t)last * D, s)))
-        return rc;
-    for (int i = VIT_DEPTH - 1; i >= 0; --i) {
-        const VitBlock& k = v->blk[i];
-        const float* wt = v->d_wt + i * W.block;  // (vit_ensure_wt)
-        // x_out = x_mid + fc2(GELU(u)):  du = (dx W2) o GELU'(u),  dh = du W1,  dx += LN2'(dh)
-        GemmArgs dfc2{dx, wt + W.fc2, nullptr, slot(i, T.u), nullptr, big, M, 4 * D, D};
-        if ((rc = launch_gemm<EPI_DGELU, true>(dfc2, "dgrad_fc2", s))) return rc;
-        GemmArgs dfc1{big, wt + W.fc1, nullptr, nullptr, nullptr, h, M, D, 4 * D};
-        if ((rc = launch_gemm<EPI_BIAS, true>(dfc1, "dgrad_fc1", s))) return rc;
-        int sl = 2 * i + 1;
-        if ((rc = launch_layernorm_bwd(slot(i, T.mid), D, h, D, gamma_of(k.norm2_w, sl), v->eps, dx, dx, D, M, D, partial,
-                                       dgamma + (size_t)sl * D, dbeta + (size_t)sl * D, s)))
-            return rc;
-        // x_mid = x + proj(attn(qkv)):  dO = dx Wp,  dqkv = attn'(dO),  dh = dqkv Wqkv,  dx += LN1'(dh)
-        GemmArgs dproj{dx, wt + W.proj, nullptr, nullptr, nullptr, h, M, D, D};
-        if ((rc = launch_gemm<EPI_BIAS, true>(dproj, "dgrad_proj", s))) return rc;
-        if ((rc = launch_attention_bwd(slot(i, T.qkv), h, big, B, D, v->heads, s))) return rc;
-        GemmArgs dqkv{big, wt + W.qkv, nullptr, nullptr, nullptr, h, M, D, 3 * D};
-        if ((rc = launch_gemm<EPI_BIAS, true>(dqkv, "dgrad_qkv", s))) return rc;
-        sl = 2 * i;
-        // (block 0: nothing upstream of its norm1 takes a gradient - the patch embedding and CLIP's norm_pre are frozen)
-        if ((rc = launch_layernorm_bwd(slot(i, T.x), D, h, D, gamma_of(k.norm1_w, sl), v->eps, dx, i > 0 ? dx : nullptr, D, M,
-                                       D, partial, dgamma + (size_t)sl * D, dbeta + (size_t)sl * D, s)))
-            return rc;
-    }
-    return ORBIT_OK;
+    const VitBwdBuffers b{reinterpret_cast<float*>(ws + L.x), reinterpret_cast<float*>(ws + L.h), nullptr,
+                          reinterpret_cast<float*>(ws + L.big), reinterpret_cast<float*>(ws + L.partial), nullptr};
+    return vit_backward_impl(v, nullptr, B, film_gamma, film_beta, dfeats, static_cast<const char*>(tape), nullptr, dgamma, dbeta,
+                             b, (hipStream_t)stream);
+}
+
+// ---- gradients of every parameter --------------------------------------------------------------------------------------
+size_t orbit_vit_grad_floats(const orbit_vit_t* v) { return v ? v->pool.pool_floats : 0; }
+size_t orbit_vit_param_offset(const orbit_vit_t* v, int i) { return (v && i >= 0 && i < v->pool.size()) ? v->pool.off(i) : 0; }
+size_t orbit_vit_backward_params_workspace_bytes(const orbit_vit_t* v, int B) {
+    if (!v || B <= 0 || B > VIT_MAX_B) return 0;
+    return vit_ws_params(v, B).total;
+}
+
+int orbit_vit_backward_params(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
+                              const float* dfeats, const void* tape, size_t tape_bytes, float* param_grads, float* dgamma,
+                              float* dbeta, void* workspace, size_t workspace_bytes, orbit_stream_t stream) {
+    const char* who = "vit_backward_params";
+    ORBIT_REQUIRE(frames && dfeats && tape && param_grads && dgamma && dbeta && workspace, "%s: null pointer", who);
+    if (int rc = vit_check_call(who, v, B, film_gamma, film_beta)) return rc;
+    const VitWsParams L = vit_ws_params(v, B);
+    if (int rc = vit_check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
+    if (int rc = vit_check_buffer(who, "tape", tape, tape_bytes, vit_tape(v, B).total)) return rc;
+    ORBIT_REQUIRE(((uintptr_t)frames & 15) == 0, "%s: frames must be 16-byte aligned", who);
+    ORBIT_REQUIRE(((uintptr_t)param_grads & 255) == 0, "%s: param_grads must be 256-byte aligned", who);
+    ORBIT_REQUIRE((((uintptr_t)dfeats | (uintptr_t)dgamma | (uintptr_t)dbeta | (uintptr_t)film_gamma | (uintptr_t)film_beta) & 3) == 0,
+                  "%s: dfeats, dgamma, dbeta and the film vectors must be 4-byte aligned", who);
+    char* ws = static_cast<char*>(workspace);
+    const VitBwdBuffers b{reinterpret_cast<float*>(ws + L.x), reinterpret_cast<float*>(ws + L.h), reinterpret_cast<float*>(ws + L.h2),
+                          reinterpret_cast<float*>(ws + L.big), reinterpret_cast<float*>(ws + L.partial),
+                          reinterpret_cast<float*>(ws + L.wgrad)};
+    return vit_backward_impl(v, frames, B, film_gamma, film_beta, dfeats, static_cast<const char*>(tape), param_grads, dgamma,
+                             dbeta, b, (hipStream_t)stream);
 }
 
 // ---- single operators (parity tests) ---------------------------------------------------------------------------------
@@ -1011,6 +1315,42 @@ int orbit_op_vit_attention_bwd(const float* qkv, const float* dout, float* dqkv,
     ORBIT_REQUIRE((((uintptr_t)qkv | (uintptr_t)dout | (uintptr_t)dqkv) & 3) == 0,
                   "op_vit_attention_bwd: pointers must be 4-byte aligned");
     return launch_attention_bwd(qkv, dout, dqkv, B, D, heads, (hipStream_t)stream);
+}
+
+size_t orbit_op_vit_linear_wgrad_workspace_floats(int M, int N, int K) {
+    if (M <= 0 || M > VIT_MAX_B * VIT_N || N <= 0 || K <= 0 || N % W_BT || K % G_BK) return 0;
+    return wgrad_ws_floats(M, N, K);
+}
+
+int orbit_op_vit_linear_wgrad(const float* dy, const float* x, float* dw, float* dbias_or_null, int M, int N, int K, int gelu_on_x,
+                              float* workspace, size_t workspace_floats, orbit_stream_t stream) {
+    ORBIT_REQUIRE(dy && x && dw, "op_vit_linear_wgrad: null pointer");
+    ORBIT_REQUIRE(M > 0 && M <= VIT_MAX_B * VIT_N && N > 0 && K > 0, "op_vit_linear_wgrad: bad shape M=%d N=%d K=%d", M, N, K);
+    ORBIT_REQUIRE(N % W_BT == 0 && K % G_BK == 0, "op_vit_linear_wgrad: N must be a multiple of %d and K of %d, got N=%d K=%d",
+                  W_BT, G_BK, N, K);
+    ORBIT_REQUIRE(gelu_on_x == 0 || gelu_on_x == 1, "op_vit_linear_wgrad: gelu_on_x must be 0 or 1, got %d", gelu_on_x);
+    const size_t need = wgrad_ws_floats(M, N, K);
+    ORBIT_REQUIRE(workspace || need == 0, "op_vit_linear_wgrad: null pointer");
+    ORBIT_REQUIRE(workspace_floats >= need, "op_vit_linear_wgrad: workspace too small (%zu < %zu floats)", workspace_floats, need);
+    ORBIT_REQUIRE((((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw | (uintptr_t)dbias_or_null | (uintptr_t)workspace) & 15) == 0,
+                  "op_vit_linear_wgrad: dy, x, dw, dbias and workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (gelu_on_x) return launch_wgrad<WX_GELU>(dy, x, dw, dbias_or_null, M, N, K, workspace, "op_wgrad_gelu", s);
+    return launch_wgrad<WX_PLAIN>(dy, x, dw, dbias_or_null, M, N, K, workspace, "op_wgrad", s);
+}
+
+int orbit_op_vit_patch_embed_bwd(const float* frames, const float* dtokens, float* dw, float* dbias_or_null, float* dpos,
+                                 float* dcls, int B, int D, float* workspace, size_t workspace_floats, orbit_stream_t stream) {
+    ORBIT_REQUIRE(frames && dtokens && dw && dpos && dcls, "op_vit_patch_embed_bwd: null pointer");
+    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "op_vit_patch_embed_bwd: batch of %d frames (1..%d)", B, VIT_MAX_B);
+    ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_patch_embed_bwd: unsupported width %d (384 or 768)", D);
+    const size_t need = wgrad_ws_floats(B * VIT_P, D, VIT_KPATCH);
+    ORBIT_REQUIRE(workspace || need == 0, "op_vit_patch_embed_bwd: null pointer");
+    ORBIT_REQUIRE(workspace_floats >= need, "op_vit_patch_embed_bwd: workspace too small (%zu < %zu floats)", workspace_floats, need);
+    ORBIT_REQUIRE((((uintptr_t)frames | (uintptr_t)dtokens | (uintptr_t)dw | (uintptr_t)dbias_or_null | (uintptr_t)workspace) & 15) == 0,
+                  "op_vit_patch_embed_bwd: frames, dtokens, dw, dbias and workspace must be 16-byte aligned");
+    ORBIT_REQUIRE((((uintptr_t)dpos | (uintptr_t)dcls) & 3) == 0, "op_vit_patch_embed_bwd: dpos and dcls must be 4-byte aligned");
+    return launch_patch_embed_bwd(frames, dtokens, dw, dbias_or_null, dpos, dcls, B, D, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

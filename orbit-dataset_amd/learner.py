@@ -55,6 +55,9 @@ def build_parser():
                    help="vit_* extractors: opt in to the native FiLM gradients through the FROZEN transformer (--adapt_features "
                         "training, with or without --with_lite; the multi-step finetuner's --adapt_features). --learn_extractor "
                         "stays refused: weight gradients are not built")
+    p.add_argument("--vit_native_weight_backward", action="store_true",
+                   help="vit_* extractors: opt in to the native gradients of every parameter of the transformer (implies what "
+                        "--vit_native_backward admits, and admits --learn_extractor). Ignored for the other extractors")
     p.add_argument("--num_lite_samples", type=int, default=16)
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--seed", type=int, default=synthetic.DEFAULT_SEED)
@@ -126,7 +129,7 @@ VIT_EXTRACTORS = {"vit_s_32": "imagenet_inception", "vit_b_32": "imagenet_incept
 def verify_args(args):
     """reference utils/args.py:203-217. For the transformer extractors also the frame normalisation the reference sets
     for them (utils/args.py:185-190; the other extractors keep --frame_norm_method) and the inference-only scope, which
-    --vit_native_backward widens to everything but --learn_extractor."""
+    --vit_native_backward widens to everything but --learn_extractor and --vit_native_weight_backward to that as well."""
     if "train" in args.mode and not args.learn_extractor and not args.adapt_features:
         sys.exit("error: at least one of --learn_extractor and --adapt_features must be used when training")
     if args.frame_size % 1 or args.frame_size < 32:
@@ -137,7 +140,9 @@ def verify_args(args):
         if args.frame_size != 224:
             sys.exit("error: --feature_extractor %s needs --frame_size 224 (got %d)" % (fe, args.frame_size))
         multistep = getattr(args, "personalize_num_grad_steps", None) is not None
-        if getattr(args, "vit_native_backward", False):
+        if getattr(args, "vit_native_weight_backward", False):
+            pass  # native gradients of every parameter: everything the other extractors train is admitted
+        elif getattr(args, "vit_native_backward", False):
             if args.learn_extractor:
                 sys.exit("error: --vit_native_backward gives FiLM gradients through a frozen %s only: --learn_extractor "
                          "(weight gradients through a ViT) is not built" % fe)
@@ -197,6 +202,8 @@ class Learner:
     def _opt_in_vit_backward(self):
         if getattr(self.args, "vit_native_backward", False) and self.args.feature_extractor in VIT_EXTRACTORS:
             self.model.feature_extractor.native_backward = True
+        if getattr(self.args, "vit_native_weight_backward", False) and self.args.feature_extractor in VIT_EXTRACTORS:
+            self.model.feature_extractor.native_weight_backward = True
 
     def make_task(self, index):
         a = self.args

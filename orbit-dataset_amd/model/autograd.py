@@ -6,7 +6,8 @@ C-ABI call; torch only routes the gradients between the nodes and into `param.gr
 `zero_grad` work unchanged, as in utils/optim.py:11-33).
 
   ExtractorFunction      orbit_extractor_train_forward / orbit_extractor_backward   (resnet18, efficientnet_b0, set encoder)
-  VitFunction            orbit_vit_train_forward / orbit_vit_backward                (vit_*: FiLM vectors of the frozen network)
+  VitFunction            orbit_vit_train_forward / orbit_vit_backward[_params]       (vit_*: FiLM vectors of the frozen network,
+                         or with native_weight_backward every parameter)
   ProtoPredictFunction   orbit_proto_predict / orbit_proto_predict_backward          (gradient w.r.t. query features;
                          the prototypes are constants, classifier_heads.py:261-263 re-wraps them in nn.Parameter)
   MahalanobisPredictFunction  orbit_mahalanobis_predict / orbit_mahalanobis_predict_backward (w.r.t. query features)
@@ -109,11 +110,13 @@ class ExtractorFunction(torch.autograd.Function):
 
 
 class VitFunction(torch.autograd.Function):
-    """feats = vit(frames; gamma, beta) with a tape; gradients for the FiLM vectors only (the network is frozen). Runs on the
-    caller's stream."""
+    """feats = vit(frames; gamma, beta) with a tape. gamma / beta get their gradients from orbit_vit_backward (the network is
+    frozen). Inputs after `param_index` are the network's other trainable Parameters, as in ExtractorFunction (only so that
+    autograd routes their gradients; `param_index` holds their (flat-gradient offset, torch shape)): when one of them needs a
+    gradient the backward is orbit_vit_backward_params. Runs on the caller's stream."""
 
     @staticmethod
-    def forward(ctx, net, plan, frames, gamma, beta):
+    def forward(ctx, net, plan, frames, gamma, beta, param_index=(), *params):
         lib = _lib.load()
         B, dev = frames.shape[0], frames.device
         gamma, beta = gamma.detach().contiguous().float(), beta.detach().contiguous().float()
@@ -124,32 +127,52 @@ class VitFunction(torch.autograd.Function):
             plan.handle, _lib.dptr(frames, torch.float32), B, _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(feats),
             ctypes.c_void_p(tape.data_ptr()), tape.numel(), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
             _lib.stream_handle()), "orbit_vit_train_forward")
-        ctx.plan, ctx.tape, ctx.B, ctx.generation = plan, tape, B, plan.generation
-        ctx.save_for_backward(gamma, beta)
+        ctx.plan, ctx.tape, ctx.B, ctx.generation, ctx.param_index = plan, tape, B, plan.generation, param_index
+        ctx.save_for_backward(gamma, beta, frames)
         return feats
 
     @staticmethod
     def backward(ctx, dfeats):
         lib = _lib.load()
-        gamma, beta = ctx.saved_tensors
+        gamma, beta, frames = ctx.saved_tensors
         plan = ctx.plan
+        n_fixed = 6
+        out = [None] * (n_fixed + len(ctx.param_index))
         if plan.generation != ctx.generation:  # (as ExtractorFunction: the backward reads the weights from the plan)
             raise RuntimeError("the extractor's parameters were modified (re-uploaded into the native plan) between the "
                                "forward that recorded this tape and its backward; run backward before changing them")
         if ctx.tape is None:
             raise RuntimeError("this ViT tape was already consumed by a backward")
-        if not (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]):
+        need_params = any(ctx.needs_input_grad[n_fixed:])
+        if not (ctx.needs_input_grad[3] or ctx.needs_input_grad[4] or need_params):
             ctx.tape = None
-            return None, None, None, None, None
+            return tuple(out)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        ws = _empty_bytes(lib.orbit_vit_backward_workspace_bytes(plan.handle, ctx.B), gamma.device)
         dfeats = dfeats.contiguous().float()
-        _lib.check(lib.orbit_vit_backward(
-            plan.handle, ctx.B, _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(dfeats), ctypes.c_void_p(ctx.tape.data_ptr()),
-            ctx.tape.numel(), _lib.dptr(dgamma), _lib.dptr(dbeta), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-            _lib.stream_handle()), "orbit_vit_backward")
+        tape = ctypes.c_void_p(ctx.tape.data_ptr())
+        if need_params:
+            flat = torch.empty(lib.orbit_vit_grad_floats(plan.handle), device=gamma.device)
+            ws = _empty_bytes(lib.orbit_vit_backward_params_workspace_bytes(plan.handle, ctx.B), gamma.device)
+            _lib.check(lib.orbit_vit_backward_params(
+                plan.handle, _lib.dptr(frames, torch.float32), ctx.B, _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(dfeats), tape,
+                ctx.tape.numel(), _lib.dptr(flat), _lib.dptr(dgamma), _lib.dptr(dbeta), ctypes.c_void_p(ws.data_ptr()),
+                ws.numel(), _lib.stream_handle()), "orbit_vit_backward_params")
+            for j, (off, shape) in enumerate(ctx.param_index):
+                if ctx.needs_input_grad[n_fixed + j]:
+                    n = 1
+                    for d in shape:
+                        n *= d
+                    out[n_fixed + j] = flat[off:off + n].view(shape)
+        else:
+            ws = _empty_bytes(lib.orbit_vit_backward_workspace_bytes(plan.handle, ctx.B), gamma.device)
+            _lib.check(lib.orbit_vit_backward(
+                plan.handle, ctx.B, _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(dfeats), tape, ctx.tape.numel(),
+                _lib.dptr(dgamma), _lib.dptr(dbeta), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_handle()),
+                "orbit_vit_backward")
         ctx.tape = None
-        return (None, None, None, dgamma if ctx.needs_input_grad[3] else None, dbeta if ctx.needs_input_grad[4] else None)
+        out[3] = dgamma if ctx.needs_input_grad[3] else None
+        out[4] = dbeta if ctx.needs_input_grad[4] else None
+        return tuple(out)
 
 
 class ProtoPredictFunction(torch.autograd.Function):

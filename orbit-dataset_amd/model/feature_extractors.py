@@ -85,6 +85,9 @@ class HipNetwork(nn.Module):
     # native entry-point family (orbit_<api>_*) and the frame size of the throw-away plan that enumerates the parameters
     _api = "extractor"
     _probe_size = 64
+    # a taped forward may be issued on a side stream beside another forward of the same plan (deferred_stats,
+    # persistent_buffers: LITE's subset / query passes, few_shot_recognisers._get_features_with_split_batch)
+    side_stream_tapes = True
 
     def __init__(self, native_name):
         super().__init__()
@@ -522,12 +525,15 @@ class VisionTransformer(HipNetwork):
     raises NotImplementedError before anything is launched. With `native_backward = True` set on the instance, the FiLM
     vectors - or, without them, the FiLM-slot LayerNorm weights / biases - of an otherwise FROZEN network get their gradients
     from orbit_vit_train_forward / orbit_vit_backward (autograd.VitFunction); any other parameter requiring a gradient is still
-    refused. There is no BatchNorm or dropout, so train() and eval() compute the same features. Frames must be 224 x 224 (the
+    refused - unless `native_weight_backward = True` (which implies the above): then every parameter that requires a gradient
+    gets it from orbit_vit_backward_params (--learn_extractor). There is no BatchNorm or dropout, so train() and eval() compute the same features. Frames must be 224 x 224 (the
     position table is fixed)."""
 
     _api = "vit"
     _probe_size = VIT_FRAME_SIZE
+    side_stream_tapes = False  # one stream per plan (include/orbit_hip.h): the tape and its backward stay on the caller's
     native_backward = False  # opt-in (learner flag --vit_native_backward)
+    native_weight_backward = False  # second opt-in (learner flag --vit_native_weight_backward): weight gradients too
 
     def __init__(self, name):
         super().__init__(name)
@@ -565,18 +571,30 @@ class VisionTransformer(HipNetwork):
     def wants_grad(self, film=None):
         if not super().wants_grad(film):
             return False
-        if not self.native_backward:
+        if not (self.native_backward or self.native_weight_backward):
             raise NotImplementedError(
                 "%s is an inference-only extractor: no native backward (LITE meta-training, --learn_extractor, FiLM "
                 "gradients); run it under torch.no_grad() with frozen parameters" % self.native_name)
         film_keys = {n + leaf for n in self._film_slot_names for leaf in (".weight", ".bias")}
         other = [key for _, _, key, own in self._leaves if own is not None and own.requires_grad and key not in film_keys]
-        if other:
+        if other and not self.native_weight_backward:
             raise NotImplementedError(
                 "%s: native_backward gives the gradients of the FiLM vectors / FiLM-slot LayerNorm parameters of a frozen "
                 "network only; %d other parameters require a gradient (first: %s) and weight gradients (--learn_extractor) "
                 "are not built" % (self.native_name, len(other), other[0]))
         return True
+
+    def _weight_index(self, plan):
+        """[(Parameter, (flat-gradient offset, torch shape))] of the own Parameters that are not FiLM-slot LayerNorm weights /
+        biases (those take their gradients through the film vectors)."""
+        cached = self.__dict__.get("_weight_index_cache")
+        if cached is None:
+            lib = _lib.load()
+            film_keys = {n + leaf for n in self._film_slot_names for leaf in (".weight", ".bias")}
+            cached = [(own, (lib.orbit_vit_param_offset(plan.handle, i), tuple(own.shape)))
+                      for i, (_, _, key, own) in enumerate(self._leaves) if own is not None and key not in film_keys]
+            self.__dict__["_weight_index_cache"] = cached
+        return cached
 
     def forward(self, x, film=None, out=None, check_sync=True):
         _lib.require_gpu()
@@ -605,7 +623,10 @@ class VisionTransformer(HipNetwork):
                 slots = self.film_slot_modules()
                 film = (torch.cat([m._parameters["weight"].reshape(-1) for _, m in slots]),
                         torch.cat([m._parameters["bias"].reshape(-1) for _, m in slots]))
-            return VitFunction.apply(self, plan, x, film[0], film[1])
+            # every other Parameter that requires a gradient (wants_grad admitted them: native_weight_backward)
+            entries = [(own, meta) for own, meta in self._weight_index(plan) if own.requires_grad]
+            return VitFunction.apply(self, plan, x, film[0], film[1], tuple(meta for _, meta in entries),
+                                     *[own for own, _ in entries])
         feats = out if out is not None else torch.empty(B, self.output_size, device=x.device, dtype=torch.float32)
         if B == 0:
             return feats

@@ -431,7 +431,7 @@ class SingleStepFewShotRecogniser(FewShotRecogniser):
         grad_dev, no_grad_dev = self._split_indices(grad_idxs, no_grad_idxs)
         fe = self.feature_extractor
         if (self.features_cache is None and self.lite_overlap and fe.training and not film_dict and len(grad_idxs) > 0
-                and hasattr(fe, "deferred_stats")):
+                and getattr(fe, "side_stream_tapes", False)):
             # First query batch of a task: the cache pass over the WHOLE context set (no autograd) and the re-encoding of the
             # H-clip subset are independent, and the subset's kernels (16 frames) are launch-bound: it runs on a second stream
             # beside the cache pass (1.6 ms of a 29 ms step when serial). Both passes are train-mode BatchNorm forwards of one

@@ -7,6 +7,11 @@ task after warm-up, query frames/s, per-family kernel time of one proto task fro
 torch.nn.functional.linear (fp32, the vendor BLAS) on the same four shapes at M = 10 000 token rows as a reference point.
 
     python tools/vit_bench.py [--steps 10] [--warmup 3] [--models vit_s_32,vit_b_32,vit_b_32_clip]
+
+--train reports the training side instead: ms of taped forward + orbit_vit_backward_params (every parameter's gradient, through
+the module with native_weight_backward) at the step shapes B = 16 and B = 200, the weight-gradient GEMM family's TF/s per layer
+shape at M = 10 000 token rows (orbit_op_vit_linear_wgrad, split-reduction launch + reduce), and fp32 `dy.t() @ x` through torch
+(the vendor BLAS) on the same shapes. Nothing here is gated.
 """
 import argparse
 import ctypes
@@ -103,14 +108,67 @@ def _torch_linear(D, steps, warmup, M=10000):
     return out
 
 
+def _train_step_ms(name, B, steps, warmup):
+    from orbit_dataset_amd.model.feature_extractors import create_feature_extractor
+    fe, _ = create_feature_extractor(name, with_film=False, learn_extractor=True)
+    synthetic.init_parameters_(fe)
+    fe.to("cuda:0")
+    fe.native_weight_backward = True
+    x = torch.randn(B, 3, 224, 224, device="cuda:0")
+    r = torch.randn(B, fe.output_size, device="cuda:0")
+
+    def step():
+        for p in fe.parameters():
+            p.grad = None
+        (fe(x) * r).sum().backward()
+    return _time(step, steps, warmup)
+
+
+def _wgrad_shapes(D, steps, warmup, M=10000):
+    """per layer shape: the native wgrad (launch + reduce) and torch's dy.t() @ x, both fp32, ms and TF/s"""
+    lib = _lib.load()
+    torch.backends.cuda.matmul.allow_tf32 = False
+    out = {}
+    for tag, N, K, gelu in (("qkv", 3 * D, D, 0), ("proj", D, D, 0), ("fc1", 4 * D, D, 0), ("fc2", D, 4 * D, 1)):
+        dy = torch.randn(M, N, device="cuda:0")
+        x = torch.randn(M, K, device="cuda:0")
+        dw, db = torch.empty(N, K, device="cuda:0"), torch.empty(N, device="cuda:0")
+        need = lib.orbit_op_vit_linear_wgrad_workspace_floats(M, N, K)
+        ws = torch.empty(max(need, 64), device="cuda:0")
+
+        def native():
+            _lib.check(lib.orbit_op_vit_linear_wgrad(_lib.dptr(dy), _lib.dptr(x), _lib.dptr(dw), _lib.dptr(db), M, N, K, gelu,
+                                                     _lib.dptr(ws), need, _lib.stream_handle()), "orbit_op_vit_linear_wgrad")
+        ms = _time(native, steps, warmup)
+        ms_t = _time(lambda: torch.matmul(dy.t(), x), steps, warmup)
+        tf = lambda t: round(2.0 * M * N * K / t / 1e9, 2)
+        out[tag] = {"N": N, "K": K, "gelu_on_x": gelu, "wgrad_ms": round(ms, 4), "wgrad_tflops": tf(ms),
+                    "torch_ms": round(ms_t, 4), "torch_tflops": tf(ms_t)}
+    return out
+
+
+def main_train(a):
+    result = {"metric": "vit_train_ms", "what": "taped forward + orbit_vit_backward_params, every parameter trainable",
+              "peak_tflops": PEAK_TF, "models": {}}
+    for name in a.models.split(","):
+        r = {"fwd_bwd_ms": {"B%d" % B: round(_train_step_ms(name, B, a.steps, a.warmup), 3) for B in (16, 200)}}
+        r["wgrad_m10000"] = _wgrad_shapes(384 if name == "vit_s_32" else 768, a.steps, a.warmup)
+        result["models"][name] = r
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--models", default="vit_s_32,vit_b_32,vit_b_32_clip")
+    p.add_argument("--train", action="store_true", help="the training step and the weight-gradient GEMMs instead")
     a = p.parse_args(argv)
     _lib.require_gpu()
     torch.cuda.set_device(0)
+    if a.train:
+        return main_train(a)
     result = {"metric": "vit_task_ms", "task": "5-way, 200 support + 200 query frames, 224x224", "peak_tflops": PEAK_TF,
               "models": {}}
     for name in a.models.split(","):
