@@ -155,6 +155,24 @@ int orbit_proto_predict(const float* Q, const float* W, const float* b,
                         int n_tasks, int M, int T, int D, int C, float logit_scale, int cosine,
                         float* logits, int32_t* argmax, orbit_stream_t stream);
 
+/* The ORBIT benchmark metrics of one task's target videos in ONE launch (utils/eval_metrics.py:27-69: frame accuracy,
+ * frames-to-recognition and video accuracy are functions of the per-frame argmax alone). All pointers are device pointers.
+ *   logits        [M][C]   the task's target-frame logits, videos back to back
+ *   video_offsets [V+1]    ascending, [0] = 0, [V] = M: video v owns rows offsets[v] .. offsets[v+1]-1 (entries are clamped
+ *                          into [0, M] on the device: a bad table gives wrong counts, never an access out of range)
+ *   video_labels  [V]      the videos' labels as logit COLUMNS; a label outside [0, C) matches no frame
+ *   preds         [M] out  per-frame predicted column, or NULL; the argmax rule is orbit_proto_predict's (first maximal
+ *                          column, as torch.argmax - one device function serves both)
+ *   correct       [V] out  frames of video v predicted as its label
+ *   first_correct [V] out  index inside the video of its first correct frame; n_v when no frame is correct
+ *   hist       [V][C] out  frames of video v predicted as class c
+ * An empty video writes correct = 0, first_correct = 0 and a zero histogram row. Integer adds and mins only: the outputs
+ * are exactly reproducible. M, V >= 0, 1 <= C <= ORBIT_VIDEO_METRICS_MAX_C and non-null pointers (preds excepted) are
+ * checked on the host (ORBIT_ERR_ARG, nothing launched); M == 0 or V == 0 is a no-op returning 0. */
+#define ORBIT_VIDEO_METRICS_MAX_C 4096
+int orbit_video_metrics(const float* logits, int M, int C, const int32_t* video_offsets, const int64_t* video_labels, int V,
+                        int32_t* preds, int32_t* correct, int32_t* first_correct, int32_t* hist, orbit_stream_t stream);
+
 /* out[i][d] = mean_t x[i*T+t][d]  (poolers.py:13-16) */
 int orbit_mean_pool(const float* x, int N, int T, int D, float* out, orbit_stream_t stream);
 

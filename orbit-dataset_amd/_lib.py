@@ -25,6 +25,7 @@ _SIGNATURES = {
     "orbit_proto_configure": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "orbit_proto_finalize": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P]),
     "orbit_proto_predict": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P]),
+    "orbit_video_metrics": (c_int, [P, c_int, c_int, P, P, c_int, P, P, P, P, P]),
     "orbit_mean_pool": (c_int, [P, c_int, c_int, c_int, P, P]),
     "orbit_set_mean": (c_int, [P, c_int, c_int, P, P]),
     "orbit_history_mean_pool": (c_int, [P, c_int, c_int, c_int, P, P]),

@@ -36,6 +36,13 @@ __device__ __forceinline__ float wave_max_xor(float v) {
     return v;
 }
 
+// One step of a running argmax over ascending columns c, started from best = -INFINITY, best_c = 0: the FIRST maximal column
+// wins, as torch.argmax. The only definition of the rule: the head's `argmax` output and the evaluation metrics
+// (csrc/eval.hip) must name the same class for the same logits.
+__device__ __forceinline__ void argmax_step(float v, int c, float& best, int& best_c) {
+    if (v > best) best = v, best_c = c;
+}
+
 // XCD-aware remap: hardware places block i on XCD i % 8, each XCD with its own L2; give each XCD a contiguous run of
 // logical blocks so that the blocks sharing an operand (the n-tiles of one A row-panel, the row blocks of one task's
 // weights) hit the same L2 (bijective for any grid size).

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void proto_predict_kernel(
                 else
                     v = logit_scale * (v + bj);
                 if (lane == 0 && row_ok[r]) logits[((size_t)task * M + m0 + r) * C + c0 + j] = v;
-                if (v > best[r]) best[r] = v, best_c[r] = c0 + j;
+                argmax_step(v, c0 + j, best[r], best_c[r]);
             }
         }
     }
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void proto_predict_lds_kernel(
                 else
                     v = logit_scale * (v + bj);
                 if (lane == 0 && row_ok[r]) logits[((size_t)task * M + m0 + r) * C + c0 + j] = v;
-                if (v > best[r]) best[r] = v, best_c[r] = c0 + j;
+                argmax_step(v, c0 + j, best[r], best_c[r]);
             }
         }
     }
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(NW * 64) void proto_predict_stream_kernel(
             else
                 v = logit_scale * (v + bj);
             if (lane == 0 && row_ok[r]) logits[((size_t)task * M + m0 + r) * C + c] = v;
-            if (!LEAN && v > best[r]) best[r] = v, best_c[r] = c;
+            if (!LEAN) argmax_step(v, c, best[r], best_c[r]);
         }
     }
     if (!LEAN && argmax != nullptr && lane == 0) {

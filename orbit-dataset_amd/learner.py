@@ -36,6 +36,7 @@ from . import synthetic
 from .data.utils import attach_frame_history, unpack_task
 from .model.few_shot_recognisers import SingleStepFewShotRecogniser
 from .optim import apply_lr_scale, cross_entropy, init_optimizer  # noqa: F401  (re-exported: bench.py, tools)
+from .utils.eval_metrics import TestEvaluator
 
 
 def build_parser():
@@ -97,6 +98,9 @@ def build_parser():
     p.add_argument("--momentum", type=float, default=0.0)
     p.add_argument("--print_by_step", action="store_true")
     p.add_argument("--results_path", default=None)
+    p.add_argument("--save_predictions", default=None, metavar="DIR",
+                   help="with --data_root: write DIR/results.json, one predicted class per frame id of every target video in "
+                        "the ORBIT challenge's layout (reference TestEvaluator.save(), utils/eval_metrics.py:112-153)")
     p.add_argument("--data_root", default=None,
                    help="--mode test: a frame directory laid out like ORBIT (root/<user>/<object>/<clean|clutter>/<video>/*.jpg, "
                         "reference data/datasets.py:139-200). Tasks are the users' (context = clean videos, target = clutter "
@@ -162,6 +166,74 @@ def mean_ci(values):
     if len(v) == 0:  # a rank (or a run) that saw no task: no statistic (None: json.dump would write a bare NaN, invalid JSON)
         return None, 0.0
     return float(v.mean()), float(1.96 * v.std() / math.sqrt(len(v))) if len(v) > 1 else 0.0
+
+
+ORBIT_METRICS = ["frame_acc", "frames_to_recognition"]
+
+
+class OrbitMetrics:
+    """The ORBIT benchmark's evaluation beside a test loop's own figures: a TestEvaluator (utils/eval_metrics.py) fed with
+    every target video's device logits - one orbit_video_metrics launch per task - that reports frame accuracy and
+    frames-to-recognition averaged per user, object, task and video, and video accuracy per object and video."""
+
+    def __init__(self, save_dir=None):
+        self.evaluator = TestEvaluator(ORBIT_METRICS, save_dir=save_dir)
+        self.tasks = []  # (global task index, user key, object list) of the tasks fed, in order
+
+    def begin_task(self, index, user, object_list=None):
+        if self.tasks:  # a new user where the key changes, as the reference's loop (single-step-learner.py:348-357)
+            if user != self.tasks[-1][1]:
+                self.evaluator.set_current_user(self.tasks[-1][1])
+                self.evaluator.next_user()
+            else:
+                self.evaluator.next_task()
+        self.tasks.append((index, user, object_list))
+        if object_list is not None:
+            self.evaluator.set_task_object_list(object_list)
+
+    def append_video(self, logits, label, paths=None):
+        self.evaluator.append_video(logits, label, paths)
+
+    def gather(self, world, with_predictions):
+        """world > 1: every rank's per-video INTEGERS (not its scores) through all_gather_object, re-assembled in global task
+        order, so every rank reports what a single-GPU run over the same tasks reports."""
+        if world == 1:
+            return self
+        import torch.distributed as dist
+        self.evaluator._flush()
+        mine = [t for user in self.evaluator.all_video_results for t in user if t]
+        assert len(mine) == len(self.tasks)
+        payload = [(tag, [([s.as_tuple() for s in v.segments], v.preds.tolist() if with_predictions else None,
+                           v.paths if with_predictions else None) for v in videos]) for tag, videos in zip(self.tasks, mine)]
+        gathered = [None] * world
+        dist.all_gather_object(gathered, payload)
+        merged = OrbitMetrics(getattr(self.evaluator, "save_dir", None))
+        for (index, user, object_list), videos in sorted((x for g in gathered for x in g), key=lambda x: x[0][0]):
+            merged.begin_task(index, user, object_list)
+            for video in videos:
+                merged.evaluator.append_video_segments(*video)
+        return merged
+
+    def report(self):
+        """{"user" | "object" | "task" | "video": {stat: [mean, ci]}} or None when no video was fed"""
+        ev = self.evaluator
+        if not self.tasks:
+            return None
+        if len(ev.all_users) == ev.current_user:
+            ev.set_current_user(self.tasks[-1][1])
+        levels = dict(zip(("user", "object", "task", "video"), ev.get_mean_stats()))
+        video, obj = ev.get_video_and_object_stats()
+        levels["video"].update(video)
+        levels["object"].update(obj)
+        return {level: {k: [float(x) for x in v] for k, v in stats.items()} for level, stats in levels.items()}
+
+    @staticmethod
+    def line(report):
+        if report is None:
+            return "orbit metrics: no target video"
+        return "orbit metrics, % (95 % ci): " + " | ".join(
+            "per %s %s" % (level, ", ".join("%s %.2f (%.2f)" % (k, 100 * m, 100 * c) for k, (m, c) in report[level].items()))
+            for level in ("user", "object", "task", "video"))
 
 
 def _shown(stat):
@@ -446,10 +518,15 @@ class Learner:
             order = order[:cap]
         source = DatasetTaskSource(dataset, order[self.rank::self.world])
         task_acc, personalise_ms, inference_ms, frames = [], [], [], 0
+        save_dir = getattr(a, "save_predictions", None)
+        metrics = OrbitMetrics(save_dir)
+        mine = list(range(len(order)))[self.rank::self.world]  # global indices of this rank's tasks
         t_all = time.perf_counter()
         prefetch = TaskPrefetcher(source, self.device, depth=3, frame_norm_method=a.frame_norm_method)
         with torch.no_grad():
-            for task in prefetch:
+            for k, task in enumerate(prefetch):
+                metrics.begin_task(mine[k], task["user"], task.get("object_list"))
+                video_labels = task["target_labels"].cpu()
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 self.model.personalise(task["context_clips"], task["context_labels"])
@@ -464,6 +541,8 @@ class Learner:
                     torch.cuda.synchronize()
                     inference_ms.append(1e3 * (time.perf_counter() - t0) / float((hi - lo) * self.model.clip_length))
                     accs.append(frame_accuracy(logits, task["target_labels"][lo:hi]))
+                    paths = task["target_paths"][len(accs) - 1] if task.get("target_paths") is not None else None
+                    metrics.append_video(logits, video_labels[lo], paths)
                     frames += hi - lo
                 task_acc.append(float(np.mean(accs)))
                 self.model._reset()
@@ -478,14 +557,19 @@ class Learner:
             personalise_ms = [x for g in gathered for x in g[1]]
             inference_ms = [x for g in gathered for x in g[2]]
             frames = sum(g[3] for g in gathered)
+        metrics = metrics.gather(self.world, with_predictions=bool(save_dir))
         stats = {"frame_acc": mean_ci(task_acc), "personalise_ms": mean_ci(personalise_ms),
                  "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world,
-                 "target_frames": frames, "wall_s": wall, "data_root": a.data_root}
+                 "target_frames": frames, "wall_s": wall, "data_root": a.data_root, "orbit_metrics": metrics.report()}
         if self.rank == 0:
             print("test (%s): frame_acc %.2f (%.2f) %% | time to personalise %.2f (%.2f) ms | inference %.4f (%.4f) ms/frame "
                   "| %d tasks, %d target frames in %.1f s incl. JPEG decode (%d threads)"
                   % (a.data_root, 100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1], *_shown(stats["personalise_ms"]),
                      *_shown(stats["inference_ms_per_frame"]), stats["num_tasks"], frames, wall, a.num_workers))
+            print(OrbitMetrics.line(stats["orbit_metrics"]))
+            if save_dir and stats["orbit_metrics"] is not None:
+                metrics.evaluator.save()
+                print("predictions written to %s" % metrics.evaluator.json_results_path)
             if a.results_path:
                 with open(a.results_path, "w") as f:
                     json.dump(stats, f)
@@ -499,10 +583,12 @@ class Learner:
         # (synthetic tasks live on the host and are uploaded per mini-batch: in its default mode, overlap_query = "auto", the
         # recogniser runs the query pass of predict() on its own stream for such clips)
         task_acc, personalise_ms, inference_ms = [], [], []
+        metrics = OrbitMetrics()
         with torch.no_grad():
             for t in odist.tasks_for_rank(a.num_test_tasks, self.rank, self.world):
                 context_clips, context_labels, videos = self.make_task(t)
                 context_labels = self._labels_to_device(context_labels)
+                metrics.begin_task(t, t)  # synthetic mode: one user is one task
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 self.model.personalise(context_clips, context_labels)
@@ -517,6 +603,7 @@ class Learner:
                     torch.cuda.synchronize()
                     inference_ms.append(1e3 * (time.perf_counter() - t0) / float(len(frames) * self.model.clip_length))
                     accs.append(frame_accuracy(logits.cpu(), labels))
+                    metrics.append_video(logits, labels)  # (a synthetic "video" mixes objects: one label per frame)
                 task_acc.append(float(np.mean(accs)))
                 self.model._reset()
         if self.world > 1:
@@ -526,13 +613,16 @@ class Learner:
             task_acc = [x for g in gathered for x in g[0]]
             personalise_ms = [x for g in gathered for x in g[1]]
             inference_ms = [x for g in gathered for x in g[2]]
+        metrics = metrics.gather(self.world, with_predictions=False)
         stats = {"frame_acc": mean_ci(task_acc), "personalise_ms": mean_ci(personalise_ms),
-                 "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world}
+                 "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world,
+                 "orbit_metrics": metrics.report()}
         if self.rank == 0:
             print("test: frame_acc %.2f (%.2f) %% | time to personalise %.2f (%.2f) ms | inference %.4f (%.4f) ms/frame "
                   "| %d tasks on %d GPU(s)" % (100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1],
                                                *_shown(stats["personalise_ms"]), *_shown(stats["inference_ms_per_frame"]),
                                                stats["num_tasks"], self.world))
+            print(OrbitMetrics.line(stats["orbit_metrics"]))
             if a.results_path:
                 with open(a.results_path, "w") as f:
                     json.dump(stats, f)
@@ -571,8 +661,10 @@ class MultiStepLearner(Learner):
                          "epsilon": a.personalize_epsilon}
         self.model.set_test_mode(True)
         task_acc, personalise_ms, inference_ms = [], [], []
+        metrics = OrbitMetrics()
         for t in odist.tasks_for_rank(a.num_test_tasks, self.rank, self.world):
             context_clips, context_labels, videos = self.make_task(t)
+            metrics.begin_task(t, t)  # synthetic mode: one user is one task
             # the finetuner starts every task from the initial parameters (multi-step-learner.py:153-154)
             self.model.load_state_dict(self.base_state, strict=False)
             torch.cuda.synchronize()
@@ -590,15 +682,18 @@ class MultiStepLearner(Learner):
                     torch.cuda.synchronize()
                     inference_ms.append(1e3 * (time.perf_counter() - t0) / float(len(clips) * self.model.clip_length))
                     accs.append(frame_accuracy(logits.cpu(), labels))
+                    metrics.append_video(logits, labels)  # (a synthetic "video" mixes objects: one label per frame)
             task_acc.append(float(np.mean(accs)))
             self.model._reset()
         stats = {"frame_acc": mean_ci(task_acc), "personalise_ms": mean_ci(personalise_ms),
-                 "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world}
+                 "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world,
+                 "orbit_metrics": metrics.report()}
         if self.rank == 0:
             print("finetuner test: frame_acc %.2f (%.2f) %% | time to personalise %.2f (%.2f) ms (%d steps) | inference "
                   "%.4f (%.4f) ms/frame | %d tasks" % (100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1],
                                                        *_shown(stats["personalise_ms"]), a.personalize_num_grad_steps,
                                                        *_shown(stats["inference_ms_per_frame"]), stats["num_tasks"]))
+            print(OrbitMetrics.line(stats["orbit_metrics"]))
         return stats
 
 
