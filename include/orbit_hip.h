@@ -184,7 +184,10 @@ int orbit_history_mean_pool(const float* x, int F, int T, int D, float* out, orb
 int orbit_set_mean(const float* x, int n, int D, float* out, orbit_stream_t stream);
 
 /* ---- feature extractors / set encoder ---------------------------------------------------------- */
-/* name: "resnet18" | "efficientnet_b0" | "set_encoder".  H,W: frame size the plan is built for. */
+/* name: "resnet18" | "efficientnet_b0" | "efficientnet_v2_s" | "set_encoder".  H,W: frame size the plan is built for.
+ * "efficientnet_v2_s" (timm tf_efficientnetv2_s_in21k, num_classes = 0; 1280-d features) is an inference plan: its ConvBnAct
+ * blocks add their skip after the activation, which the training runtime has no backward for, so
+ * orbit_extractor_supports_training is 0 and the tape / backward-workspace size queries return 0 for it. */
 int orbit_extractor_create(const char* name, int H, int W, orbit_extractor_t** out);
 /* flags: ORBIT_PLAN_UNFUSED = a plan for forwards that record a tape or use batch statistics (the LITE training step,
  * few_shot_recognisers.py:176-183): every MBConv block stays a conv + depthwise pair, whose outputs the backward needs;
@@ -329,6 +332,15 @@ int orbit_op_conv2d(const float* x, int x_nchw, const float* w, float* y,
                     int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                     int pad_top, int pad_left, int Ho, int Wo, int act, int pool2,
                     orbit_stream_t stream);
+/* The same with flags. ORBIT_CONV_RESIDUAL_POST_ACT: y = act( conv(x) * scale + shift ) + residual - the skip joins AFTER the
+ * activation (timm ConvBnAct with a skip, efficientnet_v2_s stage 0). Compiled for plain K x K NHWC convs only: a residual is
+ * required, and x_nchw, pool2, a gate or a 1x1 unpadded filter with this flag are argument errors. flags = 0: orbit_op_conv2d. */
+#define ORBIT_CONV_RESIDUAL_POST_ACT 1
+int orbit_op_conv2d_ex(const float* x, int x_nchw, const float* w, float* y,
+                       const float* scale, const float* shift, const float* residual, const float* gate,
+                       int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                       int pad_top, int pad_left, int Ho, int Wo, int act, int pool2, int flags,
+                       orbit_stream_t stream);
 /* Gated 1x1 projection with its squeeze-excite gate (no activation):
  *   gate = sigmoid(W2 silu(W1 (sum over chunks of partial[b][chunk]) / (H*W) + b1) + b2),
  *   y = conv1x1(x * gate) * scale + shift (+ residual).
@@ -461,8 +473,8 @@ int orbit_mahalanobis_predict_backward(const float* dlogits, const float* featur
  * What `loss.backward()` runs in the reference (single-step-learner.py:234) for the graph recorded by
  * model/few_shot_recognisers.py:99-122 (_get_features, grad enabled), :345-356 (_get_task_embedding on the LITE
  * subset) and model/classifier_heads.py:202-230 (head). BatchNorm mode follows few_shot_recognisers.py:176-183.
- * Available for the resnet18, efficientnet_b0 and set_encoder plans (orbit_extractor_supports_training is 0 only for a
- * plan built with the opt-in fused MBConv front op). */
+ * Available for the resnet18, efficientnet_b0 and set_encoder plans (orbit_extractor_supports_training is 0 for a plan built
+ * with the fused MBConv front op and for efficientnet_v2_s, whose post-activation skip has no backward form). */
 int orbit_extractor_supports_training(const orbit_extractor_t* fe);
 size_t orbit_extractor_tape_bytes(const orbit_extractor_t* fe, int B);
 size_t orbit_extractor_backward_workspace_bytes(const orbit_extractor_t* fe, int B);

@@ -79,6 +79,7 @@ _SIGNATURES = {
     "orbit_filmgen_load_all_async": (c_int, [P, P, c_int, P]),
     "orbit_filmgen_forward": (c_int, [P, P, P, P, P, P]),
     "orbit_op_conv2d": (c_int, [P, c_int, P, P, P, P, P, P] + [c_int] * 14 + [P]),
+    "orbit_op_conv2d_ex": (c_int, [P, c_int, P, P, P, P, P, P] + [c_int] * 15 + [P]),
     "orbit_op_dwconv2d": (c_int, [P, P, P, P, P] + [c_int] * 11 + [P]),
     "orbit_op_pw_stream": (c_int, [P] * 6 + [c_int] + [P] * 4 + [c_int, P, P] + [c_int] * 5 + [P]),
     "orbit_pw_stream_supported": (c_int, [c_int] * 4),

@@ -69,6 +69,8 @@ struct ConvDesc {
     const float* scale;     // [Cout] or nullptr
     const float* shift;     // [Cout] or nullptr
     const float* residual;  // NHWC like y or nullptr
+    int res_post = 0;       // the residual joins AFTER the activation: y = act(conv * scale + shift) + residual (timm ConvBnAct);
+                            // a compile-time form of the K x K NHWC kernel (csrc/conv_igemm.hip), refused for every other conv
     const float* gate;      // [B][Cin] or nullptr
     int B, H, W, Cin, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo;
     int act;     // ORBIT_ACT_*

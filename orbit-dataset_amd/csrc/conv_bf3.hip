@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256) void conv_bf3_kernel(const Bf3Params p) {
 }
 
 bool conv_bf3_supported(const ConvDesc& d) {
-    if (d.x_nchw || d.pool2 || d.y_raw || d.stats) return false;
+    if (d.x_nchw || d.pool2 || d.y_raw || d.stats || d.res_post) return false;  // (res_post: this epilogue adds the skip before the activation)
     if (d.Cin % 16 != 0 || d.Cout % 4 != 0 || d.Cin < 64 || d.Cout < 40) return false;
     const bool pw = d.KH == 1 && d.KW == 1 && d.pad_t == 0 && d.pad_l == 0 && d.stride == 1;
     return pw || d.gate == nullptr;  // the general form (taps, stride, padding) has no squeeze-excite prologue

@@ -11,6 +11,8 @@
 //   network stems, element-wise from the NCHW frames.
 //   Epilogue (fused, so activations make exactly one HBM round trip per layer):
 //               y = act(acc * scale[n] + shift[n] + residual[m][n])      folded BatchNorm (+FiLM), skip add
+//               RPOST form: y = act(acc * scale[n] + shift[n]) + residual[m][n]   (timm ConvBnAct: the skip joins after the
+//               activation; a compile-time form of the K x K NHWC kernel, instantiated for ConvDesc::res_post only)
 //               optional 2x2/2 max-pool: rows are enumerated window-major so that the four members of
 //               a pooling window are the four consecutive accumulator rows a lane already holds.
 //   Prologue:   optional per-(frame, input-channel) squeeze-excite gate multiplied into A.
@@ -93,7 +95,8 @@ __device__ __forceinline__ void decode_row(const ConvParams& p, int m, int& b, i
 // staged K-tile, each takes every WGK-th 8-deep k-group of it, and the partial accumulators are summed through LDS in
 // the epilogue. That buys 2-4x more (smaller) output tiles for layers whose 64x64 tiling leaves the chip short of blocks
 // (M = 9 800 rows in EfficientNet's 7x7 stages, 1 800-7 200 in resnet18 @84's layer3/4).
-template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL>
+// RPOST: the residual is added AFTER the activation (see the epilogue forms above).
+template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL, bool RPOST = false>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
     static_assert(WGM * WGN * WGK == 4, "4 waves per block");
     static_assert(WGK == 1 || !POOL2, "the fused max-pool is not linear in the K-split partial sums");
@@ -101,6 +104,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
     static_assert(MODE == 0 || BK == 32, "the stem gather is written for BK = 32");
     static_assert(!(PW && (MODE == 1 || POOL2)), "pointwise specialisation: NHWC, no fused pooling");
     static_assert(!(GATE && (MODE == 1 || POOL2)), "the squeeze-excite gate prologue: NHWC, no fused pooling");
+    static_assert(!(RPOST && (MODE == 1 || POOL2 || GATE || PW)), "the post-activation skip: plain K x K NHWC convs");
     constexpr int LDS_STRIDE = BK + 4;
     constexpr int WM = BM / WGM, WN = BN / WGN;  // wave tile
     constexpr int TM = WM / 32, TN = WN / 32;    // 32x32 accumulator tiles per wave
@@ -480,9 +484,10 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
                         o = o * dsc + dsh;
                     }
                     if (!POOL2 && p.ksplit <= 1) {
-                        o += res[it];
+                        if constexpr (!RPOST) o += res[it];
                         o[0] = apply_act(o[0], p.act), o[1] = apply_act(o[1], p.act);
                         o[2] = apply_act(o[2], p.act), o[3] = apply_act(o[3], p.act);
+                        if constexpr (RPOST) o += res[it];
                     }
                     if (yout) *reinterpret_cast<f32x4*>(yout + (size_t)(mo0 + r) * p.Cout + n) = o;  // (null: statistics sweep)
                 }
@@ -501,9 +506,10 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
                     if (p.scale) v = v * *reinterpret_cast<const f32x4*>(p.scale + n) + *reinterpret_cast<const f32x4*>(p.shift + n);
                 }
                 if (!POOL2 && p.ksplit <= 1) {
-                    if (p.residual) v += *reinterpret_cast<const f32x4*>(p.residual + (size_t)m * p.Cout + n);
+                    if (!RPOST && p.residual) v += *reinterpret_cast<const f32x4*>(p.residual + (size_t)m * p.Cout + n);
                     v[0] = apply_act(v[0], p.act), v[1] = apply_act(v[1], p.act);
                     v[2] = apply_act(v[2], p.act), v[3] = apply_act(v[3], p.act);
+                    if (RPOST && p.residual) v += *reinterpret_cast<const f32x4*>(p.residual + (size_t)m * p.Cout + n);
                 }
                 if (yout) *reinterpret_cast<f32x4*>(yout + (size_t)m * p.Cout + n) = v;
             }
@@ -528,6 +534,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
 }
 
 // ---- split-K: sum of the partial tiles in split order (deterministic) + the conv epilogue -------------------------------
+template <bool RPOST>
 __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const float* __restrict__ part, int S, size_t mn4,
                                                                  int cout4, const float* __restrict__ scale,
                                                                  const float* __restrict__ shift,
@@ -540,8 +547,9 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const float* __
         const int n4 = (int)(i % (size_t)cout4);
         if (scale) v *= reinterpret_cast<const f32x4*>(scale)[n4];
         if (shift) v += reinterpret_cast<const f32x4*>(shift)[n4];
-        if (residual) v += reinterpret_cast<const f32x4*>(residual)[i];
+        if (!RPOST && residual) v += reinterpret_cast<const f32x4*>(residual)[i];
         v[0] = apply_act(v[0], act), v[1] = apply_act(v[1], act), v[2] = apply_act(v[2], act), v[3] = apply_act(v[3], act);
+        if (RPOST && residual) v += reinterpret_cast<const f32x4*>(residual)[i];
         reinterpret_cast<f32x4*>(y)[i] = v;
     }
 }
@@ -605,14 +613,14 @@ int conv_pack_weights(const float* w_oihw, float* w_packed, int Cin, int Cout, i
     return ORBIT_OK;
 }
 
-template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL>
+template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL, bool RPOST = false>
 static int launch_cfg2(ConvParams& p, hipStream_t s) {
     p.m_tiles = cdiv(p.M, BM);
     p.n_tiles = cdiv(p.Cout, BN);
     const size_t lds_pipe = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (MODE == 1 ? 1024 : 0);  // + stem k table
     const size_t lds_epi = (size_t)WGK * (POOL2 ? BM / 4 : BM) * BN * sizeof(float);
     const size_t lds = lds_pipe > lds_epi ? lds_pipe : lds_epi;
-    auto kern = conv_igemm_kernel<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, UL>;
+    auto kern = conv_igemm_kernel<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, UL, RPOST>;
     static bool attr_set = false;  // >64 KiB dynamic LDS needs the opt-in once per kernel
     if (!attr_set && lds > 64 * 1024) {
         ORBIT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -623,8 +631,8 @@ static int launch_cfg2(ConvParams& p, hipStream_t s) {
     int rec = -1;
     if (conv_prof_enabled()) {  // per-launch event record (csrc/runtime.hip), one variant per instantiation
         char name[48];
-        snprintf(name, sizeof(name), "conv_igemm<%d,%d,%d,%s%s%s%s%s>", BM, BN, BK, MODE ? "nchw" : "nhwc",
-                 POOL2 ? ",pool2" : "", GATE ? ",gate" : "", PW ? ",pw" : "",
+        snprintf(name, sizeof(name), "conv_igemm<%d,%d,%d,%s%s%s%s%s%s>", BM, BN, BK, MODE ? "nchw" : "nhwc",
+                 POOL2 ? ",pool2" : "", GATE ? ",gate" : "", PW ? ",pw" : "", RPOST ? ",rpost" : "",
                  p.ksplit > 1 ? ",splitk" : WGK == 2 ? ",k2" : WGK == 4 ? ",k4" : (!p.y ? ",stats" : ""));
         const double pix = POOL2 ? (double)p.B * p.HoP * p.WoP * 4 : (double)p.B * p.Ho * p.Wo;
         const double flops = 2.0 * pix * p.Cout * p.KH * p.KW * p.Cin * p.prof_flop_scale;  // algorithmic (unpadded) FLOPs
@@ -640,7 +648,7 @@ static int launch_cfg2(ConvParams& p, hipStream_t s) {
     return ORBIT_OK;
 }
 
-template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW>
+template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool RPOST = false>
 static int launch_cfg(ConvParams& p, hipStream_t s) {
     // UL = staged loads without predicates, for pointwise convs (every element of a tile exists once the rows beyond M are
     // clamped): no predicate, mask or select at all. In-process A/B on MI355X: +1..2 % on most pointwise layers, +16..20 % on
@@ -649,16 +657,16 @@ static int launch_cfg(ConvParams& p, hipStream_t s) {
     if constexpr (PW)
         if (p.cin_pad == p.Cin)  // the clamped pointwise form has no K-padding predicate
             return launch_cfg2<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, true>(p, s);
-    return launch_cfg2<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, false>(p, s);
+    return launch_cfg2<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, false, RPOST>(p, s);
 }
 
-template <int BK, int MODE, bool POOL2, bool GATE, bool PW>
+template <int BK, int MODE, bool POOL2, bool GATE, bool PW, bool RPOST = false>
 static int launch_tiled(ConvParams& p, hipStream_t s) {
-    if (p.ksplit > 1) return launch_cfg<64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW>(p, s);  // split-K plans on 64x64 tiles
+    if (p.ksplit > 1) return launch_cfg<64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);  // split-K plans on 64x64 tiles
     switch (get_option("conv_tile")) {  // 0 = the heuristic below; else force one of its three tilings (parity tests, A/B)
-        case 3: return launch_cfg<64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW>(p, s);
-        case 4: return launch_cfg<128, 32, 4, 1, 1, BK, MODE, POOL2, GATE, PW>(p, s);
-        case 6: if constexpr (MODE == 0 && !POOL2 && BK == 32) return launch_cfg<32, 32, 1, 1, 4, BK, MODE, POOL2, GATE, PW>(p, s); break;
+        case 3: return launch_cfg<64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);
+        case 4: return launch_cfg<128, 32, 4, 1, 1, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);
+        case 6: if constexpr (MODE == 0 && !POOL2 && BK == 32) return launch_cfg<32, 32, 1, 1, 4, BK, MODE, POOL2, GATE, PW, RPOST>(p, s); break;
         default: break;
     }
     // Measured sweep on MI355X (tools/conv_bench.py <net> sweep, in-process A/B over every layer shape of resnet18 @84
@@ -670,22 +678,22 @@ static int launch_tiled(ConvParams& p, hipStream_t s) {
     // +-2 % on the long-K ones - removed.)
     const double waste64 = (double)(cdiv(p.Cout, 64) * 64 - p.Cout) / p.Cout;
     const double waste32 = (double)(cdiv(p.Cout, 32) * 32 - p.Cout) / p.Cout;
-    if (p.Cout <= 32 || waste64 - waste32 >= 0.15) return launch_cfg<128, 32, 4, 1, 1, BK, MODE, POOL2, GATE, PW>(p, s);
+    if (p.Cout <= 32 || waste64 - waste32 >= 0.15) return launch_cfg<128, 32, 4, 1, 1, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);
     // fewer 64x64 tiles than CUs (resnet18 @84 layer4: 29 x 8 tiles for 256 CUs): 32x32 tiles with the four waves
     // splitting K give 4x the blocks (-7..-11 % time on those layers; neutral or worse everywhere else)
     if constexpr (MODE == 0 && !POOL2 && BK == 32)
-        if (cdiv(p.M, 64) * cdiv(p.Cout, 64) < 256) return launch_cfg<32, 32, 1, 1, 4, BK, MODE, POOL2, GATE, PW>(p, s);
-    return launch_cfg<64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW>(p, s);
+        if (cdiv(p.M, 64) * cdiv(p.Cout, 64) < 256) return launch_cfg<32, 32, 1, 1, 4, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);
+    return launch_cfg<64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);
 }
 
-template <int MODE, bool POOL2, bool GATE, bool PW>
+template <int MODE, bool POOL2, bool GATE, bool PW, bool RPOST = false>
 static int launch_bk(ConvParams& p, int bk, hipStream_t s) {
     if constexpr (MODE == 1) {
         return launch_tiled<32, 1, POOL2, false, false>(p, s);
     } else {
-        if (bk == 32) return launch_tiled<32, 0, POOL2, GATE, PW>(p, s);
-        if (bk == 16) return launch_tiled<16, 0, POOL2, GATE, PW>(p, s);
-        return launch_tiled<8, 0, POOL2, GATE, PW>(p, s);
+        if (bk == 32) return launch_tiled<32, 0, POOL2, GATE, PW, RPOST>(p, s);
+        if (bk == 16) return launch_tiled<16, 0, POOL2, GATE, PW, RPOST>(p, s);
+        return launch_tiled<8, 0, POOL2, GATE, PW, RPOST>(p, s);
     }
 }
 
@@ -721,6 +729,10 @@ int launch_conv(const ConvDesc& d, hipStream_t s) {
     ORBIT_REQUIRE(!(d.pool2 && d.residual), "conv: pool2 cannot be combined with a residual input");
     ORBIT_REQUIRE(d.Cout % 4 == 0, "conv: Cout %% 4 != 0 (Cout=%d): the epilogue writes float4 rows", d.Cout);
     const bool pw = !d.x_nchw && d.KH == 1 && d.KW == 1 && d.pad_t == 0 && d.pad_l == 0;
+    // the post-activation skip is compiled for the layers that have it (timm ConvBnAct: a plain K x K NHWC conv)
+    ORBIT_REQUIRE(!d.res_post || (d.residual && !pw && !d.x_nchw && !d.pool2 && !d.gate && !d.y_raw && !d.stats && !d.stats_only),
+                  "conv: the post-activation skip needs a residual and a plain K x K NHWC conv (no gate, fused pooling, pointwise "
+                  "form, statistics or dual output)");
     if (d.stats_blocks) *d.stats_blocks = 0;
     // opt-in: three-way bf16 split of both operands on the bf16 matrix cores (a function of the layer only, like every routing
     // rule here: a frame's bits do not depend on its batch)
@@ -774,14 +786,19 @@ int launch_conv(const ConvDesc& d, hipStream_t s) {
     if (d.x_nchw) rc = d.pool2 ? launch_bk<1, true, false, false>(p, bk, s) : launch_bk<1, false, false, false>(p, bk, s);
     else if (pw && !d.pool2) rc = d.gate ? launch_bk<0, false, true, true>(p, bk, s) : launch_bk<0, false, false, true>(p, bk, s);
     else if (d.gate) rc = launch_bk<0, false, true, false>(p, bk, s);
+    else if (d.res_post) rc = launch_bk<0, false, false, false, true>(p, bk, s);
     else rc = d.pool2 ? launch_bk<0, true, false, false>(p, bk, s) : launch_bk<0, false, false, false>(p, bk, s);
     if (rc == ORBIT_OK && p.stats) *d.stats_blocks = p.m_tiles;  // (launch_cfg2 set the tiling it chose)
     if (rc != ORBIT_OK || p.ksplit <= 1) return rc;
     const size_t mn4 = (size_t)p.M * p.Cout / 4;
     const int blocks = (int)std::min<size_t>((mn4 + 255) / 256, 4096);
     const int rec = prof_start("conv_splitk_reduce", 0.0, 4.0 * (p.ksplit + 1) * (double)p.M * p.Cout, s);
-    conv_splitk_reduce_kernel<<<blocks, 256, 0, s>>>(p.part, p.ksplit, mn4, p.Cout / 4, p.scale, p.shift, p.residual, p.act,
-                                                     p.y);
+    if (d.res_post)
+        conv_splitk_reduce_kernel<true><<<blocks, 256, 0, s>>>(p.part, p.ksplit, mn4, p.Cout / 4, p.scale, p.shift, p.residual,
+                                                               p.act, p.y);
+    else
+        conv_splitk_reduce_kernel<false><<<blocks, 256, 0, s>>>(p.part, p.ksplit, mn4, p.Cout / 4, p.scale, p.shift, p.residual,
+                                                                p.act, p.y);
     prof_stop(rec, s);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
@@ -825,7 +842,16 @@ int orbit_op_conv2d(const float* x, int x_nchw, const float* w, float* y, const 
                                const float* shift, const float* residual, const float* gate, int B, int H,
                                int W, int Cin, int Cout, int KH, int KW, int stride, int pad_top,
                                int pad_left, int Ho, int Wo, int act, int pool2, orbit_stream_t stream) {
+    return orbit_op_conv2d_ex(x, x_nchw, w, y, scale, shift, residual, gate, B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left,
+                              Ho, Wo, act, pool2, 0, stream);
+}
+
+int orbit_op_conv2d_ex(const float* x, int x_nchw, const float* w, float* y, const float* scale, const float* shift,
+                       const float* residual, const float* gate, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                       int stride, int pad_top, int pad_left, int Ho, int Wo, int act, int pool2, int flags,
+                       orbit_stream_t stream) {
     ORBIT_REQUIRE(x && w && y, "op_conv2d: null pointer");
+    ORBIT_REQUIRE((flags & ~ORBIT_CONV_RESIDUAL_POST_ACT) == 0, "op_conv2d_ex: unknown flags 0x%x", flags);
     ORBIT_REQUIRE(KH > 0 && KW > 0 && stride > 0, "op_conv2d: bad kernel geometry");
     hipStream_t s = (hipStream_t)stream;
     float* wp = nullptr;
@@ -840,7 +866,7 @@ int orbit_op_conv2d(const float* x, int x_nchw, const float* w, float* y, const 
         d.x = x, d.w_packed = wp, d.y = y, d.scale = scale, d.shift = shift, d.residual = residual;
         d.gate = gate, d.B = B, d.H = H, d.W = W, d.Cin = Cin, d.Cout = Cout, d.KH = KH, d.KW = KW;
         d.stride = stride, d.pad_t = pad_top, d.pad_l = pad_left, d.Ho = Ho, d.Wo = Wo, d.act = act;
-        d.pool2 = pool2, d.x_nchw = x_nchw;
+        d.pool2 = pool2, d.x_nchw = x_nchw, d.res_post = (flags & ORBIT_CONV_RESIDUAL_POST_ACT) ? 1 : 0;
         float* sk = nullptr;
         const size_t skf = conv_splitk_floats(d);
         if (skf) ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&sk), skf * sizeof(float), s));

@@ -101,6 +101,7 @@ struct Op {
     int in = -1, out = -1, res = -1;  // buffer ids (BUF_* above)
     int H = 0, W = 0, Cin = 0, Cout = 0, KH = 1, KW = 1, stride = 1, pad_t = 0, pad_l = 0, Ho = 0, Wo = 0;
     int act = ORBIT_ACT_NONE, pool2 = 0, x_nchw = 0, use_gate = 0;
+    int res_post = 0;                     // OP_CONV: `res` joins after the activation (ConvDesc::res_post; inference plans only)
     int weight = -1, bias = -1, bn = -1;  // param / BN indices
     size_t packed_off = 0;                // into the packed-weight pool
     size_t frag_off = SIZE_MAX;           // OP_CONV: the filter in MFMA-fragment order (csrc/pw_rgemm.hip) or SIZE_MAX
@@ -253,14 +254,15 @@ struct orbit_extractor {
         if (id >= 0 && id < 3) buf_elems[id] = std::max(buf_elems[id], elems);
     }
     // dense conv + BN (+act) (+residual) (+gate) (+pool2); returns output dims through Ho/Wo
+    // (the weight may have been registered before - a builder that follows the module registration order of a checkpoint)
     void add_conv(const std::string& wkey, int bn, int in, int out, int res, int H_, int W_, int Cin, int Cout,
                   int K, int stride, int pad_t, int pad_l, int Ho, int Wo, int act, int pool2, int x_nchw,
-                  int use_gate, int bias = -1) {
+                  int use_gate, int bias = -1, int res_post = 0) {
         Op o;
         o.kind = OP_CONV, o.in = in, o.out = out, o.res = res;
         o.H = H_, o.W = W_, o.Cin = Cin, o.Cout = Cout, o.KH = K, o.KW = K, o.stride = stride;
         o.pad_t = pad_t, o.pad_l = pad_l, o.Ho = Ho, o.Wo = Wo, o.act = act, o.pool2 = pool2;
-        o.x_nchw = x_nchw, o.use_gate = use_gate, o.bn = bn, o.bias = bias;
+        o.x_nchw = x_nchw, o.use_gate = use_gate, o.bn = bn, o.bias = bias, o.res_post = res_post;
         o.weight = pool.find(wkey) >= 0 ? pool.find(wkey) : add_param(wkey, (size_t)Cout * Cin * K * K);
         o.packed_off = packed_floats;
         packed_floats += conv_packed_floats(Cin, Cout, K, K, x_nchw);

@@ -1,9 +1,9 @@
-// Network runtime: builds a static launch plan for "resnet18", "efficientnet_b0" or "set_encoder" at a
+// Network runtime: builds a static launch plan for "resnet18", "efficientnet_b0", "efficientnet_v2_s" or "set_encoder" at a
 // given frame size, owns the parameters (loaded by torch state_dict key), repacks conv weights for the
 // MFMA kernel, folds BatchNorm (+ per-task FiLM gamma/beta) into per-channel scale/shift, and replays the
 // plan on a HIP stream. This is the native counterpart of
-//   model/feature_extractors.py:37-79   create_feature_extractor (timm tf_efficientnet_b0; resnet18 is the
-//                                        torchvision-layout network BASELINE.json's configs name)
+//   model/feature_extractors.py:37-79   create_feature_extractor (timm tf_efficientnet_b0 and tf_efficientnetv2_s_in21k;
+//                                        resnet18 is the torchvision-layout network BASELINE.json's configs name)
 //   model/set_encoders.py:81-120        SimplePrePoolNet
 //   model/few_shot_recognisers.py:99-153 _get_features[_in_batches] (one call = one mini-batch of frames)
 //   model/film.py:38-74                 which BatchNorms are FiLM-modulated
@@ -74,6 +74,46 @@ static int build_resnet18(orbit_extractor* fe, int H, int W) {
     return ORBIT_OK;
 }
 
+// ---- MBConv pieces shared by the EfficientNet builders ---------------------------------------------
+static int param_of(orbit_extractor* fe, const std::string& key, size_t numel) {  // (a builder may have registered it already)
+    const int k = fe->pool.find(key);
+    return k >= 0 ? k : fe->add_param(key, numel);
+}
+// depthwise K x K (TF "SAME") + BatchNorm + SiLU, emitting the squeeze-excite pooling partials
+static void add_dw(orbit_extractor* fe, const std::string& wkey, int bnidx, int in, int out, int C, int K, int stride, int hh,
+                   int ww, int& ho, int& wo) {
+    Op o;
+    o.kind = OP_DWCONV, o.in = in, o.out = out, o.H = hh, o.W = ww, o.Cin = C, o.Cout = C;
+    o.KH = o.KW = K, o.stride = stride, o.act = ORBIT_ACT_SILU, o.bn = bnidx;
+    same_pad(hh, K, stride, o.Ho, o.pad_t);
+    same_pad(ww, K, stride, o.Wo, o.pad_l);
+    o.weight = param_of(fe, wkey, (size_t)C * K * K);
+    o.packed_off = fe->packed_floats;
+    fe->packed_floats += (size_t)(C * K * K + 3) / 4 * 4;
+    o.pool_partial = 1;
+    fe->max_partial = std::max(fe->max_partial, (size_t)dwconv_se_chunks(o.Ho) * C);
+    ho = o.Ho, wo = o.Wo;
+    fe->note_buf(out, (size_t)ho * wo * C);
+    fe->macs += (double)ho * wo * C * K * K;
+    fe->ops.push_back(o);
+}
+// squeeze-excite gate of C channels through R hidden units; the pooled sums come from the depthwise kernel's partials
+// (BUF_POOLED), not from a re-read of the tensor
+static void add_se(orbit_extractor* fe, const std::string& p, int C, int R, int hh, int ww, int chunks) {
+    Op s;
+    s.kind = OP_SE, s.in = BUF_POOLED, s.out = BUF_GATE, s.Cin = C, s.R = R;
+    s.se_chunks = chunks, s.se_hw = hh * ww;
+    s.packed_off = fe->packed_floats;  // W2 transposed to [R][C]
+    fe->packed_floats += (size_t)(C * R + 3) / 4 * 4;
+    s.se_w1 = fe->add_param(p + ".conv_reduce.weight", (size_t)R * C);
+    s.se_b1 = fe->add_param(p + ".conv_reduce.bias", R);
+    s.se_w2 = fe->add_param(p + ".conv_expand.weight", (size_t)C * R);
+    s.se_b2 = fe->add_param(p + ".conv_expand.bias", C);
+    fe->macs += 2.0 * C * R;
+    fe->max_se_c = std::max(fe->max_se_c, C);
+    fe->ops.push_back(s);
+}
+
 // ---- efficientnet_b0, timm `tf_` variant (SAME padding, BN eps 1e-3), num_classes=0 --------------
 static int build_efficientnet_b0(orbit_extractor* fe, int H, int W, bool unfused) {
     fe->out_size = 1280;
@@ -96,39 +136,6 @@ static int build_efficientnet_b0(orbit_extractor* fe, int H, int W, bool unfused
     if (fuse_stem) stem_weight = fe->add_param("conv_stem.weight", (size_t)32 * 27);
     else fe->add_conv("conv_stem.weight", bn, -1, 0, -1, H, W, 3, 32, 3, 2, pt, pl, h, w, ORBIT_ACT_SILU, 0, 1, 0);
     int cur = 0, cin = 32;
-
-    auto add_dw = [&](const std::string& wkey, int bnidx, int in, int out, int C, int K, int stride, int hh,
-                      int ww, int& ho, int& wo) {
-        Op o;
-        o.kind = OP_DWCONV, o.in = in, o.out = out, o.H = hh, o.W = ww, o.Cin = C, o.Cout = C;
-        o.KH = o.KW = K, o.stride = stride, o.act = ORBIT_ACT_SILU, o.bn = bnidx;
-        same_pad(hh, K, stride, o.Ho, o.pad_t);
-        same_pad(ww, K, stride, o.Wo, o.pad_l);
-        o.weight = fe->add_param(wkey, (size_t)C * K * K);
-        o.packed_off = fe->packed_floats;
-        fe->packed_floats += (size_t)(C * K * K + 3) / 4 * 4;
-        o.pool_partial = 1;
-        fe->max_partial = std::max(fe->max_partial, (size_t)dwconv_se_chunks(o.Ho) * C);
-        ho = o.Ho, wo = o.Wo;
-        fe->note_buf(out, (size_t)ho * wo * C);
-        fe->macs += (double)ho * wo * C * K * K;
-        fe->ops.push_back(o);
-    };
-    auto add_se = [&](const std::string& p, int buf, int C, int R, int hh, int ww, int chunks) {
-        (void)buf;  // the pooled sums come from the depthwise kernel's partials (BUF_POOLED), not from a re-read
-        Op s;
-        s.kind = OP_SE, s.in = BUF_POOLED, s.out = BUF_GATE, s.Cin = C, s.R = R;
-        s.se_chunks = chunks, s.se_hw = hh * ww;
-        s.packed_off = fe->packed_floats;  // W2 transposed to [R][C]
-        fe->packed_floats += (size_t)(C * R + 3) / 4 * 4;
-        s.se_w1 = fe->add_param(p + ".conv_reduce.weight", (size_t)R * C);
-        s.se_b1 = fe->add_param(p + ".conv_reduce.bias", R);
-        s.se_w2 = fe->add_param(p + ".conv_expand.weight", (size_t)C * R);
-        s.se_b2 = fe->add_param(p + ".conv_expand.bias", C);
-        fe->macs += 2.0 * C * R;
-        fe->max_se_c = std::max(fe->max_se_c, C);
-        fe->ops.push_back(s);
-    };
 
     // stage 0: DepthwiseSeparableConv (not FiLM-tagged, film.py:41-48)
     {
@@ -161,10 +168,10 @@ static int build_efficientnet_b0(orbit_extractor* fe, int H, int W, bool unfused
             fe->macs += (double)h * w * 27 * 32 + (double)ho * wo * 32 * 9;
             fe->ops.push_back(o);
         } else {
-            add_dw(p + ".conv_dw.weight", bn1, cur, t1, 32, 3, 1, h, w, ho, wo);
+            add_dw(fe, p + ".conv_dw.weight", bn1, cur, t1, 32, 3, 1, h, w, ho, wo);
             se_chunks0 = dwconv_se_chunks(ho);
         }
-        add_se(p + ".se", t1, 32, 8, ho, wo, se_chunks0);
+        add_se(fe, p + ".se", 32, 8, ho, wo, se_chunks0);
         const int bn2 = fe->add_bn(p + ".bn2", 16, eps, false);
         fe->add_conv(p + ".conv_pw.weight", bn2, t1, t2, -1, ho, wo, 32, 16, 1, 1, 0, 0, ho, wo, ORBIT_ACT_NONE,
                      0, 0, 1);
@@ -207,10 +214,10 @@ static int build_efficientnet_b0(orbit_extractor* fe, int H, int W, bool unfused
                 fe->add_conv(p + ".conv_pw.weight", bn1, cur, t1, -1, h, w, cin, mid, 1, 1, 0, 0, h, w, ORBIT_ACT_SILU,
                              0, 0, 0);
                 const int bn2 = fe->add_bn(p + ".bn2", mid, eps, true);  // InvertedResidual.bn2 is FiLM-tagged
-                add_dw(p + ".conv_dw.weight", bn2, t1, t2, mid, K, stride, h, w, ho, wo);
+                add_dw(fe, p + ".conv_dw.weight", bn2, t1, t2, mid, K, stride, h, w, ho, wo);
                 se_chunks = dwconv_se_chunks(ho);
             }
-            add_se(p + ".se", t2, mid, rd, ho, wo, se_chunks);
+            add_se(fe, p + ".se", mid, rd, ho, wo, se_chunks);
             const int bn3 = fe->add_bn(p + ".bn3", cout, eps, false);
             // project: reads t2 (gated), residual from cur, writes t1 (free again)
             fe->add_conv(p + ".conv_pwl.weight", bn3, t2, t1, skip ? cur : -1, ho, wo, mid, cout, 1, 1, 0, 0, ho, wo,
@@ -219,6 +226,87 @@ static int build_efficientnet_b0(orbit_extractor* fe, int H, int W, bool unfused
         }
     }
     const int t1 = (cur + 1) % 3;
+    bn = fe->add_bn("bn2", 1280, eps, true);  // root bn2 is FiLM-tagged
+    fe->add_conv("conv_head.weight", bn, cur, t1, -1, h, w, cin, 1280, 1, 1, 0, 0, h, w, ORBIT_ACT_SILU, 0, 0, 0);
+    Op o;
+    o.kind = OP_AVGPOOL, o.in = t1, o.out = BUF_FEATS, o.H = h, o.W = w, o.Cin = 1280, o.Cout = 1280;
+    fe->ops.push_back(o);
+    return ORBIT_OK;
+}
+
+// ---- efficientnet_v2_s, timm `tf_efficientnetv2_s_in21k` (SAME padding, BN eps 1e-3), num_classes=0 -----------------
+// stem 3 -> 24 /2 | cn_r2_k3_s1_e1_c24_skip | er_r4_k3_s2_e4_c48 | er_r4_k3_s2_e4_c64 | ir_r6_k3_s2_e4_c128_se0.25 |
+// ir_r9_k3_s1_e6_c160_se0.25 | ir_r15_k3_s2_e6_c256_se0.25 | head 256 -> 1280, global average pool.
+// Parameters are registered in timm's module order (conv before its BatchNorm), so the enumeration IS the checkpoint's
+// state_dict order. FiLM slots (model/film.py:38-56): root bn1 / bn2, bn1 of every ConvBnAct and EdgeResidual, bn2 of every
+// InvertedResidual. Every block is the plain conv (+ depthwise + squeeze-excite) sequence of the kernels efficientnet_b0 runs
+// at 14x14 / 7x7; the one new device form is ConvBnAct's skip, which joins AFTER the activation (Op::res_post) - the reason
+// this plan has no training path (plan_trainable, csrc/extractor_train.hip).
+static int build_efficientnet_v2_s(orbit_extractor* fe, int H, int W) {
+    fe->out_size = 1280;
+    const float eps = 1e-3f;
+    int h, w, pt, pl;
+    same_pad(H, 3, 2, h, pt);
+    same_pad(W, 3, 2, w, pl);
+    fe->add_param("conv_stem.weight", (size_t)24 * 27);
+    int bn = fe->add_bn("bn1", 24, eps, true);  // root bn1 is FiLM-tagged
+    fe->add_conv("conv_stem.weight", bn, -1, 0, -1, H, W, 3, 24, 3, 2, pt, pl, h, w, ORBIT_ACT_SILU, 0, 1, 0);
+    int cur = 0, cin = 24;
+    // dense 3x3 conv (TF "SAME") + BatchNorm (+ SiLU) (+ skip, before or after the activation)
+    auto conv3 = [&](const std::string& wkey, int bnidx, int in, int out, int res, int ci, int co, int stride, int act,
+                     int res_post, int& ho, int& wo) {
+        int ptt, pll;
+        same_pad(h, 3, stride, ho, ptt);
+        same_pad(w, 3, stride, wo, pll);
+        fe->add_conv(wkey, bnidx, in, out, res, h, w, ci, co, 3, stride, ptt, pll, ho, wo, act, 0, 0, 0, -1, res_post);
+    };
+    // {kind (0 ConvBnAct, 1 EdgeResidual, 2 InvertedResidual), repeats, stride, expansion, out channels}
+    const int cfg[6][5] = {{0, 2, 1, 1, 24}, {1, 4, 2, 4, 48}, {1, 4, 2, 4, 64}, {2, 6, 2, 4, 128}, {2, 9, 1, 6, 160}, {2, 15, 2, 6, 256}};
+    for (int s = 0; s < 6; ++s) {
+        for (int r = 0; r < cfg[s][1]; ++r) {
+            const int kind = cfg[s][0], stride = r == 0 ? cfg[s][2] : 1, cout = cfg[s][4];
+            const int mid = cin * cfg[s][3];
+            const std::string p = "blocks." + std::to_string(s) + "." + std::to_string(r);
+            const int t1 = (cur + 1) % 3, t2 = (cur + 2) % 3;
+            const bool skip = stride == 1 && cin == cout;
+            int ho, wo;
+            if (kind == 0) {
+                // ConvBnAct: x + silu(bn1(conv(x))) - the skip joins after the activation
+                fe->add_param(p + ".conv.weight", (size_t)cout * cin * 9);
+                const int bn1 = fe->add_bn(p + ".bn1", cout, eps, true);
+                conv3(p + ".conv.weight", bn1, cur, t1, skip ? cur : -1, cin, cout, stride, ORBIT_ACT_SILU, skip ? 1 : 0, ho, wo);
+                cur = t1;
+            } else if (kind == 1) {
+                // EdgeResidual: conv_exp 3x3 (carries the stride), bn1 + SiLU, conv_pwl 1x1, bn2 (+ x)
+                fe->add_param(p + ".conv_exp.weight", (size_t)mid * cin * 9);
+                const int bn1 = fe->add_bn(p + ".bn1", mid, eps, true);
+                conv3(p + ".conv_exp.weight", bn1, cur, t1, -1, cin, mid, stride, ORBIT_ACT_SILU, 0, ho, wo);
+                fe->add_param(p + ".conv_pwl.weight", (size_t)cout * mid);
+                const int bn2 = fe->add_bn(p + ".bn2", cout, eps, false);
+                fe->add_conv(p + ".conv_pwl.weight", bn2, t1, t2, skip ? cur : -1, ho, wo, mid, cout, 1, 1, 0, 0, ho, wo,
+                             ORBIT_ACT_NONE, 0, 0, 0);
+                cur = t2;
+            } else {
+                // InvertedResidual: conv_pw, bn1 + SiLU, conv_dw 3x3, bn2 + SiLU, squeeze-excite, gated conv_pwl, bn3 (+ x)
+                const int rd = (int)(cin * 0.25 + 0.5);  // timm: round(in_chs * se_ratio)
+                fe->add_param(p + ".conv_pw.weight", (size_t)mid * cin);
+                const int bn1 = fe->add_bn(p + ".bn1", mid, eps, false);
+                fe->add_conv(p + ".conv_pw.weight", bn1, cur, t1, -1, h, w, cin, mid, 1, 1, 0, 0, h, w, ORBIT_ACT_SILU, 0, 0, 0);
+                fe->add_param(p + ".conv_dw.weight", (size_t)mid * 9);
+                const int bn2 = fe->add_bn(p + ".bn2", mid, eps, true);  // InvertedResidual.bn2 is FiLM-tagged
+                add_dw(fe, p + ".conv_dw.weight", bn2, t1, t2, mid, 3, stride, h, w, ho, wo);
+                add_se(fe, p + ".se", mid, rd, ho, wo, dwconv_se_chunks(ho));
+                fe->add_param(p + ".conv_pwl.weight", (size_t)cout * mid);
+                const int bn3 = fe->add_bn(p + ".bn3", cout, eps, false);
+                fe->add_conv(p + ".conv_pwl.weight", bn3, t2, t1, skip ? cur : -1, ho, wo, mid, cout, 1, 1, 0, 0, ho, wo,
+                             ORBIT_ACT_NONE, 0, 0, 1);
+                cur = t1;
+            }
+            cin = cout, h = ho, w = wo;
+        }
+    }
+    const int t1 = (cur + 1) % 3;
+    fe->add_param("conv_head.weight", (size_t)1280 * cin);
     bn = fe->add_bn("bn2", 1280, eps, true);  // root bn2 is FiLM-tagged
     fe->add_conv("conv_head.weight", bn, cur, t1, -1, h, w, cin, 1280, 1, 1, 0, 0, h, w, ORBIT_ACT_SILU, 0, 0, 0);
     Op o;
@@ -297,6 +385,7 @@ int orbit_extractor_create_ex(const char* name, int H, int W, int flags, orbit_e
     int rc;
     if (fe->name == "resnet18") rc = build_resnet18(fe, H, W);
     else if (fe->name == "efficientnet_b0") rc = build_efficientnet_b0(fe, H, W, (flags & ORBIT_PLAN_UNFUSED) != 0);
+    else if (fe->name == "efficientnet_v2_s") rc = build_efficientnet_v2_s(fe, H, W);  // (no fused ops: one plan for both flags)
     else if (fe->name == "set_encoder") rc = build_set_encoder(fe, H, W);
     else rc = set_err(ORBIT_ERR_ARG, "Invalid feature_extractor_name: %s", name);
     if (rc != ORBIT_OK) {
@@ -540,7 +629,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                 d.gate = o.use_gate ? buf(BUF_GATE) : nullptr;
                 d.B = B, d.H = o.H, d.W = o.W, d.Cin = o.Cin, d.Cout = o.Cout, d.KH = o.KH, d.KW = o.KW;
                 d.stride = o.stride, d.pad_t = o.pad_t, d.pad_l = o.pad_l, d.Ho = o.Ho, d.Wo = o.Wo;
-                d.act = o.act, d.pool2 = o.pool2, d.x_nchw = o.x_nchw;
+                d.act = o.act, d.pool2 = o.pool2, d.x_nchw = o.x_nchw, d.res_post = o.res_post;
                 d.splitk_ws = reinterpret_cast<float*>(ws + L.splitk);
                 rc = launch_conv(d, s);
                 break;

@@ -63,6 +63,7 @@ static bool plan_trainable(const orbit_extractor* fe) {
         if (o.kind == OP_MBFRONT) return false;
         if ((o.kind == OP_CONV || o.kind == OP_DWCONV) && o.bn < 0) return false;
         if (o.kind == OP_CONV && o.use_gate && (o.pool2 || o.x_nchw)) return false;
+        if (o.kind == OP_CONV && o.res_post) return false;  // efficientnet_v2_s: no backward through the post-activation skip
     }
     return true;
 }

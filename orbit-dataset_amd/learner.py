@@ -42,7 +42,7 @@ from .utils.eval_metrics import TestEvaluator
 def build_parser():
     p = argparse.ArgumentParser(description="single-step learner on the MI355X-native recogniser (synthetic tasks)")
     # flags shared with the reference (utils/args.py)
-    p.add_argument("--feature_extractor", default="efficientnet_b0", choices=["efficientnet_b0", "resnet18", "vit_s_32", "vit_b_32", "vit_b_32_clip"])
+    p.add_argument("--feature_extractor", default="efficientnet_b0", choices=["efficientnet_b0", "efficientnet_v2_s", "resnet18", "vit_s_32", "vit_b_32", "vit_b_32_clip"])
     p.add_argument("--learn_extractor", action="store_true")
     p.add_argument("--adapt_features", action="store_true")
     p.add_argument("--classifier", default="proto", choices=["proto", "proto_cosine", "versa", "mahalanobis", "linear"])
@@ -153,6 +153,16 @@ def verify_args(args):
         elif "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
             sys.exit("error: --feature_extractor %s is inference-only here (no backward through a ViT): use --mode test "
                      "without --learn_extractor / --with_lite%s" % (fe, " / --adapt_features" if multistep else ""))
+    if fe == "efficientnet_v2_s":
+        # reference utils/args.py:187-188; any frame size, as efficientnet_b0. The native plan has no backward (its ConvBnAct
+        # blocks add the skip after the activation, csrc/extractor_train.hip plan_trainable): everything that would send a
+        # gradient or batch statistics through the extractor is refused here rather than at the first forward
+        args.frame_norm_method = "imagenet_inception"
+        multistep = getattr(args, "personalize_num_grad_steps", None) is not None
+        if "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
+            sys.exit("error: --feature_extractor efficientnet_v2_s is inference-only here (no backward through its "
+                     "post-activation skips): use --mode test without --learn_extractor / --with_lite%s"
+                     % (" / --adapt_features" if multistep else ""))
 
 
 def frame_accuracy(logits, label):

@@ -5,7 +5,8 @@ same signature and return value `(extractor, film_parameter_names)`, `extractor.
 parameters when `learn_extractor=False`, FiLM tagging when `with_film=True`. The reference builds timm
 networks; here the network lives in liborbit_hip.so and this module is only its parameter container
 (state_dict-compatible key names: torchvision layout for resnet18, timm `tf_efficientnet_b0` layout for
-efficientnet_b0, timm VisionTransformer layout for vit_s_32 / vit_b_32 / vit_b_32_clip) plus the call into
+efficientnet_b0, timm `tf_efficientnetv2_s_in21k` layout for efficientnet_v2_s, timm VisionTransformer layout for
+vit_s_32 / vit_b_32 / vit_b_32_clip) plus the call into
 `orbit_extractor_forward` (`orbit_vit_forward` for the transformers, csrc/vit.hip). `resnet18` and arbitrary frame sizes are
 additions BASELINE.json's configs require (the snapshot's args.py:27,77 no longer list them).
 
@@ -20,8 +21,8 @@ import torch.nn as nn
 from .. import _lib
 from .autograd import ExtractorFunction, VitFunction
 
-_EXTRACTOR_OUTPUT = {"resnet18": 512, "efficientnet_b0": 1280}
-_BN_EPS = {"resnet18": 1e-5, "efficientnet_b0": 1e-3, "set_encoder": 1e-5}
+_EXTRACTOR_OUTPUT = {"resnet18": 512, "efficientnet_b0": 1280, "efficientnet_v2_s": 1280}
+_BN_EPS = {"resnet18": 1e-5, "efficientnet_b0": 1e-3, "efficientnet_v2_s": 1e-3, "set_encoder": 1e-5}
 
 
 class ParamNode(nn.Module):
@@ -512,6 +513,73 @@ class EfficientNetB0(HipNetwork):
         return (cout, numel // cout, 1, 1)
 
 
+class EfficientNetV2S(HipNetwork):
+    """timm 0.6.12 `tf_efficientnetv2_s_in21k` with num_classes=0 (reference model/feature_extractors.py:31-48): same parameter
+    tree, state_dict keys, order and shapes as the timm module; FiLM on root bn1 / bn2, ConvBnAct.bn1, EdgeResidual.bn1 and
+    InvertedResidual.bn2 (reference model/film.py:38-56). Any frame size.
+
+    Inference only: the ConvBnAct blocks add their skip after the activation, which the training runtime has no backward for
+    (orbit_extractor_supports_training is 0 for this plan). A forward that would record a tape or use batch statistics raises
+    NotImplementedError before anything is launched.
+
+    One divergence from the sibling classes: every BatchNorm node's buffers are ordered (running_mean, running_var,
+    num_batches_tracked) as nn.BatchNorm2d registers them, so that the state_dict ORDER equals the timm module's;
+    HipNetwork._register_leaf leaves (running_mean, num_batches_tracked, running_var), which ResNet18 and EfficientNetB0 keep
+    (their key-list fixtures compare sets of keys and loads go by name, so the order matters to nobody there)."""
+
+    def __init__(self):
+        super().__init__("efficientnet_v2_s")
+        # the leaves arrive as (running_mean, running_var) and num_batches_tracked was registered with the first of them
+        for m in self.modules():
+            if "num_batches_tracked" in m._buffers:
+                m._buffers["num_batches_tracked"] = m._buffers.pop("num_batches_tracked")
+
+    def _leaf_shape(self, key, numel):
+        if not key.endswith(".weight") or ".bn" in key or key.startswith("bn"):
+            return (numel,)
+        if key == "conv_stem.weight":
+            return (24, 3, 3, 3)
+        # as EfficientNetB0: a conv's output-channel count is the size of the BatchNorm / bias that follows it in module order
+        keys = dict(self._keys)
+        prefix = key[: -len(".weight")]
+        if prefix.endswith("se.conv_reduce") or prefix.endswith("se.conv_expand"):
+            cout = keys[prefix + ".bias"]
+            return (cout, numel // cout, 1, 1)
+        if prefix == "conv_head":
+            return (1280, numel // 1280, 1, 1)
+        blk, conv = prefix.rsplit(".", 1)
+        if conv == "conv_dw":
+            c = keys[blk + ".bn2.weight"]
+            return (c, 1, 3, 3)
+        if conv in ("conv", "conv_exp"):  # ConvBnAct / EdgeResidual: 3x3, then bn1
+            cout = keys[blk + ".bn1.weight"]
+            return (cout, numel // (cout * 9), 3, 3)
+        if conv == "conv_pw":
+            bn = ".bn1"
+        else:  # conv_pwl: EdgeResidual -> bn2, InvertedResidual -> bn3
+            bn = ".bn3" if blk + ".bn3.weight" in keys else ".bn2"
+        cout = keys[blk + bn + ".weight"]
+        return (cout, numel // cout, 1, 1)
+
+    _REFUSAL = ("efficientnet_v2_s is an inference-only extractor: no native backward and no batch-statistics BatchNorm (LITE "
+                "meta-training, --learn_extractor, FiLM gradients); call it in eval() under torch.no_grad() with frozen parameters")
+
+    def wants_grad(self, film=None):
+        if super().wants_grad(film):
+            raise NotImplementedError(self._REFUSAL)
+        return False
+
+    def forward(self, x, film=None, out=None, check_sync=True):
+        # refused here, before a plan is built or a parameter uploaded: nothing is launched
+        if self.training and x.numel() > 0:
+            raise NotImplementedError(self._REFUSAL)
+        self.wants_grad(film)
+        return super().forward(x, film=film, out=out, check_sync=check_sync)
+
+    def _forward_train(self, plan, x, film, use_tape, bn_train, out):  # (the native plan reports no training path either)
+        raise NotImplementedError(self._REFUSAL)
+
+
 _VIT_OUTPUT = {"vit_s_32": 384, "vit_b_32": 768, "vit_b_32_clip": 768}
 VIT_FRAME_SIZE = 224
 
@@ -648,6 +716,8 @@ def create_feature_extractor(feature_extractor_name: str, pretrained: bool = Tru
         feature_extractor = ResNet18()
     elif feature_extractor_name == "efficientnet_b0":
         feature_extractor = EfficientNetB0()
+    elif feature_extractor_name == "efficientnet_v2_s":
+        feature_extractor = EfficientNetV2S()
     elif feature_extractor_name in _VIT_OUTPUT:
         feature_extractor = VisionTransformer(feature_extractor_name)
     else:

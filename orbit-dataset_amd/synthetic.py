@@ -39,6 +39,8 @@ def _calibration(name):
 def _network_of(module):
     """Which synthetic checkpoint a module's keys belong to, judged from its state_dict keys."""
     keys = module if isinstance(module, (set, list, tuple)) else set(module.state_dict().keys())
+    if "blocks.0.0.conv.weight" in keys:  # a ConvBnAct first stage: timm tf_efficientnetv2_s (no calibration asset)
+        return "efficientnet_v2_s"
     if "conv_stem.weight" in keys:
         return "efficientnet_b0"
     if "layer4.1.conv2.weight" in keys:
@@ -71,8 +73,31 @@ def _is_branch_tail_bn(key):
     return (in_resnet_layer and parts[-2] == "bn2") or parts[-2] == "bn3"
 
 
-def synth_tensor(key, shape, seed=DEFAULT_SEED, film_strength=0.1):
-    """Deterministic value for the state_dict entry `key` of the given shape."""
+def _branch_tail_bns(keys):
+    """{BatchNorm prefix: scale of its weight} for the last BatchNorm of every block of efficientnet_v2_s, which the key alone
+    does not tell: the bn1 of a ConvBnAct block (sibling `conv`), the bn2 of an EdgeResidual block (sibling `conv_exp`), the bn3
+    of an InvertedResidual block. 0.25 where the block has a skip, as in the other networks (unscaled, the four-fold expanded
+    EdgeResidual branches triple the variance of the stream at every block). The first block of stages 1-5 changes width or
+    stride and has no skip: there is no calibration asset for this network, so no BatchNorm behind it renormalises, and at
+    0.25 each of them cuts the frame-dependent part of the signal to ~1/8 under the BatchNorm biases (1e-4 of the features
+    after five stages). Unscaled, the EdgeResidual ones grow it by ~1.7 per stage (features beyond 50) while the
+    InvertedResidual ones (squeeze-excite gate ~0.5 in the branch) about hold it: 0.5 and 1.0 keep it O(1) to the head.
+    A stop-gap: the other networks get this from a calibration asset (`_calibration`); once
+    assets/bn_calibration_efficientnet_v2_s.npz exists, this rule and synth_tensor's `branch_tail` go."""
+    out = {}
+    for k in keys:
+        for conv, bn in (("conv", "bn1"), ("conv_exp", "bn2"), ("conv_pwl", "bn3")):
+            if k.endswith("." + conv + ".weight"):
+                blk = k[: -len(conv + ".weight")]  # "blocks.S.R."
+                if blk + bn + ".weight" in keys:
+                    stage, repeat = blk.split(".")[1:3]
+                    out[blk + bn] = 0.25 if (stage == "0" or repeat != "0") else (0.5 if bn == "bn2" else 1.0)
+    return out
+
+
+def synth_tensor(key, shape, seed=DEFAULT_SEED, film_strength=0.1, branch_tail=None):
+    """Deterministic value for the state_dict entry `key` of the given shape. `branch_tail`: the factor on a BatchNorm scale
+    that ends a residual branch (None: 0.25 where the key says so, `_is_branch_tail_bn`)."""
     g = _gen(seed, key)
     leaf = key.rsplit(".", 1)[-1]
     if leaf == "num_batches_tracked":
@@ -91,7 +116,9 @@ def synth_tensor(key, shape, seed=DEFAULT_SEED, film_strength=0.1):
         return (1.0 / shape[1] ** 0.5) * _randn(shape, g)
     if leaf == "weight":  # BatchNorm / LayerNorm scale
         w = _rand(shape, g, 0.5, 1.5)
-        return 0.25 * w if _is_branch_tail_bn(key) else w
+        if branch_tail is None:
+            return 0.25 * w if _is_branch_tail_bn(key) else w
+        return branch_tail * w
     if leaf == "bias":
         return 0.1 * _randn(shape, g)
     return 0.1 * _randn(shape, g)
@@ -110,7 +137,9 @@ def synthetic_state_dict(module, seed=DEFAULT_SEED, prefix="", film_strength=0.1
                 return k[len(sub):]
         return k
 
-    sd = {k: synth_tensor(prefix + seed_key(k), tuple(v.shape), seed, film_strength)
+    keys = [seed_key(k) for k in module.state_dict().keys()]
+    tails = _branch_tail_bns(set(keys)) if _network_of(set(keys)) == "efficientnet_v2_s" else {}
+    sd = {k: synth_tensor(prefix + seed_key(k), tuple(v.shape), seed, film_strength, tails.get(seed_key(k).rsplit(".", 1)[0]))
           for k, v in module.state_dict().items()}
     if use_calibration and seed == DEFAULT_SEED and prefix == "":
         for sub in ("",) + _SUBNETS:

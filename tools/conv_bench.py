@@ -1,5 +1,6 @@
 """Micro-benchmark of the MFMA implicit-GEMM convolution on the layer shapes of the bench workloads.
-Usage (GPU box): python tools/conv_bench.py [resnet18_84|resnet18_224|effnet_224]   — prints TFLOP/s per layer."""
+Usage (GPU box): python tools/conv_bench.py [resnet18_84|resnet18_224|effnet_224|effnetv2_224|setenc_224]   — prints TFLOP/s per layer.
+(effnetv2_224: the stem and the 3x3 convs of efficientnet_v2_s, TF-SAME geometry; `bk` shows each under the K-tile caps.)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,6 +25,9 @@ SHAPES = {
         ("pwl240_80", 200, 14, 240, 80, 1, 1, 0, 0), ("pwl480_80", 200, 14, 480, 80, 1, 1, 0, 0),
         ("pwl672_112", 200, 14, 672, 112, 1, 1, 0, 0), ("pwl672_192", 200, 7, 672, 192, 1, 1, 0, 0),
         ("pwl1152_192", 200, 7, 1152, 192, 1, 1, 0, 0)],
+    "effnetv2_224": [  # stem, ConvBnAct, EdgeResidual conv_exp (first of a stage: stride 2, pad_top = pad_left = 0)
+        ("stem3x3", 200, 224, 3, 24, 3, 2, 0, 1), ("cn24_24", 200, 112, 24, 24, 3, 1, 1, 0), ("er24_96_s2", 200, 112, 24, 96, 3, 2, 0, 0),
+        ("er48_192", 200, 56, 48, 192, 3, 1, 1, 0), ("er48_192_s2", 200, 56, 48, 192, 3, 2, 0, 0), ("er64_256", 200, 28, 64, 256, 3, 1, 1, 0)],
     "setenc_224": [
         ("se_l1", 200, 224, 3, 64, 3, 1, 1, 1), ("se_l2", 200, 112, 64, 64, 3, 1, 1, 0), ("se_l3", 200, 56, 64, 64, 3, 1, 1, 0),
         ("se_l4", 200, 28, 64, 64, 3, 1, 1, 0), ("se_l5", 200, 14, 64, 64, 3, 1, 1, 0)],
@@ -39,7 +43,7 @@ def main():
     dev = torch.device("cuda", 0)
     import ctypes
     for name, B, H, Cin, Cout, K, stride, pad, nchw in SHAPES[which]:
-        Ho = -(-H // stride) if (which.startswith("effnet") and nchw) else (H + 2 * pad - K) // stride + 1
+        Ho = -(-H // stride) if (which.startswith("effnet") and K > 1) else (H + 2 * pad - K) // stride + 1
         x = torch.randn(B, Cin, H, H, device=dev) if nchw else torch.randn(B, H, H, Cin, device=dev)
         w = torch.randn(Cout, Cin, K, K, device=dev)
         y = torch.empty(B, Ho, Ho, Cout, device=dev)
