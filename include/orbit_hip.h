@@ -185,14 +185,22 @@ int orbit_set_mean(const float* x, int n, int D, float* out, orbit_stream_t stre
 
 /* ---- feature extractors / set encoder ---------------------------------------------------------- */
 /* name: "resnet18" | "efficientnet_b0" | "efficientnet_v2_s" | "set_encoder".  H,W: frame size the plan is built for.
- * "efficientnet_v2_s" (timm tf_efficientnetv2_s_in21k, num_classes = 0; 1280-d features) is an inference plan: its ConvBnAct
- * blocks add their skip after the activation, which the training runtime has no backward for, so
- * orbit_extractor_supports_training is 0 and the tape / backward-workspace size queries return 0 for it. */
+ * "efficientnet_v2_s" (timm tf_efficientnetv2_s_in21k, num_classes = 0; 1280-d features) is an inference plan by default: its
+ * ConvBnAct blocks add their skip after the activation, and orbit_extractor_supports_training is 0 and the tape /
+ * backward-workspace size queries return 0 for it - unless the plan was created with ORBIT_PLAN_RES_POST_BACKWARD (below), which
+ * opens the FROZEN training path: FiLM / BatchNorm weight and bias gradients under running statistics, nothing else. */
 int orbit_extractor_create(const char* name, int H, int W, orbit_extractor_t** out);
 /* flags: ORBIT_PLAN_UNFUSED = a plan for forwards that record a tape or use batch statistics (the LITE training step,
  * few_shot_recognisers.py:176-183): every MBConv block stays a conv + depthwise pair, whose outputs the backward needs;
  * same parameters in the same order as the default plan. */
 #define ORBIT_PLAN_UNFUSED 1
+/* ORBIT_PLAN_RES_POST_BACKWARD (may be combined with ORBIT_PLAN_UNFUSED; same ops, same parameters in the same order): the
+ * training runtime accepts a plan that holds a convolution whose skip joins after the activation ("efficientnet_v2_s";
+ * accepted and without effect for every other network). Such a plan trains in frozen form only: orbit_extractor_train_forward(_ex)
+ * returns ORBIT_ERR_STATE for bn_train != 0 and orbit_extractor_backward for bn_train != 0 or filter_grads != 0, before any
+ * launch - batch-statistics BatchNorm and filter gradients are not built for it. Without the flag the plan reports no training
+ * path at all, as before. */
+#define ORBIT_PLAN_RES_POST_BACKWARD 2
 int orbit_extractor_create_ex(const char* name, int H, int W, int flags, orbit_extractor_t** out);
 void orbit_extractor_destroy(orbit_extractor_t* fe);
 
@@ -574,6 +582,20 @@ int orbit_op_bn_stats_from_gram(const float* x, int P, int Cin, const float* w, 
 int orbit_op_bn_backward(const float* dout, const float* out, const float* y, int M, int C, const float* gamma,
                          const float* mean, const float* invstd, int train, int act, float* dy, float* dres,
                          float* dgamma, float* dbeta, orbit_stream_t stream);
+/* The same with the folded scale / shift of the forward (scale = gamma * invstd, shift = beta - mean * scale; needed for SiLU,
+ * which this entry admits: its derivative is taken at scale * y + shift) and flags. ORBIT_BN_RESIDUAL_POST_ACT: backward of
+ * out = act(BN(y)) + residual, the skip joining AFTER the activation (timm ConvBnAct): with g = dout * act'(scale * y + shift),
+ * dres receives dout (not g), dgamma / dbeta are the sums of g * xhat / g and dy is formed from g as above.
+ * dres_accumulate != 0: dres += instead of dres =. */
+#define ORBIT_BN_RESIDUAL_POST_ACT 1
+int orbit_op_bn_backward_ex(const float* dout, const float* out, const float* y, int M, int C, const float* gamma,
+                            const float* mean, const float* invstd, const float* scale, const float* shift, int train, int act,
+                            int flags, float* dy, float* dres, int dres_accumulate, float* dgamma, float* dbeta,
+                            orbit_stream_t stream);
+/* The activation pass of the training forward on its own: out = act(scale * y + shift + residual), or with
+ * flags = ORBIT_BN_RESIDUAL_POST_ACT out = act(scale * y + shift) + residual. y, out, residual (nullable) [M][C]; scale, shift [C]. */
+int orbit_op_scale_shift_act(const float* y, const float* scale, const float* shift, const float* residual, int act, int M, int C,
+                             int flags, float* out, orbit_stream_t stream);
 /* dx of a convolution: dy NHWC [B][Ho][Wo][Cout], w OIHW, dx NHWC [B][H][W][Cin] (= accumulate + grad if given) */
 int orbit_op_conv2d_dgrad(const float* dy, const float* w, const float* accumulate, float* dx, int B, int H, int W,
                           int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho, int Wo,

@@ -130,6 +130,8 @@ _SIGNATURES = {
     "orbit_op_bn_train_forward": (c_int, [P, c_int, c_int, P, P, c_float, c_float, P, P, P, c_int, P, P, P, P]),
     "orbit_op_bn_stats_from_gram": (c_int, [P, c_int, c_int, P, c_int, c_float, P, P, P]),
     "orbit_op_bn_backward": (c_int, [P, P, P, c_int, c_int, P, P, P, c_int, c_int, P, P, P, P, P]),
+    "orbit_op_bn_backward_ex": (c_int, [P, P, P, c_int, c_int, P, P, P, P, P, c_int, c_int, c_int, P, P, c_int, P, P, P]),
+    "orbit_op_scale_shift_act": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "orbit_op_conv2d_dgrad": (c_int, [P, P, P, P] + [c_int] * 12 + [P]),
     "orbit_op_conv2d_wgrad": (c_int, [P, c_int, P, P] + [c_int] * 12 + [P]),
     "orbit_op_conv2d_wgrad_gated": (c_int, [P, P, P, P] + [c_int] * 5 + [P]),

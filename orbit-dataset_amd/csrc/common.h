@@ -281,17 +281,19 @@ size_t bn_gram_scratch_floats(int P, int Cin);
 int launch_bn_stats_from_gram(const float* x, int P, int Cin, const float* w, int C, const BnAffine& a, const BnFold& out,
                               float* scratch, hipStream_t s);  // (a pointwise conv with a bias is not served: a.conv_bias == nullptr)
 int launch_bn_stats_from_partials(float* partial, int nblk, int M, int C, const BnAffine& a, const BnFold& out, hipStream_t s);
+// res_post: a = act(y * scale + shift) + residual (the skip joins after the activation, ConvDesc::res_post)
 int launch_scale_shift_act(const float* y, const float* scale, const float* shift, const float* residual, int act,
-                           size_t M, int C, float* out, hipStream_t s);
+                           size_t M, int C, float* out, hipStream_t s, int res_post = 0);
 // a = act(y * scale + shift) for [B][HW][C] plus the squeeze-excite pooling partials pool[B][se_pool_chunks][C] of a
 int se_pool_chunks(int B, int HW, int C);
 int launch_scale_shift_act_pool(const float* y, const float* scale, const float* shift, int act, int B, int HW, int C,
                                 float* out, float* pool, hipStream_t s);
 // coef: 3*C floats of scratch; dy nullable (reductions only); dres nullable (gradient of the residual input)
 // bn.scale / bn.shift: folded BatchNorm of the forward (needed to rebuild the SiLU pre-activation), else nullable
+// res_post: backward of out = act(BN(y)) + residual: dres (+)= dout itself; g, the sums and dy as for the plain form
 int launch_bn_backward(const float* dout, const float* out, const float* y, const BnFoldC& bn, const BnGrads& p, int train,
                        int act, int M, int C, float* dy, float* dres, int dres_accumulate, float* partial, float* coef,
-                       hipStream_t s);
+                       hipStream_t s, int res_post = 0);
 int launch_maxpool_idx(const float* x, float* y, uint8_t* idx, int B, int H, int W, int C, int K, int stride, int pad,
                        int Ho, int Wo, hipStream_t s);
 int launch_maxpool_bwd(const float* dy, const uint8_t* idx, float* dx, int B, int H, int W, int C, int K, int stride,

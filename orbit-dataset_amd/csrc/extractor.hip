@@ -240,8 +240,9 @@ static int build_efficientnet_b0(orbit_extractor* fe, int H, int W, bool unfused
 // Parameters are registered in timm's module order (conv before its BatchNorm), so the enumeration IS the checkpoint's
 // state_dict order. FiLM slots (model/film.py:38-56): root bn1 / bn2, bn1 of every ConvBnAct and EdgeResidual, bn2 of every
 // InvertedResidual. Every block is the plain conv (+ depthwise + squeeze-excite) sequence of the kernels efficientnet_b0 runs
-// at 14x14 / 7x7; the one new device form is ConvBnAct's skip, which joins AFTER the activation (Op::res_post) - the reason
-// this plan has no training path (plan_trainable, csrc/extractor_train.hip).
+// at 14x14 / 7x7; the one new device form is ConvBnAct's skip, which joins AFTER the activation (Op::res_post). The training
+// runtime walks it only on a plan created with ORBIT_PLAN_RES_POST_BACKWARD, and then in frozen form only: running statistics,
+// no filter gradients (plan_trainable / plan_frozen_only, csrc/extractor_train.hip).
 static int build_efficientnet_v2_s(orbit_extractor* fe, int H, int W) {
     fe->out_size = 1280;
     const float eps = 1e-3f;
@@ -382,10 +383,11 @@ int orbit_extractor_create_ex(const char* name, int H, int W, int flags, orbit_e
     ORBIT_REQUIRE(H >= 8 && W >= 8 && H <= 4096 && W <= 4096, "extractor_create: bad frame size %dx%d", H, W);
     orbit_extractor* fe = new orbit_extractor();
     fe->name = name, fe->pool.owner = name, fe->H = H, fe->W = W;
+    fe->res_post_backward = (flags & ORBIT_PLAN_RES_POST_BACKWARD) != 0;  // (same ops, same parameter order)
     int rc;
     if (fe->name == "resnet18") rc = build_resnet18(fe, H, W);
     else if (fe->name == "efficientnet_b0") rc = build_efficientnet_b0(fe, H, W, (flags & ORBIT_PLAN_UNFUSED) != 0);
-    else if (fe->name == "efficientnet_v2_s") rc = build_efficientnet_v2_s(fe, H, W);  // (no fused ops: one plan for both flags)
+    else if (fe->name == "efficientnet_v2_s") rc = build_efficientnet_v2_s(fe, H, W);  // (no fused ops: one op list for every flag)
     else if (fe->name == "set_encoder") rc = build_set_encoder(fe, H, W);
     else rc = set_err(ORBIT_ERR_ARG, "Invalid feature_extractor_name: %s", name);
     if (rc != ORBIT_OK) {

@@ -9,7 +9,9 @@
 //
 // Generic over the plan ops: OP_CONV (+BN, ReLU / SiLU, residual, squeeze-excite gate on the input, fused 2x2 pool),
 // OP_DWCONV (+BN, SiLU), OP_SE, OP_MAXPOOL, OP_AVGPOOL — i.e. resnet18, efficientnet_b0 and the set encoder. (The
-// opt-in fused MBConv front op of the inference plan has no training form.)
+// opt-in fused MBConv front op of the inference plan has no training form.) efficientnet_v2_s, whose ConvBnAct blocks add
+// their skip after the activation (Op::res_post), runs on an ORBIT_PLAN_RES_POST_BACKWARD plan in frozen form only: running
+// statistics, BatchNorm weight / bias (FiLM) gradients, no filter gradients (plan_frozen_only).
 #include "extractor.h"
 
 namespace orbit {
@@ -63,9 +65,18 @@ static bool plan_trainable(const orbit_extractor* fe) {
         if (o.kind == OP_MBFRONT) return false;
         if ((o.kind == OP_CONV || o.kind == OP_DWCONV) && o.bn < 0) return false;
         if (o.kind == OP_CONV && o.use_gate && (o.pool2 || o.x_nchw)) return false;
-        if (o.kind == OP_CONV && o.res_post) return false;  // efficientnet_v2_s: no backward through the post-activation skip
+        // efficientnet_v2_s: the backward through the post-activation skip is opt-in (ORBIT_PLAN_RES_POST_BACKWARD)
+        if (o.kind == OP_CONV && o.res_post && !fe->res_post_backward) return false;
     }
     return true;
+}
+
+// a plan that holds a post-activation skip trains in frozen form only: batch statistics and filter gradients are not built for
+// it (neither the statistics nor the filter-gradient kernels have been run at that network's shapes)
+static bool plan_frozen_only(const orbit_extractor* fe) {
+    for (const Op& o : fe->ops)
+        if (o.kind == OP_CONV && o.res_post) return true;
+    return false;
 }
 
 static bool has_bn(const Op& o) { return o.kind == OP_CONV || o.kind == OP_DWCONV; }
@@ -261,8 +272,10 @@ static TrainForms train_forms(const orbit_extractor* fe, int B, int bn_train, bo
             // Dual write: running-statistics BatchNorm (frozen extractor: CNAPs meta-training, FiLM fine-tuning): scale / shift
             // are known before the conv runs, so its epilogue writes BOTH the raw output (tape: xhat and the SiLU derivative need
             // it) and the activation - no separate activation pass over the tensor
+            // (a post-activation skip keeps CONV_PLAIN: conv_igemm has no dual-output form of that epilogue, and the two such
+            // ops of efficientnet_v2_s do not pay for one - raw conv, then the activation pass in its post-skip form)
             if (front) f.conv = bn_gram_supported(o.Cin) && fronts != 3 ? CONV_SWEEP_GRAM : CONV_SWEEP_CONV, f.tiles = tiles;
-            else if (!bn_train && !o.pool2) f.conv = CONV_DUAL;
+            else if (!bn_train && !o.pool2 && !o.res_post) f.conv = CONV_DUAL;
             else if (raw) f.conv = CONV_RAW_TO_DW;
         } else if (o.kind == OP_DWCONV) {
             const int prev = (int)i - 1;  // (a conv in one of the three forms below is followed by its depthwise reader)
@@ -410,6 +423,11 @@ int orbit_extractor_train_forward_ex(orbit_extractor_t* fe, const float* frames,
     if (!fe->finalized) return set_err(ORBIT_ERR_STATE, "extractor_train_forward: call orbit_extractor_finalize first");
     if (!plan_trainable(fe))
         return set_err(ORBIT_ERR_STATE, "extractor_train_forward: the %s plan has no training path yet", fe->name.c_str());
+    if (bn_train && plan_frozen_only(fe))
+        return set_err(ORBIT_ERR_STATE,
+                       "extractor_train_forward: the %s plan trains in frozen form only (running statistics, FiLM / BatchNorm "
+                       "gradients): batch statistics and filter gradients are not built for it",
+                       fe->name.c_str());
     ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr),
                   "extractor_train_forward: film_gamma and film_beta must be given together");
     const TapeLayout L = tape_layout(fe, B);
@@ -539,7 +557,7 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
                 continue;
             }
             rc = launch_scale_shift_act(d.y, bf.scale, bf.shift, o.res >= 0 ? cur[o.res] : nullptr, o.act, (size_t)M, o.Cout,
-                                        fl(L.a[i]), s);
+                                        fl(L.a[i]), s, o.res_post);
             if (rc != ORBIT_OK) return rc;
             if (o.pool2) {
                 rc = launch_maxpool_idx(fl(L.a[i]), fl(L.p[i]), reinterpret_cast<uint8_t*>(tp + L.idx[i]), B, o.Ho, o.Wo,
@@ -633,6 +651,11 @@ int orbit_extractor_backward(orbit_extractor_t* fe, const float* frames, int B, 
     if (!fe->finalized) return set_err(ORBIT_ERR_STATE, "extractor_backward: call orbit_extractor_finalize first");
     if (!plan_trainable(fe))
         return set_err(ORBIT_ERR_STATE, "extractor_backward: the %s plan has no training path yet", fe->name.c_str());
+    if ((bn_train || filter_grads) && plan_frozen_only(fe))
+        return set_err(ORBIT_ERR_STATE,
+                       "extractor_backward: the %s plan trains in frozen form only (running statistics, FiLM / BatchNorm "
+                       "gradients): batch statistics and filter gradients are not built for it",
+                       fe->name.c_str());
     ORBIT_REQUIRE((dfilm_gamma == nullptr) == (dfilm_beta == nullptr),
                   "extractor_backward: dfilm_gamma and dfilm_beta must be given together");
     const bool film = film_gamma && film_beta && fe->film_size > 0;
@@ -899,7 +922,7 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
                 // partial holds [blocks][2][C] followed by the 3*C apply coefficients
                 float* coef = partial + (size_t)bn_reduce_blocks(M, o.Cout) * 2 * o.Cout;
                 rc = launch_bn_backward(slot_ptr(g), tf(L.a[i]), tf(L.y[i]), fold(bn), bp, bn_train, o.act, M, o.Cout, dy, dres,
-                                        dres_acc, partial, coef, s);
+                                        dres_acc, partial, coef, s, o.res_post);
             }
             if (rc != ORBIT_OK) return rc;
             if (!need_dy && dres) {

@@ -264,7 +264,9 @@ __global__ __launch_bounds__(1024) void gram_bn_finalize_kernel(const float* __r
                         shift, running_mean, running_var);
 }
 
-// a = act(y * scale + shift + residual)
+// a = act(y * scale + shift + residual); RPOST (compile-time form, the post-activation skip of timm's ConvBnAct):
+// a = act(y * scale + shift) + residual, residual required
+template <bool RPOST = false>
 __global__ __launch_bounds__(256) void scale_shift_act_kernel(const float* __restrict__ y,
                                                               const float* __restrict__ scale,
                                                               const float* __restrict__ shift,
@@ -278,13 +280,14 @@ __global__ __launch_bounds__(256) void scale_shift_act_kernel(const float* __res
          i += stride, q = q + stride_mod >= (unsigned)C4 ? q + stride_mod - C4 : q + stride_mod) {
         f32x4 v = reinterpret_cast<const f32x4*>(y)[i];
         if (scale) v = v * reinterpret_cast<const f32x4*>(scale)[q] + reinterpret_cast<const f32x4*>(shift)[q];
-        if (residual) v += reinterpret_cast<const f32x4*>(residual)[i];
+        if (!RPOST && residual) v += reinterpret_cast<const f32x4*>(residual)[i];
         if (act == ORBIT_ACT_RELU) {
             v[0] = fmaxf(v[0], 0.f), v[1] = fmaxf(v[1], 0.f), v[2] = fmaxf(v[2], 0.f), v[3] = fmaxf(v[3], 0.f);
         } else if (act == ORBIT_ACT_SILU) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) v[k] = v[k] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[k]));
         }
+        if (RPOST) v += reinterpret_cast<const f32x4*>(residual)[i];
         reinterpret_cast<f32x4*>(out)[i] = v;
     }
 }
@@ -363,7 +366,9 @@ __device__ __forceinline__ f32x4 relu_mask(f32x4 g, f32x4 a) {
 }
 
 // partial[blk][0][c] = sum_m g, partial[blk][1][c] = sum_m g * xhat, with g = dout * act'(.) and
-// xhat = (y - mean) * invstd
+// xhat = (y - mean) * invstd. RPOST (compile-time form): out = act(z) + residual, z = y * scale + shift - g is the same
+// expression, but `out` no longer tells ReLU's mask: it is taken from z (scale / shift required for every activation)
+template <bool RPOST = false>
 __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __restrict__ dout,
                                                              const float* __restrict__ out,
                                                              const float* __restrict__ y,
@@ -384,7 +389,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
         const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + q * 4);
         const f32x4 is = *reinterpret_cast<const f32x4*>(invstd + q * 4);
         f32x4 sc = {0.f, 0.f, 0.f, 0.f}, sh = {0.f, 0.f, 0.f, 0.f};
-        if (act == ORBIT_ACT_SILU) {
+        if (act == ORBIT_ACT_SILU || (RPOST && act == ORBIT_ACT_RELU)) {
             sc = *reinterpret_cast<const f32x4*>(scale + q * 4), sh = *reinterpret_cast<const f32x4*>(shift + q * 4);
         }
 #pragma unroll 2
@@ -392,7 +397,8 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
             const size_t o = (size_t)r * C + q * 4;
             f32x4 g = *reinterpret_cast<const f32x4*>(dout + o);
             const f32x4 yv = *reinterpret_cast<const f32x4*>(y + o);
-            if (act == ORBIT_ACT_RELU) g = relu_mask(g, *reinterpret_cast<const f32x4*>(out + o));
+            if (RPOST && act == ORBIT_ACT_RELU) g = relu_mask(g, yv * sc + sh);
+            else if (act == ORBIT_ACT_RELU) g = relu_mask(g, *reinterpret_cast<const f32x4*>(out + o));
             else if (act == ORBIT_ACT_SILU) g = silu_grad(g, yv * sc + sh);
             const f32x4 xh = (yv - mu) * is;
             s += g;
@@ -428,6 +434,8 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
     if (dbias) dbias[c] = train ? 0.f : k1 * (float)s;
 }
 
+// RPOST (compile-time form): out = act(z) + residual - the residual branch receives dout itself, not g
+template <bool RPOST = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dout,
                                                            const float* __restrict__ out,
                                                            const float* __restrict__ y,
@@ -445,7 +453,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
          i += stride, q = q + stride_mod >= (unsigned)C4 ? q + stride_mod - C4 : q + stride_mod) {
         f32x4 g = reinterpret_cast<const f32x4*>(dout)[i];
         const f32x4 yv = reinterpret_cast<const f32x4*>(y)[i];
-        if (act == ORBIT_ACT_RELU) g = relu_mask(g, reinterpret_cast<const f32x4*>(out)[i]);
+        if (RPOST && dres) {
+            f32x4 d = g;
+            if (dres_accumulate) d += reinterpret_cast<const f32x4*>(dres)[i];
+            reinterpret_cast<f32x4*>(dres)[i] = d;
+        }
+        if (RPOST && act == ORBIT_ACT_RELU)
+            g = relu_mask(g, yv * reinterpret_cast<const f32x4*>(scale)[q] + reinterpret_cast<const f32x4*>(shift)[q]);
+        else if (act == ORBIT_ACT_RELU) g = relu_mask(g, reinterpret_cast<const f32x4*>(out)[i]);
         else if (act == ORBIT_ACT_SILU)
             g = silu_grad(g, yv * reinterpret_cast<const f32x4*>(scale)[q] + reinterpret_cast<const f32x4*>(shift)[q]);
         const f32x4 xh = (yv - reinterpret_cast<const f32x4*>(mean)[q]) * reinterpret_cast<const f32x4*>(invstd)[q];
@@ -453,7 +468,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
         const f32x4 k2 = reinterpret_cast<const f32x4*>(coef + C)[q];
         const f32x4 k3 = reinterpret_cast<const f32x4*>(coef + 2 * C)[q];
         reinterpret_cast<f32x4*>(dy)[i] = k1 * (g - k2 - xh * k3);
-        if (dres) {
+        if (!RPOST && dres) {
             if (dres_accumulate) g += reinterpret_cast<const f32x4*>(dres)[i];
             reinterpret_cast<f32x4*>(dres)[i] = g;
         }
@@ -655,32 +670,44 @@ int launch_scale_shift_act_pool(const float* y, const float* scale, const float*
 }
 
 int launch_scale_shift_act(const float* y, const float* scale, const float* shift, const float* residual, int act,
-                           size_t M, int C, float* out, hipStream_t s) {
+                           size_t M, int C, float* out, hipStream_t s, int res_post) {
     ORBIT_REQUIRE(C % 4 == 0, "scale_shift_act: C %% 4 != 0");
+    ORBIT_REQUIRE(!res_post || residual, "scale_shift_act: the post-activation skip needs its residual");
     const size_t total4 = M * (size_t)(C / 4);
-    scale_shift_act_kernel<<<grid_for(total4), 256, 0, s>>>(y, scale, shift, residual, act, total4, C / 4, out);
+    if (res_post) scale_shift_act_kernel<true><<<grid_for(total4), 256, 0, s>>>(y, scale, shift, residual, act, total4, C / 4, out);
+    else scale_shift_act_kernel<<<grid_for(total4), 256, 0, s>>>(y, scale, shift, residual, act, total4, C / 4, out);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
 }
 
 int launch_bn_backward(const float* dout, const float* out, const float* y, const BnFoldC& bn, const BnGrads& p, int train,
                        int act, int M, int C, float* dy, float* dres, int dres_accumulate, float* partial, float* coef,
-                       hipStream_t s) {
+                       hipStream_t s, int res_post) {
     ORBIT_REQUIRE(C % 4 == 0 && M > 0, "bn_backward: C %% 4 != 0 or empty batch");
     ORBIT_REQUIRE(act != ORBIT_ACT_SILU || (bn.scale && bn.shift), "bn_backward: SiLU needs the folded scale/shift");
-    ORBIT_REQUIRE(act != ORBIT_ACT_RELU || out, "bn_backward: ReLU needs the activation output");
+    ORBIT_REQUIRE(act != ORBIT_ACT_RELU || out || res_post, "bn_backward: ReLU needs the activation output");
+    ORBIT_REQUIRE(!res_post || act == ORBIT_ACT_NONE || (bn.scale && bn.shift),
+                  "bn_backward: the post-activation skip needs the folded scale/shift");
     const ColLayout L = col_layout(C);
     const int nblk = bn_reduce_blocks(M, C);
-    bn_bwd_partial_kernel<<<dim3(nblk, L.ygroups), 256, 0, s>>>(dout, out, y, bn.mean, bn.invstd, bn.scale, bn.shift, act, M, C,
-                                                                bn_rows_per_block(M, C), L.G, L.R, partial);
+    if (res_post)
+        bn_bwd_partial_kernel<true><<<dim3(nblk, L.ygroups), 256, 0, s>>>(dout, out, y, bn.mean, bn.invstd, bn.scale, bn.shift, act,
+                                                                          M, C, bn_rows_per_block(M, C), L.G, L.R, partial);
+    else
+        bn_bwd_partial_kernel<<<dim3(nblk, L.ygroups), 256, 0, s>>>(dout, out, y, bn.mean, bn.invstd, bn.scale, bn.shift, act, M, C,
+                                                                    bn_rows_per_block(M, C), L.G, L.R, partial);
     ORBIT_LAUNCH_CHECK();
     bn_bwd_finalize_kernel<<<cdiv(C, BN_FIN_CH), 256, 0, s>>>(partial, nblk, M, C, train, p.gamma, bn.invstd, p.dgamma, p.dbeta,
                                                               p.dbias, coef);
     ORBIT_LAUNCH_CHECK();
     if (dy) {
         const size_t total4 = (size_t)M * (C / 4);
-        bn_bwd_apply_kernel<<<grid_for(total4), 256, 0, s>>>(dout, out, y, bn.mean, bn.invstd, bn.scale, bn.shift, coef, act,
-                                                             total4, C / 4, dy, dres, dres_accumulate);
+        if (res_post)
+            bn_bwd_apply_kernel<true><<<grid_for(total4), 256, 0, s>>>(dout, out, y, bn.mean, bn.invstd, bn.scale, bn.shift, coef,
+                                                                       act, total4, C / 4, dy, dres, dres_accumulate);
+        else
+            bn_bwd_apply_kernel<<<grid_for(total4), 256, 0, s>>>(dout, out, y, bn.mean, bn.invstd, bn.scale, bn.shift, coef, act,
+                                                                 total4, C / 4, dy, dres, dres_accumulate);
         ORBIT_LAUNCH_CHECK();
     }
     return ORBIT_OK;
@@ -978,6 +1005,38 @@ int orbit_op_bn_backward(const float* dout, const float* out, const float* y, in
                                       dres, 0, tmp, tmp + npart, s);
     (void)hipFreeAsync(tmp, s);
     return rc;
+}
+
+int orbit_op_bn_backward_ex(const float* dout, const float* out, const float* y, int M, int C, const float* gamma,
+                            const float* mean, const float* invstd, const float* scale, const float* shift, int train, int act,
+                            int flags, float* dy, float* dres, int dres_accumulate, float* dgamma, float* dbeta,
+                            orbit_stream_t stream) {
+    ORBIT_REQUIRE(dout && y && mean && invstd && dy, "op_bn_backward_ex: null pointer");
+    ORBIT_REQUIRE((flags & ~ORBIT_BN_RESIDUAL_POST_ACT) == 0, "op_bn_backward_ex: unknown flags 0x%x", flags);
+    ORBIT_REQUIRE(act == ORBIT_ACT_NONE || act == ORBIT_ACT_RELU || act == ORBIT_ACT_SILU, "op_bn_backward_ex: bad activation %d", act);
+    ORBIT_REQUIRE(M > 0 && C > 0 && C % 4 == 0, "op_bn_backward_ex: bad sizes M = %d, C = %d", M, C);
+    const int res_post = (flags & ORBIT_BN_RESIDUAL_POST_ACT) ? 1 : 0;
+    ORBIT_REQUIRE(act != ORBIT_ACT_RELU || out || res_post, "op_bn_backward_ex: the activation output is needed for the ReLU mask");
+    ORBIT_REQUIRE((act != ORBIT_ACT_SILU && !(res_post && act == ORBIT_ACT_RELU)) || (scale && shift),
+                  "op_bn_backward_ex: this form needs the folded scale / shift");
+    hipStream_t s = (hipStream_t)stream;
+    float* tmp = nullptr;
+    const size_t npart = (size_t)bn_reduce_blocks(M, C) * 2 * C;
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (npart + 3 * (size_t)C) * sizeof(float), s));
+    const int rc = launch_bn_backward(dout, out, y, BnFoldC{mean, invstd, scale, shift}, BnGrads{gamma, dgamma, dbeta}, train, act, M,
+                                      C, dy, dres, dres_accumulate, tmp, tmp + npart, s, res_post);
+    (void)hipFreeAsync(tmp, s);
+    return rc;
+}
+
+int orbit_op_scale_shift_act(const float* y, const float* scale, const float* shift, const float* residual, int act, int M, int C,
+                             int flags, float* out, orbit_stream_t stream) {
+    ORBIT_REQUIRE(y && scale && shift && out, "op_scale_shift_act: null pointer");
+    ORBIT_REQUIRE((flags & ~ORBIT_BN_RESIDUAL_POST_ACT) == 0, "op_scale_shift_act: unknown flags 0x%x", flags);
+    ORBIT_REQUIRE(act == ORBIT_ACT_NONE || act == ORBIT_ACT_RELU || act == ORBIT_ACT_SILU, "op_scale_shift_act: bad activation %d", act);
+    ORBIT_REQUIRE(M > 0 && C > 0 && C % 4 == 0, "op_scale_shift_act: bad sizes M = %d, C = %d", M, C);
+    return launch_scale_shift_act(y, scale, shift, residual, act, (size_t)M, C, out, (hipStream_t)stream,
+                                  (flags & ORBIT_BN_RESIDUAL_POST_ACT) ? 1 : 0);
 }
 
 int orbit_op_maxpool2d_train(const float* x, float* y, uint8_t* idx, int B, int H, int W, int C, int K, int stride,

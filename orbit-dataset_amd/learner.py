@@ -59,6 +59,10 @@ def build_parser():
     p.add_argument("--vit_native_weight_backward", action="store_true",
                    help="vit_* extractors: opt in to the native gradients of every parameter of the transformer (implies what "
                         "--vit_native_backward admits, and admits --learn_extractor). Ignored for the other extractors")
+    p.add_argument("--effnetv2_native_backward", action="store_true",
+                   help="efficientnet_v2_s: opt in to the native FiLM gradients through the FROZEN network (--adapt_features "
+                        "training, with or without --with_lite; the multi-step finetuner's --adapt_features). --learn_extractor "
+                        "stays refused: weight gradients and batch statistics are not built. Ignored for the other extractors")
     p.add_argument("--num_lite_samples", type=int, default=16)
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--seed", type=int, default=synthetic.DEFAULT_SEED)
@@ -154,12 +158,17 @@ def verify_args(args):
             sys.exit("error: --feature_extractor %s is inference-only here (no backward through a ViT): use --mode test "
                      "without --learn_extractor / --with_lite%s" % (fe, " / --adapt_features" if multistep else ""))
     if fe == "efficientnet_v2_s":
-        # reference utils/args.py:187-188; any frame size, as efficientnet_b0. The native plan has no backward (its ConvBnAct
-        # blocks add the skip after the activation, csrc/extractor_train.hip plan_trainable): everything that would send a
-        # gradient or batch statistics through the extractor is refused here rather than at the first forward
+        # reference utils/args.py:187-188; any frame size, as efficientnet_b0. By default the native plan has no backward (its
+        # ConvBnAct blocks add the skip after the activation, csrc/extractor_train.hip plan_trainable): everything that would
+        # send a gradient or batch statistics through the extractor is refused here rather than at the first forward.
+        # --effnetv2_native_backward opens the FiLM gradients through the frozen network: everything but --learn_extractor
         args.frame_norm_method = "imagenet_inception"
         multistep = getattr(args, "personalize_num_grad_steps", None) is not None
-        if "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
+        if getattr(args, "effnetv2_native_backward", False):
+            if args.learn_extractor:
+                sys.exit("error: --effnetv2_native_backward gives FiLM gradients through a frozen efficientnet_v2_s only: "
+                         "--learn_extractor (weight gradients and batch-statistics BatchNorm) is not built")
+        elif "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
             sys.exit("error: --feature_extractor efficientnet_v2_s is inference-only here (no backward through its "
                      "post-activation skips): use --mode test without --learn_extractor / --with_lite%s"
                      % (" / --adapt_features" if multistep else ""))
@@ -286,6 +295,8 @@ class Learner:
             self.model.feature_extractor.native_backward = True
         if getattr(self.args, "vit_native_weight_backward", False) and self.args.feature_extractor in VIT_EXTRACTORS:
             self.model.feature_extractor.native_weight_backward = True
+        if getattr(self.args, "effnetv2_native_backward", False) and self.args.feature_extractor == "efficientnet_v2_s":
+            self.model.feature_extractor.native_backward = True
 
     def make_task(self, index):
         a = self.args

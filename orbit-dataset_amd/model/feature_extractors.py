@@ -47,13 +47,14 @@ def _ensure_child(module, name, cls=ParamNode):
 class _Plan:
     """One native plan (frame size specific) and the parameter stamp it was last synchronised with."""
 
-    def __init__(self, name, H, W, trainable=False, api="extractor"):
+    def __init__(self, name, H, W, trainable=False, api="extractor", res_post_backward=False):
         lib = _lib.load()
         h = ctypes.c_void_p()
         if api == "extractor":
             # the fused MBConv front kernels have no backward form: a plan that will record a tape is built without them
-            _lib.check(lib.orbit_extractor_create_ex(name.encode(), H, W, 1 if trainable else 0, ctypes.byref(h)),
-                       "orbit_extractor_create_ex")
+            # (ORBIT_PLAN_UNFUSED = 1); res_post_backward adds ORBIT_PLAN_RES_POST_BACKWARD = 2 (efficientnet_v2_s's opt-in)
+            flags = (1 if trainable else 0) | (2 if res_post_backward else 0)
+            _lib.check(lib.orbit_extractor_create_ex(name.encode(), H, W, flags, ctypes.byref(h)), "orbit_extractor_create_ex")
         else:
             _lib.check(getattr(lib, "orbit_%s_create" % api)(name.encode(), H, W, ctypes.byref(h)), "orbit_%s_create" % api)
         self.api = api
@@ -162,13 +163,16 @@ class HipNetwork(nn.Module):
         statistics gets its own (unfused) plan. Both enumerate the same parameters in the same order."""
         plan = self._plans.get((H, W, trainable))
         if plan is None:
-            plan = _Plan(self.native_name, H, W, trainable, api=self._api)
+            plan = self._new_plan(H, W, trainable)
             names = [self._fn("param_name")(plan.handle, i).decode()
                      for i in range(self._fn("num_params")(plan.handle))]
             if names != [k for k, _ in self._keys]:
                 raise _lib.OrbitHipError("native plan enumerates different parameters than the module tree")
             self._plans[(H, W, trainable)] = plan
         return plan
+
+    def _new_plan(self, H, W, trainable):
+        return _Plan(self.native_name, H, W, trainable, api=self._api)
 
     def in_sync(self, H, W, trainable=True):
         """True when the plan a forward at this frame size would use exists and holds the current parameters."""
@@ -293,14 +297,16 @@ class HipNetwork(nn.Module):
             self.__dict__["_film_slot_cache"] = cached
         return cached
 
-    def _gather_swapped_film(self):
-        """If BatchNorm weights/biases were swapped in by functional_call, return (gamma, beta) concatenated."""
+    def _gather_swapped_film(self, detach=True):
+        """If BatchNorm weights/biases were swapped in by functional_call, return (gamma, beta) concatenated. detach=False keeps
+        the concatenation on the autograd graph (the gradients of the two vectors then split back into the swapped tensors)."""
         slots = self.film_slot_modules()
         if all(isinstance(m._parameters["weight"], nn.Parameter) and isinstance(m._parameters["bias"], nn.Parameter)
                for _, m in (slots[0], slots[-1])):
             return None  # functional_call with a FiLM dict swaps every slot; first and last suffice as a probe
-        gammas = [m._parameters["weight"].detach().reshape(-1) for _, m in slots]
-        betas = [m._parameters["bias"].detach().reshape(-1) for _, m in slots]
+        take = (lambda t: t.detach()) if detach else (lambda t: t)
+        gammas = [take(m._parameters["weight"]).reshape(-1) for _, m in slots]
+        betas = [take(m._parameters["bias"]).reshape(-1) for _, m in slots]
         return torch.cat(gammas).float().contiguous(), torch.cat(betas).float().contiguous()
 
     # ---- training path (tape + autograd) -------------------------------------------------------------
@@ -518,9 +524,14 @@ class EfficientNetV2S(HipNetwork):
     tree, state_dict keys, order and shapes as the timm module; FiLM on root bn1 / bn2, ConvBnAct.bn1, EdgeResidual.bn1 and
     InvertedResidual.bn2 (reference model/film.py:38-56). Any frame size.
 
-    Inference only: the ConvBnAct blocks add their skip after the activation, which the training runtime has no backward for
-    (orbit_extractor_supports_training is 0 for this plan). A forward that would record a tape or use batch statistics raises
-    NotImplementedError before anything is launched.
+    Inference only by default: the ConvBnAct blocks add their skip after the activation, and the plans this class builds report
+    no training path (orbit_extractor_supports_training is 0). A forward that would record a tape or use batch statistics raises
+    NotImplementedError before anything is launched. With `native_backward = True` set on the instance, a forward in eval()
+    whose FiLM vectors require a gradient - the `film=` pair, or BatchNorm tensors swapped in by functional_call - records a tape
+    on a plan created with ORBIT_PLAN_UNFUSED | ORBIT_PLAN_RES_POST_BACKWARD and gets their gradients through the FROZEN network
+    from orbit_extractor_backward (autograd.ExtractorFunction); so do the FiLM-slot BatchNorm weights / biases themselves when
+    they require a gradient (the multi-step finetuner's unfreeze_film). Any other own parameter that requires a gradient and
+    train() mode are still refused: weight gradients and batch statistics are not built for this network.
 
     One divergence from the sibling classes: every BatchNorm node's buffers are ordered (running_mean, running_var,
     num_batches_tracked) as nn.BatchNorm2d registers them, so that the state_dict ORDER equals the timm module's;
@@ -561,23 +572,45 @@ class EfficientNetV2S(HipNetwork):
         cout = keys[blk + bn + ".weight"]
         return (cout, numel // cout, 1, 1)
 
+    native_backward = False  # opt-in (learner flag --effnetv2_native_backward)
+
     _REFUSAL = ("efficientnet_v2_s is an inference-only extractor: no native backward and no batch-statistics BatchNorm (LITE "
                 "meta-training, --learn_extractor, FiLM gradients); call it in eval() under torch.no_grad() with frozen parameters")
+    _REFUSAL_FROZEN = ("efficientnet_v2_s: native_backward gives the gradients of the FiLM vectors through the FROZEN network in "
+                       "eval() only; %s: weight gradients (--learn_extractor) and batch-statistics BatchNorm are not built")
+
+    def _new_plan(self, H, W, trainable):
+        # (a tape is only ever recorded under native_backward: the unfused plan then also carries the flag that opens it)
+        return _Plan(self.native_name, H, W, trainable, api=self._api, res_post_backward=trainable and self.native_backward)
 
     def wants_grad(self, film=None):
-        if super().wants_grad(film):
+        if not super().wants_grad(film):
+            return False
+        if not self.native_backward:
             raise NotImplementedError(self._REFUSAL)
-        return False
+        # (the FiLM-slot BatchNorm weights / biases themselves - the multi-step finetuner's unfreeze_film - are what the frozen
+        # backward differentiates: admitted, as on VisionTransformer; every other parameter is a weight gradient)
+        film_keys = {n + leaf for n in self._film_slot_names for leaf in (".weight", ".bias")}
+        other = [key for _, _, key, p in self._leaves if p is not None and p.requires_grad and key not in film_keys]
+        if other:
+            raise NotImplementedError(self._REFUSAL_FROZEN % ("%d parameters other than the FiLM-slot BatchNorm weights / biases "
+                                                              "require a gradient (first: %s)" % (len(other), other[0])))
+        return True
 
     def forward(self, x, film=None, out=None, check_sync=True):
         # refused here, before a plan is built or a parameter uploaded: nothing is launched
         if self.training and x.numel() > 0:
-            raise NotImplementedError(self._REFUSAL)
+            raise NotImplementedError(self._REFUSAL_FROZEN % "the module is in train() mode" if self.native_backward
+                                      else self._REFUSAL)
+        if film is None and self.native_backward and torch.is_grad_enabled():
+            film = self._gather_swapped_film(detach=False)  # functional_call with tensors that require a gradient
         self.wants_grad(film)
         return super().forward(x, film=film, out=out, check_sync=check_sync)
 
-    def _forward_train(self, plan, x, film, use_tape, bn_train, out):  # (the native plan reports no training path either)
-        raise NotImplementedError(self._REFUSAL)
+    def _forward_train(self, plan, x, film, use_tape, bn_train, out):
+        if not (self.native_backward and use_tape and not bn_train):  # (the native plan reports no training path either)
+            raise NotImplementedError(self._REFUSAL)
+        return super()._forward_train(plan, x, film, use_tape, bn_train, out)
 
 
 _VIT_OUTPUT = {"vit_s_32": 384, "vit_b_32": 768, "vit_b_32_clip": 768}

@@ -7,6 +7,13 @@ dense convolutions' and the whole forward's TF/s as fractions of the fp32 MFMA p
 
     python tools/effnetv2_bench.py [--steps 10] [--warmup 3] [--frames 200] [--size 224]
 
+--train times one CNAPs LITE step instead (SingleStepFewShotRecogniser with adapt_features and the prototype head on the frozen
+extractor with native_backward: personalise_with_lite over --way x --context_per_class context frames, predict_a_batch over
+--query frames, cross-entropy, backward into the FiLM generator and the set encoder), beside the same calls under
+torch.no_grad() - the step's forward-only time - and reports orbit_extractor_tape_bytes per frame at that size.
+
+    python tools/effnetv2_bench.py --train [--steps 5] [--warmup 2] [--way 5] [--context_per_class 40] [--query 200] [--size 224]
+
 Nothing here is gated."""
 import argparse
 import ctypes
@@ -76,15 +83,67 @@ def _families(run):
     return fam
 
 
+def train_main(a):
+    """One CNAPs LITE step and its forward-only time (module docstring)."""
+    import numpy as np
+    import torch.nn.functional as F
+    from orbit_dataset_amd.model.few_shot_recognisers import SingleStepFewShotRecogniser
+    lib = _lib.load()
+    model = SingleStepFewShotRecogniser(NAME, True, "proto", 1, 256, False, a.lite_samples, 1.0)
+    synthetic.init_parameters_(model)
+    fe = model.feature_extractor
+    fe.native_backward = True
+    model._set_device("cuda:0")
+    model._send_to_device()
+    model.set_test_mode(False)
+    S = a.size
+    task = synthetic.make_task_on_device(0, a.way, 1, a.context_per_class, a.query, S, 1, "cuda:0", template="blobs")
+    ctx, lab, tgt, tlab = task["context_clips"], task["context_labels"], task["target_clips"], task["target_labels"]
+
+    def step():  # one task of Learner.train_task_with_lite (one query batch): set-encoder and feature cache passes included
+        np.random.seed(7)
+        model._clear_caches()
+        model.personalise_with_lite(ctx, lab)
+        loss = F.cross_entropy(model.predict_a_batch(tgt), tlab) + 0.001 * model.film_generator.regularization_term()
+        if loss.requires_grad:
+            loss.backward()
+        model._reset()
+        model.zero_grad(set_to_none=True)
+        return loss
+
+    def forward_only():
+        with torch.no_grad():
+            step()
+
+    plan = fe._plan(S, S, trainable=True)
+    result = {"metric": "effnetv2_lite_step_ms", "frame_size": S, "way": a.way, "context_frames": len(ctx), "query_frames": len(tgt),
+              "lite_samples": a.lite_samples,
+              "tape_bytes_per_frame": lib.orbit_extractor_tape_bytes(plan.handle, 8) // 8,
+              "tape_bytes_1_frame": lib.orbit_extractor_tape_bytes(plan.handle, 1)}
+    for tag, fn in (("step", step), ("forward_only", forward_only)):
+        med, lo, hi = _time(fn, a.steps, a.warmup)
+        result[tag] = {"ms": round(med, 3), "ms_min": round(lo, 3), "ms_max": round(hi, 3)}
+    result["loss"] = round(float(step().detach()), 6)
+    result["max_memory_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
+    print(json.dumps(result))
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--frames", type=int, default=200)
     p.add_argument("--size", type=int, default=224)
+    p.add_argument("--train", action="store_true", help="time one CNAPs LITE step and its forward-only time instead")
+    p.add_argument("--way", type=int, default=5)
+    p.add_argument("--context_per_class", type=int, default=40)
+    p.add_argument("--query", type=int, default=200)
+    p.add_argument("--lite_samples", type=int, default=16)
     a = p.parse_args(argv)
     _lib.require_gpu()
     torch.cuda.set_device(0)
+    if a.train:
+        return train_main(a)
     fe, _ = create_feature_extractor(NAME, with_film=True, learn_extractor=False)
     synthetic.init_parameters_(fe)
     fe.to("cuda:0").eval()
