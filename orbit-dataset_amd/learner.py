@@ -23,6 +23,7 @@ reproduces single-GPU accumulation; BatchNorm running statistics are combined at
 sequential updates would have left them (dist.RunningStatSync).
 """
 import argparse
+import collections
 import json
 import math
 import sys
@@ -34,6 +35,7 @@ import torch
 from . import dist as odist
 from . import synthetic
 from .data.utils import attach_frame_history, unpack_task
+from .model.feature_extractors import EXTRACTORS
 from .model.few_shot_recognisers import SingleStepFewShotRecogniser
 from .optim import apply_lr_scale, cross_entropy, init_optimizer  # noqa: F401  (re-exported: bench.py, tools)
 from .utils.eval_metrics import TestEvaluator
@@ -42,7 +44,7 @@ from .utils.eval_metrics import TestEvaluator
 def build_parser():
     p = argparse.ArgumentParser(description="single-step learner on the MI355X-native recogniser (synthetic tasks)")
     # flags shared with the reference (utils/args.py)
-    p.add_argument("--feature_extractor", default="efficientnet_b0", choices=["efficientnet_b0", "efficientnet_v2_s", "resnet18", "vit_s_32", "vit_b_32", "vit_b_32_clip"])
+    p.add_argument("--feature_extractor", default="efficientnet_b0", choices=list(EXTRACTORS))
     p.add_argument("--learn_extractor", action="store_true")
     p.add_argument("--adapt_features", action="store_true")
     p.add_argument("--classifier", default="proto", choices=["proto", "proto_cosine", "versa", "mahalanobis", "linear"])
@@ -131,47 +133,49 @@ def build_parser():
     return p
 
 
-VIT_EXTRACTORS = {"vit_s_32": "imagenet_inception", "vit_b_32": "imagenet_inception", "vit_b_32_clip": "openai_clip"}
+# The extractors whose network is frozen unless a flag opts in: the frame normalisation the reference sets for them
+# (utils/args.py:185-190; the other extractors keep --frame_norm_method), the one frame size they run on (None: any), the flag
+# that opens the FiLM gradients through the frozen network and the one that opens the weight gradients (None: not built), and
+# the words their refusals differ in.
+FrozenExtractor = collections.namedtuple("FrozenExtractor", "frame_norm frame_size film_flag weight_flag no_weights no_backward")
+_VIT = ("vit_native_backward", "vit_native_weight_backward", "weight gradients through a ViT", "a ViT")
+FROZEN_EXTRACTORS = {
+    "vit_s_32": FrozenExtractor("imagenet_inception", 224, *_VIT),
+    "vit_b_32": FrozenExtractor("imagenet_inception", 224, *_VIT),
+    "vit_b_32_clip": FrozenExtractor("openai_clip", 224, *_VIT),
+    # any frame size, as efficientnet_b0. By default the native plan has no backward (its ConvBnAct blocks add the skip after
+    # the activation, csrc/extractor_train.hip plan_trainable)
+    "efficientnet_v2_s": FrozenExtractor("imagenet_inception", None, "effnetv2_native_backward", None,
+                                         "weight gradients and batch-statistics BatchNorm", "its post-activation skips"),
+}
 
 
 def verify_args(args):
-    """reference utils/args.py:203-217. For the transformer extractors also the frame normalisation the reference sets
-    for them (utils/args.py:185-190; the other extractors keep --frame_norm_method) and the inference-only scope, which
-    --vit_native_backward widens to everything but --learn_extractor and --vit_native_weight_backward to that as well."""
+    """reference utils/args.py:203-217. For the frozen-scope extractors (FROZEN_EXTRACTORS) also the frame normalisation the
+    reference sets for them and the inference-only scope: everything that would send a gradient or batch statistics through the
+    extractor is refused here rather than at the first forward. The FiLM-gradient flag widens the scope to everything but
+    --learn_extractor, and the weight-gradient flag to that as well."""
     if "train" in args.mode and not args.learn_extractor and not args.adapt_features:
         sys.exit("error: at least one of --learn_extractor and --adapt_features must be used when training")
     if args.frame_size % 1 or args.frame_size < 32:
         sys.exit("error: --frame_size must be >= 32")
     fe = args.feature_extractor
-    if fe in VIT_EXTRACTORS:
-        args.frame_norm_method = VIT_EXTRACTORS[fe]
-        if args.frame_size != 224:
-            sys.exit("error: --feature_extractor %s needs --frame_size 224 (got %d)" % (fe, args.frame_size))
-        multistep = getattr(args, "personalize_num_grad_steps", None) is not None
-        if getattr(args, "vit_native_weight_backward", False):
-            pass  # native gradients of every parameter: everything the other extractors train is admitted
-        elif getattr(args, "vit_native_backward", False):
-            if args.learn_extractor:
-                sys.exit("error: --vit_native_backward gives FiLM gradients through a frozen %s only: --learn_extractor "
-                         "(weight gradients through a ViT) is not built" % fe)
-        elif "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
-            sys.exit("error: --feature_extractor %s is inference-only here (no backward through a ViT): use --mode test "
-                     "without --learn_extractor / --with_lite%s" % (fe, " / --adapt_features" if multistep else ""))
-    if fe == "efficientnet_v2_s":
-        # reference utils/args.py:187-188; any frame size, as efficientnet_b0. By default the native plan has no backward (its
-        # ConvBnAct blocks add the skip after the activation, csrc/extractor_train.hip plan_trainable): everything that would
-        # send a gradient or batch statistics through the extractor is refused here rather than at the first forward.
-        # --effnetv2_native_backward opens the FiLM gradients through the frozen network: everything but --learn_extractor
-        args.frame_norm_method = "imagenet_inception"
-        multistep = getattr(args, "personalize_num_grad_steps", None) is not None
-        if getattr(args, "effnetv2_native_backward", False):
-            if args.learn_extractor:
-                sys.exit("error: --effnetv2_native_backward gives FiLM gradients through a frozen efficientnet_v2_s only: "
-                         "--learn_extractor (weight gradients and batch-statistics BatchNorm) is not built")
-        elif "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
-            sys.exit("error: --feature_extractor efficientnet_v2_s is inference-only here (no backward through its "
-                     "post-activation skips): use --mode test without --learn_extractor / --with_lite%s"
-                     % (" / --adapt_features" if multistep else ""))
+    spec = FROZEN_EXTRACTORS.get(fe)
+    if spec is None:
+        return
+    args.frame_norm_method = spec.frame_norm
+    if spec.frame_size is not None and args.frame_size != spec.frame_size:
+        sys.exit("error: --feature_extractor %s needs --frame_size %d (got %d)" % (fe, spec.frame_size, args.frame_size))
+    multistep = getattr(args, "personalize_num_grad_steps", None) is not None
+    if spec.weight_flag and getattr(args, spec.weight_flag, False):
+        pass  # native gradients of every parameter: everything the other extractors train is admitted
+    elif getattr(args, spec.film_flag, False):
+        if args.learn_extractor:
+            sys.exit("error: --%s gives FiLM gradients through a frozen %s only: --learn_extractor (%s) is not built"
+                     % (spec.film_flag, fe, spec.no_weights))
+    elif "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
+        sys.exit("error: --feature_extractor %s is inference-only here (no backward through %s): use --mode test "
+                 "without --learn_extractor / --with_lite%s" % (fe, spec.no_backward, " / --adapt_features" if multistep else ""))
 
 
 def frame_accuracy(logits, label):
@@ -286,17 +290,15 @@ class Learner:
         else:
             synthetic.init_parameters_(self.model, seed=a.seed,
                                        film_strength=0.02 if a.feature_extractor == "efficientnet_b0" else 0.1)
-        self._opt_in_vit_backward()
+        self._opt_in_native_backward()
         self.model._set_device(self.device)
         self.model._send_to_device()
 
-    def _opt_in_vit_backward(self):
-        if getattr(self.args, "vit_native_backward", False) and self.args.feature_extractor in VIT_EXTRACTORS:
-            self.model.feature_extractor.native_backward = True
-        if getattr(self.args, "vit_native_weight_backward", False) and self.args.feature_extractor in VIT_EXTRACTORS:
-            self.model.feature_extractor.native_weight_backward = True
-        if getattr(self.args, "effnetv2_native_backward", False) and self.args.feature_extractor == "efficientnet_v2_s":
-            self.model.feature_extractor.native_backward = True
+    def _opt_in_native_backward(self):
+        spec = FROZEN_EXTRACTORS.get(self.args.feature_extractor)
+        for flag, attr in ((spec.film_flag, "native_backward"), (spec.weight_flag, "native_weight_backward")) if spec else ():
+            if flag and getattr(self.args, flag, False):
+                setattr(self.model.feature_extractor, attr, True)
 
     def make_task(self, index):
         a = self.args
@@ -665,7 +667,7 @@ class MultiStepLearner(Learner):
         else:
             synthetic.init_parameters_(self.model, seed=a.seed,
                                        film_strength=0.02 if a.feature_extractor == "efficientnet_b0" else 0.1)
-        self._opt_in_vit_backward()
+        self._opt_in_native_backward()
         self.model._set_device(self.device)
         self.model._send_to_device()
         self.base_state = {k: v.clone() for k, v in self.model.state_dict().items()}

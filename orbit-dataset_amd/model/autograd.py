@@ -17,6 +17,7 @@ C-ABI call; torch only routes the gradients between the nodes and into `param.gr
   SetMeanFunction        orbit_set_mean  (+ broadcast backward)
 """
 import ctypes
+import math
 
 import torch
 
@@ -25,6 +26,21 @@ from .. import _lib
 
 def _empty_bytes(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
+def _grad_views(flat, param_index, needs):
+    """The flat native gradient as one view per entry (offset, torch shape, ...) of `param_index`; None where `needs` is False."""
+    return [flat[off:off + math.prod(shape)].view(shape) if need else None
+            for need, (off, shape, *_) in zip(needs, param_index)]
+
+
+def _require_same_parameters(plan, generation):
+    if plan.generation != generation:
+        # the backward kernels read filters / normalisation weights from the native plan, not from the tape: a parameter
+        # upload between forward and backward (optimizer step, load_state_dict, mark_parameters_changed + another
+        # forward) would silently differentiate a different network than the one that ran forward
+        raise RuntimeError("the extractor's parameters were modified (re-uploaded into the native plan) between the "
+                           "forward that recorded this tape and its backward; run backward before changing them")
 
 
 class ExtractorFunction(torch.autograd.Function):
@@ -66,12 +82,7 @@ class ExtractorFunction(torch.autograd.Function):
         lib = _lib.load()
         frames, gamma, beta = ctx.saved_tensors
         net, plan = ctx.net, ctx.plan
-        if plan.generation != ctx.generation:
-            # the backward kernels read filters / BatchNorm weights from the native plan, not from the tape: a parameter
-            # upload between forward and backward (optimizer step, load_state_dict, mark_parameters_changed + another
-            # forward) would silently differentiate a different network than the one that ran forward
-            raise RuntimeError("the extractor's parameters were modified (re-uploaded into the native plan) between the "
-                               "forward that recorded this tape and its backward; run backward before changing them")
+        _require_same_parameters(plan, ctx.generation)
         B, dev = frames.shape[0], frames.device
         n_fixed = 8
         need_params = any(ctx.needs_input_grad[n_fixed:])
@@ -98,21 +109,17 @@ class ExtractorFunction(torch.autograd.Function):
             net.persistent_release(ctx.persist_key)
         if need_film:
             out[3], out[4] = dgamma, dbeta
-        if need_params:
-            for j, (off, shape, replaced_by_film) in enumerate(ctx.param_index):
-                if not ctx.needs_input_grad[n_fixed + j] or (replaced_by_film and gamma is not None):
-                    continue
-                n = 1
-                for d in shape:
-                    n *= d
-                out[n_fixed + j] = flat[off:off + n].view(shape)
+        if need_params:  # (a FiLM-slot BatchNorm weight / bias that the film vectors replaced in the forward has no gradient)
+            out[n_fixed:] = _grad_views(flat, ctx.param_index,
+                                        [need and not (film_slot and gamma is not None) for need, (_, _, film_slot)
+                                         in zip(ctx.needs_input_grad[n_fixed:], ctx.param_index)])
         return tuple(out)
 
 
 class VitFunction(torch.autograd.Function):
     """feats = vit(frames; gamma, beta) with a tape. gamma / beta get their gradients from orbit_vit_backward (the network is
     frozen). Inputs after `param_index` are the network's other trainable Parameters, as in ExtractorFunction (only so that
-    autograd routes their gradients; `param_index` holds their (flat-gradient offset, torch shape)): when one of them needs a
+    autograd routes their gradients; `param_index` holds their HipNetwork._param_index entries): when one of them needs a
     gradient the backward is orbit_vit_backward_params. Runs on the caller's stream."""
 
     @staticmethod
@@ -138,9 +145,7 @@ class VitFunction(torch.autograd.Function):
         plan = ctx.plan
         n_fixed = 6
         out = [None] * (n_fixed + len(ctx.param_index))
-        if plan.generation != ctx.generation:  # (as ExtractorFunction: the backward reads the weights from the plan)
-            raise RuntimeError("the extractor's parameters were modified (re-uploaded into the native plan) between the "
-                               "forward that recorded this tape and its backward; run backward before changing them")
+        _require_same_parameters(plan, ctx.generation)
         if ctx.tape is None:
             raise RuntimeError("this ViT tape was already consumed by a backward")
         need_params = any(ctx.needs_input_grad[n_fixed:])
@@ -157,12 +162,7 @@ class VitFunction(torch.autograd.Function):
                 plan.handle, _lib.dptr(frames, torch.float32), ctx.B, _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(dfeats), tape,
                 ctx.tape.numel(), _lib.dptr(flat), _lib.dptr(dgamma), _lib.dptr(dbeta), ctypes.c_void_p(ws.data_ptr()),
                 ws.numel(), _lib.stream_handle()), "orbit_vit_backward_params")
-            for j, (off, shape) in enumerate(ctx.param_index):
-                if ctx.needs_input_grad[n_fixed + j]:
-                    n = 1
-                    for d in shape:
-                        n *= d
-                    out[n_fixed + j] = flat[off:off + n].view(shape)
+            out[n_fixed:] = _grad_views(flat, ctx.param_index, ctx.needs_input_grad[n_fixed:])
         else:
             ws = _empty_bytes(lib.orbit_vit_backward_workspace_bytes(plan.handle, ctx.B), gamma.device)
             _lib.check(lib.orbit_vit_backward(
@@ -308,15 +308,7 @@ class FilmGeneratorFunction(torch.autograd.Function):
                                               _lib.dptr(dl2), _lib.dptr(flat), _lib.dptr(dz), _lib.stream_handle()),
                    "orbit_filmgen_backward")
         out = [None, dz.view(ctx.z_shape) if ctx.needs_input_grad[1] else None, None]
-        for j, (off, shape) in enumerate(ctx.param_index):
-            if not ctx.needs_input_grad[3 + j]:
-                out.append(None)
-                continue
-            n = 1
-            for d in shape:
-                n *= d
-            out.append(flat[off:off + n].view(shape))
-        return tuple(out)
+        return tuple(out + _grad_views(flat, ctx.param_index, ctx.needs_input_grad[3:]))
 
 
 class MeanPoolFunction(torch.autograd.Function):

@@ -21,9 +21,6 @@ import torch.nn as nn
 from .. import _lib
 from .autograd import ExtractorFunction, VitFunction
 
-_EXTRACTOR_OUTPUT = {"resnet18": 512, "efficientnet_b0": 1280, "efficientnet_v2_s": 1280}
-_BN_EPS = {"resnet18": 1e-5, "efficientnet_b0": 1e-3, "efficientnet_v2_s": 1e-3, "set_encoder": 1e-5}
-
 
 class ParamNode(nn.Module):
     """Plain container node of the parameter tree (a conv, a BatchNorm, a block ...)."""
@@ -87,6 +84,10 @@ class HipNetwork(nn.Module):
     # native entry-point family (orbit_<api>_*) and the frame size of the throw-away plan that enumerates the parameters
     _api = "extractor"
     _probe_size = 64
+    _frame_size = None  # the one frame size the family runs on, where it is fixed
+    # the family has a training runtime: batch-statistics BatchNorm in train(), and a plan of its own (unfused) for a forward
+    # that uses them or records a tape; without one there is one plan per frame size and train() computes what eval() does
+    _training_runtime = True
     # a taped forward may be issued on a side stream beside another forward of the same plan (deferred_stats,
     # persistent_buffers: LITE's subset / query passes, few_shot_recognisers._get_features_with_split_batch)
     side_stream_tapes = True
@@ -117,6 +118,8 @@ class HipNetwork(nn.Module):
                 self._film_slot_names.append(fn("film_slot_name")(h, s).decode())
                 self._film_slot_channels.append(fn("film_slot_channels")(h, s))
             self.film_size = fn("film_size")(h)
+            # the normalisation weights / biases that FiLM vectors replace
+            self._film_keys = frozenset(n + leaf for n in self._film_slot_names for leaf in (".weight", ".bias"))
         finally:
             probe.destroy()
         self._leaves = []  # (module, attr, key)
@@ -161,22 +164,29 @@ class HipNetwork(nn.Module):
     def _plan(self, H, W, trainable=False):
         """inference plans may hold fused ops that have no backward form; a forward that records a tape or uses batch
         statistics gets its own (unfused) plan. Both enumerate the same parameters in the same order."""
-        plan = self._plans.get((H, W, trainable))
+        if self._frame_size is not None and (H, W) != (self._frame_size, self._frame_size):
+            raise ValueError("%s runs on %dx%d frames only (got %dx%d)" % (self.native_name, self._frame_size, self._frame_size,
+                                                                          H, W))
+        key = self._plan_key(H, W, trainable)
+        plan = self._plans.get(key)
         if plan is None:
-            plan = self._new_plan(H, W, trainable)
+            plan = self._new_plan(*key)
             names = [self._fn("param_name")(plan.handle, i).decode()
                      for i in range(self._fn("num_params")(plan.handle))]
             if names != [k for k, _ in self._keys]:
                 raise _lib.OrbitHipError("native plan enumerates different parameters than the module tree")
-            self._plans[(H, W, trainable)] = plan
+            self._plans[key] = plan
         return plan
+
+    def _plan_key(self, H, W, trainable):
+        return H, W, bool(trainable) and self._training_runtime
 
     def _new_plan(self, H, W, trainable):
         return _Plan(self.native_name, H, W, trainable, api=self._api)
 
     def in_sync(self, H, W, trainable=True):
         """True when the plan a forward at this frame size would use exists and holds the current parameters."""
-        plan = self._plans.get((H, W, trainable))
+        plan = self._plans.get(self._plan_key(H, W, trainable))
         return plan is not None and plan.stamp == self._stamp()
 
     class persistent_buffers:
@@ -279,6 +289,8 @@ class HipNetwork(nn.Module):
         training loop - such calls replay a captured HIP graph instead of ~1 300 launches (option train_graph)."""
         lib = _lib.load()
         rep = eag = 0
+        if not self._training_runtime:
+            return rep, eag
         for pl in self._plans.values():
             a, b = ctypes.c_long(0), ctypes.c_long(0)
             lib.orbit_extractor_train_graph_stats(pl.handle, ctypes.byref(a), ctypes.byref(b))
@@ -312,28 +324,38 @@ class HipNetwork(nn.Module):
     # ---- training path (tape + autograd) -------------------------------------------------------------
     bn_momentum = 0.1  # nn.BatchNorm2d default (torchvision resnet18, SimplePrePoolNet)
 
+    # which parameters may take a gradient: "all", "film" (the FiLM vectors and the FiLM-slot normalisation weights / biases of
+    # the otherwise frozen network) or "none"; a family that can be anything but "all" also gives the texts of its refusals
+    # (% {"name", "count", "first"})
+    _grad_scope = "all"
+    _refusal_none = _refusal_film = None
+
     def wants_grad(self, film=None):
         """True when a forward issued now has to record a tape: autograd is on and either one of the network's own
-        parameters or the FiLM vectors require a gradient."""
+        parameters or the FiLM vectors require a gradient. Raises NotImplementedError where the network's gradient scope does
+        not cover what requires one."""
         if not torch.is_grad_enabled():
             return False
-        if film is not None and (film[0].requires_grad or film[1].requires_grad):
-            return True
-        return any(own is not None and own.requires_grad for _, _, _, own in self._leaves)
+        if not (film is not None and (film[0].requires_grad or film[1].requires_grad)
+                or any(own is not None and own.requires_grad for _, _, _, own in self._leaves)):
+            return False
+        scope = self._grad_scope
+        if scope == "none":
+            raise NotImplementedError(self._refusal_none % {"name": self.native_name})
+        if scope == "film":
+            other = [key for _, _, key, own in self._leaves
+                     if own is not None and own.requires_grad and key not in self._film_keys]
+            if other:
+                raise NotImplementedError(self._refusal_film % {"name": self.native_name, "count": len(other), "first": other[0]})
+        return True
 
     def _param_index(self, plan):
-        """[(flat-gradient offset, torch shape, is a FiLM-replaceable BatchNorm weight/bias)] per own Parameter."""
+        """[(own Parameter, (flat-gradient offset, torch shape, is a FiLM-replaceable normalisation weight / bias))]"""
         cached = self.__dict__.get("_param_index_cache")
         if cached is None:
-            lib = _lib.load()
-            film_keys = set()
-            for name in self._film_slot_names:
-                film_keys.add(name + ".weight"), film_keys.add(name + ".bias")
-            cached = []
-            for i, (node, attr, key, own) in enumerate(self._leaves):
-                if own is not None:
-                    cached.append((own, (lib.orbit_extractor_param_offset(plan.handle, i), tuple(own.shape),
-                                         key in film_keys)))
+            offset = self._fn("param_offset")
+            cached = [(own, (offset(plan.handle, i), tuple(own.shape), key in self._film_keys))
+                      for i, (_, _, key, own) in enumerate(self._leaves) if own is not None]
             self.__dict__["_param_index_cache"] = cached
         return cached
 
@@ -364,6 +386,8 @@ class HipNetwork(nn.Module):
         plan.stamp = self._stamp()  # the plan already holds these values
 
     def _forward_train(self, plan, x, film, use_tape, bn_train, out):
+        """The forward that records a tape (use_tape) and / or uses batch statistics (bn_train): the hook of a family whose
+        training entry points differ."""
         lib = _lib.load()
         if not lib.orbit_extractor_supports_training(plan.handle):
             raise NotImplementedError(
@@ -372,8 +396,6 @@ class HipNetwork(nn.Module):
         B = x.shape[0]
         gamma, beta = film if film is not None else (None, None)
         if use_tape:
-            if out is not None:
-                raise ValueError("`out=` cannot be combined with autograd")
             entries = [(own, meta) for own, meta in self._param_index(plan) if own.requires_grad]
             feats = ExtractorFunction.apply(self, plan, x, gamma, beta, bn_train, self.bn_momentum,
                                             tuple(meta for _, meta in entries), *[own for own, _ in entries])
@@ -421,7 +443,8 @@ class HipNetwork(nn.Module):
             self.pending = []
 
     # ---- forward ------------------------------------------------------------------------------------
-    def forward(self, x, film=None, out=None, check_sync=True):
+    def _frames(self, x):
+        """The input of a forward as contiguous fp32 frames [B,3,H,W] on the device."""
         _lib.require_gpu()
         if x.dim() == 5:
             x = x.flatten(end_dim=1)
@@ -429,31 +452,48 @@ class HipNetwork(nn.Module):
             raise ValueError("expected frames of shape [B,3,H,W], got %s" % (tuple(x.shape),))
         if not x.is_cuda:
             raise _lib.OrbitHipError("frames must be on the HIP device (got %s); no CPU fallback" % x.device)
-        x = x.contiguous().float()
-        B, _, H, W = x.shape
+        return x.contiguous().float()
+
+    def _resolve_film(self, film):
+        """The (gamma, beta) pair a forward runs with: the explicit one, else what functional_call swapped in, else None."""
         if film is None and self.film_size > 0:
             film = self._gather_swapped_film()
         if film is not None:
             if film[0].numel() != self.film_size or film[1].numel() != self.film_size:
                 raise ValueError("film vectors must have %d elements" % self.film_size)
             film = (film[0].contiguous().float(), film[1].contiguous().float())
-        use_tape = B > 0 and self.wants_grad(film)
-        plan = self._plan(H, W, trainable=B > 0 and (use_tape or self.training))
-        if check_sync or plan.stamp is None:
-            self.sync(plan)
-        if B > 0 and (use_tape or self.training):
-            # batch-statistics BatchNorm and/or a recorded tape: the training runtime (csrc/extractor_train.hip)
-            return self._forward_train(plan, x, film, use_tape, self.training, out)
+        return film
+
+    def _forward_infer(self, plan, x, film, out):
+        """The forward without a tape, on running statistics: one native call."""
+        B = x.shape[0]
         feats = out if out is not None else torch.empty(B, self.output_size, device=x.device, dtype=torch.float32)
         if B == 0:
             return feats
         ws = self._workspace(plan, B, x.device)
         gamma, beta = film if film is not None else (None, None)
-        _lib.check(_lib.load().orbit_extractor_forward(
+        _lib.check(self._fn("forward")(
             plan.handle, _lib.dptr(x, torch.float32), B, _lib.dptr(gamma), _lib.dptr(beta),
             _lib.dptr(feats, torch.float32), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_handle()),
-            "orbit_extractor_forward")
+            "orbit_%s_forward" % self._api)
         return feats
+
+    def forward(self, x, film=None, out=None, check_sync=True):
+        x = self._frames(x)
+        B, _, H, W = x.shape
+        film = self._resolve_film(film)
+        use_tape = self.wants_grad(film) and B > 0  # raises before any launch
+        bn_train = self.training and self._training_runtime
+        train = B > 0 and (use_tape or bn_train)
+        plan = self._plan(H, W, trainable=train)
+        if check_sync or plan.stamp is None:
+            self.sync(plan)
+        if not train:
+            return self._forward_infer(plan, x, film, out)
+        if use_tape and out is not None:
+            raise ValueError("`out=` cannot be combined with autograd")
+        # batch-statistics BatchNorm and/or a recorded tape: the training runtime (csrc/extractor_train.hip, csrc/vit.hip)
+        return self._forward_train(plan, x, film, use_tape, bn_train, out)
 
     def __del__(self):
         try:
@@ -464,13 +504,7 @@ class HipNetwork(nn.Module):
 
 
 # torch-layout shapes of the leaves, so that state_dicts interchange with torchvision / timm checkpoints
-def _conv_shape(cout, cin, k):
-    return (cout, cin, k, k)
-
-
 class ResNet18(HipNetwork):
-    def __init__(self):
-        super().__init__("resnet18")
 
     def _leaf_shape(self, key, numel):
         if key == "conv1.weight":
@@ -486,10 +520,6 @@ class ResNet18(HipNetwork):
 
 
 class EfficientNetB0(HipNetwork):
-    def __init__(self):
-        super().__init__("efficientnet_b0")
-        self._numel = dict(self._keys)
-
     def _leaf_shape(self, key, numel):
         if not key.endswith(".weight") or ".bn" in key or key.startswith("bn"):
             return (numel,)
@@ -538,8 +568,8 @@ class EfficientNetV2S(HipNetwork):
     HipNetwork._register_leaf leaves (running_mean, num_batches_tracked, running_var), which ResNet18 and EfficientNetB0 keep
     (their key-list fixtures compare sets of keys and loads go by name, so the order matters to nobody there)."""
 
-    def __init__(self):
-        super().__init__("efficientnet_v2_s")
+    def __init__(self, name):
+        super().__init__(name)
         # the leaves arrive as (running_mean, running_var) and num_batches_tracked was registered with the first of them
         for m in self.modules():
             if "num_batches_tracked" in m._buffers:
@@ -574,46 +604,35 @@ class EfficientNetV2S(HipNetwork):
 
     native_backward = False  # opt-in (learner flag --effnetv2_native_backward)
 
-    _REFUSAL = ("efficientnet_v2_s is an inference-only extractor: no native backward and no batch-statistics BatchNorm (LITE "
-                "meta-training, --learn_extractor, FiLM gradients); call it in eval() under torch.no_grad() with frozen parameters")
+    _refusal_none = ("efficientnet_v2_s is an inference-only extractor: no native backward and no batch-statistics BatchNorm (LITE "
+                     "meta-training, --learn_extractor, FiLM gradients); call it in eval() under torch.no_grad() with frozen "
+                     "parameters")
     _REFUSAL_FROZEN = ("efficientnet_v2_s: native_backward gives the gradients of the FiLM vectors through the FROZEN network in "
                        "eval() only; %s: weight gradients (--learn_extractor) and batch-statistics BatchNorm are not built")
+    # (the FiLM-slot BatchNorm weights / biases themselves - the multi-step finetuner's unfreeze_film - are what the frozen
+    # backward differentiates: admitted, as on VisionTransformer; every other parameter is a weight gradient)
+    _refusal_film = _REFUSAL_FROZEN % ("%(count)d parameters other than the FiLM-slot BatchNorm weights / biases require a "
+                                       "gradient (first: %(first)s)")
+
+    @property
+    def _grad_scope(self):
+        return "film" if self.native_backward else "none"
 
     def _new_plan(self, H, W, trainable):
         # (a tape is only ever recorded under native_backward: the unfused plan then also carries the flag that opens it)
         return _Plan(self.native_name, H, W, trainable, api=self._api, res_post_backward=trainable and self.native_backward)
 
-    def wants_grad(self, film=None):
-        if not super().wants_grad(film):
-            return False
-        if not self.native_backward:
-            raise NotImplementedError(self._REFUSAL)
-        # (the FiLM-slot BatchNorm weights / biases themselves - the multi-step finetuner's unfreeze_film - are what the frozen
-        # backward differentiates: admitted, as on VisionTransformer; every other parameter is a weight gradient)
-        film_keys = {n + leaf for n in self._film_slot_names for leaf in (".weight", ".bias")}
-        other = [key for _, _, key, p in self._leaves if p is not None and p.requires_grad and key not in film_keys]
-        if other:
-            raise NotImplementedError(self._REFUSAL_FROZEN % ("%d parameters other than the FiLM-slot BatchNorm weights / biases "
-                                                              "require a gradient (first: %s)" % (len(other), other[0])))
-        return True
-
     def forward(self, x, film=None, out=None, check_sync=True):
-        # refused here, before a plan is built or a parameter uploaded: nothing is launched
+        # refused here, before a plan is built, a parameter uploaded or the device asked for: nothing is launched
         if self.training and x.numel() > 0:
             raise NotImplementedError(self._REFUSAL_FROZEN % "the module is in train() mode" if self.native_backward
-                                      else self._REFUSAL)
+                                      else self._refusal_none)
         if film is None and self.native_backward and torch.is_grad_enabled():
             film = self._gather_swapped_film(detach=False)  # functional_call with tensors that require a gradient
         self.wants_grad(film)
         return super().forward(x, film=film, out=out, check_sync=check_sync)
 
-    def _forward_train(self, plan, x, film, use_tape, bn_train, out):
-        if not (self.native_backward and use_tape and not bn_train):  # (the native plan reports no training path either)
-            raise NotImplementedError(self._REFUSAL)
-        return super()._forward_train(plan, x, film, use_tape, bn_train, out)
 
-
-_VIT_OUTPUT = {"vit_s_32": 384, "vit_b_32": 768, "vit_b_32_clip": 768}
 VIT_FRAME_SIZE = 224
 
 
@@ -631,13 +650,11 @@ class VisionTransformer(HipNetwork):
     position table is fixed)."""
 
     _api = "vit"
-    _probe_size = VIT_FRAME_SIZE
+    _probe_size = _frame_size = VIT_FRAME_SIZE
+    _training_runtime = False
     side_stream_tapes = False  # one stream per plan (include/orbit_hip.h): the tape and its backward stay on the caller's
     native_backward = False  # opt-in (learner flag --vit_native_backward)
     native_weight_backward = False  # second opt-in (learner flag --vit_native_weight_backward): weight gradients too
-
-    def __init__(self, name):
-        super().__init__(name)
 
     def _leaf_shape(self, key, numel):
         # (cls_token is the first key: its size is the embedding width D)
@@ -653,91 +670,32 @@ class VisionTransformer(HipNetwork):
             return {"qkv": (3 * D, D), "proj": (D, D), "fc1": (4 * D, D), "fc2": (D, 4 * D)}[key.split(".")[-2]]
         return (numel,)
 
-    def _plan(self, H, W, trainable=False):
-        if (H, W) != (VIT_FRAME_SIZE, VIT_FRAME_SIZE):
-            raise ValueError("%s runs on %dx%d frames only (got %dx%d)" % (self.native_name, VIT_FRAME_SIZE, VIT_FRAME_SIZE,
-                                                                          H, W))
-        return super()._plan(H, W, False)  # one plan: there is no training runtime
+    _refusal_none = ("%(name)s is an inference-only extractor: no native backward (LITE meta-training, --learn_extractor, FiLM "
+                     "gradients); run it under torch.no_grad() with frozen parameters")
+    _refusal_film = ("%(name)s: native_backward gives the gradients of the FiLM vectors / FiLM-slot LayerNorm parameters of a "
+                     "frozen network only; %(count)d other parameters require a gradient (first: %(first)s) and weight gradients "
+                     "(--learn_extractor) are not built")
 
-    def in_sync(self, H, W, trainable=True):
-        plan = self._plans.get((H, W, False))
-        return plan is not None and plan.stamp == self._stamp()
+    @property
+    def _grad_scope(self):
+        return "all" if self.native_weight_backward else "film" if self.native_backward else "none"
 
-    def prepare(self, H, W, trainable=True):
-        self.sync(self._plan(H, W))
+    def _forward_train(self, plan, x, film, use_tape, bn_train, out):
+        if film is None:  # the network's own LayerNorm parameters: autograd splits dgamma / dbeta into their 50 grads
+            slots = self.film_slot_modules()
+            film = (torch.cat([m._parameters["weight"].reshape(-1) for _, m in slots]),
+                    torch.cat([m._parameters["bias"].reshape(-1) for _, m in slots]))
+        # every other Parameter that requires a gradient (wants_grad admitted them: native_weight_backward); the FiLM-slot
+        # LayerNorm weights / biases take theirs through the film vectors
+        entries = [(own, meta) for own, meta in self._param_index(plan) if own.requires_grad and not meta[2]]
+        return VitFunction.apply(self, plan, x, film[0], film[1], tuple(meta for _, meta in entries),
+                                 *[own for own, _ in entries])
 
-    def train_graph_stats(self):
-        return 0, 0  # no training entry points
 
-    def wants_grad(self, film=None):
-        if not super().wants_grad(film):
-            return False
-        if not (self.native_backward or self.native_weight_backward):
-            raise NotImplementedError(
-                "%s is an inference-only extractor: no native backward (LITE meta-training, --learn_extractor, FiLM "
-                "gradients); run it under torch.no_grad() with frozen parameters" % self.native_name)
-        film_keys = {n + leaf for n in self._film_slot_names for leaf in (".weight", ".bias")}
-        other = [key for _, _, key, own in self._leaves if own is not None and own.requires_grad and key not in film_keys]
-        if other and not self.native_weight_backward:
-            raise NotImplementedError(
-                "%s: native_backward gives the gradients of the FiLM vectors / FiLM-slot LayerNorm parameters of a frozen "
-                "network only; %d other parameters require a gradient (first: %s) and weight gradients (--learn_extractor) "
-                "are not built" % (self.native_name, len(other), other[0]))
-        return True
-
-    def _weight_index(self, plan):
-        """[(Parameter, (flat-gradient offset, torch shape))] of the own Parameters that are not FiLM-slot LayerNorm weights /
-        biases (those take their gradients through the film vectors)."""
-        cached = self.__dict__.get("_weight_index_cache")
-        if cached is None:
-            lib = _lib.load()
-            film_keys = {n + leaf for n in self._film_slot_names for leaf in (".weight", ".bias")}
-            cached = [(own, (lib.orbit_vit_param_offset(plan.handle, i), tuple(own.shape)))
-                      for i, (_, _, key, own) in enumerate(self._leaves) if own is not None and key not in film_keys]
-            self.__dict__["_weight_index_cache"] = cached
-        return cached
-
-    def forward(self, x, film=None, out=None, check_sync=True):
-        _lib.require_gpu()
-        if x.dim() == 5:
-            x = x.flatten(end_dim=1)
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError("expected frames of shape [B,3,H,W], got %s" % (tuple(x.shape),))
-        if not x.is_cuda:
-            raise _lib.OrbitHipError("frames must be on the HIP device (got %s); no CPU fallback" % x.device)
-        x = x.contiguous().float()
-        B, _, H, W = x.shape
-        if film is None:
-            film = self._gather_swapped_film()
-        if film is not None:
-            if film[0].numel() != self.film_size or film[1].numel() != self.film_size:
-                raise ValueError("film vectors must have %d elements" % self.film_size)
-            film = (film[0].contiguous().float(), film[1].contiguous().float())
-        use_tape = self.wants_grad(film) and B > 0  # raises before any launch
-        plan = self._plan(H, W)
-        if check_sync or plan.stamp is None:
-            self.sync(plan)
-        if use_tape:
-            if out is not None:
-                raise ValueError("`out=` cannot be combined with autograd")
-            if film is None:  # the network's own LayerNorm parameters: autograd splits dgamma / dbeta into their 50 grads
-                slots = self.film_slot_modules()
-                film = (torch.cat([m._parameters["weight"].reshape(-1) for _, m in slots]),
-                        torch.cat([m._parameters["bias"].reshape(-1) for _, m in slots]))
-            # every other Parameter that requires a gradient (wants_grad admitted them: native_weight_backward)
-            entries = [(own, meta) for own, meta in self._weight_index(plan) if own.requires_grad]
-            return VitFunction.apply(self, plan, x, film[0], film[1], tuple(meta for _, meta in entries),
-                                     *[own for own, _ in entries])
-        feats = out if out is not None else torch.empty(B, self.output_size, device=x.device, dtype=torch.float32)
-        if B == 0:
-            return feats
-        ws = self._workspace(plan, B, x.device)
-        gamma, beta = film if film is not None else (None, None)
-        _lib.check(_lib.load().orbit_vit_forward(
-            plan.handle, _lib.dptr(x, torch.float32), B, _lib.dptr(gamma), _lib.dptr(beta),
-            _lib.dptr(feats, torch.float32), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_handle()),
-            "orbit_vit_forward")
-        return feats
+# name -> (class, output size): the extractors `create_feature_extractor` builds and the learners' --feature_extractor accepts
+EXTRACTORS = {"efficientnet_b0": (EfficientNetB0, 1280), "efficientnet_v2_s": (EfficientNetV2S, 1280), "resnet18": (ResNet18, 512),
+              "vit_s_32": (VisionTransformer, 384), "vit_b_32": (VisionTransformer, 768),
+              "vit_b_32_clip": (VisionTransformer, 768)}
 
 
 def create_feature_extractor(feature_extractor_name: str, pretrained: bool = True, with_film: bool = False,
@@ -745,17 +703,11 @@ def create_feature_extractor(feature_extractor_name: str, pretrained: bool = Tru
     """Same contract as the reference factory (model/feature_extractors.py:37-79)."""
     from .film import get_film_parameter_names, tag_film_layers
 
-    if feature_extractor_name == "resnet18":
-        feature_extractor = ResNet18()
-    elif feature_extractor_name == "efficientnet_b0":
-        feature_extractor = EfficientNetB0()
-    elif feature_extractor_name == "efficientnet_v2_s":
-        feature_extractor = EfficientNetV2S()
-    elif feature_extractor_name in _VIT_OUTPUT:
-        feature_extractor = VisionTransformer(feature_extractor_name)
-    else:
+    if feature_extractor_name not in EXTRACTORS:
         raise ValueError(f"Invalid feature_extractor_name: {feature_extractor_name}")
-    assert feature_extractor.output_size == {**_EXTRACTOR_OUTPUT, **_VIT_OUTPUT}[feature_extractor_name]
+    cls, output_size = EXTRACTORS[feature_extractor_name]
+    feature_extractor = cls(feature_extractor_name)
+    assert feature_extractor.output_size == output_size
 
     if not learn_extractor:
         freeze_extractor(feature_extractor)

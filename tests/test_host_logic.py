@@ -235,3 +235,24 @@ def test_stream_override_and_deferred_blocks_restore_state():
     assert fe.persistent_available("k")
     t = fe._persistent_tensor("k", "tape", 1000, torch.uint8, torch.device("cpu"))
     assert t.numel() == 1000 and fe._persistent_tensor("k", "tape", 600, torch.uint8, torch.device("cpu")).data_ptr() == t.data_ptr()
+
+
+@pytest.mark.parametrize("name", ["resnet18", "efficientnet_b0"])
+def test_wants_grad_of_a_network_whose_every_parameter_may_train(name):
+    """resnet18 and efficientnet_b0 take gradients for every parameter: wants_grad follows autograd's switch and what requires
+    a gradient - the own parameters or the film pair - and refuses nothing, without building a plan."""
+    from orbit_dataset_amd.model.feature_extractors import create_feature_extractor
+    fe, _ = create_feature_extractor(name, True, True, True)
+    with torch.enable_grad():
+        assert fe.wants_grad(None) is True
+        with torch.no_grad():
+            assert fe.wants_grad(None) is False
+        fe.requires_grad_(False)
+        assert fe.wants_grad(None) is False
+        for g_req in (False, True):
+            for b_req in (False, True):
+                film = (torch.ones(fe.film_size, requires_grad=g_req), torch.zeros(fe.film_size, requires_grad=b_req))
+                assert fe.wants_grad(film) is (g_req or b_req)
+                with torch.no_grad():
+                    assert fe.wants_grad(film) is False
+    assert not fe._plans
