@@ -188,7 +188,8 @@ int orbit_set_mean(const float* x, int n, int D, float* out, orbit_stream_t stre
  * "efficientnet_v2_s" (timm tf_efficientnetv2_s_in21k, num_classes = 0; 1280-d features) is an inference plan by default: its
  * ConvBnAct blocks add their skip after the activation, and orbit_extractor_supports_training is 0 and the tape /
  * backward-workspace size queries return 0 for it - unless the plan was created with ORBIT_PLAN_RES_POST_BACKWARD (below), which
- * opens the FROZEN training path: FiLM / BatchNorm weight and bias gradients under running statistics, nothing else. */
+ * opens the FROZEN training path: FiLM / BatchNorm weight and bias gradients under running statistics, nothing else - or with
+ * ORBIT_PLAN_RES_POST_TRAINING, which opens all of the training path (batch statistics, every parameter gradient). */
 int orbit_extractor_create(const char* name, int H, int W, orbit_extractor_t** out);
 /* flags: ORBIT_PLAN_UNFUSED = a plan for forwards that record a tape or use batch statistics (the LITE training step,
  * few_shot_recognisers.py:176-183): every MBConv block stays a conv + depthwise pair, whose outputs the backward needs;
@@ -201,6 +202,13 @@ int orbit_extractor_create(const char* name, int H, int W, orbit_extractor_t** o
  * launch - batch-statistics BatchNorm and filter gradients are not built for it. Without the flag the plan reports no training
  * path at all, as before. */
 #define ORBIT_PLAN_RES_POST_BACKWARD 2
+/* ORBIT_PLAN_RES_POST_TRAINING (implies ORBIT_PLAN_RES_POST_BACKWARD; same ops, same parameters in the same order; accepted and
+ * without effect for every other network): the plan that holds a post-activation skip trains like the others -
+ * orbit_extractor_train_forward(_ex) accepts bn_train != 0 (batch statistics, running-statistics updates, with
+ * ORBIT_TRAIN_NO_BACKWARD and ORBIT_TRAIN_DEFER_RUNNING_STATS as well) and orbit_extractor_backward accepts bn_train != 0 and
+ * filter_grads != 0 (reference: the LITE recipe of the efficientnet_v2_s checkpoints, --learn_extractor --with_lite,
+ * few_shot_recognisers.py:176-183). A plan created with ORBIT_PLAN_RES_POST_BACKWARD alone keeps the refusals above. */
+#define ORBIT_PLAN_RES_POST_TRAINING 4
 int orbit_extractor_create_ex(const char* name, int H, int W, int flags, orbit_extractor_t** out);
 void orbit_extractor_destroy(orbit_extractor_t* fe);
 
@@ -482,7 +490,8 @@ int orbit_mahalanobis_predict_backward(const float* dlogits, const float* featur
  * model/few_shot_recognisers.py:99-122 (_get_features, grad enabled), :345-356 (_get_task_embedding on the LITE
  * subset) and model/classifier_heads.py:202-230 (head). BatchNorm mode follows few_shot_recognisers.py:176-183.
  * Available for the resnet18, efficientnet_b0 and set_encoder plans (orbit_extractor_supports_training is 0 for a plan built
- * with the fused MBConv front op and for efficientnet_v2_s, whose post-activation skip has no backward form). */
+ * with the fused MBConv front op, and for efficientnet_v2_s unless its plan was created with ORBIT_PLAN_RES_POST_BACKWARD or
+ * ORBIT_PLAN_RES_POST_TRAINING). */
 int orbit_extractor_supports_training(const orbit_extractor_t* fe);
 size_t orbit_extractor_tape_bytes(const orbit_extractor_t* fe, int B);
 size_t orbit_extractor_backward_workspace_bytes(const orbit_extractor_t* fe, int B);
@@ -531,6 +540,10 @@ int orbit_extractor_backward(orbit_extractor_t* fe, const float* frames, int B, 
                              const float* film_beta, int bn_train, const float* dfeats, const void* tape,
                              size_t tape_bytes, float* param_grads, int filter_grads, float* dfilm_gamma,
                              float* dfilm_beta, void* workspace, size_t workspace_bytes, orbit_stream_t stream);
+/* filter_grads = ORBIT_FILTER_GRADS_SE_PER_BLOCK: as filter_grads = 1, with the parameter gradients of every squeeze-excite
+ * block summed by a launch of its own instead of the batched launches of the reverse pass (A/B measurements and parity runs;
+ * the two forms add the frames in different orders). */
+#define ORBIT_FILTER_GRADS_SE_PER_BLOCK 2
 /* Training entry points replay captured HIP graphs when a call repeats an earlier call's pointers and scalars exactly
  * (option train_graph = 1, off by default: it frees the host but the step is GPU-bound; the plan's own buffers never move). Diagnostics: calls that replayed / ran eagerly. */
 int orbit_extractor_train_graph_stats(const orbit_extractor_t* fe, long* replays, long* eager);
@@ -641,6 +654,13 @@ int orbit_op_dwconv2d_wgrad_xf(const float* x_raw, const float* in_scale, const 
 int orbit_op_se_gate_backward(const float* dxg, const float* x, const float* pooled, const float* w1, const float* b1,
                               const float* w2, const float* b2, float* dx, float* dw1, float* db1, float* dw2,
                               float* db2, int B, int HW, int C, int R, orbit_stream_t stream);
+/* The same with flags. ORBIT_SE_PARAMS_BATCHED: the four parameter gradients come from the kernel that sums them for all the
+ * blocks of a network's reverse pass (here as a launch of one job; R <= 64) instead of the per-block kernel. The two add the
+ * frames in different orders. */
+#define ORBIT_SE_PARAMS_BATCHED 1
+int orbit_op_se_gate_backward_ex(const float* dxg, const float* x, const float* pooled, const float* w1, const float* b1,
+                                 const float* w2, const float* b2, float* dx, float* dw1, float* db1, float* dw2,
+                                 float* db2, int B, int HW, int C, int R, int flags, orbit_stream_t stream);
 
 /* ---- input side: 8-bit frames -> normalised fp32 NCHW ([B][3][H][W], what the extractors consume) -------------------
  * frames: device pointer, [B][H][W][3] when layout_hwc != 0 (decoded images) or [B][3][H][W]; mean3 / std3: HOST arrays.

@@ -319,7 +319,9 @@ int launch_se_gate_backward(const float* dxg, const float* x, const float* poole
 const float* se_bwd_dpooled(const float* scratch, int B, int C, int R);
 // The parameter gradients of several squeeze-excite blocks in one launch: call launch_se_gate_backward with dw1 = nullptr
 // and a scratch of the block's own, keep se_bwd_param_job(scratch, ...) and run the batch when all blocks are through.
+// (more blocks than SE_PARAM_JOBS: run the batch when the list is full and go on - each block's scratch is its own)
 constexpr int SE_PARAM_JOBS = 16;
+constexpr int SE_PARAM_MAX_R = 64;  // the widest hidden layer the batched kernel holds (its 16-per-thread strip form)
 struct SeParamJob {
     const float *du, *dv, *h, *pooled;
     float *dw1, *db1, *dw2, *db2;

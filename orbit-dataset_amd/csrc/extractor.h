@@ -101,8 +101,8 @@ struct Op {
     int in = -1, out = -1, res = -1;  // buffer ids (BUF_* above)
     int H = 0, W = 0, Cin = 0, Cout = 0, KH = 1, KW = 1, stride = 1, pad_t = 0, pad_l = 0, Ho = 0, Wo = 0;
     int act = ORBIT_ACT_NONE, pool2 = 0, x_nchw = 0, use_gate = 0;
-    int res_post = 0;                     // OP_CONV: `res` joins after the activation (ConvDesc::res_post; trains in frozen form
-                                          // only, and only on an ORBIT_PLAN_RES_POST_BACKWARD plan)
+    int res_post = 0;                     // OP_CONV: `res` joins after the activation (ConvDesc::res_post; trains only on an
+                                          // ORBIT_PLAN_RES_POST_BACKWARD (frozen form) or ORBIT_PLAN_RES_POST_TRAINING plan)
     int weight = -1, bias = -1, bn = -1;  // param / BN indices
     size_t packed_off = 0;                // into the packed-weight pool
     size_t frag_off = SIZE_MAX;           // OP_CONV: the filter in MFMA-fragment order (csrc/pw_rgemm.hip) or SIZE_MAX
@@ -164,6 +164,7 @@ struct orbit_extractor {
     std::vector<BNDev> bn_dev;  // host copy of the fold descriptors
     bool finalized = false;
     bool res_post_backward = false;  // ORBIT_PLAN_RES_POST_BACKWARD: plan_trainable admits the post-activation skip
+    bool res_post_training = false;  // ORBIT_PLAN_RES_POST_TRAINING: ... and plan_frozen_only no longer holds for it
     // training side (csrc/extractor_train.hip), built at the first backward: the dgrad-packed filters, their re-layouts as one
     // launch for all layers (PackJob kind 4) and whether they follow the current parameters (every load clears it)
     float* d_dgrad = nullptr;

@@ -241,8 +241,9 @@ static int build_efficientnet_b0(orbit_extractor* fe, int H, int W, bool unfused
 // state_dict order. FiLM slots (model/film.py:38-56): root bn1 / bn2, bn1 of every ConvBnAct and EdgeResidual, bn2 of every
 // InvertedResidual. Every block is the plain conv (+ depthwise + squeeze-excite) sequence of the kernels efficientnet_b0 runs
 // at 14x14 / 7x7; the one new device form is ConvBnAct's skip, which joins AFTER the activation (Op::res_post). The training
-// runtime walks it only on a plan created with ORBIT_PLAN_RES_POST_BACKWARD, and then in frozen form only: running statistics,
-// no filter gradients (plan_trainable / plan_frozen_only, csrc/extractor_train.hip).
+// runtime walks it only on a plan created with ORBIT_PLAN_RES_POST_BACKWARD - then in frozen form only: running statistics, no
+// filter gradients - or with ORBIT_PLAN_RES_POST_TRAINING, which opens batch statistics and every parameter gradient
+// (plan_trainable / plan_frozen_only, csrc/extractor_train.hip).
 static int build_efficientnet_v2_s(orbit_extractor* fe, int H, int W) {
     fe->out_size = 1280;
     const float eps = 1e-3f;
@@ -383,7 +384,9 @@ int orbit_extractor_create_ex(const char* name, int H, int W, int flags, orbit_e
     ORBIT_REQUIRE(H >= 8 && W >= 8 && H <= 4096 && W <= 4096, "extractor_create: bad frame size %dx%d", H, W);
     orbit_extractor* fe = new orbit_extractor();
     fe->name = name, fe->pool.owner = name, fe->H = H, fe->W = W;
-    fe->res_post_backward = (flags & ORBIT_PLAN_RES_POST_BACKWARD) != 0;  // (same ops, same parameter order)
+    // (same ops, same parameter order under either flag; the second implies the first)
+    fe->res_post_training = (flags & ORBIT_PLAN_RES_POST_TRAINING) != 0;
+    fe->res_post_backward = fe->res_post_training || (flags & ORBIT_PLAN_RES_POST_BACKWARD) != 0;
     int rc;
     if (fe->name == "resnet18") rc = build_resnet18(fe, H, W);
     else if (fe->name == "efficientnet_b0") rc = build_efficientnet_b0(fe, H, W, (flags & ORBIT_PLAN_UNFUSED) != 0);

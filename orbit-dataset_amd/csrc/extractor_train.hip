@@ -11,7 +11,11 @@
 // OP_DWCONV (+BN, SiLU), OP_SE, OP_MAXPOOL, OP_AVGPOOL — i.e. resnet18, efficientnet_b0 and the set encoder. (The
 // opt-in fused MBConv front op of the inference plan has no training form.) efficientnet_v2_s, whose ConvBnAct blocks add
 // their skip after the activation (Op::res_post), runs on an ORBIT_PLAN_RES_POST_BACKWARD plan in frozen form only: running
-// statistics, BatchNorm weight / bias (FiLM) gradients, no filter gradients (plan_frozen_only).
+// statistics, BatchNorm weight / bias (FiLM) gradients, no filter gradients (plan_frozen_only) - and on an
+// ORBIT_PLAN_RES_POST_TRAINING plan like the others: batch statistics, running-statistics updates, every parameter gradient
+// (the LITE recipe of its checkpoints). Its 80 dense convs and 30 squeeze-excite blocks exceed the job lists of the two
+// batched end-of-pass launches (WGRAD_REDUCE_JOBS, SE_PARAM_JOBS): the reverse pass flushes a full list with a launch and
+// goes on collecting.
 #include "extractor.h"
 
 namespace orbit {
@@ -71,9 +75,10 @@ static bool plan_trainable(const orbit_extractor* fe) {
     return true;
 }
 
-// a plan that holds a post-activation skip trains in frozen form only: batch statistics and filter gradients are not built for
-// it (neither the statistics nor the filter-gradient kernels have been run at that network's shapes)
+// a plan that holds a post-activation skip trains in frozen form only - running statistics, no filter gradients - unless it was
+// created with ORBIT_PLAN_RES_POST_TRAINING (the first opt-in keeps the scope it was merged and measured with)
 static bool plan_frozen_only(const orbit_extractor* fe) {
+    if (fe->res_post_training) return false;
     for (const Op& o : fe->ops)
         if (o.kind == OP_CONV && o.res_post) return true;
     return false;
@@ -690,6 +695,8 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
     // filter_grads == 0: only the BatchNorm weight / bias gradients are wanted (FiLM fine-tuning of a frozen extractor,
     // few_shot_recognisers.py:196-199): skip every filter / squeeze-excite / bias gradient
     const bool wg = param_grads != nullptr && filter_grads != 0;
+    // (A/B and parity runs: every squeeze-excite block sums its parameter gradients in a launch of its own)
+    const bool se_per_block = filter_grads == ORBIT_FILTER_GRADS_SE_PER_BLOCK;
     const TapeLayout L = tape_layout(fe, B);
     const BwdLayout W = bwd_layout(fe, B);
     const char* tp = static_cast<const char*>(tape);
@@ -936,12 +943,19 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
                 // partial tiles stay in a region of their own: the split reductions of all layers run as ONE launch at the end
                 float* cw = cwgrad_base + cwgrad_used;
                 cwgrad_used += align_up(conv_wgrad_scratch_floats(B, o.Cin, o.Cout, o.KH, o.KW, o.Ho, o.Wo), 64);
-                WgradReduceJob* defer = n_wg_jobs < WGRAD_REDUCE_JOBS ? &wg_jobs.j[n_wg_jobs] : nullptr;
+                // (a full job list is flushed with a launch of its own: every layer owns its region and nothing in the pass reads
+                // the reduced gradients, so the jobs after it may reuse the list - efficientnet_v2_s holds 80 dense convs)
+                if (n_wg_jobs == WGRAD_REDUCE_JOBS) {
+                    rc = launch_conv_wgrad_reduce_batched(wg_jobs, n_wg_jobs, s);
+                    if (rc != ORBIT_OK) return rc;
+                    n_wg_jobs = 0;
+                }
+                WgradReduceJob* defer = &wg_jobs.j[n_wg_jobs];
                 rc = launch_conv_wgrad(out_tensor(src), o.x_nchw, slot_ptr(kdy), param_grads + fe->pool.off(o.weight), B,
                                        o.H, o.W, o.Cin, o.Cout, o.KH, o.KW, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, cw, s,
                                        o.use_gate ? tf(L.a[P.gate[i]]) : nullptr, defer);
                 if (rc != ORBIT_OK) return rc;
-                if (defer) ++n_wg_jobs;
+                ++n_wg_jobs;
             }
             if (need_dx && o.use_gate) {
                 // d(x * gate): data gradient of the product, then squeeze-excite backward (gate MLP + average pool)
@@ -957,7 +971,13 @@ static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const
                 float* pg = wg ? param_grads : nullptr;
                 // the four parameter gradients of the block's MLP: summed over the frames for ALL blocks in one launch at the
                 // end of the reverse pass (nothing in it reads them)
-                const bool batch_params = pg != nullptr && n_se_jobs < SE_PARAM_JOBS && so.R <= 48;
+                // (a full job list is flushed as the filter-gradient list above: each block owns its scratch)
+                const bool batch_params = pg != nullptr && !se_per_block && so.R <= SE_PARAM_MAX_R;
+                if (batch_params && n_se_jobs == SE_PARAM_JOBS) {
+                    rc = launch_se_param_grad_batched(se_jobs, n_se_jobs, s);
+                    if (rc != ORBIT_OK) return rc;
+                    n_se_jobs = 0;
+                }
                 if (batch_params) {
                     se_jobs.j[n_se_jobs++] = se_bwd_param_job(se_scratch, tf(L.p[se]), B, o.Cin, so.R, pg + fe->pool.off(so.se_w1),
                                                               pg + fe->pool.off(so.se_b1), pg + fe->pool.off(so.se_w2),

@@ -305,13 +305,18 @@ __global__ __launch_bounds__(256) void se_param_grad_kernel(const float* __restr
 // stages 50 frames of (du, pooled) columns and of (h, dv) rows in LDS and every thread keeps a [<= 12] strip of both products
 // (channel = lane, r = strip) in registers - each du / pooled element is read from L2 once instead of R times (the one-output-
 // per-16-lanes form read 1.4 GB through the L2 per step: 16 launches, 446 us). Frames are added in order: deterministic.
-constexpr int SEP_CT = 64, SEP_BT = 50, SEP_RG = 12;  // channels per block, frames per stage, r per thread (R <= 48)
+// SEP_RG = the strip: 12 (R <= 48, every block of efficientnet_b0) or 16 (R <= 64: efficientnet_v2_s's stage 6, taken only by a
+// launch that holds such a job). The (h, dv) tiles have 4 * SEP_RG columns: at 16 the row pitch is 64 floats and the four tiles
+// take 51.2 KB of static LDS. A wave reads ONE (b, r) of them at a time (g = tid / 64 is the wave, r = g + 4k): a broadcast
+// whatever the pitch; the (du, pooled) reads are 64 consecutive floats.
+constexpr int SEP_CT = 64, SEP_BT = 50;  // channels per block, frames per stage
+template <int SEP_RG>                    // r per thread
 __global__ __launch_bounds__(256) void se_param_grad_batched_kernel(SeParamJobs jobs) {
     const SeParamJob& j = jobs.j[blockIdx.y];
     const int B = j.B, C = j.C, R = j.R;
     const int c0 = blockIdx.x * SEP_CT;
     if (c0 >= C) return;
-    __shared__ float du_s[SEP_BT][SEP_CT], p_s[SEP_BT][SEP_CT], h_s[SEP_BT][48], dv_s[SEP_BT][48];
+    __shared__ float du_s[SEP_BT][SEP_CT], p_s[SEP_BT][SEP_CT], h_s[SEP_BT][4 * SEP_RG], dv_s[SEP_BT][4 * SEP_RG];
     const int tid = threadIdx.x, cl = tid & (SEP_CT - 1), g = tid / SEP_CT;  // g = 0..3: r = g, g + 4, ...
     const int c = c0 + cl;
     float a2[SEP_RG], a1[SEP_RG], sdu = 0.f, sdv = 0.f;
@@ -854,12 +859,16 @@ SeParamJob se_bwd_param_job(const float* scratch, const float* pooled, int B, in
 int launch_se_param_grad_batched(const SeParamJobs& jobs, int n, hipStream_t s) {
     ORBIT_REQUIRE(n >= 0 && n <= SE_PARAM_JOBS, "se_param_grad_batched: %d jobs", n);
     if (n == 0) return ORBIT_OK;
-    int gx = 1;
+    int gx = 1, rmax = 0;
     for (int k = 0; k < n; ++k) {
-        ORBIT_REQUIRE(jobs.j[k].R <= 48, "se_param_grad_batched: R = %d > 48", jobs.j[k].R);
+        ORBIT_REQUIRE(jobs.j[k].R > 0 && jobs.j[k].R <= SE_PARAM_MAX_R, "se_param_grad_batched: R = %d not in 1..%d", jobs.j[k].R,
+                      SE_PARAM_MAX_R);
         gx = std::max(gx, cdiv(jobs.j[k].C, SEP_CT));
+        rmax = std::max(rmax, jobs.j[k].R);
     }
-    se_param_grad_batched_kernel<<<dim3(gx, n), 256, 0, s>>>(jobs);
+    // (the 12-strip form wherever it holds every job: efficientnet_b0's launch stays the kernel it was)
+    if (rmax <= 48) se_param_grad_batched_kernel<12><<<dim3(gx, n), 256, 0, s>>>(jobs);
+    else se_param_grad_batched_kernel<16><<<dim3(gx, n), 256, 0, s>>>(jobs);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
 }
@@ -1134,7 +1143,18 @@ int orbit_op_dwconv2d_wgrad_xf(const float* x_raw, const float* in_scale, const 
 int orbit_op_se_gate_backward(const float* dxg, const float* x, const float* pooled, const float* w1, const float* b1,
                               const float* w2, const float* b2, float* dx, float* dw1, float* db1, float* dw2,
                               float* db2, int B, int HW, int C, int R, orbit_stream_t stream) {
+    return orbit_op_se_gate_backward_ex(dxg, x, pooled, w1, b1, w2, b2, dx, dw1, db1, dw2, db2, B, HW, C, R, 0, stream);
+}
+
+int orbit_op_se_gate_backward_ex(const float* dxg, const float* x, const float* pooled, const float* w1, const float* b1,
+                                 const float* w2, const float* b2, float* dx, float* dw1, float* db1, float* dw2,
+                                 float* db2, int B, int HW, int C, int R, int flags, orbit_stream_t stream) {
     ORBIT_REQUIRE(dxg && x && pooled && w1 && b1 && w2 && b2 && dx, "op_se_gate_backward: null pointer");
+    ORBIT_REQUIRE((flags & ~ORBIT_SE_PARAMS_BATCHED) == 0, "op_se_gate_backward: unknown flags 0x%x", flags);
+    ORBIT_REQUIRE(B > 0 && HW > 0, "op_se_gate_backward: bad geometry");
+    const bool batched = (flags & ORBIT_SE_PARAMS_BATCHED) && dw1;
+    ORBIT_REQUIRE(!batched || R <= SE_PARAM_MAX_R, "op_se_gate_backward: the batched parameter gradients hold R <= %d (got %d)",
+                  SE_PARAM_MAX_R, R);
     ORBIT_REQUIRE((dw1 == nullptr) == (db1 == nullptr) && (dw1 == nullptr) == (dw2 == nullptr) &&
                       (dw1 == nullptr) == (db2 == nullptr),
                   "op_se_gate_backward: parameter gradients come all or none");
@@ -1146,9 +1166,17 @@ int orbit_op_se_gate_backward(const float* dxg, const float* x, const float* poo
     float* w2t = gate + (size_t)B * C;  // [R][C], as the network plans pack it
     int rc = launch_se_gate(pooled, w1, b1, w2, b2, gate, B, C, R, s);
     if (rc == ORBIT_OK) rc = launch_transpose(w2, w2t, C, R, s);
-    if (rc == ORBIT_OK)
+    if (rc == ORBIT_OK && batched) {
+        // as the reverse pass of a network: the block leaves (du, dv, h) in its scratch, the batched kernel sums the frames
+        rc = launch_se_gate_backward(dxg, x, pooled, gate, w1, b1, w2, b2, dx, nullptr, nullptr, nullptr, nullptr, tmp, B, HW, C, R,
+                                     s, nullptr, w2t);
+        SeParamJobs jobs;
+        jobs.j[0] = se_bwd_param_job(tmp, pooled, B, C, R, dw1, db1, dw2, db2);
+        if (rc == ORBIT_OK) rc = launch_se_param_grad_batched(jobs, 1, s);
+    } else if (rc == ORBIT_OK) {
         rc = launch_se_gate_backward(dxg, x, pooled, gate, w1, b1, w2, b2, dx, dw1, db1, dw2, db2, tmp, B, HW, C, R, s, nullptr,
                                      w2t);
+    }
     (void)hipFreeAsync(tmp, s);
     return rc;
 }

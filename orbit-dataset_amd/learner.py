@@ -64,7 +64,12 @@ def build_parser():
     p.add_argument("--effnetv2_native_backward", action="store_true",
                    help="efficientnet_v2_s: opt in to the native FiLM gradients through the FROZEN network (--adapt_features "
                         "training, with or without --with_lite; the multi-step finetuner's --adapt_features). --learn_extractor "
-                        "stays refused: weight gradients and batch statistics are not built. Ignored for the other extractors")
+                        "stays refused under this flag alone: --effnetv2_native_weight_backward opens it. Ignored for the other "
+                        "extractors")
+    p.add_argument("--effnetv2_native_weight_backward", action="store_true",
+                   help="efficientnet_v2_s: opt in to native training of the whole network - batch-statistics BatchNorm and the "
+                        "gradients of every parameter (implies what --effnetv2_native_backward admits, and admits "
+                        "--learn_extractor, with or without --with_lite). Ignored for the other extractors")
     p.add_argument("--num_lite_samples", type=int, default=16)
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--seed", type=int, default=synthetic.DEFAULT_SEED)
@@ -144,8 +149,8 @@ FROZEN_EXTRACTORS = {
     "vit_b_32": FrozenExtractor("imagenet_inception", 224, *_VIT),
     "vit_b_32_clip": FrozenExtractor("openai_clip", 224, *_VIT),
     # any frame size, as efficientnet_b0. By default the native plan has no backward (its ConvBnAct blocks add the skip after
-    # the activation, csrc/extractor_train.hip plan_trainable)
-    "efficientnet_v2_s": FrozenExtractor("imagenet_inception", None, "effnetv2_native_backward", None,
+    # the activation, csrc/extractor_train.hip plan_trainable); the first flag opens the frozen form, the second all of it
+    "efficientnet_v2_s": FrozenExtractor("imagenet_inception", None, "effnetv2_native_backward", "effnetv2_native_weight_backward",
                                          "weight gradients and batch-statistics BatchNorm", "its post-activation skips"),
 }
 

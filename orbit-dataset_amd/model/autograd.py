@@ -101,7 +101,9 @@ class ExtractorFunction(torch.autograd.Function):
         _lib.check(lib.orbit_extractor_backward(
             plan.handle, _lib.dptr(frames, torch.float32), B, _lib.dptr(gamma), _lib.dptr(beta), ctx.bn_train,
             _lib.dptr(dfeats), ctypes.c_void_p(ctx.tape.data_ptr()), ctx.tape.numel(), _lib.dptr(flat),
-            int(filter_grads), _lib.dptr(dgamma), _lib.dptr(dbeta), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+            # (2 = ORBIT_FILTER_GRADS_SE_PER_BLOCK: the A/B form of the squeeze-excite parameter gradients)
+            int(filter_grads) * (2 if net.se_param_grads_per_block else 1), _lib.dptr(dgamma), _lib.dptr(dbeta),
+            ctypes.c_void_p(ws.data_ptr()), ws.numel(),
             _lib.stream_handle()),
             "orbit_extractor_backward")
         ctx.tape = None

@@ -44,13 +44,14 @@ def _ensure_child(module, name, cls=ParamNode):
 class _Plan:
     """One native plan (frame size specific) and the parameter stamp it was last synchronised with."""
 
-    def __init__(self, name, H, W, trainable=False, api="extractor", res_post_backward=False):
+    def __init__(self, name, H, W, trainable=False, api="extractor", res_post_backward=False, res_post_training=False):
         lib = _lib.load()
         h = ctypes.c_void_p()
         if api == "extractor":
             # the fused MBConv front kernels have no backward form: a plan that will record a tape is built without them
-            # (ORBIT_PLAN_UNFUSED = 1); res_post_backward adds ORBIT_PLAN_RES_POST_BACKWARD = 2 (efficientnet_v2_s's opt-in)
-            flags = (1 if trainable else 0) | (2 if res_post_backward else 0)
+            # (ORBIT_PLAN_UNFUSED = 1); res_post_backward adds ORBIT_PLAN_RES_POST_BACKWARD = 2 and res_post_training
+            # ORBIT_PLAN_RES_POST_TRAINING = 4 (efficientnet_v2_s's two opt-ins)
+            flags = (1 if trainable else 0) | (2 if res_post_backward else 0) | (4 if res_post_training else 0)
             _lib.check(lib.orbit_extractor_create_ex(name.encode(), H, W, flags, ctypes.byref(h)), "orbit_extractor_create_ex")
         else:
             _lib.check(getattr(lib, "orbit_%s_create" % api)(name.encode(), H, W, ctypes.byref(h)), "orbit_%s_create" % api)
@@ -323,6 +324,9 @@ class HipNetwork(nn.Module):
 
     # ---- training path (tape + autograd) -------------------------------------------------------------
     bn_momentum = 0.1  # nn.BatchNorm2d default (torchvision resnet18, SimplePrePoolNet)
+    # A/B measurements: the backward sums every squeeze-excite block's parameter gradients in a launch of its own
+    # (ORBIT_FILTER_GRADS_SE_PER_BLOCK) instead of the batched launches of the reverse pass
+    se_param_grads_per_block = False
 
     # which parameters may take a gradient: "all", "film" (the FiLM vectors and the FiLM-slot normalisation weights / biases of
     # the otherwise frozen network) or "none"; a family that can be anything but "all" also gives the texts of its refusals
@@ -561,7 +565,10 @@ class EfficientNetV2S(HipNetwork):
     on a plan created with ORBIT_PLAN_UNFUSED | ORBIT_PLAN_RES_POST_BACKWARD and gets their gradients through the FROZEN network
     from orbit_extractor_backward (autograd.ExtractorFunction); so do the FiLM-slot BatchNorm weights / biases themselves when
     they require a gradient (the multi-step finetuner's unfreeze_film). Any other own parameter that requires a gradient and
-    train() mode are still refused: weight gradients and batch statistics are not built for this network.
+    train() mode are still refused - unless `native_weight_backward = True` (which implies the above): the plan then carries
+    ORBIT_PLAN_RES_POST_TRAINING as well, train() runs batch-statistics BatchNorm and updates the running statistics as
+    EfficientNetB0 does (LITE's side-stream forms included), and every own parameter that requires a gradient gets it
+    (--learn_extractor: the recipe of the reference's efficientnet_v2_s checkpoints).
 
     One divergence from the sibling classes: every BatchNorm node's buffers are ordered (running_mean, running_var,
     num_batches_tracked) as nn.BatchNorm2d registers them, so that the state_dict ORDER equals the timm module's;
@@ -603,6 +610,8 @@ class EfficientNetV2S(HipNetwork):
         return (cout, numel // cout, 1, 1)
 
     native_backward = False  # opt-in (learner flag --effnetv2_native_backward)
+    # second opt-in (learner flag --effnetv2_native_weight_backward): batch statistics and every parameter gradient too
+    native_weight_backward = False
 
     _refusal_none = ("efficientnet_v2_s is an inference-only extractor: no native backward and no batch-statistics BatchNorm (LITE "
                      "meta-training, --learn_extractor, FiLM gradients); call it in eval() under torch.no_grad() with frozen "
@@ -616,18 +625,24 @@ class EfficientNetV2S(HipNetwork):
 
     @property
     def _grad_scope(self):
-        return "film" if self.native_backward else "none"
+        return "all" if self.native_weight_backward else "film" if self.native_backward else "none"
 
-    def _new_plan(self, H, W, trainable):
-        # (a tape is only ever recorded under native_backward: the unfused plan then also carries the flag that opens it)
-        return _Plan(self.native_name, H, W, trainable, api=self._api, res_post_backward=trainable and self.native_backward)
+    def _plan_key(self, H, W, trainable):
+        # the scope is baked into a training plan's flags: an instance whose opt-in is flipped never reuses a plan built under
+        # another scope (the inference plan carries no flag and is shared)
+        return super()._plan_key(H, W, trainable) + ((self._grad_scope,) if trainable else ())
+
+    def _new_plan(self, H, W, trainable, scope=None):
+        # (a tape is only ever recorded under an opt-in: the unfused plan then also carries the flag that opens its scope)
+        return _Plan(self.native_name, H, W, trainable, api=self._api, res_post_backward=trainable and scope in ("film", "all"),
+                     res_post_training=trainable and scope == "all")
 
     def forward(self, x, film=None, out=None, check_sync=True):
         # refused here, before a plan is built, a parameter uploaded or the device asked for: nothing is launched
-        if self.training and x.numel() > 0:
+        if self.training and x.numel() > 0 and self._grad_scope != "all":
             raise NotImplementedError(self._REFUSAL_FROZEN % "the module is in train() mode" if self.native_backward
                                       else self._refusal_none)
-        if film is None and self.native_backward and torch.is_grad_enabled():
+        if film is None and self._grad_scope != "none" and torch.is_grad_enabled():
             film = self._gather_swapped_film(detach=False)  # functional_call with tensors that require a gradient
         self.wants_grad(film)
         return super().forward(x, film=film, out=out, check_sync=check_sync)

@@ -14,6 +14,11 @@ torch.no_grad() - the step's forward-only time - and reports orbit_extractor_tap
 
     python tools/effnetv2_bench.py --train [--steps 5] [--warmup 2] [--way 5] [--context_per_class 40] [--query 200] [--size 224]
 
+--train --learn_extractor times one ProtoNets LITE step with every parameter of the extractor trained instead (the recipe of the
+reference's efficientnet_v2_s checkpoints: learn_extractor, no FiLM, native_weight_backward; batch-statistics BatchNorm on the
+cache pass, the LITE subset and the query batch; backward into all 450 parameters), and the same step with the squeeze-excite
+parameter gradients summed per block (HipNetwork.se_param_grads_per_block) beside it: the A/B of the batched kernel.
+
 Nothing here is gated."""
 import argparse
 import ctypes
@@ -83,6 +88,48 @@ def _families(run):
     return fam
 
 
+def learn_main(a):
+    """One ProtoNets LITE step with the whole extractor trained, batched and per-block squeeze-excite gradients (module docstring)."""
+    import numpy as np
+    import torch.nn.functional as F
+    from orbit_dataset_amd.model.few_shot_recognisers import SingleStepFewShotRecogniser
+    lib = _lib.load()
+    model = SingleStepFewShotRecogniser(NAME, False, "proto", 1, 256, True, a.lite_samples, 1.0)
+    synthetic.init_parameters_(model)
+    fe = model.feature_extractor
+    fe.native_weight_backward = True
+    model._set_device("cuda:0")
+    model._send_to_device()
+    model.set_test_mode(False)
+    S = a.size
+    task = synthetic.make_task_on_device(0, a.way, 1, a.context_per_class, a.query, S, 1, "cuda:0", template="blobs")
+    ctx, lab, tgt, tlab = task["context_clips"], task["context_labels"], task["target_clips"], task["target_labels"]
+
+    def step():
+        np.random.seed(7)
+        model._clear_caches()
+        model.personalise_with_lite(ctx, lab)
+        loss = F.cross_entropy(model.predict_a_batch(tgt), tlab)
+        loss.backward()
+        model._reset()
+        model.zero_grad(set_to_none=True)
+        return loss
+
+    plan = fe._plan(S, S, trainable=True)
+    result = {"metric": "effnetv2_lite_learn_step_ms", "frame_size": S, "way": a.way, "context_frames": len(ctx),
+              "query_frames": len(tgt), "lite_samples": a.lite_samples, "parameters_trained": sum(1 for _ in fe.parameters()),
+              "tape_bytes_per_frame": lib.orbit_extractor_tape_bytes(plan.handle, 8) // 8,
+              "backward_workspace_bytes_per_frame": lib.orbit_extractor_backward_workspace_bytes(plan.handle, 8) // 8}
+    for tag, per_block in (("step", False), ("step_se_per_block", True), ("step_again", False)):
+        fe.se_param_grads_per_block = per_block
+        med, lo, hi = _time(step, a.steps, a.warmup)
+        result[tag] = {"ms": round(med, 3), "ms_min": round(lo, 3), "ms_max": round(hi, 3)}
+    fe.se_param_grads_per_block = False
+    result["loss"] = round(float(step().detach()), 6)
+    result["max_memory_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
+    print(json.dumps(result))
+
+
 def train_main(a):
     """One CNAPs LITE step and its forward-only time (module docstring)."""
     import numpy as np
@@ -135,6 +182,9 @@ def main(argv=None):
     p.add_argument("--frames", type=int, default=200)
     p.add_argument("--size", type=int, default=224)
     p.add_argument("--train", action="store_true", help="time one CNAPs LITE step and its forward-only time instead")
+    p.add_argument("--learn_extractor", action="store_true",
+                   help="with --train: one ProtoNets LITE step with every parameter trained (native_weight_backward), and its "
+                        "A/B with per-block squeeze-excite gradients")
     p.add_argument("--way", type=int, default=5)
     p.add_argument("--context_per_class", type=int, default=40)
     p.add_argument("--query", type=int, default=200)
@@ -143,7 +193,7 @@ def main(argv=None):
     _lib.require_gpu()
     torch.cuda.set_device(0)
     if a.train:
-        return train_main(a)
+        return learn_main(a) if a.learn_extractor else train_main(a)
     fe, _ = create_feature_extractor(NAME, with_film=True, learn_extractor=False)
     synthetic.init_parameters_(fe)
     fe.to("cuda:0").eval()
