@@ -668,6 +668,33 @@ int orbit_op_se_gate_backward_ex(const float* dxg, const float* x, const float* 
 int orbit_frames_from_uint8(const uint8_t* frames, int layout_hwc, int B, int H, int W, const float* mean3,
                             const float* std3, float* out_nchw, orbit_stream_t stream);
 
+/* The same for frames stored at another size than the extractor runs at: Pillow's 8-bit Image.resize((W_out, H_out), filter)
+ * - the reference's offline scripts/resize_videos.py:46 pass, Image.LANCZOS - followed by the transform above, in one launch.
+ * The resize is Pillow's integer arithmetic on Pillow's coefficient tables (orbit_resize_coeffs): horizontal pass, rounded and
+ * clamped to 8 bits, then vertical pass, rounded and clamped; an axis whose size does not change is skipped. The resized
+ * pixels equal Pillow's bit for bit, the output equals to_tensor + normalize of them. H and W take independent ratios, up or
+ * down. The tables are built once per (device, in, out, filter) - a blocking upload on first use - and kept by the library;
+ * calls may come from several threads.
+ * Limits (ORBIT_ERR_ARG with a message, nothing launched): every side is at most ORBIT_RESIZE_MAX_SIZE, and a tile's working
+ * set fits 64 KB of LDS: 96 bytes for every input row under the vertical window of one output row - min(H_in, 2 * ceil(S *
+ * max(H_in / H_out, 1)) + 1) rows, S = 1 / 2 / 3 for bilinear / bicubic / lanczos - plus one input row of the columns under the
+ * horizontal windows of 32 output columns (3 bytes per pixel). Lanczos 1080 -> 32 on both axes (a 205-row window, 1080 columns)
+ * takes 23 KB of it, 32 -> 1080 under 1 KB; an 80-fold lanczos reduction of both axes of a 2560-pixel frame still fits (54 KB). */
+#define ORBIT_RESIZE_BILINEAR 0
+#define ORBIT_RESIZE_BICUBIC 1
+#define ORBIT_RESIZE_LANCZOS 2
+#define ORBIT_RESIZE_MAX_SIZE 16384
+int orbit_frames_resize_from_uint8(const uint8_t* frames, int layout_hwc, int B, int H_in, int W_in, int H_out, int W_out,
+                                   int filter /* ORBIT_RESIZE_* */, const float* mean3, const float* std3, float* out_nchw,
+                                   orbit_stream_t stream);
+/* Host only, no GPU: one axis' table of Pillow's 8-bit resampling from in_size to out_size pixels (Resample.c
+ * precompute_coeffs + normalize_coeffs_8bpc), the table the launcher above uploads. *ksize = 2 * ceil(S * max(in / out, 1)) + 1
+ * is always written; with kk == NULL that is all (size the arrays with it), else output index i reads the inputs
+ * xmin[i] .. xmin[i] + count[i] - 1 with the weights kk[i * ksize + 0 .. count[i]) (22 fractional bits; zero behind count[i]):
+ * out = clamp(((1 << 21) + sum px * kk) >> 22, 0, 255) in 32-bit integers. */
+int orbit_resize_coeffs(int in_size, int out_size, int filter, int* ksize, int32_t* kk /* [out][ksize] or NULL */,
+                        int* xmin /* [out] */, int* count /* [out] */);
+
 /* ---- measurement: per-launch HIP-event timing of the dominant kernel (conv_igemm, all variants) ---- */
 int orbit_prof_enable(int on);   /* on: reset and start recording an event pair per launch on its stream */
 /* waits for the recorded launches, returns summed duration, summed ALGORITHMIC flops and launch count */

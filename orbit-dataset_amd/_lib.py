@@ -144,6 +144,9 @@ _SIGNATURES = {
     "orbit_op_se_gate_backward": (c_int, [P] * 12 + [c_int] * 4 + [P]),
     "orbit_op_se_gate_backward_ex": (c_int, [P] * 12 + [c_int] * 5 + [P]),
     "orbit_frames_from_uint8": (c_int, [P, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P]),
+    "orbit_frames_resize_from_uint8": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float),
+                                               POINTER(c_float), P, P]),
+    "orbit_resize_coeffs": (c_int, [c_int, c_int, c_int, POINTER(c_int), P, P, P]),
     "orbit_prof_enable": (c_int, [c_int]),
     "orbit_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(ctypes.c_long)]),
     "orbit_prof_num_variants": (c_int, []),

@@ -1,6 +1,7 @@
 // Library-wide services of liborbit_hip, no kernels: the thread-local error buffer, the option table, the per-launch event
 // profiler every kernel family reports to (prof_start / prof_stop, orbit_prof_*) and the runtime entry points of the C-ABI.
 #include <cstdlib>
+#include <mutex>
 #include <vector>
 #include "common.h"
 
@@ -87,6 +88,9 @@ bool conv_prof_enabled() { return g_prof_on; }
 static std::vector<ProfRec> g_prof_recs;
 static std::vector<hipEvent_t> g_prof_pool;
 static std::vector<ProfVariant> g_prof_variants;
+// the record lists are shared by every thread that launches: the input pipeline's staging thread resizes frames
+// (orbit_frames_resize_from_uint8, csrc/ingest.hip) while the main thread runs the extractor
+static std::mutex g_prof_mu;
 
 static hipEvent_t prof_event() {
     if (!g_prof_pool.empty()) {
@@ -111,6 +115,7 @@ static int prof_variant(const char* name) {
 // called by every kernel family's launchers: returns a record index or -1 when profiling is off
 int prof_start(const char* name, double flops, double bytes, hipStream_t s, double silu) {
     if (!g_prof_on) return -1;
+    std::lock_guard<std::mutex> lock(g_prof_mu);
     ProfRec r;
     r.start = prof_event(), r.stop = prof_event(), r.variant = prof_variant(name);
     r.flops = flops, r.bytes = bytes, r.silu = silu;
@@ -119,7 +124,9 @@ int prof_start(const char* name, double flops, double bytes, hipStream_t s, doub
     return (int)g_prof_recs.size() - 1;
 }
 void prof_stop(int idx, hipStream_t s) {
-    if (idx >= 0 && idx < (int)g_prof_recs.size()) (void)hipEventRecord(g_prof_recs[idx].stop, s);
+    if (idx < 0) return;
+    std::lock_guard<std::mutex> lock(g_prof_mu);
+    if (idx < (int)g_prof_recs.size()) (void)hipEventRecord(g_prof_recs[idx].stop, s);
 }
 
 }  // namespace orbit
@@ -174,8 +181,10 @@ int orbit_device_count(void) {
 
 // Profiling of the dominant kernel (all conv_igemm instantiations). enable(1) starts recording one HIP event
 // pair per launch on the launch stream; collect() waits for them, folds them into per-variant totals and
-// returns the grand totals; variant(i) reads one row. Not thread-safe: one profiled stream at a time.
+// returns the grand totals; variant(i) reads one row. Launches may be recorded from several threads; enable / collect are
+// for one thread, called while no other thread is launching.
 int orbit_prof_enable(int on) {
+    std::lock_guard<std::mutex> lock(g_prof_mu);
     g_prof_on = on != 0;
     if (on) {
         for (ProfRec& r : g_prof_recs) g_prof_pool.push_back(r.start), g_prof_pool.push_back(r.stop);
@@ -187,6 +196,7 @@ int orbit_prof_enable(int on) {
 
 int orbit_prof_collect(double* total_ms, double* total_flops, long* launches) {
     double ms = 0, fl = 0;
+    std::lock_guard<std::mutex> lock(g_prof_mu);
     for (ProfRec& r : g_prof_recs) {
         ORBIT_HIP_CHECK(hipEventSynchronize(r.stop));
         float t = 0.f;

@@ -15,7 +15,10 @@ the recogniser moves each mini-batch to the device on the compute stream (`model
                       pinned slot <- frames, uint8 H2D on a COPY stream (150 KB per frame instead of 602 KB), then
                       orbit_frames_from_uint8 (the reference transform, bit-identical, csrc/ingest.hip) on that stream into
                       the slot's fp32 clips, and an event the compute stream waits on. `depth` slots rotate, so the upload
-                      and the normalisation of task i+1 run while the extractor works on task i.
+                      and the normalisation of task i+1 run while the extractor works on task i. With `frame_size` the
+                      frames stored at another size are resized in that launch (orbit_frames_resize_from_uint8: Pillow's
+                      8-bit Image.resize, bit-identical - the reference's offline scripts/resize_videos.py pass): the upload
+                      stays 8-bit at the stored size, the fp32 clips take the size the extractor runs at.
 
 `write_synthetic_orbit_directory` builds a small JPEG tree in that layout (the ORBIT dataset itself is not available
 offline); it is test / benchmark scaffolding, not part of the path.
@@ -29,7 +32,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from .utils import NORMALIZE_STATS
+from .utils import NORMALIZE_STATS, output_size, resample_filter
 
 
 # ---- directory layout (reference data/datasets.py:139-200) -----------------------------------------------------------------
@@ -230,14 +233,21 @@ class TaskPrefetcher:
     A staging thread fills pinned slot buffers and issues, on a copy stream, the 8-bit upload and the normalisation kernel of
     task i+1 (and i+2 with depth 3) while the caller's stream runs the extractor on task i. The yielded tensors belong to the
     slot: they stay valid until the NEXT task is requested (then the slot is handed back: an event on the caller's stream
-    makes the copy stream wait for the kernels that still read it)."""
+    makes the copy stream wait for the kernels that still read it).
 
-    def __init__(self, source, device, depth=3, frame_norm_method="imagenet", consumer_streams=()):
+    frame_size (an int or (H, W)): uint8 clips stored at another size leave at this one, resized on the device as PIL's
+    Image.resize((W, H), resample) would ("lanczos", "bicubic" or "bilinear"); clips already at it, and float32 clips,
+    take the path without a resize. Context and target clips may be stored at different sizes."""
+
+    def __init__(self, source, device, depth=3, frame_norm_method="imagenet", consumer_streams=(), frame_size=None,
+                 resample="lanczos"):
         from .. import _lib
         _lib.require_gpu()
         self._lib = _lib
         self.source, self.device = source, torch.device(device)
         self.mean, self.std = NORMALIZE_STATS[frame_norm_method]
+        self.frame_size, self.filter = frame_size, resample_filter(resample)
+        self.stored_sizes = set()  # (H, W) of the 8-bit clips staged so far
         self.depth = max(2, int(depth))
         self.slots = [_Slot() for _ in range(self.depth)]
         self.copy_stream = torch.cuda.Stream(device=self.device)
@@ -317,12 +327,20 @@ class TaskPrefetcher:
                             host.copy_(val)                  # (host-side wait only matters if the consumer never advanced)
                         u8 = self._buffer(slot.dev_u8, key, val.shape,
                                           lambda n: torch.empty(n, dtype=torch.uint8, device=self.device))
-                        f32 = self._buffer(slot.dev_f32, key, (*lead, 3, H, W),
+                        Ho, Wo = output_size(self.frame_size, H, W)
+                        if B > 0:
+                            self.stored_sizes.add((H, W))
+                        f32 = self._buffer(slot.dev_f32, key, (*lead, 3, Ho, Wo),
                                            lambda n: torch.empty(n, dtype=torch.float32, device=self.device))
                         u8.copy_(host, non_blocking=True)
-                        self._lib.check(lib.orbit_frames_from_uint8(self._lib.dptr(u8, torch.uint8), 1 if hwc else 0, B, H, W,
-                                                                    mean, std, self._lib.dptr(f32), self._lib.stream_handle()),
-                                        "orbit_frames_from_uint8")
+                        if B > 0 and (Ho, Wo) != (H, W):
+                            self._lib.check(lib.orbit_frames_resize_from_uint8(
+                                self._lib.dptr(u8, torch.uint8), 1 if hwc else 0, B, H, W, Ho, Wo, self.filter, mean, std,
+                                self._lib.dptr(f32), self._lib.stream_handle()), "orbit_frames_resize_from_uint8")
+                        else:
+                            self._lib.check(lib.orbit_frames_from_uint8(self._lib.dptr(u8, torch.uint8), 1 if hwc else 0, B, H, W,
+                                                                        mean, std, self._lib.dptr(f32), self._lib.stream_handle()),
+                                            "orbit_frames_from_uint8")
                         out[key] = f32
                     slot.ready = torch.cuda.Event()
                     slot.ready.record(self.copy_stream)

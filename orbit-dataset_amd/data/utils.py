@@ -6,8 +6,11 @@ Restatement of the three helpers of reference data/utils.py that the hot path's 
   unpack_task          :30-47   task_dict -> tuple, labels moved to the device
 plus the input-side counterpart of data/datasets.py:422-431 (`frames_from_uint8`): decoded 8-bit frames are uploaded
 as they are (a quarter of the fp32 bytes over PCIe) and normalised on the GPU, bit-identically to to_tensor + normalize.
+With `size=` they are also resized there, in the same launch, bit-identically to Pillow's 8-bit Image.resize (the reference's
+offline scripts/resize_videos.py pass).
 """
 import ctypes
+import operator
 
 import torch
 
@@ -16,11 +19,33 @@ NORMALIZE_STATS = {  # reference data/datasets.py:82-87
     "imagenet_inception": ([0.5, 0.5, 0.5], [0.5, 0.5, 0.5]),
     "openai_clip": ([0.48145466, 0.4578275, 0.40821073], [0.26862954, 0.26130258, 0.27577711]),
 }
+RESAMPLE_FILTERS = {"bilinear": 0, "bicubic": 1, "lanczos": 2}  # ORBIT_RESIZE_* of include/orbit_hip.h
 
 
-def frames_from_uint8(frames, device, frame_norm_method="imagenet", channels_last=True):
+def resample_filter(resample):
+    try:
+        return RESAMPLE_FILTERS[resample]
+    except KeyError:
+        raise ValueError("unknown resample filter %r (one of %s)" % (resample, ", ".join(sorted(RESAMPLE_FILTERS)))) from None
+
+
+def output_size(size, H, W):
+    """`size` (None, an int or (H, W)) -> the (H, W) the frames leave at"""
+    if size is None:
+        return H, W
+    try:
+        h = w = operator.index(size)
+    except TypeError:
+        h, w = size
+    return int(h), int(w)
+
+
+def frames_from_uint8(frames, device, frame_norm_method="imagenet", channels_last=True, size=None, resample="lanczos"):
     """uint8 frames [..., H, W, 3] (channels_last, as decoded) or [..., 3, H, W] -> normalised fp32 [..., 3, H, W] on
-    `device`. Host tensors are uploaded as 8-bit (pin them for an asynchronous copy); leading dimensions are kept."""
+    `device`. Host tensors are uploaded as 8-bit (pin them for an asynchronous copy); leading dimensions are kept.
+    size (an int or (H, W)): the frames are resized to it first, bit-identically to PIL's Image.resize((W, H), resample) of
+    the 8-bit frames - `resample` is "lanczos" (the reference's choice), "bicubic" or "bilinear"; None or the stored size:
+    no resize."""
     from .. import _lib
     _lib.require_gpu()
     if frames.dtype != torch.uint8:
@@ -36,9 +61,15 @@ def frames_from_uint8(frames, device, frame_norm_method="imagenet", channels_las
     B = 1
     for d in lead:
         B *= d
-    out = torch.empty(*lead, 3, H, W, device=u8.device, dtype=torch.float32)
-    if B > 0:
-        f3 = ctypes.c_float * 3
+    Ho, Wo = output_size(size, H, W)
+    filt = resample_filter(resample)
+    out = torch.empty(*lead, 3, Ho, Wo, device=u8.device, dtype=torch.float32)
+    f3 = ctypes.c_float * 3
+    if B > 0 and (Ho, Wo) != (H, W):
+        _lib.check(_lib.load().orbit_frames_resize_from_uint8(_lib.dptr(u8, torch.uint8), 1 if channels_last else 0, B, H, W, Ho,
+                                                              Wo, filt, f3(*mean), f3(*std), _lib.dptr(out),
+                                                              _lib.stream_handle()), "orbit_frames_resize_from_uint8")
+    elif B > 0:
         _lib.check(_lib.load().orbit_frames_from_uint8(_lib.dptr(u8, torch.uint8), 1 if channels_last else 0, B, H, W,
                                                        f3(*mean), f3(*std), _lib.dptr(out), _lib.stream_handle()),
                    "orbit_frames_from_uint8")

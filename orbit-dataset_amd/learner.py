@@ -116,7 +116,11 @@ def build_parser():
                    help="--mode test: a frame directory laid out like ORBIT (root/<user>/<object>/<clean|clutter>/<video>/*.jpg, "
                         "reference data/datasets.py:139-200). Tasks are the users' (context = clean videos, target = clutter "
                         "videos); frames are decoded with PIL by --num_workers threads, uploaded as 8-bit on a copy stream and "
-                        "normalised on the GPU (data/pipeline.TaskPrefetcher) while the previous task runs")
+                        "normalised on the GPU (data/pipeline.TaskPrefetcher) while the previous task runs. Frames stored at "
+                        "another size than --frame_size are resized to it on the GPU in the same launch (--resample)")
+    p.add_argument("--resample", default="lanczos", choices=["lanczos", "bicubic", "bilinear"],
+                   help="with --data_root: the filter of that resize, PIL's 8-bit Image.resize bit for bit (default: the "
+                        "reference's offline pass, scripts/resize_videos.py:46 Image.LANCZOS)")
     # dataset-side flags of the reference (utils/args.py:41-73), used with --data_root
     p.add_argument("--test_way_method", default="max", choices=["random", "max"])
     p.add_argument("--test_object_cap", type=int, default=15)
@@ -517,7 +521,8 @@ class Learner:
     def test_directory(self):
         """The reference's test loop (single-step-learner.py:298-375) over a JPEG directory: one task per user, personalise
         on the context clips, then per target VIDEO predict on its frame history, frame accuracy per video averaged per
-        task. Decode, 8-bit upload and normalisation of task i+1 overlap the extractor work of task i."""
+        task. Decode, 8-bit upload and normalisation of task i+1 overlap the extractor work of task i. A tree stored at
+        another size than --frame_size is resized to it in the normalisation launch (--resample)."""
         import random
         from concurrent.futures import ThreadPoolExecutor
         from .data.datasets import UserEpisodicORBITDataset
@@ -550,7 +555,8 @@ class Learner:
         metrics = OrbitMetrics(save_dir)
         mine = list(range(len(order)))[self.rank::self.world]  # global indices of this rank's tasks
         t_all = time.perf_counter()
-        prefetch = TaskPrefetcher(source, self.device, depth=3, frame_norm_method=a.frame_norm_method)
+        prefetch = TaskPrefetcher(source, self.device, depth=3, frame_norm_method=a.frame_norm_method, frame_size=a.frame_size,
+                                  resample=a.resample)
         with torch.no_grad():
             for k, task in enumerate(prefetch):
                 metrics.begin_task(mine[k], task["user"], task.get("object_list"))
@@ -586,10 +592,16 @@ class Learner:
             inference_ms = [x for g in gathered for x in g[2]]
             frames = sum(g[3] for g in gathered)
         metrics = metrics.gather(self.world, with_predictions=bool(save_dir))
+        stored = sorted(prefetch.stored_sizes)  # (this rank's tasks)
         stats = {"frame_acc": mean_ci(task_acc), "personalise_ms": mean_ci(personalise_ms),
                  "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world,
-                 "target_frames": frames, "wall_s": wall, "data_root": a.data_root, "orbit_metrics": metrics.report()}
+                 "target_frames": frames, "wall_s": wall, "data_root": a.data_root, "orbit_metrics": metrics.report(),
+                 "stored_frame_size": [list(hw) for hw in stored], "frame_size": [a.frame_size, a.frame_size],
+                 "resample": a.resample if any(hw != (a.frame_size, a.frame_size) for hw in stored) else None}
         if self.rank == 0:
+            print("test (%s): frames stored at %s, extractor ran at %dx%d%s"
+                  % (a.data_root, ", ".join("%dx%d" % hw for hw in stored) or "-", a.frame_size, a.frame_size,
+                     " (resized on the GPU, %s)" % a.resample if stats["resample"] else ""))
             print("test (%s): frame_acc %.2f (%.2f) %% | time to personalise %.2f (%.2f) ms | inference %.4f (%.4f) ms/frame "
                   "| %d tasks, %d target frames in %.1f s incl. JPEG decode (%d threads)"
                   % (a.data_root, 100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1], *_shown(stats["personalise_ms"]),

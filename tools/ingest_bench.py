@@ -1,0 +1,97 @@
+"""orbit_frames_resize_from_uint8 (csrc/ingest.hip: Pillow's 8-bit resize + to_tensor + normalize in one launch) on the two
+resizes a user of the ORBIT tree runs - the raw 1080 x 1080 frames to 224, and a 224 tree to 84 - for all three filters, 200
+frames per launch: us per launch and GB/s over the profiler's bytes (8-bit frames in, fp32 frames out), the byte floor at the
+6.3 TB/s DESIGN.md prices HBM at, and beside them the time PIL's Image.resize takes for the same frames on 16 threads - the
+offline pass of the reference (scripts/resize_videos.py:46) this replaces. The first frame of every case is compared with PIL.
+Usage (GPU box): python tools/ingest_bench.py [--frames 200] [--reps 10] [--threads 16]"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from PIL import Image
+
+import orbit_dataset_amd  # noqa
+from orbit_dataset_amd import _lib
+from orbit_dataset_amd.data.utils import NORMALIZE_STATS, frames_from_uint8
+
+HBM_BYTES_PER_S = 6.3e12
+PIL_FILTERS = {"bilinear": Image.BILINEAR, "bicubic": Image.BICUBIC, "lanczos": Image.LANCZOS}
+
+
+def measure(lib, run, reps):
+    """(us per launch, profiler bytes per launch, kernel name) from the library's per-launch event records"""
+    for _ in range(2):
+        run()
+    torch.cuda.synchronize()
+    lib.orbit_prof_enable(1)
+    for _ in range(reps):
+        run()
+    torch.cuda.synchronize()
+    lib.orbit_prof_enable(0)
+    ms, n = ctypes.c_double(), ctypes.c_long()
+    lib.orbit_prof_collect(ctypes.byref(ms), None, ctypes.byref(n))
+    assert n.value == reps and lib.orbit_prof_num_variants() == 1, (n.value, lib.orbit_prof_num_variants())
+    name, nbytes = ctypes.create_string_buffer(48), ctypes.c_double()
+    lib.orbit_prof_variant(0, name, None, None, None, ctypes.byref(nbytes))
+    return 1e3 * ms.value / reps, nbytes.value / reps, name.value.decode()
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--frames", type=int, default=200)
+    p.add_argument("--reps", type=int, default=10)
+    p.add_argument("--threads", type=int, default=16)
+    p.add_argument("--json", default=None, help="also write the rows to this file")
+    a = p.parse_args(argv)
+    _lib.require_gpu()
+    lib = _lib.load()
+    dev = torch.device("cuda", 0)
+    mean, std = (torch.tensor(v)[:, None, None] for v in NORMALIZE_STATS["imagenet"])
+    pool = ThreadPoolExecutor(max_workers=a.threads)
+    rows = []
+    print("%d frames per launch, device %s, PIL %s on %d threads" % (a.frames, torch.cuda.get_device_name(0), Image.__version__, a.threads))
+    for size_in, size_out in ((1080, 224), (224, 84)):
+        u8 = torch.randint(0, 256, (a.frames, size_in, size_in, 3), dtype=torch.uint8, device=dev)
+        host = u8.cpu().numpy()
+        for resample in ("lanczos", "bicubic", "bilinear"):
+            out = {}
+
+            def run():
+                out["y"] = frames_from_uint8(u8, dev, "imagenet", channels_last=True, size=size_out, resample=resample)
+
+            us, nbytes, name = measure(lib, run, a.reps)
+            floor_us = 1e6 * nbytes / HBM_BYTES_PER_S
+
+            def pil_one(i):
+                return np.array(Image.fromarray(host[i]).resize((size_out, size_out), PIL_FILTERS[resample]))
+
+            pil_s = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                resized = list(pool.map(pil_one, range(a.frames)))
+                pil_s.append(time.perf_counter() - t0)
+            want = (torch.from_numpy(resized[0]).permute(2, 0, 1).float().div(255) - mean) / std
+            exact = bool(torch.equal(out["y"][0].cpu(), want))
+            rows.append({"in": size_in, "out": size_out, "filter": resample, "kernel": name, "frames": a.frames, "us_per_launch": us,
+                         "bytes_per_launch": nbytes, "gb_per_s": nbytes / us / 1e3, "byte_floor_us": floor_us,
+                         "floor_over_time": floor_us / us, "pil_ms": 1e3 * min(pil_s), "pil_threads": a.threads, "first_frame_equals_pil": exact})
+            print("%4d -> %3d %-8s %9.1f us/launch  %7.1f GB/s  (byte floor %6.1f us at 6.3 TB/s, %4.1f %% of the time)   PIL x%d threads %8.1f ms "
+                  "(%5.0fx)   first frame %s PIL" % (size_in, size_out, resample, us, nbytes / us / 1e3, floor_us, 100 * floor_us / us,
+                                                     a.threads, 1e3 * min(pil_s), 1e6 * min(pil_s) / us, "==" if exact else "!="), flush=True)
+            assert exact, "the resized frame differs from PIL"
+        del u8, host
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+    return rows
+
+
+if __name__ == "__main__":
+    main()
