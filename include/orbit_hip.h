@@ -695,6 +695,77 @@ int orbit_frames_resize_from_uint8(const uint8_t* frames, int layout_hwc, int B,
 int orbit_resize_coeffs(int in_size, int out_size, int filter, int* ksize, int32_t* kk /* [out][ksize] or NULL */,
                         int* xmin /* [out] */, int* count /* [out] */);
 
+/* ---- JPEG decode on the device (csrc/jpeg.hip, csrc/jpeg_core.h) -------------------------------------------------------
+ * Baseline sequential JPEG files -> 8-bit RGB frames [B][H][W][3], the layout the two launchers above take with layout_hwc = 1;
+ * the pixels equal np.asarray(Image.open(f).convert("RGB")) of Pillow / libjpeg(-turbo) bit for bit: libjpeg's integer
+ * "islow" inverse DCT, its triangle ("fancy") chroma upsampling and its YCbCr -> RGB tables. In scope: SOF0, 8-bit samples,
+ * Huffman coding, one interleaved scan, 1 component or 3 components YCbCr with luma sampled 1x1, 2x1 or 2x2 and chroma 1x1,
+ * 8-bit quantisation tables, any restart interval, sides up to ORBIT_RESIZE_MAX_SIZE. Everything else is the caller's to
+ * decode on the host (orbit_jpeg_parse says which files).
+ *
+ * The descriptor of one file. orbit_jpeg_parse fills everything but file_offset, which the caller sets to the file's first byte
+ * in the arena it uploads. Tables are in decode form: qt[c] is component c's quantisation table in natural (row-major) order;
+ * huff[0..1] are the DC tables, huff[2..3] the AC tables the scan uses, dc_slot[c] / ac_slot[c] (0 or 1) select component c's.
+ * A code of length l and value c <= maxcode[l] is the symbol huffval[(valptr[l] + c) & 255] (maxcode[l] = -1: no code of that
+ * length); look[next 8 bits] = (length << 8) | symbol for the codes of at most 8 bits, 0 for longer ones. */
+#define ORBIT_JPEG_STAGE_BYTES 1024 /* the entropy kernel stages the byte stream through LDS in tiles of this many bytes */
+typedef struct orbit_jpeg_huff {
+    int32_t maxcode[18];
+    int32_t valptr[17];
+    uint8_t huffval[256];
+    uint16_t look[256];
+} orbit_jpeg_huff_t;
+typedef struct orbit_jpeg_desc {
+    uint64_t file_offset;          /* of the file's first byte in the arena (set by the caller) */
+    uint32_t ecs_offset;           /* of the entropy-coded segment in the file: the byte behind the SOS header */
+    uint32_t ecs_bytes;            /* from there to the end of the file; the decoder stops at the EOI marker */
+    int32_t status;                /* what orbit_jpeg_parse returned: 0 = decode on the device, > 0 = skip (host decode) */
+    int32_t width, height, ncomp;
+    int32_t hs[3], vs[3];          /* sampling factors of the components */
+    int32_t dc_slot[3], ac_slot[3];
+    int32_t restart_interval;      /* in MCUs, 0 = none */
+    int32_t reserved;
+    uint16_t qt[3][64];
+    orbit_jpeg_huff_t huff[4];
+} orbit_jpeg_desc_t;
+/* orbit_jpeg_parse's positive return codes: why the file is out of the device path's scope */
+#define ORBIT_JPEG_PROGRESSIVE 1   /* SOF2 */
+#define ORBIT_JPEG_ARITHMETIC 2    /* SOF9 .. SOF15 */
+#define ORBIT_JPEG_SOF_OTHER 3     /* extended sequential, lossless, hierarchical */
+#define ORBIT_JPEG_PRECISION 4     /* not 8-bit samples */
+#define ORBIT_JPEG_COMPONENTS 5    /* neither 1 nor 3 components (CMYK / YCCK) */
+#define ORBIT_JPEG_COLORSPACE 6    /* an Adobe marker without JFIF, or components named R, G, B */
+#define ORBIT_JPEG_SAMPLING 7      /* sampling factors other than 4:4:4, 4:2:2, 4:2:0 */
+#define ORBIT_JPEG_DQT16 8         /* a 16-bit quantisation table */
+#define ORBIT_JPEG_MULTISCAN 9     /* the first scan does not hold all components in frame order, or is not 0..63 */
+#define ORBIT_JPEG_TABLES 10       /* a table the scan names is missing or malformed, or it uses more than 2 + 2 Huffman tables */
+#define ORBIT_JPEG_SIZE 11         /* a side is 0 or exceeds ORBIT_RESIZE_MAX_SIZE */
+/* Host only, no GPU: parse the headers of one file up to its first scan into *desc (desc_bytes = sizeof(orbit_jpeg_desc_t),
+ * checked). Returns 0 when the device path decodes the file, one of the codes above when the host has to (width, height and
+ * ncomp are filled in once the frame header was seen, 0 before), ORBIT_ERR_ARG with a message when the buffer is not a JPEG
+ * file or a header runs past its end. Every length in the file is checked against `bytes`. Reentrant. */
+int orbit_jpeg_parse(const uint8_t* data, size_t bytes, orbit_jpeg_desc_t* desc, size_t desc_bytes);
+/* bits of a frame's decode status (0 = the frame was decoded and equals libjpeg's output) */
+#define ORBIT_JPEG_ST_OVERRUN 1    /* the stream ended, or a marker came, before the last block */
+#define ORBIT_JPEG_ST_CODE 2       /* no Huffman code within 16 bits */
+#define ORBIT_JPEG_ST_INDEX 4      /* a coefficient index past 63 */
+#define ORBIT_JPEG_ST_RESTART 8    /* not the expected restart marker, or bytes in front of it */
+#define ORBIT_JPEG_ST_RANGE 16     /* a value outside the range in which libjpeg's variants agree with each other */
+#define ORBIT_JPEG_ST_TRAILING 32  /* the last block is not followed by EOI */
+#define ORBIT_JPEG_ST_DESC 64      /* the descriptor contradicts itself, the call's H x W or the arena */
+/* Workspace of one launch of B frames of H x W: coefficients (2 bytes) and component planes (1 byte) of every frame at the
+ * largest block count a sampling in scope gives. orbit_frames_from_jpeg works in chunks of frames when handed less, down to
+ * orbit_jpeg_workspace_bytes(1, H, W). 0 for bad sizes. */
+size_t orbit_jpeg_workspace_bytes(int B, int H, int W);
+/* arena: device buffer of arena_bytes holding the files; descs: device copy of the B descriptors; out_u8_hwc [B][H][W][3];
+ * status [B] int32, written for every frame: 0, ORBIT_JPEG_ST_* bits, or -code for a frame whose descriptor's status is a
+ * non-zero code (skipped: its pixels are left untouched). All frames are H x W; one that is not gets ORBIT_JPEG_ST_DESC.
+ * Three kernels per chunk: entropy decode (one wave per frame), dequantisation + inverse DCT, upsampling + colour
+ * conversion. No read leaves the arena, no write leaves the frame's own slice of the workspace and of the output, whatever
+ * the file holds. */
+int orbit_frames_from_jpeg(const uint8_t* arena, size_t arena_bytes, const orbit_jpeg_desc_t* descs, int B, int H, int W,
+                           uint8_t* out_u8_hwc, int32_t* status, void* workspace, size_t workspace_bytes, orbit_stream_t stream);
+
 /* ---- measurement: per-launch HIP-event timing of the dominant kernel (conv_igemm, all variants) ---- */
 int orbit_prof_enable(int on);   /* on: reset and start recording an event pair per launch on its stream */
 /* waits for the recorded launches, returns summed duration, summed ALGORITHMIC flops and launch count */

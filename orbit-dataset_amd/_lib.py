@@ -147,6 +147,9 @@ _SIGNATURES = {
     "orbit_frames_resize_from_uint8": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float),
                                                POINTER(c_float), P, P]),
     "orbit_resize_coeffs": (c_int, [c_int, c_int, c_int, POINTER(c_int), P, P, P]),
+    "orbit_jpeg_parse": (c_int, [P, c_size_t, P, c_size_t]),
+    "orbit_jpeg_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "orbit_frames_from_jpeg": (c_int, [P, c_size_t, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "orbit_prof_enable": (c_int, [c_int]),
     "orbit_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(ctypes.c_long)]),
     "orbit_prof_num_variants": (c_int, []),
@@ -173,6 +176,24 @@ _SIGNATURES = {
 }
 
 EXPORTS = tuple(_SIGNATURES)
+
+
+class JpegHuff(ctypes.Structure):
+    """orbit_jpeg_huff_t of include/orbit_hip.h"""
+    _fields_ = [("maxcode", ctypes.c_int32 * 18), ("valptr", ctypes.c_int32 * 17), ("huffval", ctypes.c_uint8 * 256),
+                ("look", ctypes.c_uint16 * 256)]
+
+
+class JpegDesc(ctypes.Structure):
+    """orbit_jpeg_desc_t of include/orbit_hip.h (orbit_jpeg_parse refuses a descriptor of another size)"""
+    _fields_ = [("file_offset", ctypes.c_uint64), ("ecs_offset", ctypes.c_uint32), ("ecs_bytes", ctypes.c_uint32),
+                ("status", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32),
+                ("hs", ctypes.c_int32 * 3), ("vs", ctypes.c_int32 * 3), ("dc_slot", ctypes.c_int32 * 3),
+                ("ac_slot", ctypes.c_int32 * 3), ("restart_interval", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("qt", (ctypes.c_uint16 * 64) * 3), ("huff", JpegHuff * 4)]
+
+
+JPEG_STAGE_BYTES = 1024  # ORBIT_JPEG_STAGE_BYTES
 
 
 class OrbitHipError(RuntimeError):

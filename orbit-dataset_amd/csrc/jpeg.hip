@@ -1,0 +1,213 @@
+// JPEG decode on the device: baseline files in one arena -> 8-bit RGB frames [B][H][W][3], equal to Pillow's decode bit for bit.
+// Reference: data/datasets.py:422-431 opens every frame with PIL on the host (libjpeg's default path: Huffman decode, integer
+// "islow" inverse DCT, triangle chroma upsampling, table-driven YCbCr -> RGB). The arithmetic of those stages is restated in
+// csrc/jpeg_core.h as host + device code; this file is the three kernels around it and the launcher.
+//   jpeg_entropy_kernel  one wave per frame. Entropy decoding is sequential inside an image, a task is hundreds of images: the
+//                        64 lanes copy the descriptor (Huffman and quantisation tables) into LDS, zero the frame's
+//                        coefficients and keep two 1 KB tiles of the byte stream resident in LDS; lane 0 walks the symbols
+//                        and scatters the non-zero coefficients, handing control back at every tile end for the next load.
+//   jpeg_idct_kernel     one thread per 8 x 8 block: dequantise, both passes of the inverse DCT in registers, range limit.
+//   jpeg_color_kernel    one thread per output pixel: chroma upsampling with libjpeg's edge rules, colour conversion, store.
+// A frame whose stream is damaged ends with a non-zero status and whatever was decoded so far stays inside its own workspace
+// slice: every stream read is bounded by the segment length (itself checked against the arena), every coefficient write by
+// the frame's block count (checked against the slice).
+#include <algorithm>
+#include "common.h"
+#include "jpeg_core.h"
+
+namespace orbit {
+using namespace orbit_jpeg;
+
+constexpr int JP_STAGE = ORBIT_JPEG_STAGE_BYTES;
+constexpr size_t JP_MAX_THREADS = (size_t)1 << 30;  // per launch of the block / pixel kernels; more frames go in another chunk
+static_assert(JP_STAGE == 64 * 16, "a tile is one 16-byte load per lane");
+static_assert(sizeof(orbit_jpeg_desc_t) % 8 == 0, "descriptors are copied by words and follow each other in an array");
+
+__device__ const uint8_t jpeg_natural_dev[64] = ORBIT_JPEG_NATURAL_ORDER;
+
+// the byte stream as the walker sees it: tiles tile0 and tile0 + 1 from LDS (tile t lives in slot t & 1), anything else - a
+// block that runs past both tiles - from memory
+struct JpegLdsSrc {
+    const uint8_t* lds;
+    const uint8_t* mem;
+    uint32_t tile0;
+    __device__ __forceinline__ uint8_t at(uint32_t pos) const {
+        return (pos / JP_STAGE - tile0 < 2u) ? lds[pos & (2 * JP_STAGE - 1)] : mem[pos];
+    }
+};
+
+// lane's 16 bytes of tile t -> its slot; bytes behind the segment read as zero
+__device__ __forceinline__ void jpeg_load_tile(uint8_t* stage, const uint8_t* mem, uint32_t len, uint32_t t, int lane) {
+    const uint64_t o = (uint64_t)t * JP_STAGE + 16u * lane;
+    uint32_t v[4] = {0, 0, 0, 0};
+    if (o + 16 <= len) {
+        __builtin_memcpy(v, mem + o, 16);
+    } else {
+        for (int j = 0; j < 16; ++j)
+            if (o + j < len) v[j >> 2] |= (uint32_t)mem[o + j] << (8 * (j & 3));
+    }
+    uint32_t* dst = reinterpret_cast<uint32_t*>(stage + (t & 1u) * JP_STAGE + 16 * lane);
+    dst[0] = v[0], dst[1] = v[1], dst[2] = v[2], dst[3] = v[3];
+}
+
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ arena, size_t arena_bytes,
+                                                          const orbit_jpeg_desc_t* __restrict__ descs, int H, int W,
+                                                          size_t cap_blocks, int16_t* __restrict__ coef_ws,
+                                                          int32_t* __restrict__ status) {
+    __shared__ __align__(16) orbit_jpeg_desc_t d;
+    __shared__ __align__(16) uint8_t stage[2 * JP_STAGE];
+    __shared__ uint8_t natural[64];
+    __shared__ uint32_t ctl[2];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(descs + f);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&d);
+        for (int i = lane; i < (int)(sizeof(orbit_jpeg_desc_t) / 4); i += 64) dst[i] = src[i];
+        natural[lane] = jpeg_natural_dev[lane];
+    }
+    __syncthreads();
+    if (d.status != 0) {  // the host decodes this frame
+        if (lane == 0) status[f] = d.status > 0 ? -d.status : d.status;
+        return;
+    }
+    JpegGeom g;
+    const bool ok = jpeg_geom(d, g) && d.width == W && d.height == H && (size_t)g.total_blocks <= cap_blocks &&
+                    d.file_offset <= arena_bytes && (uint64_t)d.ecs_offset + d.ecs_bytes <= arena_bytes - d.file_offset;
+    if (!ok) {
+        if (lane == 0) status[f] = ORBIT_JPEG_ST_DESC;
+        return;
+    }
+    int16_t* coef = coef_ws + (size_t)f * cap_blocks * 64;
+    {
+        uint4* z = reinterpret_cast<uint4*>(coef);  // (the slice starts at a multiple of 128 bytes)
+        for (int i = lane; i < g.total_blocks * 8; i += 64) z[i] = make_uint4(0, 0, 0, 0);
+    }
+    const uint8_t* mem = arena + d.file_offset + d.ecs_offset;
+    const uint32_t len = d.ecs_bytes;
+    uint32_t tile0 = 0;
+    jpeg_load_tile(stage, mem, len, 0, lane);
+    jpeg_load_tile(stage, mem, len, 1, lane);
+    JpegWalk w;
+    jpeg_walk_init(w, d);
+    __syncthreads();
+    for (;;) {
+        if (lane == 0) {
+            const JpegLdsSrc src{stage, mem, tile0};
+            jpeg_walk(w, src, d, g, natural, coef, (tile0 + 1) * JP_STAGE - 1);
+            ctl[0] = (uint32_t)w.done;
+            ctl[1] = w.bits.pos;
+        }
+        __syncthreads();
+        const uint32_t done = ctl[0], next = ctl[1] / JP_STAGE;  // next > tile0 unless done
+        if (done) break;
+        if (next == tile0 + 1) {
+            jpeg_load_tile(stage, mem, len, next + 1, lane);
+        } else {
+            jpeg_load_tile(stage, mem, len, next, lane);
+            jpeg_load_tile(stage, mem, len, next + 1, lane);
+        }
+        tile0 = next;
+        __syncthreads();
+    }
+    if (lane == 0) status[f] = w.status;
+}
+
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const orbit_jpeg_desc_t* __restrict__ descs, size_t cap_blocks, size_t total,
+                                                        const int16_t* __restrict__ coef_ws, uint8_t* __restrict__ plane_ws,
+                                                        int32_t* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t f = i / cap_blocks;
+    const int j = (int)(i - f * cap_blocks);
+    if (status[f] != 0) return;
+    const orbit_jpeg_desc_t& d = descs[f];
+    JpegGeom g;
+    if (!jpeg_geom(d, g) || j >= g.total_blocks) return;  // (the entropy kernel has vouched for the descriptor)
+    const int c = (d.ncomp == 3 && j >= g.base[2]) ? 2 : ((d.ncomp == 3 && j >= g.base[1]) ? 1 : 0);
+    const int wbc = c == 0 ? g.wb[0] : (c == 1 ? g.wb[1] : g.wb[2]), basec = c == 0 ? g.base[0] : (c == 1 ? g.base[1] : g.base[2]);
+    const int k = j - basec, by = k / wbc, bx = k - by * wbc;
+    const size_t pitch = (size_t)wbc * 8;
+    uint8_t* out = plane_ws + f * cap_blocks * 64 + (size_t)basec * 64 + (size_t)by * 8 * pitch + (size_t)bx * 8;
+    const int flag = jpeg_idct_block(coef_ws + (f * cap_blocks + j) * 64, d.qt[c], out, pitch);
+    if (flag) atomicOr(status + f, flag);
+}
+
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const orbit_jpeg_desc_t* __restrict__ descs, size_t cap_blocks, int H, int W,
+                                                         size_t total, const uint8_t* __restrict__ plane_ws,
+                                                         const int32_t* __restrict__ status, uint8_t* __restrict__ out) {
+    const size_t HW = (size_t)H * W;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t f = i / HW, p = i - f * HW;
+        if (status[f] != 0) continue;
+        const orbit_jpeg_desc_t& d = descs[f];
+        JpegGeom g;
+        if (!jpeg_geom(d, g)) continue;
+        const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
+        uint8_t rgb[3];
+        jpeg_rgb_at(d, g, plane_ws + f * cap_blocks * 64, x, y, rgb);
+        uint8_t* o = out + i * 3;
+        o[0] = rgb[0], o[1] = rgb[1], o[2] = rgb[2];
+    }
+}
+
+static size_t jpeg_frame_workspace(int H, int W) { return jpeg_cap_blocks(H, W) * 64 * (sizeof(int16_t) + 1); }
+
+}  // namespace orbit
+
+using namespace orbit;
+
+extern "C" {
+
+int orbit_jpeg_parse(const uint8_t* data, size_t bytes, orbit_jpeg_desc_t* desc, size_t desc_bytes) {
+    ORBIT_REQUIRE(desc, "jpeg_parse: null descriptor");
+    ORBIT_REQUIRE(desc_bytes == sizeof(orbit_jpeg_desc_t), "jpeg_parse: the descriptor is %zu bytes, the caller's %zu",
+                  sizeof(orbit_jpeg_desc_t), desc_bytes);
+    char msg[160];
+    const int rc = orbit_jpeg::jpeg_parse(data, bytes, desc, msg, sizeof(msg));
+    if (rc < 0) return set_err(ORBIT_ERR_ARG, "%s", msg);
+    return rc;
+}
+
+size_t orbit_jpeg_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || H > ORBIT_RESIZE_MAX_SIZE || W > ORBIT_RESIZE_MAX_SIZE) return 0;
+    return (size_t)B * jpeg_frame_workspace(H, W);
+}
+
+int orbit_frames_from_jpeg(const uint8_t* arena, size_t arena_bytes, const orbit_jpeg_desc_t* descs, int B, int H, int W,
+                           uint8_t* out_u8_hwc, int32_t* status, void* workspace, size_t workspace_bytes, orbit_stream_t stream) {
+    ORBIT_REQUIRE(arena && descs && out_u8_hwc && status && workspace, "frames_from_jpeg: null pointer");
+    ORBIT_REQUIRE(B > 0 && H > 0 && W > 0, "frames_from_jpeg: bad sizes");
+    ORBIT_REQUIRE(H <= ORBIT_RESIZE_MAX_SIZE && W <= ORBIT_RESIZE_MAX_SIZE, "frames_from_jpeg: %dx%d exceeds the limit of %d pixels per side",
+                  H, W, ORBIT_RESIZE_MAX_SIZE);
+    ORBIT_REQUIRE(arena_bytes > 0, "frames_from_jpeg: empty arena");
+    ORBIT_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)descs & 7) == 0, "frames_from_jpeg: workspace must be 16-byte aligned, descs 8-byte");
+    const size_t per_frame = jpeg_frame_workspace(H, W), cap_blocks = jpeg_cap_blocks(H, W);
+    ORBIT_REQUIRE(workspace_bytes >= per_frame, "frames_from_jpeg: workspace of %zu bytes, one %dx%d frame needs %zu", workspace_bytes, H,
+                  W, per_frame);
+    const size_t by_threads = std::max<size_t>(1, JP_MAX_THREADS / std::max(cap_blocks, (size_t)H * W));
+    const int chunk = (int)std::min<size_t>(std::min(workspace_bytes / per_frame, by_threads), (size_t)B);
+    hipStream_t s = (hipStream_t)stream;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = std::min(chunk, B - b0);
+        int16_t* coef = (int16_t*)workspace;
+        uint8_t* planes = (uint8_t*)workspace + (size_t)nb * cap_blocks * 64 * sizeof(int16_t);
+        int rec = prof_start("jpeg_entropy", 0.0, (double)nb * cap_blocks * 64 * sizeof(int16_t), s);
+        jpeg_entropy_kernel<<<nb, 64, 0, s>>>(arena, arena_bytes, descs + b0, H, W, cap_blocks, coef, status + b0);
+        prof_stop(rec, s);
+        ORBIT_LAUNCH_CHECK();
+        const size_t blocks = (size_t)nb * cap_blocks;
+        rec = prof_start("jpeg_idct", 0.0, (double)blocks * 64 * 3, s);
+        jpeg_idct_kernel<<<(unsigned)((blocks + 255) / 256), 256, 0, s>>>(descs + b0, cap_blocks, blocks, coef, planes, status + b0);
+        prof_stop(rec, s);
+        ORBIT_LAUNCH_CHECK();
+        const size_t pixels = (size_t)nb * H * W;
+        rec = prof_start("jpeg_color", 0.0, (double)pixels * 6, s);
+        jpeg_color_kernel<<<(unsigned)std::min<size_t>((pixels + 255) / 256, 1u << 20), 256, 0, s>>>(
+            descs + b0, cap_blocks, H, W, pixels, planes, status + b0, out_u8_hwc + (size_t)b0 * H * W * 3);
+        prof_stop(rec, s);
+        ORBIT_LAUNCH_CHECK();
+    }
+    return ORBIT_OK;
+}
+
+}  // extern "C"

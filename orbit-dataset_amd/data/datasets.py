@@ -23,7 +23,8 @@ context videos, target videos, context clips per video, target clips per video; 
 shuffle), so seeding the `random` module (the default source, as the reference uses it) reproduces the reference's tasks.
 
 Beyond the reference: `frames=` selects what the clips hold - "float" (normalised fp32, the reference's layout), "uint8"
-(decoded 8-bit [.., H, W, 3] for TaskPrefetcher: a quarter of the bytes over PCIe, normalised on the GPU bit-identically) or
+(decoded 8-bit [.., H, W, 3] for TaskPrefetcher: a quarter of the bytes over PCIe, normalised on the GPU bit-identically),
+"jpeg" (the files, read and parsed but not decoded: pipeline.JpegFrames, which TaskPrefetcher decodes on the GPU) or
 "paths" (nothing decoded). Frame annotations and cluster labels are not on the recognition path and are not built:
 asking for them raises.
 """
@@ -86,8 +87,8 @@ class ORBITDataset(torch.utils.data.Dataset):
                  decode_pool=None):
         if annotations_to_load or any(filter_by_annotations) or with_cluster_labels:
             raise NotImplementedError("frame annotations / cluster labels are outside the recognition path (DESIGN.md §7)")
-        if frames not in ("float", "uint8", "paths"):
-            raise ValueError("frames must be 'float', 'uint8' or 'paths'")
+        if frames not in ("float", "uint8", "paths", "jpeg"):
+            raise ValueError("frames must be 'float', 'uint8', 'jpeg' or 'paths'")
         self.root, self.mode = root, os.path.basename(root)
         self.way_method, self.object_cap = way_method, object_cap
         self.shot_method = dict(zip(("context", "target"), shot_methods))
@@ -189,10 +190,15 @@ class ORBITDataset(torch.utils.data.Dataset):
         return x.sub_(mean).div_(std)
 
     def load_clips(self, paths):
-        """clip paths [n, T] -> clips in the configured representation (float: [n, T, 3, H, W] f32; uint8: [n, T, H, W, 3])"""
+        """clip paths [n, T] -> clips in the configured representation (float: [n, T, 3, H, W] f32; uint8: [n, T, H, W, 3];
+        jpeg: pipeline.JpegFrames of that shape - the files, for the device decoder)"""
         paths = np.asarray(paths, dtype=object).reshape(-1, self.clip_length)
         if self.frames == "paths":
             return None
+        if self.frames == "jpeg":
+            from .pipeline import read_jpeg_frames
+            return read_jpeg_frames(list(paths.reshape(-1)), self.decode_pool, (len(paths), self.clip_length),
+                                    empty_size=(self.frame_size, self.frame_size))
         u8 = self._decode(list(paths.reshape(-1)))
         if self.frames == "uint8":
             return u8.reshape(len(paths), self.clip_length, *u8.shape[1:])

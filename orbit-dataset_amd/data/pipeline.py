@@ -20,10 +20,17 @@ the recogniser moves each mini-batch to the device on the compute stream (`model
                       8-bit Image.resize, bit-identical - the reference's offline scripts/resize_videos.py pass): the upload
                       stays 8-bit at the stored size, the fp32 clips take the size the extractor runs at.
 
+  JpegFrames          with decode="device" the sources hand over the FILES instead of pixels: the threads read them and parse
+                      their headers (orbit_jpeg_parse, host only); the prefetcher uploads the compressed bytes in one copy and
+                      orbit_frames_from_jpeg (csrc/jpeg.hip) decodes them on the copy stream into the same 8-bit buffer the
+                      launches above read - Pillow's pixels, bit for bit. Files outside the device path's scope (progressive,
+                      CMYK ..) and files the device reports damaged are decoded by PIL as before; the count is reported.
+
 `write_synthetic_orbit_directory` builds a small JPEG tree in that layout (the ORBIT dataset itself is not available
 offline); it is test / benchmark scaffolding, not part of the path.
 """
 import ctypes
+import io
 import os
 import queue
 import threading
@@ -156,12 +163,183 @@ def decode_frames(paths, out=None, pool=None):
     return out
 
 
+# ---- compressed frames for the device decoder -------------------------------------------------------------------------------
+JPEG_WORKSPACE_CAP = 1 << 30  # bytes of coefficient + plane workspace per launch; more frames go through it in chunks (a chunk
+#                               runs one wave per frame: at 1080 x 1080, 10.6 MB per frame, this is 100 frames at a time)
+
+
+def _pil_rgb(data):
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        return np.array(im.convert("RGB"))  # (a copy: torch wants a writable array)
+
+
+class JpegFrames:
+    """The frames of a clips tensor [*lead, H, W, 3] as FILES: `files` (one bytes object per frame, row-major over `lead`),
+    `descs` (uint8 [n, sizeof(orbit_jpeg_desc_t)], the parsed headers), `codes` (orbit_jpeg_parse's result per frame: 0 =
+    the device decodes it) and `pixels` {frame: uint8 [H, W, 3]}: the frames PIL has already decoded because the device
+    path does not cover them. All frames are `size` = (H, W)."""
+
+    def __init__(self, files, descs, codes, pixels, lead, size):
+        self.files, self.descs, self.codes, self.pixels = files, descs, codes, pixels
+        self.lead, self.size = tuple(int(v) for v in lead), (int(size[0]), int(size[1]))
+        assert int(np.prod(self.lead)) == len(files) == len(descs) == len(codes)
+
+    @property
+    def shape(self):
+        return (*self.lead, *self.size, 3)
+
+    def __len__(self):
+        return self.lead[0]
+
+    def with_lead(self, *lead):
+        return JpegFrames(self.files, self.descs, self.codes, self.pixels, lead, self.size)
+
+    def flatten(self, end_dim=1):
+        """as Tensor.flatten(end_dim=k) over the leading dimensions"""
+        k = end_dim + 1
+        return self.with_lead(int(np.prod(self.lead[:k])), *self.lead[k:])
+
+    def unsqueeze(self, dim):
+        lead = list(self.lead)
+        lead.insert(dim, 1)
+        return self.with_lead(*lead)
+
+    @staticmethod
+    def cat(parts):
+        """as torch.cat along the first dimension"""
+        parts = list(parts)
+        sizes = {p.size for p in parts if len(p.files)}
+        if len(sizes) > 1:
+            raise ValueError("JpegFrames.cat: frames of different sizes %s" % sorted(sizes))
+        files, codes, pixels, base = [], [], {}, 0
+        for p in parts:
+            files += p.files
+            codes += list(p.codes)
+            pixels.update({base + i: px for i, px in p.pixels.items()})
+            base += len(p.files)
+        return JpegFrames(files, np.concatenate([p.descs for p in parts]), codes, pixels,
+                          (sum(p.lead[0] for p in parts), *parts[0].lead[1:]), sizes.pop() if sizes else parts[0].size)
+
+
+def read_jpeg_frames(paths, pool=None, lead=None, empty_size=(0, 0)):
+    """Files -> JpegFrames: every file is read and its headers parsed (orbit_jpeg_parse releases the GIL: `pool` threads work
+    side by side); PIL decodes the files the device path does not cover, and only those."""
+    from .. import _lib
+    lib = _lib.load()
+    paths = list(paths)
+    n, size = len(paths), ctypes.sizeof(_lib.JpegDesc)
+    descs = np.zeros((n, size), dtype=np.uint8)
+    files, codes, pixels = [None] * n, [0] * n, {}
+
+    def one(i):
+        with open(paths[i], "rb") as f:
+            files[i] = f.read()
+        codes[i] = lib.orbit_jpeg_parse(files[i], len(files[i]), descs[i].ctypes.data, size)
+        if codes[i] != 0:
+            pixels[i] = _pil_rgb(files[i])  # (what PIL raises for a broken file surfaces here, as in decode_frames)
+
+    if pool is None:
+        for i in range(n):
+            one(i)
+    else:
+        list(pool.map(one, range(n)))
+    hw = empty_size
+    if n:
+        d = descs.view(np.int32)
+        sizes = {(int(d[i, 6]), int(d[i, 5])) if codes[i] == 0 else pixels[i].shape[:2] for i in range(n)}  # (height, width)
+        if len(sizes) > 1:
+            raise ValueError("read_jpeg_frames: frames of different sizes in one batch: %s" % sorted(sizes))
+        hw = sizes.pop()
+    return JpegFrames(files, descs, codes, pixels, (n,) if lead is None else lead, hw)
+
+
+def _jpeg_launch(jf, u8, pinned, dev, device):
+    """Upload jf's files and descriptors in one copy and decode them into u8 [n, H, W, 3] on the current stream; the frames PIL
+    already decoded are copied into their rows. `pinned` / `dev`: dicts that keep the buffers between calls. Returns the
+    pinned status vector (int32 [n]) and the event after which it is valid."""
+    from .. import _lib
+    lib = _lib.load()
+    n, (H, W) = len(jf.files), jf.size
+    dsize = ctypes.sizeof(_lib.JpegDesc)
+    offsets, at = np.empty(n, dtype=np.uint64), 0
+    for i, f in enumerate(jf.files):
+        offsets[i] = at
+        at += (len(f) + 15) // 16 * 16
+    head, total = n * dsize, n * dsize + max(at, 16)
+
+    def grow(store, key, count, make):
+        t = store.get(key)
+        if t is None or t.numel() < count:
+            t = store[key] = make(count)
+        return t[:count]
+
+    arena = grow(pinned, "arena", total, lambda c: torch.empty(c, dtype=torch.uint8).pin_memory())
+    host = arena.numpy()
+    rows = host[:head].reshape(n, dsize)
+    rows[:] = jf.descs
+    rows.view(np.uint64)[:, 0] = offsets  # file_offset, the descriptor's first field
+    for i, f in enumerate(jf.files):
+        o = head + int(offsets[i])
+        host[o:o + len(f)] = np.frombuffer(f, dtype=np.uint8)
+        if jf.codes[i] < 0:
+            rows.view(np.int32)[i, 4] = 127  # not a JPEG at all: skipped like any other host-decoded frame
+    d_arena = grow(dev, "arena", total, lambda c: torch.empty(c, dtype=torch.uint8, device=device))
+    d_arena.copy_(arena, non_blocking=True)
+    ws_bytes = min(lib.orbit_jpeg_workspace_bytes(n, H, W), max(JPEG_WORKSPACE_CAP, lib.orbit_jpeg_workspace_bytes(1, H, W)))
+    ws = grow(dev, "workspace", ws_bytes, lambda c: torch.empty(c, dtype=torch.uint8, device=device))
+    status = grow(dev, "status", n, lambda c: torch.empty(c, dtype=torch.int32, device=device))
+    _lib.check(lib.orbit_frames_from_jpeg(ctypes.c_void_p(d_arena.data_ptr() + head), total - head, _lib.dptr(d_arena), n, H, W,
+                                          _lib.dptr(u8, torch.uint8), _lib.dptr(status), _lib.dptr(ws), ws_bytes,
+                                          _lib.stream_handle()), "orbit_frames_from_jpeg")
+    if jf.pixels:
+        frames = u8.view(n, H, W, 3)
+        px = grow(pinned, "pixels", len(jf.pixels) * H * W * 3, lambda c: torch.empty(c, dtype=torch.uint8).pin_memory())
+        px = px.view(len(jf.pixels), H, W, 3)
+        for k, (i, a) in enumerate(sorted(jf.pixels.items())):
+            px[k].copy_(torch.from_numpy(a))
+            frames[i].copy_(px[k], non_blocking=True)
+    status_host = grow(pinned, "status", n, lambda c: torch.empty(c, dtype=torch.int32).pin_memory())
+    status_host.copy_(status, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    return status_host, done
+
+
+def decode_frames_device(paths, device, pool=None, stats=None):
+    """JPEG files -> uint8 [n, H, W, 3] on `device`, equal to decode_frames(paths): decoded by orbit_frames_from_jpeg, by PIL
+    where the device path does not cover a file or reports it damaged. `stats`, a dict, receives the counts."""
+    from .. import _lib
+    _lib.require_gpu()
+    device = torch.device(device)
+    jf = read_jpeg_frames(paths, pool)
+    n, (H, W) = len(jf.files), jf.size
+    with torch.cuda.device(device):
+        u8 = torch.empty((n, H, W, 3), dtype=torch.uint8, device=device)
+        bad = []
+        if n:
+            status, done = _jpeg_launch(jf, u8, {}, {}, device)
+            done.synchronize()
+            bad = [i for i in range(n) if status[i] > 0]
+            for i in bad:
+                u8[i].copy_(torch.from_numpy(_pil_rgb(jf.files[i])))
+            torch.cuda.current_stream().synchronize()  # the pinned buffers of this call are dropped on return
+    if stats is not None:
+        stats.update({"frames": n, "fallback_frames": len(jf.pixels) + len(bad), "out_of_scope": len(jf.pixels), "damaged": len(bad),
+                      "status": [int(v) for v in status] if n else []})
+    return u8
+
+
 class DirectoryTaskSource:
     """Iterator of host tasks decoded from an ORBITDirectory: {context_clips u8 [N,T,H,W,3], context_labels, target_clips u8
-    [M,1,H,W,3], target_labels, target_videos}. `workers` decode threads (the reference: DataLoader workers, queues.py:34)."""
+    [M,1,H,W,3], target_labels, target_videos}. `workers` decode threads (the reference: DataLoader workers, queues.py:34).
+    decode="device": the clips are JpegFrames (the files, read and parsed by the threads) for the prefetcher to decode."""
 
     def __init__(self, directory, clip_length=1, workers=8, context_frames_per_video=None, target_frames_per_video=None,
-                 users=None):
+                 users=None, decode="host"):
+        if decode not in ("host", "device"):
+            raise ValueError("decode must be 'host' or 'device', got %r" % (decode,))
+        self.decode = decode
         self.dir, self.T = directory, int(clip_length)
         self.users = list(users if users is not None else directory.users)
         self.cpv, self.tpv = context_frames_per_video, target_frames_per_video
@@ -173,6 +351,12 @@ class DirectoryTaskSource:
     def __iter__(self):
         for user in self.users:
             t = self.dir.user_task(user, self.T, self.cpv, self.tpv)
+            if self.decode == "device":
+                yield {"context_clips": read_jpeg_frames(t["context_paths"].reshape(-1), self.pool, (len(t["context_paths"]), self.T)),
+                       "context_labels": t["context_labels"],
+                       "target_clips": read_jpeg_frames(t["target_paths"].reshape(-1), self.pool, (len(t["target_paths"]), 1)),
+                       "target_labels": t["target_labels"], "target_videos": t["target_videos"], "user": user}
+                continue
             ctx = decode_frames(t["context_paths"].reshape(-1), pool=self.pool)
             tgt = decode_frames(t["target_paths"].reshape(-1), pool=self.pool)
             yield {"context_clips": torch.from_numpy(ctx).reshape(len(t["context_paths"]), self.T, *ctx.shape[1:]),
@@ -182,14 +366,14 @@ class DirectoryTaskSource:
 
 
 class DatasetTaskSource:
-    """Host tasks from a data/datasets.py dataset built with frames="uint8" (the reference-pinned sampler: way, video and clip
+    """Host tasks from a data/datasets.py dataset built with frames="uint8" - or frames="jpeg": JpegFrames for the device decoder - (the reference-pinned sampler: way, video and clip
     sampling of reference data/datasets.py:289-336,433-469,540-598), in the layout TaskPrefetcher uploads:
     context_clips u8 [N,T,H,W,3]; a test-mode target set (a list of videos) is concatenated into target_clips u8 [M,1,H,W,3]
     with `target_videos` = [(lo, hi)] row ranges and one label per frame; a train-mode target set passes through as clips."""
 
     def __init__(self, dataset, indices=None):
-        if dataset.frames != "uint8":
-            raise ValueError("DatasetTaskSource needs a dataset built with frames='uint8'")
+        if dataset.frames not in ("uint8", "jpeg"):
+            raise ValueError("DatasetTaskSource needs a dataset built with frames='uint8' or frames='jpeg'")
         self.dataset = dataset
         self.indices = list(range(len(dataset)) if indices is None else indices)
 
@@ -206,7 +390,8 @@ class DatasetTaskSource:
                 for frames in t["target_clips"]:
                     ranges.append((lo, lo + len(frames)))
                     lo += len(frames)
-                out["target_clips"] = torch.cat(t["target_clips"]).unsqueeze(1)
+                cat = JpegFrames.cat if self.dataset.frames == "jpeg" else torch.cat
+                out["target_clips"] = cat(t["target_clips"]).unsqueeze(1)
                 out["target_labels"] = torch.cat([lab.reshape(1).expand(hi - lo) for lab, (lo, hi) in
                                                   zip(t["target_labels"], ranges)]) if ranges else torch.empty(0, dtype=torch.int64)
                 out["target_videos"], out["target_paths"] = ranges, t["target_paths"]
@@ -237,7 +422,13 @@ class TaskPrefetcher:
 
     frame_size (an int or (H, W)): uint8 clips stored at another size leave at this one, resized on the device as PIL's
     Image.resize((W, H), resample) would ("lanczos", "bicubic" or "bilinear"); clips already at it, and float32 clips,
-    take the path without a resize. Context and target clips may be stored at different sizes."""
+    take the path without a resize. Context and target clips may be stored at different sizes.
+
+    Clips may also be JpegFrames (a source with decode="device"): their files are uploaded and decoded on the copy stream
+    into the 8-bit buffer, then normalised / resized like uploaded pixels. The staging thread alone waits for the decode's
+    status; a frame the device reports damaged is decoded by PIL, uploaded and normalised again - or raises what PIL
+    raises. Every yielded task then carries "decode_fallbacks", the number of its frames PIL decoded; `fallback_frames`
+    and `device_frames` count over all tasks."""
 
     def __init__(self, source, device, depth=3, frame_norm_method="imagenet", consumer_streams=(), frame_size=None,
                  resample="lanczos"):
@@ -248,6 +439,7 @@ class TaskPrefetcher:
         self.mean, self.std = NORMALIZE_STATS[frame_norm_method]
         self.frame_size, self.filter = frame_size, resample_filter(resample)
         self.stored_sizes = set()  # (H, W) of the 8-bit clips staged so far
+        self.fallback_frames = self.device_frames = 0  # JpegFrames: frames PIL decoded / frames the device decoded
         self.depth = max(2, int(depth))
         self.slots = [_Slot() for _ in range(self.depth)]
         self.copy_stream = torch.cuda.Stream(device=self.device)
@@ -271,6 +463,20 @@ class TaskPrefetcher:
             t = store[key] = make(n)
         return t[:n].view(*shape)
 
+    def _normalise(self, u8, f32, hwc, B, H, W, Ho, Wo, first=0, count=None):
+        """frames [first, first + count) of u8 [B, H, W, 3] (or [B, 3, H, W]) -> f32 [B, 3, Ho, Wo] on the current stream"""
+        lib, f3 = self._lib.load(), ctypes.c_float * 3
+        mean, std = f3(*self.mean), f3(*self.std)
+        count = B - first if count is None else count
+        src = ctypes.c_void_p(self._lib.dptr(u8, torch.uint8).value + first * 3 * H * W)
+        dst = ctypes.c_void_p(self._lib.dptr(f32, torch.float32).value + 4 * first * 3 * Ho * Wo)
+        if (Ho, Wo) != (H, W):
+            self._lib.check(lib.orbit_frames_resize_from_uint8(src, 1 if hwc else 0, count, H, W, Ho, Wo, self.filter, mean, std, dst,
+                                                               self._lib.stream_handle()), "orbit_frames_resize_from_uint8")
+        else:
+            self._lib.check(lib.orbit_frames_from_uint8(src, 1 if hwc else 0, count, H, W, mean, std, dst,
+                                                        self._lib.stream_handle()), "orbit_frames_from_uint8")
+
     def _stage(self):
         try:
             torch.cuda.set_device(self.device)
@@ -284,8 +490,26 @@ class TaskPrefetcher:
                 for ev in slot.released or ():
                     self.copy_stream.wait_event(ev)  # the consumer's kernels that read the slot's last task
                 out = dict(task)
+                pending = []  # device decodes whose status is still to be read
                 with torch.cuda.stream(self.copy_stream):
                     for key, val in task.items():
+                        if isinstance(val, JpegFrames) and key.endswith("clips"):
+                            (H, W), B = val.size, len(val.files)
+                            Ho, Wo = output_size(self.frame_size, H, W)
+                            u8 = self._buffer(slot.dev_u8, key, val.shape,
+                                              lambda n: torch.empty(n, dtype=torch.uint8, device=self.device))
+                            f32 = self._buffer(slot.dev_f32, key, (*val.lead, 3, Ho, Wo),
+                                               lambda n: torch.empty(n, dtype=torch.float32, device=self.device))
+                            if B > 0:
+                                self.stored_sizes.add((H, W))
+                                for ev in slot.released or ():
+                                    ev.synchronize()  # (the slot's pinned arena: see the 8-bit path below)
+                                status, done = _jpeg_launch(val, u8, slot.pinned.setdefault((key, "jpeg"), {}),
+                                                            slot.dev_u8.setdefault((key, "jpeg"), {}), self.device)
+                                self._normalise(u8, f32, True, B, H, W, Ho, Wo)
+                                pending.append((val, u8, f32, status, done, (B, H, W, Ho, Wo)))
+                            out[key] = f32
+                            continue
                         if not (isinstance(val, torch.Tensor) and key.endswith("clips")):
                             if isinstance(val, torch.Tensor) and key.endswith("labels"):
                                 # labels live in the slot like the clips: the slot's `released` event orders their reuse
@@ -342,6 +566,24 @@ class TaskPrefetcher:
                                                                         mean, std, self._lib.dptr(f32), self._lib.stream_handle()),
                                             "orbit_frames_from_uint8")
                         out[key] = f32
+                    # The decodes' statuses, read by this thread once everything of the task is queued (the compute stream never
+                    # waits for this): a frame the device gave up on is decoded by PIL and takes the same two steps again.
+                    fallbacks = 0
+                    for val, u8, f32, status, done, (B, H, W, Ho, Wo) in pending:
+                        done.synchronize()
+                        bad = [i for i in np.nonzero(status.numpy() > 0)[0]]
+                        frames = u8.view(B, H, W, 3)
+                        for i in bad:
+                            a = _pil_rgb(val.files[i])  # raises for a file PIL cannot decode either: surfaces from __next__
+                            if a.shape != (H, W, 3):
+                                raise ValueError("TaskPrefetcher: a frame of %s among frames of %s" % (a.shape[:2], (H, W)))
+                            frames[i].copy_(torch.from_numpy(a))
+                            self._normalise(u8, f32, True, B, H, W, Ho, Wo, first=int(i), count=1)
+                        fallbacks += len(val.pixels) + len(bad)
+                        self.device_frames += B - len(val.pixels) - len(bad)
+                    if pending:
+                        out["decode_fallbacks"] = fallbacks
+                        self.fallback_frames += fallbacks
                     slot.ready = torch.cuda.Event()
                     slot.ready.record(self.copy_stream)
                 slot.task = out

@@ -118,6 +118,11 @@ def build_parser():
                         "videos); frames are decoded with PIL by --num_workers threads, uploaded as 8-bit on a copy stream and "
                         "normalised on the GPU (data/pipeline.TaskPrefetcher) while the previous task runs. Frames stored at "
                         "another size than --frame_size are resized to it on the GPU in the same launch (--resample)")
+    p.add_argument("--decode", default="host", choices=["host", "device"],
+                   help="with --data_root: where the JPEG frames are decoded. host (default): PIL on --num_workers threads. "
+                        "device: the threads only read the files and parse their headers, the compressed bytes are uploaded and "
+                        "decoded on the GPU (baseline JPEG; Pillow's pixels bit for bit). Files the GPU path does not cover "
+                        "(progressive, CMYK ..) or reports damaged are decoded by PIL; the results record how many")
     p.add_argument("--resample", default="lanczos", choices=["lanczos", "bicubic", "bilinear"],
                    help="with --data_root: the filter of that resize, PIL's 8-bit Image.resize bit for bit (default: the "
                         "reference's offline pass, scripts/resize_videos.py:46 Image.LANCZOS)")
@@ -537,7 +542,8 @@ class Learner:
             a.data_root, a.test_way_method, a.test_object_cap, (a.test_context_shot_method, a.test_target_shot_method),
             (a.context_shot, a.target_shot), (a.context_video_type, a.target_video_type), a.subsample_factor,
             (a.test_context_clip_method, a.test_target_clip_method), a.clip_length, a.frame_size, a.frame_norm_method, [],
-            ([], []), True, False, False, None, frames="uint8", rng=random.Random(a.seed + self.rank), decode_pool=pool)
+            ([], []), True, False, False, None, frames="jpeg" if a.decode == "device" else "uint8",
+            rng=random.Random(a.seed + self.rank), decode_pool=pool)
         # TaskSampler order (data/samplers.py:24-30, no shuffle): user 0 x num_tasks, user 1 x num_tasks, ...; dealt to ranks
         # - EVERY user x num_test_tasks_per_user, as the reference's loop visits them (single-step-learner.py:313-314). An
         # optional total cap (--max_test_tasks; default none) is applied BEFORE the tasks are dealt, so the evaluated set does
@@ -597,11 +603,15 @@ class Learner:
                  "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world,
                  "target_frames": frames, "wall_s": wall, "data_root": a.data_root, "orbit_metrics": metrics.report(),
                  "stored_frame_size": [list(hw) for hw in stored], "frame_size": [a.frame_size, a.frame_size],
-                 "resample": a.resample if any(hw != (a.frame_size, a.frame_size) for hw in stored) else None}
+                 "resample": a.resample if any(hw != (a.frame_size, a.frame_size) for hw in stored) else None,
+                 "decode": a.decode, "decode_fallback_frames": prefetch.fallback_frames if a.decode == "device" else None}
         if self.rank == 0:
             print("test (%s): frames stored at %s, extractor ran at %dx%d%s"
                   % (a.data_root, ", ".join("%dx%d" % hw for hw in stored) or "-", a.frame_size, a.frame_size,
                      " (resized on the GPU, %s)" % a.resample if stats["resample"] else ""))
+            if a.decode == "device":
+                print("test (%s): JPEG decode on the GPU, %d frames; %d decoded by PIL instead (out of scope or damaged)"
+                      % (a.data_root, prefetch.device_frames, prefetch.fallback_frames))
             print("test (%s): frame_acc %.2f (%.2f) %% | time to personalise %.2f (%.2f) ms | inference %.4f (%.4f) ms/frame "
                   "| %d tasks, %d target frames in %.1f s incl. JPEG decode (%d threads)"
                   % (a.data_root, 100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1], *_shown(stats["personalise_ms"]),

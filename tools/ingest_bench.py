@@ -3,7 +3,10 @@ resizes a user of the ORBIT tree runs - the raw 1080 x 1080 frames to 224, and a
 frames per launch: us per launch and GB/s over the profiler's bytes (8-bit frames in, fp32 frames out), the byte floor at the
 6.3 TB/s DESIGN.md prices HBM at, and beside them the time PIL's Image.resize takes for the same frames on 16 threads - the
 offline pass of the reference (scripts/resize_videos.py:46) this replaces. The first frame of every case is compared with PIL.
-Usage (GPU box): python tools/ingest_bench.py [--frames 200] [--reps 10] [--threads 16]"""
+--decode measures the JPEG decoder instead (orbit_frames_from_jpeg, csrc/jpeg.hip) on 224 x 224 and 1080 x 1080 frames written
+by write_synthetic_orbit_directory: us per launch of each of its three kernels, the bytes uploaded compressed against decoded,
+and PIL's decode of the same files on 16 threads; every frame is compared with PIL.
+Usage (GPU box): python tools/ingest_bench.py [--decode] [--frames 200] [--reps 10] [--threads 16]"""
 import argparse
 import ctypes
 import json
@@ -43,8 +46,69 @@ def measure(lib, run, reps):
     return 1e3 * ms.value / reps, nbytes.value / reps, name.value.decode()
 
 
+def measure_decode(a, lib, dev, pool):
+    """orbit_frames_from_jpeg against PIL's decode, per frame size"""
+    import glob
+    import tempfile
+    from orbit_dataset_amd.data import pipeline
+    rows = []
+    for size in a.sizes:
+        with tempfile.TemporaryDirectory() as root:
+            pipeline.write_synthetic_orbit_directory(root, users=1, objects_per_user=1, clean_videos=1, clutter_videos=0,
+                                                     frames_per_video=a.frames, frame_size=size)
+            paths = sorted(glob.glob(os.path.join(root, "*", "*", "*", "*", "*.jpg")))
+            t0 = time.perf_counter()
+            jf = pipeline.read_jpeg_frames(paths, pool)
+            read_ms = 1e3 * (time.perf_counter() - t0)
+            pil_s = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                want = pipeline.decode_frames(paths, pool=pool)
+                pil_s.append(time.perf_counter() - t0)
+        assert not jf.pixels, "synthetic frames must all be in the device path's scope"
+        u8 = torch.empty(jf.shape, dtype=torch.uint8, device=dev)
+        pinned, held = {}, {}
+
+        def run():
+            status, done = pipeline._jpeg_launch(jf, u8, pinned, held, dev)
+            done.synchronize()
+            return status
+
+        for _ in range(2):
+            status = run()
+        assert not status.numpy().any(), "a frame was not decoded on the device"
+        exact = bool(np.array_equal(u8.cpu().numpy(), want))
+        lib.orbit_prof_enable(1)
+        for _ in range(a.reps):
+            run()
+        torch.cuda.synchronize()
+        lib.orbit_prof_enable(0)
+        ms, n = ctypes.c_double(), ctypes.c_long()
+        lib.orbit_prof_collect(ctypes.byref(ms), None, ctypes.byref(n))
+        kernels = {}
+        for i in range(lib.orbit_prof_num_variants()):
+            name, launches, kms = ctypes.create_string_buffer(48), ctypes.c_long(), ctypes.c_double()
+            lib.orbit_prof_variant(i, name, ctypes.byref(launches), ctypes.byref(kms), None, None)
+            kernels[name.value.decode()] = {"us_per_call": 1e3 * kms.value / a.reps, "launches_per_call": launches.value / a.reps}
+        compressed, decoded = sum(len(f) for f in jf.files), int(np.prod(jf.shape))
+        row = {"size": size, "frames": a.frames, "kernels": kernels, "us_per_call": 1e3 * ms.value / a.reps,
+               "compressed_bytes": compressed, "decoded_bytes": decoded, "pil_ms": 1e3 * min(pil_s), "pil_threads": a.threads,
+               "read_and_parse_ms": read_ms, "all_frames_equal_pil": exact}
+        rows.append(row)
+        print("%4d x %-4d %d frames: %s = %9.1f us per call | upload %.2f MB compressed, %.2f MB decoded (%.1fx) | PIL x%d threads "
+              "%8.1f ms (%5.1fx) | read + parse %6.1f ms | frames %s PIL"
+              % (size, size, a.frames, " + ".join("%s %.1f" % (k, v["us_per_call"]) for k, v in sorted(kernels.items())),
+                 row["us_per_call"], compressed / 1e6, decoded / 1e6, decoded / compressed, a.threads, row["pil_ms"],
+                 1e3 * row["pil_ms"] / row["us_per_call"], read_ms, "==" if exact else "!="), flush=True)
+        assert exact, "a decoded frame differs from PIL"
+        del u8
+    return rows
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
+    p.add_argument("--decode", action="store_true", help="measure the JPEG decoder instead of the resize")
+    p.add_argument("--sizes", type=int, nargs="+", default=[224, 1080], help="with --decode: the frame sizes")
     p.add_argument("--frames", type=int, default=200)
     p.add_argument("--reps", type=int, default=10)
     p.add_argument("--threads", type=int, default=16)
@@ -55,6 +119,13 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     mean, std = (torch.tensor(v)[:, None, None] for v in NORMALIZE_STATS["imagenet"])
     pool = ThreadPoolExecutor(max_workers=a.threads)
+    if a.decode:
+        print("%d frames per call, device %s, PIL %s on %d threads" % (a.frames, torch.cuda.get_device_name(0), Image.__version__, a.threads))
+        rows = measure_decode(a, lib, dev, pool)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(rows, f, indent=1)
+        return rows
     rows = []
     print("%d frames per launch, device %s, PIL %s on %d threads" % (a.frames, torch.cuda.get_device_name(0), Image.__version__, a.threads))
     for size_in, size_out in ((1080, 224), (224, 84)):
