@@ -261,3 +261,145 @@ def test_many_pending_label_sets_keep_their_own_count(device):
     ids, W, b = blocks.proto_configure(feats, lab, "euclidean")
     assert (head.weight.cpu() - W).abs().max().item() < 1e-5
     del later
+
+
+# ---- orbit_dense_rows on its own, and the Mahalanobis head at widths that are no multiple of 32 --------------------------
+_ACTS = {"none": 0, "relu": 1, "elu": 3}  # ORBIT_ACT_*
+
+
+def _dense_ref(x, W, b, res, act, dtype):
+    """act(x W^T + b) + res in plain torch at `dtype`."""
+    y = torch.nn.functional.linear(x.to(dtype), W.to(dtype), None if b is None else b.to(dtype))
+    y = {"none": y, "relu": torch.relu(y), "elu": torch.nn.functional.elu(y)}[act]
+    return y if res is None else y + res.to(dtype)
+
+
+def _dense_emulation(x, W, b, res, act):
+    """dense_rows_kernel of csrc/heads_extra.hip restated in float32 in its own summation order: lane l of the wave of an
+    output unit runs the fused multiply-add chain over k = l, l + 64, ..., then the 64 partial sums meet in the xor butterfly
+    of wave_sum_xor (offsets 32, 16, ..., 1); bias, activation and residual follow in float32. A float32 fma is the float64
+    product and sum rounded once more (the product of two float32 is exact in float64)."""
+    xn, Wn = x.numpy().astype(np.float64), W.numpy().astype(np.float64)
+    R, n_in = xn.shape
+    acc = np.zeros((R, Wn.shape[0], 64), np.float32)
+    for k0 in range(0, n_in, 64):
+        n = min(64, n_in - k0)
+        acc[:, :, :n] = (Wn[None, :, k0:k0 + n] * xn[:, None, k0:k0 + n] + acc[:, :, :n].astype(np.float64)).astype(np.float32)
+    lanes = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        acc = (acc + acc[:, :, lanes ^ off]).astype(np.float32)
+    v = acc[:, :, 0]
+    if b is not None:
+        v = (v + b.numpy()[None, :]).astype(np.float32)
+    if act == "elu":
+        v = np.where(v > 0, v, np.expm1(v)).astype(np.float32)
+    elif act == "relu":
+        v = np.maximum(v, np.float32(0))
+    if res is not None:
+        v = (v + res.numpy()).astype(np.float32)
+    return torch.from_numpy(v)
+
+
+@pytest.mark.parametrize("act", list(_ACTS))
+def test_dense_rows_matches_fp64(device, act):
+    """The few-rows dense layer of the Versa hyper-networks by itself, at row counts up to its limit of 16, input widths below,
+    at and off the wave's 64 lanes and output counts that leave the last block of four waves partly empty, with and without
+    bias and residual, against float64 under the gate of tests/test_gpu_vit_ops.py: max |got - ref64| <= max(4 e32, 8 * 2**-24
+    max |ref64|), e32 the error of the plain float32 torch run on the CPU. x W^T ~ N(0, 1), so ELU and ReLU see both signs.
+    The output is followed by a guard band. A case over its bound is reported with the same figures for _dense_emulation.
+    On the MI355X (torch 2.10 CPU reference, 16 threads) the largest err / e32 is 1.11 where 4 e32 sets the bound; where the
+    floor does, e32 is the rounding error of few numbers and the ratio says little: 2.67 at most, but for four cases of a single
+    number (R = out = 1, in = 64) at 5.20, 12.48, 25.44 and 84.56 with err at most 1.5e-7. Every case meets the gate as it
+    stands, so no factor is widened."""
+    from orbit_dataset_amd import _lib
+    from test_gpu_vit_ops import gate
+    _lib.require_gpu()
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(17)
+    worst, guard, failures = [0.0, 0.0], 64, []
+    for R in (1, 7, 16):
+        for n_in in (5, 64, 193):
+            for n_out in (1, 6, 129):
+                x, W = torch.randn(R, n_in, generator=g), torch.randn(n_out, n_in, generator=g) / n_in ** 0.5
+                bias, resid = 0.5 * torch.randn(n_out, generator=g), torch.randn(R, n_out, generator=g)
+                xd, Wd = x.to(device), W.to(device)
+                for b, res in ((bias, resid), (bias, None), (None, resid), (None, None)):
+                    ref64 = _dense_ref(x, W, b, res, act, torch.float64)
+                    pre = _dense_ref(x, W, b, None, "none", torch.float64)
+                    assert R * n_out < 8 or pre.min().item() < 0 < pre.max().item()  # both branches of the activation
+                    e32 = (_dense_ref(x, W, b, res, act, torch.float32).double() - ref64).abs().max().item()
+                    y = torch.full((R * n_out + guard,), 7777.0, device=device)
+                    bd, rd = (None if b is None else b.to(device)), (None if res is None else res.to(device))
+                    _lib.check(lib.orbit_dense_rows(_lib.dptr(xd), R, n_in, _lib.dptr(Wd), _lib.dptr(bd), n_out, _ACTS[act],
+                                                    _lib.dptr(rd), _lib.dptr(y), _lib.stream_handle()), "orbit_dense_rows")
+                    torch.cuda.synchronize()
+                    y = y.cpu()
+                    assert torch.all(y[R * n_out:] == 7777.0) and not (y[:R * n_out] == 7777.0).any()
+                    got = y[:R * n_out].view(R, n_out)
+                    what = "dense_rows %s R %d in %d out %d%s%s" % (act, R, n_in, n_out, " bias" if b is not None else "",
+                                                                    " residual" if res is not None else "")
+                    floor = 8 * 2.0 ** -24 * ref64.abs().max().item()
+                    try:
+                        ratio = gate(got, ref64, e32, what)
+                        worst[4 * e32 < floor] = max(worst[4 * e32 < floor], ratio)
+                    except AssertionError as e:
+                        emu = _dense_emulation(x, W, b, res, act)
+                        failures.append("%s (the emulation of the kernel's summation order: err %.4g, |kernel - emulation| %.4g)"
+                                        % (str(e).split("\n")[0], (emu.double() - ref64).abs().max().item(),
+                                           (got - emu).abs().max().item()))
+    print("[head] dense_rows %s largest err / e32: %.2f where 4 e32 is the bound, %.2f where the floor is" % (act, *worst))
+    assert not failures, "\n".join(failures)
+
+
+def test_dense_rows_refuses_17_rows(device):
+    from orbit_dataset_amd import _lib
+    _lib.require_gpu()
+    lib = _lib.load()
+    x, W, y = torch.zeros(17, 8, device=device), torch.zeros(4, 8, device=device), torch.full((17 * 4,), 7777.0, device=device)
+    assert lib.orbit_dense_rows(_lib.dptr(x), 17, 8, _lib.dptr(W), None, 4, 0, None, _lib.dptr(y), _lib.stream_handle()) != 0
+    assert "dense_rows: bad sizes (rows must be 1..16)" in _lib.last_error()
+    torch.cuda.synchronize()
+    assert torch.all(y == 7777.0)
+
+
+@pytest.mark.parametrize("D", [36, 100])
+def test_mahalanobis_at_widths_off_the_32_tile(device, D):
+    """configure -> predict -> predict_backward at feature widths that are multiples of 4 but not of 32: the covariance kernel's
+    column guards and the ragged last block of the blocked Gauss-Jordan inverse run together. 37 examples in five classes with
+    non-contiguous label values, one class with a single example (the reference's scalar 'covariance'). Tolerances: those of
+    test_G10_mahalanobis_head, test_versa_mahalanobis_at_extractor_width and test_mahalanobis_predict_backward."""
+    from oracle import blocks
+    from orbit_dataset_amd.model.classifier_heads import MahalanobisClassifier
+    g = torch.Generator().manual_seed(D)
+    values = torch.tensor([2, 5, 11, 12, 40])
+    cls = torch.tensor([0] * 10 + [1] * 9 + [2] * 1 + [3] * 9 + [4] * 8)[torch.randperm(37, generator=g)]
+    assert cls.numel() == 37 and (cls == 2).sum().item() == 1
+    lab = values[cls]
+    centres = torch.randn(5, D, generator=g)
+    feats = centres[cls] + 0.7 * torch.randn(37, D, generator=g)
+    M = 23
+    q = centres[torch.randint(0, 5, (M,), generator=g)] + 0.7 * torch.randn(M, D, generator=g)
+    dl = torch.randn(M, 5, generator=g)
+    head = MahalanobisClassifier(2.0)
+    head.configure(feats.to(device), lab.to(device))
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)  # (the float64 inverses: see test_spd_inverse)
+    try:
+        ids, means, precisions, task_mean, task_precision = blocks.mahalanobis_configure(feats.double(), lab)
+    finally:
+        torch.set_num_threads(threads)
+    assert head.class_ids.cpu().tolist() == ids.tolist() == values.tolist()
+    assert (head.means.cpu().double() - means).abs().max().item() < 1e-5
+    assert (head.task_mean.cpu().double() - task_mean).abs().max().item() < 1e-5
+    assert (head.precisions.cpu().double() - precisions).abs().max().item() < 1e-4 * precisions.abs().max().item()
+    assert (head.task_precision.cpu().double() - task_precision).abs().max().item() < 1e-4 * task_precision.abs().max().item()
+    want = blocks.mahalanobis_predict(q.double(), means, precisions, 2.0)
+    got = head.predict(q.to(device)).cpu().double()
+    assert got.shape == (M, 5)
+    assert (got - want).abs().max().item() < 1e-3 * want.abs().max().item()
+    assert torch.equal(got.argmax(1), want.argmax(1))
+    qd = q.to(device).requires_grad_(True)
+    head.predict(qd).backward(dl.to(device))
+    qr = q.double().requires_grad_(True)
+    blocks.mahalanobis_predict(qr, head.means.cpu().double(), head.precisions.cpu().double(), 2.0).backward(dl.double())
+    assert (qd.grad.cpu().double() - qr.grad).abs().max().item() < 2e-5 * qr.grad.abs().max().item()
