@@ -13,8 +13,13 @@ Training (reference single-step-learner.py:128-243): per task `train_task` or `t
 batch {personalise_with_lite -> predict_a_batch -> N/(H*tasks_per_batch) * CE + 0.001 * l2 -> backward -> _reset}),
 optimizer.step()/zero_grad() every `tasks_per_batch` tasks, optimizer groups as utils/optim.py:11-33 (extractor
 parameters in their own group with `extractor_lr_scale`). All gradients come from the native backward kernels
-(model/autograd.py); the optimizer is torch.optim on the device-resident parameters. LR schedulers, validation and
-checkpoint rotation of the reference loop are not part of the hot path and are left out.
+(model/autograd.py); the optimizer is torch.optim on the device-resident parameters. LR schedulers and checkpoint
+rotation of the reference loop are not part of the hot path and are left out.
+
+On a dataset tree (--data_path ROOT, the reference's flag; --data_root DIR for the test loop alone) all three loops take
+their tasks from the reference-pinned sampler (data/datasets.py) in the reference's queue order (task_order) through the
+input pipeline (data/pipeline.TaskPrefetcher: decode, 8-bit or compressed upload, resize and normalisation on a copy
+stream): train on ROOT/train, validate on ROOT/validation, test - the finetuner too - on ROOT/<--test_set>.
 
 Multi-GPU: launched under torchrun, tasks are dealt round-robin to ranks (task i -> rank i % world). Test mode has no
 data-path collective (per-task statistics are all-gathered at the end). Training all-reduces (SUM, RCCL) one flat
@@ -26,6 +31,8 @@ import argparse
 import collections
 import json
 import math
+import os
+import random
 import sys
 import time
 
@@ -85,11 +92,14 @@ def build_parser():
     p.add_argument("--num_query_videos", type=int, default=4)
     p.add_argument("--frames_per_video", type=int, default=50)
     p.add_argument("--num_test_tasks", type=int, default=8)
-    p.add_argument("--num_train_tasks", type=int, default=16)
+    p.add_argument("--num_train_tasks", type=int, default=16,
+                   help="synthetic tasks per epoch. With --data_path: train tasks per train USER (per OBJECT with "
+                        "--train_task_type object_centric) and epoch, as the reference counts them (utils/args.py:91)")
     p.add_argument("--epochs", "-e", type=int, default=1)
     p.add_argument("--num_val_tasks", type=int, default=0,
                    help="validation tasks run after every epoch from --validation_on_epoch on (reference validate(), "
-                        "single-step-learner.py:245-296; 0 = no validation)")
+                        "single-step-learner.py:245-296; 0 = no validation). Synthetic tasks in all; with --data_path: tasks "
+                        "per validation USER, sampled from ROOT/validation")
     p.add_argument("--validation_on_epoch", type=int, default=1, help="epoch to turn on validation (reference utils/args.py:117)")
     p.add_argument("--save_best_model_path", default=None,
                    help="where the model with the best validation frame accuracy so far is written (reference "
@@ -112,8 +122,17 @@ def build_parser():
     p.add_argument("--save_predictions", default=None, metavar="DIR",
                    help="with --data_root: write DIR/results.json, one predicted class per frame id of every target video in "
                         "the ORBIT challenge's layout (reference TestEvaluator.save(), utils/eval_metrics.py:112-153)")
+    p.add_argument("--data_path", default=None, metavar="ROOT",
+                   help="the reference's flag (utils/args.py:18): a dataset root with train/, validation/ and test/ below it, each "
+                        "laid out as --data_root describes. Train tasks are sampled from ROOT/train (--train_* flags), validation "
+                        "tasks from ROOT/validation and test tasks from ROOT/<--test_set> (--test_* flags), through the same input "
+                        "pipeline as --data_root: --frame_size, --resample, --decode and --num_workers hold in every loop. "
+                        "Not together with --data_root. Without either flag every loop runs on synthetic tasks")
+    p.add_argument("--test_set", default="test", choices=["validation", "test"],
+                   help="with --data_path: the split the test tasks are sampled from (reference utils/args.py:19)")
     p.add_argument("--data_root", default=None,
-                   help="--mode test: a frame directory laid out like ORBIT (root/<user>/<object>/<clean|clutter>/<video>/*.jpg, "
+                   help="--mode test only (training and validation stay on synthetic tasks; use --data_path for them): one "
+                        "split directory, a frame directory laid out like ORBIT (root/<user>/<object>/<clean|clutter>/<video>/*.jpg, "
                         "reference data/datasets.py:139-200). Tasks are the users' (context = clean videos, target = clutter "
                         "videos); frames are decoded with PIL by --num_workers threads, uploaded as 8-bit on a copy stream and "
                         "normalised on the GPU (data/pipeline.TaskPrefetcher) while the previous task runs. Frames stored at "
@@ -138,10 +157,20 @@ def build_parser():
     p.add_argument("--subsample_factor", type=int, default=30)
     p.add_argument("--test_context_clip_method", default="uniform", choices=["random", "random_200", "max", "uniform"])
     p.add_argument("--test_target_clip_method", default="random_200", choices=["random", "random_200", "max"])
+    # ... and their train-side counterparts (utils/args.py:39-91), used with --data_path
+    p.add_argument("--train_way_method", default="random", choices=["random", "max"])
+    p.add_argument("--train_object_cap", type=int, default=15)
+    p.add_argument("--train_context_shot_method", default="random", choices=["specific", "fixed", "random", "max"])
+    p.add_argument("--train_target_shot_method", default="random", choices=["specific", "fixed", "random", "max"])
+    p.add_argument("--with_train_shot_caps", action="store_true", help="caps the videos per object sampled in train tasks")
+    p.add_argument("--train_context_clip_method", default="uniform", choices=["random", "random_200", "max", "uniform"])
+    p.add_argument("--train_target_clip_method", default="random", choices=["random", "random_200", "max"])
+    p.add_argument("--train_task_type", default="user_centric", choices=["user_centric", "object_centric"],
+                   help="with --data_path: train tasks from one user's objects, or from the objects of all users")
     p.add_argument("--max_test_tasks", type=int, default=None,
                    help="with --data_root: evaluate only the first N tasks of the user-major order (default: all users)")
     p.add_argument("--num_test_tasks_per_user", type=int, default=1,
-                   help="with --data_root: tasks sampled per test user (reference --num_test_tasks, utils/args.py)")
+                   help="with --data_root / --data_path: tasks sampled per test user (reference --num_test_tasks, utils/args.py)")
     p.add_argument("--num_workers", type=int, default=4, help="decode threads (reference data/queues.py:34: 4 in test mode)")
     p.add_argument("--frame_norm_method", default="imagenet", choices=["imagenet", "imagenet_inception", "openai_clip"])
     return p
@@ -164,6 +193,75 @@ FROZEN_EXTRACTORS = {
 }
 
 
+# ---- tasks from a dataset tree (--data_path / --data_root) ------------------------------------------------------------------
+def split_roots(args):
+    """{split: directory} of the splits the run's mode reads from a tree (reference data/dataloaders.py:15-70): --data_path
+    ROOT gives ROOT/train (and ROOT/validation when validation is on) to the training modes and ROOT/<--test_set> to the test
+    modes; --data_root DIR is one split directory for the test loop alone. {} on synthetic tasks. Both flags: an error."""
+    root, single = getattr(args, "data_path", None), getattr(args, "data_root", None)
+    if root and single:
+        sys.exit("error: --data_path (a root with train/, validation/ and test/ below it) and --data_root (one split directory, "
+                 "test loop only) cannot be given together")
+    roots = {}
+    if root:
+        if "train" in args.mode:
+            roots["train"] = os.path.join(root, "train")
+            if getattr(args, "num_val_tasks", 0) > 0:
+                roots["validation"] = os.path.join(root, "validation")
+        if "test" in args.mode:
+            roots["test"] = os.path.join(root, getattr(args, "test_set", "test"))
+    elif single and "test" in args.mode:
+        roots["test"] = single
+    return roots
+
+
+def task_order(num_items, num_tasks, seed=None, epoch=0):
+    """The reference's task queue (data/samplers.py:24-30): every item - a user, or an object for object-centric training -
+    listed `num_tasks` times. seed None: left in that order (validation and test queues). Otherwise shuffled as the train
+    queue is, once per epoch, by ONE random.Random(seed) that advances epoch by epoch - a stream of its own, so neither the
+    datasets' sampling nor how far a prefetcher runs ahead moves it, and identical on every rank."""
+    order = [item for item in range(num_items) for _ in range(num_tasks)]
+    if seed is None:
+        return order
+    rng = random.Random(seed)
+    for _ in range(epoch + 1):
+        shuffled = list(order)
+        rng.shuffle(shuffled)
+    return shuffled
+
+
+def split_rng(args, split, rank=0):
+    """The sampling stream of a split's dataset: separate per split and rank, so tasks staged ahead for one loop never
+    interleave their draws with another's. train and test: random.Random(seed + rank); validation: a third stream."""
+    return random.Random(args.seed + rank + (7919 * 104729 if split == "validation" else 0))
+
+
+def build_split_dataset(args, split, root, frames="uint8", rank=0, decode_pool=None):
+    """The reference's queue datasets (data/dataloaders.py:15-70 -> data/queues.py) on `root`: "train" samples with the
+    --train_* flags in train mode (clips and labels shuffled), user- or object-centric; "validation" and "test" with the
+    --test_* flags in test mode (target frames grouped by video), user-centric."""
+    from .data.datasets import ObjectEpisodicORBITDataset, UserEpisodicORBITDataset
+    a = args
+    if split not in ("train", "validation", "test"):
+        raise ValueError("split must be 'train', 'validation' or 'test', got %r" % (split,))
+    train = split == "train"
+    cls = ObjectEpisodicORBITDataset if train and a.train_task_type == "object_centric" else UserEpisodicORBITDataset
+    way, cap, shot_methods, clip_methods = (
+        (a.train_way_method, a.train_object_cap, (a.train_context_shot_method, a.train_target_shot_method),
+         (a.train_context_clip_method, a.train_target_clip_method)) if train else
+        (a.test_way_method, a.test_object_cap, (a.test_context_shot_method, a.test_target_shot_method),
+         (a.test_context_clip_method, a.test_target_clip_method)))
+    return cls(root, way, cap, shot_methods, (a.context_shot, a.target_shot), (a.context_video_type, a.target_video_type),
+               a.subsample_factor, clip_methods, a.clip_length, a.frame_size, a.frame_norm_method, [], ([], []), not train, False,
+               bool(train and a.with_train_shot_caps), None, frames=frames, rng=split_rng(a, split, rank), decode_pool=decode_pool)
+
+
+def num_items(dataset):
+    """what a queue lists: the objects of an object-centric dataset, else the users (data/queues.py:54,74)"""
+    from .data.datasets import ObjectEpisodicORBITDataset
+    return dataset.num_objects if isinstance(dataset, ObjectEpisodicORBITDataset) else dataset.num_users
+
+
 def verify_args(args):
     """reference utils/args.py:203-217. For the frozen-scope extractors (FROZEN_EXTRACTORS) also the frame normalisation the
     reference sets for them and the inference-only scope: everything that would send a gradient or batch statistics through the
@@ -173,6 +271,10 @@ def verify_args(args):
         sys.exit("error: at least one of --learn_extractor and --adapt_features must be used when training")
     if args.frame_size % 1 or args.frame_size < 32:
         sys.exit("error: --frame_size must be >= 32")
+    for split, path in split_roots(args).items():  # (exits when both --data_path and --data_root are given)
+        if getattr(args, "data_path", None) and not os.path.isdir(path):
+            sys.exit("error: --data_path %s: --mode %s needs the %s split, and %s is not a directory"
+                     % (args.data_path, args.mode, split, path))
     fe = args.feature_extractor
     spec = FROZEN_EXTRACTORS.get(fe)
     if spec is None:
@@ -402,8 +504,60 @@ class Learner:
             # sequential updates would have been (dist.RunningStatSync; round 2 averaged the ranks' values)
             self.stat_sync.sync()  # (in-place copies: the plans see the new buffer versions and re-upload them)
 
-    def train(self):
+    # ---- tasks from a dataset tree (--data_path / --data_root) -----------------------------------------------------------
+    def decode_pool(self):
+        """the threads that decode (or, with --decode device, read and parse) the frames of every tree loop: --num_workers of
+        them, never the CPU count"""
+        if getattr(self, "_pool", None) is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(max_workers=max(1, int(self.args.num_workers)))
+        return self._pool
+
+    def _close_decode_pool(self):
+        if getattr(self, "_pool", None) is not None:
+            self._pool.shutdown()
+            self._pool = None
+
+    def build_dataset(self, split, frames=None):
+        """The dataset the `split` loop ("train", "validation" or "test") samples its tasks from, on this rank's sampling
+        stream. frames: what the clips hold (data/datasets.py); default "jpeg" for --decode device, else "uint8" - the two
+        forms TaskPrefetcher uploads."""
         a = self.args
+        root = split_roots(a).get(split)
+        if root is None:
+            raise ValueError("--mode %s%s reads no %s split from a tree" % (a.mode, "" if getattr(a, "data_path", None) or getattr(
+                a, "data_root", None) else " without --data_path", split))
+        if frames is None:
+            frames = "jpeg" if a.decode == "device" else "uint8"
+        return build_split_dataset(a, split, root, frames, self.rank, None if frames == "paths" else self.decode_pool())
+
+    def train_order(self, epoch):
+        """this rank's item indices (users; objects when object-centric) of train epoch `epoch`, in the order it trains on them:
+        the queue's shuffled order (task_order: the same on every rank), dealt round-robin"""
+        a = self.args
+        return task_order(self._num_train_items(), a.num_train_tasks, a.seed, epoch)[self.rank::self.world]
+
+    def _num_train_items(self):
+        if getattr(self, "_train_items", None) is None:
+            self._train_items = num_items(self.build_dataset("train", frames="paths"))
+        return self._train_items
+
+    def _prefetch(self, dataset, indices, depth):
+        """dataset[i] for i in indices, staged on the device: decode / file reads on the pool, 8-bit or compressed upload,
+        decode, resize and normalisation on the copy stream (data/pipeline.TaskPrefetcher), `depth` tasks in flight"""
+        from .data.pipeline import DatasetTaskSource, TaskPrefetcher
+        a = self.args
+        self.model.frame_norm_method = a.frame_norm_method
+        return TaskPrefetcher(DatasetTaskSource(dataset, indices), self.device, depth=depth, frame_norm_method=a.frame_norm_method,
+                              frame_size=a.frame_size, resample=a.resample)
+
+    def train(self, task_source=None):
+        """task_source: an iterable of this rank's train tasks (task dicts as data/datasets.py returns them, all epochs in
+        train_order order) that stands in for the tree and the prefetcher; loop, seeds and step boundaries are the same."""
+        a = self.args
+        tree = split_roots(a).get("train")
+        if tree is None and getattr(a, "data_root", None) and self.rank == 0:
+            print("train: --data_root names a test split only: training runs on synthetic tasks (use --data_path ROOT)")
         self.optimizer = init_optimizer(self.model, a.learning_rate, a.optimizer, a, a.extractor_lr_scale)
         apply_lr_scale(self.optimizer, a.learning_rate)  # constant schedule (the reference's timm scheduler applies it)
         self.grad_bucket = None
@@ -417,13 +571,34 @@ class Learner:
                 self.stat_sync = odist.RunningStatSync(self.model.feature_extractor,
                                                        getattr(self.model.feature_extractor, "bn_momentum", 0.1))
         train_task_fn = self.train_task_with_lite if a.with_lite else self.train_task
-        losses, accs, times = [], [], []
+        losses, accs, times, waits, task_frames = [], [], [], [], []
+        # (per task, in this rank's order: the losses are what a run on the same tasks must reproduce)
+        self.task_losses, self.task_ms, self.task_wait_ms = losses, times, waits
+        prefetch, stream, t_all = None, None, time.perf_counter()
+        lite_query_overlap = getattr(self.model, "lite_query_overlap", False)
+        if task_source is not None:
+            stream = iter(task_source)
+        elif tree is not None:
+            # ONE prefetcher over all epochs (the first tasks of epoch e+1 are staged under the validation of epoch e), two
+            # slots: the step is longer than the staging of a task, a third slot would only hold memory.
+            # A slot must not be refilled while any stream of the recogniser still reads it (LITE's subset pass and its
+            # query pass run on side streams): the loop SYNCHRONISES THE DEVICE after every task's step - the timer below needs
+            # that anyway - before it asks for the next task, so no consumer_streams are passed to the prefetcher.
+            dataset = self.build_dataset("train")
+            self._train_items = num_items(dataset)
+            prefetch = self._prefetch(dataset, [i for epoch in range(a.epochs) for i in self.train_order(epoch)], depth=2)
+            stream = iter(prefetch)
+            # The yielded clips are complete on the caller's stream when next() returns (it waits for the slot's event), so the
+            # query batch's taped pass may start from LITE's fork point as it does for clips on the host: the same kernels,
+            # and the same deferred running-statistics update, whether a task comes from the tree or from host tensors
+            self.model.lite_query_overlap = bool(getattr(self.model, "lite_overlap", False))
         prev = torch.is_grad_enabled()
         torch.set_grad_enabled(True)
         try:
             self.model.set_test_mode(False)
             for epoch in range(a.epochs):
-                total_steps = a.num_train_tasks
+                # with --data_path: --num_train_tasks per user (or object), in the queue's order (task_order)
+                total_steps = a.num_train_tasks if tree is None else self._num_train_items() * a.num_train_tasks
                 # this rank's tasks of the epoch are generated up front (the reference prefetches with DataLoader
                 # workers): generating them between steps leaves the intra-op CPU threads spinning against the thread
                 # that enqueues kernels, which showed up as random 50-80 ms stalls per task
@@ -431,10 +606,16 @@ class Learner:
                 task_bytes = 4.0 * 3 * a.frame_size ** 2 * a.way * (a.shots * a.frames_per_shot
                                                                    + a.num_query_videos * a.frames_per_video)
                 pregen = {s_: self.make_train_task(epoch * total_steps + s_) for s_ in mine} \
-                    if task_bytes * len(mine) < 16e9 else {}
+                    if stream is None and task_bytes * len(mine) < 16e9 else {}
                 for step in range(total_steps):
                     if step % self.world == self.rank:
-                        task = pregen.pop(step, None) or self.make_train_task(epoch * total_steps + step)
+                        if stream is not None:
+                            t0 = time.perf_counter()
+                            task = next(stream)  # (hands the previous task's slot back: the device is idle, see above)
+                            waits.append(1e3 * (time.perf_counter() - t0))
+                            task_frames.append(sum(int(np.prod(task[k].shape[:2])) for k in ("context_clips", "target_clips")))
+                        else:
+                            task = pregen.pop(step, None) or self.make_train_task(epoch * total_steps + step)
                         # LITE draws its subsets from np.random (few_shot_recognisers.py:330); seeding per TASK (the
                         # reference leaves numpy unseeded) makes a run independent of how tasks are dealt to ranks
                         np.random.seed((a.seed + 7919 * (epoch * total_steps + step + 1)) % (2 ** 32))
@@ -444,7 +625,7 @@ class Learner:
                         torch.cuda.synchronize()
                         times.append(1e3 * (time.perf_counter() - t0))
                         losses.append(float(task_loss))
-                        accs.append(frame_accuracy(logits.cpu(), task["target_labels"]))
+                        accs.append(frame_accuracy(logits.cpu(), task["target_labels"].cpu()))
                         if a.print_by_step:
                             print("epoch [%d/%d][%d/%d] rank %d train loss %.7f frame_acc %.3f  %.1f ms/task"
                                   % (epoch + 1, a.epochs, step + 1, total_steps, self.rank, losses[-1], accs[-1], times[-1]))
@@ -466,6 +647,11 @@ class Learner:
                     self.model.set_test_mode(False)
         finally:
             torch.set_grad_enabled(prev)
+            self.model.lite_query_overlap = lite_query_overlap
+            if prefetch is not None:
+                prefetch.close()
+                self._close_decode_pool()
+        wall = time.perf_counter() - t_all
         if self.grad_bucket is not None and self.grad_bucket.p2p is not None:
             # every optimizer step checked the exchange before it (GradientBucket.sync); this covers the last one: a peer
             # that stalled makes this rank raise instead of saving parameters updated from NaN-poisoned gradients
@@ -477,14 +663,30 @@ class Learner:
                  "ms_per_task": mean_ci(times) if times else (0.0, 0.0), "num_tasks": len(losses),
                  "world_size": self.world, "validation": getattr(self, "validation_history", None),
                  "best_validation": getattr(self, "best_validation", None)}
+        # the tree's side of the run (None / empty on synthetic tasks). ms_per_task is the step alone; data_wait_ms is the time
+        # the loop was blocked in next() on the prefetcher, per task; wall_s covers both, validation and the optimizer steps
+        stored = sorted(prefetch.stored_sizes) if prefetch is not None else []
+        stats.update({"data_path": getattr(a, "data_path", None) if tree is not None else None, "decode": a.decode if tree else None,
+                      "decode_fallback_frames": prefetch.fallback_frames if prefetch is not None and a.decode == "device" else None,
+                      "stored_frame_size": [list(hw) for hw in stored], "frame_size": [a.frame_size, a.frame_size],
+                      "resample": a.resample if any(hw != (a.frame_size, a.frame_size) for hw in stored) else None,
+                      "train_task_type": a.train_task_type if tree is not None else None,
+                      "data_wait_ms": mean_ci(waits) if waits else None,
+                      "frames_per_task": mean_ci(task_frames) if task_frames else None, "wall_s": wall})
         if self.rank == 0:
             print("train: loss %.5f | frame_acc %.2f %% | %.1f ms/task | %d tasks on this rank, %d GPU(s)"
                   % (stats["loss"][0], 100 * stats["frame_acc"][0], stats["ms_per_task"][0], stats["num_tasks"],
                      self.world))
+            if task_frames:
+                print("train (%s): %.0f frames per task | waited %.1f (%.1f) ms per task for data (decode: %s, %d threads) | "
+                      "%.2f tasks/s of wall time"
+                      % ("%s, %s" % (a.data_path, a.train_task_type) if prefetch is not None else "tasks handed in",
+                         stats["frames_per_task"][0], *stats["data_wait_ms"], a.decode, a.num_workers, len(losses) / max(wall, 1e-9)))
         return stats
 
     def validate(self, epoch=0):
-        """The reference's validate() (single-step-learner.py:245-296) on held-out synthetic tasks: test mode, no grad,
+        """The reference's validate() (single-step-learner.py:245-296) on held-out tasks - synthetic ones, or with
+        --data_path the validation split's: test mode, no grad,
         personalise on the context clips, predict every target video on its frame history, per-video frame accuracy; the
         model whose mean per-video accuracy beats the best so far (ValidationEvaluator.is_better, utils/eval_metrics.py:351-357:
         strictly greater, starting from 0) is written to --save_best_model_path. Tasks are dealt to the ranks and the
@@ -492,14 +694,28 @@ class Learner:
         a = self.args
         self.model.set_test_mode(True)
         accs = []
-        with torch.no_grad():
-            for t in odist.tasks_for_rank(a.num_val_tasks, self.rank, self.world):
-                context_clips, context_labels, videos = self.make_task(20_000 + t)
-                self.model.personalise(context_clips, self._labels_to_device(context_labels))
-                for frames, labels in videos:
-                    logits = self.model.predict_video(frames)  # = predict(attach_frame_history(frames, clip_length))
-                    accs.append(frame_accuracy(logits.cpu(), labels))
-                self.model._reset()
+        if split_roots(a).get("validation"):
+            # --data_path: --num_val_tasks tasks per user of ROOT/validation in the queue's unshuffled order, each run as the
+            # test loop runs a task. The sampling stream restarts with every call, so every epoch's model is scored on the
+            # same tasks and "strictly greater" compares like with like.
+            if getattr(self, "_validation_dataset", None) is None:
+                self._validation_dataset = self.build_dataset("validation")
+            dataset = self._validation_dataset
+            dataset.rng = split_rng(a, "validation", self.rank)
+            prefetch = self._prefetch(dataset, task_order(num_items(dataset), a.num_val_tasks)[self.rank::self.world], depth=3)
+            with torch.no_grad():
+                for task in prefetch:
+                    accs += self._run_tree_task(task, [], [])
+            prefetch.close()
+        else:
+            with torch.no_grad():
+                for t in odist.tasks_for_rank(a.num_val_tasks, self.rank, self.world):
+                    context_clips, context_labels, videos = self.make_task(20_000 + t)
+                    self.model.personalise(context_clips, self._labels_to_device(context_labels))
+                    for frames, labels in videos:
+                        logits = self.model.predict_video(frames)  # = predict(attach_frame_history(frames, clip_length))
+                        accs.append(frame_accuracy(logits.cpu(), labels))
+                    self.model._reset()
         if self.world > 1:
             import torch.distributed as dist
             gathered = [None] * self.world
@@ -523,27 +739,48 @@ class Learner:
         return unpack_task({"context_labels": labels, "target_labels": None, "context_clips": None, "target_clips": None},
                            self.device)[2]
 
+    def _personalise_tree_task(self, task):
+        self.model.personalise(task["context_clips"], task["context_labels"])
+
+    def _predict_tree_video(self, frames):
+        return self.model.predict_video(frames)  # = predict(attach_frame_history(frames, clip_length))
+
+    def _run_tree_task(self, task, personalise_ms, inference_ms, metrics=None):
+        """One staged test-mode task as the reference's test and validation loops run it (single-step-learner.py:262-281,
+        316-341): personalise on the context clips, then per target VIDEO predict on its frame history. Appends to the two
+        timer lists, feeds `metrics` (OrbitMetrics, begin_task already called) and returns the per-video frame accuracies."""
+        video_labels = task["target_labels"].cpu() if metrics is not None else None
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        self._personalise_tree_task(task)
+        torch.cuda.synchronize()
+        personalise_ms.append(1e3 * (time.perf_counter() - t0))
+        accs = []
+        target = task["target_clips"][:, 0]  # [M,3,H,W]: the videos' frames, in video order
+        for lo, hi in task["target_videos"]:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            logits = self._predict_tree_video(target[lo:hi])
+            torch.cuda.synchronize()
+            inference_ms.append(1e3 * (time.perf_counter() - t0) / float((hi - lo) * self.model.clip_length))
+            accs.append(frame_accuracy(logits, task["target_labels"][lo:hi]))
+            if metrics is not None:
+                paths = task["target_paths"][len(accs) - 1] if task.get("target_paths") is not None else None
+                metrics.append_video(logits, video_labels[lo], paths)
+        self.model._reset()
+        return accs
+
     def test_directory(self):
         """The reference's test loop (single-step-learner.py:298-375) over a JPEG directory: one task per user, personalise
         on the context clips, then per target VIDEO predict on its frame history, frame accuracy per video averaged per
         task. Decode, 8-bit upload and normalisation of task i+1 overlap the extractor work of task i. A tree stored at
         another size than --frame_size is resized to it in the normalisation launch (--resample)."""
-        import random
-        from concurrent.futures import ThreadPoolExecutor
-        from .data.datasets import UserEpisodicORBITDataset
-        from .data.pipeline import DatasetTaskSource, TaskPrefetcher
         a = self.args
+        root = split_roots(a)["test"]  # --data_root, or --data_path's <--test_set> split
         self.model.set_test_mode(True)
-        self.model.frame_norm_method = a.frame_norm_method
         # the reference's test queue (data/queues.py:44-46 -> data/datasets.py; pinned by fixture G14): every user's objects,
         # all their videos, context clips sampled uniformly, 200 random clips per target video
-        pool = ThreadPoolExecutor(max_workers=max(1, int(a.num_workers)))
-        dataset = UserEpisodicORBITDataset(
-            a.data_root, a.test_way_method, a.test_object_cap, (a.test_context_shot_method, a.test_target_shot_method),
-            (a.context_shot, a.target_shot), (a.context_video_type, a.target_video_type), a.subsample_factor,
-            (a.test_context_clip_method, a.test_target_clip_method), a.clip_length, a.frame_size, a.frame_norm_method, [],
-            ([], []), True, False, False, None, frames="jpeg" if a.decode == "device" else "uint8",
-            rng=random.Random(a.seed + self.rank), decode_pool=pool)
+        dataset = self.build_dataset("test")
         # TaskSampler order (data/samplers.py:24-30, no shuffle): user 0 x num_tasks, user 1 x num_tasks, ...; dealt to ranks
         # - EVERY user x num_test_tasks_per_user, as the reference's loop visits them (single-step-learner.py:313-314). An
         # optional total cap (--max_test_tasks; default none) is applied BEFORE the tasks are dealt, so the evaluated set does
@@ -553,41 +790,21 @@ class Learner:
         if cap is not None and cap < len(order):
             if self.rank == 0:
                 print("test (%s): --max_test_tasks %d truncates %d tasks (%d users x %d) - NOT the full test set"
-                      % (a.data_root, cap, len(order), len(dataset), a.num_test_tasks_per_user))
+                      % (root, cap, len(order), len(dataset), a.num_test_tasks_per_user))
             order = order[:cap]
-        source = DatasetTaskSource(dataset, order[self.rank::self.world])
         task_acc, personalise_ms, inference_ms, frames = [], [], [], 0
         save_dir = getattr(a, "save_predictions", None)
         metrics = OrbitMetrics(save_dir)
         mine = list(range(len(order)))[self.rank::self.world]  # global indices of this rank's tasks
         t_all = time.perf_counter()
-        prefetch = TaskPrefetcher(source, self.device, depth=3, frame_norm_method=a.frame_norm_method, frame_size=a.frame_size,
-                                  resample=a.resample)
+        prefetch = self._prefetch(dataset, order[self.rank::self.world], depth=3)
         with torch.no_grad():
             for k, task in enumerate(prefetch):
                 metrics.begin_task(mine[k], task["user"], task.get("object_list"))
-                video_labels = task["target_labels"].cpu()
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                self.model.personalise(task["context_clips"], task["context_labels"])
-                torch.cuda.synchronize()
-                personalise_ms.append(1e3 * (time.perf_counter() - t0))
-                accs = []
-                target = task["target_clips"][:, 0]  # [M,3,H,W]: the videos' frames, in video order
-                for lo, hi in task["target_videos"]:
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    logits = self.model.predict_video(target[lo:hi])  # = predict(attach_frame_history(frames, clip_length))
-                    torch.cuda.synchronize()
-                    inference_ms.append(1e3 * (time.perf_counter() - t0) / float((hi - lo) * self.model.clip_length))
-                    accs.append(frame_accuracy(logits, task["target_labels"][lo:hi]))
-                    paths = task["target_paths"][len(accs) - 1] if task.get("target_paths") is not None else None
-                    metrics.append_video(logits, video_labels[lo], paths)
-                    frames += hi - lo
-                task_acc.append(float(np.mean(accs)))
-                self.model._reset()
+                task_acc.append(float(np.mean(self._run_tree_task(task, personalise_ms, inference_ms, metrics))))
+                frames += sum(hi - lo for lo, hi in task["target_videos"])
         prefetch.close()
-        pool.shutdown()
+        self._close_decode_pool()
         wall = time.perf_counter() - t_all
         if self.world > 1:  # per-task results of every rank, as test() gathers them
             import torch.distributed as dist
@@ -601,20 +818,20 @@ class Learner:
         stored = sorted(prefetch.stored_sizes)  # (this rank's tasks)
         stats = {"frame_acc": mean_ci(task_acc), "personalise_ms": mean_ci(personalise_ms),
                  "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world,
-                 "target_frames": frames, "wall_s": wall, "data_root": a.data_root, "orbit_metrics": metrics.report(),
+                 "target_frames": frames, "wall_s": wall, "data_root": root, "orbit_metrics": metrics.report(),
                  "stored_frame_size": [list(hw) for hw in stored], "frame_size": [a.frame_size, a.frame_size],
                  "resample": a.resample if any(hw != (a.frame_size, a.frame_size) for hw in stored) else None,
                  "decode": a.decode, "decode_fallback_frames": prefetch.fallback_frames if a.decode == "device" else None}
         if self.rank == 0:
             print("test (%s): frames stored at %s, extractor ran at %dx%d%s"
-                  % (a.data_root, ", ".join("%dx%d" % hw for hw in stored) or "-", a.frame_size, a.frame_size,
+                  % (root, ", ".join("%dx%d" % hw for hw in stored) or "-", a.frame_size, a.frame_size,
                      " (resized on the GPU, %s)" % a.resample if stats["resample"] else ""))
             if a.decode == "device":
                 print("test (%s): JPEG decode on the GPU, %d frames; %d decoded by PIL instead (out of scope or damaged)"
-                      % (a.data_root, prefetch.device_frames, prefetch.fallback_frames))
+                      % (root, prefetch.device_frames, prefetch.fallback_frames))
             print("test (%s): frame_acc %.2f (%.2f) %% | time to personalise %.2f (%.2f) ms | inference %.4f (%.4f) ms/frame "
                   "| %d tasks, %d target frames in %.1f s incl. JPEG decode (%d threads)"
-                  % (a.data_root, 100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1], *_shown(stats["personalise_ms"]),
+                  % (root, 100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1], *_shown(stats["personalise_ms"]),
                      *_shown(stats["inference_ms_per_frame"]), stats["num_tasks"], frames, wall, a.num_workers))
             print(OrbitMetrics.line(stats["orbit_metrics"]))
             if save_dir and stats["orbit_metrics"] is not None:
@@ -627,7 +844,7 @@ class Learner:
 
     def test(self):
         a = self.args
-        if getattr(a, "data_root", None):
+        if split_roots(a).get("test"):
             return self.test_directory()
         self.model.set_test_mode(True)
         # (synthetic tasks live on the host and are uploaded per mini-batch: in its default mode, overlap_query = "auto", the
@@ -702,13 +919,30 @@ class MultiStepLearner(Learner):
     def run(self):
         return {"test": self.test()}
 
+    def learning_args(self):
+        a = self.args
+        return {"num_grad_steps": a.personalize_num_grad_steps, "learning_rate": a.personalize_learning_rate,
+                "extractor_lr_scale": a.personalize_extractor_lr_scale, "loss_fn": cross_entropy,
+                "optimizer": a.personalize_optimizer, "momentum": a.personalize_momentum,
+                "weight_decay": a.personalize_weight_decay, "betas": tuple(a.personalize_betas),
+                "epsilon": a.personalize_epsilon}
+
+    # the tree loop (Learner.test_directory: --data_root, or --data_path's test split) with the finetuner's two steps
+    def _personalise_tree_task(self, task):
+        # every task starts from the initial parameters (multi-step-learner.py:153-154); the gradient steps need autograd
+        # inside the loop's no_grad
+        self.model.load_state_dict(self.base_state, strict=False)
+        with torch.enable_grad():
+            self.model.personalise(task["context_clips"], task["context_labels"], self.learning_args())
+
+    def _predict_tree_video(self, frames):
+        return self.model.predict(attach_frame_history(frames, self.args.clip_length))
+
     def test(self):
         a = self.args
-        learning_args = {"num_grad_steps": a.personalize_num_grad_steps, "learning_rate": a.personalize_learning_rate,
-                         "extractor_lr_scale": a.personalize_extractor_lr_scale, "loss_fn": cross_entropy,
-                         "optimizer": a.personalize_optimizer, "momentum": a.personalize_momentum,
-                         "weight_decay": a.personalize_weight_decay, "betas": tuple(a.personalize_betas),
-                         "epsilon": a.personalize_epsilon}
+        if split_roots(a).get("test"):
+            return self.test_directory()
+        learning_args = self.learning_args()
         self.model.set_test_mode(True)
         task_acc, personalise_ms, inference_ms = [], [], []
         metrics = OrbitMetrics()

@@ -220,6 +220,14 @@ class HipNetwork(nn.Module):
     def _persistent_tensor(self, key, kind, numel, dtype, device):
         t = self._persist.get((key, kind))
         if t is None or t.numel() < numel or t.dtype != dtype or t.device != device:
+            # The first forward under `key` (and one that outgrows the buffer) does take an allocator block, and the allocator
+            # hands out what the caller's stream freed on the HOST - LITE's cache pass drops a tape per mini-batch while its
+            # kernels are still queued - so the side stream, ordered only behind the fork point, would write into a block the
+            # caller's stream still reads (seen as a wrong loss for the first task of a learner whose process had run another
+            # one before: the block came from the cache instead of the driver). Drain the caller's stream once, here: the
+            # block's previous users are all queued on it.
+            if torch.device(device).type == "cuda" and not torch.cuda.is_current_stream_capturing():
+                torch.cuda.current_stream(device).synchronize()
             t = self._persist[(key, kind)] = torch.empty(max(int(numel), 256), dtype=dtype, device=device)
         return t[:numel] if t.numel() != numel else t
 
