@@ -4,6 +4,8 @@ MI355X-native recogniser and backward kernels, synthetic ORBIT-shaped tasks. See
 
     python multi-step-learner.py --feature_extractor resnet18 --frame_size 84 --adapt_features \
         --personalize_num_grad_steps 50 --personalize_learning_rate 0.001 --num_test_tasks 4
+    # on a dataset tree, with the benchmark's filter of the clutter videos (the --test_filter_* pair and --annotations_to_load)
+    python multi-step-learner.py --feature_extractor resnet18 --data_path ROOT --test_filter_target no_object_not_present_issue
 """
 import os
 import sys

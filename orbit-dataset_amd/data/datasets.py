@@ -25,10 +25,41 @@ shuffle), so seeding the `random` module (the default source, as the reference u
 Beyond the reference: `frames=` selects what the clips hold - "float" (normalised fp32, the reference's layout), "uint8"
 (decoded 8-bit [.., H, W, 3] for TaskPrefetcher: a quarter of the bytes over PCIe, normalised on the GPU bit-identically),
 "jpeg" (the files, read and parsed but not decoded: pipeline.JpegFrames, which TaskPrefetcher decodes on the GPU) or
-"paths" (nothing decoded). Frame annotations and cluster labels are not on the recognition path and are not built:
-asking for them raises.
+"paths" (nothing decoded).
+
+Frame annotations (reference :59-74,121-134,169-178,243-266,346-374,393-420,485-522), pinned by fixture G16
+(tests/golden/make_golden_annotations.py, tests/test_annotations.py):
+
+  root             dirname(root)/annotations/basename(root) (a trailing separator of root is stripped first), one
+                   <video name>.json per video whose keys are the frame file names. Needed as soon as anything is loaded or
+                   filtered: IOError when the directory is absent, FileNotFoundError for a missing JSON, KeyError (frame and
+                   file named) for a frame the JSON does not list. A video's JSON is read at index time when annotations are
+                   loaded, or when the video's set has filter criteria; without either no annotation file is touched.
+  filter           a frame's tags are {k : value is true} | {"no_" + k : value is false} over its annotation dictionary (JSON
+                   booleans only: null, absent keys and anything else give no tag); the frame is kept when the tags meet the
+                   set's criteria. The frame floors (context 1, target 50) then count the FILTERED frames; videos, objects
+                   and users drop out, and ids are numbered over what survives, exactly as without a filter. This is the
+                   benchmark's CLU-VE rule with filter_target = ["no_object_not_present_issue"].
+  loading          annotations_to_load (kept sorted) -> per annotation a float32 tensor [n_clips, 1, 1] holding the annotation
+                   of every clip's LAST frame: true 1, false 0, null NaN. Train mode: permuted with the clips and labels (no
+                   extra draw); test mode: one dict per target video, [frames, 1] each. Nothing loaded: {} / a list of None.
+                   A frame whose dictionary lacks a requested key raises KeyError (frame and key named), as the reference
+                   does - clutter frames carry only object_not_present_issue of the seven quality keys; no value is invented.
+
+Where the reference is defective, and what is done here:
+  * clip_length > 1 with annotations loaded: the reference writes index T-1 into a dimension of size 1 (IndexError, :405-416).
+    Here the last frame's annotation is returned per clip, [n, 1, 1] - what its `without_clip_history=True` argument states.
+    Filters alone work at any clip_length in both.
+  * `no_issues` / `mixed_issues` (expand_issues, reference utils/args.py:194-199) expand to all seven `no_*` names / all seven
+    plain names, `no_issues` first and replacing the whole list. Because a frame is kept when ANY criterion matches, `no_issues`
+    keeps every frame with at least one issue absent. The reference's behaviour is kept.
+  * `object_bounding_box` in annotations_to_load (or as a filter criterion) raises NotImplementedError before any file is
+    touched: clean videos' JSONs have no such key, so the reference raises KeyError on a clean/clutter task, and combined with
+    a filter RuntimeError (a tensor compared with True) - there is nothing of it to pin. `with_cluster_labels=True` raises too:
+    the reference removed the training mode that used them.
 """
 import glob
+import json
 import os
 import random as _random
 
@@ -40,6 +71,27 @@ from .utils import NORMALIZE_STATS
 FRAME_CAP = 1000      # frames considered per video (reference :80)
 CLIP_CAP = 200        # clips sampled per video (reference :79)
 MIN_FRAMES = {"context": 1, "target": 50}  # reference :121-134
+
+# reference utils/args.py:7-10
+FRAME_ANNOTATION_OPTIONS = ["object_not_present_issue", "framing_issue", "viewpoint_issue", "blur_issue", "occlusion_issue",
+                            "overexposed_issue", "underexposed_issue"]
+NEGATED_FRAME_ANNOTATION_OPTIONS = ["no_" + a for a in FRAME_ANNOTATION_OPTIONS]
+BOUNDING_BOX_OPTIONS = ["object_bounding_box"]
+ALL_FRAME_ANNOTATION_OPTIONS = FRAME_ANNOTATION_OPTIONS + NEGATED_FRAME_ANNOTATION_OPTIONS + ["no_issues", "mixed_issues"]
+
+
+def expand_issues(criteria):
+    """reference utils/args.py:194-199: `no_issues` (checked first) / `mixed_issues` replace the whole list"""
+    if "no_issues" in criteria:
+        return list(NEGATED_FRAME_ANNOTATION_OPTIONS)
+    if "mixed_issues" in criteria:
+        return list(FRAME_ANNOTATION_OPTIONS)
+    return list(criteria)
+
+
+def frame_tags(frame_annotations):
+    """the tag set the filter matches against (reference :251-252), from the JSON's booleans only"""
+    return {k for k, v in frame_annotations.items() if v is True} | {"no_" + k for k, v in frame_annotations.items() if v is False}
 
 
 def clip_frame_indices(num_frames, clip_length, method, subsample_factor=30, rng=_random):
@@ -85,11 +137,15 @@ class ORBITDataset(torch.utils.data.Dataset):
                  clip_length, frame_size, frame_norm_method, annotations_to_load=(), filter_by_annotations=((), ()),
                  test_mode=False, with_cluster_labels=False, with_caps=False, logfile=None, frames="float", rng=None,
                  decode_pool=None):
-        if annotations_to_load or any(filter_by_annotations) or with_cluster_labels:
-            raise NotImplementedError("frame annotations / cluster labels are outside the recognition path (DESIGN.md §7)")
+        annotations_to_load = sorted(annotations_to_load)
+        criteria = dict(zip(("context", "target"), (sorted(f) for f in filter_by_annotations)))
+        asked = annotations_to_load + criteria["context"] + criteria["target"]
+        if with_cluster_labels or any(a in ("object_bounding_box", "no_object_bounding_box") for a in asked):
+            raise NotImplementedError("bounding-box annotations / cluster labels are not built (DESIGN.md §8)")
         if frames not in ("float", "uint8", "paths", "jpeg"):
             raise ValueError("frames must be 'float', 'uint8', 'jpeg' or 'paths'")
-        self.root, self.mode = root, os.path.basename(root)
+        stripped = root.rstrip(os.sep) or root
+        self.root, self.mode = root, os.path.basename(stripped)
         self.way_method, self.object_cap = way_method, object_cap
         self.shot_method = dict(zip(("context", "target"), shot_methods))
         self.shot = dict(zip(("context", "target"), shots))
@@ -101,9 +157,17 @@ class ORBITDataset(torch.utils.data.Dataset):
         self.test_mode, self.with_caps, self.logfile = test_mode, with_caps, logfile
         self.shot_cap = {"context": 15, "target": 15}
         self.frames, self.rng, self.decode_pool = frames, (rng if rng is not None else _random), decode_pool
-        self.annotations_to_load, self.with_annotations = [], False
+        self.annotations_to_load, self.with_annotations = annotations_to_load, bool(annotations_to_load)
+        self.filter_criteria = criteria
+        self.filter_context, self.filter_target = criteria["context"], criteria["target"]
+        self.with_frame_filtering = bool(self.filter_context or self.filter_target)
+        self.annotation_root = None
+        if self.with_annotations or self.with_frame_filtering:
+            self.annotation_root = os.path.join(os.path.dirname(stripped), "annotations", self.mode)
+            if not os.path.isdir(self.annotation_root):
+                raise IOError("Annotation directory %s does not exist." % self.annotation_root)
         self.users, self.user2objs, self.obj2user, self.obj2name, self.obj2vids = [], {}, {}, {}, {}
-        self.video2id, self.vid2frames = {}, {}
+        self.video2id, self.vid2frames, self.vid2anns = {}, {}, {}
         self._index()
 
     # ---- directory index -------------------------------------------------------------------------------------------------
@@ -116,21 +180,57 @@ class ORBITDataset(torch.utils.data.Dataset):
             return {"context": clean, "target": sorted(os.listdir(os.path.join(obj_path, "clutter")))}
         return {"context": [], "target": []}
 
+    def annotation_path(self, video_path):
+        return os.path.join(self.annotation_root, os.path.basename(video_path) + ".json")
+
+    def _load_video_annotations(self, video_path):
+        path = self.annotation_path(video_path)
+        if not os.path.isfile(path):
+            raise FileNotFoundError("annotation file %s (of video %s) does not exist" % (path, video_path))
+        with open(path, "r") as f:
+            return json.load(f)
+
+    def _frame_annotations(self, frame_path):
+        video_path = os.path.dirname(frame_path)
+        try:
+            return self.vid2anns[video_path][os.path.basename(frame_path)]
+        except KeyError:
+            raise KeyError("frame %s is not listed in %s" % (os.path.basename(frame_path), self.annotation_path(video_path))) from None
+
+    def _filter_frames(self, frames, criteria):
+        """reference :243-256"""
+        criteria = set(criteria)
+        return [f for f in frames if frame_tags(self._frame_annotations(f)) & criteria]
+
     def _index(self):
         next_obj = next_vid = 0
+        # what the same walk keeps WITHOUT the filters (index_summary() reports the difference)
+        plain = dict.fromkeys(("users", "objects", "context_videos", "target_videos", "context_frames", "target_frames"), 0)
         for user in sorted(os.listdir(self.root)):
-            mine = []
+            mine, plain_objects = [], 0
             user_path = os.path.join(self.root, user)
             for obj_name in sorted(os.listdir(user_path)):
                 obj_path = os.path.join(user_path, obj_name)
                 kept, frames_of = {"context": [], "target": []}, {}
+                unfiltered = {"context": [], "target": []}  # frame counts of the videos the floors keep without a filter
                 for which, names in self._split_videos(obj_path).items():
                     for name in names:
                         vp = os.path.join(obj_path, self.video_type[which], name)
                         jpgs = glob.glob(os.path.join(vp, "*.jpg"))
                         if len(jpgs) >= MIN_FRAMES[which]:
+                            unfiltered[which].append(len(jpgs))
+                        if self.with_annotations or self.filter_criteria[which]:  # reference :169-173
+                            self.vid2anns[vp] = self._load_video_annotations(vp)
+                            if self.filter_criteria[which]:
+                                jpgs = self._filter_frames(jpgs, self.filter_criteria[which])
+                        if len(jpgs) >= MIN_FRAMES[which]:
                             kept[which].append(vp)
                             frames_of[vp] = sorted(jpgs)
+                if unfiltered["context"] and unfiltered["target"]:
+                    plain_objects += 1
+                    for which in ("context", "target"):
+                        plain[which + "_videos"] += len(unfiltered[which])
+                        plain[which + "_frames"] += sum(unfiltered[which])
                 if kept["context"] and kept["target"]:
                     mine.append(next_obj)
                     self.obj2user[next_obj], self.obj2name[next_obj], self.obj2vids[next_obj] = user, obj_name, kept
@@ -138,10 +238,22 @@ class ORBITDataset(torch.utils.data.Dataset):
                     for vp in kept["context"] + kept["target"]:
                         self.video2id[vp], self.vid2frames[vp] = next_vid, frames_of[vp]
                         next_vid += 1
+            plain["objects"] += plain_objects
+            plain["users"] += 1 if plain_objects else 0
             if mine:
                 self.users.append(user)
                 self.user2objs[user] = mine
         self.num_users, self.num_objects = len(self.users), len(self.obj2name)
+        self._unfiltered = plain
+
+    def index_summary(self):
+        """What the index keeps - users, objects, context / target videos and their frames - and what the annotation filters
+        dropped of what the same tree holds without them (None when no filter is active)."""
+        videos = {w: sum(len(v[w]) for v in self.obj2vids.values()) for w in ("context", "target")}
+        frames = {w: sum(len(self.vid2frames[vp]) for v in self.obj2vids.values() for vp in v[w]) for w in ("context", "target")}
+        kept = {"users": self.num_users, "objects": self.num_objects, "context_videos": videos["context"],
+                "target_videos": videos["target"], "context_frames": frames["context"], "target_frames": frames["target"]}
+        return {"kept": kept, "dropped": {k: self._unfiltered[k] - kept[k] for k in kept} if self.with_frame_filtering else None}
 
     def __len__(self):
         return self.num_users
@@ -205,6 +317,22 @@ class ORBITDataset(torch.utils.data.Dataset):
         f = self._normalise(u8)
         return f.reshape(len(paths), self.clip_length, *f.shape[1:])
 
+    def load_annotations(self, paths):
+        """clip paths [n, T] -> {annotation: float32 [n, 1, 1]}: the annotation of every clip's last frame (reference :393-420
+        at clip_length 1; at clip_length > 1 the reference raises, see the module docstring), true 1 / false 0 / null NaN"""
+        if not self.with_annotations:
+            return {}
+        paths = np.asarray(paths, dtype=object).reshape(-1, self.clip_length)
+        out = {a: torch.empty(len(paths), 1, 1, dtype=torch.float32) for a in self.annotations_to_load}
+        for i, clip in enumerate(paths):
+            anns = self._frame_annotations(clip[-1])
+            for a in self.annotations_to_load:
+                if a not in anns:
+                    raise KeyError("frame %s has no annotation %r in %s" % (os.path.basename(clip[-1]), a,
+                                                                            self.annotation_path(os.path.dirname(clip[-1]))))
+                out[a][i, 0, 0] = float("nan") if anns[a] is None else float(anns[a])
+        return out
+
     def _finish_set(self, paths, labels, video_ids, by_video):
         paths = np.array(paths) if len(paths) else np.empty((0, self.clip_length), dtype=object)
         labels = torch.tensor(labels)
@@ -213,7 +341,7 @@ class ORBITDataset(torch.utils.data.Dataset):
             self.rng.shuffle(order)       # the draws of the reference's random.shuffle over np.arange(n) (:517-518)
             order = np.array(order, dtype=np.int64)
             paths, labels = paths[order], labels[order]
-            return self.load_clips(paths), paths, labels, {}
+            return self.load_clips(paths), paths, labels, self.load_annotations(paths)  # ({} when nothing is loaded)
         video_ids = np.asarray(video_ids)
         frames_by_video, paths_by_video, labels_by_video, anns_by_video = [], [], [], []
         for vid in np.unique(video_ids):
@@ -223,7 +351,8 @@ class ORBITDataset(torch.utils.data.Dataset):
             frames_by_video.append(None if clips is None else clips.flatten(end_dim=1))
             paths_by_video.append(vp)
             labels_by_video.append(labels[torch.from_numpy(rows)][0])
-            anns_by_video.append(None)
+            anns_by_video.append({a: t.flatten(end_dim=1) for a, t in self.load_annotations(paths[rows]).items()}
+                                 if self.with_annotations else None)
         return frames_by_video, paths_by_video, labels_by_video, anns_by_video
 
     def sample_task(self, task_objects, task_id=None):

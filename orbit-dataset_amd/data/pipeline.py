@@ -27,7 +27,8 @@ the recogniser moves each mini-batch to the device on the compute stream (`model
                       CMYK ..) and files the device reports damaged are decoded by PIL as before; the count is reported.
 
 `write_synthetic_orbit_directory` builds a small JPEG tree in that layout (the ORBIT dataset itself is not available
-offline); it is test / benchmark scaffolding, not part of the path.
+offline) and `write_synthetic_orbit_annotations` its frame annotations from explicit per-video rules; they are test / benchmark
+scaffolding, not part of the path.
 """
 import ctypes
 import io
@@ -64,6 +65,53 @@ def write_synthetic_orbit_directory(root, users=2, objects_per_user=3, clean_vid
                         img.save(os.path.join(d, "%s-%05d.jpg" % (name, f + 1)), quality=quality)
                         n += 1
     return n
+
+
+def write_synthetic_orbit_annotations(split_root, absent=None, issues=None):
+    """The frame annotations of a written split, where the datasets look for them: dirname(split_root)/annotations/<split>/
+    <video>.json, one per video, keyed by frame file name, in the two formats of the ORBIT release - a clean video's frames
+    carry the seven quality issues (all but object_not_present_issue null where the object is absent), a clutter video's
+    frames a bounding box (null where the object is absent) and object_not_present_issue.
+
+    Explicit rules, no random draws: absent = {video name: frame positions (0-based, in sorted frame order) without the
+    object}, issues = {clean video name: {issue: frame positions that have it}}; every other value is false. Returns the
+    annotation directory."""
+    import json
+    from .datasets import FRAME_ANNOTATION_OPTIONS
+    absent = {k: set(v) for k, v in (absent or {}).items()}
+    issues = {k: {i: set(f) for i, f in v.items()} for k, v in (issues or {}).items()}
+    split_root = split_root.rstrip(os.sep) or split_root
+    out = os.path.join(os.path.dirname(split_root), "annotations", os.path.basename(split_root))
+    os.makedirs(out, exist_ok=True)
+    seen = set()
+    for user in sorted(os.listdir(split_root)):
+        for obj in sorted(os.listdir(os.path.join(split_root, user))):
+            for kind in ("clean", "clutter"):
+                kind_dir = os.path.join(split_root, user, obj, kind)
+                for video in sorted(os.listdir(kind_dir)) if os.path.isdir(kind_dir) else ():
+                    seen.add(video)
+                    if kind == "clutter" and video in issues:
+                        raise ValueError("quality issues are annotated on clean videos only, %s is a clutter video" % video)
+                    unknown = set(issues.get(video, {})) - set(FRAME_ANNOTATION_OPTIONS[1:])
+                    if unknown:
+                        raise ValueError("unknown quality issues %s for %s" % (sorted(unknown), video))
+                    frames = sorted(f for f in os.listdir(os.path.join(kind_dir, video)) if f.endswith(".jpg"))
+                    anns = {}
+                    for k, frame in enumerate(frames):
+                        gone = k in absent.get(video, ())
+                        if kind == "clean":
+                            anns[frame] = {"object_not_present_issue": gone}
+                            for issue in FRAME_ANNOTATION_OPTIONS[1:]:
+                                anns[frame][issue] = None if gone else k in issues.get(video, {}).get(issue, ())
+                        else:
+                            box = None if gone else {"x": 270 + k % 7, "y": 300 + k % 5, "w": 400, "h": 360}
+                            anns[frame] = {"object_bounding_box": box, "object_not_present_issue": gone}
+                    with open(os.path.join(out, video + ".json"), "w") as f:
+                        json.dump(anns, f)
+    unknown = (set(absent) | set(issues)) - seen
+    if unknown:
+        raise ValueError("rules for videos that are not under %s: %s" % (split_root, sorted(unknown)))
+    return out
 
 
 class ORBITDirectory:
@@ -369,7 +417,9 @@ class DatasetTaskSource:
     """Host tasks from a data/datasets.py dataset built with frames="uint8" - or frames="jpeg": JpegFrames for the device decoder - (the reference-pinned sampler: way, video and clip
     sampling of reference data/datasets.py:289-336,433-469,540-598), in the layout TaskPrefetcher uploads:
     context_clips u8 [N,T,H,W,3]; a test-mode target set (a list of videos) is concatenated into target_clips u8 [M,1,H,W,3]
-    with `target_videos` = [(lo, hi)] row ranges and one label per frame; a train-mode target set passes through as clips."""
+    with `target_videos` = [(lo, hi)] row ranges and one label per frame; a train-mode target set passes through as clips.
+    Frame annotations ride along as host tensors: `context_annotations` as sampled, `target_annotations` of a test-mode target
+    set as ONE dict of [M, 1] tensors in the row order of target_clips ({} when nothing is loaded)."""
 
     def __init__(self, dataset, indices=None):
         if dataset.frames not in ("uint8", "jpeg"):
@@ -384,7 +434,8 @@ class DatasetTaskSource:
         for i in self.indices:
             t = self.dataset[i]
             out = {"context_clips": t["context_clips"], "context_labels": t["context_labels"], "context_paths": t["context_paths"],
-                   "object_list": t["object_list"], "task_id": t["task_id"], "user": t["task_id"]}
+                   "object_list": t["object_list"], "task_id": t["task_id"], "user": t["task_id"],
+                   "context_annotations": t["context_annotations"]}
             if isinstance(t["target_clips"], list):
                 ranges, lo = [], 0
                 for frames in t["target_clips"]:
@@ -395,8 +446,11 @@ class DatasetTaskSource:
                 out["target_labels"] = torch.cat([lab.reshape(1).expand(hi - lo) for lab, (lo, hi) in
                                                   zip(t["target_labels"], ranges)]) if ranges else torch.empty(0, dtype=torch.int64)
                 out["target_videos"], out["target_paths"] = ranges, t["target_paths"]
+                per_video = [a for a in t["target_annotations"] if a is not None]
+                out["target_annotations"] = {k: torch.cat([a[k] for a in per_video]) for k in (per_video[0] if per_video else ())}
             else:
                 out["target_clips"], out["target_labels"], out["target_paths"] = t["target_clips"], t["target_labels"], t["target_paths"]
+                out["target_annotations"] = t["target_annotations"]
             yield out
 
 
@@ -413,7 +467,7 @@ class TaskPrefetcher:
     """Iterate over `source` (host tasks whose `*_clips` are uint8, channels last [..., H, W, 3] or channels first
     [..., 3, H, W] - or already-normalised float32 [..., 3, H, W], the reference's layout); yields the same dicts with the
     clips replaced by normalised fp32 [..., 3, H, W] tensors RESIDENT on `device`. Every other entry passes through (label
-    tensors are moved to the device).
+    tensors are moved to the device; the `*_annotations` dicts stay on the host, as the reference's unpack_task leaves them).
 
     A staging thread fills pinned slot buffers and issues, on a copy stream, the 8-bit upload and the normalisation kernel of
     task i+1 (and i+2 with depth 3) while the caller's stream runs the extractor on task i. The yielded tensors belong to the

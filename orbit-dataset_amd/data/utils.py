@@ -114,6 +114,8 @@ def attach_frame_history(frames, history_length):
 
 
 def unpack_task(task_dict, device, context_to_device=True, target_to_device=False):
+    """reference data/utils.py:30-47. `context_annotations` / `target_annotations` may be present, as in the reference's
+    task_dict: like there they are neither moved nor returned (a caller that wants them reads them from the dict)."""
     context_labels = task_dict["context_labels"]
     target_labels = task_dict["target_labels"]
     if context_to_device and isinstance(context_labels, torch.Tensor):

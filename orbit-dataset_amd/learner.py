@@ -19,7 +19,10 @@ rotation of the reference loop are not part of the hot path and are left out.
 On a dataset tree (--data_path ROOT, the reference's flag; --data_root DIR for the test loop alone) all three loops take
 their tasks from the reference-pinned sampler (data/datasets.py) in the reference's queue order (task_order) through the
 input pipeline (data/pipeline.TaskPrefetcher: decode, 8-bit or compressed upload, resize and normalisation on a copy
-stream): train on ROOT/train, validate on ROOT/validation, test - the finetuner too - on ROOT/<--test_set>.
+stream): train on ROOT/train, validate on ROOT/validation, test - the finetuner too - on ROOT/<--test_set>. The reference's
+five annotation flags hold there (utils/args.py:79-88): --train_filter_* on the train split, --test_filter_* on the
+validation and test splits, --annotations_to_load on all three; the filters act when the tree is indexed, so a dropped
+frame is never read. `--test_filter_target no_object_not_present_issue` is the benchmark's clutter-video protocol (CLU-VE).
 
 Multi-GPU: launched under torchrun, tasks are dealt round-robin to ranks (task i -> rank i % world). Test mode has no
 data-path collective (per-task statistics are all-gathered at the end). Training all-reduces (SUM, RCCL) one flat
@@ -41,6 +44,7 @@ import torch
 
 from . import dist as odist
 from . import synthetic
+from .data.datasets import ALL_FRAME_ANNOTATION_OPTIONS, BOUNDING_BOX_OPTIONS, FRAME_ANNOTATION_OPTIONS, expand_issues
 from .data.utils import attach_frame_history, unpack_task
 from .model.feature_extractors import EXTRACTORS
 from .model.few_shot_recognisers import SingleStepFewShotRecogniser
@@ -173,7 +177,37 @@ def build_parser():
                    help="with --data_root / --data_path: tasks sampled per test user (reference --num_test_tasks, utils/args.py)")
     p.add_argument("--num_workers", type=int, default=4, help="decode threads (reference data/queues.py:34: 4 in test mode)")
     p.add_argument("--frame_norm_method", default="imagenet", choices=["imagenet", "imagenet_inception", "openai_clip"])
+    # frame annotations (reference utils/args.py:79-88), with --data_path / --data_root: ROOT/annotations/<split>/<video>.json
+    p.add_argument("--annotations_to_load", nargs="+", default=[], choices=FRAME_ANNOTATION_OPTIONS + BOUNDING_BOX_OPTIONS,
+                   help="annotations to load per frame: every task carries them as host tensors (context_annotations / "
+                        "target_annotations; object_bounding_box is not built)")
+    for split, role in (("train", "train"), ("test", "validation / test")):
+        for which in ("context", "target"):
+            p.add_argument("--%s_filter_%s" % (split, which), nargs="+", default=[], choices=ALL_FRAME_ANNOTATION_OPTIONS,
+                           help="keep only the %s frames of %s tasks that carry one of these annotations (no_<issue>: the issue "
+                                "is annotated false; no_issues / mixed_issues: all seven no_<issue> / <issue> names). "
+                                "--test_filter_target no_object_not_present_issue is the benchmark's CLU-VE rule" % (which, role))
     return p
+
+
+ANNOTATION_FLAGS = ("annotations_to_load", "train_filter_context", "train_filter_target", "test_filter_context", "test_filter_target")
+
+
+def expand_annotation_args(args):
+    """reference utils/args.py:181-184, after parsing: no_issues / mixed_issues in the four filter flags become the seven
+    names they stand for (data/datasets.expand_issues). Idempotent; flags an args object lacks are set to []. Returns args."""
+    args.annotations_to_load = list(getattr(args, "annotations_to_load", None) or [])
+    for flag in ANNOTATION_FLAGS[1:]:
+        setattr(args, flag, expand_issues(getattr(args, flag, None) or []))
+    return args
+
+
+def split_annotation_args(args, split):
+    """-> (annotations_to_load, (filter_context, filter_target)) of a split's dataset, as reference data/dataloaders.py:29-30,
+    48-49,66-67 passes them: the train pair to the train split, the test pair to the validation and test splits"""
+    expand_annotation_args(args)
+    side = "train" if split == "train" else "test"
+    return args.annotations_to_load, (getattr(args, side + "_filter_context"), getattr(args, side + "_filter_target"))
 
 
 # The extractors whose network is frozen unless a flag opts in: the frame normalisation the reference sets for them
@@ -239,7 +273,8 @@ def split_rng(args, split, rank=0):
 def build_split_dataset(args, split, root, frames="uint8", rank=0, decode_pool=None):
     """The reference's queue datasets (data/dataloaders.py:15-70 -> data/queues.py) on `root`: "train" samples with the
     --train_* flags in train mode (clips and labels shuffled), user- or object-centric; "validation" and "test" with the
-    --test_* flags in test mode (target frames grouped by video), user-centric."""
+    --test_* flags in test mode (target frames grouped by video), user-centric. --annotations_to_load goes to every split,
+    the --train_filter_* pair to "train" and the --test_filter_* pair to "validation" and "test"."""
     from .data.datasets import ObjectEpisodicORBITDataset, UserEpisodicORBITDataset
     a = args
     if split not in ("train", "validation", "test"):
@@ -251,8 +286,9 @@ def build_split_dataset(args, split, root, frames="uint8", rank=0, decode_pool=N
          (a.train_context_clip_method, a.train_target_clip_method)) if train else
         (a.test_way_method, a.test_object_cap, (a.test_context_shot_method, a.test_target_shot_method),
          (a.test_context_clip_method, a.test_target_clip_method)))
+    to_load, filters = split_annotation_args(a, split)
     return cls(root, way, cap, shot_methods, (a.context_shot, a.target_shot), (a.context_video_type, a.target_video_type),
-               a.subsample_factor, clip_methods, a.clip_length, a.frame_size, a.frame_norm_method, [], ([], []), not train, False,
+               a.subsample_factor, clip_methods, a.clip_length, a.frame_size, a.frame_norm_method, to_load, filters, not train, False,
                bool(train and a.with_train_shot_caps), None, frames=frames, rng=split_rng(a, split, rank), decode_pool=decode_pool)
 
 
@@ -271,6 +307,13 @@ def verify_args(args):
         sys.exit("error: at least one of --learn_extractor and --adapt_features must be used when training")
     if args.frame_size % 1 or args.frame_size < 32:
         sys.exit("error: --frame_size must be >= 32")
+    expand_annotation_args(args)
+    given = ["--" + f for f in ANNOTATION_FLAGS if getattr(args, f)]
+    if given and not (getattr(args, "data_path", None) or getattr(args, "data_root", None)):
+        sys.exit("error: %s need a dataset tree (--data_path / --data_root): synthetic tasks have no frame annotations "
+                 "(DESIGN.md §1)" % ", ".join(given))
+    if "object_bounding_box" in args.annotations_to_load:
+        sys.exit("error: --annotations_to_load object_bounding_box is not built (DESIGN.md §8)")
     for split, path in split_roots(args).items():  # (exits when both --data_path and --data_root are given)
         if getattr(args, "data_path", None) and not os.path.isdir(path):
             sys.exit("error: --data_path %s: --mode %s needs the %s split, and %s is not a directory"
@@ -529,7 +572,18 @@ class Learner:
                 a, "data_root", None) else " without --data_path", split))
         if frames is None:
             frames = "jpeg" if a.decode == "device" else "uint8"
-        return build_split_dataset(a, split, root, frames, self.rank, None if frames == "paths" else self.decode_pool())
+        dataset = build_split_dataset(a, split, root, frames, self.rank, None if frames == "paths" else self.decode_pool())
+        if getattr(self, "_split_index", None) is None:
+            self._split_index = {}
+        self._split_index[split] = dataset.index_summary()
+        return dataset
+
+    def annotation_stats(self, split):
+        """the annotation side of a split's results: the flags as expanded, and what the index kept and the filters dropped
+        (data/datasets.index_summary; None on synthetic tasks)"""
+        to_load, (context, target) = split_annotation_args(self.args, split)
+        return {"filter_context": list(context), "filter_target": list(target), "annotations_to_load": list(to_load),
+                "index": (getattr(self, "_split_index", None) or {}).get(split)}
 
     def train_order(self, epoch):
         """this rank's item indices (users; objects when object-centric) of train epoch `epoch`, in the order it trains on them:
@@ -673,6 +727,8 @@ class Learner:
                       "train_task_type": a.train_task_type if tree is not None else None,
                       "data_wait_ms": mean_ci(waits) if waits else None,
                       "frames_per_task": mean_ci(task_frames) if task_frames else None, "wall_s": wall})
+        stats.update(self.annotation_stats("train"))
+        stats["validation_annotations"] = self.annotation_stats("validation") if split_roots(a).get("validation") else None
         if self.rank == 0:
             print("train: loss %.5f | frame_acc %.2f %% | %.1f ms/task | %d tasks on this rank, %d GPU(s)"
                   % (stats["loss"][0], 100 * stats["frame_acc"][0], stats["ms_per_task"][0], stats["num_tasks"],
@@ -822,10 +878,18 @@ class Learner:
                  "stored_frame_size": [list(hw) for hw in stored], "frame_size": [a.frame_size, a.frame_size],
                  "resample": a.resample if any(hw != (a.frame_size, a.frame_size) for hw in stored) else None,
                  "decode": a.decode, "decode_fallback_frames": prefetch.fallback_frames if a.decode == "device" else None}
+        stats.update(self.annotation_stats("test"))
         if self.rank == 0:
             print("test (%s): frames stored at %s, extractor ran at %dx%d%s"
                   % (root, ", ".join("%dx%d" % hw for hw in stored) or "-", a.frame_size, a.frame_size,
                      " (resized on the GPU, %s)" % a.resample if stats["resample"] else ""))
+            if stats["index"]["dropped"] is not None:
+                kept, dropped = stats["index"]["kept"], stats["index"]["dropped"]
+                print("test (%s): context frames filtered by %s, target frames by %s: kept %d users, %d objects, %d + %d videos, "
+                      "%d + %d frames; dropped %d users, %d objects, %d + %d videos, %d + %d frames"
+                      % (root, stats["filter_context"] or "-", stats["filter_target"] or "-",
+                         *(d[k] for d in (kept, dropped) for k in ("users", "objects", "context_videos", "target_videos",
+                                                                   "context_frames", "target_frames"))))
             if a.decode == "device":
                 print("test (%s): JPEG decode on the GPU, %d frames; %d decoded by PIL instead (out of scope or damaged)"
                       % (root, prefetch.device_frames, prefetch.fallback_frames))

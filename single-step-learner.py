@@ -5,6 +5,9 @@ MI355X-native recogniser on synthetic ORBIT-shaped tasks. See orbit-dataset_amd/
     python single-step-learner.py --mode test --feature_extractor efficientnet_b0 --classifier proto \
         --frame_size 224 --batch_size 256 --num_test_tasks 8
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 single-step-learner.py --mode test ...
+    # the benchmark's clutter-video evaluation on a dataset tree: frames without the object are filtered out first
+    python single-step-learner.py --mode test --feature_extractor resnet18 --data_path ROOT \
+        --test_filter_target no_object_not_present_issue
 """
 import os
 import sys
