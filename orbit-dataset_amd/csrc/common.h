@@ -60,22 +60,27 @@ static inline FastDiv make_fastdiv(unsigned d) {
 }
 __device__ __forceinline__ unsigned fdiv(unsigned n, FastDiv f) { return (__umulhi(n, f.mul) + n) >> f.shift; }
 
-struct ConvDesc {
-    const float* x;         // NHWC activations, or NCHW frames when x_nchw
-    const float* w_packed;  // [CoutPad][KT], K = (kh, kw, ci) with ci fastest, zero padded
+// The geometry of one layer as a value: what every launcher and sizing function of a conv / depthwise / pooling layer takes
+// (depthwise layers: Cin = channels, KH = K; max-pool: Cin = channels, KH = window, pad_t = padding)
+struct LayerGeom {
+    int B = 0, H = 0, W = 0, Cin = 0, Cout = 0, KH = 1, KW = 1, stride = 1, pad_t = 0, pad_l = 0, Ho = 0, Wo = 0;
+};
+struct ConvDesc : LayerGeom {
+    LayerGeom& geom() { return *this; }
+    const float* x = nullptr;         // NHWC activations, or NCHW frames when x_nchw
+    const float* w_packed = nullptr;  // [CoutPad][KT], K = (kh, kw, ci) with ci fastest, zero padded
     const float* w_frag = nullptr;  // the same filter in MFMA-fragment order (conv_frag_floats / conv_frag_pack_weights) or
                                     // nullptr: pointwise convs then stay on the LDS-tiled kernel (csrc/pw_rgemm.hip)
-    float* y;               // NHWC
-    const float* scale;     // [Cout] or nullptr
-    const float* shift;     // [Cout] or nullptr
-    const float* residual;  // NHWC like y or nullptr
+    float* y = nullptr;               // NHWC
+    const float* scale = nullptr;     // [Cout] or nullptr
+    const float* shift = nullptr;     // [Cout] or nullptr
+    const float* residual = nullptr;  // NHWC like y or nullptr
     int res_post = 0;       // the residual joins AFTER the activation: y = act(conv * scale + shift) + residual (timm ConvBnAct);
                             // a compile-time form of the K x K NHWC kernel (csrc/conv_igemm.hip), refused for every other conv
-    const float* gate;      // [B][Cin] or nullptr
-    int B, H, W, Cin, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo;
-    int act;     // ORBIT_ACT_*
-    int pool2;   // fused 2x2/2 max-pool of the activated output
-    int x_nchw;  // stem gather from NCHW frames
+    const float* gate = nullptr;      // [B][Cin] or nullptr
+    int act = ORBIT_ACT_NONE;  // ORBIT_ACT_*
+    int pool2 = 0;             // fused 2x2/2 max-pool of the activated output
+    int x_nchw = 0;            // stem gather from NCHW frames
     float prof_flop_scale = 1.f;  // algorithmic / executed flops (strided dgrad runs on the zero-inserted grid)
     float* splitk_ws = nullptr;   // scratch for split-K partial tiles (conv_splitk_floats(d) floats) or nullptr: no split
     // train-mode BatchNorm statistics from the epilogue (the LITE step, csrc/extractor_train.hip): every block of output
@@ -218,14 +223,19 @@ enum DwForm { DW_STREAM, DW_PIPE, DW_WINDOW, DW_LDS };
 DwForm dw_form_rule(int K, int stride, int Ho, bool train_form, bool lds_fits = true);
 // depthwise + fused SE pooling partials [B][chunks][C] (pool_partial may be nullptr); chunks = dwconv_se_chunks(Ho)
 int dwconv_se_chunks(int Ho);
+// Input transform of the depthwise kernels: x is the RAW output y of the producing convolution and act(y * scale[c] + shift[c])
+// - that layer's BatchNorm + activation - is applied as the kernel loads it (csrc/ops.hip). Default: none.
+struct DwInXf {
+    const float *scale = nullptr, *shift = nullptr;
+    int act = ORBIT_ACT_NONE;
+};
 int launch_dwconv_se(const float* x, const float* w_khwc, float* y, const float* scale, const float* shift,
-                     float* pool_partial, int B, int H, int W, int C, int K, int stride, int pad_t, int pad_l, int Ho,
-                     int Wo, int act, hipStream_t s, int stats = 0, const float* in_scale = nullptr,
-                     const float* in_shift = nullptr, int in_act = 0, const DwBnBwd* bnb = nullptr);
+                     float* pool_partial, const LayerGeom& g, int act, hipStream_t s, int stats = 0, const DwInXf& in = {},
+                     const DwBnBwd* bnb = nullptr);
 // (bnb: the data-gradient use of these kernels - rotated taps, no scale / shift / activation, no pooling - with the
 // BatchNorm-backward epilogue above; *bnb->nblk tells whether the chosen kernel family had it)
-// in_scale / in_shift (with stats): x is the RAW output of the producing conv; act(x * in_scale[c] + in_shift[c]) is applied
-// as the kernel loads it, so the activated tensor of that layer is never written (no-backward passes of the LITE step)
+// in (with stats): x is the RAW output of the producing conv, so the activated tensor of that layer is never written
+// (no-backward passes of the LITE step)
 // stats != 0: pool_partial receives [B * dwconv_se_chunks(Ho)][2][C] column sums / sums of squares of the outputs instead
 // (train-mode BatchNorm statistics from the producing kernel; the partial layout bn_stats_finalize reads)
 int launch_se_gate2(const float* partial, int chunks, int HW, const float* w1, const float* b1, const float* w2t,
@@ -258,8 +268,7 @@ int launch_stem_rows(const float* frames, const float* w1_packed, const float* s
 int stem_pack_weights(const float* w_oihw, float* w_packed, int mid, hipStream_t s);  // [mid][27] -> [mid][32]
 // [C][1][K][K] -> [K][K][C]
 int dwconv_pack_weights(const float* w, float* w_khwc, int C, int K, hipStream_t s);
-int launch_maxpool(const float* x, float* y, int B, int H, int W, int C, int K, int stride, int pad,
-                   int Ho, int Wo, hipStream_t s);
+int launch_maxpool(const float* x, float* y, const LayerGeom& g, hipStream_t s);
 int launch_avgpool(const float* x, float* y, int B, int HW, int C, hipStream_t s);
 int launch_se_gate(const float* pooled, const float* w1, const float* b1, const float* w2,
                    const float* b2, float* gate, int B, int C, int R, hipStream_t s);
@@ -294,30 +303,34 @@ int launch_scale_shift_act_pool(const float* y, const float* scale, const float*
 int launch_bn_backward(const float* dout, const float* out, const float* y, const BnFoldC& bn, const BnGrads& p, int train,
                        int act, int M, int C, float* dy, float* dres, int dres_accumulate, float* partial, float* coef,
                        hipStream_t s, int res_post = 0);
-int launch_maxpool_idx(const float* x, float* y, uint8_t* idx, int B, int H, int W, int C, int K, int stride, int pad,
-                       int Ho, int Wo, hipStream_t s);
-int launch_maxpool_bwd(const float* dy, const uint8_t* idx, float* dx, int B, int H, int W, int C, int K, int stride,
-                       int pad, int Ho, int Wo, hipStream_t s);
+int launch_maxpool_idx(const float* x, float* y, uint8_t* idx, const LayerGeom& g, hipStream_t s);
+int launch_maxpool_bwd(const float* dy, const uint8_t* idx, float* dx, const LayerGeom& g, hipStream_t s);
 int launch_avgpool_bwd(const float* dy, float* dx, int B, int HW, int C, hipStream_t s);
 int launch_upsample_zero(const float* src, float* dst, int B, int H, int W, int C, int stride, int Hs, int Ws,
                          hipStream_t s);
 // MBConv pieces (train_mbconv.hip)
 int launch_colmean(const float* x, float* pooled, int B, int HW, int C, hipStream_t s);  // [B][HW][C] -> means [B][C]
 size_t se_bwd_scratch_floats(int B, int C, int R);
-// dxg: gradient of x*gate; writes dx (through the product, the gate MLP and the average pool) and, when dw1 != NULL, the
-// gradients of the four SE tensors (W1 [R][C], b1 [R], W2 [C][R], b2 [C])
+// dxg: gradient of x*gate; writes dx (through the product, the gate MLP and the average pool) and, when dparams != NULL, the
+// gradients of the four SE tensors
 // bn (optional): x = act(BatchNorm(y)); then `dx` receives g = d x * act'(.) instead of d x and bn->partial the per-(frame,
 // chunk) sums of g and g * xhat ([B * se_pool_chunks(B, HW, C)][2][C]): launch_bn_backward_reduced finishes that BatchNorm's
 // backward without a reduction pass of its own
 using SeBnFuse = BnTaped;
-int launch_se_gate_backward(const float* dxg, const float* x, const float* pooled, const float* gate, const float* w1,
-                            const float* b1, const float* w2, const float* b2, float* dx, float* dw1, float* db1,
-                            float* dw2, float* db2, float* scratch, int B, int HW, int C, int R, hipStream_t s,
-                            const SeBnFuse* bn = nullptr, const float* w2t = nullptr);
+struct SeWeights {  // a block's gate MLP: W1 [R][C], b1 [R], W2 [C][R], b2 [C]
+    const float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
+    const float* w2t = nullptr;  // optional: W2 transposed to [R][C] - the plan's packed copy; the MLP backward then reads W2 contiguously
+};
+struct SeGrads {  // where their gradients go
+    float *dw1 = nullptr, *db1 = nullptr, *dw2 = nullptr, *db2 = nullptr;
+};
+int launch_se_gate_backward(const float* dxg, const float* x, const float* pooled, const float* gate, const SeWeights& w,
+                            float* dx, const SeGrads* dparams, float* scratch, int B, int HW, int C, int R, hipStream_t s,
+                            const SeBnFuse* bn = nullptr);
 // With bn, dx may be nullptr: g is then NOT written (one pass over the expanded tensor less); the BatchNorm's apply pass
 // rebuilds it from dxg, the gate and the pooled-branch gradient the MLP backward left in `scratch` (se_bwd_dpooled):
 const float* se_bwd_dpooled(const float* scratch, int B, int C, int R);
-// The parameter gradients of several squeeze-excite blocks in one launch: call launch_se_gate_backward with dw1 = nullptr
+// The parameter gradients of several squeeze-excite blocks in one launch: call launch_se_gate_backward with dparams = nullptr
 // and a scratch of the block's own, keep se_bwd_param_job(scratch, ...) and run the batch when all blocks are through.
 // (more blocks than SE_PARAM_JOBS: run the batch when the list is full and go on - each block's scratch is its own)
 constexpr int SE_PARAM_JOBS = 16;
@@ -330,37 +343,33 @@ struct SeParamJob {
 struct SeParamJobs {
     SeParamJob j[SE_PARAM_JOBS];
 };
-SeParamJob se_bwd_param_job(const float* scratch, const float* pooled, int B, int C, int R, float* dw1, float* db1, float* dw2,
-                            float* db2);
+SeParamJob se_bwd_param_job(const float* scratch, const float* pooled, int B, int C, int R, const SeGrads& dparams);
 int launch_se_param_grad_batched(const SeParamJobs& jobs, int n, hipStream_t s);
 // t: the layer (y, fold view, act) and t.partial = the [nblk][2][C] sums the squeeze-excite backward left
 int launch_bn_backward_reduced_gated(const float* dxg, const float* gate, const float* dpooled, int HW, const BnTaped& t,
                                      const BnGrads& p, int train, int M, int C, float* dy, int nblk, float* coef, hipStream_t s);
-// (w2t, optional: W2 transposed to [R][C] - the plan's packed copy; the MLP backward then reads W2 contiguously)
 // BatchNorm backward whose reduction pass already ran (g = dout * act'(.) in `g`, [nblk][2][C] sums of g and g * xhat in
 // `partial`): finalize + apply only. coef: 3*C floats
 int launch_bn_backward_reduced(const float* g, const float* y, const BnFoldC& bn, const BnGrads& p, int train, int M, int C,
                                float* dy, float* partial, int nblk, float* coef, hipStream_t s);
 // flip_scratch (K*K*C floats, optional): stride-1 layers then run as a FORWARD depthwise convolution of dy with the flipped
 // taps through the LDS-patch kernels of csrc/ops.hip instead of the per-pixel gather
-int launch_dwconv_dgrad(const float* dy, const float* w_khwc, float* dx, int B, int H, int W, int C, int K, int stride,
-                        int pad_t, int pad_l, int Ho, int Wo, hipStream_t s, float* flip_scratch = nullptr,
-                        const DwBnBwd* bnb = nullptr);
-int dwconv_dgrad_bn_blocks(int B, int H, int W, int C, int stride);  // upper bound of the partial rows a fused dgrad writes
+int launch_dwconv_dgrad(const float* dy, const float* w_khwc, float* dx, const LayerGeom& g, hipStream_t s,
+                        float* flip_scratch = nullptr, const DwBnBwd* bnb = nullptr);
+int dwconv_dgrad_bn_blocks(const LayerGeom& g);  // upper bound of the partial rows a fused dgrad writes (reads B, H, W, Cin, stride)
 // scratch of a data gradient that carries the filter gradient (0: no fused form for the layer): the flipped taps of the stride-1
 // form in the first dwconv_bwd_fused_partial_offset floats, DwBnBwd::wgrad_partial behind them
-size_t dwconv_bwd_fused_scratch_floats(int B, int H, int W, int C, int K, int stride);
+size_t dwconv_bwd_fused_scratch_floats(const LayerGeom& g);
 size_t dwconv_bwd_fused_partial_offset(int C, int K);
 bool dwconv_se_window_form(int K, int stride, int Ho);
 int launch_dwconv_wgrad_reduce(const float* partial, int rows, int K, int C, float* dw, hipStream_t s);
-size_t dwconv_wgrad_scratch_floats(int B, int Ho, int Wo, int C, int K);
-int launch_dwconv_wgrad(const float* x, const float* dy, float* dw, float* scratch, int B, int H, int W, int C, int K,
-                        int stride, int pad_t, int pad_l, int Ho, int Wo, hipStream_t s, const float* in_scale = nullptr,
-                        const float* in_shift = nullptr, int in_act = 0);
-// (in_scale / in_shift: x is the RAW output of the producing conv; act(x * in_scale[c] + in_shift[c]) is applied as the patch is
-// staged in LDS - only where dwconv_wgrad_xf_supported says the LDS form fits the layer)
-bool dwconv_wgrad_xf_supported(int B, int H, int W, int C, int K, int stride, int Ho, int Wo);
-size_t conv_wgrad_scratch_floats(int B, int Cin, int Cout, int KH, int KW, int Ho, int Wo);
+size_t dwconv_wgrad_scratch_floats(const LayerGeom& g);
+int launch_dwconv_wgrad(const float* x, const float* dy, float* dw, float* scratch, const LayerGeom& g, hipStream_t s,
+                        const DwInXf& in = {});
+// (in: x is the RAW output of the producing conv; the transform is applied as the patch is staged in LDS - only where
+// dwconv_wgrad_xf_supported says the LDS form fits the layer)
+bool dwconv_wgrad_xf_supported(const LayerGeom& g);
+size_t conv_wgrad_scratch_floats(const LayerGeom& g);
 // The split reduction of several filter gradients in ONE launch: launch_conv_wgrad with `defer` fills a job instead of
 // running its reduce (the layer's partial tiles must then stay in `scratch` until launch_conv_wgrad_reduce_batched has run).
 constexpr int WGRAD_REDUCE_JOBS = 48;
@@ -375,13 +384,11 @@ struct WgradReduceJobs {
     int n;
 };
 int launch_conv_wgrad_reduce_batched(WgradReduceJobs& jobs, int n, hipStream_t s);
-int launch_conv_wgrad(const float* x, int x_nchw, const float* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout,
-                      int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, float* scratch, hipStream_t s,
+int launch_conv_wgrad(const float* x, int x_nchw, const float* dy, float* dw_oihw, const LayerGeom& g, float* scratch, hipStream_t s,
                       const float* gate = nullptr, WgradReduceJob* defer = nullptr);  // gate [B][Cin]: the filter gradient w.r.t. x * gate without materialising it
 size_t conv_dgrad_packed_floats(int Cin, int Cout, int KH, int KW);
 int conv_pack_dgrad_weights(const float* w_oihw, float* w_packed, int Cin, int Cout, int KH, int KW, hipStream_t s);
-int launch_conv_dgrad(const float* dy, const float* w_dgrad_packed, const float* accumulate, float* dx, float* up, int B,
-                      int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo,
-                      hipStream_t s);
+int launch_conv_dgrad(const float* dy, const float* w_dgrad_packed, const float* accumulate, float* dx, float* up,
+                      const LayerGeom& g, hipStream_t s);
 
 }  // namespace orbit

@@ -827,9 +827,8 @@ int orbit_op_conv2d_train(const float* x, int x_nchw, const float* w, float* y, 
     int rc = conv_pack_weights(w, tmp, Cin, Cout, KH, KW, x_nchw, s);
     if (rc == ORBIT_OK) {
         ConvDesc d;
-        d.x = x, d.w_packed = tmp, d.y = y, d.scale = d.shift = d.residual = nullptr, d.gate = gate;
-        d.B = B, d.H = H, d.W = W, d.Cin = Cin, d.Cout = Cout, d.KH = KH, d.KW = KW, d.stride = stride;
-        d.pad_t = pad_top, d.pad_l = pad_left, d.Ho = Ho, d.Wo = Wo, d.act = ORBIT_ACT_NONE, d.pool2 = 0, d.x_nchw = x_nchw;
+        d.x = x, d.w_packed = tmp, d.y = y, d.gate = gate, d.x_nchw = x_nchw;
+        d.geom() = LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
         d.stats = part, d.stats_blocks = stat_blocks;
         rc = launch_conv(d, s);
         if (rc == ORBIT_OK && *stat_blocks > 0) rc = launch_sum_partials(part, *stat_blocks, Cout, stats, s);
@@ -864,9 +863,8 @@ int orbit_op_conv2d_ex(const float* x, int x_nchw, const float* w, float* y, con
         ConvDesc d;
         d.w_frag = ffl ? wp + nfl : nullptr;
         d.x = x, d.w_packed = wp, d.y = y, d.scale = scale, d.shift = shift, d.residual = residual;
-        d.gate = gate, d.B = B, d.H = H, d.W = W, d.Cin = Cin, d.Cout = Cout, d.KH = KH, d.KW = KW;
-        d.stride = stride, d.pad_t = pad_top, d.pad_l = pad_left, d.Ho = Ho, d.Wo = Wo, d.act = act;
-        d.pool2 = pool2, d.x_nchw = x_nchw, d.res_post = (flags & ORBIT_CONV_RESIDUAL_POST_ACT) ? 1 : 0;
+        d.geom() = LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
+        d.gate = gate, d.act = act, d.pool2 = pool2, d.x_nchw = x_nchw, d.res_post = (flags & ORBIT_CONV_RESIDUAL_POST_ACT) ? 1 : 0;
         float* sk = nullptr;
         const size_t skf = conv_splitk_floats(d);
         if (skf) ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&sk), skf * sizeof(float), s));

@@ -385,7 +385,8 @@ static void wgrad_geometry(int M, int Cout, int NC, int& co_tiles, int& n_tiles,
     splits = cdiv(total_steps, steps_per_split);
 }
 
-size_t conv_wgrad_scratch_floats(int B, int Cin, int Cout, int KH, int KW, int Ho, int Wo) {
+size_t conv_wgrad_scratch_floats(const LayerGeom& g) {
+    const int B = g.B, Cin = g.Cin, Cout = g.Cout, KH = g.KH, KW = g.KW, Ho = g.Ho, Wo = g.Wo;
     int ct, nt, sp, sps;
     const int NC = KH * KW * Cin;
     wgrad_geometry(B * Ho * Wo, Cout, NC, ct, nt, sp, sps);
@@ -408,9 +409,10 @@ int launch_conv_wgrad_reduce_batched(WgradReduceJobs& jobs, int n, hipStream_t s
     return ORBIT_OK;
 }
 
-int launch_conv_wgrad(const float* x, int x_nchw, const float* dy, float* dw_oihw, int B, int H, int W, int Cin, int Cout,
-                      int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, float* scratch, hipStream_t s,
+int launch_conv_wgrad(const float* x, int x_nchw, const float* dy, float* dw_oihw, const LayerGeom& g, float* scratch, hipStream_t s,
                       const float* gate, WgradReduceJob* defer) {
+    const int B = g.B, H = g.H, W = g.W, Cin = g.Cin, Cout = g.Cout, KH = g.KH, KW = g.KW, stride = g.stride, pad_t = g.pad_t,
+              pad_l = g.pad_l, Ho = g.Ho, Wo = g.Wo;
     ORBIT_REQUIRE(x && dy && dw_oihw && scratch, "conv_wgrad: null pointer");
     ORBIT_REQUIRE(!gate || !x_nchw, "conv_wgrad: the squeeze-excite gate needs the NHWC path");
     ORBIT_REQUIRE(Cout % 4 == 0, "conv_wgrad: Cout %% 4 != 0");
@@ -518,25 +520,21 @@ int conv_pack_dgrad_weights(const float* w_oihw, float* w_packed, int Cin, int C
 }
 
 // dX (+= accumulate) of a convolution. `up` is scratch of B*H*W*Cout floats, only touched when stride > 1.
-int launch_conv_dgrad(const float* dy, const float* w_dgrad_packed, const float* accumulate, float* dx, float* up, int B,
-                      int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo,
-                      hipStream_t s) {
+int launch_conv_dgrad(const float* dy, const float* w_dgrad_packed, const float* accumulate, float* dx, float* up,
+                      const LayerGeom& g, hipStream_t s) {
     ORBIT_REQUIRE(dy && w_dgrad_packed && dx, "conv_dgrad: null pointer");
-    ORBIT_REQUIRE(pad_t <= KH - 1 && pad_l <= KW - 1, "conv_dgrad: padding larger than the filter");
-    const float* src = dy;
-    int Hs = Ho, Ws = Wo;
-    if (stride > 1) {
-        ORBIT_REQUIRE(up, "conv_dgrad: strided layers need the upsampling scratch");
-        if (int rc = launch_upsample_zero(dy, up, B, H, W, Cout, stride, Ho, Wo, s)) return rc;
-        src = up, Hs = H, Ws = W;
-    }
+    ORBIT_REQUIRE(g.pad_t <= g.KH - 1 && g.pad_l <= g.KW - 1, "conv_dgrad: padding larger than the filter");
+    // the transposed layer: a stride-1 convolution of dy (zero-inserted to the input grid when the layer is strided) with the
+    // rotated filter, channels swapped, padding K - 1 - pad, onto the layer's input map
     ConvDesc d;
-    d.x = src, d.w_packed = w_dgrad_packed, d.y = dx, d.scale = nullptr, d.shift = nullptr;
-    d.residual = accumulate, d.gate = nullptr;
-    d.B = B, d.H = Hs, d.W = Ws, d.Cin = Cout, d.Cout = Cin, d.KH = KH, d.KW = KW, d.stride = 1;
-    d.pad_t = KH - 1 - pad_t, d.pad_l = KW - 1 - pad_l, d.Ho = H, d.Wo = W;
-    d.act = ORBIT_ACT_NONE, d.pool2 = 0, d.x_nchw = 0;
-    d.prof_flop_scale = 1.0f / (float)(stride * stride);
+    d.geom() = LayerGeom{g.B, g.Ho, g.Wo, g.Cout, g.Cin, g.KH, g.KW, 1, g.KH - 1 - g.pad_t, g.KW - 1 - g.pad_l, g.H, g.W};
+    d.x = dy, d.w_packed = w_dgrad_packed, d.y = dx, d.residual = accumulate;
+    if (g.stride > 1) {
+        ORBIT_REQUIRE(up, "conv_dgrad: strided layers need the upsampling scratch");
+        if (int rc = launch_upsample_zero(dy, up, g.B, g.H, g.W, g.Cout, g.stride, g.Ho, g.Wo, s)) return rc;
+        d.x = up, d.H = g.H, d.W = g.W;
+    }
+    d.prof_flop_scale = 1.0f / (float)(g.stride * g.stride);
     return launch_conv(d, s);
 }
 
@@ -551,11 +549,11 @@ int orbit_op_conv2d_wgrad(const float* x, int x_nchw, const float* dy, float* dw
     ORBIT_REQUIRE(x && dy && dw, "op_conv2d_wgrad: null pointer");
     ORBIT_REQUIRE(B > 0 && KH > 0 && KW > 0 && stride > 0 && Ho > 0 && Wo > 0, "op_conv2d_wgrad: bad geometry");
     hipStream_t s = (hipStream_t)stream;
+    const LayerGeom g{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
     float* scratch = nullptr;
     ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&scratch),
-                                   conv_wgrad_scratch_floats(B, Cin, Cout, KH, KW, Ho, Wo) * sizeof(float), s));
-    const int rc = launch_conv_wgrad(x, x_nchw, dy, dw, B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo,
-                                     scratch, s);
+                                   conv_wgrad_scratch_floats(g) * sizeof(float), s));
+    const int rc = launch_conv_wgrad(x, x_nchw, dy, dw, g, scratch, s);
     (void)hipFreeAsync(scratch, s);
     return rc;
 }
@@ -565,10 +563,10 @@ int orbit_op_conv2d_wgrad_gated(const float* x, const float* gate, const float* 
     ORBIT_REQUIRE(x && gate && dy && dw, "op_conv2d_wgrad_gated: null pointer");
     ORBIT_REQUIRE(B > 0 && H > 0 && W > 0, "op_conv2d_wgrad_gated: bad geometry");
     hipStream_t s = (hipStream_t)stream;
+    const LayerGeom g{B, H, W, Cin, Cout, 1, 1, 1, 0, 0, H, W};
     float* scratch = nullptr;
-    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&scratch), conv_wgrad_scratch_floats(B, Cin, Cout, 1, 1, H, W) * sizeof(float),
-                                   s));
-    const int rc = launch_conv_wgrad(x, 0, dy, dw, B, H, W, Cin, Cout, 1, 1, 1, 0, 0, H, W, scratch, s, gate);
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&scratch), conv_wgrad_scratch_floats(g) * sizeof(float), s));
+    const int rc = launch_conv_wgrad(x, 0, dy, dw, g, scratch, s, gate);
     (void)hipFreeAsync(scratch, s);
     return rc;
 }
@@ -586,8 +584,8 @@ int orbit_op_conv2d_dgrad(const float* dy, const float* w, const float* accumula
     ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (npack + nup) * sizeof(float), s));
     int rc = conv_pack_dgrad_weights(w, tmp, Cin, Cout, KH, KW, s);
     if (rc == ORBIT_OK)
-        rc = launch_conv_dgrad(dy, tmp, accumulate, dx, stride > 1 ? tmp + npack : nullptr, B, H, W, Cin, Cout, KH, KW,
-                               stride, pad_top, pad_left, Ho, Wo, s);
+        rc = launch_conv_dgrad(dy, tmp, accumulate, dx, stride > 1 ? tmp + npack : nullptr,
+                               LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo}, s);
     (void)hipFreeAsync(tmp, s);
     return rc;
 }

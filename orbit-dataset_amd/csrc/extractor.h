@@ -116,6 +116,13 @@ struct Op {
     int weight2 = -1, bn2 = -1;    // OP_MBFRONT: depthwise weight (packed at packed_off) and its BatchNorm
     bool rows = false;             // OP_MBFRONT served by the row-streaming kernel (csrc/mbconv_rows.hip)
     int pool_k = 0, pool_pad = 0;
+    // the layer at batch B as the launchers take it (a max-pool carries its window and padding in KH / KW and pad_t / pad_l)
+    LayerGeom geom(int B) const {
+        if (kind == OP_MAXPOOL) return LayerGeom{B, H, W, Cin, Cout, pool_k, pool_k, stride, pool_pad, pool_pad, Ho, Wo};
+        return LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo};
+    }
+    // the fused 2x2/2 max-pool behind an OP_CONV with pool2
+    LayerGeom pool2_geom(int B) const { return LayerGeom{B, Ho, Wo, Cout, Cout, 2, 2, 2, 0, 0, Ho / 2, Wo / 2}; }
 };
 
 // folds eval-mode BatchNorm (+ per-task FiLM gamma/beta, + the bias of the preceding convolution) into scale/shift;
@@ -272,7 +279,7 @@ struct orbit_extractor {
         // the fragment-ordered copy of a pointwise filter only where the register GEMM will be asked for it (csrc/pw_rgemm.hip:
         // conv_rgemm = 1 one layer class, = 2 every supported conv) - it doubles the packed bytes and the pack work of a layer
         ConvDesc shape;
-        shape.H = H_, shape.W = W_, shape.Cin = Cin, shape.Cout = Cout;
+        shape.geom() = o.geom(0);
         const int rg = get_option("conv_rgemm");
         if (stride == 1 && pad_t == 0 && pad_l == 0 && !pool2 && conv_frag_floats(Cin, Cout, K, K, x_nchw) &&
             (rg == 2 || (rg == 1 && pw_rgemm_preferred(shape)))) {

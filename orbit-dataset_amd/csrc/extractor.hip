@@ -345,9 +345,7 @@ struct WsLayout {
 };
 static ConvDesc conv_shape(const Op& o, int B) {  // the fields the split-K plan looks at
     ConvDesc d;
-    d.x = d.w_packed = d.scale = d.shift = d.residual = d.gate = nullptr, d.y = nullptr;
-    d.B = B, d.H = o.H, d.W = o.W, d.Cin = o.Cin, d.Cout = o.Cout, d.KH = o.KH, d.KW = o.KW;
-    d.stride = o.stride, d.pad_t = o.pad_t, d.pad_l = o.pad_l, d.Ho = o.Ho, d.Wo = o.Wo;
+    d.geom() = o.geom(B);
     d.act = o.act, d.pool2 = o.pool2, d.x_nchw = o.x_nchw;
     return d;
 }
@@ -632,8 +630,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                 d.shift = o.bn >= 0 ? shift + fe->bns[o.bn].fold_off : nullptr;
                 d.residual = o.res >= 0 ? buf(o.res) : nullptr;
                 d.gate = o.use_gate ? buf(BUF_GATE) : nullptr;
-                d.B = B, d.H = o.H, d.W = o.W, d.Cin = o.Cin, d.Cout = o.Cout, d.KH = o.KH, d.KW = o.KW;
-                d.stride = o.stride, d.pad_t = o.pad_t, d.pad_l = o.pad_l, d.Ho = o.Ho, d.Wo = o.Wo;
+                d.geom() = o.geom(B);
                 d.act = o.act, d.pool2 = o.pool2, d.x_nchw = o.x_nchw, d.res_post = o.res_post;
                 d.splitk_ws = reinterpret_cast<float*>(ws + L.splitk);
                 rc = launch_conv(d, s);
@@ -642,8 +639,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
             case OP_DWCONV:
                 rc = launch_dwconv_se(buf(o.in), fe->d_packed + o.packed_off, buf(o.out),
                                       scale + fe->bns[o.bn].fold_off, shift + fe->bns[o.bn].fold_off,
-                                      o.pool_partial ? buf(BUF_POOLED) : nullptr, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t,
-                                      o.pad_l, o.Ho, o.Wo, o.act, s);
+                                      o.pool_partial ? buf(BUF_POOLED) : nullptr, o.geom(B), o.act, s);
                 break;
             case OP_MBFRONT:
                 if (o.stem)
@@ -659,8 +655,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                                             o.Cout, o.KH, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s, o.se_chunks);
                 break;
             case OP_MAXPOOL:
-                rc = launch_maxpool(buf(o.in), buf(o.out), B, o.H, o.W, o.Cin, o.pool_k, o.stride, o.pool_pad, o.Ho,
-                                    o.Wo, s);
+                rc = launch_maxpool(buf(o.in), buf(o.out), o.geom(B), s);
                 break;
             case OP_AVGPOOL:
                 rc = launch_avgpool(buf(o.in), buf(o.out), B, o.H * o.W, o.Cin, s);

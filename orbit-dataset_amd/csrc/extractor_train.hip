@@ -85,6 +85,7 @@ static bool plan_frozen_only(const orbit_extractor* fe) {
 }
 
 static bool has_bn(const Op& o) { return o.kind == OP_CONV || o.kind == OP_DWCONV; }
+static DwInXf in_xf(const BnFoldC& bn, int act) { return DwInXf{bn.scale, bn.shift, act}; }  // a layer's BatchNorm + activation as an input transform
 
 // no op from `first` on reads buffer `id` before it is written again
 static bool no_later_reader(const orbit_extractor* fe, size_t first, int id) {
@@ -118,9 +119,11 @@ static size_t max_bn_partial_floats(const orbit_extractor* fe, int B) {
             if (o.kind == OP_CONV) {
                 m = std::max(m, bn_partial_floats((M + 31) / 32, o.Cout));
                 // backward: reduction written by the data gradient of the depthwise convolution it feeds (+ coefficients)
-                for (int st : {1, 2})
-                    m = std::max(m, bn_partial_floats((size_t)dwconv_dgrad_bn_blocks(B, o.Ho, o.Wo, o.Cout, st), o.Cout) +
-                                        3 * (size_t)o.Cout);
+                for (int st : {1, 2}) {
+                    LayerGeom dw;  // (of that depthwise layer only what dwconv_dgrad_bn_blocks reads)
+                    dw.B = B, dw.H = o.Ho, dw.W = o.Wo, dw.Cin = o.Cout, dw.stride = st;
+                    m = std::max(m, bn_partial_floats((size_t)dwconv_dgrad_bn_blocks(dw), o.Cout) + 3 * (size_t)o.Cout);
+                }
             }
             else {
                 m = std::max(m, bn_partial_floats((size_t)B * dwconv_se_chunks(o.Ho), o.Cout));
@@ -223,7 +226,10 @@ struct OpForm {
     int front = -1;              // ... the conv it runs with as the row-streaming fused front (sweep 2), or -1
     bool pooled = false;         // ... its activation pass also leaves the squeeze-excite pooling partials in TapeLayout::pool
     bool through_act = false;    // ... backward: its data gradient may go through the producing conv's activation (DwBnBwd)
+    bool wgrad_rides = false;    // ... backward: and its filter gradient may ride on that kernel (DwBnBwd::wgrad_partial)
+    bool se_sums_only = false;   // OP_CONV with a gate: backward: the squeeze-excite backward may leave only the BatchNorm sums
     int se_dw = -1;              // OP_SE: the depthwise op it pools
+    bool se_batched = false;     // ... backward: its parameter gradients fit the batched end-of-pass launch
 };
 typedef std::vector<OpForm> TrainForms;
 
@@ -273,7 +279,7 @@ static TrainForms train_forms(const orbit_extractor* fe, int B, int bn_train, bo
             // reads the mask from the activated tensor).
             const bool raw = xf_conv(o) && sole &&
                              (no_backward || ((o.act == ORBIT_ACT_SILU || o.act == ORBIT_ACT_NONE) &&
-                                              dwconv_wgrad_xf_supported(B, d->H, d->W, d->Cin, d->KH, d->stride, d->Ho, d->Wo)));
+                                              dwconv_wgrad_xf_supported(d->geom(B))));
             // Dual write: running-statistics BatchNorm (frozen extractor: CNAPs meta-training, FiLM fine-tuning): scale / shift
             // are known before the conv runs, so its epilogue writes BOTH the raw output (tape: xhat and the SiLU derivative need
             // it) and the activation - no separate activation pass over the tensor
@@ -282,6 +288,9 @@ static TrainForms train_forms(const orbit_extractor* fe, int B, int bn_train, bo
             if (front) f.conv = bn_gram_supported(o.Cin) && fronts != 3 ? CONV_SWEEP_GRAM : CONV_SWEEP_CONV, f.tiles = tiles;
             else if (!bn_train && !o.pool2 && !o.res_post) f.conv = CONV_DUAL;
             else if (raw) f.conv = CONV_RAW_TO_DW;
+            const int src = P.in[i];  // (the 2^32 bound: the 32-bit element index of the BatchNorm apply pass that rebuilds g)
+            f.se_sums_only = o.use_gate && src >= 0 && fe->ops[src].kind == OP_DWCONV &&
+                             (unsigned long long)B * o.H * o.W * (o.Cin / 4) < (1ull << 32);
         } else if (o.kind == OP_DWCONV) {
             const int prev = (int)i - 1;  // (a conv in one of the three forms below is followed by its depthwise reader)
             if (prev >= 0 && F[prev].conv == CONV_RAW_TO_DW) f.raw_src = prev;
@@ -293,8 +302,10 @@ static TrainForms train_forms(const orbit_extractor* fe, int B, int bn_train, bo
             const int src = P.in[i];
             f.through_act = src >= 0 && src == prev && xf_conv(fe->ops[src]) && fe->bns[fe->ops[src].bn].conv_bias < 0 &&
                             (fe->ops[src].act == ORBIT_ACT_SILU || fe->ops[src].act == ORBIT_ACT_NONE);
+            f.wgrad_rides = f.through_act && f.raw_src >= 0 && dwconv_bwd_fused_scratch_floats(o.geom(B)) > 0;
         } else if (o.kind == OP_SE) {
             f.se_dw = se_source(fe, i);
+            f.se_batched = o.R <= SE_PARAM_MAX_R;
         }
     }
     return F;
@@ -302,25 +313,32 @@ static TrainForms train_forms(const orbit_extractor* fe, int B, int bn_train, bo
 
 struct BwdLayout {
     static const int NSLOTS = 8;
-    size_t slot_bytes = 0, slots = 0, up = 0, wgrad = 0, partial = 0, se = 0, total = 0;
-    size_t cwgrad = 0;  // the dense filter gradients' partial tiles, one region per layer (their reduce runs batched at the end)
+    size_t slot_bytes = 0, slots = 0, up = 0, wgrad = 0, partial = 0, total = 0;
+    // byte offsets per op (NONE: the op has none). OP_CONV: the partial tiles of its filter gradient; OP_SE: the scratch of its
+    // backward. A region per layer, because their reductions run batched at the end of the pass (WgradReduceJobs, SeParamJobs).
+    std::vector<size_t> cwgrad, se;
 };
 static BwdLayout bwd_layout(const orbit_extractor* fe, int B) {
     BwdLayout L;
-    size_t slot = 4, up = 4, wg = 4, se = 4, cwg = 4;
-    for (const Op& o : fe->ops) {
+    const size_t n = fe->ops.size();
+    L.cwgrad.assign(n, NONE), L.se.assign(n, NONE);
+    size_t slot = 4, up = 4, wg = 4, se = 0, cwg = 0;
+    // (in the order the reverse pass meets the layers: the last layer's regions come first)
+    for (size_t i = n; i-- > 0;) {
+        const Op& o = fe->ops[i];
+        const LayerGeom g = o.geom(B);
         if (o.kind == OP_DWCONV) {
             slot = std::max(slot, (size_t)B * o.H * o.W * o.Cin);
             slot = std::max(slot, (size_t)B * o.Ho * o.Wo * o.Cout);
-            wg = std::max(wg, dwconv_wgrad_scratch_floats(B, o.Ho, o.Wo, o.Cin, o.KH));
-            wg = std::max(wg, dwconv_bwd_fused_scratch_floats(B, o.H, o.W, o.Cin, o.KH, o.stride));
+            wg = std::max(wg, dwconv_wgrad_scratch_floats(g));
+            wg = std::max(wg, dwconv_bwd_fused_scratch_floats(g));
         } else if (o.kind == OP_SE) {
-            se += align_up(se_bwd_scratch_floats(B, o.Cin, o.R), 64);  // one scratch per block (their parameter gradients run batched)
+            L.se[i] = se * 4, se += align_up(se_bwd_scratch_floats(B, o.Cin, o.R), 64);
         } else if (o.kind == OP_CONV) {
             slot = std::max(slot, (size_t)B * o.Ho * o.Wo * o.Cout);
             if (!o.x_nchw) slot = std::max(slot, (size_t)B * o.H * o.W * o.Cin);
             if (o.stride > 1 && !o.x_nchw) up = std::max(up, (size_t)B * o.H * o.W * o.Cout);
-            cwg += align_up(conv_wgrad_scratch_floats(B, o.Cin, o.Cout, o.KH, o.KW, o.Ho, o.Wo), 64);
+            L.cwgrad[i] = cwg * 4, cwg += align_up(conv_wgrad_scratch_floats(g), 64);
         } else if (o.kind == OP_MAXPOOL || o.kind == OP_AVGPOOL) {
             slot = std::max(slot, (size_t)B * o.H * o.W * o.Cin);
         }
@@ -330,9 +348,13 @@ static BwdLayout bwd_layout(const orbit_extractor* fe, int B) {
     L.slots = off, off += L.slot_bytes * BwdLayout::NSLOTS;
     L.up = off, off += align_up(up * 4, 256);
     L.wgrad = off, off += align_up(wg * 4, 256);
-    L.cwgrad = off, off += align_up(cwg * 4, 256);
+    for (size_t& c : L.cwgrad)
+        if (c != NONE) c += off;
+    off += align_up((cwg + 4) * 4, 256);
     L.partial = off, off += align_up(max_bn_partial_floats(fe, B) * 4, 256);
-    L.se = off, off += align_up(se * 4, 256);
+    for (size_t& c : L.se)
+        if (c != NONE) c += off;
+    off += align_up((se + 4) * 4, 256);
     L.total = off;
     return L;
 }
@@ -376,9 +398,6 @@ static int ensure_dgrad_filters(orbit_extractor* fe, hipStream_t s) {
 static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, const float* film_gamma,
                              const float* film_beta, int bn_train, float momentum, float* feats, void* tape,
                              hipStream_t s, bool no_backward = false, bool defer_stats = false);
-static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const float* film_gamma,
-                        const float* film_beta, int bn_train, const float* dfeats, const void* tape, float* param_grads,
-                        int filter_grads, float* dfilm_gamma, float* dfilm_beta, void* workspace, hipStream_t s);
 
 extern "C" {
 
@@ -521,15 +540,12 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
                 continue;
             }
             ConvDesc d;
-            d.x = xin, d.w_packed = fe->d_packed + o.packed_off, d.y = fl(L.y[i]);
-            d.scale = d.shift = d.residual = d.gate = nullptr;
+            d.geom() = o.geom(B);
+            d.x = xin, d.w_packed = fe->d_packed + o.packed_off, d.y = fl(L.y[i]), d.x_nchw = o.x_nchw;
             // squeeze-excite: the projection multiplies the gate into its A operand on the fly (as the inference plan does)
             if (o.use_gate) d.gate = cur[BUF_GATE];
             int stat_blocks = 0;  // train-mode BatchNorm: column sums of the raw outputs come from the conv's epilogue
             if (bn_train) d.stats = fl(L.partial), d.stats_blocks = &stat_blocks;
-            d.B = B, d.H = o.H, d.W = o.W, d.Cin = o.Cin, d.Cout = o.Cout, d.KH = o.KH, d.KW = o.KW;
-            d.stride = o.stride, d.pad_t = o.pad_t, d.pad_l = o.pad_l, d.Ho = o.Ho, d.Wo = o.Wo;
-            d.act = ORBIT_ACT_NONE, d.pool2 = 0, d.x_nchw = o.x_nchw;
             if (f.conv == CONV_DUAL) {
                 d.y_raw = fl(L.y[i]), d.y = fl(L.a[i]);
                 d.scale = bf.scale, d.shift = bf.shift;
@@ -565,8 +581,7 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
                                         fl(L.a[i]), s, o.res_post);
             if (rc != ORBIT_OK) return rc;
             if (o.pool2) {
-                rc = launch_maxpool_idx(fl(L.a[i]), fl(L.p[i]), reinterpret_cast<uint8_t*>(tp + L.idx[i]), B, o.Ho, o.Wo,
-                                        o.Cout, 2, 2, 0, o.Ho / 2, o.Wo / 2, s);
+                rc = launch_maxpool_idx(fl(L.a[i]), fl(L.p[i]), reinterpret_cast<uint8_t*>(tp + L.idx[i]), o.pool2_geom(B), s);
                 cur[o.out] = fl(L.p[i]);
             } else {
                 cur[o.out] = fl(L.a[i]);
@@ -587,12 +602,10 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
                                         s, 0, true);
                 stat_rows = B * F[f.front].tiles;
             } else {
-                BnFoldC in;  // the producing conv's BatchNorm + activation, applied to its RAW output as it is loaded
-                int in_act = ORBIT_ACT_NONE;
-                if (f.raw_src >= 0) in = fold(fe->bns[fe->ops[f.raw_src].bn]), in_act = fe->ops[f.raw_src].act;
+                DwInXf in;  // the producing conv's BatchNorm + activation, applied to its RAW output as it is loaded
+                if (f.raw_src >= 0) in = in_xf(fold(fe->bns[fe->ops[f.raw_src].bn]), fe->ops[f.raw_src].act);
                 rc = launch_dwconv_se(cur[o.in], fe->d_packed + o.packed_off, y, nullptr, nullptr,
-                                      bn_train ? fl(L.partial) : nullptr, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t, o.pad_l,
-                                      o.Ho, o.Wo, ORBIT_ACT_NONE, s, bn_train ? 1 : 0, in.scale, in.shift, in_act);
+                                      bn_train ? fl(L.partial) : nullptr, o.geom(B), ORBIT_ACT_NONE, s, bn_train ? 1 : 0, in);
             }
             if (rc != ORBIT_OK) return rc;
             const int M = B * o.Ho * o.Wo;
@@ -624,8 +637,7 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
             }
             cur[BUF_GATE] = fl(L.a[i]);
         } else if (o.kind == OP_MAXPOOL) {
-            rc = launch_maxpool_idx(cur[o.in], fl(L.p[i]), reinterpret_cast<uint8_t*>(tp + L.idx[i]), B, o.H, o.W, o.Cin,
-                                    o.pool_k, o.stride, o.pool_pad, o.Ho, o.Wo, s);
+            rc = launch_maxpool_idx(cur[o.in], fl(L.p[i]), reinterpret_cast<uint8_t*>(tp + L.idx[i]), o.geom(B), s);
             cur[o.out] = fl(L.p[i]);
         } else {  // OP_AVGPOOL
             rc = launch_avgpool(cur[o.in], feats, B, o.H * o.W, o.Cin, s);
@@ -644,6 +656,342 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
     }
     return ORBIT_OK;
 }
+
+// ---- the reverse pass -----------------------------------------------------------------------------------------------------
+// One object per call: the views of the tape and the workspace, the gradient-slot pool, what the pass knows about every op and
+// the two job lists of the batched end-of-pass launches; run() walks the ops backwards and calls one step per kind. Runs inside
+// stream capture (run_train_graphed): nothing here allocates on the device, synchronises or reads back, and the job lists travel
+// as by-value kernel arguments.
+struct BackwardPass {
+    orbit_extractor_t* fe;  // the call's arguments
+    const float *frames, *film_gamma, *film_beta, *dfeats;
+    float *param_grads, *dfilm_gamma, *dfilm_beta;
+    int B, bn_train;
+    hipStream_t s;
+    // wg false (filter_grads == 0): only the BatchNorm weight / bias gradients are wanted (FiLM fine-tuning of a frozen extractor,
+    // few_shot_recognisers.py:196-199): skip every filter / squeeze-excite / bias gradient
+    // se_per_block (A/B and parity runs): every squeeze-excite block sums its parameter gradients in a launch of its own
+    const bool film, wg, se_per_block;
+    const TapeLayout L;
+    const BwdLayout W;
+    const Producers P;
+    const TrainForms F;
+    const char* tp;
+    char* ws;
+    float *up, *wgrad_scratch, *partial;
+    int first_needed;  // the earliest op whose backward yields something that was asked for
+
+    struct OpState {
+        int slot = -1;  // the slot holding the gradient w.r.t. the OUTPUT tensor of the op, or -1
+        // > 0: that slot already holds g = d out * act'(.) and `partial` the [n][2][C] sums of the op's BatchNorm backward
+        // (written by the squeeze-excite backward of the block, launch_se_gate_backward with SeBnFuse, or - for the expansion
+        // convolution - by the data gradient of the depthwise convolution it feeds, DwBnBwd)
+        int pre_reduced = 0;
+        // ... and when the squeeze-excite backward left only the SUMS (gate != nullptr): the slot holds d(x * gate) and g is
+        // rebuilt in the BatchNorm's apply pass from it, the gate and the pooled-branch gradient (launch_bn_backward_reduced_gated)
+        const float *gate = nullptr, *dpooled = nullptr;
+        int HW = 0;
+    };
+    std::vector<OpState> st;
+    bool used[BwdLayout::NSLOTS] = {false};
+    // the batched end-of-pass launches: the split reductions of the dense filter gradients, the parameter gradients of the
+    // squeeze-excite blocks. Every layer owns its scratch region (BwdLayout) and nothing in the pass reads the reduced gradients,
+    // so a full list is flushed with a launch of its own and goes on collecting (efficientnet_v2_s: 80 dense convs, 30 blocks).
+    WgradReduceJobs wg_jobs;
+    int n_wg_jobs = 0;
+    SeParamJobs se_jobs;
+    int n_se_jobs = 0;
+
+    BackwardPass(orbit_extractor_t* fe_, const float* frames_, int B_, const float* film_gamma_, const float* film_beta_,
+                 int bn_train_, const float* dfeats_, const void* tape, float* param_grads_, int filter_grads,
+                 float* dfilm_gamma_, float* dfilm_beta_, void* workspace, hipStream_t s_)
+        : fe(fe_), frames(frames_), film_gamma(film_gamma_), film_beta(film_beta_), dfeats(dfeats_), param_grads(param_grads_),
+          dfilm_gamma(dfilm_gamma_), dfilm_beta(dfilm_beta_), B(B_), bn_train(bn_train_), s(s_),
+          film(film_gamma_ && film_beta_ && fe_->film_size > 0), wg(param_grads_ != nullptr && filter_grads != 0),
+          se_per_block(filter_grads == ORBIT_FILTER_GRADS_SE_PER_BLOCK), L(tape_layout(fe_, B_)), W(bwd_layout(fe_, B_)),
+          P(producers(fe_)), F(train_forms(fe_, B_, bn_train_, false)), tp(static_cast<const char*>(tape)),
+          ws(static_cast<char*>(workspace)), up(wsf(W.up)), wgrad_scratch(wsf(W.wgrad)), partial(wsf(W.partial)),
+          st(fe_->ops.size()) {
+        const int n = (int)fe->ops.size();
+        first_needed = n;
+        for (int i = 0; i < n && first_needed == n; ++i) {
+            const Op& o = fe->ops[i];
+            if (!has_bn(o)) continue;
+            if (param_grads || (dfilm_gamma && fe->bns[o.bn].film_off >= 0)) first_needed = i;
+        }
+    }
+
+    const float* tf(size_t off) const { return reinterpret_cast<const float*>(tp + off); }
+    const uint8_t* tidx(int i) const { return reinterpret_cast<const uint8_t*>(tp + L.idx[i]); }
+    float* wsf(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+    float* slot_ptr(int k) const { return wsf(W.slots + (size_t)k * W.slot_bytes); }
+    float* pgrad(int param) const { return param_grads + fe->pool.off(param); }
+    const BNDesc& bn_of(int i) const { return fe->bns[fe->ops[i].bn]; }
+    const float* out_tensor(int i) const {  // forward output of op i
+        if (i < 0) return frames;
+        const Op& o = fe->ops[i];
+        if (o.kind == OP_CONV) return o.pool2 ? tf(L.p[i]) : tf(L.a[i]);
+        if (o.kind == OP_DWCONV) return tf(L.a[i]);
+        return tf(L.p[i]);
+    }
+    // a layer's slice of the fold arrays on the tape; the gamma its forward used (FiLM's or the plan's) with the matching places
+    // of its gradients
+    BnFoldC fold(const BNDesc& bn) const {
+        return BnFoldC{tf(L.mean) + bn.fold_off, tf(L.invstd) + bn.fold_off, tf(L.scale) + bn.fold_off, tf(L.shift) + bn.fold_off};
+    }
+    BnGrads grads(const BNDesc& bn) const {
+        const bool fm = film && bn.film_off >= 0;
+        BnGrads p;
+        p.gamma = fm ? film_gamma + bn.film_off : fe->param(bn.gamma);
+        if (fm) {
+            if (dfilm_gamma) p.dgamma = dfilm_gamma + bn.film_off, p.dbeta = dfilm_beta + bn.film_off;
+        } else if (param_grads) {
+            p.dgamma = pgrad(bn.gamma), p.dbeta = pgrad(bn.beta);
+        }
+        if (wg && bn.conv_bias >= 0) p.dbias = pgrad(bn.conv_bias);
+        return p;
+    }
+    // the gradient slots: take() hands out the lowest free one, or -1 with the error set
+    int take() {
+        for (int k = 0; k < BwdLayout::NSLOTS; ++k)
+            if (!used[k]) {
+                used[k] = true;
+                return k;
+            }
+        set_err(ORBIT_ERR_STATE, "extractor_backward: gradient slots exhausted");
+        return -1;
+    }
+    void release(int k) {
+        if (k >= 0) used[k] = false;
+    }
+    // the gradient of op i's output is consumed: its slot returns to the pool
+    void consumed(int i) { release(st[i].slot), st[i].slot = -1; }
+    // the next free job of each list, after the flush of a full one
+    int next_wgrad_job(WgradReduceJob** job) {
+        if (n_wg_jobs == WGRAD_REDUCE_JOBS) {
+            if (int rc = launch_conv_wgrad_reduce_batched(wg_jobs, n_wg_jobs, s)) return rc;
+            n_wg_jobs = 0;
+        }
+        *job = &wg_jobs.j[n_wg_jobs++];
+        return ORBIT_OK;
+    }
+    int next_se_job(SeParamJob** job) {
+        if (n_se_jobs == SE_PARAM_JOBS) {
+            if (int rc = launch_se_param_grad_batched(se_jobs, n_se_jobs, s)) return rc;
+            n_se_jobs = 0;
+        }
+        *job = &se_jobs.j[n_se_jobs++];
+        return ORBIT_OK;
+    }
+
+    int run() {
+        for (int i = (int)fe->ops.size() - 1; i >= first_needed; --i) {
+            int rc = ORBIT_OK;
+            switch (fe->ops[i].kind) {
+            case OP_AVGPOOL: rc = avgpool(i); break;
+            case OP_MAXPOOL: rc = maxpool(i); break;
+            case OP_DWCONV: rc = dwconv(i); break;
+            case OP_CONV: rc = conv(i); break;
+            default: break;  // OP_SE: handled together with the gated convolution that consumes the gate
+            }
+            if (rc != ORBIT_OK) return rc;
+        }
+        if (int rc = launch_conv_wgrad_reduce_batched(wg_jobs, n_wg_jobs, s)) return rc;
+        return launch_se_param_grad_batched(se_jobs, n_se_jobs, s);
+    }
+
+    int avgpool(int i) {
+        const Op& o = fe->ops[i];
+        const int src = P.in[i];
+        if (src < first_needed) return ORBIT_OK;
+        ORBIT_REQUIRE(st[src].slot < 0, "extractor_backward: unexpected fan-out into the global pool");
+        if ((st[src].slot = take()) < 0) return ORBIT_ERR_STATE;
+        return launch_avgpool_bwd(dfeats, slot_ptr(st[src].slot), B, o.H * o.W, o.Cin, s);
+    }
+
+    int maxpool(int i) {
+        const int src = P.in[i], g = st[i].slot;
+        if (g < 0) return ORBIT_OK;
+        if (src >= first_needed) {
+            ORBIT_REQUIRE(st[src].slot < 0, "extractor_backward: unexpected fan-out into a max-pool");
+            if ((st[src].slot = take()) < 0) return ORBIT_ERR_STATE;
+            if (int rc = launch_maxpool_bwd(slot_ptr(g), tidx(i), slot_ptr(st[src].slot), fe->ops[i].geom(B), s)) return rc;
+        }
+        consumed(i);
+        return ORBIT_OK;
+    }
+
+    // BatchNorm (+ activation, + residual fan-out) of op i: g = the gradient of its output, dy (nullable: reductions only)
+    // receives the gradient of the raw conv output. `partial` holds [blocks][2][C] followed by the 3*C apply coefficients.
+    int bn_backward(int i, const float* g, float* dy, const BnGrads& bp, float* dres, int dres_acc) {
+        const Op& o = fe->ops[i];
+        const BnFoldC bf = fold(bn_of(i));
+        const int M = B * o.Ho * o.Wo, pre = st[i].pre_reduced;
+        if (pre > 0) {
+            float* coef = partial + bn_partial_floats((size_t)pre, o.Cout);
+            if (st[i].gate)
+                return launch_bn_backward_reduced_gated(g, st[i].gate, st[i].dpooled, st[i].HW, BnTaped{tf(L.y[i]), bf, o.act, partial},
+                                                        bp, bn_train, M, o.Cout, dy, pre, coef, s);
+            return launch_bn_backward_reduced(g, tf(L.y[i]), bf, bp, bn_train, M, o.Cout, dy, partial, pre, coef, s);
+        }
+        float* coef = partial + (size_t)bn_reduce_blocks(M, o.Cout) * 2 * o.Cout;
+        return launch_bn_backward(g, tf(L.a[i]), tf(L.y[i]), bf, bp, bn_train, o.act, M, o.Cout, dy, dres, dres_acc, partial, coef, s,
+                                  o.res_post);
+    }
+
+    // the filter gradient of depthwise op i in a launch of its own (dy: the gradient of its raw output)
+    int dw_filter_gradient(int i, const float* dy) {
+        const Op& o = fe->ops[i];
+        const int src = P.in[i];
+        if (F[i].raw_src < 0) return launch_dwconv_wgrad(out_tensor(src), dy, pgrad(o.weight), wgrad_scratch, o.geom(B), s);
+        // the forward never wrote this layer's input: the filter gradient rebuilds it from the producing conv's raw output as it
+        // stages its patch
+        return launch_dwconv_wgrad(tf(L.y[src]), dy, pgrad(o.weight), wgrad_scratch, o.geom(B), s,
+                                   in_xf(fold(bn_of(src)), fe->ops[src].act));
+    }
+
+    int dwconv(int i) {
+        const Op& o = fe->ops[i];
+        const int g = st[i].slot;
+        if (g < 0) return ORBIT_OK;
+        const int src = P.in[i];
+        const bool need_dx = src >= first_needed;
+        const bool need_dy = need_dx || wg;
+        const int kdy = need_dy ? take() : -1;
+        if (need_dy && kdy < 0) return ORBIT_ERR_STATE;
+        float* dy = need_dy ? slot_ptr(kdy) : nullptr;
+        if (int rc = bn_backward(i, slot_ptr(g), dy, grads(bn_of(i)), nullptr, 0)) return rc;
+        consumed(i);
+        // the producer is a convolution + BatchNorm + SiLU right before this layer (see the data gradient below); on the stride-2
+        // layers and the large 3x3 maps the filter gradient rides on that data-gradient kernel (train_forms decides both)
+        const bool through_act = need_dx && F[i].through_act;
+        const bool wg_fused = wg && need_dx && F[i].wgrad_rides;
+        if (wg && !wg_fused)
+            if (int rc = dw_filter_gradient(i, dy)) return rc;
+        if (need_dx) {
+            ORBIT_REQUIRE(st[src].slot < 0, "extractor_backward: unexpected fan-out into a depthwise convolution");
+            const int k = st[src].slot = take();
+            if (k < 0) return ORBIT_ERR_STATE;
+            // wgrad_scratch is free again here (the weight-gradient launches above are earlier on the stream)
+            // through_act: the data gradient goes through the producer's activation in the same kernel and leaves the channel
+            // sums of that BatchNorm's backward, so the convolution's own backward starts at the finalize step (no reduction
+            // pass over dx and y)
+            int nblk = 0, wrows = 0;
+            DwBnBwd bnb;
+            if (through_act) {
+                if (wg_fused)
+                    bnb.wgrad_partial = wgrad_scratch + dwconv_bwd_fused_partial_offset(o.Cin, o.KH), bnb.wgrad_rows = &wrows;
+                bnb.y = tf(L.y[src]), bnb.bn = fold(bn_of(src)), bnb.act = fe->ops[src].act;
+                bnb.partial = partial, bnb.nblk = &nblk;
+            }
+            if (int rc = launch_dwconv_dgrad(dy, fe->d_packed + o.packed_off, slot_ptr(k), o.geom(B), s, wgrad_scratch,
+                                             through_act ? &bnb : nullptr))
+                return rc;
+            if (through_act) st[src].pre_reduced = nblk;  // 0: that kernel form has no such epilogue, the slot holds plain dx
+            if (wg_fused) {
+                const int rc = wrows > 0 ? launch_dwconv_wgrad_reduce(bnb.wgrad_partial, wrows, o.KH, o.Cin, pgrad(o.weight), s)
+                                         : dw_filter_gradient(i, dy);
+                if (rc != ORBIT_OK) return rc;
+            }
+        }
+        release(kdy);
+        return ORBIT_OK;
+    }
+
+    int conv(int i) {
+        const Op& o = fe->ops[i];
+        int g = st[i].slot;
+        if (g < 0) return ORBIT_OK;  // no gradient reaches this op
+        if (o.pool2) {
+            const int k = take();
+            if (k < 0) return ORBIT_ERR_STATE;
+            if (int rc = launch_maxpool_bwd(slot_ptr(g), tidx(i), slot_ptr(k), o.pool2_geom(B), s)) return rc;
+            release(g), g = st[i].slot = k;
+        }
+        // BatchNorm (+ReLU, + residual fan-out)
+        const BnGrads bp = grads(bn_of(i));
+        float* dres = nullptr;
+        int dres_acc = 0;
+        const int rsrc = o.res >= 0 ? P.res[i] : -1;
+        if (rsrc >= first_needed) {
+            dres_acc = st[rsrc].slot >= 0;
+            if (!dres_acc && (st[rsrc].slot = take()) < 0) return ORBIT_ERR_STATE;
+            dres = slot_ptr(st[rsrc].slot);
+        }
+        const int src = P.in[i];
+        const bool need_dx = src >= first_needed;
+        const bool need_dy = need_dx || wg;
+        const int kdy = need_dy ? take() : -1;
+        if (need_dy && kdy < 0) return ORBIT_ERR_STATE;
+        float* dy = need_dy ? slot_ptr(kdy) : nullptr;
+        // (reductions only, but the residual branch would still need g: the apply pass does not run without dy)
+        if (!need_dy && dres) return set_err(ORBIT_ERR_STATE, "extractor_backward: residual fan-out without a data gradient");
+        ORBIT_REQUIRE(st[i].pre_reduced <= 0 || (!dres && !bp.dbias && !o.pool2),
+                      "extractor_backward: pre-reduced BatchNorm with a residual or bias");
+        if (int rc = bn_backward(i, slot_ptr(g), dy, bp, dres, dres_acc)) return rc;
+        consumed(i);
+        if (wg) {
+            // a gated projection: d/dW of conv(x * gate) - the gate is multiplied into x inside the kernel. The layer's
+            // partial tiles stay in a region of their own: the split reductions of all layers run as ONE launch at the end
+            WgradReduceJob* defer = nullptr;
+            if (int rc = next_wgrad_job(&defer)) return rc;
+            if (int rc = launch_conv_wgrad(out_tensor(src), o.x_nchw, dy, pgrad(o.weight), o.geom(B), wsf(W.cwgrad[i]), s,
+                                           o.use_gate ? tf(L.a[P.gate[i]]) : nullptr, defer))
+                return rc;
+        }
+        if (need_dx && o.use_gate) {
+            if (int rc = gated_input_gradient(i, dy)) return rc;
+        } else if (need_dx) {
+            const float* acc = st[src].slot >= 0 ? slot_ptr(st[src].slot) : nullptr;
+            if (!acc && (st[src].slot = take()) < 0) return ORBIT_ERR_STATE;
+            if (int rc = launch_conv_dgrad(dy, fe->d_dgrad + fe->dgrad_off[i], acc, slot_ptr(st[src].slot), up, o.geom(B), s)) return rc;
+        }
+        release(kdy);
+        return ORBIT_OK;
+    }
+
+    // the input side of gated projection i: d(x * gate) = its data gradient, then the squeeze-excite backward (gate MLP + average
+    // pool) down to the gradient of x, the activated output of op P.in[i]
+    int gated_input_gradient(int i, const float* dy) {
+        const Op& o = fe->ops[i];
+        const int src = P.in[i], se = P.gate[i];
+        ORBIT_REQUIRE(se >= 0 && st[src].slot < 0, "extractor_backward: malformed squeeze-excite block");
+        const Op& so = fe->ops[se];
+        float* se_scratch = wsf(W.se[se]);  // this block's own (see se_jobs)
+        const int kt = take();
+        if (kt < 0) return ORBIT_ERR_STATE;
+        if (int rc = launch_conv_dgrad(dy, fe->d_dgrad + fe->dgrad_off[i], nullptr, slot_ptr(kt), up, o.geom(B), s)) return rc;
+        // the four parameter gradients of the block's MLP: summed over the frames for ALL blocks in one launch at the end of the
+        // reverse pass (nothing in it reads them), or by this block's own launch
+        const SeGrads dparams = wg ? SeGrads{pgrad(so.se_w1), pgrad(so.se_b1), pgrad(so.se_w2), pgrad(so.se_b2)} : SeGrads{};
+        const bool batched = wg && !se_per_block && F[se].se_batched;
+        if (batched) {
+            SeParamJob* job = nullptr;
+            if (int rc = next_se_job(&job)) return rc;
+            *job = se_bwd_param_job(se_scratch, tf(L.p[se]), B, o.Cin, so.R, dparams);
+        }
+        // x = SiLU(BatchNorm(depthwise output)): the first (reduction) pass of that BatchNorm's backward is folded into the last
+        // pass of the squeeze-excite backward, which then leaves only the sums - g itself is rebuilt by that BatchNorm's apply
+        // pass from d(x * gate) (slot kt stays the depthwise op's gradient slot)
+        const bool sums_only = F[i].se_sums_only;
+        const int k = st[src].slot = sums_only ? kt : take();
+        if (k < 0) return ORBIT_ERR_STATE;
+        SeBnFuse fuse;
+        const bool dw_src = fe->ops[src].kind == OP_DWCONV;
+        if (dw_src) {
+            fuse = BnTaped{tf(L.y[src]), fold(bn_of(src)), fe->ops[src].act, partial};
+            st[src].pre_reduced = B * se_pool_chunks(B, o.H * o.W, o.Cin);
+            if (sums_only)
+                st[src].gate = tf(L.a[se]), st[src].dpooled = se_bwd_dpooled(se_scratch, B, o.Cin, so.R), st[src].HW = o.H * o.W;
+        }
+        const SeWeights w{fe->param(so.se_w1), fe->param(so.se_b1), fe->param(so.se_w2), fe->param(so.se_b2), fe->d_packed + so.packed_off};
+        const int rc = launch_se_gate_backward(slot_ptr(kt), out_tensor(src), tf(L.p[se]), tf(L.a[se]), w,
+                                               sums_only ? nullptr : slot_ptr(k), wg && !batched ? &dparams : nullptr, se_scratch, B,
+                                               o.H * o.W, o.Cin, so.R, s, dw_src ? &fuse : nullptr);
+        if (!sums_only) release(kt);
+        return rc;
+    }
+};
 
 extern "C" {
 
@@ -681,358 +1029,11 @@ int orbit_extractor_backward(orbit_extractor_t* fe, const float* frames, int B, 
     key.p[5] = param_grads, key.p[6] = dfilm_gamma, key.p[7] = dfilm_beta, key.p[8] = workspace;
     key.v[0] = 2 /* backward */, key.v[1] = B, key.v[2] = bn_train, key.v[3] = filter_grads;
     return fe->run_train_graphed(key, (hipStream_t)stream, [&](hipStream_t s) {
-        return backward_run(fe, frames, B, film_gamma, film_beta, bn_train, dfeats, tape, param_grads, filter_grads,
-                            dfilm_gamma, dfilm_beta, workspace, s);
+        return BackwardPass(fe, frames, B, film_gamma, film_beta, bn_train, dfeats, tape, param_grads, filter_grads, dfilm_gamma,
+                            dfilm_beta, workspace, s)
+            .run();
     });
 }
-
-}  // extern "C"
-
-static int backward_run(orbit_extractor_t* fe, const float* frames, int B, const float* film_gamma,
-                        const float* film_beta, int bn_train, const float* dfeats, const void* tape, float* param_grads,
-                        int filter_grads, float* dfilm_gamma, float* dfilm_beta, void* workspace, hipStream_t s) {
-    const bool film = film_gamma && film_beta && fe->film_size > 0;
-    // filter_grads == 0: only the BatchNorm weight / bias gradients are wanted (FiLM fine-tuning of a frozen extractor,
-    // few_shot_recognisers.py:196-199): skip every filter / squeeze-excite / bias gradient
-    const bool wg = param_grads != nullptr && filter_grads != 0;
-    // (A/B and parity runs: every squeeze-excite block sums its parameter gradients in a launch of its own)
-    const bool se_per_block = filter_grads == ORBIT_FILTER_GRADS_SE_PER_BLOCK;
-    const TapeLayout L = tape_layout(fe, B);
-    const BwdLayout W = bwd_layout(fe, B);
-    const char* tp = static_cast<const char*>(tape);
-    auto tf = [&](size_t off) { return reinterpret_cast<const float*>(tp + off); };
-    char* ws = static_cast<char*>(workspace);
-    float* up = reinterpret_cast<float*>(ws + W.up);
-    float* wgrad_scratch = reinterpret_cast<float*>(ws + W.wgrad);
-    float* partial = reinterpret_cast<float*>(ws + W.partial);
-    float* cwgrad_base = reinterpret_cast<float*>(ws + W.cwgrad);
-    size_t cwgrad_used = 0;
-    WgradReduceJobs wg_jobs;
-    int n_wg_jobs = 0;
-    float* se_scratch_base = reinterpret_cast<float*>(ws + W.se);
-    size_t se_scratch_used = 0;
-    SeParamJobs se_jobs;
-    int n_se_jobs = 0;
-    auto param = [&](int k) { return fe->param(k); };
-    // a layer's slice of the fold arrays on the tape; the gamma its forward used (FiLM's or the plan's) with the matching places
-    // of its gradients
-    auto fold = [&](const BNDesc& bn) {
-        return BnFoldC{tf(L.mean) + bn.fold_off, tf(L.invstd) + bn.fold_off, tf(L.scale) + bn.fold_off, tf(L.shift) + bn.fold_off};
-    };
-    auto grads = [&](const BNDesc& bn) {
-        const bool fm = film && bn.film_off >= 0;
-        BnGrads p;
-        p.gamma = fm ? film_gamma + bn.film_off : param(bn.gamma);
-        if (fm) {
-            if (dfilm_gamma) p.dgamma = dfilm_gamma + bn.film_off, p.dbeta = dfilm_beta + bn.film_off;
-        } else if (param_grads) {
-            p.dgamma = param_grads + fe->pool.off(bn.gamma), p.dbeta = param_grads + fe->pool.off(bn.beta);
-        }
-        if (wg && bn.conv_bias >= 0) p.dbias = param_grads + fe->pool.off(bn.conv_bias);
-        return p;
-    };
-
-    const Producers P = producers(fe);
-    const TrainForms F = train_forms(fe, B, bn_train, false);
-    const int n = (int)fe->ops.size();
-    // the earliest op whose backward yields something that was asked for
-    int first_needed = n;
-    for (int i = 0; i < n && first_needed == n; ++i) {
-        const Op& o = fe->ops[i];
-        if (!has_bn(o)) continue;
-        if (param_grads || (dfilm_gamma && fe->bns[o.bn].film_off >= 0)) first_needed = i;
-    }
-
-    bool used[BwdLayout::NSLOTS] = {false};
-    std::vector<int> grad_slot(n, -1);  // gradient w.r.t. the OUTPUT tensor of op i
-    // > 0: the slot of op i already holds g = d out * act'(.) and `partial` the [n][2][C] sums of its BatchNorm backward
-    // (written by the squeeze-excite backward of the block, launch_se_gate_backward with SeBnFuse, or - for the expansion
-    // convolution - by the data gradient of the depthwise convolution it feeds, DwBnBwd)
-    std::vector<int> pre_reduced(n, 0);
-    // ... and when the squeeze-excite backward left only the SUMS: the slot of op i holds d(x * gate) and g is rebuilt in the
-    // BatchNorm's apply pass from it, the gate and the pooled-branch gradient (launch_bn_backward_reduced_gated)
-    struct GatedG {
-        const float *gate = nullptr, *dpooled = nullptr;
-        int HW = 0;
-    };
-    std::vector<GatedG> gated(n);
-    auto slot_ptr = [&](int k) { return reinterpret_cast<float*>(ws + W.slots + (size_t)k * W.slot_bytes); };
-    auto alloc = [&]() {
-        for (int k = 0; k < BwdLayout::NSLOTS; ++k)
-            if (!used[k]) {
-                used[k] = true;
-                return k;
-            }
-        return -1;
-    };
-    auto release = [&](int k) {
-        if (k >= 0) used[k] = false;
-    };
-    auto out_tensor = [&](int i) -> const float* {  // forward output of op i
-        if (i < 0) return frames;
-        const Op& o = fe->ops[i];
-        if (o.kind == OP_CONV) return o.pool2 ? tf(L.p[i]) : tf(L.a[i]);
-        if (o.kind == OP_DWCONV) return tf(L.a[i]);
-        return tf(L.p[i]);
-    };
-#define SLOT_OR_FAIL(var)                                                                      \
-    const int var = alloc();                                                                   \
-    if (var < 0) return set_err(ORBIT_ERR_STATE, "extractor_backward: gradient slots exhausted")
-
-    for (int i = n - 1; i >= first_needed; --i) {
-        const Op& o = fe->ops[i];
-        int rc = ORBIT_OK;
-        if (o.kind == OP_AVGPOOL) {
-            const int src = P.in[i];
-            if (src < first_needed) continue;
-            ORBIT_REQUIRE(grad_slot[src] < 0, "extractor_backward: unexpected fan-out into the global pool");
-            SLOT_OR_FAIL(k);
-            rc = launch_avgpool_bwd(dfeats, slot_ptr(k), B, o.H * o.W, o.Cin, s);
-            grad_slot[src] = k;
-        } else if (o.kind == OP_MAXPOOL) {
-            const int src = P.in[i];
-            const int g = grad_slot[i];
-            if (g < 0) continue;
-            if (src >= first_needed) {
-                ORBIT_REQUIRE(grad_slot[src] < 0, "extractor_backward: unexpected fan-out into a max-pool");
-                SLOT_OR_FAIL(k);
-                rc = launch_maxpool_bwd(slot_ptr(g), reinterpret_cast<const uint8_t*>(tp + L.idx[i]), slot_ptr(k), B, o.H,
-                                        o.W, o.Cin, o.pool_k, o.stride, o.pool_pad, o.Ho, o.Wo, s);
-                grad_slot[src] = k;
-            }
-            release(g), grad_slot[i] = -1;
-        } else if (o.kind == OP_SE) {
-            continue;  // handled together with the gated convolution that consumes the gate
-        } else if (o.kind == OP_DWCONV) {
-            const int g = grad_slot[i];
-            if (g < 0) continue;
-            const BNDesc& bn = fe->bns[o.bn];
-            const int M = B * o.Ho * o.Wo;
-            const int src = P.in[i];
-            const bool need_dx = src >= first_needed;
-            const bool need_dy = need_dx || wg;
-            int kdy = -1;
-            if (need_dy) {
-                kdy = alloc();
-                if (kdy < 0) return set_err(ORBIT_ERR_STATE, "extractor_backward: gradient slots exhausted");
-            }
-            float* dy = need_dy ? slot_ptr(kdy) : nullptr;
-            if (pre_reduced[i] > 0 && gated[i].gate) {
-                float* coef = partial + bn_partial_floats((size_t)pre_reduced[i], o.Cout);
-                rc = launch_bn_backward_reduced_gated(slot_ptr(g), gated[i].gate, gated[i].dpooled, gated[i].HW,
-                                                      BnTaped{tf(L.y[i]), fold(bn), o.act, partial}, grads(bn), bn_train, M, o.Cout,
-                                                      dy, pre_reduced[i], coef, s);
-            } else if (pre_reduced[i] > 0) {
-                float* coef = partial + bn_partial_floats((size_t)pre_reduced[i], o.Cout);
-                rc = launch_bn_backward_reduced(slot_ptr(g), tf(L.y[i]), fold(bn), grads(bn), bn_train, M, o.Cout, dy, partial,
-                                                pre_reduced[i], coef, s);
-            } else {
-                float* coef = partial + (size_t)bn_reduce_blocks(M, o.Cout) * 2 * o.Cout;
-                rc = launch_bn_backward(slot_ptr(g), tf(L.a[i]), tf(L.y[i]), fold(bn), grads(bn), bn_train, o.act, M, o.Cout, dy,
-                                        nullptr, 0, partial, coef, s);
-            }
-            if (rc != ORBIT_OK) return rc;
-            release(g), grad_slot[i] = -1;
-            // the producer is a convolution + BatchNorm + SiLU right before this layer (see the data gradient below), and whether
-            // the forward fed this layer that conv's RAW output (train_forms decides both)
-            const bool through_act = need_dx && F[i].through_act;
-            const bool raw_fed = F[i].raw_src >= 0;
-            // ... and on the stride-2 layers and the large 3x3 maps the filter gradient rides on that data-gradient kernel
-            // (DwBnBwd::wgrad_partial)
-            const bool wg_fused = wg && through_act && raw_fed &&
-                                  dwconv_bwd_fused_scratch_floats(B, o.H, o.W, o.Cin, o.KH, o.stride) > 0;
-            auto filter_gradient = [&]() {
-                if (raw_fed) {
-                    // the forward never wrote this layer's input: the filter gradient rebuilds it from the producing conv's raw
-                    // output as it stages its patch
-                    const BnFoldC in = fold(fe->bns[fe->ops[src].bn]);
-                    return launch_dwconv_wgrad(tf(L.y[src]), slot_ptr(kdy), param_grads + fe->pool.off(o.weight),
-                                               wgrad_scratch, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s,
-                                               in.scale, in.shift, fe->ops[src].act);
-                }
-                return launch_dwconv_wgrad(out_tensor(src), slot_ptr(kdy), param_grads + fe->pool.off(o.weight),
-                                           wgrad_scratch, B, o.H, o.W, o.Cin, o.KH, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s);
-            };
-            if (wg && !wg_fused) {
-                rc = filter_gradient();
-                if (rc != ORBIT_OK) return rc;
-            }
-            if (need_dx) {
-                ORBIT_REQUIRE(grad_slot[src] < 0, "extractor_backward: unexpected fan-out into a depthwise convolution");
-                SLOT_OR_FAIL(k);
-                grad_slot[src] = k;
-                // wgrad_scratch is free again here (the weight-gradient launches above are earlier on the stream)
-                // through_act: the data gradient goes through the producer's activation in the same kernel and leaves the channel
-                // sums of that BatchNorm's backward, so the convolution's own backward starts at the finalize step (no reduction
-                // pass over dx and y)
-                int nblk = 0, wrows = 0;
-                DwBnBwd bnb;
-                const DwBnBwd* bnb_ptr = nullptr;
-                if (through_act) {
-                    const Op& po = fe->ops[src];
-                    if (wg_fused)
-                        bnb.wgrad_partial = wgrad_scratch + dwconv_bwd_fused_partial_offset(o.Cin, o.KH), bnb.wgrad_rows = &wrows;
-                    bnb.y = tf(L.y[src]), bnb.bn = fold(fe->bns[po.bn]), bnb.act = po.act;
-                    bnb.partial = partial, bnb.nblk = &nblk;
-                    bnb_ptr = &bnb;
-                }
-                rc = launch_dwconv_dgrad(slot_ptr(kdy), fe->d_packed + o.packed_off, slot_ptr(k), B, o.H, o.W, o.Cin, o.KH,
-                                         o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s, wgrad_scratch, bnb_ptr);
-                if (rc != ORBIT_OK) return rc;
-                if (bnb_ptr) pre_reduced[src] = nblk;  // 0: that kernel form has no such epilogue, the slot holds plain dx
-                if (wg_fused)
-                    rc = wrows > 0 ? launch_dwconv_wgrad_reduce(bnb.wgrad_partial, wrows, o.KH, o.Cin,
-                                                                param_grads + fe->pool.off(o.weight), s)
-                                   : filter_gradient();
-            }
-            release(kdy);
-        } else {  // OP_CONV
-            int g = grad_slot[i];
-            if (g < 0) continue;  // no gradient reaches this op
-            const BNDesc& bn = fe->bns[o.bn];
-            const int M = B * o.Ho * o.Wo;
-            if (o.pool2) {
-                SLOT_OR_FAIL(k);
-                rc = launch_maxpool_bwd(slot_ptr(g), reinterpret_cast<const uint8_t*>(tp + L.idx[i]), slot_ptr(k), B, o.Ho,
-                                        o.Wo, o.Cout, 2, 2, 0, o.Ho / 2, o.Wo / 2, s);
-                if (rc != ORBIT_OK) return rc;
-                release(g), g = k;
-            }
-            // BatchNorm (+ReLU, + residual fan-out)
-            const BnGrads bp = grads(bn);
-            float* dres = nullptr;
-            int dres_acc = 0;
-            const int rsrc = o.res >= 0 ? P.res[i] : -1;
-            if (rsrc >= first_needed) {
-                if (grad_slot[rsrc] >= 0) {
-                    dres = slot_ptr(grad_slot[rsrc]), dres_acc = 1;
-                } else {
-                    SLOT_OR_FAIL(k);
-                    grad_slot[rsrc] = k, dres = slot_ptr(k);
-                }
-            }
-            const int src = P.in[i];
-            const bool need_dx = src >= first_needed;
-            const bool need_dy = need_dx || wg;
-            int kdy = -1;
-            if (need_dy) {
-                kdy = alloc();
-                if (kdy < 0) return set_err(ORBIT_ERR_STATE, "extractor_backward: gradient slots exhausted");
-            }
-            float* dy = need_dy ? slot_ptr(kdy) : nullptr;
-            if (pre_reduced[i] > 0) {
-                ORBIT_REQUIRE(!dres && !bp.dbias && !o.pool2, "extractor_backward: pre-reduced BatchNorm with a residual or bias");
-                float* coef = partial + bn_partial_floats((size_t)pre_reduced[i], o.Cout);
-                rc = launch_bn_backward_reduced(slot_ptr(g), tf(L.y[i]), fold(bn), bp, bn_train, M, o.Cout, dy, partial,
-                                                pre_reduced[i], coef, s);
-            } else {
-                // partial holds [blocks][2][C] followed by the 3*C apply coefficients
-                float* coef = partial + (size_t)bn_reduce_blocks(M, o.Cout) * 2 * o.Cout;
-                rc = launch_bn_backward(slot_ptr(g), tf(L.a[i]), tf(L.y[i]), fold(bn), bp, bn_train, o.act, M, o.Cout, dy, dres,
-                                        dres_acc, partial, coef, s, o.res_post);
-            }
-            if (rc != ORBIT_OK) return rc;
-            if (!need_dy && dres) {
-                // reductions only, but the residual branch still needs g: rerun the apply pass is not available
-                // without dy, so materialise it through a scratch slot
-                return set_err(ORBIT_ERR_STATE, "extractor_backward: residual fan-out without a data gradient");
-            }
-            release(g), grad_slot[i] = -1;
-            if (wg) {
-                // a gated projection: d/dW of conv(x * gate) - the gate is multiplied into x inside the kernel. The layer's
-                // partial tiles stay in a region of their own: the split reductions of all layers run as ONE launch at the end
-                float* cw = cwgrad_base + cwgrad_used;
-                cwgrad_used += align_up(conv_wgrad_scratch_floats(B, o.Cin, o.Cout, o.KH, o.KW, o.Ho, o.Wo), 64);
-                // (a full job list is flushed with a launch of its own: every layer owns its region and nothing in the pass reads
-                // the reduced gradients, so the jobs after it may reuse the list - efficientnet_v2_s holds 80 dense convs)
-                if (n_wg_jobs == WGRAD_REDUCE_JOBS) {
-                    rc = launch_conv_wgrad_reduce_batched(wg_jobs, n_wg_jobs, s);
-                    if (rc != ORBIT_OK) return rc;
-                    n_wg_jobs = 0;
-                }
-                WgradReduceJob* defer = &wg_jobs.j[n_wg_jobs];
-                rc = launch_conv_wgrad(out_tensor(src), o.x_nchw, slot_ptr(kdy), param_grads + fe->pool.off(o.weight), B,
-                                       o.H, o.W, o.Cin, o.Cout, o.KH, o.KW, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, cw, s,
-                                       o.use_gate ? tf(L.a[P.gate[i]]) : nullptr, defer);
-                if (rc != ORBIT_OK) return rc;
-                ++n_wg_jobs;
-            }
-            if (need_dx && o.use_gate) {
-                // d(x * gate): data gradient of the product, then squeeze-excite backward (gate MLP + average pool)
-                const int se = P.gate[i];
-                ORBIT_REQUIRE(se >= 0 && grad_slot[src] < 0, "extractor_backward: malformed squeeze-excite block");
-                const Op& so = fe->ops[se];
-                float* se_scratch = se_scratch_base + se_scratch_used;  // this block's own (see se_jobs)
-                se_scratch_used += align_up(se_bwd_scratch_floats(B, o.Cin, so.R), 64);
-                SLOT_OR_FAIL(kt);
-                rc = launch_conv_dgrad(slot_ptr(kdy), fe->d_dgrad + fe->dgrad_off[i], nullptr, slot_ptr(kt), up, B, o.H, o.W,
-                                       o.Cin, o.Cout, o.KH, o.KW, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s);
-                if (rc != ORBIT_OK) return rc;
-                float* pg = wg ? param_grads : nullptr;
-                // the four parameter gradients of the block's MLP: summed over the frames for ALL blocks in one launch at the
-                // end of the reverse pass (nothing in it reads them)
-                // (a full job list is flushed as the filter-gradient list above: each block owns its scratch)
-                const bool batch_params = pg != nullptr && !se_per_block && so.R <= SE_PARAM_MAX_R;
-                if (batch_params && n_se_jobs == SE_PARAM_JOBS) {
-                    rc = launch_se_param_grad_batched(se_jobs, n_se_jobs, s);
-                    if (rc != ORBIT_OK) return rc;
-                    n_se_jobs = 0;
-                }
-                if (batch_params) {
-                    se_jobs.j[n_se_jobs++] = se_bwd_param_job(se_scratch, tf(L.p[se]), B, o.Cin, so.R, pg + fe->pool.off(so.se_w1),
-                                                              pg + fe->pool.off(so.se_b1), pg + fe->pool.off(so.se_w2),
-                                                              pg + fe->pool.off(so.se_b2));
-                    pg = nullptr;
-                }
-                // x = SiLU(BatchNorm(depthwise output)): the first (reduction) pass of that BatchNorm's backward is folded
-                // into the last pass of the squeeze-excite backward, which then leaves only the sums - g itself is rebuilt by
-                // that BatchNorm's apply pass from d(x * gate) (slot kt stays the depthwise op's gradient slot)
-                SeBnFuse fuse;
-                const SeBnFuse* fuse_ptr = nullptr;
-                const bool sums_only = fe->ops[src].kind == OP_DWCONV && (unsigned long long)B * o.H * o.W * (o.Cin / 4) < (1ull << 32);
-                int k = kt;
-                if (!sums_only) {
-                    k = alloc();
-                    if (k < 0) return set_err(ORBIT_ERR_STATE, "extractor_backward: gradient slots exhausted");
-                }
-                grad_slot[src] = k;
-                if (fe->ops[src].kind == OP_DWCONV) {
-                    fuse = BnTaped{tf(L.y[src]), fold(fe->bns[fe->ops[src].bn]), fe->ops[src].act, partial};
-                    fuse_ptr = &fuse;
-                    pre_reduced[src] = B * se_pool_chunks(B, o.H * o.W, o.Cin);
-                    if (sums_only)
-                        gated[src].gate = tf(L.a[se]), gated[src].dpooled = se_bwd_dpooled(se_scratch, B, o.Cin, so.R),
-                        gated[src].HW = o.H * o.W;
-                }
-                rc = launch_se_gate_backward(slot_ptr(kt), out_tensor(src), tf(L.p[se]), tf(L.a[se]), param(so.se_w1),
-                                             param(so.se_b1), param(so.se_w2), param(so.se_b2),
-                                             sums_only ? nullptr : slot_ptr(k), pg ? pg + fe->pool.off(so.se_w1) : nullptr,
-                                             pg ? pg + fe->pool.off(so.se_b1) : nullptr,
-                                             pg ? pg + fe->pool.off(so.se_w2) : nullptr,
-                                             pg ? pg + fe->pool.off(so.se_b2) : nullptr, se_scratch, B, o.H * o.W, o.Cin,
-                                             so.R, s, fuse_ptr, fe->d_packed + so.packed_off);
-                if (!sums_only) release(kt);
-            } else if (need_dx) {
-                const float* acc = nullptr;
-                if (grad_slot[src] < 0) {
-                    SLOT_OR_FAIL(k);
-                    grad_slot[src] = k;
-                } else {
-                    acc = slot_ptr(grad_slot[src]);
-                }
-                rc = launch_conv_dgrad(slot_ptr(kdy), fe->d_dgrad + fe->dgrad_off[i], acc, slot_ptr(grad_slot[src]), up, B,
-                                       o.H, o.W, o.Cin, o.Cout, o.KH, o.KW, o.stride, o.pad_t, o.pad_l, o.Ho, o.Wo, s);
-            }
-            release(kdy);
-        }
-        if (rc != ORBIT_OK) return rc;
-    }
-#undef SLOT_OR_FAIL
-    if (int rc = launch_conv_wgrad_reduce_batched(wg_jobs, n_wg_jobs, s)) return rc;
-    return launch_se_param_grad_batched(se_jobs, n_se_jobs, s);
-}
-
-extern "C" {
 
 // diagnostics: how many training-entry calls of this plan replayed a captured graph / ran eagerly
 int orbit_extractor_train_graph_stats(const orbit_extractor_t* fe, long* replays, long* eager) {

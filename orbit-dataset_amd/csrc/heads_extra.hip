@@ -444,9 +444,8 @@ int orbit_mahalanobis_predict(const float* features, const float* means, const f
         if (int rc = launch_transpose(precisions + (size_t)c * DD, pt, D, D, s)) return rc;
         if (int rc = conv_pack_weights(pt, packed, D, D, 1, 1, 0, s)) return rc;
         ConvDesc d;
-        d.x = diff, d.w_packed = packed, d.y = first, d.scale = d.shift = d.residual = d.gate = nullptr;
-        d.B = M, d.H = 1, d.W = 1, d.Cin = D, d.Cout = D, d.KH = 1, d.KW = 1, d.stride = 1, d.pad_t = 0, d.pad_l = 0;
-        d.Ho = 1, d.Wo = 1, d.act = ORBIT_ACT_NONE, d.pool2 = 0, d.x_nchw = 0;
+        d.x = diff, d.w_packed = packed, d.y = first;
+        d.geom() = LayerGeom{M, 1, 1, D, D, 1, 1, 1, 0, 0, 1, 1};
         if (int rc = launch_conv(d, s)) return rc;
         maha_rowdot_kernel<<<cdiv(M, 4), 256, 0, s>>>(first, diff, M, D, C, c, logit_scale, logits);
         ORBIT_LAUNCH_CHECK();
@@ -478,9 +477,8 @@ int orbit_mahalanobis_predict_backward(const float* dlogits, const float* featur
         ORBIT_LAUNCH_CHECK();
         if (int rc = conv_pack_weights(psym, packed, D, D, 1, 1, 0, s)) return rc;
         ConvDesc d;
-        d.x = diff, d.w_packed = packed, d.y = g, d.scale = d.shift = d.residual = d.gate = nullptr;
-        d.B = M, d.H = 1, d.W = 1, d.Cin = D, d.Cout = D, d.KH = 1, d.KW = 1, d.stride = 1, d.pad_t = 0, d.pad_l = 0;
-        d.Ho = 1, d.Wo = 1, d.act = ORBIT_ACT_NONE, d.pool2 = 0, d.x_nchw = 0;
+        d.x = diff, d.w_packed = packed, d.y = g;
+        d.geom() = LayerGeom{M, 1, 1, D, D, 1, 1, 1, 0, 0, 1, 1};
         if (int rc = launch_conv(d, s)) return rc;
         maha_bwd_acc_kernel<<<blocks, 256, 0, s>>>(g, dlogits, M, D, C, c, logit_scale, dfeatures);
         ORBIT_LAUNCH_CHECK();

@@ -16,16 +16,11 @@ namespace orbit {
 
 using v4f = __attribute__((ext_vector_type(4))) float;
 
-// Input transform of the depthwise kernels (XF): the kernel reads the RAW output y of the producing convolution and applies
-// that layer's BatchNorm + activation, act(y * in_scale[c] + in_shift[c]), as it loads - the activated tensor is never
-// written. Used by the batch-statistics forward of passes that run no backward (csrc/extractor_train.hip): for those the
+// Input transform of the depthwise kernels (XF, DwInXf in common.h): the kernel reads the RAW output y of the producing
+// convolution and applies that layer's BatchNorm + activation, act(y * scale[c] + shift[c]), as it loads - the activated tensor
+// is never written. Used by the batch-statistics forward of passes that run no backward (csrc/extractor_train.hip): for those the
 // separate activation pass (read y, write a) over the 6x-expanded tensor disappears. Same arithmetic as
 // scale_shift_act_kernel, so the depthwise outputs are bit-identical to the two-pass form.
-struct DwInXf {
-    const float* scale;
-    const float* shift;
-    int act;
-};
 // BatchNorm-backward epilogue of the data-gradient use (DwBnBwd, common.h): g = dx * act'(z), z = y * scale + shift; the fast
 // exp / rcp of the forward activation; returns g and adds g, g * xhat to the running sums
 struct DwBnbVec {
@@ -828,32 +823,31 @@ static DwPlan dw_plan(int B, int C, int K, int stride, int Ho, int Wo, bool trai
 }
 
 static int launch_dwconv_se_impl(const float* x, const float* w_khwc, float* y, const float* scale, const float* shift,
-                                 float* pool_partial, int B, int H, int W, int C, int K, int stride, int pad_t, int pad_l, int Ho,
-                                 int Wo, int act, hipStream_t s, int stats, const float* in_scale, const float* in_shift, int in_act,
+                                 float* pool_partial, const LayerGeom& g, int act, hipStream_t s, int stats, const DwInXf& xf,
                                  const DwBnBwd* bnb);
 
 // (per-launch event record for bench.py's roofline.families: algorithmic bytes = input + output + taps, FLOP = 2 K^2 per output)
 int launch_dwconv_se(const float* x, const float* w_khwc, float* y, const float* scale, const float* shift,
-                     float* pool_partial, int B, int H, int W, int C, int K, int stride, int pad_t, int pad_l, int Ho,
-                     int Wo, int act, hipStream_t s, int stats, const float* in_scale, const float* in_shift, int in_act, const DwBnBwd* bnb) {
+                     float* pool_partial, const LayerGeom& g, int act, hipStream_t s, int stats, const DwInXf& in, const DwBnBwd* bnb) {
     int rec = -1;
     if (conv_prof_enabled()) {
+        const int C = g.Cin, K = g.KH;
         char name[48];
-        snprintf(name, sizeof(name), "dwconv<%dx%d/%d>%s", K, K, stride, bnb ? ",dgrad" : stats ? ",train" : "");
-        const double out = (double)B * Ho * Wo * C;
-        rec = prof_start(name, 2.0 * out * K * K, 4.0 * ((double)B * H * W * C + out * (bnb ? 2.0 : 1.0) + (double)K * K * C), s,
+        snprintf(name, sizeof(name), "dwconv<%dx%d/%d>%s", K, K, g.stride, bnb ? ",dgrad" : stats ? ",train" : "");
+        const double out = (double)g.B * g.Ho * g.Wo * C;
+        rec = prof_start(name, 2.0 * out * K * K, 4.0 * ((double)g.B * g.H * g.W * C + out * (bnb ? 2.0 : 1.0) + (double)K * K * C), s,
                          act == ORBIT_ACT_SILU ? out : 0.0);
     }
-    const int rc = launch_dwconv_se_impl(x, w_khwc, y, scale, shift, pool_partial, B, H, W, C, K, stride, pad_t, pad_l, Ho, Wo, act,
-                                         s, stats, in_scale, in_shift, in_act, bnb);
+    const int rc = launch_dwconv_se_impl(x, w_khwc, y, scale, shift, pool_partial, g, act, s, stats, in, bnb);
     prof_stop(rec, s);
     return rc;
 }
 
 static int launch_dwconv_se_impl(const float* x, const float* w_khwc, float* y, const float* scale, const float* shift,
-                                 float* pool_partial, int B, int H, int W, int C, int K, int stride, int pad_t, int pad_l, int Ho,
-                                 int Wo, int act, hipStream_t s, int stats, const float* in_scale, const float* in_shift, int in_act,
+                                 float* pool_partial, const LayerGeom& g, int act, hipStream_t s, int stats, const DwInXf& xf,
                                  const DwBnBwd* bnb) {
+    const int B = g.B, H = g.H, W = g.W, C = g.Cin, K = g.KH, stride = g.stride, pad_t = g.pad_t, pad_l = g.pad_l, Ho = g.Ho, Wo = g.Wo;
+    const float *in_scale = xf.scale, *in_shift = xf.shift;
     ORBIT_REQUIRE(x && w_khwc && y, "dwconv_se: null pointer");
     if (bnb) {
         ORBIT_REQUIRE(bnb->y && bnb->bn.mean && bnb->bn.invstd && bnb->bn.scale && bnb->bn.shift && bnb->partial && bnb->nblk,
@@ -865,7 +859,6 @@ static int launch_dwconv_se_impl(const float* x, const float* w_khwc, float* y, 
     ORBIT_REQUIRE(!stats || pool_partial, "dwconv_se: statistics requested without a buffer");
     ORBIT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "dwconv_se: the input transform needs scale and shift");
     ORBIT_REQUIRE(!in_scale || stats, "dwconv_se: the input transform is instantiated for the statistics form only");
-    const DwInXf xf{in_scale, in_shift, in_act};
     const bool use_xf = in_scale != nullptr;
     ORBIT_REQUIRE(C % 4 == 0, "dwconv_se: C %% 4 != 0 (C=%d)", C);
     ORBIT_REQUIRE((K == 3 || K == 5) && (stride == 1 || stride == 2), "dwconv_se: K=%d stride=%d not instantiated", K,
@@ -979,8 +972,8 @@ int dwconv_pack_weights(const float* w, float* w_khwc, int C, int K, hipStream_t
     return ORBIT_OK;
 }
 
-int launch_maxpool(const float* x, float* y, int B, int H, int W, int C, int K, int stride, int pad, int Ho,
-                   int Wo, hipStream_t s) {
+int launch_maxpool(const float* x, float* y, const LayerGeom& g, hipStream_t s) {
+    const int B = g.B, H = g.H, W = g.W, C = g.Cin, K = g.KH, stride = g.stride, pad = g.pad_t, Ho = g.Ho, Wo = g.Wo;
     ORBIT_REQUIRE(x && y, "maxpool: null pointer");
     ORBIT_REQUIRE(C % 4 == 0, "maxpool: C %% 4 != 0 (C=%d)", C);
     const size_t total = (size_t)B * Ho * Wo * (C / 4);
@@ -1025,7 +1018,7 @@ int orbit_op_dwconv2d(const float* x, const float* w, float* y, const float* sca
     ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&wp), (size_t)C * K * K * sizeof(float), s));
     int rc = dwconv_pack_weights(w, wp, C, K, s);
     if (rc == ORBIT_OK)
-        rc = launch_dwconv_se(x, wp, y, scale, shift, nullptr, B, H, W, C, K, stride, pad_top, pad_left, Ho, Wo, act, s);
+        rc = launch_dwconv_se(x, wp, y, scale, shift, nullptr, LayerGeom{B, H, W, C, C, K, K, stride, pad_top, pad_left, Ho, Wo}, act, s);
     (void)hipFreeAsync(wp, s);
     return rc;
 }
@@ -1046,8 +1039,8 @@ int orbit_op_dwconv2d_train(const float* x, const float* w, float* y, const floa
     float* part = tmp + ((wfl + 63) & ~(size_t)63);
     int rc = dwconv_pack_weights(w, tmp, C, K, s);
     if (rc == ORBIT_OK)
-        rc = launch_dwconv_se(x, tmp, y, nullptr, nullptr, part, B, H, W, C, K, stride, pad_top, pad_left, Ho, Wo,
-                              ORBIT_ACT_NONE, s, 1, in_scale, in_shift, in_act);
+        rc = launch_dwconv_se(x, tmp, y, nullptr, nullptr, part, LayerGeom{B, H, W, C, C, K, K, stride, pad_top, pad_left, Ho, Wo},
+                              ORBIT_ACT_NONE, s, 1, DwInXf{in_scale, in_shift, in_act});
     // "mean" and "invstd" outputs of the finalize carry the statistics back: mean = sum / M; from invstd the test recovers
     // the variance. Simpler for a test: finalize with M = 1 and eps = 0 is not meaningful - sum the partials directly
     if (rc == ORBIT_OK) rc = launch_sum_partials(part, nblk, C, stats, s);
@@ -1057,7 +1050,7 @@ int orbit_op_dwconv2d_train(const float* x, const float* w, float* y, const floa
 
 int orbit_op_maxpool2d(const float* x, float* y, int B, int H, int W, int C, int K, int stride, int pad,
                        int Ho, int Wo, orbit_stream_t stream) {
-    return launch_maxpool(x, y, B, H, W, C, K, stride, pad, Ho, Wo, (hipStream_t)stream);
+    return launch_maxpool(x, y, LayerGeom{B, H, W, C, C, K, K, stride, pad, pad, Ho, Wo}, (hipStream_t)stream);
 }
 
 int orbit_op_avgpool(const float* x, float* y, int B, int HW, int C, orbit_stream_t stream) {

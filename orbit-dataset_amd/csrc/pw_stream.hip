@@ -254,8 +254,8 @@ int orbit_op_pw_stream(const float* x, const float* w, const float* scale, const
         if (rc == ORBIT_OK) {
             ConvDesc d;
             d.x = x, d.w_packed = wp, d.w_frag = ffl ? wp + nfl : nullptr, d.y = y, d.scale = scale, d.shift = shift;
-            d.residual = residual, d.gate = gate, d.B = B, d.H = H, d.W = W, d.Cin = Cin, d.Cout = Cout, d.KH = d.KW = 1;
-            d.stride = 1, d.pad_t = d.pad_l = 0, d.Ho = H, d.Wo = W, d.act = ORBIT_ACT_NONE, d.pool2 = 0, d.x_nchw = 0;
+            d.residual = residual, d.gate = gate;
+            d.geom() = LayerGeom{B, H, W, Cin, Cout, 1, 1, 1, 0, 0, H, W};
             rc = launch_conv(d, s);  // (no split-K workspace: as the plan, these layers never split)
         }
     }

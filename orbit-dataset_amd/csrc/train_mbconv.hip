@@ -801,8 +801,8 @@ static DwWgLdsGeom dw_wgrad_lds_geom(int B, int H, int W, int C, int K, int S, i
     g.groups = cdiv(tiles, g.tpb);
     return g;
 }
-bool dwconv_wgrad_xf_supported(int B, int H, int W, int C, int K, int stride, int Ho, int Wo) {
-    return dw_wgrad_lds_geom(B, H, W, C, K, stride, Ho, Wo).ok;
+bool dwconv_wgrad_xf_supported(const LayerGeom& g) {
+    return dw_wgrad_lds_geom(g.B, g.H, g.W, g.Cin, g.KH, g.stride, g.Ho, g.Wo).ok;
 }
 
 // dw[c][0][kh][kw] = sum over chunks of partial[chunk][tap][c]: 16 outputs per block, 16 lanes per output take every
@@ -849,11 +849,10 @@ int launch_colmean(const float* x, float* pooled, int B, int HW, int C, hipStrea
 // scratch: du [B*C] | dv [B*R] | h [B*R] | dgate [B*C] | dpooled [B*C]
 size_t se_bwd_scratch_floats(int B, int C, int R) { return (size_t)B * (3 * (size_t)C + 2 * (size_t)R) + 16; }
 
-SeParamJob se_bwd_param_job(const float* scratch, const float* pooled, int B, int C, int R, float* dw1, float* db1, float* dw2,
-                            float* db2) {
+SeParamJob se_bwd_param_job(const float* scratch, const float* pooled, int B, int C, int R, const SeGrads& d) {
     SeParamJob j;
     j.du = scratch, j.dv = scratch + (size_t)B * C, j.h = j.dv + (size_t)B * R, j.pooled = pooled;
-    j.B = B, j.C = C, j.R = R, j.dw1 = dw1, j.db1 = db1, j.dw2 = dw2, j.db2 = db2;
+    j.B = B, j.C = C, j.R = R, j.dw1 = d.dw1, j.db1 = d.db1, j.dw2 = d.dw2, j.db2 = d.db2;
     return j;
 }
 int launch_se_param_grad_batched(const SeParamJobs& jobs, int n, hipStream_t s) {
@@ -877,10 +876,9 @@ const float* se_bwd_dpooled(const float* scratch, int B, int C, int R) {
     return scratch + (size_t)B * C + 2 * (size_t)B * R + (size_t)B * C;  // (the layout launch_se_gate_backward lays down)
 }
 
-int launch_se_gate_backward(const float* dxg, const float* x, const float* pooled, const float* gate, const float* w1,
-                            const float* b1, const float* w2, const float* b2, float* dx, float* dw1, float* db1,
-                            float* dw2, float* db2, float* scratch, int B, int HW, int C, int R, hipStream_t s,
-                            const SeBnFuse* bn, const float* w2t) {
+int launch_se_gate_backward(const float* dxg, const float* x, const float* pooled, const float* gate, const SeWeights& w,
+                            float* dx, const SeGrads* dparams, float* scratch, int B, int HW, int C, int R, hipStream_t s,
+                            const SeBnFuse* bn) {
     ORBIT_REQUIRE(C % 4 == 0 && R > 0 && R <= 256, "se_gate_backward: bad sizes (C=%d R=%d)", C, R);
     ORBIT_REQUIRE(dx || bn, "se_gate_backward: dx may only be omitted with the BatchNorm fusion");
     float* du = scratch;
@@ -893,10 +891,11 @@ int launch_se_gate_backward(const float* dxg, const float* x, const float* poole
     gate_bwd_reduce_kernel<<<dim3(B, yg), 256, 0, s>>>(dxg, x, dgate, HW, C / 4, G, Rl);
     ORBIT_LAUNCH_CHECK();
     const size_t lds = (size_t)(2 * C + 3 * R) * sizeof(float);
-    se_bwd_kernel<<<B, 256, lds, s>>>(pooled, w1, b1, w2, w2t, b2, dgate, du, dv, h, dp, C, R);
+    se_bwd_kernel<<<B, 256, lds, s>>>(pooled, w.w1, w.b1, w.w2, w.w2t, w.b2, dgate, du, dv, h, dp, C, R);
     ORBIT_LAUNCH_CHECK();
-    if (dw1) {
-        se_param_grad_kernel<<<cdiv(2 * C * R + C + R, 16), 256, 0, s>>>(du, dv, h, pooled, B, C, R, dw1, db1, dw2, db2);
+    if (dparams) {
+        se_param_grad_kernel<<<cdiv(2 * C * R + C + R, 16), 256, 0, s>>>(du, dv, h, pooled, B, C, R, dparams->dw1, dparams->db1,
+                                                                         dparams->dw2, dparams->db2);
         ORBIT_LAUNCH_CHECK();
     }
     if (bn != nullptr) {
@@ -936,9 +935,9 @@ static int dgrad_s2_blocks(int B, int H, int W, int C) {
     // (2048 row blocks when the BatchNorm sums ride along: each is a partial row of 2 * C floats; 16384 without)
     return (int)std::min<size_t>((blocks2 + R - 1) / R, 16384);
 }
-int dwconv_dgrad_bn_blocks(int B, int H, int W, int C, int stride) {
-    if (stride == 1) return B * dwconv_se_chunks(H);
-    return std::min(dgrad_s2_blocks(B, H, W, C), 2048);
+int dwconv_dgrad_bn_blocks(const LayerGeom& g) {
+    if (g.stride == 1) return g.B * dwconv_se_chunks(g.H);
+    return std::min(dgrad_s2_blocks(g.B, g.H, g.W, g.Cin), 2048);
 }
 // row blocks of the stride-2 kernel when the filter gradient rides along: a block's [K*K + 2][C] partial rows stay a few
 // percent of what it streams (about 9 quads per row lane and 2x2 block), at most 2048 rows
@@ -950,7 +949,8 @@ static int dgrad_s2_fused_blocks(int B, int H, int W, int C, int K) {
     return (int)std::max<size_t>(1, std::min<size_t>(2048, blocks2 / std::max<size_t>(per_block * 2, 1)));
 }
 size_t dwconv_bwd_fused_partial_offset(int C, int K) { return (size_t)(C * K * K + 3) / 4 * 4; }
-size_t dwconv_bwd_fused_scratch_floats(int B, int H, int W, int C, int K, int stride) {
+size_t dwconv_bwd_fused_scratch_floats(const LayerGeom& g) {
+    const int B = g.B, H = g.H, W = g.W, C = g.Cin, K = g.KH, stride = g.stride;
     if (C % 4 != 0 || (K != 3 && K != 5)) return 0;
     if (stride == 2) return dwconv_bwd_fused_partial_offset(C, K) + (size_t)dgrad_s2_fused_blocks(B, H, W, C, K) * K * K * C;
     // stride 1: the register-window kernel (the data gradient is a forward depthwise pass over dy with H output rows)
@@ -964,8 +964,9 @@ int launch_dwconv_wgrad_reduce(const float* partial, int rows, int K, int C, flo
     return ORBIT_OK;
 }
 
-int launch_dwconv_dgrad(const float* dy, const float* w_khwc, float* dx, int B, int H, int W, int C, int K, int stride,
-                        int pad_t, int pad_l, int Ho, int Wo, hipStream_t s, float* flip_scratch, const DwBnBwd* bnb) {
+int launch_dwconv_dgrad(const float* dy, const float* w_khwc, float* dx, const LayerGeom& g, hipStream_t s, float* flip_scratch,
+                        const DwBnBwd* bnb) {
+    const int B = g.B, H = g.H, W = g.W, C = g.Cin, K = g.KH, stride = g.stride, pad_t = g.pad_t, pad_l = g.pad_l, Ho = g.Ho, Wo = g.Wo;
     if (bnb) {
         *bnb->nblk = 0;
         ORBIT_REQUIRE((bnb->wgrad_partial == nullptr) == (bnb->wgrad_rows == nullptr), "dwconv_dgrad: wgrad_partial without wgrad_rows");
@@ -977,8 +978,8 @@ int launch_dwconv_dgrad(const float* dy, const float* w_khwc, float* dx, int B, 
         // (180-200 us: K*K loads of dy and K*K loads of w per pixel, each behind its bounds branch)
         dwconv_flip_kernel<<<cdiv(K * K * C, 256), 256, 0, s>>>(w_khwc, flip_scratch, K * K, C);
         ORBIT_LAUNCH_CHECK();
-        return launch_dwconv_se(dy, flip_scratch, dx, nullptr, nullptr, nullptr, B, Ho, Wo, C, K, 1, K - 1 - pad_t,
-                                K - 1 - pad_l, H, W, ORBIT_ACT_NONE, s, 0, nullptr, nullptr, 0, bnb);
+        return launch_dwconv_se(dy, flip_scratch, dx, nullptr, nullptr, nullptr,
+                                LayerGeom{B, Ho, Wo, C, C, K, K, 1, K - 1 - pad_t, K - 1 - pad_l, H, W}, ORBIT_ACT_NONE, s, 0, {}, bnb);
     }
 
     ORBIT_REQUIRE(C % 4 == 0 && (K == 3 || K == 5), "dwconv_dgrad: C %% 4 != 0 or K not in {3,5}");
@@ -1026,14 +1027,16 @@ int launch_dwconv_dgrad(const float* dy, const float* w_khwc, float* dx, int B, 
     return ORBIT_OK;
 }
 
-size_t dwconv_wgrad_scratch_floats(int B, int Ho, int Wo, int C, int K) {
+size_t dwconv_wgrad_scratch_floats(const LayerGeom& g) {
     // (the LDS form writes at most 512 partial rows, whatever stride the caller's layer has)
-    return (size_t)std::max(dwconv_wgrad_chunks(B, Ho, Wo, C), 512) * K * K * C;
+    return (size_t)std::max(dwconv_wgrad_chunks(g.B, g.Ho, g.Wo, g.Cin), 512) * g.KH * g.KH * g.Cin;
 }
 
-int launch_dwconv_wgrad(const float* x, const float* dy, float* dw, float* scratch, int B, int H, int W, int C, int K,
-                        int stride, int pad_t, int pad_l, int Ho, int Wo, hipStream_t s, const float* in_scale,
-                        const float* in_shift, int in_act) {
+int launch_dwconv_wgrad(const float* x, const float* dy, float* dw, float* scratch, const LayerGeom& g, hipStream_t s,
+                        const DwInXf& in) {
+    const int B = g.B, H = g.H, W = g.W, C = g.Cin, K = g.KH, stride = g.stride, pad_t = g.pad_t, pad_l = g.pad_l, Ho = g.Ho, Wo = g.Wo;
+    const float *in_scale = in.scale, *in_shift = in.shift;
+    const int in_act = in.act;
     ORBIT_REQUIRE(C % 4 == 0 && (K == 3 || K == 5), "dwconv_wgrad: C %% 4 != 0 or K not in {3,5}");
     ORBIT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "dwconv_wgrad: the input transform needs scale and shift");
     ORBIT_REQUIRE(stride == 1 || stride == 2, "dwconv_wgrad: stride %d", stride);
@@ -1090,13 +1093,12 @@ int orbit_op_dwconv2d_backward(const float* x, const float* w, const float* dy, 
     hipStream_t s = (hipStream_t)stream;
     float* tmp = nullptr;
     const size_t npack = (size_t)(C * K * K + 3) / 4 * 4;
-    const size_t nscr = dwconv_wgrad_scratch_floats(B, Ho, Wo, C, K);
+    const LayerGeom g{B, H, W, C, C, K, K, stride, pad_top, pad_left, Ho, Wo};
+    const size_t nscr = dwconv_wgrad_scratch_floats(g);
     ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (npack + nscr) * sizeof(float), s));
     int rc = dwconv_pack_weights(w, tmp, C, K, s);
-    if (rc == ORBIT_OK && dx)
-        rc = launch_dwconv_dgrad(dy, tmp, dx, B, H, W, C, K, stride, pad_top, pad_left, Ho, Wo, s, tmp + npack);
-    if (rc == ORBIT_OK && dw)
-        rc = launch_dwconv_wgrad(x, dy, dw, tmp + npack, B, H, W, C, K, stride, pad_top, pad_left, Ho, Wo, s);
+    if (rc == ORBIT_OK && dx) rc = launch_dwconv_dgrad(dy, tmp, dx, g, s, tmp + npack);
+    if (rc == ORBIT_OK && dw) rc = launch_dwconv_wgrad(x, dy, dw, tmp + npack, g, s);
     (void)hipFreeAsync(tmp, s);
     return rc;
 }
@@ -1108,16 +1110,17 @@ int orbit_op_dwconv2d_dgrad_bn(const float* dy, const float* w, const float* y_r
     hipStream_t s = (hipStream_t)stream;
     float* tmp = nullptr;
     const size_t npack = (size_t)(C * K * K + 3) / 4 * 4;
-    const size_t nfused = dw ? dwconv_bwd_fused_scratch_floats(B, H, W, C, K, stride) : 0;
+    const LayerGeom geom{B, H, W, C, C, K, K, stride, pad_top, pad_left, Ho, Wo};
+    const size_t nfused = dw ? dwconv_bwd_fused_scratch_floats(geom) : 0;
     if (dw && nfused == 0) return set_err(ORBIT_ERR_ARG, "op_dwconv2d_dgrad_bn: no kernel form carries the filter gradient for this layer");
-    const size_t nscr = std::max(dwconv_wgrad_scratch_floats(B, Ho, Wo, C, K), nfused);
-    const size_t npart = bn_partial_floats((size_t)dwconv_dgrad_bn_blocks(B, H, W, C, stride), C);
+    const size_t nscr = std::max(dwconv_wgrad_scratch_floats(geom), nfused);
+    const size_t npart = bn_partial_floats((size_t)dwconv_dgrad_bn_blocks(geom), C);
     ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (npack + nscr + npart) * sizeof(float), s));
     int nblk = 0, wrows = 0;
     DwBnBwd bnb{{y_raw, {mean, invstd, scale, shift}, act, tmp + npack + nscr}, &nblk};
     if (dw) bnb.wgrad_partial = tmp + npack + dwconv_bwd_fused_partial_offset(C, K), bnb.wgrad_rows = &wrows;
     int rc = dwconv_pack_weights(w, tmp, C, K, s);
-    if (rc == ORBIT_OK) rc = launch_dwconv_dgrad(dy, tmp, g, B, H, W, C, K, stride, pad_top, pad_left, Ho, Wo, s, tmp + npack, &bnb);
+    if (rc == ORBIT_OK) rc = launch_dwconv_dgrad(dy, tmp, g, geom, s, tmp + npack, &bnb);
     if (rc == ORBIT_OK && nblk <= 0) rc = set_err(ORBIT_ERR_ARG, "op_dwconv2d_dgrad_bn: no kernel form with the epilogue for this layer");
     if (rc == ORBIT_OK && dw && wrows <= 0) rc = set_err(ORBIT_ERR_ARG, "op_dwconv2d_dgrad_bn: no kernel form carries the filter gradient for this layer");
     if (rc == ORBIT_OK) rc = launch_sum_partials(bnb.partial, nblk, C, sums, s);
@@ -1130,12 +1133,12 @@ int orbit_op_dwconv2d_wgrad_xf(const float* x_raw, const float* in_scale, const 
                                float* dw, int B, int H, int W, int C, int K, int stride, int pad_top, int pad_left, int Ho, int Wo,
                                orbit_stream_t stream) {
     ORBIT_REQUIRE(x_raw && in_scale && in_shift && dy && dw, "op_dwconv2d_wgrad_xf: null pointer");
-    ORBIT_REQUIRE(dwconv_wgrad_xf_supported(B, H, W, C, K, stride, Ho, Wo), "op_dwconv2d_wgrad_xf: the LDS form does not fit this layer");
+    const LayerGeom g{B, H, W, C, C, K, K, stride, pad_top, pad_left, Ho, Wo};
+    ORBIT_REQUIRE(dwconv_wgrad_xf_supported(g), "op_dwconv2d_wgrad_xf: the LDS form does not fit this layer");
     hipStream_t s = (hipStream_t)stream;
     float* tmp = nullptr;
-    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), dwconv_wgrad_scratch_floats(B, Ho, Wo, C, K) * sizeof(float), s));
-    const int rc = launch_dwconv_wgrad(x_raw, dy, dw, tmp, B, H, W, C, K, stride, pad_top, pad_left, Ho, Wo, s, in_scale, in_shift,
-                                       in_act);
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), dwconv_wgrad_scratch_floats(g) * sizeof(float), s));
+    const int rc = launch_dwconv_wgrad(x_raw, dy, dw, tmp, g, s, DwInXf{in_scale, in_shift, in_act});
     (void)hipFreeAsync(tmp, s);
     return rc;
 }
@@ -1166,16 +1169,16 @@ int orbit_op_se_gate_backward_ex(const float* dxg, const float* x, const float* 
     float* w2t = gate + (size_t)B * C;  // [R][C], as the network plans pack it
     int rc = launch_se_gate(pooled, w1, b1, w2, b2, gate, B, C, R, s);
     if (rc == ORBIT_OK) rc = launch_transpose(w2, w2t, C, R, s);
+    const SeWeights sw{w1, b1, w2, b2, w2t};
+    const SeGrads dparams{dw1, db1, dw2, db2};
     if (rc == ORBIT_OK && batched) {
         // as the reverse pass of a network: the block leaves (du, dv, h) in its scratch, the batched kernel sums the frames
-        rc = launch_se_gate_backward(dxg, x, pooled, gate, w1, b1, w2, b2, dx, nullptr, nullptr, nullptr, nullptr, tmp, B, HW, C, R,
-                                     s, nullptr, w2t);
+        rc = launch_se_gate_backward(dxg, x, pooled, gate, sw, dx, nullptr, tmp, B, HW, C, R, s);
         SeParamJobs jobs;
-        jobs.j[0] = se_bwd_param_job(tmp, pooled, B, C, R, dw1, db1, dw2, db2);
+        jobs.j[0] = se_bwd_param_job(tmp, pooled, B, C, R, dparams);
         if (rc == ORBIT_OK) rc = launch_se_param_grad_batched(jobs, 1, s);
     } else if (rc == ORBIT_OK) {
-        rc = launch_se_gate_backward(dxg, x, pooled, gate, w1, b1, w2, b2, dx, dw1, db1, dw2, db2, tmp, B, HW, C, R, s, nullptr,
-                                     w2t);
+        rc = launch_se_gate_backward(dxg, x, pooled, gate, sw, dx, dw1 ? &dparams : nullptr, tmp, B, HW, C, R, s);
     }
     (void)hipFreeAsync(tmp, s);
     return rc;

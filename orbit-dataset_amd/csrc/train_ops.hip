@@ -818,8 +818,8 @@ int launch_bn_backward_reduced_gated(const float* dxg, const float* gate, const 
     return ORBIT_OK;
 }
 
-int launch_maxpool_idx(const float* x, float* y, uint8_t* idx, int B, int H, int W, int C, int K, int stride, int pad,
-                       int Ho, int Wo, hipStream_t s) {
+int launch_maxpool_idx(const float* x, float* y, uint8_t* idx, const LayerGeom& g, hipStream_t s) {
+    const int B = g.B, H = g.H, W = g.W, C = g.Cin, K = g.KH, stride = g.stride, pad = g.pad_t, Ho = g.Ho, Wo = g.Wo;
     ORBIT_REQUIRE(C % 4 == 0 && K * K <= 255, "maxpool: C %% 4 != 0 or window too large");
     ORBIT_REQUIRE((unsigned long long)((size_t)B * Ho * Wo * (C / 4)) < (1ull << 32), "tensor too large for the 32-bit index arithmetic of this kernel");
     maxpool_idx_kernel<<<grid_for((size_t)B * Ho * Wo * (C / 4)), 256, 0, s>>>(x, y, idx, B, H, W, C / 4, K, stride, pad,
@@ -828,8 +828,8 @@ int launch_maxpool_idx(const float* x, float* y, uint8_t* idx, int B, int H, int
     return ORBIT_OK;
 }
 
-int launch_maxpool_bwd(const float* dy, const uint8_t* idx, float* dx, int B, int H, int W, int C, int K, int stride,
-                       int pad, int Ho, int Wo, hipStream_t s) {
+int launch_maxpool_bwd(const float* dy, const uint8_t* idx, float* dx, const LayerGeom& g, hipStream_t s) {
+    const int B = g.B, H = g.H, W = g.W, C = g.Cin, K = g.KH, stride = g.stride, pad = g.pad_t, Ho = g.Ho, Wo = g.Wo;
     ORBIT_REQUIRE(C % 4 == 0, "maxpool_backward: C %% 4 != 0");
     ORBIT_REQUIRE((unsigned long long)((size_t)B * H * W * (C / 4)) < (1ull << 32), "tensor too large for the 32-bit index arithmetic of this kernel");
     maxpool_bwd_kernel<<<grid_for((size_t)B * H * W * (C / 4)), 256, 0, s>>>(dy, idx, dx, B, H, W, C / 4, K, stride, pad,
@@ -1042,13 +1042,13 @@ int orbit_op_scale_shift_act(const float* y, const float* scale, const float* sh
 int orbit_op_maxpool2d_train(const float* x, float* y, uint8_t* idx, int B, int H, int W, int C, int K, int stride,
                              int pad, int Ho, int Wo, orbit_stream_t stream) {
     ORBIT_REQUIRE(x && y && idx, "op_maxpool2d_train: null pointer");
-    return launch_maxpool_idx(x, y, idx, B, H, W, C, K, stride, pad, Ho, Wo, (hipStream_t)stream);
+    return launch_maxpool_idx(x, y, idx, LayerGeom{B, H, W, C, C, K, K, stride, pad, pad, Ho, Wo}, (hipStream_t)stream);
 }
 
 int orbit_op_maxpool2d_backward(const float* dy, const uint8_t* idx, float* dx, int B, int H, int W, int C, int K,
                                 int stride, int pad, int Ho, int Wo, orbit_stream_t stream) {
     ORBIT_REQUIRE(dy && idx && dx, "op_maxpool2d_backward: null pointer");
-    return launch_maxpool_bwd(dy, idx, dx, B, H, W, C, K, stride, pad, Ho, Wo, (hipStream_t)stream);
+    return launch_maxpool_bwd(dy, idx, dx, LayerGeom{B, H, W, C, C, K, K, stride, pad, pad, Ho, Wo}, (hipStream_t)stream);
 }
 
 int orbit_op_avgpool_backward(const float* dy, float* dx, int B, int HW, int C, orbit_stream_t stream) {

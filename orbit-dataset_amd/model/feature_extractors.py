@@ -566,9 +566,11 @@ class EfficientNetV2S(HipNetwork):
     tree, state_dict keys, order and shapes as the timm module; FiLM on root bn1 / bn2, ConvBnAct.bn1, EdgeResidual.bn1 and
     InvertedResidual.bn2 (reference model/film.py:38-56). Any frame size.
 
-    Inference only by default: the ConvBnAct blocks add their skip after the activation, and the plans this class builds report
-    no training path (orbit_extractor_supports_training is 0). A forward that would record a tape or use batch statistics raises
-    NotImplementedError before anything is launched. With `native_backward = True` set on the instance, a forward in eval()
+    Inference only by default: the ConvBnAct blocks add their skip after the activation, and a plan created without the opt-in
+    flags below reports no training path (orbit_extractor_supports_training is 0); a forward that would record a tape or use
+    batch statistics then raises NotImplementedError before anything is launched. Two opt-ins add training: `native_backward`
+    (FiLM / BatchNorm gradients through the frozen network) and `native_weight_backward` (batch statistics and every parameter
+    gradient). With `native_backward = True` set on the instance, a forward in eval()
     whose FiLM vectors require a gradient - the `film=` pair, or BatchNorm tensors swapped in by functional_call - records a tape
     on a plan created with ORBIT_PLAN_UNFUSED | ORBIT_PLAN_RES_POST_BACKWARD and gets their gradients through the FROZEN network
     from orbit_extractor_backward (autograd.ExtractorFunction); so do the FiLM-slot BatchNorm weights / biases themselves when
