@@ -257,7 +257,15 @@ int orbit_extractor_forward(orbit_extractor_t* fe, const float* frames, int B,
  * family (orbit_extractor_create rejects these names). H = W = 224 only (reference utils/args.py: --frame_size 224 for
  * these backbones; the position table is fixed). Creation and enumeration do not touch the device. Inference only by default:
  * orbit_vit_train_forward / orbit_vit_backward below give the gradients of the FiLM vectors of the FROZEN network (the reference's
- * --adapt_features recipes), orbit_vit_backward_params those of every parameter as well (--learn_extractor). */
+ * --adapt_features recipes), orbit_vit_backward_params those of every parameter as well (--learn_extractor).
+ * Six models: the patch-16 members of the same families - "vit_s_16", "vit_b_16" (timm `vit_small_patch16_224_in21k`,
+ * `vit_base_patch16_224_in21k`, named by analogy with the patch-32 ones) and "vit_b_16_clip" (the laion2b CLIP B/16) - have the
+ * same module tree, state_dict keys and FiLM slots; patch_embed.proj.weight is [D][3][16][16], pos_embed [1][197][D], and a
+ * frame is 196 patches + the class token. They are inference + FiLM only: orbit_vit_tape_bytes,
+ * orbit_vit_backward_workspace_bytes and orbit_vit_backward_params_workspace_bytes return 0 and the three training entry points
+ * return ORBIT_ERR_ARG naming the model, before any launch or allocation. Batch cap: 1..8192 frames for the patch-32 plans,
+ * 1..2048 for the patch-16 plans (B * 197 * 4 D stays below 2^31); beyond it orbit_vit_workspace_bytes returns 0 and
+ * orbit_vit_forward ORBIT_ERR_ARG. */
 int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out);
 void orbit_vit_destroy(orbit_vit_t* v);
 /* timm state_dict keys in timm's order: cls_token, pos_embed, patch_embed.proj.{weight,bias (not CLIP)}, norm_pre.* (CLIP),
@@ -279,7 +287,8 @@ int orbit_vit_film_slot_channels(const orbit_vit_t* v, int slot);
 const char* orbit_vit_film_slot_name(const orbit_vit_t* v, int slot);
 int orbit_vit_film_size(const orbit_vit_t* v);
 size_t orbit_vit_workspace_bytes(const orbit_vit_t* v, int B);
-/* patch embedding + the four linear layers + QK^T and PV, per frame */
+/* patch embedding + the four linear layers + QK^T and PV, per frame (N tokens, P = N - 1 patches of 3 p^2 values):
+ * P * 3 p^2 * D + 12 * (12 D^2 N + 2 N^2 D) */
 double orbit_vit_macs_per_frame(const orbit_vit_t* v);
 /* frames [B][3][224][224] NCHW fp32 -> feats [B][D] (model/few_shot_recognisers.py:99-153 with a ViT extractor).
  * film_gamma / film_beta: NULL, or the LayerNorm weight / bias of every FiLM slot concatenated in slot order. */
@@ -401,11 +410,22 @@ int orbit_op_vit_linear(const float* x, const float* w, const float* bias, const
  * cls_token + pos_embed[0], row 1+p = patch p (row-major 7x7) . w + bias + pos_embed[1+p]. D is 384 or 768. */
 int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,
                              const float* cls_token, float* tokens, int B, int D, int tile_rows, orbit_stream_t stream);
+/* The same with the patch size: patch 32 is the call above; patch 16 (reference model/feature_extractors.py:49-63 with timm's
+ * patch16 models: PatchEmbed = Conv2d(3, D, 16, stride 16), flatten, transpose) takes w OIHW [D][3][16][16], pos_embed [197][D]
+ * and writes tokens [B][197][D], row 1+p = patch p (row-major 14x14). B at most 2048 at patch 16. */
+int orbit_op_vit_patch_embed_p(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,
+                               const float* cls_token, float* tokens, int B, int D, int patch, int tile_rows,
+                               orbit_stream_t stream);
 /* LayerNorm over the D (384 or 768) values of each row; row r at x + r * x_stride / y + r * y_stride floats; y may alias x. */
 int orbit_op_vit_layernorm(const float* x, size_t x_stride, float* y, size_t y_stride, int rows, int D, const float* gamma,
                            const float* beta, float eps, orbit_stream_t stream);
 /* qkv [B][50][3][heads][64] -> out [B][50][heads][64] = softmax(q k^T / 8) v per (frame, head); D = 64 heads, 384 or 768. */
 int orbit_op_vit_attention(const float* qkv, float* out, int B, int D, int heads, orbit_stream_t stream);
+/* The same with the token count (timm Attention.forward, which reference model/feature_extractors.py:49-63 runs inside every
+ * block): qkv [B][tokens][3][heads][64] -> out [B][tokens][heads][64]. tokens = 50 is the call above; tokens = 197 (the patch-16
+ * models) runs QK^T and PV on the fp32 matrix cores with the padded keys 197..223 masked out of the softmax; qkv and out then
+ * 16-byte aligned and B at most 2048. Any other token count is an argument error. */
+int orbit_op_vit_attention_tokens(const float* qkv, float* out, int B, int tokens, int D, int heads, orbit_stream_t stream);
 /* The backward kernels of orbit_vit_backward one by one.
  * dx [M][K] = dy [M][N] . w [N][K] (w in the torch Linear layout; wt_scratch [K][N] receives its transpose, which the GEMM of
  * orbit_op_vit_linear then reads), optionally times GELU'(u) (u [M][K], the erf form: Phi(u) + u phi(u)) or plus residual [M][K]

@@ -92,6 +92,8 @@ _SIGNATURES = {
     "orbit_op_vit_patch_embed": (c_int, [P] * 6 + [c_int] * 3 + [P]),
     "orbit_op_vit_layernorm": (c_int, [P, c_size_t, P, c_size_t, c_int, c_int, P, P, c_float, P]),
     "orbit_op_vit_attention": (c_int, [P, P, c_int, c_int, c_int, P]),
+    "orbit_op_vit_attention_tokens": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
+    "orbit_op_vit_patch_embed_p": (c_int, [P] * 6 + [c_int] * 4 + [P]),
     "orbit_op_vit_linear_dgrad": (c_int, [P] * 6 + [c_int] * 4 + [P]),
     "orbit_op_vit_layernorm_bwd": (c_int, [P, c_size_t, P, c_size_t, P, c_float, P, P, c_size_t, c_int, c_int, P, P, P,
                                            c_size_t, P]),

@@ -19,6 +19,9 @@
 //   vit_layernorm_kernel one wave per token row, two-pass (mean, centred variance) in registers; gamma / beta from the
 //                        parameter pool or from the per-task FiLM vectors (reference model/film.py:57-66).
 //   vit_attention_kernel one workgroup per (frame, head): Q, K, V (50 x 64) in LDS, S = QK^T / 8, row softmax, O = PV.
+// The patch-16 models of the same families (vit_s_16, vit_b_16, vit_b_16_clip: 14 x 14 patches, 197 tokens, six names in all)
+// run the same forward, inference and FiLM only, with the geometry read from the plan: the patch GEMM's EPI_PATCH16 form
+// (k = c*256 + kh*16 + kw, token rows 1..196) and vit_attention197_kernel (fp32 MFMA, K and V resident in LDS).
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -41,20 +44,28 @@ constexpr int VIT_KPATCH = 3 * VIT_PATCH * VIT_PATCH;  // 3072
 constexpr int VIT_HD = 64;                        // head dim
 constexpr int VIT_DEPTH = 12;
 constexpr int VIT_MAX_B = 8192;
+// the patch-16 models (196 patches + the class token): B * 197 * 4 D stays below 2^31 up to this many frames at D = 768
+constexpr int VIT16_PATCH = 16;
+constexpr int VIT16_GRID = VIT_SIZE / VIT16_PATCH;     // 14
+constexpr int VIT16_P = VIT16_GRID * VIT16_GRID;       // 196 patches
+constexpr int VIT16_N = VIT16_P + 1;                   // 197 tokens
+constexpr int VIT16_KPATCH = 3 * VIT16_PATCH * VIT16_PATCH;  // 768
+constexpr int VIT16_MAX_B = 2048;
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 // ---- token GEMM ------------------------------------------------------------------------------------------------------
 constexpr int G_BN = 128, G_BK = 32, G_THREADS = 256;
 // EPI_GELU_TAPE: EPI_GELU that also stores the pre-activation (aux); EPI_DGELU: times GELU'(u), u read through `residual`
-enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_PATCH = 3, EPI_GELU_TAPE = 4, EPI_DGELU = 5 };
+// EPI_PATCH16: EPI_PATCH for 16 x 16 patches (its own A gather and token-row geometry)
+enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_PATCH = 3, EPI_GELU_TAPE = 4, EPI_DGELU = 5, EPI_PATCH16 = 6 };
 
 struct GemmArgs {
     const float* x;         // [M][K] token rows, or the NCHW frames (EPI_PATCH)
     const float* w;         // [N][K] (torch Linear / OIHW conv layout)
     const float* bias;      // [N] or nullptr
     const float* residual;  // [M][N] (EPI_RESIDUAL; may alias y)
-    const float* pos;       // pos_embed [50][N] (EPI_PATCH)
+    const float* pos;       // pos_embed [50][N] (EPI_PATCH) / [197][N] (EPI_PATCH16)
     float* y;
     int M, N, K;
     float* aux = nullptr;   // [M][N] pre-activation out (EPI_GELU_TAPE)
@@ -74,10 +85,20 @@ __device__ __forceinline__ const float* patch_row_ptr(const float* frames, int m
     return frames + (((size_t)b * 3 + c) * VIT_SIZE + ph * VIT_PATCH + kh) * VIT_SIZE + pw * VIT_PATCH + kw;
 }
 
+// the same for 16 x 16 patches: k = c*256 + kh*16 + kw of patch m % 196 of frame m / 196. A patch row is 16 floats, so the 8
+// four-float chunks of a 32-deep K step lie in two frame rows: chunks 0..3 in row kh, chunks 4..7 in row kh + 1
+__device__ __forceinline__ const float* patch16_row_ptr(const float* frames, int m, int k) {
+    const int b = m / VIT16_P, p = m - b * VIT16_P;
+    const int ph = p / VIT16_GRID, pw = p - ph * VIT16_GRID;
+    const int c = k >> 8, kh = (k >> 4) & 15, kw = k & 15;
+    return frames + (((size_t)b * 3 + c) * VIT_SIZE + ph * VIT16_PATCH + kh) * VIT_SIZE + pw * VIT16_PATCH + kw;
+}
+
 // address of the 4 consecutive k of A row m (clamped into [0, M)) starting at k
 template <int EPI>
 __device__ __forceinline__ const float* a_row_ptr(const GemmArgs& a, int m, int k) {
     if (EPI == EPI_PATCH) return patch_row_ptr(a.x, m, k);
+    if (EPI == EPI_PATCH16) return patch16_row_ptr(a.x, m, k);
     return a.x + (size_t)m * a.K + k;
 }
 
@@ -131,8 +152,10 @@ __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
 #pragma unroll
         for (int i = 0; i < AR; ++i) {
             // patch rows: k0 advances (c, kh) - one frame row of 32 pixels per K step
+            // (16 x 16 patches: (c, kh) with kh even - two frame rows of 16 pixels per K step, the loader's chunk picks the row)
             const float* p = EPI == EPI_PATCH ? ap[i] + ((k0 >> 10) * VIT_SIZE + ((k0 >> 5) & 31)) * VIT_SIZE
-                                              : ap[i] + k0;
+                             : EPI == EPI_PATCH16 ? ap[i] + ((k0 >> 8) * VIT_SIZE + ((k0 >> 4) & 15)) * VIT_SIZE
+                                                  : ap[i] + k0;
             ra[i] = *reinterpret_cast<const float4*>(p);
         }
 #pragma unroll
@@ -196,10 +219,11 @@ __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
                 const int row = m0 + wm * (BM / 2) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (row >= a.M) continue;
                 float v = (BLOCKED ? tot[i][j][r] : acc[i][j][r]) + bv;
-                if (EPI == EPI_PATCH) {
-                    const int b = row / VIT_P, p = row - b * VIT_P;
+                if (EPI == EPI_PATCH || EPI == EPI_PATCH16) {
+                    constexpr int NP = EPI == EPI_PATCH16 ? VIT16_P : VIT_P;  // patches per frame; token rows: NP + 1
+                    const int b = row / NP, p = row - b * NP;
                     v += a.pos[(size_t)(1 + p) * a.N + col];
-                    a.y[((size_t)b * VIT_N + 1 + p) * a.N + col] = v;
+                    a.y[((size_t)b * (NP + 1) + 1 + p) * a.N + col] = v;
                     continue;
                 }
                 if (EPI == EPI_GELU_TAPE) a.aux[(size_t)row * a.N + col] = v;
@@ -239,17 +263,18 @@ int launch_gemm(const GemmArgs& a, const char* what, hipStream_t s, int tile_row
 
 // ---- class token row -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void vit_cls_kernel(const float* __restrict__ cls, const float* __restrict__ pos,
-                                                      float* __restrict__ tokens, int B, int D) {
+                                                      float* __restrict__ tokens, int B, int D, int N) {
     const size_t n = (size_t)B * D;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const int b = (int)(i / D), d = (int)(i - (size_t)b * D);
-        tokens[(size_t)b * VIT_N * D + d] = cls[d] + pos[d];
+        tokens[(size_t)b * N * D + d] = cls[d] + pos[d];
     }
 }
 
-int launch_cls_token(const float* cls, const float* pos, float* tokens, int B, int D, hipStream_t s) {
+// N: token rows per frame (row 0 of each frame is written)
+int launch_cls_token(const float* cls, const float* pos, float* tokens, int B, int D, int N, hipStream_t s) {
     const int pi = prof_start("vit_cls_token", 0.0, 4.0 * B * D, s);
-    vit_cls_kernel<<<cdiv(B * D, 256) < 1024 ? cdiv(B * D, 256) : 1024, 256, 0, s>>>(cls, pos, tokens, B, D);
+    vit_cls_kernel<<<cdiv(B * D, 256) < 1024 ? cdiv(B * D, 256) : 1024, 256, 0, s>>>(cls, pos, tokens, B, D, N);
     prof_stop(pi, s);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
@@ -339,9 +364,127 @@ __global__ __launch_bounds__(256) void vit_attention_kernel(const float* __restr
     }
 }
 
-int launch_attention(const float* qkv, float* out, int B, int D, int heads, hipStream_t s) {
-    const int pi = prof_start("vit_attention", 4.0 * B * heads * VIT_N * VIT_N * VIT_HD, 4.0 * 4 * (double)B * VIT_N * D, s);
-    vit_attention_kernel<<<B * heads, 256, 0, s>>>(qkv, out, D, heads);
+// The same for the 197 tokens of the patch-16 models, on v_mfma_f32_32x32x2_f32. One workgroup of 7 waves per (frame, head):
+// K [224][65] and V [224][72] (rows 197..223 zero) resident in 122 752 bytes of LDS, each wave owns 32 queries. A wave computes
+// the TRANSPOSED scores S^T = K (Q/8)^T - A operand K out of LDS, B operand its queries out of registers - so that the MFMA's
+// C layout leaves every lane with one query's column: 7 tiles x 16 registers = 112 keys in the lane, the other 112 in lane ^ 32.
+// The softmax is then a reduction inside the lane plus one exchange, and P^T is already the B operand of O^T = V^T P^T (A operand
+// V out of LDS): P never goes through LDS. Keys 197..223 are set to -inf before the maximum; queries past 196 re-read query 196
+// and are never stored. k order inside a score: step kk adds d = kk and d = 32 + kk; inside an output: the keys of a lane half in
+// (tile, register) order - fixed, and independent of the other workgroups of the launch.
+constexpr int A16_WAVES = 7;
+constexpr int A16_NPAD = 32 * A16_WAVES;  // 224
+constexpr int A16_LDK = VIT_HD + 1;       // odd row stride: the 32 keys of an A fragment hit 32 banks, the two d halves the other 32
+constexpr int A16_LDV = VIT_HD + 8;       // rows 4 apart (the two lane halves of a PV step) land 32 banks apart; float4 rows
+constexpr size_t A16_LDS_BYTES = (size_t)A16_NPAD * (A16_LDK + A16_LDV) * sizeof(float);
+static_assert(A16_NPAD >= VIT16_N && A16_NPAD - VIT16_N < 32, "the last key tile must hold a valid key");
+static_assert((A16_NPAD * A16_LDK) % 4 == 0 && A16_LDV % 4 == 0, "V rows are written as float4");
+
+__global__ __launch_bounds__(64 * A16_WAVES) void vit_attention197_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                                          int D, int heads) {
+    extern __shared__ __attribute__((aligned(16))) float a16_sm[];
+    float* ks = a16_sm;
+    float* vs = a16_sm + A16_NPAD * A16_LDK;
+    const int bh = blockIdx.x, b = bh / heads, h = bh - b * heads;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int col = lane & 31, half = lane >> 5;
+    const float* base = qkv + (size_t)b * VIT16_N * 3 * D + h * VIT_HD;
+    for (int i = tid; i < A16_NPAD * (VIT_HD / 4); i += 64 * A16_WAVES) {
+        const int t = i >> 4, c = (i & 15) * 4;
+        float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
+        if (t < VIT16_N) {
+            const float* r = base + (size_t)t * 3 * D + c;
+            kv = *reinterpret_cast<const float4*>(r + D);
+            vv = *reinterpret_cast<const float4*>(r + 2 * D);
+        }
+        float* kd = ks + t * A16_LDK + c;
+        kd[0] = kv.x, kd[1] = kv.y, kd[2] = kv.z, kd[3] = kv.w;
+        *reinterpret_cast<float4*>(vs + t * A16_LDV + c) = vv;
+    }
+    // this lane's query, d = 32 half .. 32 half + 31, times head_dim ** -0.5 (a power of two: exact)
+    const int query = 32 * wave + col;
+    float qf[32];
+    {
+        const float* qp = base + (size_t)(query < VIT16_N ? query : VIT16_N - 1) * 3 * D + 32 * half;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float4 q4 = *reinterpret_cast<const float4*>(qp + 4 * i);
+            qf[4 * i + 0] = q4.x * 0.125f, qf[4 * i + 1] = q4.y * 0.125f, qf[4 * i + 2] = q4.z * 0.125f, qf[4 * i + 3] = q4.w * 0.125f;
+        }
+    }
+    __syncthreads();
+
+    // S^T tile t: rows = keys 32 t + (r & 3) + 8 (r >> 2) + 4 half, column = this lane's query
+    floatx16 sc[A16_WAVES];
+#pragma unroll
+    for (int t = 0; t < A16_WAVES; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sc[t][r] = 0.f;
+    const float* ka = ks + col * A16_LDK + 32 * half;
+#pragma unroll
+    for (int kk = 0; kk < 32; ++kk)
+#pragma unroll
+        for (int t = 0; t < A16_WAVES; ++t)
+            sc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[32 * t * A16_LDK + kk], qf[kk], sc[t], 0, 0, 0);
+
+    // softmax over the keys of this lane's query: the padded keys leave the maximum and the sum
+    float m = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < A16_WAVES; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            if (t == A16_WAVES - 1 && 32 * t + (r & 3) + 8 * (r >> 2) + 4 * half >= VIT16_N) sc[t][r] = -INFINITY;
+            m = fmaxf(m, sc[t][r]);
+        }
+    m = fmaxf(m, __shfl_xor(m, 32));
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < A16_WAVES; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sc[t][r] = expf(sc[t][r] - m), sum += sc[t][r];
+    sum += __shfl_xor(sum, 32);
+
+    // O^T tile dt: rows = d 32 dt + (r & 3) + 8 (r >> 2) + 4 half, column = this lane's query
+    floatx16 ov[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ov[dt][r] = 0.f;
+    const float* va = vs + 4 * half * A16_LDV + col;
+#pragma unroll
+    for (int t = 0; t < A16_WAVES; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            if (32 * t + 8 * (r >> 2) >= VIT16_N) continue;  // (both halves' keys are padding: P = 0 and V = 0)
+            const float* vr = va + (32 * t + (r & 3) + 8 * (r >> 2)) * A16_LDV;
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) ov[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[32 * dt], sc[t][r], ov[dt], 0, 0, 0);
+        }
+    if (query >= VIT16_N) return;
+    float* op = out + ((size_t)b * VIT16_N + query) * D + h * VIT_HD + 4 * half;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<float4*>(op + 32 * dt + 8 * g) = make_float4(ov[dt][4 * g + 0] / sum, ov[dt][4 * g + 1] / sum,
+                                                                           ov[dt][4 * g + 2] / sum, ov[dt][4 * g + 3] / sum);
+}
+
+// N: tokens per frame, 50 (the LDS-resident VALU kernel) or 197 (the MFMA kernel; qkv and out 16-byte aligned)
+int launch_attention(const float* qkv, float* out, int B, int N, int D, int heads, hipStream_t s) {
+    if (N != VIT_N && N != VIT16_N) return set_err(ORBIT_ERR_ARG, "vit attention: %d tokens (50 or 197)", N);
+    static bool attr_set = false;  // > 64 KiB of dynamic LDS needs the opt-in once
+    if (N == VIT16_N && !attr_set) {
+        ORBIT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vit_attention197_kernel),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)A16_LDS_BYTES));
+        attr_set = true;
+    }
+    const int pi = prof_start(N == VIT_N ? "vit_attention" : "vit_attention197", 4.0 * B * heads * N * N * VIT_HD,
+                              4.0 * 4 * (double)B * N * D, s);
+    if (N == VIT_N)
+        vit_attention_kernel<<<B * heads, 256, 0, s>>>(qkv, out, D, heads);
+    else
+        vit_attention197_kernel<<<B * heads, 64 * A16_WAVES, A16_LDS_BYTES, s>>>(qkv, out, D, heads);
     prof_stop(pi, s);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
@@ -764,6 +907,10 @@ struct orbit_vit {
     int D = 0, heads = 0, mlp = 0;
     float eps = 1e-6f;
     bool clip = false;  // pre_norm: no patch-embedding bias, norm_pre after the position add
+    // geometry: patch size (32 or 16), patches per side and per frame, tokens per frame, K of the patch GEMM, largest batch.
+    // The patch-16 plans are forward only (no tape, no backward)
+    int patch = VIT_PATCH, grid = VIT_GRID, P = VIT_P, N = VIT_N, kpatch = VIT_KPATCH, max_b = VIT_MAX_B;
+    bool forward_only() const { return patch != VIT_PATCH; }
     ParamPool pool{64};  // the parameters by state_dict key (csrc/param_pool.h); 256-byte aligned tensors (float4 loads)
     // where the forward and the backward find each tensor: pool offsets, fixed by orbit_vit_create
     size_t cls = 0, pos = 0, patch_w = 0, patch_b = VIT_ABSENT, pre_w = VIT_ABSENT, pre_b = VIT_ABSENT, norm_w = 0, norm_b = 0;
@@ -787,7 +934,7 @@ struct VitWs {
     size_t x, h, big, partial, total;
 };
 VitWs vit_ws(const orbit_vit* v, int B, bool backward) {
-    const size_t M = (size_t)B * VIT_N;
+    const size_t M = (size_t)B * v->N;
     VitWs L;
     L.x = 0;
     L.h = align_up(M * v->D * sizeof(float), 256);
@@ -842,9 +989,16 @@ VitWt vit_wt(const orbit_vit* v) {
 // what the three whole-network entry points refuse alike (their own null pointers are checked before, with the same text)
 int vit_check_call(const char* who, const orbit_vit* v, int B, const float* film_gamma, const float* film_beta) {
     ORBIT_REQUIRE(v, "%s: null pointer", who);
-    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "%s: batch of %d frames (1..%d)", who, B, VIT_MAX_B);
+    ORBIT_REQUIRE(B > 0 && B <= v->max_b, "%s: batch of %d frames (1..%d)", who, B, v->max_b);
     if (!v->finalized) return set_err(ORBIT_ERR_STATE, "%s: call orbit_vit_finalize first", who);
     ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr), "%s: film_gamma and film_beta must be given together", who);
+    return ORBIT_OK;
+}
+// the training entry points on a forward-only plan: refused by name, before any launch or allocation
+int vit_check_trainable(const char* who, const orbit_vit* v) {
+    ORBIT_REQUIRE(v, "%s: null pointer", who);
+    ORBIT_REQUIRE(!v->forward_only(), "%s: %s is an inference-only plan (no tape and no backward for the patch-%d models)", who,
+                  v->name.c_str(), v->patch);
     return ORBIT_OK;
 }
 int vit_check_buffer(const char* who, const char* what, const void* ptr, size_t bytes, size_t need) {
@@ -861,21 +1015,28 @@ int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out) {
     ORBIT_REQUIRE(name && out, "vit_create: null pointer");
     std::string n(name);
     int D, heads;
-    bool clip = false;
+    bool clip = false, p16 = false;
     if (n == "vit_s_32") D = 384, heads = 6;
     else if (n == "vit_b_32") D = 768, heads = 12;
     else if (n == "vit_b_32_clip") D = 768, heads = 12, clip = true;
+    else if (n == "vit_s_16") D = 384, heads = 6, p16 = true;
+    else if (n == "vit_b_16") D = 768, heads = 12, p16 = true;
+    else if (n == "vit_b_16_clip") D = 768, heads = 12, clip = true, p16 = true;
     else return set_err(ORBIT_ERR_ARG, "Invalid feature_extractor_name: %s (transformer extractors: vit_s_32, vit_b_32, "
-                        "vit_b_32_clip)", name);
+                        "vit_b_32_clip, vit_s_16, vit_b_16, vit_b_16_clip)", name);
     ORBIT_REQUIRE(H == VIT_SIZE && W == VIT_SIZE, "vit_create: %s runs on %dx%d frames only (fixed position table), got %dx%d",
                   name, VIT_SIZE, VIT_SIZE, H, W);
     orbit_vit* v = new orbit_vit();
     v->name = n, v->pool.owner = n, v->D = D, v->heads = heads, v->mlp = 4 * D, v->clip = clip, v->eps = clip ? 1e-5f : 1e-6f;
+    if (p16) {
+        v->patch = VIT16_PATCH, v->grid = VIT_SIZE / v->patch, v->P = v->grid * v->grid, v->N = v->P + 1;
+        v->kpatch = 3 * v->patch * v->patch, v->max_b = VIT16_MAX_B;
+    }
     auto add = [&](const std::string& key, size_t numel) { return v->pool.off(v->pool.add(key, numel)); };
     // timm 0.6.12 VisionTransformer state_dict order
     v->cls = add("cls_token", D);
-    v->pos = add("pos_embed", (size_t)VIT_N * D);
-    v->patch_w = add("patch_embed.proj.weight", (size_t)D * VIT_KPATCH);
+    v->pos = add("pos_embed", (size_t)v->N * D);
+    v->patch_w = add("patch_embed.proj.weight", (size_t)D * v->kpatch);
     if (!clip) v->patch_b = add("patch_embed.proj.bias", D);
     if (clip) v->pre_w = add("norm_pre.weight", D), v->pre_b = add("norm_pre.bias", D);
     for (int i = 0; i < VIT_DEPTH; ++i) {
@@ -893,7 +1054,7 @@ int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out) {
     v->norm_w = add("norm.weight", D), v->norm_b = add("norm.bias", D);
     v->film_names.push_back("norm");
     const double Dd = D;
-    v->macs = (double)VIT_P * VIT_KPATCH * Dd + VIT_DEPTH * (VIT_N * 12.0 * Dd * Dd + 2.0 * VIT_N * VIT_N * Dd);
+    v->macs = (double)v->P * v->kpatch * Dd + VIT_DEPTH * (v->N * 12.0 * Dd * Dd + 2.0 * v->N * v->N * Dd);
     *out = v;
     return ORBIT_OK;
 }
@@ -950,7 +1111,7 @@ const char* orbit_vit_film_slot_name(const orbit_vit_t* v, int slot) {
 }
 int orbit_vit_film_size(const orbit_vit_t* v) { return v ? (int)v->film_names.size() * v->D : 0; }
 size_t orbit_vit_workspace_bytes(const orbit_vit_t* v, int B) {
-    if (!v || B <= 0 || B > VIT_MAX_B) return 0;
+    if (!v || B <= 0 || B > v->max_b) return 0;
     return vit_ws(v, B, false).total;
 }
 double orbit_vit_macs_per_frame(const orbit_vit_t* v) { return v ? v->macs : 0.0; }
@@ -966,7 +1127,7 @@ int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* fi
                      void* workspace, char* tape, hipStream_t s) {
     const VitWs L = vit_ws(v, B, false);
     const VitTape T = vit_tape(v, B);
-    const int D = v->D, M = B * VIT_N;
+    const int D = v->D, N = v->N, M = B * N;
     char* ws = static_cast<char*>(workspace);
     auto slot = [&](int i, size_t off) { return reinterpret_cast<float*>(tape + (i < VIT_DEPTH ? i * T.block + off : T.last)); };
     float* x = tape ? slot(0, T.x) : reinterpret_cast<float*>(ws + L.x);
@@ -978,10 +1139,11 @@ int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* fi
         else *g = v->p(w), *be = v->p(b);
     };
     int rc;
-    {   // tokens: patch embedding (+ bias) + pos_embed into rows 1..49, cls_token + pos_embed[0] into row 0
-        GemmArgs a{frames, v->p(v->patch_w), v->p(v->patch_b), nullptr, v->p(v->pos), x, B * VIT_P, D, VIT_KPATCH};
-        if ((rc = launch_gemm<EPI_PATCH>(a, "patch_embed", s))) return rc;
-        if ((rc = launch_cls_token(v->p(v->cls), v->p(v->pos), x, B, D, s))) return rc;
+    {   // tokens: patch embedding (+ bias) + pos_embed into rows 1..N-1, cls_token + pos_embed[0] into row 0
+        GemmArgs a{frames, v->p(v->patch_w), v->p(v->patch_b), nullptr, v->p(v->pos), x, B * v->P, D, v->kpatch};
+        if ((rc = v->patch == VIT16_PATCH ? launch_gemm<EPI_PATCH16>(a, "patch_embed", s) : launch_gemm<EPI_PATCH>(a, "patch_embed", s)))
+            return rc;
+        if ((rc = launch_cls_token(v->p(v->cls), v->p(v->pos), x, B, D, N, s))) return rc;
         if (v->clip && (rc = launch_layernorm(x, D, x, D, M, D, v->p(v->pre_w), v->p(v->pre_b), v->eps, s))) return rc;
     }
     for (int i = 0; i < VIT_DEPTH; ++i) {
@@ -994,7 +1156,7 @@ int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* fi
         if ((rc = launch_layernorm(x, D, h, D, M, D, g, be, v->eps, s))) return rc;
         GemmArgs qkv{h, v->p(k.qkv_w), v->p(k.qkv_b), nullptr, nullptr, qkvb, M, 3 * D, D};
         if ((rc = launch_gemm<EPI_BIAS>(qkv, "qkv", s))) return rc;
-        if ((rc = launch_attention(qkvb, h, B, D, v->heads, s))) return rc;
+        if ((rc = launch_attention(qkvb, h, B, N, D, v->heads, s))) return rc;
         GemmArgs proj{h, v->p(k.proj_w), v->p(k.proj_b), x, nullptr, xmid, M, D, D};
         if ((rc = launch_gemm<EPI_RESIDUAL>(proj, "proj", s))) return rc;
         ln_params(k.norm2_w, k.norm2_b, 2 * i + 1, &g, &be);
@@ -1013,7 +1175,7 @@ int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* fi
     const float *g, *be;
     ln_params(v->norm_w, v->norm_b, 2 * VIT_DEPTH, &g, &be);
     // final LayerNorm on the class token of every frame, straight into the caller's feature rows
-    return launch_layernorm(x, (size_t)VIT_N * D, feats, D, B, D, g, be, v->eps, s);
+    return launch_layernorm(x, (size_t)N * D, feats, D, B, D, g, be, v->eps, s);
 }
 
 // (re)build the transposed weights on `s` if a parameter upload invalidated them
@@ -1085,7 +1247,7 @@ int vit_backward_impl(orbit_vit_t* v, const float* frames, int B, const float* f
             return rc;
         // x_mid = x + proj(attn(qkv)):  dO = dx Wp,  dqkv = attn'(dO),  dh = dqkv Wqkv,  dx += LN1'(dh)
         if (pg) {
-            if ((rc = launch_attention(slot(i, T.qkv), h2, B, D, v->heads, s))) return rc;
+            if ((rc = launch_attention(slot(i, T.qkv), h2, B, VIT_N, D, v->heads, s))) return rc;
             if ((rc = launch_wgrad<WX_PLAIN>(dx, h2, pg + k.proj_w, pg + k.proj_b, M, D, D, b.wgrad, "wgrad_proj", s))) return rc;
         }
         GemmArgs dproj{dx, wt + W.proj, nullptr, nullptr, nullptr, h, M, D, D};
@@ -1110,7 +1272,7 @@ int vit_backward_impl(orbit_vit_t* v, const float* frames, int B, const float* f
         // norm_pre ran in place: its input tokens are rebuilt from the frames (patch GEMM + class-token row) into h2
         GemmArgs a{frames, v->p(v->patch_w), v->p(v->patch_b), nullptr, v->p(v->pos), h2, B * VIT_P, D, VIT_KPATCH};
         if ((rc = launch_gemm<EPI_PATCH>(a, "patch_embed", s))) return rc;
-        if ((rc = launch_cls_token(v->p(v->cls), v->p(v->pos), h2, B, D, s))) return rc;
+        if ((rc = launch_cls_token(v->p(v->cls), v->p(v->pos), h2, B, D, VIT_N, s))) return rc;
         if ((rc = launch_layernorm_bwd(h2, D, dx, D, v->p(v->pre_w), v->eps, nullptr, h, D, M, D, partial, pg + v->pre_w,
                                        pg + v->pre_b, s)))
             return rc;
@@ -1136,11 +1298,11 @@ int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* f
 
 // ---- FiLM gradients of the frozen network ----------------------------------------------------------------------------
 size_t orbit_vit_tape_bytes(const orbit_vit_t* v, int B) {
-    if (!v || B <= 0 || B > VIT_MAX_B) return 0;
+    if (!v || v->forward_only() || B <= 0 || B > VIT_MAX_B) return 0;
     return vit_tape(v, B).total;
 }
 size_t orbit_vit_backward_workspace_bytes(const orbit_vit_t* v, int B) {
-    if (!v || B <= 0 || B > VIT_MAX_B) return 0;
+    if (!v || v->forward_only() || B <= 0 || B > VIT_MAX_B) return 0;
     return vit_ws(v, B, true).total;
 }
 
@@ -1149,6 +1311,7 @@ int orbit_vit_train_forward(orbit_vit_t* v, const float* frames, int B, const fl
                             orbit_stream_t stream) {
     const char* who = "vit_train_forward";
     ORBIT_REQUIRE(frames && feats && tape && workspace, "%s: null pointer", who);
+    if (int rc = vit_check_trainable(who, v)) return rc;  // (before the state checks: a refusal needs no loaded plan)
     if (int rc = vit_check_call(who, v, B, film_gamma, film_beta)) return rc;
     if (int rc = vit_check_buffer(who, "workspace", workspace, workspace_bytes, vit_ws(v, B, false).total)) return rc;
     if (int rc = vit_check_buffer(who, "tape", tape, tape_bytes, vit_tape(v, B).total)) return rc;
@@ -1161,6 +1324,7 @@ int orbit_vit_backward(orbit_vit_t* v, int B, const float* film_gamma, const flo
                        size_t workspace_bytes, orbit_stream_t stream) {
     const char* who = "vit_backward";
     ORBIT_REQUIRE(dfeats && tape && dgamma && dbeta && workspace, "%s: null pointer", who);
+    if (int rc = vit_check_trainable(who, v)) return rc;  // (before the state checks: a refusal needs no loaded plan)
     if (int rc = vit_check_call(who, v, B, film_gamma, film_beta)) return rc;
     const VitWs L = vit_ws(v, B, true);
     if (int rc = vit_check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
@@ -1178,7 +1342,7 @@ int orbit_vit_backward(orbit_vit_t* v, int B, const float* film_gamma, const flo
 size_t orbit_vit_grad_floats(const orbit_vit_t* v) { return v ? v->pool.pool_floats : 0; }
 size_t orbit_vit_param_offset(const orbit_vit_t* v, int i) { return (v && i >= 0 && i < v->pool.size()) ? v->pool.off(i) : 0; }
 size_t orbit_vit_backward_params_workspace_bytes(const orbit_vit_t* v, int B) {
-    if (!v || B <= 0 || B > VIT_MAX_B) return 0;
+    if (!v || v->forward_only() || B <= 0 || B > VIT_MAX_B) return 0;
     return vit_ws_params(v, B).total;
 }
 
@@ -1187,6 +1351,7 @@ int orbit_vit_backward_params(orbit_vit_t* v, const float* frames, int B, const 
                               float* dbeta, void* workspace, size_t workspace_bytes, orbit_stream_t stream) {
     const char* who = "vit_backward_params";
     ORBIT_REQUIRE(frames && dfeats && tape && param_grads && dgamma && dbeta && workspace, "%s: null pointer", who);
+    if (int rc = vit_check_trainable(who, v)) return rc;  // (before the state checks: a refusal needs no loaded plan)
     if (int rc = vit_check_call(who, v, B, film_gamma, film_beta)) return rc;
     const VitWsParams L = vit_ws_params(v, B);
     if (int rc = vit_check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
@@ -1224,10 +1389,15 @@ int orbit_op_vit_linear(const float* x, const float* w, const float* bias, const
     return launch_gemm<EPI_BIAS>(a, "op_linear", s, tile_rows);
 }
 
-int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,
-                             const float* cls_token, float* tokens, int B, int D, int tile_rows, orbit_stream_t stream) {
+// patch: 32 (7 x 7 patches, 50 token rows per frame) or 16 (14 x 14, 197)
+int orbit_op_vit_patch_embed_p(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,
+                               const float* cls_token, float* tokens, int B, int D, int patch, int tile_rows,
+                               orbit_stream_t stream) {
     ORBIT_REQUIRE(frames && w && pos_embed && cls_token && tokens, "op_vit_patch_embed: null pointer");
-    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "op_vit_patch_embed: batch of %d frames (1..%d)", B, VIT_MAX_B);
+    ORBIT_REQUIRE(patch == VIT_PATCH || patch == VIT16_PATCH, "op_vit_patch_embed: patch size %d (32 or 16)", patch);
+    const bool p16 = patch == VIT16_PATCH;
+    const int max_b = p16 ? VIT16_MAX_B : VIT_MAX_B;
+    ORBIT_REQUIRE(B > 0 && B <= max_b, "op_vit_patch_embed: batch of %d frames (1..%d)", B, max_b);
     ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_patch_embed: unsupported width %d (384 or 768)", D);
     ORBIT_REQUIRE(((uintptr_t)frames & 15) == 0 && ((uintptr_t)w & 15) == 0,
                   "op_vit_patch_embed: frames and w must be 16-byte aligned");
@@ -1235,9 +1405,15 @@ int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* b
                       ((uintptr_t)cls_token & 3) == 0,
                   "op_vit_patch_embed: tokens, bias, pos_embed and cls_token must be 4-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const GemmArgs a{frames, w, bias_or_null, nullptr, pos_embed, tokens, B * VIT_P, D, VIT_KPATCH};
-    if (int rc = launch_gemm<EPI_PATCH>(a, "op_patch_embed", s, tile_rows)) return rc;
-    return launch_cls_token(cls_token, pos_embed, tokens, B, D, s);
+    const GemmArgs a{frames, w, bias_or_null, nullptr, pos_embed, tokens, B * (p16 ? VIT16_P : VIT_P), D, p16 ? VIT16_KPATCH : VIT_KPATCH};
+    if (int rc = p16 ? launch_gemm<EPI_PATCH16>(a, "op_patch_embed", s, tile_rows) : launch_gemm<EPI_PATCH>(a, "op_patch_embed", s, tile_rows))
+        return rc;
+    return launch_cls_token(cls_token, pos_embed, tokens, B, D, p16 ? VIT16_N : VIT_N, s);
+}
+
+int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,
+                             const float* cls_token, float* tokens, int B, int D, int tile_rows, orbit_stream_t stream) {
+    return orbit_op_vit_patch_embed_p(frames, w, bias_or_null, pos_embed, cls_token, tokens, B, D, VIT_PATCH, tile_rows, stream);
 }
 
 int orbit_op_vit_layernorm(const float* x, size_t x_stride, float* y, size_t y_stride, int rows, int D, const float* gamma,
@@ -1252,13 +1428,22 @@ int orbit_op_vit_layernorm(const float* x, size_t x_stride, float* y, size_t y_s
     return launch_layernorm(x, x_stride, y, y_stride, rows, D, gamma, beta, eps, (hipStream_t)stream);
 }
 
-int orbit_op_vit_attention(const float* qkv, float* out, int B, int D, int heads, orbit_stream_t stream) {
+// tokens: 50 or 197 per frame (the 197-token kernel reads qkv and writes out as float4: 16-byte aligned)
+int orbit_op_vit_attention_tokens(const float* qkv, float* out, int B, int tokens, int D, int heads, orbit_stream_t stream) {
     ORBIT_REQUIRE(qkv && out, "op_vit_attention: null pointer");
+    ORBIT_REQUIRE(tokens == VIT_N || tokens == VIT16_N, "op_vit_attention: %d tokens per frame (50 or 197)", tokens);
     ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_attention: unsupported width %d (384 or 768)", D);
     ORBIT_REQUIRE(heads * VIT_HD == D, "op_vit_attention: %d heads of %d do not make D=%d", heads, VIT_HD, D);
-    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "op_vit_attention: batch of %d frames (1..%d)", B, VIT_MAX_B);
-    ORBIT_REQUIRE((((uintptr_t)qkv | (uintptr_t)out) & 3) == 0, "op_vit_attention: pointers must be 4-byte aligned");
-    return launch_attention(qkv, out, B, D, heads, (hipStream_t)stream);
+    const int max_b = tokens == VIT16_N ? VIT16_MAX_B : VIT_MAX_B;
+    ORBIT_REQUIRE(B > 0 && B <= max_b, "op_vit_attention: batch of %d frames (1..%d)", B, max_b);
+    const uintptr_t mask = tokens == VIT16_N ? 15 : 3;
+    ORBIT_REQUIRE((((uintptr_t)qkv | (uintptr_t)out) & mask) == 0, "op_vit_attention: pointers must be %d-byte aligned",
+                  (int)mask + 1);
+    return launch_attention(qkv, out, B, tokens, D, heads, (hipStream_t)stream);
+}
+
+int orbit_op_vit_attention(const float* qkv, float* out, int B, int D, int heads, orbit_stream_t stream) {
+    return orbit_op_vit_attention_tokens(qkv, out, B, VIT_N, D, heads, stream);
 }
 
 int orbit_op_vit_linear_dgrad(const float* dy, const float* w, float* wt_scratch, const float* u, const float* residual,

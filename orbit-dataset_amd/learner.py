@@ -66,12 +66,13 @@ def build_parser():
     p.add_argument("--tasks_per_batch", type=int, default=16)
     p.add_argument("--with_lite", action="store_true")
     p.add_argument("--vit_native_backward", action="store_true",
-                   help="vit_* extractors: opt in to the native FiLM gradients through the FROZEN transformer (--adapt_features "
+                   help="vit_*_32* extractors: opt in to the native FiLM gradients through the FROZEN transformer (--adapt_features "
                         "training, with or without --with_lite; the multi-step finetuner's --adapt_features). --learn_extractor "
                         "stays refused: weight gradients are not built")
     p.add_argument("--vit_native_weight_backward", action="store_true",
-                   help="vit_* extractors: opt in to the native gradients of every parameter of the transformer (implies what "
-                        "--vit_native_backward admits, and admits --learn_extractor). Ignored for the other extractors")
+                   help="vit_*_32* extractors: opt in to the native gradients of every parameter of the transformer (implies what "
+                        "--vit_native_backward admits, and admits --learn_extractor). Ignored for the other extractors, the "
+                        "inference-only patch-16 transformers among them")
     p.add_argument("--effnetv2_native_backward", action="store_true",
                    help="efficientnet_v2_s: opt in to the native FiLM gradients through the FROZEN network (--adapt_features "
                         "training, with or without --with_lite; the multi-step finetuner's --adapt_features). --learn_extractor "
@@ -220,6 +221,10 @@ FROZEN_EXTRACTORS = {
     "vit_s_32": FrozenExtractor("imagenet_inception", 224, *_VIT),
     "vit_b_32": FrozenExtractor("imagenet_inception", 224, *_VIT),
     "vit_b_32_clip": FrozenExtractor("openai_clip", 224, *_VIT),
+    # the patch-16 models: inference + FiLM only, no flag opens a gradient (csrc/vit.hip builds no backward at 197 tokens)
+    "vit_s_16": FrozenExtractor("imagenet_inception", 224, None, None, *_VIT[2:]),
+    "vit_b_16": FrozenExtractor("imagenet_inception", 224, None, None, *_VIT[2:]),
+    "vit_b_16_clip": FrozenExtractor("openai_clip", 224, None, None, *_VIT[2:]),
     # any frame size, as efficientnet_b0. By default the native plan has no backward (its ConvBnAct blocks add the skip after
     # the activation, csrc/extractor_train.hip plan_trainable); the first flag opens the frozen form, the second all of it
     "efficientnet_v2_s": FrozenExtractor("imagenet_inception", None, "effnetv2_native_backward", "effnetv2_native_weight_backward",
@@ -328,7 +333,7 @@ def verify_args(args):
     multistep = getattr(args, "personalize_num_grad_steps", None) is not None
     if spec.weight_flag and getattr(args, spec.weight_flag, False):
         pass  # native gradients of every parameter: everything the other extractors train is admitted
-    elif getattr(args, spec.film_flag, False):
+    elif spec.film_flag and getattr(args, spec.film_flag, False):
         if args.learn_extractor:
             sys.exit("error: --%s gives FiLM gradients through a frozen %s only: --learn_extractor (%s) is not built"
                      % (spec.film_flag, fe, spec.no_weights))

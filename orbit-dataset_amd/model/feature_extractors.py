@@ -6,7 +6,7 @@ parameters when `learn_extractor=False`, FiLM tagging when `with_film=True`. The
 networks; here the network lives in liborbit_hip.so and this module is only its parameter container
 (state_dict-compatible key names: torchvision layout for resnet18, timm `tf_efficientnet_b0` layout for
 efficientnet_b0, timm `tf_efficientnetv2_s_in21k` layout for efficientnet_v2_s, timm VisionTransformer layout for
-vit_s_32 / vit_b_32 / vit_b_32_clip) plus the call into
+vit_s_32 / vit_b_32 / vit_b_32_clip / vit_s_16 / vit_b_16 / vit_b_16_clip) plus the call into
 `orbit_extractor_forward` (`orbit_vit_forward` for the transformers, csrc/vit.hip). `resnet18` and arbitrary frame sizes are
 additions BASELINE.json's configs require (the snapshot's args.py:27,77 no longer list them).
 
@@ -672,7 +672,11 @@ class VisionTransformer(HipNetwork):
     from orbit_vit_train_forward / orbit_vit_backward (autograd.VitFunction); any other parameter requiring a gradient is still
     refused - unless `native_weight_backward = True` (which implies the above): then every parameter that requires a gradient
     gets it from orbit_vit_backward_params (--learn_extractor). There is no BatchNorm or dropout, so train() and eval() compute the same features. Frames must be 224 x 224 (the
-    position table is fixed)."""
+    position table is fixed).
+
+    vit_s_16 / vit_b_16 / vit_b_16_clip are the patch-16 models of the same families (timm `vit_small_patch16_224_in21k`,
+    `vit_base_patch16_224_in21k`, the laion2b CLIP B/16): the same tree with a [D, 3, 16, 16] patch filter and a [1, 197, D]
+    position table. They are inference + FiLM only: both opt-ins are ignored and anything that needs a gradient is refused."""
 
     _api = "vit"
     _probe_size = _frame_size = VIT_FRAME_SIZE
@@ -690,7 +694,7 @@ class VisionTransformer(HipNetwork):
         if key == "pos_embed":
             return (1, numel // D, D)
         if key == "patch_embed.proj.weight":
-            return (D, 3, 32, 32)
+            return (D, 3, self.patch_size, self.patch_size)
         if key.endswith(".weight") and (".attn." in key or ".mlp." in key):
             return {"qkv": (3 * D, D), "proj": (D, D), "fc1": (4 * D, D), "fc2": (D, 4 * D)}[key.split(".")[-2]]
         return (numel,)
@@ -702,7 +706,14 @@ class VisionTransformer(HipNetwork):
                      "(--learn_extractor) are not built")
 
     @property
+    def patch_size(self):
+        """16 for vit_s_16 / vit_b_16 / vit_b_16_clip, else 32: the third field of the name."""
+        return 16 if self.native_name.split("_")[2] == "16" else 32
+
+    @property
     def _grad_scope(self):
+        if self.patch_size == 16:  # no native backward is built for 197 tokens, whatever the opt-ins say
+            return "none"
         return "all" if self.native_weight_backward else "film" if self.native_backward else "none"
 
     def _forward_train(self, plan, x, film, use_tape, bn_train, out):
@@ -720,7 +731,8 @@ class VisionTransformer(HipNetwork):
 # name -> (class, output size): the extractors `create_feature_extractor` builds and the learners' --feature_extractor accepts
 EXTRACTORS = {"efficientnet_b0": (EfficientNetB0, 1280), "efficientnet_v2_s": (EfficientNetV2S, 1280), "resnet18": (ResNet18, 512),
               "vit_s_32": (VisionTransformer, 384), "vit_b_32": (VisionTransformer, 768),
-              "vit_b_32_clip": (VisionTransformer, 768)}
+              "vit_b_32_clip": (VisionTransformer, 768), "vit_s_16": (VisionTransformer, 384),
+              "vit_b_16": (VisionTransformer, 768), "vit_b_16_clip": (VisionTransformer, 768)}
 
 
 def create_feature_extractor(feature_extractor_name: str, pretrained: bool = True, with_film: bool = False,

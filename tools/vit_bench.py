@@ -1,12 +1,13 @@
 """Throughput of the transformer extractors (csrc/vit.hip) on config-3-shaped tasks: one JSON line.
 
-For each of vit_s_32 / vit_b_32 / vit_b_32_clip: a 5-way task with 200 support and 200 query frames at 224 x 224, run
+For each of vit_s_32 / vit_b_32 / vit_b_32_clip (or, with --models, the patch-16 vit_s_16 / vit_b_16 / vit_b_16_clip): a 5-way task with 200 support and 200 query frames at 224 x 224, run
 personalise() + predict() in test mode with ProtoNets (`proto`) and with CNAPs (`versa` + FiLM adaptation); the median ms per
 task after warm-up, query frames/s, per-family kernel time of one proto task from the library's per-launch event records
 (token GEMM, attention, LayerNorm, patch embedding), the token GEMMs' TF/s as a fraction of the 155 TF fp32 MFMA peak, and
 torch.nn.functional.linear (fp32, the vendor BLAS) on the same four shapes at M = 10 000 token rows as a reference point.
 
     python tools/vit_bench.py [--steps 10] [--warmup 3] [--models vit_s_32,vit_b_32,vit_b_32_clip]
+    python tools/vit_bench.py --models vit_s_16,vit_b_16,vit_b_16_clip
 
 --train reports the training side instead: ms of taped forward + orbit_vit_backward_params (every parameter's gradient, through
 the module with native_weight_backward) at the step shapes B = 16 and B = 200, the weight-gradient GEMM family's TF/s per layer
@@ -152,7 +153,7 @@ def main_train(a):
               "peak_tflops": PEAK_TF, "models": {}}
     for name in a.models.split(","):
         r = {"fwd_bwd_ms": {"B%d" % B: round(_train_step_ms(name, B, a.steps, a.warmup), 3) for B in (16, 200)}}
-        r["wgrad_m10000"] = _wgrad_shapes(384 if name == "vit_s_32" else 768, a.steps, a.warmup)
+        r["wgrad_m10000"] = _wgrad_shapes(384 if name.startswith("vit_s_") else 768, a.steps, a.warmup)
         result["models"][name] = r
         torch.cuda.empty_cache()
     print(json.dumps(result))
@@ -162,7 +163,8 @@ def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--models", default="vit_s_32,vit_b_32,vit_b_32_clip")
+    p.add_argument("--models", default="vit_s_32,vit_b_32,vit_b_32_clip",
+                   help="comma-separated, any of the six transformer extractors (--train: the patch-32 ones only)")
     p.add_argument("--train", action="store_true", help="the training step and the weight-gradient GEMMs instead")
     a = p.parse_args(argv)
     _lib.require_gpu()
@@ -191,7 +193,7 @@ def main(argv=None):
         cnaps = _model(name, True, "versa")
         r["cnaps_ms"] = round(_time(_task_fn(cnaps, task), a.steps, a.warmup), 3)
         del cnaps
-        r["torch_linear_m10000"] = _torch_linear(384 if name == "vit_s_32" else 768, a.steps, a.warmup)
+        r["torch_linear_m10000"] = _torch_linear(384 if name.startswith("vit_s_") else 768, a.steps, a.warmup)
         result["models"][name] = r
         torch.cuda.empty_cache()
     print(json.dumps(result))
