@@ -599,6 +599,44 @@ int orbit_cross_entropy_forward(const float* logits, const int64_t* labels, int 
 int orbit_cross_entropy_backward(const float* softmax, const int64_t* labels, const float* grad, int N, int C,
                                  int reduction, float* dlogits, orbit_stream_t stream);
 
+/* ---- multi-tensor optimizer step (csrc/optim.hip) ------------------------------------------------------------------
+ * One launch updates every fp32 tensor of a model: reference utils/optim.py:11-33 (torch.optim.Adam / torch.optim.SGD over the
+ * two parameter groups; stepped at single-step-learner.py:163 and few_shot_recognisers.py:216). The arithmetic is torch.optim's
+ * (L2 weight decay added to the gradient, Adam's bias corrections computed on the host in double, no amsgrad; SGD with
+ * dampening 0 and no Nesterov), with a correctly rounded square root and true divisions.
+ *
+ * A table has one row per tensor that has a gradient. `rows` is the table in DEVICE memory, `host_rows` the caller's HOST copy
+ * of the same n_tensors rows: every check below reads the host copy, before any launch; the kernel reads the device copy. The
+ * caller owns both and keeps the device table alive and unchanged until the step has run - two steps with two tables may be
+ * issued back to back on one stream. Pointers are 4-byte aligned device pointers to numel contiguous floats; a row whose
+ * pointers are all 16-byte aligned takes the vector path. */
+#define ORBIT_OPTIM_MAX_GROUPS 8
+#define ORBIT_OPTIM_FIRST_STEP 1 /* orbit_optim_row_t.flags, SGD with momentum: the tensor's first step, buf = g */
+typedef struct orbit_optim_row {
+    void* p;           /* parameter, updated in place */
+    const void* grad;  /* its gradient, read only */
+    void* state1;      /* Adam exp_avg / SGD momentum_buffer (may be NULL for SGD without momentum) */
+    void* state2;      /* Adam exp_avg_sq (unused by SGD, may be NULL there) */
+    uint64_t numel;
+    int32_t group;     /* index into group_lr / group_weight_decay */
+    int32_t flags;     /* ORBIT_OPTIM_* */
+} orbit_optim_row_t;
+/* Adam step number `step` (>= 1, the value torch keeps in state["step"] AFTER the step) of every row:
+ *   g += wd p;  m += (1 - beta1) (g - m);  v = beta2 v + (1 - beta2) g^2;
+ *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * Refused: a NULL table, host table, group array or row pointer; n_tensors <= 0; n_groups outside [1, 8]; a row's group outside
+ * [0, n_groups); a pointer that is not 4-byte aligned; numel == 0; step < 1; a beta outside [0, 1); a negative eps, lr or
+ * weight decay. Profiled as "optim_adam" (28 bytes per element). */
+int orbit_optim_adam_step(const orbit_optim_row_t* rows, const orbit_optim_row_t* host_rows, int n_tensors,
+                          const double* group_lr, const double* group_weight_decay, int n_groups, int64_t step, double beta1,
+                          double beta2, double eps, orbit_stream_t stream);
+/* SGD: g += wd p; momentum != 0: buf = g where the row carries ORBIT_OPTIM_FIRST_STEP, else buf = momentum buf + g, and
+ * p -= lr buf; momentum == 0: p -= lr g, state1 is not touched. The same refusals (state1 is required only with momentum;
+ * momentum must not be negative). Profiled as "optim_sgd" (12 bytes per element, 20 with momentum). */
+int orbit_optim_sgd_step(const orbit_optim_row_t* rows, const orbit_optim_row_t* host_rows, int n_tensors,
+                         const double* group_lr, const double* group_weight_decay, int n_groups, double momentum,
+                         orbit_stream_t stream);
+
 /* single training operators (NHWC, [M][C] = [B*H*W][C]), exposed for parity tests against torch autograd */
 /* out = act(BN_train(y) + residual): batch mean / biased variance, saves mean and 1/sqrt(var+eps), updates the running
  * statistics in place when given (unbiased variance, momentum). gamma/beta NULL = 1/0. act: NONE or RELU. */

@@ -129,6 +129,9 @@ _SIGNATURES = {
     "orbit_linear_head_backward": (c_int, [P, P, c_int, c_int, c_int, c_float, P, P, P]),
     "orbit_cross_entropy_forward": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
     "orbit_cross_entropy_backward": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
+    "orbit_optim_adam_step": (c_int, [P, P, c_int, POINTER(c_double), POINTER(c_double), c_int, ctypes.c_int64, c_double,
+                                      c_double, c_double, P]),
+    "orbit_optim_sgd_step": (c_int, [P, P, c_int, POINTER(c_double), POINTER(c_double), c_int, c_double, P]),
     "orbit_op_bn_train_forward": (c_int, [P, c_int, c_int, P, P, c_float, c_float, P, P, P, c_int, P, P, P, P]),
     "orbit_op_bn_stats_from_gram": (c_int, [P, c_int, c_int, P, c_int, c_float, P, P, P]),
     "orbit_op_bn_backward": (c_int, [P, P, P, c_int, c_int, P, P, P, c_int, c_int, P, P, P, P, P]),
@@ -196,6 +199,16 @@ class JpegDesc(ctypes.Structure):
 
 
 JPEG_STAGE_BYTES = 1024  # ORBIT_JPEG_STAGE_BYTES
+
+
+class OptimRow(ctypes.Structure):
+    """orbit_optim_row_t of include/orbit_hip.h"""
+    _fields_ = [("p", c_void_p), ("grad", c_void_p), ("state1", c_void_p), ("state2", c_void_p),
+                ("numel", ctypes.c_uint64), ("group", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+OPTIM_MAX_GROUPS = 8   # ORBIT_OPTIM_MAX_GROUPS
+OPTIM_FIRST_STEP = 1   # ORBIT_OPTIM_FIRST_STEP
 
 
 class OrbitHipError(RuntimeError):

@@ -13,8 +13,12 @@ Training (reference single-step-learner.py:128-243): per task `train_task` or `t
 batch {personalise_with_lite -> predict_a_batch -> N/(H*tasks_per_batch) * CE + 0.001 * l2 -> backward -> _reset}),
 optimizer.step()/zero_grad() every `tasks_per_batch` tasks, optimizer groups as utils/optim.py:11-33 (extractor
 parameters in their own group with `extractor_lr_scale`). All gradients come from the native backward kernels
-(model/autograd.py); the optimizer is torch.optim on the device-resident parameters. LR schedulers and checkpoint
-rotation of the reference loop are not part of the hot path and are left out.
+(model/autograd.py); the optimizer is torch.optim on the device-resident parameters, or with --native_optimizer the same
+update as one native launch per step (optim.NativeAdam / NativeSGD, csrc/optim.hip). The learning rate follows the
+reference's epoch schedules (--scheduler none | step | multistep | cosine with its warm-up and decay flags, utils/optim.py:34-43;
+optim.init_scheduler restates timm's formulas; default none = constant), stepped after every epoch before validation
+(single-step-learner.py:177-181). With --checkpoint_dir DIR rank 0 writes DIR/checkpoint.pt after every epoch with the reference's
+four keys (epoch, model_state_dict, optimizer_state_dict, best_stats; :377-390) and --resume continues from it at that epoch.
 
 On a dataset tree (--data_path ROOT, the reference's flag; --data_root DIR for the test loop alone) all three loops take
 their tasks from the reference-pinned sampler (data/datasets.py) in the reference's queue order (task_order) through the
@@ -48,7 +52,8 @@ from .data.datasets import ALL_FRAME_ANNOTATION_OPTIONS, BOUNDING_BOX_OPTIONS, F
 from .data.utils import attach_frame_history, unpack_task
 from .model.feature_extractors import EXTRACTORS
 from .model.few_shot_recognisers import SingleStepFewShotRecogniser
-from .optim import apply_lr_scale, cross_entropy, init_optimizer  # noqa: F401  (re-exported: bench.py, tools)
+from .optim import (SCHEDULERS, apply_lr_scale, cross_entropy, get_curr_learning_rates, init_optimizer,  # noqa: F401
+                    init_scheduler)  # (re-exported: bench.py, tools)
 from .utils.eval_metrics import TestEvaluator
 
 
@@ -120,8 +125,27 @@ def build_parser():
     p.add_argument("--fused_optimizer", action="store_true",
                    help="torch's fused multi-tensor Adam (same update, ~7 ms less host time per efficientnet_b0 step; the "
                         "native plans are re-synchronised from an optimizer step hook, optim.mark_parameters_changed)")
+    p.add_argument("--native_optimizer", action="store_true",
+                   help="the optimizer step as ONE native launch over all parameter tensors (csrc/optim.hip; torch.optim's "
+                        "arithmetic, state_dict interchangeable with torch.optim.Adam / SGD) instead of torch's foreach ops. "
+                        "Not together with --fused_optimizer")
     p.add_argument("--betas", type=float, nargs=2, default=(0.9, 0.98))
     p.add_argument("--momentum", type=float, default=0.0)
+    # learning-rate schedule (reference utils/args.py, consumed by utils/optim.py:34-43 through timm's create_scheduler)
+    p.add_argument("--scheduler", dest="sched", default="none", choices=list(SCHEDULERS),
+                   help="epoch schedule of the learning rate (the reference's --sched; none = constant --learning_rate)")
+    p.add_argument("--warmup_lr", type=float, default=1e-6, help="learning rate the linear warm-up starts from")
+    p.add_argument("--warmup_epochs", type=int, default=5, help="epochs of linear warm-up to --learning_rate (0: none)")
+    p.add_argument("--decay_epochs", type=int, default=15, help="step: epochs per decay; multistep: milestone spacing")
+    p.add_argument("--decay_rate", type=float, default=0.5, help="factor of every decay")
+    p.add_argument("--cooldown_epochs", type=int, default=0, help="accepted for the reference's command lines; has no effect")
+    p.add_argument("--lr_k_decay", type=float, default=0.1, help="cosine: exponent k of (t / epochs) ** k")
+    p.add_argument("--min_lr", type=float, default=1e-6, help="cosine: the floor of the learning rate")
+    p.add_argument("--checkpoint_dir", default=None, metavar="DIR",
+                   help="training: rank 0 writes DIR/checkpoint.pt after every epoch (epoch, model_state_dict, "
+                        "optimizer_state_dict, best_stats: reference single-step-learner.py:377-390)")
+    p.add_argument("--resume", action="store_true",
+                   help="training: load --checkpoint_dir/checkpoint.pt and continue at its epoch under the same arguments")
     p.add_argument("--print_by_step", action="store_true")
     p.add_argument("--results_path", default=None)
     p.add_argument("--save_predictions", default=None, metavar="DIR",
@@ -312,6 +336,13 @@ def verify_args(args):
         sys.exit("error: at least one of --learn_extractor and --adapt_features must be used when training")
     if args.frame_size % 1 or args.frame_size < 32:
         sys.exit("error: --frame_size must be >= 32")
+    if getattr(args, "resume", False):
+        if not getattr(args, "checkpoint_dir", None):
+            sys.exit("error: --resume needs --checkpoint_dir (the directory that holds checkpoint.pt)")
+        if not os.path.isfile(os.path.join(args.checkpoint_dir, "checkpoint.pt")):
+            sys.exit("error: --resume: %s does not exist" % os.path.join(args.checkpoint_dir, "checkpoint.pt"))
+    if getattr(args, "native_optimizer", False) and getattr(args, "fused_optimizer", False):
+        sys.exit("error: --native_optimizer and --fused_optimizer are two optimizer steps: choose one")
     expand_annotation_args(args)
     given = ["--" + f for f in ANNOTATION_FLAGS if getattr(args, f)]
     if given and not (getattr(args, "data_path", None) or getattr(args, "data_root", None)):
@@ -612,13 +643,16 @@ class Learner:
 
     def train(self, task_source=None):
         """task_source: an iterable of this rank's train tasks (task dicts as data/datasets.py returns them, all epochs in
-        train_order order) that stands in for the tree and the prefetcher; loop, seeds and step boundaries are the same."""
+        train_order order - with --resume those from the checkpoint's epoch on) that stands in for the tree and the prefetcher;
+        loop, seeds and step boundaries are the same."""
         a = self.args
         tree = split_roots(a).get("train")
         if tree is None and getattr(a, "data_root", None) and self.rank == 0:
             print("train: --data_root names a test split only: training runs on synthetic tasks (use --data_path ROOT)")
         self.optimizer = init_optimizer(self.model, a.learning_rate, a.optimizer, a, a.extractor_lr_scale)
-        apply_lr_scale(self.optimizer, a.learning_rate)  # constant schedule (the reference's timm scheduler applies it)
+        self.scheduler = init_scheduler(self.optimizer, a)  # applies f(0) * lr_scale (default: the constant --learning_rate)
+        start_epoch = self.load_checkpoint() if getattr(a, "resume", False) else 0
+        lr_history, num_updates = [], 0
         self.grad_bucket = None
         if self.world > 1:
             p2p = None
@@ -645,7 +679,8 @@ class Learner:
             # that anyway - before it asks for the next task, so no consumer_streams are passed to the prefetcher.
             dataset = self.build_dataset("train")
             self._train_items = num_items(dataset)
-            prefetch = self._prefetch(dataset, [i for epoch in range(a.epochs) for i in self.train_order(epoch)], depth=2)
+            prefetch = self._prefetch(dataset, [i for epoch in range(start_epoch, a.epochs) for i in self.train_order(epoch)],
+                                      depth=2)
             stream = iter(prefetch)
             # The yielded clips are complete on the caller's stream when next() returns (it waits for the slot's event), so the
             # query batch's taped pass may start from LITE's fork point as it does for clips on the host: the same kernels,
@@ -655,7 +690,8 @@ class Learner:
         torch.set_grad_enabled(True)
         try:
             self.model.set_test_mode(False)
-            for epoch in range(a.epochs):
+            for epoch in range(start_epoch, a.epochs):
+                first_loss = len(losses)
                 # with --data_path: --num_train_tasks per user (or object), in the queue's order (task_order)
                 total_steps = a.num_train_tasks if tree is None else self._num_train_items() * a.num_train_tasks
                 # this rank's tasks of the epoch are generated up front (the reference prefetches with DataLoader
@@ -700,10 +736,20 @@ class Learner:
                             self.grad_bucket.zero_()  # one memset; gradients keep living inside the flat bucket
                         else:
                             self.optimizer.zero_grad()
+                        num_updates += 1
+                        self.scheduler.step_update(num_updates)  # (a no-op for epoch schedules, where the reference calls it: :166)
+                lr, fe_lr = get_curr_learning_rates(self.optimizer)[:2]  # reference :170-174
+                lr_history.append((lr, fe_lr))
+                if self.rank == 0:
+                    print("epoch [%d/%d] train loss: %.7f lr: %.3e fe-lr: %.3e"
+                          % (epoch + 1, a.epochs, float(np.mean(losses[first_loss:])) if len(losses) > first_loss else float("nan"),
+                             lr, fe_lr))
+                self.scheduler.step(epoch + 1)  # before validation, the reference's order (:177-181)
                 if a.num_val_tasks > 0 and (epoch + 1) >= a.validation_on_epoch:
                     self.validate(epoch + 1)
                     torch.set_grad_enabled(True)
                     self.model.set_test_mode(False)
+                self.save_checkpoint(epoch + 1)
         finally:
             torch.set_grad_enabled(prev)
             self.model.lite_query_overlap = lite_query_overlap
@@ -721,7 +767,9 @@ class Learner:
         stats = {"loss": mean_ci(losses) if losses else (0.0, 0.0), "frame_acc": mean_ci(accs) if accs else (0.0, 0.0),
                  "ms_per_task": mean_ci(times) if times else (0.0, 0.0), "num_tasks": len(losses),
                  "world_size": self.world, "validation": getattr(self, "validation_history", None),
-                 "best_validation": getattr(self, "best_validation", None)}
+                 "best_validation": getattr(self, "best_validation", None),
+                 "lr": lr_history[-1][0] if lr_history else None, "fe_lr": lr_history[-1][1] if lr_history else None,
+                 "lr_history": lr_history, "start_epoch": start_epoch}
         # the tree's side of the run (None / empty on synthetic tasks). ms_per_task is the step alone; data_wait_ms is the time
         # the loop was blocked in next() on the prefetcher, per task; wall_s covers both, validation and the optimizer steps
         stored = sorted(prefetch.stored_sizes) if prefetch is not None else []
@@ -744,6 +792,41 @@ class Learner:
                       % ("%s, %s" % (a.data_path, a.train_task_type) if prefetch is not None else "tasks handed in",
                          stats["frames_per_task"][0], *stats["data_wait_ms"], a.decode, a.num_workers, len(losses) / max(wall, 1e-9)))
         return stats
+
+    def save_checkpoint(self, epoch):
+        """reference single-step-learner.py:377-383: DIR/checkpoint.pt with its four keys, written by rank 0 (every rank holds
+        the same parameters and optimizer state after a step). Written AFTER the epoch's validation - the reference writes it
+        before - so that best_stats covers the epoch the file names and a resumed run takes the decisions of a straight one.
+        The file is replaced atomically: an interruption during the write leaves the previous epoch's checkpoint."""
+        directory = getattr(self.args, "checkpoint_dir", None)
+        if not directory or self.rank != 0:
+            return
+        os.makedirs(directory, exist_ok=True)
+        path = os.path.join(directory, "checkpoint.pt")
+        torch.save({"epoch": epoch,
+                    "model_state_dict": {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
+                    "optimizer_state_dict": self.optimizer.state_dict(),
+                    "best_stats": {"best_validation": getattr(self, "best_validation", None),
+                                   "validation_history": getattr(self, "validation_history", None)}}, path + ".tmp")
+        os.replace(path + ".tmp", path)
+
+    def load_checkpoint(self):
+        """reference single-step-learner.py:385-390: model, optimizer state and best validation stats from
+        --checkpoint_dir/checkpoint.pt. -> the epoch to continue at; the schedule is set to f(epoch)."""
+        path = os.path.join(self.args.checkpoint_dir, "checkpoint.pt")
+        checkpoint = torch.load(path, map_location="cpu")
+        self.model.load_state_dict(checkpoint["model_state_dict"])
+        self.optimizer.load_state_dict(checkpoint["optimizer_state_dict"])
+        best = checkpoint.get("best_stats") or {}
+        if best.get("best_validation") is not None:
+            self.best_validation = tuple(best["best_validation"])
+        if best.get("validation_history") is not None:
+            self.validation_history = list(best["validation_history"])
+        epoch = int(checkpoint["epoch"])
+        self.scheduler.step(epoch)
+        if self.rank == 0:
+            print("resumed from %s: continuing at epoch %d of %d" % (path, epoch + 1, self.args.epochs))
+        return epoch
 
     def validate(self, epoch=0):
         """The reference's validate() (single-step-learner.py:245-296) on held-out tasks - synthetic ones, or with
@@ -994,7 +1077,7 @@ class MultiStepLearner(Learner):
                 "extractor_lr_scale": a.personalize_extractor_lr_scale, "loss_fn": cross_entropy,
                 "optimizer": a.personalize_optimizer, "momentum": a.personalize_momentum,
                 "weight_decay": a.personalize_weight_decay, "betas": tuple(a.personalize_betas),
-                "epsilon": a.personalize_epsilon}
+                "epsilon": a.personalize_epsilon, "native_optimizer": bool(getattr(a, "native_optimizer", False))}
 
     # the tree loop (Learner.test_directory: --data_root, or --data_path's test split) with the finetuner's two steps
     def _personalise_tree_task(self, task):
