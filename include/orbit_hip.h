@@ -391,6 +391,21 @@ int orbit_op_conv2d_train(const float* x, int x_nchw, const float* w, float* y, 
 int orbit_op_dwconv2d_train(const float* x, const float* w, float* y, const float* in_scale, const float* in_shift,
                             int in_act, int B, int H, int W, int C, int K, int stride, int pad_top, int pad_left, int Ho,
                             int Wo, float* stats, orbit_stream_t stream);
+/* The squeeze-excite chain of an MBConv block in inference, link by link (single-operator entries of the parity tests).
+ * orbit_op_dwconv2d_se: orbit_op_dwconv2d with the pooling epilogue the plan runs, partial[b][chunk][c] = sum of y over the output
+ *   rows of the chunk, [B][chunks][C]; the kernel form follows the options dw_window / dw_lds / dw_pipe.
+ * orbit_op_dwconv2d_plan (host only): the form that launch takes under the current options, after the fallback of an LDS patch
+ *   that cannot be laid out (*form: 0 streaming, 1 software-pipelined streaming, 2 register window, 3 LDS patch; train_form != 0:
+ *   the rule of the statistics form), with *chunks and *rows_per_chunk of its pooling partials.
+ * orbit_op_se_gate2: the gate kernel of the plans from pooling partials [B][chunks][C]: pooled = (sum over chunks) / hw,
+ *   gate = sigmoid(W2 silu(W1 pooled + b1) + b2); W1 [R][C], W2 torch layout [C][R]; pooled_out [B][C] or NULL. */
+int orbit_op_dwconv2d_se(const float* x, const float* w, const float* scale, const float* shift, int act, int B, int H, int W,
+                         int C, int K, int stride, int pad_top, int pad_left, int Ho, int Wo, float* y, float* partial,
+                         orbit_stream_t stream);
+int orbit_op_dwconv2d_plan(int B, int C, int K, int stride, int Ho, int Wo, int train_form, int* form, int* chunks,
+                           int* rows_per_chunk);
+int orbit_op_se_gate2(const float* partial, int chunks, int hw, const float* w1, const float* b1, const float* w2,
+                      const float* b2, int B, int C, int R, float* gate, float* pooled_out, orbit_stream_t stream);
 /* max-pool NHWC, -inf padding */
 int orbit_op_maxpool2d(const float* x, float* y, int B, int H, int W, int C, int K, int stride, int pad,
                        int Ho, int Wo, orbit_stream_t stream);

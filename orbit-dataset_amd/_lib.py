@@ -85,6 +85,9 @@ _SIGNATURES = {
     "orbit_pw_stream_supported": (c_int, [c_int] * 4),
     "orbit_op_conv2d_train": (c_int, [P, c_int, P, P, P] + [c_int] * 12 + [P, POINTER(c_int), P]),
     "orbit_op_dwconv2d_train": (c_int, [P, P, P, P, P] + [c_int] * 11 + [P, P]),
+    "orbit_op_dwconv2d_se": (c_int, [P, P, P, P] + [c_int] * 11 + [P, P, P]),
+    "orbit_op_dwconv2d_plan": (c_int, [c_int] * 7 + [POINTER(c_int)] * 3),
+    "orbit_op_se_gate2": (c_int, [P, c_int, c_int, P, P, P, P, c_int, c_int, c_int, P, P, P]),
     "orbit_op_maxpool2d": (c_int, [P, P] + [c_int] * 9 + [P]),
     "orbit_op_avgpool": (c_int, [P, P, c_int, c_int, c_int, P]),
     "orbit_op_se_gate": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P]),

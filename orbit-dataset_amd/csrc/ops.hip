@@ -1035,7 +1035,7 @@ int orbit_op_dwconv2d_train(const float* x, const float* w, float* y, const floa
     const int nblk = B * dwconv_se_chunks(Ho);
     float* tmp = nullptr;
     const size_t wfl = (size_t)C * K * K, pfl = bn_partial_floats((size_t)nblk, C) + 4 * (size_t)C;
-    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (wfl + pfl) * sizeof(float), s));
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (((wfl + 63) & ~(size_t)63) + pfl) * sizeof(float), s));
     float* part = tmp + ((wfl + 63) & ~(size_t)63);
     int rc = dwconv_pack_weights(w, tmp, C, K, s);
     if (rc == ORBIT_OK)
@@ -1045,6 +1045,53 @@ int orbit_op_dwconv2d_train(const float* x, const float* w, float* y, const floa
     // the variance. Simpler for a test: finalize with M = 1 and eps = 0 is not meaningful - sum the partials directly
     if (rc == ORBIT_OK) rc = launch_sum_partials(part, nblk, C, stats, s);
     (void)hipFreeAsync(tmp, s);
+    return rc;
+}
+
+/* Inference form of the depthwise op WITH its squeeze-excite pooling epilogue (single-operator entry for the parity tests): the
+ * launch the plan makes for an MBConv block's depthwise layer, y = act(dw(x) * scale + shift) and partial[b][chunk][c] = the sum
+ * of y over the chunk's output rows; partial is [B][chunks][C] with chunks as orbit_op_dwconv2d_plan reports them. */
+int orbit_op_dwconv2d_se(const float* x, const float* w, const float* scale, const float* shift, int act, int B, int H, int W,
+                         int C, int K, int stride, int pad_top, int pad_left, int Ho, int Wo, float* y, float* partial,
+                         orbit_stream_t stream) {
+    ORBIT_REQUIRE(x && w && y && partial, "op_dwconv2d_se: null pointer");
+    ORBIT_REQUIRE(B > 0 && C > 0 && Ho > 0 && Wo > 0 && (K == 3 || K == 5), "op_dwconv2d_se: bad geometry");
+    hipStream_t s = (hipStream_t)stream;
+    float* wp = nullptr;
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&wp), (size_t)C * K * K * sizeof(float), s));
+    int rc = dwconv_pack_weights(w, wp, C, K, s);
+    if (rc == ORBIT_OK)
+        rc = launch_dwconv_se(x, wp, y, scale, shift, partial, LayerGeom{B, H, W, C, C, K, K, stride, pad_top, pad_left, Ho, Wo}, act, s,
+                              0);
+    (void)hipFreeAsync(wp, s);
+    return rc;
+}
+
+/* Host only: the kernel form launch_dwconv_se runs for this layer under the current options, after the LDS-fit fallback, and
+ * the row chunking of its pooling partials. *form: 0 streaming, 1 software-pipelined, 2 register window, 3 LDS patch. */
+int orbit_op_dwconv2d_plan(int B, int C, int K, int stride, int Ho, int Wo, int train_form, int* form, int* chunks,
+                           int* rows_per_chunk) {
+    ORBIT_REQUIRE(form && chunks && rows_per_chunk, "op_dwconv2d_plan: null pointer");
+    ORBIT_REQUIRE(B > 0 && C > 0 && C % 4 == 0 && Ho > 0 && Wo > 0 && (K == 3 || K == 5) && (stride == 1 || stride == 2),
+                  "op_dwconv2d_plan: bad geometry");
+    const DwPlan p = dw_plan(B, C, K, stride, Ho, Wo, train_form != 0);
+    *form = (int)p.form, *chunks = (int)p.grid.y, *rows_per_chunk = p.rpc;
+    return ORBIT_OK;
+}
+
+/* The gate kernel the plans launch (se_gate2_kernel / se_gate_frame), single-operator entry for the parity tests:
+ * pooled = (sum over chunks of partial[b][chunk]) / hw, gate = sigmoid(W2 silu(W1 pooled + b1) + b2). w2 in torch layout [C][R]
+ * (transposed here as the plan's packing does); pooled_out [B][C] or nullptr. */
+int orbit_op_se_gate2(const float* partial, int chunks, int hw, const float* w1, const float* b1, const float* w2,
+                      const float* b2, int B, int C, int R, float* gate, float* pooled_out, orbit_stream_t stream) {
+    ORBIT_REQUIRE(partial && w1 && b1 && w2 && b2 && gate, "op_se_gate2: null pointer");
+    ORBIT_REQUIRE(B > 0 && C > 0 && R > 0 && chunks > 0 && hw > 0, "op_se_gate2: bad sizes");
+    hipStream_t s = (hipStream_t)stream;
+    float* w2t = nullptr;
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&w2t), (size_t)C * R * sizeof(float), s));
+    int rc = launch_transpose(w2, w2t, C, R, s);
+    if (rc == ORBIT_OK) rc = launch_se_gate2(partial, chunks, hw, w1, b1, w2t, b2, gate, B, C, R, s, pooled_out);
+    (void)hipFreeAsync(w2t, s);
     return rc;
 }
 

@@ -1,0 +1,401 @@
+"""The squeeze-excite inference chain of an MBConv block, link by link against float64 on the CPU:
+
+    depthwise conv (+BN+SiLU) with its pooling partials   orbit_op_dwconv2d_se   (all four kernel forms of csrc/ops.hip)
+      -> se_gate2_kernel<256 | 1024> / se_gate_frame       orbit_op_se_gate2      (csrc/se_gate.h)
+      -> gated projection                                  orbit_op_pw_stream (gate in the prologue) / orbit_op_conv2d
+
+Every output buffer is pre-filled with NaN and followed by a guard tail of sentinel floats: no NaN may remain and the tail must
+come back untouched. Every bound is a project constant, a summation bound or a multiple of the fp32 CPU evaluation's own error:
+
+  elementwise y      err <= max(2e-5, 4 E32) max(1, max |y64|)       (the gate of tests/test_gpu_effnetv2_ops.py)
+  pooling partials   |partial - S| <= 2 n u A, u = 2^-24, S / A the float64 sum of the n outputs THE KERNEL WROTE / of their
+                     magnitudes: twice the (n - 1) u A of any summation order - a dropped, doubled or misplaced output breaks it
+  pooled means       2 (chunks + 1) u sum_k |partial_k| / HW
+  gates              max(2e-6, 4 E32)                                 (2e-6: test_se_gate's bound for a gate in (0, 1))
+
+Each check prints "[se_path] family: case: ratio error / bound" (pytest -s)."""
+import contextlib
+import ctypes
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+import orbit_dataset_amd  # noqa: E402,F401
+from orbit_dataset_amd import _lib  # noqa: E402
+
+SILU = 2
+U = 2.0 ** -24
+GUARD = 4096
+SENTINEL = -12345.5
+STREAM, PIPE, WINDOW, LDS = 0, 1, 2, 3  # DwForm of csrc/common.h, as orbit_op_dwconv2d_plan reports it
+
+_worst = {}
+
+
+def _report(family, what, err, bound):
+    ratio = err / bound
+    _worst[family] = max(_worst.get(family, 0.0), ratio)
+    print("\n[se_path] %s: %s: err %.3g, bound %.3g, ratio %.3g (family max %.3g)" % (family, what, err, bound, ratio, _worst[family]))
+    return ratio
+
+
+def _st():
+    return _lib.stream_handle()
+
+
+class Guarded:
+    """An output buffer of `shape`, NaN-filled, with GUARD sentinel floats behind it."""
+
+    def __init__(self, shape, device):
+        n = 1
+        for s in shape:
+            n *= s
+        self.flat = torch.full((n + GUARD,), SENTINEL, device=device)
+        self.flat[:n] = float("nan")
+        self.t = self.flat[:n].view(*shape)
+
+    def cpu(self, what):
+        """The result on the CPU, after the guard checks (call after a synchronize)."""
+        flat = self.flat.cpu()
+        n = self.t.numel()
+        assert torch.equal(flat[n:], torch.full((GUARD,), SENTINEL)), "%s: wrote behind its buffer" % what
+        assert not torch.isnan(flat[:n]).any(), "%s: elements left unwritten (or NaN)" % what
+        return flat[:n].view(*self.t.shape).clone()
+
+
+@contextlib.contextmanager
+def options(lib, **kv):
+    """Set runtime options for a block; the previous values come back whatever happens inside."""
+    prev = {k.encode(): lib.orbit_get_option(k.encode()) for k in kv}
+    try:
+        for k, v in kv.items():
+            lib.orbit_set_option(k.encode(), v)
+        yield
+    finally:
+        for k, v in prev.items():
+            lib.orbit_set_option(k, v)
+
+
+def nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+# ---- references (CPU; dtype = float64 is the oracle, float32 its own-error yardstick) -------------------------------------------
+def same_pad(size, K, stride):
+    """TF-SAME: output size, total padding, leading padding."""
+    out = -(-size // stride)
+    total = max((out - 1) * stride + K - size, 0)
+    return out, total, total // 2
+
+
+def dw_inputs(family, B, C, K, H, W, seed):
+    g = torch.Generator().manual_seed(seed)
+    if family == "normal":  # the Gaussian inputs of tests/test_gpu_ops.py::test_dwconv
+        x = torch.randn(B, C, H, W, generator=g)
+        w = torch.randn(C, 1, K, K, generator=g) / K
+        scale = torch.rand(C, generator=g) + 0.5
+        shift = torch.randn(C, generator=g) * 0.1
+    else:  # one_sign: every product positive, every SiLU output bounded away from 0
+        x = torch.rand(B, C, H, W, generator=g) + 0.5
+        w = (torch.rand(C, 1, K, K, generator=g) + 0.5) / (K * K)
+        scale = torch.rand(C, generator=g) + 0.5
+        shift = torch.rand(C, generator=g) * 0.5 + 0.5
+    return x, w, scale, shift
+
+
+def dw_ref(x, w, scale, shift, K, stride, dtype):
+    """act(dw(x) * scale + shift) with TF-SAME padding, NCHW."""
+    x, w, scale, shift = (t.to(dtype) for t in (x, w, scale, shift))
+    _, th, pt = same_pad(x.shape[2], K, stride)
+    _, tw, pl = same_pad(x.shape[3], K, stride)
+    y = F.conv2d(F.pad(x, [pl, tw - pl, pt, th - pt]), w, None, stride, 0, 1, x.shape[1])
+    return F.silu(y * scale[None, :, None, None] + shift[None, :, None, None])
+
+
+def se_inputs(B, C, R, chunks, hw, seed):
+    """Synthetic pooling partials of a SiLU activation (column sums of chunks of hw / chunks pixels) and a gate MLP whose first
+    layer is scaled up so that the hidden units, and through them the gates, move with the pooled values."""
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
+    return {"partial": (0.3 + 0.5 * r(B, chunks, C)) * (hw / chunks), "w1": 2.0 * r(R, C) * C ** -0.5, "b1": 0.1 * r(R),
+            "w2": r(C, R) * R ** -0.5, "b2": 0.1 * r(C)}
+
+
+def se_ref(partial, hw, w1, b1, w2, b2, dtype):
+    """(pooled means [B][C], gates [B][C]) from partials [B][chunks][C]."""
+    partial, w1, b1, w2, b2 = (t.to(dtype) for t in (partial, w1, b1, w2, b2))
+    pooled = partial.sum(1) / hw
+    return pooled, torch.sigmoid(F.silu(pooled @ w1.t() + b1) @ w2.t() + b2)
+
+
+def gates_unsaturated(gate64):
+    """A saturated sigmoid would hide a wrong pooled value: at least 90 % of the reference gates lie in (0.05, 0.95)."""
+    return ((gate64 > 0.05) & (gate64 < 0.95)).double().mean().item() >= 0.9
+
+
+def proj_ref(x, gate, w, scale, shift, res, dtype):
+    """scale * conv1x1(x * gate) + shift (+ res); x / res NHWC, gate [B][Cin], w [Cout][Cin]."""
+    x, gate, w, scale, shift = (t.to(dtype) for t in (x, gate, w, scale, shift))
+    y = (x * gate[:, None, None, :]) @ w.t() * scale + shift
+    return y + res.to(dtype) if res is not None else y
+
+
+def elementwise_gate(family, what, got, want64, want32):
+    e32 = (want32.double() - want64).abs().max().item()
+    tol = max(2e-5, 4 * e32) * max(1.0, want64.abs().max().item())
+    err = (got.double() - want64).abs().max().item()
+    _report(family, what, err, tol)
+    assert err <= tol, (what, err, tol, e32)
+
+
+def gate_gate(family, what, got, want64, want32):
+    e32 = (want32.double() - want64).abs().max().item()
+    tol = max(2e-6, 4 * e32)
+    err = (got.double() - want64).abs().max().item()
+    _report(family, what, err, tol)
+    assert err <= tol, (what, err, tol, e32)
+
+
+# ---- a. depthwise pooling partials ------------------------------------------------------------------------------------------------
+def chunk_rows(Ho, rpc):
+    return [min(rpc, Ho - r) for r in range(0, Ho, rpc)]
+
+
+# name, B, C, K, stride, H, W, (dw_window, dw_lds, dw_pipe), form, output rows per chunk.
+# Stride 2 maps have H even and W odd: TF-SAME pads (0, 1) top / left for 3x3 and (1, 2) for 5x5. Block layouts of the streaming
+# forms (cb4 channel quads x WL column lanes of 256 threads): C = 144: 36 x 7, 4 idle; 240: 60 x 4, 16 idle; 1152: 48 x 5,
+# 16 idle; 32: 8 x 32, none idle.
+DW_CASES = [
+    # each form on a shape its rule selects
+    ("window_rule_k3s1_c32_57x6", 3, 32, 3, 1, 57, 6, (1, 1, 1), WINDOW, [8] * 7 + [1]),
+    ("window_rule_k3s1_c144_17x13", 1, 144, 3, 1, 17, 13, (1, 1, 1), WINDOW, [7, 7, 3]),
+    ("lds_rule_k5s1_c240_17x13", 3, 240, 5, 1, 17, 13, (1, 1, 1), LDS, [7, 7, 3]),
+    ("lds_rule_k3s1_c1152_13x9", 1, 1152, 3, 1, 13, 9, (1, 1, 1), LDS, [13]),
+    # 16-quad slices on a 7-row map: 11 x 12 patch pixels for 16 threads per quad, the 12-loads-in-flight staging instantiation
+    ("lds_rule_k5s1_c128_7x6", 3, 128, 5, 1, 7, 6, (1, 1, 1), LDS, [7]),
+    ("pipe_rule_k3s2_c32_114x11", 1, 32, 3, 2, 114, 11, (1, 1, 1), PIPE, [8] * 7 + [1]),
+    ("pipe_rule_k5s2_c144_56x9", 3, 144, 5, 2, 56, 9, (1, 1, 1), PIPE, [7] * 4),
+    ("stream_rule_k5s2_c1152_30x13", 1, 1152, 5, 2, 30, 13, (1, 1, 1), STREAM, [7, 7, 1]),
+    ("stream_rule_k3s2_c240_34x13", 3, 240, 3, 2, 34, 13, (1, 1, 1), STREAM, [7, 7, 3]),
+    # the LDS rule claims the shape, but no slice of 16, 8 or 4 channel quads divides C / 4 = 10: the fallback form
+    ("lds_unfit_k5s1_c40_15x10", 3, 40, 5, 1, 15, 10, (1, 1, 1), STREAM, [7, 7, 1]),
+    ("lds_unfit_k3s1_c40_14x6", 1, 40, 3, 1, 14, 6, (1, 1, 1), WINDOW, [7, 7]),
+    # each form forced on a shape the rules keep from it
+    ("stream_forced_k3s1_c144_15x10", 3, 144, 3, 1, 15, 10, (0, 0, 0), STREAM, [7, 7, 1]),
+    ("window_forced_k5s2_c32_26x9", 1, 32, 5, 2, 26, 9, (2, 0, 0), WINDOW, [13]),
+    ("window_forced_k5s1_c240_17x13", 1, 240, 5, 1, 17, 13, (2, 0, 0), WINDOW, [7, 7, 3]),
+    ("lds_forced_k3s2_c32_34x13", 3, 32, 3, 2, 34, 13, (0, 2, 0), LDS, [7, 7, 3]),
+    ("lds_forced_k5s2_c144_30x13", 1, 144, 5, 2, 30, 13, (0, 2, 0), LDS, [7, 7, 1]),
+    ("pipe_forced_k5s1_c1152_13x9", 1, 1152, 5, 1, 13, 9, (0, 0, 2), PIPE, [13]),
+    ("pipe_forced_k3s1_c32_15x6", 3, 32, 3, 1, 15, 6, (0, 0, 2), PIPE, [7, 7, 1]),
+]
+
+
+def one_sign_margin(y64, rows, Wo):
+    """(min |y64|, 4 n^2 u mean |y64|) for the largest chunk's n outputs: with the first above the second, one dropped or doubled
+    output moves a partial by more than its bound 2 n u A <= 2 n^2 u max-chunk-mean allows."""
+    n = max(rows) * Wo
+    a = y64.abs()
+    return a.min().item(), 4.0 * n * n * U * a.mean().item()
+
+
+def dw_plan(lib, B, C, K, stride, Ho, Wo):
+    form, chunks, rpc = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    _lib.check(lib.orbit_op_dwconv2d_plan(B, C, K, stride, Ho, Wo, 0, ctypes.byref(form), ctypes.byref(chunks), ctypes.byref(rpc)),
+               "orbit_op_dwconv2d_plan")
+    return form.value, chunks.value, rpc.value
+
+
+def run_dwconv_se(lib, device, x, w, scale, shift, K, stride, opts, form, rows):
+    """orbit_op_dwconv2d_se on NCHW CPU inputs under the option triple; asserts the planned form and chunking; returns
+    (y NHWC, partial [B][chunks][C]) on the CPU after the guard checks."""
+    B, C, H, W = x.shape
+    Ho, _, pt = same_pad(H, K, stride)
+    Wo, _, pl = same_pad(W, K, stride)
+    with options(lib, dw_window=opts[0], dw_lds=opts[1], dw_pipe=opts[2]):
+        got_form, chunks, rpc = dw_plan(lib, B, C, K, stride, Ho, Wo)
+        assert got_form == form, "planned form %d, the case is named after %d" % (got_form, form)
+        assert chunk_rows(Ho, rpc) == rows and chunks == len(rows) and sum(rows) == Ho  # the chunks tile Ho exactly
+        dev = [t.to(device).contiguous() for t in (nhwc(x), w, scale, shift)]
+        y, partial = Guarded((B, Ho, Wo, C), device), Guarded((B, chunks, C), device)
+        _lib.check(lib.orbit_op_dwconv2d_se(*[_lib.dptr(t) for t in dev], SILU, B, H, W, C, K, stride, pt, pl, Ho, Wo, _lib.dptr(y.t),
+                                            _lib.dptr(partial.t), _st()), "orbit_op_dwconv2d_se")
+        torch.cuda.synchronize()
+    return y.cpu("y"), partial.cpu("partial")
+
+
+def check_partials(name, y, partial, rows):
+    """partial[b][chunk][c] against the float64 sums of the outputs the kernel wrote (y NHWC, CPU), and their sum over the
+    chunks against the plane sum."""
+    B, Ho, Wo, C = y.shape
+    yd = y.double()
+    worst = 0.0
+    r0 = 0
+    for k, nr in enumerate(rows):
+        blk = yd[:, r0:r0 + nr]
+        S, A = blk.sum((1, 2)), blk.abs().sum((1, 2))
+        bound = 2.0 * nr * Wo * U * A
+        err = (partial[:, k].double() - S).abs()
+        worst = max(worst, (err / bound).max().item())
+        bad = err > bound
+        assert not bad.any(), (name, "chunk %d" % k, err[bad].max().item(), bound[bad].min().item())
+        r0 += nr
+    _report("dw_partial", name, worst, 1.0)
+    S, A = yd.sum((1, 2)), yd.abs().sum((1, 2))
+    bound = 2.0 * Ho * Wo * U * A
+    err = (partial.double().sum(1) - S).abs()
+    _report("dw_plane", name, (err / bound).max().item(), 1.0)
+    assert not (err > bound).any(), (name, "plane", err.max().item())
+
+
+@pytest.mark.parametrize("family", ["normal", "one_sign"])
+@pytest.mark.parametrize("name,B,C,K,stride,H,W,opts,form,rows", DW_CASES, ids=[c[0] for c in DW_CASES])
+def test_dwconv_pooling_partials(lib, device, family, name, B, C, K, stride, H, W, opts, form, rows):
+    x, w, scale, shift = dw_inputs(family, B, C, K, H, W, seed=C + 7 * K + stride)
+    want = dw_ref(x, w, scale, shift, K, stride, torch.float64)
+    if stride == 2:
+        assert same_pad(H, K, 2)[2] != same_pad(W, K, 2)[2]  # pad_top != pad_left
+    if family == "one_sign":  # on the reference, before the kernel's result is looked at
+        lo, need = one_sign_margin(want, rows, want.shape[3])
+        assert lo > need, (lo, need)
+    y, partial = run_dwconv_se(lib, device, x, w, scale, shift, K, stride, opts, form, rows)
+    elementwise_gate("dw_y", "%s/%s" % (name, family), y.permute(0, 3, 1, 2), want,
+                     dw_ref(x, w, scale, shift, K, stride, torch.float32))
+    check_partials("%s/%s" % (name, family), y, partial, rows)
+
+
+# ---- b. se_gate2 from synthetic partials ------------------------------------------------------------------------------------------
+# C, R, chunks. NT = 256 below C = 1024, 1024 from there; parts = NT / (C / 4) thread groups share a channel quad's chunk list
+# where C / 4 <= NT / 2, and the many-chunk pooling branch runs for parts > 1 and chunks > 8.
+SE_CASES = [
+    (32, 8, 1), (32, 8, 8), (32, 8, 9), (32, 8, 98),  # either side of the chunks > 8 switch, parts = 32
+    (96, 4, 49),      # parts = 10, 16 idle threads in the many-chunk branch; layer 2 is its tail loop only
+    (144, 6, 14),     # parts = 7
+    (240, 10, 2),     # layer 2: one group of eight hidden units plus a tail of two
+    (672, 28, 2),     # C / 4 = 168 > NT / 2: one pooling group, single-pass branch
+    (960, 40, 2),
+    (1152, 48, 1), (1152, 48, 9),  # NT = 1024; the many-chunk branch with parts = 3
+    (1536, 64, 1),    # NT = 1024, second layer-1 pass (C > 1280), full rounds of 64 hidden units
+]
+
+
+def se_hw(chunks):
+    return 61 * chunks  # pixels per frame: no power of two, so 1 / hw rounds
+
+
+def run_se_gate2(lib, device, t, B, C, R, chunks, hw, with_pooled=True):
+    dev = {k: v.to(device).contiguous() for k, v in t.items()}
+    gate = Guarded((B, C), device)
+    pooled = Guarded((B, C), device) if with_pooled else None
+    d = _lib.dptr
+    _lib.check(lib.orbit_op_se_gate2(d(dev["partial"]), chunks, hw, d(dev["w1"]), d(dev["b1"]), d(dev["w2"]), d(dev["b2"]), B, C, R,
+                                     d(gate.t), d(pooled.t) if with_pooled else None, _st()), "orbit_op_se_gate2")
+    torch.cuda.synchronize()
+    return gate.cpu("gate"), pooled.cpu("pooled_out") if with_pooled else None
+
+
+def check_se(what, t, hw, gate, pooled):
+    chunks = t["partial"].shape[1]
+    p64, g64 = se_ref(t["partial"], hw, t["w1"], t["b1"], t["w2"], t["b2"], torch.float64)
+    _, g32 = se_ref(t["partial"], hw, t["w1"], t["b1"], t["w2"], t["b2"], torch.float32)
+    assert gates_unsaturated(g64), what
+    if pooled is not None:
+        bound = 2.0 * (chunks + 1) * U * t["partial"].double().abs().sum(1) / hw
+        err = (pooled.double() - p64).abs()
+        _report("se_pooled", what, (err / bound).max().item(), 1.0)
+        assert not (err > bound).any(), (what, err.max().item(), bound.min().item())
+    gate_gate("se_gate", what, gate, g64, g32)
+
+
+@pytest.mark.parametrize("C,R,chunks", SE_CASES)
+def test_se_gate2(lib, device, C, R, chunks):
+    hw = se_hw(chunks)
+    t = se_inputs(3, C, R, chunks, hw, seed=C + chunks)
+    what = "C%d R%d chunks%d" % (C, R, chunks)
+    gate, pooled = run_se_gate2(lib, device, t, 3, C, R, chunks, hw)
+    check_se(what + " B3", t, hw, gate, pooled)
+    bare, _ = run_se_gate2(lib, device, t, 3, C, R, chunks, hw, with_pooled=False)
+    assert torch.equal(bare, gate), what + ": the gate depends on pooled_out"
+    for b in range(3):  # frame b of the B = 3 launch has the bits of a B = 1 launch on that frame
+        one = dict(t, partial=t["partial"][b:b + 1].contiguous())
+        g1, p1 = run_se_gate2(lib, device, one, 1, C, R, chunks, hw)
+        if b == 0:
+            check_se(what + " B1", one, hw, g1, p1)
+        assert torch.equal(g1[0], gate[b]) and torch.equal(p1[0], pooled[b]), (what, b)
+
+
+# ---- c. the gate in the streaming projection's prologue ---------------------------------------------------------------------------
+PW_LAYERS = [(32, 16, 8, False), (96, 24, 4, False), (144, 24, 6, True), (144, 40, 6, False)]  # Cin, Cout, R, residual
+
+
+@pytest.mark.parametrize("H,W", [(4, 4), (8, 6)])
+@pytest.mark.parametrize("Cin,Cout,R,residual", PW_LAYERS, ids=["%dx%d" % (l[0], l[1]) for l in PW_LAYERS])
+def test_pw_stream_gate_and_projection(lib, device, Cin, Cout, R, residual, H, W):
+    assert lib.orbit_pw_stream_supported(Cin, Cout, H, W) == 1
+    d = _lib.dptr
+    for B in (1, 3):
+        for chunks in (1, 9):
+            t = se_inputs(B, Cin, R, chunks, H * W, seed=Cin + Cout + 3 * B + chunks)
+            g = torch.Generator().manual_seed(Cin + H)
+            x = torch.randn(B, H, W, Cin, generator=g)
+            w = torch.randn(Cout, Cin, generator=g) * Cin ** -0.5
+            scale, shift = 1.0 + 0.1 * torch.randn(Cout, generator=g), 0.1 * torch.randn(Cout, generator=g)
+            res = torch.randn(B, H, W, Cout, generator=g) if residual else None
+            _, g64 = se_ref(t["partial"], H * W, t["w1"], t["b1"], t["w2"], t["b2"], torch.float64)
+            _, g32 = se_ref(t["partial"], H * W, t["w1"], t["b1"], t["w2"], t["b2"], torch.float32)
+            assert gates_unsaturated(g64)
+            y64 = proj_ref(x, g64, w, scale, shift, res, torch.float64)
+            y32 = proj_ref(x, g32, w, scale, shift, res, torch.float32)
+            dev = [v.to(device).contiguous() for v in (x, w.view(Cout, Cin, 1, 1), scale, shift, t["partial"], t["w1"], t["b1"],
+                                                        t["w2"].t(), t["b2"])]
+            rd = res.to(device) if residual else None
+            for rgemm in (1, 0):
+                what = "%d->%d %dx%d B%d chunks%d rgemm%d" % (Cin, Cout, H, W, B, chunks, rgemm)
+                y, gate = Guarded((B, H, W, Cout), device), Guarded((B, Cin), device)
+                with options(lib, conv_rgemm=rgemm):
+                    _lib.check(lib.orbit_op_pw_stream(d(dev[0]), d(dev[1]), d(dev[2]), d(dev[3]), d(rd), d(dev[4]), chunks, d(dev[5]),
+                                                      d(dev[6]), d(dev[7]), d(dev[8]), R, d(y.t), d(gate.t), B, H, W, Cin, Cout, _st()),
+                               "orbit_op_pw_stream")
+                    torch.cuda.synchronize()
+                gate_gate("pw_gate", what, gate.cpu("gate_out"), g64, g32)
+                elementwise_gate("pw_y", what, y.cpu("y"), y64, y32)
+
+
+# ---- d. the chain once, end to end ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,C,Cout,R,K,H,W,form,rows", [
+    ("c32_72x8", 32, 16, 8, 3, 72, 8, WINDOW, [8] * 9),      # 9 chunks: the many-chunk pooling branch from real partials
+    ("c240_17x13", 240, 40, 10, 5, 17, 13, LDS, [7, 7, 3])],  # LDS form, ragged last chunk
+    ids=["c32_72x8", "c240_17x13"])
+def test_chain(lib, device, name, C, Cout, R, K, H, W, form, rows):
+    B = 2
+    x, wd, scale, shift = dw_inputs("normal", B, C, K, H, W, seed=11 + C)
+    g = torch.Generator().manual_seed(13 + C)
+    se = se_inputs(B, C, R, 1, 1, seed=17 + C)
+    wp = torch.randn(Cout, C, generator=g) * C ** -0.5
+    pscale, pshift = 1.0 + 0.1 * torch.randn(Cout, generator=g), 0.1 * torch.randn(Cout, generator=g)
+
+    def chain(dtype):
+        a = dw_ref(x, wd, scale, shift, K, 1, dtype)  # NCHW
+        _, gate = se_ref(a.flatten(2).transpose(1, 2), H * W, se["w1"], se["b1"], se["w2"], se["b2"], dtype)  # sums over pixels
+        return a, gate, proj_ref(a.permute(0, 2, 3, 1), gate, wp, pscale, pshift, None, dtype)
+
+    a64, g64, y64 = chain(torch.float64)
+    a32, g32, y32 = chain(torch.float32)
+    assert gates_unsaturated(g64)
+    a, partial = run_dwconv_se(lib, device, x, wd, scale, shift, K, 1, (1, 1, 1), form, rows)
+    elementwise_gate("chain_dw", name, a.permute(0, 3, 1, 2), a64, a32)
+    check_partials("chain/" + name, a, partial, rows)
+    d = _lib.dptr
+    dev = [t.to(device).contiguous() for t in (partial, se["w1"], se["b1"], se["w2"], se["b2"], a, wp.view(Cout, C, 1, 1), pscale,
+                                               pshift)]
+    gate, y = Guarded((B, C), device), Guarded((B, H, W, Cout), device)
+    _lib.check(lib.orbit_op_se_gate2(d(dev[0]), len(rows), H * W, d(dev[1]), d(dev[2]), d(dev[3]), d(dev[4]), B, C, R, d(gate.t), None,
+                                     _st()), "orbit_op_se_gate2")
+    _lib.check(lib.orbit_op_conv2d(d(dev[5]), 0, d(dev[6]), d(y.t), d(dev[7]), d(dev[8]), None, d(gate.t), B, H, W, C, Cout, 1, 1, 1, 0, 0,
+                                   H, W, 0, 0, _st()), "orbit_op_conv2d")
+    torch.cuda.synchronize()
+    gate_gate("chain_gate", name, gate.cpu("gate"), g64, g32)
+    elementwise_gate("chain_y", name, y.cpu("y"), y64, y32)
