@@ -709,8 +709,8 @@ int orbit_op_dwconv2d_backward(const float* x, const float* w, const float* dy, 
  * of g * (y_raw - mean[c]) * invstd[c] (reference: autograd through timm InvertedResidual's conv_dw <- act1 <- bn1,
  * few_shot_recognisers.py:99-122). dw (optional, [C][1][K][K]): the layer's filter gradient from the same pass - its input is
  * act(y_raw * scale + shift), rebuilt at the output pixels anyway (stride-2 layers). Fails with ORBIT_ERR_ARG where no kernel
- * form carries the epilogue / the filter gradient (the caller then runs the separate passes). Single-operator entry for the
- * parity tests. */
+ * form carries the epilogue / the filter gradient (the caller then runs the separate passes): decided on the host by the rules of
+ * orbit_op_dwconv2d_backward_plan, before anything is launched or written. Single-operator entry for the parity tests. */
 int orbit_op_dwconv2d_dgrad_bn(const float* dy, const float* w, const float* y_raw, const float* mean, const float* invstd,
                                const float* scale, const float* shift, int act, float* g, float* sums, float* dw, int B, int H,
                                int W, int C, int K, int stride, int pad_top, int pad_left, int Ho, int Wo, orbit_stream_t stream);
@@ -734,6 +734,45 @@ int orbit_op_se_gate_backward(const float* dxg, const float* x, const float* poo
 int orbit_op_se_gate_backward_ex(const float* dxg, const float* x, const float* pooled, const float* w1, const float* b1,
                                  const float* w2, const float* b2, float* dx, float* dw1, float* db1, float* dw2,
                                  float* db2, int B, int HW, int C, int R, int flags, orbit_stream_t stream);
+/* Host only, launches nothing: what the depthwise backward launchers do for a layer under the current options - the rules the
+ * launchers themselves ask. mode: which call is meant (the entries above pass the flipped-tap scratch, so stride-1 data
+ * gradients run a forward kernel form over dy). A layer a mode's entry refuses reads epilogue = 0 (the _BN modes) or
+ * wgrad = 0 (_BN_WGRAD, _WGRAD_XF). Single-operator entry for the parity tests. */
+#define ORBIT_DWBWD_DGRAD 0          /* orbit_op_dwconv2d_backward, dx */
+#define ORBIT_DWBWD_DGRAD_BN 1       /* orbit_op_dwconv2d_dgrad_bn, dw = NULL */
+#define ORBIT_DWBWD_DGRAD_BN_WGRAD 2 /* orbit_op_dwconv2d_dgrad_bn with dw */
+#define ORBIT_DWBWD_WGRAD 3          /* orbit_op_dwconv2d_backward, dw (the global-load form) */
+#define ORBIT_DWBWD_WGRAD_XF 4       /* orbit_op_dwconv2d_wgrad_xf (the LDS form) */
+/* family: 0 .. 3 = a forward kernel form as orbit_op_dwconv2d_plan numbers them, or one of: */
+#define ORBIT_DWBWD_FAMILY_S2 4           /* the stride-2 kernel that owns 2x2 blocks of dx */
+#define ORBIT_DWBWD_FAMILY_GATHER 5       /* the per-pixel gather fallback */
+#define ORBIT_DWBWD_FAMILY_WGRAD_GLOBAL 6 /* filter gradient, taps loaded from global memory */
+#define ORBIT_DWBWD_FAMILY_WGRAD_LDS 7    /* filter gradient from an LDS-staged patch (with the input transform) */
+typedef struct orbit_dwconv_backward_plan {
+    int family;
+    int epilogue;   /* the BatchNorm-backward epilogue is carried */
+    int wgrad;      /* the filter gradient is carried / computed */
+    int blocks;     /* data gradient: row blocks of the launch (stride 2: blockIdx.x; forward forms: chunks * B) */
+    int bn_rows;    /* [rows][2][C] BatchNorm partial rows written, 0 without the epilogue */
+    int wgrad_rows; /* [rows][K*K][C] filter-gradient partial rows written, 0 when not carried */
+    int chunks;     /* forward forms: row chunks per frame; global-load filter gradient: chunks of B * Ho rows; LDS: per frame */
+    int rpc;        /* output rows per chunk */
+    int cs4, tpb, groups; /* LDS filter gradient: channel quads per block, tiles per block, tile groups (= partial rows) */
+} orbit_dwconv_backward_plan_t;
+int orbit_op_dwconv2d_backward_plan(int B, int H, int W, int C, int K, int stride, int pad_top, int pad_left, int Ho, int Wo,
+                                    int mode, orbit_dwconv_backward_plan_t* plan);
+/* orbit_op_se_gate_backward with the producer's BatchNorm backward riding on it, as the reverse pass of an MBConv block runs the
+ * two: x = act(y * scale[c] + shift[c]) [B][HW][C] is the activated output of a BatchNorm over the raw y (mean / invstd [C], the
+ * batch or running statistics; scale = gamma * invstd, shift = beta - mean * scale). Step 1, the squeeze-excite backward, writes
+ * g = d x * act'(.) (sums_only = 0; with sums_only != 0 pass g = NULL and nothing is written) and leaves the per-(frame, row chunk)
+ * sums of g and g * xhat, which come back summed in sums [2][C]. Step 2 finishes the BatchNorm backward from them: dy [B][HW][C],
+ * dgamma / dbeta [C] (nullable), train != 0 for batch statistics; with sums_only its apply pass rebuilds g from dxg, the gate and
+ * the pooled-branch gradient. gamma nullable (= 1). dw1 .. db2: the SE parameter gradients, all or none. */
+int orbit_op_se_gate_backward_bn(const float* dxg, const float* x, const float* y, const float* mean, const float* invstd,
+                                 const float* scale, const float* shift, int act, const float* pooled, const float* w1,
+                                 const float* b1, const float* w2, const float* b2, const float* gamma, int train, int sums_only,
+                                 float* g, float* sums, float* dy, float* dgamma, float* dbeta, float* dw1, float* db1, float* dw2,
+                                 float* db2, int B, int HW, int C, int R, orbit_stream_t stream);
 
 /* ---- input side: 8-bit frames -> normalised fp32 NCHW ([B][3][H][W], what the extractors consume) -------------------
  * frames: device pointer, [B][H][W][3] when layout_hwc != 0 (decoded images) or [B][3][H][W]; mean3 / std3: HOST arrays.

@@ -151,6 +151,8 @@ _SIGNATURES = {
     "orbit_op_dwconv2d_wgrad_xf": (c_int, [P, P, P, c_int, P, P] + [c_int] * 10 + [P]),
     "orbit_op_se_gate_backward": (c_int, [P] * 12 + [c_int] * 4 + [P]),
     "orbit_op_se_gate_backward_ex": (c_int, [P] * 12 + [c_int] * 5 + [P]),
+    "orbit_op_dwconv2d_backward_plan": (c_int, [c_int] * 11 + [P]),
+    "orbit_op_se_gate_backward_bn": (c_int, [P] * 7 + [c_int] + [P] * 6 + [c_int, c_int] + [P] * 9 + [c_int] * 4 + [P]),
     "orbit_frames_from_uint8": (c_int, [P, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), P, P]),
     "orbit_frames_resize_from_uint8": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float),
                                                POINTER(c_float), P, P]),
@@ -208,6 +210,12 @@ class OptimRow(ctypes.Structure):
     """orbit_optim_row_t of include/orbit_hip.h"""
     _fields_ = [("p", c_void_p), ("grad", c_void_p), ("state1", c_void_p), ("state2", c_void_p),
                 ("numel", ctypes.c_uint64), ("group", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+class DwconvBackwardPlan(ctypes.Structure):
+    """orbit_dwconv_backward_plan_t of include/orbit_hip.h"""
+    _fields_ = [(n, c_int) for n in ("family", "epilogue", "wgrad", "blocks", "bn_rows", "wgrad_rows", "chunks", "rpc", "cs4", "tpb",
+                                     "groups")]
 
 
 OPTIM_MAX_GROUPS = 8   # ORBIT_OPTIM_MAX_GROUPS

@@ -207,6 +207,12 @@ struct DwBnBwd : BnTaped {  // (y: raw output of the producing conv, laid out li
     float* wgrad_partial = nullptr;
     int* wgrad_rows = nullptr;
 };
+// what launch_dwconv_se does with a DwBnBwd for a layer (g: the forward-over-dy geometry launch_dwconv_dgrad passes): the form,
+// its row chunking and the partial rows it reports through DwBnBwd::nblk / wgrad_rows (0: the form does not carry that part)
+struct DwBwdForm {
+    int form = 0, chunks = 0, rpc = 0, bn_rows = 0, wgrad_rows = 0;
+};
+DwBwdForm dwconv_se_bwd_form(const LayerGeom& g, bool want_wgrad);
 // The depthwise kernels are instantiated for K in {3, 5} and stride in {1, 2}: f(integral_constant K, integral_constant stride)
 // turns the two runtime ints into template arguments, once for every launcher of the family (callers validate K and stride)
 template <class F>

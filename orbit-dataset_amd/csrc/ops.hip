@@ -822,6 +822,21 @@ static DwPlan dw_plan(int B, int C, int K, int stride, int Ho, int Wo, bool trai
     return p;
 }
 
+// The data-gradient use of the launch below (DwBnBwd): the LDS patch and the register window carry the BatchNorm-backward epilogue,
+// the register window also the filter gradient; both write one partial row per (row chunk, frame). The streaming forms carry
+// neither. What launch_dwconv_se reports through DwBnBwd::nblk / wgrad_rows, and what the backward plan query answers.
+static DwBwdForm dw_bwd_form(const DwPlan& p, int stride, bool want_wgrad) {
+    DwBwdForm f;
+    f.form = p.form, f.chunks = (int)p.grid.y, f.rpc = p.rpc;
+    const int rows = (int)(p.grid.y * p.grid.z);
+    if (stride == 1 && (p.form == DW_LDS || p.form == DW_WINDOW)) f.bn_rows = rows;
+    if (stride == 1 && p.form == DW_WINDOW && want_wgrad) f.wgrad_rows = rows;
+    return f;
+}
+DwBwdForm dwconv_se_bwd_form(const LayerGeom& g, bool want_wgrad) {
+    return dw_bwd_form(dw_plan(g.B, g.Cin, g.KH, g.stride, g.Ho, g.Wo, false), g.stride, want_wgrad);
+}
+
 static int launch_dwconv_se_impl(const float* x, const float* w_khwc, float* y, const float* scale, const float* shift,
                                  float* pool_partial, const LayerGeom& g, int act, hipStream_t s, int stats, const DwInXf& xf,
                                  const DwBnBwd* bnb);
@@ -866,6 +881,11 @@ static int launch_dwconv_se_impl(const float* x, const float* w_khwc, float* y, 
     const DwPlan p = dw_plan(B, C, K, stride, Ho, Wo, stats != 0);
     const dim3 grid = p.grid;
     const size_t lds = p.lds;
+    if (bnb) {
+        const DwBwdForm bf = dw_bwd_form(p, stride, bnb->wgrad_partial != nullptr);
+        *bnb->nblk = bf.bn_rows;
+        if (bnb->wgrad_rows) *bnb->wgrad_rows = bf.wgrad_rows;
+    }
     const int cb4 = p.cb4, rpc = p.rpc, cs4 = p.cs4, G = p.G, IWA = p.IWA;
     const DwInXf no_xf{nullptr, nullptr, 0};
     dw_dispatch_ks(K, stride, [&](auto kc, auto sc) {
@@ -876,7 +896,6 @@ static int launch_dwconv_se_impl(const float* x, const float* w_khwc, float* y, 
                 if constexpr (SS == 1)
                     dwconv_lds_kernel<KK, SS, 8, true, false, true><<<grid, 256, lds, s>>>(
                         x, w_khwc, y, nullptr, nullptr, bnb->partial, H, W, C, pad_t, pad_l, Ho, Wo, act, cs4, rpc, G, IWA, no_xf, *bnb);
-                *bnb->nblk = (int)(grid.y * grid.z);
             } else if (use_xf)
                 dwconv_lds_kernel<KK, SS, 8, true, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t,
                                                                                pad_l, Ho, Wo, act, cs4, rpc, G, IWA, xf);
@@ -897,12 +916,10 @@ static int launch_dwconv_se_impl(const float* x, const float* w_khwc, float* y, 
                 if constexpr (SS == 1)
                     dwconv_win_kernel<KK, SS, NO, true, false, true, true><<<grid, 256, lds_wg, s>>>(
                         x, w_khwc, y, nullptr, nullptr, bnb->partial, H, W, C, pad_t, pad_l, Ho, Wo, act, cb4, rpc, no_xf, *bnb);
-                *bnb->nblk = *bnb->wgrad_rows = (int)(grid.y * grid.z);
             } else if (bnb) {
                 if constexpr (SS == 1)
                     dwconv_win_kernel<KK, SS, NO, true, false, true><<<grid, 256, lds, s>>>(
                         x, w_khwc, y, nullptr, nullptr, bnb->partial, H, W, C, pad_t, pad_l, Ho, Wo, act, cb4, rpc, no_xf, *bnb);
-                *bnb->nblk = (int)(grid.y * grid.z);
             } else if (use_xf)
                 dwconv_win_kernel<KK, SS, NO, true, true><<<grid, 256, lds, s>>>(x, w_khwc, y, scale, shift, pool_partial, H, W, C, pad_t,
                                                                                  pad_l, Ho, Wo, act, cb4, rpc, xf);

@@ -948,6 +948,14 @@ static int dgrad_s2_fused_blocks(int B, int H, int W, int C, int K) {
     const size_t per_block = (size_t)R * (size_t)cdiv(K * K + 2, R);  // 2x2 blocks per row block: >= ~2 x the epilogue's quads / 9
     return (int)std::max<size_t>(1, std::min<size_t>(2048, blocks2 / std::max<size_t>(per_block * 2, 1)));
 }
+// row blocks of the stride-2 launch: the cap of the BatchNorm sums with the epilogue, the fused rule with the filter gradient
+static int dgrad_s2_grid(int B, int H, int W, int C, int K, bool bnb, bool fuse_wg) {
+    int gx = dgrad_s2_blocks(B, H, W, C);
+    if (bnb) gx = std::min(gx, 2048);
+    if (fuse_wg) gx = std::min(gx, dgrad_s2_fused_blocks(B, H, W, C, K));
+    return gx;
+}
+static bool dgrad_s2_fits(int B, int H, int W) { return (long long)B * ((H + 1) / 2) * ((W + 1) / 2) < (1ll << 31); }
 size_t dwconv_bwd_fused_partial_offset(int C, int K) { return (size_t)(C * K * K + 3) / 4 * 4; }
 size_t dwconv_bwd_fused_scratch_floats(const LayerGeom& g) {
     const int B = g.B, H = g.H, W = g.W, C = g.Cin, K = g.KH, stride = g.stride;
@@ -983,14 +991,13 @@ int launch_dwconv_dgrad(const float* dy, const float* w_khwc, float* dx, const L
     }
 
     ORBIT_REQUIRE(C % 4 == 0 && (K == 3 || K == 5), "dwconv_dgrad: C %% 4 != 0 or K not in {3,5}");
-    if (stride == 2 && (long long)B * ((H + 1) / 2) * ((W + 1) / 2) < (1ll << 31)) {
+    if (stride == 2 && dgrad_s2_fits(B, H, W)) {
         // 2x2-block form: one dy patch + LDS taps per four outputs (see dwconv_dgrad_s2_kernel)
         int G, R, yg;
         dw_layout(C, G, R, yg);
-        int gx = dgrad_s2_blocks(B, H, W, C);
         const bool fuse_wg = bnb && bnb->wgrad_partial;
-        if (bnb) gx = std::min(gx, 2048);
-        if (fuse_wg) gx = std::min(gx, dgrad_s2_fused_blocks(B, H, W, C, K)), *bnb->wgrad_rows = gx;
+        const int gx = dgrad_s2_grid(B, H, W, C, K, bnb != nullptr, fuse_wg);
+        if (fuse_wg) *bnb->wgrad_rows = gx;
         if (bnb) *bnb->nblk = gx;
         const size_t lds = (size_t)(K * K * G + (fuse_wg ? 8 * 256 : bnb ? 512 : 0)) * sizeof(f32x4);
         dw_dispatch_ks(K, 2, [&](auto kc, auto) {
@@ -1032,6 +1039,18 @@ size_t dwconv_wgrad_scratch_floats(const LayerGeom& g) {
     return (size_t)std::max(dwconv_wgrad_chunks(g.B, g.Ho, g.Wo, g.Cin), 512) * g.KH * g.KH * g.Cin;
 }
 
+// global-load form: chunks of whole output rows; never more blocks than the scratch was sized for (dwconv_wgrad_chunks), and at
+// least one row per row lane. Returns the chunks, *rows = output rows (of B * Ho) per chunk
+static int dw_wgrad_global_chunks(int B, int Ho, int Wo, int C, int* rows) {
+    int G, R, yg;
+    dw_layout(C, G, R, yg);
+    const int total_rows = B * Ho;
+    int chunks = dwconv_wgrad_chunks(B, Ho, Wo, C);
+    if (chunks > cdiv(total_rows, R)) chunks = cdiv(total_rows, R);
+    *rows = cdiv(total_rows, chunks);
+    return cdiv(total_rows, *rows);
+}
+
 int launch_dwconv_wgrad(const float* x, const float* dy, float* dw, float* scratch, const LayerGeom& g, hipStream_t s,
                         const DwInXf& in) {
     const int B = g.B, H = g.H, W = g.W, C = g.Cin, K = g.KH, stride = g.stride, pad_t = g.pad_t, pad_l = g.pad_l, Ho = g.Ho, Wo = g.Wo;
@@ -1062,13 +1081,8 @@ int launch_dwconv_wgrad(const float* x, const float* dy, float* dw, float* scrat
     int G, R, yg;
     dw_layout(C, G, R, yg);
     ORBIT_REQUIRE((long long)B * H * W * (C / 4) < (1ll << 31), "dwconv_wgrad: tensor too large for 32-bit pixel indices");
-    // chunks of whole output rows; never more blocks than the scratch was sized for (dwconv_wgrad_chunks), and at least one
-    // row per row lane
-    const int total_rows = B * Ho;
-    int chunks = dwconv_wgrad_chunks(B, Ho, Wo, C);
-    if (chunks > cdiv(total_rows, R)) chunks = cdiv(total_rows, R);
-    const int rows = cdiv(total_rows, chunks);
-    chunks = cdiv(total_rows, rows);
+    int rows = 0;
+    const int chunks = dw_wgrad_global_chunks(B, Ho, Wo, C, &rows);
     dim3 grid(chunks, yg);
     dw_dispatch_ks(K, stride, [&](auto kc, auto sc) {
         constexpr int KK = decltype(kc)::value, SS = decltype(sc)::value, NB = KK == 5 && SS == 2 ? 2 : 4;
@@ -1078,6 +1092,42 @@ int launch_dwconv_wgrad(const float* x, const float* dy, float* dw, float* scrat
     dwconv_wgrad_reduce_kernel<<<cdiv(K * K * C, 16), 256, 0, s>>>(scratch, chunks, K * K, C, dw);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
+}
+
+// What launch_dwconv_dgrad (with the flipped-tap scratch, as every caller passes it) / launch_dwconv_wgrad do for a layer under the
+// current options: the rules of the launchers themselves, asked in their order. Host only.
+static void dw_backward_plan(const LayerGeom& g, int mode, orbit_dwconv_backward_plan_t* p) {
+    const int B = g.B, H = g.H, W = g.W, C = g.Cin, K = g.KH, Ho = g.Ho, Wo = g.Wo;
+    *p = orbit_dwconv_backward_plan_t{};
+    if (mode == ORBIT_DWBWD_WGRAD) {
+        p->family = ORBIT_DWBWD_FAMILY_WGRAD_GLOBAL, p->wgrad = 1;
+        p->chunks = p->wgrad_rows = dw_wgrad_global_chunks(B, Ho, Wo, C, &p->rpc);
+        return;
+    }
+    if (mode == ORBIT_DWBWD_WGRAD_XF) {
+        const DwWgLdsGeom lg = dw_wgrad_lds_geom(B, H, W, C, K, g.stride, Ho, Wo);
+        p->family = ORBIT_DWBWD_FAMILY_WGRAD_LDS;
+        if (!lg.ok) return;  // (launch_dwconv_wgrad refuses the transform without the LDS form)
+        p->wgrad = 1, p->wgrad_rows = lg.groups;
+        p->cs4 = lg.cs4, p->rpc = lg.rpc, p->chunks = lg.chunks, p->tpb = lg.tpb, p->groups = lg.groups;
+        return;
+    }
+    const bool bnb = mode != ORBIT_DWBWD_DGRAD;
+    const bool want_wg = mode == ORBIT_DWBWD_DGRAD_BN_WGRAD && dwconv_bwd_fused_scratch_floats(g) != 0;
+    if (g.stride == 1) {
+        const DwBwdForm f = dwconv_se_bwd_form(LayerGeom{B, Ho, Wo, C, C, K, K, 1, K - 1 - g.pad_t, K - 1 - g.pad_l, H, W}, want_wg);
+        p->family = f.form, p->chunks = f.chunks, p->rpc = f.rpc, p->blocks = B * f.chunks;
+        if (bnb) p->epilogue = f.bn_rows > 0, p->bn_rows = f.bn_rows, p->wgrad = f.wgrad_rows > 0, p->wgrad_rows = f.wgrad_rows;
+        return;
+    }
+    if (g.stride == 2 && dgrad_s2_fits(B, H, W)) {
+        p->family = ORBIT_DWBWD_FAMILY_S2;
+        p->blocks = dgrad_s2_grid(B, H, W, C, K, bnb, want_wg);
+        if (bnb) p->epilogue = 1, p->bn_rows = p->blocks;
+        if (want_wg) p->wgrad = 1, p->wgrad_rows = p->blocks;
+        return;
+    }
+    p->family = ORBIT_DWBWD_FAMILY_GATHER, p->blocks = grid_for((size_t)B * H * W * (C / 4));
 }
 
 }  // namespace orbit
@@ -1111,8 +1161,14 @@ int orbit_op_dwconv2d_dgrad_bn(const float* dy, const float* w, const float* y_r
     float* tmp = nullptr;
     const size_t npack = (size_t)(C * K * K + 3) / 4 * 4;
     const LayerGeom geom{B, H, W, C, C, K, K, stride, pad_top, pad_left, Ho, Wo};
+    ORBIT_REQUIRE(B > 0 && C > 0 && C % 4 == 0 && (K == 3 || K == 5) && (stride == 1 || stride == 2) && H > 0 && W > 0 && Ho > 0 && Wo > 0,
+                  "op_dwconv2d_dgrad_bn: bad geometry");
+    // a layer whose kernel form does not carry what is asked for is refused here, before anything is launched or written
+    orbit_dwconv_backward_plan_t plan;
+    dw_backward_plan(geom, dw ? ORBIT_DWBWD_DGRAD_BN_WGRAD : ORBIT_DWBWD_DGRAD_BN, &plan);
+    if (!plan.epilogue) return set_err(ORBIT_ERR_ARG, "op_dwconv2d_dgrad_bn: no kernel form with the epilogue for this layer");
+    if (dw && !plan.wgrad) return set_err(ORBIT_ERR_ARG, "op_dwconv2d_dgrad_bn: no kernel form carries the filter gradient for this layer");
     const size_t nfused = dw ? dwconv_bwd_fused_scratch_floats(geom) : 0;
-    if (dw && nfused == 0) return set_err(ORBIT_ERR_ARG, "op_dwconv2d_dgrad_bn: no kernel form carries the filter gradient for this layer");
     const size_t nscr = std::max(dwconv_wgrad_scratch_floats(geom), nfused);
     const size_t npart = bn_partial_floats((size_t)dwconv_dgrad_bn_blocks(geom), C);
     ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (npack + nscr + npart) * sizeof(float), s));
@@ -1180,6 +1236,61 @@ int orbit_op_se_gate_backward_ex(const float* dxg, const float* x, const float* 
     } else if (rc == ORBIT_OK) {
         rc = launch_se_gate_backward(dxg, x, pooled, gate, sw, dx, dw1 ? &dparams : nullptr, tmp, B, HW, C, R, s);
     }
+    (void)hipFreeAsync(tmp, s);
+    return rc;
+}
+
+/* Host only: what the depthwise backward launchers do for this layer in `mode` under the current options. */
+int orbit_op_dwconv2d_backward_plan(int B, int H, int W, int C, int K, int stride, int pad_top, int pad_left, int Ho, int Wo,
+                                    int mode, orbit_dwconv_backward_plan_t* plan) {
+    ORBIT_REQUIRE(plan, "op_dwconv2d_backward_plan: null pointer");
+    ORBIT_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 4 == 0 && (K == 3 || K == 5) && (stride == 1 || stride == 2) &&
+                      pad_top >= 0 && pad_top < K && pad_left >= 0 && pad_left < K,
+                  "op_dwconv2d_backward_plan: bad geometry (C = %d, K = %d, stride = %d)", C, K, stride);
+    ORBIT_REQUIRE(mode >= ORBIT_DWBWD_DGRAD && mode <= ORBIT_DWBWD_WGRAD_XF, "op_dwconv2d_backward_plan: unknown mode %d", mode);
+    dw_backward_plan(LayerGeom{B, H, W, C, C, K, K, stride, pad_top, pad_left, Ho, Wo}, mode, plan);
+    return ORBIT_OK;
+}
+
+/* The squeeze-excite backward with the first pass of the producer's BatchNorm backward riding on it, then that BatchNorm's
+ * finalize + apply: the two steps the reverse pass of a network runs for an MBConv block (gated_input_gradient / bn_backward of
+ * csrc/extractor_train.hip). sums_only: g is not written and the apply pass rebuilds it (launch_bn_backward_reduced_gated). */
+int orbit_op_se_gate_backward_bn(const float* dxg, const float* x, const float* y, const float* mean, const float* invstd,
+                                 const float* scale, const float* shift, int act, const float* pooled, const float* w1,
+                                 const float* b1, const float* w2, const float* b2, const float* gamma, int train, int sums_only,
+                                 float* g, float* sums, float* dy, float* dgamma, float* dbeta, float* dw1, float* db1, float* dw2,
+                                 float* db2, int B, int HW, int C, int R, orbit_stream_t stream) {
+    ORBIT_REQUIRE(dxg && x && y && mean && invstd && scale && shift && pooled && w1 && b1 && w2 && b2 && sums && dy,
+                  "op_se_gate_backward_bn: null pointer");
+    ORBIT_REQUIRE((g == nullptr) == (sums_only != 0), "op_se_gate_backward_bn: g is written exactly when sums_only is 0");
+    ORBIT_REQUIRE(act == ORBIT_ACT_NONE || act == ORBIT_ACT_RELU || act == ORBIT_ACT_SILU, "op_se_gate_backward_bn: bad activation %d", act);
+    ORBIT_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && R > 0 && R <= 256, "op_se_gate_backward_bn: bad sizes (B=%d HW=%d C=%d R=%d)", B,
+                  HW, C, R);
+    ORBIT_REQUIRE((size_t)B * HW < ((size_t)1 << 31), "op_se_gate_backward_bn: B * HW does not fit an int");
+    ORBIT_REQUIRE((dw1 == nullptr) == (db1 == nullptr) && (dw1 == nullptr) == (dw2 == nullptr) && (dw1 == nullptr) == (db2 == nullptr),
+                  "op_se_gate_backward_bn: parameter gradients come all or none");
+    hipStream_t s = (hipStream_t)stream;
+    const int nblk = B * se_pool_chunks(B, HW, C), M = B * HW;
+    const size_t nscr = align_up(se_bwd_scratch_floats(B, C, R), 4), ngate = (size_t)B * C, nw2t = align_up((size_t)C * R, 4);
+    const size_t npart = bn_partial_floats((size_t)nblk, C);
+    float* tmp = nullptr;
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (nscr + ngate + nw2t + npart + 3 * (size_t)C) * sizeof(float), s));
+    float* gate = tmp + nscr;
+    float* w2t = gate + ngate;
+    float* partial = w2t + nw2t;
+    float* coef = partial + npart;
+    int rc = launch_se_gate(pooled, w1, b1, w2, b2, gate, B, C, R, s);
+    if (rc == ORBIT_OK) rc = launch_transpose(w2, w2t, C, R, s);
+    const SeWeights sw{w1, b1, w2, b2, w2t};
+    const SeGrads dparams{dw1, db1, dw2, db2};
+    const SeBnFuse fuse{y, BnFoldC{mean, invstd, scale, shift}, act, partial};
+    if (rc == ORBIT_OK) rc = launch_se_gate_backward(dxg, x, pooled, gate, sw, g, dw1 ? &dparams : nullptr, tmp, B, HW, C, R, s, &fuse);
+    if (rc == ORBIT_OK) rc = launch_sum_partials(partial, nblk, C, sums, s);
+    const BnGrads bp{gamma, dgamma, dbeta};
+    if (rc == ORBIT_OK && sums_only)
+        rc = launch_bn_backward_reduced_gated(dxg, gate, se_bwd_dpooled(tmp, B, C, R), HW, fuse, bp, train, M, C, dy, nblk, coef, s);
+    else if (rc == ORBIT_OK)
+        rc = launch_bn_backward_reduced(g, y, fuse.bn, bp, train, M, C, dy, partial, nblk, coef, s);
     (void)hipFreeAsync(tmp, s);
     return rc;
 }

@@ -35,10 +35,10 @@ STREAM, PIPE, WINDOW, LDS = 0, 1, 2, 3  # DwForm of csrc/common.h, as orbit_op_d
 _worst = {}
 
 
-def _report(family, what, err, bound):
+def _report(family, what, err, bound, tag="se_path"):
     ratio = err / bound
     _worst[family] = max(_worst.get(family, 0.0), ratio)
-    print("\n[se_path] %s: %s: err %.3g, bound %.3g, ratio %.3g (family max %.3g)" % (family, what, err, bound, ratio, _worst[family]))
+    print("\n[%s] %s: %s: err %.3g, bound %.3g, ratio %.3g (family max %.3g)" % (tag, family, what, err, bound, ratio, _worst[family]))
     return ratio
 
 
@@ -143,11 +143,11 @@ def proj_ref(x, gate, w, scale, shift, res, dtype):
     return y + res.to(dtype) if res is not None else y
 
 
-def elementwise_gate(family, what, got, want64, want32):
+def elementwise_gate(family, what, got, want64, want32, report=_report):
     e32 = (want32.double() - want64).abs().max().item()
     tol = max(2e-5, 4 * e32) * max(1.0, want64.abs().max().item())
     err = (got.double() - want64).abs().max().item()
-    _report(family, what, err, tol)
+    report(family, what, err, tol)
     assert err <= tol, (what, err, tol, e32)
 
 
