@@ -878,6 +878,61 @@ size_t orbit_jpeg_workspace_bytes(int B, int H, int W);
 int orbit_frames_from_jpeg(const uint8_t* arena, size_t arena_bytes, const orbit_jpeg_desc_t* descs, int B, int H, int W,
                            uint8_t* out_u8_hwc, int32_t* status, void* workspace, size_t workspace_bytes, orbit_stream_t stream);
 
+/* ---- JPEG encode on the device (csrc/jpeg_enc.hip, csrc/jpeg_enc_core.h) --------------------------------------------------
+ * 8-bit RGB frames [B][H][W][3] -> the files Pillow's Image.save(quality = q[, restart_marker_rows = r]) writes for them, byte
+ * for byte: JFIF 1.01 header, an optional COM segment, 3-component YCbCr baseline SOF0 at 4:2:0, one interleaved scan, the
+ * Annex-K Huffman tables; libjpeg's integer colour conversion, 2 x 2 chroma averaging, "islow" forward DCT and quantiser. With
+ * orbit_frames_resize_u8 and orbit_frames_from_jpeg this is the reference's offline scripts/resize_videos.py pass on the device
+ * (tools/resize_videos.py).
+ *
+ * The parameters of one encoding: quantisation tables in natural (row-major) order (0 luma, 1 chroma) with the reciprocals
+ * ceil(2^32 / (8 qt)) the quantiser multiplies by, and the code tables of the four Huffman tables, indexed by DC category and
+ * by AC run/size symbol: code << 5 | length, 0 where a symbol has no code. */
+typedef struct orbit_jpeg_enc {
+    int32_t quality, restart_rows; /* restart_rows: MCU rows per restart interval, 0 = no restart markers */
+    uint16_t qt[2][64];
+    uint32_t qrecip[2][64];
+    uint32_t dc[2][16];
+    uint32_t ac[2][256];
+} orbit_jpeg_enc_t;
+/* Host only: fill *p (p_bytes = sizeof(orbit_jpeg_enc_t), checked) for libjpeg's jpeg_set_quality(quality, force_baseline).
+ * ORBIT_ERR_ARG for a quality outside 1 .. 100 or negative restart_rows. */
+int orbit_jpeg_encode_params(int quality, int restart_rows, orbit_jpeg_enc_t* p, size_t p_bytes);
+/* Host only: the header of an H x W file - SOI, APP0, COM (comment_bytes > 0 only), DQT x 2, SOF0, DHT x 4, DRI (restart_rows
+ * > 0 only; rows x MCUs per row must fit 16 bits), SOS - into out [cap]. Returns its length, or ORBIT_ERR_ARG (a comment of
+ * more than 65533 bytes, a short `out`, bad sizes). */
+int orbit_jpeg_encode_header(const orbit_jpeg_enc_t* p, int H, int W, const uint8_t* comment, size_t comment_bytes, uint8_t* out,
+                             size_t cap);
+/* A file size no H x W frame can exceed, whatever its pixels (0 for bad sizes): a block codes to at most 22 + 63 * 26 = 1660
+ * bits and is given 1664, which also pays for the fill bits of every restart interval; byte stuffing at most doubles the
+ * scan; 3 bytes per restart interval; the header with a comment of comment_bytes; EOI. */
+size_t orbit_jpeg_encode_bound(int H, int W, int restart_rows, size_t comment_bytes);
+/* Workspace of one launch of B frames: planes, coefficients, bit sums, the unstuffed bit buffer (about 2.6 KB per 16 x 16
+ * pixels). orbit_frames_to_jpeg works in chunks of frames when handed less, down to the workspace of one frame. 0 for bad sizes. */
+size_t orbit_jpeg_encode_workspace_bytes(int B, int H, int W);
+/* frames_u8_hwc [B][H][W][3], out, out_bytes [B] and workspace (16-byte aligned) are device pointers; params is a HOST
+ * pointer, read before the call returns. Frame b's file is written to out + b * out_stride and its length to out_bytes[b].
+ * Comments: frame b carries the COM segment comments[comment_offsets[b] .. comment_offsets[b + 1]) when that range is not empty;
+ * `comments` is a DEVICE buffer, comment_offsets a HOST array of B + 1 nondecreasing offsets (both NULL: no comments).
+ * out_stride must be at least orbit_jpeg_encode_bound(H, W, restart_rows, longest comment): with that no frame can overflow
+ * its slice, so there is no device-side overflow path. Sides up to ORBIT_RESIZE_MAX_SIZE, and 6 * ceil(H / 16) * ceil(W / 16)
+ * * 1664 bits must fit 32 bits (about 10 000 x 10 000 pixels). Seven kernels per chunk of at most 512 frames: colour
+ * conversion + chroma downsampling, forward DCT + quantisation, bits per block, their prefix sum per frame, bit packing,
+ * FF count + prefix sum, byte stuffing + file assembly. No read leaves the frames, no write leaves a frame's own slice of the
+ * workspace and of `out`. */
+int orbit_frames_to_jpeg(const uint8_t* frames_u8_hwc, int B, int H, int W, const orbit_jpeg_enc_t* params,
+                         const uint8_t* comments, const uint32_t* comment_offsets, uint8_t* out, size_t out_stride,
+                         uint32_t* out_bytes, void* workspace, size_t workspace_bytes, orbit_stream_t stream);
+/* The B files of such a call one behind the other, so that the host fetches the compressed bytes and not B slices: packed
+ * (device, packed_cap >= the sum of the lengths; B * out_stride always suffices) receives them, offsets (device, [B + 1]) the
+ * first byte of each and, last, the total. A file that would run past packed_cap is not copied (its offset is still written). */
+int orbit_jpeg_compact(const uint8_t* out, size_t out_stride, const uint32_t* out_bytes, int B, uint8_t* packed,
+                       size_t packed_cap, uint32_t* offsets, orbit_stream_t stream);
+/* orbit_frames_resize_from_uint8's resize with an 8-bit store: out_u8_hwc [B][H_out][W_out][3] equals
+ * np.asarray(Image.resize((W_out, H_out), filter)) of every frame. Same tables, same limits. */
+int orbit_frames_resize_u8(const uint8_t* frames, int layout_hwc, int B, int H_in, int W_in, int H_out, int W_out,
+                           int filter /* ORBIT_RESIZE_* */, uint8_t* out_u8_hwc, orbit_stream_t stream);
+
 /* ---- measurement: per-launch HIP-event timing of the dominant kernel (conv_igemm, all variants) ---- */
 int orbit_prof_enable(int on);   /* on: reset and start recording an event pair per launch on its stream */
 /* waits for the recorded launches, returns summed duration, summed ALGORITHMIC flops and launch count */

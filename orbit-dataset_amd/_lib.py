@@ -160,6 +160,13 @@ _SIGNATURES = {
     "orbit_jpeg_parse": (c_int, [P, c_size_t, P, c_size_t]),
     "orbit_jpeg_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "orbit_frames_from_jpeg": (c_int, [P, c_size_t, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "orbit_jpeg_encode_params": (c_int, [c_int, c_int, P, c_size_t]),
+    "orbit_jpeg_encode_header": (c_int, [P, c_int, c_int, P, c_size_t, P, c_size_t]),
+    "orbit_jpeg_encode_bound": (c_size_t, [c_int, c_int, c_int, c_size_t]),
+    "orbit_jpeg_encode_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "orbit_frames_to_jpeg": (c_int, [P, c_int, c_int, c_int, P, P, P, P, c_size_t, P, P, c_size_t, P]),
+    "orbit_jpeg_compact": (c_int, [P, c_size_t, P, c_int, P, c_size_t, P, P]),
+    "orbit_frames_resize_u8": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "orbit_prof_enable": (c_int, [c_int]),
     "orbit_prof_collect": (c_int, [POINTER(c_double), POINTER(c_double), POINTER(ctypes.c_long)]),
     "orbit_prof_num_variants": (c_int, []),
@@ -204,6 +211,12 @@ class JpegDesc(ctypes.Structure):
 
 
 JPEG_STAGE_BYTES = 1024  # ORBIT_JPEG_STAGE_BYTES
+
+
+class JpegEnc(ctypes.Structure):
+    """orbit_jpeg_enc_t of include/orbit_hip.h (orbit_jpeg_encode_params refuses a block of another size)"""
+    _fields_ = [("quality", ctypes.c_int32), ("restart_rows", ctypes.c_int32), ("qt", (ctypes.c_uint16 * 64) * 2),
+                ("qrecip", (ctypes.c_uint32 * 64) * 2), ("dc", (ctypes.c_uint32 * 16) * 2), ("ac", (ctypes.c_uint32 * 256) * 2)]
 
 
 class OptimRow(ctypes.Structure):

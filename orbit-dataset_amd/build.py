@@ -18,7 +18,7 @@ LIB = os.path.join(LIBDIR, "liborbit_hip.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 
 SOURCES = ["runtime.hip", "head.hip", "heads_extra.hip", "loss.hip", "conv_igemm.hip", "pw_rgemm.hip", "pw_stream.hip", "conv_bf3.hip", "ops.hip", "film.hip", "ingest.hip", "mbconv_rows.hip", "stem.hip", "extractor.hip", "train_ops.hip", "train_mbconv.hip", "conv_wgrad.hip", "extractor_train.hip",
-           "comm.hip", "vit.hip", "param_pool.hip", "eval.hip", "jpeg.hip", "optim.hip"]
+           "comm.hip", "vit.hip", "param_pool.hip", "eval.hip", "jpeg.hip", "jpeg_enc.hip", "optim.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-I", INCLUDE, "-I", "/opt/rocm/include"]

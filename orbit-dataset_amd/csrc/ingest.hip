@@ -76,11 +76,14 @@ __device__ __forceinline__ uint8_t resize_clip8(int acc) {  // Pillow's clip8: a
 //   stage 2  resamples rs_rows vertically, normalises and stores the three planes, one contiguous float segment per row.
 // The table lookups stay inside the frame by construction of the tables (xmin >= 0, xmin + n <= in, both nondecreasing): the
 // columns of stage 1 inside [col0, col0 + wc), the rows of stage 2 inside [row0, row0 + span).
+// U8OUT: stage 2 stores the resized pixels themselves, interleaved ([B][H_out][W_out][3], out_u8), instead of normalising them.
+template <bool U8OUT>
 __global__ __launch_bounds__(RS_THREADS) void frames_resize_u8_kernel(const uint8_t* __restrict__ in, size_t in_bytes, int hwc,
                                                                       int H_in, int W_in, int H_out, int W_out, int th_max,
                                                                       int tiles_x, int tiles_y, int rc, int pitch, int stage_off,
                                                                       ResizeAxis ax, ResizeAxis ay, float m0, float m1, float m2,
-                                                                      float s0, float s1, float s2, float* __restrict__ out) {
+                                                                      float s0, float s1, float s2, float* __restrict__ out,
+                                                                      uint8_t* __restrict__ out_u8) {
     extern __shared__ __align__(16) uint8_t rs_lds[];
     uint8_t* rs_rows = rs_lds;             // [3][span][RS_TW]
     uint8_t* rs_in = rs_lds + stage_off;   // [rc][hwc ? 1 : 3][pitch]
@@ -163,6 +166,11 @@ __global__ __launch_bounds__(RS_THREADS) void frames_resize_u8_kernel(const uint
             a0 += __mul24((int)rs_rows[p], w);
             a1 += __mul24((int)rs_rows[p + span * RS_TW], w);
             a2 += __mul24((int)rs_rows[p + 2 * span * RS_TW], w);
+        }
+        if (U8OUT) {
+            uint8_t* o8 = out_u8 + (b * plane + (size_t)yo * W_out + x0 + x) * 3;
+            o8[0] = resize_clip8(a0), o8[1] = resize_clip8(a1), o8[2] = resize_clip8(a2);
+            continue;
         }
         float* o = out + b * 3 * plane + (size_t)yo * W_out + x0 + x;
         o[0] = ((float)resize_clip8(a0) / 255.0f - m0) / s0;
@@ -317,22 +325,23 @@ int orbit_resize_coeffs(int in_size, int out_size, int filter, int* ksize, int32
     return ORBIT_OK;
 }
 
-int orbit_frames_resize_from_uint8(const uint8_t* frames, int layout_hwc, int B, int H_in, int W_in, int H_out, int W_out,
-                                   int filter, const float* mean3, const float* std3, float* out_nchw, orbit_stream_t stream) {
-    ORBIT_REQUIRE(frames && mean3 && std3 && out_nchw, "frames_resize_from_uint8: null pointer");
-    ORBIT_REQUIRE(B > 0 && H_in > 0 && W_in > 0 && H_out > 0 && W_out > 0, "frames_resize_from_uint8: bad sizes");
-    ORBIT_REQUIRE(resize_filter_known(filter), "frames_resize_from_uint8: unknown filter %d", filter);
-    ORBIT_REQUIRE(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "frames_resize_from_uint8: zero std");
+// The body of both resize entry points (`who` names the one in the messages): out_u8 set -> the 8-bit store, else normalise
+// with mean3 / std3 into out_nchw.
+static int frames_resize(const char* who, const uint8_t* frames, int layout_hwc, int B, int H_in, int W_in, int H_out, int W_out,
+                         int filter, const float* mean3, const float* std3, float* out_nchw, uint8_t* out_u8, orbit_stream_t stream) {
+    ORBIT_REQUIRE(B > 0 && H_in > 0 && W_in > 0 && H_out > 0 && W_out > 0, "%s: bad sizes", who);
+    ORBIT_REQUIRE(resize_filter_known(filter), "%s: unknown filter %d", who, filter);
+    ORBIT_REQUIRE(out_u8 || (std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f), "%s: zero std", who);
     ORBIT_REQUIRE(H_in <= ORBIT_RESIZE_MAX_SIZE && W_in <= ORBIT_RESIZE_MAX_SIZE && H_out <= ORBIT_RESIZE_MAX_SIZE &&
                       W_out <= ORBIT_RESIZE_MAX_SIZE,
-                  "frames_resize_from_uint8: %dx%d -> %dx%d exceeds the limit of %d pixels per side", H_in, W_in, H_out, W_out,
+                  "%s: %dx%d -> %dx%d exceeds the limit of %d pixels per side", who, H_in, W_in, H_out, W_out,
                   ORBIT_RESIZE_MAX_SIZE);
     // A tile keeps 3 * RS_TW bytes per input row of its vertical windows in LDS. Where the window of ONE output row cannot fit,
     // no tile can: refused before any table is built or uploaded.
     const int ksize_y = H_in == H_out ? 1 : resize_ksize(H_in, H_out, filter);
     ORBIT_REQUIRE(3 * RS_TW * (size_t)std::min(ksize_y, H_in) < RS_LDS_BYTES,
-                  "frames_resize_from_uint8: %d -> %d rows (%s) needs a window of %d rows per output row, more than a tile's LDS "
-                  "holds (%d)", H_in, H_out, resize_filter_name(filter), std::min(ksize_y, H_in), RS_LDS_BYTES / (3 * RS_TW));
+                  "%s: %d -> %d rows (%s) needs a window of %d rows per output row, more than a tile's LDS "
+                  "holds (%d)", who, H_in, H_out, resize_filter_name(filter), std::min(ksize_y, H_in), RS_LDS_BYTES / (3 * RS_TW));
     ResizeAxis ax, ay;
     const int *xmin_x, *n_x, *xmin_y, *n_y;
     int rc = resize_axis(W_in, W_out, filter, &ax, &xmin_x, &n_x);
@@ -360,8 +369,8 @@ int orbit_frames_resize_from_uint8(const uint8_t* frames, int layout_hwc, int B,
         if (stage_rows >= std::min(span, RS_ROWS) || th == 1) break;
     }
     ORBIT_REQUIRE(stage_rows >= 1,
-                  "frames_resize_from_uint8: %dx%d -> %dx%d (%s): the window of one output row (%d rows of %d bytes) and one input "
-                  "row of a tile (%d bytes) exceed a tile's %d bytes of LDS", H_in, W_in, H_out, W_out, resize_filter_name(filter),
+                  "%s: %dx%d -> %dx%d (%s): the window of one output row (%d rows of %d bytes) and one input "
+                  "row of a tile (%d bytes) exceed a tile's %d bytes of LDS", who, H_in, W_in, H_out, W_out, resize_filter_name(filter),
                   span, 3 * RS_TW, row_bytes, RS_LDS_BYTES);
     const int stage_off = 3 * RS_TW * span;
     const size_t lds = (size_t)stage_off + (size_t)stage_rows * row_bytes;
@@ -371,17 +380,36 @@ int orbit_frames_resize_from_uint8(const uint8_t* frames, int layout_hwc, int B,
     hipStream_t s = (hipStream_t)stream;
     const size_t in_frame = 3 * (size_t)H_in * W_in, out_frame = 3 * (size_t)H_out * W_out;
     char name[48];
-    snprintf(name, sizeof(name), "frames_resize<%s>", resize_filter_name(filter));
+    snprintf(name, sizeof(name), out_u8 ? "frames_resize_u8<%s>" : "frames_resize<%s>", resize_filter_name(filter));
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = std::min(chunk, B - b0);
-        const int rec = prof_start(name, 0.0, (double)nb * (in_frame + 4.0 * out_frame), s);
-        frames_resize_u8_kernel<<<nb * per_frame, RS_THREADS, lds, s>>>(
-            frames + b0 * in_frame, nb * in_frame, layout_hwc, H_in, W_in, H_out, W_out, th, tiles_x, tiles_y, stage_rows, pitch,
-            stage_off, ax, ay, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], out_nchw + b0 * out_frame);
+        const int rec = prof_start(name, 0.0, (double)nb * (in_frame + (out_u8 ? 1.0 : 4.0) * out_frame), s);
+        if (out_u8)
+            frames_resize_u8_kernel<true><<<nb * per_frame, RS_THREADS, lds, s>>>(
+                frames + b0 * in_frame, nb * in_frame, layout_hwc, H_in, W_in, H_out, W_out, th, tiles_x, tiles_y, stage_rows, pitch,
+                stage_off, ax, ay, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, nullptr, out_u8 + b0 * out_frame);
+        else
+            frames_resize_u8_kernel<false><<<nb * per_frame, RS_THREADS, lds, s>>>(
+                frames + b0 * in_frame, nb * in_frame, layout_hwc, H_in, W_in, H_out, W_out, th, tiles_x, tiles_y, stage_rows, pitch,
+                stage_off, ax, ay, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], out_nchw + b0 * out_frame, nullptr);
         prof_stop(rec, s);
         ORBIT_LAUNCH_CHECK();
     }
     return ORBIT_OK;
+}
+
+int orbit_frames_resize_from_uint8(const uint8_t* frames, int layout_hwc, int B, int H_in, int W_in, int H_out, int W_out,
+                                   int filter, const float* mean3, const float* std3, float* out_nchw, orbit_stream_t stream) {
+    ORBIT_REQUIRE(frames && mean3 && std3 && out_nchw, "frames_resize_from_uint8: null pointer");
+    return frames_resize("frames_resize_from_uint8", frames, layout_hwc, B, H_in, W_in, H_out, W_out, filter, mean3, std3, out_nchw,
+                         nullptr, stream);
+}
+
+int orbit_frames_resize_u8(const uint8_t* frames, int layout_hwc, int B, int H_in, int W_in, int H_out, int W_out, int filter,
+                           uint8_t* out_u8_hwc, orbit_stream_t stream) {
+    ORBIT_REQUIRE(frames && out_u8_hwc, "frames_resize_u8: null pointer");
+    return frames_resize("frames_resize_u8", frames, layout_hwc, B, H_in, W_in, H_out, W_out, filter, nullptr, nullptr, nullptr,
+                         out_u8_hwc, stream);
 }
 
 }  // extern "C"

@@ -6,7 +6,11 @@ offline pass of the reference (scripts/resize_videos.py:46) this replaces. The f
 --decode measures the JPEG decoder instead (orbit_frames_from_jpeg, csrc/jpeg.hip) on 224 x 224 and 1080 x 1080 frames written
 by write_synthetic_orbit_directory: us per launch of each of its three kernels, the bytes uploaded compressed against decoded,
 and PIL's decode of the same files on 16 threads; every frame is compared with PIL.
-Usage (GPU box): python tools/ingest_bench.py [--decode] [--frames 200] [--reps 10] [--threads 16]"""
+--encode measures the JPEG encoder (orbit_frames_to_jpeg, csrc/jpeg_enc.hip) on 224 x 224 frames - the size tools/resize_videos.py
+writes - of smooth and of noise content at quality 95: us per call of each of its kernels beside the kernel's byte floor (its
+algorithmic bytes at 6.3 TB/s), the compressed bytes out, and PIL's save(quality=95) of the same frames on 16 threads; every
+file is compared with PIL's.
+Usage (GPU box): python tools/ingest_bench.py [--decode | --encode] [--frames 200] [--reps 10] [--threads 16]"""
 import argparse
 import ctypes
 import json
@@ -105,8 +109,91 @@ def measure_decode(a, lib, dev, pool):
     return rows
 
 
+def measure_encode(a, lib, dev, pool):
+    """orbit_frames_to_jpeg against PIL's save, per content"""
+    import io
+    from orbit_dataset_amd.data import encode as enc
+    size, n, rows = a.encode_size, a.frames, []
+    y, x = np.mgrid[0:size, 0:size]
+    rng = np.random.default_rng(0)
+    for kind in ("smooth", "noise"):
+        if kind == "noise":
+            host = rng.integers(0, 256, (n, size, size, 3), dtype=np.uint8)
+        else:
+            host = np.stack([np.stack([(x * 7 + y * 3 + 5 * k) % 256, (y * 5 + 40 + k) % 256, (x * y + k) % 256], -1).astype(np.uint8)
+                             for k in range(n)])
+        u8 = torch.from_numpy(host).to(dev)
+
+        def pil_one(i):
+            buf = io.BytesIO()
+            Image.fromarray(host[i]).save(buf, format="JPEG", quality=95)
+            return buf.getvalue()
+
+        pil_s = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            want = list(pool.map(pil_one, range(n)))
+            pil_s.append(time.perf_counter() - t0)
+        p = enc.encode_params(95, 0)
+        stride = (lib.orbit_jpeg_encode_bound(size, size, 0, 0) + 15) // 16 * 16
+        ws_bytes = lib.orbit_jpeg_encode_workspace_bytes(n, size, size)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(n * stride, dtype=torch.uint8, device=dev)
+        packed = torch.empty(n * stride, dtype=torch.uint8, device=dev)
+        sizes = torch.empty(n, dtype=torch.int32, device=dev)
+        starts = torch.empty(n + 1, dtype=torch.int32, device=dev)
+
+        def run():
+            _lib.check(lib.orbit_frames_to_jpeg(_lib.dptr(u8), n, size, size, ctypes.byref(p), None, None, _lib.dptr(out), stride,
+                                                _lib.dptr(sizes), _lib.dptr(ws), ws_bytes, _lib.stream_handle()), "orbit_frames_to_jpeg")
+            _lib.check(lib.orbit_jpeg_compact(_lib.dptr(out), stride, _lib.dptr(sizes), n, _lib.dptr(packed), n * stride,
+                                              _lib.dptr(starts), _lib.stream_handle()), "orbit_jpeg_compact")
+
+        for _ in range(2):
+            run()
+        torch.cuda.synchronize()
+        at = starts.cpu().numpy().astype(np.int64)
+        data = packed[:int(at[n])].cpu().numpy().tobytes()
+        exact = all(data[at[i]:at[i + 1]] == want[i] for i in range(n))
+        lib.orbit_prof_enable(1)
+        for _ in range(a.reps):
+            run()
+        torch.cuda.synchronize()
+        lib.orbit_prof_enable(0)
+        ms, launches = ctypes.c_double(), ctypes.c_long()
+        lib.orbit_prof_collect(ctypes.byref(ms), None, ctypes.byref(launches))
+        compressed = int(at[n])
+        mcus = ((size + 15) // 16) ** 2
+        blocks, px = 6 * mcus * n, n * size * size
+        scan_bytes = compressed - n * 623  # (header and EOI apart; stuffed bytes counted, a small overestimate)
+        algorithmic = {"jpeg_enc_color": 3 * px + 384 * mcus * n, "jpeg_enc_dct": 384 * mcus * n + 128 * blocks, "jpeg_enc_size": 132 * blocks,
+                       "jpeg_enc_scan": 8 * blocks + scan_bytes, "jpeg_enc_pack": 136 * blocks + scan_bytes,
+                       "jpeg_enc_ff": scan_bytes + scan_bytes // 8, "jpeg_enc_assemble": 2 * compressed + scan_bytes // 8,
+                       "jpeg_compact": 2 * compressed}
+        kernels = {}
+        for i in range(lib.orbit_prof_num_variants()):
+            name, count, kms = ctypes.create_string_buffer(48), ctypes.c_long(), ctypes.c_double()
+            lib.orbit_prof_variant(i, name, ctypes.byref(count), ctypes.byref(kms), None, None)
+            k = name.value.decode()
+            kernels[k] = {"us_per_call": 1e3 * kms.value / a.reps, "launches_per_call": count.value / a.reps,
+                          "byte_floor_us": 1e6 * algorithmic[k] / HBM_BYTES_PER_S}
+        row = {"size": size, "frames": n, "content": kind, "kernels": kernels, "us_per_call": 1e3 * ms.value / a.reps,
+               "compressed_bytes": compressed, "raw_bytes": 3 * px, "pil_ms": 1e3 * min(pil_s), "pil_ms_runs": [1e3 * v for v in pil_s],
+               "pil_threads": a.threads, "all_files_equal_pil": exact}
+        rows.append(row)
+        print("%d x %d %-6s %d frames: %9.1f us per call (sum of kernels) | %.2f MB out of %.2f MB | PIL x%d threads %8.1f ms (%5.1fx) | files %s PIL"
+              % (size, size, kind, n, row["us_per_call"], compressed / 1e6, 3 * px / 1e6, a.threads, row["pil_ms"],
+                 1e3 * row["pil_ms"] / row["us_per_call"], "==" if exact else "!="), flush=True)
+        for k, v in sorted(kernels.items()):
+            print("    %-20s %8.1f us   byte floor %6.2f us" % (k, v["us_per_call"], v["byte_floor_us"]), flush=True)
+        assert exact, "an encoded file differs from PIL's"
+    return rows
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
+    p.add_argument("--encode", action="store_true", help="measure the JPEG encoder instead of the resize")
+    p.add_argument("--encode_size", type=int, default=224, help="with --encode: the frame size")
     p.add_argument("--decode", action="store_true", help="measure the JPEG decoder instead of the resize")
     p.add_argument("--sizes", type=int, nargs="+", default=[224, 1080], help="with --decode: the frame sizes")
     p.add_argument("--frames", type=int, default=200)
@@ -119,6 +206,13 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     mean, std = (torch.tensor(v)[:, None, None] for v in NORMALIZE_STATS["imagenet"])
     pool = ThreadPoolExecutor(max_workers=a.threads)
+    if a.encode:
+        print("%d frames per call, device %s, PIL %s on %d threads" % (a.frames, torch.cuda.get_device_name(0), Image.__version__, a.threads))
+        rows = measure_encode(a, lib, dev, pool)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(rows, f, indent=1)
+        return rows
     if a.decode:
         print("%d frames per call, device %s, PIL %s on %d threads" % (a.frames, torch.cuda.get_device_name(0), Image.__version__, a.threads))
         rows = measure_decode(a, lib, dev, pool)
