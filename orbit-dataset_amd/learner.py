@@ -1,13 +1,17 @@
-"""Counterpart of the reference's single-step-learner.py for the native path (train / test on synthetic tasks).
+"""Counterpart of the reference's single-step-learner.py and multi-step-learner.py for the native path: train, validate and
+test, and the finetuner's test, on synthetic tasks or on a dataset tree.
 
 Keeps the reference CLI's flag names for everything that touches the hot path (reference utils/args.py:12-192:
 --feature_extractor --learn_extractor --adapt_features --classifier --logit_scale --clip_length --frame_size
 --batch_size --tasks_per_batch --with_lite --num_lite_samples --gpu --seed --mode --model_path) and the test
 loop's call order (reference single-step-learner.py:298-375): per task personalise() -> per target video
 {attach_frame_history -> predict -> frame accuracy} -> _reset(), with 'personalise' and per-frame 'inference' timers
-(here device-synchronised; the reference's time.time() pairs do not sync). The ORBIT dataset is not available
-offline, so tasks come from `synthetic.make_task` in the task_dict layout of reference data/datasets.py:584-597;
-`--feature_extractor` additionally accepts resnet18 and `--frame_size` any size (BASELINE.json configs).
+(here device-synchronised; the reference's time.time() pairs do not sync). That loop is written once
+(`Learner._evaluate`) for test and validation, the single-step learner and the finetuner (which swaps in its two steps,
+`_personalise` / `_predict_video`), a tree's tasks and synthetic ones. Without a dataset tree the tasks come from
+`synthetic.make_task` in the task_dict layout of reference data/datasets.py:584-597, their query frames grouped into videos as
+a tree's test-mode tasks are (`Learner.make_task`); `--feature_extractor` additionally accepts resnet18 and `--frame_size`
+any size (BASELINE.json configs).
 
 Training (reference single-step-learner.py:128-243): per task `train_task` or `train_task_with_lite` (per query
 batch {personalise_with_lite -> predict_a_batch -> N/(H*tasks_per_batch) * CE + 0.001 * l2 -> backward -> _reset}),
@@ -28,20 +32,22 @@ five annotation flags hold there (utils/args.py:79-88): --train_filter_* on the 
 validation and test splits, --annotations_to_load on all three; the filters act when the tree is indexed, so a dropped
 frame is never read. `--test_filter_target no_object_not_present_issue` is the benchmark's clutter-video protocol (CLU-VE).
 
-Multi-GPU: launched under torchrun, tasks are dealt round-robin to ranks (task i -> rank i % world). Test mode has no
-data-path collective (per-task statistics are all-gathered at the end). Training all-reduces (SUM, RCCL) one flat
-gradient bucket per optimizer step: every task's loss already carries 1/tasks_per_batch, so the sum over ranks
+Multi-GPU: launched under torchrun, tasks are dealt round-robin to ranks (task i -> rank i % world). Test and validation
+have no data-path collective (per-task statistics are all-gathered at the end: `gather_lists`). Training all-reduces (SUM, RCCL) one
+flat gradient bucket per optimizer step: every task's loss already carries 1/tasks_per_batch, so the sum over ranks
 reproduces single-GPU accumulation; BatchNorm running statistics are combined at the same point as the reference's
 sequential updates would have left them (dist.RunningStatSync).
 """
 import argparse
 import collections
+import contextlib
 import json
 import math
 import os
 import random
 import sys
 import time
+import types
 
 import numpy as np
 import torch
@@ -51,7 +57,7 @@ from . import synthetic
 from .data.datasets import ALL_FRAME_ANNOTATION_OPTIONS, BOUNDING_BOX_OPTIONS, FRAME_ANNOTATION_OPTIONS, expand_issues
 from .data.utils import attach_frame_history, unpack_task
 from .model.feature_extractors import EXTRACTORS
-from .model.few_shot_recognisers import SingleStepFewShotRecogniser
+from .model.few_shot_recognisers import MultiStepFewShotRecogniser, SingleStepFewShotRecogniser
 from .optim import (SCHEDULERS, apply_lr_scale, cross_entropy, get_curr_learning_rates, init_optimizer,  # noqa: F401
                     init_scheduler)  # (re-exported: bench.py, tools)
 from .utils.eval_metrics import TestEvaluator
@@ -395,6 +401,7 @@ class OrbitMetrics:
     frames-to-recognition averaged per user, object, task and video, and video accuracy per object and video."""
 
     def __init__(self, save_dir=None):
+        self.save_dir = save_dir
         self.evaluator = TestEvaluator(ORBIT_METRICS, save_dir=save_dir)
         self.tasks = []  # (global task index, user key, object list) of the tasks fed, in order
 
@@ -425,7 +432,7 @@ class OrbitMetrics:
                            v.paths if with_predictions else None) for v in videos]) for tag, videos in zip(self.tasks, mine)]
         gathered = [None] * world
         dist.all_gather_object(gathered, payload)
-        merged = OrbitMetrics(getattr(self.evaluator, "save_dir", None))
+        merged = OrbitMetrics(self.save_dir)
         for (index, user, object_list), videos in sorted((x for g in gathered for x in g), key=lambda x: x[0][0]):
             merged.begin_task(index, user, object_list)
             for video in videos:
@@ -459,7 +466,39 @@ def _shown(stat):
     return (float("nan") if stat[0] is None else stat[0]), stat[1]
 
 
+def timed_ms(fn, *args):
+    """fn(*args) between two device synchronisations -> (its result, milliseconds)"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn(*args)
+    torch.cuda.synchronize()
+    return out, 1e3 * (time.perf_counter() - t0)
+
+
+def gather_lists(world, *lists):
+    """this rank's lists -> those of all ranks, each flattened in rank order: every rank holds the statistics of the whole run"""
+    if world == 1:
+        return lists
+    import torch.distributed as dist
+    gathered = [None] * world
+    dist.all_gather_object(gathered, lists)
+    return tuple([x for g in gathered for x in g[i]] for i in range(len(lists)))
+
+
+def host_state(model):
+    """model.state_dict() on the host: what every file the learner saves holds"""
+    return {k: v.detach().cpu() for k, v in model.state_dict().items()}
+
+
 class Learner:
+    strict_load = True  # load_state_dict(strict=) of --model_path
+    # state that appears during a run (None: not there yet)
+    best_validation = None  # (mean, ci) of the best validation so far; None: no validation has beaten 0 yet
+    validation_history = None  # [(epoch, mean, better)], one entry per validate()
+    gradless_parameters = None  # diagnostic: the parameters without a gradient at the first optimizer step
+    grad_bucket = stat_sync = None  # multi-GPU training (dist.GradientBucket, dist.RunningStatSync)
+    _pool = _split_index = _train_items = _validation_dataset = None  # dataset trees: see decode_pool, build_dataset, validate
+
     def __init__(self, args):
         self.args = args
         verify_args(args)
@@ -474,42 +513,45 @@ class Learner:
         gc.collect()
         gc.freeze()  # keep torch + the model out of the cyclic collector's working set (full collections cost ms)
 
+    def new_recogniser(self):
+        a = self.args
+        return SingleStepFewShotRecogniser(a.feature_extractor, a.adapt_features, a.classifier, a.clip_length, a.batch_size,
+                                           a.learn_extractor, a.num_lite_samples, a.logit_scale)
+
     def init_model(self):
         a = self.args
-        self.model = SingleStepFewShotRecogniser(a.feature_extractor, a.adapt_features, a.classifier, a.clip_length,
-                                                 a.batch_size, a.learn_extractor, a.num_lite_samples, a.logit_scale)
+        self.model = self.new_recogniser()
         if a.model_path:
             # reference single-step-learner.py:300-302. The FiLM generator's gamma0/beta0 snapshot is not part of the file
             # (feature_adapters.py:55-58); the recogniser re-takes it from the loaded extractor (load_state_dict hook)
-            self.model.load_state_dict(torch.load(a.model_path, map_location="cpu"))
+            self.model.load_state_dict(torch.load(a.model_path, map_location="cpu"), strict=self.strict_load)
         else:
             synthetic.init_parameters_(self.model, seed=a.seed,
                                        film_strength=0.02 if a.feature_extractor == "efficientnet_b0" else 0.1)
-        self._opt_in_native_backward()
+        spec = FROZEN_EXTRACTORS.get(a.feature_extractor)
+        for flag, attr in ((spec.film_flag, "native_backward"), (spec.weight_flag, "native_weight_backward")) if spec else ():
+            if flag and getattr(a, flag):
+                setattr(self.model.feature_extractor, attr, True)
         self.model._set_device(self.device)
         self.model._send_to_device()
 
-    def _opt_in_native_backward(self):
-        spec = FROZEN_EXTRACTORS.get(self.args.feature_extractor)
-        for flag, attr in ((spec.film_flag, "native_backward"), (spec.weight_flag, "native_weight_backward")) if spec else ():
-            if flag and getattr(self.args, flag, False):
-                setattr(self.model.feature_extractor, attr, True)
+    def synthetic_task(self, index):
+        a = self.args
+        per_class = a.shots * a.frames_per_shot
+        per_class -= per_class % a.clip_length
+        return synthetic.make_task(index, a.way, 1, per_class, a.num_query_videos * a.frames_per_video, a.frame_size,
+                                   clip_length=a.clip_length, seed=a.seed)
 
     def make_task(self, index):
+        """synthetic test / validation task `index` in the layout a tree's test-mode tasks have (data/pipeline.py), frames on
+        the host: the query frames grouped into videos (reference: target_frames_by_video) by their row ranges, one label per
+        frame - a synthetic "video" mixes objects. One user is one task."""
         a = self.args
-        T = a.clip_length
-        per_class = a.shots * a.frames_per_shot
-        per_class -= per_class % T
-        task = synthetic.make_task(index, a.way, 1, per_class, a.num_query_videos * a.frames_per_video, a.frame_size,
-                                   clip_length=T, seed=a.seed)
-        # query frames grouped into videos of one object each (reference: target_frames_by_video)
-        frames = task["target_clips"][:, 0] if T == 1 else task["target_clips"][:, -1]
-        labels = task["target_labels"]
-        videos = []
-        for v in range(a.num_query_videos):
-            sl = slice(v * a.frames_per_video, (v + 1) * a.frames_per_video)
-            videos.append((frames[sl], labels[sl]))
-        return task["context_clips"], task["context_labels"], videos
+        task = self.synthetic_task(index)
+        task["target_clips"] = task["target_clips"][:, -1:]  # [M,1,3,H,W]: a video's frames are the LAST frame of its query clips
+        task["target_videos"] = [(v * a.frames_per_video, (v + 1) * a.frames_per_video) for v in range(a.num_query_videos)]
+        task["user"] = index
+        return task
 
     def run(self):
         """train / test / train_test as the reference's run() (single-step-learner.py:136-193): after training, train_test
@@ -520,8 +562,8 @@ class Learner:
             stats["train"] = self.train()
         if "test" in self.args.mode:
             stats["test"] = self.test()
-            best_path = getattr(self.args, "save_best_model_path", None)
-            if "train" in self.args.mode and getattr(self, "best_validation", None) is not None and best_path:
+            best_path = self.args.save_best_model_path
+            if "train" in self.args.mode and self.best_validation is not None and best_path:
                 if self.world > 1:  # rank 0 wrote the file (validate()): every rank loads it after the write is complete
                     import torch.distributed as dist
                     dist.barrier()
@@ -534,11 +576,7 @@ class Learner:
 
     # ---- meta-training (reference single-step-learner.py:128-243) ----------------------------------------------------
     def make_train_task(self, index):
-        a = self.args
-        per_class = a.shots * a.frames_per_shot
-        per_class -= per_class % a.clip_length
-        return synthetic.make_task(10_000 + index, a.way, 1, per_class, a.num_query_videos * a.frames_per_video,
-                                   a.frame_size, clip_length=a.clip_length, seed=a.seed)
+        return self.synthetic_task(10_000 + index)
 
     def train_task(self, task):
         a = self.args
@@ -587,13 +625,13 @@ class Learner:
     def decode_pool(self):
         """the threads that decode (or, with --decode device, read and parse) the frames of every tree loop: --num_workers of
         them, never the CPU count"""
-        if getattr(self, "_pool", None) is None:
+        if self._pool is None:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=max(1, int(self.args.num_workers)))
         return self._pool
 
     def _close_decode_pool(self):
-        if getattr(self, "_pool", None) is not None:
+        if self._pool is not None:
             self._pool.shutdown()
             self._pool = None
 
@@ -604,12 +642,12 @@ class Learner:
         a = self.args
         root = split_roots(a).get(split)
         if root is None:
-            raise ValueError("--mode %s%s reads no %s split from a tree" % (a.mode, "" if getattr(a, "data_path", None) or getattr(
-                a, "data_root", None) else " without --data_path", split))
+            raise ValueError("--mode %s%s reads no %s split from a tree"
+                             % (a.mode, "" if a.data_path or a.data_root else " without --data_path", split))
         if frames is None:
             frames = "jpeg" if a.decode == "device" else "uint8"
         dataset = build_split_dataset(a, split, root, frames, self.rank, None if frames == "paths" else self.decode_pool())
-        if getattr(self, "_split_index", None) is None:
+        if self._split_index is None:
             self._split_index = {}
         self._split_index[split] = dataset.index_summary()
         return dataset
@@ -619,7 +657,17 @@ class Learner:
         (data/datasets.index_summary; None on synthetic tasks)"""
         to_load, (context, target) = split_annotation_args(self.args, split)
         return {"filter_context": list(context), "filter_target": list(target), "annotations_to_load": list(to_load),
-                "index": (getattr(self, "_split_index", None) or {}).get(split)}
+                "index": (self._split_index or {}).get(split)}
+
+    def ingest_stats(self, prefetch, tree):
+        """the input pipeline's side of a tree loop's results (`prefetch` None: tasks that did not come through it): the sizes
+        the frames were stored at and run at, the resize filter if one ran, and where the frames were decoded"""
+        a = self.args
+        stored = sorted(prefetch.stored_sizes) if prefetch is not None else []  # (this rank's tasks)
+        return {"stored_frame_size": [list(hw) for hw in stored], "frame_size": [a.frame_size, a.frame_size],
+                "resample": a.resample if any(hw != (a.frame_size, a.frame_size) for hw in stored) else None,
+                "decode": a.decode if tree else None,
+                "decode_fallback_frames": prefetch.fallback_frames if prefetch is not None and a.decode == "device" else None}
 
     def train_order(self, epoch):
         """this rank's item indices (users; objects when object-centric) of train epoch `epoch`, in the order it trains on them:
@@ -628,7 +676,7 @@ class Learner:
         return task_order(self._num_train_items(), a.num_train_tasks, a.seed, epoch)[self.rank::self.world]
 
     def _num_train_items(self):
-        if getattr(self, "_train_items", None) is None:
+        if self._train_items is None:
             self._train_items = num_items(self.build_dataset("train", frames="paths"))
         return self._train_items
 
@@ -641,121 +689,97 @@ class Learner:
         return TaskPrefetcher(DatasetTaskSource(dataset, indices), self.device, depth=depth, frame_norm_method=a.frame_norm_method,
                               frame_size=a.frame_size, resample=a.resample)
 
-    def train(self, task_source=None):
-        """task_source: an iterable of this rank's train tasks (task dicts as data/datasets.py returns them, all epochs in
-        train_order order - with --resume those from the checkpoint's epoch on) that stands in for the tree and the prefetcher;
-        loop, seeds and step boundaries are the same."""
+    def _init_training(self):
+        """optimizer, schedule, --resume and, multi-GPU, the gradient and running-statistics exchange -> the epoch to start at"""
         a = self.args
-        tree = split_roots(a).get("train")
-        if tree is None and getattr(a, "data_root", None) and self.rank == 0:
-            print("train: --data_root names a test split only: training runs on synthetic tasks (use --data_path ROOT)")
         self.optimizer = init_optimizer(self.model, a.learning_rate, a.optimizer, a, a.extractor_lr_scale)
         self.scheduler = init_scheduler(self.optimizer, a)  # applies f(0) * lr_scale (default: the constant --learning_rate)
-        start_epoch = self.load_checkpoint() if getattr(a, "resume", False) else 0
-        lr_history, num_updates = [], 0
+        start_epoch = self.load_checkpoint() if a.resume else 0
         self.grad_bucket = None
         if self.world > 1:
             p2p = None
-            if getattr(a, "p2p_gradients", False):
+            if a.p2p_gradients:
                 cap = sum(-(-q.numel() // 64) * 64 for q in self.model.parameters() if q.requires_grad)
                 p2p = odist.P2PAllReduce(self.rank, self.world, odist.P2PAllReduce.floats_for_bucket(cap, self.world))
             self.grad_bucket = odist.GradientBucket(self.model.parameters(), p2p=p2p)
             if self.model.learn_extractor:
-                self.stat_sync = odist.RunningStatSync(self.model.feature_extractor,
-                                                       getattr(self.model.feature_extractor, "bn_momentum", 0.1))
-        train_task_fn = self.train_task_with_lite if a.with_lite else self.train_task
-        losses, accs, times, waits, task_frames = [], [], [], [], []
-        # (per task, in this rank's order: the losses are what a run on the same tasks must reproduce)
-        self.task_losses, self.task_ms, self.task_wait_ms = losses, times, waits
-        prefetch, stream, t_all = None, None, time.perf_counter()
-        lite_query_overlap = getattr(self.model, "lite_query_overlap", False)
-        if task_source is not None:
-            stream = iter(task_source)
-        elif tree is not None:
+                self.stat_sync = odist.RunningStatSync(self.model.feature_extractor, self.model.feature_extractor.bn_momentum)
+        return start_epoch
+
+    @contextlib.contextmanager
+    def _train_tasks(self, task_source, start_epoch):
+        """-> (tasks, prefetch): ONE iterator of (task, ms waited for it) over this rank's train tasks of all epochs from
+        `start_epoch` - handed in, from the tree, or synthetic (waited None) - and the tree's prefetcher (else None), which is
+        closed with its pool, and the recogniser's lite_query_overlap put back, on leaving."""
+        a = self.args
+        prefetch, lite_query_overlap = None, self.model.lite_query_overlap
+        if task_source is None and split_roots(a).get("train"):
             # ONE prefetcher over all epochs (the first tasks of epoch e+1 are staged under the validation of epoch e), two
             # slots: the step is longer than the staging of a task, a third slot would only hold memory (DESIGN.md §1).
             # A slot must not be refilled while any stream of the recogniser still reads it (LITE's subset pass and its
-            # query pass run on side streams): the loop SYNCHRONISES THE DEVICE after every task's step - the timer below needs
+            # query pass run on side streams): the loop SYNCHRONISES THE DEVICE after every task's step - the step's timer needs
             # that anyway - before it asks for the next task, so no consumer_streams are passed to the prefetcher.
             dataset = self.build_dataset("train")
             self._train_items = num_items(dataset)
             prefetch = self._prefetch(dataset, [i for epoch in range(start_epoch, a.epochs) for i in self.train_order(epoch)],
                                       depth=2)
-            stream = iter(prefetch)
             # The yielded clips are complete on the caller's stream when next() returns (it waits for the slot's event), so the
             # query batch's taped pass may start from LITE's fork point as it does for clips on the host: the same kernels,
             # and the same deferred running-statistics update, whether a task comes from the tree or from host tensors
-            self.model.lite_query_overlap = bool(getattr(self.model, "lite_overlap", False))
-        prev = torch.is_grad_enabled()
-        torch.set_grad_enabled(True)
+            self.model.lite_query_overlap = bool(self.model.lite_overlap)
         try:
-            self.model.set_test_mode(False)
-            for epoch in range(start_epoch, a.epochs):
-                first_loss = len(losses)
-                # with --data_path: --num_train_tasks per user (or object), in the queue's order (task_order)
-                total_steps = a.num_train_tasks if tree is None else self._num_train_items() * a.num_train_tasks
-                # this rank's tasks of the epoch are generated up front (the reference prefetches with DataLoader
-                # workers): generating them between steps leaves the intra-op CPU threads spinning against the thread
-                # that enqueues kernels, which showed up as random 50-80 ms stalls per task
-                mine = [s_ for s_ in range(total_steps) if s_ % self.world == self.rank]
-                task_bytes = 4.0 * 3 * a.frame_size ** 2 * a.way * (a.shots * a.frames_per_shot
-                                                                   + a.num_query_videos * a.frames_per_video)
-                pregen = {s_: self.make_train_task(epoch * total_steps + s_) for s_ in mine} \
-                    if stream is None and task_bytes * len(mine) < 16e9 else {}
-                for step in range(total_steps):
-                    if step % self.world == self.rank:
-                        if stream is not None:
-                            t0 = time.perf_counter()
-                            task = next(stream)  # (hands the previous task's slot back: the device is idle, see above)
-                            waits.append(1e3 * (time.perf_counter() - t0))
-                            task_frames.append(sum(int(np.prod(task[k].shape[:2])) for k in ("context_clips", "target_clips")))
-                        else:
-                            task = pregen.pop(step, None) or self.make_train_task(epoch * total_steps + step)
-                        # LITE draws its subsets from np.random (few_shot_recognisers.py:330); seeding per TASK (the
-                        # reference leaves numpy unseeded) makes a run independent of how tasks are dealt to ranks
-                        np.random.seed((a.seed + 7919 * (epoch * total_steps + step + 1)) % (2 ** 32))
-                        torch.cuda.synchronize()
-                        t0 = time.perf_counter()
-                        task_loss, logits = train_task_fn(task)
-                        torch.cuda.synchronize()
-                        times.append(1e3 * (time.perf_counter() - t0))
-                        losses.append(float(task_loss))
-                        accs.append(frame_accuracy(logits.cpu(), task["target_labels"].cpu()))
-                        if a.print_by_step:
-                            print("epoch [%d/%d][%d/%d] rank %d train loss %.7f frame_acc %.3f  %.1f ms/task"
-                                  % (epoch + 1, a.epochs, step + 1, total_steps, self.rank, losses[-1], accs[-1], times[-1]))
-                    if (step + 1) % a.tasks_per_batch == 0 or step == total_steps - 1:
-                        self._sync_gradients()
-                        if not hasattr(self, "gradless_parameters"):  # diagnostic, first optimizer step only
-                            self.gradless_parameters = sorted(n for n, p in self.model.named_parameters()
-                                                              if p.requires_grad and p.grad is None)
-                        self.optimizer.step()
-                        if self.grad_bucket is not None:
-                            if self.model.learn_extractor:
-                                self.stat_sync.begin()  # the next window's running statistics start from here
-                            self.grad_bucket.zero_()  # one memset; gradients keep living inside the flat bucket
-                        else:
-                            self.optimizer.zero_grad()
-                        num_updates += 1
-                        self.scheduler.step_update(num_updates)  # (a no-op for epoch schedules, where the reference calls it: :166)
-                lr, fe_lr = get_curr_learning_rates(self.optimizer)[:2]  # reference :170-174
-                lr_history.append((lr, fe_lr))
-                if self.rank == 0:
-                    print("epoch [%d/%d] train loss: %.7f lr: %.3e fe-lr: %.3e"
-                          % (epoch + 1, a.epochs, float(np.mean(losses[first_loss:])) if len(losses) > first_loss else float("nan"),
-                             lr, fe_lr))
-                self.scheduler.step(epoch + 1)  # before validation, the reference's order (:177-181)
-                if a.num_val_tasks > 0 and (epoch + 1) >= a.validation_on_epoch:
-                    self.validate(epoch + 1)
-                    torch.set_grad_enabled(True)
-                    self.model.set_test_mode(False)
-                self.save_checkpoint(epoch + 1)
+            if task_source is None and prefetch is None:
+                yield self._synthetic_train_tasks(start_epoch), None
+            else:
+                yield self._waited_for(prefetch if task_source is None else task_source), prefetch
         finally:
-            torch.set_grad_enabled(prev)
             self.model.lite_query_overlap = lite_query_overlap
             if prefetch is not None:
                 prefetch.close()
                 self._close_decode_pool()
+
+    @staticmethod
+    def _waited_for(tasks):
+        t0 = time.perf_counter()
+        for task in tasks:  # (a prefetcher hands the previous task's slot back: the device is idle, see _train_tasks)
+            yield task, 1e3 * (time.perf_counter() - t0)
+            t0 = time.perf_counter()
+
+    def _synthetic_train_tasks(self, start_epoch):
+        a = self.args
+        for epoch in range(start_epoch, a.epochs):
+            # this rank's tasks of the epoch are generated up front (the reference prefetches with DataLoader
+            # workers): generating them between steps leaves the intra-op CPU threads spinning against the thread
+            # that enqueues kernels, which showed up as random 50-80 ms stalls per task
+            mine = [s_ for s_ in range(a.num_train_tasks) if s_ % self.world == self.rank]
+            task_bytes = 4.0 * 3 * a.frame_size ** 2 * a.way * (a.shots * a.frames_per_shot
+                                                               + a.num_query_videos * a.frames_per_video)
+            pregen = {s_: self.make_train_task(epoch * a.num_train_tasks + s_) for s_ in mine} \
+                if task_bytes * len(mine) < 16e9 else {}
+            for step in mine:
+                yield pregen.pop(step, None) or self.make_train_task(epoch * a.num_train_tasks + step), None
+
+    def train(self, task_source=None):
+        """task_source: an iterable of this rank's train tasks (task dicts as data/datasets.py returns them, all epochs in
+        train_order order - with --resume those from the checkpoint's epoch on) that stands in for the tree and the prefetcher;
+        loop, seeds and step boundaries are the same."""
+        a = self.args
+        if not split_roots(a).get("train") and a.data_root and self.rank == 0:
+            print("train: --data_root names a test split only: training runs on synthetic tasks (use --data_path ROOT)")
+        start_epoch = self._init_training()
+        # per task, in this rank's order: the losses are what a run on the same tasks must reproduce
+        log = types.SimpleNamespace(losses=[], accs=[], ms=[], wait_ms=[], frames=[], lr_history=[], num_updates=0)
+        self.task_losses, self.task_ms, self.task_wait_ms = log.losses, log.ms, log.wait_ms
+        t_all = time.perf_counter()
+        prev = torch.is_grad_enabled()
+        torch.set_grad_enabled(True)
+        try:
+            with self._train_tasks(task_source, start_epoch) as (tasks, prefetch):
+                self.model.set_test_mode(False)
+                for epoch in range(start_epoch, a.epochs):
+                    self._train_epoch(epoch, tasks, log)
+        finally:
+            torch.set_grad_enabled(prev)
         wall = time.perf_counter() - t_all
         if self.grad_bucket is not None and self.grad_bucket.p2p is not None:
             # every optimizer step checked the exchange before it (GradientBucket.sync); this covers the last one: a peer
@@ -763,34 +787,91 @@ class Learner:
             torch.cuda.synchronize()
             self.grad_bucket.p2p.raise_on_error()
         if a.save_model_path and self.rank == 0:  # every rank holds the same parameters after the last step
-            torch.save({k: v.detach().cpu() for k, v in self.model.state_dict().items()}, a.save_model_path)
-        stats = {"loss": mean_ci(losses) if losses else (0.0, 0.0), "frame_acc": mean_ci(accs) if accs else (0.0, 0.0),
-                 "ms_per_task": mean_ci(times) if times else (0.0, 0.0), "num_tasks": len(losses),
-                 "world_size": self.world, "validation": getattr(self, "validation_history", None),
-                 "best_validation": getattr(self, "best_validation", None),
-                 "lr": lr_history[-1][0] if lr_history else None, "fe_lr": lr_history[-1][1] if lr_history else None,
-                 "lr_history": lr_history, "start_epoch": start_epoch}
+            torch.save(host_state(self.model), a.save_model_path)
+        return self._train_report(log, prefetch, start_epoch, wall)
+
+    def _train_epoch(self, epoch, tasks, log):
+        """one epoch of the reference's loop (single-step-learner.py:143-182): this rank's share of the epoch's steps, an
+        optimizer step every --tasks_per_batch steps and after the last one, the schedule, validation, the checkpoint"""
+        a = self.args
+        first_loss = len(log.losses)
+        # with --data_path: --num_train_tasks per user (or object), in the queue's order (task_order)
+        total_steps = a.num_train_tasks * (self._num_train_items() if split_roots(a).get("train") else 1)
+        for step in range(total_steps):
+            if step % self.world == self.rank:
+                self._train_step(epoch, step, total_steps, *next(tasks), log)
+            if (step + 1) % a.tasks_per_batch == 0 or step == total_steps - 1:
+                self._optimizer_step(log)
+        lr, fe_lr = get_curr_learning_rates(self.optimizer)[:2]  # reference :170-174
+        log.lr_history.append((lr, fe_lr))
+        if self.rank == 0:
+            losses = log.losses[first_loss:]
+            print("epoch [%d/%d] train loss: %.7f lr: %.3e fe-lr: %.3e"
+                  % (epoch + 1, a.epochs, float(np.mean(losses)) if losses else float("nan"), lr, fe_lr))
+        self.scheduler.step(epoch + 1)  # before validation, the reference's order (:177-181)
+        if a.num_val_tasks > 0 and (epoch + 1) >= a.validation_on_epoch:
+            self.validate(epoch + 1)
+            torch.set_grad_enabled(True)
+            self.model.set_test_mode(False)
+        self.save_checkpoint(epoch + 1)
+
+    def _train_step(self, epoch, step, total_steps, task, wait_ms, log):
+        """the timed step of one task: the device is synchronised before and after it"""
+        a = self.args
+        if wait_ms is not None:
+            log.wait_ms.append(wait_ms)
+            log.frames.append(sum(int(np.prod(task[k].shape[:2])) for k in ("context_clips", "target_clips")))
+        # LITE draws its subsets from np.random (few_shot_recognisers.py:330); seeding per TASK (the
+        # reference leaves numpy unseeded) makes a run independent of how tasks are dealt to ranks
+        np.random.seed((a.seed + 7919 * (epoch * total_steps + step + 1)) % (2 ** 32))
+        (task_loss, logits), ms = timed_ms(self.train_task_with_lite if a.with_lite else self.train_task, task)
+        log.ms.append(ms)
+        log.losses.append(float(task_loss))
+        log.accs.append(frame_accuracy(logits.cpu(), task["target_labels"].cpu()))
+        if a.print_by_step:
+            print("epoch [%d/%d][%d/%d] rank %d train loss %.7f frame_acc %.3f  %.1f ms/task"
+                  % (epoch + 1, a.epochs, step + 1, total_steps, self.rank, log.losses[-1], log.accs[-1], ms))
+
+    def _optimizer_step(self, log):
+        self._sync_gradients()
+        if self.gradless_parameters is None:  # diagnostic, first optimizer step only
+            self.gradless_parameters = sorted(n for n, p in self.model.named_parameters() if p.requires_grad and p.grad is None)
+        self.optimizer.step()
+        if self.grad_bucket is not None:
+            if self.model.learn_extractor:
+                self.stat_sync.begin()  # the next window's running statistics start from here
+            self.grad_bucket.zero_()  # one memset; gradients keep living inside the flat bucket
+        else:
+            self.optimizer.zero_grad()
+        log.num_updates += 1
+        self.scheduler.step_update(log.num_updates)  # (a no-op for epoch schedules, where the reference calls it: :166)
+
+    def _train_report(self, log, prefetch, start_epoch, wall):
+        """-> train()'s result dict, summarised in one or two lines by rank 0"""
+        a = self.args
+        tree = split_roots(a).get("train")
+        lr, fe_lr = log.lr_history[-1] if log.lr_history else (None, None)
+        loss, acc, ms = (mean_ci(values) if values else (0.0, 0.0) for values in (log.losses, log.accs, log.ms))
+        stats = {"loss": loss, "frame_acc": acc, "ms_per_task": ms, "num_tasks": len(log.losses), "world_size": self.world,
+                 "validation": self.validation_history, "best_validation": self.best_validation,
+                 "lr": lr, "fe_lr": fe_lr, "lr_history": log.lr_history, "start_epoch": start_epoch}
         # the tree's side of the run (None / empty on synthetic tasks). ms_per_task is the step alone; data_wait_ms is the time
         # the loop was blocked in next() on the prefetcher, per task; wall_s covers both, validation and the optimizer steps
-        stored = sorted(prefetch.stored_sizes) if prefetch is not None else []
-        stats.update({"data_path": getattr(a, "data_path", None) if tree is not None else None, "decode": a.decode if tree else None,
-                      "decode_fallback_frames": prefetch.fallback_frames if prefetch is not None and a.decode == "device" else None,
-                      "stored_frame_size": [list(hw) for hw in stored], "frame_size": [a.frame_size, a.frame_size],
-                      "resample": a.resample if any(hw != (a.frame_size, a.frame_size) for hw in stored) else None,
-                      "train_task_type": a.train_task_type if tree is not None else None,
-                      "data_wait_ms": mean_ci(waits) if waits else None,
-                      "frames_per_task": mean_ci(task_frames) if task_frames else None, "wall_s": wall})
+        stats.update(self.ingest_stats(prefetch, tree))
+        stats.update({"data_path": a.data_path if tree else None, "train_task_type": a.train_task_type if tree else None,
+                      "data_wait_ms": mean_ci(log.wait_ms) if log.wait_ms else None,
+                      "frames_per_task": mean_ci(log.frames) if log.frames else None, "wall_s": wall})
         stats.update(self.annotation_stats("train"))
         stats["validation_annotations"] = self.annotation_stats("validation") if split_roots(a).get("validation") else None
         if self.rank == 0:
             print("train: loss %.5f | frame_acc %.2f %% | %.1f ms/task | %d tasks on this rank, %d GPU(s)"
-                  % (stats["loss"][0], 100 * stats["frame_acc"][0], stats["ms_per_task"][0], stats["num_tasks"],
-                     self.world))
-            if task_frames:
+                  % (stats["loss"][0], 100 * stats["frame_acc"][0], stats["ms_per_task"][0], stats["num_tasks"], self.world))
+            if log.frames:
                 print("train (%s): %.0f frames per task | waited %.1f (%.1f) ms per task for data (decode: %s, %d threads) | "
                       "%.2f tasks/s of wall time"
                       % ("%s, %s" % (a.data_path, a.train_task_type) if prefetch is not None else "tasks handed in",
-                         stats["frames_per_task"][0], *stats["data_wait_ms"], a.decode, a.num_workers, len(losses) / max(wall, 1e-9)))
+                         stats["frames_per_task"][0], *stats["data_wait_ms"], a.decode, a.num_workers,
+                         stats["num_tasks"] / max(wall, 1e-9)))
         return stats
 
     def save_checkpoint(self, epoch):
@@ -798,16 +879,14 @@ class Learner:
         the same parameters and optimizer state after a step). Written AFTER the epoch's validation - the reference writes it
         before - so that best_stats covers the epoch the file names and a resumed run takes the decisions of a straight one.
         The file is replaced atomically: an interruption during the write leaves the previous epoch's checkpoint."""
-        directory = getattr(self.args, "checkpoint_dir", None)
+        directory = self.args.checkpoint_dir
         if not directory or self.rank != 0:
             return
         os.makedirs(directory, exist_ok=True)
         path = os.path.join(directory, "checkpoint.pt")
-        torch.save({"epoch": epoch,
-                    "model_state_dict": {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
-                    "optimizer_state_dict": self.optimizer.state_dict(),
-                    "best_stats": {"best_validation": getattr(self, "best_validation", None),
-                                   "validation_history": getattr(self, "validation_history", None)}}, path + ".tmp")
+        torch.save({"epoch": epoch, "model_state_dict": host_state(self.model), "optimizer_state_dict": self.optimizer.state_dict(),
+                    "best_stats": {"best_validation": self.best_validation, "validation_history": self.validation_history}},
+                   path + ".tmp")
         os.replace(path + ".tmp", path)
 
     def load_checkpoint(self):
@@ -828,164 +907,138 @@ class Learner:
             print("resumed from %s: continuing at epoch %d of %d" % (path, epoch + 1, self.args.epochs))
         return epoch
 
-    def validate(self, epoch=0):
-        """The reference's validate() (single-step-learner.py:245-296) on held-out tasks - synthetic ones, or with
-        --data_path the validation split's: test mode, no grad,
-        personalise on the context clips, predict every target video on its frame history, per-video frame accuracy; the
-        model whose mean per-video accuracy beats the best so far (ValidationEvaluator.is_better, utils/eval_metrics.py:351-357:
-        strictly greater, starting from 0) is written to --save_best_model_path. Tasks are dealt to the ranks and the
-        per-video accuracies gathered, so every rank takes the same decision."""
-        a = self.args
-        self.model.set_test_mode(True)
-        accs = []
-        if split_roots(a).get("validation"):
-            # --data_path: --num_val_tasks tasks per user of ROOT/validation in the queue's unshuffled order, each run as the
-            # test loop runs a task. The sampling stream restarts with every call, so every epoch's model is scored on the
-            # same tasks and "strictly greater" compares like with like.
-            if getattr(self, "_validation_dataset", None) is None:
-                self._validation_dataset = self.build_dataset("validation")
-            dataset = self._validation_dataset
-            dataset.rng = split_rng(a, "validation", self.rank)
-            prefetch = self._prefetch(dataset, task_order(num_items(dataset), a.num_val_tasks)[self.rank::self.world], depth=3)
-            with torch.no_grad():
-                for task in prefetch:
-                    accs += self._run_tree_task(task, [], [])
-            prefetch.close()
-        else:
-            with torch.no_grad():
-                for t in odist.tasks_for_rank(a.num_val_tasks, self.rank, self.world):
-                    context_clips, context_labels, videos = self.make_task(20_000 + t)
-                    self.model.personalise(context_clips, self._labels_to_device(context_labels))
-                    for frames, labels in videos:
-                        logits = self.model.predict_video(frames)  # = predict(attach_frame_history(frames, clip_length))
-                        accs.append(frame_accuracy(logits.cpu(), labels))
-                    self.model._reset()
-        if self.world > 1:
-            import torch.distributed as dist
-            gathered = [None] * self.world
-            dist.all_gather_object(gathered, accs)
-            accs = [x for g in gathered for x in g]
-        stat = mean_ci(accs)
-        best = getattr(self, "best_validation", (0.0, 0.0))
-        better = stat[0] is not None and stat[0] > best[0]
-        if better:
-            self.best_validation = stat
-            if a.save_best_model_path and self.rank == 0:
-                torch.save({k: v.detach().cpu() for k, v in self.model.state_dict().items()}, a.save_best_model_path)
-        self.validation_history = getattr(self, "validation_history", []) + [(epoch, stat[0], better)]
-        if self.rank == 0:
-            print("validation (epoch %d): per-video frame_acc %.2f (%.2f) %% over %d videos%s"
-                  % (epoch, 100 * _shown(stat)[0], 100 * stat[1], len(accs), " - best so far, model saved" if better else ""))
-        return stat
-
+    # ---- the evaluation loop of test and validation (reference single-step-learner.py:245-375) ----------------------------
     def _labels_to_device(self, labels):
         """the reference's unpack_task (data/utils.py:42-43) for the context labels; the label set rides along from the host copy"""
         return unpack_task({"context_labels": labels, "target_labels": None, "context_clips": None, "target_clips": None},
                            self.device)[2]
 
-    def _personalise_tree_task(self, task):
-        self.model.personalise(task["context_clips"], task["context_labels"])
+    def _personalise(self, context_clips, context_labels):
+        self.model.personalise(context_clips, context_labels)
 
-    def _predict_tree_video(self, frames):
-        return self.model.predict_video(frames)  # = predict(attach_frame_history(frames, clip_length))
+    def _predict_video(self, frames):
+        # = predict(attach_frame_history(frames, clip_length)) of the reference loop, frames not duplicated
+        return self.model.predict_video(frames)
 
-    def _run_tree_task(self, task, personalise_ms, inference_ms, metrics=None):
-        """One staged test-mode task as the reference's test and validation loops run it (single-step-learner.py:262-281,
-        316-341): personalise on the context clips, then per target VIDEO predict on its frame history. Appends to the two
-        timer lists, feeds `metrics` (OrbitMetrics, begin_task already called) and returns the per-video frame accuracies."""
-        video_labels = task["target_labels"].cpu() if metrics is not None else None
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        self._personalise_tree_task(task)
-        torch.cuda.synchronize()
-        personalise_ms.append(1e3 * (time.perf_counter() - t0))
-        accs = []
-        target = task["target_clips"][:, 0]  # [M,3,H,W]: the videos' frames, in video order
-        for lo, hi in task["target_videos"]:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            logits = self._predict_tree_video(target[lo:hi])
-            torch.cuda.synchronize()
-            inference_ms.append(1e3 * (time.perf_counter() - t0) / float((hi - lo) * self.model.clip_length))
-            accs.append(frame_accuracy(logits, task["target_labels"][lo:hi]))
-            if metrics is not None:
-                paths = task["target_paths"][len(accs) - 1] if task.get("target_paths") is not None else None
-                metrics.append_video(logits, video_labels[lo], paths)
-        self.model._reset()
-        return accs
-
-    def test_directory(self):
-        """The reference's test loop (single-step-learner.py:298-375) over a JPEG directory: one task per user, personalise
-        on the context clips, then per target VIDEO predict on its frame history, frame accuracy per video averaged per
-        task. Decode, 8-bit upload and normalisation of task i+1 overlap the extractor work of task i. A tree stored at
-        another size than --frame_size is resized to it in the normalisation launch (--resample)."""
-        a = self.args
-        root = split_roots(a)["test"]  # --data_root, or --data_path's <--test_set> split
+    def _evaluate(self, tasks, indices=None, metrics=None):
+        """The reference's test and validation loops (single-step-learner.py:262-281, 316-341) over an iterable of test-mode
+        tasks - a TaskPrefetcher's on the device or make_task's on the host, the loop does not ask: per task personalise on the
+        context clips, then per target VIDEO (task["target_videos"]: row ranges of target_clips [M,1,3,H,W]) predict on its frame
+        history, frame accuracy, _reset. metrics (OrbitMetrics) is fed every video; indices[k] is the k-th task's global index.
+        -> per task {"accs": per-video frame accuracies, "personalise_ms", "inference_ms": per video and frame, "frames"}"""
         self.model.set_test_mode(True)
-        # the reference's test queue (data/queues.py:44-46 -> data/datasets.py; pinned by fixture G14): every user's objects,
-        # all their videos, context clips sampled uniformly, 200 random clips per target video
+        records = []
+        with torch.no_grad():
+            for k, task in enumerate(tasks):
+                if metrics is not None:
+                    metrics.begin_task(indices[k], task["user"], task.get("object_list"))
+                # the labels' copies - the context set's to the device, the frames' to the host - stay outside the timers
+                context_labels, labels = self._labels_to_device(task["context_labels"]), task["target_labels"].cpu()
+                _, personalise_ms = timed_ms(self._personalise, task["context_clips"], context_labels)
+                accs, inference_ms = [], []
+                target = task["target_clips"][:, 0]  # [M,3,H,W]: the videos' frames, in video order
+                for v, (lo, hi) in enumerate(task["target_videos"]):
+                    logits, ms = timed_ms(self._predict_video, target[lo:hi])
+                    inference_ms.append(ms / float((hi - lo) * self.model.clip_length))
+                    accs.append(frame_accuracy(logits.cpu(), labels[lo:hi]))
+                    if metrics is not None:
+                        # one label per frame: a tree's video repeats its object's label - one run of labels, which is what
+                        # its single label gives (TestEvaluator.append_video) - and a synthetic "video" mixes objects
+                        paths = task["target_paths"][v] if task.get("target_paths") is not None else None
+                        metrics.append_video(logits, labels[lo:hi], paths)
+                self.model._reset()
+                records.append({"accs": accs, "personalise_ms": personalise_ms, "inference_ms": inference_ms,
+                                "frames": sum(hi - lo for lo, hi in task["target_videos"])})
+        return records
+
+    def validate(self, epoch=0):
+        """The reference's validate() (single-step-learner.py:245-296) on held-out tasks - synthetic ones, or with
+        --data_path the validation split's - through the evaluation loop; the
+        model whose mean per-video accuracy beats the best so far (ValidationEvaluator.is_better, utils/eval_metrics.py:351-357:
+        strictly greater, starting from 0) is written to --save_best_model_path. Tasks are dealt to the ranks and the
+        per-video accuracies gathered, so every rank takes the same decision."""
+        a = self.args
+        prefetch = None
+        if split_roots(a).get("validation"):
+            # --data_path: --num_val_tasks tasks per user of ROOT/validation in the queue's unshuffled order, each run as the
+            # test loop runs a task. The sampling stream restarts with every call, so every epoch's model is scored on the
+            # same tasks and "strictly greater" compares like with like.
+            if self._validation_dataset is None:
+                self._validation_dataset = self.build_dataset("validation")
+            dataset = self._validation_dataset
+            dataset.rng = split_rng(a, "validation", self.rank)
+            order = task_order(num_items(dataset), a.num_val_tasks)
+            tasks = prefetch = self._prefetch(dataset, order[self.rank::self.world], depth=3)
+        else:
+            tasks = (self.make_task(20_000 + t) for t in odist.tasks_for_rank(a.num_val_tasks, self.rank, self.world))
+        accs, = gather_lists(self.world, [x for record in self._evaluate(tasks) for x in record["accs"]])
+        if prefetch is not None:
+            prefetch.close()
+        stat = mean_ci(accs)
+        better = stat[0] is not None and stat[0] > (self.best_validation or (0.0, 0.0))[0]
+        if better:
+            self.best_validation = stat
+            if a.save_best_model_path and self.rank == 0:
+                torch.save(host_state(self.model), a.save_best_model_path)
+        self.validation_history = (self.validation_history or []) + [(epoch, stat[0], better)]
+        if self.rank == 0:
+            print("validation (epoch %d): per-video frame_acc %.2f (%.2f) %% over %d videos%s"
+                  % (epoch, 100 * _shown(stat)[0], 100 * stat[1], len(accs), " - best so far, model saved" if better else ""))
+        return stat
+
+    def _test_prefetcher(self, root):
+        """-> (the global indices of this rank's test tasks on the tree, the prefetcher that yields them). The reference's test
+        queue (data/queues.py:44-46 -> data/datasets.py; pinned by fixture G14): every user's objects, all their videos, context
+        clips sampled uniformly, 200 random clips per target video. Decode, 8-bit upload and normalisation of task i+1 overlap
+        the extractor work of task i; a tree stored at another size than --frame_size is resized to it in the normalisation
+        launch (--resample)."""
+        a = self.args
         dataset = self.build_dataset("test")
         # TaskSampler order (data/samplers.py:24-30, no shuffle): user 0 x num_tasks, user 1 x num_tasks, ...; dealt to ranks
         # - EVERY user x num_test_tasks_per_user, as the reference's loop visits them (single-step-learner.py:313-314). An
         # optional total cap (--max_test_tasks; default none) is applied BEFORE the tasks are dealt, so the evaluated set does
         # not depend on the world size, and is announced when it truncates the user list (ADVICE r4)
         order = [u for u in range(len(dataset)) for _ in range(a.num_test_tasks_per_user)]
-        cap = getattr(a, "max_test_tasks", None)
-        if cap is not None and cap < len(order):
+        if a.max_test_tasks is not None and a.max_test_tasks < len(order):
             if self.rank == 0:
                 print("test (%s): --max_test_tasks %d truncates %d tasks (%d users x %d) - NOT the full test set"
-                      % (root, cap, len(order), len(dataset), a.num_test_tasks_per_user))
-            order = order[:cap]
-        task_acc, personalise_ms, inference_ms, frames = [], [], [], 0
-        save_dir = getattr(a, "save_predictions", None)
-        metrics = OrbitMetrics(save_dir)
-        mine = list(range(len(order)))[self.rank::self.world]  # global indices of this rank's tasks
-        t_all = time.perf_counter()
-        prefetch = self._prefetch(dataset, order[self.rank::self.world], depth=3)
-        with torch.no_grad():
-            for k, task in enumerate(prefetch):
-                metrics.begin_task(mine[k], task["user"], task.get("object_list"))
-                task_acc.append(float(np.mean(self._run_tree_task(task, personalise_ms, inference_ms, metrics))))
-                frames += sum(hi - lo for lo, hi in task["target_videos"])
-        prefetch.close()
-        self._close_decode_pool()
+                      % (root, a.max_test_tasks, len(order), len(dataset), a.num_test_tasks_per_user))
+            order = order[:a.max_test_tasks]
+        return range(len(order))[self.rank::self.world], self._prefetch(dataset, order[self.rank::self.world], depth=3)
+
+    def test(self):
+        """The reference's test loop (single-step-learner.py:298-375) through the evaluation loop, on --num_test_tasks synthetic
+        tasks or on a tree (--data_root, or --data_path's <--test_set> split: one task per user and --num_test_tasks_per_user):
+        frame accuracy per video averaged per task, the two timers and the ORBIT metrics, gathered from all ranks."""
+        a = self.args
+        root = split_roots(a).get("test")
+        save_dir = a.save_predictions if root else None
+        metrics, prefetch, t_all = OrbitMetrics(save_dir), None, time.perf_counter()
+        if root:
+            indices, prefetch = self._test_prefetcher(root)
+            tasks = prefetch
+        else:
+            # (synthetic tasks live on the host and are uploaded per mini-batch: in its default mode, overlap_query = "auto", the
+            # recogniser runs the query pass of predict() on its own stream for such clips)
+            indices = odist.tasks_for_rank(a.num_test_tasks, self.rank, self.world)
+            tasks = (self.make_task(t) for t in indices)
+        records = self._evaluate(tasks, indices, metrics)
+        if prefetch is not None:
+            prefetch.close()
+            self._close_decode_pool()
         wall = time.perf_counter() - t_all
-        if self.world > 1:  # per-task results of every rank, as test() gathers them
-            import torch.distributed as dist
-            gathered = [None] * self.world
-            dist.all_gather_object(gathered, (task_acc, personalise_ms, inference_ms, frames))
-            task_acc = [x for g in gathered for x in g[0]]
-            personalise_ms = [x for g in gathered for x in g[1]]
-            inference_ms = [x for g in gathered for x in g[2]]
-            frames = sum(g[3] for g in gathered)
+        records, = gather_lists(self.world, records)  # per-task results of every rank
         metrics = metrics.gather(self.world, with_predictions=bool(save_dir))
-        stored = sorted(prefetch.stored_sizes)  # (this rank's tasks)
-        stats = {"frame_acc": mean_ci(task_acc), "personalise_ms": mean_ci(personalise_ms),
-                 "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world,
-                 "target_frames": frames, "wall_s": wall, "data_root": root, "orbit_metrics": metrics.report(),
-                 "stored_frame_size": [list(hw) for hw in stored], "frame_size": [a.frame_size, a.frame_size],
-                 "resample": a.resample if any(hw != (a.frame_size, a.frame_size) for hw in stored) else None,
-                 "decode": a.decode, "decode_fallback_frames": prefetch.fallback_frames if a.decode == "device" else None}
-        stats.update(self.annotation_stats("test"))
+        stats = {"frame_acc": mean_ci([float(np.mean(r["accs"])) for r in records]),
+                 "personalise_ms": mean_ci([r["personalise_ms"] for r in records]),
+                 "inference_ms_per_frame": mean_ci([ms for r in records for ms in r["inference_ms"]]),
+                 "num_tasks": len(records), "world_size": self.world, "orbit_metrics": metrics.report()}
+        if prefetch is not None:
+            stats.update({"target_frames": sum(r["frames"] for r in records), "wall_s": wall, "data_root": root})
+            stats.update(self.ingest_stats(prefetch, root))
+            stats.update(self.annotation_stats("test"))
         if self.rank == 0:
-            print("test (%s): frames stored at %s, extractor ran at %dx%d%s"
-                  % (root, ", ".join("%dx%d" % hw for hw in stored) or "-", a.frame_size, a.frame_size,
-                     " (resized on the GPU, %s)" % a.resample if stats["resample"] else ""))
-            if stats["index"]["dropped"] is not None:
-                kept, dropped = stats["index"]["kept"], stats["index"]["dropped"]
-                print("test (%s): context frames filtered by %s, target frames by %s: kept %d users, %d objects, %d + %d videos, "
-                      "%d + %d frames; dropped %d users, %d objects, %d + %d videos, %d + %d frames"
-                      % (root, stats["filter_context"] or "-", stats["filter_target"] or "-",
-                         *(d[k] for d in (kept, dropped) for k in ("users", "objects", "context_videos", "target_videos",
-                                                                   "context_frames", "target_frames"))))
-            if a.decode == "device":
-                print("test (%s): JPEG decode on the GPU, %d frames; %d decoded by PIL instead (out of scope or damaged)"
-                      % (root, prefetch.device_frames, prefetch.fallback_frames))
-            print("test (%s): frame_acc %.2f (%.2f) %% | time to personalise %.2f (%.2f) ms | inference %.4f (%.4f) ms/frame "
-                  "| %d tasks, %d target frames in %.1f s incl. JPEG decode (%d threads)"
-                  % (root, 100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1], *_shown(stats["personalise_ms"]),
-                     *_shown(stats["inference_ms_per_frame"]), stats["num_tasks"], frames, wall, a.num_workers))
-            print(OrbitMetrics.line(stats["orbit_metrics"]))
+            self._report_test(stats, prefetch)
             if save_dir and stats["orbit_metrics"] is not None:
                 metrics.evaluator.save()
                 print("predictions written to %s" % metrics.evaluator.json_results_path)
@@ -994,78 +1047,49 @@ class Learner:
                     json.dump(stats, f)
         return stats
 
-    def test(self):
+    def _report_words(self):
+        """what the report line calls the loop, and a note on its personalise timer"""
+        return "test", ""
+
+    def _report_test(self, stats, prefetch):
         a = self.args
-        if split_roots(a).get("test"):
-            return self.test_directory()
-        self.model.set_test_mode(True)
-        # (synthetic tasks live on the host and are uploaded per mini-batch: in its default mode, overlap_query = "auto", the
-        # recogniser runs the query pass of predict() on its own stream for such clips)
-        task_acc, personalise_ms, inference_ms = [], [], []
-        metrics = OrbitMetrics()
-        with torch.no_grad():
-            for t in odist.tasks_for_rank(a.num_test_tasks, self.rank, self.world):
-                context_clips, context_labels, videos = self.make_task(t)
-                context_labels = self._labels_to_device(context_labels)
-                metrics.begin_task(t, t)  # synthetic mode: one user is one task
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                self.model.personalise(context_clips, context_labels)
-                torch.cuda.synchronize()
-                personalise_ms.append(1e3 * (time.perf_counter() - t0))
-                accs = []
-                for frames, labels in videos:
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    # = predict(attach_frame_history(frames, clip_length)) of the reference loop, frames not duplicated
-                    logits = self.model.predict_video(frames)
-                    torch.cuda.synchronize()
-                    inference_ms.append(1e3 * (time.perf_counter() - t0) / float(len(frames) * self.model.clip_length))
-                    accs.append(frame_accuracy(logits.cpu(), labels))
-                    metrics.append_video(logits, labels)  # (a synthetic "video" mixes objects: one label per frame)
-                task_acc.append(float(np.mean(accs)))
-                self.model._reset()
-        if self.world > 1:
-            import torch.distributed as dist
-            gathered = [None] * self.world
-            dist.all_gather_object(gathered, (task_acc, personalise_ms, inference_ms))
-            task_acc = [x for g in gathered for x in g[0]]
-            personalise_ms = [x for g in gathered for x in g[1]]
-            inference_ms = [x for g in gathered for x in g[2]]
-        metrics = metrics.gather(self.world, with_predictions=False)
-        stats = {"frame_acc": mean_ci(task_acc), "personalise_ms": mean_ci(personalise_ms),
-                 "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world,
-                 "orbit_metrics": metrics.report()}
-        if self.rank == 0:
-            print("test: frame_acc %.2f (%.2f) %% | time to personalise %.2f (%.2f) ms | inference %.4f (%.4f) ms/frame "
-                  "| %d tasks on %d GPU(s)" % (100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1],
-                                               *_shown(stats["personalise_ms"]), *_shown(stats["inference_ms_per_frame"]),
-                                               stats["num_tasks"], self.world))
-            print(OrbitMetrics.line(stats["orbit_metrics"]))
-            if a.results_path:
-                with open(a.results_path, "w") as f:
-                    json.dump(stats, f)
-        return stats
+        name, note = self._report_words()
+        if prefetch is not None:
+            name = "%s (%s)" % (name, stats["data_root"])
+            print("%s: frames stored at %s, extractor ran at %dx%d%s"
+                  % (name, ", ".join("%dx%d" % tuple(hw) for hw in stats["stored_frame_size"]) or "-", a.frame_size, a.frame_size,
+                     " (resized on the GPU, %s)" % a.resample if stats["resample"] else ""))
+            if stats["index"]["dropped"] is not None:
+                kept, dropped = stats["index"]["kept"], stats["index"]["dropped"]
+                print("%s: context frames filtered by %s, target frames by %s: kept %d users, %d objects, %d + %d videos, "
+                      "%d + %d frames; dropped %d users, %d objects, %d + %d videos, %d + %d frames"
+                      % (name, stats["filter_context"] or "-", stats["filter_target"] or "-",
+                         *(d[k] for d in (kept, dropped) for k in ("users", "objects", "context_videos", "target_videos",
+                                                                   "context_frames", "target_frames"))))
+            if a.decode == "device":
+                print("%s: JPEG decode on the GPU, %d frames; %d decoded by PIL instead (out of scope or damaged)"
+                      % (name, prefetch.device_frames, prefetch.fallback_frames))
+        print("%s: frame_acc %.2f (%.2f) %% | time to personalise %.2f (%.2f) ms%s | inference %.4f (%.4f) ms/frame | %d tasks%s"
+              % (name, 100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1], *_shown(stats["personalise_ms"]),
+                 note, *_shown(stats["inference_ms_per_frame"]), stats["num_tasks"],
+                 " on %d GPU(s)" % self.world if prefetch is None else ", %d target frames in %.1f s incl. JPEG decode (%d threads)"
+                 % (stats["target_frames"], stats["wall_s"], a.num_workers)))
+        print(OrbitMetrics.line(stats["orbit_metrics"]))
 
 
 class MultiStepLearner(Learner):
     """Counterpart of the reference's multi-step-learner.py (FineTuner, test only): per task a fresh copy of the model is
     personalised by `personalize_num_grad_steps` optimizer steps on the context set, then evaluated per target video
-    (multi-step-learner.py:132-196)."""
+    (multi-step-learner.py:132-196). The evaluation loop is the learner's, with the finetuner's two steps swapped in."""
+    strict_load = False
+
+    def new_recogniser(self):
+        a = self.args
+        return MultiStepFewShotRecogniser(a.feature_extractor, a.adapt_features, a.classifier, a.clip_length, a.batch_size,
+                                          a.learn_extractor, a.logit_scale)
 
     def init_model(self):
-        a = self.args
-        from .model.few_shot_recognisers import MultiStepFewShotRecogniser
-        self.model = MultiStepFewShotRecogniser(a.feature_extractor, a.adapt_features, a.classifier, a.clip_length,
-                                                a.batch_size, a.learn_extractor, a.logit_scale)
-        if a.model_path:
-            self.model.load_state_dict(torch.load(a.model_path, map_location="cpu"), strict=False)
-        else:
-            synthetic.init_parameters_(self.model, seed=a.seed,
-                                       film_strength=0.02 if a.feature_extractor == "efficientnet_b0" else 0.1)
-        self._opt_in_native_backward()
-        self.model._set_device(self.device)
-        self.model._send_to_device()
+        super().init_model()
         self.base_state = {k: v.clone() for k, v in self.model.state_dict().items()}
 
     def run(self):
@@ -1077,61 +1101,20 @@ class MultiStepLearner(Learner):
                 "extractor_lr_scale": a.personalize_extractor_lr_scale, "loss_fn": cross_entropy,
                 "optimizer": a.personalize_optimizer, "momentum": a.personalize_momentum,
                 "weight_decay": a.personalize_weight_decay, "betas": tuple(a.personalize_betas),
-                "epsilon": a.personalize_epsilon, "native_optimizer": bool(getattr(a, "native_optimizer", False))}
+                "epsilon": a.personalize_epsilon, "native_optimizer": bool(a.native_optimizer)}
 
-    # the tree loop (Learner.test_directory: --data_root, or --data_path's test split) with the finetuner's two steps
-    def _personalise_tree_task(self, task):
+    def _personalise(self, context_clips, context_labels):
         # every task starts from the initial parameters (multi-step-learner.py:153-154); the gradient steps need autograd
         # inside the loop's no_grad
         self.model.load_state_dict(self.base_state, strict=False)
         with torch.enable_grad():
-            self.model.personalise(task["context_clips"], task["context_labels"], self.learning_args())
+            self.model.personalise(context_clips, context_labels, self.learning_args())
 
-    def _predict_tree_video(self, frames):
+    def _predict_video(self, frames):
         return self.model.predict(attach_frame_history(frames, self.args.clip_length))
 
-    def test(self):
-        a = self.args
-        if split_roots(a).get("test"):
-            return self.test_directory()
-        learning_args = self.learning_args()
-        self.model.set_test_mode(True)
-        task_acc, personalise_ms, inference_ms = [], [], []
-        metrics = OrbitMetrics()
-        for t in odist.tasks_for_rank(a.num_test_tasks, self.rank, self.world):
-            context_clips, context_labels, videos = self.make_task(t)
-            metrics.begin_task(t, t)  # synthetic mode: one user is one task
-            # the finetuner starts every task from the initial parameters (multi-step-learner.py:153-154)
-            self.model.load_state_dict(self.base_state, strict=False)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            self.model.personalise(context_clips, context_labels.to(self.device), dict(learning_args))
-            torch.cuda.synchronize()
-            personalise_ms.append(1e3 * (time.perf_counter() - t0))
-            accs = []
-            with torch.no_grad():
-                for frames, labels in videos:
-                    clips = attach_frame_history(frames, a.clip_length)
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    logits = self.model.predict(clips)
-                    torch.cuda.synchronize()
-                    inference_ms.append(1e3 * (time.perf_counter() - t0) / float(len(clips) * self.model.clip_length))
-                    accs.append(frame_accuracy(logits.cpu(), labels))
-                    metrics.append_video(logits, labels)  # (a synthetic "video" mixes objects: one label per frame)
-            task_acc.append(float(np.mean(accs)))
-            self.model._reset()
-        stats = {"frame_acc": mean_ci(task_acc), "personalise_ms": mean_ci(personalise_ms),
-                 "inference_ms_per_frame": mean_ci(inference_ms), "num_tasks": len(task_acc), "world_size": self.world,
-                 "orbit_metrics": metrics.report()}
-        if self.rank == 0:
-            print("finetuner test: frame_acc %.2f (%.2f) %% | time to personalise %.2f (%.2f) ms (%d steps) | inference "
-                  "%.4f (%.4f) ms/frame | %d tasks" % (100 * _shown(stats["frame_acc"])[0], 100 * stats["frame_acc"][1],
-                                                       *_shown(stats["personalise_ms"]), a.personalize_num_grad_steps,
-                                                       *_shown(stats["inference_ms_per_frame"]), stats["num_tasks"]))
-            print(OrbitMetrics.line(stats["orbit_metrics"]))
-        return stats
-
+    def _report_words(self):
+        return "finetuner test", " (%d steps)" % self.args.personalize_num_grad_steps
 
 def build_multistep_parser():
     p = build_parser()

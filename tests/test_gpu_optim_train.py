@@ -159,11 +159,12 @@ def test_finetuner_personalise_with_the_native_step(device, lib):
                                                                     "0.2", "--personalize_betas", "0.9", "0.98"] + extra)
         L = learner.MultiStepLearner(args)
         assert L.learning_args()["native_optimizer"] is bool(extra)
-        context_clips, context_labels, videos = L.make_task(0)
+        task = L.make_task(0)
+        lo, hi = task["target_videos"][0]
         L.model.set_test_mode(True)
-        L.model.personalise(context_clips, context_labels.to(L.device), dict(L.learning_args(), fused_optimizer=fused))
+        L.model.personalise(task["context_clips"], task["context_labels"].to(L.device), dict(L.learning_args(), fused_optimizer=fused))
         with torch.no_grad():
-            out = L.model.predict(attach_frame_history(videos[0][0], 1)).detach().cpu()
+            out = L.model.predict(attach_frame_history(task["target_clips"][lo:hi, 0], 1)).detach().cpu()
         L.model._reset()
         return out
 
