@@ -1,0 +1,206 @@
+"""CPU side of tests/test_gpu_conv_forms.py: what that file assumes about its own table and references, checked without a GPU.
+
+  * the literal profiler rows of the table contain every instantiation the file is there to reach; both batch sizes occur, no
+    map is square, every tile form gets its ragged row counts and channel counts, stride-2 cases pad top and left differently
+    (but for the ones that cannot, which are listed by name);
+  * every geometry is consistent: Ho x Wo is what the padded convolution produces;
+  * one_sign: dropping the smallest 8-deep K-group (in the kernel's own k order) moves an output by at least 100 gates;
+  * normal: every ReLU / SiLU case has pre-activations of both signs; the pool2 `neg` cases have none above zero;
+  * the stem_fast shapes have 64-row tiles on both sides of the interior fast path, by enumeration of (b, ho, wo);
+  * the K-tile ranges quoted for the split-K cases follow from Cin, KH * KW and BK by arithmetic.
+Which tile a shape gets is NOT restated here: the GPU file's profiler assertion is the check of the launch rules."""
+import pytest
+import torch
+
+import test_gpu_conv_forms as T
+
+CASES = {c["name"]: c for c in T.CASES}
+
+
+def parse(expect):
+    """(BM, BN, BK, layout, frozenset of the remaining fields) of a profiler row."""
+    assert expect.startswith("conv_igemm<") and expect.endswith(">"), expect
+    f = expect[len("conv_igemm<"):-1].split(",")
+    return int(f[0]), int(f[1]), int(f[2]), f[3], frozenset(f[4:])
+
+
+def rows_of(case):
+    B, Cin, H, W, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo = case["geom"]
+    return B * (Ho // 2) * (Wo // 2) * 4 if "pool2" in case["flags"] else B * Ho * Wo
+
+
+def test_table_reaches_every_instantiation():
+    names = {c["expect"] for c in T.CASES}
+    need = ["conv_igemm<%s,%d,nhwc%s>" % (tile, bk, tail)
+            for tile in ("64,64", "128,32") for bk in (32, 16, 8) for tail in ("", ",pw")]                  # KxK and pointwise
+    need += ["conv_igemm<32,32,32,nhwc%s,k4>" % mid for mid in ("", ",pw", ",gate,pw")]                       # four K-waves
+    need += ["conv_igemm<64,64,%d,nhwc,gate,pw>" % bk for bk in (32, 16, 8)]
+    need += ["conv_igemm<128,32,16,nhwc,gate,pw>", "conv_igemm<64,64,8,nhwc,gate>"]
+    need += ["conv_igemm<64,64,32,nhwc,pool2>", "conv_igemm<128,32,32,nhwc,pool2>"]
+    need += ["conv_igemm<64,64,32,nchw>", "conv_igemm<128,32,32,nchw>", "conv_igemm<64,64,32,nchw,pool2>"]
+    need += ["conv_igemm<64,64,%d,nhwc,splitk>" % bk for bk in (32, 16, 8)] + ["conv_igemm<64,64,32,nhwc,gate,pw,splitk>"]
+    assert not [n for n in need if n not in names]
+    assert len(T.CASE_IDS) == len(set(T.CASE_IDS))
+    by = lambda pred: [c for c in T.CASES if pred(c)]  # noqa: E731
+    # the 16-wide K-tile override names BK 16 although Cin % 32 == 0
+    assert all(c["geom"][1] % 32 == 0 and parse(c["expect"])[2] == 16 for c in by(lambda c: "override" in c["name"]))
+    assert len(by(lambda c: "override" in c["name"])) == 2
+    # cin_pad > Cin: 12 and 20 channels, pointwise (plain and gated) and 3x3
+    assert {(c["geom"][1], "pw" in parse(c["expect"])[4]) for c in by(lambda c: c["geom"][1] % 8 == 4)} == \
+        {(12, True), (20, True), (12, False), (20, False)}
+    assert any(c["geom"][1] == 20 and {"gate", "pw"} <= parse(c["expect"])[4] for c in T.CASES)
+    # conv_tile: the heuristic and each forced tiling; 128x32 by Cout <= 32, by Cout = 80 and forced; ,k4 by the rule and forced
+    assert {c["opts"].get("conv_tile", 0) for c in T.CASES} == {0, 3, 4, 6}
+    k3 = by(lambda c: c["geom"][5:7] == (3, 3) and parse(c["expect"])[3:] == ("nhwc", frozenset()))
+    assert {(c["geom"][4], c["opts"].get("conv_tile", 0)) for c in k3 if parse(c["expect"])[:2] == (128, 32)} >= {(4, 0), (80, 0), (36, 4)}
+    k4 = by(lambda c: "k4" in parse(c["expect"])[4] and c["geom"][5:7] == (3, 3))
+    assert {c["opts"].get("conv_tile", 0) for c in k4} == {0, 6}
+    assert all(c["opts"].get("conv_splitk") == 0 for c in k4 if c["opts"].get("conv_tile", 0) == 0)
+    # pool2 with all-negative pre-activations under ReLU and act = 0; 5x5 / 2; KH != KW both ways; stride-2 pointwise on 7x9
+    assert {c["act"] for c in by(lambda c: "neg" in c["flags"])} == {0, T.RELU}
+    assert any(c["geom"][5:8] == (5, 5, 2) for c in T.CASES)
+    assert {c["geom"][5:7] for c in T.CASES} >= {(3, 1), (1, 3), (7, 7), (5, 5), (1, 1), (3, 3)}
+    assert any(c["geom"][5:8] == (1, 1, 2) and c["geom"][2:4] == (7, 9) for c in T.CASES)
+    # split-K: the reduce epilogue with scale only, shift only, residual + ReLU, SiLU
+    sk = [c["flags"] - {"gate"} for c in by(lambda c: "splitk" in parse(c["expect"])[4])]
+    assert {"scale"} in sk and {"shift"} in sk and {"scale", "shift", "res", "relu"} in sk and {"scale", "shift", "silu"} in sk
+    assert set(T.SPLITK_RANGES) == {c["name"] for c in by(lambda c: "splitk" in parse(c["expect"])[4])}
+    # statistics: every conv_tile value, a gated pointwise case, ragged M and Cout
+    assert {c[4] for c in T.STATS_CASES} == {0, 3, 4, 6} and any(c[2] for c in T.STATS_CASES)
+    assert all((c[1][0] * c[1][10] * c[1][11]) % c[6] != 0 for c in T.STATS_CASES)
+    assert any(c[1][4] % 32 != 0 for c in T.STATS_CASES)
+    assert all(parse(c[5])[0] == c[6] for c in T.STATS_CASES)
+
+
+def test_shapes_are_ragged_in_rows_and_columns_on_every_tile_form():
+    assert {c["geom"][0] for c in T.CASES} >= {1, 3}
+    assert all(c["geom"][2] != c["geom"][3] for c in T.CASES)  # no square map
+    for form, BM in (("64x64", 64), ("128x32", 128), ("32x32,k4", 32)):
+        mine = [c for c in T.CASES if T.form_of(c["expect"]) == form]
+        M = {rows_of(c) for c in mine}
+        assert any(m > BM and m % BM == 1 for m in M) and any(m < 32 for m in M), (form, M)
+        assert {4, 36, 68} <= {c["geom"][4] for c in mine}, form
+        assert {1, 3} <= {c["geom"][0] for c in mine}, form
+    for c in T.CASES:
+        B, Cin, H, W, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo = c["geom"]
+        if stride == 2 and c["name"] not in T.SYMMETRIC_STRIDE2:
+            assert H % 2 == 0 and W % 2 == 1 and pad_t != pad_l, c["name"]
+        if c["name"] in T.SYMMETRIC_STRIDE2:
+            assert stride == 2 and pad_t == pad_l, c["name"]
+
+
+@pytest.mark.parametrize("geom", [c["geom"] for c in T.CASES] + [c[1] for c in T.STATS_CASES],
+                         ids=T.CASE_IDS + [c[0] for c in T.STATS_CASES])
+def test_geometry_is_consistent(geom):
+    """Ho x Wo is what the convolution of the padded map produces: the trailing padding the reference adds is between 0 and K - 1."""
+    B, Cin, H, W, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo = geom
+    for size, K, lead, out in ((H, KH, pad_t, Ho), (W, KW, pad_l, Wo)):
+        trail = (out - 1) * stride + K - size - lead
+        assert 0 <= trail <= K - 1 and 0 <= lead <= K - 1 and (size + lead + trail - K) // stride + 1 == out
+        assert (out - 1) * stride - lead < size  # the last output's window starts inside the map
+    assert Cout % 4 == 0 and (Cin % 4 == 0 or Cin == 3)
+
+
+def k_groups(case):
+    """The 8-deep K-groups of the kernel's own k order as lists of (kh, kw, ci): k = (kh * KW + kw) * cin_pad + ci on the NHWC
+    path (cin_pad = Cin rounded up to BK), (kh * KW + kw) * Cin + ci on the stem path; padding entries are left out."""
+    B, Cin, H, W, Cout, KH, KW = case["geom"][:7]
+    BK = parse(case["expect"])[2]
+    per = Cin if "nchw" in case["flags"] else -(-Cin // BK) * BK
+    ks = [(tap // KW, tap % KW, ci) if ci < Cin else None for tap in range(KH * KW) for ci in range(per)]
+    groups = [[k for k in ks[i:i + 8] if k is not None] for i in range(0, len(ks), 8)]
+    return [g for g in groups if g]
+
+
+@pytest.mark.parametrize("case", [c for c in T.CASES if c["name"] != "pool_neg_relu"],
+                         ids=[n for n in T.CASE_IDS if n != "pool_neg_relu"])
+def test_one_sign_margin(case):
+    """Without any one K-group, every output that the group reaches moves by at least 100 gates (pool_neg_relu is left out: its
+    outputs are the exact zeros of a ReLU over negative pre-activations; pool_neg_act0 is the same layer without the ReLU)."""
+    geom, flags, act = case["geom"], case["flags"], case["act"]
+    t = T.conv_inputs(case["name"], geom, flags, "one_sign")
+    ref64 = T.reference(geom, flags, act, t, torch.float64)
+    _, tol = T.tolerance(ref64, T.reference(geom, flags, act, t, torch.float32))
+    groups = k_groups(case)
+    assert sum(len(g) for g in groups) == geom[1] * geom[5] * geom[6]
+    smallest = float("inf")
+    for g in groups:
+        w = t["w"].double().clone()
+        for kh, kw, ci in g:
+            w[:, ci, kh, kw] = 0.0
+        diff = (T.reference(geom, flags, act, t, torch.float64, w=w) - ref64).abs()
+        assert (diff > 0).any()
+        smallest = min(smallest, diff[diff > 0].min().item())  # (exact zeros: the group's taps all lie in the padding there)
+    assert smallest >= 100 * tol, (case["name"], smallest, tol)
+
+
+@pytest.mark.parametrize("case", [c for c in T.CASES if c["act"]], ids=[c["name"] for c in T.CASES if c["act"]])
+def test_activations_see_both_signs(case):
+    geom, flags = case["geom"], case["flags"] - {"pool2"}
+    if "neg" in case["flags"]:
+        pre = T.reference(geom, flags, 0, T.conv_inputs(case["name"], geom, case["flags"], "one_sign"), torch.float64)
+        assert bool((pre < -0.5).all())
+        return
+    pre = T.reference(geom, flags, 0, T.conv_inputs(case["name"], geom, case["flags"], "normal"), torch.float64)
+    assert (pre > 0).double().mean() > 0.1 and (pre < 0).double().mean() > 0.1
+
+
+def test_pool2_negative_reference_is_negative_everywhere():
+    c = CASES["pool_neg_act0"]
+    t = T.conv_inputs(c["name"], c["geom"], c["flags"], "one_sign")
+    assert T.families(c) == ("one_sign",) and bool((T.reference(c["geom"], c["flags"], 0, t, torch.float64) < 0).all())
+    r = CASES["pool_neg_relu"]
+    assert r["geom"] == c["geom"] and r["flags"] == c["flags"] | {"relu"}
+    t = T.conv_inputs(r["name"], r["geom"], r["flags"], "one_sign")
+    assert bool((T.reference(r["geom"], r["flags"], T.RELU, t, torch.float64) == 0).all())
+
+
+@pytest.mark.parametrize("name", T.STEM_FAST_CASES)
+def test_stem_shapes_have_tiles_on_both_sides_of_the_fast_path(name):
+    """The kernel's rule: BM == 64, KT <= 256, and all 64 rows of the tile have their whole receptive field inside the image."""
+    c = CASES[name]
+    B, Cin, H, W, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo = c["geom"]
+    assert parse(c["expect"])[0] == 64 and -(-KH * KW * Cin // 32) * 32 <= 256 and "nchw" in c["flags"]
+    pool = "pool2" in c["flags"]
+    M = rows_of(c)
+
+    def inside(m):
+        if m >= M:
+            return False
+        if pool:  # window-major rows: four consecutive rows are one pooling window
+            win, q = m >> 2, m & 3
+            r = win % ((Ho // 2) * (Wo // 2))
+            ho, wo = (r // (Wo // 2)) * 2 + (q >> 1), (r % (Wo // 2)) * 2 + (q & 1)
+        else:
+            r = m % (Ho * Wo)
+            ho, wo = r // Wo, r % Wo
+        hi, wi = ho * stride - pad_t, wo * stride - pad_l
+        return hi >= 0 and hi + KH <= H and wi >= 0 and wi + KW <= W
+
+    fast = [all(inside(m) for m in range(m0, m0 + 64)) for m0 in range(0, M, 64)]
+    assert any(fast) and not all(fast), fast
+    if name == "stem7_14x224":
+        assert fast[576 // 64] and (576 // 112, 576 % 112) == (5, 16)  # row 5, columns 16..79
+    if name == "stem3_8x160_64x64":
+        assert fast[0] and not fast[1]  # the first tile of row 0 is interior, the next holds the last column
+
+
+@pytest.mark.parametrize("name", sorted(T.SPLITK_RANGES))
+def test_split_k_ranges_follow_by_arithmetic(name):
+    c = CASES[name]
+    B, Cin, H, W, Cout, KH, KW = c["geom"][:7]
+    BK = parse(c["expect"])[2]
+    cin_pad = -(-Cin // BK) * BK
+    tiles = KH * KW * cin_pad // BK
+    want = T.SPLITK_RANGES[name]
+    S = len(want)
+    per = -(-tiles // S)
+    assert [min(per, tiles - s * per) for s in range(S)] == want and sum(want) == tiles and S in (3, 4)
+    assert c["opts"].get("conv_splitk", 1) == 1
+    if name == "sk_s3_short_last_512pw_gate":
+        assert tiles == 16 and want[-1] < want[0]
+    if name == "sk_s3_even_64to36":
+        assert tiles == 18
+    if name == "sk_s4_midtap_96to68":  # range 1 starts at K-tile 7: tap 2, channel 32 - neither a tap's first tile nor tile 0
+        cpt = cin_pad // BK
+        assert tiles == 27 and (per // cpt, (per % cpt) * BK) == (2, 32)
