@@ -694,6 +694,21 @@ int orbit_op_conv2d_wgrad(const float* x, int x_nchw, const float* dy, float* dw
  * x * gate is never materialised. Single-operator entry for the parity tests. */
 int orbit_op_conv2d_wgrad_gated(const float* x, const float* gate, const float* dy, float* dw, int B, int H, int W, int Cin,
                                 int Cout, orbit_stream_t stream);
+/* orbit_op_conv2d_wgrad_plan (host only): the kernel form the two entries above and the training plans run for a layer, and its
+ *   split geometry. *form: 0 the 64x64-tile kernel on NHWC x, 1 the same on NCHW x, 2 the thin register form (pointwise, unpadded,
+ *   >= 2^18 rows, the thinner side <= 32 channels). thin[7] = TF, TT (16-channel tiles of the fat / thin side a wave holds: the
+ *   kernel instantiation), fat_is_co (1: the fat side is dy), groups and tiles_per_group of the fat side, blocks (row splits) and
+ *   rows_per_wave; zeros for the tiled forms. tiled[4] = co_tiles, n_tiles, splits, steps_per_split (32-row steps); zeros for thin.
+ *   gated != 0: the layer has a squeeze-excite gate (refused with x_nchw, as the launch refuses it).
+ * orbit_op_conv2d_wgrad_batched: the filter gradients of n <= 48 layers as a network's reverse pass computes them - every layer's
+ *   main kernel with its split reduction deferred, then the reductions of all layers in ONE launch. x, dy, dw: arrays of n device
+ *   pointers; gate: array of n device pointers (entries nullable) or NULL; x_nchw: n flags; geom: n x 12 ints
+ *   B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo. Each dw has the bits of the same layer through
+ *   orbit_op_conv2d_wgrad / _gated. Single-operator entries for the parity tests. */
+int orbit_op_conv2d_wgrad_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho,
+                               int Wo, int x_nchw, int gated, int* form, int* thin, int* tiled);
+int orbit_op_conv2d_wgrad_batched(int n, const float* const* x, const int* x_nchw, const float* const* dy, float* const* dw,
+                                  const float* const* gate, const int* geom, orbit_stream_t stream);
 /* max-pool that records the argmax (position inside the window, first maximum in scan order) and its backward */
 int orbit_op_maxpool2d_train(const float* x, float* y, uint8_t* idx, int B, int H, int W, int C, int K, int stride,
                              int pad, int Ho, int Wo, orbit_stream_t stream);

@@ -143,6 +143,8 @@ _SIGNATURES = {
     "orbit_op_conv2d_dgrad": (c_int, [P, P, P, P] + [c_int] * 12 + [P]),
     "orbit_op_conv2d_wgrad": (c_int, [P, c_int, P, P] + [c_int] * 12 + [P]),
     "orbit_op_conv2d_wgrad_gated": (c_int, [P, P, P, P] + [c_int] * 5 + [P]),
+    "orbit_op_conv2d_wgrad_plan": (c_int, [c_int] * 14 + [POINTER(c_int)] * 3),
+    "orbit_op_conv2d_wgrad_batched": (c_int, [c_int, P, POINTER(c_int), P, P, P, POINTER(c_int), P]),
     "orbit_op_maxpool2d_train": (c_int, [P, P, P] + [c_int] * 9 + [P]),
     "orbit_op_maxpool2d_backward": (c_int, [P, P, P] + [c_int] * 9 + [P]),
     "orbit_op_avgpool_backward": (c_int, [P, P, c_int, c_int, c_int, P]),

@@ -375,6 +375,16 @@ int launch_dwconv_wgrad(const float* x, const float* dy, float* dw, float* scrat
 // (in: x is the RAW output of the producing conv; the transform is applied as the patch is staged in LDS - only where
 // dwconv_wgrad_xf_supported says the LDS form fits the layer)
 bool dwconv_wgrad_xf_supported(const LayerGeom& g);
+// What launch_conv_wgrad runs for a layer: the one value the launcher dispatches from and the scratch is sized by (and what
+// orbit_op_conv2d_wgrad_plan reports). The tiled fields are filled for every layer, the thin ones where form == WGRAD_THIN.
+enum WgradForm { WGRAD_TILED_NHWC = 0, WGRAD_TILED_NCHW = 1, WGRAD_THIN = 2 };
+struct WgradPlan {
+    int form = WGRAD_TILED_NHWC;
+    int co_tiles = 0, n_tiles = 0, splits = 0, steps_per_split = 0;                       // conv_wgrad_kernel<MODE>
+    int TF = 0, TT = 0, fat_is_co = 0, groups = 0, tpg = 0, blocks = 0, rows_per_wave = 0;  // conv_wgrad_thin_kernel<TF, TT, ..>
+    int partials() const { return form == WGRAD_THIN ? blocks : splits; }  // partial tiles [Cout][NC] the reduce adds
+};
+WgradPlan conv_wgrad_plan(const LayerGeom& g, int x_nchw);
 size_t conv_wgrad_scratch_floats(const LayerGeom& g);
 // The split reduction of several filter gradients in ONE launch: launch_conv_wgrad with `defer` fills a job instead of
 // running its reduce (the layer's partial tiles must then stay in `scratch` until launch_conv_wgrad_reduce_batched has run).

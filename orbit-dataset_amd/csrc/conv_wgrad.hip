@@ -359,44 +359,57 @@ __global__ __launch_bounds__(256) void conv_wgrad_thin_kernel(const WthinParams 
 // 200-frame batch) whose thinner side has <= 2 tiles of 16 channels; blocks = row splits (<= 1024, >= 64 rows per wave).
 // (Measured, 200 frames: 16 -> 96 @112 455 -> 224 us; with 3 thin tiles - 40 <-> 240 @28 - the 24 MFMAs per 4-row step bound
 // the walk: 159-222 us against 70 us for the tiled kernel, which keeps those layers.)
-static bool wgrad_thin_geometry(int M, int Cin, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int x_nchw, int& blocks,
-                                int& rows_per_wave) {
-    if (x_nchw || KH != 1 || KW != 1 || stride != 1 || pad_t != 0 || pad_l != 0 || M < (1 << 18)) return false;
-    if (std::min(cdiv(Cin, 16), cdiv(Cout, 16)) > 2) return false;
-    blocks = std::min(1024, cdiv(M, 4 * 64));
-    rows_per_wave = cdiv(cdiv(M, blocks * 4), 32) * 32;  // whole loop iterations of every instantiation (4 * S rows, S <= 8)
-    blocks = cdiv(M, rows_per_wave * 4);
-    return true;
-}
-
-// number of m-splits for a layer: enough blocks to fill the chip, at least 8 K-steps per block
-static void wgrad_geometry(int M, int Cout, int NC, int& co_tiles, int& n_tiles, int& splits, int& steps_per_split) {
-    co_tiles = cdiv(Cout, 64), n_tiles = cdiv(NC, 64);
-    const int tiles = co_tiles * n_tiles;
+//
+// The plan of a layer: the one place that decides what launch_conv_wgrad runs and what conv_wgrad_scratch_floats sizes.
+WgradPlan conv_wgrad_plan(const LayerGeom& g, int x_nchw) {
+    WgradPlan pl;
+    const int M = g.B * g.Ho * g.Wo, NC = g.KH * g.KW * g.Cin;
+    pl.form = x_nchw ? WGRAD_TILED_NCHW : WGRAD_TILED_NHWC;
+    // number of m-splits of the tiled kernel: enough blocks to fill the chip, at least 8 K-steps per block
+    pl.co_tiles = cdiv(g.Cout, 64), pl.n_tiles = cdiv(NC, 64);
+    const int tiles = pl.co_tiles * pl.n_tiles;
     const int total_steps = cdiv(M, WG_BKM);
     // 1536 (2048 before; 1024 measured no better): a quarter less partial-tile traffic (the split reductions move ~1 GB per LITE
     // step), same-box A/B 24.54 / 24.53 -> 24.41 / 24.23 ms per step (profiles/r06_lite_ab_fused_fronts.txt)
     constexpr int WGRAD_TARGET_BLOCKS = 1536;
-    splits = cdiv(WGRAD_TARGET_BLOCKS, tiles);
+    pl.splits = cdiv(WGRAD_TARGET_BLOCKS, tiles);
     const int max_splits = total_steps >= 8 ? total_steps / 8 : 1;
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    steps_per_split = cdiv(total_steps, splits);
-    splits = cdiv(total_steps, steps_per_split);
+    if (pl.splits > max_splits) pl.splits = max_splits;
+    if (pl.splits < 1) pl.splits = 1;
+    pl.steps_per_split = cdiv(total_steps, pl.splits);
+    pl.splits = cdiv(total_steps, pl.steps_per_split);
+    // the thin form: pointwise, unpadded, >= 2^18 rows, the thinner side <= 2 tiles of 16 channels
+    if (x_nchw || g.KH != 1 || g.KW != 1 || g.stride != 1 || g.pad_t != 0 || g.pad_l != 0 || M < (1 << 18)) return pl;
+    const int tci = cdiv(g.Cin, 16), tco = cdiv(g.Cout, 16);
+    if (std::min(tci, tco) > 2) return pl;
+    pl.form = WGRAD_THIN;
+    pl.blocks = std::min(1024, cdiv(M, 4 * 64));
+    pl.rows_per_wave = cdiv(cdiv(M, pl.blocks * 4), 32) * 32;  // whole loop iterations of every instantiation (4 * S rows, S <= 8)
+    pl.blocks = cdiv(M, pl.rows_per_wave * 4);
+    pl.fat_is_co = tco >= tci ? 1 : 0;
+    const int ftiles = pl.fat_is_co ? tco : tci;
+    pl.TT = pl.fat_is_co ? tci : tco;
+    pl.groups = cdiv(ftiles, 8);
+    pl.tpg = cdiv(ftiles, pl.groups);
+    pl.TF = pl.tpg <= 2 ? 2 : pl.tpg <= 4 ? 4 : pl.tpg <= 6 ? 6 : 8;
+    return pl;
 }
 
 size_t conv_wgrad_scratch_floats(const LayerGeom& g) {
-    const int B = g.B, Cin = g.Cin, Cout = g.Cout, KH = g.KH, KW = g.KW, Ho = g.Ho, Wo = g.Wo;
-    int ct, nt, sp, sps;
-    const int NC = KH * KW * Cin;
-    wgrad_geometry(B * Ho * Wo, Cout, NC, ct, nt, sp, sps);
-    int tb = 0, rpw = 0;  // (the thin form of a pointwise layer: the caller's stride / padding are not known here - size for it)
-    if (wgrad_thin_geometry(B * Ho * Wo, Cin, Cout, KH, KW, 1, 0, 0, 0, tb, rpw)) sp = std::max(sp, tb);
-    return (size_t)sp * Cout * NC;
+    // (sized for both forms of a pointwise layer, whatever stride / padding / layout the launch then names: the larger count)
+    LayerGeom q = g;
+    q.stride = 1, q.pad_t = 0, q.pad_l = 0;
+    const WgradPlan pl = conv_wgrad_plan(q, 0);
+    return (size_t)std::max(pl.splits, pl.form == WGRAD_THIN ? pl.blocks : 0) * g.Cout * (g.KH * g.KW * g.Cin);
+}
+
+static int wgrad_reduce_jobs_check(int n) {
+    ORBIT_REQUIRE(n >= 0 && n <= WGRAD_REDUCE_JOBS, "conv_wgrad_reduce_batched: %d jobs", n);
+    return ORBIT_OK;
 }
 
 int launch_conv_wgrad_reduce_batched(WgradReduceJobs& jobs, int n, hipStream_t s) {
-    ORBIT_REQUIRE(n >= 0 && n <= WGRAD_REDUCE_JOBS, "conv_wgrad_reduce_batched: %d jobs", n);
+    if (int rc = wgrad_reduce_jobs_check(n)) return rc;
     if (n == 0) return ORBIT_OK;
     unsigned blocks = 0;
     for (int k = 0; k < n; ++k) {
@@ -409,32 +422,34 @@ int launch_conv_wgrad_reduce_batched(WgradReduceJobs& jobs, int n, hipStream_t s
     return ORBIT_OK;
 }
 
+// what the kernels need of a layer (shared with the host-only plan entry, which refuses what the launcher refuses)
+static int wgrad_layer_check(const LayerGeom& g, int x_nchw, bool gated) {
+    ORBIT_REQUIRE(!gated || !x_nchw, "conv_wgrad: the squeeze-excite gate needs the NHWC path");
+    ORBIT_REQUIRE(g.Cout % 4 == 0, "conv_wgrad: Cout %% 4 != 0");
+    ORBIT_REQUIRE(x_nchw || g.Cin % 4 == 0, "conv_wgrad: NHWC path needs Cin %% 4 == 0");
+    return ORBIT_OK;
+}
+
 int launch_conv_wgrad(const float* x, int x_nchw, const float* dy, float* dw_oihw, const LayerGeom& g, float* scratch, hipStream_t s,
                       const float* gate, WgradReduceJob* defer) {
     const int B = g.B, H = g.H, W = g.W, Cin = g.Cin, Cout = g.Cout, KH = g.KH, KW = g.KW, stride = g.stride, pad_t = g.pad_t,
               pad_l = g.pad_l, Ho = g.Ho, Wo = g.Wo;
     ORBIT_REQUIRE(x && dy && dw_oihw && scratch, "conv_wgrad: null pointer");
-    ORBIT_REQUIRE(!gate || !x_nchw, "conv_wgrad: the squeeze-excite gate needs the NHWC path");
-    ORBIT_REQUIRE(Cout % 4 == 0, "conv_wgrad: Cout %% 4 != 0");
-    ORBIT_REQUIRE(x_nchw || Cin % 4 == 0, "conv_wgrad: NHWC path needs Cin %% 4 == 0");
+    if (int rc = wgrad_layer_check(g, x_nchw, gate != nullptr)) return rc;
     WgradParams p;
     p.x = x, p.dy = dy, p.partial = scratch, p.gate = gate;
     p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout, p.KH = KH, p.KW = KW, p.stride = stride;
     p.pad_t = pad_t, p.pad_l = pad_l, p.Ho = Ho, p.Wo = Wo;
     p.M = B * Ho * Wo, p.NC = KH * KW * Cin;
     p.fd_howo = make_fastdiv((unsigned)(Ho * Wo)), p.fd_wo = make_fastdiv((unsigned)Wo);
-    int thin_blocks = 0, thin_rpw = 0;
-    if (wgrad_thin_geometry(p.M, Cin, Cout, KH, KW, stride, pad_t, pad_l, x_nchw, thin_blocks, thin_rpw)) {
-        const int tci = cdiv(Cin, 16), tco = cdiv(Cout, 16);
-        const bool fat_is_co = tco >= tci;
+    const WgradPlan pl = conv_wgrad_plan(g, x_nchw);
+    if (pl.form == WGRAD_THIN) {
+        const bool fat_is_co = pl.fat_is_co != 0;
         WthinParams q;
         q.fat = fat_is_co ? dy : x, q.thin = fat_is_co ? x : dy, q.gate = gate, q.partial = scratch;
         q.M = p.M, q.Cf = fat_is_co ? Cout : Cin, q.Ct = fat_is_co ? Cin : Cout, q.Cout = Cout, q.Cin = Cin;
-        q.rows_per_wave = thin_rpw, q.ftiles = fat_is_co ? tco : tci, q.fd_hw = p.fd_howo;
-        const int tt = fat_is_co ? tci : tco;
-        const int groups = cdiv(q.ftiles, 8);
-        q.tpg = cdiv(q.ftiles, groups);
-        const dim3 grid(thin_blocks, groups);
+        q.rows_per_wave = pl.rows_per_wave, q.ftiles = cdiv(q.Cf, 16), q.tpg = pl.tpg, q.fd_hw = p.fd_howo;
+        const dim3 grid(pl.blocks, pl.groups);
         const int rec = prof_start("conv_wgrad_thin", 2.0 * p.M * Cout * Cin,
                                    4.0 * ((double)p.M * Cin + (double)p.M * Cout + (double)Cout * Cin), s);
 #define ORBIT_WTHIN(TF_, TT_)                                                                                \
@@ -449,27 +464,27 @@ int launch_conv_wgrad(const float* x, int x_nchw, const float* dy, float* dw_oih
     } while (0)
 #define ORBIT_WTHIN_TF(TT_)                                                                                  \
     do {                                                                                                     \
-        if (q.tpg <= 2) ORBIT_WTHIN(2, TT_);                                                                 \
-        else if (q.tpg <= 4) ORBIT_WTHIN(4, TT_);                                                            \
-        else if (q.tpg <= 6) ORBIT_WTHIN(6, TT_);                                                            \
+        if (pl.TF == 2) ORBIT_WTHIN(2, TT_);                                                                 \
+        else if (pl.TF == 4) ORBIT_WTHIN(4, TT_);                                                            \
+        else if (pl.TF == 6) ORBIT_WTHIN(6, TT_);                                                            \
         else ORBIT_WTHIN(8, TT_);                                                                            \
     } while (0)
-        if (tt == 1) ORBIT_WTHIN_TF(1);
+        if (pl.TT == 1) ORBIT_WTHIN_TF(1);
         else ORBIT_WTHIN_TF(2);
 #undef ORBIT_WTHIN_TF
 #undef ORBIT_WTHIN
         prof_stop(rec, s);
         ORBIT_LAUNCH_CHECK();
         if (defer) {
-            *defer = WgradReduceJob{scratch, dw_oihw, thin_blocks, Cout, p.NC, Cin, 1, 1, 0};
+            *defer = WgradReduceJob{scratch, dw_oihw, pl.blocks, Cout, p.NC, Cin, 1, 1, 0};
             return ORBIT_OK;
         }
         const size_t total = (size_t)Cout * p.NC;
-        conv_wgrad_reduce_kernel<<<(int)((total + 15) / 16), 256, 0, s>>>(scratch, thin_blocks, Cout, p.NC, Cin, 1, 1, 0, dw_oihw);
+        conv_wgrad_reduce_kernel<<<(int)((total + 15) / 16), 256, 0, s>>>(scratch, pl.blocks, Cout, p.NC, Cin, 1, 1, 0, dw_oihw);
         ORBIT_LAUNCH_CHECK();
         return ORBIT_OK;
     }
-    wgrad_geometry(p.M, Cout, p.NC, p.co_tiles, p.n_tiles, p.splits, p.steps_per_split);
+    p.co_tiles = pl.co_tiles, p.n_tiles = pl.n_tiles, p.splits = pl.splits, p.steps_per_split = pl.steps_per_split;
     const int grid = p.co_tiles * p.n_tiles * p.splits;
     // algorithmic work: 2*M*Cout*K flops; bytes = input + output gradient once, filter gradient once
     const int rec = prof_start(x_nchw ? "conv_wgrad<nchw>" : "conv_wgrad<nhwc>", 2.0 * p.M * Cout * p.NC,
@@ -567,6 +582,59 @@ int orbit_op_conv2d_wgrad_gated(const float* x, const float* gate, const float* 
     float* scratch = nullptr;
     ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&scratch), conv_wgrad_scratch_floats(g) * sizeof(float), s));
     const int rc = launch_conv_wgrad(x, 0, dy, dw, g, scratch, s, gate);
+    (void)hipFreeAsync(scratch, s);
+    return rc;
+}
+
+/* Host only: what launch_conv_wgrad runs for this layer. *form: 0 tiled NHWC, 1 tiled NCHW, 2 thin. thin[7] = TF, TT, fat_is_co,
+ * groups, tiles_per_group, blocks, rows_per_wave of the thin form (zeros otherwise); tiled[4] = co_tiles, n_tiles, splits,
+ * steps_per_split of the tiled forms (zeros for thin). */
+int orbit_op_conv2d_wgrad_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho,
+                               int Wo, int x_nchw, int gated, int* form, int* thin, int* tiled) {
+    ORBIT_REQUIRE(form && thin && tiled, "op_conv2d_wgrad_plan: null pointer");
+    ORBIT_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && Ho > 0 && Wo > 0,
+                  "op_conv2d_wgrad_plan: bad geometry");
+    const LayerGeom g{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
+    if (int rc = wgrad_layer_check(g, x_nchw, gated != 0)) return rc;
+    const WgradPlan pl = conv_wgrad_plan(g, x_nchw);
+    const bool is_thin = pl.form == WGRAD_THIN;
+    const int t[7] = {pl.TF, pl.TT, pl.fat_is_co, pl.groups, pl.tpg, pl.blocks, pl.rows_per_wave};
+    const int d[4] = {pl.co_tiles, pl.n_tiles, pl.splits, pl.steps_per_split};
+    *form = pl.form;
+    for (int i = 0; i < 7; ++i) thin[i] = is_thin ? t[i] : 0;
+    for (int i = 0; i < 4; ++i) tiled[i] = is_thin ? 0 : d[i];
+    return ORBIT_OK;
+}
+
+/* The filter gradients of n <= 48 layers the way a network's reverse pass computes them (single-operator entry for the parity
+ * tests): each layer's main kernel with its split reduction deferred, the partial tiles of every layer kept in a scratch region
+ * of its own, then ONE launch_conv_wgrad_reduce_batched. x, dy, dw: n pointers; gate: n pointers (entries nullable) or NULL;
+ * x_nchw: n flags; geom: n x 12 ints B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo. */
+int orbit_op_conv2d_wgrad_batched(int n, const float* const* x, const int* x_nchw, const float* const* dy, float* const* dw,
+                                  const float* const* gate, const int* geom, orbit_stream_t stream) {
+    if (int rc = wgrad_reduce_jobs_check(n)) return rc;
+    ORBIT_REQUIRE(n == 0 || (x && x_nchw && dy && dw && geom), "op_conv2d_wgrad_batched: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    LayerGeom g[WGRAD_REDUCE_JOBS];
+    size_t offset[WGRAD_REDUCE_JOBS + 1];
+    offset[0] = 0;
+    for (int k = 0; k < n; ++k) {
+        const int* q = geom + 12 * k;
+        g[k] = LayerGeom{q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[11]};
+        ORBIT_REQUIRE(x[k] && dy[k] && dw[k], "op_conv2d_wgrad_batched: null pointer in layer %d", k);
+        ORBIT_REQUIRE(g[k].B > 0 && g[k].H > 0 && g[k].W > 0 && g[k].Cin > 0 && g[k].Cout > 0 && g[k].KH > 0 && g[k].KW > 0 &&
+                          g[k].stride > 0 && g[k].Ho > 0 && g[k].Wo > 0, "op_conv2d_wgrad_batched: bad geometry in layer %d", k);
+        if (int rc = wgrad_layer_check(g[k], x_nchw[k], gate && gate[k])) return rc;
+        offset[k + 1] = offset[k] + align_up(conv_wgrad_scratch_floats(g[k]), 64);
+    }
+    if (n == 0) return ORBIT_OK;
+    float* scratch = nullptr;
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&scratch), offset[n] * sizeof(float), s));
+    WgradReduceJobs jobs;
+    int rc = ORBIT_OK;
+    for (int k = 0; k < n && rc == ORBIT_OK; ++k)
+        rc = launch_conv_wgrad(x[k], x_nchw[k], dy[k], dw[k], g[k], scratch + offset[k], s, gate ? gate[k] : nullptr, &jobs.j[k]);
+    if (rc == ORBIT_OK) rc = launch_conv_wgrad_reduce_batched(jobs, n, s);
     (void)hipFreeAsync(scratch, s);
     return rc;
 }
