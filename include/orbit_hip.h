@@ -888,10 +888,23 @@ size_t orbit_jpeg_workspace_bytes(int B, int H, int W);
  * status [B] int32, written for every frame: 0, ORBIT_JPEG_ST_* bits, or -code for a frame whose descriptor's status is a
  * non-zero code (skipped: its pixels are left untouched). All frames are H x W; one that is not gets ORBIT_JPEG_ST_DESC.
  * Three kernels per chunk: entropy decode (one wave per frame), dequantisation + inverse DCT, upsampling + colour
- * conversion. No read leaves the arena, no write leaves the frame's own slice of the workspace and of the output, whatever
- * the file holds. */
+ * conversion. A frame written with restart markers (Pillow's restart_marker_rows / restart_marker_blocks, tools/resize_videos.py
+ * --restart_rows) is entropy-decoded with one lane per restart interval, 64 intervals at a time, when its markers are exactly
+ * the ones its geometry calls for: RST0, RST1, .. between the ceil(MCUs / restart_interval) intervals, then EOI, 2 to 1024
+ * intervals. Every other frame - no markers, one interval, more than 1024, a marker missing, doubled or out of order - is
+ * walked by one lane from the first byte to the last, and so is a frame any of whose intervals ends with a status: pixels and
+ * status do not depend on which way a frame went. No read leaves the arena, no write leaves the frame's own slice of the
+ * workspace and of the output, whatever the file holds. */
 int orbit_frames_from_jpeg(const uint8_t* arena, size_t arena_bytes, const orbit_jpeg_desc_t* descs, int B, int H, int W,
                            uint8_t* out_u8_hwc, int32_t* status, void* workspace, size_t workspace_bytes, orbit_stream_t stream);
+/* The entropy kernel of orbit_frames_from_jpeg on its own, for parity tests: arena, descs, B, H, W and status as above.
+ * form 0 walks every frame serially, form 1 applies the rule above. coef_out: the quantised coefficients as int16, per frame
+ * 3 * (2 * ceil(W / 16)) * (2 * ceil(H / 16)) blocks of 64 in natural order (the frame's component planes of whole blocks one
+ * behind the other, the rest of the slice untouched), 16-byte aligned; coef_bytes is checked against B, H and W before anything
+ * is launched. taken [B] int32: 0 = walked serially, 1 = one lane per restart interval, 2 = that was tried, an interval ended
+ * with a status, and the frame was walked serially again. */
+int orbit_op_jpeg_entropy(const uint8_t* arena, size_t arena_bytes, const orbit_jpeg_desc_t* descs, int B, int H, int W, int form,
+                          int16_t* coef_out, size_t coef_bytes, int32_t* status, int32_t* taken, orbit_stream_t stream);
 
 /* ---- JPEG encode on the device (csrc/jpeg_enc.hip, csrc/jpeg_enc_core.h) --------------------------------------------------
  * 8-bit RGB frames [B][H][W][3] -> the files Pillow's Image.save(quality = q[, restart_marker_rows = r]) writes for them, byte

@@ -1,11 +1,16 @@
 // JPEG decode on the device: baseline files in one arena -> 8-bit RGB frames [B][H][W][3], equal to Pillow's decode bit for bit.
 // Reference: data/datasets.py:422-431 opens every frame with PIL on the host (libjpeg's default path: Huffman decode, integer
 // "islow" inverse DCT, triangle chroma upsampling, table-driven YCbCr -> RGB). The arithmetic of those stages is restated in
-// csrc/jpeg_core.h as host + device code; this file is the three kernels around it and the launcher.
+// csrc/jpeg_core.h as host + device code; this file is the three kernels around it and the launchers.
 //   jpeg_entropy_kernel  one wave per frame. Entropy decoding is sequential inside an image, a task is hundreds of images: the
 //                        64 lanes copy the descriptor (Huffman and quantisation tables) into LDS, zero the frame's
 //                        coefficients and keep two 1 KB tiles of the byte stream resident in LDS; lane 0 walks the symbols
 //                        and scatters the non-zero coefficients, handing control back at every tile end for the next load.
+//                        A frame with restart markers where its geometry puts them (2 .. JPEG_PAR_MAX_INTERVALS intervals)
+//                        is walked by one lane per restart interval instead, 64 intervals at a time: the wave scans the
+//                        segment for markers into an LDS table, lane j decodes intervals j, j + 64, .. from a register window
+//                        on the arena; any status sends the frame through the serial walk again, so a damaged file's status
+//                        and coefficients do not depend on the form.
 //   jpeg_idct_kernel     one thread per 8 x 8 block: dequantise, both passes of the inverse DCT in registers, range limit.
 //   jpeg_color_kernel    one thread per output pixel: chroma upsampling with libjpeg's edge rules, colour conversion, store.
 // A frame whose stream is damaged ends with a non-zero status and whatever was decoded so far stays inside its own workspace
@@ -50,14 +55,57 @@ __device__ __forceinline__ void jpeg_load_tile(uint8_t* stage, const uint8_t* me
     dst[0] = v[0], dst[1] = v[1], dst[2] = v[2], dst[3] = v[3];
 }
 
+// The markers of the segment, for a frame that may take the interval form: the wave reads the segment tile by tile, every lane
+// looks through its 16 bytes (and the byte behind them), and the markers' positions go to ends[] in stream order - a marker's
+// index is the count of the tiles before plus a prefix count over the ballots of this tile, so no order depends on timing.
+// True when the first nseg markers are RST0, RST1, .. (mod 8) and EOI; only ends[0 .. nseg - 1) are used afterwards. The
+// result is uniform over the wave. The caller puts a barrier between this and its next use of the staging tiles.
+__device__ __forceinline__ bool jpeg_scan_markers(uint8_t* stage, const uint8_t* mem, uint32_t len, int nseg, uint32_t* ends, int lane) {
+    const uint32_t ntiles = (len + JP_STAGE - 1) / JP_STAGE;
+    int count = 0;  // markers in the tiles before this one (uniform)
+    bool bad = false;
+    for (uint32_t t = 0; t < ntiles && count < nseg; ++t) {
+        jpeg_load_tile(stage, mem, len, t, lane);
+        __syncthreads();  // (tile t + 1 goes to the other slot, tile t + 2 comes behind the next barrier)
+        const uint8_t* slot = stage + (t & 1u) * JP_STAGE;
+        const uint32_t o = t * JP_STAGE + 16u * lane;
+        const uint4 q = *reinterpret_cast<const uint4*>(slot + 16 * lane);
+        const int n = o >= len ? 0 : (len - o < 16u ? (int)(len - o) : 16);
+        int next = -1;
+        if (n == 16 && o + 16 < len) next = lane < 63 ? slot[16 * lane + 16] : mem[o + 16];
+        const uint32_t m = jpeg_scan_slice(q.x, q.y, q.z, q.w, n, next);
+        if (__ballot(m != 0) == 0) continue;
+        int before = 0, total = 0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const unsigned long long b = __ballot((m >> j) & 1u);
+            before += __popcll(b & ((1ull << lane) - 1ull));
+            total += __popcll(b);
+        }
+        int k = count + before;
+        for (uint32_t mm = m; mm != 0; mm &= mm - 1, ++k) {
+            const int j = __ffs(mm) - 1;
+            if (k >= nseg) break;  // (nseg <= JPEG_PAR_MAX_INTERVALS, the size of ends[])
+            const int code = j < 15 ? jpeg_slice_byte(q.x, q.y, q.z, q.w, j + 1) : next;
+            if (!jpeg_par_marker_ok(k, code, nseg)) bad = true;
+            ends[k] = o + (uint32_t)j;
+        }
+        count += total;
+    }
+    return __ballot(bad) == 0 && count >= nseg;
+}
+
+// form: 0 walks every frame serially, 1 takes the interval form where the rule of csrc/jpeg_core.h holds. taken (nullable):
+// 0 serial, 1 interval-parallel, 2 parallel attempted, then walked serially.
 __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ arena, size_t arena_bytes,
                                                           const orbit_jpeg_desc_t* __restrict__ descs, int H, int W,
                                                           size_t cap_blocks, int16_t* __restrict__ coef_ws,
-                                                          int32_t* __restrict__ status) {
+                                                          int32_t* __restrict__ status, int form, int32_t* __restrict__ taken) {
     __shared__ __align__(16) orbit_jpeg_desc_t d;
     __shared__ __align__(16) uint8_t stage[2 * JP_STAGE];
     __shared__ uint8_t natural[64];
     __shared__ uint32_t ctl[2];
+    __shared__ uint32_t ends[JPEG_PAR_MAX_INTERVALS];
     const int f = blockIdx.x, lane = threadIdx.x;
     {
         const uint32_t* src = reinterpret_cast<const uint32_t*>(descs + f);
@@ -66,6 +114,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
         natural[lane] = jpeg_natural_dev[lane];
     }
     __syncthreads();
+    if (taken && lane == 0) taken[f] = 0;
     if (d.status != 0) {  // the host decodes this frame
         if (lane == 0) status[f] = d.status > 0 ? -d.status : d.status;
         return;
@@ -84,6 +133,27 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     }
     const uint8_t* mem = arena + d.file_offset + d.ecs_offset;
     const uint32_t len = d.ecs_bytes;
+    const int nseg = form ? jpeg_par_intervals(d, g) : 0;
+    if (nseg != 0) {  // (uniform: the descriptor is in LDS)
+        const bool valid = jpeg_scan_markers(stage, mem, len, nseg, ends, lane);
+        __syncthreads();  // ends[] is complete, the zeroes are written, nobody reads the tiles any more
+        if (valid) {
+            int st = 0;
+            for (int k = lane; k < nseg; k += 64) st |= jpeg_walk_interval(k, nseg, ends, mem, d, g, natural, coef);
+            if (__ballot(st != 0) == 0) {
+                if (lane == 0) {
+                    status[f] = 0;
+                    if (taken) taken[f] = 1;
+                }
+                return;
+            }
+            // a damaged file: its status and coefficients are the serial walk's
+            if (taken && lane == 0) taken[f] = 2;
+            __syncthreads();
+            uint4* z = reinterpret_cast<uint4*>(coef);
+            for (int i = lane; i < g.total_blocks * 8; i += 64) z[i] = make_uint4(0, 0, 0, 0);
+        }
+    }
     uint32_t tile0 = 0;
     jpeg_load_tile(stage, mem, len, 0, lane);
     jpeg_load_tile(stage, mem, len, 1, lane);
@@ -192,7 +262,7 @@ int orbit_frames_from_jpeg(const uint8_t* arena, size_t arena_bytes, const orbit
         int16_t* coef = (int16_t*)workspace;
         uint8_t* planes = (uint8_t*)workspace + (size_t)nb * cap_blocks * 64 * sizeof(int16_t);
         int rec = prof_start("jpeg_entropy", 0.0, (double)nb * cap_blocks * 64 * sizeof(int16_t), s);
-        jpeg_entropy_kernel<<<nb, 64, 0, s>>>(arena, arena_bytes, descs + b0, H, W, cap_blocks, coef, status + b0);
+        jpeg_entropy_kernel<<<nb, 64, 0, s>>>(arena, arena_bytes, descs + b0, H, W, cap_blocks, coef, status + b0, 1, nullptr);
         prof_stop(rec, s);
         ORBIT_LAUNCH_CHECK();
         const size_t blocks = (size_t)nb * cap_blocks;
@@ -207,6 +277,23 @@ int orbit_frames_from_jpeg(const uint8_t* arena, size_t arena_bytes, const orbit
         prof_stop(rec, s);
         ORBIT_LAUNCH_CHECK();
     }
+    return ORBIT_OK;
+}
+
+int orbit_op_jpeg_entropy(const uint8_t* arena, size_t arena_bytes, const orbit_jpeg_desc_t* descs, int B, int H, int W, int form,
+                          int16_t* coef_out, size_t coef_bytes, int32_t* status, int32_t* taken, orbit_stream_t stream) {
+    ORBIT_REQUIRE(arena && descs && coef_out && status && taken, "op_jpeg_entropy: null pointer");
+    ORBIT_REQUIRE(B > 0 && H > 0 && W > 0, "op_jpeg_entropy: bad sizes");
+    ORBIT_REQUIRE(H <= ORBIT_RESIZE_MAX_SIZE && W <= ORBIT_RESIZE_MAX_SIZE, "op_jpeg_entropy: %dx%d exceeds the limit of %d pixels per side", H,
+                  W, ORBIT_RESIZE_MAX_SIZE);
+    ORBIT_REQUIRE(form == 0 || form == 1, "op_jpeg_entropy: form %d (0 = serial, 1 = one lane per restart interval)", form);
+    ORBIT_REQUIRE(arena_bytes > 0, "op_jpeg_entropy: empty arena");
+    ORBIT_REQUIRE(((uintptr_t)coef_out & 15) == 0 && ((uintptr_t)descs & 7) == 0, "op_jpeg_entropy: coef_out must be 16-byte aligned, descs 8-byte");
+    const size_t cap_blocks = jpeg_cap_blocks(H, W), need = (size_t)B * cap_blocks * 64 * sizeof(int16_t);
+    ORBIT_REQUIRE(coef_bytes >= need, "op_jpeg_entropy: coef_out of %zu bytes, %d frames of %dx%d need %zu", coef_bytes, B, H, W, need);
+    hipStream_t s = (hipStream_t)stream;
+    jpeg_entropy_kernel<<<B, 64, 0, s>>>(arena, arena_bytes, descs, H, W, cap_blocks, coef_out, status, form, taken);
+    ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
 }
 

@@ -1,10 +1,10 @@
 // Baseline JPEG decoding as plain integer code that compiles for the host and for the device: the header parser (host only),
 // the entropy walker (bit reader, Huffman symbol decode, block decode), libjpeg's "islow" inverse DCT, and its chroma
 // upsampling + YCbCr -> RGB conversion per pixel. csrc/jpeg.hip wraps the last three in kernels; tools/jpeg_host_check.cpp
-// runs the very same functions on the CPU under the sanitizers, which is where their behaviour on damaged files is
-// established. Restated from the JPEG standard (ITU T.81) and from the arithmetic of libjpeg's default decode path
-// (jdhuff.c, jidctint.c, jdsample.c, jdcolor.c): the output equals Pillow's for every file the parser accepts and the
-// walker finishes with status 0.
+// (and tools/jpeg_par_host_check.cpp for the walk of one restart interval per lane) runs the very same functions on the CPU
+// under the sanitizers, which is where their behaviour on damaged files is established. Restated from the JPEG standard
+// (ITU T.81) and from the arithmetic of libjpeg's default decode path (jdhuff.c, jidctint.c, jdsample.c, jdcolor.c): the
+// output equals Pillow's for every file the parser accepts and the walker finishes with status 0.
 //
 // Bounds: the walker reads the stream only through Src::at(pos) with pos < len, writes coefficients only at block indices
 // below JpegGeom::total_blocks, and indexes every table with a masked or checked index, so no content of a file can make
@@ -270,6 +270,120 @@ JPEG_HD void jpeg_walk(JpegWalk& w, const Src& s, const orbit_jpeg_desc_t& d, co
         ++w.mcu;
         if (d.restart_interval > 0) --w.to_restart;
     }
+}
+
+// ---- one restart interval per walker (the interval-parallel form) ---------------------------------------------------------------
+// Every restart interval starts byte-aligned with the DC predictors reset, so a frame whose markers are all where its
+// geometry puts them can be walked interval by interval, in any order or side by side. Three pieces: the marker scan over a
+// lane's slice of the segment, the rule that turns the markers of a frame into the table of interval ends, and the walk of
+// one interval. A frame takes this form only when the rule holds; when any interval then reports a status, the caller zeroes
+// the frame's coefficients and runs jpeg_walk over it, so status and coefficients of a damaged file are jpeg_walk's.
+#define JPEG_PAR_MAX_INTERVALS 1024  // the table is 4 KB of LDS
+
+// byte j (0 .. 15) of four little-endian words (by value: an array indexed by j would live in private memory on the device)
+JPEG_HD int jpeg_slice_byte(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, int j) {
+    const uint32_t w = j < 8 ? (j < 4 ? v0 : v1) : (j < 12 ? v2 : v3);
+    return (int)((w >> (8 * (j & 3))) & 255u);
+}
+
+// The markers of the slice [o, o + n) of the segment, n <= 16, whose bytes are the words v0 .. v3: bit j is set when byte
+// o + j is the FF of a marker, FF xx with xx neither 00 (a stuffed data byte) nor FF (fill: the marker's FF is the last one).
+// next is the byte at o + n, which decides about an FF at the end of the slice, or -1 behind the segment: an FF that ends the
+// segment is no marker.
+JPEG_HD uint32_t jpeg_scan_slice(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, int n, int next) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int c = jpeg_slice_byte(v0, v1, v2, v3, j);
+        const int c2 = j + 1 < n ? jpeg_slice_byte(v0, v1, v2, v3, (j + 1) & 15) : next;
+        if (j < n && c == 0xFF && c2 > 0 && c2 != 0xFF) m |= 1u << j;
+    }
+    return m;
+}
+
+// intervals of the frame by its geometry, or 0 when the frame is walked serially: no restart interval, a single interval, or
+// more than the table holds
+JPEG_HD int jpeg_par_intervals(const orbit_jpeg_desc_t& d, const JpegGeom& g) {
+    const int R = d.restart_interval, mcus = g.mcux * g.mcuy;
+    if (R <= 0) return 0;
+    const int nseg = mcus / R + (mcus % R != 0);
+    return nseg >= 2 && nseg <= JPEG_PAR_MAX_INTERVALS ? nseg : 0;
+}
+
+// whether the k-th marker of the segment (k = 0, 1, .. in stream order) may have this code: RST(k mod 8) between the
+// intervals, then EOI; what follows EOI is nobody's business
+JPEG_HD bool jpeg_par_marker_ok(int k, int code, int nseg) {
+    return k < nseg - 1 ? code == 0xD0 + (k & 7) : (k == nseg - 1 ? code == 0xD9 : true);
+}
+
+// The byte stream as the walker of one interval sees it: 16 bytes of the segment in two registers, reloaded in words when the
+// reader leaves them (it moves forward, so that is one load per 16 bytes). No load touches a byte at or behind `end`; the
+// last, partial window of an interval is put together from single bytes.
+struct JpegWinSrc {
+    const uint8_t* mem;  // the segment's first byte
+    uint32_t end;
+    mutable uint32_t base;
+    mutable uint64_t lo, hi;
+    JPEG_HD void load(uint32_t pos) const {
+        base = pos, lo = 0, hi = 0;
+        if ((uint64_t)pos + 16 <= end) {
+            uint64_t a, b;  // (unaligned-safe: the compiler picks the loads)
+            __builtin_memcpy(&a, mem + pos, 8);
+            __builtin_memcpy(&b, mem + pos + 8, 8);
+            lo = a, hi = b;
+        } else {
+            for (int j = 0; j < 8; ++j) {
+                if ((uint64_t)pos + j < end) lo |= (uint64_t)mem[pos + j] << (8 * j);
+                if ((uint64_t)pos + 8 + j < end) hi |= (uint64_t)mem[pos + 8 + j] << (8 * j);
+            }
+        }
+    }
+    JPEG_HD uint8_t at(uint32_t pos) const {
+        uint32_t i = pos - base;
+        if (i >= 16u) load(pos), i = 0;
+        return (uint8_t)(((i & 8u) ? hi : lo) >> (8 * (i & 7u)));
+    }
+};
+
+// Interval k of nseg: the MCUs k * R .. of the frame, read from the bytes between marker k - 1 and marker k (ends[k] is the
+// position of marker k's FF in the segment, for k < nseg - 1; the last interval runs to the end of the segment and has to
+// meet EOI). Returns the interval's status. coef: the frame's coefficient planes, zeroed; the blocks written are those
+// jpeg_walk writes for the same MCUs. mem: the segment's first byte.
+JPEG_HD int jpeg_walk_interval(int k, int nseg, const uint32_t* ends, const uint8_t* mem, const orbit_jpeg_desc_t& d, const JpegGeom& g,
+                               const uint8_t* natural, int16_t* coef) {
+    const int R = d.restart_interval, mcus = g.mcux * g.mcuy;
+    const int hs0 = d.ncomp == 3 ? d.hs[0] : 1, vs0 = d.ncomp == 3 ? d.vs[0] : 1;
+    JpegWalk w;
+    uint32_t len = d.ecs_bytes, pos = 0;
+    if (k + 1 < nseg && ends[k] < len) len = ends[k];
+    if (k > 0) pos = ends[k - 1] + 2;  // (a marker has both its bytes inside the segment)
+    if (pos > len) pos = len;
+    w.bits.acc = 0, w.bits.n = 0, w.bits.pos = pos, w.bits.len = len, w.bits.marker = 0;
+    w.mcu = k * R, w.to_restart = 0, w.next_rst = 0;
+    w.dc[0] = w.dc[1] = w.dc[2] = 0;
+    w.status = 0, w.done = 0;
+    JpegWinSrc s;
+    s.mem = mem, s.end = len;
+    s.load(pos);
+    const int stop = w.mcu + R < mcus ? w.mcu + R : mcus;
+    for (; w.mcu < stop && !w.status; ++w.mcu) {
+        const int mx = w.mcu % g.mcux, my = w.mcu / g.mcux;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= d.ncomp) continue;
+            const int h = c == 0 ? hs0 : 1, v = c == 0 ? vs0 : 1;
+            for (int by = 0; by < v && !w.status; ++by)
+                for (int bx = 0; bx < h && !w.status; ++bx) {
+                    const int blk = g.base[c] + (my * v + by) * g.wb[c] + mx * h + bx;  // < total_blocks by jpeg_geom
+                    jpeg_block(w, s, d, natural, c, coef + (size_t)blk * 64);
+                }
+        }
+    }
+    if (w.status) return w.status;
+    // fewer than 8 bits left, then nothing but the end of the sub-stream (which is where the scan found the next marker)
+    if (k + 1 == nseg) jpeg_expect_marker(w, s, 0xD9, ORBIT_JPEG_ST_TRAILING);
+    else jpeg_expect_marker(w, s, -1, ORBIT_JPEG_ST_RESTART);
+    return w.status;
 }
 
 // ---- dequantisation + inverse DCT (libjpeg jidctint.c jpeg_idct_islow) -----------------------------------------------------------

@@ -5,12 +5,13 @@ frames per launch: us per launch and GB/s over the profiler's bytes (8-bit frame
 offline pass of the reference (scripts/resize_videos.py:46) this replaces. The first frame of every case is compared with PIL.
 --decode measures the JPEG decoder instead (orbit_frames_from_jpeg, csrc/jpeg.hip) on 224 x 224 and 1080 x 1080 frames written
 by write_synthetic_orbit_directory: us per launch of each of its three kernels, the bytes uploaded compressed against decoded,
-and PIL's decode of the same files on 16 threads; every frame is compared with PIL.
+and PIL's decode of the same files on 16 threads; every frame is compared with PIL. --restart_rows N re-saves the frames with a
+restart marker every N MCU rows first: those the entropy kernel decodes with one lane per restart interval.
 --encode measures the JPEG encoder (orbit_frames_to_jpeg, csrc/jpeg_enc.hip) on 224 x 224 frames - the size tools/resize_videos.py
 writes - of smooth and of noise content at quality 95: us per call of each of its kernels beside the kernel's byte floor (its
 algorithmic bytes at 6.3 TB/s), the compressed bytes out, and PIL's save(quality=95) of the same frames on 16 threads; every
 file is compared with PIL's.
-Usage (GPU box): python tools/ingest_bench.py [--decode | --encode] [--frames 200] [--reps 10] [--threads 16]"""
+Usage (GPU box): python tools/ingest_bench.py [--decode [--restart_rows N] | --encode] [--frames 200] [--reps 10] [--threads 16]"""
 import argparse
 import ctypes
 import json
@@ -61,6 +62,9 @@ def measure_decode(a, lib, dev, pool):
             pipeline.write_synthetic_orbit_directory(root, users=1, objects_per_user=1, clean_videos=1, clutter_videos=0,
                                                      frames_per_video=a.frames, frame_size=size)
             paths = sorted(glob.glob(os.path.join(root, "*", "*", "*", "*", "*.jpg")))
+            if a.restart_rows > 0:  # the same frames with a restart marker every N MCU rows, at the quality they were written at
+                for path in paths:
+                    Image.open(path).save(path, quality=90, restart_marker_rows=a.restart_rows)
             t0 = time.perf_counter()
             jf = pipeline.read_jpeg_frames(paths, pool)
             read_ms = 1e3 * (time.perf_counter() - t0)
@@ -95,13 +99,13 @@ def measure_decode(a, lib, dev, pool):
             lib.orbit_prof_variant(i, name, ctypes.byref(launches), ctypes.byref(kms), None, None)
             kernels[name.value.decode()] = {"us_per_call": 1e3 * kms.value / a.reps, "launches_per_call": launches.value / a.reps}
         compressed, decoded = sum(len(f) for f in jf.files), int(np.prod(jf.shape))
-        row = {"size": size, "frames": a.frames, "kernels": kernels, "us_per_call": 1e3 * ms.value / a.reps,
+        row = {"size": size, "frames": a.frames, "restart_rows": a.restart_rows, "kernels": kernels, "us_per_call": 1e3 * ms.value / a.reps,
                "compressed_bytes": compressed, "decoded_bytes": decoded, "pil_ms": 1e3 * min(pil_s), "pil_threads": a.threads,
                "read_and_parse_ms": read_ms, "all_frames_equal_pil": exact}
         rows.append(row)
-        print("%4d x %-4d %d frames: %s = %9.1f us per call | upload %.2f MB compressed, %.2f MB decoded (%.1fx) | PIL x%d threads "
+        print("%4d x %-4d %d frames, restart_rows %d: %s = %9.1f us per call | upload %.2f MB compressed, %.2f MB decoded (%.1fx) | PIL x%d threads "
               "%8.1f ms (%5.1fx) | read + parse %6.1f ms | frames %s PIL"
-              % (size, size, a.frames, " + ".join("%s %.1f" % (k, v["us_per_call"]) for k, v in sorted(kernels.items())),
+              % (size, size, a.frames, a.restart_rows, " + ".join("%s %.1f" % (k, v["us_per_call"]) for k, v in sorted(kernels.items())),
                  row["us_per_call"], compressed / 1e6, decoded / 1e6, decoded / compressed, a.threads, row["pil_ms"],
                  1e3 * row["pil_ms"] / row["us_per_call"], read_ms, "==" if exact else "!="), flush=True)
         assert exact, "a decoded frame differs from PIL"
@@ -196,6 +200,9 @@ def main(argv=None):
     p.add_argument("--encode_size", type=int, default=224, help="with --encode: the frame size")
     p.add_argument("--decode", action="store_true", help="measure the JPEG decoder instead of the resize")
     p.add_argument("--sizes", type=int, nargs="+", default=[224, 1080], help="with --decode: the frame sizes")
+    p.add_argument("--restart_rows", type=int, default=0,
+                   help="with --decode: re-save the frames with a restart marker every N MCU rows (Pillow's restart_marker_rows), "
+                        "which the entropy kernel decodes with one lane per restart interval; 0 = no markers")
     p.add_argument("--frames", type=int, default=200)
     p.add_argument("--reps", type=int, default=10)
     p.add_argument("--threads", type=int, default=16)
