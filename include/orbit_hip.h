@@ -388,6 +388,19 @@ int orbit_op_dwconv2d(const float* x, const float* w, float* y, const float* sca
 int orbit_op_conv2d_train(const float* x, int x_nchw, const float* w, float* y, const float* gate, int B, int H, int W,
                           int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho, int Wo,
                           float* stats, int* stat_blocks, orbit_stream_t stream);
+/* orbit_op_conv2d_plan (host only): what orbit_op_conv2d_ex / orbit_op_conv2d_train and the network plans launch for a conv
+ *   under the current options - the one rule every dense conv launch follows. gated, residual != 0: the launch has a
+ *   squeeze-excite gate / a residual input; flags as for orbit_op_conv2d_ex. stats_mode: 0 none, 1 BatchNorm statistics from the
+ *   epilogue (orbit_op_conv2d_train), 2 the statistics sweep that stores nothing else; dual_output != 0: raw and activated
+ *   outputs (the training forward under running statistics). With stats_mode = 0 and no dual output the launch is planned as
+ *   orbit_op_conv2d_ex supplies it (fragment-packed filter where the filter has one, split-K workspace where the conv splits),
+ *   otherwise as orbit_op_conv2d_train does (neither). row: buffer of 48 chars for the profiler row of the launch
+ *   (conv_igemm<..>, conv_bf3<..> or conv_pw_rgemm<..>); *ksplit K-ranges (1: not split) of *kt_per_split K-tiles (0: not
+ *   split); *m_tiles row blocks of statistics the launch emits (0: none). A form the launch refuses is refused here with the
+ *   same error. */
+int orbit_op_conv2d_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho, int Wo,
+                         int x_nchw, int pool2, int gated, int residual, int flags, int stats_mode, int dual_output, char* row,
+                         int* ksplit, int* kt_per_split, int* m_tiles);
 int orbit_op_dwconv2d_train(const float* x, const float* w, float* y, const float* in_scale, const float* in_shift,
                             int in_act, int B, int H, int W, int C, int K, int stride, int pad_top, int pad_left, int Ho,
                             int Wo, float* stats, orbit_stream_t stream);

@@ -102,9 +102,29 @@ struct ConvDesc : LayerGeom {
     float* y_raw = nullptr;
 };
 inline size_t conv_stats_floats(size_t M, int Cout) { return ((M + 31) / 32) * 2 * (size_t)Cout; }  // smallest tile: 32 rows
-// split-K (small output, long reduction): number of K splits launch_conv uses for this conv when scratch is provided
-// (1 = none) and the scratch it needs
-int conv_splitk(const ConvDesc& d);
+// What launch_conv runs for a conv: the one value the launcher dispatches from, the profiler row is named from and
+// orbit_op_conv2d_plan reports. conv_plan (csrc/conv_igemm.hip) is a pure host function and the only place that decides it.
+enum ConvFamily { CONV_IGEMM = 0, CONV_BF3 = 1, CONV_PW_RGEMM = 2 };
+struct ConvPlan {
+    int rc = ORBIT_OK;  // a refused form: the error launch_conv returns (the message is set)
+    int family = CONV_IGEMM;
+    int BM = 64, BN = 64, BK = 32;  // igemm and bf3: the tile (igemm's 32x32 is the form with four K-waves) and the K-tile
+    bool pool2 = false, gate = false, pw = false, ul = false, res_post = false, nchw = false;  // igemm instantiation flags (bf3: gate, pw)
+    bool stats = false, stats_only = false;  // igemm: the launch emits BatchNorm statistics; ... and stores nothing else
+    int ksplit = 1, kt_per_split = 0;        // igemm: split-K ranges (1 = whole-tile launch) and K-tiles of BK per range
+    int m_tiles = 0, n_tiles = 0;            // igemm and bf3
+    int kt = 0, cin_pad = 0;                 // igemm: the packed filter's K and per-tap channels (conv_pack_geom)
+    int T = 0, wk = 0;                       // pw_rgemm: 16-channel tiles per wave and K slices (pw_rgemm_form)
+};
+ConvPlan conv_plan(const ConvDesc& d);
+void conv_plan_name(const ConvPlan& pl, char name[48]);  // the profiler row of the launch
+// 128x32 instead of 64x64 tiles where the last 64-wide column tile would be mostly padding (igemm and bf3)
+inline bool conv_tile_narrow(int Cout) {
+    const double waste64 = (double)(cdiv(Cout, 64) * 64 - Cout) / Cout;
+    const double waste32 = (double)(cdiv(Cout, 32) * 32 - Cout) / Cout;
+    return Cout <= 32 || waste64 - waste32 >= 0.15;
+}
+// scratch a split-K launch of this conv needs (0: it does not split); launch_conv splits only when given it
 size_t conv_splitk_floats(const ConvDesc& d);
 
 // geometry of the packed weight matrix for a conv (shared by pack + launch)
@@ -125,9 +145,30 @@ int conv_frag_pack_weights(const float* w_oihw, float* w_frag, int Cin, int Cout
 bool pw_rgemm_supported(const ConvDesc& d);
 // pointwise convs on the bf16 matrix cores with both operands split three ways (csrc/conv_bf3.hip; option conv_bf3, opt-in)
 bool conv_bf3_supported(const ConvDesc& d);
-int launch_conv_bf3(const ConvDesc& d, hipStream_t s);
+int launch_conv_bf3(const ConvDesc& d, const ConvPlan& pl, hipStream_t s);
 bool pw_rgemm_preferred(const ConvDesc& d);  // where it measured faster than the LDS-tiled kernel (conv_rgemm = 1)
-int launch_pw_rgemm(const ConvDesc& d, hipStream_t s);
+void pw_rgemm_form(const ConvDesc& d, int& T, int& wk);  // what conv_plan records of the register GEMM's own plan
+int launch_pw_rgemm(const ConvDesc& d, const ConvPlan& pl, hipStream_t s);
+// The temporary packed filter of a single-operator entry: one stream-ordered allocation holding the packed form, the
+// fragment-packed form where asked for and the filter has one, and `extra_floats` of scratch behind them; freed on the stream
+// when it goes out of scope.
+struct TempPackedFilter {
+    float *packed = nullptr, *frag = nullptr, *extra = nullptr;
+    hipStream_t stream = nullptr;
+    int pack(const float* w_oihw, int Cin, int Cout, int KH, int KW, int x_nchw, bool want_frag, size_t extra_floats, hipStream_t s) {
+        const size_t nfl = (conv_packed_floats(Cin, Cout, KH, KW, x_nchw) + 63) & ~(size_t)63;
+        const size_t ffl = want_frag ? conv_frag_floats(Cin, Cout, KH, KW, x_nchw) : 0;
+        stream = s;
+        ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&packed), (nfl + ffl + extra_floats) * sizeof(float), s));
+        extra = packed + nfl + ffl;
+        if (int rc = conv_pack_weights(w_oihw, packed, Cin, Cout, KH, KW, x_nchw, s)) return rc;
+        if (ffl) frag = packed + nfl;
+        return ffl ? conv_frag_pack_weights(w_oihw, frag, Cin, Cout, s) : ORBIT_OK;
+    }
+    ~TempPackedFilter() {
+        if (packed) (void)hipFreeAsync(packed, stream);
+    }
+};
 // narrow gated pointwise projections with the squeeze-excite gate computed in the prologue (csrc/pw_stream.hip; option
 // pw_stream): y = scale * conv1x1(x * gate(partial)) + shift (+ residual), no activation
 struct PwStreamDesc {

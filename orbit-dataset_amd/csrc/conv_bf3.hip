@@ -335,13 +335,12 @@ bool conv_bf3_supported(const ConvDesc& d) {
 }
 
 template <int BM, int BN, int WGM, int WGN, int BK, bool PW>
-static int bf3_launch(Bf3Params& p, const ConvDesc& d, hipStream_t s) {
-    p.m_tiles = cdiv(p.M, BM), p.n_tiles = cdiv(p.Cout, BN);
+static int bf3_launch(const Bf3Params& p, const ConvDesc& d, const ConvPlan& pl, hipStream_t s) {
     const size_t pipe = (size_t)2 * 3 * (BM + BN) * BK * 2, epi = (size_t)BM * BN * 4;
     const size_t lds = pipe > epi ? pipe : epi;
     const int grid = p.m_tiles * p.n_tiles;
     char name[48];
-    snprintf(name, sizeof(name), "conv_bf3<%d,%d,%d%s%s>", BM, BN, BK, d.gate ? ",gate" : "", PW ? ",pw" : "");
+    conv_plan_name(pl, name);
     const double pix = (double)p.M;
     const int rec = prof_start(name, 2.0 * pix * d.Cout * d.KH * d.KW * d.Cin * d.prof_flop_scale,
                                4.0 * ((double)d.B * d.H * d.W * d.Cin + pix * d.Cout * (d.residual ? 2.0 : 1.0) +
@@ -358,27 +357,23 @@ static int bf3_launch(Bf3Params& p, const ConvDesc& d, hipStream_t s) {
 }
 
 template <bool PW>
-static int bf3_dispatch(Bf3Params& p, const ConvDesc& d, hipStream_t s) {
-    // tiles as conv_igemm.hip chooses them: 128x32 where a 64-wide last column tile would be mostly padding
-    const double waste64 = (double)(cdiv(d.Cout, 64) * 64 - d.Cout) / d.Cout;
-    const double waste32 = (double)(cdiv(d.Cout, 32) * 32 - d.Cout) / d.Cout;
-    const bool narrow = waste64 - waste32 >= 0.15;
-    const int bk = d.Cin % 32 == 0 ? 32 : 16;
-    if (narrow) return bk == 32 ? bf3_launch<128, 32, 4, 1, 32, PW>(p, d, s) : bf3_launch<128, 32, 4, 1, 16, PW>(p, d, s);
-    return bk == 32 ? bf3_launch<64, 64, 2, 2, 32, PW>(p, d, s) : bf3_launch<64, 64, 2, 2, 16, PW>(p, d, s);
+static int bf3_dispatch(const Bf3Params& p, const ConvDesc& d, const ConvPlan& pl, hipStream_t s) {
+    // the tile (conv_tile_narrow) and the K-tile are conv_plan's
+    if (pl.BM == 128) return pl.BK == 32 ? bf3_launch<128, 32, 4, 1, 32, PW>(p, d, pl, s) : bf3_launch<128, 32, 4, 1, 16, PW>(p, d, pl, s);
+    return pl.BK == 32 ? bf3_launch<64, 64, 2, 2, 32, PW>(p, d, pl, s) : bf3_launch<64, 64, 2, 2, 16, PW>(p, d, pl, s);
 }
 
-int launch_conv_bf3(const ConvDesc& d, hipStream_t s) {
-    ORBIT_REQUIRE(conv_bf3_supported(d), "conv_bf3: unsupported convolution");
+int launch_conv_bf3(const ConvDesc& d, const ConvPlan& pl, hipStream_t s) {
+    ORBIT_REQUIRE(pl.family == CONV_BF3, "conv_bf3: unsupported convolution");  // (conv_plan asked conv_bf3_supported)
     Bf3Params p;
+    p.m_tiles = pl.m_tiles, p.n_tiles = pl.n_tiles;
     p.x = d.x, p.w = d.w_packed, p.y = d.y, p.scale = d.scale, p.shift = d.shift, p.residual = d.residual, p.gate = d.gate;
     p.M = d.B * d.Ho * d.Wo, p.Cin = d.Cin, p.Cout = d.Cout, p.act = d.act;
     p.H = d.H, p.W = d.W, p.KH = d.KH, p.KW = d.KW, p.stride = d.stride, p.pad_t = d.pad_t, p.pad_l = d.pad_l;
     p.Ho = d.Ho, p.Wo = d.Wo, p.KT = d.KH * d.KW * d.Cin;  // (Cin % 16 == 0: conv_pack_weights pads nothing)
     p.fd_per = make_fastdiv((unsigned)(d.Ho * d.Wo)), p.fd_wo = make_fastdiv((unsigned)d.Wo);
     ORBIT_REQUIRE((long long)d.B * d.H * d.W * d.Cin < (1ll << 40) && p.M > 0, "conv_bf3: tensor too large");
-    const bool pw = d.KH == 1 && d.KW == 1 && d.pad_t == 0 && d.pad_l == 0 && d.stride == 1;
-    return pw ? bf3_dispatch<true>(p, d, s) : bf3_dispatch<false>(p, d, s);
+    return pl.pw ? bf3_dispatch<true>(p, d, pl, s) : bf3_dispatch<false>(p, d, pl, s);
 }
 
 }  // namespace orbit

@@ -574,17 +574,17 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* __restrict_
 }
 
 // K-tile width for a layer: the widest of 32/16/8 that divides Cin (stems: 32)
-static int choose_bk(int Cin, int x_nchw) {
+// (cap = option conv_bk, tuning sweeps: 0 = widest that divides Cin (default), else 8 / 16 / 32)
+static int bk_under(int Cin, int x_nchw, int cap) {
     if (x_nchw) return 32;
-    const int cap = get_option("conv_bk");  // tuning sweeps: 0 = widest that divides Cin (default), else 8 / 16 / 32
     if (Cin % 32 == 0 && (cap == 0 || cap >= 32)) return 32;
     if (Cin % 16 == 0 && (cap == 0 || cap >= 16)) return 16;
     return 8;
 }
+static int choose_bk(int Cin, int x_nchw) { return bk_under(Cin, x_nchw, x_nchw ? 0 : get_option("conv_bk")); }
 
-ConvPackGeom conv_pack_geom(int Cin, int Cout, int KH, int KW, int x_nchw) {
+static ConvPackGeom pack_geom(int Cin, int Cout, int KH, int KW, int x_nchw, int bk) {
     ConvPackGeom g;
-    const int bk = choose_bk(Cin, x_nchw);
     if (x_nchw) {
         g.cin_pad = Cin;
         g.kt = (int)align_up((size_t)KH * KW * Cin, bk);
@@ -594,6 +594,9 @@ ConvPackGeom conv_pack_geom(int Cin, int Cout, int KH, int KW, int x_nchw) {
     }
     g.cout_pad = (int)align_up((size_t)Cout, 128);
     return g;
+}
+ConvPackGeom conv_pack_geom(int Cin, int Cout, int KH, int KW, int x_nchw) {
+    return pack_geom(Cin, Cout, KH, KW, x_nchw, choose_bk(Cin, x_nchw));
 }
 
 size_t conv_packed_floats(int Cin, int Cout, int KH, int KW, int x_nchw) {
@@ -613,10 +616,9 @@ int conv_pack_weights(const float* w_oihw, float* w_packed, int Cin, int Cout, i
     return ORBIT_OK;
 }
 
-template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL, bool RPOST = false>
-static int launch_cfg2(ConvParams& p, hipStream_t s) {
-    p.m_tiles = cdiv(p.M, BM);
-    p.n_tiles = cdiv(p.Cout, BN);
+// One instantiation: its LDS size, the opt-in above 64 KiB, the profiler record and the launch
+template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL, bool RPOST>
+static int launch_cfg2(const ConvPlan& pl, const ConvParams& p, hipStream_t s) {
     const size_t lds_pipe = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (MODE == 1 ? 1024 : 0);  // + stem k table
     const size_t lds_epi = (size_t)WGK * (POOL2 ? BM / 4 : BM) * BN * sizeof(float);
     const size_t lds = lds_pipe > lds_epi ? lds_pipe : lds_epi;
@@ -631,9 +633,7 @@ static int launch_cfg2(ConvParams& p, hipStream_t s) {
     int rec = -1;
     if (conv_prof_enabled()) {  // per-launch event record (csrc/runtime.hip), one variant per instantiation
         char name[48];
-        snprintf(name, sizeof(name), "conv_igemm<%d,%d,%d,%s%s%s%s%s%s>", BM, BN, BK, MODE ? "nchw" : "nhwc",
-                 POOL2 ? ",pool2" : "", GATE ? ",gate" : "", PW ? ",pw" : "", RPOST ? ",rpost" : "",
-                 p.ksplit > 1 ? ",splitk" : WGK == 2 ? ",k2" : WGK == 4 ? ",k4" : (!p.y ? ",stats" : ""));
+        conv_plan_name(pl, name);
         const double pix = POOL2 ? (double)p.B * p.HoP * p.WoP * 4 : (double)p.B * p.Ho * p.Wo;
         const double flops = 2.0 * pix * p.Cout * p.KH * p.KW * p.Cin * p.prof_flop_scale;  // algorithmic (unpadded) FLOPs
         // algorithmic HBM bytes: input once, output once (pooled if fused), residual once, weights once
@@ -648,62 +648,24 @@ static int launch_cfg2(ConvParams& p, hipStream_t s) {
     return ORBIT_OK;
 }
 
-template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool RPOST = false>
-static int launch_cfg(ConvParams& p, hipStream_t s) {
-    // UL = staged loads without predicates, for pointwise convs (every element of a tile exists once the rows beyond M are
-    // clamped): no predicate, mask or select at all. In-process A/B on MI355X: +1..2 % on most pointwise layers, +16..20 % on
-    // the 128x32 projections, gated projections +3..21 % (the gate and tile loads then share one wait; predicated, hipcc
-    // waits for the tile load before it issues the gate load); 3x3 convs and the stems lose 1-4 % to the selects.
-    if constexpr (PW)
-        if (p.cin_pad == p.Cin)  // the clamped pointwise form has no K-padding predicate
-            return launch_cfg2<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, true>(p, s);
-    return launch_cfg2<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, false, RPOST>(p, s);
+// the sizes and layouts every conv kernel needs (shared with the host-only plan entry, which refuses what the launcher refuses)
+static int conv_shape_check(const ConvDesc& d) {
+    ORBIT_REQUIRE(d.B > 0 && d.H > 0 && d.W > 0 && d.Cin > 0 && d.Cout > 0 && d.Ho > 0 && d.Wo > 0,
+                  "conv: bad sizes");
+    ORBIT_REQUIRE(d.x_nchw ? d.Cin <= 4 : (d.Cin % 4 == 0),
+                  "conv: NHWC path needs Cin %% 4 == 0, NCHW stem path needs Cin <= 4 (Cin=%d)", d.Cin);
+    ORBIT_REQUIRE(!(d.pool2 && d.residual), "conv: pool2 cannot be combined with a residual input");
+    ORBIT_REQUIRE(d.Cout % 4 == 0, "conv: Cout %% 4 != 0 (Cout=%d): the epilogue writes float4 rows", d.Cout);
+    ORBIT_REQUIRE(!d.pool2 || (d.Ho >= 2 && d.Wo >= 2), "conv: pool2 needs Ho, Wo >= 2");
+    return ORBIT_OK;
 }
 
-template <int BK, int MODE, bool POOL2, bool GATE, bool PW, bool RPOST = false>
-static int launch_tiled(ConvParams& p, hipStream_t s) {
-    if (p.ksplit > 1) return launch_cfg<64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);  // split-K plans on 64x64 tiles
-    switch (get_option("conv_tile")) {  // 0 = the heuristic below; else force one of its three tilings (parity tests, A/B)
-        case 3: return launch_cfg<64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);
-        case 4: return launch_cfg<128, 32, 4, 1, 1, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);
-        case 6: if constexpr (MODE == 0 && !POOL2 && BK == 32) return launch_cfg<32, 32, 1, 1, 4, BK, MODE, POOL2, GATE, PW, RPOST>(p, s); break;
-        default: break;
-    }
-    // Measured sweep on MI355X (tools/conv_bench.py <net> sweep, in-process A/B over every layer shape of resnet18 @84
-    // and @224, efficientnet_b0 @224 and the set encoder): the 64x64 tile (36 KB LDS -> 4 blocks = 4 waves per SIMD) is
-    // the fastest on EVERY layer, including the large MFMA-bound ones (+10..24 % over 128x128 / 128x64, whose 2 blocks
-    // per CU cover the per-K-tile bubble worse). 128x32 wins only where the last 64-wide column tile would be mostly
-    // padding (Cout <= 32, or e.g. Cout = 80, 96, 144).
-    // (A second K-tile of staged loads in flight was also measured: 30 more VGPRs, -6..-17 % on the short-K layers,
-    // +-2 % on the long-K ones - removed.)
-    const double waste64 = (double)(cdiv(p.Cout, 64) * 64 - p.Cout) / p.Cout;
-    const double waste32 = (double)(cdiv(p.Cout, 32) * 32 - p.Cout) / p.Cout;
-    if (p.Cout <= 32 || waste64 - waste32 >= 0.15) return launch_cfg<128, 32, 4, 1, 1, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);
-    // fewer 64x64 tiles than CUs (resnet18 @84 layer4: 29 x 8 tiles for 256 CUs): 32x32 tiles with the four waves
-    // splitting K give 4x the blocks (-7..-11 % time on those layers; neutral or worse everywhere else)
-    if constexpr (MODE == 0 && !POOL2 && BK == 32)
-        if (cdiv(p.M, 64) * cdiv(p.Cout, 64) < 256) return launch_cfg<32, 32, 1, 1, 4, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);
-    return launch_cfg<64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW, RPOST>(p, s);
-}
-
-template <int MODE, bool POOL2, bool GATE, bool PW, bool RPOST = false>
-static int launch_bk(ConvParams& p, int bk, hipStream_t s) {
-    if constexpr (MODE == 1) {
-        return launch_tiled<32, 1, POOL2, false, false>(p, s);
-    } else {
-        if (bk == 32) return launch_tiled<32, 0, POOL2, GATE, PW, RPOST>(p, s);
-        if (bk == 16) return launch_tiled<16, 0, POOL2, GATE, PW, RPOST>(p, s);
-        return launch_tiled<8, 0, POOL2, GATE, PW, RPOST>(p, s);
-    }
-}
-
-// Split-K plan. A conv whose 64x64 tiling leaves the chip short of blocks but whose reduction is long (resnet18 @84
+// Split-K. A conv whose 64x64 tiling leaves the chip short of blocks but whose reduction is long (resnet18 @84
 // layer3/4: 1 800-7 200 output rows, K = 1 152-4 608; EfficientNet's 7x7 projections) is cut into S K-ranges: S x the
 // blocks, each writing a raw partial tile; conv_splitk_reduce_kernel sums them in split order and applies the epilogue.
-int conv_splitk(const ConvDesc& d) {
+// nk: the conv's K-tiles at choose_bk's width.
+static int splitk_count(const ConvDesc& d, int nk) {
     if (get_option("conv_splitk") == 0 || d.x_nchw || d.pool2 || d.Cout <= 32 || d.Cout % 4 != 0) return 1;
-    const ConvPackGeom g = conv_pack_geom(d.Cin, d.Cout, d.KH, d.KW, 0);
-    const int nk = g.kt / choose_bk(d.Cin, 0);
     const long tiles = (long)cdiv(d.B * d.Ho * d.Wo, 64) * cdiv(d.Cout, 64);
     // measured with the reduce pass included (tools/conv_bench.py <net> ab conv_splitk): -11..-18 % time at 232 tiles
     // (resnet18 @84 layer4), break-even at ~450 tiles (layer3, EfficientNet's 7x7 projections)
@@ -713,47 +675,165 @@ int conv_splitk(const ConvDesc& d) {
     while (S > 1 && cdiv(nk, S) < 6) --S;
     return S;
 }
+// (a function of the shape alone: the form checks of conv_plan want the launch's pointers, which a workspace layout has not)
 size_t conv_splitk_floats(const ConvDesc& d) {
-    const int S = conv_splitk(d);
+    const int bk = choose_bk(d.Cin, d.x_nchw);
+    const int S = splitk_count(d, pack_geom(d.Cin, d.Cout, d.KH, d.KW, d.x_nchw, bk).kt / bk);
     return S > 1 ? (size_t)S * d.B * d.Ho * d.Wo * d.Cout : 0;
 }
 
-int launch_conv(const ConvDesc& d, hipStream_t s) {
-    ORBIT_REQUIRE(d.x && d.w_packed && (d.y || d.stats_only), "conv: null pointer");
+// The plan of a launch: the one place that decides which kernel family serves a conv and, for the implicit GEMM, which
+// instantiation, how many K-ranges and whether the epilogue emits statistics. Every rule is a function of the layer and the
+// form of the launch, never of a frame's position in its batch.
+static int conv_plan_fill(const ConvDesc& d, ConvPlan& pl) {
     ORBIT_REQUIRE(!d.stats_only || (d.y == nullptr && d.stats && d.stats_blocks && !d.pool2 && !d.splitk_ws && !d.y_raw),
                   "conv: the statistics sweep stores nothing and needs the whole-tile statistics epilogue");
-    ORBIT_REQUIRE(d.B > 0 && d.H > 0 && d.W > 0 && d.Cin > 0 && d.Cout > 0 && d.Ho > 0 && d.Wo > 0,
-                  "conv: bad sizes");
-    ORBIT_REQUIRE(d.x_nchw ? d.Cin <= 4 : (d.Cin % 4 == 0),
-                  "conv: NHWC path needs Cin %% 4 == 0, NCHW stem path needs Cin <= 4 (Cin=%d)", d.Cin);
-    ORBIT_REQUIRE(!(d.pool2 && d.residual), "conv: pool2 cannot be combined with a residual input");
-    ORBIT_REQUIRE(d.Cout % 4 == 0, "conv: Cout %% 4 != 0 (Cout=%d): the epilogue writes float4 rows", d.Cout);
     const bool pw = !d.x_nchw && d.KH == 1 && d.KW == 1 && d.pad_t == 0 && d.pad_l == 0;
     // the post-activation skip is compiled for the layers that have it (timm ConvBnAct: a plain K x K NHWC conv)
     ORBIT_REQUIRE(!d.res_post || (d.residual && !pw && !d.x_nchw && !d.pool2 && !d.gate && !d.y_raw && !d.stats && !d.stats_only),
                   "conv: the post-activation skip needs a residual and a plain K x K NHWC conv (no gate, fused pooling, pointwise "
                   "form, statistics or dual output)");
-    if (d.stats_blocks) *d.stats_blocks = 0;
+    pl.gate = d.gate != nullptr;
     // opt-in: three-way bf16 split of both operands on the bf16 matrix cores (a function of the layer only, like every routing
     // rule here: a frame's bits do not depend on its batch)
     const int rg = d.stats_only ? 0 : get_option("conv_rgemm");
     if (!d.stats_only && (get_option("conv_bf3") & 1) && conv_bf3_supported(d) &&
-        !(rg == 1 && pw_rgemm_supported(d) && pw_rgemm_preferred(d)))  // (1152 -> 320 @7x7: 770 tiles on 768 slots - the register GEMM's 1 535 blocks win)
-        return launch_conv_bf3(d, s);
-    if (rg == 2 && pw_rgemm_supported(d)) return launch_pw_rgemm(d, s);
-    if (rg && pw_rgemm_supported(d) && (rg == 2 || pw_rgemm_preferred(d))) return launch_pw_rgemm(d, s);
+        !(rg == 1 && pw_rgemm_supported(d) && pw_rgemm_preferred(d))) {  // (1152 -> 320 @7x7: 770 tiles on 768 slots - the register GEMM's 1 535 blocks win)
+        pl.family = CONV_BF3;
+        if (conv_tile_narrow(d.Cout)) pl.BM = 128, pl.BN = 32;  // (Cout >= 40 here)
+        pl.BK = d.Cin % 32 == 0 ? 32 : 16;
+        pl.pw = d.KH == 1 && d.KW == 1 && d.pad_t == 0 && d.pad_l == 0 && d.stride == 1;
+        pl.m_tiles = cdiv(d.B * d.Ho * d.Wo, pl.BM), pl.n_tiles = cdiv(d.Cout, pl.BN);
+        return ORBIT_OK;
+    }
+    if (rg && pw_rgemm_supported(d) && (rg == 2 || pw_rgemm_preferred(d))) {
+        pl.family = CONV_PW_RGEMM;
+        pw_rgemm_form(d, pl.T, pl.wk);
+        return ORBIT_OK;
+    }
     ORBIT_REQUIRE(!d.gate || (!d.x_nchw && !d.pool2), "conv: the squeeze-excite gate needs the NHWC path without fused pooling");
-    const ConvPackGeom g = conv_pack_geom(d.Cin, d.Cout, d.KH, d.KW, d.x_nchw);
+    const int cap = d.x_nchw ? 0 : get_option("conv_bk");
+    const int bk0 = bk_under(d.Cin, d.x_nchw, cap);  // the packed filter's K-tile
+    const ConvPackGeom g = pack_geom(d.Cin, d.Cout, d.KH, d.KW, d.x_nchw, bk0);
+    const int M = d.pool2 ? d.B * (d.Ho / 2) * (d.Wo / 2) * 4 : d.B * d.Ho * d.Wo;
+    pl.nchw = d.x_nchw != 0, pl.pool2 = d.pool2 != 0, pl.pw = pw && !d.pool2, pl.res_post = d.res_post != 0;
+    // UL = staged loads without predicates, for pointwise convs (every element of a tile exists once the rows beyond M are
+    // clamped): no predicate, mask or select at all. In-process A/B on MI355X: +1..2 % on most pointwise layers, +16..20 % on
+    // the 128x32 projections, gated projections +3..21 % (the gate and tile loads then share one wait; predicated, hipcc
+    // waits for the tile load before it issues the gate load); 3x3 convs and the stems lose 1-4 % to the selects.
+    pl.ul = pl.pw && g.cin_pad == d.Cin;  // the clamped pointwise form has no K-padding predicate
+    pl.BK = bk0, pl.kt = g.kt, pl.cin_pad = g.cin_pad;
+    // K-tile of 16 where 32 would also divide Cin (the packed filter is the same: cin_pad and the k-order do not depend on
+    // BK when Cin % 32 == 0). Half the LDS stage = 7 instead of 4 blocks per CU; it pays (tools/conv_bench.py effnet_224 with
+    // ORBIT_CONV_BK=16, 200 frames) on the narrow HBM-bound projections - 32 -> 16 @112x112: 131 -> 115 us, 96 -> 24 @56x56:
+    // 79.5 -> 75.9 - and where the 64x64 tiling gives between one and two rounds of 4 blocks per CU, i.e. a second round that
+    // is mostly empty (480 -> 112 and 672 -> 112 @14x14, 1 226 tiles: 65.7 -> 60.2, 81.0 -> 73.7 us); elsewhere 32 is as good
+    // or better (fewer barriers per K: 1152 -> 320 @7x7 91.8 vs 96.1 us)
+    if (bk0 == 32 && pl.pw && cap == 0) {
+        const long tiles64 = (long)cdiv(M, 64) * cdiv(d.Cout, 64);
+        if ((d.Cout <= 32 && d.Cin <= 128) || (d.Cout > 32 && tiles64 > 1024 && tiles64 <= 1792)) pl.BK = 16;
+    }
+    // (the number of ranges counts K-tiles of the packed filter's width, their length K-tiles of the launch's)
+    pl.ksplit = d.splitk_ws ? splitk_count(d, g.kt / bk0) : 1;
+    pl.kt_per_split = pl.ksplit > 1 ? cdiv(g.kt / pl.BK, pl.ksplit) : 0;
+    // statistics of the raw outputs for a train-mode BatchNorm: whole-tile launches only (a split-K partial is not the output,
+    // the fused max-pool stores pooled rows)
+    pl.stats = d.stats && d.stats_blocks && pl.ksplit <= 1 && !d.pool2;
+    pl.stats_only = d.stats_only;
+    ORBIT_REQUIRE(!d.y_raw || (!d.pool2 && pl.ksplit <= 1 && (d.scale == nullptr) == (d.shift == nullptr)),
+                  "conv: the dual (raw + activated) output needs the whole-tile epilogue without fused pooling");
+    // The tile. Measured sweep on MI355X (tools/conv_bench.py <net> sweep, in-process A/B over every layer shape of resnet18
+    // @84 and @224, efficientnet_b0 @224 and the set encoder): the 64x64 tile (36 KB LDS -> 4 blocks = 4 waves per SIMD) is
+    // the fastest on EVERY layer, including the large MFMA-bound ones (+10..24 % over 128x128 / 128x64, whose 2 blocks
+    // per CU cover the per-K-tile bubble worse). 128x32 wins only where the last 64-wide column tile would be mostly
+    // padding (Cout <= 32, or e.g. Cout = 80, 96, 144: conv_tile_narrow).
+    // (A second K-tile of staged loads in flight was also measured: 30 more VGPRs, -6..-17 % on the short-K layers,
+    // +-2 % on the long-K ones - removed.)
+    // Fewer 64x64 tiles than CUs (resnet18 @84 layer4: 29 x 8 tiles for 256 CUs): 32x32 tiles with the four waves
+    // splitting K give 4x the blocks (-7..-11 % time on those layers; neutral or worse everywhere else). That form exists
+    // for NHWC without fused pooling at BK 32 only.
+    const bool k4_exists = !pl.nchw && !pl.pool2 && pl.BK == 32;
+    // option conv_tile: 0 = the heuristic; else force one of its three tilings (parity tests, A/B); split-K plans on 64x64
+    int tile = pl.ksplit > 1 ? 3 : get_option("conv_tile");
+    if (tile != 3 && tile != 4 && !(tile == 6 && k4_exists))
+        tile = conv_tile_narrow(d.Cout) ? 4 : (k4_exists && cdiv(M, 64) * cdiv(d.Cout, 64) < 256) ? 6 : 3;
+    pl.BM = tile == 4 ? 128 : tile == 6 ? 32 : 64, pl.BN = tile == 3 ? 64 : 32;
+    pl.m_tiles = cdiv(M, pl.BM), pl.n_tiles = cdiv(d.Cout, pl.BN);
+    return ORBIT_OK;
+}
+
+ConvPlan conv_plan(const ConvDesc& d) {
+    ConvPlan pl;
+    pl.rc = conv_plan_fill(d, pl);
+    return pl;
+}
+
+void conv_plan_name(const ConvPlan& pl, char name[48]) {
+    if (pl.family == CONV_PW_RGEMM)
+        snprintf(name, 48, "conv_pw_rgemm<%d,k%d%s>", pl.T, pl.wk, pl.gate ? ",gate" : "");
+    else if (pl.family == CONV_BF3)
+        snprintf(name, 48, "conv_bf3<%d,%d,%d%s%s>", pl.BM, pl.BN, pl.BK, pl.gate ? ",gate" : "", pl.pw ? ",pw" : "");
+    else
+        snprintf(name, 48, "conv_igemm<%d,%d,%d,%s%s%s%s%s%s>", pl.BM, pl.BN, pl.BK, pl.nchw ? "nchw" : "nhwc",
+                 pl.pool2 ? ",pool2" : "", pl.gate ? ",gate" : "", pl.pw ? ",pw" : "", pl.res_post ? ",rpost" : "",
+                 pl.ksplit > 1 ? ",splitk" : pl.BM == 32 ? ",k4" : pl.stats_only ? ",stats" : "");
+}
+
+// The instantiations of conv_igemm_kernel, keyed by the plan's fields. What is listed below is what exists: the NCHW stems at
+// BK 32 without a gate, four K-waves (32x32) only for NHWC without fused pooling at BK 32, UL only with PW, RPOST only for the
+// plain K x K form.
+static constexpr int conv_inst(int BM, int BK, bool nchw, bool pool2, bool gate, bool pw, bool ul, bool rpost) {
+    return BM | BK << 8 | nchw << 14 | pool2 << 15 | gate << 16 | pw << 17 | ul << 18 | rpost << 19;
+}
+#define ORBIT_CONV_INST(BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, UL, RPOST) \
+    case conv_inst(BM, BK, MODE, POOL2, GATE, PW, UL, RPOST):                        \
+        return launch_cfg2<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, UL, RPOST>(pl, p, s);
+#define ORBIT_CONV_TILES(BK, MODE, POOL2, GATE, PW, UL, RPOST)                \
+    ORBIT_CONV_INST(64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW, UL, RPOST)    \
+    ORBIT_CONV_INST(128, 32, 4, 1, 1, BK, MODE, POOL2, GATE, PW, UL, RPOST)
+#define ORBIT_CONV_NHWC(GATE, PW, UL, RPOST) /* no fused pooling: every BK, and the four K-waves at BK 32 */ \
+    ORBIT_CONV_TILES(32, 0, false, GATE, PW, UL, RPOST)                                                      \
+    ORBIT_CONV_TILES(16, 0, false, GATE, PW, UL, RPOST)                                                      \
+    ORBIT_CONV_TILES(8, 0, false, GATE, PW, UL, RPOST)                                                       \
+    ORBIT_CONV_INST(32, 32, 1, 1, 4, 32, 0, false, GATE, PW, UL, RPOST)
+static int launch_planned(const ConvPlan& pl, const ConvParams& p, hipStream_t s) {
+    switch (conv_inst(pl.BM, pl.BK, pl.nchw, pl.pool2, pl.gate, pl.pw, pl.ul, pl.res_post)) {
+        ORBIT_CONV_TILES(32, 1, false, false, false, false, false)  // NCHW stems
+        ORBIT_CONV_TILES(32, 1, true, false, false, false, false)
+        ORBIT_CONV_TILES(32, 0, true, false, false, false, false)  // NHWC with the fused 2x2 max-pool
+        ORBIT_CONV_TILES(16, 0, true, false, false, false, false)
+        ORBIT_CONV_TILES(8, 0, true, false, false, false, false)
+        ORBIT_CONV_NHWC(false, false, false, false)  // K x K
+        ORBIT_CONV_NHWC(true, false, false, false)   // gated K x K
+        ORBIT_CONV_NHWC(false, false, false, true)   // K x K with the skip after the activation
+        ORBIT_CONV_NHWC(false, true, false, false)   // pointwise with a K-padding predicate (cin_pad > Cin)
+        ORBIT_CONV_NHWC(false, true, true, false)    // pointwise
+        ORBIT_CONV_NHWC(true, true, false, false)    // gated pointwise, both
+        ORBIT_CONV_NHWC(true, true, true, false)
+    }
+    return set_err(ORBIT_ERR_ARG, "conv: no kernel for this plan");
+}
+#undef ORBIT_CONV_NHWC
+#undef ORBIT_CONV_TILES
+#undef ORBIT_CONV_INST
+
+int launch_conv(const ConvDesc& d, hipStream_t s) {
+    ORBIT_REQUIRE(d.x && d.w_packed && (d.y || d.stats_only), "conv: null pointer");
+    if (int rc = conv_shape_check(d)) return rc;
+    if (d.stats_blocks) *d.stats_blocks = 0;
+    const ConvPlan pl = conv_plan(d);
+    if (pl.rc != ORBIT_OK) return pl.rc;
+    if (pl.family == CONV_BF3) return launch_conv_bf3(d, pl, s);
+    if (pl.family == CONV_PW_RGEMM) return launch_pw_rgemm(d, pl, s);
     ConvParams p;
     p.x = d.x, p.w = d.w_packed, p.y = d.y, p.scale = d.scale, p.shift = d.shift;
     p.residual = d.residual, p.gate = d.gate;
     p.B = d.B, p.H = d.H, p.W = d.W, p.Cin = d.Cin, p.Cout = d.Cout, p.KH = d.KH, p.KW = d.KW;
     p.stride = d.stride, p.pad_t = d.pad_t, p.pad_l = d.pad_l, p.Ho = d.Ho, p.Wo = d.Wo;
     p.HoP = d.Ho / 2, p.WoP = d.Wo / 2;
-    p.KT = g.kt, p.cin_pad = g.cin_pad, p.act = d.act;
+    p.KT = pl.kt, p.cin_pad = pl.cin_pad, p.act = d.act;
     p.prof_flop_scale = d.prof_flop_scale;
     if (d.pool2) {
-        ORBIT_REQUIRE(p.HoP > 0 && p.WoP > 0, "conv: pool2 needs Ho, Wo >= 2");
         p.M = d.B * p.HoP * p.WoP * 4;
         p.fd_per = make_fastdiv((unsigned)(p.HoP * p.WoP)), p.fd_wo = make_fastdiv((unsigned)p.WoP);
     } else {
@@ -762,33 +842,12 @@ int launch_conv(const ConvDesc& d, hipStream_t s) {
     }
     p.fd_cin = make_fastdiv((unsigned)d.Cin), p.fd_kw = make_fastdiv((unsigned)d.KW);
     ORBIT_REQUIRE((long long)d.B * d.H * d.W * d.Cin < (1ll << 40) && p.M > 0, "conv: tensor too large");
-    int bk = choose_bk(d.Cin, d.x_nchw);
-    // K-tile of 16 where 32 would also divide Cin (the packed filter is the same: cin_pad and the k-order do not depend on
-    // BK when Cin % 32 == 0). Half the LDS stage = 7 instead of 4 blocks per CU; it pays (tools/conv_bench.py effnet_224 with
-    // ORBIT_CONV_BK=16, 200 frames) on the narrow HBM-bound projections - 32 -> 16 @112x112: 131 -> 115 us, 96 -> 24 @56x56:
-    // 79.5 -> 75.9 - and where the 64x64 tiling gives between one and two rounds of 4 blocks per CU, i.e. a second round that
-    // is mostly empty (480 -> 112 and 672 -> 112 @14x14, 1 226 tiles: 65.7 -> 60.2, 81.0 -> 73.7 us); elsewhere 32 is as good
-    // or better (fewer barriers per K: 1152 -> 320 @7x7 91.8 vs 96.1 us)
-    if (bk == 32 && pw && !d.pool2 && !d.x_nchw && get_option("conv_bk") == 0) {
-        const long tiles64 = (long)cdiv(p.M, 64) * cdiv(d.Cout, 64);
-        if ((d.Cout <= 32 && d.Cin <= 128) || (d.Cout > 32 && tiles64 > 1024 && tiles64 <= 1792)) bk = 16;
-    }
-    p.ksplit = d.splitk_ws ? conv_splitk(d) : 1;
-    p.kt_per_split = p.ksplit > 1 ? cdiv(g.kt / bk, p.ksplit) : 0;
+    p.ksplit = pl.ksplit, p.kt_per_split = pl.kt_per_split, p.m_tiles = pl.m_tiles, p.n_tiles = pl.n_tiles;
     p.part = d.splitk_ws;
-    // statistics of the raw outputs for a train-mode BatchNorm: whole-tile launches only (a split-K partial is not the output,
-    // the fused max-pool stores pooled rows)
-    p.stats = (d.stats && d.stats_blocks && p.ksplit <= 1 && !d.pool2) ? d.stats : nullptr;
-    ORBIT_REQUIRE(!d.y_raw || (!d.pool2 && p.ksplit <= 1 && (d.scale == nullptr) == (d.shift == nullptr)),
-                  "conv: the dual (raw + activated) output needs the whole-tile epilogue without fused pooling");
+    p.stats = pl.stats ? d.stats : nullptr;
     p.y_raw = d.y_raw;
-    int rc;
-    if (d.x_nchw) rc = d.pool2 ? launch_bk<1, true, false, false>(p, bk, s) : launch_bk<1, false, false, false>(p, bk, s);
-    else if (pw && !d.pool2) rc = d.gate ? launch_bk<0, false, true, true>(p, bk, s) : launch_bk<0, false, false, true>(p, bk, s);
-    else if (d.gate) rc = launch_bk<0, false, true, false>(p, bk, s);
-    else if (d.res_post) rc = launch_bk<0, false, false, false, true>(p, bk, s);
-    else rc = d.pool2 ? launch_bk<0, true, false, false>(p, bk, s) : launch_bk<0, false, false, false>(p, bk, s);
-    if (rc == ORBIT_OK && p.stats) *d.stats_blocks = p.m_tiles;  // (launch_cfg2 set the tiling it chose)
+    const int rc = launch_planned(pl, p, s);
+    if (rc == ORBIT_OK && pl.stats) *d.stats_blocks = pl.m_tiles;
     if (rc != ORBIT_OK || p.ksplit <= 1) return rc;
     const size_t mn4 = (size_t)p.M * p.Cout / 4;
     const int blocks = (int)std::min<size_t>((mn4 + 255) / 256, 4096);
@@ -818,22 +877,15 @@ int orbit_op_conv2d_train(const float* x, int x_nchw, const float* w, float* y, 
                           float* stats, int* stat_blocks, orbit_stream_t stream) {
     ORBIT_REQUIRE(x && w && y && stats && stat_blocks, "op_conv2d_train: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    const size_t nfl = conv_packed_floats(Cin, Cout, KH, KW, x_nchw);
     const size_t M = (size_t)B * Ho * Wo;
-    const size_t pfl = bn_partial_floats((M + 31) / 32, Cout);
-    float* tmp = nullptr;
-    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (nfl + pfl + 64) * sizeof(float), s));
-    float* part = tmp + ((nfl + 63) & ~(size_t)63);
-    int rc = conv_pack_weights(w, tmp, Cin, Cout, KH, KW, x_nchw, s);
-    if (rc == ORBIT_OK) {
-        ConvDesc d;
-        d.x = x, d.w_packed = tmp, d.y = y, d.gate = gate, d.x_nchw = x_nchw;
-        d.geom() = LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
-        d.stats = part, d.stats_blocks = stat_blocks;
-        rc = launch_conv(d, s);
-        if (rc == ORBIT_OK && *stat_blocks > 0) rc = launch_sum_partials(part, *stat_blocks, Cout, stats, s);
-    }
-    (void)hipFreeAsync(tmp, s);
+    TempPackedFilter f;  // (+ the statistics partials)
+    if (int rc = f.pack(w, Cin, Cout, KH, KW, x_nchw, false, bn_partial_floats((M + 31) / 32, Cout), s)) return rc;
+    ConvDesc d;
+    d.x = x, d.w_packed = f.packed, d.y = y, d.gate = gate, d.x_nchw = x_nchw;
+    d.geom() = LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
+    d.stats = f.extra, d.stats_blocks = stat_blocks;
+    int rc = launch_conv(d, s);
+    if (rc == ORBIT_OK && *stat_blocks > 0) rc = launch_sum_partials(f.extra, *stat_blocks, Cout, stats, s);
     return rc;
 }
 
@@ -853,27 +905,52 @@ int orbit_op_conv2d_ex(const float* x, int x_nchw, const float* w, float* y, con
     ORBIT_REQUIRE((flags & ~ORBIT_CONV_RESIDUAL_POST_ACT) == 0, "op_conv2d_ex: unknown flags 0x%x", flags);
     ORBIT_REQUIRE(KH > 0 && KW > 0 && stride > 0, "op_conv2d: bad kernel geometry");
     hipStream_t s = (hipStream_t)stream;
-    float* wp = nullptr;
-    const size_t nfl = (conv_packed_floats(Cin, Cout, KH, KW, x_nchw) + 63) & ~(size_t)63;
-    const size_t ffl = conv_frag_floats(Cin, Cout, KH, KW, x_nchw);
-    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&wp), (nfl + ffl) * sizeof(float), s));
-    int rc = conv_pack_weights(w, wp, Cin, Cout, KH, KW, x_nchw, s);
-    if (rc == ORBIT_OK && ffl) rc = conv_frag_pack_weights(w, wp + nfl, Cin, Cout, s);
-    if (rc == ORBIT_OK) {
-        ConvDesc d;
-        d.w_frag = ffl ? wp + nfl : nullptr;
-        d.x = x, d.w_packed = wp, d.y = y, d.scale = scale, d.shift = shift, d.residual = residual;
-        d.geom() = LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
-        d.gate = gate, d.act = act, d.pool2 = pool2, d.x_nchw = x_nchw, d.res_post = (flags & ORBIT_CONV_RESIDUAL_POST_ACT) ? 1 : 0;
-        float* sk = nullptr;
-        const size_t skf = conv_splitk_floats(d);
-        if (skf) ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&sk), skf * sizeof(float), s));
-        d.splitk_ws = sk;
-        rc = launch_conv(d, s);
-        if (sk) (void)hipFreeAsync(sk, s);
-    }
-    (void)hipFreeAsync(wp, s);
+    TempPackedFilter f;
+    if (int rc = f.pack(w, Cin, Cout, KH, KW, x_nchw, true, 0, s)) return rc;
+    ConvDesc d;
+    d.x = x, d.w_packed = f.packed, d.w_frag = f.frag, d.y = y, d.scale = scale, d.shift = shift, d.residual = residual;
+    d.geom() = LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
+    d.gate = gate, d.act = act, d.pool2 = pool2, d.x_nchw = x_nchw, d.res_post = (flags & ORBIT_CONV_RESIDUAL_POST_ACT) ? 1 : 0;
+    float* sk = nullptr;
+    const size_t skf = conv_splitk_floats(d);
+    if (skf) ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&sk), skf * sizeof(float), s));
+    d.splitk_ws = sk;
+    const int rc = launch_conv(d, s);
+    if (sk) (void)hipFreeAsync(sk, s);
     return rc;
+}
+
+/* Host only: what launch_conv runs for this conv, as conv_plan decides it under the current options. The launch is described
+ * as the single-operator entries supply it: with stats_mode = 0 and no dual output as orbit_op_conv2d_ex (the fragment-packed
+ * filter where the filter has one, the split-K workspace where the conv splits); with stats_mode = 1 (statistics from the
+ * epilogue), 2 (the statistics sweep, nothing stored) or dual_output (raw + activated outputs) as orbit_op_conv2d_train and the
+ * training forward (neither). row[48] receives the profiler row of the launch; *m_tiles its row blocks when it emits
+ * statistics, else 0. A form launch_conv refuses is refused here with the same error. */
+int orbit_op_conv2d_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho, int Wo,
+                         int x_nchw, int pool2, int gated, int residual, int flags, int stats_mode, int dual_output, char* row,
+                         int* ksplit, int* kt_per_split, int* m_tiles) {
+    ORBIT_REQUIRE(row && ksplit && kt_per_split && m_tiles, "op_conv2d_plan: null pointer");
+    ORBIT_REQUIRE((flags & ~ORBIT_CONV_RESIDUAL_POST_ACT) == 0, "op_conv2d_plan: unknown flags 0x%x", flags);
+    ORBIT_REQUIRE(KH > 0 && KW > 0 && stride > 0 && stats_mode >= 0 && stats_mode <= 2, "op_conv2d_plan: bad kernel geometry");
+    static float some[1];  // stands for every buffer the launch would be given: the plan looks at which are there, not into them
+    static int blocks;
+    ConvDesc d;
+    d.geom() = LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
+    d.x_nchw = x_nchw, d.pool2 = pool2, d.res_post = (flags & ORBIT_CONV_RESIDUAL_POST_ACT) ? 1 : 0;
+    d.gate = gated ? some : nullptr, d.residual = residual ? some : nullptr;
+    if (stats_mode) d.stats = some, d.stats_blocks = &blocks;
+    d.stats_only = stats_mode == 2;
+    d.y_raw = dual_output ? some : nullptr;
+    if (int rc = conv_shape_check(d)) return rc;
+    if (!stats_mode && !dual_output) {
+        d.w_frag = conv_frag_floats(Cin, Cout, KH, KW, x_nchw) ? some : nullptr;
+        d.splitk_ws = conv_splitk_floats(d) ? some : nullptr;
+    }
+    const ConvPlan pl = conv_plan(d);
+    if (pl.rc != ORBIT_OK) return pl.rc;
+    conv_plan_name(pl, row);
+    *ksplit = pl.ksplit, *kt_per_split = pl.kt_per_split, *m_tiles = pl.stats ? pl.m_tiles : 0;
+    return ORBIT_OK;
 }
 
 }  // extern "C"

@@ -121,6 +121,13 @@ struct Op {
         if (kind == OP_MAXPOOL) return LayerGeom{B, H, W, Cin, Cout, pool_k, pool_k, stride, pool_pad, pool_pad, Ho, Wo};
         return LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo};
     }
+    // an OP_CONV at batch B as launch_conv takes it, all but the pointers
+    ConvDesc conv_desc(int B) const {
+        ConvDesc d;
+        d.geom() = geom(B);
+        d.act = act, d.pool2 = pool2, d.x_nchw = x_nchw, d.res_post = res_post;
+        return d;
+    }
     // the fused 2x2/2 max-pool behind an OP_CONV with pool2
     LayerGeom pool2_geom(int B) const { return LayerGeom{B, Ho, Wo, Cout, Cout, 2, 2, 2, 0, 0, Ho / 2, Wo / 2}; }
 };
@@ -278,11 +285,9 @@ struct orbit_extractor {
         packed_floats += conv_packed_floats(Cin, Cout, K, K, x_nchw);
         // the fragment-ordered copy of a pointwise filter only where the register GEMM will be asked for it (csrc/pw_rgemm.hip:
         // conv_rgemm = 1 one layer class, = 2 every supported conv) - it doubles the packed bytes and the pack work of a layer
-        ConvDesc shape;
-        shape.geom() = o.geom(0);
         const int rg = get_option("conv_rgemm");
         if (stride == 1 && pad_t == 0 && pad_l == 0 && !pool2 && conv_frag_floats(Cin, Cout, K, K, x_nchw) &&
-            (rg == 2 || (rg == 1 && pw_rgemm_preferred(shape)))) {
+            (rg == 2 || (rg == 1 && pw_rgemm_preferred(o.conv_desc(0))))) {
             packed_floats = (packed_floats + 63) & ~(size_t)63;
             o.frag_off = packed_floats;
             packed_floats += conv_frag_floats(Cin, Cout, K, K, x_nchw);

@@ -343,12 +343,6 @@ static int build_set_encoder(orbit_extractor* fe, int H, int W) {
 struct WsLayout {
     size_t buf[3], pooled, gate, fold, splitk, total;
 };
-static ConvDesc conv_shape(const Op& o, int B) {  // the fields the split-K plan looks at
-    ConvDesc d;
-    d.geom() = o.geom(B);
-    d.act = o.act, d.pool2 = o.pool2, d.x_nchw = o.x_nchw;
-    return d;
-}
 static WsLayout ws_layout(const orbit_extractor* fe, int B) {
     WsLayout L;
     size_t off = 0;
@@ -365,7 +359,7 @@ static WsLayout ws_layout(const orbit_extractor* fe, int B) {
     L.splitk = off;  // partial tiles of the largest split-K conv at this batch size
     size_t skf = 0;
     for (const Op& o : fe->ops)
-        if (o.kind == OP_CONV) skf = std::max(skf, conv_splitk_floats(conv_shape(o, B)));
+        if (o.kind == OP_CONV) skf = std::max(skf, conv_splitk_floats(o.conv_desc(B)));
     off += align_up(skf * sizeof(float), 256);
     L.total = off;
     return L;
@@ -575,6 +569,24 @@ static bool se_in_projection(const orbit_extractor_t* fe, size_t i) {
            c.Ho == c.H && c.Wo == c.W && pw_stream_supported(c.Cin, c.Cout, c.H, c.W);
 }
 
+// What serves op `oi` of the inference plan where the op kind leaves a choice (OP_CONV, OP_SE); `prev` is the answer for op
+// oi - 1, so a squeeze-excite block asks se_in_projection once
+enum ServedBy {
+    BY_OWN_LAUNCHER,  // launch_conv / launch_se_gate2, and every other op kind
+    BY_STEM_DIRECT,   // EfficientNet stem: LDS-staged input rows + VALU (csrc/stem.hip) instead of the element-wise gather
+    BY_PW_STREAM,     // gated projection that computes the gate of the OP_SE before it in its prologue (csrc/pw_stream.hip)
+    BY_PROJECTION     // OP_SE skipped: the projection after it is BY_PW_STREAM
+};
+static ServedBy served_by(const orbit_extractor_t* fe, size_t oi, ServedBy prev) {
+    const Op& o = fe->ops[oi];
+    if (o.kind == OP_SE) return se_in_projection(fe, oi) ? BY_PROJECTION : BY_OWN_LAUNCHER;
+    if (o.kind != OP_CONV) return BY_OWN_LAUNCHER;
+    if (o.x_nchw && !o.pool2 && o.res < 0 && o.bn >= 0 && stem_direct_supported(o.Cin, o.Cout, o.KH, o.stride, o.W, o.act) &&
+        o.KH == o.KW)
+        return BY_STEM_DIRECT;
+    return prev == BY_PROJECTION ? BY_PW_STREAM : BY_OWN_LAUNCHER;
+}
+
 static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const float* film_gamma, const float* film_beta,
                     float* feats, void* workspace, hipStream_t s) {
     const WsLayout L = ws_layout(fe, B);
@@ -597,20 +609,20 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
         ORBIT_LAUNCH_CHECK();
         scale = fs, shift = fs + fe->fold_floats;
     }
+    ServedBy by = BY_OWN_LAUNCHER;
     for (size_t oi = 0; oi < fe->ops.size(); ++oi) {
         const Op& o = fe->ops[oi];
+        by = served_by(fe, oi, by);
         int rc = ORBIT_OK;
         switch (o.kind) {
             case OP_CONV: {
-                if (o.x_nchw && !o.pool2 && o.res < 0 && o.bn >= 0 &&
-                    stem_direct_supported(o.Cin, o.Cout, o.KH, o.stride, o.W, o.act) && o.KH == o.KW) {
-                    // EfficientNet stem: LDS-staged input rows + VALU (csrc/stem.hip) instead of the element-wise gather
+                if (by == BY_STEM_DIRECT) {
                     rc = launch_stem_direct(buf(o.in), fe->param(o.weight), scale + fe->bns[o.bn].fold_off,
                                             shift + fe->bns[o.bn].fold_off, buf(o.out), B, o.H, o.W, o.pad_t, o.pad_l, o.Ho,
                                             o.Wo, s);
                     break;
                 }
-                if (oi > 0 && se_in_projection(fe, oi - 1)) {
+                if (by == BY_PW_STREAM) {
                     const Op& se = fe->ops[oi - 1];
                     PwStreamDesc d;
                     d.x = buf(o.in), d.w_packed = fe->d_packed + o.packed_off, d.y = buf(o.out);
@@ -623,15 +635,13 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                     rc = launch_pw_stream(d, s);
                     break;
                 }
-                ConvDesc d;
+                ConvDesc d = o.conv_desc(B);
                 d.x = buf(o.in), d.w_packed = fe->d_packed + o.packed_off, d.y = buf(o.out);
                 d.w_frag = o.frag_off != SIZE_MAX ? fe->d_packed + o.frag_off : nullptr;
                 d.scale = o.bn >= 0 ? scale + fe->bns[o.bn].fold_off : nullptr;
                 d.shift = o.bn >= 0 ? shift + fe->bns[o.bn].fold_off : nullptr;
                 d.residual = o.res >= 0 ? buf(o.res) : nullptr;
                 d.gate = o.use_gate ? buf(BUF_GATE) : nullptr;
-                d.geom() = o.geom(B);
-                d.act = o.act, d.pool2 = o.pool2, d.x_nchw = o.x_nchw, d.res_post = o.res_post;
                 d.splitk_ws = reinterpret_cast<float*>(ws + L.splitk);
                 rc = launch_conv(d, s);
                 break;
@@ -661,7 +671,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                 rc = launch_avgpool(buf(o.in), buf(o.out), B, o.H * o.W, o.Cin, s);
                 break;
             case OP_SE:
-                if (se_in_projection(fe, oi)) break;  // the projection computes the gate in its prologue
+                if (by == BY_PROJECTION) break;  // the projection computes the gate in its prologue
                 rc = launch_se_gate2(buf(BUF_POOLED), o.se_chunks, o.se_hw, fe->param(o.se_w1),
                                      fe->param(o.se_b1), fe->d_packed + o.packed_off,
                                      fe->param(o.se_b2), buf(BUF_GATE), B, o.Cin, o.R, s);

@@ -539,9 +539,9 @@ static int train_forward_run(orbit_extractor_t* fe, const float* frames, int B, 
                 cur[o.out] = nullptr;  // the fused front below re-expands in LDS
                 continue;
             }
-            ConvDesc d;
-            d.geom() = o.geom(B);
-            d.x = xin, d.w_packed = fe->d_packed + o.packed_off, d.y = fl(L.y[i]), d.x_nchw = o.x_nchw;
+            ConvDesc d = o.conv_desc(B);
+            d.act = ORBIT_ACT_NONE, d.pool2 = 0, d.res_post = 0;  // the raw conv: its epilogue is ops of their own here (but CONV_DUAL)
+            d.x = xin, d.w_packed = fe->d_packed + o.packed_off, d.y = fl(L.y[i]);
             // squeeze-excite: the projection multiplies the gate into its A operand on the fly (as the inference plan does)
             if (o.use_gate) d.gate = cur[BUF_GATE];
             int stat_blocks = 0;  // train-mode BatchNorm: column sums of the raw outputs come from the conv's epilogue

@@ -297,14 +297,17 @@ static int pwr_dispatch(int T, const PwrParams& p, int grid, size_t lds, hipStre
     }
 }
 
-int launch_pw_rgemm(const ConvDesc& d, hipStream_t s) {
-    ORBIT_REQUIRE(pw_rgemm_supported(d), "pw_rgemm: unsupported convolution");
+void pw_rgemm_form(const ConvDesc& d, int& T, int& wk) {
+    (void)pwr_plan(d.B * d.H * d.W, d.Cin, d.Cout, d.gate != nullptr, T, wk);
+}
+
+int launch_pw_rgemm(const ConvDesc& d, const ConvPlan& pl, hipStream_t s) {
+    ORBIT_REQUIRE(pl.family == CONV_PW_RGEMM, "pw_rgemm: unsupported convolution");  // (conv_plan asked pw_rgemm_supported)
     PwrParams p;
     p.x = d.x, p.wf = d.w_frag, p.y = d.y, p.scale = d.scale, p.shift = d.shift, p.residual = d.residual, p.gate = d.gate;
     p.M = d.B * d.H * d.W, p.K = d.Cin, p.Cout = d.Cout, p.act = d.act;
     p.nchunk = d.Cin / 16;
-    int T, wk;
-    (void)pwr_plan(p.M, p.K, p.Cout, d.gate != nullptr, T, wk);
+    const int T = pl.T, wk = pl.wk;
     p.wk = wk, p.cps = pwr_slice(p.nchunk, wk);
     p.n_groups = cdiv(cdiv(d.Cout, 16), T);
     p.m_tiles = cdiv(p.M, 32);
@@ -313,7 +316,7 @@ int launch_pw_rgemm(const ConvDesc& d, hipStream_t s) {
     const int grid = cdiv(p.m_tiles, 4 / wk) * p.n_groups;
     const size_t lds = wk > 1 ? (size_t)(4 / wk) * (wk - 1) * 2 * T * 64 * sizeof(f32x4) : 0;
     char name[48];
-    snprintf(name, sizeof(name), "conv_pw_rgemm<%d,k%d%s>", T, wk, d.gate ? ",gate" : "");
+    conv_plan_name(pl, name);
     const double pix = (double)p.M;
     const int rec = prof_start(name, 2.0 * pix * d.Cout * d.Cin * d.prof_flop_scale,
                                4.0 * (pix * d.Cin + pix * d.Cout * (d.residual ? 2.0 : 1.0) + (double)d.Cout * d.Cin), s,

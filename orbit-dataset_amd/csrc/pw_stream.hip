@@ -235,32 +235,22 @@ int orbit_op_pw_stream(const float* x, const float* w, const float* scale, const
     ORBIT_REQUIRE(x && w && scale && shift && partial && w1 && b1 && w2t && b2 && y, "op_pw_stream: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const bool fused = get_option("conv_rgemm") && pw_stream_supported(Cin, Cout, H, W);
-    const size_t nfl = (conv_packed_floats(Cin, Cout, 1, 1, 0) + 63) & ~(size_t)63;
-    const size_t ffl = conv_frag_floats(Cin, Cout, 1, 1, 0);
-    const size_t gfl = (fused || gate_out) ? 0 : (size_t)B * Cin;
-    float* wp = nullptr;
-    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&wp), (nfl + ffl + gfl) * sizeof(float), s));
-    int rc = conv_pack_weights(w, wp, Cin, Cout, 1, 1, 0, s);
-    if (rc == ORBIT_OK && ffl) rc = conv_frag_pack_weights(w, wp + nfl, Cin, Cout, s);
-    if (rc == ORBIT_OK && fused) {
+    TempPackedFilter f;  // (+ the gate, where the caller does not take it)
+    if (int rc = f.pack(w, Cin, Cout, 1, 1, 0, true, (fused || gate_out) ? 0 : (size_t)B * Cin, s)) return rc;
+    if (fused) {
         PwStreamDesc d;
-        d.x = x, d.w_packed = wp, d.y = y, d.scale = scale, d.shift = shift, d.residual = residual;
+        d.x = x, d.w_packed = f.packed, d.y = y, d.scale = scale, d.shift = shift, d.residual = residual;
         d.partial = partial, d.chunks = chunks, d.se_hw = H * W, d.w1 = w1, d.b1 = b1, d.w2t = w2t, d.b2 = b2, d.R = R;
         d.gate_out = gate_out, d.B = B, d.H = H, d.W = W, d.Cin = Cin, d.Cout = Cout;
-        rc = launch_pw_stream(d, s);
-    } else if (rc == ORBIT_OK) {
-        float* gate = gate_out ? gate_out : wp + nfl + ffl;
-        rc = launch_se_gate2(partial, chunks, H * W, w1, b1, w2t, b2, gate, B, Cin, R, s);
-        if (rc == ORBIT_OK) {
-            ConvDesc d;
-            d.x = x, d.w_packed = wp, d.w_frag = ffl ? wp + nfl : nullptr, d.y = y, d.scale = scale, d.shift = shift;
-            d.residual = residual, d.gate = gate;
-            d.geom() = LayerGeom{B, H, W, Cin, Cout, 1, 1, 1, 0, 0, H, W};
-            rc = launch_conv(d, s);  // (no split-K workspace: as the plan, these layers never split)
-        }
+        return launch_pw_stream(d, s);
     }
-    (void)hipFreeAsync(wp, s);
-    return rc;
+    float* gate = gate_out ? gate_out : f.extra;
+    if (int rc = launch_se_gate2(partial, chunks, H * W, w1, b1, w2t, b2, gate, B, Cin, R, s)) return rc;
+    ConvDesc d;
+    d.x = x, d.w_packed = f.packed, d.w_frag = f.frag, d.y = y, d.scale = scale, d.shift = shift;
+    d.residual = residual, d.gate = gate;
+    d.geom() = LayerGeom{B, H, W, Cin, Cout, 1, 1, 1, 0, 0, H, W};
+    return launch_conv(d, s);  // (no split-K workspace: as the plan, these layers never split)
 }
 
 }  // extern "C"

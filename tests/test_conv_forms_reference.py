@@ -7,14 +7,71 @@
   * one_sign: dropping the smallest 8-deep K-group (in the kernel's own k order) moves an output by at least 100 gates;
   * normal: every ReLU / SiLU case has pre-activations of both signs; the pool2 `neg` cases have none above zero;
   * the stem_fast shapes have 64-row tiles on both sides of the interior fast path, by enumeration of (b, ho, wo);
-  * the K-tile ranges quoted for the split-K cases follow from Cin, KH * KW and BK by arithmetic.
-Which tile a shape gets is NOT restated here: the GPU file's profiler assertion is the check of the launch rules."""
+  * the K-tile ranges quoted for the split-K cases follow from Cin, KH * KW and BK by arithmetic;
+  * the launch rule itself, conv_plan of csrc/conv_igemm.hip through the host-only orbit_op_conv2d_plan (the library must be
+    built): under each case's own options it names exactly the case's row, cuts K into the quoted ranges and announces
+    ceil(M / BM) statistics blocks; the forms the launcher refuses are refused with the launcher's message.
+The GPU file's profiler assertion is the proof that the launcher follows the plan."""
+import ctypes
+
 import pytest
 import torch
 
 import test_gpu_conv_forms as T
+from orbit_dataset_amd import _lib
 
 CASES = {c["name"]: c for c in T.CASES}
+
+
+def plan(lib, geom, gated=0, nchw=0, pool2=0, residual=0, flags=0, stats_mode=0, dual=0):
+    """(rc, row, ksplit, kt_per_split, m_tiles) of orbit_op_conv2d_plan; geom in the table's order."""
+    B, Cin, H, W, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo = geom
+    row = ctypes.create_string_buffer(48)
+    ks, per, mt = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    rc = lib.orbit_op_conv2d_plan(B, H, W, Cin, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo, nchw, pool2, gated, residual, flags,
+                                  stats_mode, dual, row, ctypes.byref(ks), ctypes.byref(per), ctypes.byref(mt))
+    return rc, row.value.decode(), ks.value, per.value, mt.value
+
+
+def plan_case(lib, c):
+    f = c["flags"]
+    with T.options(lib, **dict({"conv_tile": 0, "conv_bk": 0, "conv_splitk": 1, "conv_rgemm": 0, "conv_bf3": 0}, **c["opts"])):
+        return plan(lib, c["geom"], gated=int("gate" in f), nchw=int("nchw" in f), pool2=int("pool2" in f), residual=int("res" in f))
+
+
+@pytest.mark.parametrize("case", T.CASES, ids=T.CASE_IDS)
+def test_plan_names_the_row_of_the_table(lib, case):
+    rc, row, ksplit, per, m_tiles = plan_case(lib, case)
+    assert rc == 0, _lib.last_error()
+    assert row == case["expect"]
+    assert (ksplit > 1) == case["expect"].endswith(",splitk>") and (per > 0) == (ksplit > 1) and m_tiles == 0
+
+
+@pytest.mark.parametrize("name", sorted(T.SPLITK_RANGES))
+def test_plan_cuts_k_into_the_quoted_ranges(lib, name):
+    rc, row, ksplit, per, _ = plan_case(lib, CASES[name])
+    ranges = T.SPLITK_RANGES[name]
+    assert rc == 0 and ksplit == len(ranges) and per == ranges[0], (row, ksplit, per)
+
+
+@pytest.mark.parametrize("name,geom,gated,x_nchw,tile,expect,BM", T.STATS_CASES, ids=[c[0] for c in T.STATS_CASES])
+def test_plan_announces_the_statistics_blocks(lib, name, geom, gated, x_nchw, tile, expect, BM):
+    M = geom[0] * geom[10] * geom[11]
+    with T.options(lib, conv_tile=tile, conv_bk=0, conv_rgemm=0, conv_bf3=0):
+        rc, row, ksplit, per, m_tiles = plan(lib, geom, gated=int(gated), nchw=x_nchw, stats_mode=1)
+    assert rc == 0, _lib.last_error()
+    assert row == expect and (ksplit, per) == (1, 0) and m_tiles == -(-M // BM)
+
+
+@pytest.mark.parametrize("kwargs,fragment", [
+    (dict(geom=(1, 64, 5, 13, 68, 1, 1, 1, 0, 0, 5, 13), residual=1, flags=1), "the post-activation skip needs a residual and a plain K x K NHWC conv"),
+    (dict(geom=(1, 64, 12, 10, 64, 3, 3, 1, 1, 1, 12, 10), gated=1, pool2=1), "the squeeze-excite gate needs the NHWC path without fused pooling"),
+    (dict(geom=(1, 64, 12, 10, 64, 3, 3, 1, 1, 1, 12, 10), dual=1, pool2=1), "the dual (raw + activated) output needs the whole-tile epilogue without fused pooling"),
+], ids=["res_post_pointwise", "gate_pool2", "dual_pool2"])
+def test_plan_refuses_what_the_launcher_refuses(lib, kwargs, fragment):
+    with T.options(lib, conv_rgemm=0, conv_bf3=0):
+        rc = plan(lib, **kwargs)[0]
+    assert rc != 0 and fragment in _lib.last_error()
 
 
 def parse(expect):
