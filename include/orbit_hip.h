@@ -359,8 +359,14 @@ int orbit_op_conv2d(const float* x, int x_nchw, const float* w, float* y,
                     orbit_stream_t stream);
 /* The same with flags. ORBIT_CONV_RESIDUAL_POST_ACT: y = act( conv(x) * scale + shift ) + residual - the skip joins AFTER the
  * activation (timm ConvBnAct with a skip, efficientnet_v2_s stage 0). Compiled for plain K x K NHWC convs only: a residual is
- * required, and x_nchw, pool2, a gate or a 1x1 unpadded filter with this flag are argument errors. flags = 0: orbit_op_conv2d. */
+ * required, and x_nchw, pool2, a gate or a 1x1 unpadded filter with this flag are argument errors. flags = 0: orbit_op_conv2d.
+ * ORBIT_CONV_EPILOGUE_GENERIC: the launch keeps the generic epilogue of conv_igemm_kernel (activation, residual, dual output,
+ * statistics and split-K decided at run time) where conv_plan would choose one of the compile-time epilogue forms
+ * (csrc/common.h ConvEpi: stride-1 pointwise launches that store one activated output). The two are bit-identical; the flag
+ * is a property of this launch, for A/B runs (tools/conv_bench.py ab conv_epilogue) and the bitwise test - there is no
+ * runtime option for it, and the network plans always take the compile-time form where one exists. */
 #define ORBIT_CONV_RESIDUAL_POST_ACT 1
+#define ORBIT_CONV_EPILOGUE_GENERIC 4  /* (2 is not assigned: refused as an unknown flag) */
 int orbit_op_conv2d_ex(const float* x, int x_nchw, const float* w, float* y,
                        const float* scale, const float* shift, const float* residual, const float* gate,
                        int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
@@ -401,6 +407,14 @@ int orbit_op_conv2d_train(const float* x, int x_nchw, const float* w, float* y, 
 int orbit_op_conv2d_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho, int Wo,
                          int x_nchw, int pool2, int gated, int residual, int flags, int stats_mode, int dual_output, char* row,
                          int* ksplit, int* kt_per_split, int* m_tiles);
+/* The same with the launch's activation (ORBIT_ACT_*), and in *epilogue the epilogue form of the conv_igemm launch: 0 generic,
+ * 1 none, 2 ReLU, 3 SiLU, 4 none with a residual (the compile-time forms; ConvEpi of csrc/common.h). A compile-time form is
+ * planned exactly for an inference launch (stats_mode = 0, no dual output, flags without ORBIT_CONV_EPILOGUE_GENERIC) of a
+ * stride-1 pointwise conv with Cin % 16 == 0 on a whole 64x64 / 128x32 tile, not split over K, with one of those four
+ * (activation, residual) pairs. The profiler row does not depend on the epilogue form. */
+int orbit_op_conv2d_plan_ex(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho,
+                            int Wo, int x_nchw, int pool2, int gated, int residual, int flags, int stats_mode, int dual_output, int act,
+                            char* row, int* ksplit, int* kt_per_split, int* m_tiles, int* epilogue);
 int orbit_op_dwconv2d_train(const float* x, const float* w, float* y, const float* in_scale, const float* in_shift,
                             int in_act, int B, int H, int W, int C, int K, int stride, int pad_top, int pad_left, int Ho,
                             int Wo, float* stats, orbit_stream_t stream);

@@ -85,6 +85,7 @@ _SIGNATURES = {
     "orbit_pw_stream_supported": (c_int, [c_int] * 4),
     "orbit_op_conv2d_train": (c_int, [P, c_int, P, P, P] + [c_int] * 12 + [P, POINTER(c_int), P]),
     "orbit_op_conv2d_plan": (c_int, [c_int] * 19 + [c_char_p] + [POINTER(c_int)] * 3),
+    "orbit_op_conv2d_plan_ex": (c_int, [c_int] * 20 + [c_char_p] + [POINTER(c_int)] * 4),
     "orbit_op_dwconv2d_train": (c_int, [P, P, P, P, P] + [c_int] * 11 + [P, P]),
     "orbit_op_dwconv2d_se": (c_int, [P, P, P, P] + [c_int] * 11 + [P, P, P]),
     "orbit_op_dwconv2d_plan": (c_int, [c_int] * 7 + [POINTER(c_int)] * 3),

@@ -100,7 +100,20 @@ struct ConvDesc : LayerGeom {
     // the raw conv output goes to y_raw and y receives act(raw * scale + shift + residual) - the activation pass over the
     // tensor (read y, write a) disappears. Not with fused pooling, split-K or the narrow-pointwise kernel.
     float* y_raw = nullptr;
+    // inference launches (the network plans, orbit_op_conv2d_ex): conv_plan may serve this launch with a compile-time epilogue
+    // form (ConvEpi below). It cannot be read off the launch's form: the training forward under running-statistics BatchNorm
+    // (extractor_train.hip, ops that are not CONV_DUAL), launch_conv_dgrad (whose accumulate input is a residual without a gate)
+    // and the Mahalanobis head's products also store one output without statistics. Those were not measured with the
+    // compile-time forms and keep the generic one: they leave this off.
+    bool lean_epilogue = false;
 };
+// Epilogue forms of conv_igemm_kernel. GENERIC decides activation, residual, dual output, statistics and split-K partials at run
+// time; the lean forms fix the activation and the presence of a residual at compile time and do nothing else (bit-identical
+// outputs). The listed (activation, residual) pairs are the ones instantiated: SiLU for EfficientNet's expansions and conv_head,
+// none with / without the skip for its projections, ReLU for plain pointwise layers.
+enum ConvEpi { CONV_EPI_GENERIC = 0, CONV_EPI_NONE = 1, CONV_EPI_RELU = 2, CONV_EPI_SILU = 3, CONV_EPI_NONE_RES = 4 };
+constexpr int conv_epi_act(int epi) { return epi == CONV_EPI_RELU ? ORBIT_ACT_RELU : epi == CONV_EPI_SILU ? ORBIT_ACT_SILU : ORBIT_ACT_NONE; }
+constexpr bool conv_epi_res(int epi) { return epi == CONV_EPI_NONE_RES; }
 inline size_t conv_stats_floats(size_t M, int Cout) { return ((M + 31) / 32) * 2 * (size_t)Cout; }  // smallest tile: 32 rows
 // What launch_conv runs for a conv: the one value the launcher dispatches from, the profiler row is named from and
 // orbit_op_conv2d_plan reports. conv_plan (csrc/conv_igemm.hip) is a pure host function and the only place that decides it.
@@ -111,6 +124,7 @@ struct ConvPlan {
     int BM = 64, BN = 64, BK = 32;  // igemm and bf3: the tile (igemm's 32x32 is the form with four K-waves) and the K-tile
     bool pool2 = false, gate = false, pw = false, ul = false, res_post = false, nchw = false;  // igemm instantiation flags (bf3: gate, pw)
     bool stats = false, stats_only = false;  // igemm: the launch emits BatchNorm statistics; ... and stores nothing else
+    int epi = CONV_EPI_GENERIC;              // igemm: the epilogue form (ConvEpi); not part of the profiler row
     int ksplit = 1, kt_per_split = 0;        // igemm: split-K ranges (1 = whole-tile launch) and K-tiles of BK per range
     int m_tiles = 0, n_tiles = 0;            // igemm and bf3
     int kt = 0, cin_pad = 0;                 // igemm: the packed filter's K and per-tap channels (conv_pack_geom)

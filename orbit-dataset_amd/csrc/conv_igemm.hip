@@ -60,6 +60,7 @@ struct ConvParams {
     int m_tiles, n_tiles;
     FastDiv fd_per, fd_wo;   // / (Ho*Wo), / Wo  (pool2: / (HoP*WoP), / WoP)
     FastDiv fd_cin, fd_kw;   // stem mode: / Cin, / KW
+    FastDiv fd_nt;           // lean epilogue forms: / n_tiles
     float prof_flop_scale;
     int ksplit, kt_per_split;  // split-K: blockIdx = split * tiles + tile; raw partial tiles go to part[split][M][Cout]
     float* part;
@@ -96,8 +97,23 @@ __device__ __forceinline__ void decode_row(const ConvParams& p, int m, int& b, i
 // the epilogue. That buys 2-4x more (smaller) output tiles for layers whose 64x64 tiling leaves the chip short of blocks
 // (M = 9 800 rows in EfficientNet's 7x7 stages, 1 800-7 200 in resnet18 @84's layer3/4).
 // RPOST: the residual is added AFTER the activation (see the epilogue forms above).
-template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL, bool RPOST = false>
+// EPI: the epilogue form (ConvEpi, csrc/common.h). CONV_EPI_GENERIC decides everything about the epilogue at run time: the
+// activation, residual, dual output, statistics, split-K partials. On the one-to-five K-tile pointwise layers of EfficientNet
+// that run-time generality is most of the kernel's code (profiles/r08_conv_epilogue_static.txt: 499 VALU / 317 SALU /
+// 159 branches for <64,64,16,pw>, static counts, against 40 MFMAs per wave at K = 80), so the stride-1 clamped pointwise launches (PW && UL) that
+// store one activated output - no statistics, dual output, split-K - have LEAN forms with the activation and the presence
+// of a residual as compile-time values: no statistics arithmetic, one wait for all residual loads and LDS reads of a thread,
+// the activations of a thread as independent straight-line code, the block's split-K / tile bookkeeping folded away and a
+// prologue whose gather rows are x + (m0 + min(row, M - 1 - m0)) * Cin on 32-bit row offsets. Every float operation is the
+// generic form's, in its order: outputs are bit-identical (tests/test_gpu_conv_epilogue_forms.py).
+template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL, bool RPOST = false,
+          int EPI = CONV_EPI_GENERIC>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
+    constexpr bool LEAN = EPI != CONV_EPI_GENERIC;
+    constexpr int LEAN_ACT = conv_epi_act(EPI);
+    constexpr bool LEAN_RES = conv_epi_res(EPI);
+    static_assert(!LEAN || (PW && UL && MODE == 0 && WGK == 1 && !POOL2 && !RPOST && (BK == 16 || BK == 32)),
+                  "lean epilogue forms: the clamped pointwise launches on whole 64x64 / 128x32 tiles");
     static_assert(WGM * WGN * WGK == 4, "4 waves per block");
     static_assert(WGK == 1 || !POOL2, "the fused max-pool is not linear in the K-split partial sums");
     static_assert(BK == 8 || BK == 16 || BK == 32, "BK");
@@ -132,10 +148,11 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
     // tiles and requesting the next tile's first K-tile before its epilogue - was measured on MI355X: 0..-16 % on every
     // layer of resnet18 and efficientnet_b0; the hardware dispatcher's dynamic placement beats the static walk.)
     const int ntiles = p.m_tiles * p.n_tiles;
-    const int split = p.ksplit > 1 ? blockIdx.x / ntiles : 0;  // consecutive blocks share a K range (and its filter rows)
-    const int tile = xcd_remap(p.ksplit > 1 ? blockIdx.x - split * ntiles : blockIdx.x, ntiles);
-    const int m0 = (tile / p.n_tiles) * BM;
-    const int n0 = (tile % p.n_tiles) * BN;
+    const int split = (!LEAN && p.ksplit > 1) ? blockIdx.x / ntiles : 0;  // consecutive blocks share a K range (and its filter rows)
+    const int tile = xcd_remap((!LEAN && p.ksplit > 1) ? blockIdx.x - split * ntiles : blockIdx.x, ntiles);
+    const int mt = LEAN ? (int)fdiv((unsigned)tile, p.fd_nt) : tile / p.n_tiles;  // (lean: no scalar division sequence)
+    const int m0 = mt * BM;
+    const int n0 = (tile - mt * p.n_tiles) * BN;
     const int kt0 = split * p.kt_per_split;  // first K-tile of this block
 
     // ---- per-thread gather bookkeeping (rows are fixed for the whole K loop) ----
@@ -168,7 +185,19 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
         ld_tap = (ld_kh * p.W + ld_kw) * p.Cin;
     }
 
-    if (MODE == 0) {
+    if constexpr (LEAN) {
+        // stride-1 pointwise, rows beyond M clamped: NHWC rows ARE the GEMM rows. The tile's first row is a scalar 64-bit
+        // offset, a thread's rows are 32-bit offsets from it (conv_plan: 128 * Cin fits)
+        const float* xt = p.x + (size_t)m0 * p.Cin + c4 * 4;
+        const int mlast = p.M - 1 - m0;  // >= 0
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+            const int row = min(lrow + RPP * i, mlast);
+            a_ptr[i] = xt + row * p.Cin;
+            a_hi0[i] = 0, a_wi0[i] = 0;
+            if (GATE) g_ptr[i] = p.gate + (size_t)fdiv((unsigned)(m0 + row), p.fd_per) * p.Cin + c4 * 4;
+        }
+    } else if (MODE == 0) {
 #pragma unroll
         for (int i = 0; i < AR; ++i) {
             // pointwise + UL: rows beyond M are clamped to the last row instead of predicated - what they compute is never
@@ -227,7 +256,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
     f32x4 g_stage[GATE ? AR : 1];  // the gate is multiplied in when the tile is written to LDS: doing it at load time
                                    // would wait for the loads right there and expose their latency every K-tile
 
-    const int nk = p.ksplit > 1 ? min(p.KT / BK - kt0, p.kt_per_split) : p.KT / BK;  // K-tiles of this block
+    const int nk = (!LEAN && p.ksplit > 1) ? min(p.KT / BK - kt0, p.kt_per_split) : p.KT / BK;  // K-tiles of this block
     const int ktot = p.KH * p.KW * p.Cin;            // true K (stem mode)
     (void)ktot;
 
@@ -393,7 +422,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int n = n0 + wn + j * 32 + l31;
-        const bool use = n < p.Cout && p.ksplit <= 1 && p.y_raw == nullptr;
+        const bool use = n < p.Cout && (LEAN || (p.ksplit <= 1 && p.y_raw == nullptr));
         sc_pre[j] = (use && p.scale) ? p.scale[n] : 1.0f;
         sh_pre[j] = (use && p.shift && wk == 0) ? p.shift[n] : 0.0f;
     }
@@ -419,6 +448,49 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
     // linear tile for BN = 32 / 64 / 96 / 128; the BN + 4 padding of rounds 1-2 put rows 0 / 1 and 2 / 3 of a group on
     // shared slots (most of the 0.1-0.16 conflicts per LDS cycle that were left on the one-K-tile layers)
     constexpr int CS = BN;
+    if constexpr (LEAN) {
+        // The lean forms: the same staging of acc * scale + shift through LDS and the same float4 row stores as below, with
+        // ACT and RES known to the compiler. TPO * RPO == 256 and ITER * RPO == BM on both tiles: every thread moves exactly
+        // ITER float4s, whose LDS reads and residual loads (rows beyond M clamped to the last row, never stored) are all
+        // issued before the first use.
+        constexpr int TPO = BN / 4, RPO = 256 / TPO, ITER = BM / RPO;
+        static_assert(TPO * RPO == 256 && ITER * RPO == BM, "lean epilogue: whole passes of the 256 threads");
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const float sc = sc_pre[j], sh = sh_pre[j];
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int rq = 0; rq < 4; ++rq) {
+                    const int rowl = wm + i * 32 + 8 * rq + 4 * lh;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) smem[(rowl + r) * CS + wn + j * 32 + l31] = acc[i][j][rq * 4 + r] * sc + sh;
+                }
+        }
+        __syncthreads();
+        const int oc = (tid % TPO) * 4, r0 = tid / TPO;
+        if (n0 + oc >= p.Cout) return;
+        const int mlast = p.M - 1 - m0;
+        const size_t tile_off = (size_t)m0 * p.Cout + n0 + oc;  // 32-bit row offsets from here (conv_plan: 128 * Cout fits)
+        f32x4 v[ITER], res[ITER];
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) {
+            v[it] = *reinterpret_cast<const f32x4*>(smem + (r0 + it * RPO) * CS + oc);
+            if (LEAN_RES) res[it] = *reinterpret_cast<const f32x4*>(p.residual + tile_off + min(r0 + it * RPO, mlast) * p.Cout);
+        }
+#pragma unroll
+        for (int it = 0; it < ITER; ++it) {
+            f32x4 o = v[it];
+            if (LEAN_RES) o += res[it];
+            o[0] = apply_act(o[0], LEAN_ACT), o[1] = apply_act(o[1], LEAN_ACT);
+            o[2] = apply_act(o[2], LEAN_ACT), o[3] = apply_act(o[3], LEAN_ACT);
+            v[it] = o;
+        }
+#pragma unroll
+        for (int it = 0; it < ITER; ++it)
+            if (r0 + it * RPO <= mlast) *reinterpret_cast<f32x4*>(p.y + tile_off + (r0 + it * RPO) * p.Cout) = v[it];
+        return;
+    }
     constexpr int OROWS = POOL2 ? BM / 4 : BM;    // output rows of this tile
     float* Cs = smem + wk * (OROWS * CS);        // [WGK][OROWS][CS]: one partial tile per K-wave group
 #pragma unroll
@@ -617,12 +689,12 @@ int conv_pack_weights(const float* w_oihw, float* w_packed, int Cin, int Cout, i
 }
 
 // One instantiation: its LDS size, the opt-in above 64 KiB, the profiler record and the launch
-template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL, bool RPOST>
+template <int BM, int BN, int WGM, int WGN, int WGK, int BK, int MODE, bool POOL2, bool GATE, bool PW, bool UL, bool RPOST, int EPI>
 static int launch_cfg2(const ConvPlan& pl, const ConvParams& p, hipStream_t s) {
     const size_t lds_pipe = (size_t)2 * (BM + BN) * (BK + 4) * sizeof(float) + (MODE == 1 ? 1024 : 0);  // + stem k table
     const size_t lds_epi = (size_t)WGK * (POOL2 ? BM / 4 : BM) * BN * sizeof(float);
     const size_t lds = lds_pipe > lds_epi ? lds_pipe : lds_epi;
-    auto kern = conv_igemm_kernel<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, UL, RPOST>;
+    auto kern = conv_igemm_kernel<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, UL, RPOST, EPI>;
     static bool attr_set = false;  // >64 KiB dynamic LDS needs the opt-in once per kernel
     if (!attr_set && lds > 64 * 1024) {
         ORBIT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -759,6 +831,29 @@ static int conv_plan_fill(const ConvDesc& d, ConvPlan& pl) {
         tile = conv_tile_narrow(d.Cout) ? 4 : (k4_exists && cdiv(M, 64) * cdiv(d.Cout, 64) < 256) ? 6 : 3;
     pl.BM = tile == 4 ? 128 : tile == 6 ? 32 : 64, pl.BN = tile == 3 ? 64 : 32;
     pl.m_tiles = cdiv(M, pl.BM), pl.n_tiles = cdiv(d.Cout, pl.BN);
+    // The epilogue form: a function of the launch's form only. A lean form serves a launch that stores one activated output
+    // (no statistics, statistics sweep, dual output or split-K partials; pointwise excludes fused pooling and the
+    // post-activation skip) on a whole 64x64 / 128x32 tile (no K-waves), where one is instantiated: the stride-1 clamped
+    // pointwise kernels at BK 16 / 32, for the (activation, residual) pairs of ConvEpi; their 32-bit row offsets want
+    // 128 * Cin and 128 * Cout below 2^31. Everything else - and every launch that does not ask (ConvDesc::lean_epilogue:
+    // training, ORBIT_CONV_EPILOGUE_GENERIC) - runs the generic form, and so does the one class measured slower (below;
+    // profiles/r08_conv_epilogue_ab.txt).
+    pl.epi = CONV_EPI_GENERIC;
+    if (d.lean_epilogue && pl.pw && pl.ul && d.stride == 1 && (pl.BK == 16 || pl.BK == 32) && pl.BM != 32 && pl.ksplit <= 1 &&
+        !pl.stats && !pl.stats_only && !d.y_raw && d.y && d.Cin <= (1 << 20) && d.Cout <= (1 << 20)) {
+        if (!d.residual)
+            pl.epi = d.act == ORBIT_ACT_NONE ? CONV_EPI_NONE : d.act == ORBIT_ACT_RELU ? CONV_EPI_RELU : d.act == ORBIT_ACT_SILU ? CONV_EPI_SILU : CONV_EPI_GENERIC;
+        // The skip WITHOUT a gate on the 64x64 tile with a single column tile stays generic: 240 -> 40 @28x28, 200 frames
+        // (2 450 tiles, HBM-bound), tools/conv_bench.py effnet_224 ab conv_epilogue on two MI355X: lean 56.9 us against
+        // generic 54.7 us (+3.9 %, spreads of the arms' repeats 0.7 / 0.4 us) and 57.2 against 54.7 us (+4.7 %, spreads
+        // 1.2 / 1.0 us); 8 instead of 5 waves per SIMD do not pay on that launch. The same instantiation on more than one
+        // column tile is faster lean (672 -> 112 @14: 66.8 vs 68.7 us; 1152 -> 192 @7: 46.5 vs 48.3 us), and so are the
+        // 128x32 launches of the form (144 -> 24 @56: 104.6 vs 108.9 us; 480 -> 80 @14: 44.6 vs 46.1 us) and the gated
+        // 240 -> 40 (57.5 vs 58.2 us). Only BK 16 of the class was measured (efficientnet_b0 has no such layer at BK 32;
+        // efficientnet_v2_s's 256 -> 64 @28 is one): both stay on the form that was measured there, the generic one.
+        else if (d.act == ORBIT_ACT_NONE && !(!d.gate && pl.BM == 64 && pl.n_tiles == 1))
+            pl.epi = CONV_EPI_NONE_RES;
+    }
     return ORBIT_OK;
 }
 
@@ -781,28 +876,31 @@ void conv_plan_name(const ConvPlan& pl, char name[48]) {
 
 // The instantiations of conv_igemm_kernel, keyed by the plan's fields. What is listed below is what exists: the NCHW stems at
 // BK 32 without a gate, four K-waves (32x32) only for NHWC without fused pooling at BK 32, UL only with PW, RPOST only for the
-// plain K x K form.
-static constexpr int conv_inst(int BM, int BK, bool nchw, bool pool2, bool gate, bool pw, bool ul, bool rpost) {
-    return BM | BK << 8 | nchw << 14 | pool2 << 15 | gate << 16 | pw << 17 | ul << 18 | rpost << 19;
+// plain K x K form, the lean epilogue forms only for the clamped pointwise kernels on whole tiles at BK 32 / 16.
+static constexpr int conv_inst(int BM, int BK, bool nchw, bool pool2, bool gate, bool pw, bool ul, bool rpost, int epi) {
+    return BM | BK << 8 | nchw << 14 | pool2 << 15 | gate << 16 | pw << 17 | ul << 18 | rpost << 19 | epi << 20;
 }
-#define ORBIT_CONV_INST(BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, UL, RPOST) \
-    case conv_inst(BM, BK, MODE, POOL2, GATE, PW, UL, RPOST):                        \
-        return launch_cfg2<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, UL, RPOST>(pl, p, s);
-#define ORBIT_CONV_TILES(BK, MODE, POOL2, GATE, PW, UL, RPOST)                \
-    ORBIT_CONV_INST(64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW, UL, RPOST)    \
-    ORBIT_CONV_INST(128, 32, 4, 1, 1, BK, MODE, POOL2, GATE, PW, UL, RPOST)
+#define ORBIT_CONV_INST(BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, UL, RPOST, EPI) \
+    case conv_inst(BM, BK, MODE, POOL2, GATE, PW, UL, RPOST, EPI):                        \
+        return launch_cfg2<BM, BN, WGM, WGN, WGK, BK, MODE, POOL2, GATE, PW, UL, RPOST, EPI>(pl, p, s);
+#define ORBIT_CONV_TILES(BK, MODE, POOL2, GATE, PW, UL, RPOST, EPI)                \
+    ORBIT_CONV_INST(64, 64, 2, 2, 1, BK, MODE, POOL2, GATE, PW, UL, RPOST, EPI)    \
+    ORBIT_CONV_INST(128, 32, 4, 1, 1, BK, MODE, POOL2, GATE, PW, UL, RPOST, EPI)
 #define ORBIT_CONV_NHWC(GATE, PW, UL, RPOST) /* no fused pooling: every BK, and the four K-waves at BK 32 */ \
-    ORBIT_CONV_TILES(32, 0, false, GATE, PW, UL, RPOST)                                                      \
-    ORBIT_CONV_TILES(16, 0, false, GATE, PW, UL, RPOST)                                                      \
-    ORBIT_CONV_TILES(8, 0, false, GATE, PW, UL, RPOST)                                                       \
-    ORBIT_CONV_INST(32, 32, 1, 1, 4, 32, 0, false, GATE, PW, UL, RPOST)
+    ORBIT_CONV_TILES(32, 0, false, GATE, PW, UL, RPOST, CONV_EPI_GENERIC)                                    \
+    ORBIT_CONV_TILES(16, 0, false, GATE, PW, UL, RPOST, CONV_EPI_GENERIC)                                    \
+    ORBIT_CONV_TILES(8, 0, false, GATE, PW, UL, RPOST, CONV_EPI_GENERIC)                                     \
+    ORBIT_CONV_INST(32, 32, 1, 1, 4, 32, 0, false, GATE, PW, UL, RPOST, CONV_EPI_GENERIC)
+#define ORBIT_CONV_LEAN(GATE, EPI) /* clamped pointwise, one activated output */ \
+    ORBIT_CONV_TILES(32, 0, false, GATE, true, true, false, EPI)                 \
+    ORBIT_CONV_TILES(16, 0, false, GATE, true, true, false, EPI)
 static int launch_planned(const ConvPlan& pl, const ConvParams& p, hipStream_t s) {
-    switch (conv_inst(pl.BM, pl.BK, pl.nchw, pl.pool2, pl.gate, pl.pw, pl.ul, pl.res_post)) {
-        ORBIT_CONV_TILES(32, 1, false, false, false, false, false)  // NCHW stems
-        ORBIT_CONV_TILES(32, 1, true, false, false, false, false)
-        ORBIT_CONV_TILES(32, 0, true, false, false, false, false)  // NHWC with the fused 2x2 max-pool
-        ORBIT_CONV_TILES(16, 0, true, false, false, false, false)
-        ORBIT_CONV_TILES(8, 0, true, false, false, false, false)
+    switch (conv_inst(pl.BM, pl.BK, pl.nchw, pl.pool2, pl.gate, pl.pw, pl.ul, pl.res_post, pl.epi)) {
+        ORBIT_CONV_TILES(32, 1, false, false, false, false, false, CONV_EPI_GENERIC)  // NCHW stems
+        ORBIT_CONV_TILES(32, 1, true, false, false, false, false, CONV_EPI_GENERIC)
+        ORBIT_CONV_TILES(32, 0, true, false, false, false, false, CONV_EPI_GENERIC)  // NHWC with the fused 2x2 max-pool
+        ORBIT_CONV_TILES(16, 0, true, false, false, false, false, CONV_EPI_GENERIC)
+        ORBIT_CONV_TILES(8, 0, true, false, false, false, false, CONV_EPI_GENERIC)
         ORBIT_CONV_NHWC(false, false, false, false)  // K x K
         ORBIT_CONV_NHWC(true, false, false, false)   // gated K x K
         ORBIT_CONV_NHWC(false, false, false, true)   // K x K with the skip after the activation
@@ -810,9 +908,18 @@ static int launch_planned(const ConvPlan& pl, const ConvParams& p, hipStream_t s
         ORBIT_CONV_NHWC(false, true, true, false)    // pointwise
         ORBIT_CONV_NHWC(true, true, false, false)    // gated pointwise, both
         ORBIT_CONV_NHWC(true, true, true, false)
+        ORBIT_CONV_LEAN(false, CONV_EPI_NONE)        // pointwise, lean epilogue forms
+        ORBIT_CONV_LEAN(false, CONV_EPI_RELU)
+        ORBIT_CONV_LEAN(false, CONV_EPI_SILU)
+        ORBIT_CONV_LEAN(false, CONV_EPI_NONE_RES)
+        ORBIT_CONV_LEAN(true, CONV_EPI_NONE)         // gated pointwise, lean epilogue forms
+        ORBIT_CONV_LEAN(true, CONV_EPI_RELU)
+        ORBIT_CONV_LEAN(true, CONV_EPI_SILU)
+        ORBIT_CONV_LEAN(true, CONV_EPI_NONE_RES)
     }
     return set_err(ORBIT_ERR_ARG, "conv: no kernel for this plan");
 }
+#undef ORBIT_CONV_LEAN
 #undef ORBIT_CONV_NHWC
 #undef ORBIT_CONV_TILES
 #undef ORBIT_CONV_INST
@@ -841,6 +948,7 @@ int launch_conv(const ConvDesc& d, hipStream_t s) {
         p.fd_per = make_fastdiv((unsigned)(d.Ho * d.Wo)), p.fd_wo = make_fastdiv((unsigned)d.Wo);
     }
     p.fd_cin = make_fastdiv((unsigned)d.Cin), p.fd_kw = make_fastdiv((unsigned)d.KW);
+    p.fd_nt = make_fastdiv((unsigned)pl.n_tiles);
     ORBIT_REQUIRE((long long)d.B * d.H * d.W * d.Cin < (1ll << 40) && p.M > 0, "conv: tensor too large");
     p.ksplit = pl.ksplit, p.kt_per_split = pl.kt_per_split, p.m_tiles = pl.m_tiles, p.n_tiles = pl.n_tiles;
     p.part = d.splitk_ws;
@@ -902,7 +1010,7 @@ int orbit_op_conv2d_ex(const float* x, int x_nchw, const float* w, float* y, con
                        int stride, int pad_top, int pad_left, int Ho, int Wo, int act, int pool2, int flags,
                        orbit_stream_t stream) {
     ORBIT_REQUIRE(x && w && y, "op_conv2d: null pointer");
-    ORBIT_REQUIRE((flags & ~ORBIT_CONV_RESIDUAL_POST_ACT) == 0, "op_conv2d_ex: unknown flags 0x%x", flags);
+    ORBIT_REQUIRE((flags & ~(ORBIT_CONV_RESIDUAL_POST_ACT | ORBIT_CONV_EPILOGUE_GENERIC)) == 0, "op_conv2d_ex: unknown flags 0x%x", flags);
     ORBIT_REQUIRE(KH > 0 && KW > 0 && stride > 0, "op_conv2d: bad kernel geometry");
     hipStream_t s = (hipStream_t)stream;
     TempPackedFilter f;
@@ -911,6 +1019,7 @@ int orbit_op_conv2d_ex(const float* x, int x_nchw, const float* w, float* y, con
     d.x = x, d.w_packed = f.packed, d.w_frag = f.frag, d.y = y, d.scale = scale, d.shift = shift, d.residual = residual;
     d.geom() = LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
     d.gate = gate, d.act = act, d.pool2 = pool2, d.x_nchw = x_nchw, d.res_post = (flags & ORBIT_CONV_RESIDUAL_POST_ACT) ? 1 : 0;
+    d.lean_epilogue = !(flags & ORBIT_CONV_EPILOGUE_GENERIC);
     float* sk = nullptr;
     const size_t skf = conv_splitk_floats(d);
     if (skf) ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&sk), skf * sizeof(float), s));
@@ -929,27 +1038,39 @@ int orbit_op_conv2d_ex(const float* x, int x_nchw, const float* w, float* y, con
 int orbit_op_conv2d_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho, int Wo,
                          int x_nchw, int pool2, int gated, int residual, int flags, int stats_mode, int dual_output, char* row,
                          int* ksplit, int* kt_per_split, int* m_tiles) {
-    ORBIT_REQUIRE(row && ksplit && kt_per_split && m_tiles, "op_conv2d_plan: null pointer");
-    ORBIT_REQUIRE((flags & ~ORBIT_CONV_RESIDUAL_POST_ACT) == 0, "op_conv2d_plan: unknown flags 0x%x", flags);
+    int epi;
+    return orbit_op_conv2d_plan_ex(B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo, x_nchw, pool2, gated, residual,
+                                   flags, stats_mode, dual_output, ORBIT_ACT_NONE, row, ksplit, kt_per_split, m_tiles, &epi);
+}
+
+/* The same with the launch's activation, and the epilogue form (ConvEpi) the plan chose in *epilogue. */
+int orbit_op_conv2d_plan_ex(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho,
+                            int Wo, int x_nchw, int pool2, int gated, int residual, int flags, int stats_mode, int dual_output, int act,
+                            char* row, int* ksplit, int* kt_per_split, int* m_tiles, int* epilogue) {
+    ORBIT_REQUIRE(row && ksplit && kt_per_split && m_tiles && epilogue, "op_conv2d_plan: null pointer");
+    ORBIT_REQUIRE((flags & ~(ORBIT_CONV_RESIDUAL_POST_ACT | ORBIT_CONV_EPILOGUE_GENERIC)) == 0, "op_conv2d_plan: unknown flags 0x%x", flags);
     ORBIT_REQUIRE(KH > 0 && KW > 0 && stride > 0 && stats_mode >= 0 && stats_mode <= 2, "op_conv2d_plan: bad kernel geometry");
     static float some[1];  // stands for every buffer the launch would be given: the plan looks at which are there, not into them
     static int blocks;
     ConvDesc d;
     d.geom() = LayerGeom{B, H, W, Cin, Cout, KH, KW, stride, pad_top, pad_left, Ho, Wo};
-    d.x_nchw = x_nchw, d.pool2 = pool2, d.res_post = (flags & ORBIT_CONV_RESIDUAL_POST_ACT) ? 1 : 0;
+    d.x_nchw = x_nchw, d.pool2 = pool2, d.res_post = (flags & ORBIT_CONV_RESIDUAL_POST_ACT) ? 1 : 0, d.act = act;
     d.gate = gated ? some : nullptr, d.residual = residual ? some : nullptr;
     if (stats_mode) d.stats = some, d.stats_blocks = &blocks;
     d.stats_only = stats_mode == 2;
+    d.y = d.stats_only ? nullptr : some;
     d.y_raw = dual_output ? some : nullptr;
     if (int rc = conv_shape_check(d)) return rc;
     if (!stats_mode && !dual_output) {
         d.w_frag = conv_frag_floats(Cin, Cout, KH, KW, x_nchw) ? some : nullptr;
         d.splitk_ws = conv_splitk_floats(d) ? some : nullptr;
+        d.lean_epilogue = !(flags & ORBIT_CONV_EPILOGUE_GENERIC);  // (the training entry points never ask for a lean form)
     }
     const ConvPlan pl = conv_plan(d);
     if (pl.rc != ORBIT_OK) return pl.rc;
     conv_plan_name(pl, row);
     *ksplit = pl.ksplit, *kt_per_split = pl.kt_per_split, *m_tiles = pl.stats ? pl.m_tiles : 0;
+    *epilogue = pl.family == CONV_IGEMM ? pl.epi : CONV_EPI_GENERIC;
     return ORBIT_OK;
 }
 

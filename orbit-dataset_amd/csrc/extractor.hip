@@ -643,6 +643,7 @@ static int run_plan(orbit_extractor_t* fe, const float* frames, int B, const flo
                 d.residual = o.res >= 0 ? buf(o.res) : nullptr;
                 d.gate = o.use_gate ? buf(BUF_GATE) : nullptr;
                 d.splitk_ws = reinterpret_cast<float*>(ws + L.splitk);
+                d.lean_epilogue = true;  // inference: one activated output per launch
                 rc = launch_conv(d, s);
                 break;
             }

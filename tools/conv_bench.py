@@ -1,6 +1,14 @@
 """Micro-benchmark of the MFMA implicit-GEMM convolution on the layer shapes of the bench workloads.
 Usage (GPU box): python tools/conv_bench.py [resnet18_84|resnet18_224|effnet_224|effnetv2_224|setenc_224]   — prints TFLOP/s per layer.
-(effnetv2_224: the stem and the 3x3 convs of efficientnet_v2_s, TF-SAME geometry; `bk` shows each under the K-tile caps.)"""
+(effnetv2_224: the stem and the 3x3 convs of efficientnet_v2_s, TF-SAME geometry; `bk` shows each under the K-tile caps.)
+`ab <option>` / `abgate <option>`: in-process A/B of a runtime option, interleaved. `ab conv_epilogue` is not an option but the
+launch flag ORBIT_CONV_EPILOGUE_GENERIC (0 = the compile-time epilogue form where conv_plan has one, 1 = generic); under it the
+layers run as the network runs them: SiLU on expansions, stem and head, no activation on the projections (pwl*), and the skip
+connection on the projections that have one. `epilogue lean|generic`: one arm of that A/B alone, the same activations and
+skips, for counter runs (tools/conv_pmc.sh <outdir> <net> epilogue generic).
+Every launch goes through orbit_op_conv2d_ex with flags = 0, so all other modes (plain, bk, sweep, gate, `ab <option>`) time
+ReLU layers without a skip and the pointwise ones among them run the compile-time ReLU epilogue - a form no EfficientNet layer
+uses; the figures quoted in conv_plan's comments from before that form existed were taken on the generic epilogue."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -32,6 +40,7 @@ SHAPES = {
         ("se_l1", 200, 224, 3, 64, 3, 1, 1, 1), ("se_l2", 200, 112, 64, 64, 3, 1, 1, 0), ("se_l3", 200, 56, 64, 64, 3, 1, 1, 0),
         ("se_l4", 200, 28, 64, 64, 3, 1, 1, 0), ("se_l5", 200, 14, 64, 64, 3, 1, 1, 0)],
 }
+SKIP = {"pwl144_24", "pwl240_40", "pwl480_80", "pwl672_112", "pwl1152_192"}  # effnet_224 projections with a residual input
 TILES = {0: "auto", 1: "128x128", 2: "128x64", 3: "64x64", 4: "128x32", 5: "64x32k2", 6: "32x32k4", 7: "32x64k2",
          8: "32x96k4", 9: "64x96k2", 10: "128x96", 11: "32x128k4", 12: "64x128k2", 13: "128x128w4"}
 
@@ -50,11 +59,17 @@ def main():
         sc, sh = torch.rand(Cout, device=dev), torch.rand(Cout, device=dev)
         use_gate = len(sys.argv) > 2 and sys.argv[2] in ("gate", "abgate", "gatesweep") and not nchw and K == 1 and name.startswith("pwl")
         gate = torch.rand(B, Cin, device=dev) if use_gate else None
+        epi_ab = len(sys.argv) > 3 and sys.argv[2] in ("ab", "abgate") and sys.argv[3] == "conv_epilogue"
+        epi_arm = len(sys.argv) > 3 and sys.argv[2] == "epilogue"
+        net_form = epi_ab or epi_arm
+        act = (0 if name.startswith("pwl") else 2) if net_form else 1
+        skip = torch.randn(B, Ho, Ho, Cout, device=dev) if net_form and name in SKIP else None
+        flags = [4 if epi_arm and sys.argv[3] == "generic" else 0]  # ORBIT_CONV_EPILOGUE_GENERIC
 
         def run():
-            _lib.check(lib.orbit_op_conv2d(_lib.dptr(x), nchw, _lib.dptr(w), _lib.dptr(y), _lib.dptr(sc), _lib.dptr(sh), None,
-                                           _lib.dptr(gate) if use_gate else None,
-                                           B, H, H, Cin, Cout, K, K, stride, pad, pad, Ho, Ho, 1, 0, _lib.stream_handle()))
+            _lib.check(lib.orbit_op_conv2d_ex(_lib.dptr(x), nchw, _lib.dptr(w), _lib.dptr(y), _lib.dptr(sc), _lib.dptr(sh), _lib.dptr(skip),
+                                              _lib.dptr(gate) if use_gate else None,
+                                              B, H, H, Cin, Cout, K, K, stride, pad, pad, Ho, Ho, act, 0, flags[0], _lib.stream_handle()))
 
         def measure(tile):
             lib.orbit_set_option(b"conv_tile", tile)
@@ -88,11 +103,18 @@ def main():
             res = {0: [], 1: []}
             for rep_ in range(3):
                 for v in (0, 1):
-                    lib.orbit_set_option(opt, v)
+                    if epi_ab:
+                        flags[0] = 4 * v  # ORBIT_CONV_EPILOGUE_GENERIC
+                    else:
+                        lib.orbit_set_option(opt, v)
                     res[v].append(measure(0)[0])
             a0, a1 = min(res[0]), min(res[1])
             line += "  | %s=0 %.1f us  =1 %.1f us  (%+.1f%%)" % (sys.argv[3], a0, a1, 100 * (a0 / a1 - 1))
-            lib.orbit_set_option(opt, 1)
+            if epi_ab:  # the spread of each arm's own repeats beside its minimum
+                line += "  spread %.1f / %.1f us" % (max(res[0]) - a0, max(res[1]) - a1)
+                flags[0] = 0
+            else:
+                lib.orbit_set_option(opt, 1)
         if sweep:
             cand = (3, 4, 6)
             res = {t: measure(t)[0] for t in cand}

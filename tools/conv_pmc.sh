@@ -1,9 +1,10 @@
 #!/bin/bash
 # Run on the GPU box: SQ counters of the conv kernel per layer shape (tools/conv_bench.py <net>), one rocprofv3 --pmc pass
 # per counter group (PMC passes are never combined with other trace domains).
-#   tools/conv_pmc.sh <outdir> <net>
+#   tools/conv_pmc.sh <outdir> <net> [further arguments of tools/conv_bench.py, e.g. epilogue generic]
 set -u
 OUT=${1:-gpurun_out/convpmc}; NET=${2:-effnet_224}
+shift $(($# < 2 ? $# : 2))
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p "$R/$OUT"; O="$R/$OUT"
 cd /tmp && export TMPDIR=/tmp
@@ -14,7 +15,8 @@ G3="GRBM_GUI_ACTIVE SQ_INSTS_SALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VALU SQ_INST
 i=0
 for G in "$G1" "$G2" "$G3"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $G --output-format csv -d $O/pass$i -- python $R/tools/conv_bench.py $NET > $O/pass$i.log 2> $O/pass$i.err
+  timeout -k 10 600 rocprofv3 --pmc $G --output-format csv -d $O/pass$i -- python $R/tools/conv_bench.py $NET "$@" > $O/pass$i.log 2> $O/pass$i.err ||
+    { echo "conv_pmc: pass $i failed (status $?), nothing more is started; see $O/pass$i.err"; exit 1; }
 done
 python - "$O" <<'PY' > $O/summary.txt
 import csv, glob, sys, collections
