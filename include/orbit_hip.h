@@ -263,7 +263,8 @@ int orbit_extractor_forward(orbit_extractor_t* fe, const float* frames, int B,
  * same module tree, state_dict keys and FiLM slots; patch_embed.proj.weight is [D][3][16][16], pos_embed [1][197][D], and a
  * frame is 196 patches + the class token. They are inference + FiLM only: orbit_vit_tape_bytes,
  * orbit_vit_backward_workspace_bytes and orbit_vit_backward_params_workspace_bytes return 0 and the three training entry points
- * return ORBIT_ERR_ARG naming the model, before any launch or allocation. Batch cap: 1..8192 frames for the patch-32 plans,
+ * return ORBIT_ERR_ARG naming the model, before any launch or allocation - until orbit_vit_enable_backward (below) opts a plan
+ * into the taped forward and the FiLM gradients of the frozen network; weight gradients stay refused. Batch cap: 1..8192 frames for the patch-32 plans,
  * 1..2048 for the patch-16 plans (B * 197 * 4 D stays below 2^31); beyond it orbit_vit_workspace_bytes returns 0 and
  * orbit_vit_forward ORBIT_ERR_ARG. */
 int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out);
@@ -304,6 +305,12 @@ int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* f
  * allocates it. One stream per plan: a backward issued on another stream is not ordered behind those transposes (nor behind
  * the parameter upload), so the caller orders the streams itself. Tape and workspaces 256-byte aligned; byte counts are 0 for B outside 1..8192. */
 size_t orbit_vit_tape_bytes(const orbit_vit_t* v, int B);
+/* Opt a patch-16 plan into orbit_vit_train_forward / orbit_vit_backward: the same tape and workspace layouts at 197 tokens per
+ * frame ((12 * 9 + 1) * align_up(197 B * D * 4, 256) tape bytes), for 1..2048 frames, 0 outside. orbit_vit_backward_params
+ * still returns ORBIT_ERR_ARG before any launch (weight gradients are not built for the patch-16 models) and its workspace
+ * size stays 0. A flag on this plan only: idempotent, allocates nothing, legal before or after orbit_vit_finalize and after
+ * inference forwards. A no-op returning ORBIT_OK on a patch-32 plan; ORBIT_ERR_ARG for NULL. */
+int orbit_vit_enable_backward(orbit_vit_t* v);
 size_t orbit_vit_backward_workspace_bytes(const orbit_vit_t* v, int B);
 int orbit_vit_train_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
                             float* feats, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
@@ -484,6 +491,12 @@ int orbit_op_vit_layernorm_bwd(const float* x, size_t x_stride, const float* dy,
 /* qkv [B][50][3][heads][64], dout [B][50][heads][64] -> dqkv in qkv's layout (gradients of q, k and v). */
 int orbit_op_vit_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int D, int heads,
                                orbit_stream_t stream);
+/* The same with the token count: tokens = 50 is the call above; tokens = 197 (the patch-16 models) recomputes S and P and runs
+ * every product on the fp32 matrix cores, one workgroup per (frame, head), no atomics: a frame's dqkv does not depend on B and
+ * two runs are bitwise equal. qkv, dout and dqkv then 16-byte aligned and B at most 2048. Any other token count is an
+ * argument error; every refusal comes before any launch. */
+int orbit_op_vit_attention_bwd_tokens(const float* qkv, const float* dout, float* dqkv, int B, int tokens, int D, int heads,
+                                      orbit_stream_t stream);
 /* The weight-gradient kernels of orbit_vit_backward_params one by one.
  * dw [N][K] = dy [M][N]^T . x [M][K] (gelu_on_x = 1: . GELU_erf(x), the fc2 layer, whose tape holds the pre-activation) and,
  * unless dbias is NULL, dbias [N] = the column sums of dy; both overwritten. N % 128 == 0, K % 32 == 0; every pointer 16-byte

@@ -65,6 +65,7 @@ _SIGNATURES = {
     "orbit_vit_macs_per_frame": (c_double, [P]),
     "orbit_vit_forward": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P]),
     "orbit_vit_tape_bytes": (c_size_t, [P, c_int]),
+    "orbit_vit_enable_backward": (c_int, [P]),
     "orbit_vit_backward_workspace_bytes": (c_size_t, [P, c_int]),
     "orbit_vit_train_forward": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P, c_size_t, P]),
     "orbit_vit_backward": (c_int, [P, c_int, P, P, P, P, c_size_t, P, P, P, c_size_t, P]),
@@ -103,6 +104,7 @@ _SIGNATURES = {
     "orbit_op_vit_layernorm_bwd": (c_int, [P, c_size_t, P, c_size_t, P, c_float, P, P, c_size_t, c_int, c_int, P, P, P,
                                            c_size_t, P]),
     "orbit_op_vit_attention_bwd": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "orbit_op_vit_attention_bwd_tokens": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     "orbit_op_vit_linear_wgrad_workspace_floats": (c_size_t, [c_int, c_int, c_int]),
     "orbit_op_vit_linear_wgrad": (c_int, [P] * 4 + [c_int] * 4 + [P, c_size_t, P]),
     "orbit_op_vit_patch_embed_bwd": (c_int, [P] * 6 + [c_int] * 2 + [P, c_size_t, P]),

@@ -20,8 +20,10 @@
 //                        parameter pool or from the per-task FiLM vectors (reference model/film.py:57-66).
 //   vit_attention_kernel one workgroup per (frame, head): Q, K, V (50 x 64) in LDS, S = QK^T / 8, row softmax, O = PV.
 // The patch-16 models of the same families (vit_s_16, vit_b_16, vit_b_16_clip: 14 x 14 patches, 197 tokens, six names in all)
-// run the same forward, inference and FiLM only, with the geometry read from the plan: the patch GEMM's EPI_PATCH16 form
-// (k = c*256 + kh*16 + kw, token rows 1..196) and vit_attention197_kernel (fp32 MFMA, K and V resident in LDS).
+// run the same forward with the geometry read from the plan: the patch GEMM's EPI_PATCH16 form (k = c*256 + kh*16 + kw, token
+// rows 1..196) and vit_attention197_kernel (fp32 MFMA, K and V resident in LDS). Their plans are inference + FiLM only until
+// orbit_vit_enable_backward switches on the taped forward and the FiLM gradients of the frozen network (the same reverse pass
+// at 197 tokens, with vit_attention197_bwd_kernel); weight gradients are not built for them.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -571,9 +573,274 @@ __global__ __launch_bounds__(256) void vit_attention_bwd_kernel(const float* __r
     }
 }
 
-int launch_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int D, int heads, hipStream_t s) {
-    const int pi = prof_start("vit_attention_bwd", 10.0 * B * heads * VIT_N * VIT_N * VIT_HD, 4.0 * 7 * (double)B * VIT_N * D, s);
-    vit_attention_bwd_kernel<<<B * heads, 256, 0, s>>>(qkv, dout, dqkv, D, heads);
+// The same for the 197 tokens of the patch-16 models, on v_mfma_f32_32x32x2_f32 as vit_attention197_kernel, whose tile layout
+// (A16_NPAD = 224 padded tokens, 7 waves, lane = (column, k half)) it shares. Q, K, V and dO of a head are 4 x 197 x 64 floats and
+// do not fit LDS together, so one workgroup per (frame, head) runs two phases over two [224][65] LDS matrices (rows 197..223
+// zero; the odd stride serves both the row-major A fragments - 32 rows, 32 banks - and the transposed ones):
+//   A  LDS = K, V. A wave owns 32 queries, its lane one query's column: S^T = K (Q/8)^T (ab16_score_tile), 7 tiles held, softmax in
+//      the lane plus one exchange, P^T in place. dP^T = V dO^T is streamed tile by tile, twice: once for delta = sum_k P dP, once
+//      for dS^T = P^T o (dP^T - delta), which is at once the B operand of dQ^T += K^T dS^T. The statistics of every query go
+//      to a small LDS array (m, l and delta); dQ = dQ^T / 8 is stored.
+//   B  every wave takes its 32 keys' K / 8 and V rows out of LDS into registers, then LDS = Q, dO. A lane owns one key's column:
+//      S = Q (K/8)^T (the same products in the same order as phase A: the same bits), P from the saved m and l, dP = dO V^T,
+//      dS; dV^T += dO^T P and dK^T += Q^T dS over the 7 query tiles; dK = dK^T / 8 and dV are stored.
+// No wave adds into another's output and no sum depends on another workgroup: fixed order, no atomics. Padding: keys 197..223
+// get S = -inf in phase A and P = 0 by a select in phase B (their columns are never stored); queries 197..223 are never stored
+// in phase A and enter phase B as Q = dO = 0 rows with l = inf, so P = dS = 0 exactly: they add nothing to dK or dV.
+constexpr int AB16_LD = VIT_HD + 1;
+constexpr int AB16_MAT = A16_NPAD * AB16_LD;  // floats of one padded matrix
+constexpr size_t AB16_LDS_BYTES = (size_t)(2 * AB16_MAT + 3 * A16_NPAD) * sizeof(float);  // 119 168
+
+// rows 0..196 of two [197][64] global matrices (row strides in floats) into the two LDS matrices, rows 197..223 zero
+__device__ __forceinline__ void ab16_stage(float* m0, float* m1, const float* g0, size_t s0, const float* g1, size_t s1, int tid) {
+    for (int i = tid; i < A16_NPAD * (VIT_HD / 4); i += 64 * A16_WAVES) {
+        const int t = i >> 4, c = (i & 15) * 4;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+        if (t < VIT16_N) {
+            a = *reinterpret_cast<const float4*>(g0 + (size_t)t * s0 + c);
+            b = *reinterpret_cast<const float4*>(g1 + (size_t)t * s1 + c);
+        }
+        float* d0 = m0 + t * AB16_LD + c;
+        float* d1 = m1 + t * AB16_LD + c;
+        d0[0] = a.x, d0[1] = a.y, d0[2] = a.z, d0[3] = a.w;
+        d1[0] = b.x, d1[1] = b.y, d1[2] = b.z, d1[3] = b.w;
+    }
+}
+
+// the 16 registers of a tile in chains of 4, and 7 tile sums: fixed orders
+__device__ __forceinline__ float ab16_sum16(const floatx16& x) {
+    const float a = ((x[0] + x[1]) + x[2]) + x[3], b = ((x[4] + x[5]) + x[6]) + x[7];
+    const float c = ((x[8] + x[9]) + x[10]) + x[11], d = ((x[12] + x[13]) + x[14]) + x[15];
+    return (a + b) + (c + d);
+}
+__device__ __forceinline__ float ab16_sum7(const float* t) { return ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + t[6]); }
+
+// float offset of tile t's first row, kept out of the compiler's sight: folded into every LDS address of an unrolled tile loop
+// it costs one base register per pair of reads (the two-address read's offsets are 8 bits), which spills; as a value the reads
+// of a tile share one base and their offsets fit the instruction
+__device__ __forceinline__ int ab16_tile_offset(int t) {
+    int o = 32 * t * AB16_LD;
+    asm volatile("" : "+v"(o));
+    return o;
+}
+
+// One 32 x 32 score tile, A fragments a[kk] out of LDS times b[kk], as four chains of 8 steps (16 products each) added pairwise.
+// A logit reaches exp() with the rounding errors of its chain at the logit's own size (up to 15 in a peaked row), and a single
+// 64-product chain - fine for the forward's outputs - puts dK of a dominant key past what a blocked fp32 evaluation gives.
+// Both phases call this with the operands' roles swapped: the same products in the same order, the same bits.
+__device__ __forceinline__ floatx16 ab16_score_tile(const float* a, const float (&b)[32]) {
+    floatx16 part[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) part[c][r] = 0.f;
+#pragma unroll
+        for (int kk = 8 * c; kk < 8 * c + 8; ++kk) part[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], b[kk], part[c], 0, 0, 0);
+    }
+    floatx16 out;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) out[r] = (part[0][r] + part[1][r]) + (part[2][r] + part[3][r]);
+    return out;
+}
+
+__global__ __launch_bounds__(64 * A16_WAVES) void vit_attention197_bwd_kernel(const float* __restrict__ qkv,
+                                                                              const float* __restrict__ dout,
+                                                                              float* __restrict__ dqkv, int D, int heads) {
+    extern __shared__ __attribute__((aligned(16))) float ab16_sm[];
+    float* m0s = ab16_sm;             // K, then Q
+    float* m1s = ab16_sm + AB16_MAT;  // V, then dO
+    float* st_m = ab16_sm + 2 * AB16_MAT;
+    float* st_l = st_m + A16_NPAD;
+    float* st_dl = st_l + A16_NPAD;
+    const int bh = blockIdx.x, b = bh / heads, h = bh - b * heads;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int col = lane & 31, half = lane >> 5;
+    const size_t row0 = (size_t)b * VIT16_N;
+    const float* base = qkv + row0 * 3 * D + h * VIT_HD;
+    const float* dob = dout + row0 * D + h * VIT_HD;
+    float* dbase = dqkv + row0 * 3 * D + h * VIT_HD;
+    const int own = 32 * wave + col;  // this lane's query (phase A) and key (phase B)
+    const bool valid = own < VIT16_N;
+    const int ownc = valid ? own : VIT16_N - 1;  // (padded lanes re-read token 196; nothing of theirs is stored)
+
+    // ---- phase A ----
+    ab16_stage(m0s, m1s, base + D, (size_t)3 * D, base + 2 * D, (size_t)3 * D, tid);
+    {
+        float qf[32];  // this lane's query, d = 32 half .. 32 half + 31, times head_dim ** -0.5 (a power of two: exact)
+        {
+            const float* qp = base + (size_t)ownc * 3 * D + 32 * half;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float4 q4 = *reinterpret_cast<const float4*>(qp + 4 * i);
+                qf[4 * i + 0] = q4.x * 0.125f, qf[4 * i + 1] = q4.y * 0.125f, qf[4 * i + 2] = q4.z * 0.125f, qf[4 * i + 3] = q4.w * 0.125f;
+            }
+        }
+        __syncthreads();
+        // S^T tile t: rows = keys 32 t + (r & 3) + 8 (r >> 2) + 4 half, column = this lane's query
+        floatx16 sc[A16_WAVES];
+        const float* ka = m0s + col * AB16_LD + 32 * half;
+#pragma unroll
+        for (int t = 0; t < A16_WAVES; ++t) sc[t] = ab16_score_tile(ka + ab16_tile_offset(t), qf);
+        float m = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < A16_WAVES; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if (t == A16_WAVES - 1 && 32 * t + (r & 3) + 8 * (r >> 2) + 4 * half >= VIT16_N) sc[t][r] = -INFINITY;
+                m = fmaxf(m, sc[t][r]);
+            }
+        m = fmaxf(m, __shfl_xor(m, 32));
+        // the denominator and delta below are summed in short chains (4 registers, 4 of those, 7 tiles, 2 halves), not in one
+        // 112-term chain: where one key dominates, dS = P (dP - delta) cancels and carries their rounding errors at full size
+        float tsum[A16_WAVES];
+#pragma unroll
+        for (int t = 0; t < A16_WAVES; ++t) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sc[t][r] = expf(sc[t][r] - m);
+            tsum[t] = ab16_sum16(sc[t]);
+        }
+        float sum = ab16_sum7(tsum);
+        sum += __shfl_xor(sum, 32);
+#pragma unroll
+        for (int t = 0; t < A16_WAVES; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sc[t][r] /= sum;  // P^T (a division: one rounding, as the fp32 reference)
+
+        float dof[32];  // this lane's dO row, d = 32 half .. 32 half + 31
+        {
+            const float* op = dob + (size_t)ownc * D + 32 * half;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float4 o4 = *reinterpret_cast<const float4*>(op + 4 * i);
+                dof[4 * i + 0] = o4.x, dof[4 * i + 1] = o4.y, dof[4 * i + 2] = o4.z, dof[4 * i + 3] = o4.w;
+            }
+        }
+        // delta = sum over the keys of P dP, dP^T tile t = V[keys of t] dO^T: in (tile, register) order, then the other half
+        const float* va = m1s + col * AB16_LD + 32 * half;
+#pragma unroll
+        for (int t = 0; t < A16_WAVES; ++t) {
+            const int to = ab16_tile_offset(t);
+            floatx16 dp;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dp[r] = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < 32; ++kk) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(va[to + kk], dof[kk], dp, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dp[r] *= sc[t][r];
+            tsum[t] = ab16_sum16(dp);
+        }
+        float delta = ab16_sum7(tsum);
+        delta += __shfl_xor(delta, 32);
+        // (a padded query: l = inf, so that phase B gets P = exp(0 - 0) / inf = 0 for it)
+        if (half == 0) st_m[own] = valid ? m : 0.f, st_l[own] = valid ? sum : INFINITY, st_dl[own] = valid ? delta : 0.f;
+
+        // dQ^T tile dt: rows = d 32 dt + (r & 3) + 8 (r >> 2) + 4 half, column = this lane's query
+        floatx16 dq[2];
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
+        const float* kt = m0s + 4 * half * AB16_LD + col;
+#pragma unroll
+        for (int t = 0; t < A16_WAVES; ++t) {
+            const int to = ab16_tile_offset(t);
+            floatx16 dp;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dp[r] = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < 32; ++kk) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(va[to + kk], dof[kk], dp, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if (32 * t + 8 * (r >> 2) >= VIT16_N) continue;  // (both halves' keys are padding: dS = 0 and K = 0)
+                const float ds = sc[t][r] * (dp[r] - delta);
+                const float* kr = kt + to + ((r & 3) + 8 * (r >> 2)) * AB16_LD;
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[32 * dt], ds, dq[dt], 0, 0, 0);
+            }
+        }
+        if (valid) {
+            float* qo = dbase + (size_t)own * 3 * D + 4 * half;
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4*>(qo + 32 * dt + 8 * g) =
+                        make_float4(dq[dt][4 * g + 0] * 0.125f, dq[dt][4 * g + 1] * 0.125f, dq[dt][4 * g + 2] * 0.125f,
+                                    dq[dt][4 * g + 3] * 0.125f);
+        }
+    }
+
+    // ---- phase B ----
+    float kf[32], vf[32];  // this lane's key: K / 8 and V, d = 32 half .. 32 half + 31 (rows 197..223: zero)
+#pragma unroll
+    for (int kk = 0; kk < 32; ++kk) {
+        kf[kk] = m0s[own * AB16_LD + 32 * half + kk] * 0.125f;
+        vf[kk] = m1s[own * AB16_LD + 32 * half + kk];
+    }
+    __syncthreads();  // every wave has its keys and is done with K and V
+    ab16_stage(m0s, m1s, base, (size_t)3 * D, dob, (size_t)D, tid);
+    __syncthreads();
+    // dV^T / dK^T tile dt: rows = d 32 dt + (r & 3) + 8 (r >> 2) + 4 half, column = this lane's key
+    floatx16 dv[2], dk[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dv[dt][r] = 0.f, dk[dt][r] = 0.f;
+    const float* qa = m0s + col * AB16_LD + 32 * half;
+    const float* oa = m1s + col * AB16_LD + 32 * half;
+    const float* qt = m0s + 4 * half * AB16_LD + col;
+    const float* ot = m1s + 4 * half * AB16_LD + col;
+#pragma unroll 1
+    for (int t = 0; t < A16_WAVES; ++t) {
+        // S and dP tile t: rows = queries 32 t + (r & 3) + 8 (r >> 2) + 4 half, column = this lane's key
+        const floatx16 sq = ab16_score_tile(qa + 32 * t * AB16_LD, kf);
+        floatx16 dp;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dp[r] = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < 32; ++kk) dp = __builtin_amdgcn_mfma_f32_32x32x2f32(oa[32 * t * AB16_LD + kk], vf[kk], dp, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int qr = 32 * t + (r & 3) + 8 * (r >> 2);
+            const int q = qr + 4 * half;
+            float p = expf(sq[r] - st_m[q]) / st_l[q];
+            p = valid ? p : 0.f;
+            const float ds = p * (dp[r] - st_dl[q]);
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+                dv[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(ot[qr * AB16_LD + 32 * dt], p, dv[dt], 0, 0, 0);
+                dk[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(qt[qr * AB16_LD + 32 * dt], ds, dk[dt], 0, 0, 0);
+            }
+        }
+    }
+    if (!valid) return;
+    float* ko = dbase + (size_t)own * 3 * D + D + 4 * half;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            *reinterpret_cast<float4*>(ko + 32 * dt + 8 * g) =
+                make_float4(dk[dt][4 * g + 0] * 0.125f, dk[dt][4 * g + 1] * 0.125f, dk[dt][4 * g + 2] * 0.125f, dk[dt][4 * g + 3] * 0.125f);
+            *reinterpret_cast<float4*>(ko + D + 32 * dt + 8 * g) =
+                make_float4(dv[dt][4 * g + 0], dv[dt][4 * g + 1], dv[dt][4 * g + 2], dv[dt][4 * g + 3]);
+        }
+}
+
+// N: tokens per frame, 50 (the LDS-resident VALU kernel) or 197 (the MFMA kernel; qkv, dout and dqkv 16-byte aligned)
+int launch_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int N, int D, int heads, hipStream_t s) {
+    if (N != VIT_N && N != VIT16_N) return set_err(ORBIT_ERR_ARG, "vit attention backward: %d tokens (50 or 197)", N);
+    static bool attr_set = false;  // > 64 KiB of dynamic LDS needs the opt-in once
+    if (N == VIT16_N && !attr_set) {
+        ORBIT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vit_attention197_bwd_kernel),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)AB16_LDS_BYTES));
+        attr_set = true;
+    }
+    const int pi = prof_start(N == VIT_N ? "vit_attention_bwd" : "vit_attention197_bwd", 10.0 * B * heads * N * N * VIT_HD,
+                              4.0 * 7 * (double)B * N * D, s);
+    if (N == VIT_N)
+        vit_attention_bwd_kernel<<<B * heads, 256, 0, s>>>(qkv, dout, dqkv, D, heads);
+    else
+        vit_attention197_bwd_kernel<<<B * heads, 64 * A16_WAVES, AB16_LDS_BYTES, s>>>(qkv, dout, dqkv, D, heads);
     prof_stop(pi, s);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
@@ -908,9 +1175,11 @@ struct orbit_vit {
     float eps = 1e-6f;
     bool clip = false;  // pre_norm: no patch-embedding bias, norm_pre after the position add
     // geometry: patch size (32 or 16), patches per side and per frame, tokens per frame, K of the patch GEMM, largest batch.
-    // The patch-16 plans are forward only (no tape, no backward)
+    // The patch-16 plans are forward only (no tape, no backward) until orbit_vit_enable_backward; weight gradients never
     int patch = VIT_PATCH, grid = VIT_GRID, P = VIT_P, N = VIT_N, kpatch = VIT_KPATCH, max_b = VIT_MAX_B;
-    bool forward_only() const { return patch != VIT_PATCH; }
+    bool backward_enabled = false;
+    bool forward_only() const { return patch != VIT_PATCH && !backward_enabled; }
+    bool weight_grads() const { return patch == VIT_PATCH; }
     ParamPool pool{64};  // the parameters by state_dict key (csrc/param_pool.h); 256-byte aligned tensors (float4 loads)
     // where the forward and the backward find each tensor: pool offsets, fixed by orbit_vit_create
     size_t cls = 0, pos = 0, patch_w = 0, patch_b = VIT_ABSENT, pre_w = VIT_ABSENT, pre_b = VIT_ABSENT, norm_w = 0, norm_b = 0;
@@ -969,7 +1238,7 @@ struct VitTape {
     size_t x, qkv, mid, u, block, last, total;  // byte offsets inside a block, block stride, the final stream, size
 };
 VitTape vit_tape(const orbit_vit* v, int B) {
-    const size_t md = align_up((size_t)B * VIT_N * v->D * sizeof(float), 256);
+    const size_t md = align_up((size_t)B * v->N * v->D * sizeof(float), 256);
     VitTape T;
     T.x = 0, T.qkv = md, T.mid = 4 * md, T.u = 5 * md, T.block = 9 * md;
     T.last = VIT_DEPTH * T.block;
@@ -1214,16 +1483,16 @@ int vit_backward_impl(orbit_vit_t* v, const float* frames, int B, const float* f
     if ((rc = vit_ensure_wt(v, s))) return rc;
     const VitWt W = vit_wt(v);
     const VitTape T = vit_tape(v, B);
-    const int D = v->D, M = B * VIT_N;
+    const int D = v->D, N = v->N, M = B * N;  // (M * 4 D < 2^31 up to max_b frames; every index below is size_t)
     float *dx = b.dx, *h = b.h, *h2 = b.h2, *big = b.big, *partial = b.partial;
     auto slot = [&](int i, size_t off) { return reinterpret_cast<const float*>(tp + i * T.block + off); };
     auto gamma_of = [&](size_t w, int sl) { return film_gamma ? film_gamma + (size_t)sl * D : v->p(w); };
     auto beta_of = [&](size_t w, int sl) { return film_beta ? film_beta + (size_t)sl * D : v->p(w); };
-    // final norm: token 0 of every frame from dfeats; the other 49 token rows of the gradient stream are exactly zero
+    // final norm: token 0 of every frame from dfeats; the other token rows of the gradient stream are exactly zero
     const int last = 2 * VIT_DEPTH;
     if ((rc = zero_gradient_stream(dx, (size_t)M * D, s))) return rc;
-    if ((rc = launch_layernorm_bwd(reinterpret_cast<const float*>(tp + T.last), (size_t)VIT_N * D, dfeats, D, gamma_of(v->norm_w, last),
-                                   v->eps, nullptr, dx, (size_t)VIT_N * D, B, D, partial, dgamma + (size_t)last * D,
+    if ((rc = launch_layernorm_bwd(reinterpret_cast<const float*>(tp + T.last), (size_t)N * D, dfeats, D, gamma_of(v->norm_w, last),
+                                   v->eps, nullptr, dx, (size_t)N * D, B, D, partial, dgamma + (size_t)last * D,
                                    dbeta + (size_t)last * D, s)))
         return rc;
     for (int i = VIT_DEPTH - 1; i >= 0; --i) {
@@ -1247,12 +1516,12 @@ int vit_backward_impl(orbit_vit_t* v, const float* frames, int B, const float* f
             return rc;
         // x_mid = x + proj(attn(qkv)):  dO = dx Wp,  dqkv = attn'(dO),  dh = dqkv Wqkv,  dx += LN1'(dh)
         if (pg) {
-            if ((rc = launch_attention(slot(i, T.qkv), h2, B, VIT_N, D, v->heads, s))) return rc;
+            if ((rc = launch_attention(slot(i, T.qkv), h2, B, N, D, v->heads, s))) return rc;
             if ((rc = launch_wgrad<WX_PLAIN>(dx, h2, pg + k.proj_w, pg + k.proj_b, M, D, D, b.wgrad, "wgrad_proj", s))) return rc;
         }
         GemmArgs dproj{dx, wt + W.proj, nullptr, nullptr, nullptr, h, M, D, D};
         if ((rc = launch_gemm<EPI_BIAS, true>(dproj, "dgrad_proj", s))) return rc;
-        if ((rc = launch_attention_bwd(slot(i, T.qkv), h, big, B, D, v->heads, s))) return rc;
+        if ((rc = launch_attention_bwd(slot(i, T.qkv), h, big, B, N, D, v->heads, s))) return rc;
         sl = 2 * i;
         if (pg) {
             if ((rc = launch_layernorm(slot(i, T.x), D, h2, D, M, D, gamma_of(k.norm1_w, sl), beta_of(k.norm1_b, sl), v->eps, s)))
@@ -1297,12 +1566,17 @@ int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* f
 }
 
 // ---- FiLM gradients of the frozen network ----------------------------------------------------------------------------
+int orbit_vit_enable_backward(orbit_vit_t* v) {
+    ORBIT_REQUIRE(v, "vit_enable_backward: null pointer");
+    v->backward_enabled = true;  // (read by forward_only() of the patch-16 plans only)
+    return ORBIT_OK;
+}
 size_t orbit_vit_tape_bytes(const orbit_vit_t* v, int B) {
-    if (!v || v->forward_only() || B <= 0 || B > VIT_MAX_B) return 0;
+    if (!v || v->forward_only() || B <= 0 || B > v->max_b) return 0;
     return vit_tape(v, B).total;
 }
 size_t orbit_vit_backward_workspace_bytes(const orbit_vit_t* v, int B) {
-    if (!v || v->forward_only() || B <= 0 || B > VIT_MAX_B) return 0;
+    if (!v || v->forward_only() || B <= 0 || B > v->max_b) return 0;
     return vit_ws(v, B, true).total;
 }
 
@@ -1342,7 +1616,7 @@ int orbit_vit_backward(orbit_vit_t* v, int B, const float* film_gamma, const flo
 size_t orbit_vit_grad_floats(const orbit_vit_t* v) { return v ? v->pool.pool_floats : 0; }
 size_t orbit_vit_param_offset(const orbit_vit_t* v, int i) { return (v && i >= 0 && i < v->pool.size()) ? v->pool.off(i) : 0; }
 size_t orbit_vit_backward_params_workspace_bytes(const orbit_vit_t* v, int B) {
-    if (!v || v->forward_only() || B <= 0 || B > VIT_MAX_B) return 0;
+    if (!v || v->forward_only() || !v->weight_grads() || B <= 0 || B > v->max_b) return 0;
     return vit_ws_params(v, B).total;
 }
 
@@ -1352,6 +1626,8 @@ int orbit_vit_backward_params(orbit_vit_t* v, const float* frames, int B, const 
     const char* who = "vit_backward_params";
     ORBIT_REQUIRE(frames && dfeats && tape && param_grads && dgamma && dbeta && workspace, "%s: null pointer", who);
     if (int rc = vit_check_trainable(who, v)) return rc;  // (before the state checks: a refusal needs no loaded plan)
+    ORBIT_REQUIRE(v->weight_grads(), "%s: %s gives FiLM gradients through the frozen network only (weight gradients are not "
+                  "built for the patch-%d models)", who, v->name.c_str(), v->patch);
     if (int rc = vit_check_call(who, v, B, film_gamma, film_beta)) return rc;
     const VitWsParams L = vit_ws_params(v, B);
     if (int rc = vit_check_buffer(who, "workspace", workspace, workspace_bytes, L.total)) return rc;
@@ -1491,15 +1767,23 @@ int orbit_op_vit_layernorm_bwd(const float* x, size_t x_stride, const float* dy,
     return launch_layernorm_bwd(x, x_stride, dy, dy_stride, gamma, eps, dres, dx, dx_stride, rows, D, partial, dgamma, dbeta, s);
 }
 
-int orbit_op_vit_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int D, int heads,
-                               orbit_stream_t stream) {
+int orbit_op_vit_attention_bwd_tokens(const float* qkv, const float* dout, float* dqkv, int B, int tokens, int D, int heads,
+                                      orbit_stream_t stream) {
     ORBIT_REQUIRE(qkv && dout && dqkv, "op_vit_attention_bwd: null pointer");
+    ORBIT_REQUIRE(tokens == VIT_N || tokens == VIT16_N, "op_vit_attention_bwd: %d tokens per frame (50 or 197)", tokens);
     ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_attention_bwd: unsupported width %d (384 or 768)", D);
     ORBIT_REQUIRE(heads * VIT_HD == D, "op_vit_attention_bwd: %d heads of %d do not make D=%d", heads, VIT_HD, D);
-    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "op_vit_attention_bwd: batch of %d frames (1..%d)", B, VIT_MAX_B);
-    ORBIT_REQUIRE((((uintptr_t)qkv | (uintptr_t)dout | (uintptr_t)dqkv) & 3) == 0,
-                  "op_vit_attention_bwd: pointers must be 4-byte aligned");
-    return launch_attention_bwd(qkv, dout, dqkv, B, D, heads, (hipStream_t)stream);
+    const int max_b = tokens == VIT16_N ? VIT16_MAX_B : VIT_MAX_B;
+    ORBIT_REQUIRE(B > 0 && B <= max_b, "op_vit_attention_bwd: batch of %d frames (1..%d)", B, max_b);
+    const uintptr_t mask = tokens == VIT16_N ? 15 : 3;  // (the 197-token kernel moves float4)
+    ORBIT_REQUIRE((((uintptr_t)qkv | (uintptr_t)dout | (uintptr_t)dqkv) & mask) == 0,
+                  "op_vit_attention_bwd: pointers must be %d-byte aligned", (int)mask + 1);
+    return launch_attention_bwd(qkv, dout, dqkv, B, tokens, D, heads, (hipStream_t)stream);
+}
+
+int orbit_op_vit_attention_bwd(const float* qkv, const float* dout, float* dqkv, int B, int D, int heads,
+                               orbit_stream_t stream) {
+    return orbit_op_vit_attention_bwd_tokens(qkv, dout, dqkv, B, VIT_N, D, heads, stream);
 }
 
 size_t orbit_op_vit_linear_wgrad_workspace_floats(int M, int N, int K) {

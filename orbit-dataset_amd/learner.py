@@ -84,6 +84,11 @@ def build_parser():
                    help="vit_*_32* extractors: opt in to the native gradients of every parameter of the transformer (implies what "
                         "--vit_native_backward admits, and admits --learn_extractor). Ignored for the other extractors, the "
                         "inference-only patch-16 transformers among them")
+    p.add_argument("--vit16_native_backward", action="store_true",
+                   help="vit_*_16* extractors (the patch-16 transformers) only, ignored elsewhere: opt in to the native FiLM "
+                        "gradients through the FROZEN transformer at 197 tokens (--adapt_features training, with or without "
+                        "--with_lite; the multi-step finetuner's --adapt_features). --learn_extractor stays refused: weight "
+                        "gradients are not built for these models")
     p.add_argument("--effnetv2_native_backward", action="store_true",
                    help="efficientnet_v2_s: opt in to the native FiLM gradients through the FROZEN network (--adapt_features "
                         "training, with or without --with_lite; the multi-step finetuner's --adapt_features). --learn_extractor "
@@ -243,18 +248,23 @@ def split_annotation_args(args, split):
 
 # The extractors whose network is frozen unless a flag opts in: the frame normalisation the reference sets for them
 # (utils/args.py:185-190; the other extractors keep --frame_norm_method), the one frame size they run on (None: any), the flag
-# that opens the FiLM gradients through the frozen network and the one that opens the weight gradients (None: not built), and
-# the words their refusals differ in.
-FrozenExtractor = collections.namedtuple("FrozenExtractor", "frame_norm frame_size film_flag weight_flag no_weights no_backward")
+# that opens the FiLM gradients through the frozen network and the one that opens the weight gradients (None: not built), the
+# words their refusals differ in, and - the patch-16 transformers, whose refusals under the two patch-32 flags are pinned - a
+# FiLM-gradient flag of their own.
+FrozenExtractor = collections.namedtuple("FrozenExtractor",
+                                         "frame_norm frame_size film_flag weight_flag no_weights no_backward film16_flag",
+                                         defaults=(None,))
 _VIT = ("vit_native_backward", "vit_native_weight_backward", "weight gradients through a ViT", "a ViT")
+_VIT16 = (None, None) + _VIT[2:] + ("vit16_native_backward",)
 FROZEN_EXTRACTORS = {
     "vit_s_32": FrozenExtractor("imagenet_inception", 224, *_VIT),
     "vit_b_32": FrozenExtractor("imagenet_inception", 224, *_VIT),
     "vit_b_32_clip": FrozenExtractor("openai_clip", 224, *_VIT),
-    # the patch-16 models: inference + FiLM only, no flag opens a gradient (csrc/vit.hip builds no backward at 197 tokens)
-    "vit_s_16": FrozenExtractor("imagenet_inception", 224, None, None, *_VIT[2:]),
-    "vit_b_16": FrozenExtractor("imagenet_inception", 224, None, None, *_VIT[2:]),
-    "vit_b_16_clip": FrozenExtractor("openai_clip", 224, None, None, *_VIT[2:]),
+    # the patch-16 models: inference + FiLM only under the patch-32 flags; --vit16_native_backward opens the FiLM gradients
+    # through the frozen network (csrc/vit.hip vit_attention197_bwd_kernel), nothing opens the weight gradients
+    "vit_s_16": FrozenExtractor("imagenet_inception", 224, *_VIT16),
+    "vit_b_16": FrozenExtractor("imagenet_inception", 224, *_VIT16),
+    "vit_b_16_clip": FrozenExtractor("openai_clip", 224, *_VIT16),
     # any frame size, as efficientnet_b0. By default the native plan has no backward (its ConvBnAct blocks add the skip after
     # the activation, csrc/extractor_train.hip plan_trainable); the first flag opens the frozen form, the second all of it
     "efficientnet_v2_s": FrozenExtractor("imagenet_inception", None, "effnetv2_native_backward", "effnetv2_native_weight_backward",
@@ -333,6 +343,17 @@ def num_items(dataset):
     return dataset.num_objects if isinstance(dataset, ObjectEpisodicORBITDataset) else dataset.num_users
 
 
+def opted_in(args, spec):
+    """The one map from a frozen-scope extractor's opt-in flags to the gradient scope they open and the extractor attributes
+    they set -> (scope "all" | "film" | "none", the flag that opened it, the attributes of every flag given)."""
+    table = ((spec.weight_flag, "all", "native_weight_backward"), (spec.film_flag, "film", "native_backward"),
+             (spec.film16_flag, "film", "native_backward_patch16"))
+    on = [(flag, scope, attr) for flag, scope, attr in table if flag and getattr(args, flag, False)]
+    if not on:
+        return "none", None, []
+    return on[0][1], on[0][0], [attr for _, _, attr in on]
+
+
 def verify_args(args):
     """reference utils/args.py:203-217. For the frozen-scope extractors (FROZEN_EXTRACTORS) also the frame normalisation the
     reference sets for them and the inference-only scope: everything that would send a gradient or batch statistics through the
@@ -368,12 +389,13 @@ def verify_args(args):
     if spec.frame_size is not None and args.frame_size != spec.frame_size:
         sys.exit("error: --feature_extractor %s needs --frame_size %d (got %d)" % (fe, spec.frame_size, args.frame_size))
     multistep = getattr(args, "personalize_num_grad_steps", None) is not None
-    if spec.weight_flag and getattr(args, spec.weight_flag, False):
+    scope, flag, _ = opted_in(args, spec)
+    if scope == "all":
         pass  # native gradients of every parameter: everything the other extractors train is admitted
-    elif spec.film_flag and getattr(args, spec.film_flag, False):
+    elif scope == "film":
         if args.learn_extractor:
             sys.exit("error: --%s gives FiLM gradients through a frozen %s only: --learn_extractor (%s) is not built"
-                     % (spec.film_flag, fe, spec.no_weights))
+                     % (flag, fe, spec.no_weights))
     elif "train" in args.mode or args.learn_extractor or args.with_lite or (multistep and args.adapt_features):
         sys.exit("error: --feature_extractor %s is inference-only here (no backward through %s): use --mode test "
                  "without --learn_extractor / --with_lite%s" % (fe, spec.no_backward, " / --adapt_features" if multistep else ""))
@@ -529,9 +551,8 @@ class Learner:
             synthetic.init_parameters_(self.model, seed=a.seed,
                                        film_strength=0.02 if a.feature_extractor == "efficientnet_b0" else 0.1)
         spec = FROZEN_EXTRACTORS.get(a.feature_extractor)
-        for flag, attr in ((spec.film_flag, "native_backward"), (spec.weight_flag, "native_weight_backward")) if spec else ():
-            if flag and getattr(a, flag):
-                setattr(self.model.feature_extractor, attr, True)
+        for attr in opted_in(a, spec)[2] if spec else ():
+            setattr(self.model.feature_extractor, attr, True)
         self.model._set_device(self.device)
         self.model._send_to_device()
 

@@ -13,6 +13,13 @@ torch.nn.functional.linear (fp32, the vendor BLAS) on the same four shapes at M 
 the module with native_weight_backward) at the step shapes B = 16 and B = 200, the weight-gradient GEMM family's TF/s per layer
 shape at M = 10 000 token rows (orbit_op_vit_linear_wgrad, split-reduction launch + reduce), and fp32 `dy.t() @ x` through torch
 (the vendor BLAS) on the same shapes. Nothing here is gated.
+
+--train_film reports the FiLM-gradient step of the frozen network, for any of the six models: ms of taped forward +
+orbit_vit_backward (through the module with its FiLM opt-in: native_backward, or native_backward_patch16 for the patch-16
+models) at a LITE-sized batch of 16 frames, and the profiler's per-kernel rows of one such step - launches, ms and share of
+the step's kernel time - with the attention backward's time relative to the attention forward's on the same batch.
+
+    python tools/vit_bench.py --train_film --models vit_s_16,vit_b_16,vit_b_16_clip
 """
 import argparse
 import ctypes
@@ -159,6 +166,64 @@ def main_train(a):
     print(json.dumps(result))
 
 
+FILM_BATCH = 16  # frames with a gradient per LITE step (learner --num_lite_samples 16)
+
+
+def _kernel_rows(run):
+    """{profiler row: (launches, ms)} of one call of `run`"""
+    lib = _lib.load()
+    torch.cuda.synchronize()
+    lib.orbit_prof_enable(1)
+    run()
+    torch.cuda.synchronize()
+    lib.orbit_prof_collect(None, None, None)
+    rows = {}
+    for i in range(lib.orbit_prof_num_variants()):
+        name = ctypes.create_string_buffer(48)
+        launches, ms = ctypes.c_long(), ctypes.c_double()
+        lib.orbit_prof_variant(i, name, ctypes.byref(launches), ctypes.byref(ms), None, None)
+        if launches.value:
+            rows[name.value.decode()] = (launches.value, ms.value)
+    lib.orbit_prof_enable(0)
+    return rows
+
+
+def main_train_film(a):
+    from orbit_dataset_amd.model.feature_extractors import create_feature_extractor
+    B = FILM_BATCH
+    result = {"metric": "vit_train_film_ms", "what": "taped forward + orbit_vit_backward, frozen network, FiLM vectors trainable",
+              "batch_frames": B, "models": {}}
+    for name in a.models.split(","):
+        fe, _ = create_feature_extractor(name, with_film=True, learn_extractor=False)
+        synthetic.init_parameters_(fe)
+        fe.eval().to("cuda:0")
+        fe.native_backward = fe.native_backward_patch16 = True  # (each is ignored by the other patch size)
+        x = torch.randn(B, 3, 224, 224, device="cuda:0")
+        r = torch.randn(B, fe.output_size, device="cuda:0")
+        gamma = torch.ones(fe.film_size, device="cuda:0", requires_grad=True)
+        beta = torch.zeros(fe.film_size, device="cuda:0", requires_grad=True)
+
+        def step():
+            gamma.grad = beta.grad = None
+            (fe(x, film=(gamma, beta)) * r).sum().backward()
+        ms = _time(step, a.steps, a.warmup)
+        rows = _kernel_rows(step)
+        total = sum(t for _, t in rows.values())
+        out = {"fwd_bwd_ms": round(ms, 3), "kernel_ms_total": round(total, 3),
+               "kernels": {k: {"launches": n, "ms": round(t, 4), "share": round(t / total, 4)}
+                           for k, (n, t) in sorted(rows.items(), key=lambda kv: -kv[1][1])}}
+        fwd = [k for k in rows if k in ("vit_attention", "vit_attention197")]
+        bwd = [k for k in rows if k in ("vit_attention_bwd", "vit_attention197_bwd")]
+        if fwd and bwd:
+            per = lambda k: rows[k][1] / rows[k][0]
+            out["attention_bwd_share_of_step"] = round(rows[bwd[0]][1] / total, 4)
+            out["attention_bwd_over_fwd"] = round(per(bwd[0]) / per(fwd[0]), 2)
+        result["models"][name] = out
+        del fe
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--steps", type=int, default=10)
@@ -166,9 +231,13 @@ def main(argv=None):
     p.add_argument("--models", default="vit_s_32,vit_b_32,vit_b_32_clip",
                    help="comma-separated, any of the six transformer extractors (--train: the patch-32 ones only)")
     p.add_argument("--train", action="store_true", help="the training step and the weight-gradient GEMMs instead")
+    p.add_argument("--train_film", action="store_true",
+                   help="the FiLM-gradient step of the frozen network at a batch of %d frames instead (all six models)" % FILM_BATCH)
     a = p.parse_args(argv)
     _lib.require_gpu()
     torch.cuda.set_device(0)
+    if a.train_film:
+        return main_train_film(a)
     if a.train:
         return main_train(a)
     result = {"metric": "vit_task_ms", "task": "5-way, 200 support + 200 query frames, 224x224", "peak_tflops": PEAK_TF,
