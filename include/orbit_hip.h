@@ -264,7 +264,8 @@ int orbit_extractor_forward(orbit_extractor_t* fe, const float* frames, int B,
  * frame is 196 patches + the class token. They are inference + FiLM only: orbit_vit_tape_bytes,
  * orbit_vit_backward_workspace_bytes and orbit_vit_backward_params_workspace_bytes return 0 and the three training entry points
  * return ORBIT_ERR_ARG naming the model, before any launch or allocation - until orbit_vit_enable_backward (below) opts a plan
- * into the taped forward and the FiLM gradients of the frozen network; weight gradients stay refused. Batch cap: 1..8192 frames for the patch-32 plans,
+ * into the taped forward and the FiLM gradients of the frozen network, and orbit_vit_enable_weight_backward (below) into the
+ * gradients of every parameter; without the latter weight gradients stay refused. Batch cap: 1..8192 frames for the patch-32 plans,
  * 1..2048 for the patch-16 plans (B * 197 * 4 D stays below 2^31); beyond it orbit_vit_workspace_bytes returns 0 and
  * orbit_vit_forward ORBIT_ERR_ARG. */
 int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out);
@@ -307,10 +308,19 @@ int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* f
 size_t orbit_vit_tape_bytes(const orbit_vit_t* v, int B);
 /* Opt a patch-16 plan into orbit_vit_train_forward / orbit_vit_backward: the same tape and workspace layouts at 197 tokens per
  * frame ((12 * 9 + 1) * align_up(197 B * D * 4, 256) tape bytes), for 1..2048 frames, 0 outside. orbit_vit_backward_params
- * still returns ORBIT_ERR_ARG before any launch (weight gradients are not built for the patch-16 models) and its workspace
- * size stays 0. A flag on this plan only: idempotent, allocates nothing, legal before or after orbit_vit_finalize and after
+ * still returns ORBIT_ERR_ARG before any launch (weight gradients are a second opt-in for the patch-16 models:
+ * orbit_vit_enable_weight_backward, next) and its workspace size stays 0. A flag on this plan only: idempotent, allocates nothing, legal before or after orbit_vit_finalize and after
  * inference forwards. A no-op returning ORBIT_OK on a patch-32 plan; ORBIT_ERR_ARG for NULL. */
 int orbit_vit_enable_backward(orbit_vit_t* v);
+/* Opt a patch-16 plan into orbit_vit_backward_params as well (--learn_extractor): implies orbit_vit_enable_backward, and
+ * orbit_vit_backward_params_workspace_bytes is then nonzero for 1..2048 frames, 0 outside. The reverse pass is the patch-32
+ * one with the geometry of the plan: every Linear weight gradient at 197 B rows, the patch filter gradient [D][3][16][16] from
+ * 196 B gathered 16-float patch rows (K = 768), dpos [197][D]; the promises of orbit_vit_backward_params below hold unchanged
+ * (dgamma / dbeta bit for bit those of orbit_vit_backward, FiLM-slot entries of param_grads untouched, deterministic). A flag
+ * on this plan only: idempotent, allocates nothing, legal before or after orbit_vit_finalize and after inference forwards. A
+ * patch-16 plan that has not called it behaves as described above. A no-op returning ORBIT_OK on a patch-32 plan;
+ * ORBIT_ERR_ARG for NULL. */
+int orbit_vit_enable_weight_backward(orbit_vit_t* v);
 size_t orbit_vit_backward_workspace_bytes(const orbit_vit_t* v, int B);
 int orbit_vit_train_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
                             float* feats, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
@@ -328,7 +338,8 @@ int orbit_vit_backward(orbit_vit_t* v, int B, const float* film_gamma, const flo
  * (16-byte aligned; the patch-embedding filter gradient reads it). Per block the X operands that are not on the tape are
  * recomputed by the forward's kernels; the Linear filter gradients dW [N][K] = dY^T X split their reduction over the token
  * rows into a number of partial tiles that depends on (rows, N, K) only, added in a fixed order: deterministic, no atomics.
- * param_grads 256-byte aligned; workspace of orbit_vit_backward_params_workspace_bytes (0 for B outside 1..8192). */
+ * param_grads 256-byte aligned; workspace of orbit_vit_backward_params_workspace_bytes (0 for B outside 1..8192; for a
+ * patch-16 plan 0 until orbit_vit_enable_weight_backward, then 0 for B outside 1..2048). */
 size_t orbit_vit_grad_floats(const orbit_vit_t* v);
 size_t orbit_vit_param_offset(const orbit_vit_t* v, int i);
 size_t orbit_vit_backward_params_workspace_bytes(const orbit_vit_t* v, int B);
@@ -511,6 +522,13 @@ int orbit_op_vit_linear_wgrad(const float* dy, const float* x, float* dw, float*
  * workspace: orbit_op_vit_linear_wgrad_workspace_floats(49 B, D, 3072) floats. */
 int orbit_op_vit_patch_embed_bwd(const float* frames, const float* dtokens, float* dw, float* dbias_or_null, float* dpos,
                                  float* dcls, int B, int D, float* workspace, size_t workspace_floats, orbit_stream_t stream);
+/* The same with the patch size as an argument (backward of orbit_op_vit_patch_embed_p). patch = 32: the call above. patch = 16:
+ * dtokens [B][197][D] -> dw OIHW [D][3][16][16], dbias [D] (or NULL) = the sum of token rows 1..196, dpos [197][D], dcls [D];
+ * workspace: orbit_op_vit_linear_wgrad_workspace_floats(196 B, D, 768) floats; B at most 2048. Any other patch size, width or
+ * batch, a null pointer, a misaligned pointer or a short workspace is an argument error before any launch. */
+int orbit_op_vit_patch_embed_bwd_p(const float* frames, const float* dtokens, float* dw, float* dbias_or_null, float* dpos,
+                                   float* dcls, int B, int D, int patch, float* workspace, size_t workspace_floats,
+                                   orbit_stream_t stream);
 
 /* fused MBConv front half (EfficientNet InvertedResidual, Cin <= 40): y = silu(bn2(dw_KxK(silu(bn1(x . w1^T))))) with the
  * expanded tensor kept in LDS. x NHWC [B][H][W][Cin]; w1 torch [mid][Cin][1][1]; wdw torch [mid][1][K][K];

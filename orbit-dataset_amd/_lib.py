@@ -66,6 +66,7 @@ _SIGNATURES = {
     "orbit_vit_forward": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P]),
     "orbit_vit_tape_bytes": (c_size_t, [P, c_int]),
     "orbit_vit_enable_backward": (c_int, [P]),
+    "orbit_vit_enable_weight_backward": (c_int, [P]),
     "orbit_vit_backward_workspace_bytes": (c_size_t, [P, c_int]),
     "orbit_vit_train_forward": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P, c_size_t, P]),
     "orbit_vit_backward": (c_int, [P, c_int, P, P, P, P, c_size_t, P, P, P, c_size_t, P]),
@@ -108,6 +109,7 @@ _SIGNATURES = {
     "orbit_op_vit_linear_wgrad_workspace_floats": (c_size_t, [c_int, c_int, c_int]),
     "orbit_op_vit_linear_wgrad": (c_int, [P] * 4 + [c_int] * 4 + [P, c_size_t, P]),
     "orbit_op_vit_patch_embed_bwd": (c_int, [P] * 6 + [c_int] * 2 + [P, c_size_t, P]),
+    "orbit_op_vit_patch_embed_bwd_p": (c_int, [P] * 6 + [c_int] * 3 + [P, c_size_t, P]),
     "orbit_op_mbconv_front": (c_int, [P] * 9 + [c_int] * 11 + [P]),
     "orbit_op_mbconv_front_partials": (c_int, [c_int] * 6),
     "orbit_op_stem_dw_front_partials": (c_int, [c_int] * 3),

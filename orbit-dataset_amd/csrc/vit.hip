@@ -23,7 +23,9 @@
 // run the same forward with the geometry read from the plan: the patch GEMM's EPI_PATCH16 form (k = c*256 + kh*16 + kw, token
 // rows 1..196) and vit_attention197_kernel (fp32 MFMA, K and V resident in LDS). Their plans are inference + FiLM only until
 // orbit_vit_enable_backward switches on the taped forward and the FiLM gradients of the frozen network (the same reverse pass
-// at 197 tokens, with vit_attention197_bwd_kernel); weight gradients are not built for them.
+// at 197 tokens, with vit_attention197_bwd_kernel). orbit_vit_enable_weight_backward opens orbit_vit_backward_params for such a
+// plan as well: the patch filter gradient is the WX_PATCH16 form of vit_wgrad_kernel (16-float patch rows, M = 196 B, K = 768),
+// vit_token_bwd_kernel sums dpos over 197 token rows, and every Linear weight gradient runs at M = 197 B.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -966,10 +968,20 @@ int launch_layernorm_bwd(const float* x, size_t xs, const float* dy, size_t dys,
 // summed here, not merely left unstored as in the forward). Columns past K (K a multiple of 32, not of 128) likewise.
 //   WX_GELU   X = GELU_erf(u), applied to the loaded registers (fc2: only the pre-activation is on the tape)
 //   WX_PATCH  X = the patches gathered from the NCHW frames (patch_row_ptr), dY row m = token 1 + m % 49 of frame m / 49
+//   WX_PATCH16  the same for 16 x 16 patches (patch16_row_ptr, k = c*256 + kh*16 + kw, K = 768, M = 196 B), dY row m = token
+//             1 + m % 196 of frame m / 196 of the [B][197][D] stream. A float4 chunk of four consecutive k lies inside one
+//             16-float patch row, 16-byte aligned (kw = 0, 4, 8, 12; patch columns start at multiples of 64 bytes). A loader's
+//             32 chunks (128 k) cover eight frame rows of one channel with 64 contiguous bytes each, where patch-32 covers four
+//             rows of 128 bytes: a wave's load (rows m, m + 1 x 32 chunks) is 16 runs of 64 bytes instead of 8 of 128. The
+//             wave's two rows are an even m and m + 1, and 14 and 196 are even, so they are always the patches pw, pw + 1 (pw
+//             even) of one patch row: the two 64-byte runs of a frame row are the halves of one 128-byte line (frames at least
+//             128-byte aligned, as torch allocates them). The wave therefore still touches 8 whole lines per load and no frame
+//             byte is fetched twice; the difference to patch-32 is that a line is covered by lanes l..l+3 and l+32..l+35
+//             instead of eight consecutive lanes: four dwordx4 lanes per contiguous run instead of eight.
 // The bias gradient db [n] = sum_m dY [m][n] is folded into the blocks of k-tile 0, which sum the dY tile they hold in LDS (32
 // rows into a fresh sum per step, steps and 256-row chunks as the accumulators): dY is not read a second time.
 constexpr int W_BT = 128;
-enum { WX_PLAIN = 0, WX_GELU = 1, WX_PATCH = 2 };
+enum { WX_PLAIN = 0, WX_GELU = 1, WX_PATCH = 2, WX_PATCH16 = 3 };
 
 struct WgradArgs {
     const float* dy;
@@ -1024,10 +1036,14 @@ __global__ __launch_bounds__(G_THREADS, 2) void vit_wgrad_kernel(WgradArgs a) {
             const int m = st * G_BK + lr + 8 * i;
             ra[i] = rb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (m >= a.M) continue;
-            const size_t dyrow = XM == WX_PATCH ? (size_t)(m / VIT_P) * VIT_N + 1 + m % VIT_P : (size_t)m;
+            const size_t dyrow = XM == WX_PATCH     ? (size_t)(m / VIT_P) * VIT_N + 1 + m % VIT_P
+                                 : XM == WX_PATCH16 ? (size_t)(m / VIT16_P) * VIT16_N + 1 + m % VIT16_P
+                                                    : (size_t)m;
             ra[i] = *reinterpret_cast<const float4*>(a.dy + dyrow * a.N + n0 + 4 * lc);
             if (!k_in) continue;
-            const float* xp = XM == WX_PATCH ? patch_row_ptr(a.x, m, k0 + 4 * lc) : a.x + (size_t)m * a.K + k0 + 4 * lc;
+            const float* xp = XM == WX_PATCH     ? patch_row_ptr(a.x, m, k0 + 4 * lc)
+                              : XM == WX_PATCH16 ? patch16_row_ptr(a.x, m, k0 + 4 * lc)
+                                                 : a.x + (size_t)m * a.K + k0 + 4 * lc;
             rb[i] = *reinterpret_cast<const float4*>(xp);
             if (XM == WX_GELU) rb[i] = make_float4(gelu_erf(rb[i].x), gelu_erf(rb[i].y), gelu_erf(rb[i].z), gelu_erf(rb[i].w));
         }
@@ -1131,14 +1147,14 @@ int launch_wgrad(const float* dy, const float* x, float* dw, float* db, int M, i
     return ORBIT_OK;
 }
 
-// gradient stream dx0 [B][50][D] entering the token assembly -> dpos [50][D] = sum_b dx0[b] (frames in ascending order, a fresh
-// sum every 64 frames), dcls [D] = its row 0. (The patch bias gradient, the sum of rows 1..49, is the folded bias of the patch
-// weight-gradient GEMM, which holds exactly those rows in LDS.)
-__global__ __launch_bounds__(256) void vit_token_bwd_kernel(const float* __restrict__ dx0, int B, int D, float* __restrict__ dpos,
-                                                            float* __restrict__ dcls) {
+// gradient stream dx0 [B][N][D] (N = 50 or 197 tokens) entering the token assembly -> dpos [N][D] = sum_b dx0[b] (frames in
+// ascending order, a fresh sum every 64 frames), dcls [D] = its row 0. (The patch bias gradient, the sum of rows 1..N-1, is the
+// folded bias of the patch weight-gradient GEMM, which holds exactly those rows in LDS.)
+__global__ __launch_bounds__(256) void vit_token_bwd_kernel(const float* __restrict__ dx0, int B, int N, int D,
+                                                            float* __restrict__ dpos, float* __restrict__ dcls) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const size_t stride = (size_t)VIT_N * D;
-    if (i >= VIT_N * D) return;
+    const size_t stride = (size_t)N * D;
+    if (i >= N * D) return;
     float tot = 0.f;
     for (int b0 = 0; b0 < B; b0 += 64) {
         const int b1 = b0 + 64 < B ? b0 + 64 : B;
@@ -1151,12 +1167,17 @@ __global__ __launch_bounds__(256) void vit_token_bwd_kernel(const float* __restr
     if (i < D) dcls[i] = tot;
 }
 
-// frames, dx0 -> d patch weight [D][3072], d patch bias [D] (or nullptr: CLIP), d pos_embed [50][D], d cls_token [D]
+// frames, dx0 -> d patch weight [D][3072] / [D][768], d patch bias [D] (or nullptr: CLIP), d pos_embed [50][D] / [197][D],
+// d cls_token [D]; patch = 32 or 16 (validated by the callers)
 int launch_patch_embed_bwd(const float* frames, const float* dx0, float* dw, float* db, float* dpos, float* dcls, int B, int D,
-                           float* ws, hipStream_t s) {
-    if (int rc = launch_wgrad<WX_PATCH>(dx0, frames, dw, db, B * VIT_P, D, VIT_KPATCH, ws, "wgrad_patch_embed", s)) return rc;
-    const int pi = prof_start("vit_token_bwd", (double)B * VIT_N * D, 4.0 * (B + 1) * VIT_N * D, s);
-    vit_token_bwd_kernel<<<cdiv(VIT_N * D, 256), 256, 0, s>>>(dx0, B, D, dpos, dcls);
+                           int patch, float* ws, hipStream_t s) {
+    const bool p16 = patch == VIT16_PATCH;
+    const int N = p16 ? VIT16_N : VIT_N;
+    if (int rc = p16 ? launch_wgrad<WX_PATCH16>(dx0, frames, dw, db, B * VIT16_P, D, VIT16_KPATCH, ws, "wgrad_patch16_embed", s)
+                     : launch_wgrad<WX_PATCH>(dx0, frames, dw, db, B * VIT_P, D, VIT_KPATCH, ws, "wgrad_patch_embed", s))
+        return rc;
+    const int pi = prof_start("vit_token_bwd", (double)B * N * D, 4.0 * (B + 1) * N * D, s);
+    vit_token_bwd_kernel<<<cdiv(N * D, 256), 256, 0, s>>>(dx0, B, N, D, dpos, dcls);
     prof_stop(pi, s);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
@@ -1175,11 +1196,12 @@ struct orbit_vit {
     float eps = 1e-6f;
     bool clip = false;  // pre_norm: no patch-embedding bias, norm_pre after the position add
     // geometry: patch size (32 or 16), patches per side and per frame, tokens per frame, K of the patch GEMM, largest batch.
-    // The patch-16 plans are forward only (no tape, no backward) until orbit_vit_enable_backward; weight gradients never
+    // The patch-16 plans are forward only (no tape, no backward) until orbit_vit_enable_backward; weight gradients only after
+    // orbit_vit_enable_weight_backward
     int patch = VIT_PATCH, grid = VIT_GRID, P = VIT_P, N = VIT_N, kpatch = VIT_KPATCH, max_b = VIT_MAX_B;
-    bool backward_enabled = false;
+    bool backward_enabled = false, weight_backward_enabled = false;
     bool forward_only() const { return patch != VIT_PATCH && !backward_enabled; }
-    bool weight_grads() const { return patch == VIT_PATCH; }
+    bool weight_grads() const { return patch == VIT_PATCH || weight_backward_enabled; }
     ParamPool pool{64};  // the parameters by state_dict key (csrc/param_pool.h); 256-byte aligned tensors (float4 loads)
     // where the forward and the backward find each tensor: pool offsets, fixed by orbit_vit_create
     size_t cls = 0, pos = 0, patch_w = 0, patch_b = VIT_ABSENT, pre_w = VIT_ABSENT, pre_b = VIT_ABSENT, norm_w = 0, norm_b = 0;
@@ -1219,9 +1241,9 @@ struct VitWsParams {
     size_t x, h, h2, big, partial, wgrad, total;
 };
 VitWsParams vit_ws_params(const orbit_vit* v, int B) {
-    const int M = B * VIT_N, D = v->D;
+    const int M = B * v->N, D = v->D;
     const size_t md = align_up((size_t)M * D * sizeof(float), 256);
-    size_t wg = wgrad_ws_floats(B * VIT_P, D, VIT_KPATCH);
+    size_t wg = wgrad_ws_floats(B * v->P, D, v->kpatch);
     const int shapes[4][2] = {{D, 4 * D}, {4 * D, D}, {D, D}, {3 * D, D}};  // (N, K) of fc2, fc1, proj, qkv
     for (const auto& nk : shapes) wg = std::max(wg, wgrad_ws_floats(M, nk[0], nk[1]));
     VitWsParams L;
@@ -1539,16 +1561,17 @@ int vit_backward_impl(orbit_vit_t* v, const float* frames, int B, const float* f
     const float* dx0 = dx;
     if (v->clip) {
         // norm_pre ran in place: its input tokens are rebuilt from the frames (patch GEMM + class-token row) into h2
-        GemmArgs a{frames, v->p(v->patch_w), v->p(v->patch_b), nullptr, v->p(v->pos), h2, B * VIT_P, D, VIT_KPATCH};
-        if ((rc = launch_gemm<EPI_PATCH>(a, "patch_embed", s))) return rc;
-        if ((rc = launch_cls_token(v->p(v->cls), v->p(v->pos), h2, B, D, VIT_N, s))) return rc;
+        GemmArgs a{frames, v->p(v->patch_w), v->p(v->patch_b), nullptr, v->p(v->pos), h2, B * v->P, D, v->kpatch};
+        if ((rc = v->patch == VIT16_PATCH ? launch_gemm<EPI_PATCH16>(a, "patch_embed", s) : launch_gemm<EPI_PATCH>(a, "patch_embed", s)))
+            return rc;
+        if ((rc = launch_cls_token(v->p(v->cls), v->p(v->pos), h2, B, D, N, s))) return rc;
         if ((rc = launch_layernorm_bwd(h2, D, dx, D, v->p(v->pre_w), v->eps, nullptr, h, D, M, D, partial, pg + v->pre_w,
                                        pg + v->pre_b, s)))
             return rc;
         dx0 = h;
     }
     return launch_patch_embed_bwd(frames, dx0, pg + v->patch_w, v->patch_b == VIT_ABSENT ? nullptr : pg + v->patch_b, pg + v->pos,
-                                  pg + v->cls, B, D, b.wgrad, s);
+                                  pg + v->cls, B, D, v->patch, b.wgrad, s);
 }
 
 }  // namespace
@@ -1569,6 +1592,13 @@ int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* f
 int orbit_vit_enable_backward(orbit_vit_t* v) {
     ORBIT_REQUIRE(v, "vit_enable_backward: null pointer");
     v->backward_enabled = true;  // (read by forward_only() of the patch-16 plans only)
+    return ORBIT_OK;
+}
+// weight gradients of a patch-16 plan (orbit_vit_backward_params); a patch-32 plan has them already
+int orbit_vit_enable_weight_backward(orbit_vit_t* v) {
+    ORBIT_REQUIRE(v, "vit_enable_weight_backward: null pointer");
+    if (v->patch == VIT_PATCH) return ORBIT_OK;
+    v->backward_enabled = true, v->weight_backward_enabled = true;
     return ORBIT_OK;
 }
 size_t orbit_vit_tape_bytes(const orbit_vit_t* v, int B) {
@@ -1808,18 +1838,29 @@ int orbit_op_vit_linear_wgrad(const float* dy, const float* x, float* dw, float*
     return launch_wgrad<WX_PLAIN>(dy, x, dw, dbias_or_null, M, N, K, workspace, "op_wgrad", s);
 }
 
-int orbit_op_vit_patch_embed_bwd(const float* frames, const float* dtokens, float* dw, float* dbias_or_null, float* dpos,
-                                 float* dcls, int B, int D, float* workspace, size_t workspace_floats, orbit_stream_t stream) {
+// patch: 32 (dtokens [B][50][D], dw [D][3][32][32], B <= 8192) or 16 ([B][197][D], [D][3][16][16], B <= 2048)
+int orbit_op_vit_patch_embed_bwd_p(const float* frames, const float* dtokens, float* dw, float* dbias_or_null, float* dpos,
+                                   float* dcls, int B, int D, int patch, float* workspace, size_t workspace_floats,
+                                   orbit_stream_t stream) {
     ORBIT_REQUIRE(frames && dtokens && dw && dpos && dcls, "op_vit_patch_embed_bwd: null pointer");
-    ORBIT_REQUIRE(B > 0 && B <= VIT_MAX_B, "op_vit_patch_embed_bwd: batch of %d frames (1..%d)", B, VIT_MAX_B);
+    ORBIT_REQUIRE(patch == VIT_PATCH || patch == VIT16_PATCH, "op_vit_patch_embed_bwd: patch size %d (32 or 16)", patch);
+    const bool p16 = patch == VIT16_PATCH;
+    const int max_b = p16 ? VIT16_MAX_B : VIT_MAX_B;
+    ORBIT_REQUIRE(B > 0 && B <= max_b, "op_vit_patch_embed_bwd: batch of %d frames (1..%d)", B, max_b);
     ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_patch_embed_bwd: unsupported width %d (384 or 768)", D);
-    const size_t need = wgrad_ws_floats(B * VIT_P, D, VIT_KPATCH);
+    const size_t need = p16 ? wgrad_ws_floats(B * VIT16_P, D, VIT16_KPATCH) : wgrad_ws_floats(B * VIT_P, D, VIT_KPATCH);
     ORBIT_REQUIRE(workspace || need == 0, "op_vit_patch_embed_bwd: null pointer");
     ORBIT_REQUIRE(workspace_floats >= need, "op_vit_patch_embed_bwd: workspace too small (%zu < %zu floats)", workspace_floats, need);
     ORBIT_REQUIRE((((uintptr_t)frames | (uintptr_t)dtokens | (uintptr_t)dw | (uintptr_t)dbias_or_null | (uintptr_t)workspace) & 15) == 0,
                   "op_vit_patch_embed_bwd: frames, dtokens, dw, dbias and workspace must be 16-byte aligned");
     ORBIT_REQUIRE((((uintptr_t)dpos | (uintptr_t)dcls) & 3) == 0, "op_vit_patch_embed_bwd: dpos and dcls must be 4-byte aligned");
-    return launch_patch_embed_bwd(frames, dtokens, dw, dbias_or_null, dpos, dcls, B, D, workspace, (hipStream_t)stream);
+    return launch_patch_embed_bwd(frames, dtokens, dw, dbias_or_null, dpos, dcls, B, D, patch, workspace, (hipStream_t)stream);
+}
+
+int orbit_op_vit_patch_embed_bwd(const float* frames, const float* dtokens, float* dw, float* dbias_or_null, float* dpos,
+                                 float* dcls, int B, int D, float* workspace, size_t workspace_floats, orbit_stream_t stream) {
+    return orbit_op_vit_patch_embed_bwd_p(frames, dtokens, dw, dbias_or_null, dpos, dcls, B, D, VIT_PATCH, workspace,
+                                          workspace_floats, stream);
 }
 
 }  // extern "C"

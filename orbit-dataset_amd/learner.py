@@ -87,8 +87,12 @@ def build_parser():
     p.add_argument("--vit16_native_backward", action="store_true",
                    help="vit_*_16* extractors (the patch-16 transformers) only, ignored elsewhere: opt in to the native FiLM "
                         "gradients through the FROZEN transformer at 197 tokens (--adapt_features training, with or without "
-                        "--with_lite; the multi-step finetuner's --adapt_features). --learn_extractor stays refused: weight "
-                        "gradients are not built for these models")
+                        "--with_lite; the multi-step finetuner's --adapt_features). --learn_extractor stays refused under this "
+                        "flag alone: --vit16_native_weight_backward opens it")
+    p.add_argument("--vit16_native_weight_backward", action="store_true",
+                   help="vit_*_16* extractors only, ignored elsewhere: opt in to the native gradients of every parameter of the "
+                        "transformer at 197 tokens (implies what --vit16_native_backward admits, and admits --learn_extractor, "
+                        "with or without --with_lite / --adapt_features)")
     p.add_argument("--effnetv2_native_backward", action="store_true",
                    help="efficientnet_v2_s: opt in to the native FiLM gradients through the FROZEN network (--adapt_features "
                         "training, with or without --with_lite; the multi-step finetuner's --adapt_features). --learn_extractor "
@@ -250,18 +254,19 @@ def split_annotation_args(args, split):
 # (utils/args.py:185-190; the other extractors keep --frame_norm_method), the one frame size they run on (None: any), the flag
 # that opens the FiLM gradients through the frozen network and the one that opens the weight gradients (None: not built), the
 # words their refusals differ in, and - the patch-16 transformers, whose refusals under the two patch-32 flags are pinned - a
-# FiLM-gradient flag of their own.
+# FiLM-gradient flag and a weight-gradient flag of their own.
 FrozenExtractor = collections.namedtuple("FrozenExtractor",
-                                         "frame_norm frame_size film_flag weight_flag no_weights no_backward film16_flag",
-                                         defaults=(None,))
+                                         "frame_norm frame_size film_flag weight_flag no_weights no_backward film16_flag "
+                                         "weight16_flag", defaults=(None, None))
 _VIT = ("vit_native_backward", "vit_native_weight_backward", "weight gradients through a ViT", "a ViT")
-_VIT16 = (None, None) + _VIT[2:] + ("vit16_native_backward",)
+_VIT16 = (None, None) + _VIT[2:] + ("vit16_native_backward", "vit16_native_weight_backward")
 FROZEN_EXTRACTORS = {
     "vit_s_32": FrozenExtractor("imagenet_inception", 224, *_VIT),
     "vit_b_32": FrozenExtractor("imagenet_inception", 224, *_VIT),
     "vit_b_32_clip": FrozenExtractor("openai_clip", 224, *_VIT),
     # the patch-16 models: inference + FiLM only under the patch-32 flags; --vit16_native_backward opens the FiLM gradients
-    # through the frozen network (csrc/vit.hip vit_attention197_bwd_kernel), nothing opens the weight gradients
+    # through the frozen network (csrc/vit.hip vit_attention197_bwd_kernel), --vit16_native_weight_backward the weight
+    # gradients (vit_wgrad_kernel<WX_PATCH16> and the Linear weight gradients at 197 tokens)
     "vit_s_16": FrozenExtractor("imagenet_inception", 224, *_VIT16),
     "vit_b_16": FrozenExtractor("imagenet_inception", 224, *_VIT16),
     "vit_b_16_clip": FrozenExtractor("openai_clip", 224, *_VIT16),
@@ -347,7 +352,7 @@ def opted_in(args, spec):
     """The one map from a frozen-scope extractor's opt-in flags to the gradient scope they open and the extractor attributes
     they set -> (scope "all" | "film" | "none", the flag that opened it, the attributes of every flag given)."""
     table = ((spec.weight_flag, "all", "native_weight_backward"), (spec.film_flag, "film", "native_backward"),
-             (spec.film16_flag, "film", "native_backward_patch16"))
+             (spec.weight16_flag, "all", "native_weight_backward_patch16"), (spec.film16_flag, "film", "native_backward_patch16"))
     on = [(flag, scope, attr) for flag, scope, attr in table if flag and getattr(args, flag, False)]
     if not on:
         return "none", None, []

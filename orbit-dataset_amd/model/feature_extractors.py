@@ -679,8 +679,10 @@ class VisionTransformer(HipNetwork):
     position table. They are inference + FiLM only by default: the two opt-ins above are ignored and anything that needs a
     gradient is refused. Their own opt-in, `native_backward_patch16 = True` (ignored by the patch-32 models), gives the FiLM
     vectors / FiLM-slot LayerNorm parameters of the FROZEN network their gradients through the same VitFunction at 197 tokens
-    (orbit_vit_enable_backward on the plan); weight gradients are not built for them, so any other parameter requiring a
-    gradient is refused by name. The attribute may be set after a plan exists and after inference forwards."""
+    (orbit_vit_enable_backward on the plan); any other parameter requiring a gradient is refused by name - unless
+    `native_weight_backward_patch16 = True` (also ignored by the patch-32 models, and implying the above): then every parameter
+    that requires a gradient gets it from orbit_vit_backward_params at 197 tokens (orbit_vit_enable_weight_backward on the
+    plan; --learn_extractor). Either attribute may be set after a plan exists and after inference forwards."""
 
     _api = "vit"
     _probe_size = _frame_size = VIT_FRAME_SIZE
@@ -689,6 +691,8 @@ class VisionTransformer(HipNetwork):
     native_backward = False  # opt-in (learner flag --vit_native_backward)
     native_weight_backward = False  # second opt-in (learner flag --vit_native_weight_backward): weight gradients too
     native_backward_patch16 = False  # the patch-16 models' opt-in (learner flag --vit16_native_backward): FiLM gradients
+    # the patch-16 models' second opt-in (learner flag --vit16_native_weight_backward): weight gradients too
+    native_weight_backward_patch16 = False
 
     def _leaf_shape(self, key, numel):
         # (cls_token is the first key: its size is the embedding width D)
@@ -717,13 +721,16 @@ class VisionTransformer(HipNetwork):
 
     @property
     def _grad_scope(self):
-        if self.patch_size == 16:  # its own opt-in, FiLM gradients only: the patch-32 opt-ins say nothing here
-            return "film" if self.native_backward_patch16 else "none"
+        if self.patch_size == 16:  # its own two opt-ins: the patch-32 opt-ins say nothing here
+            return "all" if self.native_weight_backward_patch16 else "film" if self.native_backward_patch16 else "none"
         return "all" if self.native_weight_backward else "film" if self.native_backward else "none"
 
     def _forward_train(self, plan, x, film, use_tape, bn_train, out):
         # (a patch-16 plan is forward only until told otherwise; wants_grad admitted this forward, so the opt-in is set)
-        _lib.check(_lib.load().orbit_vit_enable_backward(plan.handle), "orbit_vit_enable_backward")
+        if self.patch_size == 16 and self._grad_scope == "all":
+            _lib.check(_lib.load().orbit_vit_enable_weight_backward(plan.handle), "orbit_vit_enable_weight_backward")
+        else:
+            _lib.check(_lib.load().orbit_vit_enable_backward(plan.handle), "orbit_vit_enable_backward")
         if film is None:  # the network's own LayerNorm parameters: autograd splits dgamma / dbeta into their 50 grads
             slots = self.film_slot_modules()
             film = (torch.cat([m._parameters["weight"].reshape(-1) for _, m in slots]),

@@ -9,10 +9,15 @@ torch.nn.functional.linear (fp32, the vendor BLAS) on the same four shapes at M 
     python tools/vit_bench.py [--steps 10] [--warmup 3] [--models vit_s_32,vit_b_32,vit_b_32_clip]
     python tools/vit_bench.py --models vit_s_16,vit_b_16,vit_b_16_clip
 
---train reports the training side instead: ms of taped forward + orbit_vit_backward_params (every parameter's gradient, through
-the module with native_weight_backward) at the step shapes B = 16 and B = 200, the weight-gradient GEMM family's TF/s per layer
-shape at M = 10 000 token rows (orbit_op_vit_linear_wgrad, split-reduction launch + reduce), and fp32 `dy.t() @ x` through torch
-(the vendor BLAS) on the same shapes. Nothing here is gated.
+--train reports the training side instead, for any of the six models: ms of taped forward + orbit_vit_backward_params (every
+parameter's gradient, through the module with its weight-gradient opt-in: native_weight_backward, or
+native_weight_backward_patch16 for the patch-16 models) at the step shapes B = 16 and B = 200 - median, minimum and maximum over
+--steps repetitions after --warmup - the profiler's weight-gradient rows of one such step per layer (launches, ms and TF/s of
+the split-reduction launches at the step's own row count, the patch-embedding filter gradient among them), the weight-gradient
+GEMM family's TF/s per layer shape at M = 10 000 token rows (orbit_op_vit_linear_wgrad, split-reduction launch + reduce), and
+fp32 `dy.t() @ x` through torch (the vendor BLAS) on the same shapes. Nothing here is gated.
+
+    python tools/vit_bench.py --train --models vit_s_16,vit_b_16,vit_b_16_clip
 
 --train_film reports the FiLM-gradient step of the frozen network, for any of the six models: ms of taped forward +
 orbit_vit_backward (through the module with its FiLM opt-in: native_backward, or native_backward_patch16 for the patch-16
@@ -40,7 +45,7 @@ from orbit_dataset_amd.model.few_shot_recognisers import SingleStepFewShotRecogn
 PEAK_TF = 155.0  # fp32 MFMA, measured (v_mfma_f32_32x32x2_f32)
 
 
-def _time(fn, steps, warmup):
+def _samples(fn, steps, warmup):
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
@@ -52,7 +57,11 @@ def _time(fn, steps, warmup):
         b.record()
         b.synchronize()
         ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
+    return ms
+
+
+def _time(fn, steps, warmup):
+    return statistics.median(_samples(fn, steps, warmup))
 
 
 def _model(name, adapt, classifier):
@@ -116,12 +125,40 @@ def _torch_linear(D, steps, warmup, M=10000):
     return out
 
 
-def _train_step_ms(name, B, steps, warmup):
+def _spread(fn, steps, warmup):
+    """as _time, with the spread: {median, min, max} ms over `steps` repetitions"""
+    ms = _samples(fn, steps, warmup)
+    return {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
+
+
+def _wgrad_rows(run):
+    """the profiler's weight-gradient rows of one call of `run`, per layer: launches, ms and TF/s (the split launches' own
+    flops; the reduce launches are listed apart)"""
+    lib = _lib.load()
+    torch.cuda.synchronize()
+    lib.orbit_prof_enable(1)
+    run()
+    torch.cuda.synchronize()
+    lib.orbit_prof_collect(None, None, None)
+    out = {}
+    for i in range(lib.orbit_prof_num_variants()):
+        name = ctypes.create_string_buffer(48)
+        launches, ms, flops = ctypes.c_long(), ctypes.c_double(), ctypes.c_double()
+        lib.orbit_prof_variant(i, name, ctypes.byref(launches), ctypes.byref(ms), ctypes.byref(flops), None)
+        v = name.value.decode()
+        if launches.value and v.startswith("vit_wgrad_"):
+            out[v[len("vit_wgrad_"):]] = {"launches": launches.value, "ms": round(ms.value, 4),
+                                          "tflops": round(flops.value / ms.value / 1e9, 2) if ms.value else 0.0}
+    lib.orbit_prof_enable(0)
+    return out
+
+
+def _train_step(name, B, steps, warmup):
     from orbit_dataset_amd.model.feature_extractors import create_feature_extractor
     fe, _ = create_feature_extractor(name, with_film=False, learn_extractor=True)
     synthetic.init_parameters_(fe)
     fe.to("cuda:0")
-    fe.native_weight_backward = True
+    fe.native_weight_backward = fe.native_weight_backward_patch16 = True  # (each is ignored by the other patch size)
     x = torch.randn(B, 3, 224, 224, device="cuda:0")
     r = torch.randn(B, fe.output_size, device="cuda:0")
 
@@ -129,7 +166,7 @@ def _train_step_ms(name, B, steps, warmup):
         for p in fe.parameters():
             p.grad = None
         (fe(x) * r).sum().backward()
-    return _time(step, steps, warmup)
+    return _spread(step, steps, warmup), _wgrad_rows(step)
 
 
 def _wgrad_shapes(D, steps, warmup, M=10000):
@@ -159,7 +196,13 @@ def main_train(a):
     result = {"metric": "vit_train_ms", "what": "taped forward + orbit_vit_backward_params, every parameter trainable",
               "peak_tflops": PEAK_TF, "models": {}}
     for name in a.models.split(","):
-        r = {"fwd_bwd_ms": {"B%d" % B: round(_train_step_ms(name, B, a.steps, a.warmup), 3) for B in (16, 200)}}
+        r = {"fwd_bwd_ms": {}, "fwd_bwd_ms_spread": {}, "wgrad_rows_of_a_step": {}}
+        for B in (16, 200):
+            ms, rows = _train_step(name, B, a.steps, a.warmup)
+            r["fwd_bwd_ms"]["B%d" % B] = ms["median"]
+            r["fwd_bwd_ms_spread"]["B%d" % B] = ms
+            r["wgrad_rows_of_a_step"]["B%d" % B] = rows
+            torch.cuda.empty_cache()
         r["wgrad_m10000"] = _wgrad_shapes(384 if name.startswith("vit_s_") else 768, a.steps, a.warmup)
         result["models"][name] = r
         torch.cuda.empty_cache()
@@ -229,7 +272,7 @@ def main(argv=None):
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--models", default="vit_s_32,vit_b_32,vit_b_32_clip",
-                   help="comma-separated, any of the six transformer extractors (--train: the patch-32 ones only)")
+                   help="comma-separated, any of the six transformer extractors")
     p.add_argument("--train", action="store_true", help="the training step and the weight-gradient GEMMs instead")
     p.add_argument("--train_film", action="store_true",
                    help="the FiLM-gradient step of the frozen network at a batch of %d frames instead (all six models)" % FILM_BATCH)
