@@ -740,6 +740,28 @@ int orbit_op_bn_backward_ex(const float* dout, const float* out, const float* y,
  * flags = ORBIT_BN_RESIDUAL_POST_ACT out = act(scale * y + shift) + residual. y, out, residual (nullable) [M][C]; scale, shift [C]. */
 int orbit_op_scale_shift_act(const float* y, const float* scale, const float* shift, const float* residual, int act, int M, int C,
                              int flags, float* out, orbit_stream_t stream);
+/* The train-mode BatchNorm chain link by link (single-operator entries of the parity tests, csrc/train_ops.hip).
+ * orbit_op_bn_reduce_plan (host only): the layout of the per-channel reductions over an [M][C] tensor - *G channel-quad lanes
+ *   and *R = 256 / G row lanes of a block, *ygroups column groups of G quads, *nblk row blocks of *rows_per_block rows.
+ * orbit_op_se_pool_chunks (host only): *chunks per frame of the pooled apply pass below, *rows_per_chunk pixels each.
+ * orbit_op_bn_stats_from_partials: the finalize behind a producer's partial[nblk][2][C] (sums of y and of y^2 over row blocks that
+ *   tile the M rows): mean, invstd [C], and when given (NULL to skip) the folded scale / shift and the running statistics
+ *   (conv_bias [C], nullable: the bias the producing convolution left out of y). Lists of more than 2048 blocks pass the
+ *   compaction stage. The caller's partials are not modified.
+ * orbit_op_bn_backward_reduced: the BatchNorm backward behind a producer's partial[nblk][2][C] of g and g * xhat (g = the
+ *   gradient behind the activation, xhat = (y - mean) * invstd): dgamma, dbeta (NULL to skip), dy [M][C] (NULL to skip).
+ * orbit_op_scale_shift_act_pool: out = act(scale * y + shift) on [B][HW][C] with pool[b][chunk][c] = the sum of out over the
+ *   chunk's pixels, [B][chunks][C] - what orbit_op_se_gate2 reads. */
+int orbit_op_bn_reduce_plan(int M, int C, int* G, int* R, int* ygroups, int* nblk, int* rows_per_block);
+int orbit_op_se_pool_chunks(int B, int HW, int C, int* chunks, int* rows_per_chunk);
+int orbit_op_bn_stats_from_partials(const float* partial, int nblk, int M, int C, const float* gamma, const float* beta,
+                                    const float* conv_bias, float eps, float momentum, float* running_mean, float* running_var,
+                                    float* mean, float* invstd, float* scale, float* shift, orbit_stream_t stream);
+int orbit_op_bn_backward_reduced(const float* g, const float* y, const float* mean, const float* invstd, const float* gamma, int train,
+                                 int M, int C, const float* partial, int nblk, float* dy, float* dgamma, float* dbeta,
+                                 orbit_stream_t stream);
+int orbit_op_scale_shift_act_pool(const float* y, const float* scale, const float* shift, int act, int B, int HW, int C, float* out,
+                                  float* pool, orbit_stream_t stream);
 /* dx of a convolution: dy NHWC [B][Ho][Wo][Cout], w OIHW, dx NHWC [B][H][W][Cin] (= accumulate + grad if given) */
 int orbit_op_conv2d_dgrad(const float* dy, const float* w, const float* accumulate, float* dx, int B, int H, int W,
                           int Cin, int Cout, int KH, int KW, int stride, int pad_top, int pad_left, int Ho, int Wo,

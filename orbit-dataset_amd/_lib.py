@@ -146,6 +146,11 @@ _SIGNATURES = {
     "orbit_op_bn_backward": (c_int, [P, P, P, c_int, c_int, P, P, P, c_int, c_int, P, P, P, P, P]),
     "orbit_op_bn_backward_ex": (c_int, [P, P, P, c_int, c_int, P, P, P, P, P, c_int, c_int, c_int, P, P, c_int, P, P, P]),
     "orbit_op_scale_shift_act": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "orbit_op_bn_reduce_plan": (c_int, [c_int, c_int] + [POINTER(c_int)] * 5),
+    "orbit_op_se_pool_chunks": (c_int, [c_int] * 3 + [POINTER(c_int)] * 2),
+    "orbit_op_bn_stats_from_partials": (c_int, [P, c_int, c_int, c_int, P, P, P, c_float, c_float, P, P, P, P, P, P, P]),
+    "orbit_op_bn_backward_reduced": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, c_int, P, P, P, P]),
+    "orbit_op_scale_shift_act_pool": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P]),
     "orbit_op_conv2d_dgrad": (c_int, [P, P, P, P] + [c_int] * 12 + [P]),
     "orbit_op_conv2d_wgrad": (c_int, [P, c_int, P, P] + [c_int] * 12 + [P]),
     "orbit_op_conv2d_wgrad_gated": (c_int, [P, P, P, P] + [c_int] * 5 + [P]),

@@ -1039,6 +1039,76 @@ int orbit_op_scale_shift_act(const float* y, const float* scale, const float* sh
                                   (flags & ORBIT_BN_RESIDUAL_POST_ACT) ? 1 : 0);
 }
 
+/* The layout rules of the per-channel reductions (host only), for the parity tests: col_layout, bn_reduce_blocks and
+ * bn_rows_per_block of an [M][C] tensor. */
+int orbit_op_bn_reduce_plan(int M, int C, int* G, int* R, int* ygroups, int* nblk, int* rows_per_block) {
+    ORBIT_REQUIRE(G && R && ygroups && nblk && rows_per_block, "op_bn_reduce_plan: null pointer");
+    ORBIT_REQUIRE(M > 0 && C > 0 && C % 4 == 0, "op_bn_reduce_plan: bad sizes M = %d, C = %d", M, C);
+    const ColLayout L = col_layout(C);
+    *G = L.G, *R = L.R, *ygroups = L.ygroups, *nblk = bn_reduce_blocks(M, C), *rows_per_block = bn_rows_per_block(M, C);
+    return ORBIT_OK;
+}
+
+/* ... and of the pooled apply pass (host only): se_pool_chunks and the rows of a chunk. */
+int orbit_op_se_pool_chunks(int B, int HW, int C, int* chunks, int* rows_per_chunk) {
+    ORBIT_REQUIRE(chunks && rows_per_chunk, "op_se_pool_chunks: null pointer");
+    ORBIT_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 4 == 0, "op_se_pool_chunks: bad sizes B = %d, HW = %d, C = %d", B, HW, C);
+    *chunks = se_pool_chunks(B, HW, C), *rows_per_chunk = cdiv(HW, *chunks);
+    return ORBIT_OK;
+}
+
+/* The train-mode finalize from a producer's partial sums, single-operator entry for the parity tests: the caller's
+ * partial[nblk][2][C] (sums of y and y^2 over M rows in all) is copied into scratch with room for the compaction stage, then
+ * launch_bn_stats_from_partials runs as behind a conv epilogue. gamma / beta / conv_bias / scale+shift / running statistics nullable. */
+int orbit_op_bn_stats_from_partials(const float* partial, int nblk, int M, int C, const float* gamma, const float* beta,
+                                    const float* conv_bias, float eps, float momentum, float* running_mean, float* running_var,
+                                    float* mean, float* invstd, float* scale, float* shift, orbit_stream_t stream) {
+    ORBIT_REQUIRE(partial && mean && invstd, "op_bn_stats_from_partials: null pointer");
+    ORBIT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "op_bn_stats_from_partials: running stats come in pairs");
+    ORBIT_REQUIRE((scale == nullptr) == (shift == nullptr), "op_bn_stats_from_partials: scale and shift come in pairs");
+    ORBIT_REQUIRE(nblk > 0 && M > 0 && C > 0 && C % 4 == 0, "op_bn_stats_from_partials: bad sizes nblk = %d, M = %d, C = %d", nblk, M, C);
+    hipStream_t s = (hipStream_t)stream;
+    float* tmp = nullptr;
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), bn_partial_floats((size_t)nblk, C) * sizeof(float), s));
+    const hipError_t e = hipMemcpyAsync(tmp, partial, (size_t)nblk * 2 * C * sizeof(float), hipMemcpyDeviceToDevice, s);
+    int rc = e == hipSuccess ? ORBIT_OK : set_err(ORBIT_ERR_HIP, "%s: copying the partials failed: %s", "op_bn_stats_from_partials", hipGetErrorString(e));
+    const BnAffine a{gamma, beta, conv_bias, running_mean, running_var, eps, momentum};
+    if (rc == ORBIT_OK) rc = launch_bn_stats_from_partials(tmp, nblk, M, C, a, BnFold{mean, invstd, scale, shift}, s);
+    (void)hipFreeAsync(tmp, s);
+    return rc;
+}
+
+/* The BatchNorm backward behind a producer that already summed g and g * xhat (the depthwise and squeeze-excite backward kernels),
+ * single-operator entry for the parity tests: partial[nblk][2][C] as above through launch_bn_backward_reduced. g is the gradient
+ * at the BatchNorm's output (activation derivative applied); dy nullable. */
+int orbit_op_bn_backward_reduced(const float* g, const float* y, const float* mean, const float* invstd, const float* gamma, int train,
+                                 int M, int C, const float* partial, int nblk, float* dy, float* dgamma, float* dbeta,
+                                 orbit_stream_t stream) {
+    ORBIT_REQUIRE(g && y && mean && invstd && partial, "op_bn_backward_reduced: null pointer");
+    ORBIT_REQUIRE(nblk > 0 && M > 0 && C > 0 && C % 4 == 0, "op_bn_backward_reduced: bad sizes nblk = %d, M = %d, C = %d", nblk, M, C);
+    hipStream_t s = (hipStream_t)stream;
+    float* tmp = nullptr;
+    const size_t npart = bn_partial_floats((size_t)nblk, C);
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&tmp), (npart + 3 * (size_t)C) * sizeof(float), s));
+    const hipError_t e = hipMemcpyAsync(tmp, partial, (size_t)nblk * 2 * C * sizeof(float), hipMemcpyDeviceToDevice, s);
+    int rc = e == hipSuccess ? ORBIT_OK : set_err(ORBIT_ERR_HIP, "%s: copying the partials failed: %s", "op_bn_backward_reduced", hipGetErrorString(e));
+    if (rc == ORBIT_OK)
+        rc = launch_bn_backward_reduced(g, y, BnFoldC{mean, invstd}, BnGrads{gamma, dgamma, dbeta}, train, M, C, dy, tmp, nblk,
+                                        tmp + npart, s);
+    (void)hipFreeAsync(tmp, s);
+    return rc;
+}
+
+/* out = act(scale * y + shift) for [B][HW][C] with the squeeze-excite pooling partials pool[B][chunks][C] of out from the same
+ * pass (chunks as orbit_op_se_pool_chunks reports), single-operator entry for the parity tests. */
+int orbit_op_scale_shift_act_pool(const float* y, const float* scale, const float* shift, int act, int B, int HW, int C, float* out,
+                                  float* pool, orbit_stream_t stream) {
+    ORBIT_REQUIRE(y && scale && shift && out && pool, "op_scale_shift_act_pool: null pointer");
+    ORBIT_REQUIRE(act == ORBIT_ACT_NONE || act == ORBIT_ACT_RELU || act == ORBIT_ACT_SILU, "op_scale_shift_act_pool: bad activation %d", act);
+    ORBIT_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 4 == 0, "op_scale_shift_act_pool: bad sizes B = %d, HW = %d, C = %d", B, HW, C);
+    return launch_scale_shift_act_pool(y, scale, shift, act, B, HW, C, out, pool, (hipStream_t)stream);
+}
+
 int orbit_op_maxpool2d_train(const float* x, float* y, uint8_t* idx, int B, int H, int W, int C, int K, int stride,
                              int pad, int Ho, int Wo, orbit_stream_t stream) {
     ORBIT_REQUIRE(x && y && idx, "op_maxpool2d_train: null pointer");
