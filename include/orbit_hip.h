@@ -973,7 +973,8 @@ size_t orbit_jpeg_workspace_bytes(int B, int H, int W);
  * the ones its geometry calls for: RST0, RST1, .. between the ceil(MCUs / restart_interval) intervals, then EOI, 2 to 1024
  * intervals. Every other frame - no markers, one interval, more than 1024, a marker missing, doubled or out of order - is
  * walked by one lane from the first byte to the last, and so is a frame any of whose intervals ends with a status: pixels and
- * status do not depend on which way a frame went. No read leaves the arena, no write leaves the frame's own slice of the
+ * status do not depend on which way a frame went. A frame without restart markers takes the subsequence-parallel form by its
+ * production rule (orbit_op_jpeg_entropy_sub below, a second launch behind the first), with the same guarantee. No read leaves the arena, no write leaves the frame's own slice of the
  * workspace and of the output, whatever the file holds. */
 int orbit_frames_from_jpeg(const uint8_t* arena, size_t arena_bytes, const orbit_jpeg_desc_t* descs, int B, int H, int W,
                            uint8_t* out_u8_hwc, int32_t* status, void* workspace, size_t workspace_bytes, orbit_stream_t stream);
@@ -985,6 +986,22 @@ int orbit_frames_from_jpeg(const uint8_t* arena, size_t arena_bytes, const orbit
  * with a status, and the frame was walked serially again. */
 int orbit_op_jpeg_entropy(const uint8_t* arena, size_t arena_bytes, const orbit_jpeg_desc_t* descs, int B, int H, int W, int form,
                           int16_t* coef_out, size_t coef_bytes, int32_t* status, int32_t* taken, orbit_stream_t stream);
+/* The entropy stage as orbit_frames_from_jpeg launches it, for parity tests: the kernel above with form 1, which leaves the
+ * frames of the subsequence-parallel form alone, and behind it the kernel of that form. A frame WITHOUT restart markers whose
+ * entropy-coded segment makes N = ceil(ecs_bytes / S) subsequences of S bytes, 2 <= N <= 1024, is decoded by one block of 256
+ * threads, one thread per subsequence at a time: every subsequence is walked from a guessed state (its first byte, first
+ * block of the MCU, DC next), the exit of each replaces the entry of the next in rounds until nothing changes - at most N
+ * rounds, in practice few, since Huffman streams self-synchronise - and a last pass writes the coefficients from the final
+ * entries, block ordinals and DC predictors coming from an exclusive scan (csrc/jpeg_core.h). When a check fails - block
+ * total, block index at an entry, EOI behind the last block, any status - the frame is walked serially again: status and
+ * coefficients never depend on the form. sub_bytes: 0 = the production rule (S = 128, doubled until N <= 256, the
+ * threads of the block; segments under 512 bytes and frames of fewer than 64 MCUs are walked serially), >= 4 = that S; 1 .. 3 and negative values are refused.
+ * Arguments as above, all checked before anything is launched. taken [B] int32: 0 .. 2 as above, 3 = one walker per
+ * subsequence, 4 = that was tried, a check failed, and the frame was walked serially again. rounds [B] int32: the rounds the
+ * frame took (1 .. N; they depend on the file and on S alone), 0 when the form was not taken. */
+int orbit_op_jpeg_entropy_sub(const uint8_t* arena, size_t arena_bytes, const orbit_jpeg_desc_t* descs, int B, int H, int W, int sub_bytes,
+                              int16_t* coef_out, size_t coef_bytes, int32_t* status, int32_t* taken, int32_t* rounds,
+                              orbit_stream_t stream);
 
 /* ---- JPEG encode on the device (csrc/jpeg_enc.hip, csrc/jpeg_enc_core.h) --------------------------------------------------
  * 8-bit RGB frames [B][H][W][3] -> the files Pillow's Image.save(quality = q[, restart_marker_rows = r]) writes for them, byte

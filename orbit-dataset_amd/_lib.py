@@ -174,6 +174,7 @@ _SIGNATURES = {
     "orbit_jpeg_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "orbit_frames_from_jpeg": (c_int, [P, c_size_t, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "orbit_op_jpeg_entropy": (c_int, [P, c_size_t, P, c_int, c_int, c_int, c_int, P, c_size_t, P, P, P]),
+    "orbit_op_jpeg_entropy_sub": (c_int, [P, c_size_t, P, c_int, c_int, c_int, c_int, P, c_size_t, P, P, P, P]),
     "orbit_jpeg_encode_params": (c_int, [c_int, c_int, P, c_size_t]),
     "orbit_jpeg_encode_header": (c_int, [P, c_int, c_int, P, c_size_t, P, c_size_t]),
     "orbit_jpeg_encode_bound": (c_size_t, [c_int, c_int, c_int, c_size_t]),
@@ -226,6 +227,7 @@ class JpegDesc(ctypes.Structure):
 
 JPEG_STAGE_BYTES = 1024  # ORBIT_JPEG_STAGE_BYTES
 JPEG_PAR_MAX_INTERVALS = 1024  # of csrc/jpeg_core.h: more restart intervals than this and a frame is walked serially
+JPEG_SUB_MAX = 1024  # of csrc/jpeg_core.h: more subsequences than this and a frame without restart markers is walked serially
 
 
 class JpegEnc(ctypes.Structure):

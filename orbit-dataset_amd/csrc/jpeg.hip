@@ -11,6 +11,11 @@
 //                        segment for markers into an LDS table, lane j decodes intervals j, j + 64, .. from a register window
 //                        on the arena; any status sends the frame through the serial walk again, so a damaged file's status
 //                        and coefficients do not depend on the form.
+//   jpeg_entropy_sub_kernel  launched behind it for the frames WITHOUT restart markers that jpeg_sub_size admits (the first
+//                        kernel leaves those alone): one block of 256 threads per frame, one thread per subsequence of the
+//                        segment; walkers from guessed states hand their exits on in rounds until nothing changes, a scan gives
+//                        block ordinals and DC predictors, a last pass writes the coefficients; a failed check sends the
+//                        frame through the same serial walk.
 //   jpeg_idct_kernel     one thread per 8 x 8 block: dequantise, both passes of the inverse DCT in registers, range limit.
 //   jpeg_color_kernel    one thread per output pixel: chroma upsampling with libjpeg's edge rules, colour conversion, store.
 // A frame whose stream is damaged ends with a non-zero status and whatever was decoded so far stays inside its own workspace
@@ -95,12 +100,49 @@ __device__ __forceinline__ bool jpeg_scan_markers(uint8_t* stage, const uint8_t*
     return __ballot(bad) == 0 && count >= nseg;
 }
 
-// form: 0 walks every frame serially, 1 takes the interval form where the rule of csrc/jpeg_core.h holds. taken (nullable):
-// 0 serial, 1 interval-parallel, 2 parallel attempted, then walked serially.
+// The serial walk of one frame, by a block of T threads: the first 64 keep two tiles of the stream in LDS, thread 0 walks the
+// symbols and hands control back at every tile end for the next load. coef: zeroed (a barrier in here comes before the first
+// write). Returns the walk's status in thread 0.
+template <int T>
+__device__ __forceinline__ int jpeg_walk_tiled(uint8_t* stage, uint32_t* ctl, const uint8_t* mem, uint32_t len, const orbit_jpeg_desc_t& d,
+                                               const JpegGeom& g, const uint8_t* natural, int16_t* coef, int tid) {
+    const bool loader = T == 64 || tid < 64;
+    uint32_t tile0 = 0;
+    if (loader) {
+        jpeg_load_tile(stage, mem, len, 0, tid);
+        jpeg_load_tile(stage, mem, len, 1, tid);
+    }
+    JpegWalk w;
+    jpeg_walk_init(w, d);
+    __syncthreads();
+    for (;;) {
+        if (tid == 0) {
+            const JpegLdsSrc src{stage, mem, tile0};
+            jpeg_walk(w, src, d, g, natural, coef, (tile0 + 1) * JP_STAGE - 1);
+            ctl[0] = (uint32_t)w.done;
+            ctl[1] = w.bits.pos;
+        }
+        __syncthreads();
+        const uint32_t done = ctl[0], next = ctl[1] / JP_STAGE;  // next > tile0 unless done
+        if (done) break;
+        if (loader) {
+            if (next != tile0 + 1) jpeg_load_tile(stage, mem, len, next, tid);
+            jpeg_load_tile(stage, mem, len, next + 1, tid);
+        }
+        tile0 = next;
+        __syncthreads();
+    }
+    return w.status;
+}
+
+// form: 0 walks every frame serially, 1 takes the interval form where the rule of csrc/jpeg_core.h holds. sub: < 0, or the
+// sub_bytes of the jpeg_entropy_sub_kernel launched behind this one, whose frames (jpeg_sub_size) are left alone here. taken
+// (nullable): 0 serial, 1 interval-parallel, 2 parallel attempted, then walked serially.
 __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ arena, size_t arena_bytes,
                                                           const orbit_jpeg_desc_t* __restrict__ descs, int H, int W,
                                                           size_t cap_blocks, int16_t* __restrict__ coef_ws,
-                                                          int32_t* __restrict__ status, int form, int32_t* __restrict__ taken) {
+                                                          int32_t* __restrict__ status, int form, int sub,
+                                                          int32_t* __restrict__ taken) {
     __shared__ __align__(16) orbit_jpeg_desc_t d;
     __shared__ __align__(16) uint8_t stage[2 * JP_STAGE];
     __shared__ uint8_t natural[64];
@@ -126,6 +168,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
         if (lane == 0) status[f] = ORBIT_JPEG_ST_DESC;
         return;
     }
+    if (jpeg_sub_size(d, sub) != 0) return;  // jpeg_entropy_sub_kernel's frame (sub < 0: there is none)
     int16_t* coef = coef_ws + (size_t)f * cap_blocks * 64;
     {
         uint4* z = reinterpret_cast<uint4*>(coef);  // (the slice starts at a multiple of 128 bytes)
@@ -154,32 +197,118 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
             for (int i = lane; i < g.total_blocks * 8; i += 64) z[i] = make_uint4(0, 0, 0, 0);
         }
     }
-    uint32_t tile0 = 0;
-    jpeg_load_tile(stage, mem, len, 0, lane);
-    jpeg_load_tile(stage, mem, len, 1, lane);
-    JpegWalk w;
-    jpeg_walk_init(w, d);
-    __syncthreads();
-    for (;;) {
-        if (lane == 0) {
-            const JpegLdsSrc src{stage, mem, tile0};
-            jpeg_walk(w, src, d, g, natural, coef, (tile0 + 1) * JP_STAGE - 1);
-            ctl[0] = (uint32_t)w.done;
-            ctl[1] = w.bits.pos;
-        }
-        __syncthreads();
-        const uint32_t done = ctl[0], next = ctl[1] / JP_STAGE;  // next > tile0 unless done
-        if (done) break;
-        if (next == tile0 + 1) {
-            jpeg_load_tile(stage, mem, len, next + 1, lane);
-        } else {
-            jpeg_load_tile(stage, mem, len, next, lane);
-            jpeg_load_tile(stage, mem, len, next + 1, lane);
-        }
-        tile0 = next;
-        __syncthreads();
+    const int st = jpeg_walk_tiled<64>(stage, ctl, mem, len, d, g, natural, coef, lane);
+    if (lane == 0) status[f] = st;
+}
+
+// The subsequence-parallel form (csrc/jpeg_core.h) for the frames without restart markers that jpeg_sub_size admits; every
+// other frame of the launch is jpeg_entropy_kernel's and returns at once. One block of JP_SUB_THREADS threads per frame, the
+// threads striding over the N subsequences; the table of N rows lives in LDS. A round is: walk what changed, barrier, hand the
+// exits over, barrier - so entries are read from the round before - until a round walks nothing, at most N rounds. Then the
+// exclusive scan over blocks and DC sums (a run of consecutive rows per thread, the runs' sums through LDS), the checks, the
+// write pass, and on any failure the serial walk of jpeg_entropy_kernel over the zeroed frame. rounds (nullable): rounds taken.
+constexpr int JP_SUB_THREADS = JPEG_SUB_PER_ROUND;
+static_assert(JP_SUB_THREADS == 256 && JPEG_SUB_MAX % JP_SUB_THREADS == 0, "the production rule sizes S by the block's width");
+
+__global__ __launch_bounds__(JP_SUB_THREADS) void jpeg_entropy_sub_kernel(const uint8_t* __restrict__ arena, size_t arena_bytes,
+                                                                          const orbit_jpeg_desc_t* __restrict__ descs, int H, int W,
+                                                                          size_t cap_blocks, int16_t* __restrict__ coef_ws,
+                                                                          int32_t* __restrict__ status, int sub, int32_t* __restrict__ taken,
+                                                                          int32_t* __restrict__ rounds) {
+    constexpr int T = JP_SUB_THREADS;
+    __shared__ __align__(16) orbit_jpeg_desc_t d;
+    __shared__ __align__(16) uint8_t stage[2 * JP_STAGE];
+    __shared__ uint8_t natural[64];
+    __shared__ uint32_t ctl[2];
+    __shared__ __align__(16) JpegSubRow rows[JPEG_SUB_MAX];
+    __shared__ uint4 part[T];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    if (rounds && tid == 0) rounds[f] = 0;
+    // the other kernel's frame: three words of the descriptor say so, before anything is copied (a launch of restart-marked
+    // frames then costs little more than the launch itself)
+    if (descs[f].status != 0 || jpeg_sub_size(descs[f], sub) == 0) return;
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(descs + f);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&d);
+        for (int i = tid; i < (int)(sizeof(orbit_jpeg_desc_t) / 4); i += T) dst[i] = src[i];
+        if (tid < 64) natural[tid] = jpeg_natural_dev[tid];
     }
-    if (lane == 0) status[f] = w.status;
+    __syncthreads();
+    JpegGeom g;
+    // (what jpeg_entropy_kernel checks, and answers in status[] when it does not hold)
+    if (d.status != 0 || !jpeg_geom(d, g) || d.width != W || d.height != H || (size_t)g.total_blocks > cap_blocks ||
+        d.file_offset > arena_bytes || (uint64_t)d.ecs_offset + d.ecs_bytes > arena_bytes - d.file_offset)
+        return;
+    const uint32_t S = jpeg_sub_size(d, sub);
+    if (S == 0) return;  // (uniform: the descriptor is in LDS)
+    const int N = jpeg_sub_count(d, S);  // 2 .. JPEG_SUB_MAX
+    int16_t* coef = coef_ws + (size_t)f * cap_blocks * 64;
+    uint4* z = reinterpret_cast<uint4*>(coef);  // (the slice starts at a multiple of 128 bytes)
+    for (int i = tid; i < g.total_blocks * 8; i += T) z[i] = make_uint4(0, 0, 0, 0);
+    const uint8_t* mem = arena + d.file_offset + d.ecs_offset;
+    const uint32_t len = d.ecs_bytes;
+    for (int i = tid; i < N; i += T) {
+        rows[i].entry = jpeg_sub_guess(mem, len, S, i);
+        rows[i].exit.pos = 0, rows[i].exit.st = 0;
+        rows[i].blocks = rows[i].dc0 = rows[i].dc1 = rows[i].dc2 = 0;
+    }
+    int nrounds = 0;
+    while (nrounds < N) {
+        __syncthreads();
+        int walked = 0;
+        for (int i = tid; i < N; i += T)
+            if (rows[i].entry.st & JPEG_SUB_CHANGED) {
+                rows[i].entry.st &= ~JPEG_SUB_CHANGED;
+                jpeg_sub_walk<false>(rows[i], (uint32_t)(i + 1) * S, mem, d, g, natural, nullptr);
+                walked = 1;
+            }
+        if (!__syncthreads_or(walked)) break;
+        ++nrounds;
+        for (int i = tid; i + 1 < N; i += T) jpeg_sub_hand_over(rows[i], rows[i + 1]);
+    }
+    __syncthreads();
+    // exclusive scan: thread t owns rows t * run .. ; part[t] = their sums
+    const int run = (N + T - 1) / T, first = tid * run;
+    uint4 own = make_uint4(0, 0, 0, 0);
+    for (int i = first; i < first + run && i < N; ++i) own.x += rows[i].blocks, own.y += rows[i].dc0, own.z += rows[i].dc1, own.w += rows[i].dc2;
+    part[tid] = own;
+    __syncthreads();
+    uint4 at = make_uint4(0, 0, 0, 0);
+    uint32_t total = 0;
+    for (int u = 0; u < T; ++u) {
+        const uint4 p = part[u];
+        if (u < tid) at.x += p.x, at.y += p.y, at.z += p.z, at.w += p.w;
+        total += p.x;
+    }
+    const int bpm = jpeg_sub_blocks_per_mcu(d);
+    int bad = 0;
+    for (int i = first; i < first + run && i < N; ++i) {
+        const uint4 r = make_uint4(rows[i].blocks, rows[i].dc0, rows[i].dc1, rows[i].dc2);
+        rows[i].blocks = at.x, rows[i].dc0 = at.y, rows[i].dc1 = at.z, rows[i].dc2 = at.w;
+        at.x += r.x, at.y += r.y, at.z += r.z, at.w += r.w;
+        if (!jpeg_sub_row_ok(rows[i], bpm)) bad = 1;
+    }
+    if (tid == 0 && (total != (uint32_t)g.total_blocks || !jpeg_sub_last_ok(rows[N - 1].exit, mem, len))) bad = 1;
+    if (!__syncthreads_or(bad)) {
+        int st = 0;
+        for (int i = tid; i < N; i += T) st |= jpeg_sub_walk<true>(rows[i], (uint32_t)(i + 1) * S, mem, d, g, natural, coef);
+        if (!__syncthreads_or(st)) {
+            if (tid == 0) {
+                status[f] = 0;
+                if (taken) taken[f] = 3;
+                if (rounds) rounds[f] = nrounds;
+            }
+            return;
+        }
+    }
+    // a damaged file: its status and coefficients are the serial walk's
+    if (tid == 0) {
+        if (taken) taken[f] = 4;
+        if (rounds) rounds[f] = nrounds;
+    }
+    for (int i = tid; i < g.total_blocks * 8; i += T) z[i] = make_uint4(0, 0, 0, 0);
+    const int st = jpeg_walk_tiled<T>(stage, ctl, mem, len, d, g, natural, coef, tid);
+    if (tid == 0) status[f] = st;
 }
 
 __global__ __launch_bounds__(256) void jpeg_idct_kernel(const orbit_jpeg_desc_t* __restrict__ descs, size_t cap_blocks, size_t total,
@@ -262,7 +391,9 @@ int orbit_frames_from_jpeg(const uint8_t* arena, size_t arena_bytes, const orbit
         int16_t* coef = (int16_t*)workspace;
         uint8_t* planes = (uint8_t*)workspace + (size_t)nb * cap_blocks * 64 * sizeof(int16_t);
         int rec = prof_start("jpeg_entropy", 0.0, (double)nb * cap_blocks * 64 * sizeof(int16_t), s);
-        jpeg_entropy_kernel<<<nb, 64, 0, s>>>(arena, arena_bytes, descs + b0, H, W, cap_blocks, coef, status + b0, 1, nullptr);
+        jpeg_entropy_kernel<<<nb, 64, 0, s>>>(arena, arena_bytes, descs + b0, H, W, cap_blocks, coef, status + b0, 1, 0, nullptr);
+        jpeg_entropy_sub_kernel<<<nb, JP_SUB_THREADS, 0, s>>>(arena, arena_bytes, descs + b0, H, W, cap_blocks, coef, status + b0, 0, nullptr,
+                                                              nullptr);
         prof_stop(rec, s);
         ORBIT_LAUNCH_CHECK();
         const size_t blocks = (size_t)nb * cap_blocks;
@@ -292,7 +423,27 @@ int orbit_op_jpeg_entropy(const uint8_t* arena, size_t arena_bytes, const orbit_
     const size_t cap_blocks = jpeg_cap_blocks(H, W), need = (size_t)B * cap_blocks * 64 * sizeof(int16_t);
     ORBIT_REQUIRE(coef_bytes >= need, "op_jpeg_entropy: coef_out of %zu bytes, %d frames of %dx%d need %zu", coef_bytes, B, H, W, need);
     hipStream_t s = (hipStream_t)stream;
-    jpeg_entropy_kernel<<<B, 64, 0, s>>>(arena, arena_bytes, descs, H, W, cap_blocks, coef_out, status, form, taken);
+    jpeg_entropy_kernel<<<B, 64, 0, s>>>(arena, arena_bytes, descs, H, W, cap_blocks, coef_out, status, form, -1, taken);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
+int orbit_op_jpeg_entropy_sub(const uint8_t* arena, size_t arena_bytes, const orbit_jpeg_desc_t* descs, int B, int H, int W, int sub_bytes,
+                              int16_t* coef_out, size_t coef_bytes, int32_t* status, int32_t* taken, int32_t* rounds, orbit_stream_t stream) {
+    ORBIT_REQUIRE(arena && descs && coef_out && status && taken && rounds, "op_jpeg_entropy_sub: null pointer");
+    ORBIT_REQUIRE(B > 0 && H > 0 && W > 0, "op_jpeg_entropy_sub: bad sizes");
+    ORBIT_REQUIRE(H <= ORBIT_RESIZE_MAX_SIZE && W <= ORBIT_RESIZE_MAX_SIZE, "op_jpeg_entropy_sub: %dx%d exceeds the limit of %d pixels per side",
+                  H, W, ORBIT_RESIZE_MAX_SIZE);
+    ORBIT_REQUIRE(sub_bytes == 0 || sub_bytes >= 4, "op_jpeg_entropy_sub: sub_bytes %d (0 = the production rule, or at least 4)", sub_bytes);
+    ORBIT_REQUIRE(arena_bytes > 0, "op_jpeg_entropy_sub: empty arena");
+    ORBIT_REQUIRE(((uintptr_t)coef_out & 15) == 0 && ((uintptr_t)descs & 7) == 0,
+                  "op_jpeg_entropy_sub: coef_out must be 16-byte aligned, descs 8-byte");
+    const size_t cap_blocks = jpeg_cap_blocks(H, W), need = (size_t)B * cap_blocks * 64 * sizeof(int16_t);
+    ORBIT_REQUIRE(coef_bytes >= need, "op_jpeg_entropy_sub: coef_out of %zu bytes, %d frames of %dx%d need %zu", coef_bytes, B, H, W, need);
+    hipStream_t s = (hipStream_t)stream;
+    jpeg_entropy_kernel<<<B, 64, 0, s>>>(arena, arena_bytes, descs, H, W, cap_blocks, coef_out, status, 1, sub_bytes, taken);
+    ORBIT_LAUNCH_CHECK();
+    jpeg_entropy_sub_kernel<<<B, JP_SUB_THREADS, 0, s>>>(arena, arena_bytes, descs, H, W, cap_blocks, coef_out, status, sub_bytes, taken, rounds);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
 }

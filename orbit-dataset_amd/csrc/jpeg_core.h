@@ -1,7 +1,8 @@
 // Baseline JPEG decoding as plain integer code that compiles for the host and for the device: the header parser (host only),
 // the entropy walker (bit reader, Huffman symbol decode, block decode), libjpeg's "islow" inverse DCT, and its chroma
 // upsampling + YCbCr -> RGB conversion per pixel. csrc/jpeg.hip wraps the last three in kernels; tools/jpeg_host_check.cpp
-// (and tools/jpeg_par_host_check.cpp for the walk of one restart interval per lane) runs the very same functions on the CPU
+// (tools/jpeg_par_host_check.cpp for the walk of one restart interval per lane, tools/jpeg_sub_host_check.cpp for the walk of
+// one subsequence of a marker-free stream per lane) runs the very same functions on the CPU
 // under the sanitizers, which is where their behaviour on damaged files is established. Restated from the JPEG standard
 // (ITU T.81) and from the arithmetic of libjpeg's default decode path (jdhuff.c, jidctint.c, jdsample.c, jdcolor.c): the
 // output equals Pillow's for every file the parser accepts and the walker finishes with status 0.
@@ -384,6 +385,295 @@ JPEG_HD int jpeg_walk_interval(int k, int nseg, const uint32_t* ends, const uint
     if (k + 1 == nseg) jpeg_expect_marker(w, s, 0xD9, ORBIT_JPEG_ST_TRAILING);
     else jpeg_expect_marker(w, s, -1, ORBIT_JPEG_ST_RESTART);
     return w.status;
+}
+
+// ---- one subsequence of the segment per walker (the subsequence-parallel form, files without restart markers) --------------------
+// The segment is cut into N = ceil(ecs_bytes / S) subsequences of S raw bytes; a subsequence owns the symbols that START in
+// it. The state of the walk at a symbol start is (position of the next unread bit, block inside the MCU, zig-zag index, ended)
+// - JpegSubState. Subsequence 0 enters with the true state; every other one with a guess (its first byte, block 0, DC next).
+// A round walks every subsequence whose entry changed from that entry to the first symbol start at or behind the next
+// boundary, writing nothing but its exit state, the blocks it STARTED (a DC symbol starts a block) and the sum of the DC
+// differences per component; then every exit that differs from the next entry replaces it (entries are read from the round
+// before: the result and the number of rounds do not depend on the order or the timing of the walkers).
+// Exactness: a walk from a true state reads the symbols jpeg_walk reads there - same tables, same reader arithmetic - so by
+// induction from entry 0 every entry of the fixed point (exit i == entry i + 1 for all i) is a state of the serial walk.
+// Termination: entry 0 is true from the start, so exit 0 is final after round 1, entry i after round i: at most N rounds, and
+// N is the loop bound. A Huffman stream self-synchronises - a walk from a wrong state falls into step with the true one
+// after some symbols - which is why far fewer rounds are needed in practice. A walk from a wrong state may meet an
+// invalid code or an index past 63: it then leaves through the next boundary at (block 0, DC next) with JPEG_SUB_ERROR set.
+// With the entries final, an exclusive scan over blocks and DC sums gives every subsequence the ordinal of its first block and
+// its DC predictors, and jpeg_sub_walk<true> decodes it once more, writing the coefficients jpeg_block writes to the blocks
+// jpeg_walk puts them in. The caller checks (jpeg_sub_row_ok, the block total, jpeg_sub_last_ok, no error bit, no status of
+// the write pass); when anything fails it zeroes the frame's coefficients and runs jpeg_walk over it, as the interval form does.
+#define JPEG_SUB_MAX 1024          // subsequences per frame: the table is 32 KB of LDS
+#define JPEG_SUB_BYTES 128         // S of the production rule, doubled until N <= JPEG_SUB_PER_ROUND
+#define JPEG_SUB_PER_ROUND 256     // the threads of the kernel's block: a round then walks one subsequence per thread at most
+#define JPEG_SUB_MIN_BYTES 512     // a shorter segment is walked serially (fewer than four subsequences)
+#define JPEG_SUB_MIN_MCUS 64       // so is a frame of fewer MCUs: measured slower at 16 MCUs and below, faster from 64 on
+
+#define JPEG_SUB_ENDED 0x1000u     // a marker or the end of the segment follows: nothing more to read
+#define JPEG_SUB_ERROR 0x2000u     // (exit only) the walk met an invalid code, an index past 63 or ran into the end
+#define JPEG_SUB_CHANGED 0x4000u   // (entry only) replaced since this subsequence was last walked
+#define JPEG_SUB_STATE 0x1FFFu     // the bits two states are compared by
+
+// pos: raw offset in the segment of the byte that holds the next unread bit - never the 00 of a stuffed FF 00 - or of the FF
+// of the marker the walk ended at. st: bit inside that byte (0 = its MSB) | block inside the MCU << 3 | zig-zag index << 6 | flags
+struct JpegSubState {
+    uint32_t pos, st;
+};
+// one row of the table (32 bytes): entry, exit, and what the walk from entry to exit counted. After the scan blocks / dc0..2
+// hold the sums over the subsequences before this one (unsigned: a walk from a wrong state may sum anything).
+struct JpegSubRow {
+    JpegSubState entry, exit;
+    uint32_t blocks, dc0, dc1, dc2;
+};
+
+// S for this frame, or 0 when it does not take the form. forced: 0 = the production rule, >= 4 = that S
+JPEG_HD uint32_t jpeg_sub_size(const orbit_jpeg_desc_t& d, int forced) {
+    if (d.restart_interval != 0 || forced < 0) return 0;
+    uint32_t S = (uint32_t)forced;
+    if (forced == 0) {
+        const int h = d.ncomp == 3 && d.hs[0] == 2 ? 2 : 1, v = d.ncomp == 3 && d.vs[0] == 2 ? 2 : 1;  // (as jpeg_geom, for any descriptor)
+        const int64_t mcus = (int64_t)((d.width + 8 * h - 1) / (8 * h)) * ((d.height + 8 * v - 1) / (8 * v));
+        if (d.ecs_bytes < JPEG_SUB_MIN_BYTES || mcus < JPEG_SUB_MIN_MCUS) return 0;
+        S = JPEG_SUB_BYTES;
+        while ((d.ecs_bytes - 1) / S + 1 > JPEG_SUB_PER_ROUND) S *= 2;  // (ecs_bytes < 2^31: S stays below 2^24)
+    }
+    if (S < 4) return 0;
+    const uint32_t n = d.ecs_bytes / S + (d.ecs_bytes % S != 0);
+    return n >= 2 && n <= JPEG_SUB_MAX ? S : 0;
+}
+JPEG_HD int jpeg_sub_count(const orbit_jpeg_desc_t& d, uint32_t S) { return (int)(d.ecs_bytes / S + (d.ecs_bytes % S != 0)); }
+JPEG_HD int jpeg_sub_blocks_per_mcu(const orbit_jpeg_desc_t& d) { return d.ncomp == 3 ? d.hs[0] * d.vs[0] + 2 : 1; }
+
+// the guessed entry of subsequence i > 0 (i = 0: the true one). mem: the segment's first byte
+JPEG_HD JpegSubState jpeg_sub_guess(const uint8_t* mem, uint32_t len, uint32_t S, int i) {
+    JpegSubState e;
+    e.pos = (uint32_t)i * S, e.st = JPEG_SUB_CHANGED;
+    if (i > 0 && e.pos < len && mem[e.pos] == 0 && mem[e.pos - 1] == 0xFF) ++e.pos;  // the 00 of FF 00 belongs to the byte before
+    return e;
+}
+
+// The reader of this form: as jpeg_fill, but an FF that is not followed by 00 - a marker, fill bytes in front of one, the end of
+// the segment - ends the stream with pos left ON that FF, so that the bytes in the accumulator account for every raw byte
+// between the position of the next unread bit and pos. jpeg_symbol and jpeg_get_bits find either 57 bits or the end here and
+// never call jpeg_fill themselves.
+template <class Src>
+JPEG_HD void jpeg_sub_fill(JpegBits& b, const Src& s) {
+    while (b.n <= 56 && b.marker == 0) {
+        if (b.pos >= b.len) {
+            b.marker = -1;
+            break;
+        }
+        const int c = s.at(b.pos);
+        if (c == 0xFF) {
+            const int c2 = b.pos + 1 < b.len ? s.at(b.pos + 1) : -1;
+            if (c2 != 0) {
+                b.marker = c2;
+                break;
+            }
+            ++b.pos;
+        }
+        ++b.pos;
+        b.acc = (b.acc << 8) | (uint64_t)c;
+        b.n += 8;
+    }
+}
+
+// The position of the next unread bit: the accumulator's last ceil(n / 8) bytes are unread (the oldest of them in part), each
+// took one raw byte, two when it is FF.
+JPEG_HD JpegSubState jpeg_sub_position(const JpegBits& b) {
+    const int m = (b.n + 7) >> 3;
+    uint64_t x = m >= 8 ? b.acc : (b.acc & ((1ull << (8 * m)) - 1ull));
+    x &= x >> 1, x &= x >> 2, x &= x >> 4;  // bit 0 of every byte: the byte is FF
+    x &= 0x0101010101010101ull;
+    x = (x * 0x0101010101010101ull) >> 56;  // the count of those bytes
+    JpegSubState p;
+    p.pos = b.pos - (uint32_t)m - (uint32_t)x;
+    p.st = (uint32_t)((8 - (b.n & 7)) & 7);
+    return p;
+}
+
+// The block with ordinal ord in scan order -> its number in the coefficient planes, as jpeg_walk counts
+JPEG_HD int jpeg_sub_block_at(const orbit_jpeg_desc_t& d, const JpegGeom& g, uint32_t ord, int& c) {
+    const int bpm = jpeg_sub_blocks_per_mcu(d);
+    const int mcu = (int)(ord / (uint32_t)bpm), j = (int)(ord % (uint32_t)bpm);
+    const int mx = mcu % g.mcux, my = mcu / g.mcux;
+    if (d.ncomp != 3) {
+        c = 0;
+        return g.base[0] + my * g.wb[0] + mx;
+    }
+    const int h = d.hs[0], v = d.vs[0];
+    if (j < h * v) {
+        c = 0;
+        return g.base[0] + (my * v + j / h) * g.wb[0] + mx * h + j % h;
+    }
+    c = j - h * v + 1;
+    return (c == 1 ? g.base[1] : g.base[2]) + my * g.wb[1] + mx;  // (both chroma planes are mcux x mcuy blocks)
+}
+
+// Subsequence i from row.entry to the first symbol start at or behind `limit` = (i + 1) * S. WRITE = false: fills row.exit,
+// row.blocks and row.dc0..2 and returns 0. WRITE = true: row.blocks / dc0..2 are the scanned sums in front of the
+// subsequence (row is not written); the coefficients go to coef, zeroed by the caller; returns ORBIT_JPEG_ST_* bits (RANGE as
+// jpeg_block sets it; anything else means the walk does not repeat the one the entries came from). Every iteration
+// consumes at least one bit of a stream that ends, or leaves. mem: the segment's first byte.
+template <bool WRITE>
+JPEG_HD int jpeg_sub_walk(JpegSubRow& row, uint32_t limit, const uint8_t* mem, const orbit_jpeg_desc_t& d, const JpegGeom& g,
+                          const uint8_t* natural, int16_t* coef) {
+    const JpegSubState e = row.entry;
+    const int bpm = jpeg_sub_blocks_per_mcu(d), nluma = bpm == 1 ? 1 : bpm - 2;
+    int blk = (int)((e.st >> 3) & 7u), k = (int)((e.st >> 6) & 63u);
+    uint32_t blocks = 0, s0 = 0, s1 = 0, s2 = 0;
+    uint32_t ord = 0;            // WRITE: ordinal of the block the next symbol belongs to
+    int p0 = 0, p1 = 0, p2 = 0;  // WRITE: DC predictors
+    int16_t* out = coef;         // WRITE: that block's coefficients
+    int c = 0;                   // component of block blk
+    if (WRITE) {
+        ord = row.blocks - (k != 0 ? 1u : 0u);  // a block in progress was started by a subsequence before
+        p0 = (int)row.dc0, p1 = (int)row.dc1, p2 = (int)row.dc2;
+    }
+    JpegSubState x;
+    x.pos = e.pos, x.st = e.st & JPEG_SUB_STATE;
+    if (!(e.st & JPEG_SUB_ENDED) && blk < bpm) {
+        JpegWalk w;
+        w.bits.acc = 0, w.bits.n = 0, w.bits.pos = e.pos, w.bits.len = d.ecs_bytes, w.bits.marker = 0;
+        w.status = 0;
+        JpegWinSrc s;
+        s.mem = mem, s.end = d.ecs_bytes;
+        s.load(e.pos < d.ecs_bytes ? e.pos : d.ecs_bytes);
+        jpeg_sub_fill(w.bits, s);
+        const int skip = (int)(e.st & 7u);
+        bool fail = w.bits.n < skip, ended = false;
+        if (!fail) w.bits.n -= skip;
+        if (WRITE && k != 0 && !fail) {
+            int cc;
+            if (ord >= (uint32_t)g.total_blocks) fail = true;
+            else out = coef + (size_t)jpeg_sub_block_at(d, g, ord, cc) * 64;
+        }
+        c = blk < nluma ? 0 : blk - nluma + 1;
+        while (!fail) {
+            jpeg_sub_fill(w.bits, s);
+            // fewer than 8 bits, then a marker: the last symbols of the stream, or the pad bits (ones, which are no code)
+            const bool tail = w.bits.marker != 0 && w.bits.n < 8;
+            if (w.bits.pos - (uint32_t)((w.bits.n + 7) >> 3) >= limit) {  // (an upper bound of the position: rarely true)
+                const JpegSubState p = jpeg_sub_position(w.bits);
+                if (p.pos >= limit) {
+                    x.pos = p.pos, x.st = p.st | ((uint32_t)blk << 3) | ((uint32_t)k << 6);
+                    break;
+                }
+            }
+            if (k == 0) {
+                int sym = jpeg_symbol(w, s, d.huff[d.dc_slot[c] & 1]);
+                if (sym < 0) {
+                    ended = tail && w.status == ORBIT_JPEG_ST_OVERRUN;
+                    break;
+                }
+                sym &= 15;
+                int diff = 0;
+                if (sym) {
+                    const int v = jpeg_get_bits(w, s, sym);
+                    if (w.status) break;
+                    diff = jpeg_extend(v, sym);
+                }
+                ++blocks;
+                if (c == 0) s0 += (uint32_t)diff;
+                else if (c == 1) s1 += (uint32_t)diff;
+                else s2 += (uint32_t)diff;
+                if (WRITE) {
+                    if (ord >= (uint32_t)g.total_blocks) {
+                        w.status |= ORBIT_JPEG_ST_DESC;
+                        break;
+                    }
+                    const int dcv = (int)((uint32_t)(c == 0 ? p0 : (c == 1 ? p1 : p2)) + (uint32_t)diff);  // (wraps on a damaged file)
+                    if (c == 0) p0 = dcv;
+                    else if (c == 1) p1 = dcv;
+                    else p2 = dcv;
+                    const int q0 = (int)d.qt[c][0];
+                    if (dcv < -32768 || dcv > 32767 || dcv * q0 < -32768 || dcv * q0 > 32767) {
+                        w.status |= ORBIT_JPEG_ST_RANGE;
+                        break;
+                    }
+                    int cc;
+                    out = coef + (size_t)jpeg_sub_block_at(d, g, ord, cc) * 64;
+                    out[0] = (int16_t)dcv;
+                }
+                k = 1;
+            } else {
+                const int rs = jpeg_symbol(w, s, d.huff[2 + (d.ac_slot[c] & 1)]);
+                if (rs < 0) {
+                    ended = tail && w.status == ORBIT_JPEG_ST_OVERRUN;
+                    break;
+                }
+                const int r = rs >> 4, sz = rs & 15;
+                if (sz == 0) {
+                    k = r == 15 ? k + 16 : 64;
+                } else {
+                    k += r;
+                    if (k > 63) {
+                        w.status |= ORBIT_JPEG_ST_INDEX;
+                        break;
+                    }
+                    const int raw = jpeg_get_bits(w, s, sz);
+                    if (w.status) break;
+                    if (WRITE) {
+                        const int v = jpeg_extend(raw, sz);
+                        const int pos = natural[k] & 63;
+                        const int dq = v * (int)d.qt[c][pos];
+                        if (dq < -32768 || dq > 32767) {
+                            w.status |= ORBIT_JPEG_ST_RANGE;
+                            break;
+                        }
+                        out[pos] = (int16_t)v;
+                    }
+                    ++k;
+                }
+            }
+            if (k >= 64) {
+                k = 0;
+                blk = blk + 1 == bpm ? 0 : blk + 1;
+                c = blk < nluma ? 0 : blk - nluma + 1;
+                ++ord;
+            }
+        }
+        if (ended) {  // in front of the marker: no symbol starts in the bits that are left
+            x.pos = w.bits.pos, x.st = ((uint32_t)blk << 3) | ((uint32_t)k << 6) | JPEG_SUB_ENDED;
+        } else if (fail || w.status) {
+            if (WRITE) return w.status ? w.status : ORBIT_JPEG_ST_OVERRUN;
+            x.pos = limit, x.st = JPEG_SUB_ERROR;
+        }
+    } else if (blk >= bpm) {
+        x.pos = limit, x.st = JPEG_SUB_ERROR;
+    }
+    if (!WRITE) {
+        row.exit = x;
+        row.blocks = blocks, row.dc0 = s0, row.dc1 = s1, row.dc2 = s2;
+    }
+    return 0;
+}
+
+// after a round: exit i replaces entry i + 1 where they differ. True when it did.
+JPEG_HD bool jpeg_sub_hand_over(const JpegSubRow& from, JpegSubRow& to) {
+    const uint32_t st = from.exit.st & JPEG_SUB_STATE;
+    if (from.exit.pos == to.entry.pos && st == (to.entry.st & JPEG_SUB_STATE)) return false;
+    to.entry.pos = from.exit.pos, to.entry.st = st | JPEG_SUB_CHANGED;
+    return true;
+}
+
+// row i with the sums scanned: no error bit, and the ordinal of the block its entry is in agrees with the entry's block index
+JPEG_HD bool jpeg_sub_row_ok(const JpegSubRow& r, int bpm) {
+    if (r.exit.st & JPEG_SUB_ERROR) return false;
+    const uint32_t in_block = (r.entry.st >> 6) & 63u ? 1u : 0u;
+    if (r.blocks < in_block) return false;
+    return (r.blocks - in_block) % (uint32_t)bpm == ((r.entry.st >> 3) & 7u);
+}
+
+// the last exit: ended between two MCUs, and the marker there is EOI (fill bytes in front of it are allowed, as jpeg_fill has it)
+JPEG_HD bool jpeg_sub_last_ok(const JpegSubState& x, const uint8_t* mem, uint32_t len) {
+    if ((x.st & (JPEG_SUB_STATE | JPEG_SUB_ERROR)) != JPEG_SUB_ENDED) return false;  // (block 0, DC next, bit 0)
+    uint32_t p = x.pos;
+    if (p >= len || mem[p] != 0xFF) return false;
+    while (p < len && mem[p] == 0xFF) ++p;
+    return p < len && mem[p] == 0xD9;
 }
 
 // ---- dequantisation + inverse DCT (libjpeg jidctint.c jpeg_idct_islow) -----------------------------------------------------------

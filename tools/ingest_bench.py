@@ -6,12 +6,13 @@ offline pass of the reference (scripts/resize_videos.py:46) this replaces. The f
 --decode measures the JPEG decoder instead (orbit_frames_from_jpeg, csrc/jpeg.hip) on 224 x 224 and 1080 x 1080 frames written
 by write_synthetic_orbit_directory: us per launch of each of its three kernels, the bytes uploaded compressed against decoded,
 and PIL's decode of the same files on 16 threads; every frame is compared with PIL. --restart_rows N re-saves the frames with a
-restart marker every N MCU rows first: those the entropy kernel decodes with one lane per restart interval.
+restart marker every N MCU rows first: those the entropy kernel decodes with one lane per restart interval. --content noise
+replaces the frames by uniform noise; --sub_sweep S .. measures the entropy stage alone at these subsequence sizes.
 --encode measures the JPEG encoder (orbit_frames_to_jpeg, csrc/jpeg_enc.hip) on 224 x 224 frames - the size tools/resize_videos.py
 writes - of smooth and of noise content at quality 95: us per call of each of its kernels beside the kernel's byte floor (its
 algorithmic bytes at 6.3 TB/s), the compressed bytes out, and PIL's save(quality=95) of the same frames on 16 threads; every
 file is compared with PIL's.
-Usage (GPU box): python tools/ingest_bench.py [--decode [--restart_rows N] | --encode] [--frames 200] [--reps 10] [--threads 16]"""
+Usage (GPU box): python tools/ingest_bench.py [--decode [--restart_rows N] [--content noise] [--sub_sweep S ..] | --encode] [--frames 200] [--reps 10] [--threads 16]"""
 import argparse
 import ctypes
 import json
@@ -51,6 +52,81 @@ def measure(lib, run, reps):
     return 1e3 * ms.value / reps, nbytes.value / reps, name.value.decode()
 
 
+def _rewrite_frames(a, paths, size):
+    """--content noise: the frames replaced by uniform noise, the least compressible content; --restart_rows N: re-saved with a
+    restart marker every N MCU rows. Both at the quality the frames were written at."""
+    if a.content != "noise" and a.restart_rows <= 0:
+        return
+    rng = np.random.default_rng(0)
+    kw = {"restart_marker_rows": a.restart_rows} if a.restart_rows > 0 else {}
+    for path in paths:
+        img = Image.fromarray(rng.integers(0, 256, (size, size, 3), dtype=np.uint8)) if a.content == "noise" else Image.open(path)
+        img.save(path, quality=90, **kw)
+
+
+def measure_sub_sweep(a, lib, dev, pool):
+    """the entropy stage alone, per frame size: orbit_op_jpeg_entropy form 0 (serial) and form 1, then orbit_op_jpeg_entropy_sub
+    at every sub_bytes of --sub_sweep (0 = the production rule) - us per call between two events, the forms taken, the rounds
+    per frame - each compared with form 0's coefficients"""
+    import glob
+    import tempfile
+    from orbit_dataset_amd.data import pipeline
+    rows = []
+    for size in a.sizes:
+        with tempfile.TemporaryDirectory() as root:
+            pipeline.write_synthetic_orbit_directory(root, users=1, objects_per_user=1, clean_videos=1, clutter_videos=0,
+                                                     frames_per_video=a.frames, frame_size=size)
+            paths = sorted(glob.glob(os.path.join(root, "*", "*", "*", "*", "*.jpg")))
+            _rewrite_frames(a, paths, size)
+            jf = pipeline.read_jpeg_frames(paths, pool)
+        n, dsize = len(jf.files), ctypes.sizeof(_lib.JpegDesc)
+        descs = np.ascontiguousarray(jf.descs).reshape(n, dsize).copy()
+        descs.view(np.uint64)[:, 0] = np.cumsum([0] + [len(f) for f in jf.files[:-1]])
+        arena = torch.from_numpy(np.frombuffer(b"".join(jf.files), dtype=np.uint8).copy()).to(dev)
+        d_descs = torch.from_numpy(descs.reshape(-1)).to(dev)
+        cap = 3 * (2 * ((size + 15) // 16)) ** 2
+        coef = torch.zeros((n, cap, 64), dtype=torch.int16, device=dev)
+        status, taken, rounds = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(3))
+        args = (_lib.dptr(arena), arena.numel(), _lib.dptr(d_descs), n, size, size)
+        tail = (_lib.dptr(coef, torch.int16), coef.numel() * 2, _lib.dptr(status), _lib.dptr(taken))
+
+        def timed(call):
+            for _ in range(2):
+                call()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.reps + 1)]
+            ev[0].record()
+            for i in range(a.reps):
+                call()
+                ev[i + 1].record()
+            torch.cuda.synchronize()
+            assert not status.cpu().numpy().any(), "a frame was not decoded"
+            us = sorted(1e3 * ev[i].elapsed_time(ev[i + 1]) for i in range(a.reps))
+            return us[0], us[len(us) // 2]
+
+        ecs = [len(f) for f in jf.files]
+        best, med = timed(lambda: _lib.check(lib.orbit_op_jpeg_entropy(*args, 0, *tail, _lib.stream_handle()), "orbit_op_jpeg_entropy"))
+        want = coef.clone()
+        rows.append({"size": size, "content": a.content, "restart_rows": a.restart_rows, "what": "form 0", "us_min": best, "us_median": med,
+                     "mean_file_bytes": float(np.mean(ecs))})
+        best, med = timed(lambda: _lib.check(lib.orbit_op_jpeg_entropy(*args, 1, *tail, _lib.stream_handle()), "orbit_op_jpeg_entropy"))
+        rows.append({"size": size, "content": a.content, "restart_rows": a.restart_rows, "what": "form 1", "us_min": best, "us_median": med})
+        for sub_bytes in a.sub_sweep:
+            best, med = timed(lambda: _lib.check(lib.orbit_op_jpeg_entropy_sub(*args, sub_bytes, *tail, _lib.dptr(rounds), _lib.stream_handle()),
+                                                 "orbit_op_jpeg_entropy_sub"))
+            t, r = taken.cpu().numpy(), rounds.cpu().numpy()
+            rows.append({"size": size, "content": a.content, "restart_rows": a.restart_rows, "what": "sub_bytes %d" % sub_bytes, "us_min": best,
+                         "us_median": med, "taken": {int(k): int((t == k).sum()) for k in np.unique(t)},
+                         "rounds_mean": float(r[t == 3].mean()) if (t == 3).any() else 0.0, "rounds_max": int(r.max()),
+                         "equals_form_0": bool(torch.equal(coef, want))})
+        for row in rows[-(2 + len(a.sub_sweep)):]:
+            print("%4d %-6s restart_rows %d  %-14s %9.1f us min %9.1f us median  %s" % (
+                size, a.content, a.restart_rows, row["what"], row["us_min"], row["us_median"],
+                {k: v for k, v in row.items() if k in ("taken", "rounds_mean", "rounds_max", "equals_form_0", "mean_file_bytes")}), flush=True)
+            assert row.get("equals_form_0", True), "coefficients differ from the serial walk's"
+        del coef, want, arena
+    return rows
+
+
 def measure_decode(a, lib, dev, pool):
     """orbit_frames_from_jpeg against PIL's decode, per frame size"""
     import glob
@@ -62,9 +138,7 @@ def measure_decode(a, lib, dev, pool):
             pipeline.write_synthetic_orbit_directory(root, users=1, objects_per_user=1, clean_videos=1, clutter_videos=0,
                                                      frames_per_video=a.frames, frame_size=size)
             paths = sorted(glob.glob(os.path.join(root, "*", "*", "*", "*", "*.jpg")))
-            if a.restart_rows > 0:  # the same frames with a restart marker every N MCU rows, at the quality they were written at
-                for path in paths:
-                    Image.open(path).save(path, quality=90, restart_marker_rows=a.restart_rows)
+            _rewrite_frames(a, paths, size)
             t0 = time.perf_counter()
             jf = pipeline.read_jpeg_frames(paths, pool)
             read_ms = 1e3 * (time.perf_counter() - t0)
@@ -99,7 +173,7 @@ def measure_decode(a, lib, dev, pool):
             lib.orbit_prof_variant(i, name, ctypes.byref(launches), ctypes.byref(kms), None, None)
             kernels[name.value.decode()] = {"us_per_call": 1e3 * kms.value / a.reps, "launches_per_call": launches.value / a.reps}
         compressed, decoded = sum(len(f) for f in jf.files), int(np.prod(jf.shape))
-        row = {"size": size, "frames": a.frames, "restart_rows": a.restart_rows, "kernels": kernels, "us_per_call": 1e3 * ms.value / a.reps,
+        row = {"size": size, "frames": a.frames, "restart_rows": a.restart_rows, "content": a.content, "kernels": kernels, "us_per_call": 1e3 * ms.value / a.reps,
                "compressed_bytes": compressed, "decoded_bytes": decoded, "pil_ms": 1e3 * min(pil_s), "pil_threads": a.threads,
                "read_and_parse_ms": read_ms, "all_frames_equal_pil": exact}
         rows.append(row)
@@ -203,6 +277,11 @@ def main(argv=None):
     p.add_argument("--restart_rows", type=int, default=0,
                    help="with --decode: re-save the frames with a restart marker every N MCU rows (Pillow's restart_marker_rows), "
                         "which the entropy kernel decodes with one lane per restart interval; 0 = no markers")
+    p.add_argument("--content", choices=("smooth", "noise"), default="smooth",
+                   help="with --decode: the frames write_synthetic_orbit_directory draws, or uniform noise (the least compressible content)")
+    p.add_argument("--sub_sweep", type=int, nargs="+", default=None,
+                   help="with --decode: measure the entropy stage alone instead - serial, interval form, and the subsequence form at "
+                        "each of these sub_bytes (0 = the production rule)")
     p.add_argument("--frames", type=int, default=200)
     p.add_argument("--reps", type=int, default=10)
     p.add_argument("--threads", type=int, default=16)
@@ -222,7 +301,7 @@ def main(argv=None):
         return rows
     if a.decode:
         print("%d frames per call, device %s, PIL %s on %d threads" % (a.frames, torch.cuda.get_device_name(0), Image.__version__, a.threads))
-        rows = measure_decode(a, lib, dev, pool)
+        rows = measure_sub_sweep(a, lib, dev, pool) if a.sub_sweep is not None else measure_decode(a, lib, dev, pool)
         if a.json:
             with open(a.json, "w") as f:
                 json.dump(rows, f, indent=1)
