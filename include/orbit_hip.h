@@ -321,6 +321,26 @@ int orbit_vit_enable_backward(orbit_vit_t* v);
  * patch-16 plan that has not called it behaves as described above. A no-op returning ORBIT_OK on a patch-32 plan;
  * ORBIT_ERR_ARG for NULL. */
 int orbit_vit_enable_weight_backward(orbit_vit_t* v);
+/* Opt a plan (any of the six models) into bf16 token GEMMs for INFERENCE: orbit_vit_forward then runs qkv, proj, fc1 and fc2 of
+ * all 12 blocks on v_mfma_f32_32x32x16_bf16 (vit_gemm_bf16_kernel), everything else - patch embedding, class-token row,
+ * LayerNorm + FiLM, attention, the fp32 residual stream in HBM - on the fp32 kernels, unchanged. Workspace layout,
+ * orbit_vit_workspace_bytes and orbit_vit_macs_per_frame do not change. A documented precision trade, off by default: without
+ * this call a plan computes what it always did, bit for bit.
+ * Numerics of a bf16 GEMM: x (fp32 token rows) and the weight are each rounded to bf16 once, round to nearest even; their
+ * products are exact; every 64-deep K step is summed in the matrix unit from zero and added to the running fp32 sum with one
+ * fp32 add per step, in ascending k; bias, GELU and the residual add follow in fp32. Deterministic, and a row's bits depend
+ * neither on the number of rows nor on the tile height (so a frame's features do not depend on its batch). Nothing is promised
+ * about subnormal inputs.
+ * The bf16 weight copies (144 D^2 * 2 bytes, one plan-owned device buffer) are made on `stream` by the first bf16 forward after
+ * a parameter upload; every orbit_vit_load* invalidates them, orbit_vit_destroy frees them, and a plan without the flag never
+ * allocates them. A flag on this plan only: idempotent, allocates nothing, legal before or after orbit_vit_finalize and after
+ * fp32 forwards. Training is fp32 only: on a bf16 plan orbit_vit_train_forward, orbit_vit_backward and orbit_vit_backward_params
+ * return ORBIT_ERR_ARG naming orbit_vit_enable_bf16 before any launch or allocation, orbit_vit_enable_backward /
+ * orbit_vit_enable_weight_backward are refused the same way, and so is this call on a plan that has either of them set.
+ * ORBIT_ERR_ARG for NULL. */
+int orbit_vit_enable_bf16(orbit_vit_t* v);
+/* 1 after orbit_vit_enable_bf16, else 0 (0 for NULL) */
+int orbit_vit_bf16_enabled(const orbit_vit_t* v);
 size_t orbit_vit_backward_workspace_bytes(const orbit_vit_t* v, int B);
 int orbit_vit_train_forward(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta,
                             float* feats, void* tape, size_t tape_bytes, void* workspace, size_t workspace_bytes,
@@ -466,6 +486,14 @@ int orbit_op_se_gate(const float* pooled, const float* w1, const float* b1, cons
  * tiles when they make at least 512 workgroups, else 64-row), 64 or 128 = that tile height. */
 int orbit_op_vit_linear(const float* x, const float* w, const float* bias, const float* residual, float* y, int M, int N,
                         int K, int epilogue, int tile_rows, orbit_stream_t stream);
+/* fp32 -> bf16, round to nearest even (ties to even), numel elements: the weight copies of a bf16 plan. w 4-byte aligned, out
+ * 2-byte aligned (16-byte aligned buffers take the 8-elements-per-thread path); nothing is written past out[numel - 1]. */
+int orbit_op_vit_pack_bf16(const float* w, uint16_t* out, size_t numel, orbit_stream_t stream);
+/* orbit_op_vit_linear on the bf16 matrix cores (the numerics stated at orbit_vit_enable_bf16): x [M][K] fp32, rounded to bf16
+ * inside the kernel; w_bf16 [N][K] bf16 (orbit_op_vit_pack_bf16); bias, residual (may alias y), y, epilogue and tile_rows as
+ * above. N % 128 == 0 and K % 64 == 0, else ORBIT_ERR_ARG with the shape in the message; x and w_bf16 16-byte aligned. */
+int orbit_op_vit_linear_bf16(const float* x, const uint16_t* w_bf16, const float* bias, const float* residual, float* y, int M,
+                             int N, int K, int epilogue, int tile_rows, orbit_stream_t stream);
 /* frames NCHW [B][3][224][224], w OIHW [D][3][32][32], pos_embed [50][D], cls_token [D] -> tokens [B][50][D]: row 0 =
  * cls_token + pos_embed[0], row 1+p = patch p (row-major 7x7) . w + bias + pos_embed[1+p]. D is 384 or 768. */
 int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,

@@ -67,6 +67,8 @@ _SIGNATURES = {
     "orbit_vit_tape_bytes": (c_size_t, [P, c_int]),
     "orbit_vit_enable_backward": (c_int, [P]),
     "orbit_vit_enable_weight_backward": (c_int, [P]),
+    "orbit_vit_enable_bf16": (c_int, [P]),
+    "orbit_vit_bf16_enabled": (c_int, [P]),
     "orbit_vit_backward_workspace_bytes": (c_size_t, [P, c_int]),
     "orbit_vit_train_forward": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P, c_size_t, P]),
     "orbit_vit_backward": (c_int, [P, c_int, P, P, P, P, c_size_t, P, P, P, c_size_t, P]),
@@ -96,6 +98,8 @@ _SIGNATURES = {
     "orbit_op_avgpool": (c_int, [P, P, c_int, c_int, c_int, P]),
     "orbit_op_se_gate": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P]),
     "orbit_op_vit_linear": (c_int, [P] * 5 + [c_int] * 5 + [P]),
+    "orbit_op_vit_pack_bf16": (c_int, [P, P, c_size_t, P]),
+    "orbit_op_vit_linear_bf16": (c_int, [P] * 5 + [c_int] * 5 + [P]),
     "orbit_op_vit_patch_embed": (c_int, [P] * 6 + [c_int] * 3 + [P]),
     "orbit_op_vit_layernorm": (c_int, [P, c_size_t, P, c_size_t, c_int, c_int, P, P, c_float, P]),
     "orbit_op_vit_attention": (c_int, [P, P, c_int, c_int, c_int, P]),

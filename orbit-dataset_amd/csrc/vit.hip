@@ -19,6 +19,9 @@
 //   vit_layernorm_kernel one wave per token row, two-pass (mean, centred variance) in registers; gamma / beta from the
 //                        parameter pool or from the per-task FiLM vectors (reference model/film.py:57-66).
 //   vit_attention_kernel one workgroup per (frame, head): Q, K, V (50 x 64) in LDS, S = QK^T / 8, row softmax, O = PV.
+//   vit_gemm_bf16_kernel the opt-in inference form of the four token GEMMs (orbit_vit_enable_bf16): bf16 operands, fp32
+//                        accumulation on v_mfma_f32_32x32x16_bf16, weights from bf16 copies made by vit_pack_bf16_kernel;
+//                        everything else of such a plan's forward is the fp32 kernels of this list.
 // The patch-16 models of the same families (vit_s_16, vit_b_16, vit_b_16_clip: 14 x 14 patches, 197 tokens, six names in all)
 // run the same forward with the geometry read from the plan: the patch GEMM's EPI_PATCH16 form (k = c*256 + kh*16 + kw, token
 // rows 1..196) and vit_attention197_kernel (fp32 MFMA, K and V resident in LDS). Their plans are inference + FiLM only until
@@ -31,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "bf3.h"
 #include "common.h"
 #include "device_util.h"
 #include "param_pool.h"
@@ -57,6 +61,8 @@ constexpr int VIT16_KPATCH = 3 * VIT16_PATCH * VIT16_PATCH;  // 768
 constexpr int VIT16_MAX_B = 2048;
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 // ---- token GEMM ------------------------------------------------------------------------------------------------------
 constexpr int G_BN = 128, G_BK = 32, G_THREADS = 256;
@@ -260,6 +266,188 @@ int launch_gemm(const GemmArgs& a, const char* what, hipStream_t s, int tile_row
         vit_gemm_kernel<128, EPI, BLOCKED><<<dim3(n_tiles, cdiv(a.M, 128)), G_THREADS, 0, s>>>(a);
     else
         vit_gemm_kernel<64, EPI, BLOCKED><<<dim3(n_tiles, cdiv(a.M, 64)), G_THREADS, 0, s>>>(a);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
+// ---- bf16 token GEMM (opt-in: orbit_vit_enable_bf16) -----------------------------------------------------------------
+// y = x W^T + b (+ erf-GELU | + residual) on v_mfma_f32_32x32x16_bf16: the outer shape of vit_gemm_kernel (BM x 128 block tile,
+// 256 threads, 2 x 2 waves, the same tail rule and epilogues), 64-deep K steps. x is the fp32 token rows, rounded to bf16 (RNE,
+// v_cvt_pk_bf16_f32) on the way into LDS; w is a bf16 copy of the weight [N][K] (vit_pack_bf16_kernel). LDS rows are
+// K-contiguous, 64 bf16 + 16 bytes of padding (GB_ROWB = 144 bytes: 9 r mod 16 is a bijection, so the sixteen rows of a
+// ds_read_b128 lane group fall on sixteen different 16-byte slots), and a lane's fragment is one 16-byte read:
+// lane l holds row l & 31, k = 16 ks + 8 (l >> 5) + j.
+// Numerics: every operand is rounded to bf16 once (RNE); products of two bf16 are exact in the matrix unit. Each 64-deep K step
+// is summed by four chained MFMAs that start from ZERO, and that partial sum is added to the running fp32 sum with one RNE add
+// per step, in ascending k (the unit aligns its addends to the largest exponent and drops low bits without rounding - fed the
+// running sum as C it would lose up to an ulp of the SUM per instruction, always toward zero; see the conv_bf3 row of DESIGN.md
+// §5). The epilogue is fp32. Deterministic; a row's bits depend neither on M nor on the tile height (every row sees the same
+// steps in the same order). Nothing is promised about subnormal inputs.
+constexpr int GB_BK = 64, GB_ROWB = 2 * GB_BK + 16;
+
+struct GemmBf16Args {
+    const float* x;           // [M][K] fp32 token rows
+    const unsigned short* w;  // [N][K] bf16
+    const float* bias;        // [N] or nullptr
+    const float* residual;    // [M][N] (EPI_RESIDUAL; may alias y)
+    float* y;
+    int M, N, K;
+};
+
+template <int BM, int EPI>
+__global__ __launch_bounds__(G_THREADS) void vit_gemm_bf16_kernel(GemmBf16Args a) {
+    constexpr int TI = BM / 64;   // 32-row MFMA tiles per wave (waves are 2 x 2 over the block tile)
+    constexpr int AR = BM / 32;   // 32-byte loads of A per thread per K step (8 fp32 -> 8 bf16)
+    constexpr int BR = G_BN / 32; // 16-byte loads of B
+    constexpr int KS = GB_BK / 16;
+    __shared__ __attribute__((aligned(16))) char smem[(BM + G_BN) * GB_ROWB];
+    char* As = smem;
+    char* Bs = smem + BM * GB_ROWB;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int n0 = blockIdx.x * G_BN, m0 = blockIdx.y * BM;
+    const int lc = tid & 7, lr = tid >> 3;  // loader: k chunk (8 elements) and row
+
+    const float* ap[AR];
+#pragma unroll
+    for (int i = 0; i < AR; ++i) {
+        int m = m0 + lr + 32 * i;
+        m = m < a.M ? m : a.M - 1;  // rows past the tail re-read the last row; their outputs are never stored
+        ap[i] = a.x + (size_t)m * a.K + 8 * lc;
+    }
+    const unsigned short* bp[BR];
+#pragma unroll
+    for (int i = 0; i < BR; ++i) bp[i] = a.w + (size_t)(n0 + lr + 32 * i) * a.K + 8 * lc;
+
+    floatx16 acc[TI][2];
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    floatx4 ra0[AR], ra1[AR];
+    uintx4 rb[BR];
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+            ra0[i] = *reinterpret_cast<const floatx4*>(ap[i] + k0);
+            ra1[i] = *reinterpret_cast<const floatx4*>(ap[i] + k0 + 4);
+        }
+#pragma unroll
+        for (int i = 0; i < BR; ++i) rb[i] = *reinterpret_cast<const uintx4*>(bp[i] + k0);
+    };
+
+    // fragment addresses: row l & 31 of the wave's tiles, 16 bytes at k = 8 (l >> 5) of each 16-deep k-step
+    const int fr = lane & 31, fh = lane >> 5;
+    const char* afp = As + (wm * (BM / 2) + fr) * GB_ROWB + 16 * fh;
+    const char* bfp = Bs + (wn * 64 + fr) * GB_ROWB + 16 * fh;
+
+    const int nk = a.K / GB_BK;
+    load(0);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < AR; ++i) {
+            const uintx4 p = {pk_bf16(ra0[i][0], ra0[i][1]), pk_bf16(ra0[i][2], ra0[i][3]), pk_bf16(ra1[i][0], ra1[i][1]),
+                              pk_bf16(ra1[i][2], ra1[i][3])};
+            *reinterpret_cast<uintx4*>(As + (lr + 32 * i) * GB_ROWB + 16 * lc) = p;
+        }
+#pragma unroll
+        for (int i = 0; i < BR; ++i) *reinterpret_cast<uintx4*>(Bs + (lr + 32 * i) * GB_ROWB + 16 * lc) = rb[i];
+        __syncthreads();
+        if (kt + 1 < nk) load((kt + 1) * GB_BK);  // next K step in flight during the MFMAs
+        // EVERY fragment of the K step is in registers before its first MFMA, and none is written again before the step's last
+        // MFMA result has been read (the adds below): an issued bf16 MFMA that waits behind another stream's matrix work has been
+        // seen to pick up operands that a later LDS return overwrote (csrc/conv_bf3.hip, compute_tile)
+        bf16x8 af[KS][TI], bf[KS][2];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+#pragma unroll
+            for (int i = 0; i < TI; ++i) af[ks][i] = *reinterpret_cast<const bf16x8*>(afp + 32 * i * GB_ROWB + 32 * ks);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bf[ks][j] = *reinterpret_cast<const bf16x8*>(bfp + 32 * j * GB_ROWB + 32 * ks);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < TI; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                floatx16 t;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) t[r] = 0.f;
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks][i], bf[ks][j], t, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] += t[r];
+            }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+
+    // epilogue: C[row][col], col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) - the map of the fp32 32x32x2 form
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = n0 + wn * 64 + 32 * j + (lane & 31);
+            const float bv = a.bias ? a.bias[col] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = m0 + wm * (BM / 2) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (row >= a.M) continue;
+                float v = acc[i][j][r] + bv;
+                if (EPI == EPI_GELU) v = gelu_erf(v);
+                if (EPI == EPI_RESIDUAL) v += a.residual[(size_t)row * a.N + col];
+                a.y[(size_t)row * a.N + col] = v;
+            }
+        }
+}
+
+// the tile rule and the tile_rows override of launch_gemm; profiler rows vit_<what>_bf16<64|128>
+template <int EPI>
+int launch_gemm_bf16(const GemmBf16Args& a, const char* what, hipStream_t s, int tile_rows = 0) {
+    if (a.N % G_BN || a.K % GB_BK || a.M <= 0)
+        return set_err(ORBIT_ERR_ARG, "vit bf16 gemm: unsupported shape M=%d N=%d K=%d (N %% %d and K %% %d must be 0)", a.M, a.N, a.K,
+                       G_BN, GB_BK);
+    if (int rc = check_tile_rows(tile_rows)) return rc;
+    const int n_tiles = a.N / G_BN;
+    const bool tall = tile_rows ? tile_rows == 128 : (long)cdiv(a.M, 128) * n_tiles >= 512;
+    const double flops = 2.0 * a.M * a.N * a.K;
+    const double bytes = 4.0 * a.M * a.K + 2.0 * a.N * a.K + 4.0 * a.M * a.N * (EPI == EPI_RESIDUAL ? 2 : 1);
+    char name[56];
+    snprintf(name, sizeof(name), "vit_%s_bf16<%d>", what, tall ? 128 : 64);
+    const int pi = prof_start(name, flops, bytes, s);
+    if (tall)
+        vit_gemm_bf16_kernel<128, EPI><<<dim3(n_tiles, cdiv(a.M, 128)), G_THREADS, 0, s>>>(a);
+    else
+        vit_gemm_bf16_kernel<64, EPI><<<dim3(n_tiles, cdiv(a.M, 64)), G_THREADS, 0, s>>>(a);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
+// fp32 -> bf16 (RNE), 8 elements per thread; the tail and unaligned buffers go element by element
+__global__ __launch_bounds__(256) void vit_pack_bf16_kernel(const float* __restrict__ w, unsigned short* __restrict__ out,
+                                                            size_t numel, int vec_ok) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (i >= numel) return;
+    if (vec_ok && i + 8 <= numel) {
+        const float4 lo = *reinterpret_cast<const float4*>(w + i), hi = *reinterpret_cast<const float4*>(w + i + 4);
+        const uint4 p = {pk_bf16(lo.x, lo.y), pk_bf16(lo.z, lo.w), pk_bf16(hi.x, hi.y), pk_bf16(hi.z, hi.w)};
+        *reinterpret_cast<uint4*>(out + i) = p;
+        return;
+    }
+    for (size_t j = i; j < numel && j < i + 8; ++j) out[j] = (unsigned short)(pk_bf16(w[j], 0.f) & 0xffffu);
+}
+
+int launch_pack_bf16(const float* w, unsigned short* out, size_t numel, hipStream_t s) {
+    const int vec_ok = (((uintptr_t)w | (uintptr_t)out) & 15) == 0;
+    const size_t blocks = (numel + 2047) / 2048;  // 256 threads x 8 elements
+    const int pi = prof_start("vit_pack_bf16", 0.0, 6.0 * numel, s);
+    vit_pack_bf16_kernel<<<(unsigned)blocks, 256, 0, s>>>(w, out, numel, vec_ok);
     prof_stop(pi, s);
     ORBIT_LAUNCH_CHECK();
     return ORBIT_OK;
@@ -1213,6 +1401,11 @@ struct orbit_vit {
     // first orbit_vit_backward after a parameter upload, never by inference
     float* d_wt = nullptr;
     bool wt_valid = false;
+    // orbit_vit_enable_bf16: qkv / proj / fc1 / fc2 run on vit_gemm_bf16_kernel from bf16 copies of their weights (the layout of
+    // vit_wt, 2 bytes per element): made by the first bf16 forward after a parameter upload, never on a plan without the flag
+    bool bf16_enabled = false;
+    unsigned short* d_wbf = nullptr;
+    bool wbf_valid = false;
 
     const float* p(size_t off) const { return off == VIT_ABSENT ? nullptr : pool.d_pool + off; }
 };
@@ -1288,6 +1481,8 @@ int vit_check_call(const char* who, const orbit_vit* v, int B, const float* film
 // the training entry points on a forward-only plan: refused by name, before any launch or allocation
 int vit_check_trainable(const char* who, const orbit_vit* v) {
     ORBIT_REQUIRE(v, "%s: null pointer", who);
+    ORBIT_REQUIRE(!v->bf16_enabled, "%s: %s is a bf16 inference plan (orbit_vit_enable_bf16): the training paths are fp32 only", who,
+                  v->name.c_str());
     ORBIT_REQUIRE(!v->forward_only(), "%s: %s is an inference-only plan (no tape and no backward for the patch-%d models)", who,
                   v->name.c_str(), v->patch);
     return ORBIT_OK;
@@ -1354,6 +1549,7 @@ void orbit_vit_destroy(orbit_vit_t* v) {
     if (!v) return;
     v->pool.free_device();
     (void)hipFree(v->d_wt);
+    (void)hipFree(v->d_wbf);
     delete v;
 }
 
@@ -1361,25 +1557,25 @@ int orbit_vit_num_params(const orbit_vit_t* v) { return v ? v->pool.size() : 0; 
 const char* orbit_vit_param_name(const orbit_vit_t* v, int i) { return v ? v->pool.name(i) : nullptr; }
 size_t orbit_vit_param_numel(const orbit_vit_t* v, int i) { return v ? v->pool.numel(i) : 0; }
 
-// every upload invalidates the finalized state and the transposed weights of the backward
+// every upload invalidates the finalized state, the transposed weights of the backward and the bf16 copies
 int orbit_vit_load(orbit_vit_t* v, const char* key, const float* data, size_t numel) {
     ORBIT_REQUIRE(v && key && data, "vit_load: null pointer");
     if (int rc = v->pool.load("vit_load", key, data, numel)) return rc;
-    v->finalized = false, v->wt_valid = false;
+    v->finalized = false, v->wt_valid = false, v->wbf_valid = false;
     return ORBIT_OK;
 }
 
 int orbit_vit_load_async(orbit_vit_t* v, const char* key, const float* device_data, size_t numel, orbit_stream_t stream) {
     ORBIT_REQUIRE(v && key && device_data, "vit_load_async: null pointer");
     if (int rc = v->pool.load_async("vit_load_async", key, device_data, numel, (hipStream_t)stream)) return rc;
-    v->finalized = false, v->wt_valid = false;
+    v->finalized = false, v->wt_valid = false, v->wbf_valid = false;
     return ORBIT_OK;
 }
 
 int orbit_vit_load_all_async(orbit_vit_t* v, const float* const* device_ptrs, int n, orbit_stream_t stream) {
     ORBIT_REQUIRE(v && device_ptrs, "vit_load_all_async: null pointer");
     if (int rc = v->pool.load_all_async("vit_load_all_async", device_ptrs, n, 32, (hipStream_t)stream)) return rc;
-    v->finalized = false, v->wt_valid = false;
+    v->finalized = false, v->wt_valid = false, v->wbf_valid = false;
     return ORBIT_OK;
 }
 
@@ -1414,8 +1610,34 @@ namespace {
 // the forward. tape == nullptr: inference, the stream is updated in place inside the workspace. With a tape the same kernels in
 // the same order write what the backward reads straight into it (each residual GEMM reads one tape slot and writes the next),
 // and fc1 stores its pre-activation beside GELU(u) (EPI_GELU_TAPE): the features are bitwise those of the inference forward.
+// (re)build the bf16 weight copies on `s` if a parameter upload invalidated them
+int vit_ensure_wbf(orbit_vit_t* v, hipStream_t s) {
+    const VitWt W = vit_wt(v);
+    const size_t DD = (size_t)v->D * v->D;
+    if (!v->d_wbf) ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&v->d_wbf), VIT_DEPTH * W.block * sizeof(unsigned short)));
+    if (v->wbf_valid) return ORBIT_OK;
+    int rc;
+    for (int i = 0; i < VIT_DEPTH; ++i) {
+        const VitBlock& k = v->blk[i];
+        unsigned short* wb = v->d_wbf + i * W.block;
+        if ((rc = launch_pack_bf16(v->p(k.qkv_w), wb + W.qkv, 3 * DD, s))) return rc;
+        if ((rc = launch_pack_bf16(v->p(k.proj_w), wb + W.proj, DD, s))) return rc;
+        if ((rc = launch_pack_bf16(v->p(k.fc1_w), wb + W.fc1, 4 * DD, s))) return rc;
+        if ((rc = launch_pack_bf16(v->p(k.fc2_w), wb + W.fc2, 4 * DD, s))) return rc;
+    }
+    v->wbf_valid = true;
+    return ORBIT_OK;
+}
+
+// With bf16 (a plan under orbit_vit_enable_bf16, tape == nullptr) the four token GEMMs of every block run on vit_gemm_bf16_kernel;
+// everything else, the residual stream included, is the fp32 kernels in the same buffers.
 int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta, float* feats,
                      void* workspace, char* tape, hipStream_t s) {
+    const bool bf16 = v->bf16_enabled;
+    if (bf16 && tape) return set_err(ORBIT_ERR_ARG, "vit_forward: a bf16 plan (orbit_vit_enable_bf16) has no taped forward");
+    const VitWt W = vit_wt(v);
+    if (bf16)
+        if (int rc = vit_ensure_wbf(v, s)) return rc;
     const VitWs L = vit_ws(v, B, false);
     const VitTape T = vit_tape(v, B);
     const int D = v->D, N = v->N, M = B * N;
@@ -1445,6 +1667,17 @@ int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* fi
         const float *g, *be;
         ln_params(k.norm1_w, k.norm1_b, 2 * i, &g, &be);
         if ((rc = launch_layernorm(x, D, h, D, M, D, g, be, v->eps, s))) return rc;
+        if (bf16) {
+            const unsigned short* wb = v->d_wbf + i * W.block;
+            if ((rc = launch_gemm_bf16<EPI_BIAS>({h, wb + W.qkv, v->p(k.qkv_b), nullptr, big, M, 3 * D, D}, "qkv", s))) return rc;
+            if ((rc = launch_attention(big, h, B, N, D, v->heads, s))) return rc;
+            if ((rc = launch_gemm_bf16<EPI_RESIDUAL>({h, wb + W.proj, v->p(k.proj_b), x, x, M, D, D}, "proj", s))) return rc;
+            ln_params(k.norm2_w, k.norm2_b, 2 * i + 1, &g, &be);
+            if ((rc = launch_layernorm(x, D, h, D, M, D, g, be, v->eps, s))) return rc;
+            if ((rc = launch_gemm_bf16<EPI_GELU>({h, wb + W.fc1, v->p(k.fc1_b), nullptr, big, M, 4 * D, D}, "fc1", s))) return rc;
+            if ((rc = launch_gemm_bf16<EPI_RESIDUAL>({big, wb + W.fc2, v->p(k.fc2_b), x, x, M, D, 4 * D}, "fc2", s))) return rc;
+            continue;
+        }
         GemmArgs qkv{h, v->p(k.qkv_w), v->p(k.qkv_b), nullptr, nullptr, qkvb, M, 3 * D, D};
         if ((rc = launch_gemm<EPI_BIAS>(qkv, "qkv", s))) return rc;
         if ((rc = launch_attention(qkvb, h, B, N, D, v->heads, s))) return rc;
@@ -1589,16 +1822,30 @@ int orbit_vit_forward(orbit_vit_t* v, const float* frames, int B, const float* f
 }
 
 // ---- FiLM gradients of the frozen network ----------------------------------------------------------------------------
+// opt-in bf16 token GEMMs (inference only): a flag on this plan, nothing is allocated here
+int orbit_vit_enable_bf16(orbit_vit_t* v) {
+    ORBIT_REQUIRE(v, "vit_enable_bf16: null pointer");
+    ORBIT_REQUIRE(!v->backward_enabled && !v->weight_backward_enabled, "vit_enable_bf16: %s has orbit_vit_enable_backward / "
+                  "orbit_vit_enable_weight_backward set; bf16 is an inference mode (the training paths are fp32 only)", v->name.c_str());
+    v->bf16_enabled = true;
+    return ORBIT_OK;
+}
+int orbit_vit_bf16_enabled(const orbit_vit_t* v) { return v && v->bf16_enabled ? 1 : 0; }
+
 int orbit_vit_enable_backward(orbit_vit_t* v) {
     ORBIT_REQUIRE(v, "vit_enable_backward: null pointer");
+    ORBIT_REQUIRE(!v->bf16_enabled, "vit_enable_backward: %s is a bf16 inference plan (orbit_vit_enable_bf16)", v->name.c_str());
     v->backward_enabled = true;  // (read by forward_only() of the patch-16 plans only)
     return ORBIT_OK;
 }
 // weight gradients of a patch-16 plan (orbit_vit_backward_params); a patch-32 plan has them already
 int orbit_vit_enable_weight_backward(orbit_vit_t* v) {
     ORBIT_REQUIRE(v, "vit_enable_weight_backward: null pointer");
+    ORBIT_REQUIRE(!v->bf16_enabled, "vit_enable_weight_backward: %s is a bf16 inference plan (orbit_vit_enable_bf16)",
+                  v->name.c_str());
+    v->weight_backward_enabled = true;  // (a patch-32 plan has the gradients anyway: remembered for orbit_vit_enable_bf16's refusal)
     if (v->patch == VIT_PATCH) return ORBIT_OK;
-    v->backward_enabled = true, v->weight_backward_enabled = true;
+    v->backward_enabled = true;
     return ORBIT_OK;
 }
 size_t orbit_vit_tape_bytes(const orbit_vit_t* v, int B) {
@@ -1693,6 +1940,33 @@ int orbit_op_vit_linear(const float* x, const float* w, const float* bias, const
     if (epilogue == EPI_GELU) return launch_gemm<EPI_GELU>(a, "op_linear_gelu", s, tile_rows);
     if (epilogue == EPI_RESIDUAL) return launch_gemm<EPI_RESIDUAL>(a, "op_linear_residual", s, tile_rows);
     return launch_gemm<EPI_BIAS>(a, "op_linear", s, tile_rows);
+}
+
+int orbit_op_vit_pack_bf16(const float* w, uint16_t* out, size_t numel, orbit_stream_t stream) {
+    ORBIT_REQUIRE(w && out, "op_vit_pack_bf16: null pointer");
+    ORBIT_REQUIRE(numel > 0 && numel < ((size_t)1 << 40), "op_vit_pack_bf16: bad numel %zu", numel);
+    ORBIT_REQUIRE(((uintptr_t)w & 3) == 0 && ((uintptr_t)out & 1) == 0, "op_vit_pack_bf16: w must be 4-byte and out 2-byte aligned");
+    return launch_pack_bf16(w, out, numel, (hipStream_t)stream);
+}
+
+// the conventions of orbit_op_vit_linear; w_bf16 is [N][K] bf16 (orbit_op_vit_pack_bf16), K a multiple of 64
+int orbit_op_vit_linear_bf16(const float* x, const uint16_t* w_bf16, const float* bias, const float* residual, float* y, int M,
+                             int N, int K, int epilogue, int tile_rows, orbit_stream_t stream) {
+    ORBIT_REQUIRE(x && w_bf16 && y, "op_vit_linear_bf16: null pointer");
+    ORBIT_REQUIRE(M > 0 && M <= VIT_MAX_B * VIT_N && N > 0 && K > 0, "op_vit_linear_bf16: bad shape M=%d N=%d K=%d", M, N, K);
+    ORBIT_REQUIRE(N % G_BN == 0 && K % GB_BK == 0, "op_vit_linear_bf16: N must be a multiple of %d and K of %d, got M=%d N=%d K=%d",
+                  G_BN, GB_BK, M, N, K);
+    ORBIT_REQUIRE(epilogue == EPI_BIAS || epilogue == EPI_GELU || epilogue == EPI_RESIDUAL,
+                  "op_vit_linear_bf16: epilogue must be 0 (bias), 1 (erf-GELU) or 2 (residual), got %d", epilogue);
+    ORBIT_REQUIRE((epilogue == EPI_RESIDUAL) == (residual != nullptr), "op_vit_linear_bf16: residual goes with epilogue 2 only");
+    ORBIT_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w_bf16 & 15) == 0, "op_vit_linear_bf16: x and w_bf16 must be 16-byte aligned");
+    ORBIT_REQUIRE(((uintptr_t)y & 3) == 0 && ((uintptr_t)bias & 3) == 0 && ((uintptr_t)residual & 3) == 0,
+                  "op_vit_linear_bf16: y, bias and residual must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const GemmBf16Args a{x, w_bf16, bias, residual, y, M, N, K};
+    if (epilogue == EPI_GELU) return launch_gemm_bf16<EPI_GELU>(a, "op_linear_gelu", s, tile_rows);
+    if (epilogue == EPI_RESIDUAL) return launch_gemm_bf16<EPI_RESIDUAL>(a, "op_linear_residual", s, tile_rows);
+    return launch_gemm_bf16<EPI_BIAS>(a, "op_linear", s, tile_rows);
 }
 
 // patch: 32 (7 x 7 patches, 50 token rows per frame) or 16 (14 x 14, 197)

@@ -93,6 +93,11 @@ def build_parser():
                    help="vit_*_16* extractors only, ignored elsewhere: opt in to the native gradients of every parameter of the "
                         "transformer at 197 tokens (implies what --vit16_native_backward admits, and admits --learn_extractor, "
                         "with or without --with_lite / --adapt_features)")
+    p.add_argument("--vit_bf16", action="store_true",
+                   help="vit_* extractors (all six), test modes only: run the qkv / proj / fc1 / fc2 GEMMs of the transformer with "
+                        "bf16 operands and fp32 accumulation (VisionTransformer.bf16_inference; everything else stays fp32). A "
+                        "documented precision trade, off by default; refused with a training mode and with the finetuner's "
+                        "--learn_extractor / --adapt_features; ignored with a note for the other extractors")
     p.add_argument("--effnetv2_native_backward", action="store_true",
                    help="efficientnet_v2_s: opt in to the native FiLM gradients through the FROZEN network (--adapt_features "
                         "training, with or without --with_lite; the multi-step finetuner's --adapt_features). --learn_extractor "
@@ -387,13 +392,23 @@ def verify_args(args):
             sys.exit("error: --data_path %s: --mode %s needs the %s split, and %s is not a directory"
                      % (args.data_path, args.mode, split, path))
     fe = args.feature_extractor
+    multistep = getattr(args, "personalize_num_grad_steps", None) is not None
+    if getattr(args, "vit_bf16", False):
+        if not fe.startswith("vit_"):
+            print("note: --vit_bf16 is ignored for --feature_extractor %s (bf16 token GEMMs exist for the vit_* extractors only)" % fe)
+            args.vit_bf16 = False
+        elif "train" in args.mode:
+            sys.exit("error: --vit_bf16 is an inference mode (bf16 token GEMMs have no backward): use --mode test, got --mode %s"
+                     % args.mode)
+        elif multistep and (args.learn_extractor or args.adapt_features):
+            sys.exit("error: --vit_bf16 is an inference mode: the finetuner's --learn_extractor / --adapt_features send gradients "
+                     "through the extractor, which a bf16 plan refuses")
     spec = FROZEN_EXTRACTORS.get(fe)
     if spec is None:
         return
     args.frame_norm_method = spec.frame_norm
     if spec.frame_size is not None and args.frame_size != spec.frame_size:
         sys.exit("error: --feature_extractor %s needs --frame_size %d (got %d)" % (fe, spec.frame_size, args.frame_size))
-    multistep = getattr(args, "personalize_num_grad_steps", None) is not None
     scope, flag, _ = opted_in(args, spec)
     if scope == "all":
         pass  # native gradients of every parameter: everything the other extractors train is admitted
@@ -558,6 +573,8 @@ class Learner:
         spec = FROZEN_EXTRACTORS.get(a.feature_extractor)
         for attr in opted_in(a, spec)[2] if spec else ():
             setattr(self.model.feature_extractor, attr, True)
+        if getattr(a, "vit_bf16", False):  # (verify_args cleared it for the other extractors)
+            self.model.feature_extractor.bf16_inference = True
         self.model._set_device(self.device)
         self.model._send_to_device()
 
@@ -1059,6 +1076,8 @@ class Learner:
                  "personalise_ms": mean_ci([r["personalise_ms"] for r in records]),
                  "inference_ms_per_frame": mean_ci([ms for r in records for ms in r["inference_ms"]]),
                  "num_tasks": len(records), "world_size": self.world, "orbit_metrics": metrics.report()}
+        if a.feature_extractor.startswith("vit_"):  # the precision of the transformer's token GEMMs (--vit_bf16)
+            stats["vit_precision"] = "bf16" if getattr(a, "vit_bf16", False) else "fp32"
         if prefetch is not None:
             stats.update({"target_frames": sum(r["frames"] for r in records), "wall_s": wall, "data_root": root})
             stats.update(self.ingest_stats(prefetch, root))

@@ -342,14 +342,17 @@ class HipNetwork(nn.Module):
     _grad_scope = "all"
     _refusal_none = _refusal_film = None
 
+    def _grad_requested(self, film=None):
+        """autograd is on and one of the network's own parameters or the FiLM vectors requires a gradient"""
+        return torch.is_grad_enabled() and (
+            film is not None and (film[0].requires_grad or film[1].requires_grad)
+            or any(own is not None and own.requires_grad for _, _, _, own in self._leaves))
+
     def wants_grad(self, film=None):
         """True when a forward issued now has to record a tape: autograd is on and either one of the network's own
         parameters or the FiLM vectors require a gradient. Raises NotImplementedError where the network's gradient scope does
         not cover what requires one."""
-        if not torch.is_grad_enabled():
-            return False
-        if not (film is not None and (film[0].requires_grad or film[1].requires_grad)
-                or any(own is not None and own.requires_grad for _, _, _, own in self._leaves)):
+        if not self._grad_requested(film):
             return False
         scope = self._grad_scope
         if scope == "none":
@@ -682,7 +685,13 @@ class VisionTransformer(HipNetwork):
     (orbit_vit_enable_backward on the plan); any other parameter requiring a gradient is refused by name - unless
     `native_weight_backward_patch16 = True` (also ignored by the patch-32 models, and implying the above): then every parameter
     that requires a gradient gets it from orbit_vit_backward_params at 197 tokens (orbit_vit_enable_weight_backward on the
-    plan; --learn_extractor). Either attribute may be set after a plan exists and after inference forwards."""
+    plan; --learn_extractor). Either attribute may be set after a plan exists and after inference forwards.
+
+    `bf16_inference = True` (set per instance; learner flag --vit_bf16; all six models) is a second INFERENCE mode, a documented
+    precision trade that is off by default: the forward runs on a plan of its own under orbit_vit_enable_bf16, whose qkv / proj /
+    fc1 / fc2 GEMMs take bf16 operands with fp32 accumulation while everything else stays fp32 (include/orbit_hip.h). A forward
+    that needs a gradient on such a module - FiLM vector or parameter, under any of the four opt-ins above - raises
+    NotImplementedError naming the attribute before anything is launched."""
 
     _api = "vit"
     _probe_size = _frame_size = VIT_FRAME_SIZE
@@ -693,6 +702,31 @@ class VisionTransformer(HipNetwork):
     native_backward_patch16 = False  # the patch-16 models' opt-in (learner flag --vit16_native_backward): FiLM gradients
     # the patch-16 models' second opt-in (learner flag --vit16_native_weight_backward): weight gradients too
     native_weight_backward_patch16 = False
+    bf16_inference = False  # opt-in (learner flag --vit_bf16): bf16 token GEMMs with fp32 accumulation, inference only
+
+    _refusal_bf16 = ("%(name)s: bf16_inference = True is an inference mode (bf16 token GEMMs have no taped forward and no "
+                     "backward); run it under torch.no_grad() with frozen parameters, or set bf16_inference = False to train")
+
+    def wants_grad(self, film=None):
+        # refused before a plan is built or the device asked for, whichever native-backward opt-in is set
+        if self.bf16_inference and self._grad_requested(film):
+            raise NotImplementedError(self._refusal_bf16 % {"name": self.native_name})
+        return super().wants_grad(film)
+
+    def forward(self, x, film=None, out=None, check_sync=True):
+        if self.bf16_inference:  # (the refusal above, before the device is asked for)
+            self.wants_grad(self._resolve_film(film))
+        return super().forward(x, film=film, out=out, check_sync=check_sync)
+
+    def _plan_key(self, H, W, trainable):
+        # a bf16 plan is a plan of its own: flipping the attribute never turns an fp32 plan (or its features) into a bf16 one
+        return super()._plan_key(H, W, trainable) + (("bf16",) if self.bf16_inference else ())
+
+    def _new_plan(self, H, W, trainable, precision=None):
+        plan = super()._new_plan(H, W, trainable)
+        if precision == "bf16":
+            _lib.check(_lib.load().orbit_vit_enable_bf16(plan.handle), "orbit_vit_enable_bf16")
+        return plan
 
     def _leaf_shape(self, key, numel):
         # (cls_token is the first key: its size is the embedding width D)

@@ -25,6 +25,16 @@ models) at a LITE-sized batch of 16 frames, and the profiler's per-kernel rows o
 the step's kernel time - with the attention backward's time relative to the attention forward's on the same batch.
 
     python tools/vit_bench.py --train_film --models vit_s_16,vit_b_16,vit_b_16_clip
+
+--precision bf16 runs the same inference report on the opt-in bf16 plan (VisionTransformer.bf16_inference: qkv / proj / fc1 / fc2
+on v_mfma_f32_32x32x16_bf16, everything else fp32); the token GEMMs' TF/s are then a fraction of the 2 500 TF dense bf16 peak.
+--compare_precision runs one resident task on both plans of one model and prints the largest feature difference, the largest
+logit difference and the argmax agreement. --gemm_shapes times the bf16 and the fp32 token GEMM on the eight ViT-S / ViT-B layer
+shapes at M = 39 400 rows (200 frames of 197 tokens) from the per-launch event records.
+
+    python tools/vit_bench.py --precision bf16 --models vit_s_32,vit_b_32,vit_b_32_clip,vit_s_16,vit_b_16,vit_b_16_clip
+    python tools/vit_bench.py --compare_precision --models vit_s_32,vit_b_16
+    python tools/vit_bench.py --gemm_shapes
 """
 import argparse
 import ctypes
@@ -43,6 +53,7 @@ from orbit_dataset_amd import _lib, synthetic  # noqa: E402
 from orbit_dataset_amd.model.few_shot_recognisers import SingleStepFewShotRecogniser  # noqa: E402
 
 PEAK_TF = 155.0  # fp32 MFMA, measured (v_mfma_f32_32x32x2_f32)
+PEAK_TF_BF16 = 2500.0  # dense bf16 MFMA (v_mfma_f32_32x32x16_bf16), the specification's figure
 
 
 def _samples(fn, steps, warmup):
@@ -64,9 +75,10 @@ def _time(fn, steps, warmup):
     return statistics.median(_samples(fn, steps, warmup))
 
 
-def _model(name, adapt, classifier):
+def _model(name, adapt, classifier, bf16=False):
     m = SingleStepFewShotRecogniser(name, adapt, classifier, 1, 200, False, 16, 1.0)
     synthetic.init_parameters_(m)
+    m.feature_extractor.bf16_inference = bool(bf16)
     m._set_device("cuda:0")
     m._send_to_device()
     m.set_test_mode(True)
@@ -267,6 +279,78 @@ def main_train_film(a):
     print(json.dumps(result))
 
 
+def main_compare_precision(a):
+    """one resident task through the fp32 plan and the bf16 plan of the same module (same parameters): features of all 400 frames,
+    logits of the 200 query frames"""
+    result = {"metric": "vit_bf16_vs_fp32", "task": "5-way, 200 support + 200 query frames, 224x224, proto head", "models": {}}
+    for name in a.models.split(","):
+        task = synthetic.make_task_on_device(0, 5, 5, 8, 200, 224, 1, "cuda:0")
+        model = _model(name, False, "proto")
+        fe = model.feature_extractor
+        frames = torch.cat((task["context_clips"].flatten(end_dim=1), task["target_clips"].flatten(end_dim=1)))
+        out = {}
+        for precision in ("fp32", "bf16"):
+            fe.bf16_inference = precision == "bf16"
+            with torch.no_grad():
+                feats = torch.cat([fe(frames[i:i + 200]) for i in range(0, frames.shape[0], 200)])
+                model.personalise(task["context_clips"], task["context_labels"])
+                logits = model.predict(task["target_clips"]).clone()
+                model._reset()
+            out[precision] = (feats, logits)
+        (f32, l32), (f16, l16) = out["fp32"], out["bf16"]
+        result["models"][name] = {
+            "max_abs_feature": round(f32.abs().max().item(), 4), "max_abs_feature_diff": round((f16 - f32).abs().max().item(), 5),
+            "max_abs_logit": round(l32.abs().max().item(), 3), "max_abs_logit_diff": round((l16 - l32).abs().max().item(), 4),
+            "argmax_agreement": round((l16.argmax(1) == l32.argmax(1)).float().mean().item(), 4), "query_frames": l32.shape[0]}
+        del model, fe
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
+GEMM_M = 39400  # 200 frames of 197 tokens
+
+
+def main_gemm_shapes(a):
+    """orbit_op_vit_linear and orbit_op_vit_linear_bf16 (tile rule of the forward) on the eight layer shapes: mean ms per launch of
+    --steps launches after --warmup, from the per-launch event records"""
+    lib = _lib.load()
+    M = GEMM_M
+    result = {"metric": "vit_gemm_bf16_vs_fp32", "M": M, "peak_tflops": {"fp32": PEAK_TF, "bf16": PEAK_TF_BF16}, "shapes": {}}
+    for D in (384, 768):
+        for tag, K, N, epi in (("qkv", D, 3 * D, 0), ("proj", D, D, 2), ("fc1", D, 4 * D, 1), ("fc2", 4 * D, D, 2)):
+            x = torch.randn(M, K, device="cuda:0")
+            w = torch.randn(N, K, device="cuda:0") / K ** 0.5
+            b = torch.randn(N, device="cuda:0")
+            res = torch.randn(M, N, device="cuda:0") if epi == 2 else None
+            y = torch.empty(M, N, device="cuda:0")
+            wb = torch.empty(N, K, dtype=torch.int16, device="cuda:0")
+            _lib.check(lib.orbit_op_vit_pack_bf16(_lib.dptr(w), ctypes.c_void_p(wb.data_ptr()), w.numel(), _lib.stream_handle()),
+                       "orbit_op_vit_pack_bf16")
+
+            def fp32():
+                _lib.check(lib.orbit_op_vit_linear(_lib.dptr(x), _lib.dptr(w), _lib.dptr(b), _lib.dptr(res), _lib.dptr(y), M, N, K,
+                                                   epi, 0, _lib.stream_handle()), "orbit_op_vit_linear")
+
+            def bf16():
+                _lib.check(lib.orbit_op_vit_linear_bf16(_lib.dptr(x), ctypes.c_void_p(wb.data_ptr()), _lib.dptr(b), _lib.dptr(res),
+                                                        _lib.dptr(y), M, N, K, epi, 0, _lib.stream_handle()),
+                           "orbit_op_vit_linear_bf16")
+            r = {"K": K, "N": N}
+            for what, fn in (("fp32", fp32), ("bf16", bf16)):
+                for _ in range(a.warmup):
+                    fn()
+
+                def many():
+                    for _ in range(a.steps):
+                        fn()
+                rows = {k: v for k, v in _kernel_rows(many).items() if k.startswith("vit_op_linear")}
+                (row, (launches, ms)), = rows.items()
+                r[what] = {"row": row, "ms": round(ms / launches, 4), "tflops": round(2.0 * M * N * K / (ms / launches) / 1e9, 1)}
+            r["speedup"] = round(r["fp32"]["ms"] / r["bf16"]["ms"], 2)
+            result["shapes"]["%s_D%d" % (tag, D)] = r
+    print(json.dumps(result))
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--steps", type=int, default=10)
@@ -276,19 +360,31 @@ def main(argv=None):
     p.add_argument("--train", action="store_true", help="the training step and the weight-gradient GEMMs instead")
     p.add_argument("--train_film", action="store_true",
                    help="the FiLM-gradient step of the frozen network at a batch of %d frames instead (all six models)" % FILM_BATCH)
+    p.add_argument("--precision", choices=("fp32", "bf16"), default="fp32",
+                   help="the inference report on the fp32 plan (default) or on the opt-in bf16 plan")
+    p.add_argument("--compare_precision", action="store_true",
+                   help="one resident task on both plans of each model: feature / logit differences and argmax agreement instead")
+    p.add_argument("--gemm_shapes", action="store_true",
+                   help="the bf16 and the fp32 token GEMM on the eight layer shapes at M = %d instead" % GEMM_M)
     a = p.parse_args(argv)
     _lib.require_gpu()
     torch.cuda.set_device(0)
+    if a.compare_precision:
+        return main_compare_precision(a)
+    if a.gemm_shapes:
+        return main_gemm_shapes(a)
     if a.train_film:
         return main_train_film(a)
     if a.train:
         return main_train(a)
-    result = {"metric": "vit_task_ms", "task": "5-way, 200 support + 200 query frames, 224x224", "peak_tflops": PEAK_TF,
-              "models": {}}
+    bf16 = a.precision == "bf16"
+    peak = PEAK_TF_BF16 if bf16 else PEAK_TF  # of the token GEMMs; the floor below stays the fp32 one (what the default path can reach)
+    result = {"metric": "vit_task_ms", "task": "5-way, 200 support + 200 query frames, 224x224", "precision": a.precision,
+              "peak_tflops": peak, "models": {}}
     for name in a.models.split(","):
         task = synthetic.make_task_on_device(0, 5, 5, 8, 200, 224, 1, "cuda:0")
         r = {}
-        proto = _model(name, False, "proto")
+        proto = _model(name, False, "proto", bf16)
         run = _task_fn(proto, task)
         r["proto_ms"] = round(_time(run, a.steps, a.warmup), 3)
         r["query_frames_per_s"] = round(200.0 / (r["proto_ms"] / 2) * 1e3, 1)  # (support and query passes are the same size)
@@ -297,12 +393,12 @@ def main(argv=None):
         g = fam.get("gemm", {"ms": 0.0, "flops": 0.0})
         tf = g["flops"] / g["ms"] / 1e9 if g["ms"] else 0.0
         r["gemm_tflops"] = round(tf, 2)
-        r["gemm_fraction_of_peak"] = round(tf / PEAK_TF, 3)
+        r["gemm_fraction_of_peak"] = round(tf / peak, 3)
         macs = proto.feature_extractor.macs_per_frame(224, 224)
         r["task_tflop"] = round(2 * macs * 400 / 1e12, 3)
         r["task_floor_ms"] = round(2 * macs * 400 / (PEAK_TF * 1e12) * 1e3, 2)
         del proto
-        cnaps = _model(name, True, "versa")
+        cnaps = _model(name, True, "versa", bf16)
         r["cnaps_ms"] = round(_time(_task_fn(cnaps, task), a.steps, a.warmup), 3)
         del cnaps
         r["torch_linear_m10000"] = _torch_linear(384 if name.startswith("vit_s_") else 768, a.steps, a.warmup)
