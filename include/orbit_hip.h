@@ -568,6 +568,22 @@ int orbit_op_mbconv_front(const float* x, const float* w1, const float* scale1, 
                           const float* wdw, const float* scale2, const float* shift2, float* y, float* pool_partial,
                           int B, int H, int W, int Cin, int mid, int K, int stride, int pad_top, int pad_left,
                           int Ho, int Wo, orbit_stream_t stream);
+/* The tiling of the row-streaming front on an H x W input map (host only; an argument error for every shape
+ * orbit_op_mbconv_front refuses, for which orbit_op_mbconv_front_partials returns 0). The Ho x Wo output map is cut into
+ * `bands` bands of `band_rows` output rows and `strips` strips of `strip_w` output columns; tiles = strips * bands, and tile t of a
+ * frame covers band t / strips and strip t % strips, clipped to the map: rows [band * band_rows, min(Ho, (band + 1) * band_rows))
+ * and columns [strip * strip_w, min(Wo, (strip + 1) * strip_w)). pool_partial[b][t] / stats_partial[b * tiles + t] hold the sums
+ * over that rectangle. exact = 1: the launch takes a branch-free instantiation (strips tile Wo, every band is a whole number of
+ * steps, mid % 32 is 0 or 16); 0: the predicated one. */
+int orbit_op_mbconv_front_plan(int H, int W, int Cin, int mid, int K, int stride, int* strips, int* bands, int* strip_w,
+                               int* band_rows, int* exact);
+/* The train-mode BatchNorm form of orbit_op_mbconv_front: scale1 / shift1 are the first BatchNorm's batch-statistics fold, the second
+ * BatchNorm is NOT applied: y_raw NHWC [B][Ho][Wo][mid] receives the depthwise outputs, and stats_partial [B * tiles][2][mid]
+ * (required) the per-tile column sums ([.][0][c]) and sums of squares ([.][1][c]) of those outputs - the partial layout
+ * orbit_op_bn_stats_from_partials reads with nblk = B * tiles, M = B * Ho * Wo. */
+int orbit_op_mbconv_front_raw(const float* x, const float* w1, const float* scale1, const float* shift1, const float* wdw,
+                              float* y_raw, float* stats_partial, int B, int H, int W, int Cin, int mid, int K, int stride,
+                              int pad_top, int pad_left, int Ho, int Wo, orbit_stream_t stream);
 /* The stem form of the same kernel (timm tf_efficientnet_b0: conv_stem -> bn1 -> SiLU -> blocks.0.0.conv_dw -> bn1 ->
  * SiLU, reached from model/feature_extractors.py:39-43): frames NCHW [B][3][FH][FW], w_stem torch [mid][3][3][3]
  * (3x3 stride 2, padding spad_top / spad_left before, the rest after), depthwise 3x3 stride 1 on the stem's H x W output
@@ -577,6 +593,9 @@ int orbit_op_stem_dw_front(const float* frames, const float* w_stem, const float
                            const float* wdw, const float* scale2, const float* shift2, float* y, float* pool_partial,
                            int B, int FH, int FW, int spad_top, int spad_left, int H, int W, int mid, int pad_top,
                            int pad_left, int Ho, int Wo, orbit_stream_t stream);
+/* The tiling of orbit_op_stem_dw_front on the stem's H x W output grid (host only; an argument error for a shape that entry
+ * refuses): strips, bands, tile rectangles and `exact` as orbit_op_mbconv_front_plan reports them, with Ho = H, Wo = W. */
+int orbit_op_stem_dw_front_plan(int H, int W, int mid, int* strips, int* bands, int* strip_w, int* band_rows, int* exact);
 
 /* ---- Versa / Mahalanobis heads -----------------------------------------------------------
  * y[r][o] = act(x[r] . W[o] + b[o]) (+ residual[r][o]) for a few rows r < R <= 16 (one row per class): the layers of

@@ -118,6 +118,9 @@ _SIGNATURES = {
     "orbit_op_mbconv_front_partials": (c_int, [c_int] * 6),
     "orbit_op_stem_dw_front_partials": (c_int, [c_int] * 3),
     "orbit_op_stem_dw_front": (c_int, [P] * 9 + [c_int] * 12 + [P]),
+    "orbit_op_mbconv_front_plan": (c_int, [c_int] * 6 + [POINTER(c_int)] * 5),
+    "orbit_op_stem_dw_front_plan": (c_int, [c_int] * 3 + [POINTER(c_int)] * 5),
+    "orbit_op_mbconv_front_raw": (c_int, [P] * 7 + [c_int] * 11 + [P]),
     "orbit_dense_rows": (c_int, [P, c_int, c_int, P, P, c_int, c_int, P, P, P]),
     "orbit_spd_inverse": (c_int, [P, P, c_int, c_int, P]),
     "orbit_mahalanobis_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

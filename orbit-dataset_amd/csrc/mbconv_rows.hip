@@ -453,6 +453,13 @@ static bool rows_geom(int H, int W, int Cin, int mid, int K, int stride, int Ho,
     return true;
 }
 
+// branch-free stores (the EXACT instantiations) need: strips tile the width exactly, every band is a whole number of steps, and
+// the last 32-channel chunk is full or exactly half full (a missing quad duplicates the quad 16 channels below)
+static bool rows_exact(const RowsGeom& g, int mid, int Ho, int Wo) {
+    return g.strips * g.SWo == Wo && Ho % g.TO == 0 && g.band_rows % g.TO == 0 && (mid % 32 == 0 || mid % 32 == 16) &&
+           g.SWo % g.NOUT == 0;
+}
+
 bool mbconv_rows_supported(int H, int W, int Cin, int mid, int K, int stride) {
     RowsGeom g;
     const int Ho = cdiv(H, stride), Wo = cdiv(W, stride);
@@ -513,10 +520,7 @@ int launch_mbconv_rows(const float* x, const float* w1, const float* sc1, const 
         kern<<<grid, 256, lds, s>>>(p);                                                                 \
     } while (0)
     const int ng = Cin / 8;
-    // branch-free stores need: strips tile the width exactly, every band is a whole number of steps, and the last 32-channel
-    // chunk is full or exactly half full (a missing quad duplicates the quad 16 channels below)
-    const bool exact = g.strips * g.SWo == Wo && Ho % g.TO == 0 && g.band_rows % g.TO == 0 && (mid % 32 == 0 || mid % 32 == 16) &&
-                       g.SWo % g.NOUT == 0;
+    const bool exact = rows_exact(g, mid, Ho, Wo);
     const bool bf3 = !raw_stats && (get_option("conv_bf3") & 2) != 0;  // (opt-in bit 2; the exact-tiling instantiations only)
 #define ORBIT_MBR3X(KK, SS, TO_, NOUT_, NG_, SPR_)                    \
     do {                                                              \
@@ -821,6 +825,9 @@ static bool stem_rows_geom(int H, int W, int mid, int K, int stride, StemRowsGeo
     g.bands = cdiv(H, g.band_rows);
     return true;
 }
+// branch-free stores: strips tile the width exactly and every band is a whole number of 2-row steps
+static bool stem_rows_exact(const StemRowsGeom& g, int H, int W) { return g.strips * g.SWo == W && H % 2 == 0 && g.band_rows % 2 == 0; }
+
 bool stem_rows_supported(int H, int W, int mid, int K, int stride) {
     StemRowsGeom g;
     return stem_rows_geom(H, W, mid, K, stride, g);
@@ -848,8 +855,7 @@ int launch_stem_rows(const float* frames, const float* w1_packed, const float* s
     const double pix = (double)B * H * W;
     const int rec = prof_start("stem_rows", 2.0 * pix * 32 * 27 + 2.0 * pix * 32 * 9,
                                4.0 * ((double)B * 3 * FH * FW + pix * 32), s, 2.0 * pix * 32);
-    // branch-free stores: strips tile the width exactly and every band is a whole number of 2-row steps
-    if (g.strips * g.SWo == W && H % 2 == 0 && g.band_rows % 2 == 0) stem_rows_kernel<true><<<grid, 256, lds, s>>>(p, w1_packed, sc1, sh1);
+    if (stem_rows_exact(g, H, W)) stem_rows_kernel<true><<<grid, 256, lds, s>>>(p, w1_packed, sc1, sh1);
     else stem_rows_kernel<false><<<grid, 256, lds, s>>>(p, w1_packed, sc1, sh1);
     prof_stop(rec, s);
     ORBIT_LAUNCH_CHECK();
@@ -879,6 +885,15 @@ extern "C" int orbit_op_stem_dw_front_partials(int H, int W, int mid) {
     return stem_rows_supported(H, W, mid, 3, 1) ? stem_rows_tiles(H, W) : 0;
 }
 
+// the tiling of orbit_op_stem_dw_front on an H x W stem grid, and whether the launch takes the branch-free instantiation
+extern "C" int orbit_op_stem_dw_front_plan(int H, int W, int mid, int* strips, int* bands, int* strip_w, int* band_rows, int* exact) {
+    ORBIT_REQUIRE(strips && bands && strip_w && band_rows && exact, "op_stem_dw_front_plan: null pointer");
+    StemRowsGeom g;
+    ORBIT_REQUIRE(stem_rows_geom(H, W, mid, 3, 1, g), "op_stem_dw_front_plan: unsupported shape (H=%d W=%d mid=%d)", H, W, mid);
+    *strips = g.strips, *bands = g.bands, *strip_w = g.SWo, *band_rows = g.band_rows, *exact = stem_rows_exact(g, H, W) ? 1 : 0;
+    return ORBIT_OK;
+}
+
 // frames NCHW, w_stem torch [mid][3][3][3], wdw torch [mid][1][3][3]
 extern "C" int orbit_op_stem_dw_front(const float* frames, const float* w_stem, const float* scale1, const float* shift1,
                                       const float* wdw, const float* scale2, const float* shift2, float* y,
@@ -904,6 +919,19 @@ extern "C" int orbit_op_mbconv_front_partials(int H, int W, int Cin, int mid, in
     return mbconv_rows_supported(H, W, Cin, mid, K, stride) ? mbconv_rows_tiles(H, W, Cin, mid, K, stride) : 0;
 }
 
+// the tiling of orbit_op_mbconv_front / _raw on an H x W map, and whether the launch takes a branch-free (EXACT) instantiation
+extern "C" int orbit_op_mbconv_front_plan(int H, int W, int Cin, int mid, int K, int stride, int* strips, int* bands, int* strip_w,
+                                          int* band_rows, int* exact) {
+    ORBIT_REQUIRE(strips && bands && strip_w && band_rows && exact, "op_mbconv_front_plan: null pointer");
+    ORBIT_REQUIRE(stride >= 1, "op_mbconv_front_plan: stride = %d", stride);
+    RowsGeom g;
+    const int Ho = cdiv(H, stride), Wo = cdiv(W, stride);
+    ORBIT_REQUIRE(rows_geom(H, W, Cin, mid, K, stride, Ho, Wo, g),
+                  "op_mbconv_front_plan: unsupported shape (H=%d W=%d Cin=%d mid=%d K=%d s=%d)", H, W, Cin, mid, K, stride);
+    *strips = g.strips, *bands = g.bands, *strip_w = g.SWo, *band_rows = g.band_rows, *exact = rows_exact(g, mid, Ho, Wo) ? 1 : 0;
+    return ORBIT_OK;
+}
+
 // w1 torch [mid][Cin][1][1], wdw torch [mid][1][K][K]
 extern "C" int orbit_op_mbconv_front(const float* x, const float* w1, const float* scale1, const float* shift1,
                                      const float* wdw, const float* scale2, const float* shift2, float* y,
@@ -919,6 +947,25 @@ extern "C" int orbit_op_mbconv_front(const float* x, const float* w1, const floa
     if (rc == ORBIT_OK)
         rc = launch_mbconv_rows(x, w1, scale1, shift1, wp, scale2, shift2, y, pool_partial, B, H, W, Cin, mid, K, stride,
                                 pad_top, pad_left, Ho, Wo, s);
+    (void)hipFreeAsync(wp, s);
+    return rc;
+}
+
+// the train-mode form: raw depthwise outputs + the per-tile column sums / sums of squares the second BatchNorm's finalize reads
+extern "C" int orbit_op_mbconv_front_raw(const float* x, const float* w1, const float* scale1, const float* shift1,
+                                         const float* wdw, float* y_raw, float* stats_partial, int B, int H, int W, int Cin,
+                                         int mid, int K, int stride, int pad_top, int pad_left, int Ho, int Wo,
+                                         orbit_stream_t stream) {
+    ORBIT_REQUIRE(x && w1 && scale1 && shift1 && wdw && y_raw && stats_partial, "op_mbconv_front_raw: null pointer");
+    ORBIT_REQUIRE(mbconv_rows_supported(H, W, Cin, mid, K, stride),
+                  "op_mbconv_front_raw: unsupported shape (H=%d W=%d Cin=%d mid=%d K=%d s=%d)", H, W, Cin, mid, K, stride);
+    hipStream_t s = (hipStream_t)stream;
+    float* wp = nullptr;
+    ORBIT_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&wp), (size_t)mid * K * K * sizeof(float), s));
+    int rc = dwconv_pack_weights(wdw, wp, mid, K, s);
+    if (rc == ORBIT_OK)
+        rc = launch_mbconv_rows(x, w1, scale1, shift1, wp, nullptr, nullptr, y_raw, stats_partial, B, H, W, Cin, mid, K, stride,
+                                pad_top, pad_left, Ho, Wo, s, 0, true);
     (void)hipFreeAsync(wp, s);
     return rc;
 }
