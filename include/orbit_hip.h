@@ -269,6 +269,22 @@ int orbit_extractor_forward(orbit_extractor_t* fe, const float* frames, int B,
  * 1..2048 for the patch-16 plans (B * 197 * 4 D stays below 2^31); beyond it orbit_vit_workspace_bytes returns 0 and
  * orbit_vit_forward ORBIT_ERR_ARG. */
 int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out);
+/* Opt-in: the same six models on square frames of another side S = H = W, a multiple of the model's patch size, 32 <= S <= 512
+ * (ORBIT_ERR_ARG with the reason otherwise: non-square, not a multiple - naming the two nearest sizes -, below 32, above 512,
+ * unknown name). The parameters, their order and their numels are those of orbit_vit_create: pos_embed keeps its checkpoint
+ * shape [1][50 | 197][D]. With G = S / patch patches per side and g = 7 | 14, the table the forward adds is row 0 unchanged and
+ * rows 1..G^2 = F.interpolate(pos_embed[1:] as [1][D][g][g], size=(G, G), mode="bicubic", align_corners=False): cubic
+ * convolution with A = -0.75, source coordinate (i + 0.5) g / G - 0.5, four taps per axis clamped to [0, g - 1], no
+ * antialiasing (timm 0.6.12 resize_pos_embed; transformers' interpolate_pos_encoding=True). It is made by the first forward
+ * after a parameter upload in a plan-owned [G^2 + 1][D] buffer; every orbit_vit_load* invalidates it, orbit_vit_destroy frees
+ * it. Tokens per frame N = G^2 + 1, orbit_vit_macs_per_frame by its formula at that N; batch cap: the largest B with
+ * B * N <= 8192 * 50. At S = 224 the plan IS an orbit_vit_create plan: no resampled table, the same kernels with compile-time
+ * geometry, the same caps, and the backward entry points on the same terms. At any other S the plan is inference + FiLM only
+ * for good: orbit_vit_enable_backward, orbit_vit_enable_weight_backward, orbit_vit_train_forward, orbit_vit_backward and
+ * orbit_vit_backward_params return ORBIT_ERR_ARG naming the frame size before any launch or allocation, and the tape / backward
+ * workspace size queries return 0. orbit_vit_enable_bf16 is allowed. Attention runs on a streaming fp32 matrix-core kernel for
+ * every token count but 50 and 197; a frame's features do not depend on the batch it is in. */
+int orbit_vit_create_sized(const char* name, int H, int W, orbit_vit_t** out);
 void orbit_vit_destroy(orbit_vit_t* v);
 /* timm state_dict keys in timm's order: cls_token, pos_embed, patch_embed.proj.{weight,bias (not CLIP)}, norm_pre.* (CLIP),
  * blocks.{i}.{norm1, attn.qkv, attn.proj, norm2, mlp.fc1, mlp.fc2}.{weight,bias}, norm.{weight,bias} */
@@ -504,6 +520,16 @@ int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* b
 int orbit_op_vit_patch_embed_p(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,
                                const float* cls_token, float* tokens, int B, int D, int patch, int tile_rows,
                                orbit_stream_t stream);
+/* The same on square frames of side S (a multiple of `patch`, 32..512; the plans of orbit_vit_create_sized): frames NCHW
+ * [B][3][S][S], pos_embed the table AT that grid [(S / patch)^2 + 1][D] (orbit_op_vit_pos_resample), tokens
+ * [B][(S / patch)^2 + 1][D]. Always the runtime-geometry form of the GEMM: at S = 224 its result is bit for bit that of
+ * orbit_op_vit_patch_embed_p. B * ((S / patch)^2 + 1) at most 8192 * 50. */
+int orbit_op_vit_patch_embed_sized(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,
+                                   const float* cls_token, float* tokens, int B, int D, int patch, int S, int tile_rows,
+                                   orbit_stream_t stream);
+/* The position table of orbit_vit_create_sized: pos [g^2 + 1][D] (g = 7 or 14) -> out [G^2 + 1][D] (1 <= G <= 32, out != pos),
+ * row 0 copied, the rest torch's bicubic resample as stated there. D is 384 or 768. */
+int orbit_op_vit_pos_resample(const float* pos, float* out, int g, int G, int D, orbit_stream_t stream);
 /* LayerNorm over the D (384 or 768) values of each row; row r at x + r * x_stride / y + r * y_stride floats; y may alias x. */
 int orbit_op_vit_layernorm(const float* x, size_t x_stride, float* y, size_t y_stride, int rows, int D, const float* gamma,
                            const float* beta, float eps, orbit_stream_t stream);
@@ -514,6 +540,10 @@ int orbit_op_vit_attention(const float* qkv, float* out, int B, int D, int heads
  * models) runs QK^T and PV on the fp32 matrix cores with the padded keys 197..223 masked out of the softmax; qkv and out then
  * 16-byte aligned and B at most 2048. Any other token count is an argument error. */
 int orbit_op_vit_attention_tokens(const float* qkv, float* out, int B, int tokens, int D, int heads, orbit_stream_t stream);
+/* The same for ANY token count >= 1, always on the streaming kernel of the sized plans (at 50 and 197 too, where the plans keep
+ * the two kernels above): K and V pass through LDS in tiles of 32 keys under a running softmax, keys past tokens - 1 masked; a
+ * row's bits depend on the token count alone. qkv and out 16-byte aligned, B * tokens at most 8192 * 50. */
+int orbit_op_vit_attention_n(const float* qkv, float* out, int B, int tokens, int D, int heads, orbit_stream_t stream);
 /* The backward kernels of orbit_vit_backward one by one.
  * dx [M][K] = dy [M][N] . w [N][K] (w in the torch Linear layout; wt_scratch [K][N] receives its transpose, which the GEMM of
  * orbit_op_vit_linear then reads), optionally times GELU'(u) (u [M][K], the erf form: Phi(u) + u phi(u)) or plus residual [M][K]

@@ -64,6 +64,7 @@ _SIGNATURES = {
     "orbit_vit_workspace_bytes": (c_size_t, [P, c_int]),
     "orbit_vit_macs_per_frame": (c_double, [P]),
     "orbit_vit_forward": (c_int, [P, P, c_int, P, P, P, P, c_size_t, P]),
+    "orbit_vit_create_sized": (c_int, [c_char_p, c_int, c_int, POINTER(c_void_p)]),
     "orbit_vit_tape_bytes": (c_size_t, [P, c_int]),
     "orbit_vit_enable_backward": (c_int, [P]),
     "orbit_vit_enable_weight_backward": (c_int, [P]),
@@ -105,6 +106,9 @@ _SIGNATURES = {
     "orbit_op_vit_attention": (c_int, [P, P, c_int, c_int, c_int, P]),
     "orbit_op_vit_attention_tokens": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "orbit_op_vit_patch_embed_p": (c_int, [P] * 6 + [c_int] * 4 + [P]),
+    "orbit_op_vit_attention_n": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
+    "orbit_op_vit_pos_resample": (c_int, [P, P, c_int, c_int, c_int, P]),
+    "orbit_op_vit_patch_embed_sized": (c_int, [P] * 6 + [c_int] * 5 + [P]),
     "orbit_op_vit_linear_dgrad": (c_int, [P] * 6 + [c_int] * 4 + [P]),
     "orbit_op_vit_layernorm_bwd": (c_int, [P, c_size_t, P, c_size_t, P, c_float, P, P, c_size_t, c_int, c_int, P, P, P,
                                            c_size_t, P]),

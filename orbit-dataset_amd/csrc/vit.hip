@@ -29,6 +29,11 @@
 // at 197 tokens, with vit_attention197_bwd_kernel). orbit_vit_enable_weight_backward opens orbit_vit_backward_params for such a
 // plan as well: the patch filter gradient is the WX_PATCH16 form of vit_wgrad_kernel (16-float patch rows, M = 196 B, K = 768),
 // vit_token_bwd_kernel sums dpos over 197 token rows, and every Linear weight gradient runs at M = 197 B.
+// Other frame sizes (orbit_vit_create_sized: square, a multiple of the patch, 32..512; inference + FiLM only): the same forward
+// with the position table resampled to the plan's grid once per parameter upload (vit_pos_resample_kernel, torch's bicubic), the
+// patch GEMM's EPI_PATCH_RT / EPI_PATCH16_RT forms (frame side and patches per side from the arguments) and, at every token
+// count but 50 and 197, vit_attention_n_kernel (the 197-token scheme with K and V streamed through LDS under a running softmax).
+// A 224 plan launches what it launched before.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -68,7 +73,10 @@ typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 constexpr int G_BN = 128, G_BK = 32, G_THREADS = 256;
 // EPI_GELU_TAPE: EPI_GELU that also stores the pre-activation (aux); EPI_DGELU: times GELU'(u), u read through `residual`
 // EPI_PATCH16: EPI_PATCH for 16 x 16 patches (its own A gather and token-row geometry)
-enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_PATCH = 3, EPI_GELU_TAPE = 4, EPI_DGELU = 5, EPI_PATCH16 = 6 };
+// EPI_PATCH_RT / EPI_PATCH16_RT: the two patch forms with the frame side and the patches per side read from the arguments (the
+// plans of orbit_vit_create_sized at other frame sizes than 224); the patch size, and with it the k order, stays a constant
+enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESIDUAL = 2, EPI_PATCH = 3, EPI_GELU_TAPE = 4, EPI_DGELU = 5, EPI_PATCH16 = 6,
+       EPI_PATCH_RT = 7, EPI_PATCH16_RT = 8 };
 
 struct GemmArgs {
     const float* x;         // [M][K] token rows, or the NCHW frames (EPI_PATCH)
@@ -79,6 +87,7 @@ struct GemmArgs {
     float* y;
     int M, N, K;
     float* aux = nullptr;   // [M][N] pre-activation out (EPI_GELU_TAPE)
+    int side = 0, grid = 0; // frame side and patches per side (EPI_PATCH_RT / EPI_PATCH16_RT only; pos is then [grid^2 + 1][N])
 };
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
@@ -104,11 +113,23 @@ __device__ __forceinline__ const float* patch16_row_ptr(const float* frames, int
     return frames + (((size_t)b * 3 + c) * VIT_SIZE + ph * VIT16_PATCH + kh) * VIT_SIZE + pw * VIT16_PATCH + kw;
 }
 
+// the two gathers on square frames of any side (a multiple of the patch): LG = log2(patch), k = c*patch^2 + kh*patch + kw
+template <int LG>
+__device__ __forceinline__ const float* patch_rt_row_ptr(const float* frames, int m, int k, int side, int grid) {
+    const int np = grid * grid;
+    const int b = m / np, p = m - b * np;
+    const int ph = p / grid, pw = p - ph * grid;
+    const int c = k >> (2 * LG), kh = (k >> LG) & ((1 << LG) - 1), kw = k & ((1 << LG) - 1);
+    return frames + (((size_t)b * 3 + c) * side + (ph << LG) + kh) * side + (pw << LG) + kw;
+}
+
 // address of the 4 consecutive k of A row m (clamped into [0, M)) starting at k
 template <int EPI>
 __device__ __forceinline__ const float* a_row_ptr(const GemmArgs& a, int m, int k) {
     if (EPI == EPI_PATCH) return patch_row_ptr(a.x, m, k);
     if (EPI == EPI_PATCH16) return patch16_row_ptr(a.x, m, k);
+    if (EPI == EPI_PATCH_RT) return patch_rt_row_ptr<5>(a.x, m, k, a.side, a.grid);
+    if (EPI == EPI_PATCH16_RT) return patch_rt_row_ptr<4>(a.x, m, k, a.side, a.grid);
     return a.x + (size_t)m * a.K + k;
 }
 
@@ -165,7 +186,9 @@ __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
             // (16 x 16 patches: (c, kh) with kh even - two frame rows of 16 pixels per K step, the loader's chunk picks the row)
             const float* p = EPI == EPI_PATCH ? ap[i] + ((k0 >> 10) * VIT_SIZE + ((k0 >> 5) & 31)) * VIT_SIZE
                              : EPI == EPI_PATCH16 ? ap[i] + ((k0 >> 8) * VIT_SIZE + ((k0 >> 4) & 15)) * VIT_SIZE
-                                                  : ap[i] + k0;
+                             : EPI == EPI_PATCH_RT ? ap[i] + (size_t)((k0 >> 10) * a.side + ((k0 >> 5) & 31)) * a.side
+                             : EPI == EPI_PATCH16_RT ? ap[i] + (size_t)((k0 >> 8) * a.side + ((k0 >> 4) & 15)) * a.side
+                                                     : ap[i] + k0;
             ra[i] = *reinterpret_cast<const float4*>(p);
         }
 #pragma unroll
@@ -229,6 +252,13 @@ __global__ __launch_bounds__(G_THREADS) void vit_gemm_kernel(GemmArgs a) {
                 const int row = m0 + wm * (BM / 2) + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (row >= a.M) continue;
                 float v = (BLOCKED ? tot[i][j][r] : acc[i][j][r]) + bv;
+                if (EPI == EPI_PATCH_RT || EPI == EPI_PATCH16_RT) {
+                    const int np = a.grid * a.grid;  // patches per frame; token rows: np + 1
+                    const int b = row / np, p = row - b * np;
+                    v += a.pos[(size_t)(1 + p) * a.N + col];
+                    a.y[((size_t)b * (np + 1) + 1 + p) * a.N + col] = v;
+                    continue;
+                }
                 if (EPI == EPI_PATCH || EPI == EPI_PATCH16) {
                     constexpr int NP = EPI == EPI_PATCH16 ? VIT16_P : VIT_P;  // patches per frame; token rows: NP + 1
                     const int b = row / NP, p = row - b * NP;
@@ -472,6 +502,61 @@ int launch_cls_token(const float* cls, const float* pos, float* tokens, int B, i
     return ORBIT_OK;
 }
 
+// ---- position table at another grid -----------------------------------------------------------------------------------
+// pos [1 + g*g][D] -> out [1 + G*G][D]: row 0 copied, rows 1.. the g x g table resampled to G x G as torch's
+// F.interpolate(mode="bicubic", align_corners=False) does it (aten UpSampleBicubic2d): source coordinate (i + 0.5) * (g / G) - 0.5
+// with the ratio rounded to fp32 first, cubic convolution with A = -0.75 on t = coordinate - floor, four taps per axis clamped to
+// [0, g - 1], the four rows interpolated along x and then those four along y. One thread per output element, fp32.
+__device__ __forceinline__ void bicubic_coeffs(float t, float (&c)[4]) {
+    const float A = -0.75f;
+    const float x0 = t + 1.f, x3 = (1.f - t) + 1.f, x2 = 1.f - t;
+    c[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
+    c[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
+    c[2] = ((A + 2.f) * x2 - (A + 3.f)) * x2 * x2 + 1.f;
+    c[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
+}
+
+__global__ __launch_bounds__(256) void vit_pos_resample_kernel(const float* __restrict__ pos, float* __restrict__ out, int g, int G,
+                                                               int D) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= (G * G + 1) * D) return;
+    const int row = i / D, d = i - row * D;
+    if (row == 0) {
+        out[i] = pos[i];
+        return;
+    }
+    const int oy = (row - 1) / G, ox = (row - 1) - oy * G;
+    const float ratio = (float)g / (float)G;
+    const float fy = ratio * (oy + 0.5f) - 0.5f, fx = ratio * (ox + 0.5f) - 0.5f;
+    const float iyf = floorf(fy), ixf = floorf(fx);
+    const int iy = (int)iyf, ix = (int)ixf;
+    float cy[4], cx[4];
+    bicubic_coeffs(fy - iyf, cy);
+    bicubic_coeffs(fx - ixf, cx);
+    float v = 0.f;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const int y = min(max(iy - 1 + a, 0), g - 1);
+        float r = 0.f;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int x = min(max(ix - 1 + b, 0), g - 1);
+            r += pos[(size_t)(1 + y * g + x) * D + d] * cx[b];
+        }
+        v += r * cy[a];
+    }
+    out[i] = v;
+}
+
+int launch_pos_resample(const float* pos, float* out, int g, int G, int D, hipStream_t s) {
+    const int n = (G * G + 1) * D;
+    const int pi = prof_start("vit_pos_resample", 40.0 * n, 4.0 * (n + (g * g + 1) * D), s);
+    vit_pos_resample_kernel<<<cdiv(n, 256), 256, 0, s>>>(pos, out, g, G, D);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
 // ---- LayerNorm -------------------------------------------------------------------------------------------------------
 template <int NPL>  // D / 64 values per lane
 __global__ __launch_bounds__(256) void vit_layernorm_kernel(const float* x, size_t x_stride, float* y, size_t y_stride,
@@ -662,9 +747,136 @@ __global__ __launch_bounds__(64 * A16_WAVES) void vit_attention197_kernel(const 
                                                                            ov[dt][4 * g + 2] / sum, ov[dt][4 * g + 3] / sum);
 }
 
-// N: tokens per frame, 50 (the LDS-resident VALU kernel) or 197 (the MFMA kernel; qkv and out 16-byte aligned)
+// Any token count N >= 1 (the plans of orbit_vit_create_sized): the scheme of vit_attention197_kernel made streaming. One
+// workgroup of 4 waves per (frame, head, block of 128 queries); a wave owns 32 queries and keeps, per lane, its query (32 of the
+// 64 d, pre-scaled), one 32-key tile of S^T, the running maximum and (half-)sum and the two O^T accumulators - nothing grows with
+// N. K and V pass through LDS in tiles of 32 keys, [32][65] + [32][72] floats = 17 536 bytes, the row strides of the 197 kernel;
+// the next tile is read from memory into registers while the MFMAs of the current one run. Per tile: S^T = K (Q/8)^T, keys past
+// N - 1 to -inf (their K and V rows are staged as zeros), m' = max(m, tile maximum), the sum and the accumulators times
+// exp(m - m'), P^T = exp(S^T - m') straight into O^T += V^T P^T. Tiles go in ascending order, so tile 0 holds key 0: m' is finite
+// from the first step on, exp(-inf - m') = 0 wipes the (zero) initial state and (-inf) - (-inf) never occurs. Queries past N - 1
+// re-read query N - 1 and are never stored; a wave with no valid query only helps staging. The order of every sum is fixed by N
+// alone: a row's bits do not depend on B, on the query's place in its block or on the other workgroups.
+constexpr int AN_WAVES = 4;
+constexpr int AN_QB = 32 * AN_WAVES;  // queries per workgroup
+constexpr int AN_KT = 32;             // keys per tile
+static_assert(AN_KT * (VIT_HD / 4) == 2 * 64 * AN_WAVES, "two float4 of K and of V per thread and tile");
+
+__global__ __launch_bounds__(64 * AN_WAVES) void vit_attention_n_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                                        int N, int D, int heads, int qblocks) {
+    __shared__ __attribute__((aligned(16))) float ks[AN_KT * A16_LDK];
+    __shared__ __attribute__((aligned(16))) float vs[AN_KT * A16_LDV];
+    const int qb = blockIdx.x % qblocks, bh = blockIdx.x / qblocks, b = bh / heads, h = bh - b * heads;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int col = lane & 31, half = lane >> 5;
+    const float* base = qkv + (size_t)b * N * 3 * D + h * VIT_HD;
+    const int q0 = AN_QB * qb + 32 * wave;  // this wave's first query
+    const bool active = q0 < N;             // (wave-uniform)
+    const int query = q0 + col;
+    float qf[32];
+    {
+        const float* qp = base + (size_t)(query < N ? query : N - 1) * 3 * D + 32 * half;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float4 q4 = *reinterpret_cast<const float4*>(qp + 4 * i);
+            qf[4 * i + 0] = q4.x * 0.125f, qf[4 * i + 1] = q4.y * 0.125f, qf[4 * i + 2] = q4.z * 0.125f, qf[4 * i + 3] = q4.w * 0.125f;
+        }
+    }
+    // staging: thread -> (key tid >> 4 and 16 + (tid >> 4), four d at 4 (tid & 15))
+    const int sk = tid >> 4, sc4 = (tid & 15) * 4;
+    float4 rk[2], rv[2];
+    auto fetch = [&](int t) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int key = AN_KT * t + sk + 16 * i;
+            rk[i] = rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (key < N) {
+                const float* r = base + (size_t)key * 3 * D + sc4;
+                rk[i] = *reinterpret_cast<const float4*>(r + D);
+                rv[i] = *reinterpret_cast<const float4*>(r + 2 * D);
+            }
+        }
+    };
+
+    float m = -INFINITY, sum = 0.f;  // running maximum (both lane halves agree) and this lane half's share of the sum
+    floatx16 ov[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ov[dt][r] = 0.f;
+    const float* ka = ks + col * A16_LDK + 32 * half;
+    const float* va = vs + 4 * half * A16_LDV + col;
+
+    const int nt = (N + AN_KT - 1) / AN_KT;
+    fetch(0);
+    for (int t = 0; t < nt; ++t) {
+        __syncthreads();  // the previous tile has been read by every wave
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float* kd = ks + (sk + 16 * i) * A16_LDK + sc4;
+            kd[0] = rk[i].x, kd[1] = rk[i].y, kd[2] = rk[i].z, kd[3] = rk[i].w;
+            *reinterpret_cast<float4*>(vs + (sk + 16 * i) * A16_LDV + sc4) = rv[i];
+        }
+        __syncthreads();
+        if (t + 1 < nt) fetch(t + 1);
+        if (!active) continue;
+        // S^T tile: rows = keys 32 t + (r & 3) + 8 (r >> 2) + 4 half, column = this lane's query
+        floatx16 sc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sc[r] = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < 32; ++kk) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[kk], qf[kk], sc, 0, 0, 0);
+        float mt = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            if (AN_KT * t + (r & 3) + 8 * (r >> 2) + 4 * half >= N) sc[r] = -INFINITY;
+            mt = fmaxf(mt, sc[r]);
+        }
+        mt = fmaxf(mt, __shfl_xor(mt, 32));
+        const float mn = fmaxf(m, mt);
+        const float scale = expf(m - mn);  // tile 0: exp(-inf) = 0 on a zero state
+        m = mn;
+        float ts = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sc[r] = expf(sc[r] - mn), ts += sc[r];
+        sum = sum * scale + ts;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) ov[dt][r] *= scale;
+        // O^T tile dt: rows = d 32 dt + (r & 3) + 8 (r >> 2) + 4 half, column = this lane's query
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float* vr = va + ((r & 3) + 8 * (r >> 2)) * A16_LDV;
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) ov[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[32 * dt], sc[r], ov[dt], 0, 0, 0);
+        }
+    }
+    if (!active || query >= N) return;
+    sum += __shfl_xor(sum, 32);
+    float* op = out + ((size_t)b * N + query) * D + h * VIT_HD + 4 * half;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<float4*>(op + 32 * dt + 8 * g) = make_float4(ov[dt][4 * g + 0] / sum, ov[dt][4 * g + 1] / sum,
+                                                                           ov[dt][4 * g + 2] / sum, ov[dt][4 * g + 3] / sum);
+}
+
+int launch_attention_n(const float* qkv, float* out, int B, int N, int D, int heads, hipStream_t s) {
+    const int qblocks = cdiv(N, AN_QB);
+    const int pi = prof_start("vit_attention_n", 4.0 * B * heads * (double)N * N * VIT_HD, 4.0 * 4 * (double)B * N * D, s);
+    vit_attention_n_kernel<<<B * heads * qblocks, 64 * AN_WAVES, 0, s>>>(qkv, out, N, D, heads, qblocks);
+    prof_stop(pi, s);
+    ORBIT_LAUNCH_CHECK();
+    return ORBIT_OK;
+}
+
+// N: tokens per frame: 50 (the LDS-resident VALU kernel), 197 (the MFMA kernel) or anything else (the streaming MFMA kernel);
+// but for 50, qkv and out are 16-byte aligned
 int launch_attention(const float* qkv, float* out, int B, int N, int D, int heads, hipStream_t s) {
-    if (N != VIT_N && N != VIT16_N) return set_err(ORBIT_ERR_ARG, "vit attention: %d tokens (50 or 197)", N);
+    if (N < 1) return set_err(ORBIT_ERR_ARG, "vit attention: %d tokens", N);
+    if (N != VIT_N && N != VIT16_N) return launch_attention_n(qkv, out, B, N, D, heads, s);
     static bool attr_set = false;  // > 64 KiB of dynamic LDS needs the opt-in once
     if (N == VIT16_N && !attr_set) {
         ORBIT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vit_attention197_kernel),
@@ -1387,8 +1599,12 @@ struct orbit_vit {
     // The patch-16 plans are forward only (no tape, no backward) until orbit_vit_enable_backward; weight gradients only after
     // orbit_vit_enable_weight_backward
     int patch = VIT_PATCH, grid = VIT_GRID, P = VIT_P, N = VIT_N, kpatch = VIT_KPATCH, max_b = VIT_MAX_B;
+    // frame side: 224 unless the plan came from orbit_vit_create_sized. Any other side is inference + FiLM only for good (the
+    // attention backward and the patch filter gradient are 50 / 197-token kernels), and its forward adds the resampled table
+    int side = VIT_SIZE;
+    bool sized() const { return side != VIT_SIZE; }
     bool backward_enabled = false, weight_backward_enabled = false;
-    bool forward_only() const { return patch != VIT_PATCH && !backward_enabled; }
+    bool forward_only() const { return sized() || (patch != VIT_PATCH && !backward_enabled); }
     bool weight_grads() const { return patch == VIT_PATCH || weight_backward_enabled; }
     ParamPool pool{64};  // the parameters by state_dict key (csrc/param_pool.h); 256-byte aligned tensors (float4 loads)
     // where the forward and the backward find each tensor: pool offsets, fixed by orbit_vit_create
@@ -1406,6 +1622,11 @@ struct orbit_vit {
     bool bf16_enabled = false;
     unsigned short* d_wbf = nullptr;
     bool wbf_valid = false;
+    // the position table resampled to this plan's grid, [P + 1][D] (vit_pos_resample_kernel): made by the first forward after a
+    // parameter upload, never on a plan whose grid is the checkpoint's (side 224)
+    float* d_pos_rs = nullptr;
+    bool pos_rs_valid = false;
+    void invalidate() { finalized = false, wt_valid = false, wbf_valid = false, pos_rs_valid = false; }
 
     const float* p(size_t off) const { return off == VIT_ABSENT ? nullptr : pool.d_pool + off; }
 };
@@ -1478,9 +1699,16 @@ int vit_check_call(const char* who, const orbit_vit* v, int B, const float* film
     ORBIT_REQUIRE((film_gamma == nullptr) == (film_beta == nullptr), "%s: film_gamma and film_beta must be given together", who);
     return ORBIT_OK;
 }
+// a plan of orbit_vit_create_sized at another frame size has no training path at all
+int vit_check_frame_size(const char* who, const orbit_vit* v) {
+    ORBIT_REQUIRE(!v->sized(), "%s: %s is a %dx%d plan (orbit_vit_create_sized): frame size %d is inference + FiLM only, the "
+                  "training paths run on %dx%d frames", who, v->name.c_str(), v->side, v->side, v->side, VIT_SIZE, VIT_SIZE);
+    return ORBIT_OK;
+}
 // the training entry points on a forward-only plan: refused by name, before any launch or allocation
 int vit_check_trainable(const char* who, const orbit_vit* v) {
     ORBIT_REQUIRE(v, "%s: null pointer", who);
+    if (int rc = vit_check_frame_size(who, v)) return rc;
     ORBIT_REQUIRE(!v->bf16_enabled, "%s: %s is a bf16 inference plan (orbit_vit_enable_bf16): the training paths are fp32 only", who,
                   v->name.c_str());
     ORBIT_REQUIRE(!v->forward_only(), "%s: %s is an inference-only plan (no tape and no backward for the patch-%d models)", who,
@@ -1493,12 +1721,11 @@ int vit_check_buffer(const char* who, const char* what, const void* ptr, size_t 
     return ORBIT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out) {
-    ORBIT_REQUIRE(name && out, "vit_create: null pointer");
+// any_size false: orbit_vit_create (224 x 224, or its refusal); true: orbit_vit_create_sized (square, a multiple of the patch,
+// 32..512). At 224 x 224 the two build the same plan.
+constexpr int VIT_SIZED_MIN = 32, VIT_SIZED_MAX = 512;
+int vit_create_impl(const char* who, const char* name, int H, int W, bool any_size, orbit_vit_t** out) {
+    ORBIT_REQUIRE(name && out, "%s: null pointer", who);
     std::string n(name);
     int D, heads;
     bool clip = false, p16 = false;
@@ -1510,8 +1737,17 @@ int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out) {
     else if (n == "vit_b_16_clip") D = 768, heads = 12, clip = true, p16 = true;
     else return set_err(ORBIT_ERR_ARG, "Invalid feature_extractor_name: %s (transformer extractors: vit_s_32, vit_b_32, "
                         "vit_b_32_clip, vit_s_16, vit_b_16, vit_b_16_clip)", name);
-    ORBIT_REQUIRE(H == VIT_SIZE && W == VIT_SIZE, "vit_create: %s runs on %dx%d frames only (fixed position table), got %dx%d",
-                  name, VIT_SIZE, VIT_SIZE, H, W);
+    const int patch = p16 ? VIT16_PATCH : VIT_PATCH;
+    if (!any_size) {
+        ORBIT_REQUIRE(H == VIT_SIZE && W == VIT_SIZE, "vit_create: %s runs on %dx%d frames only (fixed position table), got %dx%d",
+                      name, VIT_SIZE, VIT_SIZE, H, W);
+    } else {
+        ORBIT_REQUIRE(H == W, "%s: %s runs on square frames only, got %dx%d", who, name, H, W);
+        ORBIT_REQUIRE(H >= VIT_SIZED_MIN, "%s: frame size %d is below %d", who, H, VIT_SIZED_MIN);
+        ORBIT_REQUIRE(H <= VIT_SIZED_MAX, "%s: frame size %d is above %d", who, H, VIT_SIZED_MAX);
+        ORBIT_REQUIRE(H % patch == 0, "%s: frame size %d is not a multiple of %s's patch size %d (nearest: %d and %d)", who, H, name,
+                      patch, H / patch * patch, (H / patch + 1) * patch);
+    }
     orbit_vit* v = new orbit_vit();
     v->name = n, v->pool.owner = n, v->D = D, v->heads = heads, v->mlp = 4 * D, v->clip = clip, v->eps = clip ? 1e-5f : 1e-6f;
     if (p16) {
@@ -1521,7 +1757,13 @@ int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out) {
     auto add = [&](const std::string& key, size_t numel) { return v->pool.off(v->pool.add(key, numel)); };
     // timm 0.6.12 VisionTransformer state_dict order
     v->cls = add("cls_token", D);
-    v->pos = add("pos_embed", (size_t)v->N * D);
+    v->pos = add("pos_embed", (size_t)v->N * D);  // (the checkpoint's shape at any frame size)
+    if (H != VIT_SIZE) {
+        // another frame size: the same parameters, the geometry of S / patch patches per side, and as many frames as keep the
+        // token rows within what the caps at 224 already allow (workspace sizes stay in that range)
+        v->side = H, v->grid = H / patch, v->P = v->grid * v->grid, v->N = v->P + 1;
+        v->max_b = VIT_MAX_B * VIT_N / v->N;
+    }
     v->patch_w = add("patch_embed.proj.weight", (size_t)D * v->kpatch);
     if (!clip) v->patch_b = add("patch_embed.proj.bias", D);
     if (clip) v->pre_w = add("norm_pre.weight", D), v->pre_b = add("norm_pre.bias", D);
@@ -1545,11 +1787,24 @@ int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out) {
     return ORBIT_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int orbit_vit_create(const char* name, int H, int W, orbit_vit_t** out) {
+    return vit_create_impl("vit_create", name, H, W, false, out);
+}
+
+int orbit_vit_create_sized(const char* name, int H, int W, orbit_vit_t** out) {
+    return vit_create_impl("vit_create_sized", name, H, W, true, out);
+}
+
 void orbit_vit_destroy(orbit_vit_t* v) {
     if (!v) return;
     v->pool.free_device();
     (void)hipFree(v->d_wt);
     (void)hipFree(v->d_wbf);
+    (void)hipFree(v->d_pos_rs);
     delete v;
 }
 
@@ -1557,25 +1812,25 @@ int orbit_vit_num_params(const orbit_vit_t* v) { return v ? v->pool.size() : 0; 
 const char* orbit_vit_param_name(const orbit_vit_t* v, int i) { return v ? v->pool.name(i) : nullptr; }
 size_t orbit_vit_param_numel(const orbit_vit_t* v, int i) { return v ? v->pool.numel(i) : 0; }
 
-// every upload invalidates the finalized state, the transposed weights of the backward and the bf16 copies
+// every upload invalidates the finalized state, the transposed weights of the backward, the bf16 copies and the resampled table
 int orbit_vit_load(orbit_vit_t* v, const char* key, const float* data, size_t numel) {
     ORBIT_REQUIRE(v && key && data, "vit_load: null pointer");
     if (int rc = v->pool.load("vit_load", key, data, numel)) return rc;
-    v->finalized = false, v->wt_valid = false, v->wbf_valid = false;
+    v->invalidate();
     return ORBIT_OK;
 }
 
 int orbit_vit_load_async(orbit_vit_t* v, const char* key, const float* device_data, size_t numel, orbit_stream_t stream) {
     ORBIT_REQUIRE(v && key && device_data, "vit_load_async: null pointer");
     if (int rc = v->pool.load_async("vit_load_async", key, device_data, numel, (hipStream_t)stream)) return rc;
-    v->finalized = false, v->wt_valid = false, v->wbf_valid = false;
+    v->invalidate();
     return ORBIT_OK;
 }
 
 int orbit_vit_load_all_async(orbit_vit_t* v, const float* const* device_ptrs, int n, orbit_stream_t stream) {
     ORBIT_REQUIRE(v && device_ptrs, "vit_load_all_async: null pointer");
     if (int rc = v->pool.load_all_async("vit_load_all_async", device_ptrs, n, 32, (hipStream_t)stream)) return rc;
-    v->finalized = false, v->wt_valid = false, v->wbf_valid = false;
+    v->invalidate();
     return ORBIT_OK;
 }
 
@@ -1629,6 +1884,16 @@ int vit_ensure_wbf(orbit_vit_t* v, hipStream_t s) {
     return ORBIT_OK;
 }
 
+// (re)build the resampled position table on `s` if a parameter upload invalidated it (plans at another grid than the checkpoint's)
+int vit_ensure_pos(orbit_vit_t* v, hipStream_t s) {
+    if (!v->sized()) return ORBIT_OK;
+    if (!v->d_pos_rs) ORBIT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&v->d_pos_rs), (size_t)v->N * v->D * sizeof(float)));
+    if (v->pos_rs_valid) return ORBIT_OK;
+    if (int rc = launch_pos_resample(v->p(v->pos), v->d_pos_rs, VIT_SIZE / v->patch, v->grid, v->D, s)) return rc;
+    v->pos_rs_valid = true;
+    return ORBIT_OK;
+}
+
 // With bf16 (a plan under orbit_vit_enable_bf16, tape == nullptr) the four token GEMMs of every block run on vit_gemm_bf16_kernel;
 // everything else, the residual stream included, is the fp32 kernels in the same buffers.
 int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* film_gamma, const float* film_beta, float* feats,
@@ -1638,6 +1903,9 @@ int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* fi
     const VitWt W = vit_wt(v);
     if (bf16)
         if (int rc = vit_ensure_wbf(v, s)) return rc;
+    if (v->sized() && tape) return set_err(ORBIT_ERR_ARG, "vit_forward: a %dx%d plan has no taped forward", v->side, v->side);
+    if (int rc = vit_ensure_pos(v, s)) return rc;
+    const float* pos = v->sized() ? v->d_pos_rs : v->p(v->pos);  // [N][D]
     const VitWs L = vit_ws(v, B, false);
     const VitTape T = vit_tape(v, B);
     const int D = v->D, N = v->N, M = B * N;
@@ -1653,10 +1921,16 @@ int vit_forward_impl(orbit_vit_t* v, const float* frames, int B, const float* fi
     };
     int rc;
     {   // tokens: patch embedding (+ bias) + pos_embed into rows 1..N-1, cls_token + pos_embed[0] into row 0
-        GemmArgs a{frames, v->p(v->patch_w), v->p(v->patch_b), nullptr, v->p(v->pos), x, B * v->P, D, v->kpatch};
-        if ((rc = v->patch == VIT16_PATCH ? launch_gemm<EPI_PATCH16>(a, "patch_embed", s) : launch_gemm<EPI_PATCH>(a, "patch_embed", s)))
-            return rc;
-        if ((rc = launch_cls_token(v->p(v->cls), v->p(v->pos), x, B, D, N, s))) return rc;
+        GemmArgs a{frames, v->p(v->patch_w), v->p(v->patch_b), nullptr, pos, x, B * v->P, D, v->kpatch};
+        if (v->sized()) {  // (a 224 plan keeps its compile-time geometry)
+            a.side = v->side, a.grid = v->grid;
+            rc = v->patch == VIT16_PATCH ? launch_gemm<EPI_PATCH16_RT>(a, "patch_embed_sized", s)
+                                         : launch_gemm<EPI_PATCH_RT>(a, "patch_embed_sized", s);
+        } else {
+            rc = v->patch == VIT16_PATCH ? launch_gemm<EPI_PATCH16>(a, "patch_embed", s) : launch_gemm<EPI_PATCH>(a, "patch_embed", s);
+        }
+        if (rc) return rc;
+        if ((rc = launch_cls_token(v->p(v->cls), pos, x, B, D, N, s))) return rc;
         if (v->clip && (rc = launch_layernorm(x, D, x, D, M, D, v->p(v->pre_w), v->p(v->pre_b), v->eps, s))) return rc;
     }
     for (int i = 0; i < VIT_DEPTH; ++i) {
@@ -1834,6 +2108,7 @@ int orbit_vit_bf16_enabled(const orbit_vit_t* v) { return v && v->bf16_enabled ?
 
 int orbit_vit_enable_backward(orbit_vit_t* v) {
     ORBIT_REQUIRE(v, "vit_enable_backward: null pointer");
+    if (int rc = vit_check_frame_size("vit_enable_backward", v)) return rc;
     ORBIT_REQUIRE(!v->bf16_enabled, "vit_enable_backward: %s is a bf16 inference plan (orbit_vit_enable_bf16)", v->name.c_str());
     v->backward_enabled = true;  // (read by forward_only() of the patch-16 plans only)
     return ORBIT_OK;
@@ -1841,6 +2116,7 @@ int orbit_vit_enable_backward(orbit_vit_t* v) {
 // weight gradients of a patch-16 plan (orbit_vit_backward_params); a patch-32 plan has them already
 int orbit_vit_enable_weight_backward(orbit_vit_t* v) {
     ORBIT_REQUIRE(v, "vit_enable_weight_backward: null pointer");
+    if (int rc = vit_check_frame_size("vit_enable_weight_backward", v)) return rc;
     ORBIT_REQUIRE(!v->bf16_enabled, "vit_enable_weight_backward: %s is a bf16 inference plan (orbit_vit_enable_bf16)",
                   v->name.c_str());
     v->weight_backward_enabled = true;  // (a patch-32 plan has the gradients anyway: remembered for orbit_vit_enable_bf16's refusal)
@@ -1996,6 +2272,44 @@ int orbit_op_vit_patch_embed(const float* frames, const float* w, const float* b
     return orbit_op_vit_patch_embed_p(frames, w, bias_or_null, pos_embed, cls_token, tokens, B, D, VIT_PATCH, tile_rows, stream);
 }
 
+// the patch embedding on square frames of side S (a multiple of the patch, 32..512): pos_embed is the table AT that grid,
+// [(S / patch)^2 + 1][D] (orbit_op_vit_pos_resample makes it); always the runtime-geometry form of the GEMM, at S = 224 too
+int orbit_op_vit_patch_embed_sized(const float* frames, const float* w, const float* bias_or_null, const float* pos_embed,
+                                   const float* cls_token, float* tokens, int B, int D, int patch, int S, int tile_rows,
+                                   orbit_stream_t stream) {
+    const char* who = "op_vit_patch_embed_sized";
+    ORBIT_REQUIRE(frames && w && pos_embed && cls_token && tokens, "%s: null pointer", who);
+    ORBIT_REQUIRE(patch == VIT_PATCH || patch == VIT16_PATCH, "%s: patch size %d (32 or 16)", who, patch);
+    ORBIT_REQUIRE(S >= VIT_SIZED_MIN && S <= VIT_SIZED_MAX && S % patch == 0,
+                  "%s: frame size %d (a multiple of the patch size %d in %d..%d)", who, S, patch, VIT_SIZED_MIN, VIT_SIZED_MAX);
+    const int grid = S / patch, np = grid * grid, max_b = VIT_MAX_B * VIT_N / (np + 1);
+    ORBIT_REQUIRE(B > 0 && B <= max_b, "%s: batch of %d frames (1..%d)", who, B, max_b);
+    ORBIT_REQUIRE(D == 384 || D == 768, "%s: unsupported width %d (384 or 768)", who, D);
+    ORBIT_REQUIRE(((uintptr_t)frames & 15) == 0 && ((uintptr_t)w & 15) == 0, "%s: frames and w must be 16-byte aligned", who);
+    ORBIT_REQUIRE(((uintptr_t)tokens & 3) == 0 && ((uintptr_t)bias_or_null & 3) == 0 && ((uintptr_t)pos_embed & 3) == 0 &&
+                      ((uintptr_t)cls_token & 3) == 0,
+                  "%s: tokens, bias, pos_embed and cls_token must be 4-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    GemmArgs a{frames, w, bias_or_null, nullptr, pos_embed, tokens, B * np, D, 3 * patch * patch};
+    a.side = S, a.grid = grid;
+    if (int rc = patch == VIT16_PATCH ? launch_gemm<EPI_PATCH16_RT>(a, "op_patch_embed_sized", s, tile_rows)
+                                      : launch_gemm<EPI_PATCH_RT>(a, "op_patch_embed_sized", s, tile_rows))
+        return rc;
+    return launch_cls_token(cls_token, pos_embed, tokens, B, D, np + 1, s);
+}
+
+// pos [g*g + 1][D] (g = 7 or 14: the checkpoint's table) -> out [G*G + 1][D], 1 <= G <= 32
+int orbit_op_vit_pos_resample(const float* pos, float* out, int g, int G, int D, orbit_stream_t stream) {
+    ORBIT_REQUIRE(pos && out, "op_vit_pos_resample: null pointer");
+    ORBIT_REQUIRE(g == VIT_GRID || g == VIT16_GRID, "op_vit_pos_resample: source grid %d (7 or 14)", g);
+    ORBIT_REQUIRE(G >= 1 && G <= VIT_SIZED_MAX / VIT16_PATCH, "op_vit_pos_resample: target grid %d (1..%d)", G,
+                  VIT_SIZED_MAX / VIT16_PATCH);
+    ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_pos_resample: unsupported width %d (384 or 768)", D);
+    ORBIT_REQUIRE((((uintptr_t)pos | (uintptr_t)out) & 3) == 0, "op_vit_pos_resample: pointers must be 4-byte aligned");
+    ORBIT_REQUIRE(pos != out, "op_vit_pos_resample: out must not alias pos");
+    return launch_pos_resample(pos, out, g, G, D, (hipStream_t)stream);
+}
+
 int orbit_op_vit_layernorm(const float* x, size_t x_stride, float* y, size_t y_stride, int rows, int D, const float* gamma,
                            const float* beta, float eps, orbit_stream_t stream) {
     ORBIT_REQUIRE(x && y && gamma && beta, "op_vit_layernorm: null pointer");
@@ -2020,6 +2334,19 @@ int orbit_op_vit_attention_tokens(const float* qkv, float* out, int B, int token
     ORBIT_REQUIRE((((uintptr_t)qkv | (uintptr_t)out) & mask) == 0, "op_vit_attention: pointers must be %d-byte aligned",
                   (int)mask + 1);
     return launch_attention(qkv, out, B, tokens, D, heads, (hipStream_t)stream);
+}
+
+// any token count on vit_attention_n_kernel (50 and 197 too): B * tokens at most 8192 * 50 rows
+int orbit_op_vit_attention_n(const float* qkv, float* out, int B, int tokens, int D, int heads, orbit_stream_t stream) {
+    ORBIT_REQUIRE(qkv && out, "op_vit_attention_n: null pointer");
+    ORBIT_REQUIRE(tokens >= 1 && tokens <= VIT_MAX_B * VIT_N, "op_vit_attention_n: %d tokens per frame (1..%d)", tokens,
+                  VIT_MAX_B * VIT_N);
+    ORBIT_REQUIRE(D == 384 || D == 768, "op_vit_attention_n: unsupported width %d (384 or 768)", D);
+    ORBIT_REQUIRE(heads * VIT_HD == D, "op_vit_attention_n: %d heads of %d do not make D=%d", heads, VIT_HD, D);
+    const int max_b = VIT_MAX_B * VIT_N / tokens;
+    ORBIT_REQUIRE(B > 0 && B <= max_b, "op_vit_attention_n: batch of %d frames (1..%d)", B, max_b);
+    ORBIT_REQUIRE((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0, "op_vit_attention_n: pointers must be 16-byte aligned");
+    return launch_attention_n(qkv, out, B, tokens, D, heads, (hipStream_t)stream);
 }
 
 int orbit_op_vit_attention(const float* qkv, float* out, int B, int D, int heads, orbit_stream_t stream) {

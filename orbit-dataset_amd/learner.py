@@ -98,6 +98,13 @@ def build_parser():
                         "bf16 operands and fp32 accumulation (VisionTransformer.bf16_inference; everything else stays fp32). A "
                         "documented precision trade, off by default; refused with a training mode and with the finetuner's "
                         "--learn_extractor / --adapt_features; ignored with a note for the other extractors")
+    p.add_argument("--vit_resample_pos_embed", action="store_true",
+                   help="vit_* extractors (all six), test modes only: lift the 224x224 restriction. --frame_size S (a multiple of "
+                        "the model's patch size, 32..512) goes to the data pipeline as for the CNN extractors, and the transformer "
+                        "adds its position table resampled to the S / patch grid (torch's bicubic, timm's resize_pos_embed; "
+                        "VisionTransformer.resample_pos_embed). Off by default; at another size than 224 refused with a training "
+                        "mode and with the finetuner's --learn_extractor / --adapt_features; ignored with a note for the other "
+                        "extractors")
     p.add_argument("--effnetv2_native_backward", action="store_true",
                    help="efficientnet_v2_s: opt in to the native FiLM gradients through the FROZEN network (--adapt_features "
                         "training, with or without --with_lite; the multi-step finetuner's --adapt_features). --learn_extractor "
@@ -403,11 +410,32 @@ def verify_args(args):
         elif multistep and (args.learn_extractor or args.adapt_features):
             sys.exit("error: --vit_bf16 is an inference mode: the finetuner's --learn_extractor / --adapt_features send gradients "
                      "through the extractor, which a bf16 plan refuses")
+    resample = getattr(args, "vit_resample_pos_embed", False)
+    if resample:
+        S = args.frame_size
+        if not fe.startswith("vit_"):
+            print("note: --vit_resample_pos_embed is ignored for --feature_extractor %s (it runs at any --frame_size already; the "
+                  "position table belongs to the vit_* extractors)" % fe)
+            resample = args.vit_resample_pos_embed = False
+        elif S != 224:
+            patch = 16 if fe.split("_")[2] == "16" else 32
+            if S > 512:
+                sys.exit("error: --vit_resample_pos_embed covers --frame_size 32..512 (got %d)" % S)
+            if S % patch:
+                sys.exit("error: --vit_resample_pos_embed: --frame_size %d is not a multiple of %s's patch size %d; the nearest "
+                         "valid sizes are %d and %d" % (S, fe, patch, max(S // patch * patch, patch), (S // patch + 1) * patch))
+            if "train" in args.mode:
+                sys.exit("error: --vit_resample_pos_embed at --frame_size %d is an inference mode (the native backward runs on "
+                         "224x224 frames only): use --mode test, got --mode %s" % (S, args.mode))
+            if multistep and (args.learn_extractor or args.adapt_features):
+                sys.exit("error: --vit_resample_pos_embed at --frame_size %d is an inference mode: the finetuner's "
+                         "--learn_extractor / --adapt_features send gradients through the extractor, which runs its backward on "
+                         "224x224 frames only" % S)
     spec = FROZEN_EXTRACTORS.get(fe)
     if spec is None:
         return
     args.frame_norm_method = spec.frame_norm
-    if spec.frame_size is not None and args.frame_size != spec.frame_size:
+    if spec.frame_size is not None and args.frame_size != spec.frame_size and not resample:
         sys.exit("error: --feature_extractor %s needs --frame_size %d (got %d)" % (fe, spec.frame_size, args.frame_size))
     scope, flag, _ = opted_in(args, spec)
     if scope == "all":
@@ -575,6 +603,8 @@ class Learner:
             setattr(self.model.feature_extractor, attr, True)
         if getattr(a, "vit_bf16", False):  # (verify_args cleared it for the other extractors)
             self.model.feature_extractor.bf16_inference = True
+        if getattr(a, "vit_resample_pos_embed", False):  # (the same)
+            self.model.feature_extractor.resample_pos_embed = True
         self.model._set_device(self.device)
         self.model._send_to_device()
 
@@ -1078,6 +1108,7 @@ class Learner:
                  "num_tasks": len(records), "world_size": self.world, "orbit_metrics": metrics.report()}
         if a.feature_extractor.startswith("vit_"):  # the precision of the transformer's token GEMMs (--vit_bf16)
             stats["vit_precision"] = "bf16" if getattr(a, "vit_bf16", False) else "fp32"
+            stats["vit_frame_size"] = [a.frame_size, a.frame_size]  # the frames the plan ran at (--vit_resample_pos_embed)
         if prefetch is not None:
             stats.update({"target_frames": sum(r["frames"] for r in records), "wall_s": wall, "data_root": root})
             stats.update(self.ingest_stats(prefetch, root))

@@ -44,7 +44,8 @@ def _ensure_child(module, name, cls=ParamNode):
 class _Plan:
     """One native plan (frame size specific) and the parameter stamp it was last synchronised with."""
 
-    def __init__(self, name, H, W, trainable=False, api="extractor", res_post_backward=False, res_post_training=False):
+    def __init__(self, name, H, W, trainable=False, api="extractor", res_post_backward=False, res_post_training=False,
+                 create="create"):
         lib = _lib.load()
         h = ctypes.c_void_p()
         if api == "extractor":
@@ -54,7 +55,9 @@ class _Plan:
             flags = (1 if trainable else 0) | (2 if res_post_backward else 0) | (4 if res_post_training else 0)
             _lib.check(lib.orbit_extractor_create_ex(name.encode(), H, W, flags, ctypes.byref(h)), "orbit_extractor_create_ex")
         else:
-            _lib.check(getattr(lib, "orbit_%s_create" % api)(name.encode(), H, W, ctypes.byref(h)), "orbit_%s_create" % api)
+            # (create: the family's constructor - "create_sized" for a transformer plan at any frame size)
+            _lib.check(getattr(lib, "orbit_%s_%s" % (api, create))(name.encode(), H, W, ctypes.byref(h)),
+                       "orbit_%s_%s" % (api, create))
         self.api = api
         self.handle = h
         self.stamp = None
@@ -165,9 +168,7 @@ class HipNetwork(nn.Module):
     def _plan(self, H, W, trainable=False):
         """inference plans may hold fused ops that have no backward form; a forward that records a tape or uses batch
         statistics gets its own (unfused) plan. Both enumerate the same parameters in the same order."""
-        if self._frame_size is not None and (H, W) != (self._frame_size, self._frame_size):
-            raise ValueError("%s runs on %dx%d frames only (got %dx%d)" % (self.native_name, self._frame_size, self._frame_size,
-                                                                          H, W))
+        self._check_frame_size(H, W)
         key = self._plan_key(H, W, trainable)
         plan = self._plans.get(key)
         if plan is None:
@@ -178,6 +179,11 @@ class HipNetwork(nn.Module):
                 raise _lib.OrbitHipError("native plan enumerates different parameters than the module tree")
             self._plans[key] = plan
         return plan
+
+    def _check_frame_size(self, H, W):
+        if self._frame_size is not None and (H, W) != (self._frame_size, self._frame_size):
+            raise ValueError("%s runs on %dx%d frames only (got %dx%d)" % (self.native_name, self._frame_size, self._frame_size,
+                                                                          H, W))
 
     def _plan_key(self, H, W, trainable):
         return H, W, bool(trainable) and self._training_runtime
@@ -691,7 +697,15 @@ class VisionTransformer(HipNetwork):
     precision trade that is off by default: the forward runs on a plan of its own under orbit_vit_enable_bf16, whose qkv / proj /
     fc1 / fc2 GEMMs take bf16 operands with fp32 accumulation while everything else stays fp32 (include/orbit_hip.h). A forward
     that needs a gradient on such a module - FiLM vector or parameter, under any of the four opt-ins above - raises
-    NotImplementedError naming the attribute before anything is launched."""
+    NotImplementedError naming the attribute before anything is launched.
+
+    `resample_pos_embed = True` (set per instance, also after plans exist; learner flag --vit_resample_pos_embed; all six
+    models) lifts the 224 x 224 restriction for INFERENCE: a forward on square frames of side S, S a multiple of the patch size,
+    32 <= S <= 512, builds its plan through orbit_vit_create_sized, whose forward adds the position table resampled to the
+    S / patch grid (torch's bicubic, timm's resize_pos_embed; include/orbit_hip.h). `pos_embed` stays the checkpoint's
+    parameter: key, shape and state_dict do not change. At 224 the features are bit for bit the default's. A forward that needs
+    a gradient at any other size raises NotImplementedError naming the attribute before a plan is built, under any of the four
+    opt-ins above; the training paths stay 224 x 224. It composes with bf16_inference."""
 
     _api = "vit"
     _probe_size = _frame_size = VIT_FRAME_SIZE
@@ -707,6 +721,11 @@ class VisionTransformer(HipNetwork):
     _refusal_bf16 = ("%(name)s: bf16_inference = True is an inference mode (bf16 token GEMMs have no taped forward and no "
                      "backward); run it under torch.no_grad() with frozen parameters, or set bf16_inference = False to train")
 
+    resample_pos_embed = False  # opt-in (learner flag --vit_resample_pos_embed): other frame sizes, inference only
+    SIZED_MIN, SIZED_MAX = 32, 512  # the frame sides orbit_vit_create_sized accepts (multiples of the patch size)
+    _refusal_resample = ("%(name)s: resample_pos_embed = True at %(H)dx%(W)d frames is an inference mode (the native backward "
+                         "runs on 224x224 frames only); run it under torch.no_grad() with frozen parameters, or train at 224x224")
+
     def wants_grad(self, film=None):
         # refused before a plan is built or the device asked for, whichever native-backward opt-in is set
         if self.bf16_inference and self._grad_requested(film):
@@ -716,15 +735,35 @@ class VisionTransformer(HipNetwork):
     def forward(self, x, film=None, out=None, check_sync=True):
         if self.bf16_inference:  # (the refusal above, before the device is asked for)
             self.wants_grad(self._resolve_film(film))
+        H, W = x.shape[-2:]
+        if self.resample_pos_embed and (H, W) != (VIT_FRAME_SIZE, VIT_FRAME_SIZE):  # (before a plan or the device, as above)
+            self._check_frame_size(H, W)
+            if self._grad_requested(self._resolve_film(film)):
+                raise NotImplementedError(self._refusal_resample % {"name": self.native_name, "H": H, "W": W})
         return super().forward(x, film=film, out=out, check_sync=check_sync)
 
-    def _plan_key(self, H, W, trainable):
-        # a bf16 plan is a plan of its own: flipping the attribute never turns an fp32 plan (or its features) into a bf16 one
-        return super()._plan_key(H, W, trainable) + (("bf16",) if self.bf16_inference else ())
+    def _check_frame_size(self, H, W):
+        if not self.resample_pos_embed:
+            return super()._check_frame_size(H, W)
+        p = self.patch_size
+        if H != W:
+            raise ValueError("%s runs on square frames only (got %dx%d)" % (self.native_name, H, W))
+        if not self.SIZED_MIN <= H <= self.SIZED_MAX:
+            raise ValueError("%s: resample_pos_embed covers frame sizes %d..%d (got %dx%d)" % (self.native_name, self.SIZED_MIN,
+                                                                                              self.SIZED_MAX, H, W))
+        if H % p:
+            raise ValueError("%s: frame size %d is not a multiple of the patch size %d (nearest: %d and %d)" % (
+                self.native_name, H, p, H // p * p, (H // p + 1) * p))
 
-    def _new_plan(self, H, W, trainable, precision=None):
-        plan = super()._new_plan(H, W, trainable)
-        if precision == "bf16":
+    def _plan_key(self, H, W, trainable):
+        # a sized plan and a bf16 plan are plans of their own: flipping an attribute never turns an existing plan (or its
+        # features) into another kind
+        return (super()._plan_key(H, W, trainable) + (("sized",) if self.resample_pos_embed else ())
+                + (("bf16",) if self.bf16_inference else ()))
+
+    def _new_plan(self, H, W, trainable, *kinds):
+        plan = _Plan(self.native_name, H, W, trainable, api=self._api, create="create_sized" if "sized" in kinds else "create")
+        if "bf16" in kinds:
             _lib.check(_lib.load().orbit_vit_enable_bf16(plan.handle), "orbit_vit_enable_bf16")
         return plan
 

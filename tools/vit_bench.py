@@ -35,6 +35,13 @@ shapes at M = 39 400 rows (200 frames of 197 tokens) from the per-launch event r
     python tools/vit_bench.py --precision bf16 --models vit_s_32,vit_b_32,vit_b_32_clip,vit_s_16,vit_b_16,vit_b_16_clip
     python tools/vit_bench.py --compare_precision --models vit_s_32,vit_b_16
     python tools/vit_bench.py --gemm_shapes
+
+--frame_size S runs the inference report on S x S frames (square, a multiple of the patch size, 32..512): it sets
+VisionTransformer.resample_pos_embed when S is not 224, so the plans come from orbit_vit_create_sized and the position table is
+resampled to the S / patch grid; with --precision bf16 as well.
+
+    python tools/vit_bench.py --frame_size 96 --models vit_b_32_clip
+    python tools/vit_bench.py --frame_size 384 --models vit_b_16_clip --precision bf16
 """
 import argparse
 import ctypes
@@ -75,10 +82,11 @@ def _time(fn, steps, warmup):
     return statistics.median(_samples(fn, steps, warmup))
 
 
-def _model(name, adapt, classifier, bf16=False):
+def _model(name, adapt, classifier, bf16=False, frame_size=224):
     m = SingleStepFewShotRecogniser(name, adapt, classifier, 1, 200, False, 16, 1.0)
     synthetic.init_parameters_(m)
     m.feature_extractor.bf16_inference = bool(bf16)
+    m.feature_extractor.resample_pos_embed = frame_size != 224  # (other sizes: the opt-in resampled position table)
     m._set_device("cuda:0")
     m._send_to_device()
     m.set_test_mode(True)
@@ -362,6 +370,9 @@ def main(argv=None):
                    help="the FiLM-gradient step of the frozen network at a batch of %d frames instead (all six models)" % FILM_BATCH)
     p.add_argument("--precision", choices=("fp32", "bf16"), default="fp32",
                    help="the inference report on the fp32 plan (default) or on the opt-in bf16 plan")
+    p.add_argument("--frame_size", type=int, default=224,
+                   help="the inference report at another frame size (a multiple of the patch size in 32..512): sets "
+                        "VisionTransformer.resample_pos_embed when it is not 224")
     p.add_argument("--compare_precision", action="store_true",
                    help="one resident task on both plans of each model: feature / logit differences and argmax agreement instead")
     p.add_argument("--gemm_shapes", action="store_true",
@@ -379,12 +390,13 @@ def main(argv=None):
         return main_train(a)
     bf16 = a.precision == "bf16"
     peak = PEAK_TF_BF16 if bf16 else PEAK_TF  # of the token GEMMs; the floor below stays the fp32 one (what the default path can reach)
-    result = {"metric": "vit_task_ms", "task": "5-way, 200 support + 200 query frames, 224x224", "precision": a.precision,
-              "peak_tflops": peak, "models": {}}
+    S = a.frame_size
+    result = {"metric": "vit_task_ms", "task": "5-way, 200 support + 200 query frames, %dx%d" % (S, S), "precision": a.precision,
+              "frame_size": S, "peak_tflops": peak, "models": {}}
     for name in a.models.split(","):
-        task = synthetic.make_task_on_device(0, 5, 5, 8, 200, 224, 1, "cuda:0")
+        task = synthetic.make_task_on_device(0, 5, 5, 8, 200, S, 1, "cuda:0")
         r = {}
-        proto = _model(name, False, "proto", bf16)
+        proto = _model(name, False, "proto", bf16, S)
         run = _task_fn(proto, task)
         r["proto_ms"] = round(_time(run, a.steps, a.warmup), 3)
         r["query_frames_per_s"] = round(200.0 / (r["proto_ms"] / 2) * 1e3, 1)  # (support and query passes are the same size)
@@ -394,11 +406,11 @@ def main(argv=None):
         tf = g["flops"] / g["ms"] / 1e9 if g["ms"] else 0.0
         r["gemm_tflops"] = round(tf, 2)
         r["gemm_fraction_of_peak"] = round(tf / peak, 3)
-        macs = proto.feature_extractor.macs_per_frame(224, 224)
+        macs = proto.feature_extractor.macs_per_frame(S, S)
         r["task_tflop"] = round(2 * macs * 400 / 1e12, 3)
         r["task_floor_ms"] = round(2 * macs * 400 / (PEAK_TF * 1e12) * 1e3, 2)
         del proto
-        cnaps = _model(name, True, "versa", bf16)
+        cnaps = _model(name, True, "versa", bf16, S)
         r["cnaps_ms"] = round(_time(_task_fn(cnaps, task), a.steps, a.warmup), 3)
         del cnaps
         r["torch_linear_m10000"] = _torch_linear(384 if name.startswith("vit_s_") else 768, a.steps, a.warmup)
